@@ -2,6 +2,8 @@
 """Benchmark of the selected-branch attention hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W        (N>1 without WORLD_SIZE: bench.py starts the N ranks itself)
+    python bench.py ... --dump-outputs DIR               (also write what the last timed step returned, as DIR/<name>.npy)
+    python bench.py ... --full                           (also every figure below: runs of their own beside the timed steps)
 
 A "step" = one pass of the hot path over one batch of synthetic input for one layer:
     Q,K_cmp -> p_grp (softmax scores, Eq.9, Eq.10) -> deterministic top-n ranges -> selection attention
@@ -9,11 +11,18 @@ A "step" = one pass of the hot path over one batch of synthetic input for one la
 on the m7c_125m shape (dim 768: 12 heads, G=2, h=6, d_k=d_v=64; l=32 d=16 l'=64 n=16) at S=65536 (north_star's target
 length, BASELINE.json configs[3]), bf16, B=16 sequences per GPU: K/V = 512 MiB, twice the Infinity Cache, so the inputs
 really live in HBM.  Inputs are resident in HBM before the timed region.  (--seq/--batch select the other BASELINE shapes;
-S=4096 B=8, S=16384 and S=65536 B=1 are reported under `extra`.)
+S=4096 B=8, S=16384 and S=65536 B=1 are reported under `extra` with --full.)
 Multi-GPU: the batch x group axis is sharded, every rank runs its own B sequences, no data-path collective exists on this
 path (weak scaling); time = max over ranks.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints one JSON line: metric, value (tok/s), unit, higher_is_better, dtype,
+ms_per_step (wall time of the K steps / K), the workload, the per-rank step times and `library` (path and sha256 of the
+libnsa_sel_hip.so that ran; NSA_HIP_LIB can point a measurement at an A/B build).  --dump-outputs DIR writes the
+ranges and the attention output O of the last timed step on a fixed, seeded sample of query rows (see dump_outputs); the inputs are seeded,
+so two builds run with the same arguments can be compared output for output.
+
+With --full the JSON line also carries (--full --no-extra: the per-stage times and rooflines, without cpu_baseline and extra)
+  stages_ms        per-launch HIP-event medians of the step's kernels, each timed alone
   roofline         dominant kernel of the step (the selection-attention launches; the step is scores + select in one launch, then the attention
                    and the merge launch of its key-split form from 32k keys on).  Top level = the roof SURVEY 8(d) names for the timed (prefill)
                    form: in-block QK^T + PV flops against the dense bf16 MFMA peak, a fraction <= 1 (qk_frac = the QK^T half).  The
@@ -28,7 +37,6 @@ The JSON line also carries
                    beside it.  Top level = the S = 65536 configuration with the highest cold fraction; every shape is in `extra`.
   cpu_baseline     the CPU oracle (a port of the reference path, validated against the reference) timed on this node's host
                    cores on a bounded sample of the same workload
-  library          path and sha256 of the libnsa_sel_hip.so that ran (NSA_HIP_LIB can point a measurement at an A/B build)
   extra            decode tok/s (cold) and prefill ms at S in {4k,16k,64k} of the hot path, MFMA TFLOP/s of the attention kernel,
                    selection backward with its roofline, the sliding/compressed branch kernel, and the whole NSAAttention layer (native path)
 """
@@ -70,6 +78,24 @@ def hot_path(nv, meta, Q, Kc, K, V, S):
     # ... then the selection attention over the ranges (they are an output of the path)
     with torch.no_grad():
         return ranges, nv.selection_attention_hip(Q, K, V, ranges)
+
+
+DUMP_ROWS = 8192  # query rows --dump-outputs keeps: 24 MiB of O + 4 MiB of ranges at the m7c shape (all rows of the headline: 3.4 GB)
+
+
+def dump_outputs(path, ranges, O):
+    """--dump-outputs: what one step of the hot path returns to its caller -- the ranges (B, S, G, n, 2) and the attention output
+    O (B, S, G, h, D) -- on DUMP_ROWS (b, t) query rows drawn with a fixed seed, written as path/<name>.npy:
+    rows (flat index b * S + t, float64), ranges (float64, exact), O (float32, exact from bf16).  The sample depends on B * S only."""
+    os.makedirs(path, exist_ok=True)
+    BS = O.shape[0] * O.shape[1]
+    rows = np.sort(np.random.default_rng(0).choice(BS, min(DUMP_ROWS, BS), replace=False))
+    idx = torch.from_numpy(rows).to(O.device)
+    arrays = {"rows": rows.astype(np.float64),
+              "ranges": ranges.reshape(BS, *ranges.shape[2:])[idx].double().cpu().numpy(),
+              "O": O.reshape(BS, *O.shape[2:])[idx].float().cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def time_events(fn, iters, warm=2):
@@ -670,7 +696,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=None, help="sequences per GPU (default 16 at S=65536, 8 otherwise)")
     ap.add_argument("--seq", type=int, default=65536)
-    ap.add_argument("--no-extra", action="store_true", help="skip the decode / 4k / 16k extras and the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the per-stage times, the rooflines, the decode / 4k / 16k / band / layer / model "
+                         "extras and the CPU baseline (each in runs of its own) and put them into the JSON line")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the decode / 4k / 16k extras and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the ranges and O the last timed step returned (a fixed, seeded sample of rows) as DIR/<name>.npy")
     ap.add_argument("--train", action="store_true",
                     help="instead of the hot path: forward+backward of the whole NSAAttention layer under DistributedDataParallel "
                          "(BASELINE config 5: gradient all-reduce over RCCL/xGMI, batch sharded over the ranks)")
@@ -682,6 +713,10 @@ def main():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only with --dry)")
     ap.add_argument("--dry", action="store_true", help="CPU rehearsal of the multi-rank plumbing (no GPU, no kernels, no measurement)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.train or args.train_model or args.dry):
+        ap.error("--dump-outputs writes the outputs of the hot path; --train, --train-model and --dry do not run it")
     if args.batch is None:
         args.batch = 16 if (args.seq >= 65536 and not (args.train or args.train_model)) else 8
         if args.train or args.train_model:
@@ -731,7 +766,8 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        hot_path(nv, meta, Q, Kc, K, V, S)
+        last = None  # the previous step's outputs go back to the allocator first: every step reuses the same blocks
+        last = hot_path(nv, meta, Q, Kc, K, V, S)
     barrier()
     elapsed = time.perf_counter() - t0
     ranks = rank_report(dist, world, elapsed, args.steps, device)
@@ -756,8 +792,11 @@ def main():
     from nsa_vibe_amd import _lib as _nsa_lib
 
     out["library"] = _nsa_lib.loaded_library()  # which build of libnsa_sel_hip.so ran (NSA_HIP_LIB can point at an A/B build: never the product figure)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, *last)
+    del last
     refused = None
-    if rank == 0:
+    if rank == 0 and args.full:
         t_sc, t_sel, t_att, t_sa, Lsum, Lmean, n_tiles, t_scsel = stage_times(nv, meta, Q, Kc, K, V, S, max(5, args.steps // 2))
         gathered = n_tiles * BLK_KEYS * (D + D) * 2
         alg_bytes = Lsum * (D + D) * 2  # L_row * (Dk+Dv) * sizeof(bf16), K/V counted once per group
@@ -860,6 +899,7 @@ def main():
                 extra["error"] = repr(e)
             out["extra"] = extra
             out["cpu_baseline"] = cpu_baseline(S, B)
+    if rank == 0:
         if refused is None:
             print(json.dumps(out))
         else:

@@ -7,6 +7,6 @@ for v in base extra base extra; do
   echo "VARIANT $v"
   timeout -k 10 120 python tools/bench_band.py 1 65536
   timeout -k 10 120 python tools/bench_band.py 8 4096
-  timeout -k 10 200 python bench.py --no-extra --steps 20 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('hot', d['ms_per_step'], d['stages_ms'])"
+  timeout -k 10 200 python bench.py --full --no-extra --steps 20 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('hot', d['ms_per_step'], d['stages_ms'])"
   timeout -k 10 120 python tools/bench_bwd.py 8 4096 | head -1
 done
