@@ -257,6 +257,19 @@ NSA_API size_t nsa_layer_prefill_workspace(const nsa_layer_desc *L, int B, int S
 NSA_API int nsa_layer_prefill(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *proj, int S, int selector,
                       const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out,
                       int out_width, void *O_mix, float *gates_out, void *workspace, size_t workspace_bytes, void *stream);
+/* Extend: S new tokens at positions t0 .. t0 + S - 1 onto caches that hold t0 tokens (t0 = 0: an empty cache), between the two big GEMMs in
+ * one call, with the semantics of S decode steps (the next turn of a chat, a chunk of a chunked prefill, k draft tokens to verify): proj
+ * [B,S,NQ+3GDk+3GDv] -> RoPE + append at t0 -> compressed tokens n_cmp(t0 - 1) <= j < n_cmp(t0 + S - 1) on the absolute schedule ->
+ * DECODE-normalised scores (nsa_sel_scores_rows, q0 = t0, norm = 1) + sequential top-n at t (forced init and local blocks) -> selection
+ * attention over K_sel[:t + 1] -> sliding and compressed branches at t -> gates + combine -> O_mix [B,S,G*h*Dv].  Caches, ranges and outputs
+ * are those of S nsa_layer_decode_step calls up to the rounding of the different kernel forms; unlike nsa_layer_prefill (whose rows normalise
+ * over every compressed token of the prompt) the result does not depend on how a prompt is split into chunks.  ranges_out [B,S,G,n_sel,2],
+ * gates_out [B,S,G,3] fp32 nullable.  csc_* / S_sel: Eq.9 map of the metadata covering t0 + S tokens.  The workspace grows with the chunk
+ * (p_grp is B*S*G*S_sel floats), not with the context. */
+NSA_API size_t nsa_layer_extend_workspace(const nsa_layer_desc *L, int B, int S, int t0, int S_sel);
+NSA_API int nsa_layer_extend(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *proj, int t0, int S, const int32_t *csc_ptr,
+                     const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out, void *O_mix, float *gates_out,
+                     void *workspace, size_t workspace_bytes, void *stream);
 /* One decode step of the whole layer in one call (nsa_attention.py:509-830, decode branch): x [B,dim] is the new token at
  * position t (= tokens already cached); appends it to the caches, emits a compressed token when due, runs the three branches,
  * the gate and the output projection -> y [B,dim].  csc_* / S_sel: the Eq.9 map of the block metadata covering t
@@ -312,6 +325,23 @@ NSA_API int nsa_sel_scores(const void *Q, const void *K_cmp, float *p_grp, int B
                    const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel,
                    int l, int d, int l_sel, int causal_skip, int variant /* 0 auto, 1 generic, 2 MFMA, 3 decode */,
                    int dtype, float scale, void *workspace, size_t workspace_bytes, void *stream);
+/* The same scorer for query rows at absolute positions (a chunk of a chunked prefill, an extend of a filled cache, speculative-verify rows):
+ *   q0   absolute position of query row 0: row (b,s,g) sits at token t = q0 + s; causal_skip counts blocks from t.
+ *   norm 0 = softmax over all S_cmp columns (nsa_sel_scores, q0 = 0: the same kernels and bits);
+ *        1 = DECODE normalisation: row t normalises over its own n_cmp(t) = (t + 1 < l) ? 0 : (t + 1 - l) / d + 1 columns (clamped to
+ *            S_cmp), the compressed tokens a decode step at t sees (nsa/core/nsa_attention.py:651); columns c >= n_cmp(t) contribute nothing to
+ *            Eq.9 / 10.  This deliberately differs from the one-shot prefill, whose rows normalise over every compressed token of the prompt.
+ *   With norm = 1 every route bounds its sweeps by the rows it holds (the first sweep becomes triangular), the decode-shaped pair is taken only
+ *   for chunks of fewer than 64 rows, and a row's p_grp bits do not depend on the chunk it sits in when chunk boundaries are multiples of 64.
+ *   Results are bitwise reproducible run to run.  workspace: nsa_sel_scores_rows_workspace(same shape, variant, norm) bytes.
+ * Note for nsa_sel_scores / nsa_sel_scores_select: their causal_skip counts blocks from row 0, so rows that are not at tokens 0 .. S - 1 need
+ * causal_skip = 0 there (or these entry points). */
+NSA_API size_t nsa_sel_scores_rows_workspace(int B, int S, int G, int h, int Dk, int S_cmp, int S_sel, int l, int d, int l_sel, int dtype,
+                                     int variant, int norm);
+NSA_API int nsa_sel_scores_rows(const void *Q, const void *K_cmp, float *p_grp, int B, int S, int G, int h, int Dk, int S_cmp,
+                        int64_t kc_stride_b, int64_t kc_stride_g, int64_t kc_stride_s, const int32_t *csc_ptr, const int32_t *csc_rows,
+                        const float *csc_vals, int S_sel, int l, int d, int l_sel, int causal_skip, int variant, int dtype, float scale,
+                        int q0, int norm, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * Deterministic top-n + forced blocks + range merge.
@@ -346,6 +376,13 @@ NSA_API int nsa_sel_scores_select(const void *Q, const void *K_cmp, float *p_grp
                           const float *csc_vals, int S_sel, int l, int d, int l_sel, int causal_skip, int dtype, float scale, int t0,
                           int n_top, int force_init, int force_local, int mode, int S_total, int32_t *ranges_out, int out_width,
                           void *workspace, size_t workspace_bytes, void *stream);
+/* nsa_sel_scores_select with the q0 / norm of nsa_sel_scores_rows (scorer rows at q0 + s; t0 stays the selector's token of row 0, normally
+ * t0 = q0).  workspace: the larger of nsa_sel_scores_rows_workspace(..., variant 0, norm) and (..., variant 1, norm) bytes. */
+NSA_API int nsa_sel_scores_select_rows(const void *Q, const void *K_cmp, float *p_grp, int B, int S, int G, int h, int Dk, int S_cmp,
+                               int64_t kc_stride_b, int64_t kc_stride_g, int64_t kc_stride_s, const int32_t *csc_ptr, const int32_t *csc_rows,
+                               const float *csc_vals, int S_sel, int l, int d, int l_sel, int causal_skip, int dtype, float scale, int t0,
+                               int n_top, int force_init, int force_local, int mode, int S_total, int32_t *ranges_out, int out_width, int q0,
+                               int norm, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * Top-n selection + selection attention in one call (prefill): the arguments of nsa_select_topn_ranges followed by those of

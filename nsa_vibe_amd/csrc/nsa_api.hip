@@ -73,18 +73,20 @@ int batched_width(int, int, int, int, int, int);
 int launch_map_pcmp(const float *, int64_t, int, int, const int32_t *, const int32_t *, const float *, int, float *,
                     float *, hipStream_t);
 int launch_pcmp(const void *, const void *, float *, int64_t, int64_t, int, int, int, int, int, int64_t, int64_t,
-                int64_t, int, float, hipStream_t);
+                int64_t, int, float, hipStream_t, int q0 = 0, int norm = 0, int l = 1, int d = 1);
 size_t scores_workspace(int64_t, int, int);
 int launch_sel_scores(const void *, const void *, float *, int, int, int, int, int, int, int64_t, int64_t, int64_t,
-                      const int32_t *, const int32_t *, const float *, int, int, float, void *, size_t, hipStream_t);
+                      const int32_t *, const int32_t *, const float *, int, int, float, void *, size_t, hipStream_t, int q0 = 0, int norm = 0,
+                      int l = 1, int d = 1);
 
 constexpr int64_t DECODE_MAX_ROWS = 1024;  // rows (B*S*G) up to which the decode-shaped scorer is used
 size_t decode_scores_workspace(int64_t, int, int);
 int launch_decode_scores(const void *, const void *, float *, int, int, int, int, int, int, int64_t, int64_t, int64_t,
-                         const int32_t *, const int32_t *, const float *, int, int, float, void *, size_t, hipStream_t);
+                         const int32_t *, const int32_t *, const float *, int, int, float, void *, size_t, hipStream_t, int q0 = 0,
+                         int norm = 0, int l = 1, int d = 1);
 bool scores_mfma_supported(int, int, int, int, int, int);
 int launch_sel_scores_mfma(const void *, const void *, float *, int, int, int, int, int, int, int64_t, int64_t, int64_t, int,
-                           int, int, float, int, hipStream_t, const SelectParams *, int *);
+                           int, int, float, int, hipStream_t, const SelectParams *, int *, int q0 = 0, int norm = 0, int l = 1);
 
 int launch_sel_first_key(const void *, const int32_t *, void *, int64_t, int, int, int, int, int, int, int64_t, int64_t, int64_t, int,
                          hipStream_t);
@@ -506,37 +508,48 @@ int nsa_pcmp_all(const void *Q, const void *K_cmp, float *p_cmp, int B, int S, i
                        (hipStream_t)stream);
 }
 
-// route of nsa_sel_scores for (shape, dtype, geometry, variant): 1 generic, 2 MFMA (prefill), 3 decode-shaped
-static int scores_route(int B, int S, int G, int h, int Dk, int S_cmp, int S_sel, int l, int d, int l_sel, int dtype, int variant) {
+// route of nsa_sel_scores for (shape, dtype, geometry, variant): 1 generic, 2 MFMA (prefill), 3 decode-shaped.  norm = 1 (decode-normalised rows
+// of an extend): the decode-shaped pair only for chunks of fewer than 64 rows, so that chunks whose boundaries are multiples of 64 all take
+// the same (prefill) route and a row's scores do not depend on the chunk it sits in
+static int scores_route(int B, int S, int G, int h, int Dk, int S_cmp, int S_sel, int l, int d, int l_sel, int dtype, int variant,
+                        int norm = 0) {
     const int64_t R = (int64_t)B * S * G;
     if (variant != 0) return variant;
-    if (R > 0 && S_cmp >= 1 && S_sel > 0 && R <= DECODE_MAX_ROWS && h <= 64 && (size_t)h * Dk * 4 <= 64 * 1024) return 3;
-    if (scores_mfma_supported(dtype, h, Dk, l, d, l_sel) && S_cmp >= 1 && R > 0 && S_sel > 0 && (int64_t)B * G <= 65535) return 2;
+    const bool mfma = scores_mfma_supported(dtype, h, Dk, l, d, l_sel) && S_cmp >= 1 && R > 0 && S_sel > 0 && (int64_t)B * G <= 65535;
+    if (R > 0 && S_cmp >= 1 && S_sel > 0 && R <= DECODE_MAX_ROWS && h <= 64 && (size_t)h * Dk * 4 <= 64 * 1024 && !(norm && S >= 64)) return 3;
+    if (mfma) return 2;
     return 1;
 }
 
-size_t nsa_sel_scores_workspace(int B, int S, int G, int h, int Dk, int S_cmp, int S_sel, int l, int d, int l_sel, int dtype,
-                                int variant) {
+size_t nsa_sel_scores_rows_workspace(int B, int S, int G, int h, int Dk, int S_cmp, int S_sel, int l, int d, int l_sel, int dtype,
+                                     int variant, int norm) {
     const int64_t R = (int64_t)B * S * G;
-    switch (scores_route(B, S, G, h, Dk, S_cmp, S_sel, l, d, l_sel, dtype, variant)) {
+    switch (scores_route(B, S, G, h, Dk, S_cmp, S_sel, l, d, l_sel, dtype, variant, norm)) {
         case 2: return 0;
         case 3: return decode_scores_workspace(R, h, S_cmp);
         default: return S_cmp > 0 ? scores_workspace(R, h, S_cmp) : 0;
     }
 }
 
-int nsa_sel_scores(const void *Q, const void *K_cmp, float *p_grp, int B, int S, int G, int h, int Dk, int S_cmp,
-                   int64_t csb, int64_t csg, int64_t css, const int32_t *csc_ptr, const int32_t *csc_rows,
-                   const float *csc_vals, int S_sel, int l, int d, int l_sel, int causal_skip, int variant, int dtype,
-                   float scale, void *workspace, size_t workspace_bytes, void *stream) {
+size_t nsa_sel_scores_workspace(int B, int S, int G, int h, int Dk, int S_cmp, int S_sel, int l, int d, int l_sel, int dtype,
+                                int variant) {
+    return nsa_sel_scores_rows_workspace(B, S, G, h, Dk, S_cmp, S_sel, l, d, l_sel, dtype, variant, 0);
+}
+
+int nsa_sel_scores_rows(const void *Q, const void *K_cmp, float *p_grp, int B, int S, int G, int h, int Dk, int S_cmp,
+                        int64_t csb, int64_t csg, int64_t css, const int32_t *csc_ptr, const int32_t *csc_rows,
+                        const float *csc_vals, int S_sel, int l, int d, int l_sel, int causal_skip, int variant, int dtype,
+                        float scale, int q0, int norm, void *workspace, size_t workspace_bytes, void *stream) {
     NSA_CHECK_ARG(dtype_ok(dtype), "sel_scores: unknown dtype %d", dtype);
     NSA_CHECK_ARG(B >= 0 && S >= 0 && G >= 1 && h >= 1, "sel_scores: bad sizes");
     NSA_CHECK_ARG(variant >= 0 && variant <= 3, "sel_scores: unknown variant %d", variant);
+    NSA_CHECK_ARG(q0 >= 0 && (norm == 0 || norm == 1), "sel_scores: bad q0 / norm");
+    NSA_CHECK_ARG(norm == 0 || (l >= 1 && d >= 1), "sel_scores: norm = 1 needs the block geometry l, d");
     if (scale <= 0.f) scale = 1.0f / sqrtf((float)Dk);
-    const int route = scores_route(B, S, G, h, Dk, S_cmp, S_sel, l, d, l_sel, dtype, variant);
+    const int route = scores_route(B, S, G, h, Dk, S_cmp, S_sel, l, d, l_sel, dtype, variant, norm);
     if (route == 3 && S_cmp >= 1 && (int64_t)B * S * G > 0 && S_sel > 0)
         return launch_decode_scores(Q, K_cmp, p_grp, B, S, G, h, Dk, S_cmp, csb, csg, css, csc_ptr, csc_rows, csc_vals, S_sel, dtype,
-                                    scale, workspace, workspace_bytes, (hipStream_t)stream);
+                                    scale, workspace, workspace_bytes, (hipStream_t)stream, q0, norm, l, d);
     if (route == 2) {
         const bool ok = scores_mfma_supported(dtype, h, Dk, l, d, l_sel) && S_cmp >= 1 && (int64_t)B * S * G > 0 && S_sel > 0 &&
                         csb % 8 == 0 && csg % 8 == 0 && css % 8 == 0 && ((uintptr_t)Q % 16 == 0) && ((uintptr_t)K_cmp % 16 == 0) &&
@@ -544,25 +557,35 @@ int nsa_sel_scores(const void *Q, const void *K_cmp, float *p_grp, int B, int S,
         NSA_CHECK_ARG(ok, "sel_scores: MFMA route needs bf16/f16, Dk in {64,128}, h <= 16, l = 2d, l' = 4d and 16-byte aligned rows "
                           "(pass variant 1 for the generic route)");
         return launch_sel_scores_mfma(Q, K_cmp, p_grp, B, S, G, h, Dk, S_cmp, csb, csg, css, S_sel, d, dtype, scale, causal_skip,
-                                      (hipStream_t)stream, nullptr, nullptr);
+                                      (hipStream_t)stream, nullptr, nullptr, q0, norm, l);
     }
     return launch_sel_scores(Q, K_cmp, p_grp, B, S, G, h, Dk, S_cmp, csb, csg, css, csc_ptr, csc_rows, csc_vals, S_sel,
-                             dtype, scale, workspace, workspace_bytes, (hipStream_t)stream);
+                             dtype, scale, workspace, workspace_bytes, (hipStream_t)stream, q0, norm, l, d);
+}
+
+int nsa_sel_scores(const void *Q, const void *K_cmp, float *p_grp, int B, int S, int G, int h, int Dk, int S_cmp,
+                   int64_t csb, int64_t csg, int64_t css, const int32_t *csc_ptr, const int32_t *csc_rows,
+                   const float *csc_vals, int S_sel, int l, int d, int l_sel, int causal_skip, int variant, int dtype,
+                   float scale, void *workspace, size_t workspace_bytes, void *stream) {
+    return nsa_sel_scores_rows(Q, K_cmp, p_grp, B, S, G, h, Dk, S_cmp, csb, csg, css, csc_ptr, csc_rows, csc_vals, S_sel, l, d, l_sel,
+                               causal_skip, variant, dtype, scale, 0, 0, workspace, workspace_bytes, stream);
 }
 
 // scores + top-n ranges of every row (prefill): on the 32x32x16 scorer route the selection of a query tile runs inside the scorer launch,
 // everywhere else the scorer and the select kernel are launched back to back -- the same ranges bit for bit either way
-int nsa_sel_scores_select(const void *Q, const void *K_cmp, float *p_grp, int B, int S, int G, int h, int Dk, int S_cmp, int64_t csb, int64_t csg,
-                          int64_t css, const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel, int l, int d,
-                          int l_sel, int causal_skip, int dtype, float scale, int t0, int n_top, int force_init, int force_local, int mode,
-                          int S_total, int32_t *ranges_out, int out_width, void *workspace, size_t workspace_bytes, void *stream) {
+int nsa_sel_scores_select_rows(const void *Q, const void *K_cmp, float *p_grp, int B, int S, int G, int h, int Dk, int S_cmp, int64_t csb,
+                               int64_t csg, int64_t css, const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel, int l,
+                               int d, int l_sel, int causal_skip, int dtype, float scale, int t0, int n_top, int force_init, int force_local,
+                               int mode, int S_total, int32_t *ranges_out, int out_width, int q0, int norm, void *workspace,
+                               size_t workspace_bytes, void *stream) {
     NSA_CHECK_ARG(dtype_ok(dtype), "sel_scores_select: unknown dtype %d", dtype);
     NSA_CHECK_ARG(B >= 0 && S >= 0 && G >= 1 && h >= 1 && out_width >= 0, "sel_scores_select: bad sizes");
+    NSA_CHECK_ARG(q0 >= 0 && (norm == 0 || norm == 1), "sel_scores_select: bad q0 / norm");
     const int64_t R = (int64_t)B * S * G;
     if (R == 0 || out_width == 0) return NSA_OK;
     NSA_CHECK_ARG(p_grp && ranges_out, "sel_scores_select: null pointer");
     if (scale <= 0.f) scale = 1.0f / sqrtf((float)Dk);
-    const int route = scores_route(B, S, G, h, Dk, S_cmp, S_sel, l, d, l_sel, dtype, 0);
+    const int route = scores_route(B, S, G, h, Dk, S_cmp, S_sel, l, d, l_sel, dtype, 0, norm);
     const bool mfma_ok = route == 2 && S_cmp >= 1 && S_sel > 0 && csb % 8 == 0 && csg % 8 == 0 && css % 8 == 0 && ((uintptr_t)Q % 16 == 0) &&
                          ((uintptr_t)K_cmp % 16 == 0) && (int64_t)B * G <= 65535;
     if (mfma_ok) {
@@ -571,16 +594,25 @@ int nsa_sel_scores_select(const void *Q, const void *K_cmp, float *p_grp, int B,
         if (int rc = select_params_fill(&SP, S_sel, l_sel, n_top, force_init, force_local, mode, S_total, out_width)) return rc;
         int done = 0;
         if (int rc = launch_sel_scores_mfma(Q, K_cmp, p_grp, B, S, G, h, Dk, S_cmp, csb, csg, css, S_sel, d, dtype, scale, causal_skip,
-                                            (hipStream_t)stream, &SP, &done))
+                                            (hipStream_t)stream, &SP, &done, q0, norm, l))
             return rc;
         if (done) return NSA_OK;
-    } else if (int rc = nsa_sel_scores(Q, K_cmp, p_grp, B, S, G, h, Dk, S_cmp, csb, csg, css, csc_ptr, csc_rows, csc_vals, S_sel, l, d, l_sel,
-                                       causal_skip, route == 2 ? 1 : 0 /* rows the MFMA route cannot take: the generic one */, dtype, scale,
-                                       workspace, workspace_bytes, stream)) {
+    } else if (int rc = nsa_sel_scores_rows(Q, K_cmp, p_grp, B, S, G, h, Dk, S_cmp, csb, csg, css, csc_ptr, csc_rows, csc_vals, S_sel, l, d,
+                                            l_sel, causal_skip, route == 2 ? 1 : route /* rows the MFMA route cannot take: the generic one */,
+                                            dtype, scale, q0, norm, workspace, workspace_bytes, stream)) {
         return rc;
     }
     return nsa_select_topn_ranges(p_grp, R, S, G, t0, nullptr, S_sel, l_sel, n_top, force_init, force_local, mode, S_total, ranges_out,
                                   out_width, stream);
+}
+
+int nsa_sel_scores_select(const void *Q, const void *K_cmp, float *p_grp, int B, int S, int G, int h, int Dk, int S_cmp, int64_t csb, int64_t csg,
+                          int64_t css, const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel, int l, int d,
+                          int l_sel, int causal_skip, int dtype, float scale, int t0, int n_top, int force_init, int force_local, int mode,
+                          int S_total, int32_t *ranges_out, int out_width, void *workspace, size_t workspace_bytes, void *stream) {
+    return nsa_sel_scores_select_rows(Q, K_cmp, p_grp, B, S, G, h, Dk, S_cmp, csb, csg, css, csc_ptr, csc_rows, csc_vals, S_sel, l, d, l_sel,
+                                      causal_skip, dtype, scale, t0, n_top, force_init, force_local, mode, S_total, ranges_out, out_width, 0, 0,
+                                      workspace, workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------ selection

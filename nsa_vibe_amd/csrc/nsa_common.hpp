@@ -77,6 +77,13 @@ constexpr int WAVE = 64;
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float LN2 = 0.6931471805599453f;
 
+// compressed tokens a decode step at absolute position t sees (emission schedule of the l / d pooling), clamped to S_cmp:
+// n_cmp(t) = (t + 1 < l) ? 0 : (t + 1 - l) / d + 1.  Column c is visible at t exactly when c d + l <= t + 1.
+__host__ __device__ __forceinline__ int ncmp_at(int t, int l, int d, int S_cmp) {
+    const int n = (t + 1 < l) ? 0 : (t + 1 - l) / d + 1;
+    return n < S_cmp ? n : S_cmp;
+}
+
 // ---- element traits --------------------------------------------------------------------
 template <typename T>
 struct Elt;

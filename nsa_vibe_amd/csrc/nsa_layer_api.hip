@@ -232,6 +232,85 @@ int nsa_layer_prefill(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void
     return nsa_gate_combine(L, Q, Ocmp, Osel, Owin, O_mix, gates_out, (int64_t)B * S * G, stream);
 }
 
+// extend workspace: Q | p_grp | O_cmp | O_sel | O_win | scorer scratch | attention scratch | band scratch (all sized by the chunk's S rows;
+// only the attention's key-split records and the scorer's columns grow with the context t0 + S)
+static PrefillWs extend_ws(const nsa_layer_desc *L, int B, int S, int t0, int S_sel) {
+    PrefillWs w;
+    const size_t e = esize(L->dtype);
+    const size_t NQ = (size_t)L->G * L->h * L->Dk, NO = (size_t)L->G * L->h * L->Dv;
+    const int S_kv = t0 + S;
+    const int n_cmp = S_kv < L->l ? 0 : (S_kv - L->l) / L->d + 1;
+    size_t o = 0;
+    w.q = o; o += up256((size_t)B * S * NQ * e);
+    w.pgrp = o; o += up256(sizeof(float) * (size_t)B * S * L->G * (size_t)(S_sel > 0 ? S_sel : 1));
+    w.ocmp = o; o += up256((size_t)B * S * NO * e);
+    w.osel = o; o += up256((size_t)B * S * NO * e);
+    w.owin = o; o += up256((size_t)B * S * NO * e);
+    w.sc_bytes = nsa_sel_scores_rows_workspace(B, S, L->G, L->h, L->Dk, n_cmp, S_sel, L->l, L->d, L->l_sel, L->dtype, 0, 1);
+    const size_t sc1 = nsa_sel_scores_rows_workspace(B, S, L->G, L->h, L->Dk, n_cmp, S_sel, L->l, L->d, L->l_sel, L->dtype, 1, 1);
+    if (sc1 > w.sc_bytes) w.sc_bytes = sc1;  // the generic route may be taken for unaligned inputs
+    w.sc = o; o += up256(w.sc_bytes);
+    w.att_bytes = nsa_sel_attn_fwd_workspace_kv(B, S, L->G, L->h, L->Dk, L->Dv, S_kv, L->n_sel, L->dtype);
+    w.att = o; o += up256(w.att_bytes);
+    w.band_bytes = nsa_band_attn_fwd_workspace(B, S, L->G, L->h, L->Dk, L->Dv, L->dtype);
+    w.band = o; o += up256(w.band_bytes);
+    w.total = o;
+    return w;
+}
+
+size_t nsa_layer_extend_workspace(const nsa_layer_desc *L, int B, int S, int t0, int S_sel) {
+    if (!L || !dt_ok(L->dtype) || B < 1 || S < 1 || t0 < 0) return 0;
+    return extend_ws(L, B, S, t0, S_sel).total;
+}
+
+int nsa_layer_extend(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *proj, int t0, int S, const int32_t *csc_ptr,
+                     const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out, void *O_mix, float *gates_out,
+                     void *workspace, size_t workspace_bytes, void *stream) {
+    if (int rc = check_layer(L, "layer_extend")) return rc;
+    if (int rc = check_kv(kv, "layer_extend")) return rc;
+    NSA_CHECK_ARG(proj && O_mix && ranges_out, "layer_extend: null pointer");
+    NSA_CHECK_ARG(t0 >= 0 && S >= 1 && (int64_t)t0 + S <= kv->S_max, "layer_extend: tokens [%d,%d) exceed the cache capacity %d", t0, t0 + S,
+                  kv->S_max);
+    NSA_CHECK_ARG(S_sel >= 1 && (int64_t)S_sel * L->l_sel >= (int64_t)t0 + S, "layer_extend: block metadata (S_sel=%d) does not cover %d tokens",
+                  S_sel, t0 + S);
+    const int B = kv->B, G = L->G, h = L->h, Dk = L->Dk, Dv = L->Dv, dt = L->dtype;
+    const int S_kv = t0 + S;
+    const PrefillWs W = extend_ws(L, B, S, t0, S_sel);
+    NSA_CHECK_ARG(workspace && ((uintptr_t)workspace % 256 == 0) && workspace_bytes >= W.total,
+                  "layer_extend: workspace missing, misaligned or too small");
+    unsigned char *ws = (unsigned char *)workspace;
+    void *Q = ws + W.q, *Ocmp = ws + W.ocmp, *Osel = ws + W.osel, *Owin = ws + W.owin;
+    float *p_grp = (float *)(ws + W.pgrp);
+    // compressed tokens emitted before the chunk (n_cmp(t0 - 1)) and after it (n_cmp(t0 + S - 1)), on the absolute schedule
+    const int n0 = t0 < L->l ? 0 : (t0 - L->l) / L->d + 1;
+    const int n1 = S_kv < L->l ? 0 : (S_kv - L->l) / L->d + 1;
+    NSA_CHECK_ARG(n1 <= kv->n_cmp_max, "layer_extend: compressed cache too small");
+    if (int rc = nsa_rope_cache_append(L, kv, proj, Q, S, t0, stream)) return rc;
+    if (n1 > n0)
+        if (int rc = nsa_cmp_pool_append(L, kv, n0, n1, stream)) return rc;
+    const int64_t ksb = (int64_t)G * kv->S_max * Dk, ksg = (int64_t)kv->S_max * Dk;
+    const int64_t vsb = (int64_t)G * kv->S_max * Dv, vsg = (int64_t)kv->S_max * Dv;
+    const int64_t kcb = (int64_t)G * kv->n_cmp_max * Dk, kcg = (int64_t)kv->n_cmp_max * Dk;
+    const int64_t vcb = (int64_t)G * kv->n_cmp_max * Dv, vcg = (int64_t)kv->n_cmp_max * Dv;
+    const float scale = 1.0f / sqrtf((float)Dk);
+    // selected branch: decode-normalised scores of rows t0 .. t0 + S - 1 + sequential top-n at their tokens, then the attention over K_sel[:t + 1]
+    if (int rc = nsa_sel_scores_select_rows(Q, kv->K_cmp, p_grp, B, S, G, h, Dk, n1, kcb, kcg, Dk, csc_ptr, csc_rows, csc_vals, S_sel, L->l,
+                                            L->d, L->l_sel, 2 /* skipped blocks stay unwritten: only the selector reads p_grp */, dt, scale, t0,
+                                            L->n_sel, 1, 2, NSA_SEL_SEQUENTIAL, S, ranges_out, L->n_sel, t0, 1, ws + W.sc, W.sc_bytes, stream))
+        return rc;
+    if (int rc = nsa_sel_attn_fwd(Q, kv->K_sel, kv->V_sel, ranges_out, Osel, nullptr, B, S, G, h, Dk, Dv, S_kv, L->n_sel, ksb, ksg, Dk, vsb,
+                                  vsg, Dv, dt, scale, 0, ws + W.att, W.att_bytes, stream))
+        return rc;
+    // sliding and compressed branches at the chunk's absolute positions
+    if (int rc = nsa_band_attn_fwd(Q, kv->K_win, kv->V_win, Owin, nullptr, B, S, G, h, Dk, Dv, S_kv, ksb, ksg, Dk, vsb, vsg, Dv, t0, 0, 1, 0,
+                                   L->w, dt, scale, 0, ws + W.band, W.band_bytes, stream))
+        return rc;
+    if (int rc = nsa_band_attn_fwd(Q, kv->K_cmp, kv->V_cmp, Ocmp, nullptr, B, S, G, h, Dk, Dv, n1, kcb, kcg, Dk, vcb, vcg, Dv, t0, L->l, L->d,
+                                   1, 1 << 30, dt, scale, 0, ws + W.band, W.band_bytes, stream))
+        return rc;
+    return nsa_gate_combine(L, Q, Ocmp, Osel, Owin, O_mix, gates_out, (int64_t)B * S * G, stream);
+}
+
 // workspace: proj | Q | O_cmp | O_sel | O_win | O_mix | ranges | selection-decode scratch | band scratch
 struct DecodeWs {
     size_t proj, q, ocmp, osel, owin, omix, ranges, gates, sel, band, band2, total, sel_bytes, band_bytes;

@@ -75,6 +75,7 @@ struct PcmpParams {
     int S, G, h, Dk, S_cmp;
     int64_t csb, csg, css;
     float scale;
+    int q0, norm, l, d;  // norm = 1: row (b,s,g) at token q0 + s normalises over its own n_cmp(q0 + s) columns, the rest are written as 0
 };
 
 template <typename T>
@@ -96,8 +97,9 @@ __global__ __launch_bounds__(256) void pcmp_kernel(PcmpParams P) {
     wave_lds_fence();
     const T *kb = (const T *)P.Kc + (int64_t)b * P.csb + (int64_t)g * P.csg;
     float *out = P.p_cmp + (lrow * P.h + hh) * (int64_t)P.S_cmp;
+    const int nc = P.norm ? ncmp_at(P.q0 + (int)((row / P.G) % P.S), P.l, P.d, P.S_cmp) : P.S_cmp;
     float mx = -INFINITY;
-    for (int c = lane; c < P.S_cmp; c += 64) {
+    for (int c = lane; c < nc; c += 64) {
         const T *kr = kb + (int64_t)c * P.css;
         float acc = 0.f;
         for (int e = 0; e < Dk; ++e) acc = fmaf(qs[e], Elt<T>::to_f(kr[e]), acc);
@@ -107,20 +109,22 @@ __global__ __launch_bounds__(256) void pcmp_kernel(PcmpParams P) {
     }
     mx = wave_max(mx);
     float sum = 0.f;
-    for (int c = lane; c < P.S_cmp; c += 64) {
+    for (int c = lane; c < nc; c += 64) {
         const float e = expf(out[c] - mx);
         out[c] = e;
         sum += e;
     }
     sum = wave_sum(sum);
-    for (int c = lane; c < P.S_cmp; c += 64) out[c] = out[c] / sum;
+    for (int c = lane; c < nc; c += 64) out[c] = out[c] / sum;
+    for (int c = nc + lane; c < P.S_cmp; c += 64) out[c] = 0.f;  // columns not emitted yet at the row's token (the map adds them as +0)
 }
 
 int launch_pcmp(const void *Q, const void *Kc, float *p_cmp, int64_t row0, int64_t nrows, int S, int G, int h,
-                int Dk, int S_cmp, int64_t csb, int64_t csg, int64_t css, int dtype, float scale, hipStream_t st) {
+                int Dk, int S_cmp, int64_t csb, int64_t csg, int64_t css, int dtype, float scale, hipStream_t st,
+                int q0, int norm, int l, int d) {
     NSA_CHECK_ARG(h >= 1 && Dk >= 1 && Dk <= 4096, "pcmp: bad h/Dk");
     if (nrows == 0 || S_cmp == 0) return NSA_OK;
-    PcmpParams P{Q, Kc, p_cmp, row0, nrows, S, G, h, Dk, S_cmp, csb, csg, css, scale};
+    PcmpParams P{Q, Kc, p_cmp, row0, nrows, S, G, h, Dk, S_cmp, csb, csg, css, scale, q0, norm, l, d};
     const int64_t waves = nrows * h;
     const unsigned grid = (unsigned)((waves + 3) / 4);
     const size_t lds = 4 * sizeof(float) * (size_t)Dk;
@@ -154,7 +158,13 @@ struct DecodeParams {
     int64_t csb, csg, css;
     float c2;
     int stencil;  // fused decode kernel: l = 2d and l' = 4d, Eq.9 is the closed-form 5-tap stencil (no CSC loads)
+    int q0, norm, l, d;  // norm = 1 (two-kernel route only): row (b,s,g) at token q0 + s sees its own n_cmp(q0 + s) columns
 };
+
+// columns row `row` of a decode-shaped launch normalises over (all S_cmp, or its own n_cmp with norm = 1)
+__device__ __forceinline__ int dec_row_cols(const DecodeParams &P, int64_t row) {
+    return P.norm ? ncmp_at(P.q0 + (int)((row / P.G) % P.S), P.l, P.d, P.S_cmp) : P.S_cmp;
+}
 
 constexpr int DEC_HMAX = 16;
 
@@ -171,13 +181,15 @@ __global__ __launch_bounds__(64) void decode_logits_kernel(DecodeParams P) {
     const int lane = threadIdx.x;
     const int64_t row = blockIdx.y;
     const int chunk = blockIdx.x, nchunk = dec_nchunk(P.S_cmp);
+    const int nc = dec_row_cols(P, row);
+    if (chunk * 64 >= nc && chunk > 0) return;  // past the row's columns (norm = 1): kernel 2 reads no record of this chunk
     const int g = (int)(row % P.G);
     const int b = (int)(row / ((int64_t)P.G * P.S));
     const T *q = (const T *)P.Q + row * (int64_t)P.h * P.Dk;
     for (int i = lane; i < P.h * P.Dk; i += 64) qs[i] = Elt<T>::to_f(q[i]);
     wave_lds_fence();
     const int c = chunk * 64 + lane;
-    const bool valid = c < P.S_cmp;
+    const bool valid = c < nc;
     const T *kr = (const T *)P.Kc + (int64_t)b * P.csb + (int64_t)g * P.csg + (int64_t)(valid ? c : P.S_cmp - 1) * P.css;
     const bool vec = (P.Dk % EPV == 0) && (((uintptr_t)kr & 15) == 0) && ((P.css * sizeof(T)) % 16 == 0);
     for (int h0 = 0; h0 < P.h; h0 += DEC_HMAX) {
@@ -229,6 +241,8 @@ __global__ __launch_bounds__(64, 2) void decode_logits_mfma_kernel(DecodeParams 
     const int lane = threadIdx.x, rho = lane & 15, q = lane >> 4;
     const int64_t row = blockIdx.y;
     const int chunk = blockIdx.x, nchunk = dec_nchunk(P.S_cmp);
+    const int nc = dec_row_cols(P, row);
+    if (chunk * 64 >= nc && chunk > 0) return;  // past the row's columns (norm = 1): kernel 2 reads no record of this chunk
     const int g = (int)(row % P.G);
     const int b = (int)(row / ((int64_t)P.G * P.S));
     const int Dk = 32 * KSTEPS;
@@ -262,7 +276,7 @@ __global__ __launch_bounds__(64, 2) void decode_logits_mfma_kernel(DecodeParams 
             const int c = chunk * 64 + 16 * u + 4 * q + j;
             const float v = acc[u][j] * P.c2;
             x[4 * u + j] = v;
-            if (c < P.S_cmp) {
+            if (c < nc) {
                 if (rho < P.h) P.x[(row * P.h + rho) * (int64_t)P.S_cmp + c] = v;
                 m = fmaxf(m, v);
             }
@@ -274,7 +288,7 @@ __global__ __launch_bounds__(64, 2) void decode_logits_mfma_kernel(DecodeParams 
     for (int u = 0; u < 4; ++u)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            if (chunk * 64 + 16 * u + 4 * q + j < P.S_cmp) l += __builtin_amdgcn_exp2f(x[4 * u + j] - m);
+            if (chunk * 64 + 16 * u + 4 * q + j < nc) l += __builtin_amdgcn_exp2f(x[4 * u + j] - m);
     l += __shfl_xor(l, 16, 64);
     l += __shfl_xor(l, 32, 64);
     if (q == 0 && rho < P.h) {
@@ -291,15 +305,17 @@ __global__ __launch_bounds__(64) void decode_pgrp_kernel(DecodeParams P) {
     __shared__ float mlog_s[64];
     const int64_t row = blockIdx.y;
     const int lane = threadIdx.x;
-    const int nchunk = dec_nchunk(P.S_cmp);
+    const int nchunk = dec_nchunk(P.S_cmp);  // records per (row, head) in the workspace
+    const int nc = dec_row_cols(P, row);      // columns of this row (S_cmp, or n_cmp(t) with norm = 1)
+    const int nch = P.norm ? max(dec_nchunk(nc), 1) : nchunk;  // chunks holding them (chunk 0 always has a record)
     // per-head softmax statistics from the chunk records.  The kernel is latency bound (a handful of waves per decode
     // step): the loads of 8 heads are issued together, the arithmetic per head is unchanged.
     for (int h0 = 0; h0 < P.h; h0 += 8) {
-        if (nchunk <= 64) {
+        if (nch <= 64) {
             float mv[8], lv[8];
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const bool ok = h0 + i < P.h && lane < nchunk;
+                const bool ok = h0 + i < P.h && lane < nch;
                 const float *pr = P.part + (row * P.h + min(h0 + i, P.h - 1)) * (int64_t)nchunk * 2;
                 mv[i] = ok ? pr[2 * lane] : -INFINITY;
                 lv[i] = ok ? pr[2 * lane + 1] : 0.f;
@@ -308,17 +324,17 @@ __global__ __launch_bounds__(64) void decode_pgrp_kernel(DecodeParams P) {
             for (int i = 0; i < 8; ++i) {
                 if (h0 + i >= P.h) break;
                 const float m = wave_max(mv[i]);
-                const float l = wave_sum(lane < nchunk ? lv[i] * __builtin_amdgcn_exp2f(mv[i] - m) : 0.f);
+                const float l = wave_sum(lane < nch ? lv[i] * __builtin_amdgcn_exp2f(mv[i] - m) : 0.f);
                 if (lane == 0) mlog_s[h0 + i] = m + __builtin_amdgcn_logf(l);
             }
         } else {
             for (int hh = h0; hh < min(P.h, h0 + 8); ++hh) {
                 const float *pr = P.part + (row * P.h + hh) * (int64_t)nchunk * 2;
                 float m = -INFINITY;
-                for (int c = lane; c < nchunk; c += 64) m = fmaxf(m, pr[2 * c]);
+                for (int c = lane; c < nch; c += 64) m = fmaxf(m, pr[2 * c]);
                 m = wave_max(m);
                 float l = 0.f;
-                for (int c = lane; c < nchunk; c += 64) l += pr[2 * c + 1] * __builtin_amdgcn_exp2f(pr[2 * c] - m);
+                for (int c = lane; c < nch; c += 64) l += pr[2 * c + 1] * __builtin_amdgcn_exp2f(pr[2 * c] - m);
                 l = wave_sum(l);
                 if (lane == 0) mlog_s[hh] = m + __builtin_amdgcn_logf(l);
             }
@@ -337,7 +353,7 @@ __global__ __launch_bounds__(64) void decode_pgrp_kernel(DecodeParams P) {
         for (int t = 0; t < 8; ++t) {
             const bool ok = k0 + t < k1;
             const int r = ok ? P.csc_rows[k0 + t] : P.S_cmp;
-            rr[t] = r < P.S_cmp ? r : -1;
+            rr[t] = r < nc ? r : -1;
             vv[t] = ok ? P.csc_vals[k0 + t] : 0.f;
         }
         for (int h0 = 0; h0 < P.h; h0 += 4) {
@@ -366,7 +382,7 @@ __global__ __launch_bounds__(64) void decode_pgrp_kernel(DecodeParams P) {
             float acc = 0.f;
             for (int k = k0; k < k1; ++k) {
                 const int r = P.csc_rows[k];
-                if (r < P.S_cmp) acc = __fadd_rn(acc, __fmul_rn(__builtin_amdgcn_exp2f(x[r] - ml), P.csc_vals[k]));
+                if (r < nc) acc = __fadd_rn(acc, __fmul_rn(__builtin_amdgcn_exp2f(x[r] - ml), P.csc_vals[k]));
             }
             grp = __fadd_rn(grp, acc);
         }
@@ -699,13 +715,13 @@ size_t decode_scores_workspace(int64_t R, int h, int S_cmp) {
 
 int launch_decode_scores(const void *Q, const void *Kc, float *p_grp, int B, int S, int G, int h, int Dk, int S_cmp, int64_t csb,
                          int64_t csg, int64_t css, const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals,
-                         int S_sel, int dtype, float scale, void *ws, size_t ws_bytes, hipStream_t st) {
+                         int S_sel, int dtype, float scale, void *ws, size_t ws_bytes, hipStream_t st, int q0, int norm, int l, int d) {
     const int64_t R = (int64_t)B * S * G;
     NSA_CHECK_ARG(h <= 64 && Dk >= 1 && (size_t)h * Dk * 4 <= 64 * 1024, "decode scorer: h/Dk too large");
     NSA_CHECK_ARG(ws && ws_bytes >= decode_scores_workspace(R, h, S_cmp), "decode scorer: workspace too small");
     NSA_CHECK_ARG(R <= 65535, "decode scorer: too many rows");
     DecodeParams P{Q, Kc, (float *)ws, (float *)ws + (size_t)R * h * S_cmp, p_grp, csc_ptr, csc_rows, csc_vals, R, S, G, h, Dk, S_cmp,
-                   S_sel, csb, csg, css, scale * LOG2E};
+                   S_sel, csb, csg, css, scale * LOG2E, 0, q0, norm, l, d};
     const dim3 grid1((unsigned)dec_nchunk(S_cmp), (unsigned)R);
     const size_t lds = sizeof(float) * (size_t)h * Dk;
     const bool mfma = (dtype == NSA_DT_BF16 || dtype == NSA_DT_F16) && (Dk == 64 || Dk == 128) && h <= 16 && css % 8 == 0 &&
@@ -750,7 +766,7 @@ size_t scores_workspace(int64_t R, int h, int S_cmp) {
 int launch_sel_scores(const void *Q, const void *Kc, float *p_grp, int B, int S, int G, int h, int Dk, int S_cmp,
                       int64_t csb, int64_t csg, int64_t css, const int32_t *csc_ptr, const int32_t *csc_rows,
                       const float *csc_vals, int S_sel, int dtype, float scale, void *ws, size_t ws_bytes,
-                      hipStream_t st) {
+                      hipStream_t st, int q0, int norm, int l, int d) {
     const int64_t R = (int64_t)B * S * G;
     if (R == 0 || S_sel == 0) return NSA_OK;
     if (S_cmp == 0) {  // selection_scorer.py:97-98 -> zeros
@@ -762,7 +778,7 @@ int launch_sel_scores(const void *Q, const void *Kc, float *p_grp, int B, int S,
     const int64_t chunk = (int64_t)(ws_bytes / per_row);
     for (int64_t r0 = 0; r0 < R; r0 += chunk) {
         const int64_t nr = (R - r0 < chunk) ? R - r0 : chunk;
-        int rc = launch_pcmp(Q, Kc, (float *)ws, r0, nr, S, G, h, Dk, S_cmp, csb, csg, css, dtype, scale, st);
+        int rc = launch_pcmp(Q, Kc, (float *)ws, r0, nr, S, G, h, Dk, S_cmp, csb, csg, css, dtype, scale, st, q0, norm, l, d);
         if (rc) return rc;
         rc = launch_map_pcmp((const float *)ws, nr, h, S_cmp, csc_ptr, csc_rows, csc_vals, S_sel, nullptr,
                              p_grp + r0 * S_sel, st);

@@ -20,6 +20,11 @@
 // end), sweep 2 = recompute logits, normalise, stencil, head sum, store.  With causal_skip the
 // second sweep stops at the last selection block any query of the workgroup may select
 // ((j+1) l' <= t+1); blocks beyond are never read by the selector (masked to -inf there).
+// NORM (decode-normalised scores of a chunked prefill / extend, P.norm = 1): query t = q0 + s sees only the n_cmp(t) compressed tokens
+// a decode step at t sees.  Both sweeps end at the workgroup's last visible column (the first sweep becomes triangular over the
+// sequence); columns c >= n_cmp(t) are masked per lane (-inf in sweep 1, p = 0 in sweep 2) on the few tiles that reach past the wave's
+// earliest bound, so masked tiles leave a row's statistics bit for bit unchanged and a row's p_grp does not depend on which later rows
+// share its chunk (chunk boundaries at multiples of the workgroup's QW queries).
 #include "sel_scores_mfma.hpp"
 #include "sel_select_row.hpp"
 
@@ -47,7 +52,7 @@ struct MfmaS<_Float16> {
 // MFMA and VALU issue do not overlap on a SIMD (tools/ubench/issue_rates.hip: 4 MFMA + 8 FMA take 90 cycles, 67 + 31 apart), so the time of
 // this kernel is the SUM of its MFMA and VALU cycles and every unused column costs both.  Queries 2 and 5 of the eight straddle two tiles:
 // their head sum takes the tail of one tile's shifted sums and the head of the next one's (one more DPP add each).
-template <typename T, int D, int NT, int HC>
+template <typename T, int D, int NT, int HC, bool NORM>
 __global__ __launch_bounds__(256, 2) void scores_mfma_kernel(ScoresMfmaParams P) {
     constexpr bool FLAT = (HC == 6 && NT == 3);
     using M = MfmaS<T>;
@@ -97,6 +102,17 @@ __global__ __launch_bounds__(256, 2) void scores_mfma_kernel(ScoresMfmaParams P)
     }
 
     const int ntiles = (P.S_cmp + TILE_ROWS - 1) / TILE_ROWS;
+    // NORM: visible columns per lane column (n_cmp of its query; columns of absent queries take the last row's), the wave's smallest
+    // bound (its first query) and the workgroup's largest (its last query)
+    int ncl[NT];
+    int nc_wmin = P.S_cmp, nc_wgmax = P.S_cmp;
+    if constexpr (NORM) {
+#pragma unroll
+        for (int n = 0; n < NT; ++n) ncl[n] = ncmp_at(P.q0 + (tq[n] >= 0 ? tq[n] : P.S - 1), P.l, P.d_stride, P.S_cmp);
+        nc_wmin = ncmp_at(P.q0 + min(t0 + wave * QPW, P.S - 1), P.l, P.d_stride, P.S_cmp);
+        nc_wgmax = ncmp_at(P.q0 + min(t0 + QW, P.S) - 1, P.l, P.d_stride, P.S_cmp);
+    }
+    const int ntiles1 = NORM ? (nc_wgmax + TILE_ROWS - 1) / TILE_ROWS : ntiles;  // tiles of the first sweep
     // staging: thread -> (row, piece) pairs
     u32x4 stg[LD_PER_THREAD];
     // full tiles: one scalar base per tile + a lane-constant 32-bit offset (the per-lane 64-bit row arithmetic with its clamp was 16 VALU
@@ -160,12 +176,13 @@ __global__ __launch_bounds__(256, 2) void scores_mfma_kernel(ScoresMfmaParams P)
     load_tile(0);
     store_tile(0);
     __syncthreads();
-    for (int tile = 0; tile < ntiles; ++tile) {
+    for (int tile = 0; tile < ntiles1; ++tile) {
         const int buf = tile & 1;
-        if (tile + 1 < ntiles) load_tile(tile + 1);
+        if (tile + 1 < ntiles1) load_tile(tile + 1);
         f32x4 acc[4][NT];
         compute_tile(buf, acc);
         const int rows_valid = P.S_cmp - tile * TILE_ROWS;  // rows >= this are padding
+        const bool masked = NORM && (tile + 1) * TILE_ROWS > nc_wmin;  // NORM: some lane column of the wave ends inside this tile
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
             // common path: every lane keeps its own reference max and only accumulates sum(exp2(x - m)); no max, no
@@ -185,10 +202,15 @@ __global__ __launch_bounds__(256, 2) void scores_mfma_kernel(ScoresMfmaParams P)
                     sum2 += e2;
                 }
             float sum = sum2[0] + sum2[1];
-            if (__any(!(sum <= 4096.f)) || rows_valid < TILE_ROWS) {
+            if (__any(!(sum <= 4096.f)) || rows_valid < TILE_ROWS || masked) {
                 asm volatile("; sweep-1 slow path" ::: "memory");
                 int rv = rows_valid;  // (same reason as for the logits below: the 16 row masks belong to this block)
-                asm volatile("" : "+s"(rv));
+                if constexpr (NORM) {
+                    rv = min(rv, ncl[n] - tile * TILE_ROWS);  // per lane column
+                    asm volatile("" : "+v"(rv));
+                } else {
+                    asm volatile("" : "+s"(rv));
+                }
                 float v[16];
                 float mx = -INFINITY;
 #pragma unroll
@@ -215,7 +237,7 @@ __global__ __launch_bounds__(256, 2) void scores_mfma_kernel(ScoresMfmaParams P)
             }
             lrun[n] += sum;
         }
-        if (tile + 1 < ntiles) store_tile(buf ^ 1);
+        if (tile + 1 < ntiles1) store_tile(buf ^ 1);
         __syncthreads();
     }
     // merge the 4 lane groups of each column
@@ -234,9 +256,10 @@ __global__ __launch_bounds__(256, 2) void scores_mfma_kernel(ScoresMfmaParams P)
     const int l_sel = 4 * P.d_stride;
     int jlast = P.S_sel - 1;  // last selection block this workgroup has to produce
     if (P.causal_skip) {
-        const int t_last = min(t0 + QW, P.S) - 1;
+        const int t_last = P.q0 + min(t0 + QW, P.S) - 1;  // absolute position of the workgroup's last query
         jlast = min(jlast, (t_last + 1) / l_sel - 1);
     }
+    if constexpr (NORM) jlast = min(jlast, nc_wgmax / 4);  // later blocks have no visible tap (block j's first tap is column 4j - 1)
     const int tiles2 = (jlast < 0) ? 0 : min(ntiles, (4 * jlast + 3) / TILE_ROWS + 1);
     float rot_prev[NT];
 #pragma unroll
@@ -272,7 +295,15 @@ __global__ __launch_bounds__(256, 2) void scores_mfma_kernel(ScoresMfmaParams P)
                     p[k] = __builtin_amdgcn_exp2f(t2[0]);
                     p[k + 1] = __builtin_amdgcn_exp2f(t2[1]);
                 }
-                if (rows_valid < TILE_ROWS) {  // padded last tile only (wave uniform).  rv: the row masks stay inside this block (left to
+                if constexpr (NORM) {
+                    if ((tile + 1) * TILE_ROWS > nc_wmin || rows_valid < TILE_ROWS) {  // wave uniform: a lane column ends in this tile
+                        int rv = min(rows_valid, ncl[n] - tile * TILE_ROWS);
+                        asm volatile("" : "+v"(rv));
+#pragma unroll
+                        for (int k = 0; k < 4; ++k)
+                            if (16 * u + 4 * q + k >= rv) p[k] = 0.f;
+                    }
+                } else if (rows_valid < TILE_ROWS) {  // padded last tile only (wave uniform).  rv: the row masks stay inside this block (left to
                                                // the compiler they are formed and applied on every tile: 8 of 36 VALU per sub-tile)
                     int rv = rows_valid;
                     asm volatile("" : "+s"(rv));
@@ -354,20 +385,20 @@ bool scores_mfma_supported(int dtype, int h, int Dk, int l, int d, int l_sel) {
            l_sel == 4 * d;
 }
 
-template <typename T, int D>
+template <typename T, int D, bool NORM>
 static int launch_scores_t(const ScoresMfmaParams &P, hipStream_t st) {
     constexpr int NT = 4;
     const bool flat = P.h == 6 && tuning(TUNE_SCORES_FORM) != 0;  // 8 queries per wave on 3 column tiles instead of 4 (A/B switch: 0 = 4 tiles)
     const int QW = flat ? 32 : 4 * NT * (16 / P.h);
     dim3 grid((unsigned)((P.S + QW - 1) / QW), (unsigned)(P.B * P.G));
     if (flat) {
-        hipLaunchKernelGGL((scores_mfma_kernel<T, D, 3, 6>), grid, dim3(256), 0, st, P);
+        hipLaunchKernelGGL((scores_mfma_kernel<T, D, 3, 6, NORM>), grid, dim3(256), 0, st, P);
     } else {
         switch (P.h) {  // the common group sizes get straight-line head sums
-            case 6: hipLaunchKernelGGL((scores_mfma_kernel<T, D, NT, 6>), grid, dim3(256), 0, st, P); break;
-            case 4: hipLaunchKernelGGL((scores_mfma_kernel<T, D, NT, 4>), grid, dim3(256), 0, st, P); break;
-            case 8: hipLaunchKernelGGL((scores_mfma_kernel<T, D, NT, 8>), grid, dim3(256), 0, st, P); break;
-            default: hipLaunchKernelGGL((scores_mfma_kernel<T, D, NT, 0>), grid, dim3(256), 0, st, P); break;
+            case 6: hipLaunchKernelGGL((scores_mfma_kernel<T, D, NT, 6, NORM>), grid, dim3(256), 0, st, P); break;
+            case 4: hipLaunchKernelGGL((scores_mfma_kernel<T, D, NT, 4, NORM>), grid, dim3(256), 0, st, P); break;
+            case 8: hipLaunchKernelGGL((scores_mfma_kernel<T, D, NT, 8, NORM>), grid, dim3(256), 0, st, P); break;
+            default: hipLaunchKernelGGL((scores_mfma_kernel<T, D, NT, 0, NORM>), grid, dim3(256), 0, st, P); break;
         }
     }
     NSA_LAUNCH_CHECK("scores_mfma");
@@ -378,7 +409,7 @@ static int launch_scores_t(const ScoresMfmaParams &P, hipStream_t st) {
 // selects inside the launch) or the caller has to run the select kernel behind it
 int launch_sel_scores_mfma(const void *Q, const void *Kc, float *p_grp, int B, int S, int G, int h, int Dk, int S_cmp,
                            int64_t csb, int64_t csg, int64_t css, int S_sel, int d_stride, int dtype, float scale,
-                           int causal_skip, hipStream_t st, const SelectParams *sel, int *sel_done) {
+                           int causal_skip, hipStream_t st, const SelectParams *sel, int *sel_done, int q0, int norm, int l) {
     if (sel_done) *sel_done = 0;
     NSA_CHECK_ARG(css % 8 == 0 && csb % 8 == 0 && csg % 8 == 0 && ((uintptr_t)Q % 16 == 0) && ((uintptr_t)Kc % 16 == 0),
                   "scores_mfma: Q/K_cmp must be 16-byte aligned with strides that are multiples of 8 elements");
@@ -389,7 +420,7 @@ int launch_sel_scores_mfma(const void *Q, const void *Kc, float *p_grp, int B, i
     // asked for causal_skip == 2: it then reads only entries with (j+1) l' <= t+1 (what both selectors do), all of which are written
     if (causal_skip != 2) NSA_HIP_TRY(hipMemsetAsync(p_grp, 0, sizeof(float) * (size_t)B * S * G * S_sel, st));
     ScoresMfmaParams P{Q, Kc, p_grp, B, S, G, h, S_cmp, S_sel, csb, csg, css, scale, causal_skip, d_stride,
-                       (int64_t)S * G * S_sel < ((int64_t)1 << 31) ? 0 : 1};
+                       (int64_t)S * G * S_sel < ((int64_t)1 << 31) ? 0 : 1, q0, norm ? 1 : 0, l};
     const int form = tuning(TUNE_SCORES_FORM);
     if ((form < 0 || form == 2) && scores_mfma32_supported(P, Dk)) {
         // in the launch only where it pays (same box, tools/bench_scores_select.py: 64k x 4 3,537 -> 3,433 us, 64k x 1 905 -> 890, but 32k x 2
@@ -400,8 +431,12 @@ int launch_sel_scores_mfma(const void *Q, const void *Kc, float *p_grp, int B, i
         if (fuse) *sel_done = 1;
         return launch_scores_mfma32(P, dtype, st, fuse ? sel : nullptr);
     }
-    if (dtype == NSA_DT_BF16) return Dk == 64 ? launch_scores_t<__bf16, 64>(P, st) : launch_scores_t<__bf16, 128>(P, st);
-    return Dk == 64 ? launch_scores_t<_Float16, 64>(P, st) : launch_scores_t<_Float16, 128>(P, st);
+    if (P.norm) {
+        if (dtype == NSA_DT_BF16) return Dk == 64 ? launch_scores_t<__bf16, 64, true>(P, st) : launch_scores_t<__bf16, 128, true>(P, st);
+        return Dk == 64 ? launch_scores_t<_Float16, 64, true>(P, st) : launch_scores_t<_Float16, 128, true>(P, st);
+    }
+    if (dtype == NSA_DT_BF16) return Dk == 64 ? launch_scores_t<__bf16, 64, false>(P, st) : launch_scores_t<__bf16, 128, false>(P, st);
+    return Dk == 64 ? launch_scores_t<_Float16, 64, false>(P, st) : launch_scores_t<_Float16, 128, false>(P, st);
 }
 
 }  // namespace nsa

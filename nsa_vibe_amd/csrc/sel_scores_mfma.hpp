@@ -15,6 +15,9 @@ struct ScoresMfmaParams {
     int causal_skip;
     int d_stride;  // the compression stride d (tokens); l' = 4d
     int big_out;   // S G S_sel >= 2^31 elements per sequence: 64-bit output offsets
+    int q0;        // absolute position of query row 0 (a chunk of a chunked prefill starts at q0 > 0)
+    int norm;      // 1: row t = q0 + s normalises over its own n_cmp(t) columns (decode semantics); 0: over all S_cmp
+    int l;         // compression window (tokens): n_cmp(t) = (t + 1 < l) ? 0 : (t + 1 - l) / d + 1
 };
 
 // h = 6, D = 64, 32-bit output offsets: the 32x32x16 form (sel_scores_mfma32.hip)

@@ -27,6 +27,10 @@
 // ~60 head-sum + 8 stencil operations ~ 1,200; floor of the two-sweep algorithm (MFMA + exp + one fma per logit, nothing else) ~ 950 each.
 // Ablation switches (timing only, results meaningless; tools/ablate_scorer.sh): SC32_KSTEPS=n keeps n of the 4 k-steps, SC32_NOEXP replaces
 // v_exp_f32 by a multiply, SC32_NOSYNC drops staging and barriers, SC32_SWEEP1 stops after the first sweep.
+// NORM (P.norm = 1, decode-normalised scores of a chunked prefill / extend): query t = q0 + s sees the n_cmp(t) compressed tokens a decode
+// step at t sees.  Sweep 1 ends at the workgroup's last visible column and masks a lane's column past its own bound (-inf) on the half
+// tiles that reach past the wave's earliest bound; sweep 2 zeroes the head sum of a (query, column) the query cannot see (the 6 p of
+// the query are then all zero, their head sum is exactly 0) before the stencil.  Masked tiles leave a row's statistics unchanged bit for bit.
 #include "sel_scores_mfma.hpp"
 #include "sel_select_row.hpp"
 #ifdef SC32_NOEXP  // ablation: a full-rate VALU op in place of v_exp_f32
@@ -61,7 +65,7 @@ struct Mfma32<_Float16> {
 // the ranges are those of the separate launch bit for bit) right after its second sweep.  The scores it reads are the ones it has just stored
 // (wave-private rows; its stores drained first): L2 hits instead of the 4.3 GB HBM read of a select launch at 64k x 16, and the selector's
 // scalar chains run beside the other waves' matrix / vector work -- this kernel leaves the CU's scalar unit idle, the select kernel is bound by it.
-template <typename T, bool SEL>
+template <typename T, bool SEL, bool NORM>
 __global__ __launch_bounds__(256, 3) void scores_mfma32_kernel(ScoresMfmaParams P, SelectParams SP) {
     using M = Mfma32<T>;
     using x8 = typename M::x8;
@@ -111,6 +115,22 @@ __global__ __launch_bounds__(256, 3) void scores_mfma32_kernel(ScoresMfmaParams 
     }
 
     const int ntiles = (P.S_cmp + TILE_ROWS - 1) / TILE_ROWS;
+    // NORM: visible columns of the lane's sweep-1 column per tile n (its query's n_cmp; absent queries take the last row's), the wave's
+    // smallest bound (query tw) and the workgroup's largest (its last query)
+    int ncl[3];
+    int nc_wmin = P.S_cmp, nc_wgmax = P.S_cmp;
+    if constexpr (NORM) {
+#pragma unroll
+        for (int n = 0; n < 3; ++n) {
+            const int R = 32 * n + r;
+            const int ridx = ((R >> 3) << 2) | (R & 3);
+            const int t = tw + 8 * ((R >> 2) & 1) + ridx / HC;
+            ncl[n] = ncmp_at(P.q0 + min(t, P.S - 1), P.l, P.d_stride, P.S_cmp);
+        }
+        nc_wmin = ncmp_at(P.q0 + min(tw, P.S - 1), P.l, P.d_stride, P.S_cmp);
+        nc_wgmax = ncmp_at(P.q0 + min(t0 + QW, P.S) - 1, P.l, P.d_stride, P.S_cmp);
+    }
+    const int ntiles1 = NORM ? (nc_wgmax + TILE_ROWS - 1) / TILE_ROWS : ntiles;  // tiles of the first sweep
     // staging of one 64-row K_cmp tile: thread -> 2 (row, 16-B piece) pairs.  LDS piece swizzle (row >> 1) & 7: the 16 rows x one piece a
     // quarter-wave reads, and the 2 rows x 8 pieces it writes, both cover the 64 banks exactly once.
     u32x4 stg[NLD];
@@ -164,19 +184,20 @@ __global__ __launch_bounds__(256, 3) void scores_mfma32_kernel(ScoresMfmaParams 
     load_tile(0);
     store_tile(0);
     __syncthreads();
-    for (int tile = 0; tile < ntiles; ++tile) {
+    for (int tile = 0; tile < ntiles1; ++tile) {
 #ifdef SC32_NOSYNC  // ablation: no staging, no barriers (every tile reads buffer 0)
         const int buf = 0;
 #else
         const int buf = tile & 1;
 #endif
 #ifndef SC32_NOSYNC
-        if (tile + 1 < ntiles) load_tile(tile + 1);
+        if (tile + 1 < ntiles1) load_tile(tile + 1);
 #endif
 #pragma unroll
         for (int hf = 0; hf < NH; ++hf) {
             const int rows_valid = P.S_cmp - tile * TILE_ROWS - 32 * hf;  // rows of this half >= this are padding
             if (rows_valid <= 0) break;
+            const bool masked = NORM && tile * TILE_ROWS + 32 * hf + 32 > nc_wmin;  // NORM: a lane column of the wave ends in this half
             x8 kf[4];
             load_kf(buf, hf, kf);
             f32x16 acc[3];
@@ -200,10 +221,15 @@ __global__ __launch_bounds__(256, 3) void scores_mfma32_kernel(ScoresMfmaParams 
                     s1 += SC32_EXP(__builtin_fmaf(acc[n][i + 1], c2, nm));
                 }
                 float sum = s0 + s1;
-                if (__any(!(sum <= 4096.f)) || rows_valid < 32) {
+                if (__any(!(sum <= 4096.f)) || rows_valid < 32 || masked) {
                     asm volatile("; sweep-1 slow path" ::: "memory");
                     int rv = rows_valid;  // the row masks belong to this block
-                    asm volatile("" : "+s"(rv));
+                    if constexpr (NORM) {
+                        rv = min(rv, ncl[n] - tile * TILE_ROWS - 32 * hf);  // per lane column
+                        asm volatile("" : "+v"(rv));
+                    } else {
+                        asm volatile("" : "+s"(rv));
+                    }
                     float v[16];
                     float mx = -INFINITY;
 #pragma unroll
@@ -228,7 +254,7 @@ __global__ __launch_bounds__(256, 3) void scores_mfma32_kernel(ScoresMfmaParams 
             }
         }
 #ifndef SC32_NOSYNC
-        if (tile + 1 < ntiles) store_tile(buf ^ 1);
+        if (tile + 1 < ntiles1) store_tile(buf ^ 1);
         __syncthreads();
 #endif
     }
@@ -248,9 +274,10 @@ __global__ __launch_bounds__(256, 3) void scores_mfma32_kernel(ScoresMfmaParams 
     const int l_sel = 4 * P.d_stride;
     int jlast = P.S_sel - 1;  // last selection block this workgroup has to produce
     if (P.causal_skip) {
-        const int t_last = min(t0 + QW, P.S) - 1;
+        const int t_last = P.q0 + min(t0 + QW, P.S) - 1;  // absolute position of the workgroup's last query
         jlast = min(jlast, (t_last + 1) / l_sel - 1);
     }
+    if constexpr (NORM) jlast = min(jlast, nc_wgmax / 4);  // later blocks have no visible tap (block j's first tap is column 4j - 1)
     const int nhalf2 = (jlast < 0) ? 0 : min(NH * ntiles, (4 * jlast + 3) / 32 + 1);  // 32-row halves (8 selection blocks each) to visit
 #ifdef SC32_SWEEP1  // ablation: first sweep only
     const int tiles2 = 0;
@@ -339,6 +366,15 @@ __global__ __launch_bounds__(256, 3) void scores_mfma32_kernel(ScoresMfmaParams 
                 auto pf = [&](int i) -> float { return p[(6 * z + i) >> 2][(6 * z + i) & 3]; };
                 zs[z] = ((pf(0) + pf(1)) + (pf(2) + pf(3))) + (pf(4) + pf(5));
             }
+            if constexpr (NORM) {
+                if (32 * hfi + 32 > nc_wmin) {  // wave uniform: a query of the wave cannot see every column of this half
+                    // column c is visible at token t exactly when c d + l <= t + 1; register z holds query tw + 8 half + z
+                    const int tcol = (32 * hfi + r) * P.d_stride + P.l - 1 - P.q0 - tw - 8 * half;
+#pragma unroll
+                    for (int z = 0; z < 8; ++z)
+                        if (z < tcol) zs[z] = 0.f;
+                }
+            }
             {
 #pragma unroll
                 for (int z = 0; z < 8; ++z) st_w[128 * z + 32 * (hfi & 3) + r] = zs[z];
@@ -413,13 +449,25 @@ bool scores_mfma32_select_supported(const ScoresMfmaParams &P, int Dk, const Sel
 
 int launch_scores_mfma32(const ScoresMfmaParams &P, int dtype, hipStream_t st, const SelectParams *sel) {
     dim3 grid((unsigned)((P.S + 63) / 64), (unsigned)(P.B * P.G));
+    if (P.norm) {
+        const SelectParams none{};
+        if (dtype == NSA_DT_BF16) {
+            if (sel) hipLaunchKernelGGL((scores_mfma32_kernel<__bf16, true, true>), grid, dim3(256), 0, st, P, *sel);
+            else hipLaunchKernelGGL((scores_mfma32_kernel<__bf16, false, true>), grid, dim3(256), 0, st, P, none);
+        } else {
+            if (sel) hipLaunchKernelGGL((scores_mfma32_kernel<_Float16, true, true>), grid, dim3(256), 0, st, P, *sel);
+            else hipLaunchKernelGGL((scores_mfma32_kernel<_Float16, false, true>), grid, dim3(256), 0, st, P, none);
+        }
+        NSA_LAUNCH_CHECK("scores_mfma32");
+        return NSA_OK;
+    }
     if (sel) {
-        if (dtype == NSA_DT_BF16) hipLaunchKernelGGL((scores_mfma32_kernel<__bf16, true>), grid, dim3(256), 0, st, P, *sel);
-        else hipLaunchKernelGGL((scores_mfma32_kernel<_Float16, true>), grid, dim3(256), 0, st, P, *sel);
+        if (dtype == NSA_DT_BF16) hipLaunchKernelGGL((scores_mfma32_kernel<__bf16, true, false>), grid, dim3(256), 0, st, P, *sel);
+        else hipLaunchKernelGGL((scores_mfma32_kernel<_Float16, true, false>), grid, dim3(256), 0, st, P, *sel);
     } else {
         const SelectParams none{};
-        if (dtype == NSA_DT_BF16) hipLaunchKernelGGL((scores_mfma32_kernel<__bf16, false>), grid, dim3(256), 0, st, P, none);
-        else hipLaunchKernelGGL((scores_mfma32_kernel<_Float16, false>), grid, dim3(256), 0, st, P, none);
+        if (dtype == NSA_DT_BF16) hipLaunchKernelGGL((scores_mfma32_kernel<__bf16, false, false>), grid, dim3(256), 0, st, P, none);
+        else hipLaunchKernelGGL((scores_mfma32_kernel<_Float16, false, false>), grid, dim3(256), 0, st, P, none);
     }
     NSA_LAUNCH_CHECK("scores_mfma32");
     return NSA_OK;

@@ -112,7 +112,7 @@ class LlamaBlockNSA(nn.Module):
         if not prefill and x.shape[1] == 1 and self.attn._native_ok(x) and self.norm1.weight.dtype == x.dtype:
             y = self._decode_native(x, kv)
             return (y, kv) if return_kv else y
-        if prefill and kv.t == 0 and self.attn._native_ok(x) and self.norm1.weight.dtype == x.dtype:
+        if prefill and kv.t == 0 and self.attn.prefill_tile <= 0 and self.attn._native_ok(x) and self.norm1.weight.dtype == x.dtype:
             y = self._prefill_native(x, kv)
             return (y, kv) if return_kv else y
         out, kv = self.attn(self.norm1(x), kv, prefill=prefill)

@@ -14,6 +14,11 @@ What runs where:
   * projections, RoPE, avg-pool phi, gate MLP: plain PyTorch-ROCm ops.
 Selector semantics: `selector="sequential"` (reference default prefill, :1521-1723, and decode) or `"batched"`
 (NSA_PREFILL_BATCHED=1, :978-1448).
+Extend route (inference): a prefill onto a cache that already holds tokens (the next turn of a chat, the draft tokens of a speculative
+decoder) or any prefill with `prefill_tile > 0` (NSA_PREFILL_TILE, where the reference steps its decode path token by token, :538-539) runs
+nsa_layer_extend chunk by chunk with DECODE semantics: row t's compressed-score softmax covers only the n_cmp(t) compressed tokens emitted
+by then, and it selects sequentially.  That deliberately differs from the one-shot prefill of an empty cache (its softmax covers every
+compressed token of the prompt); in exchange the result equals S decode steps and does not depend on the chunking.
 """
 from __future__ import annotations
 
@@ -41,6 +46,20 @@ from .selection_scorer import (_DT, _stream, select_topn_ranges_batched, select_
                                workspace)
 
 _ORIG_SELECTORS = (select_topn_ranges_batched, select_topn_ranges_rows, selection_scores)
+
+
+def _env_prefill_tile() -> int:
+    """NSA_PREFILL_TILE parsed as the reference parses it (nsa_attention.py:250-255): an int, negative or invalid -> 0"""
+    try:
+        pt = int(os.getenv("NSA_PREFILL_TILE", "0"))
+    except ValueError:
+        return 0
+    return pt if pt > 0 else 0
+
+
+def _n_cmp(S_raw: int, l: int, d: int) -> int:
+    """compressed tokens emitted once S_raw tokens are cached"""
+    return 0 if S_raw < l else (S_raw - l) // d + 1
 
 
 def _scores_and_ranges(Q, K_cmp, meta, n_sel, selector, S, scale):
@@ -256,7 +275,7 @@ class NSAAttention(nn.Module):
     def __init__(self, dim: int, n_heads: int, n_kv_groups: int, d_k: int, d_v: int, l: int = 32, d: int = 16, l_sel: int = 64,
                  n_sel: int = 16, w: int = 512, phi: str = "avg", gate_hidden: Optional[int] = None, gate_temp: float = 1.0,
                  rope_impl: str = "llama", use_flash: bool = True, use_triton_sel: bool = False, *,
-                 selector: Optional[str] = None, query_chunk: int = 2048) -> None:
+                 selector: Optional[str] = None, query_chunk: int = 2048, prefill_tile: Optional[int] = None) -> None:
         super().__init__()
         assert n_heads % n_kv_groups == 0, "heads must be divisible by kv groups"
         if l % d != 0 or l_sel % d != 0:
@@ -272,6 +291,10 @@ class NSAAttention(nn.Module):
         assert selector in ("sequential", "batched")
         self.selector = selector
         self.query_chunk = query_chunk  # reserved: the fused scorer never materialises p_cmp, so prefill is not query-chunked (p_grp is 512 MiB at 64k)
+        # prefill_tile > 0: every prefill runs the extend route (decode semantics) in chunks of at most that many rows; None reads
+        # NSA_PREFILL_TILE once, here, as the reference does (invalid or negative -> 0)
+        self.prefill_tile = _env_prefill_tile() if prefill_tile is None else max(0, int(prefill_tile))
+        self._tile_grad_warned = False
         self.W_Q = nn.Linear(dim, n_heads * d_k, bias=False)
         self.W_K_sel = nn.Linear(dim, n_kv_groups * d_k, bias=False)
         self.W_V_sel = nn.Linear(dim, n_kv_groups * d_v, bias=False)
@@ -424,8 +447,13 @@ class NSAAttention(nn.Module):
         # several units, a memory fault when the result is consumed; tools/dbg_gemm.py) -- the contiguous 2-D GEMM is correct
         if not x.is_contiguous():
             x = x.contiguous()
+        extend = prefill and self._extend_wanted(x, kv)
         one_call = self._native_ok(x)
+        if extend:
+            saved = (kv.t, kv.n_cmp, len(kv.reads_pred))
         try:
+            if extend:
+                return self._extend(x, kv)
             return self._prefill(x, kv) if prefill else self._decode(x, kv)
         except RuntimeError as e:
             # the reference's router counts a failed native executor (nsa_attention.py:764-782) ...
@@ -439,9 +467,137 @@ class NSAAttention(nn.Module):
             # ... and falls back to its next executor and returns normally: the layer composed from the separate native calls
             warnings.warn(f"nsa_vibe_amd: the one-call native layer failed ({e}); falling back to the per-stage native route", RuntimeWarning)
             try:
+                if extend:
+                    kv.t, kv.n_cmp = saved[0], saved[1]  # the chunks the one-call route appended are written again
+                    for lst in (kv.reads_pred, kv.reads_act_total, kv.reads_act_sel, kv.reads_act_cmp, kv.reads_act_win):
+                        del lst[saved[2]:]
+                    return self._extend(x, kv, one_call=False)
                 return self._prefill(x, kv, one_call=False) if prefill else self._decode(x, kv, one_call=False)
             except Exception as e2:
                 raise e2 from e  # (both tracebacks: the per-stage route's failure, caused by the one-call route's)
+
+    # ---- extend: prefill onto a filled cache / tiled prefill, decode semantics -------------------------------------------------
+    def _extend_wanted(self, x: torch.Tensor, kv: NSA_KV) -> bool:
+        """whether this prefill runs the extend route (kv.t > 0 or prefill_tile > 0); raises where it cannot run"""
+        if kv.t == 0 and self.prefill_tile <= 0:
+            return False
+        grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+        if grad:
+            if kv.t > 0:
+                raise RuntimeError(f"NSAAttention: prefill onto a filled cache (kv.t = {kv.t}) runs the extend route, which is inference only "
+                                   "(no backward); run it under torch.no_grad() or start training from an empty cache")
+            if not self._tile_grad_warned:
+                self._tile_grad_warned = True
+                warnings.warn("nsa_vibe_amd: prefill_tile / NSA_PREFILL_TILE is not applied under autograd (the extend route has no "
+                              "backward); the training prefill runs unchunked", RuntimeWarning)
+            return False
+        if self._force_parity:
+            if kv.t > 0:
+                raise RuntimeError(f"NSAAttention: NSA_FORCE_PARITY has no extend route: prefill onto a filled cache (kv.t = {kv.t}) is "
+                                   "not supported in parity mode")
+            return False
+        return True
+
+    def _extend(self, x: torch.Tensor, kv: NSA_KV, one_call: bool = True):
+        """S tokens onto the cache in chunks of at most prefill_tile rows (all of them at once when prefill_tile = 0), each chunk one
+        nsa_layer_extend call (or its per-stage composition): the caches, ranges and outputs of S decode steps"""
+        B, S, _ = x.shape
+        tile = self.prefill_tile if self.prefill_tile > 0 else S
+        native = one_call and self._native_ok(x)
+        mixes, rs, gs = [], [], []
+        for c0 in range(0, S, tile):
+            xc = x[:, c0: c0 + tile]
+            if not xc.is_contiguous():
+                xc = xc.contiguous()
+            O, ranges, gates = self._extend_native(xc, kv) if native else self._extend_stages(xc, kv)
+            mixes.append(O)
+            rs.append(ranges)
+            gs.append(gates)
+        O = mixes[0] if len(mixes) == 1 else torch.cat(mixes, dim=1)
+        _set_plain(self, "_last_ranges", rs[0] if len(rs) == 1 else torch.cat(rs, dim=1))
+        _set_plain(self, "_last_gates", gs[0] if len(gs) == 1 else torch.cat(gs, dim=1))
+        return self.out(O), kv
+
+    def _extend_begin(self, kv: NSA_KV, S: int):
+        """capacity and block metadata for the chunk (metadata refreshed by the decode step's policy, reference :606-632)"""
+        t0 = kv.t
+        kv.ensure_capacity(t0 + S)
+        if kv.meta.S_sel == 0:
+            kv.ensure_meta(max(t0 + S, self.l_sel))
+        elif t0 + S > kv.meta.S_sel * self.l_sel:
+            kv.ensure_meta(t0 + S)
+        return t0, kv.meta
+
+    def _extend_end(self, kv: NSA_KV, t0: int, S: int) -> None:
+        """cache state and read counters as S decode steps leave them"""
+        for t in range(t0, t0 + S):
+            kv.append_reads(_n_cmp(t + 1, self.l, self.d), t + 1)
+        kv.t, kv.n_cmp = t0 + S, _n_cmp(t0 + S, self.l, self.d)
+
+    def _extend_native(self, x: torch.Tensor, kv: NSA_KV):
+        """one chunk: fused projection GEMM -> ONE native call (nsa_layer_extend) -> O_mix, ranges, gates"""
+        B, S, _ = x.shape
+        t0, meta = self._extend_begin(kv, S)
+        L, dev = _lib.lib(), x.device
+        desc, W_qkv = self._layer_desc()
+        kd = self._kv_desc(kv)
+        proj = F.linear(x, W_qkv)
+        ranges = torch.empty((B, S, self.n_kv_groups, self.n_sel, 2), dtype=torch.int32, device=dev)
+        gates = torch.empty((B, S, self.n_kv_groups, 3), dtype=torch.float32, device=dev)
+        O = torch.empty((B, S, self.n_heads * self.d_v), dtype=x.dtype, device=dev)
+        ws = workspace(dev, L.nsa_layer_extend_workspace(ctypes.byref(desc), B, S, t0, int(meta.S_sel)) + 256, "layer_extend")
+        wptr = (ws.data_ptr() + 255) & ~255
+        cptr, crows, cvals = meta.device_csc(dev)
+        rc = L.nsa_layer_extend(ctypes.byref(desc), ctypes.byref(kd), proj.data_ptr(), t0, S, cptr.data_ptr(), crows.data_ptr(),
+                                cvals.data_ptr(), int(meta.S_sel), ranges.data_ptr(), O.data_ptr(), gates.data_ptr(), wptr,
+                                ws.numel() - (wptr - ws.data_ptr()), _stream(dev))
+        _lib.check(rc, "nsa_layer_extend")
+        self._extend_end(kv, t0, S)
+        return O, ranges, gates
+
+    def _extend_stages(self, x: torch.Tensor, kv: NSA_KV):
+        """one chunk composed from the separate native entry points (the next executor of the one-call route): the same kernels with the
+        same arguments and workspaces, so the same bits"""
+        B, S, _ = x.shape
+        if not (x.is_cuda and x.dtype in _DT):
+            raise RuntimeError("nsa_vibe_amd: the extend route needs a HIP device tensor of a supported dtype (no CPU fallback exists)")
+        t0, meta = self._extend_begin(kv, S)
+        L, dev, st = _lib.lib(), x.device, _stream(x.device)
+        desc, W_qkv = self._layer_desc()
+        dref, kd = ctypes.byref(desc), self._kv_desc(kv)
+        G, h, Dk, Dv, dt = self.n_kv_groups, self.h_per_group, self.d_k, self.d_v, _DT[x.dtype]
+        S_kv, n0, n1 = t0 + S, _n_cmp(t0, self.l, self.d), _n_cmp(t0 + S, self.l, self.d)
+        scale = 1.0 / math.sqrt(Dk)
+        proj = F.linear(x, W_qkv)
+        Q = torch.empty((B, S, G, h, Dk), dtype=x.dtype, device=dev)
+        _lib.check(L.nsa_rope_cache_append(dref, ctypes.byref(kd), proj.data_ptr(), Q.data_ptr(), S, t0, st), "nsa_rope_cache_append")
+        if n1 > n0:
+            _lib.check(L.nsa_cmp_pool_append(dref, ctypes.byref(kd), n0, n1, st), "nsa_cmp_pool_append")
+        _, ranges = selection_scores_select(Q, kv._K_cmp[:, :, :n1], meta, self.n_sel, mode="sequential", t0=t0, scale=scale,
+                                            q0=t0, normalize="causal")
+        Ks, Vs, Kw, Vw = kv._K_sel, kv._V_sel, kv._K_win, kv._V_win
+        O_sel, O_win, O_cmp = (torch.empty((B, S, G, h, Dv), dtype=x.dtype, device=dev) for _ in range(3))
+        nb = L.nsa_sel_attn_fwd_workspace_kv(B, S, G, h, Dk, Dv, S_kv, self.n_sel, dt)
+        ws = workspace(dev, nb, "extend_attn")
+        _lib.check(L.nsa_sel_attn_fwd(Q.data_ptr(), Ks.data_ptr(), Vs.data_ptr(), ranges.data_ptr(), O_sel.data_ptr(), None, B, S, G, h, Dk, Dv,
+                                      S_kv, self.n_sel, Ks.stride(0), Ks.stride(1), Ks.stride(2), Vs.stride(0), Vs.stride(1), Vs.stride(2), dt,
+                                      scale, 0, ws.data_ptr() if ws is not None else None, nb, st), "nsa_sel_attn_fwd")
+        nb = L.nsa_band_attn_fwd_workspace(B, S, G, h, Dk, Dv, dt)
+        ws = workspace(dev, nb, "extend_band")
+        wp = ws.data_ptr() if ws is not None else None
+        _lib.check(L.nsa_band_attn_fwd(Q.data_ptr(), Kw.data_ptr(), Vw.data_ptr(), O_win.data_ptr(), None, B, S, G, h, Dk, Dv, S_kv,
+                                       Kw.stride(0), Kw.stride(1), Kw.stride(2), Vw.stride(0), Vw.stride(1), Vw.stride(2), t0, 0, 1, 0, self.w,
+                                       dt, scale, 0, wp, nb, st), "nsa_band_attn_fwd")
+        Kc, Vc = kv._K_cmp, kv._V_cmp
+        _lib.check(L.nsa_band_attn_fwd(Q.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), O_cmp.data_ptr(), None, B, S, G, h, Dk, Dv, n1,
+                                       Kc.stride(0), Kc.stride(1), Kc.stride(2), Vc.stride(0), Vc.stride(1), Vc.stride(2), t0, self.l, self.d,
+                                       1, 1 << 30, dt, scale, 0, wp, nb, st), "nsa_band_attn_fwd")
+        O = torch.empty((B, S, self.n_heads * Dv), dtype=x.dtype, device=dev)
+        gates = torch.empty((B, S, G, 3), dtype=torch.float32, device=dev)
+        _lib.check(L.nsa_gate_combine(dref, Q.data_ptr(), O_cmp.data_ptr(), O_sel.data_ptr(), O_win.data_ptr(), O.data_ptr(),
+                                      gates.data_ptr(), B * S * G, st), "nsa_gate_combine")
+        self._extend_end(kv, t0, S)
+        return O, ranges, gates
 
     def _prefill(self, x: torch.Tensor, kv: NSA_KV, one_call: bool = True):
         B, S, _ = x.shape

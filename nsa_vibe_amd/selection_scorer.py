@@ -123,8 +123,18 @@ def group_reduce_pslc(p_slc: torch.Tensor) -> torch.Tensor:
     return acc
 
 
+_NORM = {"all": 0, "causal": 1}
+
+
+def _norm_code(normalize: str) -> int:
+    if normalize not in _NORM:
+        raise ValueError("normalize must be 'all' or 'causal'")
+    return _NORM[normalize]
+
+
 def selection_scores(Q_all: torch.Tensor, K_cmp: torch.Tensor, meta: BlockMeta, scale: Optional[float] = None,
-                     causal_skip: bool = False, variant: int = 0, leave_skipped: bool = False) -> torch.Tensor:
+                     causal_skip: bool = False, variant: int = 0, leave_skipped: bool = False, q0: int = 0,
+                     normalize: str = "all") -> torch.Tensor:
     """Fused A2+A3+A4: Q [B,S,G,h,Dk], K_cmp [B,G,S_cmp,Dk] -> p_grp [B,S,G,S_sel] fp32 without
     materialising p_cmp (nsa_attention.py:1073-1091 in one call).
 
@@ -132,7 +142,12 @@ def selection_scores(Q_all: torch.Tensor, K_cmp: torch.Tensor, meta: BlockMeta, 
     them to -inf, selection_scorer.py:156,276-280): such an entry holds 0 or, where its workgroup computed the block for a later row, the
     full value; with leave_skipped=True those entries are left
     uninitialised (no zero fill of the tensor) -- for results that go straight to the selectors.  variant: 0 auto, 1 generic
-    (any dtype/geometry, query-chunked), 2 the MFMA kernel (bf16/f16, default block geometry)."""
+    (any dtype/geometry, query-chunked), 2 the MFMA kernel (bf16/f16, default block geometry), 3 the decode-shaped pair.
+
+    q0: absolute position of query row 0 (row s sits at token q0 + s; causal_skip counts from there).  normalize="all" is the
+    one-shot prefill's softmax over every S_cmp column; "causal" gives row t the DECODE normalisation: the softmax over the
+    n_cmp(t) = (t + 1 < l) ? 0 : (t + 1 - l) // d + 1 compressed tokens a decode step at t sees (nsa_sel_scores_rows)."""
+    norm = _norm_code(normalize)
     dev = _need_gpu(Q_all, K_cmp)
     B, S, G, h, Dk = Q_all.shape
     S_cmp, S_sel = K_cmp.shape[2], meta.S_sel
@@ -144,26 +159,37 @@ def selection_scores(Q_all: torch.Tensor, K_cmp: torch.Tensor, meta: BlockMeta, 
     L = _lib.lib()
     if variant == 0 and B * S * G > 1024 and not (sb % 8 == 0 and sg % 8 == 0 and ss % 8 == 0 and K_cmp.data_ptr() % 16 == 0):
         variant = 1  # rows not 16-byte aligned: the MFMA route would refuse them
-    nbytes = L.nsa_sel_scores_workspace(B, S, G, h, Dk, S_cmp, S_sel, int(meta.l), int(meta.d), int(meta.l_sel), _DT[Q_all.dtype],
-                                        int(variant))
+    if q0 == 0 and norm == 0:  # the original entry point (same kernels and bits as nsa_sel_scores_rows with q0 = 0, norm = 0)
+        nbytes = L.nsa_sel_scores_workspace(B, S, G, h, Dk, S_cmp, S_sel, int(meta.l), int(meta.d), int(meta.l_sel), _DT[Q_all.dtype],
+                                            int(variant))
+    else:
+        nbytes = L.nsa_sel_scores_rows_workspace(B, S, G, h, Dk, S_cmp, S_sel, int(meta.l), int(meta.d), int(meta.l_sel),
+                                                 _DT[Q_all.dtype], int(variant), norm)
     ws = workspace(dev, nbytes, "scores")
     cptr, crows, cvals = meta.device_csc(dev)
-    rc = L.nsa_sel_scores(Q_all.data_ptr(), K_cmp.data_ptr(), p_grp.data_ptr(), B, S, G, h, Dk, S_cmp, sb, sg, ss,
-                          cptr.data_ptr(), crows.data_ptr(), cvals.data_ptr(), S_sel, int(meta.l), int(meta.d), int(meta.l_sel),
-                          (2 if leave_skipped else 1) if causal_skip else 0, int(variant), _DT[Q_all.dtype], float(scale) if scale else 0.0,
-                          ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, _stream(dev))
-    _lib.check(rc, "nsa_sel_scores")
+    args = (Q_all.data_ptr(), K_cmp.data_ptr(), p_grp.data_ptr(), B, S, G, h, Dk, S_cmp, sb, sg, ss, cptr.data_ptr(), crows.data_ptr(),
+            cvals.data_ptr(), S_sel, int(meta.l), int(meta.d), int(meta.l_sel), (2 if leave_skipped else 1) if causal_skip else 0, int(variant),
+            _DT[Q_all.dtype], float(scale) if scale else 0.0)
+    tail = (ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, _stream(dev))
+    if q0 == 0 and norm == 0:
+        _lib.check(L.nsa_sel_scores(*args, *tail), "nsa_sel_scores")
+    else:
+        _lib.check(L.nsa_sel_scores_rows(*args, int(q0), norm, *tail), "nsa_sel_scores_rows")
     return p_grp
 
 
 def selection_scores_select(Q_all: torch.Tensor, K_cmp: torch.Tensor, meta: BlockMeta, n_top: int, *, mode: str = "batched", t0: int = 0,
-                            scale: Optional[float] = None, force_init: bool = True, force_local: int = 2, leave_skipped: bool = True):
+                            scale: Optional[float] = None, force_init: bool = True, force_local: int = 2, leave_skipped: bool = True,
+                            q0: Optional[int] = None, normalize: str = "all"):
     """Prefill (inference): group scores AND the top-n ranges of every row in ONE native call (nsa_sel_scores_select) -- on the MFMA scorer's
     default route (h = 6, Dk = 64, default block geometry, bf16 / f16, up to 1024 selection blocks) in one LAUNCH: a workgroup selects the
     ranges of its 64 query rows right behind its second sweep, reading its scores back out of L2.  Q [B,S,G,h,Dk], K_cmp [B,G,S_cmp,Dk] ->
     (p_grp [B,S,G,S_sel] fp32 with blocks no selector can read skipped, ranges [B,S,G,W,2] int32).  mode "batched" =
     select_topn_ranges_batched (nsa/core/selection_scorer.py:255-362), "sequential" = select_topn_ranges at token t0 + s (:124-249).
-    ranges are bit-identical to selection_scores(..., causal_skip=True) followed by select_topn_ranges_batched / _rows."""
+    ranges are bit-identical to selection_scores(..., causal_skip=True) followed by select_topn_ranges_batched / _rows.
+    q0 / normalize: as selection_scores (q0 defaults to t0); normalize="causal" with mode="sequential" is the extend route's scorer."""
+    norm = _norm_code(normalize)
+    q0 = int(t0) if q0 is None else int(q0)
     dev = _need_gpu(Q_all, K_cmp)
     B, S, G, h, Dk = Q_all.shape
     S_cmp, S_sel = K_cmp.shape[2], meta.S_sel
@@ -182,15 +208,21 @@ def selection_scores_select(Q_all: torch.Tensor, K_cmp: torch.Tensor, meta: Bloc
     L = _lib.lib()
     dt = _DT[Q_all.dtype]
     geo = (int(meta.l), int(meta.d), int(meta.l_sel))
-    nbytes = max(L.nsa_sel_scores_workspace(B, S, G, h, Dk, S_cmp, S_sel, *geo, dt, 0), L.nsa_sel_scores_workspace(B, S, G, h, Dk, S_cmp, S_sel, *geo, dt, 1))
+    if q0 == 0 and norm == 0:
+        nbytes = max(L.nsa_sel_scores_workspace(B, S, G, h, Dk, S_cmp, S_sel, *geo, dt, 0), L.nsa_sel_scores_workspace(B, S, G, h, Dk, S_cmp, S_sel, *geo, dt, 1))
+    else:
+        nbytes = max(L.nsa_sel_scores_rows_workspace(B, S, G, h, Dk, S_cmp, S_sel, *geo, dt, 0, norm),
+                     L.nsa_sel_scores_rows_workspace(B, S, G, h, Dk, S_cmp, S_sel, *geo, dt, 1, norm))
     ws = workspace(dev, nbytes, "scores")
     cptr, crows, cvals = meta.device_csc(dev)
-    rc = L.nsa_sel_scores_select(Q_all.data_ptr(), K_cmp.data_ptr(), p_grp.data_ptr(), B, S, G, h, Dk, S_cmp, sb, sg, ss,
-                                 cptr.data_ptr(), crows.data_ptr(), cvals.data_ptr(), S_sel, *geo, 2 if leave_skipped else 1, dt,
-                                 float(scale) if scale else 0.0, int(t0), int(n_top), int(bool(force_init)), int(force_local), md, S,
-                                 ranges.data_ptr(), W, ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0,
-                                 _stream(dev))
-    _lib.check(rc, "nsa_sel_scores_select")
+    args = (Q_all.data_ptr(), K_cmp.data_ptr(), p_grp.data_ptr(), B, S, G, h, Dk, S_cmp, sb, sg, ss, cptr.data_ptr(), crows.data_ptr(),
+            cvals.data_ptr(), S_sel, *geo, 2 if leave_skipped else 1, dt, float(scale) if scale else 0.0, int(t0), int(n_top),
+            int(bool(force_init)), int(force_local), md, S, ranges.data_ptr(), W)
+    tail = (ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, _stream(dev))
+    if q0 == 0 and norm == 0:
+        _lib.check(L.nsa_sel_scores_select(*args, *tail), "nsa_sel_scores_select")
+    else:
+        _lib.check(L.nsa_sel_scores_select_rows(*args, q0, norm, *tail), "nsa_sel_scores_select_rows")
     return p_grp, ranges
 
 
