@@ -129,7 +129,7 @@ NSA_API int nsa_sel_attn_head_causal_parity(const void *Q, const void *K, const 
 /* Backward.  dO like O; dQ like Q (dtype); dK/dV are fp32 [B,G,S_kv,D] contiguous, fully written by the callee.
  * O and lse come from the forward.
  *   variant 0 auto, 1 generic (any dtype/shape: one wave per query row, dK/dV by fp32 atomics),
- *   2 MFMA (bf16/f16, Dk = Dv = 64, h <= 16): dQ query-major + dK/dV key-block-major, no atomics, reproducible.
+ *   2 MFMA (bf16/f16, Dk = Dv in {64, 128}, h <= 16): dQ query-major + dK/dV key-block-major, no atomics, reproducible.
  *   workspace: nsa_sel_attn_bwd_workspace() bytes (MFMA route: B*S*G*h floats for rowsum(dO*O) plus, when the query
  *   rows are split over workgroups, the per-split dK/dV partial sums that are added in fixed order; else 0). */
 NSA_API size_t nsa_sel_attn_bwd_workspace(int B, int S, int G, int h, int Dk, int Dv, int S_kv, int dtype, int variant);
@@ -148,7 +148,7 @@ NSA_API int nsa_sel_attn_bwd(const void *Q, const void *K, const void *V, const 
  *   compressed (emission schedule num_cmp(t), attention_kernels.py:118-121): a = l, dd = d, c = 1, w = INT_MAX (K/V = K_cmp/V_cmp).
  * Layouts, strides, scale, lse and the empty-row rule (zeros, lse = -inf) as in nsa_sel_attn_fwd.  Prefill passes t0 = 0 and
  * all S rows; a decode step passes S = 1 and t0 = position of the new token.
- *   variant 0 = auto, 1 = generic VALU kernel (any dtype, D <= 256), 2 = MFMA kernel (bf16/f16, Dk = Dv = 64, h <= 16).
+ *   variant 0 = auto, 1 = generic VALU kernel (any dtype, D <= 256), 2 = MFMA kernel (bf16/f16, Dk = Dv in {64, 128}, h <= 16).
  * ------------------------------------------------------------------------------------- */
 NSA_API size_t nsa_band_attn_fwd_workspace(int B, int S, int G, int h, int Dk, int Dv, int dtype);
 NSA_API int nsa_band_attn_fwd(const void *Q, const void *K, const void *V, void *O, float *lse, int B, int S, int G, int h,
@@ -157,7 +157,8 @@ NSA_API int nsa_band_attn_fwd(const void *Q, const void *K, const void *V, void 
                       int dtype, float scale, int variant, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Band attention backward (same interval rule and layouts as nsa_band_attn_fwd; O and lse from the forward; dQ in the activation
- * dtype, dK/dV fp32 [B,G,S_kv,D] fully written).  MFMA route (bf16/f16, Dk = Dv = 64): dQ by a dense 48-slot query-major kernel, dK/dV by
+ * dtype, dK/dV fp32 [B,G,S_kv,D] fully written).  MFMA route (bf16/f16, Dk = Dv in {64, 128}): dQ by a dense query-major kernel (48
+ * slots per wave at D = 64, 16 at D = 128), dK/dV by
  * the key-block-major kernels of nsa_sel_attn_bwd fed with one [lo,hi) range per row; otherwise the generic selection backward. */
 NSA_API size_t nsa_band_attn_bwd_workspace(int B, int S, int G, int h, int Dk, int Dv, int S_kv, int dtype, int variant);
 NSA_API int nsa_band_attn_bwd(const void *Q, const void *K, const void *V, const void *O, const float *lse, const void *dO, void *dQ,

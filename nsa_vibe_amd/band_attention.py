@@ -19,6 +19,7 @@ from typing import Optional
 import torch
 
 from . import _lib
+from .selection_attention import _bwd_variant
 from .selection_scorer import _DT, _need_gpu, _stream, workspace
 
 _W_INF = 2 ** 30
@@ -64,11 +65,11 @@ def _fwd(Q, K, V, band, scale, variant, want_lse):
 
 class _BandAttnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, Q, K, V, band, scale, variant):
+    def forward(ctx, Q, K, V, band, scale, variant, bwd_variant):
         O, lse, (Qc, Kc, Vc) = _fwd(Q, K, V, band, scale, variant, True)
         ctx.save_for_backward(Qc, Kc, Vc, O, lse)
         ctx.band, ctx.scale = band, scale
-        ctx.bwd_variant = 0 if variant != 1 else 1
+        ctx.bwd_variant = _bwd_variant(variant, bwd_variant)
         return O
 
     @staticmethod
@@ -92,19 +93,22 @@ class _BandAttnFn(torch.autograd.Function):
                                  int(t0), int(a), int(dd), int(c), int(min(w, _W_INF)), dt, float(ctx.scale) if ctx.scale else 0.0,
                                  int(ctx.bwd_variant), wptr, ws.numel() - (wptr - ws.data_ptr()), _stream(dev))
         _lib.check(rc, "nsa_band_attn_bwd")
-        return dQ, dK.to(Kc.dtype), dV.to(Vc.dtype), None, None, None
+        return dQ, dK.to(Kc.dtype), dV.to(Vc.dtype), None, None, None, None
 
 
 def band_attention_hip(Q, K, V, *, t0: int = 0, a: int = 0, dd: int = 1, c: int = 0, w: int = _W_INF,
-                       scale: Optional[float] = None, variant: int = 0, return_lse: bool = False):
-    """Row t attends keys [max(0, hi - w), hi), hi = (t0+t+1 >= a) ? min(S_kv, (t0+t+1-a)//dd + c) : 0."""
+                       scale: Optional[float] = None, variant: int = 0, return_lse: bool = False,
+                       bwd_variant: Optional[int] = None):
+    """Row t attends keys [max(0, hi - w), hi), hi = (t0+t+1 >= a) ? min(S_kv, (t0+t+1-a)//dd + c) : 0.
+
+    variant: 0 auto, 1 generic, 2 MFMA (forward); bwd_variant: the same for the backward, None = 0 unless variant is 1."""
     band = (int(t0), int(a), int(dd), int(c), int(w))
     if torch.is_grad_enabled() and (Q.requires_grad or K.requires_grad or V.requires_grad):
         if return_lse:
             raise RuntimeError("return_lse is not available on the autograd path")
         if K.shape[2] == 0:
             return Q.new_zeros(Q.shape[:-1] + (V.shape[-1],)) + 0.0 * Q.sum()
-        return _BandAttnFn.apply(Q, K, V, band, scale, variant)
+        return _BandAttnFn.apply(Q, K, V, band, scale, variant, bwd_variant)
     O, lse, _ = _fwd(Q, K, V, band, scale, variant, return_lse)
     return (O, lse) if return_lse else O
 

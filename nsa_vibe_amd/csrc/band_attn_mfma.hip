@@ -1,4 +1,4 @@
-// MFMA band attention forward for gfx950 (bf16 / f16, Dk = Dv = 64, h <= 16): the sliding-window and the compressed
+// MFMA band attention forward for gfx950 (bf16 / f16, Dk = Dv in {64, 128}, h <= 16): the sliding-window and the compressed
 // branch of NSA (reference: sliding_window_attention, nsa/core/attention_kernels.py:146-178; compressed branch with the
 // num_cmp(t) emission schedule, :106-143).  Query row t attends the contiguous key interval [lo(t), hi(t)) defined in
 // sel_attn_params.hpp (BandAttnParams); rows with an empty interval give zeros.
@@ -44,13 +44,21 @@ struct BandBwdExtra {
     void *dQ;            // [B,S,G,h,D]
 };
 
-template <typename T, int NT>
+// D = 128 (NT = 1): K is staged ONCE, in the chunk-swizzled image of the transposing reads; its b128 row-fragment reads are bank-conflict
+// free too (see sel_attn_bwd_mfma.hip, BGeo), so a wave needs 2 x 8 KiB of LDS instead of 3 x 8 KiB and two workgroups fit a CU
+template <int D>
+constexpr int band_dq_wave_lds() {
+    return (D == 64 ? 3 : 2) * Geo<D>::TILE_BYTES;
+}
+
+template <typename T, int D, int NT>
 __global__ __launch_bounds__(256, 2) void band_attn_bwd_dq_kernel(BandAttnParams P, BandBwdExtra E) {
     using M = MfmaT<T>;
-    using G_ = Geo<64>;
+    using G_ = Geo<D>;
     using x8 = typename M::x8;
     using x4 = typename M::x4;
-    constexpr int D = 64;
+    constexpr int KS = G_::KSTEPS, MT = G_::MT;
+    constexpr bool ONE_K = D == 128;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = lane_id();
     const int wave = uniform((int)(threadIdx.x >> 6));
@@ -71,8 +79,8 @@ __global__ __launch_bounds__(256, 2) void band_attn_bwd_dq_kernel(BandAttnParams
     if (grp >= ngrp || bg >= nbg) return;
     const int b = bg / P.G, g = bg - b * P.G;
     const int tw0 = grp * tpw, ntok = min(tpw, P.S - tw0);
-    unsigned char *kl = smem + (size_t)wave * (3 * G_::TILE_BYTES);  // K rows | K transposable | V rows
-    unsigned char *ktl = kl + G_::TILE_BYTES, *vl = ktl + G_::TILE_BYTES;
+    unsigned char *kl = smem + (size_t)wave * band_dq_wave_lds<D>();  // K rows | K transposable | V rows (ONE_K: K transposable | V rows)
+    unsigned char *ktl = ONE_K ? kl : kl + G_::TILE_BYTES, *vl = ktl + G_::TILE_BYTES;
 
     const int hi_min = band_hi(P.t0, P.a, P.dd, P.c, P.S_kv, tw0);
     const int hi_max = band_hi(P.t0, P.a, P.dd, P.c, P.S_kv, tw0 + ntok - 1);
@@ -81,7 +89,7 @@ __global__ __launch_bounds__(256, 2) void band_attn_bwd_dq_kernel(BandAttnParams
     int hi_s[NT], lo_s[NT];
     int64_t orow[NT];
     float lse2[NT], dlt[NT];
-    x8 qf[NT][2], dof[NT][2];
+    x8 qf[NT][KS], dof[NT][KS];
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
         const int slot = 16 * n + rho, tok = slot / h, head = slot - tok * h;
@@ -94,7 +102,7 @@ __global__ __launch_bounds__(256, 2) void band_attn_bwd_dq_kernel(BandAttnParams
         lse2[n] = l > -INFINITY ? l * LOG2E : INFINITY;  // empty / unused slot: exp2(s - inf) = 0
         dlt[n] = used ? E.delta[orow[n]] : 0.f;
 #pragma unroll
-        for (int s = 0; s < 2; ++s) {
+        for (int s = 0; s < KS; ++s) {
             u32x4 rq = {0u, 0u, 0u, 0u}, rd = {0u, 0u, 0u, 0u};
             if (used) {
                 rq = *(const u32x4 *)((const T *)P.Q + orow[n] * D + 32 * s + 8 * q);
@@ -118,13 +126,17 @@ __global__ __launch_bounds__(256, 2) void band_attn_bwd_dq_kernel(BandAttnParams
     [[maybe_unused]] const auto vrs = make_rsrc(Vb, (int64_t)(P.S_kv - 1) * vrowb + G_::ROWB);
     [[maybe_unused]] const int krowb32 = uniform((int)krowb), vrowb32 = uniform((int)vrowb);
     [[maybe_unused]] const int ld_row = lane / G_::PIECES, ld_piece = lane % G_::PIECES;
-    uint32_t krd0[2], trd0[4];
+    uint32_t krd0[KS], vrd0[KS], trd0[MT];
 #pragma unroll
-    for (int s = 0; s < 2; ++s) krd0[s] = rho * G_::ROWB + (((4 * s + q) ^ G_::swz_k(rho)) << 4);
+    for (int s = 0; s < KS; ++s) {
+        const int pc = 4 * s + q;
+        vrd0[s] = rho * G_::ROWB + ((pc ^ G_::swz_k(rho)) << 4);
+        krd0[s] = ONE_K ? rho * G_::ROWB + ((((pc >> 1) ^ G_::swz_v(rho)) << 5) | ((pc & 1) << 4)) : vrd0[s];
+    }
     {
         const int qq = rho >> 2, pp = rho & 3, r = 4 * q + qq;
 #pragma unroll
-        for (int m = 0; m < 4; ++m) trd0[m] = r * G_::ROWB + ((m ^ G_::swz_v(r)) << 5) + 8 * pp;
+        for (int m = 0; m < MT; ++m) trd0[m] = r * G_::ROWB + ((m ^ G_::swz_v(r)) << 5) + 8 * pp;
     }
     // one 32-key tile -> three wave-private images (rows past the end of K/V re-read the last row; they are masked)
     auto issue_dma = [&](int tok0) {
@@ -138,7 +150,7 @@ __global__ __launch_bounds__(256, 2) void band_attn_bwd_dq_kernel(BandAttnParams
             const int rc = min(r, last);
             const uint32_t pk = (uint32_t)((ld_piece ^ G_::swz_k(r)) << 4);
             const uint32_t pt = (uint32_t)(((((ld_piece >> 1) ^ G_::swz_v(r)) << 1) | (ld_piece & 1)) << 4);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(krs, (lds_void *)(kl + i * 1024), 16, rc * krowb32 + pk, ks, 0, 0);
+            if constexpr (!ONE_K) __builtin_amdgcn_raw_ptr_buffer_load_lds(krs, (lds_void *)(kl + i * 1024), 16, rc * krowb32 + pk, ks, 0, 0);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(krs, (lds_void *)(ktl + i * 1024), 16, rc * krowb32 + pt, ks, 0, 0);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(vrs, (lds_void *)(vl + i * 1024), 16, rc * vrowb32 + pk, vs, 0, 0);
         }
@@ -147,27 +159,27 @@ __global__ __launch_bounds__(256, 2) void band_attn_bwd_dq_kernel(BandAttnParams
 #endif
     };
 
-    f32x4 dq[NT][4];
+    f32x4 dq[NT][MT];
 #pragma unroll
     for (int n = 0; n < NT; ++n)
 #pragma unroll
-        for (int m = 0; m < 4; ++m) dq[n][m] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int m = 0; m < MT; ++m) dq[n][m] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const float c2 = P.scale * LOG2E;
     const int ntile = hi_max > klo ? (hi_max - klo + 31) >> 5 : 0;
     if (ntile > 0) issue_dma(klo);
     for (int tile = 0; tile < ntile; ++tile) {
         const int tok0 = klo + 32 * tile;
-        x8 kfr[2][2], vfr[2][2], ka[4];
+        x8 kfr[2][KS], vfr[2][KS], ka[MT];
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
-            for (int s = 0; s < 2; ++s) {
+            for (int s = 0; s < KS; ++s) {
                 kfr[u][s] = *(const x8 *)(kl + krd0[s] + u * 16 * G_::ROWB);
-                vfr[u][s] = *(const x8 *)(vl + krd0[s] + u * 16 * G_::ROWB);
+                vfr[u][s] = *(const x8 *)(vl + vrd0[s] + u * 16 * G_::ROWB);
             }
 #pragma unroll
-        for (int m = 0; m < 4; ++m) {
+        for (int m = 0; m < MT; ++m) {
             const x4 lo = M::tr(ktl + trd0[m]), hi = M::tr(ktl + trd0[m] + 16 * G_::ROWB);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -187,7 +199,7 @@ __global__ __launch_bounds__(256, 2) void band_attn_bwd_dq_kernel(BandAttnParams
                 sacc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
                 dpacc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int s = 0; s < 2; ++s) {
+                for (int s = 0; s < KS; ++s) {
                     sacc[u] = M::mma(kfr[u][s], qf[n][s], sacc[u]);
                     dpacc[u] = M::mma(vfr[u][s], dof[n][s], dpacc[u]);
                 }
@@ -205,7 +217,7 @@ __global__ __launch_bounds__(256, 2) void band_attn_bwd_dq_kernel(BandAttnParams
                     dsf[4 * u + j] = Elt<T>::from_f(p * (dpacc[u][j] - dlt[n]) * P.scale);
                 }
 #pragma unroll
-            for (int m = 0; m < 4; ++m) dq[n][m] = M::mma(ka[m], dsf, dq[n][m]);
+            for (int m = 0; m < MT; ++m) dq[n][m] = M::mma(ka[m], dsf, dq[n][m]);
         }
     }
 #pragma unroll
@@ -213,7 +225,7 @@ __global__ __launch_bounds__(256, 2) void band_attn_bwd_dq_kernel(BandAttnParams
         if (orow[n] < 0) continue;
         T *dst = (T *)E.dQ + orow[n] * D;
 #pragma unroll
-        for (int m = 0; m < 4; ++m) {
+        for (int m = 0; m < MT; ++m) {
             x4 ov;
 #pragma unroll
             for (int j = 0; j < 4; ++j) ov[j] = Elt<T>::from_f(dq[n][m][j]);
@@ -345,11 +357,13 @@ int launch_band_attn_fwd_dual(const BandAttnParams &A0, const BandAttnParams &A1
     return NSA_OK;
 }
 
-// dQ of the band (bf16/f16, Dk = Dv = 64).  delta = rowsum(dO * O) [B,S,G,h] fp32 comes from the caller.
-template <typename T>
+// dQ of the band (bf16/f16, Dk = Dv = 64 or 128).  delta = rowsum(dO * O) [B,S,G,h] fp32 comes from the caller.
+template <typename T, int D>
 static int launch_band_dq_t(BandAttnParams P, const BandBwdExtra &E, hipStream_t st) {
-    // 48 slots per wave when there are enough token groups, else 16
-    const int tpw3 = 48 / P.h, tpw1 = 16 / P.h;
+    // 48 slots per wave when there are enough token groups, else 16.  D = 128: always 16 -- at 32 (NT = 2, the forward's form) the dQ
+    // accumulators, Q / dO fragments and K / V tile fragments need more than 256 registers (the compiler spilled 308 B per lane)
+    constexpr int NTW = D == 64 ? 3 : 1;
+    const int tpw3 = 16 * NTW / P.h, tpw1 = 16 / P.h;
     const int64_t nbg = (int64_t)P.B * P.G;
     const bool big = nbg * ((P.S + tpw3 - 1) / tpw3) >= 2048;
     P.tpw = big ? tpw3 : tpw1;
@@ -357,19 +371,19 @@ static int launch_band_dq_t(BandAttnParams P, const BandBwdExtra &E, hipStream_t
     const int64_t W = (ngrp + 3) / 4;
     P.map_mode = (nbg % 8 == 0) ? 2 : 1;
     NSA_CHECK_ARG(nbg * W < ((int64_t)1 << 31), "band_attn_bwd: too many workgroups for one launch");
-    const size_t lds = 4 * (size_t)(3 * Geo<64>::TILE_BYTES);
-    if (big) hipLaunchKernelGGL((band_attn_bwd_dq_kernel<T, 3>), dim3((unsigned)(nbg * W)), dim3(256), lds, st, P, E);
-    else hipLaunchKernelGGL((band_attn_bwd_dq_kernel<T, 1>), dim3((unsigned)(nbg * W)), dim3(256), lds, st, P, E);
+    const size_t lds = 4 * (size_t)band_dq_wave_lds<D>();  // 48 KiB (D = 64), 64 KiB (D = 128)
+    if (big) hipLaunchKernelGGL((band_attn_bwd_dq_kernel<T, D, NTW>), dim3((unsigned)(nbg * W)), dim3(256), lds, st, P, E);
+    else hipLaunchKernelGGL((band_attn_bwd_dq_kernel<T, D, 1>), dim3((unsigned)(nbg * W)), dim3(256), lds, st, P, E);
     NSA_LAUNCH_CHECK("band_attn_bwd_dq");
     return NSA_OK;
 }
 
 int launch_band_attn_bwd_dq(const BandAttnParams &P, const void *dO, const float *lse, const float *delta, void *dQ, int dtype,
                             hipStream_t st) {
-    NSA_CHECK_ARG(band_attn_mfma_supported(dtype, P.h, P.Dk, P.Dv) && P.Dk == 64, "band dQ kernel: unsupported dtype/h/Dk/Dv");
+    NSA_CHECK_ARG(band_attn_mfma_supported(dtype, P.h, P.Dk, P.Dv), "band dQ kernel: unsupported dtype/h/Dk/Dv");
     BandBwdExtra E{dO, lse, delta, dQ};
-    if (dtype == NSA_DT_BF16) return launch_band_dq_t<__bf16>(P, E, st);
-    return launch_band_dq_t<_Float16>(P, E, st);
+    if (dtype == NSA_DT_BF16) return P.Dk == 64 ? launch_band_dq_t<__bf16, 64>(P, E, st) : launch_band_dq_t<__bf16, 128>(P, E, st);
+    return P.Dk == 64 ? launch_band_dq_t<_Float16, 64>(P, E, st) : launch_band_dq_t<_Float16, 128>(P, E, st);
 }
 
 }  // namespace nsa

@@ -1,4 +1,4 @@
-// MFMA backward of the selection attention for gfx950 (bf16 / f16, Dk = Dv = 64, h <= 16).
+// MFMA backward of the selection attention for gfx950 (bf16 / f16, Dk = Dv = D in {64, 128}, h <= 16).
 //
 // Reference: autograd of the masked SDPA (nsa/core/attention_kernels.py:705-772); the structure of the reference's
 // analytic backward (nsa/kernels/triton_sel_kernel/__init__.py:163-231: recompute P, dS = P*(dP - delta), dQ/dK/dV)
@@ -9,7 +9,7 @@
 //   2. dQ, query-major (one wave per query row, the forward's mapping): per 32-key tile
 //        S^T = K.Q^T, dP^T = V.dO^T, dS^T = exp2(S^T c - lse) * (dP^T - delta) * scale, dQ^T += K^T.dS^T
 //      (K is staged twice in LDS: a row image for the S^T A-operand and a transposable image for the dQ^T A-operand.)
-//   3. dK, dV, KEY-BLOCK-major: one workgroup owns 64 keys of one (b,g) and keeps their dK/dV (64x64 fp32 each) in MFMA
+//   3. dK, dV, KEY-BLOCK-major: one workgroup owns 64 keys of one (b,g) and keeps their dK/dV (64xD fp32 each) in MFMA
 //      accumulators while it sweeps every query row that selected the block.  The rows are found by scanning the range
 //      lists (lane = row) and compacted in ascending t, so the summation order is fixed.  Rows are processed two at a
 //      time in round 1 (2 x 6 heads = 12 of the 16 MFMA rows); round 2 lays the (row, head) slots end to end, every tile full:
@@ -48,23 +48,36 @@ __device__ __forceinline__ X4 tr_read(const unsigned char *p) {
     return __builtin_bit_cast(X4, r);
 }
 
-constexpr int BD = 64;           // head dim handled here
-constexpr int BROWB = BD * 2;    // 128-B rows
-__device__ __forceinline__ int bswz_row(int r) { return r & 7; }          // 16-B piece XOR for b128 row reads
-__device__ __forceinline__ int bswz_tr(int r) { return (r >> 1) & 3; }    // 32-B chunk XOR for transposed reads
-__device__ __forceinline__ uint32_t off_row_img(int r, int piece) { return r * BROWB + ((piece ^ bswz_row(r)) << 4); }
-__device__ __forceinline__ uint32_t off_tr_img(int r, int piece) {
-    return r * BROWB + ((((piece >> 1) ^ bswz_tr(r)) << 5) | ((piece & 1) << 4));
-}
+// Head dimension D = Dk = Dv in {64, 128}: rows of D bf16/f16 elements = D / 8 pieces of 16 B = D / 16 chunks of 32 B.
+//   D = 64:  128-B rows, piece XOR r & 7,  chunk XOR (r >> 1) & 3.
+//   D = 128: 256-B rows, piece XOR r & 15, chunk XOR r & 7 (the forward's Geo<128> swizzles).
+// Bank check (MI355X LDS: 64 banks of 4 B, ds_read_b128 served in the four 16-lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31}, ...,
+// ds_read_b64_tr_b16 in two 32-lane groups), done exhaustively over every lane group, fragment index and 16-row half, for both D:
+// the row reads of the row image (row rho, piece 4s + q), the row reads of the transposable image (same pieces) and the transposing
+// reads (row 4q + rho / 4, chunk m, 8 B at 8 (rho & 3)) each touch every bank once per group -- no conflicts.
+template <int D>
+struct BGeo {
+    static constexpr int ROWB = D * 2;          // bytes per row
+    static constexpr int PIECES = D / 8;        // 16-B pieces per row
+    static constexpr int RPI = 64 / PIECES;     // rows of one wave-wide 16-B load (1 KiB)
+    static constexpr int NLD = 32 / RPI;        // such loads per 32-row tile
+    static constexpr int KS = D / 32;           // 16x16x32 k-steps over d
+    static constexpr int MT = D / 16;           // 16-column d tiles
+    __device__ static int swz_row(int r) { return r & (PIECES - 1); }            // 16-B piece XOR for b128 row reads
+    __device__ static int swz_tr(int r) { return D == 64 ? ((r >> 1) & 3) : (r & 7); }  // 32-B chunk XOR for transposed reads
+    __device__ static uint32_t off_row_img(int r, int piece) { return r * ROWB + ((piece ^ swz_row(r)) << 4); }
+    __device__ static uint32_t off_tr_img(int r, int piece) { return r * ROWB + ((((piece >> 1) ^ swz_tr(r)) << 5) | ((piece & 1) << 4)); }
+};
 
 // ------------------------------------------------------------------------------------------ 1. delta
-// Dv = 64: 8 lanes per (row, head), 16 bytes per lane -- a wave reads 8 whole rows of O and of dO per instruction (one thread
+// Dv / 8 lanes per (row, head), 16 bytes per lane -- a wave reads 512 / Dv whole rows of O and of dO per instruction (one thread
 // per row made every lane walk its own 128-byte row: 0.9 TB/s)
-template <typename T>
+template <typename T, int D>
 __global__ __launch_bounds__(256) void bwd_delta_kernel(const T *__restrict__ O, const T *__restrict__ dO, float *__restrict__ delta,
                                                          int64_t n_rows, int Dv) {
-    const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 3;  // (row, head)
-    const int sub = threadIdx.x & 7;
+    constexpr int LPR = D / 8;  // lanes per (row, head)
+    const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) / LPR;  // (row, head)
+    const int sub = threadIdx.x % LPR;
     float acc = 0.f;
     if (i < n_rows) {
         const u32x4 a = *(const u32x4 *)(O + i * Dv + 8 * sub), b = *(const u32x4 *)(dO + i * Dv + 8 * sub);
@@ -72,21 +85,26 @@ __global__ __launch_bounds__(256) void bwd_delta_kernel(const T *__restrict__ O,
 #pragma unroll
         for (int k = 0; k < 8; ++k) acc = fmaf(Elt<T>::to_f(pa[k]), Elt<T>::to_f(pb[k]), acc);
     }
-    acc += __shfl_xor(acc, 1, 64);
-    acc += __shfl_xor(acc, 2, 64);
-    acc += __shfl_xor(acc, 4, 64);
+#pragma unroll
+    for (int m = 1; m < LPR; m <<= 1) acc += __shfl_xor(acc, m, 64);
     if (i < n_rows && sub == 0) delta[i] = acc;
 }
 
 // ------------------------------------------------------------------------------------------ 2. dQ (query-major)
-template <typename T>
+template <int D>
+constexpr int bwd_dq_wave_lds() {
+    return 3 * 32 * BGeo<D>::ROWB + ((SEG_INTS * 4 + 15) / 16) * 16;
+}
+
+template <typename T, int D>
 __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(SelAttnBwdParams P, const float *__restrict__ delta, int map_mode) {
     using M = BwdT<T>;
+    using Gm = BGeo<D>;
     using x8 = typename M::x8;
     using x4 = typename M::x4;
-    constexpr int TILE = 32 * BROWB;  // 4 KiB
-    constexpr int SEGB = ((SEG_INTS * 4 + 15) / 16) * 16;
-    constexpr int WAVE_LDS = 3 * TILE + SEGB;
+    constexpr int BROWB = Gm::ROWB, KS = Gm::KS, MT = Gm::MT, NLD = Gm::NLD, RPI = Gm::RPI;
+    constexpr int TILE = 32 * BROWB;  // 4 KiB (D = 64), 8 KiB (D = 128)
+    constexpr int WAVE_LDS = bwd_dq_wave_lds<D>();
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = lane_id();
     const int wave = uniform((int)(threadIdx.x >> 6));
@@ -123,13 +141,13 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(SelAttnBwdParams P, cons
     const int rho = lane & 15, q = lane >> 4;
 
     // B operands held for the whole row: Q^T and dO^T fragments (head = column), per-head lse (log2 domain) and delta
-    x8 qf[2], dof[2];
+    x8 qf[KS], dof[KS];
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
+    for (int s = 0; s < KS; ++s) {
         u32x4 a = {0u, 0u, 0u, 0u}, c = {0u, 0u, 0u, 0u};
         if (rho < h) {
-            a = *(const u32x4 *)((const T *)P.Q + (row * h + rho) * (int64_t)BD + 32 * s + 8 * q);
-            c = *(const u32x4 *)((const T *)P.dO + (row * h + rho) * (int64_t)BD + 32 * s + 8 * q);
+            a = *(const u32x4 *)((const T *)P.Q + (row * h + rho) * (int64_t)D + 32 * s + 8 * q);
+            c = *(const u32x4 *)((const T *)P.dO + (row * h + rho) * (int64_t)D + 32 * s + 8 * q);
         }
         qf[s] = __builtin_bit_cast(x8, a);
         dof[s] = __builtin_bit_cast(x8, c);
@@ -138,22 +156,22 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(SelAttnBwdParams P, cons
     const float dlt = (rho < h) ? delta[row * h + rho] : 0.f;
     const float c2 = P.scale * LOG2E;
 
-    const int ld_row = lane >> 3, ld_piece = lane & 7;  // 8 rows x 8 pieces per wave-wide 16-B load
-    uint32_t kd_row[4], kd_tr[4], vd_row[4];
+    const int ld_row = lane / Gm::PIECES, ld_piece = lane % Gm::PIECES;  // RPI rows x PIECES pieces per wave-wide 16-B load
+    uint32_t kd_row[NLD], kd_tr[NLD], vd_row[NLD];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = 8 * i + ld_row;
-        kd_row[i] = (uint32_t)(ld_row * krowb + ((ld_piece ^ bswz_row(r)) << 4));
-        kd_tr[i] = (uint32_t)(ld_row * krowb + (((((ld_piece >> 1) ^ bswz_tr(r)) << 1) | (ld_piece & 1)) << 4));
-        vd_row[i] = (uint32_t)(ld_row * vrowb + ((ld_piece ^ bswz_row(r)) << 4));
+    for (int i = 0; i < NLD; ++i) {
+        const int r = RPI * i + ld_row;
+        kd_row[i] = (uint32_t)(ld_row * krowb + ((ld_piece ^ Gm::swz_row(r)) << 4));
+        kd_tr[i] = (uint32_t)(ld_row * krowb + (((((ld_piece >> 1) ^ Gm::swz_tr(r)) << 1) | (ld_piece & 1)) << 4));
+        vd_row[i] = (uint32_t)(ld_row * vrowb + ((ld_piece ^ Gm::swz_row(r)) << 4));
     }
-    uint32_t rd_row[2], rd_tr[4];
+    uint32_t rd_row[KS], rd_tr[MT];
 #pragma unroll
-    for (int s = 0; s < 2; ++s) rd_row[s] = off_row_img(rho, 4 * s + q);
+    for (int s = 0; s < KS; ++s) rd_row[s] = Gm::off_row_img(rho, 4 * s + q);
     {
         const int qq = rho >> 2, pp = rho & 3, r = 4 * q + qq;
 #pragma unroll
-        for (int m = 0; m < 4; ++m) rd_tr[m] = r * BROWB + ((m ^ bswz_tr(r)) << 5) + 8 * pp;
+        for (int m = 0; m < MT; ++m) rd_tr[m] = r * BROWB + ((m ^ Gm::swz_tr(r)) << 5) + 8 * pp;
     }
     auto make_rsrc = [&](const unsigned char *base, int64_t bytes) {
         const uint64_t a = (uint64_t)base;
@@ -164,7 +182,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(SelAttnBwdParams P, cons
     [[maybe_unused]] const auto krs = make_rsrc(Kb, (int64_t)(P.S_kv - 1) * krowb + BROWB);
     [[maybe_unused]] const auto vrs = make_rsrc(Vb, (int64_t)(P.S_kv - 1) * vrowb + BROWB);
     [[maybe_unused]] const int krowb32 = uniform((int)krowb), vrowb32 = uniform((int)vrowb);
-    [[maybe_unused]] const int kstep = uniform(8 * (int)krowb), vstep = uniform(8 * (int)vrowb);
+    [[maybe_unused]] const int kstep = uniform(RPI * (int)krowb), vstep = uniform(RPI * (int)vrowb);
 
     int it_seg = -1, it_start = 0, it_len = 0, it_pos = 0;
     auto next_tile = [&](int &tok0, int &nvalid) -> bool {
@@ -186,9 +204,9 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(SelAttnBwdParams P, cons
         typedef __attribute__((address_space(3))) void lds_void;
         const int ks = uniform(tok0 * krowb32), vs = uniform(tok0 * vrowb32);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
+        for (int i = 0; i < NLD; ++i) {
             // tail tiles: rows past the segment re-read its last row (their dS is masked to zero below)
-            const int rowshift = (nvalid == 32) ? 0 : (min(8 * i + ld_row, nvalid - 1) - ld_row);
+            const int rowshift = (nvalid == 32) ? 0 : (min(RPI * i + ld_row, nvalid - 1) - ld_row);
             const int kso = (nvalid == 32) ? ks + i * kstep : ks, vso = (nvalid == 32) ? vs + i * vstep : vs;
             const uint32_t kadd = (nvalid == 32) ? 0u : (uint32_t)(rowshift * krowb32), vadd = (nvalid == 32) ? 0u : (uint32_t)(rowshift * vrowb32);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(krs, (lds_void *)(k_row + i * 1024), 16, kd_row[i] + kadd, kso, 0, 0);
@@ -201,28 +219,28 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(SelAttnBwdParams P, cons
 #endif
     };
 
-    f32x4 dq[4];
+    f32x4 dq[MT];
 #pragma unroll
-    for (int m = 0; m < 4; ++m) dq[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int m = 0; m < MT; ++m) dq[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
     int tok0 = 0, nvalid = 0;
     bool have = next_tile(tok0, nvalid);
     if (have) issue_dma(tok0, nvalid);
     while (have) {
         const int cur_nvalid = nvalid;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        x8 kfr[2][2], vfr[2][2];
-        x4 ktr[2][4];
+        x8 kfr[2][KS], vfr[2][KS];
+        x4 ktr[2][MT];
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
-            for (int s = 0; s < 2; ++s) {
+            for (int s = 0; s < KS; ++s) {
                 kfr[u][s] = *(const x8 *)(k_row + rd_row[s] + u * 16 * BROWB);
                 vfr[u][s] = *(const x8 *)(v_row + rd_row[s] + u * 16 * BROWB);
             }
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
-            for (int m = 0; m < 4; ++m) ktr[u][m] = tr_read<x4>(k_tr + rd_tr[m] + u * 16 * BROWB);
+            for (int m = 0; m < MT; ++m) ktr[u][m] = tr_read<x4>(k_tr + rd_tr[m] + u * 16 * BROWB);
         have = next_tile(tok0, nvalid);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
@@ -234,7 +252,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(SelAttnBwdParams P, cons
             sacc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
             pacc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int s = 0; s < 2; ++s) {
+            for (int s = 0; s < KS; ++s) {
                 sacc[u] = M::mma32(kfr[u][s], qf[s], sacc[u]);
                 pacc[u] = M::mma32(vfr[u][s], dof[s], pacc[u]);
             }
@@ -249,7 +267,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(SelAttnBwdParams P, cons
                 dsf[4 * u + j] = Elt<T>::from_f(p * (pacc[u][j] - dlt) * P.scale);
             }
 #pragma unroll
-        for (int m = 0; m < 4; ++m) {
+        for (int m = 0; m < MT; ++m) {
             x8 a;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -260,9 +278,9 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(SelAttnBwdParams P, cons
         }
     }
     if (rho < h) {
-        T *dQr = (T *)P.dQ + (row * (int64_t)h + rho) * BD;
+        T *dQr = (T *)P.dQ + (row * (int64_t)h + rho) * D;
 #pragma unroll
-        for (int m = 0; m < 4; ++m) {
+        for (int m = 0; m < MT; ++m) {
             x4 ov;
 #pragma unroll
             for (int j = 0; j < 4; ++j) ov[j] = Elt<T>::from_f(dq[m][j]);
@@ -285,13 +303,15 @@ __device__ __forceinline__ void bwd_lds_or(unsigned *p, unsigned v) {
     __hip_atomic_fetch_or((lds_u32 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
 }
 
-template <typename T>
+template <typename T, int D>
 __global__ __launch_bounds__(256, 2) void bwd_dq_rows_kernel(SelAttnBwdParams P, const float *__restrict__ delta, int map_mode, int tpw, int NW,
                                                           int wave_lds) {
     using M = BwdT<T>;
+    using Gm = BGeo<D>;
     using x8 = typename M::x8;
     using x4 = typename M::x4;
-    constexpr int TILE = 32 * BROWB;  // 4 KiB
+    constexpr int BROWB = Gm::ROWB, KS = Gm::KS, MT = Gm::MT, NLD = Gm::NLD, RPI = Gm::RPI;
+    constexpr int TILE = 32 * BROWB;  // 4 KiB (D = 64), 8 KiB (D = 128)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = lane_id();
     const int wave = uniform((int)(threadIdx.x >> 6));
@@ -361,13 +381,13 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_rows_kernel(SelAttnBwdParams P,
     const bool used = tok < ntok;
     const int64_t orow = used ? ((((int64_t)b * P.S + tw0 + tok) * P.G + g) * h + head) : -1;  // row * h + head
 
-    x8 qf[2], dof[2];
+    x8 qf[KS], dof[KS];
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
+    for (int s = 0; s < KS; ++s) {
         u32x4 a = {0u, 0u, 0u, 0u}, c = {0u, 0u, 0u, 0u};
         if (used) {
-            a = *(const u32x4 *)((const T *)P.Q + orow * BD + 32 * s + 8 * q);
-            c = *(const u32x4 *)((const T *)P.dO + orow * BD + 32 * s + 8 * q);
+            a = *(const u32x4 *)((const T *)P.Q + orow * D + 32 * s + 8 * q);
+            c = *(const u32x4 *)((const T *)P.dO + orow * D + 32 * s + 8 * q);
         }
         qf[s] = __builtin_bit_cast(x8, a);
         dof[s] = __builtin_bit_cast(x8, c);
@@ -385,24 +405,24 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_rows_kernel(SelAttnBwdParams P,
     const unsigned char *Kb = (const unsigned char *)((const T *)P.K + (int64_t)b * P.ksb + (int64_t)g * P.ksg);
     const unsigned char *Vb = (const unsigned char *)((const T *)P.V + (int64_t)b * P.vsb + (int64_t)g * P.vsg);
     const int64_t krowb = P.kss * 2, vrowb = P.vss * 2;
-    const int ld_row = lane >> 3, ld_piece = lane & 7;
-    uint32_t kd_tr[4], vd_row[4];
+    const int ld_row = lane / Gm::PIECES, ld_piece = lane % Gm::PIECES;
+    uint32_t kd_tr[NLD], vd_row[NLD];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = 8 * i + ld_row;
-        kd_tr[i] = (uint32_t)(ld_row * krowb + (((((ld_piece >> 1) ^ bswz_tr(r)) << 1) | (ld_piece & 1)) << 4));
-        vd_row[i] = (uint32_t)(ld_row * vrowb + ((ld_piece ^ bswz_row(r)) << 4));
+    for (int i = 0; i < NLD; ++i) {
+        const int r = RPI * i + ld_row;
+        kd_tr[i] = (uint32_t)(ld_row * krowb + (((((ld_piece >> 1) ^ Gm::swz_tr(r)) << 1) | (ld_piece & 1)) << 4));
+        vd_row[i] = (uint32_t)(ld_row * vrowb + ((ld_piece ^ Gm::swz_row(r)) << 4));
     }
-    uint32_t rd_row[2], rd_krow[2], rd_tr[4];
+    uint32_t rd_row[KS], rd_krow[KS], rd_tr[MT];
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        rd_row[s] = off_row_img(rho, 4 * s + q);
-        rd_krow[s] = off_tr_img(rho, 4 * s + q);
+    for (int s = 0; s < KS; ++s) {
+        rd_row[s] = Gm::off_row_img(rho, 4 * s + q);
+        rd_krow[s] = Gm::off_tr_img(rho, 4 * s + q);
     }
     {
         const int qq = rho >> 2, pp = rho & 3, r = 4 * q + qq;
 #pragma unroll
-        for (int m = 0; m < 4; ++m) rd_tr[m] = r * BROWB + ((m ^ bswz_tr(r)) << 5) + 8 * pp;
+        for (int m = 0; m < MT; ++m) rd_tr[m] = r * BROWB + ((m ^ Gm::swz_tr(r)) << 5) + 8 * pp;
     }
     auto make_rsrc = [&](const unsigned char *base, int64_t bytes) {
         const uint64_t a = (uint64_t)base;
@@ -413,7 +433,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_rows_kernel(SelAttnBwdParams P,
     [[maybe_unused]] const auto krs = make_rsrc(Kb, (int64_t)(P.S_kv - 1) * krowb + BROWB);
     [[maybe_unused]] const auto vrs = make_rsrc(Vb, (int64_t)(P.S_kv - 1) * vrowb + BROWB);
     [[maybe_unused]] const int krowb32 = uniform((int)krowb), vrowb32 = uniform((int)vrowb);
-    [[maybe_unused]] const int kstep = uniform(8 * (int)krowb), vstep = uniform(8 * (int)vrowb);
+    [[maybe_unused]] const int kstep = uniform(RPI * (int)krowb), vstep = uniform(RPI * (int)vrowb);
     auto issue_dma = [&](int tok0) {
 #ifdef DQ_NODMA  // ablation (timing only, results meaningless): no K / V tile fetches
         return;
@@ -424,8 +444,8 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_rows_kernel(SelAttnBwdParams P,
         const bool whole = tok0 + 32 <= P.S_kv;
         const int last = P.S_kv - 1 - tok0;  // rows past the end of K/V re-read the last row (masked: such a tile is never `full`)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int rowshift = whole ? 0 : (min(8 * i + ld_row, last) - ld_row);
+        for (int i = 0; i < NLD; ++i) {
+            const int rowshift = whole ? 0 : (min(RPI * i + ld_row, last) - ld_row);
             const int kso = whole ? ks + i * kstep : ks, vso = whole ? vs + i * vstep : vs;
             const uint32_t kadd = whole ? 0u : (uint32_t)(rowshift * krowb32), vadd = whole ? 0u : (uint32_t)(rowshift * vrowb32);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(krs, (lds_void *)(k_tr + i * 1024), 16, kd_tr[i] + kadd, kso, 0, 0);
@@ -458,9 +478,9 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_rows_kernel(SelAttnBwdParams P,
         return 32 * iw + bit;
     };
 
-    f32x4 dq[4];
+    f32x4 dq[MT];
 #pragma unroll
-    for (int m = 0; m < 4; ++m) dq[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int m = 0; m < MT; ++m) dq[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
     int cur = next_tile();
     if (cur >= 0) issue_dma(32 * cur);
     int cw = -1;
@@ -470,19 +490,19 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_rows_kernel(SelAttnBwdParams P,
         const int nxt = next_tile();
         const int tok0 = 32 * cur;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        x8 kfr[2][2], vfr[2][2];
-        x4 ktr[2][4];
+        x8 kfr[2][KS], vfr[2][KS];
+        x4 ktr[2][MT];
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
-            for (int s = 0; s < 2; ++s) {
+            for (int s = 0; s < KS; ++s) {
                 kfr[u][s] = *(const x8 *)(k_tr + rd_krow[s] + u * 16 * BROWB);
                 vfr[u][s] = *(const x8 *)(v_row + rd_row[s] + u * 16 * BROWB);
             }
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
-            for (int m = 0; m < 4; ++m) ktr[u][m] = tr_read<x4>(k_tr + rd_tr[m] + u * 16 * BROWB);
+            for (int m = 0; m < MT; ++m) ktr[u][m] = tr_read<x4>(k_tr + rd_tr[m] + u * 16 * BROWB);
         if ((cur >> 5) != cw) {  // lane r < ntok caches row r's bitmap words of the current 32-tile group
             cw = cur >> 5;
             if (lane < ntok) {
@@ -523,7 +543,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_rows_kernel(SelAttnBwdParams P,
             sacc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
             pacc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int s = 0; s < 2; ++s) {
+            for (int s = 0; s < KS; ++s) {
                 sacc[u] = M::mma32(kfr[u][s], qf[s], sacc[u]);
                 pacc[u] = M::mma32(vfr[u][s], dof[s], pacc[u]);
             }
@@ -539,7 +559,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_rows_kernel(SelAttnBwdParams P,
                 dsf[4 * u + j] = Elt<T>::from_f(p * (pacc[u][j] - dlt) * P.scale);
             }
 #pragma unroll
-        for (int m = 0; m < 4; ++m) {
+        for (int m = 0; m < MT; ++m) {
             x8 a;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -551,9 +571,9 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_rows_kernel(SelAttnBwdParams P,
         cur = nxt;
     }
     if (used) {
-        T *dQr = (T *)P.dQ + orow * BD;
+        T *dQr = (T *)P.dQ + orow * D;
 #pragma unroll
-        for (int m = 0; m < 4; ++m) {
+        for (int m = 0; m < MT; ++m) {
             x4 ov;
 #pragma unroll
             for (int j = 0; j < 4; ++j) ov[j] = Elt<T>::from_f(dq[m][j]);
@@ -563,18 +583,26 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_rows_kernel(SelAttnBwdParams P,
 }
 
 // ------------------------------------------------------------------------------------------ 3. dK / dV (key-block-major)
-constexpr int KB_NCT = 8;
+// column tiles (of 16 (query,head) slots) staged per round.  D = 128 stages 4 (two 16 KiB images, plus 32 KiB of K / V block images:
+// 71 KiB per workgroup, two per CU); at 8 the kernel either spills (Q / dO of a round in registers: 2 x 8 x 16 B per thread beside
+// 64 dK / dV accumulator registers) or needs 104 KiB of LDS (one workgroup per CU)
+template <int D>
+constexpr int kb_nct() {
+    return D == 64 ? 8 : 4;
+}
 #ifdef NSA_DBG_WGTIME
 __device__ unsigned long long g_dbg[4 * 65536];
-#endif  // column tiles (of 16 (query,head) slots) staged per round
+#endif
 
-template <typename T>
+template <typename T, int D>
 __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(SelAttnBwdParams P, const float *__restrict__ delta, float *__restrict__ part,
                                                         const unsigned long long *__restrict__ hitmap, const unsigned long long *__restrict__ fullmap,
                                                         int *__restrict__ flags, int rows_per_split, int nkb, int nbg, int nsplit) {
     using M = BwdT<T>;
+    using Gm = BGeo<D>;
     using x8 = typename M::x8;
     using x4 = typename M::x4;
+    constexpr int BROWB = Gm::ROWB, PIECES = Gm::PIECES, KS = Gm::KS, MT = Gm::MT;
     // Workgroup -> (key block j, bg, row split z).  Workgroups go round-robin over the 8 XCDs by linear id; all key blocks
     // of one (bg, z) pair are put on ONE XCD (its 512 Q/dO rows stay in that L2), and the pairs are dealt evenly over the
     // XCDs (every pair carries about the same number of hits, while key block 0 alone is hit by every row: a j-major
@@ -588,19 +616,26 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(SelAttnBwdParams P, co
         zsp = pair / nbg;
         bg = pair - zsp * nbg;
     }
+    constexpr int KB_NCT = kb_nct<D>();
+    // D = 128 fits 256 registers without scratch only by giving up the register prefetch of the next round's Q / dO rows (they are
+    // loaded at the top of their own round) and by reading the K / V fragments from LDS (KV_LDS below)
+    constexpr bool PREFETCH = D == 64;
     constexpr int SLOTS = 16 * KB_NCT;        // (query,head) slots per round
     constexpr int IMG = SLOTS * BROWB;        // bytes of one staged image
-    constexpr int NLD = SLOTS * 8 / 256;      // 16-byte pieces per thread and image
+    constexpr int NLD = SLOTS * PIECES / 256; // 16-byte pieces per thread and image
     // ONE image per staged operand (round 4): the chunk-swizzled image the transposing reads need serves the b128 row-fragment reads too, free
     // of bank conflicts (every 16-lane service group of ds_read_b128 touches 64 distinct banks: checked exhaustively) -- rounds 1-3 staged
     // Q and dO twice (row image + transposable image: 64 KiB of LDS writes per round instead of 32)
-    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * IMG];  // the K/V block images alias the staging images (only read before the loop)
+    // D = 64: the K/V block images alias the staging images (only read before the loop: their fragments stay in registers).
+    // D = 128: the fragments are read from LDS inside the loop (32 registers fewer), the images get LDS of their own
+    constexpr bool KV_LDS = D == 128;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * IMG + (KV_LDS ? 2 * 64 * BROWB : 0)];
     __shared__ __attribute__((aligned(16))) float s_lse2[SLOTS], s_delta[SLOTS];
     __shared__ __attribute__((aligned(16))) unsigned long long s_mask[SLOTS];
     __shared__ int s_tilefull[KB_NCT];  // every used slot of the tile covers all 64 keys of the block: the mask test is skipped
     __shared__ int s_t[512];
     __shared__ unsigned long long s_m[512];
-    unsigned char *k_img = lds, *v_img = lds + 64 * BROWB;
+    unsigned char *k_img = KV_LDS ? lds + 2 * IMG : lds, *v_img = k_img + 64 * BROWB;
     unsigned char *q_img = lds, *do_img = lds + IMG;
 
 #ifdef NSA_DBG_WGTIME
@@ -617,34 +652,38 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(SelAttnBwdParams P, co
 
     // ---- K_j, V_j -> LDS (row images); rows past S_kv re-read the last row (never covered by a mask)
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int p = tid + 256 * i, r = p >> 3, pc = p & 7;
+    for (int i = 0; i < 64 * PIECES / 256; ++i) {
+        const int p = tid + 256 * i, r = p / PIECES, pc = p % PIECES;
         const int64_t kr = min(key0 + r, P.S_kv - 1);
-        *(u32x4 *)(k_img + off_row_img(r, pc)) = *(const u32x4 *)(Kb + kr * P.kss + pc * 8);
-        *(u32x4 *)(v_img + off_row_img(r, pc)) = *(const u32x4 *)(Vb + kr * P.vss + pc * 8);
+        *(u32x4 *)(k_img + Gm::off_row_img(r, pc)) = *(const u32x4 *)(Kb + kr * P.kss + pc * 8);
+        *(u32x4 *)(v_img + Gm::off_row_img(r, pc)) = *(const u32x4 *)(Vb + kr * P.vss + pc * 8);
     }
     __syncthreads();
     // B operands of S = Q.K^T and dP = dO.V^T for this wave's 16 keys: loop invariant
-    x8 kB[2], vB[2];
+    x8 kB[KV_LDS ? 1 : KS], vB[KV_LDS ? 1 : KS];
+    uint32_t kvrd[KS];
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        kB[s] = *(const x8 *)(k_img + off_row_img(16 * wave + rho, 4 * s + q));
-        vB[s] = *(const x8 *)(v_img + off_row_img(16 * wave + rho, 4 * s + q));
+    for (int s = 0; s < KS; ++s) {
+        kvrd[s] = Gm::off_row_img(16 * wave + rho, 4 * s + q);
+        if constexpr (!KV_LDS) {
+            kB[s] = *(const x8 *)(k_img + kvrd[s]);
+            vB[s] = *(const x8 *)(v_img + kvrd[s]);
+        }
     }
     __syncthreads();
-    f32x4 dK[4], dV[4];
+    f32x4 dK[MT], dV[MT];
 #pragma unroll
-    for (int n = 0; n < 4; ++n) {
+    for (int n = 0; n < MT; ++n) {
         dK[n] = (f32x4){0.f, 0.f, 0.f, 0.f};
         dV[n] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
-    uint32_t rd_row[2], rd_tr[4];
+    uint32_t rd_row[KS], rd_tr[MT];
 #pragma unroll
-    for (int s = 0; s < 2; ++s) rd_row[s] = off_tr_img(rho, 4 * s + q);
+    for (int s = 0; s < KS; ++s) rd_row[s] = Gm::off_tr_img(rho, 4 * s + q);
     {
         const int qq = rho >> 2, pp = rho & 3, r = 4 * q + qq;
 #pragma unroll
-        for (int n = 0; n < 4; ++n) rd_tr[n] = r * BROWB + ((n ^ bswz_tr(r)) << 5) + 8 * pp;
+        for (int n = 0; n < MT; ++n) rd_tr[n] = r * BROWB + ((n ^ Gm::swz_tr(r)) << 5) + 8 * pp;
     }
 
     // query rows are split over gridDim.z workgroups per key block (block 0 and the local blocks are selected by every
@@ -714,15 +753,15 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(SelAttnBwdParams P, co
 #endif
 #pragma unroll
             for (int i = 0; i < NLD; ++i) {
-                const int p = tid + 256 * i, slot = p >> 3, pc = p & 7;
+                const int p = tid + 256 * i, slot = p / PIECES, pc = p % PIECES;
                 const int qi = slot / h, hh = slot - qi * h;
                 const int li = r0 + qi;
                 qa[i] = (u32x4){0u, 0u, 0u, 0u};
                 da[i] = (u32x4){0u, 0u, 0u, 0u};
                 if (qi < rows_per_round && li < nhit) {
                     const int64_t rrow = ((int64_t)b * P.S + s_t[li]) * P.G + g;
-                    qa[i] = *(const u32x4 *)((const T *)P.Q + (rrow * h + hh) * (int64_t)BD + pc * 8);
-                    da[i] = *(const u32x4 *)((const T *)P.dO + (rrow * h + hh) * (int64_t)BD + pc * 8);
+                    qa[i] = *(const u32x4 *)((const T *)P.Q + (rrow * h + hh) * (int64_t)D + pc * 8);
+                    da[i] = *(const u32x4 *)((const T *)P.dO + (rrow * h + hh) * (int64_t)D + pc * 8);
                 }
             }
             l2n = 0.f;
@@ -739,14 +778,15 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(SelAttnBwdParams P, co
                 }
             }
         };
-        if (nhit > 0) fetch_round(0);
+        if (PREFETCH && nhit > 0) fetch_round(0);
         for (int r0 = 0; r0 < nhit; r0 += rows_per_round) {
+            if (!PREFETCH) fetch_round(r0);
             // stage Q and dO rows of every slot twice (row image + transposable image), plus lse / delta / mask per slot
 #pragma unroll
             for (int i = 0; i < NLD; ++i) {
-                const int p = tid + 256 * i, slot = p >> 3, pc = p & 7;
-                *(u32x4 *)(q_img + off_tr_img(slot, pc)) = qa[i];
-                *(u32x4 *)(do_img + off_tr_img(slot, pc)) = da[i];
+                const int p = tid + 256 * i, slot = p / PIECES, pc = p % PIECES;
+                *(u32x4 *)(q_img + Gm::off_tr_img(slot, pc)) = qa[i];
+                *(u32x4 *)(do_img + Gm::off_tr_img(slot, pc)) = da[i];
             }
             if (tid < SLOTS) {
                 s_lse2[tid] = l2n;
@@ -758,7 +798,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(SelAttnBwdParams P, co
                 const unsigned long long fb = __ballot(fullslot);  // waves 0 and 1: 64 slots = 4 tiles each
                 if (lane < 4) s_tilefull[4 * wave + lane] = ((fb >> (16 * lane)) & 0xffffull) == 0xffffull;
             }
-            if (r0 + rows_per_round < nhit) fetch_round(r0 + rows_per_round);
+            if (PREFETCH && r0 + rows_per_round < nhit) fetch_round(r0 + rows_per_round);
             __syncthreads();
             // column tiles go in PAIRS: the dV / dK products contract over the 32 (row, head) slots of two tiles with ONE 16x16x32 MFMA per
             // 16 output columns (round 4: the 16x16x16 form they used costs the same issue cycles for half the work --
@@ -777,9 +817,11 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(SelAttnBwdParams P, co
                     const int sbase = 16 * (ct + half);
                     f32x4 S = {0.f, 0.f, 0.f, 0.f}, dP = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                    for (int s = 0; s < 2; ++s) {
-                        S = M::mma32(*(const x8 *)(q_img + rd_row[s] + sbase * BROWB), kB[s], S);
-                        dP = M::mma32(*(const x8 *)(do_img + rd_row[s] + sbase * BROWB), vB[s], dP);
+                    for (int s = 0; s < KS; ++s) {
+                        const x8 kb = KV_LDS ? *(const x8 *)(k_img + kvrd[s]) : kB[KV_LDS ? 0 : s];
+                        const x8 vb = KV_LDS ? *(const x8 *)(v_img + kvrd[s]) : vB[KV_LDS ? 0 : s];
+                        S = M::mma32(*(const x8 *)(q_img + rd_row[s] + sbase * BROWB), kb, S);
+                        dP = M::mma32(*(const x8 *)(do_img + rd_row[s] + sbase * BROWB), vb, dP);
                     }
                     // accumulator rows = slots sbase + 4q + r, column = key 16 wave + rho
                     const f32x4 l2 = *(const f32x4 *)(s_lse2 + sbase + 4 * q);
@@ -802,9 +844,11 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(SelAttnBwdParams P, co
                             dsa8[4 * half + r] = Elt<T>::from_f(p * (dP[r] - dl[r]));
                         }
                     }
+                    // D = 128: the second half's fragment reads are not hoisted above the first half's MFMAs (their registers would not fit)
+                    if constexpr (D == 128) __builtin_amdgcn_sched_barrier(0);
                 }
 #pragma unroll
-                for (int n = 0; n < 4; ++n) {
+                for (int n = 0; n < MT; ++n) {
                     const x4 d0 = tr_read<x4>(do_img + rd_tr[n] + 16 * ct * BROWB), d1 = tr_read<x4>(do_img + rd_tr[n] + 16 * (ct + 1) * BROWB);
                     const x4 q0 = tr_read<x4>(q_img + rd_tr[n] + 16 * ct * BROWB), q1 = tr_read<x4>(q_img + rd_tr[n] + 16 * (ct + 1) * BROWB);
                     x8 db, qb;
@@ -841,32 +885,33 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(SelAttnBwdParams P, co
         if (tid == 0) flags[((int64_t)zsp * nbg + bg) * nkb + j] = total_hits > 0;
         if (total_hits == 0) return;
     }
-    const int64_t slab = (int64_t)nbg * P.S_kv * BD;  // floats of one [B*G,S_kv,D] tensor
-    float *dKb = (nsplit > 1 ? part + (int64_t)zsp * 2 * slab : P.dK) + ((int64_t)bg * P.S_kv) * BD;
-    float *dVb = (nsplit > 1 ? part + (int64_t)zsp * 2 * slab + slab : P.dV) + ((int64_t)bg * P.S_kv) * BD;
+    const int64_t slab = (int64_t)nbg * P.S_kv * D;  // floats of one [B*G,S_kv,D] tensor
+    float *dKb = (nsplit > 1 ? part + (int64_t)zsp * 2 * slab : P.dK) + ((int64_t)bg * P.S_kv) * D;
+    float *dVb = (nsplit > 1 ? part + (int64_t)zsp * 2 * slab + slab : P.dV) + ((int64_t)bg * P.S_kv) * D;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int key = key0 + 16 * wave + 4 * q + r;
         if (key < P.S_kv) {
 #pragma unroll
-            for (int n = 0; n < 4; ++n) {
-                dKb[(int64_t)key * BD + 16 * n + rho] = dK[n][r] * P.scale;
-                dVb[(int64_t)key * BD + 16 * n + rho] = dV[n][r];
+            for (int n = 0; n < MT; ++n) {
+                dKb[(int64_t)key * D + 16 * n + rho] = dK[n][r] * P.scale;
+                dVb[(int64_t)key * D + 16 * n + rho] = dV[n][r];
             }
         }
     }
 }
 
 // sum the row-split partials [ns][2][slab] into dK / dV in ascending split order (splits without hits are skipped)
+template <int D>
 __global__ __launch_bounds__(256) void bwd_reduce_kernel(const float *__restrict__ part, const int *__restrict__ flags,
                                                           float *__restrict__ dK, float *__restrict__ dV, int64_t slab, int ns, int S_kv,
                                                           int nkb) {
     const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (i >= 2 * slab) return;
     const int64_t e = i < slab ? i : i - slab;
-    const int64_t krow = e / BD, bg = krow / S_kv;
+    const int64_t krow = e / D, bg = krow / S_kv;
     const int jb = (int)(krow - bg * S_kv) >> 6;
-    const int64_t nfl = slab / BD / S_kv * nkb;  // flags per split
+    const int64_t nfl = slab / D / S_kv * nkb;  // flags per split
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     for (int z = 0; z < ns; ++z)
         if (flags[z * nfl + bg * nkb + jb]) acc += *(const f32x4 *)(part + (int64_t)z * 2 * slab + i);
@@ -921,7 +966,7 @@ static int dkdv_splits(int S) {
 }
 
 bool sel_attn_bwd_mfma_supported(int dtype, int h, int Dk, int Dv) {
-    return (dtype == NSA_DT_BF16 || dtype == NSA_DT_F16) && Dk == 64 && Dv == 64 && h >= 1 && h <= 16;
+    return (dtype == NSA_DT_BF16 || dtype == NSA_DT_F16) && Dk == Dv && (Dk == 64 || Dk == 128) && h >= 1 && h <= 16;
 }
 
 // workspace layout: delta [R*h] f32 | hit map [nbg][nkb][ceil(S/64)] u64 | full map (same shape) | flags [ns][nbg][nkb] i32 | ns partial [dK|dV] slabs
@@ -929,7 +974,7 @@ struct BwdWs {
     size_t hitmap, fullmap, flags, part, total, hitmap_bytes;
     int ns, nkb;
 };
-static BwdWs bwd_ws_layout(int64_t R, int h, int S, int64_t nbg, int S_kv) {
+static BwdWs bwd_ws_layout(int64_t R, int h, int S, int64_t nbg, int S_kv, int D) {
     BwdWs w;
     w.ns = dkdv_splits(S);
     w.nkb = (S_kv + 63) / 64;
@@ -939,17 +984,19 @@ static BwdWs bwd_ws_layout(int64_t R, int h, int S, int64_t nbg, int S_kv) {
     w.fullmap = w.hitmap + up(w.hitmap_bytes);
     w.flags = w.fullmap + up(w.hitmap_bytes);
     w.part = w.flags + up(sizeof(int) * (size_t)w.ns * nbg * w.nkb);
-    w.total = w.part + (w.ns > 1 ? sizeof(float) * (size_t)w.ns * 2 * (size_t)nbg * S_kv * BD : 0);
+    w.total = w.part + (w.ns > 1 ? sizeof(float) * (size_t)w.ns * 2 * (size_t)nbg * S_kv * D : 0);
     return w;
 }
-size_t sel_attn_bwd_mfma_workspace(int64_t R, int h, int S, int64_t nbg, int S_kv) { return bwd_ws_layout(R, h, S, nbg, S_kv).total; }
+size_t sel_attn_bwd_mfma_workspace(int64_t R, int h, int S, int64_t nbg, int S_kv, int D) {
+    return bwd_ws_layout(R, h, S, nbg, S_kv, D).total;
+}
 
-template <typename T>
+template <typename T, int D>
 static int launch_bwd_t(const SelAttnBwdParams &P, float *delta, hipStream_t st) {
     const int64_t nrh = P.R * P.h;
     if (!P.skip_delta_dq) {
-        hipLaunchKernelGGL(bwd_delta_kernel<T>, dim3((unsigned)((nrh * 8 + 255) / 256)), dim3(256), 0, st, (const T *)P.O, (const T *)P.dO,
-                           delta, nrh, P.Dv);
+        hipLaunchKernelGGL((bwd_delta_kernel<T, D>), dim3((unsigned)((nrh * (D / 8) + 255) / 256)), dim3(256), 0, st, (const T *)P.O,
+                           (const T *)P.dO, delta, nrh, P.Dv);
         NSA_LAUNCH_CHECK("bwd_delta");
     }
     int map_mode = 0;
@@ -961,7 +1008,7 @@ static int launch_bwd_t(const SelAttnBwdParams &P, float *delta, hipStream_t st)
             grid = (unsigned)(nbg * W);
         }
     }
-    constexpr size_t lds = 4 * (3 * 32 * BROWB + ((SEG_INTS * 4 + 15) / 16) * 16);
+    constexpr size_t lds = 4 * (size_t)bwd_dq_wave_lds<D>();  // 50 KiB (D = 64), 98 KiB (D = 128: one workgroup per CU)
     if (!P.skip_delta_dq) {
         // rows of one wave share the K/V tile images when 16/h >= 2 rows fit the MFMA columns (NSA_HIP_SEL_ROWS=0: one row per wave)
         int tpw = 16 / P.h;
@@ -969,22 +1016,24 @@ static int launch_bwd_t(const SelAttnBwdParams &P, float *delta, hipStream_t st)
         const int nw = ((P.S_kv + 31) / 32 + 31) / 32;
         if (tpw >= 2 && P.S >= 2 * tpw && P.n >= 1 && P.n <= 64 && nw <= 128) {
             const int rg_ints = (2 * tpw * P.n + 3) & ~3, bm_ints = (2 * tpw * nw + 16 + 3) & ~3;
-            const int wave_lds = 2 * 32 * BROWB + 4 * (rg_ints + bm_ints);
+            const int wave_lds = 2 * 32 * BGeo<D>::ROWB + 4 * (rg_ints + bm_ints);
             const int64_t nbg2 = P.R / P.S, ngrp = (P.S + tpw - 1) / tpw, W4 = (ngrp + 3) / 4;
             NSA_CHECK_ARG(nbg2 * W4 < ((int64_t)1 << 31) && 4 * (size_t)wave_lds <= 160 * 1024, "bwd_dq_rows: launch too large");
             if (4 * (size_t)wave_lds > 64 * 1024)
-                NSA_HIP_TRY(hipFuncSetAttribute((const void *)bwd_dq_rows_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * wave_lds));
-            hipLaunchKernelGGL(bwd_dq_rows_kernel<T>, dim3((unsigned)(nbg2 * W4)), dim3(256), 4 * (size_t)wave_lds, st, P, (const float *)delta,
+                NSA_HIP_TRY(hipFuncSetAttribute((const void *)bwd_dq_rows_kernel<T, D>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * wave_lds));
+            hipLaunchKernelGGL((bwd_dq_rows_kernel<T, D>), dim3((unsigned)(nbg2 * W4)), dim3(256), 4 * (size_t)wave_lds, st, P, (const float *)delta,
                                (nbg2 % 8 == 0) ? 2 : 1, tpw, nw, wave_lds);
             NSA_LAUNCH_CHECK("bwd_dq_rows");
         } else {
-            hipLaunchKernelGGL(bwd_dq_kernel<T>, dim3(grid), dim3(256), lds, st, P, (const float *)delta, map_mode);
+            if (lds > 64 * 1024)
+                NSA_HIP_TRY(hipFuncSetAttribute((const void *)bwd_dq_kernel<T, D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL((bwd_dq_kernel<T, D>), dim3(grid), dim3(256), lds, st, P, (const float *)delta, map_mode);
             NSA_LAUNCH_CHECK("bwd_dq");
         }
     }
     const int64_t nbg = (int64_t)(P.R / P.S);
     NSA_CHECK_ARG(nbg <= 65535, "bwd: B*G too large for one launch");
-    const BwdWs W = bwd_ws_layout(P.R, P.h, P.S, nbg, P.S_kv);
+    const BwdWs W = bwd_ws_layout(P.R, P.h, P.S, nbg, P.S_kv, D);
     const int ns = W.ns;
     const int rows_per_split = ((P.S + ns - 1) / ns + 255) / 256 * 256;
     unsigned char *ws = (unsigned char *)delta;
@@ -999,12 +1048,12 @@ static int launch_bwd_t(const SelAttnBwdParams &P, float *delta, hipStream_t st)
     NSA_LAUNCH_CHECK("bwd_hitmap");
     const int64_t ngrid = ((nbg * ns + 7) / 8) * 8 * W.nkb;
     NSA_CHECK_ARG(ngrid < ((int64_t)1 << 31), "bwd: too many key-block workgroups for one launch");
-    hipLaunchKernelGGL(bwd_dkdv_kernel<T>, dim3((unsigned)ngrid), dim3(256), 0, st, P, (const float *)delta, part,
+    hipLaunchKernelGGL((bwd_dkdv_kernel<T, D>), dim3((unsigned)ngrid), dim3(256), 0, st, P, (const float *)delta, part,
                        (const unsigned long long *)hitmap, (const unsigned long long *)fullmap, flags, rows_per_split, W.nkb, (int)nbg, ns);
     NSA_LAUNCH_CHECK("bwd_dkdv");
     if (ns > 1) {
-        const int64_t slab = nbg * P.S_kv * BD;
-        hipLaunchKernelGGL(bwd_reduce_kernel, dim3((unsigned)((2 * slab / 4 + 255) / 256)), dim3(256), 0, st, (const float *)part,
+        const int64_t slab = nbg * P.S_kv * D;
+        hipLaunchKernelGGL(bwd_reduce_kernel<D>, dim3((unsigned)((2 * slab / 4 + 255) / 256)), dim3(256), 0, st, (const float *)part,
                            (const int *)flags, P.dK, P.dV, slab, ns, P.S_kv, W.nkb);
         NSA_LAUNCH_CHECK("bwd_reduce");
     }
@@ -1022,15 +1071,24 @@ int launch_sel_attn_bwd_mfma(const SelAttnBwdParams &P, int dtype, float *delta_
                   "bwd MFMA: K/V strides must be multiples of 8 elements");
     NSA_CHECK_ARG((int64_t)P.S_kv * P.kss * 2 < ((int64_t)1 << 31) && (int64_t)P.S_kv * P.vss * 2 < ((int64_t)1 << 31),
                   "bwd MFMA: one (b,g) K/V slab must be smaller than 2 GiB");
-    if (dtype == NSA_DT_BF16) return launch_bwd_t<__bf16>(P, delta_ws, st);
-    return launch_bwd_t<_Float16>(P, delta_ws, st);
+    if (dtype == NSA_DT_BF16) return P.Dk == 64 ? launch_bwd_t<__bf16, 64>(P, delta_ws, st) : launch_bwd_t<__bf16, 128>(P, delta_ws, st);
+    return P.Dk == 64 ? launch_bwd_t<_Float16, 64>(P, delta_ws, st) : launch_bwd_t<_Float16, 128>(P, delta_ws, st);
+}
+
+template <typename T>
+static void launch_bwd_delta_t(const void *O, const void *dO, float *delta, int64_t n_rows, int Dv, hipStream_t st) {
+    if (Dv == 64)
+        hipLaunchKernelGGL((bwd_delta_kernel<T, 64>), dim3((unsigned)((n_rows * 8 + 255) / 256)), dim3(256), 0, st, (const T *)O, (const T *)dO,
+                           delta, n_rows, Dv);
+    else
+        hipLaunchKernelGGL((bwd_delta_kernel<T, 128>), dim3((unsigned)((n_rows * 16 + 255) / 256)), dim3(256), 0, st, (const T *)O, (const T *)dO,
+                           delta, n_rows, Dv);
 }
 
 int launch_bwd_delta(const void *O, const void *dO, float *delta, int64_t n_rows, int Dv, int dtype, hipStream_t st) {
-    NSA_CHECK_ARG(Dv == 64 && (dtype == NSA_DT_BF16 || dtype == NSA_DT_F16), "bwd_delta: bf16/f16 with Dv = 64 only");
-    const dim3 grid((unsigned)((n_rows * 8 + 255) / 256));
-    if (dtype == NSA_DT_BF16) hipLaunchKernelGGL(bwd_delta_kernel<__bf16>, grid, dim3(256), 0, st, (const __bf16 *)O, (const __bf16 *)dO, delta, n_rows, Dv);
-    else hipLaunchKernelGGL(bwd_delta_kernel<_Float16>, grid, dim3(256), 0, st, (const _Float16 *)O, (const _Float16 *)dO, delta, n_rows, Dv);
+    NSA_CHECK_ARG((Dv == 64 || Dv == 128) && (dtype == NSA_DT_BF16 || dtype == NSA_DT_F16), "bwd_delta: bf16/f16 with Dv = 64 or 128 only");
+    if (dtype == NSA_DT_BF16) launch_bwd_delta_t<__bf16>(O, dO, delta, n_rows, Dv, st);
+    else launch_bwd_delta_t<_Float16>(O, dO, delta, n_rows, Dv, st);
     NSA_LAUNCH_CHECK("bwd_delta");
     return NSA_OK;
 }

@@ -122,7 +122,7 @@ int launch_sel_attn_rows_mfma(const SelAttnParams &P, int dtype, int tpw, int nt
 int sel_attn_blocks_nt(int dtype, int h, int Dk, int Dv, int S, int S_kv, int n, int64_t R, int64_t kss, int64_t vss);
 int launch_sel_attn_blocks_mfma(const SelAttnParams &P, int dtype, int nt, hipStream_t st);
 bool sel_attn_bwd_mfma_supported(int dtype, int h, int Dk, int Dv);
-size_t sel_attn_bwd_mfma_workspace(int64_t R, int h, int S, int64_t nbg, int S_kv);
+size_t sel_attn_bwd_mfma_workspace(int64_t R, int h, int S, int64_t nbg, int S_kv, int D);  // D = Dk = Dv
 int launch_sel_attn_bwd_mfma(const SelAttnBwdParams &P, int dtype, float *delta_ws, hipStream_t st);
 
 }  // namespace nsa

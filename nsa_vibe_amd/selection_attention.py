@@ -77,11 +77,11 @@ class _SelAttnFn(torch.autograd.Function):
     nsa/kernels/triton_sel_kernel/__init__.py:125-142: save Q,K,V,ranges; backward -> dQ,dK,dV,None)."""
 
     @staticmethod
-    def forward(ctx, Q, K, V, ranges, scale, variant):
+    def forward(ctx, Q, K, V, ranges, scale, variant, bwd_variant):
         O, lse, (Qc, Kc, Vc, rg) = _fwd(Q, K, V, ranges, scale, variant, True)
         ctx.save_for_backward(Qc, Kc, Vc, rg, O, lse)
         ctx.scale = scale
-        ctx.bwd_variant = 0 if variant != 1 else 1  # variant 1 keeps the generic kernels on both passes
+        ctx.bwd_variant = _bwd_variant(variant, bwd_variant)
         return O
 
     @staticmethod
@@ -103,18 +103,31 @@ class _SelAttnFn(torch.autograd.Function):
                                 _DT[Qc.dtype], float(ctx.scale) if ctx.scale else 0.0, int(ctx.bwd_variant),
                                 ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, _stream(dev))
         _lib.check(rc, "nsa_sel_attn_bwd")
-        return dQ, dK.to(Kc.dtype), dV.to(Vc.dtype), None, None, None
+        return dQ, dK.to(Kc.dtype), dV.to(Vc.dtype), None, None, None, None
+
+
+def _bwd_variant(variant: int, bwd_variant: Optional[int]) -> int:
+    """Kernel choice of the backward: an explicit bwd_variant, else 0 (auto) unless the forward was asked for the generic kernel
+    (variant 1 keeps the generic kernels on both passes)."""
+    if bwd_variant is None:
+        return 0 if variant != 1 else 1
+    if bwd_variant not in (0, 1, 2):
+        raise ValueError(f"bwd_variant must be None, 0, 1 or 2 (got {bwd_variant})")
+    return int(bwd_variant)
 
 
 def selection_attention_hip(Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, ranges: torch.Tensor, *,
-                            scale: Optional[float] = None, variant: int = 0, return_lse: bool = False):
+                            scale: Optional[float] = None, variant: int = 0, return_lse: bool = False,
+                            bwd_variant: Optional[int] = None):
     """The MI355X selection executor (drop-in for selection_attention_cuda / grouped_selection_attention_masked).
 
-    variant: 0 auto (MFMA kernel when dtype/shape allow, else the generic kernel), 1 generic, 2 MFMA."""
+    variant: 0 auto (MFMA kernel when dtype/shape allow, else the generic kernel), 1 generic, 2 MFMA.
+    bwd_variant: the same choice for the backward; None = 0 (auto) unless variant is 1.  2 raises where the MFMA backward does not
+    cover the shape (bf16/f16, Dk = Dv = 64 or 128, h <= 16, 16-byte aligned K/V strides)."""
     if torch.is_grad_enabled() and (Q.requires_grad or K.requires_grad or V.requires_grad):
         if return_lse:
             raise RuntimeError("return_lse is not available on the autograd path")
-        return _SelAttnFn.apply(Q, K, V, ranges, scale, variant)
+        return _SelAttnFn.apply(Q, K, V, ranges, scale, variant, bwd_variant)
     O, lse, _ = _fwd(Q, K, V, ranges, scale, variant, return_lse)
     return (O, lse) if return_lse else O
 
