@@ -659,3 +659,144 @@ NSA_API void nsa_oracle_set_num_threads(int n) {
     (void)n;
 #endif
 }
+
+/* ------------------------------------------------------------------------- */
+/* Gate MLP + three-branch mix  (nsa/core/nsa_attention.py:32-82, 1380-1395)  */
+/* ------------------------------------------------------------------------- */
+
+/*
+ * One row: the fp32 logits and gates of GateMLP.forward (nsa/core/nsa_attention.py:71-81) on the pooled query q_gp = Q.mean(dim=3)
+ * (:1381).  Dot products and the head mean accumulate in double and round once to fp32, at the points where the fp32 PyTorch ops round
+ * (mean, fc1 + bias, silu, fc2 + bias, / max(tau, 1e-6), softmax).  qp [Dk], act [Hd] and pre [Hd] (fc1 output) are written for the
+ * backward.  Returns 1 when the row is "peaked" (top-2 logit gap > 50, :77-81: one-hot of the argmax, first index on ties).
+ */
+static int gate_row(const float *Q, int h, int Dk, int Hd, const float *w1, const float *b1, const float *w2, const float *b2,
+                    float tau, float *qp, float *pre, float *act, float *lg, float *p) {
+    for (int k = 0; k < Dk; ++k) { /* :1381 Q.mean(dim=3) */
+        double a = 0.0;
+        for (int i = 0; i < h; ++i) a += (double)Q[(int64_t)i * Dk + k];
+        qp[k] = (float)(a / (double)h);
+    }
+    for (int j = 0; j < Hd; ++j) { /* :71 silu(fc1(q)) */
+        double a = 0.0;
+        for (int k = 0; k < Dk; ++k) a += (double)w1[(int64_t)j * Dk + k] * (double)qp[k];
+        pre[j] = (float)(a + (double)b1[j]);
+        act[j] = (float)((double)pre[j] / (1.0 + exp(-(double)pre[j])));
+    }
+    const float td = tau > 1e-6f ? tau : 1e-6f; /* :72 / max(tau, 1e-6) */
+    for (int c = 0; c < 3; ++c) {
+        double a = 0.0;
+        for (int j = 0; j < Hd; ++j) a += (double)w2[c * Hd + j] * (double)act[j];
+        const float z = (float)(a + (double)b2[c]);
+        lg[c] = z / td;
+    }
+    float mx = lg[0];
+    int arg = 0;
+    for (int c = 1; c < 3; ++c)
+        if (lg[c] > mx) { mx = lg[c]; arg = c; }
+    double e[3], den = 0.0; /* :73 softmax */
+    for (int c = 0; c < 3; ++c) { e[c] = exp((double)lg[c] - (double)mx); den += e[c]; }
+    float second = -INFINITY;
+    for (int c = 0; c < 3; ++c)
+        if (c != arg && lg[c] > second) second = lg[c];
+    const int peaked = (lg[arg] - second) > 50.0f; /* :76-78 */
+    for (int c = 0; c < 3; ++c) p[c] = peaked ? (c == arg ? 1.0f : 0.0f) : (float)(e[c] / den);
+    return peaked;
+}
+
+/*
+ * nsa/core/nsa_attention.py:1380-1395 (prefill; the decode form :931-950 is the same expression per [B,G] row): gates [R,3] of
+ * GateMLP.forward and O = w_cmp * O_cmp + w_sel * O_sel + w_win * O_win in fp32, left to right, one rounding per op.
+ * Q [R,h,Dk]; O_cmp, O_sel, O_win, O [R,h,Dv]; w1 [Hd,Dk], b1 [Hd], w2 [3,Hd], b2 [3].  logits [R,3] may be NULL.
+ */
+NSA_API void nsa_oracle_gate_combine(const float *Q, const float *Oc, const float *Os, const float *Ow, const float *w1, const float *b1,
+                                     const float *w2, const float *b2, long R, int h, int Dk, int Dv, int Hd, float tau, float *gates,
+                                     float *O, float *logits) {
+#pragma omp parallel for schedule(static)
+    for (long r = 0; r < R; ++r) {
+        float *qp = (float *)malloc(sizeof(float) * (size_t)(Dk + 2 * Hd));
+        float *pre = qp + Dk, *act = pre + Hd;
+        float lg[3], p[3];
+        gate_row(Q + (int64_t)r * h * Dk, h, Dk, Hd, w1, b1, w2, b2, tau, qp, pre, act, lg, p);
+        for (int c = 0; c < 3; ++c) {
+            gates[r * 3 + c] = p[c];
+            if (logits) logits[r * 3 + c] = lg[c];
+        }
+        const int64_t base = (int64_t)r * h * Dv;
+        for (int e = 0; e < h * Dv; ++e) {
+            const float t1 = p[0] * Oc[base + e], t2 = p[1] * Os[base + e];
+            const float t3 = t1 + t2, t4 = p[2] * Ow[base + e];
+            O[base + e] = t3 + t4;
+        }
+        free(qp);
+    }
+}
+
+/*
+ * Gradient of nsa_oracle_gate_combine (the autograd of nsa/core/nsa_attention.py:70-81 + 1392-1395) for the upstream gradient dO [R,h,Dv]:
+ *   dO_i = gate_i dO (fp32 products), dgates [R,3] = sum_{h,d} O_i dO;
+ *   peaked rows: the gates are the one-hot (torch.where of :81 passes no gradient to the softmax) -> no gradient into the MLP;
+ *   else dlogit = p (dgates - <p, dgates>) / max(tau, 1e-6), then fc2, silu'(x) = s(x)(1 + x (1 - s(x))), fc1, and dQ = dq_gp / h
+ *   on every head (the mean).  dW1 [Hd,Dk], db1 [Hd], dW2 [3,Hd], db2 [3] are summed over the R rows.  Inner math in double.
+ */
+NSA_API void nsa_oracle_gate_combine_bwd(const float *Q, const float *Oc, const float *Os, const float *Ow, const float *w1, const float *b1,
+                                         const float *w2, const float *b2, const float *dO, long R, int h, int Dk, int Dv, int Hd, float tau,
+                                         float *dOc, float *dOs, float *dOw, float *dgates, float *dQ, float *dW1, float *db1, float *dW2,
+                                         float *db2) {
+    double *aW1 = (double *)calloc((size_t)Hd * Dk + Hd + 3 * (size_t)Hd + 3, sizeof(double));
+    double *ab1 = aW1 + (size_t)Hd * Dk, *aW2 = ab1 + Hd, *ab2 = aW2 + 3 * Hd;
+    float *qp = (float *)malloc(sizeof(float) * (size_t)(Dk + 2 * Hd));
+    float *pre = qp + Dk, *act = pre + Hd;
+    double *da = (double *)malloc(sizeof(double) * (size_t)(Hd + Dk));
+    double *dq = da + Hd;
+    const double td = tau > 1e-6f ? (double)tau : (double)1e-6f;
+    for (long r = 0; r < R; ++r) {
+        float lg[3], p[3];
+        const int peaked = gate_row(Q + (int64_t)r * h * Dk, h, Dk, Hd, w1, b1, w2, b2, tau, qp, pre, act, lg, p);
+        const int64_t base = (int64_t)r * h * Dv;
+        double dg[3] = {0.0, 0.0, 0.0};
+        for (int e = 0; e < h * Dv; ++e) {
+            const float d = dO[base + e];
+            dOc[base + e] = p[0] * d;
+            dOs[base + e] = p[1] * d;
+            dOw[base + e] = p[2] * d;
+            dg[0] += (double)Oc[base + e] * d;
+            dg[1] += (double)Os[base + e] * d;
+            dg[2] += (double)Ow[base + e] * d;
+        }
+        for (int c = 0; c < 3; ++c) dgates[r * 3 + c] = (float)dg[c];
+        float *dQr = dQ + (int64_t)r * h * Dk;
+        if (peaked) {
+            memset(dQr, 0, sizeof(float) * (size_t)h * Dk);
+            continue;
+        }
+        const double dot = (double)p[0] * dg[0] + (double)p[1] * dg[1] + (double)p[2] * dg[2];
+        double dl[3];
+        for (int c = 0; c < 3; ++c) {
+            dl[c] = (double)p[c] * (dg[c] - dot) / td;
+            ab2[c] += dl[c];
+            for (int j = 0; j < Hd; ++j) aW2[c * Hd + j] += dl[c] * (double)act[j];
+        }
+        for (int j = 0; j < Hd; ++j) {
+            const double x = (double)pre[j], s = 1.0 / (1.0 + exp(-x));
+            const double dact = dl[0] * w2[j] + dl[1] * w2[Hd + j] + dl[2] * w2[2 * Hd + j];
+            da[j] = dact * s * (1.0 + x * (1.0 - s));
+            ab1[j] += da[j];
+            for (int k = 0; k < Dk; ++k) aW1[(int64_t)j * Dk + k] += da[j] * (double)qp[k];
+        }
+        for (int k = 0; k < Dk; ++k) {
+            double a = 0.0;
+            for (int j = 0; j < Hd; ++j) a += da[j] * (double)w1[(int64_t)j * Dk + k];
+            dq[k] = a / (double)h;
+        }
+        for (int i = 0; i < h; ++i)
+            for (int k = 0; k < Dk; ++k) dQr[(int64_t)i * Dk + k] = (float)dq[k];
+    }
+    for (int64_t i = 0; i < (int64_t)Hd * Dk; ++i) dW1[i] = (float)aW1[i];
+    for (int j = 0; j < Hd; ++j) db1[j] = (float)ab1[j];
+    for (int i = 0; i < 3 * Hd; ++i) dW2[i] = (float)aW2[i];
+    for (int c = 0; c < 3; ++c) db2[c] = (float)ab2[c];
+    free(da);
+    free(qp);
+    free(aW1);
+}

@@ -309,3 +309,34 @@ def num_threads() -> int:
 
 def set_num_threads(n: int) -> None:
     lib().nsa_oracle_set_num_threads(int(n))
+
+
+def gate_combine(Q, O_cmp, O_sel, O_win, w1, b1, w2, b2, tau: float, return_logits: bool = False):
+    """GateMLP.forward + the module's eager three-branch mix (nsa/core/nsa_attention.py:32-82, 1380-1395), fp32.
+    Q [R,h,Dk] (or [...,h,Dk]), O_* [R,h,Dv]; w1 [Hd,Dk], b1 [Hd], w2 [3,Hd], b2 [3] -> gates [R,3], O [R,h,Dv] (, logits [R,3])."""
+    Q, Oc, Os, Ow = _f32(Q), _f32(O_cmp), _f32(O_sel), _f32(O_win)
+    w1, b1, w2, b2 = _f32(w1), _f32(b1), _f32(w2), _f32(b2)
+    h, Dk, Dv, Hd = Q.shape[-2], Q.shape[-1], Oc.shape[-1], w1.shape[0]
+    R = Q.size // (h * Dk)
+    assert Oc.size == Os.size == Ow.size == R * h * Dv and w1.shape == (Hd, Dk) and w2.shape == (3, Hd)
+    gates, O, lg = np.zeros((R, 3), np.float32), np.zeros((R, h, Dv), np.float32), np.zeros((R, 3), np.float32)
+    lib().nsa_oracle_gate_combine(_p(Q), _p(Oc), _p(Os), _p(Ow), _p(w1), _p(b1), _p(w2), _p(b2), C.c_long(R), h, Dk, Dv, Hd,
+                                  C.c_float(tau), _p(gates), _p(O), _p(lg))
+    return (gates, O, lg) if return_logits else (gates, O)
+
+
+def gate_combine_bwd(Q, O_cmp, O_sel, O_win, w1, b1, w2, b2, tau: float, dO) -> dict:
+    """gradient of gate_combine for the upstream dO [R,h,Dv] -> dict dO_cmp, dO_sel, dO_win [R,h,Dv], dgates [R,3], dQ [R,h,Dk],
+    dW1, db1, dW2, db2 (summed over the rows; no gradient into the MLP from a peaked, one-hot row)"""
+    Q, Oc, Os, Ow, dO = _f32(Q), _f32(O_cmp), _f32(O_sel), _f32(O_win), _f32(dO)
+    w1, b1, w2, b2 = _f32(w1), _f32(b1), _f32(w2), _f32(b2)
+    h, Dk, Dv, Hd = Q.shape[-2], Q.shape[-1], Oc.shape[-1], w1.shape[0]
+    R = Q.size // (h * Dk)
+    assert Oc.size == Os.size == Ow.size == dO.size == R * h * Dv
+    out = dict(dO_cmp=np.zeros((R, h, Dv), np.float32), dO_sel=np.zeros((R, h, Dv), np.float32), dO_win=np.zeros((R, h, Dv), np.float32),
+               dgates=np.zeros((R, 3), np.float32), dQ=np.zeros((R, h, Dk), np.float32), dW1=np.zeros((Hd, Dk), np.float32),
+               db1=np.zeros(Hd, np.float32), dW2=np.zeros((3, Hd), np.float32), db2=np.zeros(3, np.float32))
+    lib().nsa_oracle_gate_combine_bwd(_p(Q), _p(Oc), _p(Os), _p(Ow), _p(w1), _p(b1), _p(w2), _p(b2), _p(dO), C.c_long(R), h, Dk, Dv, Hd,
+                                      C.c_float(tau), *(_p(out[k]) for k in ("dO_cmp", "dO_sel", "dO_win", "dgates", "dQ", "dW1", "db1",
+                                                                             "dW2", "db2")))
+    return out

@@ -180,3 +180,40 @@ def topn_gap(p_row, t, n_top=16, l_sel=64):
     k = np.sort(key[ok])[::-1]
     kk = n_top - 3
     return float(k[kk - 1] - k[kk]) if kk >= 1 and k.size > kk else float("inf")
+
+
+# g21: the gate MLP + three-branch mix of the reference module (oracle/make_gate_goldens.py).  Per case: Q [1,S,G,h,Dk] (post-RoPE query
+# rows of S tokens, G = 2 groups), the three branch outputs O_cmp / O_sel / O_win [1,S,G,h,Dv], the gate weights fc1 [Hd,Dk] + bias,
+# fc2 [3,Hd] + bias and a seeded upstream gradient dO; every value bf16-representable.  fc2 is scaled so the gates of a row span roughly
+# 0.05-0.9 (non-saturated, clearly non-uniform, each branch winning some rows); its bias shifts the three logits apart.  The first
+# G21_RD rows carry the dense outputs (O and the autograd gradients) in the fixture; every row carries its gates.
+G21_CASES = {  # name: (Dk, h, hidden, Dv, tau, fc2 gain, fc2 bias[, shift of the sel row of fc2 (peaked: half the rows beyond the gap 50)])
+    "m7c": (64, 6, 32, 64, 1.0, 1.0, (0.0, 0.4, -0.3)),
+    "boundary": (64, 8, 32, 64, 0.7, 0.8, (0.3, -0.2, 0.0)),
+    "wide_hidden": (64, 6, 64, 64, 2.0, 2.0, (-0.3, 0.0, 0.5)),
+    "many_heads": (64, 12, 32, 64, 1.0, 1.0, (0.0, 0.2, -0.2)),
+    "d128": (128, 6, 64, 128, 1.0, 1.0, (0.2, 0.0, -0.2)),
+    "tiny": (16, 4, 8, 16, 1.0, 1.0, (0.0, 0.3, -0.3)),
+    "odd_split": (40, 3, 20, 32, 1.0, 1.0, (-0.2, 0.3, 0.0)),
+    "peaked": (64, 6, 32, 64, 1.0, 2.0, (0.0, 50.0, 0.0), 7.0),
+    "clamp": (64, 6, 32, 64, 0.0, 1.0, (0.0, 0.0, 0.0)),
+}
+G21_S, G21_G, G21_RD = 48, 2, 6
+
+
+def g21_inputs(case):
+    """-> dict of fp32 arrays (bf16-representable) + scalars for one g21 case"""
+    Dk, h, Hd, Dv, tau, gain, bias = G21_CASES[case][:7]
+    shift = G21_CASES[case][7] if len(G21_CASES[case]) > 7 else 0.0
+    r = _rng(21, list(G21_CASES).index(case))
+    S, G = G21_S, G21_G
+    q = _bf16_round(randn(r, 1, S, G, h, Dk))
+    oc, os_, ow = (_bf16_round(randn(r, 1, S, G, h, Dv)) for _ in range(3))
+    w1 = _bf16_round(randn(r, Hd, Dk) * np.float32(2.0 / np.sqrt(Dk) * np.sqrt(h)))
+    b1 = _bf16_round(randn(r, Hd) * np.float32(0.1))
+    w2 = randn(r, 3, Hd) * np.float32(gain * 1.2 / np.sqrt(Hd))
+    w2[1] += np.float32(shift / Hd)
+    w2 = _bf16_round(w2)
+    b2 = _bf16_round(np.asarray(bias, np.float32))
+    dO = _bf16_round(randn(r, 1, S, G, h, Dv))
+    return dict(Q=q, O_cmp=oc, O_sel=os_, O_win=ow, w1=w1, b1=b1, w2=w2, b2=b2, dO=dO, tau=float(tau), h=h, Dk=Dk, Dv=Dv, Hd=Hd)

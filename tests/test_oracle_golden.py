@@ -293,3 +293,41 @@ def test_g20_tiny_bench_shape_selection_matches_the_oracle_selector(orc):
     for k, v in gi.g20_state(names_shapes).items():
         assert np.array_equal(torch.from_numpy(v).bfloat16().float().numpy(), v), k
     assert g["out_pre_seq"].shape == (1, S, 256) and g["out_dec"].shape == (gi.G20_N_DEC, 1, 1, 256)
+
+
+# ---- g21: gate MLP + three-branch mix (oracle/make_gate_goldens.py) ------------------------------------------------------------------
+def _g21(case):
+    x = gi.g21_inputs(case)
+    R, h, Dk, Dv = gi.G21_S * gi.G21_G, x["h"], x["Dk"], x["Dv"]
+    return x, R, x["Q"].reshape(R, h, Dk), [x[k].reshape(R, h, Dv) for k in ("O_cmp", "O_sel", "O_win")]
+
+
+@pytest.mark.parametrize("case", list(gi.G21_CASES))
+def test_g21_gate_oracle_matches_reference(orc, case):
+    """the oracle gate (nsa_oracle_gate_combine / _bwd) against the reference GateMLP + module mix and its autograd gradients"""
+    g = load_golden("g21_gate")
+    x, R, q, os_ = _g21(case)
+    RD = gi.G21_RD
+    gates, O, lg = orc.gate_combine(q, *os_, x["w1"], x["b1"], x["w2"], x["b2"], x["tau"], return_logits=True)
+    assert np.abs(gates - g[case + "_gates"]).max() <= 1e-6
+    scale = max(1.0, float(np.abs(g[case + "_O"]).max()))
+    assert np.abs(O[:RD] - g[case + "_O"]).max() <= 1e-5 * scale
+    lscale = max(1.0, float(np.abs(g[case + "_logits"]).max()))
+    assert np.abs(lg - g[case + "_logits"]).max() <= 1e-6 * lscale
+    # the one-hot rule on exactly the reference's rows (the fixture asserts no gap sits within rounding of 50).  In fp32 a softmax row has
+    # at most one exact zero (the second logit is within 50 of the first: exp(-50) is a normal float), a one-hot row has two.
+    peaked = g[case + "_gap"] > 50.0
+    assert np.array_equal((gates == 0.0).sum(1) == 2, peaked)
+    assert np.array_equal((g[case + "_gates"] == 0.0).sum(1) == 2, peaked)
+    bw = orc.gate_combine_bwd(q[:RD], *(o[:RD] for o in os_), x["w1"], x["b1"], x["w2"], x["b2"], x["tau"],
+                              x["dO"].reshape(R, x["h"], x["Dv"])[:RD])
+    for k in ("dQ", "dO_cmp", "dO_sel", "dO_win", "dW1", "db1", "dW2", "db2"):
+        ref = g[case + "_" + k]
+        err = float(np.abs(bw[k] - ref).max())
+        assert err <= 1e-5 * max(1.0, float(np.abs(ref).max())), (k, err)
+    dg = [(o[:RD] * x["dO"].reshape(R, x["h"], x["Dv"])[:RD]).astype(np.float64).sum((1, 2)) for o in os_]
+    assert np.abs(bw["dgates"] - np.stack(dg, 1)).max() <= 1e-4
+    if case == "peaked":
+        pk = peaked[:RD]
+        assert pk.any() and (~pk).any()
+        assert (bw["dQ"][pk] == 0).all() and (g[case + "_dQ"][pk] == 0).all()
