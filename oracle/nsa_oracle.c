@@ -800,3 +800,146 @@ NSA_API void nsa_oracle_gate_combine_bwd(const float *Q, const float *Oc, const 
     free(qp);
     free(aW1);
 }
+
+/* ------------------------------------------------------------------------- */
+/* RoPE and compressed-token pooling  (nsa/core/rope.py:6-51,                 */
+/* nsa/core/compress_pool.py:9-38)                                            */
+/* ------------------------------------------------------------------------- */
+
+/*
+ * dt: the activation dtype of the reference's chain, coded as the package's NSA_DT_* (0 fp32, 1 bf16, 2 fp16).  rnd_dt rounds a double
+ * the way a PyTorch CPU op of that dtype leaves its result: to fp32 first (the op's compute type), then round-to-nearest-even to the dtype.
+ */
+static float rnd_dt(double x, int dt) {
+    float f = (float)x;
+    if (dt == 1) { /* bf16: keep the top 16 bits, ties to even */
+        uint32_t u;
+        memcpy(&u, &f, 4);
+        if ((u & 0x7f800000u) != 0x7f800000u) {
+            u += 0x7fffu + ((u >> 16) & 1u);
+            u &= 0xffff0000u;
+            memcpy(&f, &u, 4);
+        }
+    } else if (dt == 2 && f != 0.0f && isfinite(f)) { /* fp16: 11 significant bits, subnormals below 2^-14 */
+        int e;
+        frexp((double)f, &e); /* |f| = m 2^e, m in [0.5, 1) */
+        const int q = (e - 1 < -14 ? -14 : e - 1) - 10;
+        const double r = nearbyint(ldexp((double)f, -q));
+        f = (float)ldexp(r, q);
+        if (fabsf(f) > 65504.0f) f = copysignf(INFINITY, f);
+    }
+    return f;
+}
+
+/* nsa/core/rope.py:6-13: inv_freq[i] = base ** (-2 i / D), the exponent an fp32 division, the power evaluated in double and rounded once */
+static float rope_freq(int i, int D, float base) {
+    const float e = (float)((-2.0 * (double)i) / (double)D);
+    return (float)pow((double)base, (double)e);
+}
+
+NSA_API void nsa_oracle_rope_inv_freq(int D, float base, float *out) {
+    for (int i = 0; i < D / 2; ++i) out[i] = rope_freq(i, D, base);
+}
+
+/* nsa/core/rope.py:38-44: angle = fl(fl(pos / scale) * inv_freq) in fp32; sin / cos of that angle in double, rounded to the dtype */
+static void rope_sc(int p, int i, int D, float base, float scale, int dt, float *sn, float *cs) {
+    const float s = scale > 0.0f ? scale : 1.0f; /* :35-36 */
+    const float ps = (float)((double)p / (double)s);
+    const float a = (float)((double)ps * (double)rope_freq(i, D, base));
+    *sn = rnd_dt(sin((double)a), dt);
+    *cs = rnd_dt(cos((double)a), dt);
+}
+
+/*
+ * nsa/core/rope.py:16-51 on rows x [R,D] (adjacent pairs (2i, 2i+1) of the last dim), row r at position pos[r]:
+ * y0 = x0 c - x1 s, y1 = x0 s + x1 c with a rounding to the dtype after every product and sum (:45-48).
+ */
+NSA_API void nsa_oracle_rope(const float *x, const int *pos, long R, int D, float base, float scale, int dt, float *y) {
+#pragma omp parallel for schedule(static)
+    for (long r = 0; r < R; ++r)
+        for (int i = 0; i < D / 2; ++i) {
+            float sn, cs;
+            rope_sc(pos[r], i, D, base, scale, dt, &sn, &cs);
+            const double x0 = x[(int64_t)r * D + 2 * i], x1 = x[(int64_t)r * D + 2 * i + 1];
+            y[(int64_t)r * D + 2 * i] = rnd_dt((double)rnd_dt(x0 * cs, dt) - (double)rnd_dt(x1 * sn, dt), dt);
+            y[(int64_t)r * D + 2 * i + 1] = rnd_dt((double)rnd_dt(x0 * sn, dt) + (double)rnd_dt(x1 * cs, dt), dt);
+        }
+}
+
+/* the autograd of nsa/core/rope.py:45-48 for the upstream gradient g [R,D]: dx0 = g0 c + g1 s, dx1 = g1 c - g0 s, each product and the
+ * sum of the two paths rounded to the dtype */
+static void rope_bwd_pair(double g0, double g1, float sn, float cs, int dt, float *d0, float *d1) {
+    *d0 = rnd_dt((double)rnd_dt(g0 * cs, dt) + (double)rnd_dt(g1 * sn, dt), dt);
+    *d1 = rnd_dt((double)rnd_dt(g1 * cs, dt) - (double)rnd_dt(g0 * sn, dt), dt);
+}
+
+NSA_API void nsa_oracle_rope_bwd(const float *g, const int *pos, long R, int D, float base, float scale, int dt, float *dx) {
+#pragma omp parallel for schedule(static)
+    for (long r = 0; r < R; ++r)
+        for (int i = 0; i < D / 2; ++i) {
+            float sn, cs;
+            rope_sc(pos[r], i, D, base, scale, dt, &sn, &cs);
+            rope_bwd_pair(g[(int64_t)r * D + 2 * i], g[(int64_t)r * D + 2 * i + 1], sn, cs, dt, dx + (int64_t)r * D + 2 * i,
+                          dx + (int64_t)r * D + 2 * i + 1);
+        }
+}
+
+/*
+ * nsa/core/compress_pool.py:9-38 (avg_pool_phi_rope_kv with pos given): K_rope = apply_rope(K_raw, pos) WITHOUT position scaling (:20),
+ * then the mean over windows of l rows with stride d (avg_pool2d, :31-32) of K_rope and of the raw V.  K_raw [nbg,S,Dk], V_raw [nbg,S,Dv],
+ * pos [S] -> K_cmp [nbg,n_cmp,Dk], V_cmp [nbg,n_cmp,Dv] with n_cmp = 0 for S < l (:24-28), else (S - l) / d + 1.  The window sum is exact
+ * (double), divided by l and rounded once to the dtype.
+ */
+NSA_API void nsa_oracle_cmp_pool(const float *K_raw, const float *V_raw, const int *pos, long nbg, int S, int Dk, int Dv, int l, int d,
+                                 float base, int dt, float *K_cmp, float *V_cmp) {
+    const int n_cmp = S < l ? 0 : (S - l) / d + 1;
+#pragma omp parallel for schedule(static)
+    for (long bg = 0; bg < nbg; ++bg) {
+        float *kr = (float *)malloc(sizeof(float) * (size_t)Dk);
+        for (int j = 0; j < n_cmp; ++j) {
+            float *kc = K_cmp + ((int64_t)bg * n_cmp + j) * Dk;
+            float *vc = V_cmp + ((int64_t)bg * n_cmp + j) * Dv;
+            double *ak = (double *)calloc((size_t)(Dk + Dv), sizeof(double));
+            for (int i = 0; i < l; ++i) {
+                const int r = j * d + i;
+                nsa_oracle_rope(K_raw + ((int64_t)bg * S + r) * Dk, pos + r, 1, Dk, base, 1.0f, dt, kr);
+                for (int c = 0; c < Dk; ++c) ak[c] += kr[c];
+                for (int c = 0; c < Dv; ++c) ak[Dk + c] += V_raw[((int64_t)bg * S + r) * Dv + c];
+            }
+            for (int c = 0; c < Dk; ++c) kc[c] = rnd_dt(ak[c] / (double)l, dt);
+            for (int c = 0; c < Dv; ++c) vc[c] = rnd_dt(ak[Dk + c] / (double)l, dt);
+            free(ak);
+        }
+        free(kr);
+    }
+}
+
+/*
+ * The autograd of nsa_oracle_cmp_pool for the upstream gradients dK_cmp [nbg,n_cmp,Dk], dV_cmp [nbg,n_cmp,Dv] (n_cmp may be smaller than
+ * the forward's count, 0 included): raw row r receives 1/l of the gradient of every window j < n_cmp with j d <= r < j d + l (avg_pool2d
+ * backward: each window's share rounded to the dtype and added to the row in the dtype, j ascending), and its key gradient is rotated back
+ * at pos[r] (rope_bwd_pair).  A row in no window gets exactly 0.
+ */
+NSA_API void nsa_oracle_cmp_pool_bwd(const float *dK_cmp, const float *dV_cmp, const int *pos, long nbg, int S, int n_cmp, int Dk, int Dv,
+                                     int l, int d, float base, int dt, float *dK_raw, float *dV_raw) {
+#pragma omp parallel for schedule(static)
+    for (long bg = 0; bg < nbg; ++bg) {
+        double *a = (double *)malloc(sizeof(double) * (size_t)(Dk + Dv));
+        for (int r = 0; r < S; ++r) {
+            for (int c = 0; c < Dk + Dv; ++c) a[c] = 0.0;
+            for (int j = 0; j < n_cmp; ++j) {
+                if (!(j * d <= r && r < j * d + l)) continue;
+                for (int c = 0; c < Dk; ++c) a[c] = rnd_dt(a[c] + (double)rnd_dt(dK_cmp[((int64_t)bg * n_cmp + j) * Dk + c] / (double)l, dt), dt);
+                for (int c = 0; c < Dv; ++c) a[Dk + c] = rnd_dt(a[Dk + c] + (double)rnd_dt(dV_cmp[((int64_t)bg * n_cmp + j) * Dv + c] / (double)l, dt), dt);
+            }
+            float *dk = dK_raw + ((int64_t)bg * S + r) * Dk;
+            for (int i = 0; i < Dk / 2; ++i) {
+                float sn, cs;
+                rope_sc(pos[r], i, Dk, base, 1.0f, dt, &sn, &cs);
+                rope_bwd_pair(a[2 * i], a[2 * i + 1], sn, cs, dt, dk + 2 * i, dk + 2 * i + 1);
+            }
+            for (int c = 0; c < Dv; ++c) dV_raw[((int64_t)bg * S + r) * Dv + c] = (float)a[Dk + c];
+        }
+        free(a);
+    }
+}

@@ -340,3 +340,143 @@ def gate_combine_bwd(Q, O_cmp, O_sel, O_win, w1, b1, w2, b2, tau: float, dO) -> 
                                       C.c_float(tau), *(_p(out[k]) for k in ("dO_cmp", "dO_sel", "dO_win", "dgates", "dQ", "dW1", "db1",
                                                                              "dW2", "db2")))
     return out
+
+
+# RoPE and the compressed-token pooling (nsa/core/rope.py:6-51, nsa/core/compress_pool.py:9-38).  dtype: the activation dtype whose rounding
+# chain is followed, "fp32" / "bf16" / "fp16" (or the package's NSA_DT_* code); inputs must already be representable in it.
+_DT_CODE = {"fp32": 0, "bf16": 1, "fp16": 2, 0: 0, 1: 1, 2: 2}
+
+
+def _pos(pos, n):
+    pos = np.ascontiguousarray(np.broadcast_to(np.asarray(pos, np.int64), (n,)), np.int32)
+    assert pos.min(initial=0) >= 0
+    return pos
+
+
+def rope_inv_freq(D: int, base: float = 10000.0) -> np.ndarray:
+    """build_inv_freq (nsa/core/rope.py:6-13): fl(base ** fl(-2 i / D)), [D/2] fp32"""
+    out = np.zeros(D // 2, np.float32)
+    lib().nsa_oracle_rope_inv_freq(D, C.c_float(base), _p(out))
+    return out
+
+
+def rope(x, pos, dtype="fp32", scale: float = 1.0, base: float = 10000.0) -> np.ndarray:
+    """apply_rope (nsa/core/rope.py:16-51): x [..., S, D], pos [S] (or one position per row of x) -> y like x"""
+    x = _f32(x)
+    D = x.shape[-1]
+    R = x.size // D
+    S = x.shape[-2] if x.ndim >= 2 else 1
+    p = _pos(pos, S)
+    p = np.ascontiguousarray(np.broadcast_to(p, (R // S, S)).reshape(R))
+    y = np.zeros_like(x)
+    lib().nsa_oracle_rope(_p(x), _p(p), C.c_long(R), D, C.c_float(base), C.c_float(scale), _DT_CODE[dtype], _p(y))
+    return y
+
+
+def rope_bwd(g, pos, dtype="fp32", scale: float = 1.0, base: float = 10000.0) -> np.ndarray:
+    """gradient of rope for the upstream g [..., S, D] -> dx like g"""
+    g = _f32(g)
+    D = g.shape[-1]
+    R = g.size // D
+    S = g.shape[-2] if g.ndim >= 2 else 1
+    p = np.ascontiguousarray(np.broadcast_to(_pos(pos, S), (R // S, S)).reshape(R))
+    dx = np.zeros_like(g)
+    lib().nsa_oracle_rope_bwd(_p(g), _p(p), C.c_long(R), D, C.c_float(base), C.c_float(scale), _DT_CODE[dtype], _p(dx))
+    return dx
+
+
+def cmp_pool(K_raw, V_raw, l: int, d: int, pos=None, dtype="fp32", base: float = 10000.0):
+    """avg_pool_phi_rope_kv (nsa/core/compress_pool.py:9-38): K_raw [..., S, Dk], V_raw [..., S, Dv], pos [S] (default arange(S))
+    -> K_cmp [..., n_cmp, Dk], V_cmp [..., n_cmp, Dv]"""
+    K, V = _f32(K_raw), _f32(V_raw)
+    S, Dk, Dv = K.shape[-2], K.shape[-1], V.shape[-1]
+    nbg = K.size // (S * Dk)
+    assert V.size == nbg * S * Dv
+    p = _pos(np.arange(S) if pos is None else pos, S)
+    n = 0 if S < l else (S - l) // d + 1
+    Kc, Vc = np.zeros(K.shape[:-2] + (n, Dk), np.float32), np.zeros(V.shape[:-2] + (n, Dv), np.float32)
+    lib().nsa_oracle_cmp_pool(_p(K), _p(V), _p(p), C.c_long(nbg), S, Dk, Dv, l, d, C.c_float(base), _DT_CODE[dtype], _p(Kc), _p(Vc))
+    return Kc, Vc
+
+
+def cmp_pool_bwd(dK_cmp, dV_cmp, S: int, l: int, d: int, pos=None, dtype="fp32", base: float = 10000.0):
+    """gradient of cmp_pool: dK_cmp [..., n_cmp, Dk], dV_cmp [..., n_cmp, Dv] -> dK_raw [..., S, Dk], dV_raw [..., S, Dv]"""
+    dK, dV = _f32(dK_cmp), _f32(dV_cmp)
+    n, Dk, Dv = dK.shape[-2], dK.shape[-1], dV.shape[-1]
+    lead = dK.shape[:-2]
+    nbg = int(np.prod(lead, dtype=np.int64))
+    assert dV.shape == lead + (n, Dv) and (n == 0 or (n - 1) * d + l <= S)
+    p = _pos(np.arange(S) if pos is None else pos, S)
+    dKr, dVr = np.zeros(lead + (S, Dk), np.float32), np.zeros(lead + (S, Dv), np.float32)
+    lib().nsa_oracle_cmp_pool_bwd(_p(dK), _p(dV), _p(p), C.c_long(nbg), S, n, Dk, Dv, l, d, C.c_float(base), _DT_CODE[dtype], _p(dKr), _p(dVr))
+    return dKr, dVr
+
+
+# ---- error bounds of a RoPE kernel against the functions above (float64) ----------------------------------------------------------------
+# A kernel whose inv_freq is within 1 ulp of build_inv_freq's and whose scaled position p / s is within 1 ulp (p * fl(1 / s) is) evaluates
+# the fp32 angle a = fl(fl(p / s) f_i) to within  a 2^-22 + 2 ulp32(a) + 2^-22  (the 2^-22 term: its sin / cos, ~2 ulp32 each).  An element
+# of a rotated pair (x0, x1) is then within  |(x0, x1)| angle_err + c ulp_T(|(x0, x1)|):  c covers the sin / cos rounded to the dtype on both
+# sides (they may land one ulp_T(1) apart: (|x0| + |x1|) 2^-m <= 2 sqrt(2) ulp_T(|x|)), the two products and the sum rounded on both sides
+# (3 ulp_T) and, for fp32, the device sincosf (~2 ulp, another 4.4 ulp32(|x|)):  c = 6 for bf16 / fp16, 8 for fp32.
+_MANT = {"fp32": 23, "bf16": 7, "fp16": 10}
+_EMIN = {"fp32": -126, "bf16": -126, "fp16": -14}
+ROPE_C = {"fp32": 8.0, "bf16": 6.0, "fp16": 6.0}
+
+
+def ulp(v, dtype="fp32") -> np.ndarray:
+    """ulp of |v| in dtype (float64; 0 where v == 0, the subnormal spacing below the normal range)"""
+    v = np.abs(np.asarray(v, np.float64))
+    e = np.floor(np.log2(np.where(v > 0, v, 1.0)))
+    return np.where(v > 0, np.exp2(np.maximum(e, _EMIN[dtype]) - _MANT[dtype]), 0.0)
+
+
+def rope_angle_err(pos, D: int, scale: float = 1.0, base: float = 10000.0) -> np.ndarray:
+    """[len(pos), D/2] bound on a kernel's fp32 angle error (see above)"""
+    s = scale if scale > 0 else 1.0
+    a = np.asarray(pos, np.float64)[:, None] / s * rope_inv_freq(D, base).astype(np.float64)[None, :]
+    return a * 2.0 ** -22 + 2.0 * ulp(a) + 2.0 ** -22
+
+
+def _pair_norm(x):
+    x = np.asarray(x, np.float64)
+    n = np.sqrt(x[..., 0::2] ** 2 + x[..., 1::2] ** 2)
+    return np.repeat(n, 2, axis=-1)
+
+
+def rope_bound(x, pos, dtype="fp32", scale: float = 1.0, c=None, base: float = 10000.0) -> np.ndarray:
+    """per-element bound on |kernel - rope(x, pos)| (and on rope_bwd with x = the upstream gradient): x [..., S, D], pos [S]"""
+    D = x.shape[-1]
+    n = _pair_norm(x)
+    err = np.repeat(rope_angle_err(np.asarray(pos).reshape(-1), D, scale, base), 2, axis=-1)
+    return n * err + (ROPE_C[dtype] if c is None else c) * ulp(n, dtype)
+
+
+def cmp_pool_bound(K_raw, V_raw, l: int, d: int, pos=None, dtype="fp32", base: float = 10000.0):
+    """per-element bounds (K_cmp, V_cmp) on a pooling kernel: the mean of the l rows' rope_bound, the fp32 sum of l terms (l 2^-24 of the
+    mean magnitude) and the final rounding to the dtype on both sides (1 ulp_T)"""
+    S = K_raw.shape[-2]
+    p = np.arange(S) if pos is None else np.asarray(pos)
+    bk, nk, nv = rope_bound(K_raw, p, dtype, base=base), _pair_norm(K_raw), np.abs(np.asarray(V_raw, np.float64))
+    n = 0 if S < l else (S - l) // d + 1
+    w = lambda a: np.stack([a[..., j * d: j * d + l, :].mean(-2) for j in range(n)], -2) if n else a[..., :0, :]  # noqa: E731
+    mk, mv = w(nk), w(nv)
+    return w(bk) + ulp(mk, dtype) + l * 2.0 ** -24 * mk, ulp(mv, dtype) + l * 2.0 ** -24 * mv
+
+
+def cmp_pool_bwd_bound(dK_cmp, dV_cmp, S: int, l: int, d: int, pos=None, dtype="fp32", base: float = 10000.0):
+    """per-element bounds (dK_raw, dV_raw) on a pooling backward kernel: rope_bound of the pooled gradient g = sum_j dK_cmp[j] / l (taken
+    on sum_j |dK_cmp[j]| / l) with c + w + 1 for the w = ceil(l / d) windows of a row (the reference rounds each window's share and each
+    partial sum to the dtype before the rotation, a kernel may sum in fp32 and round once), its fp32 sum; exactly 0 on rows in no window"""
+    dK, dV = np.asarray(dK_cmp, np.float64), np.asarray(dV_cmp, np.float64)
+    n = dK.shape[-2]
+    gk, gv = np.zeros(dK.shape[:-2] + (S, dK.shape[-1])), np.zeros(dV.shape[:-2] + (S, dV.shape[-1]))
+    ak, av = np.zeros_like(gk), np.zeros_like(gv)
+    for j in range(n):
+        gk[..., j * d: j * d + l, :] += dK[..., j: j + 1, :] / l
+        gv[..., j * d: j * d + l, :] += dV[..., j: j + 1, :] / l
+        ak[..., j * d: j * d + l, :] += np.abs(dK[..., j: j + 1, :]) / l
+        av[..., j * d: j * d + l, :] += np.abs(dV[..., j: j + 1, :]) / l
+    p = np.arange(S) if pos is None else np.asarray(pos)
+    nk, w = _pair_norm(ak), -(-l // d)
+    bk = rope_bound(ak, p, dtype, c=ROPE_C[dtype] + w + 1.0, base=base) + 2.0 ** -22 * nk
+    return bk, (w + 1.0) * ulp(av, dtype) + 2.0 ** -22 * av

@@ -217,3 +217,64 @@ def g21_inputs(case):
     b2 = _bf16_round(np.asarray(bias, np.float32))
     dO = _bf16_round(randn(r, 1, S, G, h, Dv))
     return dict(Q=q, O_cmp=oc, O_sel=os_, O_win=ow, w1=w1, b1=b1, w2=w2, b2=b2, dO=dO, tau=float(tau), h=h, Dk=Dk, Dv=Dv, Hd=Hd)
+
+
+# g22: RoPE and the compressed-token pooling of the reference (oracle/make_rope_pool_goldens.py).  Every value is a multiple of 1/32 below 8
+# in magnitude (8 significant bits), so it is exact in bf16 AND fp16 and each case runs in fp32, bf16 and fp16 on the same numbers.
+G22_POS_LONG = (2047, 2048, 4095, 32767, 65535, 65536, 131071, 262143)
+G22_DTYPES = ("fp32", "bf16", "fp16")
+# RoPE cases: name -> (D, scale, positions, with gradient).  384 / 768 / 1536 are flattened Q widths (n_heads d_k); "dense" = 0 .. 299.
+G22_ROPE_CASES = {
+    "d16_dense_s1": (16, 1.0, "dense", False),
+    "d16_dense_s3": (16, 3.0, "dense", True),
+    "d16_dense_s4": (16, 4.0, "dense", False),
+    **{f"d{D}_long_s{s}": (D, float(s), G22_POS_LONG, D in (64, 384)) for D in (16, 32, 64, 128) for s in (1, 4, 3)},
+    **{f"d384_long_s{s}": (384, float(s), G22_POS_LONG, s == 3) for s in (1, 3)},
+    **{f"d768_long_s{s}": (768, float(s), G22_POS_LONG[3::2] + (65536,), False) for s in (1, 3)},
+    **{f"d1536_long_s{s}": (1536, float(s), (65536, 262143), False) for s in (1, 3)},
+}
+# pooling cases: name -> (l, d, D = Dk = Dv, S, first position, windows stored (None = all), with gradient).  Position offset p0 > 0 with
+# S = l is a decode emission (pos = arange(S_raw - l, S_raw), reference nsa_attention.py:586-604).
+G22_POOL_CASES = {}
+for _l, _d in ((32, 16), (16, 8), (32, 32), (64, 16), (24, 8)):
+    for _D in (32, 64, 128):
+        for _S in (_l - 1, _l, _l + _d - 1):
+            G22_POOL_CASES[f"l{_l}d{_d}_D{_D}_S{_S}"] = (_l, _d, _D, _S, 0, None, False)
+        G22_POOL_CASES[f"l{_l}d{_d}_D{_D}_S4101"] = (_l, _d, _D, 4101, 0, "ends", False)
+        G22_POOL_CASES[f"l{_l}d{_d}_D{_D}_dec65568"] = (_l, _d, _D, _l, 65568, None, False)
+    G22_POOL_CASES[f"l{_l}d{_d}_D64_dec262112"] = (_l, _d, 64, _l, 262112, None, False)
+    G22_POOL_CASES[f"l{_l}d{_d}_D32_grad"] = (_l, _d, 32, _l + _d + 5, 0, None, True)  # two windows, then 5 rows after the last
+G22_POOL_CASES["l32d16_D32_grad_off"] = (32, 16, 32, 32 + 16 + 5, 65568, None, True)
+
+
+def g22_pool_windows(case):
+    """indices of the compressed tokens stored for a pooling case ("ends": the first 2 and the last 2 of a long run)"""
+    l, d, _, S, _, rows, _ = G22_POOL_CASES[case]
+    n = 0 if S < l else (S - l) // d + 1
+    return np.arange(n) if rows is None else np.array([0, 1, n - 2, n - 1])
+
+
+def _g22_vals(r, *shape):
+    return (np.clip(np.rint(randn(r, *shape) * np.float32(32.0)), -255, 255) / np.float32(32.0)).astype(np.float32)
+
+
+def g22_inputs(case):
+    """-> dict: RoPE case: x [R,D], pos [R] int64, dy [R,D] (upstream gradient); pooling case: K [1,1,S,D], V [1,1,S,D], pos [S],
+    dKc / dVc [1,1,n_cmp,D]"""
+    if case in G22_ROPE_CASES:
+        D, _, pos, _ = G22_ROPE_CASES[case]
+        r = _rng(22, 0, list(G22_ROPE_CASES).index(case))
+        p = np.arange(300, dtype=np.int64) if pos == "dense" else np.asarray(pos, np.int64)
+        return dict(x=_g22_vals(r, p.size, D), pos=p, dy=_g22_vals(r, p.size, D))
+    l, d, D, S, p0, _, _ = G22_POOL_CASES[case]
+    r = _rng(22, 1, list(G22_POOL_CASES).index(case))
+    n = 0 if S < l else (S - l) // d + 1
+    return dict(K=_g22_vals(r, 1, 1, S, D), V=_g22_vals(r, 1, 1, S, D), pos=np.arange(p0, p0 + S, dtype=np.int64),
+                dKc=_g22_vals(r, 1, 1, n, D), dVc=_g22_vals(r, 1, 1, n, D))
+
+
+def g22_unpack(a):
+    """a stored g22 output -> float32 (bf16 is stored as its uint16 bit pattern)"""
+    if a.dtype == np.uint16:
+        return (a.astype(np.uint32) << 16).view(np.float32)
+    return a.astype(np.float32)

@@ -331,3 +331,61 @@ def test_g21_gate_oracle_matches_reference(orc, case):
         pk = peaked[:RD]
         assert pk.any() and (~pk).any()
         assert (bw["dQ"][pk] == 0).all() and (g[case + "_dQ"][pk] == 0).all()
+
+
+# ---- g22: RoPE and the compressed-token pooling (oracle/make_rope_pool_goldens.py) -----------------------------------------------------
+@pytest.mark.parametrize("D", sorted({c[0] for c in gi.G22_ROPE_CASES.values()} | {c[2] for c in gi.G22_POOL_CASES.values()}))
+def test_g22_oracle_inv_freq_within_one_ulp_of_reference(orc, D):
+    """the oracle's fl(base ** fl(-2 i / D)) (pow in double, rounded once) against build_inv_freq's fp32 pow: at most 1 ulp apart, and
+    exactly equal at D <= 32 (measured: 2 of 32 entries differ at D = 64, 3 of 64 at 128, 9 of 384 at 768)"""
+    ref = load_golden("g22_rope_pool")[f"inv_freq_{D}"]
+    du = np.abs(orc.rope_inv_freq(D).view(np.int32).astype(np.int64) - ref.view(np.int32))
+    assert du.max() <= 1
+    if D <= 32:
+        assert du.max() == 0
+
+
+def _within(got, ref, bound):
+    e = np.abs(np.asarray(got, np.float64) - np.asarray(ref, np.float64))
+    assert (e[bound == 0] == 0).all()
+    return float((e / np.where(bound > 0, bound, 1.0)).max()) if e.size else 0.0
+
+
+@pytest.mark.parametrize("dt", gi.G22_DTYPES)
+@pytest.mark.parametrize("case", list(gi.G22_ROPE_CASES))
+def test_g22_oracle_rope_matches_reference(orc, case, dt):
+    """nsa_oracle_rope / _bwd against apply_rope and its autograd gradient, within the per-element bound (nsa_oracle.rope_bound) that the
+    GPU tests hold the kernels to.  Worst seen: 0.35 of the bound (fp32), 0.27 (bf16), 0.19 (fp16)."""
+    g = load_golden("g22_rope_pool")
+    D, scale, _, grad = gi.G22_ROPE_CASES[case]
+    x = gi.g22_inputs(case)
+    pre = f"rope_{case}_{dt}_"
+    assert _within(orc.rope(x["x"], x["pos"], dt, scale), gi.g22_unpack(g[pre + "y"]), orc.rope_bound(x["x"], x["pos"], dt, scale)) <= 1.0
+    if grad:
+        assert _within(orc.rope_bwd(x["dy"], x["pos"], dt, scale), gi.g22_unpack(g[pre + "dx"]),
+                       orc.rope_bound(x["dy"], x["pos"], dt, scale)) <= 1.0
+
+
+@pytest.mark.parametrize("dt", gi.G22_DTYPES)
+@pytest.mark.parametrize("case", list(gi.G22_POOL_CASES))
+def test_g22_oracle_cmp_pool_matches_reference(orc, case, dt):
+    """nsa_oracle_cmp_pool / _bwd against avg_pool_phi_rope_kv (no position scale inside) and its autograd gradients.  In bf16 / fp16 the
+    oracle follows the reference's rounding exactly (the backward's per-window shares included); worst seen 0.1 of the bound in fp32."""
+    g = load_golden("g22_rope_pool")
+    l, d, D, S, _, _, grad = gi.G22_POOL_CASES[case]
+    x = gi.g22_inputs(case)
+    win = gi.g22_pool_windows(case)
+    pre = f"pool_{case}_{dt}_"
+    oK, oV = orc.cmp_pool(x["K"], x["V"], l, d, x["pos"], dt)
+    bK, bV = orc.cmp_pool_bound(x["K"], x["V"], l, d, x["pos"], dt)
+    assert oK.shape[-2] == (0 if S < l else (S - l) // d + 1)
+    assert _within(oK[:, :, win], gi.g22_unpack(g[pre + "Kc"]), bK[:, :, win]) <= 1.0
+    assert _within(oV[:, :, win], gi.g22_unpack(g[pre + "Vc"]), bV[:, :, win]) <= 1.0
+    if dt != "fp32":
+        assert np.array_equal(oV[:, :, win], gi.g22_unpack(g[pre + "Vc"]))
+    if grad:
+        dK, dV = orc.cmp_pool_bwd(x["dKc"], x["dVc"], S, l, d, x["pos"], dt)
+        bK, bV = orc.cmp_pool_bwd_bound(x["dKc"], x["dVc"], S, l, d, x["pos"], dt)
+        assert _within(dK, gi.g22_unpack(g[pre + "dK"]), bK) <= 1.0 and _within(dV, gi.g22_unpack(g[pre + "dV"]), bV) <= 1.0
+        if dt != "fp32":
+            assert np.array_equal(dK, gi.g22_unpack(g[pre + "dK"])) and np.array_equal(dV, gi.g22_unpack(g[pre + "dV"]))
