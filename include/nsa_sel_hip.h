@@ -274,7 +274,11 @@ NSA_API int nsa_layer_extend(const nsa_layer_desc *L, const nsa_kv_desc *kv, con
 /* One decode step of the whole layer in one call (nsa_attention.py:509-830, decode branch): x [B,dim] is the new token at
  * position t (= tokens already cached); appends it to the caches, emits a compressed token when due, runs the three branches,
  * the gate and the output projection -> y [B,dim].  csc_* / S_sel: the Eq.9 map of the block metadata covering t
- * (nsa_build_block_meta_host).  ranges_out [B,G,n_sel,2] int32 and gates_out [B,G,3] fp32 are nullable monitors. */
+ * (nsa_build_block_meta_host).  ranges_out [B,G,n_sel,2] int32 and gates_out [B,G,3] fp32 are nullable monitors.
+ * The selected branch runs as the one-launch decode step (nsa_sel_decode_step) at Dk = Dv = 64 and 128.  The tuning switch
+ * "DECODE_BAND" >= 1 (sliding + compressed branches on that launch, their splits merged there, the mix in the output projection)
+ * applies to Dk = Dv = 64 only: at 128 the two branches are their own launches (mode 0) and gate + mix run as the gate kernel,
+ * whatever the switch says.  The workspace size follows Dk / Dv. */
 NSA_API size_t nsa_layer_decode_step_workspace(const nsa_layer_desc *L, int B, int S_max);
 NSA_API int nsa_layer_decode_step(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *x, void *y, int t,
                           const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel,
@@ -405,11 +409,21 @@ NSA_API int nsa_sel_select_attn_fwd(const float *p_grp, int t0, const int32_t *t
  *   (nsa/core/nsa_attention.py:651 compute_pcmp_all, :658 map_pcmp_to_pslc_batched, :670 head sum,
  *   :672 select_topn_ranges, :704-830 selection executor).
  *   ranges_out [B,G,n_top,2] int32, O [B,1,G,h,Dv]; workspace: nsa_sel_decode_step_workspace() bytes, 16-B aligned.
- *   Kernel form (one launch wherever the default block geometry, bf16 / f16 and Dk = Dv = 64 allow): chosen from (B*G, S_cmp) -- logits
+ *   Kernel form (one launch wherever the default block geometry, bf16 / f16 and Dk = Dv in {64, 128} allow): chosen from (B*G, S_cmp) -- logits
  *   in registers for rows of up to 32 chunks of 64 compressed rows, a team of workgroups per row for longer rows while B*G teams fit the
  *   chip, and for more rows than that (B >= 128 at a 64k context) the one-pass form, whose group scores carry one more rounding (<= 2 ulp)
  *   than the other forms': its ranges are theirs wherever the (n_top - 3)-th and the next ranking key differ by more than that (tuning
  *   switch "DECODE_WIDE": 0 = never, 1 = the exact one-workgroup form instead).  Every form is bitwise reproducible run to run.
+ *   Dk = Dv = 128: the exact forms with the logits in registers only (eight waves per row, one workgroup per CU; a row of more than 16
+ *   chunks as a team of workgroups while B*G teams fit the chip).  Shapes beyond that -- more rows at a long context than teams fit (B*G*4
+ *   workgroups > CUs at 64k), DECODE_WIDE forms -- take the separate launches (scores + top-n, then the decode attention), whose
+ *   results are the same bits: the decode attention of both routes runs the same row functions.
+ *   nsa_sel_decode_step_workspace does not depend on the route: it covers the team form's records (independent of Dk) and the scratch of
+ *   the separate launches for the given Dk / Dv.
+ *   nsa_sel_decode_step_plan reports what nsa_sel_decode_step does with a shape under the current tuning switches, assuming the default
+ *   block geometry (l = 2d, l' = 4d = 64), 16-byte aligned pointers and contiguous rows: *launches = 1 exactly when the call is the
+ *   one-launch step; for a declined shape it is an estimate (> 1) of the launches of the separate route -- only "> 1" is contractual there --, *form = 0 logits in registers / 1 four chunks per wave / 2 one-pass (-1 when the step is declined), *nsplit =
+ *   workgroups per row (0 when declined).
  * ------------------------------------------------------------------------------------- */
 NSA_API size_t nsa_sel_decode_step_workspace(int B, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int n_top, int dtype);
 NSA_API int nsa_sel_decode_step(const void *Q, const void *K_cmp, const void *K, const void *V, const int32_t *csc_ptr,
@@ -418,6 +432,8 @@ NSA_API int nsa_sel_decode_step(const void *Q, const void *K_cmp, const void *K,
                         int64_t kc_stride_b, int64_t kc_stride_g, int64_t kc_stride_s, int64_t k_stride_b,
                         int64_t k_stride_g, int64_t k_stride_s, int64_t v_stride_b, int64_t v_stride_g,
                         int64_t v_stride_s, int dtype, float scale, void *workspace, size_t workspace_bytes, void *stream);
+NSA_API int nsa_sel_decode_step_plan(int B, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int n_top, int dtype,
+                             int *launches /* host */, int *form /* host */, int *nsplit /* host */);
 
 /* indices [R,K] int32 ascending with -1 padding -> ranges [R,K,2]; clamp end to t+1. */
 NSA_API int nsa_indices_to_ranges_v2(const int32_t *indices, int64_t R, int S, int G, int t0, int K, int S_sel,

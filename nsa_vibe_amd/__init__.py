@@ -26,6 +26,7 @@ from .selection_attention import (  # noqa: F401
     selection_attention_head_causal_parity,
     selection_attention_hip,
     selection_decode_step,
+    selection_decode_step_plan,
 )
 from .selection_scorer import (  # noqa: F401
     batched_ranges_width,

@@ -190,8 +190,8 @@ int nsa::sel_attn_fwd_impl(const void *Q, const void *K, const void *V, const in
     if (variant == 2) NSA_CHECK_ARG(fast_ok, "sel_attn_fwd: MFMA variant requested but shape/dtype/alignment unsupported");
     NSA_CHECK_ARG(variant >= 0 && variant <= 2, "sel_attn_fwd: unknown variant %d", variant);
     if (variant == 0 && S == 1 && !lse && sel_attn_decode_wg_supported(dtype, h, Dk, Dv, n_ranges, ksb, ksg, kss, vsb, vsg, vss, Q, K, V) &&
-        (int64_t)S_kv * 128 < ((int64_t)1 << 31))  // decode: one workgroup per row, partials merged through LDS, no combine launch
-        return launch_sel_attn_decode_wg(Q, K, V, ranges, O, R, G, h, S_kv, n_ranges, ksb, ksg, kss, vsb, vsg, vss, dtype, P.scale, st);
+        (int64_t)S_kv * 2 * Dv < ((int64_t)1 << 31))  // decode: one workgroup per row, partials merged through LDS, no combine launch
+        return launch_sel_attn_decode_wg(Q, K, V, ranges, O, R, G, h, S_kv, n_ranges, ksb, ksg, kss, vsb, vsg, vss, dtype, P.scale, st, Dk);
     if (variant == 2 || (variant == 0 && fast_ok)) {
         int ns = 1;
         const size_t need = sel_attn_mfma_workspace(R, h, Dv, &ns);
@@ -702,14 +702,14 @@ int nsa::sel_decode_step_impl(const void *Q, const void *K_cmp, const void *K, c
     int rc;
     const float sc = scale > 0.f ? scale : 1.0f / sqrtf((float)Dk);
     const bool wg_attn = sel_attn_decode_wg_supported(dtype, h, Dk, Dv, n_top, ksb, ksg, kss, vsb, vsg, vss, Q, K, V) && S_kv >= 1 &&
-                         (int64_t)S_kv * 128 < ((int64_t)1 << 31);
+                         (int64_t)S_kv * 2 * Dv < ((int64_t)1 << 31);
     const int stencil = (l == 2 * d && l_sel == 4 * d) ? 1 : 0;  // Eq.9 in closed form (the fused kernel then reads no CSC arrays)
     if (decode_step_supported((int64_t)B * G, dtype, h, Dk, Dv, S_cmp, S_sel, S_kv, l, d, l_sel, n_top, t_token, kcb, kcg, kcs, ksb, ksg, kss, vsb, vsg, vss, Q, K_cmp,
                               K, V)) {  // scores -> statistics -> Eq.9/10 -> sequential top-n -> selection attention: ONE launch, O is final
         if (ns_used) *ns_used = 1;
         if (band && band_taken) *band_taken = 1;
         return launch_decode_step(Q, K_cmp, K, V, O, ranges_out, B, G, h, S_cmp, S_sel, S_kv, n_top, t_token, kcb, kcg, kcs, ksb, ksg, kss, vsb, vsg,
-                                  vss, dtype, sc, w, a, (hipStream_t)stream, band_taken ? band : nullptr);
+                                  vss, dtype, sc, w, a, (hipStream_t)stream, band_taken ? band : nullptr, Dk);
     }
     (void)wg_attn;
     if (decode_score_select_supported(dtype, h, Dk, S_cmp, S_sel, kcb, kcg, kcs, Q, K_cmp, (int64_t)B * G)) {
@@ -741,6 +741,31 @@ int nsa_sel_decode_step(const void *Q, const void *K_cmp, const void *K, const v
     return sel_decode_step_impl(Q, K_cmp, K, V, csc_ptr, csc_rows, csc_vals, ranges_out, O, B, G, h, Dk, Dv, S_cmp, S_sel, S_kv, l, d, l_sel,
                                 n_top, t_token, kcb, kcg, kcs, ksb, ksg, kss, vsb, vsg, vss, dtype, scale, workspace, workspace_bytes, stream, 0,
                                 nullptr, nullptr);
+}
+
+int nsa_sel_decode_step_plan(int B, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int n_top, int dtype, int *launches, int *form,
+                             int *nsplit) {
+    NSA_CHECK_ARG(launches && form && nsplit, "decode_step_plan: null pointer");
+    NSA_CHECK_ARG(dtype_ok(dtype), "decode_step_plan: unknown dtype %d", dtype);
+    NSA_CHECK_ARG(B >= 1 && G >= 1 && h >= 1 && Dk >= 1 && Dv >= 1 && S_cmp >= 0 && S_sel >= 1 && S_kv >= 1 && n_top >= 1 && n_top <= 64,
+                  "decode_step_plan: bad sizes");
+    const int64_t R = (int64_t)B * G;
+    if (decode_step_shape_plan(R, dtype, h, Dk, Dv, S_cmp, S_sel, S_kv, n_top, form, nsplit)) {
+        *launches = 1;
+        return NSA_OK;
+    }
+    // the route of sel_decode_step_impl for a declined shape, by the shape parts of the predicates it asks: scores + top-n in one launch or
+    // three, then the attention (its decode form is one launch; the prefill kernel with the keys split adds a combine launch)
+    int n = decode_score_select_shape_ok(dtype, h, Dk, S_cmp, S_sel, R) ? 1 : 3;
+    if (sel_attn_decode_wg_shape_ok(dtype, h, Dk, Dv, n_top) && (int64_t)S_kv * 2 * Dv < ((int64_t)1 << 31)) {
+        n += 1;
+    } else {
+        int ns = 1;
+        if (sel_attn_mfma_supported(dtype, h, Dk, Dv)) sel_attn_mfma_workspace(R, h, Dv, &ns);
+        n += ns > 1 ? 2 : 1;
+    }
+    *launches = n;
+    return NSA_OK;
 }
 
 int nsa_indices_to_ranges_v2(const int32_t *indices, int64_t R, int S, int G, int t0, int K, int S_sel, int l_sel,

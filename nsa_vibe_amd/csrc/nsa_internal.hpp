@@ -39,6 +39,10 @@ size_t decode_step_workspace(int64_t R, int h, int S_cmp);
 int launch_decode_step(const void *Q, const void *Kc, const void *K, const void *V, void *O, int32_t *ranges_out, int B, int G, int h, int S_cmp,
                        int S_sel, int S_kv, int n_top, int t_token, int64_t kcb, int64_t kcg, int64_t kcs, int64_t ksb, int64_t ksg, int64_t kss,
                        int64_t vsb, int64_t vsg, int64_t vss, int dtype, float scale, void *ws, size_t ws_bytes, hipStream_t st,
-                       const DecBandPair *band = nullptr);
+                       const DecBandPair *band = nullptr, int D = 64);
+// shape / tuning part of decode_step_supported (default block geometry): false = declined (form -1, nsplit 0)
+bool decode_step_shape_plan(int64_t R, int dtype, int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int n_top, int *form, int *nsplit);
+// shape / tuning part of decode_score_select_supported
+bool decode_score_select_shape_ok(int dtype, int h, int Dk, int S_cmp, int S_sel, int64_t rows);
 
 }  // namespace nsa

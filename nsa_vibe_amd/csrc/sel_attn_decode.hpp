@@ -13,7 +13,10 @@
 // normalised segments of arbitrary ranges (standalone launch: sel_attn_decode.hip).  For selector output both enumerate the same
 // chunks in the same order, so the two routes give the same bits.
 // Semantics: union of the clamped ranges (normalise_ranges_lanes), end <= start ignored, empty row -> zeros
-// (attention_kernels.py:705-772).  bf16 / f16, Dk = Dv = 64, h <= 16, V rows contiguous (128 B apart).
+// (attention_kernels.py:705-772).  bf16 / f16, Dk = Dv = D in {64, 128}, h <= 16, V rows contiguous (2 D bytes apart).
+// D = 128: a 64-key V tile is 16 KiB (16 LDS-DMA pieces of 4 rows; 32-byte column pairs XOR-swizzled with row & 7, Geo<128>::swz_v: the
+// transposing reads of 16 rows 256 B apart would otherwise all start in the same bank), so sixteen tiles (256 KiB) do not fit the 160 KiB
+// of a CU: NW = 8 only (128 KiB of V tiles, one workgroup per CU, up to 256 VGPRs); the K rows of a chunk are 16 global_load_dwordx4.
 #pragma once
 #include "attn_mfma_tiles.hpp"
 
@@ -28,21 +31,23 @@ static __device__ long long g_dec_ts[64];
 #endif
 
 struct DecAttnArgs {
-    const void *Q;  // [R,h,64]
-    const void *K;  // [B,G,S_kv,64] strided
+    const void *Q;  // [R,h,D]
+    const void *K;  // [B,G,S_kv,D] strided
     const void *V;
-    void *O;        // [R,h,64]
+    void *O;        // [R,h,D]
     int G, h, S_kv, n;
     int64_t ksb, ksg, kss, vsb, vsg, vss;
     float c2;  // scale * log2(e)
 };
 
-constexpr int DEC_ATT_TILE = 64 * 128;                         // V chunk per wave
+constexpr int dec_att_tile(int D) { return 64 * 2 * D; }        // V chunk per wave: 64 keys
+constexpr int DEC_ATT_TILE = dec_att_tile(64);
 constexpr int DEC_ATT_TAIL = ((SEG_INTS * 4 + 15) / 16) * 16;  // sorted segments of the row (standalone launch)
-constexpr int dec_att_lds(int nw) { return nw * DEC_ATT_TILE + DEC_ATT_TAIL; }
+constexpr int dec_att_lds(int nw, int D = 64) { return nw * dec_att_tile(D) + DEC_ATT_TAIL; }
 
-// waves per row workgroup for a launch of `rows` rows: 16 while every row can have a CU of its own, 8 beyond (two rows per CU)
-int dec_att_waves(int64_t rows);
+// waves per row workgroup for a launch of `rows` rows: 16 while every row can have a CU of its own, 8 beyond (two rows per CU).
+// D = 128: always 8 (sixteen 16 KiB V tiles do not fit a CU's LDS)
+int dec_att_waves(int64_t rows, int D = 64);
 
 // ---- chunk providers: chunk e (ascending token order) -> first key and number of keys (1..64)
 // blocks picked by the selector, in LDS (sorted, disjoint, 64 keys each; the last one is cut at t_end = min(t + 1, S_kv))
@@ -128,16 +133,21 @@ __device__ __forceinline__ void decode_prefetch_chunk(const DecAttnArgs &A, int6
 #endif
 }
 
-// vt: NW * DEC_ATT_TILE bytes of LDS, 16-byte aligned (V tiles, then the partial records); every thread of the NW * 64-thread workgroup must
+// vt: NW * dec_att_tile(D) bytes of LDS, 16-byte aligned (V tiles, then the partial records); every thread of the NW * 64-thread workgroup must
 // call (one workgroup barrier inside).  qf_in: the row's Q^T fragments if the caller holds them already (lane (rho, q):
 // Q[head min(rho, h-1)][32 s + 8 q ..], s = 0, 1).  NC chunks; chunks with len <= 0 must not occur.
-template <typename T, int NW, typename CH>
+template <typename T, int NW, typename CH, int D = 64>
 __device__ __forceinline__ void decode_attend_chunks(const DecAttnArgs &A, int64_t row, const CH &ch, const int NC, unsigned char *vt,
                                                      const typename MfmaT<T>::x8 *qf_in = nullptr, const DecPrefetch pre = DecPrefetch{-1, nullptr}) {
     using M = MfmaT<T>;
     using x8 = typename M::x8;
     using x4 = typename M::x4;
-    constexpr int ROWB = 128;
+    using G_ = Geo<D>;
+    constexpr int ROWB = G_::ROWB, KS = G_::KSTEPS, MT = G_::MT;
+    constexpr int TILE = dec_att_tile(D);
+    [[maybe_unused]] constexpr int VLD = TILE / 1024, VRPI = G_::RPI;  // LDS-DMA pieces of a V chunk (1 KiB = VRPI rows each)
+    constexpr int LOG2D = D == 64 ? 6 : 7;
+    static_assert(D == 64 || (D == 128 && NW == 8), "D = 128: eight waves per row");
     constexpr bool PF = NW < 16;  // K rows of the wave's next chunk fetched behind the current one (the register budget of 512 threads allows it)
     const int lane = lane_id();
     const int wave = uniform((int)(threadIdx.x >> 6));
@@ -145,24 +155,29 @@ __device__ __forceinline__ void decode_attend_chunks(const DecAttnArgs &A, int64
     const int h = A.h;
     const int g = (int)(row % A.G);
     const int64_t b = row / A.G;
-    unsigned char *vl = vt + wave * DEC_ATT_TILE;
+    unsigned char *vl = vt + wave * TILE;
 
     // Q^T fragments (B operand): column = head (columns >= h repeat the last head: their results are never stored)
-    x8 qf[2];
+    x8 qf[KS];
 #pragma unroll
-    for (int s = 0; s < 2; ++s)
-        qf[s] = qf_in ? qf_in[s] : __builtin_bit_cast(x8, *(const u32x4 *)((const T *)A.Q + (row * h + min(rho, h - 1)) * 64 + 32 * s + 8 * q));
+    for (int s = 0; s < KS; ++s)
+        qf[s] = qf_in ? qf_in[s] : __builtin_bit_cast(x8, *(const u32x4 *)((const T *)A.Q + (row * h + min(rho, h - 1)) * D + 32 * s + 8 * q));
 
     const unsigned char *Kb = (const unsigned char *)((const T *)A.K + b * A.ksb + (int64_t)g * A.ksg);
     const unsigned char *Vb = (const unsigned char *)((const T *)A.V + b * A.vsb + (int64_t)g * A.vsg);
     const int64_t krowb = A.kss * 2;
-    const int ld_row = lane >> 3, ld_piece = lane & 7;
-    [[maybe_unused]] const uint32_t vsw = (uint32_t)(((((ld_piece >> 1) ^ ((ld_row >> 1) & 3)) << 1) | (ld_piece & 1)) << 4);
-    uint32_t vrd0[4];
+    const int ld_row = lane >> (D == 64 ? 3 : 4), ld_piece = lane & (G_::PIECES - 1);
+    // source piece of the lane's 16 bytes of DMA piece i: the swizzle of LDS row VRPI i + ld_row (D = 64: that of ld_row; D = 128: it
+    // alternates with the parity of i)
+    constexpr int NSW = D == 64 ? 1 : 2;
+    [[maybe_unused]] uint32_t vsw[NSW];
+#pragma unroll
+    for (int j = 0; j < NSW; ++j) vsw[j] = (uint32_t)(((((ld_piece >> 1) ^ G_::swz_v(VRPI * j + ld_row)) << 1) | (ld_piece & 1)) << 4);
+    uint32_t vrd0[MT];
     {
         const int qq = rho >> 2, pp = rho & 3, r = 4 * q + qq;
 #pragma unroll
-        for (int m = 0; m < 4; ++m) vrd0[m] = r * ROWB + ((m ^ ((r >> 1) & 3)) << 5) + 8 * pp;
+        for (int m = 0; m < MT; ++m) vrd0[m] = r * ROWB + ((m ^ G_::swz_v(r)) << 5) + 8 * pp;
     }
     // (readfirstlane returns a SIGNED int: the halves go through uint32_t, or a low half >= 2^31 sign-extends into the high one --
     // tests/test_hip_descriptor_bit31.py runs every descriptor-building kernel on such addresses)
@@ -177,39 +192,39 @@ __device__ __forceinline__ void decode_attend_chunks(const DecAttnArgs &A, int64
         typedef __attribute__((address_space(3))) void lds_void;
         const int vs = uniform(tok0 * ROWB);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int rc = min(8 * i + ld_row, len - 1);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(vrs, (lds_void *)(vl + i * 1024), 16, rc * ROWB + vsw, vs, 0, 0);
+        for (int i = 0; i < VLD; ++i) {
+            const int rc = min(VRPI * i + ld_row, len - 1);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(vrs, (lds_void *)(vl + i * 1024), 16, rc * ROWB + vsw[i % NSW], vs, 0, 0);
         }
 #else
         (void)tok0, (void)len;
 #endif
     };
-    auto load_k = [&](int tok0, int len, x8 (&k)[4][2]) {
+    auto load_k = [&](int tok0, int len, x8 (&k)[4][KS]) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int kr = tok0 + min(16 * u + rho, len - 1);
 #pragma unroll
-            for (int s = 0; s < 2; ++s) k[u][s] = __builtin_bit_cast(x8, *(const u32x4 *)(Kb + (int64_t)kr * krowb + 64 * s + 16 * q));
+            for (int s = 0; s < KS; ++s) k[u][s] = __builtin_bit_cast(x8, *(const u32x4 *)(Kb + (int64_t)kr * krowb + 64 * s + 16 * q));
         }
     };
 
-    f32x4 o[4];
+    f32x4 o[MT];
 #pragma unroll
-    for (int m = 0; m < 4; ++m) o[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int m = 0; m < MT; ++m) o[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
     float mrun = -INFINITY, lrun = 0.f;
 
     int cur = dec_first_chunk<NW>(wave, NC), tok0 = 0, len = 0;
-    x8 kfr[4][2];
+    x8 kfr[4][KS];
     if (cur < NC) {
         ch.get(cur, tok0, len);
-        if (pre.tok0 == tok0 && pre.tok0 >= 0) {
+        if (D == 64 && pre.tok0 == tok0 && pre.tok0 >= 0) {
             // this chunk went out at kernel start (K and V by LDS-DMA): both have long landed; the K fragments come from the LDS image
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
             for (int u = 0; u < 4; ++u)
 #pragma unroll
-                for (int s = 0; s < 2; ++s) kfr[u][s] = *(const x8 *)(pre.ktile + (16 * u + rho) * ROWB + (((4 * s + q) ^ (rho & 7)) << 4));
+                for (int s = 0; s < KS; ++s) kfr[u][s] = *(const x8 *)(pre.ktile + (16 * u + rho) * ROWB + (((4 * s + q) ^ (rho & 7)) << 4));
         } else {
             load_k(tok0, len, kfr);  // K first: loads complete in order, and the scores need K before the P V product needs V
             issue_v(tok0, len);
@@ -219,7 +234,7 @@ __device__ __forceinline__ void decode_attend_chunks(const DecAttnArgs &A, int64
         const int nxt = dec_next_chunk<NW>(cur, wave, NC);
         const bool hn = nxt < NC;
         int ntok0 = 0, nlen = 0;
-        [[maybe_unused]] x8 kn[4][2];
+        [[maybe_unused]] x8 kn[4][KS];
         if (hn) {
             ch.get(nxt, ntok0, nlen);
             if constexpr (PF) load_k(ntok0, nlen, kn);
@@ -229,7 +244,7 @@ __device__ __forceinline__ void decode_attend_chunks(const DecAttnArgs &A, int64
         for (int u = 0; u < 4; ++u) {
             sacc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int s = 0; s < 2; ++s) sacc[u] = M::mma(kfr[u][s], qf[s], sacc[u]);
+            for (int s = 0; s < KS; ++s) sacc[u] = M::mma(kfr[u][s], qf[s], sacc[u]);
         }
         float x[16];
         float vmax = -INFINITY;
@@ -254,12 +269,14 @@ __device__ __forceinline__ void decode_attend_chunks(const DecAttnArgs &A, int64
             pf[i >> 3][i & 7] = Elt<T>::from_f(pe);
         }
         lrun = lrun * alpha + psum;
-        // the V pieces have landed (LDS-DMA completion is a vmcnt event; loads complete in order: the 8 prefetched K loads may stay out)
-        if (PF && hn) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // the V pieces have landed (LDS-DMA completion is a vmcnt event; loads complete in order: the 4 KS prefetched K loads may stay out)
+        if (PF && hn) {
+            if constexpr (KS == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+        } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int m = 0; m < 4; ++m) {
+        for (int m = 0; m < MT; ++m) {
             o[m] *= alpha;
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf) {
@@ -280,7 +297,7 @@ __device__ __forceinline__ void decode_attend_chunks(const DecAttnArgs &A, int64
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
 #pragma unroll
-                    for (int s = 0; s < 2; ++s) kfr[u][s] = kn[u][s];
+                    for (int s = 0; s < KS; ++s) kfr[u][s] = kn[u][s];
             } else {
                 load_k(ntok0, nlen, kfr);
             }
@@ -290,7 +307,7 @@ __device__ __forceinline__ void decode_attend_chunks(const DecAttnArgs &A, int64
         tok0 = ntok0;
         len = nlen;
     }
-    // ---- partial record of this wave over its own V tile: m[16] | l[16] | o[16 slots][64]
+    // ---- partial record of this wave over its own V tile: m[16] | l[16] | o[16 slots][D]
     const float ltot = xor32_add(xor16_add(lrun));
     float *pm = (float *)vl, *pl = pm + 16, *po = pm + 32;
     if (q == 0) {
@@ -298,34 +315,34 @@ __device__ __forceinline__ void decode_attend_chunks(const DecAttnArgs &A, int64
         pl[rho] = ltot;
     }
 #pragma unroll
-    for (int m = 0; m < 4; ++m) *(f32x4 *)(po + rho * 64 + 16 * m + 4 * q) = o[m];
+    for (int m = 0; m < MT; ++m) *(f32x4 *)(po + rho * D + 16 * m + 4 * q) = o[m];
     __syncthreads();
     // ---- merge: thread (head, d) walks the NW partial records in wave order (fixed order: bitwise reproducible)
-    for (int tid = threadIdx.x; tid < h * 64; tid += NW * 64) {
-        const int hh = tid >> 6, d = tid & 63;
+    for (int tid = threadIdx.x; tid < h * D; tid += NW * 64) {
+        const int hh = tid >> LOG2D, d = tid & (D - 1);
         float mm = -INFINITY;
 #pragma unroll
-        for (int w = 0; w < NW; ++w) mm = fmaxf(mm, ((const float *)(vt + w * DEC_ATT_TILE))[hh]);
+        for (int w = 0; w < NW; ++w) mm = fmaxf(mm, ((const float *)(vt + w * TILE))[hh]);
         float acc = 0.f, l = 0.f;
         if (mm > -INFINITY) {
 #pragma unroll
             for (int w = 0; w < NW; ++w) {
-                const float *pw = (const float *)(vt + w * DEC_ATT_TILE);
+                const float *pw = (const float *)(vt + w * TILE);
                 const float wgt = __builtin_amdgcn_exp2f(pw[hh] - mm);  // exp2(-inf) = 0 for a wave without a chunk
                 l = fmaf(pw[16 + hh], wgt, l);
-                acc = fmaf(pw[32 + hh * 64 + d], wgt, acc);
+                acc = fmaf(pw[32 + hh * D + d], wgt, acc);
             }
         }
-        ((T *)A.O)[(row * h + hh) * 64 + d] = Elt<T>::from_f(l > 0.f ? acc / l : 0.f);
+        ((T *)A.O)[(row * h + hh) * D + d] = Elt<T>::from_f(l > 0.f ? acc / l : 0.f);
     }
 }
 
-// arbitrary ranges (lanes i < n of wave 0 pass range i, unclamped): sorted union -> chunks.  lds: dec_att_lds(NW) bytes.
-template <typename T, int NW>
+// arbitrary ranges (lanes i < n of wave 0 pass range i, unclamped): sorted union -> chunks.  lds: dec_att_lds(NW, D) bytes.
+template <typename T, int NW, int D = 64>
 __device__ __forceinline__ void decode_attend_row(const DecAttnArgs &A, int64_t row, int rs, int re, unsigned char *lds) {
     const int lane = lane_id();
     const int wave = uniform((int)(threadIdx.x >> 6));
-    int *seg = (int *)(lds + NW * DEC_ATT_TILE);
+    int *seg = (int *)(lds + NW * dec_att_tile(D));
     if (wave == 0) {
         int ns;
         const int total = normalise_ranges_lanes(rs, re, A.n, A.S_kv, seg, &ns);
@@ -352,7 +369,7 @@ __device__ __forceinline__ void decode_attend_row(const DecAttnArgs &A, int64_t 
     }
     ch.cb = inc - ch.nck;
     const int NC = uniform(__shfl(inc, 63, 64));
-    decode_attend_chunks<T, NW>(A, row, ch, NC, lds);
+    decode_attend_chunks<T, NW, SegChunks, D>(A, row, ch, NC, lds);
 }
 
 }  // namespace nsa

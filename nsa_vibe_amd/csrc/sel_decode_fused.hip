@@ -40,8 +40,8 @@ static __device__ long long g_ts2[32];
 #endif
 
 struct DecStepParams {
-    const void *Q;   // [R,h,64]
-    const void *Kc;  // [B,G,S_cmp,64] strided
+    const void *Q;   // [R,h,D]
+    const void *Kc;  // [B,G,S_cmp,D] strided
     float *part_g;   // SPLIT: [R][h][64][2] per-chunk (max, sum exp2)
     float *halo_g;   // SPLIT: [R][64][16] scaled logit of every chunk's last row, per head
     float *pg_g;     // SPLIT: [R][2048] group scores of the row's blocks
@@ -55,7 +55,9 @@ constexpr int DSTEP_CH = 128;                  // chunks of 64 compressed rows p
 constexpr int DSTEP_PART = 16 * DSTEP_CH * 2;  // floats: [head][chunk][2]
 constexpr int DSTEP_HALO = DSTEP_CH * 16;      // floats: [chunk][head] scaled logit of the chunk's last row
 constexpr int DSTEP_TAIL = 1024 + 4 * (128 + 68 + 4);  // bytes behind the V tiles: mlw [16][16] f32 | scr | list | misc
-static size_t dstep_lds(int nw) { return (size_t)nw * DEC_ATT_TILE + DSTEP_TAIL + (nw == 16 ? 3 * DEC_ATT_TILE : 0); }
+// D = 128 (eight waves): 8 x 16 KiB of V tiles + the tail = 132,896 bytes -- one workgroup per CU; the score phases (part 16 KiB | halo 8 KiB |
+// pg <= 8 KiB) fit the 128 KiB of tiles with room to spare
+static size_t dstep_lds(int nw, int D = 64) { return (size_t)nw * dec_att_tile(D) + DSTEP_TAIL + (nw == 16 ? 3 * dec_att_tile(D) : 0); }
 
 // workgroup barrier for data exchanged through LDS only: waits for this wave's LDS operations, NOT for its vector memory operations
 // (__syncthreads() drains vmcnt too, which would stall the three prefetching waves -- and with them the whole workgroup -- until their
@@ -82,9 +84,12 @@ __device__ __forceinline__ bool decode_band_workgroup(const DecBandPair &BP) {
 // registers, those of the later three wait in LDS ([slot][u][head][q] f32x4, 256 h bytes per chunk: each lane reads back exactly what it
 // wrote, so no barrier guards them) until the row's log-sum-exp is known.  Two chunks (16 KiB per wave) are in flight throughout.  Same
 // arithmetic on the same values: p_grp, ranges and O have the bits of every other form.
-template <typename T, int NW, bool SPLIT, int HC, int CPW = 2>
-__global__ __launch_bounds__(NW * 64, 4) void decode_step_kernel(DecStepParams P, SelectParams SP, int cand, DecAttnArgs AT, DecBandPair BP) {
+template <typename T, int NW, bool SPLIT, int HC, int CPW = 2, int D = 64>
+__global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(DecStepParams P, SelectParams SP, int cand, DecAttnArgs AT, DecBandPair BP) {
     static_assert(CPW == 2 || (CPW == 4 && !SPLIT), "four chunks per wave: unsplit form only");
+    static_assert(D == 64 || (D == 128 && NW == 8 && CPW == 2), "D = 128: eight waves per row, logits in the accumulators");
+    constexpr int KS = D / 32;              // MFMA k-steps of a logit
+    constexpr int TILE = dec_att_tile(D);   // V tile of a wave (the score phases live in the same LDS)
     if (decode_band_workgroup<T, NW>(BP)) return;
     using M = MfmaT<T>;
     using x8 = typename M::x8;
@@ -93,14 +98,14 @@ __global__ __launch_bounds__(NW * 64, 4) void decode_step_kernel(DecStepParams P
     // the row's forced blocks (0, t//64 - 1, t//64: known from t alone, selection_scorer.py:159-170) at kernel start, V into their own
     // tiles, K into three tiles behind the tail -- so the score data starts at tile 1
     constexpr bool PREF = NW == 16 && !SPLIT;
-    float *part = (float *)(lds + (PREF ? DEC_ATT_TILE : 0));
+    float *part = (float *)(lds + (PREF ? TILE : 0));
     float *halo = part + DSTEP_PART;
     float *pg = halo + DSTEP_HALO;  // [S_sel]
-    float *mlw = (float *)(lds + NW * DEC_ATT_TILE);  // [NW][16] per-wave copy of the per-head log-sum-exp
+    float *mlw = (float *)(lds + NW * TILE);  // [NW][16] per-wave copy of the per-head log-sum-exp
     int *scr = (int *)(mlw + NW * 16);                // [128] run extraction of the selector
     int *list = scr + 128;                            // [68] picked blocks, ascending
     int *misc = list + 68;                            // [0] number of picked blocks, [1] ticket, [2] team assembled
-    [[maybe_unused]] unsigned char *ktiles = lds + NW * DEC_ATT_TILE + DSTEP_TAIL;  // PREF: [3] K images of the prefetched blocks
+    [[maybe_unused]] unsigned char *ktiles = lds + NW * TILE + DSTEP_TAIL;  // PREF: [3] K images of the prefetched blocks
 
     const int lane = lane_id(), wave = uniform((int)(threadIdx.x >> 6)), rho = lane & 15, q = lane >> 4;
     const int h = P.h;
@@ -121,20 +126,20 @@ __global__ __launch_bounds__(NW * 64, 4) void decode_step_kernel(DecStepParams P
     const int hc = min(rho, h - 1);  // head of this lane's column (columns >= h repeat the last head: their results are never used)
     // ---- phase 1: logits of this workgroup's chunks (64 compressed rows each = MFMA rows; heads = columns), up to two per wave,
     // all loads out at once
-    x8 qf[2];
+    x8 qf[KS];
 #pragma unroll
-    for (int s = 0; s < 2; ++s) qf[s] = *(const x8 *)((const T *)P.Q + ((int64_t)row * h + hc) * 64 + 32 * s + 8 * q);
+    for (int s = 0; s < KS; ++s) qf[s] = *(const x8 *)((const T *)P.Q + ((int64_t)row * h + hc) * D + 32 * s + 8 * q);
     const T *kb = (const T *)P.Kc + b * P.csb + (int64_t)g * P.csg;
     const int c_lo = SPLIT ? sp * P.cpg : 0, c_hi = SPLIT ? min(P.nchunk, c_lo + P.cpg) : P.nchunk;
     constexpr int REGC = CPW == 2 ? 2 : 1;  // chunks of a wave whose logits stay in registers
-    x8 a[2][4][2];
+    x8 a[2][4][KS];
     f32x4 acc[REGC][4];
-    auto load_chunk = [&](int c, x8 (&dst)[4][2]) {
+    auto load_chunk = [&](int c, x8 (&dst)[4][KS]) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int r = min(c * 64 + 16 * u + rho, P.S_cmp - 1);
 #pragma unroll
-            for (int s = 0; s < 2; ++s) dst[u][s] = *(const x8 *)(kb + (int64_t)r * P.css + 32 * s + 8 * q);
+            for (int s = 0; s < KS; ++s) dst[u][s] = *(const x8 *)(kb + (int64_t)r * P.css + 32 * s + 8 * q);
         }
     };
 #pragma unroll
@@ -150,20 +155,20 @@ __global__ __launch_bounds__(NW * 64, 4) void decode_step_kernel(DecStepParams P
         if ((wave == 0 || wave >= 14) && cb >= 2 && cb < P.S_sel && AT.kss == 64) {
             const int blk = wave == 0 ? 0 : cb - (15 - wave);
             pre.tok0 = 64 * blk;
-            pre.ktile = ktiles + slot * DEC_ATT_TILE;
-            decode_prefetch_chunk<T>(AT, row, pre.tok0, min(64, t_end - pre.tok0), lds + wave * DEC_ATT_TILE, ktiles + slot * DEC_ATT_TILE);
+            pre.ktile = ktiles + slot * TILE;
+            decode_prefetch_chunk<T>(AT, row, pre.tok0, min(64, t_end - pre.tok0), lds + wave * TILE, ktiles + slot * TILE);
         }
     }
 
     for (int i = threadIdx.x; i < P.S_sel; i += NW * 64) pg[i] = 0.f;  // blocks without a compressed row keep a zero score
     // scaled logits of chunk c (MFMA rows = 64 compressed rows, columns = heads) and the chunk's (max, sum exp2) per head: the arithmetic of
     // decode_logits_mfma_kernel
-    auto chunk_logits = [&](int c, const x8 (&src)[4][2], f32x4 (&z)[4]) {
+    auto chunk_logits = [&](int c, const x8 (&src)[4][KS], f32x4 (&z)[4]) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             f32x4 zz = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int s = 0; s < 2; ++s) zz = M::mma(src[u][s], qf[s], zz);
+            for (int s = 0; s < KS; ++s) zz = M::mma(src[u][s], qf[s], zz);
             z[u] = zz;
         }
     };
@@ -210,7 +215,7 @@ __global__ __launch_bounds__(NW * 64, 4) void decode_step_kernel(DecStepParams P
                 for (int u = 0; u < 4; ++u) {
                     f32x4 z = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                    for (int s = 0; s < 2; ++s) z = M::mma(a[k][u][s], qf[s], z);
+                    for (int s = 0; s < KS; ++s) z = M::mma(a[k][u][s], qf[s], z);
                     acc[k][u] = z;
                 }
                 chunk_stats(c, acc[k]);
@@ -280,12 +285,12 @@ __global__ __launch_bounds__(NW * 64, 4) void decode_step_kernel(DecStepParams P
             // the CUs).  Nobody waits for anybody here: this workgroup forms the records and edge logits of ALL chunks of the row itself --
             // the same instructions on the same data, so the same bits as its team mates publish -- and carries on.  Slower, never stuck.
             for (int c = wave; c < P.nchunk; c += NW) {
-                x8 b2[4][2];
+                x8 b2[4][KS];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const int r = min(c * 64 + 16 * u + rho, P.S_cmp - 1);
 #pragma unroll
-                    for (int s2 = 0; s2 < 2; ++s2) b2[u][s2] = *(const x8 *)(kb + (int64_t)r * P.css + 32 * s2 + 8 * q);
+                    for (int s2 = 0; s2 < KS; ++s2) b2[u][s2] = *(const x8 *)(kb + (int64_t)r * P.css + 32 * s2 + 8 * q);
                 }
                 f32x4 z[4];
                 float m = -INFINITY;
@@ -293,7 +298,7 @@ __global__ __launch_bounds__(NW * 64, 4) void decode_step_kernel(DecStepParams P
                 for (int u = 0; u < 4; ++u) {
                     z[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                    for (int s2 = 0; s2 < 2; ++s2) z[u] = M::mma(b2[u][s2], qf[s2], z[u]);
+                    for (int s2 = 0; s2 < KS; ++s2) z[u] = M::mma(b2[u][s2], qf[s2], z[u]);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const float v = z[u][j] * P.c2;
@@ -474,7 +479,7 @@ __global__ __launch_bounds__(NW * 64, 4) void decode_step_kernel(DecStepParams P
     // ---- phase 4: selection attention over the picked blocks (wave e mod NW gathers block e; partials merged through LDS)
     const ListChunks ch{list, min(P.t_token + 1, AT.S_kv)};
     DS_TS(9);
-    decode_attend_chunks<T, NW>(AT, row, ch, NC, lds, qf, pre);
+    decode_attend_chunks<T, NW, ListChunks, D>(AT, row, ch, NC, lds, qf, pre);
     DS_TS(10);
 }
 
@@ -753,7 +758,7 @@ static int device_cu_count() {
 static size_t dstep_score_bytes(int nw, int h, int S_sel, int cpw) {
     return sizeof(float) * (DSTEP_PART + DSTEP_HALO + (size_t)((S_sel + 3) & ~3)) + (cpw == 4 ? (size_t)3 * nw * 256 * h : 0);
 }
-static size_t dstep_score_room(int nw) { return (size_t)(nw == 16 ? 13 : nw) * DEC_ATT_TILE; }
+static size_t dstep_score_room(int nw, int D = 64) { return (size_t)(nw == 16 ? 13 : nw) * dec_att_tile(D); }
 
 // waves per row workgroup, workgroups per row (1 = an unsplit kernel) and the kernel form; false = this shape is not for the one-launch step.
 // form 0: logits in the accumulators (two chunks per wave; a long row as a team of NS workgroups that meet inside the launch: R * NS of them
@@ -762,13 +767,15 @@ static size_t dstep_score_room(int nw) { return (size_t)(nw == 16 ? 13 : nw) * D
 // TUNE_DECODE_WIDE: -1 = form 2 where a team would not fit the chip (measured cold, profiles/r04/decode_cold_forms.txt: B=256@64k 75.5 us
 // against 98.4 for form 1 and 98.1 for the round-2 two-launch route; B=128@64k 47.4 / 52.3 / 56.8), 0 = never, 1 / 2 = that form wherever
 // the row fits it.
-static bool decode_step_plan(int64_t R, int nchunk, int h, int S_sel, int *nw_out, int *ns_out, int *form_out) {
-    const int nw = dec_att_waves(R);
-    const int64_t slots = (int64_t)device_cu_count() * (nw == 16 ? 1 : 2);  // 1024-thread workgroups hold a CU each (LDS), 512-thread ones share it
+// D = 128: form 0 only, on eight waves with a CU each (132,896 bytes of LDS); a long row whose team does not fit the chip is declined (the
+// forms that keep logits or exponential sums of later chunks are not built for it: the caller takes the two-launch route).
+static bool decode_step_plan(int64_t R, int nchunk, int h, int S_sel, int D, int *nw_out, int *ns_out, int *form_out) {
+    const int nw = dec_att_waves(R, D);
+    const int64_t slots = (int64_t)device_cu_count() * (nw == 16 || D == 128 ? 1 : 2);  // 1024-thread workgroups hold a CU each (LDS), 512-thread ones share it
     const int mode = tuning(TUNE_DECODE_SPLIT), wide = tuning(TUNE_DECODE_WIDE);
     int ns = (nchunk + 2 * nw - 1) / (2 * nw);  // at most two chunks per wave (the accumulators of a wave's chunks stay in registers)
-    const bool wide_fits = nchunk > 2 * nw && nchunk <= 4 * nw && dstep_score_bytes(nw, h, S_sel, 4) <= dstep_score_room(nw);
-    const bool onepass_fits = nchunk <= 8 * nw && dstep_score_bytes(nw, h, S_sel, 2) <= dstep_score_room(nw);
+    const bool wide_fits = D == 64 && nchunk > 2 * nw && nchunk <= 4 * nw && dstep_score_bytes(nw, h, S_sel, 4) <= dstep_score_room(nw);
+    const bool onepass_fits = D == 64 && nchunk <= 8 * nw && dstep_score_bytes(nw, h, S_sel, 2) <= dstep_score_room(nw);
     const bool no_team = ns > 1 && R * ns > slots;
     *nw_out = nw;
     *ns_out = 1;
@@ -800,26 +807,42 @@ static bool decode_step_plan(int64_t R, int nchunk, int h, int S_sel, int *nw_ou
     return true;
 }
 
+// the part of decode_step_supported that depends on the shape and the tuning switches alone (default block geometry assumed): the one
+// predicate behind both the call and nsa_sel_decode_step_plan.  form / nsplit: the plan (-1 / 0 when declined)
+bool decode_step_shape_plan(int64_t R, int dtype, int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int n_top, int *form, int *nsplit) {
+    if (form) *form = -1;
+    if (nsplit) *nsplit = 0;
+    if (tuning(TUNE_DECODE_STEP) == 0 || tuning(TUNE_DECODE_UNFUSED) > 0) return false;
+    int nw, ns, fm;
+    if (R < 1 || S_cmp < 1 || S_sel < 1 || h < 1 || h > 16 || Dk != Dv || (Dk != 64 && Dk != 128) ||
+        !decode_step_plan(R, (S_cmp + 63) / 64, h, S_sel, Dk, &nw, &ns, &fm))
+        return false;
+    if (!((dtype == NSA_DT_BF16 || dtype == NSA_DT_F16) && S_cmp <= 64 * DSTEP_CH && S_sel <= 2048 && n_top >= 3 && n_top <= 64 && S_kv >= 1 &&
+          (int64_t)S_kv * 2 * Dv < ((int64_t)1 << 31) && sel_attn_decode_wg_shape_ok(dtype, h, Dk, Dv, n_top) &&
+          dstep_score_bytes(nw, h, S_sel, fm == 1 ? 4 : 2) <= dstep_score_room(nw, Dk)))
+        return false;
+    if (form) *form = fm;
+    if (nsplit) *nsplit = ns;
+    return true;
+}
+
 bool decode_step_supported(int64_t R, int dtype, int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int l, int d, int l_sel, int n_top, int t_token,
                            int64_t kcb, int64_t kcg, int64_t kcs, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg, int64_t vss,
                            const void *Q, const void *Kc, const void *K, const void *V) {
-    if (tuning(TUNE_DECODE_STEP) == 0 || tuning(TUNE_DECODE_UNFUSED) > 0) return false;
-    int nw, ns, form;
-    if (R < 1 || S_cmp < 1 || S_sel < 1 || h < 1 || h > 16 || !decode_step_plan(R, (S_cmp + 63) / 64, h, S_sel, &nw, &ns, &form)) return false;
-    return (dtype == NSA_DT_BF16 || dtype == NSA_DT_F16) && Dk == 64 && Dv == 64 && h >= 1 && h <= 16 && d > 0 && l == 2 * d && l_sel == 4 * d &&
-           l_sel == 64 && S_cmp >= 1 && S_cmp <= 64 * DSTEP_CH && S_sel >= 1 && S_sel <= 2048 && n_top >= 3 && n_top <= 64 && t_token >= 0 &&
-           S_kv >= t_token + 1 && (int64_t)S_kv * 128 < ((int64_t)1 << 31) && kcs % 8 == 0 && kcb % 8 == 0 && kcg % 8 == 0 &&
-           ((uintptr_t)Kc % 16 == 0) && sel_attn_decode_wg_supported(dtype, h, Dk, Dv, n_top, ksb, ksg, kss, vsb, vsg, vss, Q, K, V);
+    return decode_step_shape_plan(R, dtype, h, Dk, Dv, S_cmp, S_sel, S_kv, n_top, nullptr, nullptr) && d > 0 && l == 2 * d && l_sel == 4 * d &&
+           l_sel == 64 && t_token >= 0 && S_kv >= t_token + 1 && kcs % 8 == 0 && kcb % 8 == 0 && kcg % 8 == 0 && ((uintptr_t)Kc % 16 == 0) &&
+           sel_attn_decode_wg_supported(dtype, h, Dk, Dv, n_top, ksb, ksg, kss, vsb, vsg, vss, Q, K, V);
 }
 
 int launch_decode_step(const void *Q, const void *Kc, const void *K, const void *V, void *O, int32_t *ranges_out, int B, int G, int h, int S_cmp,
                        int S_sel, int S_kv, int n_top, int t_token, int64_t kcb, int64_t kcg, int64_t kcs, int64_t ksb, int64_t ksg, int64_t kss,
-                       int64_t vsb, int64_t vsg, int64_t vss, int dtype, float scale, void *ws, size_t ws_bytes, hipStream_t st, const DecBandPair *band) {
+                       int64_t vsb, int64_t vsg, int64_t vss, int dtype, float scale, void *ws, size_t ws_bytes, hipStream_t st, const DecBandPair *band, int D) {
     const int64_t R = (int64_t)B * G;
+    NSA_CHECK_ARG(D == 64 || D == 128, "decode step: head dimension 64 or 128");
     NSA_CHECK_ARG(R >= 1 && R <= (1 << 24), "decode step: bad row count");
     const int nchunk = ((S_cmp + 63) / 64);
     int nw = 16, ns = 1, form = 0;
-    NSA_CHECK_ARG(decode_step_plan(R, nchunk, h, S_sel, &nw, &ns, &form), "decode step: shape not covered (decode_step_supported)");
+    NSA_CHECK_ARG(decode_step_plan(R, nchunk, h, S_sel, D, &nw, &ns, &form), "decode step: shape not covered (decode_step_supported)");
     const int cpw = form == 1 ? 4 : 2;
     DecStepParams P{Q, Kc, nullptr, nullptr, nullptr, nullptr, (int)R, G, h, S_cmp, S_sel, ns, nchunk, (nchunk + ns - 1) / ns, t_token, 0, kcb, kcg, kcs, scale * LOG2E};
     P.spin = tuning(TUNE_DECODE_TEAM_SPIN) >= 0 ? tuning(TUNE_DECODE_TEAM_SPIN) : 512;  // polls of ~0.5-1 us each before a workgroup goes on alone
@@ -846,19 +869,24 @@ int launch_decode_step(const void *Q, const void *Kc, const void *K, const void 
 #define NSA_DSK(NW_, SP_, HC_) (bf ? decode_step_kernel<__bf16, NW_, SP_, HC_> : decode_step_kernel<_Float16, NW_, SP_, HC_>)
 #define NSA_DSK4(NW_, HC_) (bf ? decode_step_kernel<__bf16, NW_, false, HC_, 4> : decode_step_kernel<_Float16, NW_, false, HC_, 4>)
 #define NSA_DSK1(NW_, HC_) (bf ? decode_step_onepass_kernel<__bf16, NW_, HC_> : decode_step_onepass_kernel<_Float16, NW_, HC_>)
-    if (form == 2) k = h == 6 ? (nw == 16 ? NSA_DSK1(16, 6) : NSA_DSK1(8, 6)) : (nw == 16 ? NSA_DSK1(16, 0) : NSA_DSK1(8, 0));
+#define NSA_DSK128(SP_, HC_) (bf ? decode_step_kernel<__bf16, 8, SP_, HC_, 2, 128> : decode_step_kernel<_Float16, 8, SP_, HC_, 2, 128>)
+    if (D == 128) {
+        NSA_CHECK_ARG(form == 0 && nw == 8, "decode step: D = 128 runs form 0 on eight waves");
+        k = h == 6 ? (split ? NSA_DSK128(true, 6) : NSA_DSK128(false, 6)) : (split ? NSA_DSK128(true, 0) : NSA_DSK128(false, 0));
+    } else if (form == 2) k = h == 6 ? (nw == 16 ? NSA_DSK1(16, 6) : NSA_DSK1(8, 6)) : (nw == 16 ? NSA_DSK1(16, 0) : NSA_DSK1(8, 0));
     else if (cpw == 4) k = h == 6 ? (nw == 16 ? NSA_DSK4(16, 6) : NSA_DSK4(8, 6)) : (nw == 16 ? NSA_DSK4(16, 0) : NSA_DSK4(8, 0));
     else if (h == 6) k = nw == 16 ? (split ? NSA_DSK(16, true, 6) : NSA_DSK(16, false, 6)) : (split ? NSA_DSK(8, true, 6) : NSA_DSK(8, false, 6));
     else k = nw == 16 ? (split ? NSA_DSK(16, true, 0) : NSA_DSK(16, false, 0)) : (split ? NSA_DSK(8, true, 0) : NSA_DSK(8, false, 0));
+#undef NSA_DSK128
 #undef NSA_DSK1
 #undef NSA_DSK4
 #undef NSA_DSK
-    const size_t lds = dstep_lds(nw);
+    const size_t lds = dstep_lds(nw, D);
     // the score data sits in V tiles 1 .. (the prefetching waves of the 16-wave form own tiles 0, 14, 15)
-    NSA_CHECK_ARG(dstep_score_bytes(nw, h, S_sel, cpw) <= dstep_score_room(nw), "decode step: S_sel too large");
+    NSA_CHECK_ARG(dstep_score_bytes(nw, h, S_sel, cpw) <= dstep_score_room(nw, D), "decode step: S_sel too large");
     {  // raise the dynamic-LDS limit once per kernel (the runtime call costs about a millisecond)
         static std::mutex mu;
-        static void *raised[32] = {};
+        static void *raised[48] = {};
         std::lock_guard<std::mutex> lk(mu);
         bool done = false;
         for (void *r : raised) done |= (r == (void *)k);
@@ -877,7 +905,7 @@ int launch_decode_step(const void *Q, const void *Kc, const void *K, const void 
     if (band) {  // the layer step's sliding + compressed branches on workgroups behind the step's own (decode_band_workgroup)
         BP = *band;
         int64_t waves[2];
-        NSA_CHECK_ARG(BP.w.Dk == 64 && BP.w.Dv == 64 && band_dual_plan(&BP.w, &BP.c, dtype, waves), "decode step: band branches not in split form");
+        NSA_CHECK_ARG(D == 64 && BP.w.Dk == 64 && BP.w.Dv == 64 && band_dual_plan(&BP.w, &BP.c, dtype, waves), "decode step: band branches not in split form");
         if (BP.mg.on) {  // splits merged by the workgroup that holds them: a unit = nsplit consecutive waves of one workgroup
             NSA_CHECK_ARG(BP.w.S == 1 && BP.c.S == 1 && BP.mg.gates && BP.w.O && BP.c.O && h <= 16, "decode step: band merge needs S = 1, outputs and a gate buffer");
             int nsm = 1;

@@ -207,6 +207,21 @@ def selection_decode_step(Q: torch.Tensor, K_cmp: torch.Tensor, K: torch.Tensor,
     return O, rg
 
 
+def selection_decode_step_plan(B: int, G: int, h: int, Dk: int, Dv: int, S_cmp: int, S_sel: int, S_kv: int, n_top: int,
+                               dtype: torch.dtype = torch.bfloat16) -> dict:
+    """What selection_decode_step does with a shape under the current tuning switches (nsa_sel_decode_step_plan; default block geometry,
+    aligned contiguous-row inputs): {"launches": 1 exactly when the call is the one-launch step, otherwise an estimate > 1 of the separate route's launches, "form": 0 logits in registers /
+    1 four chunks per wave / 2 one-pass / -1 step declined, "nsplit": workgroups per row (0 when declined)}.  Launches no kernel, but asks the HIP runtime for the current device's CU count (which initialises the runtime): the
+    answer is for the device that is current when it is called."""
+    import ctypes
+
+    n, f, s = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    rc = _lib.lib().nsa_sel_decode_step_plan(int(B), int(G), int(h), int(Dk), int(Dv), int(S_cmp), int(S_sel), int(S_kv), int(n_top),
+                                             _DT[dtype], ctypes.byref(n), ctypes.byref(f), ctypes.byref(s))
+    _lib.check(rc, "nsa_sel_decode_step_plan")
+    return {"launches": n.value, "form": f.value, "nsplit": s.value}
+
+
 def select_and_attend(p_grp: torch.Tensor, Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, meta, n_top: int, *,
                       mode: str = "batched", t0: int = 0, force_init: bool = True, force_local: int = 2,
                       scale: Optional[float] = None, return_lse: bool = False):
