@@ -1,0 +1,384 @@
+// Host check of the C ABI's dispatch layer (tests/test_dispatch_host.py runs it; no GPU).  A plain host program that loads the library and
+// answers the HIP calls of its host code itself: hipMalloc comes from the heap, the memsets fill host memory, and hipLaunchKernel is counted
+// and refused -- no kernel runs.  A refused launch comes back through the entry point as "HIP error ... in <launcher> launch", so calling an
+// entry point again and again with the refusal moved one launch further walks its whole route: every case prints the launchers in order,
+// each launch's grid / block / LDS bytes, the host memsets, and the status and nsa_hip_last_error() of the complete call.
+//   dispatch_check <path of libnsa_sel_hip.so>      prints one JSON object, a member per case
+#include <dlfcn.h>
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <functional>
+#include <string>
+#include <vector>
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/nsa_sel_hip.h"
+#include "sel_attn_params.hpp"
+
+// ---- the HIP runtime as this program answers it ------------------------------------------------
+static const hipError_t REFUSED = hipErrorNotSupported;
+static int g_refuse_at = -1;  // index of the launch that is refused (-1: none)
+static int g_launches = 0, g_memsets = 0;
+static hipError_t g_last = hipSuccess;
+static std::vector<std::string> g_geom;
+static int g_peek_launch = -1;  // copy g_peek bytes of this launch's first kernel argument (an argument block passed by value)
+static std::vector<unsigned char> g_peek;
+struct Config {
+    dim3 grid, block;
+    size_t shmem;
+    hipStream_t stream;
+};
+static std::vector<Config> g_config;
+
+extern "C" {
+__attribute__((visibility("default"))) hipError_t hipMalloc(void **p, size_t n) {
+    *p = aligned_alloc(256, (n + 255) & ~(size_t)255);
+    return *p ? hipSuccess : hipErrorOutOfMemory;
+}
+__attribute__((visibility("default"))) hipError_t hipFree(void *p) {
+    free(p);
+    return hipSuccess;
+}
+__attribute__((visibility("default"))) hipError_t hipMemsetAsync(void *dst, int value, size_t n, hipStream_t) {
+    ++g_memsets;
+    memset(dst, value, n);
+    return hipSuccess;
+}
+__attribute__((visibility("default"))) hipError_t hipMemsetD32Async(hipDeviceptr_t dst, int value, size_t count, hipStream_t) {
+    ++g_memsets;
+    for (size_t i = 0; i < count; ++i) ((int *)dst)[i] = value;
+    return hipSuccess;
+}
+__attribute__((visibility("default"))) hipError_t hipGetLastError(void) {
+    const hipError_t e = g_last;
+    g_last = hipSuccess;
+    return e;
+}
+__attribute__((visibility("default"))) const char *hipGetErrorString(hipError_t e) { return e == REFUSED ? "launch refused" : "other"; }
+__attribute__((visibility("default"))) hipError_t hipGetDevice(int *dev) {
+    *dev = 0;
+    return hipSuccess;
+}
+__attribute__((visibility("default"))) hipError_t hipDeviceGetAttribute(int *v, hipDeviceAttribute_t, int) {
+    *v = 256;  // compute units of the MI355X (the only attribute the library asks for)
+    return hipSuccess;
+}
+__attribute__((visibility("default"))) hipError_t hipFuncSetAttribute(const void *, hipFuncAttribute, int) { return hipSuccess; }
+__attribute__((visibility("default"))) hipError_t __hipPushCallConfiguration(dim3 grid, dim3 block, size_t shmem, hipStream_t stream) {
+    g_config.push_back({grid, block, shmem, stream});
+    return hipSuccess;
+}
+__attribute__((visibility("default"))) hipError_t __hipPopCallConfiguration(dim3 *grid, dim3 *block, size_t *shmem, hipStream_t *stream) {
+    const Config c = g_config.back();
+    g_config.pop_back();
+    *grid = c.grid; *block = c.block; *shmem = c.shmem; *stream = c.stream;
+    return hipSuccess;
+}
+__attribute__((visibility("default"))) hipError_t hipLaunchKernel(const void *, dim3 grid, dim3 block, void **args, size_t shmem, hipStream_t) {
+    const int i = g_launches++;
+    char s[96];
+    snprintf(s, sizeof(s), "%u,%u,%u/%u,%u,%u/%zu", grid.x, grid.y, grid.z, block.x, block.y, block.z, shmem);
+    g_geom.push_back(s);
+    if (i == g_peek_launch && !g_peek.empty()) memcpy(g_peek.data(), args[0], g_peek.size());
+    if (i == g_refuse_at) return g_last = REFUSED;
+    return hipSuccess;
+}
+}  // extern "C"
+
+// ---- the library --------------------------------------------------------------------------------
+static void *g_lib;
+#define NSA_FN(name) ((decltype(&name))sym(#name))
+static void *sym(const char *name) {
+    void *p = dlsym(g_lib, name);
+    if (!p) {
+        fprintf(stderr, "missing symbol %s\n", name);
+        exit(2);
+    }
+    return p;
+}
+
+static void *dev(size_t bytes, int fill = 0) {
+    void *p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) exit(2);
+    memset(p, fill, bytes);
+    return p;
+}
+static void *off(void *p, size_t bytes) { return (unsigned char *)p + bytes; }
+static bool all_zero(const void *p, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        if (((const unsigned char *)p)[i]) return false;
+    return true;
+}
+
+static bool g_first = true;
+static std::string quoted(const std::string &s) {
+    std::string o = "\"";
+    for (char c : s) {
+        if (c == '"' || c == '\\') o += '\\';
+        o += c;
+    }
+    return o + "\"";
+}
+static std::string list(const std::vector<std::string> &v) {
+    std::string o = "[";
+    for (size_t i = 0; i < v.size(); ++i) o += (i ? ", " : "") + quoted(v[i]);
+    return o + "]";
+}
+
+// Walks the route of one call: refuses launch 0, 1, 2, ... until the call ends without a refused launch.  `after` may add fields
+// ("key": value, ...) from what the complete call left behind.
+static void run(const char *label, const std::function<int()> &call, const std::function<std::string()> &after = nullptr) {
+    auto last_error = NSA_FN(nsa_hip_last_error);
+    std::vector<std::string> names;
+    int rc = 0;
+    std::string err;
+    for (int n = 0; n < 64; ++n) {
+        g_refuse_at = n;
+        g_launches = g_memsets = 0;
+        g_geom.clear();
+        g_last = hipSuccess;
+        rc = call();
+        err = rc ? last_error() : "";
+        const size_t in = err.find(" in ");
+        if (rc == NSA_ERR_HIP && g_launches == n + 1 && in != std::string::npos) {
+            names.push_back(err.substr(in + 4));
+            continue;
+        }
+        break;
+    }
+    printf("%s\n%s: {\"rc\": %d, \"error\": %s, \"launches\": %s, \"geometry\": %s, \"memsets\": %d%s%s}", g_first ? "" : ",", quoted(label).c_str(),
+           rc, quoted(err).c_str(), list(names).c_str(), list(g_geom).c_str(), g_memsets, after ? ", " : "", after ? after().c_str() : "");
+    g_first = false;
+    g_peek_launch = -1;
+    g_peek.clear();
+}
+
+// the argument block of pcmp_kernel up to its scale (PcmpParams, sel_scores.hip)
+struct PcmpHead {
+    const void *Q, *Kc;
+    float *p_cmp;
+    int64_t row0, nrows;
+    int S, G, h, Dk, S_cmp;
+    int64_t csb, csg, css;
+    float scale;
+};
+
+template <class P>
+static void peek(int launch) {
+    g_peek_launch = launch;
+    g_peek.assign(sizeof(P), 0);
+}
+template <class P>
+static std::string peeked_scale() {
+    P p;
+    memcpy(&p, g_peek.data(), sizeof(P));
+    char s[64];
+    snprintf(s, sizeof(s), "\"scale\": %.9g", (double)p.scale);
+    return s;
+}
+
+int main(int argc, char **argv) {
+    if (argc < 2) {
+        fprintf(stderr, "usage: dispatch_check <libnsa_sel_hip.so>\n");
+        return 2;
+    }
+    g_lib = dlopen(argv[1], RTLD_NOW | RTLD_GLOBAL);
+    if (!g_lib) {
+        fprintf(stderr, "%s\n", dlerror());
+        return 2;
+    }
+    auto set_tuning = NSA_FN(nsa_hip_set_tuning);
+    const int dt = NSA_DT_BF16;
+    const int B = 1, S = 128, G = 2, h = 6, D = 64, S_kv = 128, n = 16;
+    const int64_t sb = (int64_t)G * S_kv * D, sg = (int64_t)S_kv * D;
+    const size_t MB = 1 << 20;
+    void *Q = dev(MB), *K = dev(MB), *V = dev(MB), *O = dev(MB), *dO = dev(MB), *dQ = dev(MB), *ws = dev(64 * MB);
+    float *lse = (float *)dev(MB), *dK = (float *)dev(MB), *dV = (float *)dev(MB), *p_grp = (float *)dev(MB);
+    int32_t *ranges = (int32_t *)dev(MB);
+    const size_t dkv_bytes = sizeof(float) * (size_t)B * G * S_kv * D;
+    printf("{");
+
+    // ---- selection attention forward: the MFMA route asks for aligned operands, everything else keeps the generic (VALU) kernel
+    auto fwd = NSA_FN(nsa_sel_attn_fwd);
+    auto sel_fwd = [&](void *K_, int64_t kss, int variant, float scale, int n_ranges = 16, float *lse_ = nullptr) {
+        return fwd(Q, K_, V, ranges, O, lse_, B, S, G, h, D, D, S_kv, n_ranges, sb, sg, kss, sb, sg, D, dt, scale, variant, ws, 64 * MB, nullptr);
+    };
+    run("sel_attn_fwd/aligned", [&] { return sel_fwd(K, D, 0, 0.f); });
+    run("sel_attn_fwd/K_2_bytes_off", [&] { return sel_fwd(off(K, 2), D, 0, 0.f); });
+    run("sel_attn_fwd/K_8_bytes_off", [&] { return sel_fwd(off(K, 8), D, 0, 0.f); });
+    run("sel_attn_fwd/kss_not_8", [&] { return sel_fwd(K, D + 4, 0, 0.f); });
+    run("sel_attn_fwd/forced_mfma_unaligned", [&] { return sel_fwd(off(K, 2), D, 2, 0.f); });
+    run("sel_attn_fwd/forced_mfma_aligned", [&] { return sel_fwd(K, D, 2, 0.f); });
+    run("sel_attn_fwd/no_ranges", [&] { memset(O, 0xff, 4096); return sel_fwd(K, D, 0, 0.f, 0, lse); },
+        [&] { return std::string("\"O_zero\": ") + (all_zero(O, (size_t)B * S * G * h * D * 2) ? "true" : "false"); });
+    peek<nsa::SelAttnParams>(0);
+    run("sel_attn_fwd/scale_default", [&] { return sel_fwd(K, D, 1, 0.f); }, peeked_scale<nsa::SelAttnParams>);
+    peek<nsa::SelAttnParams>(0);
+    run("sel_attn_fwd/scale_negative", [&] { return sel_fwd(K, D, 1, -1.f); }, peeked_scale<nsa::SelAttnParams>);
+    peek<nsa::SelAttnParams>(0);
+    run("sel_attn_fwd/scale_given", [&] { return sel_fwd(K, D, 1, 0.25f); }, peeked_scale<nsa::SelAttnParams>);
+
+    // ---- selection attention backward: the generic kernel accumulates into dK / dV, so the host zeroes them on that route only
+    auto bwd = NSA_FN(nsa_sel_attn_bwd);
+    const size_t bwd_need = NSA_FN(nsa_sel_attn_bwd_workspace)(B, S, G, h, D, D, S_kv, dt, 0);
+    auto sel_bwd = [&](void *K_, void *dO_, int variant, float scale, int n_ranges = 16, size_t ws_bytes = 64 * MB) {
+        memset(dK, 0xff, dkv_bytes);
+        memset(dV, 0xff, dkv_bytes);
+        memset(dQ, 0xff, 4096);
+        return bwd(Q, K_, V, ranges, O, lse, dO_, dQ, dK, dV, B, S, G, h, D, D, S_kv, n_ranges, sb, sg, D, sb, sg, D, dt, scale, variant, ws, ws_bytes,
+                   nullptr);
+    };
+    auto zeroed = [&] {
+        return std::string("\"dK_zero\": ") + (all_zero(dK, dkv_bytes) ? "true" : "false") + ", \"dV_zero\": " + (all_zero(dV, dkv_bytes) ? "true" : "false") +
+               ", \"dQ_zero\": " + (all_zero(dQ, (size_t)B * S * G * h * D * 2) ? "true" : "false");
+    };
+    run("sel_attn_bwd/aligned", [&] { return sel_bwd(K, dO, 0, 0.f); }, zeroed);
+    run("sel_attn_bwd/K_2_bytes_off", [&] { return sel_bwd(off(K, 2), dO, 0, 0.f); }, zeroed);
+    run("sel_attn_bwd/dO_8_bytes_off", [&] { return sel_bwd(K, off(dO, 8), 0, 0.f); }, zeroed);
+    run("sel_attn_bwd/workspace_one_byte_short", [&] { return sel_bwd(K, dO, 0, 0.f, 16, bwd_need - 1); }, zeroed);
+    run("sel_attn_bwd/generic_asked", [&] { return sel_bwd(K, dO, 1, 0.f); }, zeroed);
+    run("sel_attn_bwd/forced_mfma_unaligned", [&] { return sel_bwd(off(K, 2), dO, 2, 0.f); }, zeroed);
+    run("sel_attn_bwd/no_ranges", [&] { return sel_bwd(K, dO, 0, 0.f, 0); }, zeroed);
+    peek<nsa::SelAttnBwdParams>(0);
+    run("sel_attn_bwd/scale_default", [&] { return sel_bwd(K, dO, 1, 0.f); }, peeked_scale<nsa::SelAttnBwdParams>);
+    peek<nsa::SelAttnBwdParams>(0);
+    run("sel_attn_bwd/scale_given", [&] { return sel_bwd(K, dO, 1, 0.25f); }, peeked_scale<nsa::SelAttnBwdParams>);
+
+    // ---- band attention forward and backward
+    auto bfwd = NSA_FN(nsa_band_attn_fwd);
+    auto band_fwd = [&](void *K_, void *O_, int variant, float scale) {
+        return bfwd(Q, K_, V, O_, nullptr, B, S, G, h, D, D, S_kv, sb, sg, D, sb, sg, D, 0, 0, 1, 0, 64, dt, scale, variant, ws, 64 * MB, nullptr);
+    };
+    run("band_attn_fwd/aligned", [&] { return band_fwd(K, O, 0, 0.f); });
+    run("band_attn_fwd/K_2_bytes_off", [&] { return band_fwd(off(K, 2), O, 0, 0.f); });
+    run("band_attn_fwd/O_4_bytes_off", [&] { return band_fwd(K, off(O, 4), 0, 0.f); });
+    run("band_attn_fwd/forced_mfma_unaligned", [&] { return band_fwd(off(K, 2), O, 2, 0.f); });
+    peek<nsa::BandAttnParams>(0);
+    run("band_attn_fwd/scale_default", [&] { return band_fwd(K, O, 1, 0.f); }, peeked_scale<nsa::BandAttnParams>);
+    peek<nsa::BandAttnParams>(0);
+    run("band_attn_fwd/scale_given", [&] { return band_fwd(K, O, 1, 0.25f); }, peeked_scale<nsa::BandAttnParams>);
+    auto bbwd = NSA_FN(nsa_band_attn_bwd);
+    const size_t bband_need = NSA_FN(nsa_band_attn_bwd_workspace)(B, S, G, h, D, D, S_kv, dt, 0);
+    auto band_bwd = [&](void *K_, void *dO_, int variant, size_t ws_bytes = 64 * MB) {
+        memset(dK, 0xff, dkv_bytes);
+        memset(dV, 0xff, dkv_bytes);
+        memset(dQ, 0xff, 4096);
+        return bbwd(Q, K_, V, O, lse, dO_, dQ, dK, dV, B, S, G, h, D, D, S_kv, sb, sg, D, sb, sg, D, 0, 0, 1, 0, 64, dt, 0.f, variant, ws, ws_bytes,
+                    nullptr);
+    };
+    run("band_attn_bwd/aligned", [&] { return band_bwd(K, dO, 0); }, zeroed);
+    run("band_attn_bwd/K_2_bytes_off", [&] { return band_bwd(off(K, 2), dO, 0); }, zeroed);
+    run("band_attn_bwd/dO_8_bytes_off", [&] { return band_bwd(K, off(dO, 8), 0); }, zeroed);
+    run("band_attn_bwd/forced_mfma_unaligned", [&] { return band_bwd(off(K, 2), dO, 2); }, zeroed);
+    run("band_attn_bwd/workspace_one_byte_short", [&] { return band_bwd(K, dO, 0, bband_need - 1); }, zeroed);
+    run("band_attn_bwd/workspace_exact", [&] { return band_bwd(K, dO, 0, bband_need); }, zeroed);
+
+    // ---- selector + attention: one launch only with SEL_FUSE on aligned operands
+    auto ssa = NSA_FN(nsa_sel_select_attn_fwd);
+    // (with fewer than 1024 rows the attention splits the keys and is never fused: S = 512 is the shape on which SEL_FUSE decides)
+    auto select_attn = [&](void *K_, int S_) {
+        return ssa(p_grp, 0, nullptr, (S_ + 63) / 64, 64, n, 1, 2, NSA_SEL_SEQUENTIAL, S_, ranges, n, Q, K_, V, O, nullptr, B, S_, G, h, D, D, S_, (int64_t)G * S_ * D,
+                   (int64_t)S_ * D, D, (int64_t)G * S_ * D, (int64_t)S_ * D, D, dt, 0.f, ws, 64 * MB, nullptr);
+    };
+    for (int S_ : {128, 512}) {
+        const std::string at = "sel_select_attn_fwd/S" + std::to_string(S_);
+        run((at + "_two_launches").c_str(), [&] { return select_attn(K, S_); });
+        set_tuning("SEL_FUSE", 1);
+        run((at + "_SEL_FUSE").c_str(), [&] { return select_attn(K, S_); });
+        run((at + "_SEL_FUSE_K_2_bytes_off").c_str(), [&] { return select_attn(off(K, 2), S_); });
+        set_tuning("SEL_FUSE", 0);
+    }
+
+    // ---- scorer: default scale; decode-normalised rows leave the decode-shaped route at S = 64
+    auto scores_rows = NSA_FN(nsa_sel_scores_rows);
+    void *Kc = dev(MB);
+    int32_t *csc_ptr = (int32_t *)dev(MB), *csc_rows = (int32_t *)dev(MB);
+    float *csc_vals = (float *)dev(MB);
+    auto scores = [&](int S_, int norm, int variant, float scale) {
+        const int n_cmp = (S_ - 32) / 16 + 1;
+        return scores_rows(Q, Kc, p_grp, B, S_, G, h, D, n_cmp, (int64_t)G * n_cmp * D, (int64_t)n_cmp * D, D, csc_ptr, csc_rows, csc_vals, (S_ + 63) / 64,
+                           32, 16, 64, 0, variant, dt, scale, 0, norm, ws, 64 * MB, nullptr);
+    };
+    for (int S_ : {63, 64})
+        for (int norm : {0, 1}) {
+            char label[64];
+            snprintf(label, sizeof(label), "sel_scores_rows/S%d_norm%d", S_, norm);
+            run(label, [&] { return scores(S_, norm, 0, 0.f); });
+        }
+    for (float scale : {0.f, -1.f, 0.25f}) {
+        char label[64];
+        snprintf(label, sizeof(label), "sel_scores_rows/generic_scale_%g", scale);
+        peek<PcmpHead>(0);
+        run(label, [&] { return scores(64, 0, 1, scale); }, peeked_scale<PcmpHead>);
+        snprintf(label, sizeof(label), "pcmp_all/scale_%g", scale);
+        peek<PcmpHead>(0);
+        run(label, [&] { return NSA_FN(nsa_pcmp_all)(Q, Kc, p_grp, B, 64, G, h, D, 3, (int64_t)G * 3 * D, 3 * D, D, dt, scale, nullptr); }, peeked_scale<PcmpHead>);
+    }
+
+    // ---- the layer calls on real pointers (the m7c layer, capacity 1024)
+    nsa_layer_desc L{};
+    L.dim = 768; L.G = 2; L.h = 6; L.Dk = 64; L.Dv = 64; L.l = 32; L.d = 16; L.l_sel = 64; L.n_sel = 16; L.w = 512; L.gate_hidden = 32; L.dtype = dt;
+    L.rope_base = 10000.f; L.rope_scale = 1.f; L.gate_tau = 1.f;
+    L.W_qkv = dev(4 * MB); L.W_out = dev(4 * MB); L.gate_w1 = dev(MB); L.gate_b1 = dev(MB); L.gate_w2 = dev(MB); L.gate_b2 = dev(MB);
+    nsa_kv_desc kv{};
+    kv.K_sel = dev(MB); kv.V_sel = dev(MB); kv.K_win = dev(MB); kv.V_win = dev(MB); kv.K_raw = dev(MB); kv.V_raw = dev(MB);
+    void *Kcmp = dev(MB);
+    kv.K_cmp = Kcmp; kv.V_cmp = dev(MB);
+    kv.B = 1; kv.S_max = 1024; kv.n_cmp_max = 63;
+    void *proj = dev(4 * MB), *O_mix = dev(MB), *x = dev(MB), *y = dev(MB);
+    const int S_sel_max = 16;
+    auto prefill_fn = NSA_FN(nsa_layer_prefill);
+    auto extend_fn = NSA_FN(nsa_layer_extend);
+    auto decode_fn = NSA_FN(nsa_layer_decode_step);
+    auto width = NSA_FN(nsa_batched_ranges_width);
+    auto prefill = [&](int S_, size_t ws_bytes = 64 * MB, int selector = NSA_SEL_BATCHED) {
+        return prefill_fn(&L, &kv, proj, S_, selector, csc_ptr, csc_rows, csc_vals, S_sel_max, ranges, selector == NSA_SEL_BATCHED ? width(S_, S_sel_max, 64, 16, 1, 2) : 16, O_mix, nullptr,
+                          ws, ws_bytes, nullptr);
+    };
+    auto extend = [&](int t0, int S_, size_t ws_bytes = 64 * MB) {
+        return extend_fn(&L, &kv, proj, t0, S_, csc_ptr, csc_rows, csc_vals, S_sel_max, ranges, O_mix, nullptr, ws, ws_bytes, nullptr);
+    };
+    auto decode = [&](int t, size_t ws_bytes = 64 * MB) {
+        return decode_fn(&L, &kv, x, y, t, csc_ptr, csc_rows, csc_vals, S_sel_max, nullptr, nullptr, ws, ws_bytes, nullptr);
+    };
+    const size_t need_p = NSA_FN(nsa_layer_prefill_workspace)(&L, 1, 100, S_sel_max);
+    const size_t need_e = NSA_FN(nsa_layer_extend_workspace)(&L, 1, 100, 924, S_sel_max);
+    const size_t need_d = NSA_FN(nsa_layer_decode_step_workspace)(&L, 1, 1024);
+    run("layer_prefill/S100_sequential", [&] { return prefill(100, 64 * MB, NSA_SEL_SEQUENTIAL); });
+    run("layer_prefill/S16_no_compressed_token", [&] { return prefill(16); });
+    run("layer_prefill/workspace_exact", [&] { return prefill(100, need_p); });
+    run("layer_prefill/workspace_one_byte_short", [&] { return prefill(100, need_p - 1); });
+    run("layer_extend/t100_S28", [&] { return extend(100, 28); });
+    run("layer_extend/t100_S64", [&] { return extend(100, 64); });
+    run("layer_extend/to_capacity", [&] { return extend(924, 100); });
+    run("layer_extend/to_capacity_workspace_exact", [&] { return extend(924, 100, need_e); });
+    run("layer_extend/workspace_one_byte_short", [&] { return extend(924, 100, need_e - 1); });
+    run("layer_extend/past_capacity", [&] { return extend(925, 100); });
+    // prefill alone decides on SEL_FUSE and on the alignment of K_cmp (S = 512: 1024 rows, the shape on which the choice shows)
+    for (int fuse : {0, 1})
+        for (int shift : {0, 8})
+            for (int S_ : {100, 512}) {
+                set_tuning("SEL_FUSE", fuse);
+                kv.K_cmp = off(Kcmp, shift);
+                const std::string at = "S" + std::to_string(S_) + (fuse ? "_SEL_FUSE" : "") + (shift ? "_K_cmp_8_bytes_off" : "");
+                run(("layer_prefill/" + at).c_str(), [&] { return prefill(S_); });
+                run(("layer_extend/t0_" + at).c_str(), [&] { return extend(0, S_); });
+            }
+    set_tuning("SEL_FUSE", 0);
+    kv.K_cmp = Kcmp;
+    run("layer_decode_step/t100", [&] { return decode(100); });
+    run("layer_decode_step/t31_first_compressed_token", [&] { return decode(31); });
+    run("layer_decode_step/t5_no_compressed_token", [&] { return decode(5); });
+    run("layer_decode_step/workspace_exact", [&] { return decode(100, need_d); });
+    run("layer_decode_step/workspace_one_byte_short", [&] { return decode(100, need_d - 1); });
+    run("layer_decode_step/position_at_capacity", [&] { return decode(1024); });
+    L.Dk = L.Dv = 128;
+    run("layer_decode_step/D128_t100", [&] { return decode(100); });
+    run("layer_prefill/D128_S100", [&] { return prefill(100); });
+    printf("\n}\n");
+    return 0;
+}

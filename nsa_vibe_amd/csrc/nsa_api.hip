@@ -8,12 +8,10 @@
 #include <strings.h>
 
 #include <atomic>
-#include <cmath>
 #include <mutex>
 #include <vector>
 
-#include "nsa_common.hpp"
-#include "sel_attn_params.hpp"
+#include "nsa_host.hpp"
 #include "nsa_internal.hpp"
 #include "sel_select_row.hpp"
 
@@ -34,17 +32,15 @@ int hip_fail(hipError_t e, const char *what) {
 }
 
 // ---- tuning switches -------------------------------------------------------------------------
-static const char *const g_tune_names[TUNE_COUNT] = {"SEL_ROWS", "ATTN_MAP", "ATTN_STAGE", "BAND_STAGE", "DECODE_UNFUSED", "SEL_BLOCKS", "DECODE_WG", "SEL_ROWSUM", "DECODE_STENCIL", "SEL_FUSE", "SCORES_FORM", "SEL_FLAT", "SEL_KSPLIT", "DECODE_STOP", "DECODE_WAVES", "DECODE_SPLIT", "DECODE_STEP", "DECODE_TEAM_SPIN", "DECODE_WIDE", "SEL_KSPLIT_T1", "SEL_KSPLIT_T2", "SCORES_SELECT", "DECODE_BAND"};
-static const int g_tune_defaults[TUNE_COUNT] = {-1, -1, 1, 1, -1, -1, -1, 1, 1, 0, -1, -1, -1, 0, -1, -1, 1, -1, -1, -1, -1, -1, -1};
 static std::atomic<int> g_tune[TUNE_COUNT];
 static std::once_flag g_tune_once;
 
 static void tune_init() {
     for (int i = 0; i < TUNE_COUNT; ++i) {
         char name[64];
-        snprintf(name, sizeof(name), "NSA_HIP_%s", g_tune_names[i]);
+        snprintf(name, sizeof(name), "NSA_HIP_%s", TUNE_TABLE[i].name);
         const char *e = getenv(name);
-        int v = e ? atoi(e) : g_tune_defaults[i];
+        int v = e ? atoi(e) : TUNE_TABLE[i].def;
 #ifndef NSA_DEC_TS
         if (i == TUNE_DECODE_STOP) v = 0;  // TIMELINE build only (see nsa_hip_set_tuning)
 #endif
@@ -61,37 +57,9 @@ static int tune_index(const char *name) {
     if (!name) return -1;
     if (strncmp(name, "NSA_HIP_", 8) == 0) name += 8;
     for (int i = 0; i < TUNE_COUNT; ++i)
-        if (strcasecmp(name, g_tune_names[i]) == 0) return i;
+        if (strcasecmp(name, TUNE_TABLE[i].name) == 0) return i;
     return -1;
 }
-
-// implemented in the kernel translation units
-int launch_select_topn(const float *, int64_t, int, int, int, const int32_t *, int, int, int, int, int, int, int,
-                       int32_t *, int, hipStream_t);
-int launch_indices_to_ranges(const int32_t *, int64_t, int, int, int, int, int, int, int32_t *, hipStream_t);
-int batched_width(int, int, int, int, int, int);
-int launch_map_pcmp(const float *, int64_t, int, int, const int32_t *, const int32_t *, const float *, int, float *,
-                    float *, hipStream_t);
-int launch_pcmp(const void *, const void *, float *, int64_t, int64_t, int, int, int, int, int, int64_t, int64_t,
-                int64_t, int, float, hipStream_t, int q0 = 0, int norm = 0, int l = 1, int d = 1);
-size_t scores_workspace(int64_t, int, int);
-int launch_sel_scores(const void *, const void *, float *, int, int, int, int, int, int, int64_t, int64_t, int64_t,
-                      const int32_t *, const int32_t *, const float *, int, int, float, void *, size_t, hipStream_t, int q0 = 0, int norm = 0,
-                      int l = 1, int d = 1);
-
-constexpr int64_t DECODE_MAX_ROWS = 1024;  // rows (B*S*G) up to which the decode-shaped scorer is used
-size_t decode_scores_workspace(int64_t, int, int);
-int launch_decode_scores(const void *, const void *, float *, int, int, int, int, int, int, int64_t, int64_t, int64_t,
-                         const int32_t *, const int32_t *, const float *, int, int, float, void *, size_t, hipStream_t, int q0 = 0,
-                         int norm = 0, int l = 1, int d = 1);
-bool scores_mfma_supported(int, int, int, int, int, int);
-int launch_sel_scores_mfma(const void *, const void *, float *, int, int, int, int, int, int, int64_t, int64_t, int64_t, int,
-                           int, int, float, int, hipStream_t, const SelectParams *, int *, int q0 = 0, int norm = 0, int l = 1);
-
-int launch_sel_first_key(const void *, const int32_t *, void *, int64_t, int, int, int, int, int, int, int64_t, int64_t, int64_t, int,
-                         hipStream_t);
-
-static bool dtype_ok(int dt) { return dt == NSA_DT_F32 || dt == NSA_DT_BF16 || dt == NSA_DT_F16; }
 
 }  // namespace nsa
 
@@ -169,24 +137,14 @@ int nsa::sel_attn_fwd_impl(const void *Q, const void *K, const void *V, const in
     NSA_CHECK_ARG(Q && O && ranges || n_ranges == 0, "sel_attn_fwd: null pointer");
     NSA_CHECK_ARG((K && V) || S_kv == 0, "sel_attn_fwd: null K/V");
     hipStream_t st = (hipStream_t)stream;
-    const size_t esz = dtype == NSA_DT_F32 ? 4 : 2;
-    if (S_kv == 0 || n_ranges == 0) {  // attention_kernels.py:718-719
-        NSA_HIP_TRY(hipMemsetAsync(O, 0, (size_t)R * h * Dv * esz, st));
-        if (lse) {
-            std::vector<float> neg;  // lse = -inf: fill with the bit pattern 0xff800000
-            NSA_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)lse, (int)0xff800000, (size_t)R * h, st));
-        }
+    if (S_kv == 0 || n_ranges == 0) {
+        if (int rc = zero_rows(O, R, h, Dv, dtype, st)) return rc;
+        if (lse) NSA_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)lse, (int)0xff800000, (size_t)R * h, st));  // lse = -inf (its bit pattern)
         return NSA_OK;
     }
-    SelAttnParams P{};
-    P.Q = Q; P.K = K; P.V = V; P.ranges = ranges; P.O = O; P.lse = lse; P.R = R;
-    P.S = S; P.G = G; P.h = h; P.Dk = Dk; P.Dv = Dv; P.S_kv = S_kv; P.n = n_ranges;
-    P.ksb = ksb; P.ksg = ksg; P.kss = kss; P.vsb = vsb; P.vsg = vsg; P.vss = vss;
-    P.scale = scale > 0.f ? scale : 1.0f / sqrtf((float)Dk);
-    P.part = nullptr; P.nsplit = 1;
-    const bool fast_ok = sel_attn_mfma_supported(dtype, h, Dk, Dv) && kss % 8 == 0 && vss % 8 == 0 && ksb % 8 == 0 &&
-                         vsb % 8 == 0 && ksg % 8 == 0 && vsg % 8 == 0 && ((uintptr_t)Q % 16 == 0) &&
-                         ((uintptr_t)K % 16 == 0) && ((uintptr_t)V % 16 == 0);
+    SelAttnParams P = sel_attn_params(Q, K, V, ranges, O, lse, R, S, G, h, Dk, Dv, S_kv, n_ranges, ksb, ksg, kss, vsb, vsg, vss, scale);
+    P.nsplit = 1;
+    const bool fast_ok = sel_attn_mfma_supported(dtype, h, Dk, Dv) && qkv_aligned(Q, K, V, ksb, ksg, kss, vsb, vsg, vss);
     if (variant == 2) NSA_CHECK_ARG(fast_ok, "sel_attn_fwd: MFMA variant requested but shape/dtype/alignment unsupported");
     NSA_CHECK_ARG(variant >= 0 && variant <= 2, "sel_attn_fwd: unknown variant %d", variant);
     if (variant == 0 && S == 1 && !lse && sel_attn_decode_wg_supported(dtype, h, Dk, Dv, n_ranges, ksb, ksg, kss, vsb, vsg, vss, Q, K, V) &&
@@ -228,12 +186,8 @@ int nsa_sel_attn_first_key_parity(const void *V, const int32_t *ranges, void *O,
     const int64_t R = (int64_t)B * S * G;
     if (R == 0) return NSA_OK;
     NSA_CHECK_ARG(O && (ranges || n_ranges == 0) && (V || S_kv == 0), "sel_attn_first_key_parity: null pointer");
-    const int esz = dtype == NSA_DT_F32 ? 4 : 2;
-    if (S_kv == 0 || n_ranges == 0) {
-        NSA_HIP_TRY(hipMemsetAsync(O, 0, (size_t)R * h * Dv * esz, (hipStream_t)stream));
-        return NSA_OK;
-    }
-    return launch_sel_first_key(V, ranges, O, R, S, G, h, Dv, n_ranges, S_kv, vsb, vsg, vss, esz, (hipStream_t)stream);
+    if (S_kv == 0 || n_ranges == 0) return zero_rows(O, R, h, Dv, dtype, (hipStream_t)stream);
+    return launch_sel_first_key(V, ranges, O, R, S, G, h, Dv, n_ranges, S_kv, vsb, vsg, vss, (int)esize(dtype), (hipStream_t)stream);
 }
 
 int nsa_sel_attn_head_causal_parity(const void *Q, const void *K, const void *V, const int32_t *ranges, void *O, int B, int S, int G, int h,
@@ -246,16 +200,8 @@ int nsa_sel_attn_head_causal_parity(const void *Q, const void *K, const void *V,
     const int64_t R = (int64_t)B * S * G;
     if (R == 0) return NSA_OK;
     NSA_CHECK_ARG(Q && O && (ranges || n_ranges == 0) && ((K && V) || S_kv == 0), "sel_attn_head_causal_parity: null pointer");
-    const int esz = dtype == NSA_DT_F32 ? 4 : 2;
-    if (S_kv == 0 || n_ranges == 0) {
-        NSA_HIP_TRY(hipMemsetAsync(O, 0, (size_t)R * h * Dv * esz, (hipStream_t)stream));
-        return NSA_OK;
-    }
-    SelAttnParams P{};
-    P.Q = Q, P.K = K, P.V = V, P.ranges = ranges, P.O = O, P.lse = nullptr;
-    P.R = R, P.S = S, P.G = G, P.h = h, P.Dk = Dk, P.Dv = Dv, P.S_kv = S_kv, P.n = n_ranges;
-    P.ksb = ksb, P.ksg = ksg, P.kss = kss, P.vsb = vsb, P.vsg = vsg, P.vss = vss;
-    P.scale = scale > 0.f ? scale : 1.0f / sqrtf((float)Dk);
+    if (S_kv == 0 || n_ranges == 0) return zero_rows(O, R, h, Dv, dtype, (hipStream_t)stream);
+    const SelAttnParams P = sel_attn_params(Q, K, V, ranges, O, nullptr, R, S, G, h, Dk, Dv, S_kv, n_ranges, ksb, ksg, kss, vsb, vsg, vss, scale);
     return launch_sel_head_causal(P, dtype, (hipStream_t)stream);
 }
 
@@ -277,11 +223,9 @@ int nsa_sel_attn_bwd(const void *Q, const void *K, const void *V, const int32_t 
     NSA_CHECK_ARG(variant >= 0 && variant <= 2, "sel_attn_bwd: unknown variant %d", variant);
     hipStream_t st = (hipStream_t)stream;
     const int64_t R = (int64_t)B * S * G;
-    const size_t esz = dtype == NSA_DT_F32 ? 4 : 2;
     const bool empty = R == 0 || S_kv == 0 || n_ranges == 0;
-    const bool fast_ok = !empty && sel_attn_bwd_mfma_supported(dtype, h, Dk, Dv) && kss % 8 == 0 && vss % 8 == 0 && ksb % 8 == 0 &&
-                         vsb % 8 == 0 && ksg % 8 == 0 && vsg % 8 == 0 && ((uintptr_t)Q % 16 == 0) && ((uintptr_t)K % 16 == 0) &&
-                         ((uintptr_t)V % 16 == 0) && ((uintptr_t)dO % 16 == 0) && ((uintptr_t)O % 16 == 0) && (int64_t)B * G <= 65535 &&
+    const bool fast_ok = !empty && sel_attn_bwd_mfma_supported(dtype, h, Dk, Dv) && qkv_aligned(Q, K, V, ksb, ksg, kss, vsb, vsg, vss) &&
+                         ((uintptr_t)dO % 16 == 0) && ((uintptr_t)O % 16 == 0) && (int64_t)B * G <= 65535 &&
                          workspace && workspace_bytes >= sel_attn_bwd_mfma_workspace(R, h, S, (int64_t)B * G, S_kv, Dk) && ((uintptr_t)workspace % 16 == 0);
     if (variant == 2) NSA_CHECK_ARG(fast_ok, "sel_attn_bwd: MFMA variant requested but shape/dtype/alignment/workspace unsupported");
     const bool fast = fast_ok && variant != 1;
@@ -291,15 +235,13 @@ int nsa_sel_attn_bwd(const void *Q, const void *K, const void *V, const int32_t 
     }
     if (R == 0) return NSA_OK;
     if (S_kv == 0 || n_ranges == 0) {
+        const size_t esz = esize(dtype);
         NSA_HIP_TRY(hipMemsetAsync(dQ, 0, (size_t)R * h * Dk * esz, st));
         return NSA_OK;
     }
     NSA_CHECK_ARG(Q && K && V && ranges && O && lse && dO && dQ && dK && dV, "sel_attn_bwd: null pointer");
-    SelAttnBwdParams P{};
-    P.Q = Q; P.K = K; P.V = V; P.ranges = ranges; P.O = O; P.lse = lse; P.dO = dO; P.dQ = dQ; P.dK = dK; P.dV = dV;
-    P.R = R; P.S = S; P.G = G; P.h = h; P.Dk = Dk; P.Dv = Dv; P.S_kv = S_kv; P.n = n_ranges;
-    P.ksb = ksb; P.ksg = ksg; P.kss = kss; P.vsb = vsb; P.vsg = vsg; P.vss = vss;
-    P.scale = scale > 0.f ? scale : 1.0f / sqrtf((float)Dk);
+    const SelAttnBwdParams P =
+        sel_attn_bwd_params(Q, K, V, ranges, O, lse, dO, dQ, dK, dV, R, S, G, h, Dk, Dv, S_kv, n_ranges, ksb, ksg, kss, vsb, vsg, vss, scale);
     if (fast) return launch_sel_attn_bwd_mfma(P, dtype, (float *)workspace, st);
     return launch_sel_attn_bwd_generic(P, dtype, st);
 }
@@ -325,15 +267,9 @@ int nsa::band_attn_fwd_impl(const void *Q, const void *K, const void *V, void *O
     if (R == 0) return NSA_OK;
     // S_kv == 0 or w == 0: every interval is empty; the generic kernel writes the zeros / -inf rows
     NSA_CHECK_ARG(Q && O && ((K && V) || S_kv == 0), "band_attn_fwd: null pointer");
-    BandAttnParams P{};
-    P.Q = Q; P.K = K; P.V = V; P.O = O; P.lse = lse;
-    P.B = B; P.S = S; P.G = G; P.h = h; P.Dk = Dk; P.Dv = Dv; P.S_kv = S_kv;
-    P.ksb = ksb; P.ksg = ksg; P.kss = kss; P.vsb = vsb; P.vsg = vsg; P.vss = vss;
-    P.scale = scale > 0.f ? scale : 1.0f / sqrtf((float)Dk);
-    P.t0 = t0; P.a = a; P.dd = dd; P.c = c; P.w = w;
-    const bool fast_ok = S_kv > 0 && w > 0 && band_attn_mfma_supported(dtype, h, Dk, Dv) && kss % 8 == 0 && vss % 8 == 0 && ksb % 8 == 0 &&
-                         vsb % 8 == 0 && ksg % 8 == 0 && vsg % 8 == 0 && ((uintptr_t)Q % 16 == 0) && ((uintptr_t)K % 16 == 0) &&
-                         ((uintptr_t)V % 16 == 0) && ((uintptr_t)O % 8 == 0) && (int64_t)S_kv * kss * 2 < ((int64_t)1 << 31) &&
+    BandAttnParams P = band_attn_params(Q, K, V, O, lse, B, S, G, h, Dk, Dv, S_kv, ksb, ksg, kss, vsb, vsg, vss, t0, a, dd, c, w, scale);
+    const bool fast_ok = S_kv > 0 && w > 0 && band_attn_mfma_supported(dtype, h, Dk, Dv) && qkv_aligned(Q, K, V, ksb, ksg, kss, vsb, vsg, vss) &&
+                         ((uintptr_t)O % 8 == 0) && (int64_t)S_kv * kss * 2 < ((int64_t)1 << 31) &&
                          (int64_t)S_kv * vss * 2 < ((int64_t)1 << 31);
     if (variant == 2) NSA_CHECK_ARG(fast_ok, "band_attn_fwd: MFMA variant requested but shape/dtype/alignment unsupported");
     if (fast_ok && variant != 1) {
@@ -383,14 +319,11 @@ int nsa_band_attn_bwd(const void *Q, const void *K, const void *V, const void *O
     if (R == 0) return NSA_OK;
     hipStream_t st = (hipStream_t)stream;
     const size_t roff = band_bwd_ranges_off(B, S, G, h, Dk, Dv, S_kv, dtype, variant);
-    NSA_CHECK_ARG(workspace && ((uintptr_t)workspace % 256 == 0) && workspace_bytes >= roff + sizeof(int32_t) * 2 * (size_t)R,
-                  "band_attn_bwd: workspace missing, misaligned or too small");
+    if (int rc = check_workspace("band_attn_bwd", workspace, workspace_bytes, roff + sizeof(int32_t) * 2 * (size_t)R)) return rc;
     int32_t *ranges = (int32_t *)((unsigned char *)workspace + roff);
     if (int rc = launch_band_ranges(ranges, B, S, G, S_kv, t0, a, dd, c, w, st)) return rc;
     const bool fast_ok = S_kv > 0 && w > 0 && roff > 0 && band_attn_mfma_supported(dtype, h, Dk, Dv) && sel_attn_bwd_mfma_supported(dtype, h, Dk, Dv) &&
-                         kss % 8 == 0 && vss % 8 == 0 && ksb % 8 == 0 && vsb % 8 == 0 && ksg % 8 == 0 && vsg % 8 == 0 &&
-                         ((uintptr_t)Q % 16 == 0) && ((uintptr_t)K % 16 == 0) && ((uintptr_t)V % 16 == 0) && ((uintptr_t)dO % 16 == 0) &&
-                         ((uintptr_t)O % 16 == 0) && (int64_t)B * G <= 65535 && (int64_t)S_kv * kss * 2 < ((int64_t)1 << 31) &&
+                         qkv_aligned(Q, K, V, ksb, ksg, kss, vsb, vsg, vss) && ((uintptr_t)dO % 16 == 0) && ((uintptr_t)O % 16 == 0) && (int64_t)B * G <= 65535 && (int64_t)S_kv * kss * 2 < ((int64_t)1 << 31) &&
                          (int64_t)S_kv * vss * 2 < ((int64_t)1 << 31);
     if (variant == 2) NSA_CHECK_ARG(fast_ok, "band_attn_bwd: MFMA variant requested but shape/dtype/alignment unsupported");
     if (!fast_ok || variant == 1)
@@ -399,18 +332,10 @@ int nsa_band_attn_bwd(const void *Q, const void *K, const void *V, const void *O
     NSA_CHECK_ARG(Q && K && V && O && lse && dO && dQ && dK && dV, "band_attn_bwd: null pointer");
     float *delta = (float *)workspace;
     if (int rc = launch_bwd_delta(O, dO, delta, R * h, Dv, dtype, st)) return rc;
-    BandAttnParams BP{};
-    BP.Q = Q; BP.K = K; BP.V = V;
-    BP.B = B; BP.S = S; BP.G = G; BP.h = h; BP.Dk = Dk; BP.Dv = Dv; BP.S_kv = S_kv;
-    BP.ksb = ksb; BP.ksg = ksg; BP.kss = kss; BP.vsb = vsb; BP.vsg = vsg; BP.vss = vss;
-    BP.scale = scale > 0.f ? scale : 1.0f / sqrtf((float)Dk);
-    BP.t0 = t0; BP.a = a; BP.dd = dd; BP.c = c; BP.w = w;
+    const BandAttnParams BP =
+        band_attn_params(Q, K, V, nullptr, nullptr, B, S, G, h, Dk, Dv, S_kv, ksb, ksg, kss, vsb, vsg, vss, t0, a, dd, c, w, scale);
     if (int rc = launch_band_attn_bwd_dq(BP, dO, lse, delta, dQ, dtype, st)) return rc;
-    SelAttnBwdParams P{};
-    P.Q = Q; P.K = K; P.V = V; P.ranges = ranges; P.O = O; P.lse = lse; P.dO = dO; P.dQ = dQ; P.dK = dK; P.dV = dV;
-    P.R = R; P.S = S; P.G = G; P.h = h; P.Dk = Dk; P.Dv = Dv; P.S_kv = S_kv; P.n = 1;
-    P.ksb = ksb; P.ksg = ksg; P.kss = kss; P.vsb = vsb; P.vsg = vsg; P.vss = vss;
-    P.scale = BP.scale;
+    SelAttnBwdParams P = sel_attn_bwd_params(Q, K, V, ranges, O, lse, dO, dQ, dK, dV, R, S, G, h, Dk, Dv, S_kv, 1, ksb, ksg, kss, vsb, vsg, vss, scale);
     P.skip_delta_dq = 1;
     return launch_sel_attn_bwd_mfma(P, dtype, delta, st);
 }
@@ -419,7 +344,7 @@ int nsa_band_attn_bwd(const void *Q, const void *K, const void *V, const void *O
 int nsa_block_counts(int seq_len, int l, int d, int l_sel, int *S_cmp, int *S_sel, int *nnz) {
     NSA_CHECK_ARG(l > 0 && d > 0 && l_sel > 0, "Block parameters must be positive");
     NSA_CHECK_ARG(l % d == 0 && l_sel % d == 0, "Require d|l and d|l_sel in M0");  // block_index.py:75-77
-    const int sc = seq_len < l ? 0 : (seq_len - l) / d + 1;
+    const int sc = ncmp_of(seq_len, l, d);
     const int ss = seq_len <= 0 ? 0 : (seq_len + l_sel - 1) / l_sel;
     if (S_cmp) *S_cmp = sc;
     if (S_sel) *S_sel = ss;
@@ -503,7 +428,7 @@ int nsa_pcmp_all(const void *Q, const void *K_cmp, float *p_cmp, int B, int S, i
                  int64_t csb, int64_t csg, int64_t css, int dtype, float scale, void *stream) {
     NSA_CHECK_ARG(dtype_ok(dtype), "pcmp_all: unknown dtype %d", dtype);
     NSA_CHECK_ARG(B >= 0 && S >= 0 && G >= 1, "pcmp_all: bad sizes");
-    if (scale <= 0.f) scale = 1.0f / sqrtf((float)Dk);
+    if (scale <= 0.f) scale = default_scale(0.f, Dk);  // (the scorers hand a NaN on, the attention fills replace it)
     return launch_pcmp(Q, K_cmp, p_cmp, 0, (int64_t)B * S * G, S, G, h, Dk, S_cmp, csb, csg, css, dtype, scale,
                        (hipStream_t)stream);
 }
@@ -512,7 +437,7 @@ int nsa_pcmp_all(const void *Q, const void *K_cmp, float *p_cmp, int B, int S, i
 // of an extend): the decode-shaped pair only for chunks of fewer than 64 rows, so that chunks whose boundaries are multiples of 64 all take
 // the same (prefill) route and a row's scores do not depend on the chunk it sits in
 static int scores_route(int B, int S, int G, int h, int Dk, int S_cmp, int S_sel, int l, int d, int l_sel, int dtype, int variant,
-                        int norm = 0) {
+                        int norm) {
     const int64_t R = (int64_t)B * S * G;
     if (variant != 0) return variant;
     const bool mfma = scores_mfma_supported(dtype, h, Dk, l, d, l_sel) && S_cmp >= 1 && R > 0 && S_sel > 0 && (int64_t)B * G <= 65535;
@@ -545,7 +470,7 @@ int nsa_sel_scores_rows(const void *Q, const void *K_cmp, float *p_grp, int B, i
     NSA_CHECK_ARG(variant >= 0 && variant <= 3, "sel_scores: unknown variant %d", variant);
     NSA_CHECK_ARG(q0 >= 0 && (norm == 0 || norm == 1), "sel_scores: bad q0 / norm");
     NSA_CHECK_ARG(norm == 0 || (l >= 1 && d >= 1), "sel_scores: norm = 1 needs the block geometry l, d");
-    if (scale <= 0.f) scale = 1.0f / sqrtf((float)Dk);
+    if (scale <= 0.f) scale = default_scale(0.f, Dk);  // (the scorers hand a NaN on, the attention fills replace it)
     const int route = scores_route(B, S, G, h, Dk, S_cmp, S_sel, l, d, l_sel, dtype, variant, norm);
     if (route == 3 && S_cmp >= 1 && (int64_t)B * S * G > 0 && S_sel > 0)
         return launch_decode_scores(Q, K_cmp, p_grp, B, S, G, h, Dk, S_cmp, csb, csg, css, csc_ptr, csc_rows, csc_vals, S_sel, dtype,
@@ -584,7 +509,7 @@ int nsa_sel_scores_select_rows(const void *Q, const void *K_cmp, float *p_grp, i
     const int64_t R = (int64_t)B * S * G;
     if (R == 0 || out_width == 0) return NSA_OK;
     NSA_CHECK_ARG(p_grp && ranges_out, "sel_scores_select: null pointer");
-    if (scale <= 0.f) scale = 1.0f / sqrtf((float)Dk);
+    if (scale <= 0.f) scale = default_scale(0.f, Dk);  // (the scorers hand a NaN on, the attention fills replace it)
     const int route = scores_route(B, S, G, h, Dk, S_cmp, S_sel, l, d, l_sel, dtype, 0, norm);
     const bool mfma_ok = route == 2 && S_cmp >= 1 && S_sel > 0 && csb % 8 == 0 && csg % 8 == 0 && css % 8 == 0 && ((uintptr_t)Q % 16 == 0) &&
                          ((uintptr_t)K_cmp % 16 == 0) && (int64_t)B * G <= 65535;
@@ -639,9 +564,7 @@ int nsa_sel_select_attn_fwd(const float *p_grp, int t0, const int32_t *t_rows, i
     if (R == 0) return NSA_OK;
     NSA_CHECK_ARG(p_grp && ranges_out, "sel_select_attn_fwd: null pointer");
     int ns = 1;
-    const bool fast_ok = sel_attn_mfma_supported(dtype, h, Dk, Dv) && kss % 8 == 0 && vss % 8 == 0 && ksb % 8 == 0 && vsb % 8 == 0 &&
-                         ksg % 8 == 0 && vsg % 8 == 0 && ((uintptr_t)Q % 16 == 0) && ((uintptr_t)K % 16 == 0) && ((uintptr_t)V % 16 == 0) &&
-                         S_kv > 0 && out_width >= 1 && out_width <= 64 && S_sel >= 1 && S_sel <= 1024 &&
+    const bool fast_ok = sel_attn_mfma_supported(dtype, h, Dk, Dv) && qkv_aligned(Q, K, V, ksb, ksg, kss, vsb, vsg, vss) && S_kv > 0 && out_width >= 1 && out_width <= 64 && S_sel >= 1 && S_sel <= 1024 &&
                          (sel_attn_mfma_workspace(R, h, Dv, &ns), ns == 1);
     // One launch (the selector inside the attention kernel) or two.  The fused selector runs 8 rows one after the other in a wave of a
     // kernel held to 2 waves per SIMD by its 253 VGPRs: its scalar chains run at latency and it adds 36 / 120 / 424 us at 4k x 8 / 16k x 2 /
@@ -661,12 +584,8 @@ int nsa_sel_select_attn_fwd(const float *p_grp, int t0, const int32_t *t_rows, i
     SelectParams SP{};
     SP.p_grp = p_grp; SP.t_rows = t_rows; SP.out = ranges_out; SP.R = R; SP.S = S; SP.G = G; SP.t0 = t0;
     if (int rc = select_params_fill(&SP, S_sel, l_sel, n_top, force_init, force_local, mode, S_total, out_width)) return rc;
-    SelAttnParams P{};
-    P.Q = Q; P.K = K; P.V = V; P.ranges = ranges_out; P.O = O; P.lse = lse; P.R = R;
-    P.S = S; P.G = G; P.h = h; P.Dk = Dk; P.Dv = Dv; P.S_kv = S_kv; P.n = out_width;
-    P.ksb = ksb; P.ksg = ksg; P.kss = kss; P.vsb = vsb; P.vsg = vsg; P.vss = vss;
-    P.scale = scale > 0.f ? scale : 1.0f / sqrtf((float)Dk);
-    P.part = nullptr; P.nsplit = 1;
+    SelAttnParams P = sel_attn_params(Q, K, V, ranges_out, O, lse, R, S, G, h, Dk, Dv, S_kv, out_width, ksb, ksg, kss, vsb, vsg, vss, scale);
+    P.nsplit = 1;
     P.fuse_select = 1;
     P.select = &SP;
     return launch_sel_attn_fwd_mfma(P, dtype, (hipStream_t)stream);
@@ -675,11 +594,18 @@ int nsa_sel_select_attn_fwd(const float *p_grp, int t0, const int32_t *t_rows, i
 // ------------------------------------------------------------------------------ fused decode step
 static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
+// decode-step workspace: scorer scratch (a bytes) | p_grp (p bytes) | attention scratch (c bytes), each a multiple of 16 bytes
+struct SelDecodeWs {
+    size_t a, p, c;
+    SelDecodeWs(int B, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int n_top, int dtype)
+        : a(align16(nsa_sel_scores_workspace(B, 1, G, h, Dk, S_cmp, S_sel, 0, 0, 0, dtype, 3))),
+          p(align16(sizeof(float) * (size_t)B * G * (size_t)(S_sel > 0 ? S_sel : 1))),
+          c(align16(nsa_sel_attn_fwd_workspace(B, 1, G, h, Dk, Dv, n_top, dtype))) {}
+    size_t total() const { return a + p + c; }
+};
+
 size_t nsa_sel_decode_step_workspace(int B, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int n_top, int dtype) {
-    const size_t a = align16(nsa_sel_scores_workspace(B, 1, G, h, Dk, S_cmp, S_sel, 0, 0, 0, dtype, 3));
-    const size_t p = align16(sizeof(float) * (size_t)B * G * (size_t)(S_sel > 0 ? S_sel : 1));
-    const size_t c = align16(nsa_sel_attn_fwd_workspace(B, 1, G, h, Dk, Dv, n_top, dtype));
-    return a + p + c;
+    return SelDecodeWs(B, G, h, Dk, Dv, S_cmp, S_sel, n_top, dtype).total();
 }
 
 }  // extern "C"
@@ -691,18 +617,15 @@ int nsa::sel_decode_step_impl(const void *Q, const void *K_cmp, const void *K, c
                               size_t workspace_bytes, void *stream, int defer, int *ns_used, float **part_used, const DecBandPair *band,
                               int *band_taken) {
     if (band_taken) *band_taken = 0;
-    NSA_CHECK_ARG(workspace && ((uintptr_t)workspace % 16 == 0) &&
-                      workspace_bytes >= nsa_sel_decode_step_workspace(B, G, h, Dk, Dv, S_cmp, S_sel, n_top, dtype),
+    const SelDecodeWs W(B, G, h, Dk, Dv, S_cmp, S_sel, n_top, dtype);
+    NSA_CHECK_ARG(workspace && ((uintptr_t)workspace % 16 == 0) && workspace_bytes >= W.total(),
                   "decode_step: workspace missing, misaligned or too small");
     NSA_CHECK_ARG(n_top >= 1 && n_top <= 64, "decode_step: n_top must be in [1,64]");
     unsigned char *w = (unsigned char *)workspace;
-    const size_t a = align16(nsa_sel_scores_workspace(B, 1, G, h, Dk, S_cmp, S_sel, 0, 0, 0, dtype, 3));
-    const size_t p = align16(sizeof(float) * (size_t)B * G * (size_t)(S_sel > 0 ? S_sel : 1));
+    const size_t a = W.a, p = W.p;
     float *p_grp = (float *)(w + a);
     int rc;
-    const float sc = scale > 0.f ? scale : 1.0f / sqrtf((float)Dk);
-    const bool wg_attn = sel_attn_decode_wg_supported(dtype, h, Dk, Dv, n_top, ksb, ksg, kss, vsb, vsg, vss, Q, K, V) && S_kv >= 1 &&
-                         (int64_t)S_kv * 2 * Dv < ((int64_t)1 << 31);
+    const float sc = default_scale(scale, Dk);
     const int stencil = (l == 2 * d && l_sel == 4 * d) ? 1 : 0;  // Eq.9 in closed form (the fused kernel then reads no CSC arrays)
     if (decode_step_supported((int64_t)B * G, dtype, h, Dk, Dv, S_cmp, S_sel, S_kv, l, d, l_sel, n_top, t_token, kcb, kcg, kcs, ksb, ksg, kss, vsb, vsg, vss, Q, K_cmp,
                               K, V)) {  // scores -> statistics -> Eq.9/10 -> sequential top-n -> selection attention: ONE launch, O is final
@@ -711,7 +634,6 @@ int nsa::sel_decode_step_impl(const void *Q, const void *K_cmp, const void *K, c
         return launch_decode_step(Q, K_cmp, K, V, O, ranges_out, B, G, h, S_cmp, S_sel, S_kv, n_top, t_token, kcb, kcg, kcs, ksb, ksg, kss, vsb, vsg,
                                   vss, dtype, sc, w, a, (hipStream_t)stream, band_taken ? band : nullptr, Dk);
     }
-    (void)wg_attn;
     if (decode_score_select_supported(dtype, h, Dk, S_cmp, S_sel, kcb, kcg, kcs, Q, K_cmp, (int64_t)B * G)) {
         // scores -> statistics -> Eq.9/10 -> sequential top-n in one launch (bit-identical to the route below)
         rc = launch_decode_score_select(Q, K_cmp, B, G, h, Dk, S_cmp, kcb, kcg, kcs, csc_ptr, csc_rows, csc_vals, S_sel, l_sel, n_top, t_token,

@@ -60,6 +60,28 @@ enum Tune {
     TUNE_DECODE_BAND,       // NSA_HIP_DECODE_BAND: layer decode step, the sliding + compressed branches: 0 = their own launch; 1 = on the launch of the selected branch's one-launch decode step, splits merged by the finish kernel; 2 = the same with the splits merged by the workgroup that holds them (branch outputs and gates final); 3 / -1 (default) = 2 + with <= 8 rows the gate mix is the A operand of the output projection (three launches per step)
     TUNE_COUNT
 };
+// the switches' names (environment: NSA_HIP_<name>) and defaults, one entry per Tune in the enum's order
+struct TuneEntry {
+    Tune id;
+    const char *name;
+    int def;
+};
+#define NSA_TUNE(NAME, DEF) {TUNE_##NAME, #NAME, DEF}
+constexpr TuneEntry TUNE_TABLE[] = {
+    NSA_TUNE(SEL_ROWS, -1),       NSA_TUNE(ATTN_MAP, -1),      NSA_TUNE(ATTN_STAGE, 1),     NSA_TUNE(BAND_STAGE, 1),
+    NSA_TUNE(DECODE_UNFUSED, -1), NSA_TUNE(SEL_BLOCKS, -1),    NSA_TUNE(DECODE_WG, -1),     NSA_TUNE(SEL_ROWSUM, 1),
+    NSA_TUNE(DECODE_STENCIL, 1),  NSA_TUNE(SEL_FUSE, 0),       NSA_TUNE(SCORES_FORM, -1),   NSA_TUNE(SEL_FLAT, -1),
+    NSA_TUNE(SEL_KSPLIT, -1),     NSA_TUNE(DECODE_STOP, 0),    NSA_TUNE(DECODE_WAVES, -1),  NSA_TUNE(DECODE_SPLIT, -1),
+    NSA_TUNE(DECODE_STEP, 1),     NSA_TUNE(DECODE_TEAM_SPIN, -1), NSA_TUNE(DECODE_WIDE, -1), NSA_TUNE(SEL_KSPLIT_T1, -1),
+    NSA_TUNE(SEL_KSPLIT_T2, -1),  NSA_TUNE(SCORES_SELECT, -1), NSA_TUNE(DECODE_BAND, -1),
+};
+#undef NSA_TUNE
+constexpr bool tune_table_in_order() {
+    for (int i = 0; i < TUNE_COUNT; ++i)
+        if (TUNE_TABLE[i].id != i) return false;
+    return true;
+}
+static_assert(sizeof(TUNE_TABLE) / sizeof(TUNE_TABLE[0]) == TUNE_COUNT && tune_table_in_order(), "TUNE_TABLE: one entry per Tune, in order");
 int tuning(Tune t);
 
 // ---- vector types ----------------------------------------------------------------------

@@ -1,0 +1,100 @@
+// Host-only helpers of the C ABI's dispatch layer (nsa_api.hip, nsa_layer_api.hip): the predicates, defaults and argument-block fills
+// that every entry point shares.  One of each; a call site keeps its own extra conditions next to the call.
+#pragma once
+#include <climits>
+#include <cmath>
+
+#include "nsa_common.hpp"
+#include "layer_fused.hpp"
+#include "sel_attn_params.hpp"
+
+namespace nsa {
+
+inline bool dtype_ok(int dt) { return dt == NSA_DT_F32 || dt == NSA_DT_BF16 || dt == NSA_DT_F16; }
+inline size_t esize(int dt) { return dt == NSA_DT_F32 ? 4 : 2; }
+inline float default_scale(float scale, int Dk) { return scale > 0.f ? scale : 1.0f / sqrtf((float)Dk); }
+
+// compressed tokens of a context of S tokens: what its last position S - 1 sees on the emission schedule (ncmp_at), (S - l) / d + 1 from S = l on
+inline int ncmp_of(int S, int l, int d) { return ncmp_at(S - 1, l, d, INT_MAX); }
+
+// "<who>: workspace missing, misaligned or too small" unless `need` bytes at a 256-byte boundary are there
+inline int check_workspace(const char *who, const void *ws, size_t bytes, size_t need) {
+    NSA_CHECK_ARG(ws && ((uintptr_t)ws % 256 == 0) && bytes >= need, "%s: workspace missing, misaligned or too small", who);
+    return NSA_OK;
+}
+
+// what the MFMA attention kernels ask of their operands: every K / V stride a multiple of 8 elements, Q, K and V 16-byte aligned
+inline bool qkv_aligned(const void *Q, const void *K, const void *V, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg,
+                        int64_t vss) {
+    return kss % 8 == 0 && vss % 8 == 0 && ksb % 8 == 0 && vsb % 8 == 0 && ksg % 8 == 0 && vsg % 8 == 0 && ((uintptr_t)Q % 16 == 0) &&
+           ((uintptr_t)K % 16 == 0) && ((uintptr_t)V % 16 == 0);
+}
+
+// O [R,h,Dv] = 0: the output of rows that select nothing (attention_kernels.py:718-719)
+inline int zero_rows(void *O, int64_t R, int h, int Dv, int dtype, hipStream_t st) {
+    const size_t esz = esize(dtype);
+    NSA_HIP_TRY(hipMemsetAsync(O, 0, (size_t)R * h * Dv * esz, st));
+    return NSA_OK;
+}
+
+// element strides of a layer's caches ([B,G,S_max,D] and [B,G,n_cmp_max,D], rows contiguous) and the softmax scale
+struct CacheStrides {
+    int64_t ksb, ksg, vsb, vsg;  // K_sel / K_win / K_raw and their V
+    int64_t kcb, kcg, vcb, vcg;  // K_cmp / V_cmp
+    float scale;
+    CacheStrides(const nsa_layer_desc *L, const nsa_kv_desc *kv)
+        : ksb((int64_t)L->G * kv->S_max * L->Dk), ksg((int64_t)kv->S_max * L->Dk), vsb((int64_t)L->G * kv->S_max * L->Dv),
+          vsg((int64_t)kv->S_max * L->Dv), kcb((int64_t)L->G * kv->n_cmp_max * L->Dk), kcg((int64_t)kv->n_cmp_max * L->Dk),
+          vcb((int64_t)L->G * kv->n_cmp_max * L->Dv), vcg((int64_t)kv->n_cmp_max * L->Dv), scale(1.0f / sqrtf((float)L->Dk)) {}
+};
+
+// RoPE + append of S tokens at position t0 of the caches kv (the backward passes the gradients in the caches' places)
+inline RopeAppendParams rope_append_params(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *proj, void *Q_out, int S, int t0) {
+    RopeAppendParams P{};
+    P.proj = proj;
+    P.Q_out = Q_out;
+    P.cache[0] = kv->K_sel; P.cache[1] = kv->V_sel; P.cache[2] = kv->K_win; P.cache[3] = kv->V_win; P.cache[4] = kv->K_raw; P.cache[5] = kv->V_raw;
+    P.B = kv->B; P.S = S; P.G = L->G; P.h = L->h; P.Dk = L->Dk; P.Dv = L->Dv; P.S_max = kv->S_max; P.t0 = t0;
+    P.rope_base = L->rope_base > 0.f ? L->rope_base : 10000.0f;
+    P.inv_scale = 1.0f / (L->rope_scale > 0.f ? L->rope_scale : 1.0f);
+    return P;
+}
+
+// everything else (split-KV, mapping, fused selector) stays zero: the caller sets what its route needs
+inline SelAttnParams sel_attn_params(const void *Q, const void *K, const void *V, const int32_t *ranges, void *O, float *lse, int64_t R, int S,
+                                     int G, int h, int Dk, int Dv, int S_kv, int n, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb,
+                                     int64_t vsg, int64_t vss, float scale) {
+    SelAttnParams P{};
+    P.Q = Q; P.K = K; P.V = V; P.ranges = ranges; P.O = O; P.lse = lse; P.R = R;
+    P.S = S; P.G = G; P.h = h; P.Dk = Dk; P.Dv = Dv; P.S_kv = S_kv; P.n = n;
+    P.ksb = ksb; P.ksg = ksg; P.kss = kss; P.vsb = vsb; P.vsg = vsg; P.vss = vss;
+    P.scale = default_scale(scale, Dk);
+    return P;
+}
+
+inline SelAttnBwdParams sel_attn_bwd_params(const void *Q, const void *K, const void *V, const int32_t *ranges, const void *O, const float *lse,
+                                            const void *dO, void *dQ, float *dK, float *dV, int64_t R, int S, int G, int h, int Dk, int Dv,
+                                            int S_kv, int n, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg, int64_t vss,
+                                            float scale) {
+    SelAttnBwdParams P{};
+    P.Q = Q; P.K = K; P.V = V; P.ranges = ranges; P.O = O; P.lse = lse; P.dO = dO; P.dQ = dQ; P.dK = dK; P.dV = dV;
+    P.R = R; P.S = S; P.G = G; P.h = h; P.Dk = Dk; P.Dv = Dv; P.S_kv = S_kv; P.n = n;
+    P.ksb = ksb; P.ksg = ksg; P.kss = kss; P.vsb = vsb; P.vsg = vsg; P.vss = vss;
+    P.scale = default_scale(scale, Dk);
+    return P;
+}
+
+// the split-KV fields stay zero (one split, the kernel's own combine)
+inline BandAttnParams band_attn_params(const void *Q, const void *K, const void *V, void *O, float *lse, int B, int S, int G, int h, int Dk,
+                                       int Dv, int S_kv, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg, int64_t vss, int t0,
+                                       int a, int dd, int c, int w, float scale) {
+    BandAttnParams P{};
+    P.Q = Q; P.K = K; P.V = V; P.O = O; P.lse = lse;
+    P.B = B; P.S = S; P.G = G; P.h = h; P.Dk = Dk; P.Dv = Dv; P.S_kv = S_kv;
+    P.ksb = ksb; P.ksg = ksg; P.kss = kss; P.vsb = vsb; P.vsg = vsg; P.vss = vss;
+    P.scale = default_scale(scale, Dk);
+    P.t0 = t0; P.a = a; P.dd = dd; P.c = c; P.w = w;
+    return P;
+}
+
+}  // namespace nsa

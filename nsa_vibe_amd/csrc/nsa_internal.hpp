@@ -45,4 +45,36 @@ bool decode_step_shape_plan(int64_t R, int dtype, int h, int Dk, int Dv, int S_c
 // shape / tuning part of decode_score_select_supported
 bool decode_score_select_shape_ok(int dtype, int h, int Dk, int S_cmp, int S_sel, int64_t rows);
 
+// ---- launchers the C ABI dispatches to; every translation unit that defines one includes this header, so a definition whose return type or
+// default arguments disagree does not compile (a changed parameter list still declares an overload and fails at link time).
+// The default arguments (q0 / norm / l / d: prefill rows, normalised over all S_cmp columns) live here only.
+// sel_select.hip
+int launch_select_topn(const float *p_grp, int64_t R, int S, int G, int t0, const int32_t *t_rows, int S_sel, int l_sel, int n_top,
+                       int force_init, int force_local, int mode, int S_total, int32_t *out, int W, hipStream_t st);
+int launch_indices_to_ranges(const int32_t *idx, int64_t R, int S, int G, int t0, int K, int S_sel, int l_sel, int32_t *out, hipStream_t st);
+int batched_width(int S, int S_sel, int l_sel, int n_top, int force_init, int force_local);
+// sel_scores.hip
+int launch_map_pcmp(const float *p_cmp, int64_t R, int h, int S_cmp_cur, const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals,
+                    int S_sel, float *p_slc, float *p_grp, hipStream_t st);
+int launch_pcmp(const void *Q, const void *Kc, float *p_cmp, int64_t row0, int64_t nrows, int S, int G, int h, int Dk, int S_cmp, int64_t csb,
+                int64_t csg, int64_t css, int dtype, float scale, hipStream_t st, int q0 = 0, int norm = 0, int l = 1, int d = 1);
+size_t scores_workspace(int64_t R, int h, int S_cmp);
+int launch_sel_scores(const void *Q, const void *Kc, float *p_grp, int B, int S, int G, int h, int Dk, int S_cmp, int64_t csb, int64_t csg,
+                      int64_t css, const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel, int dtype, float scale,
+                      void *ws, size_t ws_bytes, hipStream_t st, int q0 = 0, int norm = 0, int l = 1, int d = 1);
+constexpr int64_t DECODE_MAX_ROWS = 1024;  // rows (B*S*G) up to which the decode-shaped scorer is used
+size_t decode_scores_workspace(int64_t R, int h, int S_cmp);
+int launch_decode_scores(const void *Q, const void *Kc, float *p_grp, int B, int S, int G, int h, int Dk, int S_cmp, int64_t csb, int64_t csg,
+                         int64_t css, const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel, int dtype, float scale,
+                         void *ws, size_t ws_bytes, hipStream_t st, int q0 = 0, int norm = 0, int l = 1, int d = 1);
+// sel_scores_mfma.hip
+struct SelectParams;  // sel_select_row.hpp
+bool scores_mfma_supported(int dtype, int h, int Dk, int l, int d, int l_sel);
+int launch_sel_scores_mfma(const void *Q, const void *Kc, float *p_grp, int B, int S, int G, int h, int Dk, int S_cmp, int64_t csb, int64_t csg,
+                           int64_t css, int S_sel, int d_stride, int dtype, float scale, int causal_skip, hipStream_t st, const SelectParams *sel,
+                           int *sel_done, int q0 = 0, int norm = 0, int l = 1);
+// sel_attn_generic.hip
+int launch_sel_first_key(const void *V, const int32_t *ranges, void *O, int64_t R, int S, int G, int h, int Dv, int n, int S_kv, int64_t vsb,
+                         int64_t vsg, int64_t vss, int esz, hipStream_t st);
+
 }  // namespace nsa

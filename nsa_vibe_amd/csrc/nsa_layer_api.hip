@@ -1,20 +1,14 @@
 // C ABI of the layer-level entry points (include/nsa_sel_hip.h, "Layer-level entry points").
-#include <cmath>
-
-#include "nsa_common.hpp"
-#include "layer_fused.hpp"
+#include "nsa_host.hpp"
 #include "nsa_internal.hpp"
-#include "sel_attn_params.hpp"
 
 using namespace nsa;
 
-static bool dt_ok(int dt) { return dt == NSA_DT_F32 || dt == NSA_DT_BF16 || dt == NSA_DT_F16; }
 static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-static size_t esize(int dt) { return dt == NSA_DT_F32 ? 4 : 2; }
 
 static int check_layer(const nsa_layer_desc *L, const char *who) {
     NSA_CHECK_ARG(L, "%s: null layer descriptor", who);
-    NSA_CHECK_ARG(dt_ok(L->dtype), "%s: unknown dtype %d", who, L->dtype);
+    NSA_CHECK_ARG(dtype_ok(L->dtype), "%s: unknown dtype %d", who, L->dtype);
     NSA_CHECK_ARG(L->dim >= 1 && L->G >= 1 && L->h >= 1 && L->Dk >= 2 && L->Dv >= 1 && L->Dk % 2 == 0 && L->Dv % 2 == 0,
                   "%s: bad geometry (Dk, Dv must be even)", who);
     NSA_CHECK_ARG(L->l >= 1 && L->d >= 1 && L->l_sel >= 1 && L->n_sel >= 1 && L->w >= 0, "%s: bad block parameters", who);
@@ -30,7 +24,7 @@ static int check_kv(const nsa_kv_desc *kv, const char *who) {
 extern "C" {
 
 int nsa_linear_small(const void *A, const void *W, void *out, int M, int N, int K, int dtype, int epilogue, const void *residual, void *stream) {
-    NSA_CHECK_ARG(dt_ok(dtype), "linear_small: unknown dtype %d", dtype);
+    NSA_CHECK_ARG(dtype_ok(dtype), "linear_small: unknown dtype %d", dtype);
     NSA_CHECK_ARG(M >= 0 && N >= 0 && K >= 1, "linear_small: bad sizes");
     NSA_CHECK_ARG(epilogue >= 0 && epilogue <= 2 && (epilogue != 2 || residual), "linear_small: bad epilogue");
     if (M == 0 || N == 0) return NSA_OK;
@@ -39,7 +33,7 @@ int nsa_linear_small(const void *A, const void *W, void *out, int M, int N, int 
 }
 
 int nsa_rmsnorm_rows(const void *x, const void *w, void *y, int M, int dim, float eps, int dtype, void *stream) {
-    NSA_CHECK_ARG(dt_ok(dtype), "rmsnorm_rows: unknown dtype %d", dtype);
+    NSA_CHECK_ARG(dtype_ok(dtype), "rmsnorm_rows: unknown dtype %d", dtype);
     NSA_CHECK_ARG(M >= 0 && dim >= 1, "rmsnorm_rows: bad sizes");
     if (M == 0) return NSA_OK;
     NSA_CHECK_ARG(x && w && y, "rmsnorm_rows: null pointer");
@@ -50,7 +44,7 @@ size_t nsa_rmsnorm_rows_bwd_workspace(int M, int dim) { return M > 0 && dim > 0 
 
 int nsa_rmsnorm_rows_bwd(const void *x, const void *w, const void *dy, void *dx, void *dw, int M, int dim, float eps, int dtype,
                          void *workspace, size_t workspace_bytes, void *stream) {
-    NSA_CHECK_ARG(dt_ok(dtype), "rmsnorm_rows_bwd: unknown dtype %d", dtype);
+    NSA_CHECK_ARG(dtype_ok(dtype), "rmsnorm_rows_bwd: unknown dtype %d", dtype);
     NSA_CHECK_ARG(M >= 1 && dim >= 1, "rmsnorm_rows_bwd: bad sizes");
     NSA_CHECK_ARG(x && w && dy && dx && dw, "rmsnorm_rows_bwd: null pointer");
     return launch_rmsnorm_rows_bwd(x, w, dy, dx, dw, M, dim, eps, dtype, workspace, workspace_bytes, (hipStream_t)stream);
@@ -64,14 +58,7 @@ int nsa_rope_cache_append(const nsa_layer_desc *L, const nsa_kv_desc *kv, const 
                   kv->S_max);
     if (S == 0) return NSA_OK;
     NSA_CHECK_ARG(proj && Q_out, "rope_cache_append: null pointer");
-    RopeAppendParams P{};
-    P.proj = proj;
-    P.Q_out = Q_out;
-    P.cache[0] = kv->K_sel; P.cache[1] = kv->V_sel; P.cache[2] = kv->K_win; P.cache[3] = kv->V_win; P.cache[4] = kv->K_raw; P.cache[5] = kv->V_raw;
-    P.B = kv->B; P.S = S; P.G = L->G; P.h = L->h; P.Dk = L->Dk; P.Dv = L->Dv; P.S_max = kv->S_max; P.t0 = t0;
-    P.rope_base = L->rope_base > 0.f ? L->rope_base : 10000.0f;
-    P.inv_scale = 1.0f / (L->rope_scale > 0.f ? L->rope_scale : 1.0f);
-    return launch_rope_cache_append(P, L->dtype, (hipStream_t)stream);
+    return launch_rope_cache_append(rope_append_params(L, kv, proj, Q_out, S, t0), L->dtype, (hipStream_t)stream);
 }
 
 int nsa_cmp_pool_append(const nsa_layer_desc *L, const nsa_kv_desc *kv, int j0, int j1, void *stream) {
@@ -107,15 +94,12 @@ int nsa_rope_cache_append_bwd(const nsa_layer_desc *L, int B, int S, int t0, con
     NSA_CHECK_ARG(B >= 0 && S >= 0 && t0 >= 0, "rope_cache_append_bwd: negative size");
     if (B == 0 || S == 0) return NSA_OK;
     NSA_CHECK_ARG(dQ && dproj, "rope_cache_append_bwd: null pointer");
-    RopeAppendParams P{};
-    P.proj = dproj;              // written
-    P.Q_out = (void *)dQ;        // read
-    P.cache[0] = (void *)dK_sel; P.cache[1] = (void *)dV_sel; P.cache[2] = (void *)dK_win; P.cache[3] = (void *)dV_win;
-    P.cache[4] = (void *)dK_raw; P.cache[5] = (void *)dV_raw;
-    P.B = B; P.S = S; P.G = L->G; P.h = L->h; P.Dk = L->Dk; P.Dv = L->Dv; P.S_max = S; P.t0 = t0;
-    P.rope_base = L->rope_base > 0.f ? L->rope_base : 10000.0f;
-    P.inv_scale = 1.0f / (L->rope_scale > 0.f ? L->rope_scale : 1.0f);
-    return launch_rope_cache_append_bwd(P, L->dtype, (hipStream_t)stream);
+    // the forward's argument block with the gradients in the tensors' places: dproj is written, dQ and the "cache" of capacity S are read
+    nsa_kv_desc g{};
+    g.K_sel = (void *)dK_sel; g.V_sel = (void *)dV_sel; g.K_win = (void *)dK_win; g.V_win = (void *)dV_win;
+    g.K_raw = (void *)dK_raw; g.V_raw = (void *)dV_raw;
+    g.B = B; g.S_max = S;
+    return launch_rope_cache_append_bwd(rope_append_params(L, &g, dproj, (void *)dQ, S, t0), L->dtype, (hipStream_t)stream);
 }
 
 int nsa_cmp_pool_bwd(const nsa_layer_desc *L, int B, int S, int n_cmp, const void *dK_cmp, const void *dV_cmp, void *dK_raw, void *dV_raw,
@@ -144,110 +128,26 @@ int nsa_gate_combine_bwd(const nsa_layer_desc *L, const void *dO, const void *O_
     return launch_gate_combine_bwd(P, dO, gates, dO_cmp, dO_sel, dO_win, dgates, L->dtype, (hipStream_t)stream);
 }
 
-// prefill workspace: Q | p_grp | O_cmp | O_sel | O_win | scorer scratch | attention scratch | band scratch
-struct PrefillWs {
+// workspace of a layer call over S rows at positions t0 .. t0 + S - 1 (prefill: t0 = 0):
+// Q | p_grp | O_cmp | O_sel | O_win | scorer scratch | attention scratch | band scratch (all sized by the S rows; only the attention's
+// key-split records and the scorer's columns grow with the context t0 + S).  norm: the scorer's flag (its route depends on it)
+struct RowsWs {
     size_t q, pgrp, ocmp, osel, owin, sc, att, band, total, sc_bytes, att_bytes, band_bytes;
 };
-static PrefillWs prefill_ws(const nsa_layer_desc *L, int B, int S, int S_sel) {
-    PrefillWs w;
-    const size_t e = esize(L->dtype);
-    const size_t NQ = (size_t)L->G * L->h * L->Dk, NO = (size_t)L->G * L->h * L->Dv;
-    const int n_cmp = S < L->l ? 0 : (S - L->l) / L->d + 1;
-    size_t o = 0;
-    w.q = o; o += up256((size_t)B * S * NQ * e);
-    w.pgrp = o; o += up256(sizeof(float) * (size_t)B * S * L->G * (size_t)(S_sel > 0 ? S_sel : 1));
-    w.ocmp = o; o += up256((size_t)B * S * NO * e);
-    w.osel = o; o += up256((size_t)B * S * NO * e);
-    w.owin = o; o += up256((size_t)B * S * NO * e);
-    w.sc_bytes = nsa_sel_scores_workspace(B, S, L->G, L->h, L->Dk, n_cmp, S_sel, L->l, L->d, L->l_sel, L->dtype, 0);
-    const size_t sc1 = nsa_sel_scores_workspace(B, S, L->G, L->h, L->Dk, n_cmp, S_sel, L->l, L->d, L->l_sel, L->dtype, 1);
-    if (sc1 > w.sc_bytes) w.sc_bytes = sc1;  // the generic route may be taken for unaligned inputs
-    w.sc = o; o += up256(w.sc_bytes);
-    w.att_bytes = nsa_sel_attn_fwd_workspace(B, S, L->G, L->h, L->Dk, L->Dv, L->n_sel, L->dtype);
-    w.att = o; o += up256(w.att_bytes);
-    w.band_bytes = nsa_band_attn_fwd_workspace(B, S, L->G, L->h, L->Dk, L->Dv, L->dtype);
-    w.band = o; o += up256(w.band_bytes);
-    w.total = o;
-    return w;
-}
-
-size_t nsa_layer_prefill_workspace(const nsa_layer_desc *L, int B, int S, int S_sel) {
-    if (!L || !dt_ok(L->dtype) || B < 1 || S < 1) return 0;
-    return prefill_ws(L, B, S, S_sel).total;
-}
-
-int nsa_layer_prefill(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *proj, int S, int selector, const int32_t *csc_ptr,
-                      const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out, int out_width, void *O_mix,
-                      float *gates_out, void *workspace, size_t workspace_bytes, void *stream) {
-    if (int rc = check_layer(L, "layer_prefill")) return rc;
-    if (int rc = check_kv(kv, "layer_prefill")) return rc;
-    NSA_CHECK_ARG(proj && O_mix && ranges_out, "layer_prefill: null pointer");
-    NSA_CHECK_ARG(S >= 1 && S <= kv->S_max, "layer_prefill: %d tokens exceed the cache capacity %d", S, kv->S_max);
-    NSA_CHECK_ARG(S_sel >= 1 && (int64_t)S_sel * L->l_sel >= S, "layer_prefill: block metadata (S_sel=%d) does not cover %d tokens", S_sel, S);
-    NSA_CHECK_ARG(selector == NSA_SEL_BATCHED || selector == NSA_SEL_SEQUENTIAL, "layer_prefill: unknown selector %d", selector);
-    const int B = kv->B, G = L->G, h = L->h, Dk = L->Dk, Dv = L->Dv, dt = L->dtype;
-    const PrefillWs W = prefill_ws(L, B, S, S_sel);
-    NSA_CHECK_ARG(workspace && ((uintptr_t)workspace % 256 == 0) && workspace_bytes >= W.total,
-                  "layer_prefill: workspace missing, misaligned or too small");
-    unsigned char *ws = (unsigned char *)workspace;
-    void *Q = ws + W.q, *Ocmp = ws + W.ocmp, *Osel = ws + W.osel, *Owin = ws + W.owin;
-    float *p_grp = (float *)(ws + W.pgrp);
-    const int n_cmp = S < L->l ? 0 : (S - L->l) / L->d + 1;
-    NSA_CHECK_ARG(n_cmp <= kv->n_cmp_max, "layer_prefill: compressed cache too small");
-    if (int rc = nsa_rope_cache_append(L, kv, proj, Q, S, 0, stream)) return rc;
-    if (int rc = nsa_cmp_pool_append(L, kv, 0, n_cmp, stream)) return rc;
-    const int64_t ksb = (int64_t)G * kv->S_max * Dk, ksg = (int64_t)kv->S_max * Dk;
-    const int64_t vsb = (int64_t)G * kv->S_max * Dv, vsg = (int64_t)kv->S_max * Dv;
-    const int64_t kcb = (int64_t)G * kv->n_cmp_max * Dk, kcg = (int64_t)kv->n_cmp_max * Dk;
-    const int64_t vcb = (int64_t)G * kv->n_cmp_max * Dv, vcg = (int64_t)kv->n_cmp_max * Dv;
-    const float scale = 1.0f / sqrtf((float)Dk);
-    // selected branch: scores (blocks no selector can read at row t are skipped) -> top-n + attention
-    const bool aligned = ((uintptr_t)kv->K_cmp % 16 == 0) && kcb % 8 == 0 && kcg % 8 == 0 && Dk % 8 == 0;
-    if (aligned && n_cmp >= 1 && tuning(TUNE_SEL_FUSE) <= 0) {
-        // scores + top-n in one call (round 4: on the 32x32x16 scorer's route one LAUNCH, the selection in the scorer's epilogue), then the attention
-        if (int rc = nsa_sel_scores_select(Q, kv->K_cmp, p_grp, B, S, G, h, Dk, n_cmp, kcb, kcg, Dk, csc_ptr, csc_rows, csc_vals, S_sel, L->l,
-                                           L->d, L->l_sel, 2 /* skipped blocks stay unwritten: only the selector reads p_grp */, dt, scale, 0,
-                                           L->n_sel, 1, 2, selector, S, ranges_out, out_width, ws + W.sc, W.sc_bytes, stream))
-            return rc;
-        if (int rc = nsa_sel_attn_fwd(Q, kv->K_sel, kv->V_sel, ranges_out, Osel, nullptr, B, S, G, h, Dk, Dv, S, out_width, ksb, ksg, Dk, vsb, vsg,
-                                      Dv, dt, scale, 0, ws + W.att, W.att_bytes, stream))
-            return rc;
-    } else {
-        if (int rc = nsa_sel_scores(Q, kv->K_cmp, p_grp, B, S, G, h, Dk, n_cmp, kcb, kcg, Dk, csc_ptr, csc_rows, csc_vals, S_sel, L->l, L->d,
-                                    L->l_sel, 2 /* skipped blocks stay unwritten: only the selector below reads p_grp */, aligned ? 0 : 1, dt, scale,
-                                    ws + W.sc, W.sc_bytes, stream))
-            return rc;
-        if (int rc = nsa_sel_select_attn_fwd(p_grp, 0, nullptr, S_sel, L->l_sel, L->n_sel, 1, 2, selector, S, ranges_out, out_width, Q, kv->K_sel,
-                                             kv->V_sel, Osel, nullptr, B, S, G, h, Dk, Dv, S, ksb, ksg, Dk, vsb, vsg, Dv, dt, scale, ws + W.att,
-                                             W.att_bytes, stream))
-            return rc;
-    }
-    // sliding and compressed branches
-    if (int rc = nsa_band_attn_fwd(Q, kv->K_win, kv->V_win, Owin, nullptr, B, S, G, h, Dk, Dv, S, ksb, ksg, Dk, vsb, vsg, Dv, 0, 0, 1, 0, L->w,
-                                   dt, scale, 0, ws + W.band, W.band_bytes, stream))
-        return rc;
-    if (int rc = nsa_band_attn_fwd(Q, kv->K_cmp, kv->V_cmp, Ocmp, nullptr, B, S, G, h, Dk, Dv, n_cmp, kcb, kcg, Dk, vcb, vcg, Dv, 0, L->l, L->d,
-                                   1, 1 << 30, dt, scale, 0, ws + W.band, W.band_bytes, stream))
-        return rc;
-    return nsa_gate_combine(L, Q, Ocmp, Osel, Owin, O_mix, gates_out, (int64_t)B * S * G, stream);
-}
-
-// extend workspace: Q | p_grp | O_cmp | O_sel | O_win | scorer scratch | attention scratch | band scratch (all sized by the chunk's S rows;
-// only the attention's key-split records and the scorer's columns grow with the context t0 + S)
-static PrefillWs extend_ws(const nsa_layer_desc *L, int B, int S, int t0, int S_sel) {
-    PrefillWs w;
+static RowsWs rows_ws(const nsa_layer_desc *L, int B, int S, int t0, int S_sel, int norm) {
+    RowsWs w;
     const size_t e = esize(L->dtype);
     const size_t NQ = (size_t)L->G * L->h * L->Dk, NO = (size_t)L->G * L->h * L->Dv;
     const int S_kv = t0 + S;
-    const int n_cmp = S_kv < L->l ? 0 : (S_kv - L->l) / L->d + 1;
+    const int n_cmp = ncmp_of(S_kv, L->l, L->d);
     size_t o = 0;
     w.q = o; o += up256((size_t)B * S * NQ * e);
     w.pgrp = o; o += up256(sizeof(float) * (size_t)B * S * L->G * (size_t)(S_sel > 0 ? S_sel : 1));
     w.ocmp = o; o += up256((size_t)B * S * NO * e);
     w.osel = o; o += up256((size_t)B * S * NO * e);
     w.owin = o; o += up256((size_t)B * S * NO * e);
-    w.sc_bytes = nsa_sel_scores_rows_workspace(B, S, L->G, L->h, L->Dk, n_cmp, S_sel, L->l, L->d, L->l_sel, L->dtype, 0, 1);
-    const size_t sc1 = nsa_sel_scores_rows_workspace(B, S, L->G, L->h, L->Dk, n_cmp, S_sel, L->l, L->d, L->l_sel, L->dtype, 1, 1);
+    w.sc_bytes = nsa_sel_scores_rows_workspace(B, S, L->G, L->h, L->Dk, n_cmp, S_sel, L->l, L->d, L->l_sel, L->dtype, 0, norm);
+    const size_t sc1 = nsa_sel_scores_rows_workspace(B, S, L->G, L->h, L->Dk, n_cmp, S_sel, L->l, L->d, L->l_sel, L->dtype, 1, norm);
     if (sc1 > w.sc_bytes) w.sc_bytes = sc1;  // the generic route may be taken for unaligned inputs
     w.sc = o; o += up256(w.sc_bytes);
     w.att_bytes = nsa_sel_attn_fwd_workspace_kv(B, S, L->G, L->h, L->Dk, L->Dv, S_kv, L->n_sel, L->dtype);
@@ -258,57 +158,94 @@ static PrefillWs extend_ws(const nsa_layer_desc *L, int B, int S, int t0, int S_
     return w;
 }
 
+// The layer over S rows at positions t0 .. t0 + S - 1 of the caches: RoPE + append, pooling, the three branches, gate mix.
+// norm = 0 with t0 = 0 is the prefill (scores normalised over all columns, either selector, out_width ranges per row); norm = 1 is the
+// extend (decode semantics: every row normalises over its own columns and selects sequentially at its token).
+static int layer_rows(const char *who, const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *proj, int t0, int S, int selector, int norm,
+                      const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out, int out_width,
+                      void *O_mix, float *gates_out, void *workspace, size_t workspace_bytes, void *stream) {
+    const bool prefill = norm == 0;
+    if (int rc = check_layer(L, who)) return rc;
+    if (int rc = check_kv(kv, who)) return rc;
+    NSA_CHECK_ARG(proj && O_mix && ranges_out, "%s: null pointer", who);
+    if (prefill)
+        NSA_CHECK_ARG(S >= 1 && S <= kv->S_max, "%s: %d tokens exceed the cache capacity %d", who, S, kv->S_max);
+    else
+        NSA_CHECK_ARG(t0 >= 0 && S >= 1 && (int64_t)t0 + S <= kv->S_max, "%s: tokens [%d,%d) exceed the cache capacity %d", who, t0, t0 + S,
+                      kv->S_max);
+    NSA_CHECK_ARG(S_sel >= 1 && (int64_t)S_sel * L->l_sel >= (int64_t)t0 + S, "%s: block metadata (S_sel=%d) does not cover %d tokens", who,
+                  S_sel, t0 + S);
+    NSA_CHECK_ARG(selector == NSA_SEL_BATCHED || selector == NSA_SEL_SEQUENTIAL, "%s: unknown selector %d", who, selector);
+    const int B = kv->B, G = L->G, h = L->h, Dk = L->Dk, Dv = L->Dv, dt = L->dtype;
+    const int S_kv = t0 + S;
+    const RowsWs W = rows_ws(L, B, S, t0, S_sel, norm);
+    if (int rc = check_workspace(who, workspace, workspace_bytes, W.total)) return rc;
+    unsigned char *ws = (unsigned char *)workspace;
+    void *Q = ws + W.q, *Ocmp = ws + W.ocmp, *Osel = ws + W.osel, *Owin = ws + W.owin;
+    float *p_grp = (float *)(ws + W.pgrp);
+    // compressed tokens emitted before the rows (n_cmp(t0 - 1)) and after them (n_cmp(t0 + S - 1)), on the absolute schedule
+    const int n0 = ncmp_of(t0, L->l, L->d), n1 = ncmp_of(S_kv, L->l, L->d);
+    NSA_CHECK_ARG(n1 <= kv->n_cmp_max, "%s: compressed cache too small", who);
+    if (int rc = nsa_rope_cache_append(L, kv, proj, Q, S, t0, stream)) return rc;
+    if (n1 > n0)
+        if (int rc = nsa_cmp_pool_append(L, kv, n0, n1, stream)) return rc;
+    const CacheStrides C(L, kv);
+    const float scale = C.scale;
+    // selected branch: scores of rows t0 .. t0 + S - 1 (blocks no selector can read at row t are skipped) -> top-n at their tokens -> the
+    // attention over K_sel[:t + 1]
+    const bool aligned = ((uintptr_t)kv->K_cmp % 16 == 0) && C.kcb % 8 == 0 && C.kcg % 8 == 0 && Dk % 8 == 0;
+    if (!prefill || (aligned && n1 >= 1 && tuning(TUNE_SEL_FUSE) <= 0)) {
+        // scores + top-n in one call (on the 32x32x16 scorer's route one LAUNCH, the selection in the scorer's epilogue), then the attention
+        if (int rc = nsa_sel_scores_select_rows(Q, kv->K_cmp, p_grp, B, S, G, h, Dk, n1, C.kcb, C.kcg, Dk, csc_ptr, csc_rows, csc_vals, S_sel,
+                                                L->l, L->d, L->l_sel, 2 /* skipped blocks stay unwritten: only the selector reads p_grp */, dt,
+                                                scale, t0, L->n_sel, 1, 2, selector, S, ranges_out, out_width, t0, norm, ws + W.sc, W.sc_bytes,
+                                                stream))
+            return rc;
+        if (int rc = nsa_sel_attn_fwd(Q, kv->K_sel, kv->V_sel, ranges_out, Osel, nullptr, B, S, G, h, Dk, Dv, S_kv, out_width, C.ksb, C.ksg, Dk,
+                                      C.vsb, C.vsg, Dv, dt, scale, 0, ws + W.att, W.att_bytes, stream))
+            return rc;
+    } else {  // prefill only: the selector inside the attention launch (SEL_FUSE), an unaligned K_cmp, or no compressed token yet
+        if (int rc = nsa_sel_scores(Q, kv->K_cmp, p_grp, B, S, G, h, Dk, n1, C.kcb, C.kcg, Dk, csc_ptr, csc_rows, csc_vals, S_sel, L->l, L->d,
+                                    L->l_sel, 2 /* skipped blocks stay unwritten: only the selector below reads p_grp */, aligned ? 0 : 1, dt, scale,
+                                    ws + W.sc, W.sc_bytes, stream))
+            return rc;
+        if (int rc = nsa_sel_select_attn_fwd(p_grp, 0, nullptr, S_sel, L->l_sel, L->n_sel, 1, 2, selector, S, ranges_out, out_width, Q, kv->K_sel,
+                                             kv->V_sel, Osel, nullptr, B, S, G, h, Dk, Dv, S, C.ksb, C.ksg, Dk, C.vsb, C.vsg, Dv, dt, scale,
+                                             ws + W.att, W.att_bytes, stream))
+            return rc;
+    }
+    // sliding and compressed branches at the rows' absolute positions
+    if (int rc = nsa_band_attn_fwd(Q, kv->K_win, kv->V_win, Owin, nullptr, B, S, G, h, Dk, Dv, S_kv, C.ksb, C.ksg, Dk, C.vsb, C.vsg, Dv, t0, 0, 1, 0,
+                                   L->w, dt, scale, 0, ws + W.band, W.band_bytes, stream))
+        return rc;
+    if (int rc = nsa_band_attn_fwd(Q, kv->K_cmp, kv->V_cmp, Ocmp, nullptr, B, S, G, h, Dk, Dv, n1, C.kcb, C.kcg, Dk, C.vcb, C.vcg, Dv, t0, L->l,
+                                   L->d, 1, 1 << 30, dt, scale, 0, ws + W.band, W.band_bytes, stream))
+        return rc;
+    return nsa_gate_combine(L, Q, Ocmp, Osel, Owin, O_mix, gates_out, (int64_t)B * S * G, stream);
+}
+
+size_t nsa_layer_prefill_workspace(const nsa_layer_desc *L, int B, int S, int S_sel) {
+    if (!L || !dtype_ok(L->dtype) || B < 1 || S < 1) return 0;
+    return rows_ws(L, B, S, 0, S_sel, 0).total;
+}
+
+int nsa_layer_prefill(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *proj, int S, int selector, const int32_t *csc_ptr,
+                      const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out, int out_width, void *O_mix,
+                      float *gates_out, void *workspace, size_t workspace_bytes, void *stream) {
+    return layer_rows("layer_prefill", L, kv, proj, 0, S, selector, 0, csc_ptr, csc_rows, csc_vals, S_sel, ranges_out, out_width, O_mix, gates_out,
+                      workspace, workspace_bytes, stream);
+}
+
 size_t nsa_layer_extend_workspace(const nsa_layer_desc *L, int B, int S, int t0, int S_sel) {
-    if (!L || !dt_ok(L->dtype) || B < 1 || S < 1 || t0 < 0) return 0;
-    return extend_ws(L, B, S, t0, S_sel).total;
+    if (!L || !dtype_ok(L->dtype) || B < 1 || S < 1 || t0 < 0) return 0;
+    return rows_ws(L, B, S, t0, S_sel, 1).total;
 }
 
 int nsa_layer_extend(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *proj, int t0, int S, const int32_t *csc_ptr,
                      const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out, void *O_mix, float *gates_out,
                      void *workspace, size_t workspace_bytes, void *stream) {
-    if (int rc = check_layer(L, "layer_extend")) return rc;
-    if (int rc = check_kv(kv, "layer_extend")) return rc;
-    NSA_CHECK_ARG(proj && O_mix && ranges_out, "layer_extend: null pointer");
-    NSA_CHECK_ARG(t0 >= 0 && S >= 1 && (int64_t)t0 + S <= kv->S_max, "layer_extend: tokens [%d,%d) exceed the cache capacity %d", t0, t0 + S,
-                  kv->S_max);
-    NSA_CHECK_ARG(S_sel >= 1 && (int64_t)S_sel * L->l_sel >= (int64_t)t0 + S, "layer_extend: block metadata (S_sel=%d) does not cover %d tokens",
-                  S_sel, t0 + S);
-    const int B = kv->B, G = L->G, h = L->h, Dk = L->Dk, Dv = L->Dv, dt = L->dtype;
-    const int S_kv = t0 + S;
-    const PrefillWs W = extend_ws(L, B, S, t0, S_sel);
-    NSA_CHECK_ARG(workspace && ((uintptr_t)workspace % 256 == 0) && workspace_bytes >= W.total,
-                  "layer_extend: workspace missing, misaligned or too small");
-    unsigned char *ws = (unsigned char *)workspace;
-    void *Q = ws + W.q, *Ocmp = ws + W.ocmp, *Osel = ws + W.osel, *Owin = ws + W.owin;
-    float *p_grp = (float *)(ws + W.pgrp);
-    // compressed tokens emitted before the chunk (n_cmp(t0 - 1)) and after it (n_cmp(t0 + S - 1)), on the absolute schedule
-    const int n0 = t0 < L->l ? 0 : (t0 - L->l) / L->d + 1;
-    const int n1 = S_kv < L->l ? 0 : (S_kv - L->l) / L->d + 1;
-    NSA_CHECK_ARG(n1 <= kv->n_cmp_max, "layer_extend: compressed cache too small");
-    if (int rc = nsa_rope_cache_append(L, kv, proj, Q, S, t0, stream)) return rc;
-    if (n1 > n0)
-        if (int rc = nsa_cmp_pool_append(L, kv, n0, n1, stream)) return rc;
-    const int64_t ksb = (int64_t)G * kv->S_max * Dk, ksg = (int64_t)kv->S_max * Dk;
-    const int64_t vsb = (int64_t)G * kv->S_max * Dv, vsg = (int64_t)kv->S_max * Dv;
-    const int64_t kcb = (int64_t)G * kv->n_cmp_max * Dk, kcg = (int64_t)kv->n_cmp_max * Dk;
-    const int64_t vcb = (int64_t)G * kv->n_cmp_max * Dv, vcg = (int64_t)kv->n_cmp_max * Dv;
-    const float scale = 1.0f / sqrtf((float)Dk);
-    // selected branch: decode-normalised scores of rows t0 .. t0 + S - 1 + sequential top-n at their tokens, then the attention over K_sel[:t + 1]
-    if (int rc = nsa_sel_scores_select_rows(Q, kv->K_cmp, p_grp, B, S, G, h, Dk, n1, kcb, kcg, Dk, csc_ptr, csc_rows, csc_vals, S_sel, L->l,
-                                            L->d, L->l_sel, 2 /* skipped blocks stay unwritten: only the selector reads p_grp */, dt, scale, t0,
-                                            L->n_sel, 1, 2, NSA_SEL_SEQUENTIAL, S, ranges_out, L->n_sel, t0, 1, ws + W.sc, W.sc_bytes, stream))
-        return rc;
-    if (int rc = nsa_sel_attn_fwd(Q, kv->K_sel, kv->V_sel, ranges_out, Osel, nullptr, B, S, G, h, Dk, Dv, S_kv, L->n_sel, ksb, ksg, Dk, vsb,
-                                  vsg, Dv, dt, scale, 0, ws + W.att, W.att_bytes, stream))
-        return rc;
-    // sliding and compressed branches at the chunk's absolute positions
-    if (int rc = nsa_band_attn_fwd(Q, kv->K_win, kv->V_win, Owin, nullptr, B, S, G, h, Dk, Dv, S_kv, ksb, ksg, Dk, vsb, vsg, Dv, t0, 0, 1, 0,
-                                   L->w, dt, scale, 0, ws + W.band, W.band_bytes, stream))
-        return rc;
-    if (int rc = nsa_band_attn_fwd(Q, kv->K_cmp, kv->V_cmp, Ocmp, nullptr, B, S, G, h, Dk, Dv, n1, kcb, kcg, Dk, vcb, vcg, Dv, t0, L->l, L->d,
-                                   1, 1 << 30, dt, scale, 0, ws + W.band, W.band_bytes, stream))
-        return rc;
-    return nsa_gate_combine(L, Q, Ocmp, Osel, Owin, O_mix, gates_out, (int64_t)B * S * G, stream);
+    return layer_rows("layer_extend", L, kv, proj, t0, S, NSA_SEL_SEQUENTIAL, 1, csc_ptr, csc_rows, csc_vals, S_sel, ranges_out,
+                      L ? L->n_sel : 0 /* a null L is refused there */, O_mix, gates_out, workspace, workspace_bytes, stream);
 }
 
 // workspace: proj | Q | O_cmp | O_sel | O_win | O_mix | ranges | selection-decode scratch | band scratch
@@ -320,7 +257,7 @@ static DecodeWs decode_ws(const nsa_layer_desc *L, int B, int S_max) {
     const size_t e = esize(L->dtype);
     const size_t NQ = (size_t)L->G * L->h * L->Dk, NO = (size_t)L->G * L->h * L->Dv;
     const size_t NT = NQ + 3 * (size_t)L->G * L->Dk + 3 * (size_t)L->G * L->Dv;
-    const int n_cmp_max = S_max < L->l ? 0 : (S_max - L->l) / L->d + 1;
+    const int n_cmp_max = ncmp_of(S_max, L->l, L->d);
     const int S_sel_max = (S_max + L->l_sel - 1) / L->l_sel + 1;
     size_t o = 0;
     w.proj = o; o += up256(B * NT * e);
@@ -341,7 +278,7 @@ static DecodeWs decode_ws(const nsa_layer_desc *L, int B, int S_max) {
 }
 
 size_t nsa_layer_decode_step_workspace(const nsa_layer_desc *L, int B, int S_max) {
-    if (!L || !dt_ok(L->dtype) || B < 1 || S_max < 1) return 0;
+    if (!L || !dtype_ok(L->dtype) || B < 1 || S_max < 1) return 0;
     return decode_ws(L, B, S_max).total;
 }
 
@@ -356,8 +293,7 @@ static int layer_decode_step_impl(const nsa_layer_desc *L, const nsa_kv_desc *kv
     NSA_CHECK_ARG(S_sel >= 1 && (int64_t)S_sel * L->l_sel >= t + 1, "layer_decode_step: block metadata (S_sel=%d) does not cover token %d", S_sel, t);
     const int B = kv->B;
     const DecodeWs W = decode_ws(L, B, kv->S_max);
-    NSA_CHECK_ARG(workspace && ((uintptr_t)workspace % 256 == 0) && workspace_bytes >= W.total,
-                  "layer_decode_step: workspace missing, misaligned or too small");
+    if (int rc = check_workspace("layer_decode_step", workspace, workspace_bytes, W.total)) return rc;
     unsigned char *ws = (unsigned char *)workspace;
     hipStream_t st = (hipStream_t)stream;
     const int dt = L->dtype;
@@ -366,26 +302,18 @@ static int layer_decode_step_impl(const nsa_layer_desc *L, const nsa_kv_desc *kv
     void *proj = ws + W.proj, *Q = ws + W.q, *Ocmp = ws + W.ocmp, *Osel = ws + W.osel, *Owin = ws + W.owin, *Omix = ws + W.omix;
     int32_t *ranges = ranges_out ? ranges_out : (int32_t *)(ws + W.ranges);
 
-    RopeAppendParams RP{};
-    RP.proj = proj;
-    RP.Q_out = Q;
-    RP.cache[0] = kv->K_sel; RP.cache[1] = kv->V_sel; RP.cache[2] = kv->K_win; RP.cache[3] = kv->V_win; RP.cache[4] = kv->K_raw; RP.cache[5] = kv->V_raw;
-    RP.B = B; RP.S = 1; RP.G = G; RP.h = h; RP.Dk = Dk; RP.Dv = Dv; RP.S_max = kv->S_max; RP.t0 = t;
-    RP.rope_base = L->rope_base > 0.f ? L->rope_base : 10000.0f;
-    RP.inv_scale = 1.0f / (L->rope_scale > 0.f ? L->rope_scale : 1.0f);
+    const RopeAppendParams RP = rope_append_params(L, kv, proj, Q, 1, t);
     // 1+2. fused QKV projection with RoPE + cache append at position t in its epilogue
     if (int rc = launch_qkv_rope_append(RP, x, L->W_qkv, L->dim, dt, st, norm_w, norm_eps)) return rc;
     // 3. emit a compressed token when a window completes (nsa_attention.py:588-604)
     const int S_raw = t + 1;
-    const int n_cmp = S_raw < L->l ? 0 : (S_raw - L->l) / L->d + 1;
+    const int n_cmp = ncmp_of(S_raw, L->l, L->d);
     NSA_CHECK_ARG(n_cmp <= kv->n_cmp_max, "layer_decode_step: compressed cache too small");
     if (S_raw >= L->l && (S_raw - L->l) % L->d == 0)
         if (int rc = nsa_cmp_pool_append(L, kv, n_cmp - 1, n_cmp, stream)) return rc;
-    const int64_t ksb = (int64_t)G * kv->S_max * Dk, ksg = (int64_t)kv->S_max * Dk;
-    const int64_t vsb = (int64_t)G * kv->S_max * Dv, vsg = (int64_t)kv->S_max * Dv;
-    const int64_t kcb = (int64_t)G * kv->n_cmp_max * Dk, kcg = (int64_t)kv->n_cmp_max * Dk;
-    const int64_t vcb = (int64_t)G * kv->n_cmp_max * Dv, vcg = (int64_t)kv->n_cmp_max * Dv;
-    const float scale = 1.0f / sqrtf((float)Dk);
+    const CacheStrides C(L, kv);
+    const int64_t ksb = C.ksb, ksg = C.ksg, vsb = C.vsb, vsg = C.vsg, kcb = C.kcb, kcg = C.kcg, vcb = C.vcb, vcg = C.vcg;
+    const float scale = C.scale;
     // When the final pass can take split-KV partial records (Dv = 64) the three branches skip their own combine kernels:
     // one kernel then merges the splits of all branches, evaluates the gate and mixes.
     const int defer = Dv == 64 ? 1 : 0;
@@ -405,10 +333,7 @@ static int layer_decode_step_impl(const nsa_layer_desc *L, const nsa_kv_desc *kv
     DecBandPair BP{};
     BandAttnParams &PW = BP.w, &PC = BP.c;
     if (dual) {
-        PW.Q = Q; PW.K = kv->K_win; PW.V = kv->V_win; PW.O = Owin;
-        PW.B = B; PW.S = 1; PW.G = G; PW.h = h; PW.Dk = Dk; PW.Dv = Dv; PW.S_kv = S_raw;
-        PW.ksb = ksb; PW.ksg = ksg; PW.kss = Dk; PW.vsb = vsb; PW.vsg = vsg; PW.vss = Dv;
-        PW.scale = scale; PW.t0 = t; PW.a = 0; PW.dd = 1; PW.c = 0; PW.w = L->w;
+        PW = band_attn_params(Q, kv->K_win, kv->V_win, Owin, nullptr, B, 1, G, h, Dk, Dv, S_raw, ksb, ksg, Dk, vsb, vsg, Dv, t, 0, 1, 0, L->w, scale);
         PW.part = (float *)(ws + W.band); PW.nsplit = ns_band; PW.defer_combine = 1;
         PC = PW;
         PC.K = kv->K_cmp; PC.V = kv->V_cmp; PC.O = Ocmp; PC.S_kv = n_cmp;
@@ -493,7 +418,7 @@ static BlockWs block_ws(const nsa_block_desc *Bk, int B, int S_max) {
 }
 
 size_t nsa_block_decode_step_workspace(const nsa_block_desc *Bk, int B, int S_max) {
-    if (!Bk || !dt_ok(Bk->attn.dtype) || B < 1 || S_max < 1 || Bk->mlp_hidden < 1) return 0;
+    if (!Bk || !dtype_ok(Bk->attn.dtype) || B < 1 || S_max < 1 || Bk->mlp_hidden < 1) return 0;
     return block_ws(Bk, B, S_max).total;
 }
 
@@ -506,8 +431,7 @@ int nsa_block_decode_step(const nsa_block_desc *Bk, const nsa_kv_desc *kv, const
     NSA_CHECK_ARG(x && y && Bk->norm1_w && Bk->norm2_w && Bk->mlp_w1 && Bk->mlp_w2 && Bk->mlp_hidden >= 1, "block_decode_step: null pointer");
     const int B = kv->B, dim = Bk->attn.dim, dt = Bk->attn.dtype;
     const BlockWs W = block_ws(Bk, B, kv->S_max);
-    NSA_CHECK_ARG(workspace && ((uintptr_t)workspace % 256 == 0) && workspace_bytes >= W.total,
-                  "block_decode_step: workspace missing, misaligned or too small");
+    if (int rc = check_workspace("block_decode_step", workspace, workspace_bytes, W.total)) return rc;
     unsigned char *ws = (unsigned char *)workspace;
     hipStream_t st = (hipStream_t)stream;
     void *xn = ws + W.xn, *h = ws + W.h, *hn = ws + W.hn, *u = ws + W.u;
@@ -555,7 +479,7 @@ int nsa_model_decode_step(const nsa_block_desc *blocks, const nsa_kv_desc *kvs, 
                       "model_decode_step: blocks / caches disagree on batch, width, dtype or capacity");
     const size_t need = nsa_model_decode_step_workspace(blocks, n_blocks, B, kvs[0].S_max);
     NSA_CHECK_ARG(need > 0 && workspace && ((uintptr_t)workspace % 256 == 0) && workspace_bytes >= need,
-                  "model_decode_step: workspace missing, misaligned or too small");
+                  "model_decode_step: workspace missing, misaligned or too small");  // need = 0: a block the workspace query refuses
     hipStream_t st = (hipStream_t)stream;
     const size_t xb = up256((size_t)B * dim * esize(dt));
     unsigned char *ws = (unsigned char *)workspace;

@@ -5,6 +5,7 @@
 // grouped_selection_attention_masked (nsa/core/attention_kernels.py:705-772).
 #include "nsa_common.hpp"
 #include "sel_attn_params.hpp"
+#include "nsa_internal.hpp"
 
 namespace nsa {
 

@@ -27,6 +27,7 @@
 // share its chunk (chunk boundaries at multiples of the workgroup's QW queries).
 #include "sel_scores_mfma.hpp"
 #include "sel_select_row.hpp"
+#include "nsa_internal.hpp"
 
 namespace nsa {
 

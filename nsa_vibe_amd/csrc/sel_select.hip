@@ -16,6 +16,7 @@
 #include "nsa_common.hpp"
 
 #include "sel_select_row.hpp"
+#include "nsa_internal.hpp"
 
 namespace nsa {
 
