@@ -46,27 +46,25 @@ __device__ __forceinline__ void raw8(const u32x4 &raw, float (&out)[8]) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) out[j] = Elt<T>::to_f(e[j]);
 }
-// sum of squares of a row held raw in up to two chunks per lane, with row_rms's rounding (chunk c valid when has[c])
+
+// the element type of a runtime dtype, once: f(T{}) with T = float (F32: where the kernel has an fp32 form), __bf16 or _Float16
+template <bool F32 = true, typename F>
+static inline void with_elt(int dtype, F &&f) {
+    if constexpr (F32)
+        if (dtype == NSA_DT_F32) return f(float{});
+    if (dtype == NSA_DT_BF16) return f(__bf16{});
+    return f(_Float16{});
+}
+
+// RMSNorm's rsqrt(mean(x^2) + eps) from a lane's partial sum of rnd(x^2), with the rounding points of the eager chain
+// (llama_block_nsa.py:16-19)
 template <typename T>
-__device__ __forceinline__ float row_rms_raw(const u32x4 (&x)[2], bool has1, int K, float eps) {
-    float acc = 0.f, v[8];
-    raw8<T>(x[0], v);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc += rnd<T>(v[j] * v[j]);
-    if (has1) {
-        raw8<T>(x[1], v);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc += rnd<T>(v[j] * v[j]);
-    }
+__device__ __forceinline__ float rms_finish(float acc, int K, float eps) {
     float r = rnd<T>(wave_sum(acc) / (float)K);
     r = rnd<T>(r + eps);
     return rnd<T>(1.0f / sqrtf(r));
 }
-
-// ------------------------------------------------------------------------------------------ small-M linear
-// one wave per output column n (W row n stays in registers), rows of A in chunks of 8
-// RMSNorm folded into a small-M projection: rsqrt(mean(x^2) + eps) of one row, computed by the whole wave with the rounding points
-// of the eager chain (llama_block_nsa.py:16-19); the caller then feeds rnd(rnd(x * r) * g) into its dot products
+// of one row, computed by the whole wave
 template <typename T>
 __device__ __forceinline__ float row_rms(const T *xr, int K, bool vec, float eps) {
     float acc = 0.f;
@@ -76,360 +74,38 @@ __device__ __forceinline__ float row_rms(const T *xr, int K, bool vec, float eps
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc += rnd<T>(v[j] * v[j]);
     }
-    float r = rnd<T>(wave_sum(acc) / (float)K);
-    r = rnd<T>(r + eps);
-    return rnd<T>(1.0f / sqrtf(r));
+    return rms_finish<T>(acc, K, eps);
 }
 
+// epi: 0 none, 1 silu, 2 + res (the residual value of this output)
 template <typename T>
-__device__ __forceinline__ float linear_epilogue(float acc, int epi, const T *res, int64_t idx) {
+__device__ __forceinline__ float linear_epilogue(float acc, int epi, float res) {
     float v = rnd<T>(acc);  // the GEMM result in the activation dtype, then the fused elementwise op rounds again like the eager chain
-    if (epi == 1) v = rnd<T>(v / (1.f + expf(-v)));       // silu
-    else if (epi == 2) v = v + Elt<T>::to_f(res[idx]);  // + residual
+    if (epi == 1) v = rnd<T>(v / (1.f + expf(-v)));  // silu
+    else if (epi == 2) v = v + res;
     return v;
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void linear_small_kernel(const T *__restrict__ A, const T *__restrict__ W, T *__restrict__ out, int M,
-                                                           int N, int K, int epi, const T *__restrict__ res, const T *__restrict__ norm_w,
-                                                           float norm_eps) {
-    const int lane = lane_id();
-    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (n >= N) return;
-    const T *w = W + (int64_t)n * K;
-    const bool vec = (K % 8 == 0) && (((uintptr_t)A | (uintptr_t)W) % 16 == 0);
-    for (int m0 = 0; m0 < M; m0 += 8) {
-        float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        const int mm = min(8, M - m0);
-        float rms[8];
-        if (norm_w)
-            for (int r = 0; r < mm; ++r) rms[r] = row_rms<T>(A + (int64_t)(m0 + r) * K, K, vec, norm_eps);
-        for (int k = lane * 8; k < K; k += 512) {
-            float wv[8], av[8], gv[8];
-            load8<T>(w + k, K - k, vec, wv);
-            if (norm_w) load8<T>(norm_w + k, K - k, vec && ((uintptr_t)norm_w % 16 == 0), gv);
-            for (int r = 0; r < mm; ++r) {
-                load8<T>(A + (int64_t)(m0 + r) * K + k, K - k, vec, av);
-                if (norm_w) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) av[j] = rnd<T>(rnd<T>(av[j] * rms[r]) * gv[j]);
-                }
-#pragma unroll
-                for (int j = 0; j < 8; ++j) acc[r] = fmaf(wv[j], av[j], acc[r]);
-            }
-        }
-        for (int r = 0; r < mm; ++r) {
-            const float s = wave_sum(acc[r]);
-            if (lane == 0) out[(int64_t)(m0 + r) * N + n] = Elt<T>::from_f(linear_epilogue<T>(s, epi, res, (int64_t)(m0 + r) * N + n));
-        }
-    }
-}
-
-// GEMV form for 1-2 rows and many columns (LM head): one wave = 4 output columns, so 4 weight rows are in flight per wave and the
-// weight matrix streams at memory speed; x (normalised on the fly when norm_w is given) is read once per wave
-template <typename T>
-__global__ __launch_bounds__(256) void linear_gemv4_kernel(const T *__restrict__ A, const T *__restrict__ W, T *__restrict__ out, int M, int N,
-                                                           int K, int epi, const T *__restrict__ res, const T *__restrict__ norm_w,
-                                                           float norm_eps) {
-    const int lane = lane_id();
-    const int n0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 4;
-    if (n0 >= N) return;
-    const bool vec = (K % 8 == 0) && (((uintptr_t)A | (uintptr_t)W) % 16 == 0);
-    float rms[2] = {1.f, 1.f};
-    if (norm_w)
-        for (int r = 0; r < M; ++r) rms[r] = row_rms<T>(A + (int64_t)r * K, K, vec, norm_eps);
-    float acc[4][2] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
-    for (int k = lane * 8; k < K; k += 512) {
-        float wv[4][8], av[2][8], gv[8];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) load8<T>(W + (int64_t)min(n0 + c, N - 1) * K + k, K - k, vec, wv[c]);
-        if (norm_w) load8<T>(norm_w + k, K - k, vec && ((uintptr_t)norm_w % 16 == 0), gv);
-        for (int r = 0; r < M; ++r) {
-            load8<T>(A + (int64_t)r * K + k, K - k, vec, av[r]);
-            if (norm_w) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) av[r][j] = rnd<T>(rnd<T>(av[r][j] * rms[r]) * gv[j]);
-            }
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) acc[c][r] = fmaf(wv[c][j], av[r][j], acc[c][r]);
-        }
-    }
-    for (int r = 0; r < M; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const float sum = wave_sum(acc[c][r]);
-            if (lane == 0 && n0 + c < N) out[(int64_t)r * N + n0 + c] = Elt<T>::from_f(linear_epilogue<T>(sum, epi, res, (int64_t)r * N + n0 + c));
-        }
-}
-
-// Latency forms of the two kernels above for 1-2 rows of 16-bit activations with K <= 512 NC (16-byte aligned rows): a decode step is a
-// chain of such launches and each is as long as its chain of dependent memory round trips -- the generic k loops wait for the loads of
-// one 512-element chunk before they issue the next (fc2 at K = 3072: six round trips in a row).  Here every load of the wave (weights,
-// norm weights, the rows of A) goes out before the first use; the arithmetic is the generic kernels' in the same order (same bits).
-template <typename T, int NC>
-__global__ __launch_bounds__(256) void linear_small_fast_kernel(const T *__restrict__ A, const T *__restrict__ W, T *__restrict__ out, int M, int N,
-                                                                int K, int epi, const T *__restrict__ res, const T *__restrict__ norm_w,
-                                                                float norm_eps) {
-    const int lane = lane_id();
-    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (n >= N) return;
-    const T *w = W + (int64_t)n * K;
-    u32x4 wr[NC], gr[NC], ar[2][NC];
-    bool has[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const int k = lane * 8 + 512 * c;
-        has[c] = k < K;
-        const int kc = min(k, K - 8);
-        wr[c] = *(const u32x4 *)(w + kc);
-        if (norm_w) gr[c] = *(const u32x4 *)(norm_w + kc);
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-            if (r < M) ar[r][c] = *(const u32x4 *)(A + (int64_t)r * K + kc);
-    }
-    float rms[2] = {1.f, 1.f};
-    if (norm_w) {
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-            if (r < M) {
-                float acc = 0.f;
-#pragma unroll
-                for (int c = 0; c < NC; ++c)
-                    if (has[c]) {
-                        float v[8];
-                        raw8<T>(ar[r][c], v);
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) acc += rnd<T>(v[j] * v[j]);
-                    }
-                float q = rnd<T>(wave_sum(acc) / (float)K);
-                q = rnd<T>(q + norm_eps);
-                rms[r] = rnd<T>(1.0f / sqrtf(q));
-            }
-    }
-    float acc[2] = {0.f, 0.f};
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-        if (has[c]) {
-            float wv[8], gv[8], av[8];
-            raw8<T>(wr[c], wv);
-            if (norm_w) raw8<T>(gr[c], gv);
-#pragma unroll
-            for (int r = 0; r < 2; ++r)
-                if (r < M) {
-                    raw8<T>(ar[r][c], av);
-                    if (norm_w) {
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) av[j] = rnd<T>(rnd<T>(av[j] * rms[r]) * gv[j]);
-                    }
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) acc[r] = fmaf(wv[j], av[j], acc[r]);
-                }
-        }
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-        if (r < M) {
-            const float sum = wave_sum(acc[r]);
-            if (lane == 0) out[(int64_t)r * N + n] = Elt<T>::from_f(linear_epilogue<T>(sum, epi, res, (int64_t)r * N + n));
-        }
-}
-
-template <typename T, int NC>
-__global__ __launch_bounds__(256) void linear_gemv4_fast_kernel(const T *__restrict__ A, const T *__restrict__ W, T *__restrict__ out, int M, int N,
-                                                                int K, int epi, const T *__restrict__ res, const T *__restrict__ norm_w,
-                                                                float norm_eps) {
-    const int lane = lane_id();
-    const int n0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 4;
-    if (n0 >= N) return;
-    u32x4 wr[4][NC], gr[NC], ar[2][NC];
-    bool has[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const int k = lane * 8 + 512 * c;
-        has[c] = k < K;
-        const int kc = min(k, K - 8);
-#pragma unroll
-        for (int cc = 0; cc < 4; ++cc) wr[cc][c] = *(const u32x4 *)(W + (int64_t)min(n0 + cc, N - 1) * K + kc);
-        if (norm_w) gr[c] = *(const u32x4 *)(norm_w + kc);
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-            if (r < M) ar[r][c] = *(const u32x4 *)(A + (int64_t)r * K + kc);
-    }
-    float rms[2] = {1.f, 1.f};
-    if (norm_w) {
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-            if (r < M) {
-                float acc = 0.f;
-#pragma unroll
-                for (int c = 0; c < NC; ++c)
-                    if (has[c]) {
-                        float v[8];
-                        raw8<T>(ar[r][c], v);
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) acc += rnd<T>(v[j] * v[j]);
-                    }
-                float q = rnd<T>(wave_sum(acc) / (float)K);
-                q = rnd<T>(q + norm_eps);
-                rms[r] = rnd<T>(1.0f / sqrtf(q));
-            }
-    }
-    float acc[4][2] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-        if (has[c]) {
-            float gv[8], av[2][8];
-            if (norm_w) raw8<T>(gr[c], gv);
-#pragma unroll
-            for (int r = 0; r < 2; ++r)
-                if (r < M) {
-                    raw8<T>(ar[r][c], av[r]);
-                    if (norm_w) {
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) av[r][j] = rnd<T>(rnd<T>(av[r][j] * rms[r]) * gv[j]);
-                    }
-                }
-#pragma unroll
-            for (int r = 0; r < 2; ++r)
-                if (r < M) {
-#pragma unroll
-                    for (int cc = 0; cc < 4; ++cc) {
-                        float wv[8];
-                        raw8<T>(wr[cc][c], wv);
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) acc[cc][r] = fmaf(wv[j], av[r][j], acc[cc][r]);
-                    }
-                }
-        }
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-        if (r < M) {
-#pragma unroll
-            for (int cc = 0; cc < 4; ++cc) {
-                const float sum = wave_sum(acc[cc][r]);
-                if (lane == 0 && n0 + cc < N) out[(int64_t)r * N + n0 + cc] = Elt<T>::from_f(linear_epilogue<T>(sum, epi, res, (int64_t)r * N + n0 + cc));
-            }
-        }
-}
-
-// decode, few rows: the three-branch mix as the A operand of the output projection -- A[r, k] = g_cmp O_cmp + g_sel O_sel + g_win O_win of
-// group k / (K / G) with the gate probabilities gates[r G + g][3] (evaluated by the launch that produced the branches), rounded to the
-// activation dtype exactly where the mix kernel rounds (mix3), so this is decode_finish + linear_small in one launch, same bits
-template <typename T, int NC>
-__global__ __launch_bounds__(256) void linear_small_mix_kernel(const T *__restrict__ Oc, const T *__restrict__ Os, const T *__restrict__ Ow,
-                                                               const float *__restrict__ gates, const T *__restrict__ W, T *__restrict__ out, int M,
-                                                               int N, int K, int G, int epi, const T *__restrict__ res) {
-    const int lane = lane_id();
-    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (n >= N) return;
-    const T *w = W + (int64_t)n * K;
-    const int kpg = K / G;
-    // (M <= 2, K <= 512 NC: every load of the wave out before the first use, like linear_small_fast_kernel)
-    u32x4 wr[NC], ocr[2][NC], osr[2][NC], owr[2][NC];
-    float pr[2][NC][3];
-    bool has[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const int k = lane * 8 + 512 * c;
-        has[c] = k < K;
-        const int kc = min(k, K - 8), g = kc / kpg;
-        wr[c] = *(const u32x4 *)(w + kc);
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-            if (r < M) {
-                const int64_t o = (int64_t)r * K + kc;
-                ocr[r][c] = *(const u32x4 *)(Oc + o);
-                osr[r][c] = *(const u32x4 *)(Os + o);
-                owr[r][c] = *(const u32x4 *)(Ow + o);
-                const float *gp = gates + ((int64_t)r * G + g) * 3;
-#pragma unroll
-                for (int i = 0; i < 3; ++i) pr[r][c][i] = gp[i];
-            }
-    }
-    float acc[2] = {0.f, 0.f};
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-        if (has[c]) {
-            float wv[8];
-            raw8<T>(wr[c], wv);
-#pragma unroll
-            for (int r = 0; r < 2; ++r)
-                if (r < M) {
-                    float oc[8], os[8], ow[8];
-                    raw8<T>(ocr[r][c], oc);
-                    raw8<T>(osr[r][c], os);
-                    raw8<T>(owr[r][c], ow);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) acc[r] = fmaf(wv[j], rnd<T>(mix3<T>(pr[r][c], oc[j], os[j], ow[j])), acc[r]);
-                }
-        }
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-        if (r < M) {
-            const float sum = wave_sum(acc[r]);
-            if (lane == 0) out[(int64_t)r * N + n] = Elt<T>::from_f(linear_epilogue<T>(sum, epi, res, (int64_t)r * N + n));
-        }
-}
-
-template <typename T>
-static int linear_small_t(const void *A, const void *W, void *out, int M, int N, int K, int epi, const void *res, const void *norm_w, float eps,
-                          hipStream_t st) {
-    if constexpr (sizeof(T) == 2) {
-        const bool fast = M <= 2 && K >= 8 && K % 8 == 0 && K <= 4096 && (((uintptr_t)A | (uintptr_t)W) % 16 == 0) &&
-                          (!norm_w || (uintptr_t)norm_w % 16 == 0);
-        if (fast) {
-            const int nc = (K + 511) / 512;
-            const bool g4 = N >= 4096 && nc <= 2;
-            const dim3 grid(g4 ? (unsigned)((N + 15) / 16) : (unsigned)((N + 3) / 4));
-#define NSA_LSF(KERN, NC_) hipLaunchKernelGGL((KERN<T, NC_>), grid, dim3(256), 0, st, (const T *)A, (const T *)W, (T *)out, M, N, K, epi, (const T *)res, (const T *)norm_w, eps)
-            if (g4) NSA_LSF(linear_gemv4_fast_kernel, 2);
-            else if (nc <= 2) NSA_LSF(linear_small_fast_kernel, 2);
-            else if (nc <= 4) NSA_LSF(linear_small_fast_kernel, 4);
-            else if (nc <= 6) NSA_LSF(linear_small_fast_kernel, 6);
-            else NSA_LSF(linear_small_fast_kernel, 8);
-#undef NSA_LSF
-            NSA_LAUNCH_CHECK("linear_small(fast)");
-            return NSA_OK;
-        }
-    }
-    if (M <= 2 && N >= 4096)
-        hipLaunchKernelGGL(linear_gemv4_kernel<T>, dim3((unsigned)((N + 15) / 16)), dim3(256), 0, st, (const T *)A, (const T *)W, (T *)out, M, N, K,
-                           epi, (const T *)res, (const T *)norm_w, eps);
-    else
-        hipLaunchKernelGGL(linear_small_kernel<T>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, (const T *)A, (const T *)W, (T *)out, M, N, K, epi,
-                           (const T *)res, (const T *)norm_w, eps);
-    NSA_LAUNCH_CHECK("linear_small");
-    return NSA_OK;
-}
-static int launch_linear_small_valu(const void *A, const void *W, void *out, int M, int N, int K, int dtype, int epi, const void *res,
-                                    const void *norm_w, float eps, hipStream_t st) {
-    if (dtype == NSA_DT_F32) return linear_small_t<float>(A, W, out, M, N, K, epi, res, norm_w, eps, st);
-    if (dtype == NSA_DT_BF16) return linear_small_t<__bf16>(A, W, out, M, N, K, epi, res, norm_w, eps, st);
-    return linear_small_t<_Float16>(A, W, out, M, N, K, epi, res, norm_w, eps, st);
-}
-
 // ------------------------------------------------------------------------------------------ RoPE + cache append
-// prefill form.  A thread owns ONE column pair (its rotation frequency, destination tensor and column are computed once) and
-// walks the tokens: consecutive threads = consecutive columns, so loads and stores stay coalesced.
+// Where the column pair starting at `col` of a fused QKV projection row [Q | K_sel V_sel | K_win V_win | K_raw V_raw] goes -- the one place
+// that knows the layout.  The destinations are Q_out [B,S,NQ] and the six cache tensors [B,G,rows,D]; element (b, s) of the pair is at
+// p + b sb + s ss.  Q is rotated as ONE row of width NQ, K_sel and K_win per group over Dk, the raw keys and the values not at all.
 template <typename T>
-__global__ __launch_bounds__(256) void rope_cache_append_kernel(RopeAppendParams P) {
-    const int NQ = P.G * P.h * P.Dk, GK = P.G * P.Dk, GV = P.G * P.Dv;
-    const int NT = NQ + 3 * GK + 3 * GV;
-    const int cp = blockIdx.x * 256 + threadIdx.x;
-    if (cp >= NT / 2) return;
-    const int col = 2 * cp;
-    // destination: base pointer + per-batch and per-token strides (elements), rotation: pair index i of D_rope (or none)
-    T *dst;
-    int64_t sb, ss;
-    int ri = -1, rD = 1;
-    if (col < NQ) {
-        dst = (T *)P.Q_out + col;
-        sb = (int64_t)P.S * NQ;
-        ss = NQ;
-        ri = col >> 1;
-        rD = NQ;
-    } else {
+struct QkvCol {
+    T *p;            // null when the tensor is (the backward: a gradient that is zero)
+    int64_t sb, ss;  // elements between batches / tokens
+    int ri, rD;      // rotation: pair index and width; ri < 0 = not rotated
+    // col < NT; rows = rows per (b, g) of a cache tensor, row0 = the row of s = 0 there
+    __device__ __forceinline__ QkvCol(const RopeAppendParams &P, int col, int rows, int row0) {
+        const int NQ = P.G * P.h * P.Dk, GK = P.G * P.Dk, GV = P.G * P.Dv;
+        if (col < NQ) {
+            p = (T *)P.Q_out + col;
+            sb = (int64_t)P.S * NQ;
+            ss = NQ;
+            ri = col >> 1;
+            rD = NQ;
+            return;
+        }
         int c = col - NQ;
         const int pairw = GK + GV;
         const int sp = c / pairw;
@@ -438,19 +114,29 @@ __global__ __launch_bounds__(256) void rope_cache_append_kernel(RopeAppendParams
         if (isv) c -= GK;
         const int D = isv ? P.Dv : P.Dk;
         const int g = c / D, dc = c - g * D;
-        dst = (T *)P.cache[2 * sp + (isv ? 1 : 0)] + ((int64_t)g * P.S_max + P.t0) * D + dc;
-        sb = (int64_t)P.G * P.S_max * D;
+        T *base = (T *)P.cache[2 * sp + (isv ? 1 : 0)];
+        p = base ? base + ((int64_t)g * rows + row0) * D + dc : nullptr;
+        sb = (int64_t)P.G * rows * D;
         ss = D;
-        if (!isv && sp < 2) {
-            ri = dc >> 1;
-            rD = P.Dk;
-        }
+        ri = !isv && sp < 2 ? dc >> 1 : -1;
+        rD = P.Dk;
     }
-    const float inv_freq = ri >= 0 ? powf(P.rope_base, (-2.0f * (float)ri) / (float)rD) : 0.f;
+};
+
+// prefill form.  A thread owns ONE column pair (its rotation frequency, destination tensor and column are computed once) and
+// walks the tokens: consecutive threads = consecutive columns, so loads and stores stay coalesced.
+template <typename T>
+__global__ __launch_bounds__(256) void rope_cache_append_kernel(RopeAppendParams P) {
+    const int NT = P.G * P.h * P.Dk + 3 * P.G * P.Dk + 3 * P.G * P.Dv;
+    const int cp = blockIdx.x * 256 + threadIdx.x;
+    if (cp >= NT / 2) return;
+    const int col = 2 * cp;
+    const QkvCol<T> c(P, col, P.S_max, P.t0);
+    const float inv_freq = c.ri >= 0 ? powf(P.rope_base, (-2.0f * (float)c.ri) / (float)c.rD) : 0.f;
     // positions outside, sequences inside: the rotation (sincosf: most of this kernel's arithmetic) depends on the position only
     for (int s = blockIdx.y; s < P.S; s += gridDim.y) {
         float sn = 0.f, cs = 1.f;
-        if (ri >= 0) {
+        if (c.ri >= 0) {
             const float ang = ((float)(P.t0 + s) * P.inv_scale) * inv_freq;
             sincosf(ang, &sn, &cs);
             sn = rnd<T>(sn);
@@ -459,12 +145,8 @@ __global__ __launch_bounds__(256) void rope_cache_append_kernel(RopeAppendParams
         for (int b = blockIdx.z; b < P.B; b += gridDim.z) {
             const T *src = (const T *)P.proj + ((int64_t)b * P.S + s) * NT + col;
             float x0 = Elt<T>::to_f(src[0]), x1 = Elt<T>::to_f(src[1]);
-            if (ri >= 0) {
-                const float r0 = rnd<T>(rnd<T>(x0 * cs) - rnd<T>(x1 * sn));
-                x1 = rnd<T>(rnd<T>(x0 * sn) + rnd<T>(x1 * cs));
-                x0 = r0;
-            }
-            T *d = dst + b * sb + s * ss;
+            if (c.ri >= 0) rope_rotate<T>(x0, x1, sn, cs, x0, x1);
+            T *d = c.p + b * c.sb + s * c.ss;
             d[0] = Elt<T>::from_f(x0);
             d[1] = Elt<T>::from_f(x1);
         }
@@ -479,60 +161,31 @@ int launch_rope_cache_append(const RopeAppendParams &P, int dtype, hipStream_t s
     const unsigned gy = (unsigned)std::min<int64_t>(P.S, 2048);
     const unsigned gz = (unsigned)std::max<int64_t>(1, std::min<int64_t>(P.B, 2048 / gy));
     const dim3 grid((unsigned)((NT / 2 + 255) / 256), gy, gz);
-    if (dtype == NSA_DT_F32) hipLaunchKernelGGL(rope_cache_append_kernel<float>, grid, dim3(256), 0, st, P);
-    else if (dtype == NSA_DT_BF16) hipLaunchKernelGGL(rope_cache_append_kernel<__bf16>, grid, dim3(256), 0, st, P);
-    else hipLaunchKernelGGL(rope_cache_append_kernel<_Float16>, grid, dim3(256), 0, st, P);
+    with_elt(dtype, [&](auto t) { hipLaunchKernelGGL(rope_cache_append_kernel<decltype(t)>, grid, dim3(256), 0, st, P); });
     NSA_LAUNCH_CHECK("rope_cache_append");
     return NSA_OK;
 }
 
-// backward of rope_cache_append: d(proj) from dQ [B,S,NQ] and the six cache-slice gradients [B,G,S,D] (null = zero).  The
-// rotation is orthogonal, so the gradient of a rotated pair is the pair rotated back by the same angle.
+// backward of rope_cache_append: d(proj) from dQ [B,S,NQ] and the six cache-slice gradients [B,G,S,D] (S rows, not S_max; null = zero),
+// read where the forward writes.  The rotation is orthogonal, so the gradient of a rotated pair is the pair rotated back by the same angle.
 template <typename T>
 __global__ __launch_bounds__(256) void rope_cache_append_bwd_kernel(RopeAppendParams P) {
-    const int NQ = P.G * P.h * P.Dk, GK = P.G * P.Dk, GV = P.G * P.Dv;
-    const int NT = NQ + 3 * GK + 3 * GV;
+    const int NT = P.G * P.h * P.Dk + 3 * P.G * P.Dk + 3 * P.G * P.Dv;
     const int cp = blockIdx.x * 256 + threadIdx.x;
     if (cp >= NT / 2) return;
     const int col = 2 * cp;
-    const T *src;  // gradient of the forward's destination
-    int64_t sb, ss;
-    int ri = -1, rD = 1;
-    if (col < NQ) {
-        src = (const T *)P.Q_out + col;
-        sb = (int64_t)P.S * NQ;
-        ss = NQ;
-        ri = col >> 1;
-        rD = NQ;
-    } else {
-        int c = col - NQ;
-        const int pairw = GK + GV;
-        const int sp = c / pairw;
-        c -= sp * pairw;
-        const bool isv = c >= GK;
-        if (isv) c -= GK;
-        const int D = isv ? P.Dv : P.Dk;
-        const int g = c / D, dc = c - g * D;
-        const T *base = (const T *)P.cache[2 * sp + (isv ? 1 : 0)];  // [B,G,S,D] gradient tensor (S rows, not S_max)
-        src = base ? base + (int64_t)g * P.S * D + dc : nullptr;
-        sb = (int64_t)P.G * P.S * D;
-        ss = D;
-        if (!isv && sp < 2) {
-            ri = dc >> 1;
-            rD = P.Dk;
-        }
-    }
-    const float inv_freq = ri >= 0 ? powf(P.rope_base, (-2.0f * (float)ri) / (float)rD) : 0.f;
+    const QkvCol<T> c(P, col, P.S, 0);
+    const float inv_freq = c.ri >= 0 ? powf(P.rope_base, (-2.0f * (float)c.ri) / (float)c.rD) : 0.f;
     const int64_t ntok = (int64_t)P.B * P.S;
     for (int64_t row = blockIdx.y; row < ntok; row += gridDim.y) {
         const int b = (int)(row / P.S), s = (int)(row - (int64_t)b * P.S);
         float g0 = 0.f, g1 = 0.f;
-        if (src) {
-            const T *p = src + b * sb + s * ss;
+        if (c.p) {
+            const T *p = c.p + b * c.sb + s * c.ss;
             g0 = Elt<T>::to_f(p[0]);
             g1 = Elt<T>::to_f(p[1]);
         }
-        if (ri >= 0) {
+        if (c.ri >= 0) {
             const float ang = ((float)(P.t0 + s) * P.inv_scale) * inv_freq;
             float sn, cs;
             sincosf(ang, &sn, &cs);
@@ -553,88 +206,13 @@ int launch_rope_cache_append_bwd(const RopeAppendParams &P, int dtype, hipStream
     const int64_t ntok = (int64_t)P.B * P.S;
     if (ntok == 0) return NSA_OK;
     const dim3 grid((unsigned)((NT / 2 + 255) / 256), (unsigned)std::min<int64_t>(ntok, 2048));
-    if (dtype == NSA_DT_F32) hipLaunchKernelGGL(rope_cache_append_bwd_kernel<float>, grid, dim3(256), 0, st, P);
-    else if (dtype == NSA_DT_BF16) hipLaunchKernelGGL(rope_cache_append_bwd_kernel<__bf16>, grid, dim3(256), 0, st, P);
-    else hipLaunchKernelGGL(rope_cache_append_bwd_kernel<_Float16>, grid, dim3(256), 0, st, P);
+    with_elt(dtype, [&](auto t) { hipLaunchKernelGGL(rope_cache_append_bwd_kernel<decltype(t)>, grid, dim3(256), 0, st, P); });
     NSA_LAUNCH_CHECK("rope_cache_append_bwd");
     return NSA_OK;
 }
 
-// decode form: the fused QKV projection and the RoPE + cache append in one kernel.  One wave per PAIR of adjacent output
-// columns (a rotation pair), rows of x in chunks of 8; lane r of the wave finishes row r of the chunk.
-template <typename T>
-__device__ __forceinline__ void rope_store_pair(const RopeAppendParams &P, int b, int s, int col, float x0, float x1) {
-    const int NQ = P.G * P.h * P.Dk, GK = P.G * P.Dk, GV = P.G * P.Dv;
-    const float pos = (float)(P.t0 + s);
-    if (col < NQ) {
-        rope_pair<T>(x0, x1, col >> 1, NQ, pos, P.rope_base, P.inv_scale, x0, x1);
-        T *dst = (T *)P.Q_out + ((int64_t)b * P.S + s) * NQ + col;
-        dst[0] = Elt<T>::from_f(x0);
-        dst[1] = Elt<T>::from_f(x1);
-        return;
-    }
-    int c = col - NQ;
-    const int pairw = GK + GV;
-    const int sp = c / pairw;
-    c -= sp * pairw;
-    const bool isv = c >= GK;
-    if (isv) c -= GK;
-    const int D = isv ? P.Dv : P.Dk;
-    const int g = c / D, dc = c - g * D;
-    if (!isv && sp < 2) rope_pair<T>(x0, x1, dc >> 1, P.Dk, pos, P.rope_base, P.inv_scale, x0, x1);
-    T *dst = (T *)P.cache[2 * sp + (isv ? 1 : 0)] + (((int64_t)b * P.G + g) * P.S_max + (P.t0 + s)) * D + dc;
-    dst[0] = Elt<T>::from_f(x0);
-    dst[1] = Elt<T>::from_f(x1);
-}
-
-template <typename T>
-__global__ __launch_bounds__(256, 2) void qkv_rope_append_kernel(RopeAppendParams P, const T *__restrict__ X, const T *__restrict__ W, int K,
-                                                              const T *__restrict__ norm_w, float norm_eps) {
-    const int lane = lane_id();
-    const int NT = P.G * P.h * P.Dk + 3 * P.G * P.Dk + 3 * P.G * P.Dv;
-    const int pair = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (2 * pair >= NT) return;
-    const T *w0 = W + (int64_t)(2 * pair) * K, *w1 = w0 + K;
-    const bool vec = (K % 8 == 0) && (((uintptr_t)X | (uintptr_t)W) % 16 == 0);
-    const int M = P.B;  // S == 1
-    for (int m0 = 0; m0 < M; m0 += 8) {
-        float a0[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, a1[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        const int mm = min(8, M - m0);
-        float rms[8];
-        if (norm_w)
-            for (int r = 0; r < mm; ++r) rms[r] = row_rms<T>(X + (int64_t)(m0 + r) * K, K, vec, norm_eps);
-        for (int k = lane * 8; k < K; k += 512) {
-            float u0[8], u1[8], xv[8], gv[8];
-            load8<T>(w0 + k, K - k, vec, u0);
-            load8<T>(w1 + k, K - k, vec, u1);
-            if (norm_w) load8<T>(norm_w + k, K - k, vec && ((uintptr_t)norm_w % 16 == 0), gv);
-            for (int r = 0; r < mm; ++r) {
-                load8<T>(X + (int64_t)(m0 + r) * K + k, K - k, vec, xv);
-                if (norm_w) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) xv[j] = rnd<T>(rnd<T>(xv[j] * rms[r]) * gv[j]);
-                }
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    a0[r] = fmaf(u0[j], xv[j], a0[r]);
-                    a1[r] = fmaf(u1[j], xv[j], a1[r]);
-                }
-            }
-        }
-        float x0 = 0.f, x1 = 0.f;
-        for (int r = 0; r < mm; ++r) {
-            const float s0 = wave_sum(a0[r]), s1 = wave_sum(a1[r]);
-            if (lane == r) {
-                x0 = rnd<T>(s0);  // the projection output in the activation dtype, as the separate GEMM leaves it
-                x1 = rnd<T>(s1);
-            }
-        }
-        if (lane < mm) rope_store_pair<T>(P, m0 + lane, 0, 2 * pair, x0, x1);
-    }
-}
-
-// destination and rotation of the column pair starting at `col` of a decode-step projection row (S = 1): rope_store_pair's cases with the
-// position-only part (powf + sincosf) separated, so that a kernel can evaluate it while its loads are in flight
+// decode step (S = 1): destination and rotation of a column pair with the position-only part (powf + sincosf) separated, so that a kernel can
+// evaluate it while its loads are in flight
 template <typename T>
 struct RopeDest {
     float sn, cs;
@@ -643,29 +221,13 @@ struct RopeDest {
     int64_t dst_row;  // elements between consecutive rows b
     // with_rotation = false: destination only (sn / cs come from elsewhere, e.g. from a thread of the workgroup that evaluated them once)
     __device__ __forceinline__ void init(const RopeAppendParams &P, int col, bool with_rotation = true) {
-        const int NQ = P.G * P.h * P.Dk, GK = P.G * P.Dk, GV = P.G * P.Dv;
-        const float pos = (float)P.t0;
+        const QkvCol<T> c(P, col, P.S_max, P.t0);  // (the MFMA form clamps the columns of a partial tile to NT - 2 before it asks)
         sn = 0.f;
         cs = 1.f;
-        if (col < NQ) {
-            rot = true;
-            if (with_rotation) rope_sincos<T>(col >> 1, NQ, pos, P.rope_base, P.inv_scale, sn, cs);
-            dst = (T *)P.Q_out + col;
-            dst_row = NQ;
-            return;
-        }
-        int c = col - NQ;
-        const int pairw = GK + GV;
-        const int sp = min(c / pairw, 2);
-        c -= sp * pairw;
-        const bool isv = c >= GK;
-        if (isv) c -= GK;
-        const int D = isv ? P.Dv : P.Dk;
-        const int g = c / D, dc = c - g * D;
-        rot = !isv && sp < 2;
-        if (rot && with_rotation) rope_sincos<T>(dc >> 1, P.Dk, pos, P.rope_base, P.inv_scale, sn, cs);
-        dst = (T *)P.cache[2 * sp + (isv ? 1 : 0)] + ((int64_t)g * P.S_max + P.t0) * D + dc;
-        dst_row = (int64_t)P.G * P.S_max * D;
+        rot = c.ri >= 0;
+        if (rot && with_rotation) rope_sincos<T>(c.ri, c.rD, (float)P.t0, P.rope_base, P.inv_scale, sn, cs);
+        dst = c.p;
+        dst_row = c.sb;
     }
     __device__ __forceinline__ void store(int b, float x0, float x1) const {
         if (rot) rope_rotate<T>(x0, x1, sn, cs, x0, x1);
@@ -674,36 +236,53 @@ struct RopeDest {
     }
 };
 
-// latency form of qkv_rope_append_kernel for 1-2 rows, K <= 512 NC (see linear_small_fast_kernel): every load out first, the pair's
-// rotation (powf + sincosf, ~1 us of arithmetic that depends on the position only) evaluated while they are in flight
-template <typename T, int NC>
-__global__ __launch_bounds__(256, 2) void qkv_rope_append_fast_kernel(RopeAppendParams P, const T *__restrict__ X, const T *__restrict__ W, int K,
-                                                                   const T *__restrict__ norm_w, float norm_eps) {
-    const int lane = lane_id();
-    const int NQ = P.G * P.h * P.Dk, GK = P.G * P.Dk, GV = P.G * P.Dv;
-    const int NT = NQ + 3 * GK + 3 * GV;
-    const int pair = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (2 * pair >= NT) return;
-    const T *w0 = W + (int64_t)(2 * pair) * K, *w1 = w0 + K;
-    const int M = P.B;  // S == 1, M <= 2
-    u32x4 u0r[NC], u1r[NC], gr[NC], xr[2][NC];
-    bool has[NC];
+// ------------------------------------------------------------------------------------------ few-row projections on the VALU
+// out[m, n] = A[m, :] . W[n, :] for a few rows m: a wave owns CW weight rows (1; 2 = a rotation pair; 4 = the LM head, where four rows in
+// flight per wave let the weight matrix stream at memory speed) and keeps one accumulator per (weight row, row of A): fmaf over k
+// ascending, j ascending, then wave_sum.  Two kernel templates differ in how the k axis is walked and nothing else; two policies say what
+// the A operand is and where a finished row goes.
+//
+// A-operand policies: the 8 activations of a row at k .. k + 7 as floats, for the chunk loop (loaded at each use) and for the
+// all-loads-first form (Regs<NC>: the raw 16-byte pieces of up to 2 rows, fetched before the first use).
+// RowsA: rows of A; when norm_w is given RMSNorm(A) is folded in -- the dot products see rnd(rnd(x r) g), r = row_rms
+template <typename T>
+struct RowsA {
+    const T *A, *norm_w;
+    float eps;
+    static __device__ __forceinline__ void normed(float (&av)[8], float r, const float (&gv)[8]) {
 #pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const int k = lane * 8 + 512 * c;
-        has[c] = k < K;
-        const int kc = min(k, K - 8);
-        u0r[c] = *(const u32x4 *)(w0 + kc);
-        u1r[c] = *(const u32x4 *)(w1 + kc);
-        if (norm_w) gr[c] = *(const u32x4 *)(norm_w + kc);
+        for (int j = 0; j < 8; ++j) av[j] = rnd<T>(rnd<T>(av[j] * r) * gv[j]);
+    }
+    // (chunk loop: rms = one value per row of the pass, gv = the norm weights of the k chunk; plain arrays of the kernel, so that the
+    // row-indexed one stays in registers)
+    template <int RB>
+    __device__ __forceinline__ void rows(float (&rms)[RB], int m0, int mm, int K, bool vec) const {
+        if (norm_w)
+            for (int r = 0; r < mm; ++r) rms[r] = row_rms<T>(A + (int64_t)(m0 + r) * K, K, vec, eps);
+    }
+    __device__ __forceinline__ void chunk(float (&gv)[8], int k, int K, bool vec) const {
+        if (norm_w) load8<T>(norm_w + k, K - k, vec && ((uintptr_t)norm_w % 16 == 0), gv);
+    }
+    __device__ __forceinline__ void row(float rms, const float (&gv)[8], int m, int k, int K, bool vec, float (&av)[8]) const {
+        load8<T>(A + (int64_t)m * K + k, K - k, vec, av);
+        if (norm_w) normed(av, rms, gv);
+    }
+    template <int NC>
+    struct Regs {
+        u32x4 ar[2][NC], gr[NC];
+        float rms[2], gv[8];
+    };
+    template <int NC>
+    __device__ __forceinline__ void fetch(Regs<NC> &x, int c, int kc, int M, int K) const {
+        if (norm_w) x.gr[c] = *(const u32x4 *)(norm_w + kc);
 #pragma unroll
         for (int r = 0; r < 2; ++r)
-            if (r < M) xr[r][c] = *(const u32x4 *)(X + (int64_t)r * K + kc);
+            if (r < M) x.ar[r][c] = *(const u32x4 *)(A + (int64_t)r * K + kc);
     }
-    RopeDest<T> rd;  // destination and rotation of this wave's column pair, evaluated under the loads
-    rd.init(P, 2 * pair);
-    float rms[2] = {1.f, 1.f};
-    if (norm_w) {
+    template <int NC>
+    __device__ __forceinline__ void rows(Regs<NC> &x, const bool (&has)[NC], int M, int K) const {
+        x.rms[0] = x.rms[1] = 1.f;
+        if (!norm_w) return;
 #pragma unroll
         for (int r = 0; r < 2; ++r)
             if (r < M) {
@@ -712,43 +291,202 @@ __global__ __launch_bounds__(256, 2) void qkv_rope_append_fast_kernel(RopeAppend
                 for (int c = 0; c < NC; ++c)
                     if (has[c]) {
                         float v[8];
-                        raw8<T>(xr[r][c], v);
+                        raw8<T>(x.ar[r][c], v);
 #pragma unroll
                         for (int j = 0; j < 8; ++j) acc += rnd<T>(v[j] * v[j]);
                     }
-                float q = rnd<T>(wave_sum(acc) / (float)K);
-                q = rnd<T>(q + norm_eps);
-                rms[r] = rnd<T>(1.0f / sqrtf(q));
+                x.rms[r] = rms_finish<T>(acc, K, eps);
             }
     }
-    float a0[2] = {0.f, 0.f}, a1[2] = {0.f, 0.f};
+    template <int NC>
+    __device__ __forceinline__ void chunk(Regs<NC> &x, int c) const {
+        if (norm_w) raw8<T>(x.gr[c], x.gv);
+    }
+    template <int NC>
+    __device__ __forceinline__ void row(const Regs<NC> &x, int r, int c, float (&av)[8]) const {
+        raw8<T>(x.ar[r][c], av);
+        if (norm_w) normed(av, x.rms[r], x.gv);
+    }
+};
+// MixA (decode output projection, all-loads-first form only): A[r, k] = g_cmp O_cmp + g_sel O_sel + g_win O_win of group k / (K / G) with the
+// gate probabilities gates[r G + g][3] (evaluated by the launch that produced the branches), rounded to the activation dtype exactly where
+// the mix kernel rounds (mix3), so this is decode_finish + the plain projection in one launch, same bits
+template <typename T>
+struct MixA {
+    const T *Oc, *Os, *Ow;
+    const float *gates;
+    int G;
+    template <int NC>
+    struct Regs {
+        u32x4 oc[2][NC], os[2][NC], ow[2][NC];
+        float pr[2][NC][3];
+    };
+    template <int NC>
+    __device__ __forceinline__ void fetch(Regs<NC> &x, int c, int kc, int M, int K) const {
+        const int g = kc / (K / G);
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+            if (r < M) {
+                const int64_t o = (int64_t)r * K + kc;
+                x.oc[r][c] = *(const u32x4 *)(Oc + o);
+                x.os[r][c] = *(const u32x4 *)(Os + o);
+                x.ow[r][c] = *(const u32x4 *)(Ow + o);
+                const float *gp = gates + ((int64_t)r * G + g) * 3;
+#pragma unroll
+                for (int i = 0; i < 3; ++i) x.pr[r][c][i] = gp[i];
+            }
+    }
+    template <int NC>
+    __device__ __forceinline__ void rows(Regs<NC> &, const bool (&)[NC], int, int) const {}
+    template <int NC>
+    __device__ __forceinline__ void chunk(Regs<NC> &, int) const {}
+    template <int NC>
+    __device__ __forceinline__ void row(const Regs<NC> &x, int r, int c, float (&av)[8]) const {
+        float oc[8], os[8], ow[8];
+        raw8<T>(x.oc[r][c], oc);
+        raw8<T>(x.os[r][c], os);
+        raw8<T>(x.ow[r][c], ow);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) av[j] = rnd<T>(mix3<T>(x.pr[r][c], oc[j], os[j], ow[j]));
+    }
+};
+
+// Epilogue policies: init(n0) once per wave (the all-loads-first form calls it while its loads are in flight) gives the wave's state, then
+// store(state, m, n, s) by lane 0 with s = the dot products of row m with the weight rows n, n + 1, ...: a multiple of GROUP of them (the
+// chunk loop hands them over GROUP at a time, as soon as they are summed).
+// LinearEpi: out[m, n] = linear_epilogue(s)
+template <typename T>
+struct LinearEpi {
+    static constexpr int MIN_BLOCKS = 1, GROUP = 1;
+    T *out;
+    const T *res;
+    int epi, N;
+    struct Wave {};
+    __device__ __forceinline__ Wave init(int) const { return {}; }
+    template <int CW>
+    __device__ __forceinline__ void store(const Wave &, int m, int n0, const float (&s)[CW]) const {
+#pragma unroll
+        for (int cc = 0; cc < CW; ++cc)
+            if (n0 + cc < N) {
+                const int64_t idx = (int64_t)m * N + n0 + cc;
+                out[idx] = Elt<T>::from_f(linear_epilogue<T>(s[cc], epi, epi == 2 ? Elt<T>::to_f(res[idx]) : 0.f));
+            }
+    }
+};
+// RopeEpi (CW = 2, the decode step's fused QKV projection): the pair, rounded to the activation dtype as the separate GEMM leaves it, is
+// rotated and appended to Q_out / its cache tensor at position t0
+template <typename T>
+struct RopeEpi {
+    static constexpr int MIN_BLOCKS = 2, GROUP = 2;
+    RopeAppendParams P;
+    using Wave = RopeDest<T>;
+    __device__ __forceinline__ Wave init(int n0) const {
+        Wave rd;
+        rd.init(P, n0);
+        return rd;
+    }
+    __device__ __forceinline__ void store(const Wave &rd, int m, int, const float (&s)[2]) const { rd.store(m, rnd<T>(s[0]), rnd<T>(s[1])); }
+};
+
+// chunk-loop form (any dtype, K and alignment): k in 512-element chunks, rows of A in passes of 8 (CW = 4: at most 2 rows, one pass).  The
+// loads of one k chunk are waited for before the next goes out.
+template <typename T, int CW, typename AOp, typename Epi>
+__global__ __launch_bounds__(256, Epi::MIN_BLOCKS) void proj_loop_kernel(const AOp a, const T *__restrict__ W, int M, int N, int K, const Epi e) {
+    constexpr int RB = CW == 4 ? 2 : 8;  // rows of A per pass; the 4-row form is only routed 1-2 rows: one pass, no row loop
+    const int lane = lane_id();
+    const int n0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * CW;
+    if (n0 >= N) return;
+    const bool vec = (K % 8 == 0) && (((uintptr_t)a.A | (uintptr_t)W) % 16 == 0);
+    const typename Epi::Wave ew = e.init(n0);
+    for (int m0 = 0; m0 < (CW == 4 ? 1 : M); m0 += RB) {
+        const int mm = min(RB, M - m0);
+        float rms[RB];
+#pragma unroll
+        for (int r = 0; r < RB; ++r) rms[r] = 1.f;
+        a.rows(rms, m0, mm, K, vec);
+        float acc[CW][RB];
+#pragma unroll
+        for (int cc = 0; cc < CW; ++cc)
+#pragma unroll
+            for (int r = 0; r < RB; ++r) acc[cc][r] = 0.f;
+        for (int k = lane * 8; k < K; k += 512) {
+            // (the 4-row form keeps each row's activations in registers of their own, as the kernel it was folded from did: one shared
+            // buffer costs it 3 VGPRs and with them a wave per SIMD)
+            float wv[CW][8], av[CW == 4 ? RB : 1][8], gv[8];
+#pragma unroll
+            for (int cc = 0; cc < CW; ++cc) load8<T>(W + (int64_t)min(n0 + cc, N - 1) * K + k, K - k, vec, wv[cc]);
+            a.chunk(gv, k, K, vec);
+            for (int r = 0; r < mm; ++r) {
+                float (&avr)[8] = av[CW == 4 ? r : 0];
+                a.row(rms[r], gv, m0 + r, k, K, vec, avr);
+#pragma unroll
+                for (int cc = 0; cc < CW; ++cc)
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) acc[cc][r] = fmaf(wv[cc][j], avr[j], acc[cc][r]);
+            }
+        }
+        for (int r = 0; r < mm; ++r)
+#pragma unroll
+            for (int cc = 0; cc < CW; cc += Epi::GROUP) {
+                float s[Epi::GROUP];
+#pragma unroll
+                for (int i = 0; i < Epi::GROUP; ++i) s[i] = wave_sum(acc[cc + i][r]);
+                if (lane == 0) e.store(ew, m0 + r, n0 + cc, s);
+            }
+    }
+}
+
+// all-loads-first form for 1-2 rows of 16-bit activations with K <= 512 NC (16-byte aligned rows): a decode step is a chain of such launches
+// and each is as long as its chain of dependent memory round trips -- the chunk loop waits for the loads of one 512-element chunk before it
+// issues the next (fc2 at K = 3072: six round trips in a row).  Here every load of the wave (weights, norm weights, the rows of A) goes out
+// before the first use, and the epilogue's position-only arithmetic (RoPE: powf + sincosf, ~1 us) runs while they are in flight; the
+// arithmetic is the chunk loop's in the same order (same bits).
+template <typename T, int NC, int CW, typename AOp, typename Epi>
+__global__ __launch_bounds__(256, Epi::MIN_BLOCKS) void proj_fast_kernel(const AOp a, const T *__restrict__ W, int M, int N, int K, const Epi e) {
+    const int lane = lane_id();
+    const int n0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * CW;
+    if (n0 >= N) return;
+    u32x4 wr[CW][NC];
+    typename AOp::template Regs<NC> x;
+    bool has[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const int k = lane * 8 + 512 * c;
+        has[c] = k < K;
+        const int kc = min(k, K - 8);
+#pragma unroll
+        for (int cc = 0; cc < CW; ++cc) wr[cc][c] = *(const u32x4 *)(W + (int64_t)min(n0 + cc, N - 1) * K + kc);
+        a.fetch(x, c, kc, M, K);
+    }
+    const typename Epi::Wave ew = e.init(n0);
+    a.rows(x, has, M, K);
+    float acc[CW][2];
+#pragma unroll
+    for (int cc = 0; cc < CW; ++cc) acc[cc][0] = acc[cc][1] = 0.f;
 #pragma unroll
     for (int c = 0; c < NC; ++c)
         if (has[c]) {
-            float u0[8], u1[8], gv[8], xv[8];
-            raw8<T>(u0r[c], u0);
-            raw8<T>(u1r[c], u1);
-            if (norm_w) raw8<T>(gr[c], gv);
+            float wv[CW][8], av[8];
+#pragma unroll
+            for (int cc = 0; cc < CW; ++cc) raw8<T>(wr[cc][c], wv[cc]);
+            a.chunk(x, c);
 #pragma unroll
             for (int r = 0; r < 2; ++r)
                 if (r < M) {
-                    raw8<T>(xr[r][c], xv);
-                    if (norm_w) {
+                    a.row(x, r, c, av);
 #pragma unroll
-                        for (int j = 0; j < 8; ++j) xv[j] = rnd<T>(rnd<T>(xv[j] * rms[r]) * gv[j]);
-                    }
+                    for (int j = 0; j < 8; ++j)
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        a0[r] = fmaf(u0[j], xv[j], a0[r]);
-                        a1[r] = fmaf(u1[j], xv[j], a1[r]);
-                    }
+                        for (int cc = 0; cc < CW; ++cc) acc[cc][r] = fmaf(wv[cc][j], av[j], acc[cc][r]);
                 }
         }
 #pragma unroll
     for (int r = 0; r < 2; ++r)
         if (r < M) {
-            const float x0 = rnd<T>(wave_sum(a0[r])), x1 = rnd<T>(wave_sum(a1[r]));  // the projection output in the activation dtype
-            if (lane == 0) rd.store(r, x0, x1);
+            float s[CW];
+#pragma unroll
+            for (int cc = 0; cc < CW; ++cc) s[cc] = wave_sum(acc[cc][r]);
+            if (lane == 0) e.store(ew, r, n0, s);
         }
 }
 
@@ -895,28 +633,61 @@ __global__ __launch_bounds__(NWV * 64, 2) void linear_mfma_kernel(RopeAppendPara
         for (int r = 0; r < CPT; ++r) {
             if (n0 + CPT * nq + r >= N) break;
             const int64_t idx = (int64_t)m * N + n0 + CPT * nq + r;
-            float y = rnd<T>(v[r]);  // linear_epilogue's steps, the residual from the registers
-            if (epi == 1) y = rnd<T>(y / (1.f + expf(-y)));
-            else if (epi == 2) y = y + resv[r];
-            out[idx] = Elt<T>::from_f(y);
+            out[idx] = Elt<T>::from_f(linear_epilogue<T>(v[r], epi, epi == 2 ? resv[r] : 0.f));  // (the residual from the registers)
         }
     }
+}
+
+// the VALU forms of out = A . W^T (norm_w: RMSNorm(A) folded in)
+static int launch_linear_small_valu(const void *A, const void *W, void *out, int M, int N, int K, int dtype, int epi, const void *res,
+                                    const void *norm_w, float eps, hipStream_t st) {
+    const bool fast = dtype != NSA_DT_F32 && M <= 2 && K >= 8 && K % 8 == 0 && K <= 4096 && (((uintptr_t)A | (uintptr_t)W) % 16 == 0) &&
+                      (!norm_w || (uintptr_t)norm_w % 16 == 0);
+    const int nc = (K + 511) / 512;
+    const bool g4 = fast ? N >= 4096 && nc <= 2 : M <= 2 && N >= 4096;  // four weight rows per wave
+    const dim3 grid(g4 ? (unsigned)((N + 15) / 16) : (unsigned)((N + 3) / 4));
+    with_elt(dtype, [&](auto t) {
+        using T = decltype(t);
+        const RowsA<T> a{(const T *)A, (const T *)norm_w, eps};
+        const LinearEpi<T> e{(T *)out, (const T *)res, epi, N};
+        auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, a, (const T *)W, M, N, K, e); };
+        if constexpr (sizeof(T) == 2) {
+            if (fast) {
+                if (g4) go(proj_fast_kernel<T, 2, 4, RowsA<T>, LinearEpi<T>>);
+                else if (nc <= 2) go(proj_fast_kernel<T, 2, 1, RowsA<T>, LinearEpi<T>>);
+                else if (nc <= 4) go(proj_fast_kernel<T, 4, 1, RowsA<T>, LinearEpi<T>>);
+                else if (nc <= 6) go(proj_fast_kernel<T, 6, 1, RowsA<T>, LinearEpi<T>>);
+                else go(proj_fast_kernel<T, 8, 1, RowsA<T>, LinearEpi<T>>);
+                return;
+            }
+        }
+        if (g4) go(proj_loop_kernel<T, 4, RowsA<T>, LinearEpi<T>>);
+        else go(proj_loop_kernel<T, 1, RowsA<T>, LinearEpi<T>>);
+    });
+    if (fast) NSA_LAUNCH_CHECK("linear_small(fast)");
+    else NSA_LAUNCH_CHECK("linear_small");
+    return NSA_OK;
 }
 
 static bool linear_mfma_ok(int dtype, int M, int N, int K, const void *X, const void *W) {
     return (dtype == NSA_DT_BF16 || dtype == NSA_DT_F16) && M >= 3 && K % 32 == 0 &&
            (((uintptr_t)X | (uintptr_t)W) % 16 == 0);
 }
+template <bool ROPE, bool MIX = false, int NWV = 4>
+static void launch_linear_mfma(const RopeAppendParams &P, const void *X, const void *W, void *out, int M, int N, int K, int dtype, int epi,
+                               const void *res, const LinearMixArgs &mx, hipStream_t st) {
+    const dim3 grid((unsigned)((N + 15) / 16), (unsigned)((M + 63) / 64));
+    with_elt<false>(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((linear_mfma_kernel<T, ROPE, MIX, NWV>), grid, dim3(NWV * 64), 0, st, P, (const T *)X, (const T *)W, (T *)out, M, N, K,
+                           epi, (const T *)res, mx);
+    });
+}
 
 int launch_linear_small_epi(const void *A, const void *W, void *out, int M, int N, int K, int dtype, int epi, const void *res, hipStream_t st) {
     if (linear_mfma_ok(dtype, M, N, K, A, W)) {
-        RopeAppendParams P{};
-        const dim3 g2((unsigned)((N + 15) / 16), (unsigned)((M + 63) / 64));
-        if (K >= 2048) {
-            if (dtype == NSA_DT_BF16) hipLaunchKernelGGL((linear_mfma_kernel<__bf16, false, false, 8>), g2, dim3(512), 0, st, P, (const __bf16 *)A, (const __bf16 *)W, (__bf16 *)out, M, N, K, epi, (const __bf16 *)res, LinearMixArgs{});
-            else hipLaunchKernelGGL((linear_mfma_kernel<_Float16, false, false, 8>), g2, dim3(512), 0, st, P, (const _Float16 *)A, (const _Float16 *)W, (_Float16 *)out, M, N, K, epi, (const _Float16 *)res, LinearMixArgs{});
-        } else if (dtype == NSA_DT_BF16) hipLaunchKernelGGL((linear_mfma_kernel<__bf16, false>), g2, dim3(256), 0, st, P, (const __bf16 *)A, (const __bf16 *)W, (__bf16 *)out, M, N, K, epi, (const __bf16 *)res, LinearMixArgs{});
-        else hipLaunchKernelGGL((linear_mfma_kernel<_Float16, false>), g2, dim3(256), 0, st, P, (const _Float16 *)A, (const _Float16 *)W, (_Float16 *)out, M, N, K, epi, (const _Float16 *)res, LinearMixArgs{});
+        if (K >= 2048) launch_linear_mfma<false, false, 8>({}, A, W, out, M, N, K, dtype, epi, res, {}, st);
+        else launch_linear_mfma<false>({}, A, W, out, M, N, K, dtype, epi, res, {}, st);
         NSA_LAUNCH_CHECK("linear_small(mfma)");
         return NSA_OK;
     }
@@ -929,29 +700,22 @@ bool linear_small_mix_supported(int dtype, int M, int N, int K, int G, const voi
            (((uintptr_t)Oc | (uintptr_t)Os | (uintptr_t)Ow | (uintptr_t)W) % 16 == 0);
 }
 
-// rows 1-2: the VALU dot products of linear_small_kernel; from 3 on: the MFMA kernel (what launch_linear_small_epi picks for a ready-made A)
+// rows 1-2: the VALU dot products (all-loads-first form); from 3 on: the MFMA kernel (what launch_linear_small_epi picks for a ready-made A)
 int launch_linear_small_mix(const void *Oc, const void *Os, const void *Ow, const float *gates, const void *W, void *out, int M, int N, int K, int G,
                             int dtype, int epi, const void *res, hipStream_t st) {
     NSA_CHECK_ARG(linear_small_mix_supported(dtype, M, N, K, G, Oc, Os, Ow, W) && gates && out, "linear_small_mix: unsupported shape");
-    const bool bf = dtype == NSA_DT_BF16;
     if (linear_mfma_ok(dtype, M, N, K, Oc, W)) {
-        const dim3 g2((unsigned)((N + 15) / 16), (unsigned)((M + 63) / 64));
-        const RopeAppendParams P{};
-        const LinearMixArgs mx{Os, Ow, gates, G};
-        if (bf) hipLaunchKernelGGL((linear_mfma_kernel<__bf16, false, true>), g2, dim3(256), 0, st, P, (const __bf16 *)Oc, (const __bf16 *)W, (__bf16 *)out, M, N, K, epi, (const __bf16 *)res, mx);
-        else hipLaunchKernelGGL((linear_mfma_kernel<_Float16, false, true>), g2, dim3(256), 0, st, P, (const _Float16 *)Oc, (const _Float16 *)W, (_Float16 *)out, M, N, K, epi, (const _Float16 *)res, mx);
+        launch_linear_mfma<false, true>({}, Oc, W, out, M, N, K, dtype, epi, res, LinearMixArgs{Os, Ow, gates, G}, st);
     } else {
         NSA_CHECK_ARG(M <= 2 && K <= 2048, "linear_small_mix: the VALU form takes 1-2 rows of at most 2048 elements");
-        const dim3 grid((unsigned)((N + 3) / 4));
-#define NSA_LSM(T_, NC_) hipLaunchKernelGGL((linear_small_mix_kernel<T_, NC_>), grid, dim3(256), 0, st, (const T_ *)Oc, (const T_ *)Os, (const T_ *)Ow, gates, (const T_ *)W, (T_ *)out, M, N, K, G, epi, (const T_ *)res)
-        if (K <= 1024) {
-            if (bf) NSA_LSM(__bf16, 2);
-            else NSA_LSM(_Float16, 2);
-        } else {
-            if (bf) NSA_LSM(__bf16, 4);
-            else NSA_LSM(_Float16, 4);
-        }
-#undef NSA_LSM
+        with_elt<false>(dtype, [&](auto t) {
+            using T = decltype(t);
+            const MixA<T> a{(const T *)Oc, (const T *)Os, (const T *)Ow, gates, G};
+            const LinearEpi<T> e{(T *)out, (const T *)res, epi, N};
+            auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, a, (const T *)W, M, N, K, e); };
+            if (K <= 1024) go(proj_fast_kernel<T, 2, 1, MixA<T>, LinearEpi<T>>);
+            else go(proj_fast_kernel<T, 4, 1, MixA<T>, LinearEpi<T>>);
+        });
     }
     NSA_LAUNCH_CHECK("linear_small_mix");
     return NSA_OK;
@@ -975,30 +739,28 @@ int launch_qkv_rope_append(const RopeAppendParams &P, const void *X, const void 
     const int NT = P.G * P.h * P.Dk + 3 * P.G * P.Dk + 3 * P.G * P.Dv;
     if (linear_mfma_ok(dtype, P.B, NT, K, X, W)) {
         NSA_CHECK_ARG(norm_w == nullptr, "qkv_rope_append: the MFMA form takes normalised input");
-        const dim3 g2((unsigned)((NT + 15) / 16), (unsigned)((P.B + 63) / 64));
-        if (dtype == NSA_DT_BF16) hipLaunchKernelGGL((linear_mfma_kernel<__bf16, true>), g2, dim3(256), 0, st, P, (const __bf16 *)X, (const __bf16 *)W, (__bf16 *)nullptr, P.B, NT, K, 0, (const __bf16 *)nullptr, LinearMixArgs{});
-        else hipLaunchKernelGGL((linear_mfma_kernel<_Float16, true>), g2, dim3(256), 0, st, P, (const _Float16 *)X, (const _Float16 *)W, (_Float16 *)nullptr, P.B, NT, K, 0, (const _Float16 *)nullptr, LinearMixArgs{});
+        launch_linear_mfma<true>(P, X, W, nullptr, P.B, NT, K, dtype, 0, nullptr, {}, st);
         NSA_LAUNCH_CHECK("qkv_rope_append(mfma)");
         return NSA_OK;
     }
-    const dim3 grid((unsigned)((NT / 2 + 3) / 4)), block(256);
-    if (dtype != NSA_DT_F32 && P.B <= 2 && P.S == 1 && K >= 8 && K % 8 == 0 && K <= 2048 && (((uintptr_t)X | (uintptr_t)W) % 16 == 0) &&
-        (!norm_w || (uintptr_t)norm_w % 16 == 0)) {
-        const bool bf = dtype == NSA_DT_BF16;
-        if (K <= 1024) {
-            if (bf) hipLaunchKernelGGL((qkv_rope_append_fast_kernel<__bf16, 2>), grid, block, 0, st, P, (const __bf16 *)X, (const __bf16 *)W, K, (const __bf16 *)norm_w, norm_eps);
-            else hipLaunchKernelGGL((qkv_rope_append_fast_kernel<_Float16, 2>), grid, block, 0, st, P, (const _Float16 *)X, (const _Float16 *)W, K, (const _Float16 *)norm_w, norm_eps);
-        } else {
-            if (bf) hipLaunchKernelGGL((qkv_rope_append_fast_kernel<__bf16, 4>), grid, block, 0, st, P, (const __bf16 *)X, (const __bf16 *)W, K, (const __bf16 *)norm_w, norm_eps);
-            else hipLaunchKernelGGL((qkv_rope_append_fast_kernel<_Float16, 4>), grid, block, 0, st, P, (const _Float16 *)X, (const _Float16 *)W, K, (const _Float16 *)norm_w, norm_eps);
+    const bool fast = dtype != NSA_DT_F32 && P.B <= 2 && P.S == 1 && K >= 8 && K % 8 == 0 && K <= 2048 &&
+                      (((uintptr_t)X | (uintptr_t)W) % 16 == 0) && (!norm_w || (uintptr_t)norm_w % 16 == 0);
+    with_elt(dtype, [&](auto t) {
+        using T = decltype(t);
+        const RowsA<T> a{(const T *)X, (const T *)norm_w, norm_eps};
+        const RopeEpi<T> e{P};
+        auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)((NT / 2 + 3) / 4)), dim3(256), 0, st, a, (const T *)W, P.B, NT, K, e); };
+        if constexpr (sizeof(T) == 2) {
+            if (fast) {
+                if (K <= 1024) go(proj_fast_kernel<T, 2, 2, RowsA<T>, RopeEpi<T>>);
+                else go(proj_fast_kernel<T, 4, 2, RowsA<T>, RopeEpi<T>>);
+                return;
+            }
         }
-        NSA_LAUNCH_CHECK("qkv_rope_append(fast)");
-        return NSA_OK;
-    }
-    if (dtype == NSA_DT_F32) hipLaunchKernelGGL(qkv_rope_append_kernel<float>, grid, block, 0, st, P, (const float *)X, (const float *)W, K, (const float *)norm_w, norm_eps);
-    else if (dtype == NSA_DT_BF16) hipLaunchKernelGGL(qkv_rope_append_kernel<__bf16>, grid, block, 0, st, P, (const __bf16 *)X, (const __bf16 *)W, K, (const __bf16 *)norm_w, norm_eps);
-    else hipLaunchKernelGGL(qkv_rope_append_kernel<_Float16>, grid, block, 0, st, P, (const _Float16 *)X, (const _Float16 *)W, K, (const _Float16 *)norm_w, norm_eps);
-    NSA_LAUNCH_CHECK("qkv_rope_append");
+        go(proj_loop_kernel<T, 2, RowsA<T>, RopeEpi<T>>);
+    });
+    if (fast) NSA_LAUNCH_CHECK("qkv_rope_append(fast)");
+    else NSA_LAUNCH_CHECK("qkv_rope_append");
     return NSA_OK;
 }
 
@@ -1104,15 +866,11 @@ int launch_cmp_pool(const CmpPoolParams &P, int dtype, hipStream_t st) {
     // (a prefill pools thousands of tokens: there the 64-thread form's many small blocks fill the chip better; the wide form is for the few
     // tokens of a decode step, where the length of one block's chain is the kernel's time)
     if (lds <= 48 * 1024 && P.Dk % 2 == 0 && nblk <= 1024) {
-        if (dtype == NSA_DT_F32) hipLaunchKernelGGL(cmp_pool_wide_kernel<float>, dim3((unsigned)nblk), dim3(256), lds, st, P);
-        else if (dtype == NSA_DT_BF16) hipLaunchKernelGGL(cmp_pool_wide_kernel<__bf16>, dim3((unsigned)nblk), dim3(256), lds, st, P);
-        else hipLaunchKernelGGL(cmp_pool_wide_kernel<_Float16>, dim3((unsigned)nblk), dim3(256), lds, st, P);
+        with_elt(dtype, [&](auto t) { hipLaunchKernelGGL(cmp_pool_wide_kernel<decltype(t)>, dim3((unsigned)nblk), dim3(256), lds, st, P); });
         NSA_LAUNCH_CHECK("cmp_pool(wide)");
         return NSA_OK;
     }
-    if (dtype == NSA_DT_F32) hipLaunchKernelGGL(cmp_pool_kernel<float>, dim3((unsigned)nblk), dim3(64), 0, st, P);
-    else if (dtype == NSA_DT_BF16) hipLaunchKernelGGL(cmp_pool_kernel<__bf16>, dim3((unsigned)nblk), dim3(64), 0, st, P);
-    else hipLaunchKernelGGL(cmp_pool_kernel<_Float16>, dim3((unsigned)nblk), dim3(64), 0, st, P);
+    with_elt(dtype, [&](auto t) { hipLaunchKernelGGL(cmp_pool_kernel<decltype(t)>, dim3((unsigned)nblk), dim3(64), 0, st, P); });
     NSA_LAUNCH_CHECK("cmp_pool");
     return NSA_OK;
 }
@@ -1162,9 +920,10 @@ int launch_cmp_pool_bwd(const CmpPoolParams &P, const void *dKc, const void *dVc
     const int64_t nblk = (int64_t)P.nbg * S;
     if (nblk <= 0) return NSA_OK;
     NSA_CHECK_ARG(nblk < ((int64_t)1 << 31), "cmp_pool_bwd: too many blocks");
-    if (dtype == NSA_DT_F32) hipLaunchKernelGGL(cmp_pool_bwd_kernel<float>, dim3((unsigned)nblk), dim3(64), 0, st, P, (const float *)dKc, (const float *)dVc, (float *)dKr, (float *)dVr, S, n_cmp);
-    else if (dtype == NSA_DT_BF16) hipLaunchKernelGGL(cmp_pool_bwd_kernel<__bf16>, dim3((unsigned)nblk), dim3(64), 0, st, P, (const __bf16 *)dKc, (const __bf16 *)dVc, (__bf16 *)dKr, (__bf16 *)dVr, S, n_cmp);
-    else hipLaunchKernelGGL(cmp_pool_bwd_kernel<_Float16>, dim3((unsigned)nblk), dim3(64), 0, st, P, (const _Float16 *)dKc, (const _Float16 *)dVc, (_Float16 *)dKr, (_Float16 *)dVr, S, n_cmp);
+    with_elt(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(cmp_pool_bwd_kernel<T>, dim3((unsigned)nblk), dim3(64), 0, st, P, (const T *)dKc, (const T *)dVc, (T *)dKr, (T *)dVr, S, n_cmp);
+    });
     NSA_LAUNCH_CHECK("cmp_pool_bwd");
     return NSA_OK;
 }
@@ -1210,9 +969,7 @@ __global__ __launch_bounds__(256) void rmsnorm_rows_kernel(const T *__restrict__
         const float v = Elt<T>::to_f(xr[i]);
         acc += rnd<T>(v * v);
     }
-    float r = rnd<T>(wave_sum(acc) / (float)dim);
-    r = rnd<T>(r + eps);
-    r = rnd<T>(1.0f / sqrtf(r));
+    const float r = rms_finish<T>(acc, dim, eps);
     for (int i = lane; i < dim; i += 64) yr[i] = Elt<T>::from_f(rnd<T>(Elt<T>::to_f(xr[i]) * r) * Elt<T>::to_f(w[i]));
 }
 
@@ -1220,9 +977,10 @@ int launch_rmsnorm_rows(const void *x, const void *w, void *y, int M, int dim, f
     if (M == 0) return NSA_OK;
     const dim3 grid((unsigned)((M + 3) / 4)), block(256);
     const int vec = dim % 8 == 0 && (uintptr_t)x % 16 == 0 && (uintptr_t)w % 16 == 0 && (uintptr_t)y % 16 == 0;
-    if (dtype == NSA_DT_F32) hipLaunchKernelGGL(rmsnorm_rows_kernel<float>, grid, block, 0, st, (const float *)x, (const float *)w, (float *)y, M, dim, eps, vec);
-    else if (dtype == NSA_DT_BF16) hipLaunchKernelGGL(rmsnorm_rows_kernel<__bf16>, grid, block, 0, st, (const __bf16 *)x, (const __bf16 *)w, (__bf16 *)y, M, dim, eps, vec);
-    else hipLaunchKernelGGL(rmsnorm_rows_kernel<_Float16>, grid, block, 0, st, (const _Float16 *)x, (const _Float16 *)w, (_Float16 *)y, M, dim, eps, vec);
+    with_elt(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(rmsnorm_rows_kernel<T>, grid, block, 0, st, (const T *)x, (const T *)w, (T *)y, M, dim, eps, vec);
+    });
     NSA_LAUNCH_CHECK("rmsnorm_rows");
     return NSA_OK;
 }
@@ -1338,9 +1096,9 @@ int launch_rmsnorm_rows_bwd(const void *x, const void *w, const void *dy, void *
                   "rmsnorm_rows_bwd: 16-byte aligned tensors required");
     NSA_CHECK_ARG(workspace && workspace_bytes >= rmsnorm_rows_bwd_workspace(M, dim) && (uintptr_t)workspace % 16 == 0,
                   "rmsnorm_rows_bwd: workspace too small");
-    if (dtype == NSA_DT_F32) return launch_rmsnorm_bwd_t<float>(x, w, dy, dx, dw, M, dim, eps, (float *)workspace, st);
-    if (dtype == NSA_DT_BF16) return launch_rmsnorm_bwd_t<__bf16>(x, w, dy, dx, dw, M, dim, eps, (float *)workspace, st);
-    return launch_rmsnorm_bwd_t<_Float16>(x, w, dy, dx, dw, M, dim, eps, (float *)workspace, st);
+    int rc = NSA_OK;
+    with_elt(dtype, [&](auto t) { rc = launch_rmsnorm_bwd_t<decltype(t)>(x, w, dy, dx, dw, M, dim, eps, (float *)workspace, st); });
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------------ gate MLP + combine
@@ -1433,9 +1191,10 @@ int launch_gate_combine_bwd(const GateCombineParams &P, const void *dO, const fl
                             int dtype, hipStream_t st) {
     if (P.R == 0) return NSA_OK;
     const dim3 grid((unsigned)((P.R + 3) / 4)), block(256);
-    if (dtype == NSA_DT_F32) hipLaunchKernelGGL(gate_combine_bwd_kernel<float>, grid, block, 0, st, P, (const float *)dO, gates, (float *)dOc, (float *)dOs, (float *)dOw, dgates);
-    else if (dtype == NSA_DT_BF16) hipLaunchKernelGGL(gate_combine_bwd_kernel<__bf16>, grid, block, 0, st, P, (const __bf16 *)dO, gates, (__bf16 *)dOc, (__bf16 *)dOs, (__bf16 *)dOw, dgates);
-    else hipLaunchKernelGGL(gate_combine_bwd_kernel<_Float16>, grid, block, 0, st, P, (const _Float16 *)dO, gates, (_Float16 *)dOc, (_Float16 *)dOs, (_Float16 *)dOw, dgates);
+    with_elt(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(gate_combine_bwd_kernel<T>, grid, block, 0, st, P, (const T *)dO, gates, (T *)dOc, (T *)dOs, (T *)dOw, dgates);
+    });
     NSA_LAUNCH_CHECK("gate_combine_bwd");
     return NSA_OK;
 }
@@ -1494,9 +1253,9 @@ int launch_decode_finish(const DecodeFinishParams &P, int dtype, hipStream_t st)
     NSA_CHECK_ARG(P.Dv == 64 && P.Dk <= 256 && P.Hd >= 1 && P.Hd <= 64, "decode_finish: Dv = 64, Dk <= 256, hidden <= 64 supported");
     for (int i = 0; i < 3; ++i) NSA_CHECK_ARG(P.ns[i] >= 1 && P.ns[i] <= 16 && (P.ns[i] == 1 ? P.O[i] != nullptr : P.part[i] != nullptr), "decode_finish: bad branch input");
     const dim3 grid((unsigned)((P.R * P.h + 3) / 4)), block(256);
-    if (dtype == NSA_DT_BF16) hipLaunchKernelGGL(decode_finish_kernel<__bf16>, grid, block, 0, st, P);
-    else if (dtype == NSA_DT_F16) hipLaunchKernelGGL(decode_finish_kernel<_Float16>, grid, block, 0, st, P);
-    else hipLaunchKernelGGL(decode_finish_kernel<float>, grid, block, 0, st, P);
+    // (anything that is not a 16-bit dtype takes the fp32 kernel here)
+    with_elt(dtype == NSA_DT_BF16 || dtype == NSA_DT_F16 ? dtype : NSA_DT_F32,
+             [&](auto t) { hipLaunchKernelGGL(decode_finish_kernel<decltype(t)>, grid, block, 0, st, P); });
     NSA_LAUNCH_CHECK("decode_finish");
     return NSA_OK;
 }
@@ -1505,9 +1264,7 @@ int launch_gate_combine(const GateCombineParams &P, int dtype, hipStream_t st) {
     if (P.R == 0) return NSA_OK;
     NSA_CHECK_ARG(P.Dk <= 256 && P.Hd >= 1 && P.Hd <= 64, "gate_combine: Dk <= 256 and 1 <= hidden <= 64 supported");
     const dim3 grid((unsigned)((P.R + 3) / 4)), block(256);
-    if (dtype == NSA_DT_F32) hipLaunchKernelGGL(gate_combine_kernel<float>, grid, block, 0, st, P);
-    else if (dtype == NSA_DT_BF16) hipLaunchKernelGGL(gate_combine_kernel<__bf16>, grid, block, 0, st, P);
-    else hipLaunchKernelGGL(gate_combine_kernel<_Float16>, grid, block, 0, st, P);
+    with_elt(dtype, [&](auto t) { hipLaunchKernelGGL(gate_combine_kernel<decltype(t)>, grid, block, 0, st, P); });
     NSA_LAUNCH_CHECK("gate_combine");
     return NSA_OK;
 }
@@ -1523,9 +1280,10 @@ __global__ __launch_bounds__(256) void embed_rows_kernel(const int32_t *__restri
 }
 int launch_embed_rows(const int32_t *tokens, const void *embed, void *x, int B, int dim, int vocab, int dtype, hipStream_t st) {
     if (B == 0) return NSA_OK;
-    if (dtype == NSA_DT_F32) hipLaunchKernelGGL(embed_rows_kernel<float>, dim3(B), dim3(256), 0, st, tokens, (const float *)embed, (float *)x, B, dim, vocab);
-    else if (dtype == NSA_DT_BF16) hipLaunchKernelGGL(embed_rows_kernel<__bf16>, dim3(B), dim3(256), 0, st, tokens, (const __bf16 *)embed, (__bf16 *)x, B, dim, vocab);
-    else hipLaunchKernelGGL(embed_rows_kernel<_Float16>, dim3(B), dim3(256), 0, st, tokens, (const _Float16 *)embed, (_Float16 *)x, B, dim, vocab);
+    with_elt(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(embed_rows_kernel<T>, dim3(B), dim3(256), 0, st, tokens, (const T *)embed, (T *)x, B, dim, vocab);
+    });
     NSA_LAUNCH_CHECK("embed_rows");
     return NSA_OK;
 }
@@ -1596,9 +1354,7 @@ int launch_argmax_rows(const void *logits, int32_t *next, int B, int vocab, int 
     float *pv = (float *)ws;
     int32_t *pi = (int32_t *)(pv + (size_t)B * nchunk);
     const dim3 grid((unsigned)nchunk, (unsigned)B);
-    if (dtype == NSA_DT_F32) hipLaunchKernelGGL(argmax_part_kernel<float>, grid, dim3(256), 0, st, (const float *)logits, pv, pi, vocab);
-    else if (dtype == NSA_DT_BF16) hipLaunchKernelGGL(argmax_part_kernel<__bf16>, grid, dim3(256), 0, st, (const __bf16 *)logits, pv, pi, vocab);
-    else hipLaunchKernelGGL(argmax_part_kernel<_Float16>, grid, dim3(256), 0, st, (const _Float16 *)logits, pv, pi, vocab);
+    with_elt(dtype, [&](auto t) { hipLaunchKernelGGL(argmax_part_kernel<decltype(t)>, grid, dim3(256), 0, st, (const decltype(t) *)logits, pv, pi, vocab); });
     NSA_LAUNCH_CHECK("argmax_part");
     hipLaunchKernelGGL(argmax_final_kernel, dim3(B), dim3(64), 0, st, (const float *)pv, (const int32_t *)pi, next, nchunk);
     NSA_LAUNCH_CHECK("argmax_final");

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""few-row projections of the decode step (nsa_linear_small), per shape: python3 tools/bench_linear_small.py [M ...]"""
+"""few-row projections of the decode step (nsa_linear_small), per shape: python3 tools/bench_linear_small.py [--unaligned] [M ...]
+(--unaligned: A starts 2 bytes off a 16-byte boundary, which sends 1-2 rows to the chunk-loop kernels)"""
 import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from nsa_vibe_amd import _lib
 from nsa_vibe_amd.selection_scorer import _DT, _stream
 dev = torch.device("cuda")
-Ms = [int(a) for a in sys.argv[1:]] or [1, 2, 8, 32, 64, 256]
+OFF = 1 if "--unaligned" in sys.argv[1:] else 0
+Ms = [int(a) for a in sys.argv[1:] if a != "--unaligned"] or [1, 2, 8, 32, 64, 256]
 shapes = [("fc1", 3072, 768, 1), ("fc2", 768, 3072, 2), ("out", 768, 768, 2), ("head", 50257, 768, 0)]
 L = _lib.lib()
 for M in Ms:
@@ -14,7 +16,7 @@ for M in Ms:
         # rotate over enough weight copies that every call reads its weights from beyond the caches (a 12-block model does)
         ncopy = max(2, int(600e6 // (N * K * 2)))
         Ws = [(torch.randn(N, K, device=dev) / K ** 0.5).bfloat16() for _ in range(ncopy)]
-        A = torch.randn(M, K, device=dev).bfloat16()
+        A = torch.randn(M * K + 8, device=dev).bfloat16()[OFF: OFF + M * K].view(M, K)
         res = torch.randn(M, N, device=dev).bfloat16()
         out = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
         st = _stream(dev)
