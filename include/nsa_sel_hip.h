@@ -435,6 +435,41 @@ NSA_API int nsa_sel_decode_step(const void *Q, const void *K_cmp, const void *K,
 NSA_API int nsa_sel_decode_step_plan(int B, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int n_top, int dtype,
                              int *launches /* host */, int *form /* host */, int *nsplit /* host */);
 
+/* ---------------------------------------------------------------------------------------
+ * The decode step of the selected branch for S CONSECUTIVE tokens per sequence in one call (k draft tokens to verify, the tail of a chunked
+ * prefill): the cache already holds the S new tokens, row (b,s,g) sits at token t = t0 + s and computes what nsa_sel_decode_step computes at
+ * t on the cache truncated to t + 1 tokens:
+ *   it sees the first n_cmp(t) = (t + 1 < l) ? 0 : (t + 1 - l) / d + 1 rows of K_cmp[b,g] (clamped to S_cmp) and normalises its compressed
+ *   scores over those columns alone (the decode semantics of nsa_sel_scores_rows(q0 = t0, norm = 1)), selects sequentially at t with the
+ *   forced initial and local blocks, and attends K/V[b,g,:t+1].
+ *   Q [B,S,G,h,Dk], O [B,S,G,h,Dv], ranges_out [B,S,G,n_top,2] int32; K_cmp / K / V and their strides as in nsa_sel_decode_step.
+ *   S_cmp, S_sel, S_kv describe the cache AFTER the S tokens were appended (the block meta of t0 + S tokens); S_kv >= t0 + S.
+ * This is not a ragged-batch step: there is no array of positions, every row's bounds follow from its index, S and t0.
+ * Kernel form: ONE launch -- the decode step's kernel with one workgroup per row, each deriving its own token, compressed rows and chunks
+ * from the row index -- on the unsplit exact forms only: logits in registers (two chunks of 64 compressed rows per wave, 8 or 16 waves by
+ * B*S*G) at Dk = Dv in {64, 128}, four chunks per wave at 64 where the LARGEST row (t0 + S - 1) exceeds that, whatever DECODE_WIDE says;
+ * no team of workgroups, no one-pass form, no band workgroups.  Ranges and O have the bits of S nsa_sel_decode_step calls that run the
+ * same number of waves per row (sel_attn_decode.hpp: 16 up to 256 rows per launch at D = 64, else 8); ranges are theirs bit for bit always.
+ * Everywhere else -- another block geometry than l = 2d, l' = 4d = 64, n_cmp(t0) < 1, S > 16, other dtypes, a largest row beyond the unsplit
+ * forms (more than 64 / 32 / 16 chunks at 16 waves / 8 waves / D = 128), DECODE_UNFUSED = 1, unaligned inputs -- the call runs the separate
+ * launches: nsa_sel_scores_select_rows(q0 = t0, norm = 1, sequential) then nsa_sel_attn_fwd (same ranges; O within the rounding of the
+ * attention kernel forms).  Tuning switch "DECODE_ROWS": 1 = the one-launch form wherever it applies, 0 = never, -1 (default) = in the
+ * (S, context) cells where it was measured not slower than both S single steps and the separate launches (DESIGN.md 4.1f has the table: every measured cell except S = 1 on rows of 32 chunks and more; cells
+ * where it loses default to the separate launches).
+ * nsa_sel_decode_rows_plan reports the route for a cache that holds exactly t0 + S tokens (t0 = S_kv - S), default geometry and aligned
+ * inputs assumed: *launches = 1 and *form = 0 / 1 for the one-launch form, else *launches > 1 (an estimate) and *form = -1.
+ * workspace: nsa_sel_decode_rows_workspace() bytes, 16-byte aligned (the scratch of the separate launches; the one-launch form uses none).
+ * ------------------------------------------------------------------------------------- */
+NSA_API size_t nsa_sel_decode_rows_workspace(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int n_top, int dtype);
+NSA_API int nsa_sel_decode_rows(const void *Q, const void *K_cmp, const void *K, const void *V, const int32_t *csc_ptr,
+                        const int32_t *csc_rows, const float *csc_vals, int32_t *ranges_out, void *O, int B, int S, int G, int h,
+                        int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int l, int d, int l_sel, int n_top, int t0,
+                        int64_t kc_stride_b, int64_t kc_stride_g, int64_t kc_stride_s, int64_t k_stride_b,
+                        int64_t k_stride_g, int64_t k_stride_s, int64_t v_stride_b, int64_t v_stride_g,
+                        int64_t v_stride_s, int dtype, float scale, void *workspace, size_t workspace_bytes, void *stream);
+NSA_API int nsa_sel_decode_rows_plan(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int n_top, int dtype,
+                             int *launches /* host */, int *form /* host */);
+
 /* indices [R,K] int32 ascending with -1 padding -> ranges [R,K,2]; clamp end to t+1. */
 NSA_API int nsa_indices_to_ranges_v2(const int32_t *indices, int64_t R, int S, int G, int t0, int K, int S_sel,
                              int l_sel, int32_t *ranges_out, void *stream);

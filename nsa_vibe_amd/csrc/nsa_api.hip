@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include <strings.h>
 
+#include <algorithm>
 #include <atomic>
 #include <mutex>
 #include <vector>
@@ -687,6 +688,68 @@ int nsa_sel_decode_step_plan(int B, int G, int h, int Dk, int Dv, int S_cmp, int
         n += ns > 1 ? 2 : 1;
     }
     *launches = n;
+    return NSA_OK;
+}
+
+// ------------------------------------------------------------------------------ decode step for S consecutive tokens
+// workspace: scorer scratch (a) | p_grp (p) | attention scratch (c) of the separate launches; the one-launch form needs none
+struct SelDecodeRowsWs {
+    size_t a, p, c;
+    SelDecodeRowsWs(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int n_top, int dtype)
+        : a(align16(std::max(nsa_sel_scores_rows_workspace(B, S, G, h, Dk, S_cmp, S_sel, 0, 0, 0, dtype, 1, 1),
+                             S_cmp >= 1 ? nsa_sel_scores_rows_workspace(B, S, G, h, Dk, S_cmp, S_sel, 0, 0, 0, dtype, 3, 1) : (size_t)0))),
+          p(align16(sizeof(float) * (size_t)B * S * G * (size_t)(S_sel > 0 ? S_sel : 1))),
+          c(align16(nsa_sel_attn_fwd_workspace_kv(B, S, G, h, Dk, Dv, 64 * (S_sel > 0 ? S_sel : 1), n_top, dtype))) {}
+    size_t total() const { return a + p + c; }
+};
+
+size_t nsa_sel_decode_rows_workspace(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int n_top, int dtype) {
+    if (B < 1 || S < 1 || G < 1 || h < 1) return 0;
+    return SelDecodeRowsWs(B, S, G, h, Dk, Dv, S_cmp, S_sel, n_top, dtype).total();
+}
+
+int nsa_sel_decode_rows(const void *Q, const void *K_cmp, const void *K, const void *V, const int32_t *csc_ptr, const int32_t *csc_rows,
+                        const float *csc_vals, int32_t *ranges_out, void *O, int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel,
+                        int S_kv, int l, int d, int l_sel, int n_top, int t0, int64_t kcb, int64_t kcg, int64_t kcs, int64_t ksb, int64_t ksg,
+                        int64_t kss, int64_t vsb, int64_t vsg, int64_t vss, int dtype, float scale, void *workspace, size_t workspace_bytes,
+                        void *stream) {
+    NSA_CHECK_ARG(dtype_ok(dtype), "decode_rows: unknown dtype %d", dtype);
+    NSA_CHECK_ARG(B >= 0 && S >= 0 && G >= 1 && h >= 1 && Dk >= 1 && Dv >= 1 && S_cmp >= 0 && S_sel >= 1 && S_kv >= 1, "decode_rows: bad sizes");
+    NSA_CHECK_ARG(n_top >= 1 && n_top <= 64, "decode_rows: n_top must be in [1,64]");
+    NSA_CHECK_ARG(t0 >= 0 && S_kv >= t0 + S, "decode_rows: the cache must hold the S tokens t0 .. t0 + S - 1");
+    if ((int64_t)B * S * G == 0) return NSA_OK;
+    NSA_CHECK_ARG(Q && K && V && O && ranges_out, "decode_rows: null pointer");
+    if (decode_rows_supported(B, S, G, dtype, h, Dk, Dv, S_cmp, S_sel, S_kv, l, d, l_sel, n_top, t0, kcb, kcg, kcs, ksb, ksg, kss, vsb, vsg, vss, Q,
+                              K_cmp, K, V))  // every row's scores -> top-n at its own token -> selection attention over K/V[:t + 1]: ONE launch
+        return launch_decode_rows(Q, K_cmp, K, V, O, ranges_out, B, S, G, h, S_cmp, S_sel, S_kv, n_top, t0, kcb, kcg, kcs, ksb, ksg, kss, vsb, vsg,
+                                  vss, dtype, default_scale(scale, Dk), (hipStream_t)stream, Dk);
+    // the separate launches: decode-normalised scores + sequential top-n at t0 + s, then the attention (what an extend of S tokens runs)
+    const SelDecodeRowsWs W(B, S, G, h, Dk, Dv, S_cmp, S_sel, n_top, dtype);
+    NSA_CHECK_ARG(workspace && ((uintptr_t)workspace % 16 == 0) && workspace_bytes >= W.total(), "decode_rows: workspace missing, misaligned or too small");
+    unsigned char *w = (unsigned char *)workspace;
+    if (int rc = nsa_sel_scores_select_rows(Q, K_cmp, (float *)(w + W.a), B, S, G, h, Dk, S_cmp, kcb, kcg, kcs, csc_ptr, csc_rows, csc_vals, S_sel, l, d,
+                                            l_sel, 2 /* skipped blocks stay unwritten: only the selector reads p_grp */, dtype, scale, t0, n_top, 1, 2,
+                                            NSA_SEL_SEQUENTIAL, S, ranges_out, n_top, t0, 1, w, W.a, stream))
+        return rc;
+    return nsa_sel_attn_fwd(Q, K, V, ranges_out, O, nullptr, B, S, G, h, Dk, Dv, S_kv, n_top, ksb, ksg, kss, vsb, vsg, vss, dtype, scale, 0,
+                            w + W.a + W.p, workspace_bytes - W.a - W.p, stream);
+}
+
+// the plan of nsa_sel_decode_rows for a cache that holds exactly the S new tokens behind t0 = S_kv - S (default block geometry, aligned inputs)
+int nsa_sel_decode_rows_plan(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int n_top, int dtype, int *launches,
+                             int *form) {
+    NSA_CHECK_ARG(launches && form, "decode_rows_plan: null pointer");
+    NSA_CHECK_ARG(dtype_ok(dtype), "decode_rows_plan: unknown dtype %d", dtype);
+    NSA_CHECK_ARG(B >= 1 && S >= 1 && G >= 1 && h >= 1 && Dk >= 1 && Dv >= 1 && S_cmp >= 0 && S_sel >= 1 && S_kv >= S && n_top >= 1 && n_top <= 64,
+                  "decode_rows_plan: bad sizes");
+    if (decode_rows_shape_plan(B, S, G, dtype, h, Dk, Dv, S_cmp, S_sel, S_kv, n_top, S_kv - S, form, nullptr)) {
+        *launches = 1;
+        return NSA_OK;
+    }
+    // separate launches: the scorer (the decode-shaped pair, or one launch of the tiled / generic scorer), the select kernel, the attention
+    // (a combine launch more where it splits the keys): an estimate, only "> 1" is contractual
+    const int route = scores_route(B, S, G, h, Dk, S_cmp, S_sel, 32, 16, 64, dtype, 0, 1);
+    *launches = (route == 3 ? 2 : 1) + 1 + 1;
     return NSA_OK;
 }
 

@@ -42,6 +42,15 @@ int launch_decode_step(const void *Q, const void *Kc, const void *K, const void 
                        const DecBandPair *band = nullptr, int D = 64);
 // shape / tuning part of decode_step_supported (default block geometry): false = declined (form -1, nsplit 0)
 bool decode_step_shape_plan(int64_t R, int dtype, int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int n_top, int *form, int *nsplit);
+// rows form of the one-launch step (nsa_sel_decode_rows): S consecutive tokens per sequence at t0 .. t0 + S - 1, one workgroup per row
+bool decode_rows_shape_plan(int B, int S, int G, int dtype, int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int n_top, int t0, int *form,
+                            int *nw_out);
+bool decode_rows_supported(int B, int S, int G, int dtype, int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int l, int d, int l_sel, int n_top,
+                           int t0, int64_t kcb, int64_t kcg, int64_t kcs, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg,
+                           int64_t vss, const void *Q, const void *Kc, const void *K, const void *V);
+int launch_decode_rows(const void *Q, const void *Kc, const void *K, const void *V, void *O, int32_t *ranges_out, int B, int S, int G, int h,
+                       int S_cmp, int S_sel, int S_kv, int n_top, int t0, int64_t kcb, int64_t kcg, int64_t kcs, int64_t ksb, int64_t ksg, int64_t kss,
+                       int64_t vsb, int64_t vsg, int64_t vss, int dtype, float scale, hipStream_t st, int D);
 // shape / tuning part of decode_score_select_supported
 bool decode_score_select_shape_ok(int dtype, int h, int Dk, int S_cmp, int S_sel, int64_t rows);
 

@@ -96,7 +96,8 @@ __device__ __forceinline__ int dec_next_chunk(int cur, int w, int NC) {
 }
 
 // a chunk fetched ahead of time (fused decode step): K rows by LDS-DMA into an 8 KiB tile of their own (XOR-swizzled 16-B pieces, the
-// image of sel_attn_blocks_mfma.hip), V rows into the wave's V tile as always.  Needs contiguous K rows (kss = 64).
+// image of sel_attn_blocks_mfma.hip), V rows into the wave's V tile as always.  Needs contiguous K rows (kss = 64).  `row` only names the
+// K/V plane (b = row / G, g = row % G): the rows form of the decode step, whose rows are (b, s, g), passes b G + g.
 struct DecPrefetch {
     int tok0;                    // first key of the chunk the wave fetched, -1 = none
     const unsigned char *ktile;  // its K image in LDS
@@ -136,9 +137,12 @@ __device__ __forceinline__ void decode_prefetch_chunk(const DecAttnArgs &A, int6
 // vt: NW * dec_att_tile(D) bytes of LDS, 16-byte aligned (V tiles, then the partial records); every thread of the NW * 64-thread workgroup must
 // call (one workgroup barrier inside).  qf_in: the row's Q^T fragments if the caller holds them already (lane (rho, q):
 // Q[head min(rho, h-1)][32 s + 8 q ..], s = 0, 1).  NC chunks; chunks with len <= 0 must not occur.
+// kv_row >= 0: the K/V plane of the row is (kv_row / G, kv_row % G) instead of (row / G, row % G) -- several query rows per (b, g), the
+// rows form of the decode step; Q and O stay indexed by `row`.
 template <typename T, int NW, typename CH, int D = 64>
 __device__ __forceinline__ void decode_attend_chunks(const DecAttnArgs &A, int64_t row, const CH &ch, const int NC, unsigned char *vt,
-                                                     const typename MfmaT<T>::x8 *qf_in = nullptr, const DecPrefetch pre = DecPrefetch{-1, nullptr}) {
+                                                     const typename MfmaT<T>::x8 *qf_in = nullptr, const DecPrefetch pre = DecPrefetch{-1, nullptr},
+                                                     const int64_t kv_row = -1) {
     using M = MfmaT<T>;
     using x8 = typename M::x8;
     using x4 = typename M::x4;
@@ -153,8 +157,9 @@ __device__ __forceinline__ void decode_attend_chunks(const DecAttnArgs &A, int64
     const int wave = uniform((int)(threadIdx.x >> 6));
     const int rho = lane & 15, q = lane >> 4;
     const int h = A.h;
-    const int g = (int)(row % A.G);
-    const int64_t b = row / A.G;
+    const int64_t kvr = kv_row < 0 ? row : kv_row;
+    const int g = (int)(kvr % A.G);
+    const int64_t b = kvr / A.G;
     unsigned char *vl = vt + wave * TILE;
 
     // Q^T fragments (B operand): column = head (columns >= h repeat the last head: their results are never stored)

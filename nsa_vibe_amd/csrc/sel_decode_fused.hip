@@ -20,6 +20,16 @@
 //     while later rows still sweep, which is the overlap the single-workgroup form cannot have at 64k.
 // Results: ranges identical, O bit-identical to the three separate launches (tests: test_fused_decode_step,
 // test_fused_decode_scorer_equals_three_kernel_route).
+// Rows form (template flag ROWS; nsa_sel_decode_rows): S consecutive tokens per sequence at t0 .. t0 + S - 1 in one launch, on the cache
+// that already holds them ("k draft tokens to verify", speculative-verify rows, the tail of a chunked prefill -- cases that otherwise take
+// the extend route's three or more launches).  One workgroup is one row (b, s, g); only the row's bounds and position were launch-wide
+// scalars (S_cmp, nchunk, t_token, and S_kv through t_end), so the workgroup derives its own from the row index, S, G and t0 and uses them
+// everywhere -- no device array of positions, not a ragged-batch step.  Unsplit exact forms only (form 0 at D = 64 / 128, form 1 at D = 64
+// where the largest row exceeds form 0): no team of workgroups, no tickets, no wait of one workgroup on another, no band workgroups; shapes
+// beyond them take the separate launches.  Ranges and O are those of S single steps (tests/test_hip_decode_rows.py).  Measured against S
+// single steps and the separate launches: not slower in every cell but S = 1 on rows of >= 32 chunks, which default to the
+// separate launches.
+#include <algorithm>
 #include <mutex>
 #include <unordered_map>
 
@@ -49,6 +59,7 @@ struct DecStepParams {
     int R, G, h, S_cmp, S_sel, NS, nchunk, cpg, t_token, spin;
     int64_t csb, csg, css;
     float c2;
+    int S;           // rows form: query rows per sequence, row (b, s, g) at token t_token + s (in the struct's tail padding: the layout of the rest is unchanged)
 };
 
 constexpr int DSTEP_CH = 128;                  // chunks of 64 compressed rows per row of the step: contexts up to 128k tokens (S_cmp <= 8192)
@@ -84,13 +95,16 @@ __device__ __forceinline__ bool decode_band_workgroup(const DecBandPair &BP) {
 // registers, those of the later three wait in LDS ([slot][u][head][q] f32x4, 256 h bytes per chunk: each lane reads back exactly what it
 // wrote, so no barrier guards them) until the row's log-sum-exp is known.  Two chunks (16 KiB per wave) are in flight throughout.  Same
 // arithmetic on the same values: p_grp, ranges and O have the bits of every other form.
-template <typename T, int NW, bool SPLIT, int HC, int CPW = 2, int D = 64>
+template <typename T, int NW, bool SPLIT, int HC, int CPW = 2, int D = 64, bool ROWS = false>
 __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(DecStepParams P, SelectParams SP, int cand, DecAttnArgs AT, DecBandPair BP) {
     static_assert(CPW == 2 || (CPW == 4 && !SPLIT), "four chunks per wave: unsplit form only");
     static_assert(D == 64 || (D == 128 && NW == 8 && CPW == 2), "D = 128: eight waves per row, logits in the accumulators");
     constexpr int KS = D / 32;              // MFMA k-steps of a logit
     constexpr int TILE = dec_att_tile(D);   // V tile of a wave (the score phases live in the same LDS)
-    if (decode_band_workgroup<T, NW>(BP)) return;
+    static_assert(!ROWS || !SPLIT, "rows form: one workgroup per row, no meeting of workgroups");
+    if constexpr (!ROWS) {
+        if (decode_band_workgroup<T, NW>(BP)) return;
+    }
     using M = MfmaT<T>;
     using x8 = typename M::x8;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -122,7 +136,14 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
     [[maybe_unused]] const bool ts_on = row == P.R / 2;
     DS_TS(0);
     const int g = row % P.G;
-    const int64_t b = row / P.G;
+    const int64_t b = ROWS ? row / (P.S * P.G) : row / P.G;
+    // ROWS: the workgroup's row is (b, s, g) of S consecutive tokens per sequence on ONE cache that already holds them; its token, the
+    // compressed rows it sees (n_cmp(t) of the default geometry l = 32, d = 16; the host launches only where n_cmp(t0) >= 1) and its
+    // chunks follow from the row index alone.  Otherwise they are the launch's.
+    const int t_tok = ROWS ? P.t_token + (row / P.G) % P.S : P.t_token;
+    const int S_cmp = ROWS ? min(P.S_cmp, (t_tok + 1 - 32) / 16 + 1) : P.S_cmp;
+    const int nchunk = ROWS ? (S_cmp + 63) >> 6 : P.nchunk;
+    [[maybe_unused]] const int64_t kvrow = ROWS ? b * P.G + g : (int64_t)row;  // the row's K/V plane
     const int hc = min(rho, h - 1);  // head of this lane's column (columns >= h repeat the last head: their results are never used)
     // ---- phase 1: logits of this workgroup's chunks (64 compressed rows each = MFMA rows; heads = columns), up to two per wave,
     // all loads out at once
@@ -130,14 +151,14 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
 #pragma unroll
     for (int s = 0; s < KS; ++s) qf[s] = *(const x8 *)((const T *)P.Q + ((int64_t)row * h + hc) * D + 32 * s + 8 * q);
     const T *kb = (const T *)P.Kc + b * P.csb + (int64_t)g * P.csg;
-    const int c_lo = SPLIT ? sp * P.cpg : 0, c_hi = SPLIT ? min(P.nchunk, c_lo + P.cpg) : P.nchunk;
+    const int c_lo = SPLIT ? sp * P.cpg : 0, c_hi = SPLIT ? min(nchunk, c_lo + P.cpg) : nchunk;
     constexpr int REGC = CPW == 2 ? 2 : 1;  // chunks of a wave whose logits stay in registers
     x8 a[2][4][KS];
     f32x4 acc[REGC][4];
     auto load_chunk = [&](int c, x8 (&dst)[4][KS]) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const int r = min(c * 64 + 16 * u + rho, P.S_cmp - 1);
+            const int r = min(c * 64 + 16 * u + rho, S_cmp - 1);
 #pragma unroll
             for (int s = 0; s < KS; ++s) dst[u][s] = *(const x8 *)(kb + (int64_t)r * P.css + 32 * s + 8 * q);
         }
@@ -150,13 +171,13 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
     // (behind the K_cmp loads in program order: vector memory operations complete in order, the scores must not wait for these)
     DecPrefetch pre{-1, nullptr};
     if constexpr (PREF) {
-        const int cb = P.t_token >> 6, t_end = min(P.t_token + 1, AT.S_kv);
+        const int cb = t_tok >> 6, t_end = min(t_tok + 1, AT.S_kv);
         const int slot = wave == 0 ? 0 : wave - 13;  // waves 14, 15 -> K tiles 1, 2
         if ((wave == 0 || wave >= 14) && cb >= 2 && cb < P.S_sel && AT.kss == 64) {
             const int blk = wave == 0 ? 0 : cb - (15 - wave);
             pre.tok0 = 64 * blk;
             pre.ktile = ktiles + slot * TILE;
-            decode_prefetch_chunk<T>(AT, row, pre.tok0, min(64, t_end - pre.tok0), lds + wave * TILE, ktiles + slot * TILE);
+            decode_prefetch_chunk<T>(AT, kvrow, pre.tok0, min(64, t_end - pre.tok0), lds + wave * TILE, ktiles + slot * TILE);
         }
     }
 
@@ -180,7 +201,7 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
             for (int j = 0; j < 4; ++j) {
                 const float v = z[u][j] * P.c2;
                 z[u][j] = v;
-                if (c * 64 + 16 * u + 4 * q + j < P.S_cmp) m = fmaxf(m, v);
+                if (c * 64 + 16 * u + 4 * q + j < S_cmp) m = fmaxf(m, v);
             }
         m = xor32_max(xor16_max(m));  // (= the xor-16, xor-32 shuffle steps of decode_logits_mfma_kernel: same bits)
         float l = 0.f;
@@ -188,7 +209,7 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
         for (int u = 0; u < 4; ++u)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                if (c * 64 + 16 * u + 4 * q + j < P.S_cmp) l += __builtin_amdgcn_exp2f(z[u][j] - m);
+                if (c * 64 + 16 * u + 4 * q + j < S_cmp) l += __builtin_amdgcn_exp2f(z[u][j] - m);
         l = xor32_add(xor16_add(l));
         if constexpr (SPLIT) {
             if (rho < h) {  // write-through (sc1) stores: no release fence needed (cdna guide, Guideline 16 R1)
@@ -272,23 +293,23 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
             // the row's records and edge logits -> LDS, one sc1 load per thread
             for (int i = threadIdx.x; i < h * DSTEP_CH; i += NW * 64) {
                 const int hh = i / DSTEP_CH, idx = i % DSTEP_CH;
-                if (idx < P.nchunk) {
+                if (idx < nchunk) {
                     const unsigned long long r = __hip_atomic_load((const unsigned long long *)(P.part_g + (((int64_t)row * h + hh) * DSTEP_CH + idx) * 2), __ATOMIC_RELAXED,
                                                                    __HIP_MEMORY_SCOPE_AGENT);
                     *(f32x2 *)(part + (hh * DSTEP_CH + idx) * 2) = (f32x2){__uint_as_float((unsigned)r), __uint_as_float((unsigned)(r >> 32))};
                 }
             }
-            for (int i = threadIdx.x; i < P.nchunk * 16; i += NW * 64)
+            for (int i = threadIdx.x; i < nchunk * 16; i += NW * 64)
                 if ((i & 15) < h) halo[i] = __uint_as_float(__hip_atomic_load((const unsigned *)(P.halo_g + (int64_t)row * DSTEP_CH * 16 + i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
         } else {
             // The team did not assemble within the poll budget (its other workgroups are not resident yet: a second stream or process holds
             // the CUs).  Nobody waits for anybody here: this workgroup forms the records and edge logits of ALL chunks of the row itself --
             // the same instructions on the same data, so the same bits as its team mates publish -- and carries on.  Slower, never stuck.
-            for (int c = wave; c < P.nchunk; c += NW) {
+            for (int c = wave; c < nchunk; c += NW) {
                 x8 b2[4][KS];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    const int r = min(c * 64 + 16 * u + rho, P.S_cmp - 1);
+                    const int r = min(c * 64 + 16 * u + rho, S_cmp - 1);
 #pragma unroll
                     for (int s2 = 0; s2 < KS; ++s2) b2[u][s2] = *(const x8 *)(kb + (int64_t)r * P.css + 32 * s2 + 8 * q);
                 }
@@ -303,7 +324,7 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
                     for (int j = 0; j < 4; ++j) {
                         const float v = z[u][j] * P.c2;
                         z[u][j] = v;
-                        if (c * 64 + 16 * u + 4 * q + j < P.S_cmp) m = fmaxf(m, v);
+                        if (c * 64 + 16 * u + 4 * q + j < S_cmp) m = fmaxf(m, v);
                     }
                 }
                 m = xor32_max(xor16_max(m));
@@ -312,7 +333,7 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
                 for (int u = 0; u < 4; ++u)
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
-                        if (c * 64 + 16 * u + 4 * q + j < P.S_cmp) l += __builtin_amdgcn_exp2f(z[u][j] - m);
+                        if (c * 64 + 16 * u + 4 * q + j < S_cmp) l += __builtin_amdgcn_exp2f(z[u][j] - m);
                 l = xor32_add(xor16_add(l));
                 if (rho < h) {
                     if (q == 0) *(f32x2 *)(part + (rho * DSTEP_CH + c) * 2) = (f32x2){m, l};
@@ -330,7 +351,7 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
     // ---- phase 2a: per-head log-sum-exp of the row's logits from the chunk records, by every wave for itself.  One 16-lane row of the
     // wave per head, lane i holds records i, i+16, i+32, i+48: ((a_i + a_{i+32}) + (a_{i+16} + a_{i+48})) then xor 8, 4, 2, 1 is the
     // summation tree of wave_sum over 64 lanes (decode_pgrp_kernel / the round-2 fused kernel): same bits.
-    const int nr = (P.nchunk + 15) >> 4;  // records per lane that exist at all (a context of 16k has 16 chunks: one; 128k: eight)
+    const int nr = (nchunk + 15) >> 4;  // records per lane that exist at all (a context of 16k has 16 chunks: one; 128k: eight)
     for (int h0 = 0; h0 < h; h0 += 4) {
         const int hh = h0 + q;
         float mv[8], lv[8];
@@ -339,7 +360,7 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
             const int idx = rho + 16 * i;
             mv[i] = -INFINITY;
             lv[i] = 0.f;
-            if (i < nr && hh < h && idx < P.nchunk) {
+            if (i < nr && hh < h && idx < nchunk) {
                 const f32x2 r = *(const f32x2 *)(part + (hh * DSTEP_CH + idx) * 2);
                 mv[i] = r[0];
                 lv[i] = r[1];
@@ -353,9 +374,9 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
         float av[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {  // (a record that does not exist adds +0: exact, so skipping its exponential changes nothing)
-            av[i] = (i < nr && rho + 16 * i < P.nchunk) ? lv[i] * __builtin_amdgcn_exp2f(mv[i] - m) : 0.f;
+            av[i] = (i < nr && rho + 16 * i < nchunk) ? lv[i] * __builtin_amdgcn_exp2f(mv[i] - m) : 0.f;
             // beyond 64 chunks the three-kernel route lets lane L add records L and L + 64 before the butterfly: the same sum here
-            if (i + 4 < nr && rho + 16 * (i + 4) < P.nchunk) av[i] += lv[i + 4] * __builtin_amdgcn_exp2f(mv[i + 4] - m);
+            if (i + 4 < nr && rho + 16 * (i + 4) < nchunk) av[i] += lv[i + 4] * __builtin_amdgcn_exp2f(mv[i + 4] - m);
         }
         float s = (av[0] + av[2]) + (av[1] + av[3]);
         s += row_ror<8>(s);
@@ -371,7 +392,7 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
     // ---- phase 2b: p = exp2(x - ml), Eq.9 stencil (1/2, 1, 1, 1, 1/2 over rows 4j-1 .. 4j+3, ascending), Eq.10 head sum (ascending h)
     auto blocks_of_chunk = [&](int c, const f32x4 (&v)[4], float hprev) {
         float rot_prev = c > 0 ? __builtin_amdgcn_exp2f(hprev - ml) : 0.f;  // p of row 64 c - 1 (a chunk that exists has its predecessor complete)
-        const bool tail = c * 64 + 64 > P.S_cmp;  // only the row's last chunk can reach past S_cmp (wave uniform): the others need no row masks
+        const bool tail = c * 64 + 64 > S_cmp;  // only the row's last chunk can reach past S_cmp (wave uniform): the others need no row masks
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             float p[4];
@@ -380,7 +401,7 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
             if (tail) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
-                    if (c * 64 + 16 * u + 4 * q + k >= P.S_cmp) p[k] = 0.f;
+                    if (c * 64 + 16 * u + 4 * q + k >= S_cmp) p[k] = 0.f;
             }
             const float rot = __shfl(p[3], (lane + 48) & 63, 64);  // row 4j - 1 = last row of the previous lane group (previous sub-tile for q = 0)
             const float tapm1 = (q == 0) ? rot_prev : rot;
@@ -443,7 +464,7 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
         __syncthreads();
         if (misc[1] != P.NS - 1) return;
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        for (int j = threadIdx.x; j < min(P.S_sel, 16 * P.nchunk); j += NW * 64)
+        for (int j = threadIdx.x; j < min(P.S_sel, 16 * nchunk); j += NW * 64)
             pg[j] = __uint_as_float(__hip_atomic_load((const unsigned *)(P.pg_g + (int64_t)row * 2048 + j), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     }
     DS_TS(6);
@@ -459,12 +480,12 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
     if (wave == 0) {
         int nb = 0;
         switch (cand) {
-            case 1: select_topn_row_regs<1>(SP, pg, P.t_token, rs, re, scr, list, &nb); break;
-            case 2: select_topn_row_regs<2>(SP, pg, P.t_token, rs, re, scr, list, &nb); break;
-            case 4: select_topn_row_regs<4>(SP, pg, P.t_token, rs, re, scr, list, &nb); break;
-            case 8: select_topn_row_regs<8>(SP, pg, P.t_token, rs, re, scr, list, &nb); break;
-            case 16: select_topn_row_regs<16>(SP, pg, P.t_token, rs, re, scr, list, &nb); break;
-            default: select_topn_row_regs<32, true>(SP, pg, P.t_token, rs, re, scr, list, &nb); break;
+            case 1: select_topn_row_regs<1>(SP, pg, t_tok, rs, re, scr, list, &nb); break;
+            case 2: select_topn_row_regs<2>(SP, pg, t_tok, rs, re, scr, list, &nb); break;
+            case 4: select_topn_row_regs<4>(SP, pg, t_tok, rs, re, scr, list, &nb); break;
+            case 8: select_topn_row_regs<8>(SP, pg, t_tok, rs, re, scr, list, &nb); break;
+            case 16: select_topn_row_regs<16>(SP, pg, t_tok, rs, re, scr, list, &nb); break;
+            default: select_topn_row_regs<32, true>(SP, pg, t_tok, rs, re, scr, list, &nb); break;
         }
         if (lane == 0) misc[0] = nb;
     }
@@ -477,9 +498,10 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
     }
     const int NC = uniform(misc[0]);
     // ---- phase 4: selection attention over the picked blocks (wave e mod NW gathers block e; partials merged through LDS)
-    const ListChunks ch{list, min(P.t_token + 1, AT.S_kv)};
+    const ListChunks ch{list, min(t_tok + 1, AT.S_kv)};
     DS_TS(9);
-    decode_attend_chunks<T, NW, ListChunks, D>(AT, row, ch, NC, lds, qf, pre);
+    if constexpr (ROWS) decode_attend_chunks<T, NW, ListChunks, D>(AT, row, ch, NC, lds, qf, pre, kvrow);
+    else decode_attend_chunks<T, NW, ListChunks, D>(AT, row, ch, NC, lds, qf, pre);
     DS_TS(10);
 }
 
@@ -834,6 +856,22 @@ bool decode_step_supported(int64_t R, int dtype, int h, int Dk, int Dv, int S_cm
            sel_attn_decode_wg_supported(dtype, h, Dk, Dv, n_top, ksb, ksg, kss, vsb, vsg, vss, Q, K, V);
 }
 
+// raise the dynamic-LDS limit once per kernel (the runtime call costs about a millisecond)
+static int dstep_raise_lds(void *k) {
+    static std::mutex mu;
+    static void *raised[80] = {};
+    std::lock_guard<std::mutex> lk(mu);
+    for (void *r : raised)
+        if (r == k) return NSA_OK;
+    NSA_HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    for (void *&r : raised)
+        if (!r) {
+            r = k;
+            break;
+        }
+    return NSA_OK;
+}
+
 int launch_decode_step(const void *Q, const void *Kc, const void *K, const void *V, void *O, int32_t *ranges_out, int B, int G, int h, int S_cmp,
                        int S_sel, int S_kv, int n_top, int t_token, int64_t kcb, int64_t kcg, int64_t kcs, int64_t ksb, int64_t ksg, int64_t kss,
                        int64_t vsb, int64_t vsg, int64_t vss, int dtype, float scale, void *ws, size_t ws_bytes, hipStream_t st, const DecBandPair *band, int D) {
@@ -884,21 +922,7 @@ int launch_decode_step(const void *Q, const void *Kc, const void *K, const void 
     const size_t lds = dstep_lds(nw, D);
     // the score data sits in V tiles 1 .. (the prefetching waves of the 16-wave form own tiles 0, 14, 15)
     NSA_CHECK_ARG(dstep_score_bytes(nw, h, S_sel, cpw) <= dstep_score_room(nw, D), "decode step: S_sel too large");
-    {  // raise the dynamic-LDS limit once per kernel (the runtime call costs about a millisecond)
-        static std::mutex mu;
-        static void *raised[48] = {};
-        std::lock_guard<std::mutex> lk(mu);
-        bool done = false;
-        for (void *r : raised) done |= (r == (void *)k);
-        if (!done) {
-            NSA_HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            for (void *&r : raised)
-                if (!r) {
-                    r = (void *)k;
-                    break;
-                }
-        }
-    }
+    if (int rc = dstep_raise_lds((void *)k)) return rc;
     int64_t grid = ns > 1 ? ((R + 7) / 8) * 8 * ns : R;
     DecBandPair BP{};
     BP.n_sel = 0xffffffffu;
@@ -922,6 +946,90 @@ int launch_decode_step(const void *Q, const void *Kc, const void *K, const void 
     static_assert(2 * Geo<64>::TILE_BYTES <= DEC_ATT_TILE, "a band wave keeps its K and V tile in the wave's V tile of the step");
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(nw * 64), lds, st, P, SP, cand, AT, BP);
     NSA_LAUNCH_CHECK("decode_step");
+    return NSA_OK;
+}
+
+
+// The measured rule behind DECODE_ROWS = -1 (tools/bench_sel_decode_rows.py, table in DESIGN.md 4.1f; S in {1, 2, 4, 8} x 4k / 16k / 32k x
+// B in {1, 16}): one rows launch beat both S single decode steps and the separate launches in every cell except S = 1 at 32k, where the
+// single step runs as a team of workgroups (rows of 32 chunks and more, decode_step_plan) and is 3.5 - 4.4 us faster than one workgroup per
+// row.  Below 32 chunks the single step IS the unsplit kernel and the two tie.  So: S = 1 with a row of >= 32 chunks is declined.
+static bool decode_rows_measured_ok(int S, int nchunk_max) { return !(S == 1 && nchunk_max >= 32); }
+
+// ---- rows form: S consecutive tokens per sequence in one launch (nsa_sel_decode_rows) -----------------------------------------------
+// compressed rows a decode step at token t sees, default geometry (l = 32, d = 16)
+static int dstep_ncmp(int t) { return t + 1 < 32 ? 0 : (t + 1 - 32) / 16 + 1; }
+
+// Shape / tuning part of the rows form's predicate (default block geometry assumed).  One workgroup per row (b, s, g), the form and the
+// waves chosen for the launch from its LARGEST row (t0 + S - 1) and its row count B S G: form 0 (two chunks per wave) or, at D = 64, form 1
+// (four chunks per wave) where that row exceeds form 0 -- the unsplit exact forms only, whatever DECODE_WIDE says; no team of workgroups,
+// no one-pass form.  DECODE_ROWS: 0 = never, 1 = wherever the forms hold the shape, -1 = the measured rule.
+bool decode_rows_shape_plan(int B, int S, int G, int dtype, int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int n_top, int t0, int *form,
+                            int *nw_out) {
+    if (form) *form = -1;
+    const int sw = tuning(TUNE_DECODE_ROWS);
+    if (tuning(TUNE_DECODE_STEP) == 0 || tuning(TUNE_DECODE_UNFUSED) > 0 || sw == 0) return false;
+    if (B < 1 || S < 1 || S > 16 || G < 1 || h < 1 || h > 16 || Dk != Dv || (Dk != 64 && Dk != 128) || S_cmp < 1 || S_sel < 1) return false;
+    if (t0 < 0 || t0 > (1 << 30) || dstep_ncmp(t0) < 1 || S_kv < t0 + S) return false;  // every row has a compressed row and its own token in the cache
+    const int64_t R = (int64_t)B * S * G;
+    if (R > (1 << 24)) return false;
+    const int nw = dec_att_waves(R, Dk);
+    const int n_max = std::min(S_cmp, dstep_ncmp(t0 + S - 1)), nchunk = (n_max + 63) / 64;
+    int fm;
+    if (nchunk <= 2 * nw) fm = 0;
+    else if (Dk == 64 && nchunk <= 4 * nw) fm = 1;
+    else return false;
+    if (!((dtype == NSA_DT_BF16 || dtype == NSA_DT_F16) && S_cmp <= 64 * DSTEP_CH && S_sel <= 2048 && n_top >= 3 && n_top <= 64 &&
+          (int64_t)S_kv * 2 * Dv < ((int64_t)1 << 31) && sel_attn_decode_wg_shape_ok(dtype, h, Dk, Dv, n_top) &&
+          dstep_score_bytes(nw, h, S_sel, fm == 1 ? 4 : 2) <= dstep_score_room(nw, Dk)))
+        return false;
+    if (sw < 0 && !decode_rows_measured_ok(S, nchunk)) return false;
+    if (form) *form = fm;
+    if (nw_out) *nw_out = nw;
+    return true;
+}
+
+bool decode_rows_supported(int B, int S, int G, int dtype, int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int l, int d, int l_sel, int n_top,
+                           int t0, int64_t kcb, int64_t kcg, int64_t kcs, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg,
+                           int64_t vss, const void *Q, const void *Kc, const void *K, const void *V) {
+    return decode_rows_shape_plan(B, S, G, dtype, h, Dk, Dv, S_cmp, S_sel, S_kv, n_top, t0, nullptr, nullptr) && d == 16 && l == 32 && l_sel == 64 &&
+           kcs % 8 == 0 && kcb % 8 == 0 && kcg % 8 == 0 && ((uintptr_t)Kc % 16 == 0) &&
+           sel_attn_decode_wg_supported(dtype, h, Dk, Dv, n_top, ksb, ksg, kss, vsb, vsg, vss, Q, K, V);
+}
+
+int launch_decode_rows(const void *Q, const void *Kc, const void *K, const void *V, void *O, int32_t *ranges_out, int B, int S, int G, int h,
+                       int S_cmp, int S_sel, int S_kv, int n_top, int t0, int64_t kcb, int64_t kcg, int64_t kcs, int64_t ksb, int64_t ksg, int64_t kss,
+                       int64_t vsb, int64_t vsg, int64_t vss, int dtype, float scale, hipStream_t st, int D) {
+    int nw = 16, form = 0;
+    NSA_CHECK_ARG(decode_rows_shape_plan(B, S, G, dtype, h, D, D, S_cmp, S_sel, S_kv, n_top, t0, &form, &nw), "decode rows: shape not covered (decode_rows_supported)");
+    const int64_t R = (int64_t)B * S * G;
+    const int cpw = form == 1 ? 4 : 2;
+    const int nchunk = (std::min(S_cmp, dstep_ncmp(t0 + S - 1)) + 63) / 64;  // of the largest row: every row derives its own
+    DecStepParams P{Q, Kc, nullptr, nullptr, nullptr, nullptr, (int)R, G, h, S_cmp, S_sel, 1, nchunk, nchunk, t0, 0, kcb, kcg, kcs, scale * LOG2E, S};
+    SelectParams SP{};
+    if (int rc = select_params_sequential(&SP, S_sel, 64, n_top, 1, 2, n_top)) return rc;
+    SP.out = ranges_out;
+    SP.R = R;
+    SP.S = S;
+    SP.G = G;
+    SP.t0 = t0;
+    const int c = (S_sel + 63) / 64;
+    const int cand = c <= 1 ? 1 : c <= 2 ? 2 : c <= 4 ? 4 : c <= 8 ? 8 : c <= 16 ? 16 : 32;
+    const DecAttnArgs AT{Q, K, V, O, G, h, S_kv, n_top, ksb, ksg, kss, vsb, vsg, vss, scale * LOG2E};
+    void (*k)(DecStepParams, SelectParams, int, DecAttnArgs, DecBandPair);
+    const bool bf = dtype == NSA_DT_BF16;
+#define NSA_DSR(NW_, HC_, CPW_, D_) (bf ? decode_step_kernel<__bf16, NW_, false, HC_, CPW_, D_, true> : decode_step_kernel<_Float16, NW_, false, HC_, CPW_, D_, true>)
+    if (D == 128) {
+        NSA_CHECK_ARG(form == 0 && nw == 8, "decode rows: D = 128 runs form 0 on eight waves");
+        k = h == 6 ? NSA_DSR(8, 6, 2, 128) : NSA_DSR(8, 0, 2, 128);
+    } else if (cpw == 4) k = h == 6 ? (nw == 16 ? NSA_DSR(16, 6, 4, 64) : NSA_DSR(8, 6, 4, 64)) : (nw == 16 ? NSA_DSR(16, 0, 4, 64) : NSA_DSR(8, 0, 4, 64));
+    else k = h == 6 ? (nw == 16 ? NSA_DSR(16, 6, 2, 64) : NSA_DSR(8, 6, 2, 64)) : (nw == 16 ? NSA_DSR(16, 0, 2, 64) : NSA_DSR(8, 0, 2, 64));
+#undef NSA_DSR
+    if (int rc = dstep_raise_lds((void *)k)) return rc;
+    DecBandPair BP{};
+    BP.n_sel = 0xffffffffu;  // (no band workgroups on this form)
+    hipLaunchKernelGGL(k, dim3((unsigned)R), dim3(nw * 64), dstep_lds(nw, D), st, P, SP, cand, AT, BP);
+    NSA_LAUNCH_CHECK("decode_rows");
     return NSA_OK;
 }
 

@@ -222,6 +222,55 @@ def selection_decode_step_plan(B: int, G: int, h: int, Dk: int, Dv: int, S_cmp: 
     return {"launches": n.value, "form": f.value, "nsplit": s.value}
 
 
+def selection_decode_rows(Q: torch.Tensor, K_cmp: torch.Tensor, K: torch.Tensor, V: torch.Tensor, meta, n_top: int, t0: int,
+                          *, scale: Optional[float] = None, out: Optional[torch.Tensor] = None,
+                          ranges_out: Optional[torch.Tensor] = None):
+    """The decode step of the selected branch for S consecutive tokens per sequence in a single native call (nsa_sel_decode_rows).
+
+    Q [B,S,G,h,Dk] holds the queries of tokens t0 .. t0 + S - 1; K_cmp [B,G,S_cmp,Dk] and K/V [B,G,S_kv,D] are the cache AFTER those S
+    tokens were appended (S_kv >= t0 + S) and meta = BlockMeta of t0 + S tokens.  Row s computes what selection_decode_step computes at
+    t = t0 + s on the cache truncated to t + 1 tokens (its own n_cmp(t) compressed rows, sequential selection at t, K/V[:t+1]).
+    Returns (O [B,S,G,h,Dv], ranges [B,S,G,n_top,2] int32)."""
+    dev = _need_gpu(Q, K_cmp, K, V)
+    B, S, G, h, Dk = Q.shape
+    S_kv, Dv = K.shape[2], V.shape[3]
+    S_cmp, S_sel = K_cmp.shape[2], meta.S_sel
+    if S_kv < t0 + S:
+        raise RuntimeError("selection_decode_rows: the cache must hold the S tokens t0 .. t0 + S - 1")
+    Qc, Kc, Kk, Vv = Q.contiguous(), _prep_kv(K_cmp), _prep_kv(K), _prep_kv(V)
+    O = out if out is not None else torch.empty((B, S, G, h, Dv), dtype=V.dtype, device=dev)
+    rg = ranges_out if ranges_out is not None else torch.empty((B, S, G, n_top, 2), dtype=torch.int32, device=dev)
+    if O.numel() == 0:
+        return O, rg
+    L = _lib.lib()
+    dt = _DT[Q.dtype]
+    ws = workspace(dev, L.nsa_sel_decode_rows_workspace(B, S, G, h, Dk, Dv, S_cmp, S_sel, n_top, dt) + 16, "decode_rows")
+    wptr = (ws.data_ptr() + 15) & ~15
+    cptr, crows, cvals = meta.device_csc(dev)
+    rc = L.nsa_sel_decode_rows(Qc.data_ptr(), Kc.data_ptr(), Kk.data_ptr(), Vv.data_ptr(), cptr.data_ptr(), crows.data_ptr(),
+                               cvals.data_ptr(), rg.data_ptr(), O.data_ptr(), B, S, G, h, Dk, Dv, S_cmp, S_sel, S_kv,
+                               int(meta.l), int(meta.d), int(meta.l_sel), int(n_top), int(t0),
+                               Kc.stride(0), Kc.stride(1), Kc.stride(2), Kk.stride(0), Kk.stride(1), Kk.stride(2),
+                               Vv.stride(0), Vv.stride(1), Vv.stride(2), dt, float(scale) if scale else 0.0,
+                               wptr, ws.numel() - (wptr - ws.data_ptr()), _stream(dev))
+    _lib.check(rc, "nsa_sel_decode_rows")
+    return O, rg
+
+
+def selection_decode_rows_plan(B: int, S: int, G: int, h: int, Dk: int, Dv: int, S_cmp: int, S_sel: int, S_kv: int, n_top: int,
+                               dtype: torch.dtype = torch.bfloat16) -> dict:
+    """What selection_decode_rows does with a shape under the current tuning switches (nsa_sel_decode_rows_plan; default block geometry,
+    aligned contiguous-row inputs, a cache of exactly S_kv = t0 + S tokens): {"launches": 1 exactly when the call is the one-launch rows
+    form, otherwise an estimate > 1 of the separate launches, "form": 0 logits in registers / 1 four chunks per wave / -1 declined}."""
+    import ctypes
+
+    n, f = ctypes.c_int(0), ctypes.c_int(0)
+    rc = _lib.lib().nsa_sel_decode_rows_plan(int(B), int(S), int(G), int(h), int(Dk), int(Dv), int(S_cmp), int(S_sel), int(S_kv), int(n_top),
+                                             _DT[dtype], ctypes.byref(n), ctypes.byref(f))
+    _lib.check(rc, "nsa_sel_decode_rows_plan")
+    return {"launches": n.value, "form": f.value}
+
+
 def select_and_attend(p_grp: torch.Tensor, Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, meta, n_top: int, *,
                       mode: str = "batched", t0: int = 0, force_init: bool = True, force_local: int = 2,
                       scale: Optional[float] = None, return_lse: bool = False):
