@@ -283,6 +283,31 @@ NSA_API size_t nsa_layer_decode_step_workspace(const nsa_layer_desc *L, int B, i
 NSA_API int nsa_layer_decode_step(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *x, void *y, int t,
                           const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel,
                           int32_t *ranges_out, float *gates_out, void *workspace, size_t workspace_bytes, void *stream);
+/* The decode step of the whole layer for S CONSECUTIVE tokens per sequence in one call (k draft tokens to verify, the tail of a chunked
+ * prefill), 1 <= S <= 16: x [B,S,dim] holds the tokens of positions t0 .. t0 + S - 1 (t0 = tokens already cached, t0 + S <= S_max) and the call
+ * does what S nsa_layer_decode_step calls at t = t0 .. t0 + S - 1 do -- the same caches, ranges, gates and y rows [B,S,dim]:
+ *   1. the fused QKV projection of the B S rows with RoPE + cache append in its epilogue, row (b, s) rotated at and appended to position
+ *      t0 + s (the MFMA form from B S >= 3 rows of bf16 / f16 on, else the chunk loop: where the single step at t0 + s projects on the same
+ *      form, the cached bits are the single step's);
+ *   2. the compressed tokens n_cmp(t0 - 1) <= j < n_cmp(t0 + S - 1) whose windows complete inside the call;
+ *   3. the selected branch as nsa_sel_decode_rows (one launch, or its separate launches where that form declines);
+ *   4. the sliding and the compressed branch of the S rows (one launch in split form where Dk = Dv = 64 allows, else one each);
+ *   5. split combine + gates + mix (Dv = 64; the gate kernel otherwise), 6. the output projection of the B S rows.
+ * Six launches at the m7c shape when a compressed token is due, five otherwise.  y is within the rounding of the band kernels' split
+ * count of the single steps' rows; ranges are theirs wherever both project on the same form (B >= 3).
+ * csc_* / S_sel: the Eq.9 map of block metadata covering t0 + S tokens.  ranges_out [B,S,G,n_sel,2] int32 and gates_out [B,S,G,3] fp32 are
+ * nullable monitors.  workspace: nsa_layer_decode_rows_workspace() bytes, 256-byte aligned (0 for a null descriptor, B < 1 or S outside
+ * [1,16]; at S = 1 not smaller than nsa_layer_decode_step_workspace).
+ * nsa_layer_decode_rows_plan makes no HIP call and reports, for aligned caches of capacity S_max, *launches and *route = 1 (the selected
+ * branch in its one-launch rows form) / 0 (its separate launches) / -1 with *launches = 0: DECLINED -- the caller should run S single steps.
+ * Tuning switch "LAYER_DECODE_ROWS": 1 = never declined, 0 = always, -1 (default) = declined where the call was measured slower than S
+ * single steps (S = 1).  nsa_layer_decode_rows itself runs whatever the switch says. */
+NSA_API size_t nsa_layer_decode_rows_workspace(const nsa_layer_desc *L, int B, int S, int S_max);
+NSA_API int nsa_layer_decode_rows(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *x, void *y, int t0, int S,
+                          const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel,
+                          int32_t *ranges_out, float *gates_out, void *workspace, size_t workspace_bytes, void *stream);
+NSA_API int nsa_layer_decode_rows_plan(const nsa_layer_desc *L, int B, int S, int S_max, int t0, int S_sel, int *launches /* host */,
+                               int *route /* host */);
 
 /* ---------------------------------------------------------------------------------------
  * Eq.9 map in gather (CSC) form.  For selection block j the entries csc_ptr[j]..csc_ptr[j+1]

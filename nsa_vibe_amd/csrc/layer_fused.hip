@@ -236,6 +236,36 @@ struct RopeDest {
     }
 };
 
+// rows form (S consecutive tokens per sequence: row m = b S + s of the projection sits at position t0 + s): the destination of a column pair.
+// The rotation of (pair, s) is the single step's rope_sincos call at (float)(t0 + s), evaluated by whoever owns that pair of values.
+template <typename T>
+struct RopeRowsDest {
+    bool rot;
+    int ri, rD;
+    T *dst;          // row (b, s) = (0, 0)
+    int64_t sb, ss;  // elements between sequences / positions
+    __device__ __forceinline__ void init(const RopeAppendParams &P, int col) {
+        const QkvCol<T> c(P, col, P.S_max, P.t0);
+        rot = c.ri >= 0;
+        ri = c.ri;
+        rD = c.rD;
+        dst = c.p;
+        sb = c.sb;
+        ss = c.ss;
+    }
+    __device__ __forceinline__ void sincos(const RopeAppendParams &P, int s, float &sn, float &cs) const {
+        sn = 0.f;
+        cs = 1.f;
+        if (rot) rope_sincos<T>(ri, rD, (float)(P.t0 + s), P.rope_base, P.inv_scale, sn, cs);
+    }
+    __device__ __forceinline__ void store(int b, int s, float sn, float cs, float x0, float x1) const {
+        if (rot) rope_rotate<T>(x0, x1, sn, cs, x0, x1);
+        T *d = dst + b * sb + s * ss;
+        d[0] = Elt<T>::from_f(x0);
+        d[1] = Elt<T>::from_f(x1);
+    }
+};
+
 // ------------------------------------------------------------------------------------------ few-row projections on the VALU
 // out[m, n] = A[m, :] . W[n, :] for a few rows m: a wave owns CW weight rows (1; 2 = a rotation pair; 4 = the LM head, where four rows in
 // flight per wave let the weight matrix stream at memory speed) and keeps one accumulator per (weight row, row of A): fmaf over k
@@ -387,6 +417,32 @@ struct RopeEpi {
     }
     __device__ __forceinline__ void store(const Wave &rd, int m, int, const float (&s)[2]) const { rd.store(m, rnd<T>(s[0]), rnd<T>(s[1])); }
 };
+// RopeRowsEpi (CW = 2, chunk loop): the same for S <= 16 consecutive tokens per sequence, row m = b S + s appended at position t0 + s.  The
+// wave's pair has one rotation per s: lane s evaluates it once (powf + sincosf), lane 0 picks it up from the wave's own LDS slice per row
+template <typename T>
+struct RopeRowsEpi {
+    static constexpr int MIN_BLOCKS = 2, GROUP = 2;
+    static constexpr int MAX_S = 16;
+    RopeAppendParams P;
+    struct Wave {
+        RopeRowsDest<T> rd;
+        const float *sc;  // [S][2]: (sin, cos) of position t0 + s
+    };
+    __device__ __forceinline__ Wave init(int n0) const {
+        __shared__ float sc[4][MAX_S][2];
+        Wave w;
+        w.rd.init(P, n0);
+        const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
+        if (lane < P.S) w.rd.sincos(P, lane, sc[wave][lane][0], sc[wave][lane][1]);
+        wave_lds_fence();
+        w.sc = &sc[wave][0][0];
+        return w;
+    }
+    __device__ __forceinline__ void store(const Wave &w, int m, int, const float (&s)[2]) const {
+        const int b = m / P.S, si = m - b * P.S;
+        w.rd.store(b, si, w.sc[2 * si], w.sc[2 * si + 1], rnd<T>(s[0]), rnd<T>(s[1]));
+    }
+};
 
 // chunk-loop form (any dtype, K and alignment): k in 512-element chunks, rows of A in passes of 8 (CW = 4: at most 2 rows, one pass).  The
 // loads of one k chunk are waited for before the next goes out.
@@ -503,11 +559,13 @@ struct LinearMixArgs {
 };
 // NWV = waves of a workgroup that split the K axis: 4, or 8 for long rows (K >= 2048: fc2 of the MLP) -- a wave's k-steps go out in
 // rounds of 6, each round a memory round trip, so K = 3072 on 4 waves was four of them in a row (15.5 us at 32 rows, 8.5 for fc1)
-template <typename T, bool ROPE, bool MIX = false, int NWV = 4>
+// ROWS (with ROPE): P.S <= 16 consecutive tokens per sequence, row m = b P.S + s appended at position P.t0 + s (RopeRowsDest)
+template <typename T, bool ROPE, bool MIX = false, int NWV = 4, bool ROWS = false>
 __global__ __launch_bounds__(NWV * 64, 2) void linear_mfma_kernel(RopeAppendParams P, const T *__restrict__ X, const T *__restrict__ W,
                                                                T *__restrict__ out, int M, int N, int K, int epi, const T *__restrict__ res,
                                                                LinearMixArgs mx) {
     static_assert(NWV == 4 || (NWV == 8 && !ROPE && !MIX), "eight waves: the plain projection only");
+    static_assert(!ROWS || ROPE, "rows form: the RoPE + append epilogue only");
     using MT_ = MfmaT<T>;
     using x8 = typename MT_::x8;
     __shared__ float part[NWV][16][65];
@@ -531,9 +589,18 @@ __global__ __launch_bounds__(NWV * 64, 2) void linear_mfma_kernel(RopeAppendPara
     const T *wrow = W + (int64_t)min(n0 + rho, N - 1) * K + 8 * q;  // the last column tile may be partial: clamp, store guarded
     // ROPE (P.S == 1): the rotations of the workgroup's 8 column pairs depend on the position only -- threads 0..7 evaluate one each (powf +
     // sincosf) while the loads are in flight and pass it through LDS; every thread then needs only the destinations of its two pairs
-    [[maybe_unused]] RopeDest<T> rd[2];
-    __shared__ float rsc[8][2];
-    if constexpr (ROPE) {
+    // ROWS: one rotation per (pair, s), 8 P.S <= 128 values: thread 8 s + pair evaluates one, entry [8 s + pair]
+    [[maybe_unused]] std::conditional_t<ROWS, RopeRowsDest<T>, RopeDest<T>> rd[2];
+    __shared__ float rsc[ROWS ? 128 : 8][2];
+    if constexpr (ROWS) {
+        if ((int)threadIdx.x < 8 * P.S) {
+            RopeRowsDest<T> one;
+            one.init(P, min(n0 + 2 * (int)(threadIdx.x & 7), N - 2));
+            one.sincos(P, (int)(threadIdx.x >> 3), rsc[threadIdx.x][0], rsc[threadIdx.x][1]);
+        }
+#pragma unroll
+        for (int p = 0; p < 2; ++p) rd[p].init(P, min(n0 + 4 * (int)(threadIdx.x >> 6) + 2 * p, N - 2));
+    } else if constexpr (ROPE) {
         if (threadIdx.x < 8) {
             RopeDest<T> one;
             one.init(P, min(n0 + 2 * (int)threadIdx.x, N - 2));
@@ -624,9 +691,14 @@ __global__ __launch_bounds__(NWV * 64, 2) void linear_mfma_kernel(RopeAppendPara
 #pragma unroll
         for (int p = 0; p < 2; ++p)
             if (n0 + 4 * nq + 2 * p < N) {
-                rd[p].sn = rsc[2 * nq + p][0];  // (written before the barrier above)
-                rd[p].cs = rsc[2 * nq + p][1];
-                rd[p].store(m, rnd<T>(v[2 * p]), rnd<T>(v[2 * p + 1]));
+                if constexpr (ROWS) {
+                    const int b = m / P.S, s = m - b * P.S, e = 8 * s + 2 * nq + p;  // (the entry of this row's position)
+                    rd[p].store(b, s, rsc[e][0], rsc[e][1], rnd<T>(v[2 * p]), rnd<T>(v[2 * p + 1]));
+                } else {
+                    rd[p].sn = rsc[2 * nq + p][0];  // (written before the barrier above)
+                    rd[p].cs = rsc[2 * nq + p][1];
+                    rd[p].store(m, rnd<T>(v[2 * p]), rnd<T>(v[2 * p + 1]));
+                }
             }
     } else {
 #pragma unroll
@@ -673,13 +745,13 @@ static bool linear_mfma_ok(int dtype, int M, int N, int K, const void *X, const 
     return (dtype == NSA_DT_BF16 || dtype == NSA_DT_F16) && M >= 3 && K % 32 == 0 &&
            (((uintptr_t)X | (uintptr_t)W) % 16 == 0);
 }
-template <bool ROPE, bool MIX = false, int NWV = 4>
+template <bool ROPE, bool MIX = false, int NWV = 4, bool ROWS = false>
 static void launch_linear_mfma(const RopeAppendParams &P, const void *X, const void *W, void *out, int M, int N, int K, int dtype, int epi,
                                const void *res, const LinearMixArgs &mx, hipStream_t st) {
     const dim3 grid((unsigned)((N + 15) / 16), (unsigned)((M + 63) / 64));
     with_elt<false>(dtype, [&](auto t) {
         using T = decltype(t);
-        hipLaunchKernelGGL((linear_mfma_kernel<T, ROPE, MIX, NWV>), grid, dim3(NWV * 64), 0, st, P, (const T *)X, (const T *)W, (T *)out, M, N, K,
+        hipLaunchKernelGGL((linear_mfma_kernel<T, ROPE, MIX, NWV, ROWS>), grid, dim3(NWV * 64), 0, st, P, (const T *)X, (const T *)W, (T *)out, M, N, K,
                            epi, (const T *)res, mx);
     });
 }
@@ -734,8 +806,31 @@ bool qkv_can_fold_norm(const RopeAppendParams &P, const void *X, const void *W, 
     const int NT = P.G * P.h * P.Dk + 3 * P.G * P.Dk + 3 * P.G * P.Dv;
     return !linear_mfma_ok(dtype, P.B, NT, K, X, W);
 }
+// P.S consecutive tokens per sequence (the layer's rows call): X [B S, K], row m = b S + s at position t0 + s.  The MFMA form where the
+// projection of B S rows takes it, else the chunk loop; the all-loads-first form stays with the single step
+static int launch_qkv_rope_append_rows(const RopeAppendParams &P, const void *X, const void *W, int K, int dtype, hipStream_t st,
+                                       const void *norm_w, float norm_eps) {
+    const int NT = P.G * P.h * P.Dk + 3 * P.G * P.Dk + 3 * P.G * P.Dv, M = P.B * P.S;
+    NSA_CHECK_ARG(P.S >= 1 && P.S <= RopeRowsEpi<float>::MAX_S, "qkv_rope_append: 1 to 16 tokens per sequence");
+    if (linear_mfma_ok(dtype, M, NT, K, X, W)) {
+        NSA_CHECK_ARG(norm_w == nullptr, "qkv_rope_append: the MFMA form takes normalised input");
+        launch_linear_mfma<true, false, 4, true>(P, X, W, nullptr, M, NT, K, dtype, 0, nullptr, {}, st);
+        NSA_LAUNCH_CHECK("qkv_rope_append(rows, mfma)");
+        return NSA_OK;
+    }
+    with_elt(dtype, [&](auto t) {
+        using T = decltype(t);
+        const RowsA<T> a{(const T *)X, (const T *)norm_w, norm_eps};
+        const RopeRowsEpi<T> e{P};
+        hipLaunchKernelGGL((proj_loop_kernel<T, 2, RowsA<T>, RopeRowsEpi<T>>), dim3((unsigned)((NT / 2 + 3) / 4)), dim3(256), 0, st, a, (const T *)W, M,
+                           NT, K, e);
+    });
+    NSA_LAUNCH_CHECK("qkv_rope_append(rows)");
+    return NSA_OK;
+}
 int launch_qkv_rope_append(const RopeAppendParams &P, const void *X, const void *W, int K, int dtype, hipStream_t st, const void *norm_w,
-                           float norm_eps) {
+                           float norm_eps, bool rows) {
+    if (rows) return launch_qkv_rope_append_rows(P, X, W, K, dtype, st, norm_w, norm_eps);
     const int NT = P.G * P.h * P.Dk + 3 * P.G * P.Dk + 3 * P.G * P.Dv;
     if (linear_mfma_ok(dtype, P.B, NT, K, X, W)) {
         NSA_CHECK_ARG(norm_w == nullptr, "qkv_rope_append: the MFMA form takes normalised input");

@@ -40,8 +40,10 @@ struct DecodeFinishParams {
     float tau;
 };
 bool qkv_can_fold_norm(const RopeAppendParams &P, const void *X, const void *W, int K, int dtype);
+// rows: P.S (1 to 16) consecutive tokens per sequence, row b P.S + s of X at position P.t0 + s (the layer's rows call; false: P.S = 1, the
+// single step, with its all-loads-first form)
 int launch_qkv_rope_append(const RopeAppendParams &P, const void *X, const void *W, int K, int dtype, hipStream_t st, const void *norm_w = nullptr,
-                           float norm_eps = 0.f);
+                           float norm_eps = 0.f, bool rows = false);
 bool linear_small_can_fold_norm(int dtype, int M, int N, int K, const void *A, const void *W);
 int launch_linear_small_norm(const void *A, const void *W, void *out, int M, int N, int K, int dtype, int epi, const void *res, const void *norm_w,
                              float eps, hipStream_t st);

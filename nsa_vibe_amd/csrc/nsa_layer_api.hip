@@ -249,11 +249,13 @@ int nsa_layer_extend(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void 
 }
 
 // workspace: proj | Q | O_cmp | O_sel | O_win | O_mix | ranges | selection-decode scratch | band scratch
+// S = 0: the single step (B rows); S >= 1: the rows call, every piece sized by its B S rows
 struct DecodeWs {
     size_t proj, q, ocmp, osel, owin, omix, ranges, gates, sel, band, band2, total, sel_bytes, band_bytes;
 };
-static DecodeWs decode_ws(const nsa_layer_desc *L, int B, int S_max) {
+static DecodeWs decode_ws(const nsa_layer_desc *L, int B1, int S_max, int S = 0) {
     DecodeWs w;
+    const size_t B = (size_t)B1 * (S > 0 ? S : 1);
     const size_t e = esize(L->dtype);
     const size_t NQ = (size_t)L->G * L->h * L->Dk, NO = (size_t)L->G * L->h * L->Dv;
     const size_t NT = NQ + 3 * (size_t)L->G * L->Dk + 3 * (size_t)L->G * L->Dv;
@@ -266,11 +268,12 @@ static DecodeWs decode_ws(const nsa_layer_desc *L, int B, int S_max) {
     w.osel = o; o += up256(B * NO * e);
     w.owin = o; o += up256(B * NO * e);
     w.omix = o; o += up256(B * NO * e);
-    w.ranges = o; o += up256(sizeof(int32_t) * (size_t)B * L->G * L->n_sel * 2);
-    w.gates = o; o += up256(sizeof(float) * (size_t)B * L->G * 3);
-    w.sel_bytes = nsa_sel_decode_step_workspace(B, L->G, L->h, L->Dk, L->Dv, n_cmp_max, S_sel_max, L->n_sel, L->dtype);
+    w.ranges = o; o += up256(sizeof(int32_t) * B * L->G * L->n_sel * 2);
+    w.gates = o; o += up256(sizeof(float) * B * L->G * 3);
+    w.sel_bytes = nsa_sel_decode_step_workspace(B1, L->G, L->h, L->Dk, L->Dv, n_cmp_max, S_sel_max, L->n_sel, L->dtype);
+    if (S > 0) w.sel_bytes = std::max(w.sel_bytes, nsa_sel_decode_rows_workspace(B1, S, L->G, L->h, L->Dk, L->Dv, n_cmp_max, S_sel_max, L->n_sel, L->dtype));
     w.sel = o; o += up256(w.sel_bytes);
-    w.band_bytes = nsa_band_attn_fwd_workspace(B, 1, L->G, L->h, L->Dk, L->Dv, L->dtype);
+    w.band_bytes = nsa_band_attn_fwd_workspace(B1, S > 0 ? S : 1, L->G, L->h, L->Dk, L->Dv, L->dtype);
     w.band = o; o += up256(w.band_bytes);
     w.band2 = o; o += up256(w.band_bytes);
     w.total = o;
@@ -280,6 +283,29 @@ static DecodeWs decode_ws(const nsa_layer_desc *L, int B, int S_max) {
 size_t nsa_layer_decode_step_workspace(const nsa_layer_desc *L, int B, int S_max) {
     if (!L || !dtype_ok(L->dtype) || B < 1 || S_max < 1) return 0;
     return decode_ws(L, B, S_max).total;
+}
+
+// The sliding and the compressed branch of S rows at t0 as ONE launch (launch_band_attn_fwd_dual): both in split form with the combine left to
+// the finish kernel (defer: Dv = 64).  *ns_band = the splits of a branch at (B, S)
+static bool band_pair_dual(const nsa_layer_desc *L, const nsa_kv_desc *kv, const CacheStrides &C, int S, int n_cmp, int defer, int *ns_band) {
+    *ns_band = 1;
+    band_attn_workspace(kv->B, S, L->G, L->h, L->Dk, L->Dv, L->dtype, ns_band);
+    return defer && *ns_band > 1 && n_cmp > 0 && L->w > 0 && band_attn_mfma_supported(L->dtype, L->h, L->Dk, L->Dv) &&
+           ((uintptr_t)kv->K_win % 16 == 0) && ((uintptr_t)kv->V_win % 16 == 0) && ((uintptr_t)kv->K_cmp % 16 == 0) &&
+           ((uintptr_t)kv->V_cmp % 16 == 0) && C.ksb * 2 < ((int64_t)1 << 31) && C.vsb * 2 < ((int64_t)1 << 31);
+}
+// their argument blocks: rows t0 .. t0 + S - 1 over K_win[:t0 + S] (the last w tokens) and over the n_cmp compressed tokens (emission schedule)
+static void band_pair_fill(DecBandPair &BP, const nsa_layer_desc *L, const nsa_kv_desc *kv, const CacheStrides &C, const void *Q, void *Owin,
+                           void *Ocmp, int S, int t0, int n_cmp, int ns_band, float *part_w, float *part_c) {
+    BandAttnParams &PW = BP.w, &PC = BP.c;
+    PW = band_attn_params(Q, kv->K_win, kv->V_win, Owin, nullptr, kv->B, S, L->G, L->h, L->Dk, L->Dv, t0 + S, C.ksb, C.ksg, L->Dk, C.vsb, C.vsg,
+                          L->Dv, t0, 0, 1, 0, L->w, C.scale);
+    PW.part = part_w; PW.nsplit = ns_band; PW.defer_combine = 1;
+    PC = PW;
+    PC.K = kv->K_cmp; PC.V = kv->V_cmp; PC.O = Ocmp; PC.S_kv = n_cmp;
+    PC.ksb = C.kcb; PC.ksg = C.kcg; PC.vsb = C.vcb; PC.vsg = C.vcg;
+    PC.a = L->l; PC.dd = L->d; PC.c = 1; PC.w = 1 << 30;
+    PC.part = part_c;
 }
 
 static int layer_decode_step_impl(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *x, void *y, int t, const int32_t *csc_ptr,
@@ -326,21 +352,10 @@ static int layer_decode_step_impl(const nsa_layer_desc *L, const nsa_kv_desc *kv
     // the selected branch runs as the one-launch decode step they ride on ITS launch (workgroups behind the step's own: sel_decode_fused.hip),
     // otherwise they are one launch of their own.
     int ns_band = 1;
-    band_attn_workspace(B, 1, G, h, Dk, Dv, dt, &ns_band);
-    const bool dual = defer && ns_band > 1 && n_cmp > 0 && L->w > 0 && band_attn_mfma_supported(dt, h, Dk, Dv) &&
-                      ((uintptr_t)kv->K_win % 16 == 0) && ((uintptr_t)kv->V_win % 16 == 0) && ((uintptr_t)kv->K_cmp % 16 == 0) &&
-                      ((uintptr_t)kv->V_cmp % 16 == 0) && ksb * 2 < ((int64_t)1 << 31) && vsb * 2 < ((int64_t)1 << 31);
+    const bool dual = band_pair_dual(L, kv, C, 1, n_cmp, defer, &ns_band);
     DecBandPair BP{};
     BandAttnParams &PW = BP.w, &PC = BP.c;
-    if (dual) {
-        PW = band_attn_params(Q, kv->K_win, kv->V_win, Owin, nullptr, B, 1, G, h, Dk, Dv, S_raw, ksb, ksg, Dk, vsb, vsg, Dv, t, 0, 1, 0, L->w, scale);
-        PW.part = (float *)(ws + W.band); PW.nsplit = ns_band; PW.defer_combine = 1;
-        PC = PW;
-        PC.K = kv->K_cmp; PC.V = kv->V_cmp; PC.O = Ocmp; PC.S_kv = n_cmp;
-        PC.ksb = kcb; PC.ksg = kcg; PC.vsb = vcb; PC.vsg = vcg;
-        PC.a = L->l; PC.dd = L->d; PC.c = 1; PC.w = 1 << 30;
-        PC.part = (float *)(ws + W.band2);
-    }
+    if (dual) band_pair_fill(BP, L, kv, C, Q, Owin, Ocmp, 1, t, n_cmp, ns_band, (float *)(ws + W.band), (float *)(ws + W.band2));
     const int band_mode = tuning(TUNE_DECODE_BAND);  // 0 own launch, 1 ride, 2 ride + merge in the workgroup, -1 / 3: 2 + the mix in the output projection
     const bool ride = dual && Dk == 64 && band_mode != 0;
     float *gates = gates_out ? gates_out : (float *)(ws + W.gates);
@@ -397,6 +412,139 @@ int nsa_layer_decode_step(const nsa_layer_desc *L, const nsa_kv_desc *kv, const 
                           void *workspace, size_t workspace_bytes, void *stream) {
     return layer_decode_step_impl(L, kv, x, y, t, csc_ptr, csc_rows, csc_vals, S_sel, ranges_out, gates_out, workspace, workspace_bytes, stream,
                                   nullptr);
+}
+
+// ------------------------------------------------------------------------------ layer decode step for S consecutive tokens
+constexpr int LAYER_ROWS_MAX_S = 16;
+
+// the launches of the call and the route of its selected branch (1 = the one-launch rows form, 0 = its separate launches), from the shape and
+// the switches alone: aligned caches of capacity S_max assumed.  Returns false for a shape the call refuses.
+static bool layer_decode_rows_route(const nsa_layer_desc *L, int B, int S, int S_max, int t0, int S_sel, int *launches, int *route) {
+    if (check_layer(L, "layer_decode_rows_plan")) return false;
+    if (B < 1 || S < 1 || S > LAYER_ROWS_MAX_S || t0 < 0 || (int64_t)t0 + S > S_max || S_sel < 1 || (int64_t)S_sel * L->l_sel < (int64_t)t0 + S) return false;
+    nsa_kv_desc kv{};  // stands in for aligned caches: the predicates below read the sizes and the pointers' alignment only
+    kv.K_sel = kv.V_sel = kv.K_win = kv.V_win = kv.K_raw = kv.V_raw = kv.K_cmp = kv.V_cmp = (void *)(uintptr_t)256;
+    kv.B = B; kv.S_max = S_max; kv.n_cmp_max = std::max(1, ncmp_of(S_max, L->l, L->d));
+    const CacheStrides C(L, &kv);
+    const int n0 = ncmp_of(t0, L->l, L->d), n1 = ncmp_of(t0 + S, L->l, L->d);
+    const int G = L->G, h = L->h, Dk = L->Dk, Dv = L->Dv, dt = L->dtype;
+    int n = 1 + (n1 > n0 ? 1 : 0);  // projection + RoPE + append, pooling
+    const bool one = decode_rows_supported(B, S, G, dt, h, Dk, Dv, n1, S_sel, t0 + S, L->l, L->d, L->l_sel, L->n_sel, t0, C.kcb, C.kcg, Dk, C.ksb,
+                                           C.ksg, Dk, C.vsb, C.vsg, Dv, kv.K_sel, kv.K_cmp, kv.K_sel, kv.V_sel);
+    if (one) {
+        n += 1;
+    } else {
+        int nl = 3, form = -1;  // (the selected branch's own estimate of its separate launches)
+        if (nsa_sel_decode_rows_plan(B, S, G, h, Dk, Dv, n1, S_sel, t0 + S, L->n_sel, dt, &nl, &form) != NSA_OK || nl < 2) nl = 3;
+        n += nl;
+    }
+    int ns_band = 1;
+    n += band_pair_dual(L, &kv, C, S, n1, Dv == 64 ? 1 : 0, &ns_band) ? 1 : 2;  // (an undeferred split branch adds its combine: not counted)
+    n += 2;                                                                       // finish (or gate + mix), output projection
+    *launches = n;
+    *route = one ? 1 : 0;
+    return true;
+}
+
+// The measured rule behind LAYER_DECODE_ROWS = -1 (tools/bench_layer_decode_rows.py): S = 1 stays with the single step, whose
+// band branches ride on the selected branch's launch (three launches against five here)
+static bool layer_decode_rows_measured_ok(int B, int S, int t0) { return S >= 2; }
+
+static int layer_decode_rows_impl(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *x, void *y, int t0, int S, const int32_t *csc_ptr,
+                                  const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out, float *gates_out,
+                                  void *workspace, size_t workspace_bytes, void *stream, const void *residual, const void *norm_w = nullptr,
+                                  float norm_eps = 0.f) {
+    if (int rc = check_layer(L, "layer_decode_rows")) return rc;
+    if (int rc = check_kv(kv, "layer_decode_rows")) return rc;
+    NSA_CHECK_ARG(x && y && L->W_qkv && L->W_out, "layer_decode_rows: null pointer");
+    NSA_CHECK_ARG(S >= 1 && S <= LAYER_ROWS_MAX_S, "layer_decode_rows: 1 to %d tokens per sequence (got %d)", LAYER_ROWS_MAX_S, S);
+    NSA_CHECK_ARG(t0 >= 0 && (int64_t)t0 + S <= kv->S_max, "layer_decode_rows: tokens [%d,%d) exceed the cache capacity %d", t0, t0 + S, kv->S_max);
+    NSA_CHECK_ARG(S_sel >= 1 && (int64_t)S_sel * L->l_sel >= (int64_t)t0 + S, "layer_decode_rows: block metadata (S_sel=%d) does not cover %d tokens",
+                  S_sel, t0 + S);
+    const int B = kv->B;
+    const DecodeWs W = decode_ws(L, B, kv->S_max, S);
+    if (int rc = check_workspace("layer_decode_rows", workspace, workspace_bytes, W.total)) return rc;
+    unsigned char *ws = (unsigned char *)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    const int dt = L->dtype;
+    const int G = L->G, h = L->h, Dk = L->Dk, Dv = L->Dv;
+    const int NO = G * h * Dv, M = B * S, S_kv = t0 + S;
+    void *Q = ws + W.q, *Ocmp = ws + W.ocmp, *Osel = ws + W.osel, *Owin = ws + W.owin, *Omix = ws + W.omix;
+    int32_t *ranges = ranges_out ? ranges_out : (int32_t *)(ws + W.ranges);
+    // compressed tokens emitted before the rows (n_cmp(t0 - 1)) and after them (n_cmp(t0 + S - 1)), on the absolute schedule
+    const int n0 = ncmp_of(t0, L->l, L->d), n1 = ncmp_of(S_kv, L->l, L->d);
+    NSA_CHECK_ARG(n1 <= kv->n_cmp_max, "layer_decode_rows: compressed cache too small");
+
+    // 1. fused QKV projection of the B S rows, each rotated and appended at its own position t0 + s
+    const RopeAppendParams RP = rope_append_params(L, kv, ws + W.proj, Q, S, t0);
+    if (int rc = launch_qkv_rope_append(RP, x, L->W_qkv, L->dim, dt, st, norm_w, norm_eps, true)) return rc;
+    // 2. the compressed tokens whose windows complete inside the call
+    if (n1 > n0)
+        if (int rc = nsa_cmp_pool_append(L, kv, n0, n1, stream)) return rc;
+    const CacheStrides C(L, kv);
+    // 3. selected branch: every row's scores -> top-n at its token -> attention over K_sel[:t + 1] (one launch, or the separate launches)
+    if (int rc = nsa_sel_decode_rows(Q, kv->K_cmp, kv->K_sel, kv->V_sel, csc_ptr, csc_rows, csc_vals, ranges, Osel, B, S, G, h, Dk, Dv, n1, S_sel,
+                                     S_kv, L->l, L->d, L->l_sel, L->n_sel, t0, C.kcb, C.kcg, Dk, C.ksb, C.ksg, Dk, C.vsb, C.vsg, Dv, dt, C.scale,
+                                     ws + W.sel, W.sel_bytes, stream))
+        return rc;
+    // 4. sliding and compressed branches of the S rows: one launch in split form with the combine left to the finish kernel, else one each
+    const int defer = Dv == 64 ? 1 : 0;
+    DecodeFinishParams F{};
+    F.Q = Q; F.O_out = Omix; F.gates_out = gates_out;
+    F.w1 = L->gate_w1; F.b1 = L->gate_b1; F.w2 = L->gate_w2; F.b2 = L->gate_b2;
+    F.R = (int64_t)M * G; F.h = h; F.Dk = Dk; F.Dv = Dv; F.Hd = L->gate_hidden; F.tau = L->gate_tau;
+    F.O[0] = Ocmp; F.O[1] = Osel; F.O[2] = Owin;
+    F.ns[1] = 1;
+    int ns_band = 1;
+    if (band_pair_dual(L, kv, C, S, n1, defer, &ns_band)) {
+        DecBandPair BP{};
+        band_pair_fill(BP, L, kv, C, Q, Owin, Ocmp, S, t0, n1, ns_band, (float *)(ws + W.band), (float *)(ws + W.band2));
+        if (int rc = launch_band_attn_fwd_dual(BP.w, BP.c, dt, st)) return rc;
+        F.ns[2] = F.ns[0] = ns_band;
+        F.part[2] = BP.w.part;
+        F.part[0] = BP.c.part;
+    } else {
+        if (int rc = band_attn_fwd_impl(Q, kv->K_win, kv->V_win, Owin, nullptr, B, S, G, h, Dk, Dv, S_kv, C.ksb, C.ksg, Dk, C.vsb, C.vsg, Dv, t0, 0, 1,
+                                        0, L->w, dt, C.scale, 0, ws + W.band, W.band_bytes, stream, defer, &F.ns[2]))
+            return rc;
+        F.part[2] = (const float *)(ws + W.band);
+        if (int rc = band_attn_fwd_impl(Q, kv->K_cmp, kv->V_cmp, Ocmp, nullptr, B, S, G, h, Dk, Dv, n1, C.kcb, C.kcg, Dk, C.vcb, C.vcg, Dv, t0, L->l,
+                                        L->d, 1, 1 << 30, dt, C.scale, 0, ws + W.band2, W.band_bytes, stream, defer, &F.ns[0]))
+            return rc;
+        F.part[0] = (const float *)(ws + W.band2);
+    }
+    // 5. split combine + gates + mix, 6. output projection of the B S rows
+    if (defer) {
+        if (int rc = launch_decode_finish(F, dt, st)) return rc;
+    } else {
+        if (int rc = nsa_gate_combine(L, Q, Ocmp, Osel, Owin, Omix, gates_out, (int64_t)M * G, stream)) return rc;
+    }
+    return launch_linear_small_epi(Omix, L->W_out, y, M, L->dim, NO, dt, residual ? 2 : 0, residual, st);
+}
+
+size_t nsa_layer_decode_rows_workspace(const nsa_layer_desc *L, int B, int S, int S_max) {
+    if (!L || !dtype_ok(L->dtype) || B < 1 || S < 1 || S > LAYER_ROWS_MAX_S || S_max < 1) return 0;
+    return decode_ws(L, B, S_max, S).total;
+}
+
+int nsa_layer_decode_rows(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *x, void *y, int t0, int S, const int32_t *csc_ptr,
+                          const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out, float *gates_out, void *workspace,
+                          size_t workspace_bytes, void *stream) {
+    return layer_decode_rows_impl(L, kv, x, y, t0, S, csc_ptr, csc_rows, csc_vals, S_sel, ranges_out, gates_out, workspace, workspace_bytes, stream,
+                                  nullptr);
+}
+
+int nsa_layer_decode_rows_plan(const nsa_layer_desc *L, int B, int S, int S_max, int t0, int S_sel, int *launches, int *route) {
+    NSA_CHECK_ARG(launches && route, "layer_decode_rows_plan: null pointer");
+    *launches = 0;
+    *route = -1;
+    int n = 0, r = -1;
+    NSA_CHECK_ARG(layer_decode_rows_route(L, B, S, S_max, t0, S_sel, &n, &r), "layer_decode_rows_plan: a shape nsa_layer_decode_rows refuses");
+    const int sw = tuning(TUNE_LAYER_DECODE_ROWS);
+    if (sw == 0 || (sw < 0 && !layer_decode_rows_measured_ok(B, S, t0))) return NSA_OK;  // declined: S single steps
+    *launches = n;
+    *route = r;
+    return NSA_OK;
 }
 
 // block workspace: xn | h | hn | u [B, mlp_hidden] | layer decode workspace

@@ -134,6 +134,21 @@ class NSA_KV:
         self.meta_seq_len = seq_len
         return self.meta
 
+    def truncate(self, t: int) -> None:
+        """forget every token from position t on (0 <= t <= self.t): what a speculative decoder calls after rejecting draft tokens.
+        Sets t and n_cmp = n_cmp(t) and drops the read counters of the forgotten tokens: the last self.t - t entries of the five reads_*
+        lists, which leaves t entries where every token was decoded (a prefill appends none, so a list may be shorter than t and then only
+        loses what the decode steps behind the prefill added).  The buffers are left as they are: the next append overwrites row t, and
+        the emission schedule overwrites compressed row n_cmp when its window completes again."""
+        t = int(t)
+        if t < 0 or t > self.t:
+            raise ValueError(f"NSA_KV.truncate: t = {t} outside [0, {self.t}]")
+        drop = self.t - t
+        self.t = t
+        self.n_cmp = 0 if t < self.l else (t - self.l) // self.d + 1
+        for lst in (self.reads_pred, self.reads_act_total, self.reads_act_sel, self.reads_act_cmp, self.reads_act_win):
+            del lst[max(0, len(lst) - drop):]
+
     def append_reads(self, num_cmp: int, S_raw: int) -> None:
         sel, win = self.n_sel * self.l_sel, min(self.w, S_raw)
         total = num_cmp + sel + win  # the reads formula of nsa_attention.py:634-635

@@ -720,6 +720,87 @@ class NSAAttention(nn.Module):
         _set_plain(self, "_last_gates", gates)
         return y, kv
 
+    # ---- decode step for S consecutive tokens (k draft tokens to verify, the tail of a chunked prefill) ------------------------------
+    def decode_rows_plan(self, B: int, S: int, S_max: int, t0: int, S_sel: int) -> dict:
+        """what nsa_layer_decode_rows does with a shape under the current tuning switches (nsa_layer_decode_rows_plan, no device call):
+        {"launches", "route": 1 the selected branch in its one-launch rows form / 0 its separate launches / -1 declined (S single steps)}"""
+        desc, _ = self._layer_desc()
+        n, r = ctypes.c_int(0), ctypes.c_int(0)
+        rc = _lib.lib().nsa_layer_decode_rows_plan(ctypes.byref(desc), int(B), int(S), int(S_max), int(t0), int(S_sel), ctypes.byref(n),
+                                                   ctypes.byref(r))
+        _lib.check(rc, "nsa_layer_decode_rows_plan")
+        return {"launches": n.value, "route": r.value}
+
+    def decode_rows(self, x: torch.Tensor, kv: NSA_KV):
+        """x [B,S,dim], 1 <= S <= 16: the S tokens of positions kv.t .. kv.t + S - 1 in ONE native call (nsa_layer_decode_rows) -> (y [B,S,dim],
+        kv) with the caches, read counters, ranges (_last_ranges [B,S,G,n,2]) and gates (_last_gates [B,S,G,3]) of S decode steps.  Inference
+        only.  Where the native route does not apply (parity mode, a dtype or device the kernels do not take, a declining plan) it IS S
+        decode steps, concatenated; a failed native call is counted and, unless NSA_HIP_STRICT, falls back to them as well."""
+        assert x.dim() == 3, "x must be [B,S,dim]"
+        B, S, _ = x.shape
+        if not 1 <= S <= 16:
+            raise ValueError(f"NSAAttention.decode_rows takes 1 to 16 tokens per sequence, got S={S}")
+        self._check_kv(x, kv)
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise RuntimeError("NSAAttention.decode_rows is inference only (no backward); run it under torch.no_grad()")
+        if not x.is_contiguous():
+            x = x.contiguous()
+        if not self._native_ok(x):
+            return self._decode_rows_steps(x, kv)
+        t0, meta = self._extend_begin(kv, S)
+        if self.decode_rows_plan(B, S, self._kv_desc(kv).S_max, t0, int(meta.S_sel))["route"] < 0:
+            return self._decode_rows_steps(x, kv)
+        saved = (kv.t, kv.n_cmp, len(kv.reads_pred))
+        try:
+            return self._decode_rows_native(x, kv)
+        except RuntimeError as e:  # forward's router: counted; strict or a device error raises; else the S single steps from the saved state
+            self._fallback_counters["selection_hip_fails"] += 1
+            self._fallback_counters["total_fallbacks"] += 1
+            self._last_error = str(e)
+            if self._strict or "HIP error" in str(e):
+                raise
+            warnings.warn(f"nsa_vibe_amd: the one-call decode step for {S} tokens failed ({e}); falling back to {S} single steps", RuntimeWarning)
+            try:
+                kv.t, kv.n_cmp = saved[0], saved[1]
+                for lst in (kv.reads_pred, kv.reads_act_total, kv.reads_act_sel, kv.reads_act_cmp, kv.reads_act_win):
+                    del lst[saved[2]:]
+                return self._decode_rows_steps(x, kv)
+            except Exception as e2:
+                raise e2 from e
+
+    def _decode_rows_steps(self, x: torch.Tensor, kv: NSA_KV):
+        """S decode steps, concatenated: the definition of decode_rows' result"""
+        ys, rs, gs = [], [], []
+        for s in range(x.shape[1]):
+            y, kv = self._decode(x[:, s:s + 1], kv)
+            ys.append(y)
+            rs.append(self._last_ranges.unsqueeze(1).clone())  # (the native step writes every step's ranges and gates into the same tensors)
+            gs.append(self._last_gates.reshape(x.shape[0], 1, self.n_kv_groups, 3).clone())
+        _set_plain(self, "_last_ranges", torch.cat(rs, dim=1))
+        _set_plain(self, "_last_gates", torch.cat(gs, dim=1))
+        return torch.cat(ys, dim=1), kv
+
+    def _decode_rows_native(self, x: torch.Tensor, kv: NSA_KV):
+        B, S, _ = x.shape
+        t0, meta = self._extend_begin(kv, S)
+        L, dev = _lib.lib(), x.device
+        desc, _ = self._layer_desc()
+        kd = self._kv_desc(kv)
+        ranges = torch.empty((B, S, self.n_kv_groups, self.n_sel, 2), dtype=torch.int32, device=dev)
+        gates = torch.empty((B, S, self.n_kv_groups, 3), dtype=torch.float32, device=dev)
+        y = torch.empty((B, S, self.dim), dtype=x.dtype, device=dev)
+        ws = workspace(dev, L.nsa_layer_decode_rows_workspace(ctypes.byref(desc), B, S, kd.S_max) + 256, "layer_decode_rows")
+        wptr = (ws.data_ptr() + 255) & ~255
+        cptr, crows, cvals = meta.device_csc(dev)
+        rc = L.nsa_layer_decode_rows(ctypes.byref(desc), ctypes.byref(kd), x.data_ptr(), y.data_ptr(), t0, S, cptr.data_ptr(), crows.data_ptr(),
+                                     cvals.data_ptr(), int(meta.S_sel), ranges.data_ptr(), gates.data_ptr(), wptr,
+                                     ws.numel() - (wptr - ws.data_ptr()), _stream(dev))
+        _lib.check(rc, "nsa_layer_decode_rows")
+        self._extend_end(kv, t0, S)
+        _set_plain(self, "_last_ranges", ranges)
+        _set_plain(self, "_last_gates", gates)
+        return y, kv
+
     def _decode(self, x: torch.Tensor, kv: NSA_KV, one_call: bool = True):
         if one_call and self._native_ok(x):
             return self._decode_native(x, kv)
