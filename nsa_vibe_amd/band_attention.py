@@ -20,7 +20,7 @@ import torch
 
 from . import _lib
 from .selection_attention import _bwd_variant
-from .selection_scorer import _DT, _need_gpu, _stream, workspace
+from .selection_scorer import _DT, _need_gpu, _scale_arg, _stream, _ws_args, workspace, workspace_at
 
 _W_INF = 2 ** 30
 
@@ -57,8 +57,8 @@ def _fwd(Q, K, V, band, scale, variant, want_lse):
     rc = L.nsa_band_attn_fwd(Qc.data_ptr(), Kc.data_ptr() if S_kv else None, Vc.data_ptr() if S_kv else None, O.data_ptr(),
                              lse.data_ptr() if lse is not None else None, B, S, G, h, Dk, Dv, S_kv,
                              Kc.stride(0), Kc.stride(1), Kc.stride(2), Vc.stride(0), Vc.stride(1), Vc.stride(2),
-                             int(t0), int(a), int(dd), int(c), int(min(w, _W_INF)), dt, float(scale) if scale else 0.0, int(variant),
-                             ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, _stream(dev))
+                             int(t0), int(a), int(dd), int(c), int(min(w, _W_INF)), dt, _scale_arg(scale), int(variant),
+                             *_ws_args(ws), _stream(dev))
     _lib.check(rc, "nsa_band_attn_fwd")
     return O, lse, (Qc, Kc, Vc)
 
@@ -85,13 +85,12 @@ class _BandAttnFn(torch.autograd.Function):
         dV = torch.empty((B, G, S_kv, Dv), dtype=torch.float32, device=dev)
         L = _lib.lib()
         dt = _DT[Qc.dtype]
-        ws = workspace(dev, L.nsa_band_attn_bwd_workspace(B, S, G, h, Dk, Dv, S_kv, dt, ctx.bwd_variant) + 256, "band_bwd")
-        wptr = (ws.data_ptr() + 255) & ~255
+        wptr, wsize, _ = workspace_at(dev, L.nsa_band_attn_bwd_workspace(B, S, G, h, Dk, Dv, S_kv, dt, ctx.bwd_variant), "band_bwd", 256)
         rc = L.nsa_band_attn_bwd(Qc.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), O.data_ptr(), lse.data_ptr(), dO.data_ptr(), dQ.data_ptr(),
                                  dK.data_ptr(), dV.data_ptr(), B, S, G, h, Dk, Dv, S_kv,
                                  Kc.stride(0), Kc.stride(1), Kc.stride(2), Vc.stride(0), Vc.stride(1), Vc.stride(2),
-                                 int(t0), int(a), int(dd), int(c), int(min(w, _W_INF)), dt, float(ctx.scale) if ctx.scale else 0.0,
-                                 int(ctx.bwd_variant), wptr, ws.numel() - (wptr - ws.data_ptr()), _stream(dev))
+                                 int(t0), int(a), int(dd), int(c), int(min(w, _W_INF)), dt, _scale_arg(ctx.scale),
+                                 int(ctx.bwd_variant), wptr, wsize, _stream(dev))
         _lib.check(rc, "nsa_band_attn_bwd")
         return dQ, dK.to(Kc.dtype), dV.to(Vc.dtype), None, None, None, None
 

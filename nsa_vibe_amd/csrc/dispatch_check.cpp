@@ -27,6 +27,8 @@ static hipError_t g_last = hipSuccess;
 static std::vector<std::string> g_geom;
 static int g_peek_launch = -1;  // copy g_peek bytes of this launch's first kernel argument (an argument block passed by value)
 static std::vector<unsigned char> g_peek;
+static int g_peek_arg2 = -1;  // and g_peek2 bytes of this further argument of the same launch
+static std::vector<unsigned char> g_peek2;
 struct Config {
     dim3 grid, block;
     size_t shmem;
@@ -84,6 +86,7 @@ __attribute__((visibility("default"))) hipError_t hipLaunchKernel(const void *, 
     snprintf(s, sizeof(s), "%u,%u,%u/%u,%u,%u/%zu", grid.x, grid.y, grid.z, block.x, block.y, block.z, shmem);
     g_geom.push_back(s);
     if (i == g_peek_launch && !g_peek.empty()) memcpy(g_peek.data(), args[0], g_peek.size());
+    if (i == g_peek_launch && g_peek_arg2 >= 0) memcpy(g_peek2.data(), args[g_peek_arg2], g_peek2.size());
     if (i == g_refuse_at) return g_last = REFUSED;
     return hipSuccess;
 }
@@ -131,9 +134,11 @@ static std::string list(const std::vector<std::string> &v) {
 
 // Walks the route of one call: refuses launch 0, 1, 2, ... until the call ends without a refused launch.  `after` may add fields
 // ("key": value, ...) from what the complete call left behind.
+static std::vector<std::string> g_names;  // the launchers of the call walked last
 static void run(const char *label, const std::function<int()> &call, const std::function<std::string()> &after = nullptr) {
     auto last_error = NSA_FN(nsa_hip_last_error);
-    std::vector<std::string> names;
+    std::vector<std::string> &names = g_names;
+    names.clear();
     int rc = 0;
     std::string err;
     for (int n = 0; n < 64; ++n) {
@@ -150,10 +155,13 @@ static void run(const char *label, const std::function<int()> &call, const std::
         }
         break;
     }
-    printf("%s\n%s: {\"rc\": %d, \"error\": %s, \"launches\": %s, \"geometry\": %s, \"memsets\": %d%s%s}", g_first ? "" : ",", quoted(label).c_str(),
-           rc, quoted(err).c_str(), list(names).c_str(), list(g_geom).c_str(), g_memsets, after ? ", " : "", after ? after().c_str() : "");
+    const std::string geometry = list(g_geom);
+    const int memsets = g_memsets;
+    const std::string more = after ? ", " + after() : "";  // (last: `after` may call the entry point again)
+    printf("%s\n%s: {\"rc\": %d, \"error\": %s, \"launches\": %s, \"geometry\": %s, \"memsets\": %d%s}", g_first ? "" : ",", quoted(label).c_str(), rc,
+           quoted(err).c_str(), list(names).c_str(), geometry.c_str(), memsets, more.c_str());
     g_first = false;
-    g_peek_launch = -1;
+    g_peek_launch = g_peek_arg2 = -1;
     g_peek.clear();
 }
 
@@ -179,6 +187,54 @@ static std::string peeked_scale() {
     char s[64];
     snprintf(s, sizeof(s), "\"scale\": %.9g", (double)p.scale);
     return s;
+}
+
+// ---- the argument blocks of the one-launch decode step (decode_step_kernel(DecStepParams, SelectParams, int, DecAttnArgs, DecBandPair)):
+// every scalar member, and for a pointer the test buffer it points into and the offset -- what tells two swapped neighbours of a
+// positional list apart where the launch geometry does not
+struct Named {
+    const char *name;
+    const void *base;
+    size_t bytes;
+};
+static std::vector<Named> g_named;
+static std::string where(const void *p) {
+    if (!p) return "null";
+    for (const Named &b : g_named)
+        if ((const unsigned char *)p >= (const unsigned char *)b.base && (const unsigned char *)p < (const unsigned char *)b.base + b.bytes)
+            return std::string(b.name) + "+" + std::to_string((const unsigned char *)p - (const unsigned char *)b.base);
+    return "other";
+}
+// walks `call` like run(), then calls it once more to copy the blocks of its decode_step / decode_rows launch ("step": null without one)
+static void run_step(const char *label, const std::function<int()> &call) {
+    run(label, call, [&] {
+        int at = -1;
+        for (size_t i = 0; i < g_names.size(); ++i)
+            if (g_names[i] == "decode_step launch" || g_names[i] == "decode_rows launch") at = (int)i;
+        if (at < 0) return std::string("\"step\": null");
+        nsa::DecStepParams P;
+        nsa::DecAttnArgs A;
+        g_peek_launch = at;
+        g_peek.assign(sizeof(P), 0);
+        g_peek_arg2 = 3;
+        g_peek2.assign(sizeof(A), 0);
+        g_refuse_at = -1;
+        g_launches = 0;
+        call();
+        memcpy(&P, g_peek.data(), sizeof(P));
+        memcpy(&A, g_peek2.data(), sizeof(A));
+        char s[1024];
+        snprintf(s, sizeof(s),
+                 "\"step\": {\"Q\": \"%s\", \"Kc\": \"%s\", \"part_g\": \"%s\", \"halo_g\": \"%s\", \"pg_g\": \"%s\", \"cnt\": \"%s\", \"R\": %d, \"G\": %d, "
+                 "\"h\": %d, \"S_cmp\": %d, \"S_sel\": %d, \"NS\": %d, \"nchunk\": %d, \"cpg\": %d, \"t_token\": %d, \"spin\": %d, \"csb\": %lld, \"csg\": %lld, "
+                 "\"css\": %lld, \"c2\": %.9g, \"S\": %d}, \"attn\": {\"Q\": \"%s\", \"K\": \"%s\", \"V\": \"%s\", \"O\": \"%s\", \"G\": %d, \"h\": %d, "
+                 "\"S_kv\": %d, \"n\": %d, \"ksb\": %lld, \"ksg\": %lld, \"kss\": %lld, \"vsb\": %lld, \"vsg\": %lld, \"vss\": %lld, \"c2\": %.9g}",
+                 where(P.Q).c_str(), where(P.Kc).c_str(), where(P.part_g).c_str(), where(P.halo_g).c_str(), where(P.pg_g).c_str(), where(P.cnt).c_str(), P.R,
+                 P.G, P.h, P.S_cmp, P.S_sel, P.NS, P.nchunk, P.cpg, P.t_token, P.spin, (long long)P.csb, (long long)P.csg, (long long)P.css, (double)P.c2,
+                 P.S, where(A.Q).c_str(), where(A.K).c_str(), where(A.V).c_str(), where(A.O).c_str(), A.G, A.h, A.S_kv, A.n, (long long)A.ksb,
+                 (long long)A.ksg, (long long)A.kss, (long long)A.vsb, (long long)A.vsg, (long long)A.vss, (double)A.c2);
+        return std::string(s);
+    });
 }
 
 int main(int argc, char **argv) {
@@ -379,6 +435,55 @@ int main(int argc, char **argv) {
     L.Dk = L.Dv = 128;
     run("layer_decode_step/D128_t100", [&] { return decode(100); });
     run("layer_prefill/D128_S100", [&] { return prefill(100); });
+
+    // ---- the decode-step family (m7c layer, capacity 1024), with the argument blocks of the one-launch kernels
+    L.Dk = L.Dv = 64;
+    g_named = {{"Q", Q, MB}, {"O", O, MB}, {"ranges", ranges, MB}, {"ws", ws, 64 * MB}, {"K_sel", kv.K_sel, MB}, {"V_sel", kv.V_sel, MB}, {"K_cmp", Kcmp, MB}};
+    const int64_t csb = (int64_t)L.G * 1024 * D, csg = (int64_t)1024 * D, ccb = (int64_t)L.G * 63 * D, ccg = (int64_t)63 * D;
+    auto ncmp = [](int S_) { return S_ < 32 ? 0 : (S_ - 32) / 16 + 1; };
+    auto sel_step_fn = NSA_FN(nsa_sel_decode_step);
+    auto sel_step_need = [&](int t, int n_top) { return NSA_FN(nsa_sel_decode_step_workspace)(1, L.G, L.h, D, D, ncmp(t + 1), S_sel_max, n_top, dt); };
+    auto sel_step = [&](int t, void *Kc_ = nullptr, int n_top = 16, size_t ws_bytes = 64 * MB) {
+        return sel_step_fn(Q, Kc_ ? Kc_ : Kcmp, kv.K_sel, kv.V_sel, csc_ptr, csc_rows, csc_vals, ranges, O, 1, L.G, L.h, D, D, ncmp(t + 1), S_sel_max, t + 1, 32, 16, 64,
+                           n_top, t, ccb, ccg, D, csb, csg, D, csb, csg, D, dt, 0.f, ws, ws_bytes, nullptr);
+    };
+    run_step("sel_decode_step/t100", [&] { return sel_step(100); });
+    run_step("sel_decode_step/t5_no_compressed_token", [&] { return sel_step(5); });
+    run_step("sel_decode_step/K_cmp_8_bytes_off", [&] { return sel_step(100, off(Kcmp, 8)); });
+    run_step("sel_decode_step/n_top_2", [&] { return sel_step(100, nullptr, 2); });
+    run_step("sel_decode_step/workspace_one_byte_short", [&] { return sel_step(100, nullptr, 16, sel_step_need(100, 16) - 1); });
+    auto sel_rows_fn = NSA_FN(nsa_sel_decode_rows);
+    auto sel_rows = [&](int t0, int S_, void *K_ = nullptr) {
+        return sel_rows_fn(Q, Kcmp, K_ ? K_ : kv.K_sel, kv.V_sel, csc_ptr, csc_rows, csc_vals, ranges, O, 1, S_, L.G, L.h, D, D, ncmp(t0 + S_), S_sel_max, t0 + S_, 32, 16,
+                           64, 16, t0, ccb, ccg, D, csb, csg, D, csb, csg, D, dt, 0.f, ws, 64 * MB, nullptr);
+    };
+    run_step("sel_decode_rows/t100_S4", [&] { return sel_rows(100, 4); });
+    run_step("sel_decode_rows/t31_S2_first_compressed_token", [&] { return sel_rows(31, 2); });
+    run_step("sel_decode_rows/t20_S4_no_compressed_token_at_t0", [&] { return sel_rows(20, 4); });
+    run_step("sel_decode_rows/t100_S17", [&] { return sel_rows(100, 17); });
+    set_tuning("DECODE_ROWS", 0);
+    run_step("sel_decode_rows/t100_S4_DECODE_ROWS_0", [&] { return sel_rows(100, 4); });
+    set_tuning("DECODE_ROWS", -1);
+    run_step("sel_decode_rows/t100_S4_K_2_bytes_off", [&] { return sel_rows(100, 4, off(kv.K_sel, 2)); });
+    auto layer_rows_fn = NSA_FN(nsa_layer_decode_rows);
+    auto layer_rows = [&](int t0, int S_, size_t ws_bytes = 64 * MB) {
+        return layer_rows_fn(&L, &kv, x, y, t0, S_, csc_ptr, csc_rows, csc_vals, S_sel_max, nullptr, nullptr, ws, ws_bytes, nullptr);
+    };
+    const size_t need_r = NSA_FN(nsa_layer_decode_rows_workspace)(&L, 1, 4, 1024);
+    run_step("layer_decode_rows/t100_S4", [&] { return layer_rows(100, 4); });
+    run_step("layer_decode_rows/t100_S1", [&] { return layer_rows(100, 1); });
+    run_step("layer_decode_rows/t30_S4_pooling", [&] { return layer_rows(30, 4); });
+    run_step("layer_decode_rows/workspace_exact", [&] { return layer_rows(100, 4, need_r); });
+    run_step("layer_decode_rows/workspace_one_byte_short", [&] { return layer_rows(100, 4, need_r - 1); });
+    run_step("layer_decode_rows/S17", [&] { return layer_rows(100, 17); });
+    run_step("layer_decode_rows/past_capacity", [&] { return layer_rows(1021, 4); });
+    for (int band : {0, 1}) {  // the tail's other two arms: the band pair as its own dual launch, and riding without the merge
+        set_tuning("DECODE_BAND", band);
+        run_step(("layer_decode_step/t100_DECODE_BAND_" + std::to_string(band)).c_str(), [&] { return decode(100); });
+    }
+    set_tuning("DECODE_BAND", -1);
+    L.Dk = L.Dv = 128;
+    run_step("layer_decode_rows/D128_t100_S4", [&] { return layer_rows(100, 4); });
     printf("\n}\n");
     return 0;
 }

@@ -609,50 +609,78 @@ size_t nsa_sel_decode_step_workspace(int B, int G, int h, int Dk, int Dv, int S_
     return SelDecodeWs(B, G, h, Dk, Dv, S_cmp, S_sel, n_top, dtype).total();
 }
 
+// nsa_sel_decode_rows: scorer scratch (a) | p_grp (p) | attention scratch (c) of the separate launches; the one-launch form needs none
+struct SelDecodeRowsWs {
+    size_t a, p, c;
+    SelDecodeRowsWs(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int n_top, int dtype)
+        : a(align16(std::max(nsa_sel_scores_rows_workspace(B, S, G, h, Dk, S_cmp, S_sel, 0, 0, 0, dtype, 1, 1),
+                             S_cmp >= 1 ? nsa_sel_scores_rows_workspace(B, S, G, h, Dk, S_cmp, S_sel, 0, 0, 0, dtype, 3, 1) : (size_t)0))),
+          p(align16(sizeof(float) * (size_t)B * S * G * (size_t)(S_sel > 0 ? S_sel : 1))),
+          c(align16(nsa_sel_attn_fwd_workspace_kv(B, S, G, h, Dk, Dv, 64 * (S_sel > 0 ? S_sel : 1), n_top, dtype))) {}
+    size_t total() const { return a + p + c; }
+};
+
+size_t nsa_sel_decode_rows_workspace(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int n_top, int dtype) {
+    if (B < 1 || S < 1 || G < 1 || h < 1) return 0;
+    return SelDecodeRowsWs(B, S, G, h, Dk, Dv, S_cmp, S_sel, n_top, dtype).total();
+}
+
 }  // extern "C"
 
-int nsa::sel_decode_step_impl(const void *Q, const void *K_cmp, const void *K, const void *V, const int32_t *csc_ptr, const int32_t *csc_rows,
-                              const float *csc_vals, int32_t *ranges_out, void *O, int B, int G, int h, int Dk, int Dv, int S_cmp, int S_sel,
-                              int S_kv, int l, int d, int l_sel, int n_top, int t_token, int64_t kcb, int64_t kcg, int64_t kcs, int64_t ksb,
-                              int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg, int64_t vss, int dtype, float scale, void *workspace,
-                              size_t workspace_bytes, void *stream, int defer, int *ns_used, float **part_used, const DecBandPair *band,
-                              int *band_taken) {
+int nsa::sel_decode_step_impl(const SelDecodeCall &c, void *workspace, size_t workspace_bytes, void *stream, int defer, int *ns_used,
+                              float **part_used, const DecBandPair *band, int *band_taken) {
     if (band_taken) *band_taken = 0;
-    const SelDecodeWs W(B, G, h, Dk, Dv, S_cmp, S_sel, n_top, dtype);
-    NSA_CHECK_ARG(workspace && ((uintptr_t)workspace % 16 == 0) && workspace_bytes >= W.total(),
-                  "decode_step: workspace missing, misaligned or too small");
-    NSA_CHECK_ARG(n_top >= 1 && n_top <= 64, "decode_step: n_top must be in [1,64]");
+    const SelDecodeWs W(c.B, c.G, c.h, c.Dk, c.Dv, c.S_cmp, c.S_sel, c.n_top, c.dtype);
+    NSA_CHECK_ARG(workspace && ((uintptr_t)workspace % 16 == 0) && workspace_bytes >= W.total(), "decode_step: workspace missing, misaligned or too small");
+    NSA_CHECK_ARG(c.n_top >= 1 && c.n_top <= 64, "decode_step: n_top must be in [1,64]");
     unsigned char *w = (unsigned char *)workspace;
     const size_t a = W.a, p = W.p;
     float *p_grp = (float *)(w + a);
-    int rc;
-    const float sc = default_scale(scale, Dk);
-    const int stencil = (l == 2 * d && l_sel == 4 * d) ? 1 : 0;  // Eq.9 in closed form (the fused kernel then reads no CSC arrays)
-    if (decode_step_supported((int64_t)B * G, dtype, h, Dk, Dv, S_cmp, S_sel, S_kv, l, d, l_sel, n_top, t_token, kcb, kcg, kcs, ksb, ksg, kss, vsb, vsg, vss, Q, K_cmp,
-                              K, V)) {  // scores -> statistics -> Eq.9/10 -> sequential top-n -> selection attention: ONE launch, O is final
+    const int stencil = (c.l == 2 * c.d && c.l_sel == 4 * c.d) ? 1 : 0;  // Eq.9 in closed form (the fused kernel then reads no CSC arrays)
+    if (decode_step_supported(c)) {  // scores -> statistics -> Eq.9/10 -> sequential top-n -> selection attention: ONE launch, O is final
         if (ns_used) *ns_used = 1;
         if (band && band_taken) *band_taken = 1;
-        return launch_decode_step(Q, K_cmp, K, V, O, ranges_out, B, G, h, S_cmp, S_sel, S_kv, n_top, t_token, kcb, kcg, kcs, ksb, ksg, kss, vsb, vsg,
-                                  vss, dtype, sc, w, a, (hipStream_t)stream, band_taken ? band : nullptr, Dk);
+        return launch_decode_step(c, w, a, (hipStream_t)stream, band_taken ? band : nullptr);
     }
-    if (decode_score_select_supported(dtype, h, Dk, S_cmp, S_sel, kcb, kcg, kcs, Q, K_cmp, (int64_t)B * G)) {
+    if (decode_score_select_supported(c.dtype, c.h, c.Dk, c.S_cmp, c.S_sel, c.kcb, c.kcg, c.kcs, c.Q, c.K_cmp, c.rows())) {
         // scores -> statistics -> Eq.9/10 -> sequential top-n in one launch (bit-identical to the route below)
-        rc = launch_decode_score_select(Q, K_cmp, B, G, h, Dk, S_cmp, kcb, kcg, kcs, csc_ptr, csc_rows, csc_vals, S_sel, l_sel, n_top, t_token,
-                                        dtype, sc, ranges_out, (hipStream_t)stream, nullptr, stencil);
-        if (rc) return rc;
+        if (int rc = launch_decode_score_select(c.Q, c.K_cmp, c.B, c.G, c.h, c.Dk, c.S_cmp, c.kcb, c.kcg, c.kcs, c.csc_ptr, c.csc_rows, c.csc_vals,
+                                                c.S_sel, c.l_sel, c.n_top, c.t0, c.dtype, default_scale(c.scale, c.Dk), c.ranges_out,
+                                                (hipStream_t)stream, nullptr, stencil))
+            return rc;
     } else {
-        rc = nsa_sel_scores(Q, K_cmp, p_grp, B, 1, G, h, Dk, S_cmp, kcb, kcg, kcs, csc_ptr, csc_rows, csc_vals, S_sel, l, d, l_sel, 1,
-                            S_cmp >= 1 ? 3 : 1, dtype, scale, w, a, stream);
-        if (rc) return rc;
-        rc = nsa_select_topn_ranges(p_grp, (int64_t)B * G, 1, G, t_token, nullptr, S_sel, l_sel, n_top, 1, 2, NSA_SEL_SEQUENTIAL, 1,
-                                    ranges_out, n_top, stream);
-        if (rc) return rc;
+        if (int rc = nsa_sel_scores(c.Q, c.K_cmp, p_grp, c.B, 1, c.G, c.h, c.Dk, c.S_cmp, c.kcb, c.kcg, c.kcs, c.csc_ptr, c.csc_rows, c.csc_vals, c.S_sel,
+                                    c.l, c.d, c.l_sel, 1, c.S_cmp >= 1 ? 3 : 1, c.dtype, c.scale, w, a, stream))
+            return rc;
+        if (int rc = nsa_select_topn_ranges(p_grp, c.rows(), 1, c.G, c.t0, nullptr, c.S_sel, c.l_sel, c.n_top, 1, 2, NSA_SEL_SEQUENTIAL, 1,
+                                            c.ranges_out, c.n_top, stream))
+            return rc;
     }
     if (part_used) *part_used = (float *)(w + a + p);
-    return sel_attn_fwd_impl(Q, K, V, ranges_out, O, nullptr, B, 1, G, h, Dk, Dv, S_kv, n_top, ksb, ksg, kss, vsb, vsg, vss, dtype, scale, 0,
-                             w + a + p, workspace_bytes - a - p, stream, defer, ns_used);
+    return sel_attn_fwd_impl(c.Q, c.K, c.V, c.ranges_out, c.O, nullptr, c.B, 1, c.G, c.h, c.Dk, c.Dv, c.S_kv, c.n_top, c.ksb, c.ksg, c.kss, c.vsb,
+                             c.vsg, c.vss, c.dtype, c.scale, 0, w + a + p, workspace_bytes - a - p, stream, defer, ns_used);
 }
 
+int nsa::sel_decode_rows_impl(const SelDecodeCall &c, void *workspace, size_t workspace_bytes, void *stream) {
+    NSA_CHECK_ARG(dtype_ok(c.dtype), "decode_rows: unknown dtype %d", c.dtype);
+    NSA_CHECK_ARG(c.B >= 0 && c.S >= 0 && c.G >= 1 && c.h >= 1 && c.Dk >= 1 && c.Dv >= 1 && c.S_cmp >= 0 && c.S_sel >= 1 && c.S_kv >= 1, "decode_rows: bad sizes");
+    NSA_CHECK_ARG(c.n_top >= 1 && c.n_top <= 64, "decode_rows: n_top must be in [1,64]");
+    NSA_CHECK_ARG(c.t0 >= 0 && c.S_kv >= c.t0 + c.S, "decode_rows: the cache must hold the S tokens t0 .. t0 + S - 1");
+    if (c.rows() == 0) return NSA_OK;
+    NSA_CHECK_ARG(c.Q && c.K && c.V && c.O && c.ranges_out, "decode_rows: null pointer");
+    if (decode_rows_supported(c))  // every row's scores -> top-n at its own token -> selection attention over K/V[:t + 1]: ONE launch
+        return launch_decode_rows(c, (hipStream_t)stream);
+    // the separate launches: decode-normalised scores + sequential top-n at t0 + s, then the attention (what an extend of S tokens runs)
+    const SelDecodeRowsWs W(c.B, c.S, c.G, c.h, c.Dk, c.Dv, c.S_cmp, c.S_sel, c.n_top, c.dtype);
+    NSA_CHECK_ARG(workspace && ((uintptr_t)workspace % 16 == 0) && workspace_bytes >= W.total(), "decode_rows: workspace missing, misaligned or too small");
+    unsigned char *w = (unsigned char *)workspace;
+    if (int rc = nsa_sel_scores_select_rows(c.Q, c.K_cmp, (float *)(w + W.a), c.B, c.S, c.G, c.h, c.Dk, c.S_cmp, c.kcb, c.kcg, c.kcs, c.csc_ptr, c.csc_rows,
+                                            c.csc_vals, c.S_sel, c.l, c.d, c.l_sel, 2 /* skipped blocks stay unwritten: only the selector reads p_grp */,
+                                            c.dtype, c.scale, c.t0, c.n_top, 1, 2, NSA_SEL_SEQUENTIAL, c.S, c.ranges_out, c.n_top, c.t0, 1, w, W.a, stream))
+        return rc;
+    return nsa_sel_attn_fwd(c.Q, c.K, c.V, c.ranges_out, c.O, nullptr, c.B, c.S, c.G, c.h, c.Dk, c.Dv, c.S_kv, c.n_top, c.ksb, c.ksg, c.kss, c.vsb, c.vsg,
+                            c.vss, c.dtype, c.scale, 0, w + W.a + W.p, workspace_bytes - W.a - W.p, stream);
+}
 
 extern "C" {
 
@@ -661,9 +689,19 @@ int nsa_sel_decode_step(const void *Q, const void *K_cmp, const void *K, const v
                         int Dv, int S_cmp, int S_sel, int S_kv, int l, int d, int l_sel, int n_top, int t_token, int64_t kcb,
                         int64_t kcg, int64_t kcs, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg, int64_t vss,
                         int dtype, float scale, void *workspace, size_t workspace_bytes, void *stream) {
-    return sel_decode_step_impl(Q, K_cmp, K, V, csc_ptr, csc_rows, csc_vals, ranges_out, O, B, G, h, Dk, Dv, S_cmp, S_sel, S_kv, l, d, l_sel,
-                                n_top, t_token, kcb, kcg, kcs, ksb, ksg, kss, vsb, vsg, vss, dtype, scale, workspace, workspace_bytes, stream, 0,
-                                nullptr, nullptr);
+    const SelDecodeCall c{Q, K_cmp, K, V, csc_ptr, csc_rows, csc_vals, ranges_out, O, B, 1, G, h, Dk, Dv, S_cmp, S_sel, S_kv, l, d, l_sel, n_top, t_token,
+                          kcb, kcg, kcs, ksb, ksg, kss, vsb, vsg, vss, dtype, scale};
+    return sel_decode_step_impl(c, workspace, workspace_bytes, stream, 0, nullptr, nullptr);
+}
+
+int nsa_sel_decode_rows(const void *Q, const void *K_cmp, const void *K, const void *V, const int32_t *csc_ptr, const int32_t *csc_rows,
+                        const float *csc_vals, int32_t *ranges_out, void *O, int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel,
+                        int S_kv, int l, int d, int l_sel, int n_top, int t0, int64_t kcb, int64_t kcg, int64_t kcs, int64_t ksb, int64_t ksg,
+                        int64_t kss, int64_t vsb, int64_t vsg, int64_t vss, int dtype, float scale, void *workspace, size_t workspace_bytes,
+                        void *stream) {
+    const SelDecodeCall c{Q, K_cmp, K, V, csc_ptr, csc_rows, csc_vals, ranges_out, O, B, S, G, h, Dk, Dv, S_cmp, S_sel, S_kv, l, d, l_sel, n_top, t0,
+                          kcb, kcg, kcs, ksb, ksg, kss, vsb, vsg, vss, dtype, scale};
+    return sel_decode_rows_impl(c, workspace, workspace_bytes, stream);
 }
 
 int nsa_sel_decode_step_plan(int B, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int n_top, int dtype, int *launches, int *form,
@@ -673,7 +711,7 @@ int nsa_sel_decode_step_plan(int B, int G, int h, int Dk, int Dv, int S_cmp, int
     NSA_CHECK_ARG(B >= 1 && G >= 1 && h >= 1 && Dk >= 1 && Dv >= 1 && S_cmp >= 0 && S_sel >= 1 && S_kv >= 1 && n_top >= 1 && n_top <= 64,
                   "decode_step_plan: bad sizes");
     const int64_t R = (int64_t)B * G;
-    if (decode_step_shape_plan(R, dtype, h, Dk, Dv, S_cmp, S_sel, S_kv, n_top, form, nsplit)) {
+    if (decode_step_shape_plan(sel_decode_plan_call(B, 1, G, h, Dk, Dv, S_cmp, S_sel, S_kv, n_top, dtype), form, nsplit)) {
         *launches = 1;
         return NSA_OK;
     }
@@ -691,50 +729,6 @@ int nsa_sel_decode_step_plan(int B, int G, int h, int Dk, int Dv, int S_cmp, int
     return NSA_OK;
 }
 
-// ------------------------------------------------------------------------------ decode step for S consecutive tokens
-// workspace: scorer scratch (a) | p_grp (p) | attention scratch (c) of the separate launches; the one-launch form needs none
-struct SelDecodeRowsWs {
-    size_t a, p, c;
-    SelDecodeRowsWs(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int n_top, int dtype)
-        : a(align16(std::max(nsa_sel_scores_rows_workspace(B, S, G, h, Dk, S_cmp, S_sel, 0, 0, 0, dtype, 1, 1),
-                             S_cmp >= 1 ? nsa_sel_scores_rows_workspace(B, S, G, h, Dk, S_cmp, S_sel, 0, 0, 0, dtype, 3, 1) : (size_t)0))),
-          p(align16(sizeof(float) * (size_t)B * S * G * (size_t)(S_sel > 0 ? S_sel : 1))),
-          c(align16(nsa_sel_attn_fwd_workspace_kv(B, S, G, h, Dk, Dv, 64 * (S_sel > 0 ? S_sel : 1), n_top, dtype))) {}
-    size_t total() const { return a + p + c; }
-};
-
-size_t nsa_sel_decode_rows_workspace(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int n_top, int dtype) {
-    if (B < 1 || S < 1 || G < 1 || h < 1) return 0;
-    return SelDecodeRowsWs(B, S, G, h, Dk, Dv, S_cmp, S_sel, n_top, dtype).total();
-}
-
-int nsa_sel_decode_rows(const void *Q, const void *K_cmp, const void *K, const void *V, const int32_t *csc_ptr, const int32_t *csc_rows,
-                        const float *csc_vals, int32_t *ranges_out, void *O, int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel,
-                        int S_kv, int l, int d, int l_sel, int n_top, int t0, int64_t kcb, int64_t kcg, int64_t kcs, int64_t ksb, int64_t ksg,
-                        int64_t kss, int64_t vsb, int64_t vsg, int64_t vss, int dtype, float scale, void *workspace, size_t workspace_bytes,
-                        void *stream) {
-    NSA_CHECK_ARG(dtype_ok(dtype), "decode_rows: unknown dtype %d", dtype);
-    NSA_CHECK_ARG(B >= 0 && S >= 0 && G >= 1 && h >= 1 && Dk >= 1 && Dv >= 1 && S_cmp >= 0 && S_sel >= 1 && S_kv >= 1, "decode_rows: bad sizes");
-    NSA_CHECK_ARG(n_top >= 1 && n_top <= 64, "decode_rows: n_top must be in [1,64]");
-    NSA_CHECK_ARG(t0 >= 0 && S_kv >= t0 + S, "decode_rows: the cache must hold the S tokens t0 .. t0 + S - 1");
-    if ((int64_t)B * S * G == 0) return NSA_OK;
-    NSA_CHECK_ARG(Q && K && V && O && ranges_out, "decode_rows: null pointer");
-    if (decode_rows_supported(B, S, G, dtype, h, Dk, Dv, S_cmp, S_sel, S_kv, l, d, l_sel, n_top, t0, kcb, kcg, kcs, ksb, ksg, kss, vsb, vsg, vss, Q,
-                              K_cmp, K, V))  // every row's scores -> top-n at its own token -> selection attention over K/V[:t + 1]: ONE launch
-        return launch_decode_rows(Q, K_cmp, K, V, O, ranges_out, B, S, G, h, S_cmp, S_sel, S_kv, n_top, t0, kcb, kcg, kcs, ksb, ksg, kss, vsb, vsg,
-                                  vss, dtype, default_scale(scale, Dk), (hipStream_t)stream, Dk);
-    // the separate launches: decode-normalised scores + sequential top-n at t0 + s, then the attention (what an extend of S tokens runs)
-    const SelDecodeRowsWs W(B, S, G, h, Dk, Dv, S_cmp, S_sel, n_top, dtype);
-    NSA_CHECK_ARG(workspace && ((uintptr_t)workspace % 16 == 0) && workspace_bytes >= W.total(), "decode_rows: workspace missing, misaligned or too small");
-    unsigned char *w = (unsigned char *)workspace;
-    if (int rc = nsa_sel_scores_select_rows(Q, K_cmp, (float *)(w + W.a), B, S, G, h, Dk, S_cmp, kcb, kcg, kcs, csc_ptr, csc_rows, csc_vals, S_sel, l, d,
-                                            l_sel, 2 /* skipped blocks stay unwritten: only the selector reads p_grp */, dtype, scale, t0, n_top, 1, 2,
-                                            NSA_SEL_SEQUENTIAL, S, ranges_out, n_top, t0, 1, w, W.a, stream))
-        return rc;
-    return nsa_sel_attn_fwd(Q, K, V, ranges_out, O, nullptr, B, S, G, h, Dk, Dv, S_kv, n_top, ksb, ksg, kss, vsb, vsg, vss, dtype, scale, 0,
-                            w + W.a + W.p, workspace_bytes - W.a - W.p, stream);
-}
-
 // the plan of nsa_sel_decode_rows for a cache that holds exactly the S new tokens behind t0 = S_kv - S (default block geometry, aligned inputs)
 int nsa_sel_decode_rows_plan(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int n_top, int dtype, int *launches,
                              int *form) {
@@ -742,7 +736,7 @@ int nsa_sel_decode_rows_plan(int B, int S, int G, int h, int Dk, int Dv, int S_c
     NSA_CHECK_ARG(dtype_ok(dtype), "decode_rows_plan: unknown dtype %d", dtype);
     NSA_CHECK_ARG(B >= 1 && S >= 1 && G >= 1 && h >= 1 && Dk >= 1 && Dv >= 1 && S_cmp >= 0 && S_sel >= 1 && S_kv >= S && n_top >= 1 && n_top <= 64,
                   "decode_rows_plan: bad sizes");
-    if (decode_rows_shape_plan(B, S, G, dtype, h, Dk, Dv, S_cmp, S_sel, S_kv, n_top, S_kv - S, form, nullptr)) {
+    if (decode_rows_shape_plan(sel_decode_plan_call(B, S, G, h, Dk, Dv, S_cmp, S_sel, S_kv, n_top, dtype), form, nullptr)) {
         *launches = 1;
         return NSA_OK;
     }

@@ -48,6 +48,41 @@ struct CacheStrides {
           vcb((int64_t)L->G * kv->n_cmp_max * L->Dv), vcg((int64_t)kv->n_cmp_max * L->Dv), scale(1.0f / sqrtf((float)L->Dk)) {}
 };
 
+// What the selected-branch decode family (nsa_sel_decode_step / nsa_sel_decode_rows and everything below them) passes around: the arguments
+// of the C ABI, once.  S consecutive tokens per sequence at t0 .. t0 + S - 1; the single step is S = 1 with t0 = its token.
+struct SelDecodeCall {
+    const void *Q, *K_cmp, *K, *V;
+    const int32_t *csc_ptr, *csc_rows;
+    const float *csc_vals;
+    int32_t *ranges_out;
+    void *O;
+    int B, S, G, h, Dk, Dv, S_cmp, S_sel, S_kv;
+    int l, d, l_sel, n_top, t0;
+    int64_t kcb, kcg, kcs, ksb, ksg, kss, vsb, vsg, vss;
+    int dtype;
+    float scale;
+    int64_t rows() const { return (int64_t)B * S * G; }
+};
+// the layer calls' block: rows t0 .. t0 + S - 1 over the caches kv, which then hold t0 + S tokens and n_cmp compressed ones; the caller adds
+// what the caches do not hold (Q, the CSC arrays, ranges_out, O)
+inline SelDecodeCall sel_decode_call(const nsa_layer_desc *L, const nsa_kv_desc *kv, const CacheStrides &C, int S, int t0, int n_cmp, int S_sel) {
+    SelDecodeCall c{};
+    c.K_cmp = kv->K_cmp; c.K = kv->K_sel; c.V = kv->V_sel;
+    c.B = kv->B; c.S = S; c.G = L->G; c.h = L->h; c.Dk = L->Dk; c.Dv = L->Dv; c.S_cmp = n_cmp; c.S_sel = S_sel; c.S_kv = t0 + S;
+    c.l = L->l; c.d = L->d; c.l_sel = L->l_sel; c.n_top = L->n_sel; c.t0 = t0;
+    c.kcb = C.kcb; c.kcg = C.kcg; c.kcs = L->Dk; c.ksb = C.ksb; c.ksg = C.ksg; c.kss = L->Dk; c.vsb = C.vsb; c.vsg = C.vsg; c.vss = L->Dv;
+    c.dtype = L->dtype; c.scale = C.scale;
+    return c;
+}
+
+// the public plan queries' block: no tensors, default block geometry, the S rows at the end of a cache of S_kv tokens
+inline SelDecodeCall sel_decode_plan_call(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int n_top, int dtype) {
+    SelDecodeCall c{};
+    c.B = B; c.S = S; c.G = G; c.h = h; c.Dk = Dk; c.Dv = Dv; c.S_cmp = S_cmp; c.S_sel = S_sel; c.S_kv = S_kv; c.n_top = n_top; c.dtype = dtype;
+    c.l = 32; c.d = 16; c.l_sel = 64; c.t0 = S_kv - S;
+    return c;
+}
+
 // RoPE + append of S tokens at position t0 of the caches kv (the backward passes the gradients in the caches' places)
 inline RopeAppendParams rope_append_params(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *proj, void *Q_out, int S, int t0) {
     RopeAppendParams P{};

@@ -308,103 +308,140 @@ static void band_pair_fill(DecBandPair &BP, const nsa_layer_desc *L, const nsa_k
     PC.part = part_c;
 }
 
+// One layer decode call over S rows per sequence at t0 .. t0 + S - 1: what its prologue checks, carves from the workspace and derives
+struct LayerDecode {
+    const nsa_layer_desc *L;
+    const nsa_kv_desc *kv;
+    DecodeWs W;
+    unsigned char *ws;
+    void *Q, *Ocmp, *Osel, *Owin, *Omix;
+    int S, t0, n0, n1;  // n0 / n1: compressed tokens emitted before the rows (n_cmp(t0 - 1)) and after them (n_cmp(t0 + S - 1))
+};
+constexpr int LAYER_ROWS_MAX_S = 16;
+
+// rows = false: the single step at token t0 (S = 1, its own wording of the position checks, the workspace of one row per sequence)
+static int layer_decode_begin(const char *who, const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *x, void *y, int t0, int S, bool rows,
+                              int S_sel, void *workspace, size_t workspace_bytes, LayerDecode *D) {
+    if (int rc = check_layer(L, who)) return rc;
+    if (int rc = check_kv(kv, who)) return rc;
+    NSA_CHECK_ARG(x && y && L->W_qkv && L->W_out, "%s: null pointer", who);
+    if (!rows) {
+        NSA_CHECK_ARG(t0 >= 0 && t0 < kv->S_max, "%s: position %d outside the cache capacity %d", who, t0, kv->S_max);
+        NSA_CHECK_ARG(S_sel >= 1 && (int64_t)S_sel * L->l_sel >= t0 + 1, "%s: block metadata (S_sel=%d) does not cover token %d", who, S_sel, t0);
+    } else {
+        NSA_CHECK_ARG(S >= 1 && S <= LAYER_ROWS_MAX_S, "%s: 1 to %d tokens per sequence (got %d)", who, LAYER_ROWS_MAX_S, S);
+        NSA_CHECK_ARG(t0 >= 0 && (int64_t)t0 + S <= kv->S_max, "%s: tokens [%d,%d) exceed the cache capacity %d", who, t0, t0 + S, kv->S_max);
+        NSA_CHECK_ARG(S_sel >= 1 && (int64_t)S_sel * L->l_sel >= (int64_t)t0 + S, "%s: block metadata (S_sel=%d) does not cover %d tokens", who, S_sel,
+                      t0 + S);
+    }
+    const DecodeWs W = decode_ws(L, kv->B, kv->S_max, rows ? S : 0);
+    if (int rc = check_workspace(who, workspace, workspace_bytes, W.total)) return rc;
+    unsigned char *ws = (unsigned char *)workspace;
+    *D = LayerDecode{L, kv, W, ws, ws + W.q, ws + W.ocmp, ws + W.osel, ws + W.owin, ws + W.omix, S, t0, ncmp_of(t0, L->l, L->d), ncmp_of(t0 + S, L->l, L->d)};
+    return NSA_OK;
+}
+
+// the selected branch of the call as the decode family's argument block (ranges_out null: the ranges stay in the workspace)
+static SelDecodeCall layer_sel_call(const LayerDecode &D, const CacheStrides &C, const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals,
+                                    int S_sel, int32_t *ranges_out) {
+    SelDecodeCall c = sel_decode_call(D.L, D.kv, C, D.S, D.t0, D.n1, S_sel);
+    c.Q = D.Q; c.csc_ptr = csc_ptr; c.csc_rows = csc_rows; c.csc_vals = csc_vals; c.O = D.Osel;
+    c.ranges_out = ranges_out ? ranges_out : (int32_t *)(D.ws + D.W.ranges);
+    return c;
+}
+
+// the finish kernel's block: one pass merges the splits of all three branches, evaluates the gate and mixes (ns / part: set by the branches)
+static DecodeFinishParams decode_finish_params(const LayerDecode &D, float *gates_out) {
+    const nsa_layer_desc *L = D.L;
+    DecodeFinishParams F{};
+    F.Q = D.Q; F.O_out = D.Omix; F.gates_out = gates_out;
+    F.w1 = L->gate_w1; F.b1 = L->gate_b1; F.w2 = L->gate_w2; F.b2 = L->gate_b2;
+    F.R = (int64_t)D.kv->B * D.S * L->G; F.h = L->h; F.Dk = L->Dk; F.Dv = L->Dv; F.Hd = L->gate_hidden; F.tau = L->gate_tau;
+    F.O[0] = D.Ocmp; F.O[1] = D.Osel; F.O[2] = D.Owin;
+    return F;
+}
+
+// The rest of a call once its selected branch is under way.  The sliding and the compressed branch of the rows: BP = both in split form with the
+// combine left to the finish kernel, as ONE launch of their own unless they rode on the selected branch's (ridden: the single step); null = one
+// band_attn_fwd_impl each.  Then split combine + gates + mix (Dv = 64: the finish kernel), and the output projection of the B S rows.
+static int layer_decode_tail(const LayerDecode &D, const CacheStrides &C, DecodeFinishParams &F, const DecBandPair *BP, bool ridden, float *gates_out,
+                             void *y, const void *residual, void *stream) {
+    const nsa_layer_desc *L = D.L;
+    const nsa_kv_desc *kv = D.kv;
+    hipStream_t st = (hipStream_t)stream;
+    const int B = kv->B, S = D.S, G = L->G, h = L->h, Dk = L->Dk, Dv = L->Dv, dt = L->dtype, t0 = D.t0, defer = Dv == 64 ? 1 : 0;
+    if (BP) {
+        if (!ridden)
+            if (int rc = launch_band_attn_fwd_dual(BP->w, BP->c, dt, st)) return rc;
+        F.ns[2] = F.ns[0] = BP->w.nsplit;
+        F.part[2] = BP->w.part;
+        F.part[0] = BP->c.part;
+    } else {
+        if (int rc = band_attn_fwd_impl(D.Q, kv->K_win, kv->V_win, D.Owin, nullptr, B, S, G, h, Dk, Dv, t0 + S, C.ksb, C.ksg, Dk, C.vsb, C.vsg, Dv, t0, 0,
+                                        1, 0, L->w, dt, C.scale, 0, D.ws + D.W.band, D.W.band_bytes, stream, defer, &F.ns[2]))
+            return rc;
+        F.part[2] = (const float *)(D.ws + D.W.band);
+        if (int rc = band_attn_fwd_impl(D.Q, kv->K_cmp, kv->V_cmp, D.Ocmp, nullptr, B, S, G, h, Dk, Dv, D.n1, C.kcb, C.kcg, Dk, C.vcb, C.vcg, Dv, t0, L->l,
+                                        L->d, 1, 1 << 30, dt, C.scale, 0, D.ws + D.W.band2, D.W.band_bytes, stream, defer, &F.ns[0]))
+            return rc;
+        F.part[0] = (const float *)(D.ws + D.W.band2);
+    }
+    if (defer) {
+        if (int rc = launch_decode_finish(F, dt, st)) return rc;
+    } else {
+        if (int rc = nsa_gate_combine(L, D.Q, D.Ocmp, D.Osel, D.Owin, D.Omix, gates_out, (int64_t)B * S * G, stream)) return rc;
+    }
+    return launch_linear_small_epi(D.Omix, L->W_out, y, B * S, L->dim, G * h * Dv, dt, residual ? 2 : 0, residual, st);
+}
+
 static int layer_decode_step_impl(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *x, void *y, int t, const int32_t *csc_ptr,
                                   const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out, float *gates_out,
                                   void *workspace, size_t workspace_bytes, void *stream, const void *residual, const void *norm_w = nullptr,
                                   float norm_eps = 0.f) {
-    if (int rc = check_layer(L, "layer_decode_step")) return rc;
-    if (int rc = check_kv(kv, "layer_decode_step")) return rc;
-    NSA_CHECK_ARG(x && y && L->W_qkv && L->W_out, "layer_decode_step: null pointer");
-    NSA_CHECK_ARG(t >= 0 && t < kv->S_max, "layer_decode_step: position %d outside the cache capacity %d", t, kv->S_max);
-    NSA_CHECK_ARG(S_sel >= 1 && (int64_t)S_sel * L->l_sel >= t + 1, "layer_decode_step: block metadata (S_sel=%d) does not cover token %d", S_sel, t);
-    const int B = kv->B;
-    const DecodeWs W = decode_ws(L, B, kv->S_max);
-    if (int rc = check_workspace("layer_decode_step", workspace, workspace_bytes, W.total)) return rc;
-    unsigned char *ws = (unsigned char *)workspace;
+    LayerDecode D;
+    if (int rc = layer_decode_begin("layer_decode_step", L, kv, x, y, t, 1, false, S_sel, workspace, workspace_bytes, &D)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const int dt = L->dtype;
-    const int G = L->G, h = L->h, Dk = L->Dk, Dv = L->Dv;
-    const int NO = G * h * Dv;
-    void *proj = ws + W.proj, *Q = ws + W.q, *Ocmp = ws + W.ocmp, *Osel = ws + W.osel, *Owin = ws + W.owin, *Omix = ws + W.omix;
-    int32_t *ranges = ranges_out ? ranges_out : (int32_t *)(ws + W.ranges);
-
-    const RopeAppendParams RP = rope_append_params(L, kv, proj, Q, 1, t);
+    const int dt = L->dtype, B = kv->B, G = L->G, h = L->h, Dk = L->Dk, Dv = L->Dv, NO = G * h * Dv, n_cmp = D.n1;
     // 1+2. fused QKV projection with RoPE + cache append at position t in its epilogue
-    if (int rc = launch_qkv_rope_append(RP, x, L->W_qkv, L->dim, dt, st, norm_w, norm_eps)) return rc;
+    if (int rc = launch_qkv_rope_append(rope_append_params(L, kv, D.ws + D.W.proj, D.Q, 1, t), x, L->W_qkv, L->dim, dt, st, norm_w, norm_eps)) return rc;
     // 3. emit a compressed token when a window completes (nsa_attention.py:588-604)
-    const int S_raw = t + 1;
-    const int n_cmp = ncmp_of(S_raw, L->l, L->d);
     NSA_CHECK_ARG(n_cmp <= kv->n_cmp_max, "layer_decode_step: compressed cache too small");
-    if (S_raw >= L->l && (S_raw - L->l) % L->d == 0)
-        if (int rc = nsa_cmp_pool_append(L, kv, n_cmp - 1, n_cmp, stream)) return rc;
+    if (n_cmp > D.n0)
+        if (int rc = nsa_cmp_pool_append(L, kv, D.n0, n_cmp, stream)) return rc;
     const CacheStrides C(L, kv);
-    const int64_t ksb = C.ksb, ksg = C.ksg, vsb = C.vsb, vsg = C.vsg, kcb = C.kcb, kcg = C.kcg, vcb = C.vcb, vcg = C.vcg;
-    const float scale = C.scale;
     // When the final pass can take split-KV partial records (Dv = 64) the three branches skip their own combine kernels:
     // one kernel then merges the splits of all branches, evaluates the gate and mixes.
     const int defer = Dv == 64 ? 1 : 0;
-    DecodeFinishParams F{};
-    F.Q = Q; F.O_out = Omix; F.gates_out = gates_out;
-    F.w1 = L->gate_w1; F.b1 = L->gate_b1; F.w2 = L->gate_w2; F.b2 = L->gate_b2;
-    F.R = (int64_t)B * G; F.h = h; F.Dk = Dk; F.Dv = Dv; F.Hd = L->gate_hidden; F.tau = L->gate_tau;
-    F.O[0] = Ocmp; F.O[1] = Osel; F.O[2] = Owin;
+    DecodeFinishParams F = decode_finish_params(D, gates_out);
     // 4 + 5. the three branches.  The sliding and the compressed branch run in split-KV form with the combine left to the finish kernel; when
     // the selected branch runs as the one-launch decode step they ride on ITS launch (workgroups behind the step's own: sel_decode_fused.hip),
     // otherwise they are one launch of their own.
     int ns_band = 1;
     const bool dual = band_pair_dual(L, kv, C, 1, n_cmp, defer, &ns_band);
     DecBandPair BP{};
-    BandAttnParams &PW = BP.w, &PC = BP.c;
-    if (dual) band_pair_fill(BP, L, kv, C, Q, Owin, Ocmp, 1, t, n_cmp, ns_band, (float *)(ws + W.band), (float *)(ws + W.band2));
+    if (dual) band_pair_fill(BP, L, kv, C, D.Q, D.Owin, D.Ocmp, 1, t, n_cmp, ns_band, (float *)(D.ws + D.W.band), (float *)(D.ws + D.W.band2));
     const int band_mode = tuning(TUNE_DECODE_BAND);  // 0 own launch, 1 ride, 2 ride + merge in the workgroup, -1 / 3: 2 + the mix in the output projection
     const bool ride = dual && Dk == 64 && band_mode != 0;
-    float *gates = gates_out ? gates_out : (float *)(ws + W.gates);
-    if (ride && band_mode != 1 && h <= 16) {
-        BP.mg.on = 1;
-        BP.mg.Hd = L->gate_hidden;
-        BP.mg.tau = L->gate_tau;
-        BP.mg.gw1 = L->gate_w1; BP.mg.gb1 = L->gate_b1; BP.mg.gw2 = L->gate_w2; BP.mg.gb2 = L->gate_b2;
-        BP.mg.gates = gates;
-    }
+    float *gates = gates_out ? gates_out : (float *)(D.ws + D.W.gates);
+    if (ride && band_mode != 1 && h <= 16) BP.mg = BandMergeArgs{1, L->gate_hidden, L->gate_tau, L->gate_w1, L->gate_b1, L->gate_w2, L->gate_b2, gates};
     float *sel_part = nullptr;
     int band_taken = 0;
-    if (int rc = sel_decode_step_impl(Q, kv->K_cmp, kv->K_sel, kv->V_sel, csc_ptr, csc_rows, csc_vals, ranges, Osel, B, G, h, Dk, Dv, n_cmp,
-                                      S_sel, S_raw, L->l, L->d, L->l_sel, L->n_sel, t, kcb, kcg, Dk, ksb, ksg, Dk, vsb, vsg, Dv, dt, scale,
-                                      ws + W.sel, W.sel_bytes, stream, defer, &F.ns[1], &sel_part, ride ? &BP : nullptr, &band_taken))
+    if (int rc = sel_decode_step_impl(layer_sel_call(D, C, csc_ptr, csc_rows, csc_vals, S_sel, ranges_out), D.ws + D.W.sel, D.W.sel_bytes, stream, defer, &F.ns[1],
+                                      &sel_part, ride ? &BP : nullptr, &band_taken))
         return rc;
     F.part[1] = sel_part;
-    if (dual && band_taken && BP.mg.on) {
-        // O_win, O_cmp (merged by the workgroups that held their splits), O_sel and the row gates are final: with few rows the mix is the
-        // A operand of the output projection -- three launches per step
-        F.ns[2] = F.ns[0] = 1;
-        // (measured: the mix in the projection wins up to 32 rows -- 43.3 -> 40.5 us at B = 32 -- and loses from 64 on, where every one of the
-        // projection's 48 workgroups would redo the mix of all rows: 47.1 -> 50.6 us; DECODE_BAND = 3 takes it at any batch)
-        if (((band_mode < 0 && B <= 32) || band_mode == 3) && F.ns[1] == 1 &&
-            linear_small_mix_supported(dt, B, L->dim, NO, G, Ocmp, Osel, Owin, L->W_out) && Dv == 64)
-            return launch_linear_small_mix(Ocmp, Osel, Owin, gates, L->W_out, y, B, L->dim, NO, G, dt, residual ? 2 : 0, residual, st);
-    } else if (dual) {
-        if (!band_taken)
-            if (int rc = launch_band_attn_fwd_dual(PW, PC, dt, st)) return rc;
-        F.ns[2] = F.ns[0] = ns_band;
-        F.part[2] = PW.part;
-        F.part[0] = PC.part;
-    } else {
-        if (int rc = band_attn_fwd_impl(Q, kv->K_win, kv->V_win, Owin, nullptr, B, 1, G, h, Dk, Dv, S_raw, ksb, ksg, Dk, vsb, vsg, Dv, t, 0, 1, 0,
-                                        L->w, dt, scale, 0, ws + W.band, W.band_bytes, stream, defer, &F.ns[2]))
-            return rc;
-        F.part[2] = (const float *)(ws + W.band);
-        if (int rc = band_attn_fwd_impl(Q, kv->K_cmp, kv->V_cmp, Ocmp, nullptr, B, 1, G, h, Dk, Dv, n_cmp, kcb, kcg, Dk, vcb, vcg, Dv, t, L->l,
-                                        L->d, 1, 1 << 30, dt, scale, 0, ws + W.band2, W.band_bytes, stream, defer, &F.ns[0]))
-            return rc;
-        F.part[0] = (const float *)(ws + W.band2);
-    }
+    if (!(dual && band_taken && BP.mg.on)) return layer_decode_tail(D, C, F, dual ? &BP : nullptr, band_taken != 0, gates_out, y, residual, stream);
+    // O_win, O_cmp (merged by the workgroups that held their splits), O_sel and the row gates are final: with few rows the mix is the
+    // A operand of the output projection -- three launches per step
+    F.ns[2] = F.ns[0] = 1;
+    // (measured: the mix in the projection wins up to 32 rows -- 43.3 -> 40.5 us at B = 32 -- and loses from 64 on, where every one of the
+    // projection's 48 workgroups would redo the mix of all rows: 47.1 -> 50.6 us; DECODE_BAND = 3 takes it at any batch)
+    if (((band_mode < 0 && B <= 32) || band_mode == 3) && F.ns[1] == 1 &&
+        linear_small_mix_supported(dt, B, L->dim, NO, G, D.Ocmp, D.Osel, D.Owin, L->W_out) && Dv == 64)
+        return launch_linear_small_mix(D.Ocmp, D.Osel, D.Owin, gates, L->W_out, y, B, L->dim, NO, G, dt, residual ? 2 : 0, residual, st);
     // 6. split combine + gates + mix, 7. output projection
-    if (defer) {
-        if (int rc = launch_decode_finish(F, dt, st)) return rc;
-    } else {
-        if (int rc = nsa_gate_combine(L, Q, Ocmp, Osel, Owin, Omix, gates_out, (int64_t)B * G, stream)) return rc;
-    }
-    return launch_linear_small_epi(Omix, L->W_out, y, B, L->dim, NO, dt, residual ? 2 : 0, residual, st);
+    if (int rc = launch_decode_finish(F, dt, st)) return rc;
+    return launch_linear_small_epi(D.Omix, L->W_out, y, B, L->dim, NO, dt, residual ? 2 : 0, residual, st);
 }
 
 int nsa_layer_decode_step(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *x, void *y, int t, const int32_t *csc_ptr,
@@ -415,8 +452,6 @@ int nsa_layer_decode_step(const nsa_layer_desc *L, const nsa_kv_desc *kv, const 
 }
 
 // ------------------------------------------------------------------------------ layer decode step for S consecutive tokens
-constexpr int LAYER_ROWS_MAX_S = 16;
-
 // the launches of the call and the route of its selected branch (1 = the one-launch rows form, 0 = its separate launches), from the shape and
 // the switches alone: aligned caches of capacity S_max assumed.  Returns false for a shape the call refuses.
 static bool layer_decode_rows_route(const nsa_layer_desc *L, int B, int S, int S_max, int t0, int S_sel, int *launches, int *route) {
@@ -427,20 +462,20 @@ static bool layer_decode_rows_route(const nsa_layer_desc *L, int B, int S, int S
     kv.B = B; kv.S_max = S_max; kv.n_cmp_max = std::max(1, ncmp_of(S_max, L->l, L->d));
     const CacheStrides C(L, &kv);
     const int n0 = ncmp_of(t0, L->l, L->d), n1 = ncmp_of(t0 + S, L->l, L->d);
-    const int G = L->G, h = L->h, Dk = L->Dk, Dv = L->Dv, dt = L->dtype;
     int n = 1 + (n1 > n0 ? 1 : 0);  // projection + RoPE + append, pooling
-    const bool one = decode_rows_supported(B, S, G, dt, h, Dk, Dv, n1, S_sel, t0 + S, L->l, L->d, L->l_sel, L->n_sel, t0, C.kcb, C.kcg, Dk, C.ksb,
-                                           C.ksg, Dk, C.vsb, C.vsg, Dv, kv.K_sel, kv.K_cmp, kv.K_sel, kv.V_sel);
+    SelDecodeCall c = sel_decode_call(L, &kv, C, S, t0, n1, S_sel);
+    c.Q = kv.K_sel;
+    const bool one = decode_rows_supported(c);
     if (one) {
         n += 1;
     } else {
         int nl = 3, form = -1;  // (the selected branch's own estimate of its separate launches)
-        if (nsa_sel_decode_rows_plan(B, S, G, h, Dk, Dv, n1, S_sel, t0 + S, L->n_sel, dt, &nl, &form) != NSA_OK || nl < 2) nl = 3;
+        if (nsa_sel_decode_rows_plan(B, S, L->G, L->h, L->Dk, L->Dv, n1, S_sel, t0 + S, L->n_sel, L->dtype, &nl, &form) != NSA_OK || nl < 2) nl = 3;
         n += nl;
     }
     int ns_band = 1;
-    n += band_pair_dual(L, &kv, C, S, n1, Dv == 64 ? 1 : 0, &ns_band) ? 1 : 2;  // (an undeferred split branch adds its combine: not counted)
-    n += 2;                                                                       // finish (or gate + mix), output projection
+    n += band_pair_dual(L, &kv, C, S, n1, L->Dv == 64 ? 1 : 0, &ns_band) ? 1 : 2;  // (an undeferred split branch adds its combine: not counted)
+    n += 2;                                                                          // finish (or gate + mix), output projection
     *launches = n;
     *route = one ? 1 : 0;
     return true;
@@ -454,72 +489,28 @@ static int layer_decode_rows_impl(const nsa_layer_desc *L, const nsa_kv_desc *kv
                                   const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out, float *gates_out,
                                   void *workspace, size_t workspace_bytes, void *stream, const void *residual, const void *norm_w = nullptr,
                                   float norm_eps = 0.f) {
-    if (int rc = check_layer(L, "layer_decode_rows")) return rc;
-    if (int rc = check_kv(kv, "layer_decode_rows")) return rc;
-    NSA_CHECK_ARG(x && y && L->W_qkv && L->W_out, "layer_decode_rows: null pointer");
-    NSA_CHECK_ARG(S >= 1 && S <= LAYER_ROWS_MAX_S, "layer_decode_rows: 1 to %d tokens per sequence (got %d)", LAYER_ROWS_MAX_S, S);
-    NSA_CHECK_ARG(t0 >= 0 && (int64_t)t0 + S <= kv->S_max, "layer_decode_rows: tokens [%d,%d) exceed the cache capacity %d", t0, t0 + S, kv->S_max);
-    NSA_CHECK_ARG(S_sel >= 1 && (int64_t)S_sel * L->l_sel >= (int64_t)t0 + S, "layer_decode_rows: block metadata (S_sel=%d) does not cover %d tokens",
-                  S_sel, t0 + S);
-    const int B = kv->B;
-    const DecodeWs W = decode_ws(L, B, kv->S_max, S);
-    if (int rc = check_workspace("layer_decode_rows", workspace, workspace_bytes, W.total)) return rc;
-    unsigned char *ws = (unsigned char *)workspace;
-    hipStream_t st = (hipStream_t)stream;
-    const int dt = L->dtype;
-    const int G = L->G, h = L->h, Dk = L->Dk, Dv = L->Dv;
-    const int NO = G * h * Dv, M = B * S, S_kv = t0 + S;
-    void *Q = ws + W.q, *Ocmp = ws + W.ocmp, *Osel = ws + W.osel, *Owin = ws + W.owin, *Omix = ws + W.omix;
-    int32_t *ranges = ranges_out ? ranges_out : (int32_t *)(ws + W.ranges);
-    // compressed tokens emitted before the rows (n_cmp(t0 - 1)) and after them (n_cmp(t0 + S - 1)), on the absolute schedule
-    const int n0 = ncmp_of(t0, L->l, L->d), n1 = ncmp_of(S_kv, L->l, L->d);
-    NSA_CHECK_ARG(n1 <= kv->n_cmp_max, "layer_decode_rows: compressed cache too small");
-
+    LayerDecode D;
+    if (int rc = layer_decode_begin("layer_decode_rows", L, kv, x, y, t0, S, true, S_sel, workspace, workspace_bytes, &D)) return rc;
+    NSA_CHECK_ARG(D.n1 <= kv->n_cmp_max, "layer_decode_rows: compressed cache too small");
     // 1. fused QKV projection of the B S rows, each rotated and appended at its own position t0 + s
-    const RopeAppendParams RP = rope_append_params(L, kv, ws + W.proj, Q, S, t0);
-    if (int rc = launch_qkv_rope_append(RP, x, L->W_qkv, L->dim, dt, st, norm_w, norm_eps, true)) return rc;
+    if (int rc = launch_qkv_rope_append(rope_append_params(L, kv, D.ws + D.W.proj, D.Q, S, t0), x, L->W_qkv, L->dim, L->dtype, (hipStream_t)stream, norm_w,
+                                        norm_eps, true))
+        return rc;
     // 2. the compressed tokens whose windows complete inside the call
-    if (n1 > n0)
-        if (int rc = nsa_cmp_pool_append(L, kv, n0, n1, stream)) return rc;
+    if (D.n1 > D.n0)
+        if (int rc = nsa_cmp_pool_append(L, kv, D.n0, D.n1, stream)) return rc;
     const CacheStrides C(L, kv);
     // 3. selected branch: every row's scores -> top-n at its token -> attention over K_sel[:t + 1] (one launch, or the separate launches)
-    if (int rc = nsa_sel_decode_rows(Q, kv->K_cmp, kv->K_sel, kv->V_sel, csc_ptr, csc_rows, csc_vals, ranges, Osel, B, S, G, h, Dk, Dv, n1, S_sel,
-                                     S_kv, L->l, L->d, L->l_sel, L->n_sel, t0, C.kcb, C.kcg, Dk, C.ksb, C.ksg, Dk, C.vsb, C.vsg, Dv, dt, C.scale,
-                                     ws + W.sel, W.sel_bytes, stream))
-        return rc;
-    // 4. sliding and compressed branches of the S rows: one launch in split form with the combine left to the finish kernel, else one each
-    const int defer = Dv == 64 ? 1 : 0;
-    DecodeFinishParams F{};
-    F.Q = Q; F.O_out = Omix; F.gates_out = gates_out;
-    F.w1 = L->gate_w1; F.b1 = L->gate_b1; F.w2 = L->gate_w2; F.b2 = L->gate_b2;
-    F.R = (int64_t)M * G; F.h = h; F.Dk = Dk; F.Dv = Dv; F.Hd = L->gate_hidden; F.tau = L->gate_tau;
-    F.O[0] = Ocmp; F.O[1] = Osel; F.O[2] = Owin;
+    if (int rc = sel_decode_rows_impl(layer_sel_call(D, C, csc_ptr, csc_rows, csc_vals, S_sel, ranges_out), D.ws + D.W.sel, D.W.sel_bytes, stream)) return rc;
+    // 4. sliding and compressed branches of the S rows: one launch in split form with the combine left to the finish kernel, else one each;
+    // 5. split combine + gates + mix, 6. output projection of the B S rows
+    DecodeFinishParams F = decode_finish_params(D, gates_out);
     F.ns[1] = 1;
     int ns_band = 1;
-    if (band_pair_dual(L, kv, C, S, n1, defer, &ns_band)) {
-        DecBandPair BP{};
-        band_pair_fill(BP, L, kv, C, Q, Owin, Ocmp, S, t0, n1, ns_band, (float *)(ws + W.band), (float *)(ws + W.band2));
-        if (int rc = launch_band_attn_fwd_dual(BP.w, BP.c, dt, st)) return rc;
-        F.ns[2] = F.ns[0] = ns_band;
-        F.part[2] = BP.w.part;
-        F.part[0] = BP.c.part;
-    } else {
-        if (int rc = band_attn_fwd_impl(Q, kv->K_win, kv->V_win, Owin, nullptr, B, S, G, h, Dk, Dv, S_kv, C.ksb, C.ksg, Dk, C.vsb, C.vsg, Dv, t0, 0, 1,
-                                        0, L->w, dt, C.scale, 0, ws + W.band, W.band_bytes, stream, defer, &F.ns[2]))
-            return rc;
-        F.part[2] = (const float *)(ws + W.band);
-        if (int rc = band_attn_fwd_impl(Q, kv->K_cmp, kv->V_cmp, Ocmp, nullptr, B, S, G, h, Dk, Dv, n1, C.kcb, C.kcg, Dk, C.vcb, C.vcg, Dv, t0, L->l,
-                                        L->d, 1, 1 << 30, dt, C.scale, 0, ws + W.band2, W.band_bytes, stream, defer, &F.ns[0]))
-            return rc;
-        F.part[0] = (const float *)(ws + W.band2);
-    }
-    // 5. split combine + gates + mix, 6. output projection of the B S rows
-    if (defer) {
-        if (int rc = launch_decode_finish(F, dt, st)) return rc;
-    } else {
-        if (int rc = nsa_gate_combine(L, Q, Ocmp, Osel, Owin, Omix, gates_out, (int64_t)M * G, stream)) return rc;
-    }
-    return launch_linear_small_epi(Omix, L->W_out, y, M, L->dim, NO, dt, residual ? 2 : 0, residual, st);
+    DecBandPair BP{};
+    const bool dual = band_pair_dual(L, kv, C, S, D.n1, L->Dv == 64 ? 1 : 0, &ns_band);
+    if (dual) band_pair_fill(BP, L, kv, C, D.Q, D.Owin, D.Ocmp, S, t0, D.n1, ns_band, (float *)(D.ws + D.W.band), (float *)(D.ws + D.W.band2));
+    return layer_decode_tail(D, C, F, dual ? &BP : nullptr, false, gates_out, y, residual, stream);
 }
 
 size_t nsa_layer_decode_rows_workspace(const nsa_layer_desc *L, int B, int S, int S_max) {

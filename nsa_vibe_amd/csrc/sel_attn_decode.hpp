@@ -30,16 +30,6 @@ static __device__ long long g_dec_ts[64];
 #endif
 #endif
 
-struct DecAttnArgs {
-    const void *Q;  // [R,h,D]
-    const void *K;  // [B,G,S_kv,D] strided
-    const void *V;
-    void *O;        // [R,h,D]
-    int G, h, S_kv, n;
-    int64_t ksb, ksg, kss, vsb, vsg, vss;
-    float c2;  // scale * log2(e)
-};
-
 constexpr int dec_att_tile(int D) { return 64 * 2 * D; }        // V chunk per wave: 64 keys
 constexpr int DEC_ATT_TILE = dec_att_tile(64);
 constexpr int DEC_ATT_TAIL = ((SEG_INTS * 4 + 15) / 16) * 16;  // sorted segments of the row (standalone launch)

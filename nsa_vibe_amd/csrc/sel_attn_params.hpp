@@ -93,6 +93,29 @@ struct DecBandPair {
     unsigned n_sel;  // workgroups of the host kernel's own work (0xffffffff: the launch carries no band work)
     unsigned n_w;    // workgroups of the sliding branch
 };
+// argument blocks of the one-launch decode step (here so that the host check of the dispatch layer reads them too): the row's selection
+// attention (sel_attn_decode.hpp) and the scoring part (sel_decode_fused.hip)
+struct DecAttnArgs {
+    const void *Q;  // [R,h,D]
+    const void *K;  // [B,G,S_kv,D] strided
+    const void *V;
+    void *O;        // [R,h,D]
+    int G, h, S_kv, n;
+    int64_t ksb, ksg, kss, vsb, vsg, vss;
+    float c2;  // scale * log2(e)
+};
+struct DecStepParams {
+    const void *Q;   // [R,h,D]
+    const void *Kc;  // [B,G,S_cmp,D] strided
+    float *part_g;   // SPLIT: [R][h][64][2] per-chunk (max, sum exp2)
+    float *halo_g;   // SPLIT: [R][64][16] scaled logit of every chunk's last row, per head
+    float *pg_g;     // SPLIT: [R][2048] group scores of the row's blocks
+    int *cnt;        // SPLIT: [2][R] arrivals (records published) and tickets (scores published); zero between launches
+    int R, G, h, S_cmp, S_sel, NS, nchunk, cpg, t_token, spin;
+    int64_t csb, csg, css;
+    float c2;
+    int S;           // rows form: query rows per sequence, row (b, s, g) at token t_token + s (in the struct's tail padding: the layout of the rest is unchanged)
+};
 // fills tpw of both argument blocks and returns the (row, split) units = waves of each; false: not both in split form with deferred combine
 bool band_dual_plan(BandAttnParams *P0, BandAttnParams *P1, int dtype, int64_t waves[2]);
 int launch_band_attn_bwd_dq(const BandAttnParams &P, const void *dO, const float *lse, const float *delta, void *dQ, int dtype,

@@ -34,6 +34,7 @@
 #include <unordered_map>
 
 #define DEC_TS(i)  // (the shared device functions' own stamps belong to the round-2 kernel's timeline: this kernel stamps with DS_TS)
+#include "nsa_host.hpp"
 #include "nsa_internal.hpp"
 #include "sel_attn_decode.hpp"
 #include "sel_attn_params.hpp"
@@ -48,19 +49,6 @@ static __device__ long long g_ts2[32];
 #else
 #define DS_TS(i)
 #endif
-
-struct DecStepParams {
-    const void *Q;   // [R,h,D]
-    const void *Kc;  // [B,G,S_cmp,D] strided
-    float *part_g;   // SPLIT: [R][h][64][2] per-chunk (max, sum exp2)
-    float *halo_g;   // SPLIT: [R][64][16] scaled logit of every chunk's last row, per head
-    float *pg_g;     // SPLIT: [R][2048] group scores of the row's blocks
-    int *cnt;        // SPLIT: [2][R] arrivals (records published) and tickets (scores published); zero between launches
-    int R, G, h, S_cmp, S_sel, NS, nchunk, cpg, t_token, spin;
-    int64_t csb, csg, css;
-    float c2;
-    int S;           // rows form: query rows per sequence, row (b, s, g) at token t_token + s (in the struct's tail padding: the layout of the rest is unchanged)
-};
 
 constexpr int DSTEP_CH = 128;                  // chunks of 64 compressed rows per row of the step: contexts up to 128k tokens (S_cmp <= 8192)
 constexpr int DSTEP_PART = 16 * DSTEP_CH * 2;  // floats: [head][chunk][2]
@@ -829,31 +817,37 @@ static bool decode_step_plan(int64_t R, int nchunk, int h, int S_sel, int D, int
     return true;
 }
 
+// what both shape plans end with, for a launch of nw waves per workgroup in form fm: the formats and sizes the kernel's phases hold
+static bool dstep_shape_ok(const SelDecodeCall &c, int nw, int fm) {
+    return (c.dtype == NSA_DT_BF16 || c.dtype == NSA_DT_F16) && c.S_cmp <= 64 * DSTEP_CH && c.S_sel <= 2048 && c.n_top >= 3 && c.n_top <= 64 &&
+           (int64_t)c.S_kv * 2 * c.Dv < ((int64_t)1 << 31) && sel_attn_decode_wg_shape_ok(c.dtype, c.h, c.Dk, c.Dv, c.n_top) &&
+           dstep_score_bytes(nw, c.h, c.S_sel, fm == 1 ? 4 : 2) <= dstep_score_room(nw, c.Dk);
+}
+// what both forms ask of the call beyond its shape: the default block geometry (l = 2d, l' = 4d = 64), an aligned K_cmp with strides in
+// multiples of 8 elements, and the operands of the row's attention (sel_attn_decode_wg_supported)
+static bool dstep_operands_ok(const SelDecodeCall &c) {
+    return c.d == 16 && c.l == 32 && c.l_sel == 64 && c.kcs % 8 == 0 && c.kcb % 8 == 0 && c.kcg % 8 == 0 && ((uintptr_t)c.K_cmp % 16 == 0) &&
+           sel_attn_decode_wg_supported(c.dtype, c.h, c.Dk, c.Dv, c.n_top, c.ksb, c.ksg, c.kss, c.vsb, c.vsg, c.vss, c.Q, c.K, c.V);
+}
+
 // the part of decode_step_supported that depends on the shape and the tuning switches alone (default block geometry assumed): the one
 // predicate behind both the call and nsa_sel_decode_step_plan.  form / nsplit: the plan (-1 / 0 when declined)
-bool decode_step_shape_plan(int64_t R, int dtype, int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int n_top, int *form, int *nsplit) {
+bool decode_step_shape_plan(const SelDecodeCall &c, int *form, int *nsplit) {
     if (form) *form = -1;
     if (nsplit) *nsplit = 0;
     if (tuning(TUNE_DECODE_STEP) == 0 || tuning(TUNE_DECODE_UNFUSED) > 0) return false;
     int nw, ns, fm;
-    if (R < 1 || S_cmp < 1 || S_sel < 1 || h < 1 || h > 16 || Dk != Dv || (Dk != 64 && Dk != 128) ||
-        !decode_step_plan(R, (S_cmp + 63) / 64, h, S_sel, Dk, &nw, &ns, &fm))
+    if (c.rows() < 1 || c.S_cmp < 1 || c.S_sel < 1 || c.h < 1 || c.h > 16 || c.Dk != c.Dv || (c.Dk != 64 && c.Dk != 128) ||
+        !decode_step_plan(c.rows(), (c.S_cmp + 63) / 64, c.h, c.S_sel, c.Dk, &nw, &ns, &fm))
         return false;
-    if (!((dtype == NSA_DT_BF16 || dtype == NSA_DT_F16) && S_cmp <= 64 * DSTEP_CH && S_sel <= 2048 && n_top >= 3 && n_top <= 64 && S_kv >= 1 &&
-          (int64_t)S_kv * 2 * Dv < ((int64_t)1 << 31) && sel_attn_decode_wg_shape_ok(dtype, h, Dk, Dv, n_top) &&
-          dstep_score_bytes(nw, h, S_sel, fm == 1 ? 4 : 2) <= dstep_score_room(nw, Dk)))
-        return false;
+    if (c.S_kv < 1 || !dstep_shape_ok(c, nw, fm)) return false;
     if (form) *form = fm;
     if (nsplit) *nsplit = ns;
     return true;
 }
 
-bool decode_step_supported(int64_t R, int dtype, int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int l, int d, int l_sel, int n_top, int t_token,
-                           int64_t kcb, int64_t kcg, int64_t kcs, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg, int64_t vss,
-                           const void *Q, const void *Kc, const void *K, const void *V) {
-    return decode_step_shape_plan(R, dtype, h, Dk, Dv, S_cmp, S_sel, S_kv, n_top, nullptr, nullptr) && d > 0 && l == 2 * d && l_sel == 4 * d &&
-           l_sel == 64 && t_token >= 0 && S_kv >= t_token + 1 && kcs % 8 == 0 && kcb % 8 == 0 && kcg % 8 == 0 && ((uintptr_t)Kc % 16 == 0) &&
-           sel_attn_decode_wg_supported(dtype, h, Dk, Dv, n_top, ksb, ksg, kss, vsb, vsg, vss, Q, K, V);
+bool decode_step_supported(const SelDecodeCall &c) {
+    return decode_step_shape_plan(c, nullptr, nullptr) && c.t0 >= 0 && c.S_kv >= c.t0 + 1 && dstep_operands_ok(c);
 }
 
 // raise the dynamic-LDS limit once per kernel (the runtime call costs about a millisecond)
@@ -872,38 +866,45 @@ static int dstep_raise_lds(void *k) {
     return NSA_OK;
 }
 
-int launch_decode_step(const void *Q, const void *Kc, const void *K, const void *V, void *O, int32_t *ranges_out, int B, int G, int h, int S_cmp,
-                       int S_sel, int S_kv, int n_top, int t_token, int64_t kcb, int64_t kcg, int64_t kcs, int64_t ksb, int64_t ksg, int64_t kss,
-                       int64_t vsb, int64_t vsg, int64_t vss, int dtype, float scale, void *ws, size_t ws_bytes, hipStream_t st, const DecBandPair *band, int D) {
-    const int64_t R = (int64_t)B * G;
+// what both launchers hand the kernel besides DecStepParams: the sequential selector, its candidate width, the row attention (c2 = scale log2 e)
+struct DecStepBlocks {
+    SelectParams SP;
+    int cand;
+    DecAttnArgs AT;
+};
+static int dstep_blocks(const SelDecodeCall &c, float c2, DecStepBlocks *b) {
+    if (int rc = select_params_sequential(&b->SP, c.S_sel, 64, c.n_top, 1, 2, c.n_top)) return rc;
+    b->SP.out = c.ranges_out; b->SP.R = c.rows(); b->SP.S = c.S; b->SP.G = c.G; b->SP.t0 = c.t0;
+    const int n = (c.S_sel + 63) / 64;
+    b->cand = n <= 1 ? 1 : n <= 2 ? 2 : n <= 4 ? 4 : n <= 8 ? 8 : n <= 16 ? 16 : 32;
+    b->AT = DecAttnArgs{c.Q, c.K, c.V, c.O, c.G, c.h, c.S_kv, c.n_top, c.ksb, c.ksg, c.kss, c.vsb, c.vsg, c.vss, c2};
+    return NSA_OK;
+}
+
+int launch_decode_step(const SelDecodeCall &c, void *ws, size_t ws_bytes, hipStream_t st, const DecBandPair *band) {
+    const int64_t R = c.rows();
+    const int D = c.Dk, h = c.h;
     NSA_CHECK_ARG(D == 64 || D == 128, "decode step: head dimension 64 or 128");
     NSA_CHECK_ARG(R >= 1 && R <= (1 << 24), "decode step: bad row count");
-    const int nchunk = ((S_cmp + 63) / 64);
+    const int nchunk = ((c.S_cmp + 63) / 64);
     int nw = 16, ns = 1, form = 0;
-    NSA_CHECK_ARG(decode_step_plan(R, nchunk, h, S_sel, D, &nw, &ns, &form), "decode step: shape not covered (decode_step_supported)");
+    NSA_CHECK_ARG(decode_step_plan(R, nchunk, h, c.S_sel, D, &nw, &ns, &form), "decode step: shape not covered (decode_step_supported)");
     const int cpw = form == 1 ? 4 : 2;
-    DecStepParams P{Q, Kc, nullptr, nullptr, nullptr, nullptr, (int)R, G, h, S_cmp, S_sel, ns, nchunk, (nchunk + ns - 1) / ns, t_token, 0, kcb, kcg, kcs, scale * LOG2E};
+    const float c2 = default_scale(c.scale, D) * LOG2E;
+    DecStepParams P{c.Q, c.K_cmp, nullptr, nullptr, nullptr, nullptr, (int)R, c.G, h, c.S_cmp, c.S_sel, ns, nchunk, (nchunk + ns - 1) / ns, c.t0, 0, c.kcb, c.kcg, c.kcs, c2};
     P.spin = tuning(TUNE_DECODE_TEAM_SPIN) >= 0 ? tuning(TUNE_DECODE_TEAM_SPIN) : 512;  // polls of ~0.5-1 us each before a workgroup goes on alone
     if (ns > 1) {
-        NSA_CHECK_ARG(ws && ws_bytes >= decode_step_workspace(R, h, S_cmp) && ((uintptr_t)ws % 16 == 0), "decode step: workspace too small");
+        NSA_CHECK_ARG(ws && ws_bytes >= decode_step_workspace(R, h, c.S_cmp) && ((uintptr_t)ws % 16 == 0), "decode step: workspace too small");
         P.part_g = (float *)ws;
         P.halo_g = P.part_g + (size_t)R * h * DSTEP_CH * 2;
         P.pg_g = P.halo_g + (size_t)R * DSTEP_CH * 16;
         P.cnt = decode_tickets(st, 2 * R);
         NSA_CHECK_ARG(P.cnt != nullptr, "decode step: could not allocate the arrival tickets");
     }
-    SelectParams SP{};
-    if (int rc = select_params_sequential(&SP, S_sel, 64, n_top, 1, 2, n_top)) return rc;
-    SP.out = ranges_out;
-    SP.R = R;
-    SP.S = 1;
-    SP.G = G;
-    SP.t0 = t_token;
-    const int c = (S_sel + 63) / 64;
-    const int cand = c <= 1 ? 1 : c <= 2 ? 2 : c <= 4 ? 4 : c <= 8 ? 8 : c <= 16 ? 16 : 32;
-    const DecAttnArgs AT{Q, K, V, O, G, h, S_kv, n_top, ksb, ksg, kss, vsb, vsg, vss, scale * LOG2E};
+    DecStepBlocks A{};
+    if (int rc = dstep_blocks(c, c2, &A)) return rc;
     void (*k)(DecStepParams, SelectParams, int, DecAttnArgs, DecBandPair);
-    const bool bf = dtype == NSA_DT_BF16, split = ns > 1;
+    const bool bf = c.dtype == NSA_DT_BF16, split = ns > 1;
 #define NSA_DSK(NW_, SP_, HC_) (bf ? decode_step_kernel<__bf16, NW_, SP_, HC_> : decode_step_kernel<_Float16, NW_, SP_, HC_>)
 #define NSA_DSK4(NW_, HC_) (bf ? decode_step_kernel<__bf16, NW_, false, HC_, 4> : decode_step_kernel<_Float16, NW_, false, HC_, 4>)
 #define NSA_DSK1(NW_, HC_) (bf ? decode_step_onepass_kernel<__bf16, NW_, HC_> : decode_step_onepass_kernel<_Float16, NW_, HC_>)
@@ -921,7 +922,7 @@ int launch_decode_step(const void *Q, const void *Kc, const void *K, const void 
 #undef NSA_DSK
     const size_t lds = dstep_lds(nw, D);
     // the score data sits in V tiles 1 .. (the prefetching waves of the 16-wave form own tiles 0, 14, 15)
-    NSA_CHECK_ARG(dstep_score_bytes(nw, h, S_sel, cpw) <= dstep_score_room(nw, D), "decode step: S_sel too large");
+    NSA_CHECK_ARG(dstep_score_bytes(nw, h, c.S_sel, cpw) <= dstep_score_room(nw, D), "decode step: S_sel too large");
     if (int rc = dstep_raise_lds((void *)k)) return rc;
     int64_t grid = ns > 1 ? ((R + 7) / 8) * 8 * ns : R;
     DecBandPair BP{};
@@ -929,7 +930,7 @@ int launch_decode_step(const void *Q, const void *Kc, const void *K, const void 
     if (band) {  // the layer step's sliding + compressed branches on workgroups behind the step's own (decode_band_workgroup)
         BP = *band;
         int64_t waves[2];
-        NSA_CHECK_ARG(D == 64 && BP.w.Dk == 64 && BP.w.Dv == 64 && band_dual_plan(&BP.w, &BP.c, dtype, waves), "decode step: band branches not in split form");
+        NSA_CHECK_ARG(D == 64 && BP.w.Dk == 64 && BP.w.Dv == 64 && band_dual_plan(&BP.w, &BP.c, c.dtype, waves), "decode step: band branches not in split form");
         if (BP.mg.on) {  // splits merged by the workgroup that holds them: a unit = nsplit consecutive waves of one workgroup
             NSA_CHECK_ARG(BP.w.S == 1 && BP.c.S == 1 && BP.mg.gates && BP.w.O && BP.c.O && h <= 16, "decode step: band merge needs S = 1, outputs and a gate buffer");
             int nsm = 1;
@@ -944,7 +945,7 @@ int launch_decode_step(const void *Q, const void *Kc, const void *K, const void 
         grid += gw + gc;
     }
     static_assert(2 * Geo<64>::TILE_BYTES <= DEC_ATT_TILE, "a band wave keeps its K and V tile in the wave's V tile of the step");
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(nw * 64), lds, st, P, SP, cand, AT, BP);
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(nw * 64), lds, st, P, A.SP, A.cand, A.AT, BP);
     NSA_LAUNCH_CHECK("decode_step");
     return NSA_OK;
 }
@@ -964,60 +965,40 @@ static int dstep_ncmp(int t) { return t + 1 < 32 ? 0 : (t + 1 - 32) / 16 + 1; }
 // waves chosen for the launch from its LARGEST row (t0 + S - 1) and its row count B S G: form 0 (two chunks per wave) or, at D = 64, form 1
 // (four chunks per wave) where that row exceeds form 0 -- the unsplit exact forms only, whatever DECODE_WIDE says; no team of workgroups,
 // no one-pass form.  DECODE_ROWS: 0 = never, 1 = wherever the forms hold the shape, -1 = the measured rule.
-bool decode_rows_shape_plan(int B, int S, int G, int dtype, int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int n_top, int t0, int *form,
-                            int *nw_out) {
+bool decode_rows_shape_plan(const SelDecodeCall &c, int *form, int *nw_out) {
     if (form) *form = -1;
-    const int sw = tuning(TUNE_DECODE_ROWS);
+    const int sw = tuning(TUNE_DECODE_ROWS), S = c.S, t0 = c.t0;
     if (tuning(TUNE_DECODE_STEP) == 0 || tuning(TUNE_DECODE_UNFUSED) > 0 || sw == 0) return false;
-    if (B < 1 || S < 1 || S > 16 || G < 1 || h < 1 || h > 16 || Dk != Dv || (Dk != 64 && Dk != 128) || S_cmp < 1 || S_sel < 1) return false;
-    if (t0 < 0 || t0 > (1 << 30) || dstep_ncmp(t0) < 1 || S_kv < t0 + S) return false;  // every row has a compressed row and its own token in the cache
-    const int64_t R = (int64_t)B * S * G;
-    if (R > (1 << 24)) return false;
-    const int nw = dec_att_waves(R, Dk);
-    const int n_max = std::min(S_cmp, dstep_ncmp(t0 + S - 1)), nchunk = (n_max + 63) / 64;
+    if (c.B < 1 || S < 1 || S > 16 || c.G < 1 || c.h < 1 || c.h > 16 || c.Dk != c.Dv || (c.Dk != 64 && c.Dk != 128) || c.S_cmp < 1 || c.S_sel < 1) return false;
+    if (t0 < 0 || t0 > (1 << 30) || dstep_ncmp(t0) < 1 || c.S_kv < t0 + S) return false;  // every row has a compressed row and its own token in the cache
+    if (c.rows() > (1 << 24)) return false;
+    const int nw = dec_att_waves(c.rows(), c.Dk);
+    const int n_max = std::min(c.S_cmp, dstep_ncmp(t0 + S - 1)), nchunk = (n_max + 63) / 64;
     int fm;
     if (nchunk <= 2 * nw) fm = 0;
-    else if (Dk == 64 && nchunk <= 4 * nw) fm = 1;
+    else if (c.Dk == 64 && nchunk <= 4 * nw) fm = 1;
     else return false;
-    if (!((dtype == NSA_DT_BF16 || dtype == NSA_DT_F16) && S_cmp <= 64 * DSTEP_CH && S_sel <= 2048 && n_top >= 3 && n_top <= 64 &&
-          (int64_t)S_kv * 2 * Dv < ((int64_t)1 << 31) && sel_attn_decode_wg_shape_ok(dtype, h, Dk, Dv, n_top) &&
-          dstep_score_bytes(nw, h, S_sel, fm == 1 ? 4 : 2) <= dstep_score_room(nw, Dk)))
-        return false;
+    if (!dstep_shape_ok(c, nw, fm)) return false;
     if (sw < 0 && !decode_rows_measured_ok(S, nchunk)) return false;
     if (form) *form = fm;
     if (nw_out) *nw_out = nw;
     return true;
 }
 
-bool decode_rows_supported(int B, int S, int G, int dtype, int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int l, int d, int l_sel, int n_top,
-                           int t0, int64_t kcb, int64_t kcg, int64_t kcs, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg,
-                           int64_t vss, const void *Q, const void *Kc, const void *K, const void *V) {
-    return decode_rows_shape_plan(B, S, G, dtype, h, Dk, Dv, S_cmp, S_sel, S_kv, n_top, t0, nullptr, nullptr) && d == 16 && l == 32 && l_sel == 64 &&
-           kcs % 8 == 0 && kcb % 8 == 0 && kcg % 8 == 0 && ((uintptr_t)Kc % 16 == 0) &&
-           sel_attn_decode_wg_supported(dtype, h, Dk, Dv, n_top, ksb, ksg, kss, vsb, vsg, vss, Q, K, V);
-}
+bool decode_rows_supported(const SelDecodeCall &c) { return decode_rows_shape_plan(c, nullptr, nullptr) && dstep_operands_ok(c); }
 
-int launch_decode_rows(const void *Q, const void *Kc, const void *K, const void *V, void *O, int32_t *ranges_out, int B, int S, int G, int h,
-                       int S_cmp, int S_sel, int S_kv, int n_top, int t0, int64_t kcb, int64_t kcg, int64_t kcs, int64_t ksb, int64_t ksg, int64_t kss,
-                       int64_t vsb, int64_t vsg, int64_t vss, int dtype, float scale, hipStream_t st, int D) {
+int launch_decode_rows(const SelDecodeCall &c, hipStream_t st) {
     int nw = 16, form = 0;
-    NSA_CHECK_ARG(decode_rows_shape_plan(B, S, G, dtype, h, D, D, S_cmp, S_sel, S_kv, n_top, t0, &form, &nw), "decode rows: shape not covered (decode_rows_supported)");
-    const int64_t R = (int64_t)B * S * G;
-    const int cpw = form == 1 ? 4 : 2;
-    const int nchunk = (std::min(S_cmp, dstep_ncmp(t0 + S - 1)) + 63) / 64;  // of the largest row: every row derives its own
-    DecStepParams P{Q, Kc, nullptr, nullptr, nullptr, nullptr, (int)R, G, h, S_cmp, S_sel, 1, nchunk, nchunk, t0, 0, kcb, kcg, kcs, scale * LOG2E, S};
-    SelectParams SP{};
-    if (int rc = select_params_sequential(&SP, S_sel, 64, n_top, 1, 2, n_top)) return rc;
-    SP.out = ranges_out;
-    SP.R = R;
-    SP.S = S;
-    SP.G = G;
-    SP.t0 = t0;
-    const int c = (S_sel + 63) / 64;
-    const int cand = c <= 1 ? 1 : c <= 2 ? 2 : c <= 4 ? 4 : c <= 8 ? 8 : c <= 16 ? 16 : 32;
-    const DecAttnArgs AT{Q, K, V, O, G, h, S_kv, n_top, ksb, ksg, kss, vsb, vsg, vss, scale * LOG2E};
+    NSA_CHECK_ARG(decode_rows_shape_plan(c, &form, &nw), "decode rows: shape not covered (decode_rows_supported)");
+    const int64_t R = c.rows();
+    const int D = c.Dk, h = c.h, cpw = form == 1 ? 4 : 2;
+    const int nchunk = (std::min(c.S_cmp, dstep_ncmp(c.t0 + c.S - 1)) + 63) / 64;  // of the largest row: every row derives its own
+    const float c2 = default_scale(c.scale, D) * LOG2E;
+    DecStepParams P{c.Q, c.K_cmp, nullptr, nullptr, nullptr, nullptr, (int)R, c.G, h, c.S_cmp, c.S_sel, 1, nchunk, nchunk, c.t0, 0, c.kcb, c.kcg, c.kcs, c2, c.S};
+    DecStepBlocks A{};
+    if (int rc = dstep_blocks(c, c2, &A)) return rc;
     void (*k)(DecStepParams, SelectParams, int, DecAttnArgs, DecBandPair);
-    const bool bf = dtype == NSA_DT_BF16;
+    const bool bf = c.dtype == NSA_DT_BF16;
 #define NSA_DSR(NW_, HC_, CPW_, D_) (bf ? decode_step_kernel<__bf16, NW_, false, HC_, CPW_, D_, true> : decode_step_kernel<_Float16, NW_, false, HC_, CPW_, D_, true>)
     if (D == 128) {
         NSA_CHECK_ARG(form == 0 && nw == 8, "decode rows: D = 128 runs form 0 on eight waves");
@@ -1028,7 +1009,7 @@ int launch_decode_rows(const void *Q, const void *Kc, const void *K, const void 
     if (int rc = dstep_raise_lds((void *)k)) return rc;
     DecBandPair BP{};
     BP.n_sel = 0xffffffffu;  // (no band workgroups on this form)
-    hipLaunchKernelGGL(k, dim3((unsigned)R), dim3(nw * 64), dstep_lds(nw, D), st, P, SP, cand, AT, BP);
+    hipLaunchKernelGGL(k, dim3((unsigned)R), dim3(nw * 64), dstep_lds(nw, D), st, P, A.SP, A.cand, A.AT, BP);
     NSA_LAUNCH_CHECK("decode_rows");
     return NSA_OK;
 }

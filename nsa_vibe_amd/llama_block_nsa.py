@@ -20,7 +20,7 @@ import ctypes
 from . import _lib
 from .kv_cache import NSA_KV
 from .nsa_attention import NSAAttention
-from .selection_scorer import _stream, workspace
+from .selection_scorer import _stream, workspace_at
 
 
 def _rmsnorm_native_ok(x: torch.Tensor, w: torch.Tensor) -> bool:
@@ -58,10 +58,9 @@ class _RMSNormFn(torch.autograd.Function):
         M, dim = xc.numel() // xc.shape[-1], xc.shape[-1]
         dx, dw = torch.empty_like(xc), torch.empty_like(wc)
         L = _lib.lib()
-        ws = workspace(xc.device, L.nsa_rmsnorm_rows_bwd_workspace(M, dim) + 256, "rmsnorm_bwd")
-        wptr = (ws.data_ptr() + 255) & ~255
+        wptr, wsize, _ = workspace_at(xc.device, L.nsa_rmsnorm_rows_bwd_workspace(M, dim), "rmsnorm_bwd", 256)
         rc = L.nsa_rmsnorm_rows_bwd(xc.data_ptr(), wc.data_ptr(), dyc.data_ptr(), dx.data_ptr(), dw.data_ptr(), M, dim, ctx.eps, _DT[xc.dtype],
-                                    wptr, ws.numel() - (wptr - ws.data_ptr()), _stream(xc.device))
+                                    wptr, wsize, _stream(xc.device))
         _lib.check(rc, "nsa_rmsnorm_rows_bwd")
         return dx, dw, None
 
@@ -170,11 +169,10 @@ class LlamaBlockNSA(nn.Module):
         ctx = getattr(kv, "_blk_ctx", None)
         if ctx is None or ctx[0] is not desc:
             kd = a._kv_desc(kv)
-            ws = workspace(dev, L.nsa_block_decode_step_workspace(ctypes.byref(desc), B, kd.S_max) + 256, "block_decode")
-            wptr = (ws.data_ptr() + 255) & ~255
+            wptr, wsize, ws = workspace_at(dev, L.nsa_block_decode_step_workspace(ctypes.byref(desc), B, kd.S_max), "block_decode", 256)
             ranges = torch.empty((B, a.n_kv_groups, a.n_sel, 2), dtype=torch.int32, device=dev)
             gates = torch.empty((B, 1, a.n_kv_groups, 3), dtype=torch.float32, device=dev)
-            ctx = kv._blk_ctx = (desc, ctypes.byref(desc), ctypes.byref(kd), kd, ws, wptr, ws.numel() - (wptr - ws.data_ptr()), ranges, gates)
+            ctx = kv._blk_ctx = (desc, ctypes.byref(desc), ctypes.byref(kd), kd, ws, wptr, wsize, ranges, gates)
         _, desc_ref, kd_ref, _, _, wptr, wsize, ranges, gates = ctx
         cptr, crows, cvals = kv.meta.device_csc(dev)
         xc = x.reshape(B, a.dim)
@@ -265,10 +263,9 @@ class TinyLM(nn.Module):
         if ctx is None or ctx[0] != key:
             barr = (_lib.NsaBlockDesc * n)(*descs)
             karr = (_lib.NsaKvDesc * n)(*[blk.attn._kv_desc(kv) for blk, kv in zip(self.blocks, caches)])
-            ws = workspace(dev, L.nsa_model_decode_step_workspace(barr, n, B, karr[0].S_max) + 256, "model_decode")
-            wptr = (ws.data_ptr() + 255) & ~255
+            wptr, wsize, ws = workspace_at(dev, L.nsa_model_decode_step_workspace(barr, n, B, karr[0].S_max), "model_decode", 256)
             nxt = torch.empty((B, 1), dtype=torch.int32, device=dev)
-            ctx = self._dec_ctx = (key, barr, karr, ws, wptr, ws.numel() - (wptr - ws.data_ptr()), nxt)
+            ctx = self._dec_ctx = (key, barr, karr, ws, wptr, wsize, nxt)
         _, barr, karr, _, wptr, wsize, nxt = ctx
         cptr, crows, cvals = meta.device_csc(dev)
         tok32 = tokens.reshape(B).to(torch.int32)

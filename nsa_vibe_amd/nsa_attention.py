@@ -42,8 +42,8 @@ from .selection_attention import (
     selection_attention_hip,
     selection_decode_step,
 )
-from .selection_scorer import (_DT, _stream, select_topn_ranges_batched, select_topn_ranges_rows, selection_scores, selection_scores_select,
-                               workspace)
+from .selection_scorer import (_DT, _stream, _ws_args, select_topn_ranges_batched, select_topn_ranges_rows, selection_scores,
+                               selection_scores_select, workspace, workspace_at)
 
 _ORIG_SELECTORS = (select_topn_ranges_batched, select_topn_ranges_rows, selection_scores)
 
@@ -60,6 +60,13 @@ def _env_prefill_tile() -> int:
 def _n_cmp(S_raw: int, l: int, d: int) -> int:
     """compressed tokens emitted once S_raw tokens are cached"""
     return 0 if S_raw < l else (S_raw - l) // d + 1
+
+
+def _restore(kv: NSA_KV, saved) -> None:
+    """back to saved = (kv.t, kv.n_cmp, len(kv.reads_pred)): the rows a failed call appended are written again by the next executor"""
+    kv.t, kv.n_cmp = saved[0], saved[1]
+    for lst in (kv.reads_pred, kv.reads_act_total, kv.reads_act_sel, kv.reads_act_cmp, kv.reads_act_win):
+        del lst[saved[2]:]
 
 
 def _scores_and_ranges(Q, K_cmp, meta, n_sel, selector, S, scale):
@@ -211,7 +218,7 @@ class _CmpPoolFn(torch.autograd.Function):
         L, dev = _lib.lib(), K_raw.device
         desc, _ = module._layer_desc()
         kd = module._kv_desc(kv)
-        n_cmp = 0 if S < module.l else (S - module.l) // module.d + 1
+        n_cmp = _n_cmp(S, module.l, module.d)
         _lib.check(L.nsa_cmp_pool_append(ctypes.byref(desc), ctypes.byref(kd), 0, n_cmp, _stream(dev)), "nsa_cmp_pool_append")
         kv.n_cmp = n_cmp
         ctx.module, ctx.S, ctx.n_cmp, ctx.B = module, S, n_cmp, K_raw.shape[0]
@@ -449,32 +456,35 @@ class NSAAttention(nn.Module):
             x = x.contiguous()
         extend = prefill and self._extend_wanted(x, kv)
         one_call = self._native_ok(x)
-        if extend:
-            saved = (kv.t, kv.n_cmp, len(kv.reads_pred))
+        saved = (kv.t, kv.n_cmp, len(kv.reads_pred)) if extend else None
         try:
             if extend:
                 return self._extend(x, kv)
             return self._prefill(x, kv) if prefill else self._decode(x, kv)
         except RuntimeError as e:
-            # the reference's router counts a failed native executor (nsa_attention.py:764-782) ...
-            self._fallback_counters["selection_hip_fails"] += 1
-            self._fallback_counters["total_fallbacks"] += 1
-            self._last_error = str(e)
-            if self._strict or not one_call or "HIP error" in str(e):
-                # ... the per-stage composition is the last executor there is: no CPU / eager-SDPA route exists by design; and a HIP
-                # runtime / device error (a launch failure, a fault) is not a status return to route around: raised as it is
-                raise
-            # ... and falls back to its next executor and returns normally: the layer composed from the separate native calls
-            warnings.warn(f"nsa_vibe_amd: the one-call native layer failed ({e}); falling back to the per-stage native route", RuntimeWarning)
-            try:
+            def stages():  # the next executor: the layer composed from the separate native calls
                 if extend:
-                    kv.t, kv.n_cmp = saved[0], saved[1]  # the chunks the one-call route appended are written again
-                    for lst in (kv.reads_pred, kv.reads_act_total, kv.reads_act_sel, kv.reads_act_cmp, kv.reads_act_win):
-                        del lst[saved[2]:]
+                    _restore(kv, saved)  # the chunks the one-call route appended are written again
                     return self._extend(x, kv, one_call=False)
                 return self._prefill(x, kv, one_call=False) if prefill else self._decode(x, kv, one_call=False)
-            except Exception as e2:
-                raise e2 from e  # (both tracebacks: the per-stage route's failure, caused by the one-call route's)
+            # (not one_call: the per-stage composition is the last executor there is, no CPU / eager-SDPA route exists by design)
+            return self._route_failure(e, not one_call, f"nsa_vibe_amd: the one-call native layer failed ({e}); falling back to the per-stage "
+                                       "native route", stages)
+
+    def _route_failure(self, e: RuntimeError, last: bool, warning: str, next_executor):
+        """The reference's router for a failed native executor (nsa_attention.py:764-782), called while `e` is being handled: it is counted;
+        then raised as it is when strict, when the failed executor was the last one, or when it is a HIP runtime / device error (a launch
+        failure, a fault: not a status return to route around); otherwise a warning, and the next executor's result is returned normally."""
+        self._fallback_counters["selection_hip_fails"] += 1
+        self._fallback_counters["total_fallbacks"] += 1
+        self._last_error = str(e)
+        if self._strict or last or "HIP error" in str(e):
+            raise
+        warnings.warn(warning, RuntimeWarning)
+        try:
+            return next_executor()
+        except Exception as e2:
+            raise e2 from e  # (both tracebacks: the next executor's failure, caused by the first one's)
 
     # ---- extend: prefill onto a filled cache / tiled prefill, decode semantics -------------------------------------------------
     def _extend_wanted(self, x: torch.Tensor, kv: NSA_KV) -> bool:
@@ -522,11 +532,15 @@ class NSAAttention(nn.Module):
         """capacity and block metadata for the chunk (metadata refreshed by the decode step's policy, reference :606-632)"""
         t0 = kv.t
         kv.ensure_capacity(t0 + S)
-        if kv.meta.S_sel == 0:
-            kv.ensure_meta(max(t0 + S, self.l_sel))
-        elif t0 + S > kv.meta.S_sel * self.l_sel:
-            kv.ensure_meta(t0 + S)
+        self._refresh_meta(kv, t0 + S)
         return t0, kv.meta
+
+    def _refresh_meta(self, kv: NSA_KV, upto: int) -> None:
+        """block metadata refresh policy of the reference (:606-632): rebuilt only when the first `upto` tokens leave the covered blocks"""
+        if kv.meta.S_sel == 0:
+            kv.ensure_meta(max(upto, self.l_sel))
+        elif upto > kv.meta.S_sel * self.l_sel:
+            kv.ensure_meta(upto)
 
     def _extend_end(self, kv: NSA_KV, t0: int, S: int) -> None:
         """cache state and read counters as S decode steps leave them"""
@@ -545,12 +559,10 @@ class NSAAttention(nn.Module):
         ranges = torch.empty((B, S, self.n_kv_groups, self.n_sel, 2), dtype=torch.int32, device=dev)
         gates = torch.empty((B, S, self.n_kv_groups, 3), dtype=torch.float32, device=dev)
         O = torch.empty((B, S, self.n_heads * self.d_v), dtype=x.dtype, device=dev)
-        ws = workspace(dev, L.nsa_layer_extend_workspace(ctypes.byref(desc), B, S, t0, int(meta.S_sel)) + 256, "layer_extend")
-        wptr = (ws.data_ptr() + 255) & ~255
+        wptr, wsize, _ = workspace_at(dev, L.nsa_layer_extend_workspace(ctypes.byref(desc), B, S, t0, int(meta.S_sel)), "layer_extend", 256)
         cptr, crows, cvals = meta.device_csc(dev)
         rc = L.nsa_layer_extend(ctypes.byref(desc), ctypes.byref(kd), proj.data_ptr(), t0, S, cptr.data_ptr(), crows.data_ptr(),
-                                cvals.data_ptr(), int(meta.S_sel), ranges.data_ptr(), O.data_ptr(), gates.data_ptr(), wptr,
-                                ws.numel() - (wptr - ws.data_ptr()), _stream(dev))
+                                cvals.data_ptr(), int(meta.S_sel), ranges.data_ptr(), O.data_ptr(), gates.data_ptr(), wptr, wsize, _stream(dev))
         _lib.check(rc, "nsa_layer_extend")
         self._extend_end(kv, t0, S)
         return O, ranges, gates
@@ -581,10 +593,10 @@ class NSAAttention(nn.Module):
         ws = workspace(dev, nb, "extend_attn")
         _lib.check(L.nsa_sel_attn_fwd(Q.data_ptr(), Ks.data_ptr(), Vs.data_ptr(), ranges.data_ptr(), O_sel.data_ptr(), None, B, S, G, h, Dk, Dv,
                                       S_kv, self.n_sel, Ks.stride(0), Ks.stride(1), Ks.stride(2), Vs.stride(0), Vs.stride(1), Vs.stride(2), dt,
-                                      scale, 0, ws.data_ptr() if ws is not None else None, nb, st), "nsa_sel_attn_fwd")
+                                      scale, 0, _ws_args(ws)[0], nb, st), "nsa_sel_attn_fwd")
         nb = L.nsa_band_attn_fwd_workspace(B, S, G, h, Dk, Dv, dt)
         ws = workspace(dev, nb, "extend_band")
-        wp = ws.data_ptr() if ws is not None else None
+        wp = _ws_args(ws)[0]
         _lib.check(L.nsa_band_attn_fwd(Q.data_ptr(), Kw.data_ptr(), Vw.data_ptr(), O_win.data_ptr(), None, B, S, G, h, Dk, Dv, S_kv,
                                        Kw.stride(0), Kw.stride(1), Kw.stride(2), Vw.stride(0), Vw.stride(1), Vw.stride(2), t0, 0, 1, 0, self.w,
                                        dt, scale, 0, wp, nb, st), "nsa_band_attn_fwd")
@@ -650,15 +662,13 @@ class NSAAttention(nn.Module):
         ranges = torch.empty((B, S, G, W, 2), dtype=torch.int32, device=dev)
         gates = torch.empty((B, S, G, 3), dtype=torch.float32, device=dev)
         O = torch.empty((B, S, self.n_heads * self.d_v), dtype=x.dtype, device=dev)
-        ws = workspace(dev, L.nsa_layer_prefill_workspace(ctypes.byref(desc), B, S, int(meta.S_sel)) + 256, "layer_prefill")
-        wptr = (ws.data_ptr() + 255) & ~255
+        wptr, wsize, _ = workspace_at(dev, L.nsa_layer_prefill_workspace(ctypes.byref(desc), B, S, int(meta.S_sel)), "layer_prefill", 256)
         cptr, crows, cvals = meta.device_csc(dev)
         rc = L.nsa_layer_prefill(ctypes.byref(desc), ctypes.byref(kd), proj.data_ptr(), S, mode, cptr.data_ptr(), crows.data_ptr(),
-                                 cvals.data_ptr(), int(meta.S_sel), ranges.data_ptr(), W, O.data_ptr(), gates.data_ptr(), wptr,
-                                 ws.numel() - (wptr - ws.data_ptr()), _stream(dev))
+                                 cvals.data_ptr(), int(meta.S_sel), ranges.data_ptr(), W, O.data_ptr(), gates.data_ptr(), wptr, wsize, _stream(dev))
         _lib.check(rc, "nsa_layer_prefill")
         kv.t = S
-        kv.n_cmp = 0 if S < self.l else (S - self.l) // self.d + 1
+        kv.n_cmp = _n_cmp(S, self.l, self.d)
         _set_plain(self, "_last_ranges", ranges)
         _set_plain(self, "_last_gates", gates)
         return O if mix_only else self.out(O), kv
@@ -689,7 +699,7 @@ class NSAAttention(nn.Module):
         """the whole decode step in one native call (nsa_layer_decode_step): ~15 kernel launches, no host sync"""
         t, B, dev = kv.t, x.shape[0], x.device
         kv.ensure_capacity(t + 1)
-        if kv.meta.S_sel == 0:  # block metadata refresh policy of the reference (:606-632)
+        if kv.meta.S_sel == 0:  # _refresh_meta and _n_cmp, inline: a call each is measurable in this step's host time
             kv.ensure_meta(max(t + 1, self.l_sel))
         elif t + 1 > kv.meta.S_sel * self.l_sel:
             kv.ensure_meta(t + 1)
@@ -700,11 +710,10 @@ class NSAAttention(nn.Module):
         ctx = getattr(kv, "_dec_ctx", None)  # per-cache constants of the native call (descriptors, workspace, monitors)
         if ctx is None or ctx[0] is not desc:
             kd = self._kv_desc(kv)
-            ws = workspace(dev, L.nsa_layer_decode_step_workspace(ctypes.byref(desc), B, kd.S_max) + 256, "layer_decode")
-            wptr = (ws.data_ptr() + 255) & ~255
+            wptr, wsize, ws = workspace_at(dev, L.nsa_layer_decode_step_workspace(ctypes.byref(desc), B, kd.S_max), "layer_decode", 256)
             ranges = torch.empty((B, self.n_kv_groups, self.n_sel, 2), dtype=torch.int32, device=dev)
             gates = torch.empty((B, 1, self.n_kv_groups, 3), dtype=torch.float32, device=dev)
-            ctx = kv._dec_ctx = (desc, ctypes.byref(desc), ctypes.byref(kd), kd, ws, wptr, ws.numel() - (wptr - ws.data_ptr()), ranges, gates)
+            ctx = kv._dec_ctx = (desc, ctypes.byref(desc), ctypes.byref(kd), kd, ws, wptr, wsize, ranges, gates)
         _, desc_ref, kd_ref, _, _, wptr, wsize, ranges, gates = ctx
         cptr, crows, cvals = kv.meta.device_csc(dev)
         xc = x.reshape(B, self.dim)
@@ -753,20 +762,12 @@ class NSAAttention(nn.Module):
         saved = (kv.t, kv.n_cmp, len(kv.reads_pred))
         try:
             return self._decode_rows_native(x, kv)
-        except RuntimeError as e:  # forward's router: counted; strict or a device error raises; else the S single steps from the saved state
-            self._fallback_counters["selection_hip_fails"] += 1
-            self._fallback_counters["total_fallbacks"] += 1
-            self._last_error = str(e)
-            if self._strict or "HIP error" in str(e):
-                raise
-            warnings.warn(f"nsa_vibe_amd: the one-call decode step for {S} tokens failed ({e}); falling back to {S} single steps", RuntimeWarning)
-            try:
-                kv.t, kv.n_cmp = saved[0], saved[1]
-                for lst in (kv.reads_pred, kv.reads_act_total, kv.reads_act_sel, kv.reads_act_cmp, kv.reads_act_win):
-                    del lst[saved[2]:]
+        except RuntimeError as e:
+            def steps():  # the next executor: the S single steps from the saved state
+                _restore(kv, saved)
                 return self._decode_rows_steps(x, kv)
-            except Exception as e2:
-                raise e2 from e
+            return self._route_failure(e, False, f"nsa_vibe_amd: the one-call decode step for {S} tokens failed ({e}); falling back to {S} "
+                                       "single steps", steps)
 
     def _decode_rows_steps(self, x: torch.Tensor, kv: NSA_KV):
         """S decode steps, concatenated: the definition of decode_rows' result"""
@@ -789,12 +790,10 @@ class NSAAttention(nn.Module):
         ranges = torch.empty((B, S, self.n_kv_groups, self.n_sel, 2), dtype=torch.int32, device=dev)
         gates = torch.empty((B, S, self.n_kv_groups, 3), dtype=torch.float32, device=dev)
         y = torch.empty((B, S, self.dim), dtype=x.dtype, device=dev)
-        ws = workspace(dev, L.nsa_layer_decode_rows_workspace(ctypes.byref(desc), B, S, kd.S_max) + 256, "layer_decode_rows")
-        wptr = (ws.data_ptr() + 255) & ~255
+        wptr, wsize, _ = workspace_at(dev, L.nsa_layer_decode_rows_workspace(ctypes.byref(desc), B, S, kd.S_max), "layer_decode_rows", 256)
         cptr, crows, cvals = meta.device_csc(dev)
         rc = L.nsa_layer_decode_rows(ctypes.byref(desc), ctypes.byref(kd), x.data_ptr(), y.data_ptr(), t0, S, cptr.data_ptr(), crows.data_ptr(),
-                                     cvals.data_ptr(), int(meta.S_sel), ranges.data_ptr(), gates.data_ptr(), wptr,
-                                     ws.numel() - (wptr - ws.data_ptr()), _stream(dev))
+                                     cvals.data_ptr(), int(meta.S_sel), ranges.data_ptr(), gates.data_ptr(), wptr, wsize, _stream(dev))
         _lib.check(rc, "nsa_layer_decode_rows")
         self._extend_end(kv, t0, S)
         _set_plain(self, "_last_ranges", ranges)
@@ -814,12 +813,8 @@ class NSAAttention(nn.Module):
             K_new = apply_rope(kv._K_raw[:, :, S_raw - self.l: S_raw], p_last).mean(dim=2, keepdim=True)
             V_new = kv._V_raw[:, :, S_raw - self.l: S_raw].mean(dim=2, keepdim=True)
             kv.write_compressed(K_new.to(kv._K_cmp.dtype), V_new.to(kv._V_cmp.dtype))
-        # block metadata refresh policy of the reference (:606-632): rebuild only when t leaves the covered blocks
-        if kv.meta.S_sel == 0:
-            kv.ensure_meta(max(t + 1, self.l_sel))
-        elif t + 1 > kv.meta.S_sel * self.l_sel:
-            kv.ensure_meta(t + 1)
-        num_cmp = 0 if S_raw < self.l else (S_raw - self.l) // self.d + 1
+        self._refresh_meta(kv, t + 1)
+        num_cmp = _n_cmp(S_raw, self.l, self.d)
         kv.append_reads(num_cmp, S_raw)
         scale = 1.0 / math.sqrt(self.d_k)
         Qc = Q.contiguous()

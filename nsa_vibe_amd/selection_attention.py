@@ -20,7 +20,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .selection_scorer import _DT, _need_gpu, _stream, workspace
+from .selection_scorer import _DT, _need_gpu, _scale_arg, _stream, _ws_args, workspace
 
 
 def _prep_kv(X: torch.Tensor) -> torch.Tensor:
@@ -66,8 +66,8 @@ def _fwd(Q, K, V, ranges, scale, variant, want_lse):
     rc = L.nsa_sel_attn_fwd(Qc.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), rg.data_ptr(), O.data_ptr(),
                             lse.data_ptr() if lse is not None else None, B, S, G, h, Dk, Dv, S_kv, n,
                             Kc.stride(0), Kc.stride(1), Kc.stride(2), Vc.stride(0), Vc.stride(1), Vc.stride(2),
-                            dt, float(scale) if scale else 0.0, int(variant),
-                            ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, _stream(dev))
+                            dt, _scale_arg(scale), int(variant),
+                            *_ws_args(ws), _stream(dev))
     _lib.check(rc, "nsa_sel_attn_fwd")
     return O, lse, (Qc, Kc, Vc, rg)
 
@@ -100,8 +100,8 @@ class _SelAttnFn(torch.autograd.Function):
                                 lse.data_ptr(), dO.data_ptr(), dQ.data_ptr(), dK.data_ptr(), dV.data_ptr(),
                                 B, S, G, h, Dk, Dv, S_kv, rg.shape[3],
                                 Kc.stride(0), Kc.stride(1), Kc.stride(2), Vc.stride(0), Vc.stride(1), Vc.stride(2),
-                                _DT[Qc.dtype], float(ctx.scale) if ctx.scale else 0.0, int(ctx.bwd_variant),
-                                ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, _stream(dev))
+                                _DT[Qc.dtype], _scale_arg(ctx.scale), int(ctx.bwd_variant),
+                                *_ws_args(ws), _stream(dev))
         _lib.check(rc, "nsa_sel_attn_bwd")
         return dQ, dK.to(Kc.dtype), dV.to(Vc.dtype), None, None, None, None
 
@@ -169,7 +169,7 @@ def selection_attention_head_causal_parity(Q: torch.Tensor, K: torch.Tensor, V: 
     O = torch.empty((B, S, G, h, Dv), dtype=V.dtype, device=dev)
     rc = _lib.lib().nsa_sel_attn_head_causal_parity(Qc.data_ptr(), Kk.data_ptr(), Vv.data_ptr(), rg.data_ptr(), O.data_ptr(), B, S, G, h, Dk,
                                                     Dv, S_kv, rg.shape[3], Kk.stride(0), Kk.stride(1), Kk.stride(2), Vv.stride(0),
-                                                    Vv.stride(1), Vv.stride(2), _DT[Q.dtype], float(scale) if scale else 0.0, _stream(dev))
+                                                    Vv.stride(1), Vv.stride(2), _DT[Q.dtype], _scale_arg(scale), _stream(dev))
     _lib.check(rc, "nsa_sel_attn_head_causal_parity")
     return O
 
@@ -183,27 +183,37 @@ def selection_decode_step(Q: torch.Tensor, K_cmp: torch.Tensor, K: torch.Tensor,
     covering t_token.  Returns (O [B,1,G,h,Dv], ranges [B,G,n_top,2] int32) = what the decode branch of the
     reference computes with compute_pcmp_all -> map_pcmp_to_pslc_batched -> sum(dim=3) -> select_topn_ranges ->
     selection executor (nsa/core/nsa_attention.py:651-672, 704-830), sequential-selector semantics."""
+    L = _lib.lib()
+    return _selection_decode(L.nsa_sel_decode_step, L.nsa_sel_decode_step_workspace, "decode", False, Q, K_cmp, K, V, meta, n_top, t_token, scale,
+                             out, ranges_out)
+
+
+def _selection_decode(call, size, tag: str, rows: bool, Q, K_cmp, K, V, meta, n_top, t0, scale, out, ranges_out):
+    """the body of selection_decode_step (rows = False: S = 1, ranges without the S axis, no S in the C signatures) and selection_decode_rows.
+    (The single step is host bound at small shapes -- tools/prof_decode_step_host.py -- so the workspace and scale idioms stay inline here.)"""
     dev = _need_gpu(Q, K_cmp, K, V)
     B, S, G, h, Dk = Q.shape
-    if S != 1:
-        raise RuntimeError("selection_decode_step: decode requires S == 1")
     S_kv, Dv = K.shape[2], V.shape[3]
     S_cmp, S_sel = K_cmp.shape[2], meta.S_sel
+    if not rows and S != 1:
+        raise RuntimeError("selection_decode_step: decode requires S == 1")
+    if rows and S_kv < t0 + S:
+        raise RuntimeError("selection_decode_rows: the cache must hold the S tokens t0 .. t0 + S - 1")
     Qc, Kc, Kk, Vv = Q.contiguous(), _prep_kv(K_cmp), _prep_kv(K), _prep_kv(V)
-    O = out if out is not None else torch.empty((B, 1, G, h, Dv), dtype=V.dtype, device=dev)
-    rg = ranges_out if ranges_out is not None else torch.empty((B, G, n_top, 2), dtype=torch.int32, device=dev)
-    L = _lib.lib()
+    O = out if out is not None else torch.empty((B, S, G, h, Dv), dtype=V.dtype, device=dev)
+    rg = ranges_out if ranges_out is not None else torch.empty((B, S, G, n_top, 2) if rows else (B, G, n_top, 2), dtype=torch.int32, device=dev)
+    if rows and O.numel() == 0:
+        return O, rg
     dt = _DT[Q.dtype]
-    ws = workspace(dev, L.nsa_sel_decode_step_workspace(B, G, h, Dk, Dv, S_cmp, S_sel, n_top, dt) + 16, "decode")
+    s = (S,) if rows else ()
+    ws = workspace(dev, size(B, *s, G, h, Dk, Dv, S_cmp, S_sel, n_top, dt) + 16, tag)
     wptr = (ws.data_ptr() + 15) & ~15
     cptr, crows, cvals = meta.device_csc(dev)
-    rc = L.nsa_sel_decode_step(Qc.data_ptr(), Kc.data_ptr(), Kk.data_ptr(), Vv.data_ptr(), cptr.data_ptr(), crows.data_ptr(),
-                               cvals.data_ptr(), rg.data_ptr(), O.data_ptr(), B, G, h, Dk, Dv, S_cmp, S_sel, S_kv,
-                               int(meta.l), int(meta.d), int(meta.l_sel), int(n_top), int(t_token),
-                               Kc.stride(0), Kc.stride(1), Kc.stride(2), Kk.stride(0), Kk.stride(1), Kk.stride(2),
-                               Vv.stride(0), Vv.stride(1), Vv.stride(2), dt, float(scale) if scale else 0.0,
-                               wptr, ws.numel() - (wptr - ws.data_ptr()), _stream(dev))
-    _lib.check(rc, "nsa_sel_decode_step")
+    rc = call(Qc.data_ptr(), Kc.data_ptr(), Kk.data_ptr(), Vv.data_ptr(), cptr.data_ptr(), crows.data_ptr(), cvals.data_ptr(), rg.data_ptr(),
+              O.data_ptr(), B, *s, G, h, Dk, Dv, S_cmp, S_sel, S_kv, int(meta.l), int(meta.d), int(meta.l_sel), int(n_top), int(t0),
+              Kc.stride(0), Kc.stride(1), Kc.stride(2), Kk.stride(0), Kk.stride(1), Kk.stride(2), Vv.stride(0), Vv.stride(1), Vv.stride(2), dt,
+              float(scale) if scale else 0.0, wptr, ws.numel() - (wptr - ws.data_ptr()), _stream(dev))
+    _lib.check(rc, call.__name__)
     return O, rg
 
 
@@ -231,30 +241,9 @@ def selection_decode_rows(Q: torch.Tensor, K_cmp: torch.Tensor, K: torch.Tensor,
     tokens were appended (S_kv >= t0 + S) and meta = BlockMeta of t0 + S tokens.  Row s computes what selection_decode_step computes at
     t = t0 + s on the cache truncated to t + 1 tokens (its own n_cmp(t) compressed rows, sequential selection at t, K/V[:t+1]).
     Returns (O [B,S,G,h,Dv], ranges [B,S,G,n_top,2] int32)."""
-    dev = _need_gpu(Q, K_cmp, K, V)
-    B, S, G, h, Dk = Q.shape
-    S_kv, Dv = K.shape[2], V.shape[3]
-    S_cmp, S_sel = K_cmp.shape[2], meta.S_sel
-    if S_kv < t0 + S:
-        raise RuntimeError("selection_decode_rows: the cache must hold the S tokens t0 .. t0 + S - 1")
-    Qc, Kc, Kk, Vv = Q.contiguous(), _prep_kv(K_cmp), _prep_kv(K), _prep_kv(V)
-    O = out if out is not None else torch.empty((B, S, G, h, Dv), dtype=V.dtype, device=dev)
-    rg = ranges_out if ranges_out is not None else torch.empty((B, S, G, n_top, 2), dtype=torch.int32, device=dev)
-    if O.numel() == 0:
-        return O, rg
     L = _lib.lib()
-    dt = _DT[Q.dtype]
-    ws = workspace(dev, L.nsa_sel_decode_rows_workspace(B, S, G, h, Dk, Dv, S_cmp, S_sel, n_top, dt) + 16, "decode_rows")
-    wptr = (ws.data_ptr() + 15) & ~15
-    cptr, crows, cvals = meta.device_csc(dev)
-    rc = L.nsa_sel_decode_rows(Qc.data_ptr(), Kc.data_ptr(), Kk.data_ptr(), Vv.data_ptr(), cptr.data_ptr(), crows.data_ptr(),
-                               cvals.data_ptr(), rg.data_ptr(), O.data_ptr(), B, S, G, h, Dk, Dv, S_cmp, S_sel, S_kv,
-                               int(meta.l), int(meta.d), int(meta.l_sel), int(n_top), int(t0),
-                               Kc.stride(0), Kc.stride(1), Kc.stride(2), Kk.stride(0), Kk.stride(1), Kk.stride(2),
-                               Vv.stride(0), Vv.stride(1), Vv.stride(2), dt, float(scale) if scale else 0.0,
-                               wptr, ws.numel() - (wptr - ws.data_ptr()), _stream(dev))
-    _lib.check(rc, "nsa_sel_decode_rows")
-    return O, rg
+    return _selection_decode(L.nsa_sel_decode_rows, L.nsa_sel_decode_rows_workspace, "decode_rows", True, Q, K_cmp, K, V, meta, n_top, t0, scale,
+                             out, ranges_out)
 
 
 def selection_decode_rows_plan(B: int, S: int, G: int, h: int, Dk: int, Dv: int, S_cmp: int, S_sel: int, S_kv: int, n_top: int,
@@ -309,8 +298,7 @@ def select_and_attend(p_grp: torch.Tensor, Q: torch.Tensor, K: torch.Tensor, V: 
                                    md, S, ranges.data_ptr(), W, Qc.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), O.data_ptr(),
                                    lse.data_ptr() if lse is not None else None, B, S, G, h, Dk, Dv, S_kv,
                                    Kc.stride(0), Kc.stride(1), Kc.stride(2), Vc.stride(0), Vc.stride(1), Vc.stride(2),
-                                   dt, float(scale) if scale else 0.0, ws.data_ptr() if ws is not None else None,
-                                   ws.numel() if ws is not None else 0, _stream(dev))
+                                   dt, _scale_arg(scale), *_ws_args(ws), _stream(dev))
     _lib.check(rc, "nsa_sel_select_attn_fwd")
     return (ranges, O, lse) if return_lse else (ranges, O)
 

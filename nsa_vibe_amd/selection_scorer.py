@@ -55,6 +55,23 @@ def workspace(dev: torch.device, nbytes: int, tag: str = "ws") -> Optional[torch
     return buf
 
 
+def workspace_at(dev: torch.device, nbytes: int, tag: str, align: int):
+    """workspace() of nbytes from an `align`-byte boundary on -> (pointer, bytes behind it, the buffer)"""
+    ws = workspace(dev, nbytes + align, tag)
+    ptr = (ws.data_ptr() + align - 1) & ~(align - 1)
+    return ptr, ws.numel() - (ptr - ws.data_ptr()), ws
+
+
+def _ws_args(ws: Optional[torch.Tensor]):
+    """(pointer, bytes) of an optional workspace as the C ABI takes them"""
+    return (ws.data_ptr(), ws.numel()) if ws is not None else (None, 0)
+
+
+def _scale_arg(scale: Optional[float]) -> float:
+    """the C ABI's scale: 0 asks for 1/sqrt(Dk)"""
+    return float(scale) if scale else 0.0
+
+
 def _kc_strides(K_cmp: torch.Tensor):
     if K_cmp.stride(-1) != 1:
         K_cmp = K_cmp.contiguous()
@@ -169,8 +186,8 @@ def selection_scores(Q_all: torch.Tensor, K_cmp: torch.Tensor, meta: BlockMeta, 
     cptr, crows, cvals = meta.device_csc(dev)
     args = (Q_all.data_ptr(), K_cmp.data_ptr(), p_grp.data_ptr(), B, S, G, h, Dk, S_cmp, sb, sg, ss, cptr.data_ptr(), crows.data_ptr(),
             cvals.data_ptr(), S_sel, int(meta.l), int(meta.d), int(meta.l_sel), (2 if leave_skipped else 1) if causal_skip else 0, int(variant),
-            _DT[Q_all.dtype], float(scale) if scale else 0.0)
-    tail = (ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, _stream(dev))
+            _DT[Q_all.dtype], _scale_arg(scale))
+    tail = (*_ws_args(ws), _stream(dev))
     if q0 == 0 and norm == 0:
         _lib.check(L.nsa_sel_scores(*args, *tail), "nsa_sel_scores")
     else:
@@ -216,9 +233,9 @@ def selection_scores_select(Q_all: torch.Tensor, K_cmp: torch.Tensor, meta: Bloc
     ws = workspace(dev, nbytes, "scores")
     cptr, crows, cvals = meta.device_csc(dev)
     args = (Q_all.data_ptr(), K_cmp.data_ptr(), p_grp.data_ptr(), B, S, G, h, Dk, S_cmp, sb, sg, ss, cptr.data_ptr(), crows.data_ptr(),
-            cvals.data_ptr(), S_sel, *geo, 2 if leave_skipped else 1, dt, float(scale) if scale else 0.0, int(t0), int(n_top),
+            cvals.data_ptr(), S_sel, *geo, 2 if leave_skipped else 1, dt, _scale_arg(scale), int(t0), int(n_top),
             int(bool(force_init)), int(force_local), md, S, ranges.data_ptr(), W)
-    tail = (ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, _stream(dev))
+    tail = (*_ws_args(ws), _stream(dev))
     if q0 == 0 and norm == 0:
         _lib.check(L.nsa_sel_scores_select(*args, *tail), "nsa_sel_scores_select")
     else:
