@@ -18,6 +18,7 @@
 
 #include "../../include/nsa_sel_hip.h"
 #include "sel_attn_params.hpp"
+#include "sel_scores_params.hpp"
 
 // ---- the HIP runtime as this program answers it ------------------------------------------------
 static const hipError_t REFUSED = hipErrorNotSupported;
@@ -25,10 +26,11 @@ static int g_refuse_at = -1;  // index of the launch that is refused (-1: none)
 static int g_launches = 0, g_memsets = 0;
 static hipError_t g_last = hipSuccess;
 static std::vector<std::string> g_geom;
-static int g_peek_launch = -1;  // copy g_peek bytes of this launch's first kernel argument (an argument block passed by value)
-static std::vector<unsigned char> g_peek;
-static int g_peek_arg2 = -1;  // and g_peek2 bytes of this further argument of the same launch
-static std::vector<unsigned char> g_peek2;
+struct Peek {  // copy `bytes` of kernel argument `arg` of launch `launch` (an argument block or a scalar passed by value)
+    int launch, arg;
+    std::vector<unsigned char> bytes;
+};
+static std::vector<Peek> g_peeks;
 struct Config {
     dim3 grid, block;
     size_t shmem;
@@ -85,8 +87,8 @@ __attribute__((visibility("default"))) hipError_t hipLaunchKernel(const void *, 
     char s[96];
     snprintf(s, sizeof(s), "%u,%u,%u/%u,%u,%u/%zu", grid.x, grid.y, grid.z, block.x, block.y, block.z, shmem);
     g_geom.push_back(s);
-    if (i == g_peek_launch && !g_peek.empty()) memcpy(g_peek.data(), args[0], g_peek.size());
-    if (i == g_peek_launch && g_peek_arg2 >= 0) memcpy(g_peek2.data(), args[g_peek_arg2], g_peek2.size());
+    for (Peek &p : g_peeks)
+        if (p.launch == i) memcpy(p.bytes.data(), args[p.arg], p.bytes.size());
     if (i == g_refuse_at) return g_last = REFUSED;
     return hipSuccess;
 }
@@ -161,29 +163,22 @@ static void run(const char *label, const std::function<int()> &call, const std::
     printf("%s\n%s: {\"rc\": %d, \"error\": %s, \"launches\": %s, \"geometry\": %s, \"memsets\": %d%s}", g_first ? "" : ",", quoted(label).c_str(), rc,
            quoted(err).c_str(), list(names).c_str(), geometry.c_str(), memsets, more.c_str());
     g_first = false;
-    g_peek_launch = g_peek_arg2 = -1;
-    g_peek.clear();
+    g_peeks.clear();
 }
 
-// the argument block of pcmp_kernel up to its scale (PcmpParams, sel_scores.hip)
-struct PcmpHead {
-    const void *Q, *Kc;
-    float *p_cmp;
-    int64_t row0, nrows;
-    int S, G, h, Dk, S_cmp;
-    int64_t csb, csg, css;
-    float scale;
-};
-
 template <class P>
-static void peek(int launch) {
-    g_peek_launch = launch;
-    g_peek.assign(sizeof(P), 0);
+static void peek(int launch, int arg = 0) {
+    g_peeks.push_back({launch, arg, std::vector<unsigned char>(sizeof(P), 0)});
+}
+template <class P>
+static P peeked(size_t i = 0) {
+    P p;
+    memcpy(&p, g_peeks[i].bytes.data(), sizeof(P));
+    return p;
 }
 template <class P>
 static std::string peeked_scale() {
-    P p;
-    memcpy(&p, g_peek.data(), sizeof(P));
+    const P p = peeked<P>();
     char s[64];
     snprintf(s, sizeof(s), "\"scale\": %.9g", (double)p.scale);
     return s;
@@ -212,17 +207,13 @@ static void run_step(const char *label, const std::function<int()> &call) {
         for (size_t i = 0; i < g_names.size(); ++i)
             if (g_names[i] == "decode_step launch" || g_names[i] == "decode_rows launch") at = (int)i;
         if (at < 0) return std::string("\"step\": null");
-        nsa::DecStepParams P;
-        nsa::DecAttnArgs A;
-        g_peek_launch = at;
-        g_peek.assign(sizeof(P), 0);
-        g_peek_arg2 = 3;
-        g_peek2.assign(sizeof(A), 0);
+        peek<nsa::DecStepParams>(at);
+        peek<nsa::DecAttnArgs>(at, 3);
         g_refuse_at = -1;
         g_launches = 0;
         call();
-        memcpy(&P, g_peek.data(), sizeof(P));
-        memcpy(&A, g_peek2.data(), sizeof(A));
+        const nsa::DecStepParams P = peeked<nsa::DecStepParams>(0);
+        const nsa::DecAttnArgs A = peeked<nsa::DecAttnArgs>(1);
         char s[1024];
         snprintf(s, sizeof(s),
                  "\"step\": {\"Q\": \"%s\", \"Kc\": \"%s\", \"part_g\": \"%s\", \"halo_g\": \"%s\", \"pg_g\": \"%s\", \"cnt\": \"%s\", \"R\": %d, \"G\": %d, "
@@ -234,6 +225,87 @@ static void run_step(const char *label, const std::function<int()> &call) {
                  P.S, where(A.Q).c_str(), where(A.K).c_str(), where(A.V).c_str(), where(A.O).c_str(), A.G, A.h, A.S_kv, A.n, (long long)A.ksb,
                  (long long)A.ksg, (long long)A.kss, (long long)A.vsb, (long long)A.vsg, (long long)A.vss, (double)A.c2);
         return std::string(s);
+    });
+}
+
+// ---- the argument blocks of the scorer and selector family (sel_scores_params.hpp), member by member
+struct Obj {
+    std::string s;
+    Obj &raw(const char *k, const std::string &v) {
+        s += (s.empty() ? "\"" : ", \"") + std::string(k) + "\": " + v;
+        return *this;
+    }
+    Obj &i(const char *k, long long v) { return raw(k, std::to_string(v)); }
+    Obj &f(const char *k, double v) {
+        char b[40];
+        snprintf(b, sizeof(b), "%.9g", v);
+        return raw(k, b);
+    }
+    Obj &p(const char *k, const void *v) { return raw(k, quoted(where(v))); }
+    std::string str() const { return "{" + s + "}"; }
+};
+#define M_I(m) i(#m, P.m)
+#define M_P(m) p(#m, P.m)
+static std::string show(const nsa::PcmpParams &P) {
+    return Obj().M_P(Q).M_P(Kc).M_P(p_cmp).M_I(row0).M_I(nrows).M_I(S).M_I(G).M_I(h).M_I(Dk).M_I(S_cmp).M_I(csb).M_I(csg).M_I(css).f("scale", P.scale)
+        .M_I(q0).M_I(norm).M_I(l).M_I(d).str();
+}
+static std::string show(const nsa::MapParams &P) {
+    return Obj().M_P(p_cmp).M_P(csc_ptr).M_P(csc_rows).M_P(csc_vals).M_P(p_slc).M_P(p_grp).M_I(R).M_I(h).M_I(S_cmp_cur).M_I(S_sel).str();
+}
+static std::string show(const nsa::DecodeParams &P) {
+    return Obj().M_P(Q).M_P(Kc).M_P(x).M_P(part).M_P(p_grp).M_P(csc_ptr).M_P(csc_rows).M_P(csc_vals).M_I(R).M_I(S).M_I(G).M_I(h).M_I(Dk).M_I(S_cmp)
+        .M_I(S_sel).M_I(csb).M_I(csg).M_I(css).f("c2", P.c2).M_I(stencil).M_I(q0).M_I(norm).M_I(l).M_I(d).str();
+}
+static std::string show(const nsa::ScoresMfmaParams &P) {
+    return Obj().M_P(Q).M_P(Kc).M_P(p_grp).M_I(B).M_I(S).M_I(G).M_I(h).M_I(S_cmp).M_I(S_sel).M_I(csb).M_I(csg).M_I(css).f("scale", P.scale)
+        .M_I(causal_skip).M_I(d_stride).M_I(big_out).M_I(q0).M_I(norm).M_I(l).str();
+}
+static std::string show(const nsa::SelectParams &P) {
+    return Obj().M_P(p_grp).M_P(t_rows).M_P(out).M_I(R).M_I(S).M_I(G).M_I(t0).M_I(S_sel).M_I(l_sel).M_I(n_top).M_I(force_init).M_I(force_local).M_I(mode)
+        .M_I(W).M_I(k_actual).M_I(n_forced).M_I(keepmask).M_I(all_valid).M_I(l_sel_shift).M_I(forced_plain).str();
+}
+static std::string show(const int &v) { return std::to_string(v); }
+#undef M_I
+#undef M_P
+
+// one kernel argument of every launch of `launcher` (as nsa_hip_last_error() names it): its index, its size and how to print it
+struct Want {
+    std::string launcher;
+    int arg;
+    size_t bytes;
+    const char *key;
+    std::function<std::string(const void *)> print;
+};
+template <class P>
+static Want want(const char *launcher, const char *key, int arg = 0) {
+    return {std::string(launcher) + " launch", arg, sizeof(P), key, [](const void *b) {
+                P p;
+                memcpy(&p, b, sizeof(P));
+                return show(p);
+            }};
+}
+// walks `call` like run(), then calls it once more and prints the wanted arguments of its launches, in launch order:
+// "args": [{"launch": index, "<key>": value, ...}, ...]
+static void run_args(const std::string &label, const std::function<int()> &call, const std::vector<Want> &wants) {
+    run(label.c_str(), call, [&] {
+        std::vector<const Want *> of;
+        for (size_t i = 0; i < g_names.size(); ++i)
+            for (const Want &w : wants)
+                if (w.launcher == g_names[i]) {
+                    g_peeks.push_back({(int)i, w.arg, std::vector<unsigned char>(w.bytes, 0)});
+                    of.push_back(&w);
+                }
+        g_refuse_at = -1;
+        g_launches = 0;
+        call();
+        std::string o = "\"args\": [";
+        for (size_t k = 0; k < g_peeks.size(); ++k) {
+            const bool first = k == 0 || g_peeks[k].launch != g_peeks[k - 1].launch;
+            if (first) o += std::string(k ? "}, " : "") + "{\"launch\": " + std::to_string(g_peeks[k].launch);
+            o += ", " + quoted(of[k]->key) + ": " + of[k]->print(g_peeks[k].bytes.data());
+        }
+        return o + (g_peeks.empty() ? "]" : "}]");
     });
 }
 
@@ -368,12 +440,104 @@ int main(int argc, char **argv) {
     for (float scale : {0.f, -1.f, 0.25f}) {
         char label[64];
         snprintf(label, sizeof(label), "sel_scores_rows/generic_scale_%g", scale);
-        peek<PcmpHead>(0);
-        run(label, [&] { return scores(64, 0, 1, scale); }, peeked_scale<PcmpHead>);
+        peek<nsa::PcmpParams>(0);
+        run(label, [&] { return scores(64, 0, 1, scale); }, peeked_scale<nsa::PcmpParams>);
         snprintf(label, sizeof(label), "pcmp_all/scale_%g", scale);
-        peek<PcmpHead>(0);
-        run(label, [&] { return NSA_FN(nsa_pcmp_all)(Q, Kc, p_grp, B, 64, G, h, D, 3, (int64_t)G * 3 * D, 3 * D, D, dt, scale, nullptr); }, peeked_scale<PcmpHead>);
+        peek<nsa::PcmpParams>(0);
+        run(label, [&] { return NSA_FN(nsa_pcmp_all)(Q, Kc, p_grp, B, 64, G, h, D, 3, (int64_t)G * 3 * D, 3 * D, D, dt, scale, nullptr); }, peeked_scale<nsa::PcmpParams>);
     }
+
+    // ---- the scorer and selector family with its argument blocks.  64 rows of h = 6 at norm = 1 are the tiled (MFMA) scorers' shape: with
+    // norm = 0 the 128 rows of B = 1, G = 2 stay under DECODE_MAX_ROWS and take the decode-shaped pair
+    float *p_slc = (float *)dev(MB);
+    int32_t *t_rows = (int32_t *)dev(MB);
+    g_named = {{"Q", Q, MB}, {"O", O, MB}, {"ranges", ranges, MB}, {"ws", ws, 64 * MB}, {"p_grp", p_grp, MB}, {"Kc", Kc, MB}, {"csc_ptr", csc_ptr, MB},
+               {"csc_rows", csc_rows, MB}, {"csc_vals", csc_vals, MB}, {"p_slc", p_slc, MB}, {"t_rows", t_rows, MB}};
+    struct ScoresCase {
+        int B = 1, S = 64, h = 6, S_cmp = 3, dtype = NSA_DT_BF16, causal_skip = 0, variant = 0, q0 = 0, norm = 1;
+        void *Kc = nullptr;
+        int64_t css = 64;
+        size_t ws_bytes = (size_t)64 << 20;
+        // the selection of nsa_sel_scores_select_rows
+        int mode = NSA_SEL_SEQUENTIAL, out_width = 16;
+    };
+    typedef std::function<void(ScoresCase &)> Tweak;
+    const std::vector<Want> scorer_blocks = {want<nsa::PcmpParams>("pcmp", "PcmpParams"), want<nsa::MapParams>("map_pcmp", "MapParams"),
+                                             want<nsa::DecodeParams>("decode_logits", "DecodeParams"), want<nsa::DecodeParams>("decode_pgrp", "DecodeParams"),
+                                             want<nsa::ScoresMfmaParams>("scores_mfma", "ScoresMfmaParams"),
+                                             want<nsa::ScoresMfmaParams>("scores_mfma32", "ScoresMfmaParams"),
+                                             want<nsa::SelectParams>("scores_mfma32", "SelectParams", 1), want<nsa::SelectParams>("select_topn", "SelectParams")};
+    auto scores_case = [&](const char *label, const Tweak &tweak) {
+        ScoresCase c;
+        c.Kc = Kc;
+        tweak(c);
+        run_args(std::string("sel_scores_rows/") + label, [&] {
+            return scores_rows(Q, c.Kc, p_grp, c.B, c.S, G, c.h, D, c.S_cmp, (int64_t)G * c.S_cmp * c.css, (int64_t)c.S_cmp * c.css, c.css, csc_ptr, csc_rows,
+                               csc_vals, (c.q0 + c.S + 63) / 64, 32, 16, 64, c.causal_skip, c.variant, c.dtype, 0.f, c.q0, c.norm, ws, c.ws_bytes, nullptr);
+        }, scorer_blocks);
+    };
+    scores_case("v1", [](ScoresCase &c) { c.variant = 1; });
+    scores_case("mfma32_h6", [](ScoresCase &) {});
+    scores_case("mfma_h4", [](ScoresCase &c) { c.h = 4; });
+    for (int form : {0, 1}) {
+        set_tuning("SCORES_FORM", form);
+        scores_case(form ? "h6_SCORES_FORM_1" : "h6_SCORES_FORM_0", [](ScoresCase &) {});
+    }
+    set_tuning("SCORES_FORM", -1);
+    scores_case("v3", [](ScoresCase &c) { c.variant = 3; });
+    scores_case("f32_norm0", [](ScoresCase &c) { c.dtype = NSA_DT_F32; c.norm = 0; });
+    scores_case("f32_norm1", [](ScoresCase &c) { c.dtype = NSA_DT_F32; });
+    for (int variant : {0, 1, 2}) {  // (the entry point itself never leaves the tiled route of a shape: its callers ask for variant 1)
+        const std::string v = variant == 2 ? "_forced_v2" : variant ? "_v1" : "";
+        scores_case(("K_cmp_8_bytes_off" + v).c_str(), [&](ScoresCase &c) { c.Kc = off(Kc, 8); c.variant = variant; });
+        scores_case(("css_not_8" + v).c_str(), [&](ScoresCase &c) { c.css = 68; c.variant = variant; });
+    }
+    for (int variant : {0, 1, 3})
+        scores_case(("q0_100_v" + std::to_string(variant)).c_str(), [&](ScoresCase &c) { c.q0 = 100; c.S_cmp = 9; c.variant = variant; });
+    for (int skip : {0, 1, 2}) scores_case(("causal_skip_" + std::to_string(skip)).c_str(), [&](ScoresCase &c) { c.causal_skip = skip; });
+    scores_case("S_cmp_0", [](ScoresCase &c) { c.S_cmp = 0; });
+    // the generic scorer walks its rows in chunks of what the workspace holds: three rows' worth on a call of ten
+    scores_case("v1_10_rows_workspace_of_3", [](ScoresCase &c) { c.variant = 1; c.S = 5; c.S_cmp = 9; c.norm = 0; c.ws_bytes = 3 * sizeof(float) * 6 * 9; });
+
+    auto select_rows_fn = NSA_FN(nsa_sel_scores_select_rows);
+    auto select_rows_case = [&](const char *label, const Tweak &tweak) {
+        ScoresCase c;
+        c.Kc = Kc;
+        tweak(c);
+        run_args(std::string("sel_scores_select_rows/") + label, [&] {
+            return select_rows_fn(Q, c.Kc, p_grp, c.B, c.S, G, c.h, D, c.S_cmp, (int64_t)G * c.S_cmp * c.css, (int64_t)c.S_cmp * c.css, c.css, csc_ptr, csc_rows,
+                                  csc_vals, (c.q0 + c.S + 63) / 64, 32, 16, 64, c.causal_skip, c.dtype, 0.f, c.q0, n, 1, 2, c.mode, c.S, ranges, c.out_width,
+                                  c.q0, c.norm, ws, c.ws_bytes, nullptr);
+        }, scorer_blocks);
+    };
+    auto width = NSA_FN(nsa_batched_ranges_width);
+    select_rows_case("mfma32_sequential", [](ScoresCase &) {});
+    set_tuning("SCORES_SELECT", 1);
+    select_rows_case("mfma32_sequential_SCORES_SELECT_1", [](ScoresCase &) {});
+    select_rows_case("mfma32_batched_SCORES_SELECT_1", [&](ScoresCase &c) { c.mode = NSA_SEL_BATCHED; c.out_width = width(64, 1, 64, n, 1, 2); });
+    set_tuning("SCORES_SELECT", -1);
+    select_rows_case("mfma32_batched", [&](ScoresCase &c) { c.mode = NSA_SEL_BATCHED; c.out_width = width(64, 1, 64, n, 1, 2); });
+    select_rows_case("mfma32_q0_100", [](ScoresCase &c) { c.q0 = 100; c.S_cmp = 9; });
+    select_rows_case("mfma_h4", [](ScoresCase &c) { c.h = 4; });
+    select_rows_case("norm0_decode_shaped", [](ScoresCase &c) { c.norm = 0; });
+    select_rows_case("K_cmp_8_bytes_off", [&](ScoresCase &c) { c.Kc = off(Kc, 8); });
+    select_rows_case("sequential_wrong_out_width", [](ScoresCase &c) { c.out_width = 15; });
+    select_rows_case("batched_wrong_out_width", [&](ScoresCase &c) { c.mode = NSA_SEL_BATCHED; c.out_width = width(64, 1, 64, n, 1, 2) + 1; });
+    select_rows_case("no_rows", [](ScoresCase &c) { c.B = 0; });
+
+    auto topn_fn = NSA_FN(nsa_select_topn_ranges);
+    for (int S_sel : {64, 65}) {
+        const std::string at = "select_topn_ranges/S_sel" + std::to_string(S_sel);
+        const int S_ = 64 * S_sel, wb = width(S_, S_sel, 64, n, 1, 2);
+        const std::vector<Want> sp = {want<nsa::SelectParams>("select_topn", "SelectParams")};
+        run_args(at + "_batched", [&] { return topn_fn(p_grp, (int64_t)S_ * G, S_, G, 0, nullptr, S_sel, 64, n, 1, 2, NSA_SEL_BATCHED, S_, ranges, wb, nullptr); }, sp);
+        run_args(at + "_sequential", [&] { return topn_fn(p_grp, (int64_t)4 * G, 4, G, 7, nullptr, S_sel, 64, n, 1, 2, NSA_SEL_SEQUENTIAL, 4, ranges, n, nullptr); }, sp);
+        run_args(at + "_t_rows", [&] { return topn_fn(p_grp, (int64_t)4 * G, 4, G, 7, t_rows, S_sel, 64, n, 0, 1, NSA_SEL_SEQUENTIAL, 4, ranges, n, nullptr); }, sp);
+    }
+    for (float *slc : {(float *)nullptr, p_slc})
+        run_args(slc ? "map_pcmp_to_pgrp/with_p_slc" : "map_pcmp_to_pgrp/without_p_slc",
+                 [&] { return NSA_FN(nsa_map_pcmp_to_pgrp)((const float *)ws, 10, h, 9, csc_ptr, csc_rows, csc_vals, 3, slc, p_grp, nullptr); },
+                 {want<nsa::MapParams>("map_pcmp", "MapParams")});
 
     // ---- the layer calls on real pointers (the m7c layer, capacity 1024)
     nsa_layer_desc L{};
@@ -390,7 +554,6 @@ int main(int argc, char **argv) {
     auto prefill_fn = NSA_FN(nsa_layer_prefill);
     auto extend_fn = NSA_FN(nsa_layer_extend);
     auto decode_fn = NSA_FN(nsa_layer_decode_step);
-    auto width = NSA_FN(nsa_batched_ranges_width);
     auto prefill = [&](int S_, size_t ws_bytes = 64 * MB, int selector = NSA_SEL_BATCHED) {
         return prefill_fn(&L, &kv, proj, S_, selector, csc_ptr, csc_rows, csc_vals, S_sel_max, ranges, selector == NSA_SEL_BATCHED ? width(S_, S_sel_max, 64, 16, 1, 2) : 16, O_mix, nullptr,
                           ws, ws_bytes, nullptr);
@@ -438,14 +601,14 @@ int main(int argc, char **argv) {
 
     // ---- the decode-step family (m7c layer, capacity 1024), with the argument blocks of the one-launch kernels
     L.Dk = L.Dv = 64;
-    g_named = {{"Q", Q, MB}, {"O", O, MB}, {"ranges", ranges, MB}, {"ws", ws, 64 * MB}, {"K_sel", kv.K_sel, MB}, {"V_sel", kv.V_sel, MB}, {"K_cmp", Kcmp, MB}};
+    g_named.insert(g_named.end(), {{"K_sel", kv.K_sel, MB}, {"V_sel", kv.V_sel, MB}, {"K_cmp", Kcmp, MB}});
     const int64_t csb = (int64_t)L.G * 1024 * D, csg = (int64_t)1024 * D, ccb = (int64_t)L.G * 63 * D, ccg = (int64_t)63 * D;
     auto ncmp = [](int S_) { return S_ < 32 ? 0 : (S_ - 32) / 16 + 1; };
     auto sel_step_fn = NSA_FN(nsa_sel_decode_step);
     auto sel_step_need = [&](int t, int n_top) { return NSA_FN(nsa_sel_decode_step_workspace)(1, L.G, L.h, D, D, ncmp(t + 1), S_sel_max, n_top, dt); };
-    auto sel_step = [&](int t, void *Kc_ = nullptr, int n_top = 16, size_t ws_bytes = 64 * MB) {
-        return sel_step_fn(Q, Kc_ ? Kc_ : Kcmp, kv.K_sel, kv.V_sel, csc_ptr, csc_rows, csc_vals, ranges, O, 1, L.G, L.h, D, D, ncmp(t + 1), S_sel_max, t + 1, 32, 16, 64,
-                           n_top, t, ccb, ccg, D, csb, csg, D, csb, csg, D, dt, 0.f, ws, ws_bytes, nullptr);
+    auto sel_step = [&](int t, void *Kc_ = nullptr, int n_top = 16, size_t ws_bytes = 64 * MB, int d_ = 16, int l_ = 32, int l_sel_ = 64) {
+        return sel_step_fn(Q, Kc_ ? Kc_ : Kcmp, kv.K_sel, kv.V_sel, csc_ptr, csc_rows, csc_vals, ranges, O, 1, L.G, L.h, D, D, (t + 1 - l_) / d_ + 1, S_sel_max, t + 1,
+                           l_, d_, l_sel_, n_top, t, ccb, ccg, D, csb, csg, D, csb, csg, D, dt, 0.f, ws, ws_bytes, nullptr);
     };
     run_step("sel_decode_step/t100", [&] { return sel_step(100); });
     run_step("sel_decode_step/t5_no_compressed_token", [&] { return sel_step(5); });
@@ -482,6 +645,21 @@ int main(int argc, char **argv) {
         run_step(("layer_decode_step/t100_DECODE_BAND_" + std::to_string(band)).c_str(), [&] { return decode(100); });
     }
     set_tuning("DECODE_BAND", -1);
+    // the step's separate launches (DECODE_STEP 0): scores + top-n in one launch, or the three-kernel scorer and the select kernel
+    // (DECODE_UNFUSED 1), then the attention; a block geometry other than l = 2d, l' = 4d leaves the closed-form stencil
+    set_tuning("DECODE_STEP", 0);
+    for (int unfused : {-1, 1}) {
+        set_tuning("DECODE_UNFUSED", unfused);
+        const std::string at = std::string("sel_decode_step/t100_DECODE_STEP_0") + (unfused > 0 ? "_DECODE_UNFUSED_1" : "");
+        const std::vector<Want> blocks = {want<nsa::DecodeParams>("decode_score_select", "DecodeParams"), want<nsa::SelectParams>("decode_score_select", "SelectParams", 1),
+                                          want<int>("decode_score_select", "cand", 2), want<int>("decode_score_select", "t_token", 3),
+                                          want<nsa::DecodeParams>("decode_logits", "DecodeParams"), want<nsa::DecodeParams>("decode_pgrp", "DecodeParams"),
+                                          want<nsa::SelectParams>("select_topn", "SelectParams")};
+        run_args(at, [&] { return sel_step(100); }, blocks);
+        run_args(at + "_geometry_16_16_32", [&] { return sel_step(100, nullptr, 16, 64 * MB, 16, 16, 32); }, blocks);
+    }
+    set_tuning("DECODE_UNFUSED", -1);
+    set_tuning("DECODE_STEP", 1);
     L.Dk = L.Dv = 128;
     run_step("layer_decode_rows/D128_t100_S4", [&] { return layer_rows(100, 4); });
     printf("\n}\n");

@@ -47,15 +47,6 @@ __device__ __forceinline__ void raw8(const u32x4 &raw, float (&out)[8]) {
     for (int j = 0; j < 8; ++j) out[j] = Elt<T>::to_f(e[j]);
 }
 
-// the element type of a runtime dtype, once: f(T{}) with T = float (F32: where the kernel has an fp32 form), __bf16 or _Float16
-template <bool F32 = true, typename F>
-static inline void with_elt(int dtype, F &&f) {
-    if constexpr (F32)
-        if (dtype == NSA_DT_F32) return f(float{});
-    if (dtype == NSA_DT_BF16) return f(__bf16{});
-    return f(_Float16{});
-}
-
 // RMSNorm's rsqrt(mean(x^2) + eps) from a lane's partial sum of rnd(x^2), with the rounding points of the eager chain
 // (llama_block_nsa.py:16-19)
 template <typename T>

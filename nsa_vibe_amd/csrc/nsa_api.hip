@@ -425,32 +425,23 @@ int nsa_map_pcmp_to_pgrp(const float *p_cmp, int64_t R, int h, int S_cmp_cur, co
     return launch_map_pcmp(p_cmp, R, h, S_cmp_cur, csc_ptr, csc_rows, csc_vals, S_sel, p_slc, p_grp, (hipStream_t)stream);
 }
 
+// (the scorers hand a NaN scale on, the attention fills replace it)
+static float scorer_scale(float scale, int Dk) { return scale <= 0.f ? default_scale(0.f, Dk) : scale; }
+
 int nsa_pcmp_all(const void *Q, const void *K_cmp, float *p_cmp, int B, int S, int G, int h, int Dk, int S_cmp,
                  int64_t csb, int64_t csg, int64_t css, int dtype, float scale, void *stream) {
     NSA_CHECK_ARG(dtype_ok(dtype), "pcmp_all: unknown dtype %d", dtype);
     NSA_CHECK_ARG(B >= 0 && S >= 0 && G >= 1, "pcmp_all: bad sizes");
-    if (scale <= 0.f) scale = default_scale(0.f, Dk);  // (the scorers hand a NaN on, the attention fills replace it)
-    return launch_pcmp(Q, K_cmp, p_cmp, 0, (int64_t)B * S * G, S, G, h, Dk, S_cmp, csb, csg, css, dtype, scale,
-                       (hipStream_t)stream);
-}
-
-// route of nsa_sel_scores for (shape, dtype, geometry, variant): 1 generic, 2 MFMA (prefill), 3 decode-shaped.  norm = 1 (decode-normalised rows
-// of an extend): the decode-shaped pair only for chunks of fewer than 64 rows, so that chunks whose boundaries are multiples of 64 all take
-// the same (prefill) route and a row's scores do not depend on the chunk it sits in
-static int scores_route(int B, int S, int G, int h, int Dk, int S_cmp, int S_sel, int l, int d, int l_sel, int dtype, int variant,
-                        int norm) {
-    const int64_t R = (int64_t)B * S * G;
-    if (variant != 0) return variant;
-    const bool mfma = scores_mfma_supported(dtype, h, Dk, l, d, l_sel) && S_cmp >= 1 && R > 0 && S_sel > 0 && (int64_t)B * G <= 65535;
-    if (R > 0 && S_cmp >= 1 && S_sel > 0 && R <= DECODE_MAX_ROWS && h <= 64 && (size_t)h * Dk * 4 <= 64 * 1024 && !(norm && S >= 64)) return 3;
-    if (mfma) return 2;
-    return 1;
+    ScoresCall c{};  // all rows in one chunk, written to p_cmp; normalised over all S_cmp columns
+    c.Q = Q; c.K_cmp = K_cmp; c.B = B; c.S = S; c.G = G; c.h = h; c.Dk = Dk; c.S_cmp = S_cmp; c.csb = csb; c.csg = csg; c.css = css;
+    c.l = 1; c.d = 1; c.dtype = dtype; c.scale = scorer_scale(scale, Dk); c.ws = p_cmp; c.st = (hipStream_t)stream;
+    return launch_pcmp(c, 0, c.rows());
 }
 
 size_t nsa_sel_scores_rows_workspace(int B, int S, int G, int h, int Dk, int S_cmp, int S_sel, int l, int d, int l_sel, int dtype,
                                      int variant, int norm) {
     const int64_t R = (int64_t)B * S * G;
-    switch (scores_route(B, S, G, h, Dk, S_cmp, S_sel, l, d, l_sel, dtype, variant, norm)) {
+    switch (scores_route(scores_shape_call(B, S, G, h, Dk, S_cmp, S_sel, l, d, l_sel, dtype, norm), variant).route) {
         case 2: return 0;
         case 3: return decode_scores_workspace(R, h, S_cmp);
         default: return S_cmp > 0 ? scores_workspace(R, h, S_cmp) : 0;
@@ -466,79 +457,37 @@ int nsa_sel_scores_rows(const void *Q, const void *K_cmp, float *p_grp, int B, i
                         int64_t csb, int64_t csg, int64_t css, const int32_t *csc_ptr, const int32_t *csc_rows,
                         const float *csc_vals, int S_sel, int l, int d, int l_sel, int causal_skip, int variant, int dtype,
                         float scale, int q0, int norm, void *workspace, size_t workspace_bytes, void *stream) {
-    NSA_CHECK_ARG(dtype_ok(dtype), "sel_scores: unknown dtype %d", dtype);
-    NSA_CHECK_ARG(B >= 0 && S >= 0 && G >= 1 && h >= 1, "sel_scores: bad sizes");
-    NSA_CHECK_ARG(variant >= 0 && variant <= 3, "sel_scores: unknown variant %d", variant);
-    NSA_CHECK_ARG(q0 >= 0 && (norm == 0 || norm == 1), "sel_scores: bad q0 / norm");
-    NSA_CHECK_ARG(norm == 0 || (l >= 1 && d >= 1), "sel_scores: norm = 1 needs the block geometry l, d");
-    if (scale <= 0.f) scale = default_scale(0.f, Dk);  // (the scorers hand a NaN on, the attention fills replace it)
-    const int route = scores_route(B, S, G, h, Dk, S_cmp, S_sel, l, d, l_sel, dtype, variant, norm);
-    if (route == 3 && S_cmp >= 1 && (int64_t)B * S * G > 0 && S_sel > 0)
-        return launch_decode_scores(Q, K_cmp, p_grp, B, S, G, h, Dk, S_cmp, csb, csg, css, csc_ptr, csc_rows, csc_vals, S_sel, dtype,
-                                    scale, workspace, workspace_bytes, (hipStream_t)stream, q0, norm, l, d);
-    if (route == 2) {
-        const bool ok = scores_mfma_supported(dtype, h, Dk, l, d, l_sel) && S_cmp >= 1 && (int64_t)B * S * G > 0 && S_sel > 0 &&
-                        csb % 8 == 0 && csg % 8 == 0 && css % 8 == 0 && ((uintptr_t)Q % 16 == 0) && ((uintptr_t)K_cmp % 16 == 0) &&
-                        (int64_t)B * G <= 65535;
-        NSA_CHECK_ARG(ok, "sel_scores: MFMA route needs bf16/f16, Dk in {64,128}, h <= 16, l = 2d, l' = 4d and 16-byte aligned rows "
-                          "(pass variant 1 for the generic route)");
-        return launch_sel_scores_mfma(Q, K_cmp, p_grp, B, S, G, h, Dk, S_cmp, csb, csg, css, S_sel, d, dtype, scale, causal_skip,
-                                      (hipStream_t)stream, nullptr, nullptr, q0, norm, l);
-    }
-    return launch_sel_scores(Q, K_cmp, p_grp, B, S, G, h, Dk, S_cmp, csb, csg, css, csc_ptr, csc_rows, csc_vals, S_sel,
-                             dtype, scale, workspace, workspace_bytes, (hipStream_t)stream, q0, norm, l, d);
+    return sel_scores_impl(ScoresCall{Q, K_cmp, p_grp, csc_ptr, csc_rows, csc_vals, B, S, G, h, Dk, S_cmp, S_sel, csb, csg, css, l, d, l_sel, causal_skip,
+                                      dtype, scale, q0, norm, workspace, workspace_bytes, (hipStream_t)stream},
+                           variant);
 }
 
 int nsa_sel_scores(const void *Q, const void *K_cmp, float *p_grp, int B, int S, int G, int h, int Dk, int S_cmp,
                    int64_t csb, int64_t csg, int64_t css, const int32_t *csc_ptr, const int32_t *csc_rows,
                    const float *csc_vals, int S_sel, int l, int d, int l_sel, int causal_skip, int variant, int dtype,
                    float scale, void *workspace, size_t workspace_bytes, void *stream) {
-    return nsa_sel_scores_rows(Q, K_cmp, p_grp, B, S, G, h, Dk, S_cmp, csb, csg, css, csc_ptr, csc_rows, csc_vals, S_sel, l, d, l_sel,
-                               causal_skip, variant, dtype, scale, 0, 0, workspace, workspace_bytes, stream);
+    return sel_scores_impl(ScoresCall{Q, K_cmp, p_grp, csc_ptr, csc_rows, csc_vals, B, S, G, h, Dk, S_cmp, S_sel, csb, csg, css, l, d, l_sel, causal_skip,
+                                      dtype, scale, 0, 0, workspace, workspace_bytes, (hipStream_t)stream},
+                           variant);
 }
 
-// scores + top-n ranges of every row (prefill): on the 32x32x16 scorer route the selection of a query tile runs inside the scorer launch,
-// everywhere else the scorer and the select kernel are launched back to back -- the same ranges bit for bit either way
 int nsa_sel_scores_select_rows(const void *Q, const void *K_cmp, float *p_grp, int B, int S, int G, int h, int Dk, int S_cmp, int64_t csb,
                                int64_t csg, int64_t css, const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel, int l,
                                int d, int l_sel, int causal_skip, int dtype, float scale, int t0, int n_top, int force_init, int force_local,
                                int mode, int S_total, int32_t *ranges_out, int out_width, int q0, int norm, void *workspace,
                                size_t workspace_bytes, void *stream) {
-    NSA_CHECK_ARG(dtype_ok(dtype), "sel_scores_select: unknown dtype %d", dtype);
-    NSA_CHECK_ARG(B >= 0 && S >= 0 && G >= 1 && h >= 1 && out_width >= 0, "sel_scores_select: bad sizes");
-    NSA_CHECK_ARG(q0 >= 0 && (norm == 0 || norm == 1), "sel_scores_select: bad q0 / norm");
-    const int64_t R = (int64_t)B * S * G;
-    if (R == 0 || out_width == 0) return NSA_OK;
-    NSA_CHECK_ARG(p_grp && ranges_out, "sel_scores_select: null pointer");
-    if (scale <= 0.f) scale = default_scale(0.f, Dk);  // (the scorers hand a NaN on, the attention fills replace it)
-    const int route = scores_route(B, S, G, h, Dk, S_cmp, S_sel, l, d, l_sel, dtype, 0, norm);
-    const bool mfma_ok = route == 2 && S_cmp >= 1 && S_sel > 0 && csb % 8 == 0 && csg % 8 == 0 && css % 8 == 0 && ((uintptr_t)Q % 16 == 0) &&
-                         ((uintptr_t)K_cmp % 16 == 0) && (int64_t)B * G <= 65535;
-    if (mfma_ok) {
-        SelectParams SP{};
-        SP.p_grp = p_grp; SP.t_rows = nullptr; SP.out = ranges_out; SP.R = R; SP.S = S; SP.G = G; SP.t0 = t0;
-        if (int rc = select_params_fill(&SP, S_sel, l_sel, n_top, force_init, force_local, mode, S_total, out_width)) return rc;
-        int done = 0;
-        if (int rc = launch_sel_scores_mfma(Q, K_cmp, p_grp, B, S, G, h, Dk, S_cmp, csb, csg, css, S_sel, d, dtype, scale, causal_skip,
-                                            (hipStream_t)stream, &SP, &done, q0, norm, l))
-            return rc;
-        if (done) return NSA_OK;
-    } else if (int rc = nsa_sel_scores_rows(Q, K_cmp, p_grp, B, S, G, h, Dk, S_cmp, csb, csg, css, csc_ptr, csc_rows, csc_vals, S_sel, l, d,
-                                            l_sel, causal_skip, route == 2 ? 1 : route /* rows the MFMA route cannot take: the generic one */,
-                                            dtype, scale, q0, norm, workspace, workspace_bytes, stream)) {
-        return rc;
-    }
-    return nsa_select_topn_ranges(p_grp, R, S, G, t0, nullptr, S_sel, l_sel, n_top, force_init, force_local, mode, S_total, ranges_out,
-                                  out_width, stream);
+    return sel_scores_select_impl(ScoresCall{Q, K_cmp, p_grp, csc_ptr, csc_rows, csc_vals, B, S, G, h, Dk, S_cmp, S_sel, csb, csg, css, l, d, l_sel,
+                                             causal_skip, dtype, scale, q0, norm, workspace, workspace_bytes, (hipStream_t)stream},
+                                  SelectCall{t0, nullptr, n_top, force_init, force_local, mode, S_total, ranges_out, out_width});
 }
 
 int nsa_sel_scores_select(const void *Q, const void *K_cmp, float *p_grp, int B, int S, int G, int h, int Dk, int S_cmp, int64_t csb, int64_t csg,
                           int64_t css, const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel, int l, int d,
                           int l_sel, int causal_skip, int dtype, float scale, int t0, int n_top, int force_init, int force_local, int mode,
                           int S_total, int32_t *ranges_out, int out_width, void *workspace, size_t workspace_bytes, void *stream) {
-    return nsa_sel_scores_select_rows(Q, K_cmp, p_grp, B, S, G, h, Dk, S_cmp, csb, csg, css, csc_ptr, csc_rows, csc_vals, S_sel, l, d, l_sel,
-                                      causal_skip, dtype, scale, t0, n_top, force_init, force_local, mode, S_total, ranges_out, out_width, 0, 0,
-                                      workspace, workspace_bytes, stream);
+    return sel_scores_select_impl(ScoresCall{Q, K_cmp, p_grp, csc_ptr, csc_rows, csc_vals, B, S, G, h, Dk, S_cmp, S_sel, csb, csg, css, l, d, l_sel,
+                                             causal_skip, dtype, scale, 0, 0, workspace, workspace_bytes, (hipStream_t)stream},
+                                  SelectCall{t0, nullptr, n_top, force_init, force_local, mode, S_total, ranges_out, out_width});
 }
 
 // ------------------------------------------------------------------------------ selection
@@ -549,9 +498,8 @@ int nsa_batched_ranges_width(int S, int S_sel, int l_sel, int n_top, int force_i
 int nsa_select_topn_ranges(const float *p_grp, int64_t R, int S, int G, int t0, const int32_t *t_rows, int S_sel,
                            int l_sel, int n_top, int force_init, int force_local, int mode, int S_total,
                            int32_t *ranges_out, int out_width, void *stream) {
-    NSA_CHECK_ARG(p_grp && ranges_out || R == 0, "select_topn_ranges: null pointer");
-    return launch_select_topn(p_grp, R, S, G, t0, t_rows, S_sel, l_sel, n_top, force_init, force_local, mode, S_total,
-                              ranges_out, out_width, (hipStream_t)stream);
+    return select_topn_impl(p_grp, R, S, G, S_sel, l_sel, SelectCall{t0, t_rows, n_top, force_init, force_local, mode, S_total, ranges_out, out_width},
+                            (hipStream_t)stream);
 }
 
 int nsa_sel_select_attn_fwd(const float *p_grp, int t0, const int32_t *t_rows, int S_sel, int l_sel, int n_top, int force_init,
@@ -574,17 +522,15 @@ int nsa_sel_select_attn_fwd(const float *p_grp, int t0, const int32_t *t_rows, i
     // (never fused where the attention would split the keys over two XCD groups: that form takes its ranges from memory, and both ways of
     // calling must give the same bits)
     const bool fuse = tuning(TUNE_SEL_FUSE) > 0 && sel_attn_ksplit_workspace(dtype, h, Dk, Dv, S, S_kv, out_width, R) == 0;
+    const SelectCall sel{t0, t_rows, n_top, force_init, force_local, mode, S_total, ranges_out, out_width};
     if (!fast_ok || !fuse) {  // two launches
-        if (int rc = nsa_select_topn_ranges(p_grp, R, S, G, t0, t_rows, S_sel, l_sel, n_top, force_init, force_local, mode, S_total, ranges_out,
-                                            out_width, stream))
-            return rc;
+        if (int rc = select_topn_impl(p_grp, R, S, G, S_sel, l_sel, sel, (hipStream_t)stream)) return rc;
         return nsa_sel_attn_fwd(Q, K, V, ranges_out, O, lse, B, S, G, h, Dk, Dv, S_kv, out_width, ksb, ksg, kss, vsb, vsg, vss, dtype, scale, 0,
                                 workspace, workspace_bytes, stream);
     }
     NSA_CHECK_ARG(Q && K && V && O, "sel_select_attn_fwd: null pointer");
     SelectParams SP{};
-    SP.p_grp = p_grp; SP.t_rows = t_rows; SP.out = ranges_out; SP.R = R; SP.S = S; SP.G = G; SP.t0 = t0;
-    if (int rc = select_params_fill(&SP, S_sel, l_sel, n_top, force_init, force_local, mode, S_total, out_width)) return rc;
+    if (int rc = select_params_fill(&SP, p_grp, R, S, G, S_sel, l_sel, sel)) return rc;
     SelAttnParams P = sel_attn_params(Q, K, V, ranges_out, O, lse, R, S, G, h, Dk, Dv, S_kv, out_width, ksb, ksg, kss, vsb, vsg, vss, scale);
     P.nsplit = 1;
     P.fuse_select = 1;
@@ -627,6 +573,68 @@ size_t nsa_sel_decode_rows_workspace(int B, int S, int G, int h, int Dk, int Dv,
 
 }  // extern "C"
 
+// ---- the scorer and selector family on its argument blocks (what the entry points above fill)
+ScoresRoute nsa::scores_route(const ScoresCall &c, int variant) {
+    const int64_t R = c.rows();
+    const bool some = R > 0 && c.S_cmp >= 1 && c.S_sel > 0;  // something to score
+    const bool tiled = some && scores_mfma_supported(c) && (int64_t)c.B * c.G <= 65535;
+    ScoresRoute r;
+    r.decode_fits = c.h <= 64 && (size_t)c.h * c.Dk * 4 <= 64 * 1024;
+    r.route = variant != 0 ? variant : some && R <= DECODE_MAX_ROWS && r.decode_fits && !(c.norm && c.S >= 64) ? 3 : tiled ? 2 : 1;
+    const bool logits_mfma = (c.dtype == NSA_DT_BF16 || c.dtype == NSA_DT_F16) && (c.Dk == 64 || c.Dk == 128) && c.h <= 16;
+    r.mfma = (r.route == 3 ? logits_mfma : tiled) && kcmp_aligned(c.Q, c.K_cmp, c.csb, c.csg, c.css);
+    return r;
+}
+
+int nsa::sel_scores_impl(ScoresCall c, int variant) {
+    NSA_CHECK_ARG(dtype_ok(c.dtype), "sel_scores: unknown dtype %d", c.dtype);
+    NSA_CHECK_ARG(c.B >= 0 && c.S >= 0 && c.G >= 1 && c.h >= 1, "sel_scores: bad sizes");
+    NSA_CHECK_ARG(variant >= 0 && variant <= 3, "sel_scores: unknown variant %d", variant);
+    NSA_CHECK_ARG(c.q0 >= 0 && (c.norm == 0 || c.norm == 1), "sel_scores: bad q0 / norm");
+    NSA_CHECK_ARG(c.norm == 0 || (c.l >= 1 && c.d >= 1), "sel_scores: norm = 1 needs the block geometry l, d");
+    c.scale = scorer_scale(c.scale, c.Dk);
+    const ScoresRoute r = scores_route(c, variant);
+    if (r.route == 3 && c.S_cmp >= 1 && c.rows() > 0 && c.S_sel > 0) return launch_decode_scores(c);
+    if (r.route == 2) {
+        NSA_CHECK_ARG(r.mfma, "sel_scores: MFMA route needs bf16/f16, Dk in {64,128}, h <= 16, l = 2d, l' = 4d and 16-byte aligned rows "
+                              "(pass variant 1 for the generic route)");
+        return launch_sel_scores_mfma(c, nullptr, nullptr);
+    }
+    return launch_sel_scores(c);
+}
+
+int nsa::select_topn_impl(const float *p_grp, int64_t R, int S, int G, int S_sel, int l_sel, const SelectCall &s, hipStream_t st) {
+    NSA_CHECK_ARG(p_grp && s.ranges_out || R == 0, "select_topn_ranges: null pointer");
+    NSA_CHECK_ARG(R >= 0 && S >= 1 && G >= 1 && S_sel >= 1 && l_sel >= 1 && s.n_top >= 0, "select: bad sizes");
+    NSA_CHECK_ARG(S_sel <= 64 * 64, "select: S_sel=%d exceeds 4096 selection blocks", S_sel);
+    NSA_CHECK_ARG(s.force_local >= 0 && s.force_local <= 30, "select: force_local out of range");
+    SelectParams P{};
+    if (int rc = select_params_fill(&P, p_grp, R, S, G, S_sel, l_sel, s)) return rc;
+    return launch_select_topn(P, st);
+}
+
+// scores + top-n ranges of every row (prefill): on the 32x32x16 scorer route the selection of a query tile runs inside the scorer launch,
+// everywhere else the scorer and the select kernel are launched back to back -- the same ranges bit for bit either way
+int nsa::sel_scores_select_impl(ScoresCall c, const SelectCall &s) {
+    NSA_CHECK_ARG(dtype_ok(c.dtype), "sel_scores_select: unknown dtype %d", c.dtype);
+    NSA_CHECK_ARG(c.B >= 0 && c.S >= 0 && c.G >= 1 && c.h >= 1 && s.out_width >= 0, "sel_scores_select: bad sizes");
+    NSA_CHECK_ARG(c.q0 >= 0 && (c.norm == 0 || c.norm == 1), "sel_scores_select: bad q0 / norm");
+    const int64_t R = c.rows();
+    if (R == 0 || s.out_width == 0) return NSA_OK;
+    NSA_CHECK_ARG(c.p_grp && s.ranges_out, "sel_scores_select: null pointer");
+    c.scale = scorer_scale(c.scale, c.Dk);
+    const ScoresRoute r = scores_route(c, 0);
+    if (r.route == 2 && r.mfma) {
+        SelectParams SP{};
+        if (int rc = select_params_fill(&SP, c.p_grp, R, c.S, c.G, c.S_sel, c.l_sel, s)) return rc;
+        int done = 0;
+        if (int rc = launch_sel_scores_mfma(c, &SP, &done)) return rc;
+        return done ? NSA_OK : launch_select_topn(SP, c.st);
+    }
+    if (int rc = sel_scores_impl(c, r.route == 2 ? 1 : r.route /* rows the MFMA route cannot take: the generic one */)) return rc;
+    return select_topn_impl(c.p_grp, R, c.S, c.G, c.S_sel, c.l_sel, s, c.st);
+}
+
 int nsa::sel_decode_step_impl(const SelDecodeCall &c, void *workspace, size_t workspace_bytes, void *stream, int defer, int *ns_used,
                               float **part_used, const DecBandPair *band, int *band_taken) {
     if (band_taken) *band_taken = 0;
@@ -642,19 +650,14 @@ int nsa::sel_decode_step_impl(const SelDecodeCall &c, void *workspace, size_t wo
         if (band && band_taken) *band_taken = 1;
         return launch_decode_step(c, w, a, (hipStream_t)stream, band_taken ? band : nullptr);
     }
-    if (decode_score_select_supported(c.dtype, c.h, c.Dk, c.S_cmp, c.S_sel, c.kcb, c.kcg, c.kcs, c.Q, c.K_cmp, c.rows())) {
+    const ScoresCall sc = scores_call(c, p_grp, 1, 0, w, a, stream);  // the step's one row per (b, g), scored over all S_cmp columns
+    const SelectCall sel = decode_select_call(c);
+    if (decode_score_select_supported(sc)) {
         // scores -> statistics -> Eq.9/10 -> sequential top-n in one launch (bit-identical to the route below)
-        if (int rc = launch_decode_score_select(c.Q, c.K_cmp, c.B, c.G, c.h, c.Dk, c.S_cmp, c.kcb, c.kcg, c.kcs, c.csc_ptr, c.csc_rows, c.csc_vals,
-                                                c.S_sel, c.l_sel, c.n_top, c.t0, c.dtype, default_scale(c.scale, c.Dk), c.ranges_out,
-                                                (hipStream_t)stream, nullptr, stencil))
-            return rc;
+        if (int rc = launch_decode_score_select(sc, sel, stencil)) return rc;
     } else {
-        if (int rc = nsa_sel_scores(c.Q, c.K_cmp, p_grp, c.B, 1, c.G, c.h, c.Dk, c.S_cmp, c.kcb, c.kcg, c.kcs, c.csc_ptr, c.csc_rows, c.csc_vals, c.S_sel,
-                                    c.l, c.d, c.l_sel, 1, c.S_cmp >= 1 ? 3 : 1, c.dtype, c.scale, w, a, stream))
-            return rc;
-        if (int rc = nsa_select_topn_ranges(p_grp, c.rows(), 1, c.G, c.t0, nullptr, c.S_sel, c.l_sel, c.n_top, 1, 2, NSA_SEL_SEQUENTIAL, 1,
-                                            c.ranges_out, c.n_top, stream))
-            return rc;
+        if (int rc = sel_scores_impl(sc, c.S_cmp >= 1 ? 3 : 1)) return rc;
+        if (int rc = select_topn_impl(p_grp, c.rows(), 1, c.G, c.S_sel, c.l_sel, sel, sc.st)) return rc;
     }
     if (part_used) *part_used = (float *)(w + a + p);
     return sel_attn_fwd_impl(c.Q, c.K, c.V, c.ranges_out, c.O, nullptr, c.B, 1, c.G, c.h, c.Dk, c.Dv, c.S_kv, c.n_top, c.ksb, c.ksg, c.kss, c.vsb,
@@ -674,9 +677,8 @@ int nsa::sel_decode_rows_impl(const SelDecodeCall &c, void *workspace, size_t wo
     const SelDecodeRowsWs W(c.B, c.S, c.G, c.h, c.Dk, c.Dv, c.S_cmp, c.S_sel, c.n_top, c.dtype);
     NSA_CHECK_ARG(workspace && ((uintptr_t)workspace % 16 == 0) && workspace_bytes >= W.total(), "decode_rows: workspace missing, misaligned or too small");
     unsigned char *w = (unsigned char *)workspace;
-    if (int rc = nsa_sel_scores_select_rows(c.Q, c.K_cmp, (float *)(w + W.a), c.B, c.S, c.G, c.h, c.Dk, c.S_cmp, c.kcb, c.kcg, c.kcs, c.csc_ptr, c.csc_rows,
-                                            c.csc_vals, c.S_sel, c.l, c.d, c.l_sel, 2 /* skipped blocks stay unwritten: only the selector reads p_grp */,
-                                            c.dtype, c.scale, c.t0, c.n_top, 1, 2, NSA_SEL_SEQUENTIAL, c.S, c.ranges_out, c.n_top, c.t0, 1, w, W.a, stream))
+    if (int rc = sel_scores_select_impl(scores_call(c, (float *)(w + W.a), 2 /* skipped blocks stay unwritten: only the selector reads p_grp */, 1, w, W.a, stream),
+                                        decode_select_call(c)))
         return rc;
     return nsa_sel_attn_fwd(c.Q, c.K, c.V, c.ranges_out, c.O, nullptr, c.B, c.S, c.G, c.h, c.Dk, c.Dv, c.S_kv, c.n_top, c.ksb, c.ksg, c.kss, c.vsb, c.vsg,
                             c.vss, c.dtype, c.scale, 0, w + W.a + W.p, workspace_bytes - W.a - W.p, stream);
@@ -717,7 +719,7 @@ int nsa_sel_decode_step_plan(int B, int G, int h, int Dk, int Dv, int S_cmp, int
     }
     // the route of sel_decode_step_impl for a declined shape, by the shape parts of the predicates it asks: scores + top-n in one launch or
     // three, then the attention (its decode form is one launch; the prefill kernel with the keys split adds a combine launch)
-    int n = decode_score_select_shape_ok(dtype, h, Dk, S_cmp, S_sel, R) ? 1 : 3;
+    int n = decode_score_select_shape_ok(scores_shape_call(B, 1, G, h, Dk, S_cmp, S_sel, 32, 16, 64, dtype, 0)) ? 1 : 3;
     if (sel_attn_decode_wg_shape_ok(dtype, h, Dk, Dv, n_top) && (int64_t)S_kv * 2 * Dv < ((int64_t)1 << 31)) {
         n += 1;
     } else {
@@ -742,7 +744,7 @@ int nsa_sel_decode_rows_plan(int B, int S, int G, int h, int Dk, int Dv, int S_c
     }
     // separate launches: the scorer (the decode-shaped pair, or one launch of the tiled / generic scorer), the select kernel, the attention
     // (a combine launch more where it splits the keys): an estimate, only "> 1" is contractual
-    const int route = scores_route(B, S, G, h, Dk, S_cmp, S_sel, 32, 16, 64, dtype, 0, 1);
+    const int route = scores_route(scores_shape_call(B, S, G, h, Dk, S_cmp, S_sel, 32, 16, 64, dtype, 1), 0).route;
     *launches = (route == 3 ? 2 : 1) + 1 + 1;
     return NSA_OK;
 }

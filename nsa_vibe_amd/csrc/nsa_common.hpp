@@ -131,6 +131,16 @@ struct Elt<_Float16> {
     __device__ static _Float16 from_f(float x) { return (_Float16)x; }
 };
 
+// the element type of a runtime dtype, once (host): f(T{}) with T = float (F32: where the kernel has an fp32 form), __bf16 or _Float16.
+// The entry points refuse an unknown dtype (dtype_ok) before any launcher runs.
+template <bool F32 = true, typename F>
+static inline void with_elt(int dtype, F &&f) {
+    if constexpr (F32)
+        if (dtype == NSA_DT_F32) return f(float{});
+    if (dtype == NSA_DT_BF16) return f(__bf16{});
+    return f(_Float16{});
+}
+
 // ---- wave helpers ----------------------------------------------------------------------
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 __device__ __forceinline__ int uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }

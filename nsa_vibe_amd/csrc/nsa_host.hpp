@@ -7,6 +7,7 @@
 #include "nsa_common.hpp"
 #include "layer_fused.hpp"
 #include "sel_attn_params.hpp"
+#include "sel_scores_params.hpp"
 
 namespace nsa {
 
@@ -28,6 +29,11 @@ inline bool qkv_aligned(const void *Q, const void *K, const void *V, int64_t ksb
                         int64_t vss) {
     return kss % 8 == 0 && vss % 8 == 0 && ksb % 8 == 0 && vsb % 8 == 0 && ksg % 8 == 0 && vsg % 8 == 0 && ((uintptr_t)Q % 16 == 0) &&
            ((uintptr_t)K % 16 == 0) && ((uintptr_t)V % 16 == 0);
+}
+
+// what the MFMA scorer kernels ask of their operands: every K_cmp stride a multiple of 8 elements, Q and K_cmp 16-byte aligned
+inline bool kcmp_aligned(const void *Q, const void *Kc, int64_t csb, int64_t csg, int64_t css) {
+    return csb % 8 == 0 && csg % 8 == 0 && css % 8 == 0 && ((uintptr_t)Q % 16 == 0) && ((uintptr_t)Kc % 16 == 0);
 }
 
 // O [R,h,Dv] = 0: the output of rows that select nothing (attention_kernels.py:718-719)
@@ -82,6 +88,46 @@ inline SelDecodeCall sel_decode_plan_call(int B, int S, int G, int h, int Dk, in
     c.l = 32; c.d = 16; c.l_sel = 64; c.t0 = S_kv - S;
     return c;
 }
+
+// What the scorer family (nsa_sel_scores* / nsa_pcmp_all and every launcher below them) passes around: the arguments of the C ABI, once.
+// Rows (b, s, g) at tokens q0 + s; norm = 1: a row normalises over the n_cmp(q0 + s) columns a decode step at its token sees.
+struct ScoresCall {
+    const void *Q, *K_cmp;
+    float *p_grp;
+    const int32_t *csc_ptr, *csc_rows;
+    const float *csc_vals;
+    int B, S, G, h, Dk, S_cmp, S_sel;
+    int64_t csb, csg, css;
+    int l, d, l_sel, causal_skip, dtype;
+    float scale;
+    int q0, norm;
+    void *ws;  // the route's scratch (nsa_sel_scores_rows_workspace); nsa_pcmp_all: p_cmp itself
+    size_t ws_bytes;
+    hipStream_t st;
+    int64_t rows() const { return (int64_t)B * S * G; }
+};
+// the shape alone (workspace and plan queries: no tensors, the route of variant 0 is what they ask)
+inline ScoresCall scores_shape_call(int B, int S, int G, int h, int Dk, int S_cmp, int S_sel, int l, int d, int l_sel, int dtype, int norm) {
+    ScoresCall c{};
+    c.B = B; c.S = S; c.G = G; c.h = h; c.Dk = Dk; c.S_cmp = S_cmp; c.S_sel = S_sel; c.l = l; c.d = d; c.l_sel = l_sel; c.dtype = dtype; c.norm = norm;
+    return c;
+}
+// the scorer's block of a decode-family call: norm = 1 scores its S rows at their own tokens t0 + s, norm = 0 over all S_cmp columns
+inline ScoresCall scores_call(const SelDecodeCall &c, float *p_grp, int causal_skip, int norm, void *ws, size_t ws_bytes, void *stream) {
+    return ScoresCall{c.Q, c.K_cmp, p_grp, c.csc_ptr, c.csc_rows, c.csc_vals, c.B, c.S, c.G, c.h, c.Dk, c.S_cmp, c.S_sel, c.kcb, c.kcg, c.kcs, c.l, c.d, c.l_sel,
+                      causal_skip, c.dtype, c.scale, norm ? c.t0 : 0, norm, ws, ws_bytes, (hipStream_t)stream};
+}
+
+// The top-n selection of a call's rows: row (b, s, g) selects at token t0 + s (or t_rows[row]) into ranges_out [R, out_width, 2].
+struct SelectCall {
+    int t0;
+    const int32_t *t_rows;
+    int n_top, force_init, force_local, mode, S_total;
+    int32_t *ranges_out;
+    int out_width;
+};
+// a decode step's selection: sequential, block 0 and the two newest blocks forced, n_top ranges per row
+inline SelectCall decode_select_call(const SelDecodeCall &c) { return SelectCall{c.t0, nullptr, c.n_top, 1, 2, NSA_SEL_SEQUENTIAL, c.S, c.ranges_out, c.n_top}; }
 
 // RoPE + append of S tokens at position t0 of the caches kv (the backward passes the gradients in the caches' places)
 inline RopeAppendParams rope_append_params(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *proj, void *Q_out, int S, int t0) {

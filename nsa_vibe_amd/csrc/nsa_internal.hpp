@@ -1,5 +1,7 @@
-// Internal forms of a few C-ABI entry points: same arguments plus the split-KV hand-over used by the fused decode step
-// (defer != 0: the partial records stay in the workspace, *ns_used tells how many splits were written; 1 = O is final).
+// Internal forms of the C-ABI entry points and the launchers behind them.  The attention forms take the entry point's arguments plus the
+// split-KV hand-over used by the fused decode step (defer != 0: the partial records stay in the workspace, *ns_used tells how many splits
+// were written; 1 = O is final); the decode-step and the scorer / selector families take their argument blocks (nsa_host.hpp:
+// SelDecodeCall, ScoresCall, SelectCall), filled once by the entry point or built from the block the caller already holds.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -22,13 +24,13 @@ int sel_decode_step_impl(const SelDecodeCall &c, void *workspace, size_t workspa
                          const DecBandPair *band = nullptr, int *band_taken = nullptr);
 int sel_decode_rows_impl(const SelDecodeCall &c, void *workspace, size_t workspace_bytes, void *stream);
 
-bool decode_score_select_supported(int dtype, int h, int Dk, int S_cmp, int S_sel, int64_t csb, int64_t csg, int64_t css, const void *Q,
-                                   const void *Kc, int64_t rows);
-struct DecAttnArgs;  // sel_attn_params.hpp: non-null = the row's selection attention runs in the same launch
-int launch_decode_score_select(const void *Q, const void *Kc, int B, int G, int h, int Dk, int S_cmp, int64_t csb, int64_t csg, int64_t css,
-                               const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel, int l_sel, int n_top,
-                               int t_token, int dtype, float scale, int32_t *ranges_out, hipStream_t st, const DecAttnArgs *attend,
-                               int stencil);
+struct ScoresCall;  // nsa_host.hpp: the arguments of the scorer family (nsa_sel_scores* and every launcher below them)
+struct SelectCall;  // nsa_host.hpp: the top-n selection of a call's rows
+struct SelectParams;  // sel_scores_params.hpp
+// scores + top-n of a decode step's rows in one launch (sel_scores.hip): the shape / tuning part, and with the operands' alignment
+bool decode_score_select_shape_ok(const ScoresCall &c);
+bool decode_score_select_supported(const ScoresCall &c);
+int launch_decode_score_select(const ScoresCall &c, const SelectCall &s, int stencil);
 // the one-launch decode step (sel_decode_fused.hip): default block geometry, bf16 / f16, Dk = Dv = 64 or 128
 bool decode_step_supported(const SelDecodeCall &c);
 size_t decode_step_workspace(int64_t R, int h, int S_cmp);
@@ -39,37 +41,43 @@ bool decode_step_shape_plan(const SelDecodeCall &c, int *form, int *nsplit);
 bool decode_rows_shape_plan(const SelDecodeCall &c, int *form, int *nw_out);
 bool decode_rows_supported(const SelDecodeCall &c);
 int launch_decode_rows(const SelDecodeCall &c, hipStream_t st);
-// shape / tuning part of decode_score_select_supported
-bool decode_score_select_shape_ok(int dtype, int h, int Dk, int S_cmp, int S_sel, int64_t rows);
 
-// ---- launchers the C ABI dispatches to; every translation unit that defines one includes this header, so a definition whose return type or
-// default arguments disagree does not compile (a changed parameter list still declares an overload and fails at link time).
-// The default arguments (q0 / norm / l / d: prefill rows, normalised over all S_cmp columns) live here only.
+// ---- the scorer and selector family behind the C ABI (nsa_api.hip): what nsa_sel_scores[_rows], nsa_sel_scores_select[_rows] and
+// nsa_select_topn_ranges run once their arguments are in the blocks
+int sel_scores_impl(ScoresCall c, int variant);
+int sel_scores_select_impl(ScoresCall c, const SelectCall &s);
+int select_topn_impl(const float *p_grp, int64_t R, int S, int G, int S_sel, int l_sel, const SelectCall &s, hipStream_t st);
+// The scorer's route: 1 generic (pcmp + map), 2 the tiled MFMA scorers, 3 the decode-shaped pair.  `route` rests on the shape, dtype, block
+// geometry, variant and norm alone (what the workspace and plan queries ask: no tensors); `mfma` adds the operands: Q / K_cmp also allow
+// the MFMA kernels of that route (kcmp_aligned; on route 3 the MFMA form of decode_logits).  norm = 1 (decode-normalised rows of an
+// extend): the decode-shaped pair only for chunks of fewer than 64 rows, so that chunks whose boundaries are multiples of 64 all take the
+// same (prefill) route and a row's scores do not depend on the chunk it sits in
+struct ScoresRoute {
+    int route;
+    bool decode_fits;  // the decode-shaped pair holds the h heads' queries in LDS
+    bool mfma;
+};
+ScoresRoute scores_route(const ScoresCall &c, int variant);
+constexpr int64_t DECODE_MAX_ROWS = 1024;  // rows (B*S*G) up to which the decode-shaped scorer is used
+
+// ---- launchers the C ABI dispatches to; every translation unit that defines one includes this header, so a definition whose return type
+// disagrees does not compile (a changed parameter list still declares an overload and fails at link time).
 // sel_select.hip
-int launch_select_topn(const float *p_grp, int64_t R, int S, int G, int t0, const int32_t *t_rows, int S_sel, int l_sel, int n_top,
-                       int force_init, int force_local, int mode, int S_total, int32_t *out, int W, hipStream_t st);
+int launch_select_topn(const SelectParams &P, hipStream_t st);
 int launch_indices_to_ranges(const int32_t *idx, int64_t R, int S, int G, int t0, int K, int S_sel, int l_sel, int32_t *out, hipStream_t st);
 int batched_width(int S, int S_sel, int l_sel, int n_top, int force_init, int force_local);
 // sel_scores.hip
 int launch_map_pcmp(const float *p_cmp, int64_t R, int h, int S_cmp_cur, const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals,
                     int S_sel, float *p_slc, float *p_grp, hipStream_t st);
-int launch_pcmp(const void *Q, const void *Kc, float *p_cmp, int64_t row0, int64_t nrows, int S, int G, int h, int Dk, int S_cmp, int64_t csb,
-                int64_t csg, int64_t css, int dtype, float scale, hipStream_t st, int q0 = 0, int norm = 0, int l = 1, int d = 1);
+int launch_pcmp(const ScoresCall &c, int64_t row0, int64_t nrows);  // rows [row0, row0 + nrows) -> c.ws
 size_t scores_workspace(int64_t R, int h, int S_cmp);
-int launch_sel_scores(const void *Q, const void *Kc, float *p_grp, int B, int S, int G, int h, int Dk, int S_cmp, int64_t csb, int64_t csg,
-                      int64_t css, const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel, int dtype, float scale,
-                      void *ws, size_t ws_bytes, hipStream_t st, int q0 = 0, int norm = 0, int l = 1, int d = 1);
-constexpr int64_t DECODE_MAX_ROWS = 1024;  // rows (B*S*G) up to which the decode-shaped scorer is used
+int launch_sel_scores(const ScoresCall &c);
 size_t decode_scores_workspace(int64_t R, int h, int S_cmp);
-int launch_decode_scores(const void *Q, const void *Kc, float *p_grp, int B, int S, int G, int h, int Dk, int S_cmp, int64_t csb, int64_t csg,
-                         int64_t css, const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel, int dtype, float scale,
-                         void *ws, size_t ws_bytes, hipStream_t st, int q0 = 0, int norm = 0, int l = 1, int d = 1);
+int launch_decode_scores(const ScoresCall &c);
 // sel_scores_mfma.hip
-struct SelectParams;  // sel_select_row.hpp
-bool scores_mfma_supported(int dtype, int h, int Dk, int l, int d, int l_sel);
-int launch_sel_scores_mfma(const void *Q, const void *Kc, float *p_grp, int B, int S, int G, int h, int Dk, int S_cmp, int64_t csb, int64_t csg,
-                           int64_t css, int S_sel, int d_stride, int dtype, float scale, int causal_skip, hipStream_t st, const SelectParams *sel,
-                           int *sel_done, int q0 = 0, int norm = 0, int l = 1);
+bool scores_mfma_supported(const ScoresCall &c);  // bf16 / f16, Dk 64 or 128, h <= 16, the default block geometry l = 2d, l' = 4d
+// sel / sel_done: the caller wants the top-n ranges of every row too; *sel_done says whether the launch produced them
+int launch_sel_scores_mfma(const ScoresCall &c, const SelectParams *sel, int *sel_done);
 // sel_attn_generic.hip
 int launch_sel_first_key(const void *V, const int32_t *ranges, void *O, int64_t R, int S, int G, int h, int Dv, int n, int S_kv, int64_t vsb,
                          int64_t vsg, int64_t vss, int esz, hipStream_t st);

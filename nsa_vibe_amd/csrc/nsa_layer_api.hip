@@ -193,22 +193,18 @@ static int layer_rows(const char *who, const nsa_layer_desc *L, const nsa_kv_des
     const float scale = C.scale;
     // selected branch: scores of rows t0 .. t0 + S - 1 (blocks no selector can read at row t are skipped) -> top-n at their tokens -> the
     // attention over K_sel[:t + 1]
-    const bool aligned = ((uintptr_t)kv->K_cmp % 16 == 0) && C.kcb % 8 == 0 && C.kcg % 8 == 0 && Dk % 8 == 0;
+    // (causal_skip 2: skipped blocks stay unwritten, only the selector reads p_grp)
+    const ScoresCall sc{Q, kv->K_cmp, p_grp, csc_ptr, csc_rows, csc_vals, B, S, G, h, Dk, n1, S_sel, C.kcb, C.kcg, Dk, L->l, L->d, L->l_sel, 2, dt, scale,
+                        t0, norm, ws + W.sc, W.sc_bytes, (hipStream_t)stream};
+    const bool aligned = kcmp_aligned(Q, kv->K_cmp, C.kcb, C.kcg, Dk);
     if (!prefill || (aligned && n1 >= 1 && tuning(TUNE_SEL_FUSE) <= 0)) {
         // scores + top-n in one call (on the 32x32x16 scorer's route one LAUNCH, the selection in the scorer's epilogue), then the attention
-        if (int rc = nsa_sel_scores_select_rows(Q, kv->K_cmp, p_grp, B, S, G, h, Dk, n1, C.kcb, C.kcg, Dk, csc_ptr, csc_rows, csc_vals, S_sel,
-                                                L->l, L->d, L->l_sel, 2 /* skipped blocks stay unwritten: only the selector reads p_grp */, dt,
-                                                scale, t0, L->n_sel, 1, 2, selector, S, ranges_out, out_width, t0, norm, ws + W.sc, W.sc_bytes,
-                                                stream))
-            return rc;
+        if (int rc = sel_scores_select_impl(sc, SelectCall{t0, nullptr, L->n_sel, 1, 2, selector, S, ranges_out, out_width})) return rc;
         if (int rc = nsa_sel_attn_fwd(Q, kv->K_sel, kv->V_sel, ranges_out, Osel, nullptr, B, S, G, h, Dk, Dv, S_kv, out_width, C.ksb, C.ksg, Dk,
                                       C.vsb, C.vsg, Dv, dt, scale, 0, ws + W.att, W.att_bytes, stream))
             return rc;
     } else {  // prefill only: the selector inside the attention launch (SEL_FUSE), an unaligned K_cmp, or no compressed token yet
-        if (int rc = nsa_sel_scores(Q, kv->K_cmp, p_grp, B, S, G, h, Dk, n1, C.kcb, C.kcg, Dk, csc_ptr, csc_rows, csc_vals, S_sel, L->l, L->d,
-                                    L->l_sel, 2 /* skipped blocks stay unwritten: only the selector below reads p_grp */, aligned ? 0 : 1, dt, scale,
-                                    ws + W.sc, W.sc_bytes, stream))
-            return rc;
+        if (int rc = sel_scores_impl(sc, aligned ? 0 : 1)) return rc;
         if (int rc = nsa_sel_select_attn_fwd(p_grp, 0, nullptr, S_sel, L->l_sel, L->n_sel, 1, 2, selector, S, ranges_out, out_width, Q, kv->K_sel,
                                              kv->V_sel, Osel, nullptr, B, S, G, h, Dk, Dv, S, C.ksb, C.ksg, Dk, C.vsb, C.vsg, Dv, dt, scale,
                                              ws + W.att, W.att_bytes, stream))

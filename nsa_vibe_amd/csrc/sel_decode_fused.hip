@@ -873,8 +873,7 @@ struct DecStepBlocks {
     DecAttnArgs AT;
 };
 static int dstep_blocks(const SelDecodeCall &c, float c2, DecStepBlocks *b) {
-    if (int rc = select_params_sequential(&b->SP, c.S_sel, 64, c.n_top, 1, 2, c.n_top)) return rc;
-    b->SP.out = c.ranges_out; b->SP.R = c.rows(); b->SP.S = c.S; b->SP.G = c.G; b->SP.t0 = c.t0;
+    if (int rc = select_params_fill(&b->SP, nullptr, c.rows(), c.S, c.G, c.S_sel, 64, decode_select_call(c))) return rc;
     const int n = (c.S_sel + 63) / 64;
     b->cand = n <= 1 ? 1 : n <= 2 ? 2 : n <= 4 ? 4 : n <= 8 ? 8 : n <= 16 ? 16 : 32;
     b->AT = DecAttnArgs{c.Q, c.K, c.V, c.O, c.G, c.h, c.S_kv, c.n_top, c.ksb, c.ksg, c.kss, c.vsb, c.vsg, c.vss, c2};

@@ -7,13 +7,13 @@
 // CPU result bit for bit -- per (row, head, selection block) it accumulates p_cmp[r]*w over the CSC
 // list in ascending compressed row r, product and sum rounded separately (the order in which the
 // CPU scatter_add visits the COO entries), then sums the heads in ascending h.
-#include <type_traits>
-
 #include <stdlib.h>
 
 #include "nsa_common.hpp"
+#include "attn_mfma_tiles.hpp"
 #include "sel_attn_decode.hpp"
 #include "sel_select_row.hpp"
+#include "nsa_host.hpp"
 #include "nsa_internal.hpp"
 
 namespace nsa {
@@ -21,15 +21,6 @@ namespace nsa {
 // ---------------------------------------------------------------------------------------
 // Eq.9 + Eq.10.  thread = (row, selection block j); p_cmp [R,h,S_cmp_cur].
 // ---------------------------------------------------------------------------------------
-struct MapParams {
-    const float *p_cmp;
-    const int32_t *csc_ptr, *csc_rows;
-    const float *csc_vals;
-    float *p_slc, *p_grp;
-    int64_t R;
-    int h, S_cmp_cur, S_sel;
-};
-
 __global__ __launch_bounds__(256) void map_pcmp_kernel(MapParams P) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= P.R * P.S_sel) return;
@@ -67,17 +58,6 @@ int launch_map_pcmp(const float *p_cmp, int64_t R, int h, int S_cmp_cur, const i
 // VALU implementation (each lane owns columns lane, lane+64, ...); used by the parity API
 // nsa_pcmp_all and, query-chunked, by the first fused scorer.
 // ---------------------------------------------------------------------------------------
-struct PcmpParams {
-    const void *Q;   // [R,h,Dk]
-    const void *Kc;  // [B,G,S_cmp,Dk] strided
-    float *p_cmp;    // [Rchunk,h,S_cmp]
-    int64_t row0, nrows;  // rows [row0,row0+nrows) of the full R = B*S*G
-    int S, G, h, Dk, S_cmp;
-    int64_t csb, csg, css;
-    float scale;
-    int q0, norm, l, d;  // norm = 1: row (b,s,g) at token q0 + s normalises over its own n_cmp(q0 + s) columns, the rest are written as 0
-};
-
 template <typename T>
 __global__ __launch_bounds__(256) void pcmp_kernel(PcmpParams P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -119,21 +99,14 @@ __global__ __launch_bounds__(256) void pcmp_kernel(PcmpParams P) {
     for (int c = nc + lane; c < P.S_cmp; c += 64) out[c] = 0.f;  // columns not emitted yet at the row's token (the map adds them as +0)
 }
 
-int launch_pcmp(const void *Q, const void *Kc, float *p_cmp, int64_t row0, int64_t nrows, int S, int G, int h,
-                int Dk, int S_cmp, int64_t csb, int64_t csg, int64_t css, int dtype, float scale, hipStream_t st,
-                int q0, int norm, int l, int d) {
-    NSA_CHECK_ARG(h >= 1 && Dk >= 1 && Dk <= 4096, "pcmp: bad h/Dk");
-    if (nrows == 0 || S_cmp == 0) return NSA_OK;
-    PcmpParams P{Q, Kc, p_cmp, row0, nrows, S, G, h, Dk, S_cmp, csb, csg, css, scale, q0, norm, l, d};
-    const int64_t waves = nrows * h;
+int launch_pcmp(const ScoresCall &c, int64_t row0, int64_t nrows) {
+    NSA_CHECK_ARG(c.h >= 1 && c.Dk >= 1 && c.Dk <= 4096, "pcmp: bad h/Dk");
+    if (nrows == 0 || c.S_cmp == 0) return NSA_OK;
+    PcmpParams P{c.Q, c.K_cmp, (float *)c.ws, row0, nrows, c.S, c.G, c.h, c.Dk, c.S_cmp, c.csb, c.csg, c.css, c.scale, c.q0, c.norm, c.l, c.d};
+    const int64_t waves = nrows * c.h;
     const unsigned grid = (unsigned)((waves + 3) / 4);
-    const size_t lds = 4 * sizeof(float) * (size_t)Dk;
-    switch (dtype) {
-        case NSA_DT_F32: hipLaunchKernelGGL(pcmp_kernel<float>, dim3(grid), dim3(256), lds, st, P); break;
-        case NSA_DT_BF16: hipLaunchKernelGGL(pcmp_kernel<__bf16>, dim3(grid), dim3(256), lds, st, P); break;
-        case NSA_DT_F16: hipLaunchKernelGGL(pcmp_kernel<_Float16>, dim3(grid), dim3(256), lds, st, P); break;
-        default: NSA_CHECK_ARG(false, "pcmp: unknown dtype %d", dtype);
-    }
+    const size_t lds = 4 * sizeof(float) * (size_t)c.Dk;
+    with_elt(c.dtype, [&](auto t) { hipLaunchKernelGGL(pcmp_kernel<decltype(t)>, dim3(grid), dim3(256), lds, c.st, P); });
     NSA_LAUNCH_CHECK("pcmp");
     return NSA_OK;
 }
@@ -145,22 +118,6 @@ int launch_pcmp(const void *Q, const void *Kc, float *p_cmp, int64_t row0, int64
 //   kernel 2: workgroup = query row; per-head max / sum, then per selection block the CSC taps are
 //             normalised, weighted and summed over heads (any block geometry) -> p_grp [R,S_sel]
 // ---------------------------------------------------------------------------------------
-struct DecodeParams {
-    const void *Q;   // [R,h,Dk]
-    const void *Kc;  // strided
-    float *x;        // [R,h,S_cmp] logits * scale * log2(e)
-    float *part;     // [R,h,nchunk,2] per 64-row chunk: max, sum exp2(x - max)
-    float *p_grp;    // [R,S_sel]
-    const int32_t *csc_ptr, *csc_rows;
-    const float *csc_vals;
-    int64_t R;
-    int S, G, h, Dk, S_cmp, S_sel;
-    int64_t csb, csg, css;
-    float c2;
-    int stencil;  // fused decode kernel: l = 2d and l' = 4d, Eq.9 is the closed-form 5-tap stencil (no CSC loads)
-    int q0, norm, l, d;  // norm = 1 (two-kernel route only): row (b,s,g) at token q0 + s sees its own n_cmp(q0 + s) columns
-};
-
 // columns row `row` of a decode-shaped launch normalises over (all S_cmp, or its own n_cmp with norm = 1)
 __device__ __forceinline__ int dec_row_cols(const DecodeParams &P, int64_t row) {
     return P.norm ? ncmp_at(P.q0 + (int)((row / P.G) % P.S), P.l, P.d, P.S_cmp) : P.S_cmp;
@@ -237,7 +194,7 @@ __global__ __launch_bounds__(64) void decode_logits_kernel(DecodeParams P) {
 // the h heads the 16 columns; K_cmp fragments are loaded straight into the A-operand layout (one pass, no reuse).
 template <typename T, int KSTEPS>
 __global__ __launch_bounds__(64, 2) void decode_logits_mfma_kernel(DecodeParams P) {
-    typedef typename std::conditional<std::is_same<T, __bf16>::value, bf16x8, f16x8>::type x8;
+    using x8 = typename MfmaT<T>::x8;
     const int lane = threadIdx.x, rho = lane & 15, q = lane >> 4;
     const int64_t row = blockIdx.y;
     const int chunk = blockIdx.x, nchunk = dec_nchunk(P.S_cmp);
@@ -262,8 +219,7 @@ __global__ __launch_bounds__(64, 2) void decode_logits_mfma_kernel(DecodeParams 
 #pragma unroll
         for (int s = 0; s < KSTEPS; ++s) {
             const x8 a = *(const x8 *)(kb + (int64_t)c * P.css + 32 * s + 8 * q);
-            if constexpr (std::is_same<T, __bf16>::value) acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, qf[s], acc[u], 0, 0, 0);
-            else acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, qf[s], acc[u], 0, 0, 0);
+            acc[u] = MfmaT<T>::mma(a, qf[s], acc[u]);
         }
     }
     // lane (head rho, group q) holds rows 16u + 4q + j of the chunk
@@ -397,9 +353,9 @@ __global__ __launch_bounds__(64) void decode_pgrp_kernel(DecodeParams P) {
 // and select_topn_kernel (same operations, same order), so p_grp and the ranges are bit-identical to the 3-kernel route;
 // it exists because a decode step is a chain of tiny launches and each one costs ~5 us of latency.
 // ---------------------------------------------------------------------------------------
-template <typename T, int KSTEPS, bool ATTEND>
-__global__ __launch_bounds__(1024) void decode_score_select_kernel(DecodeParams P, SelectParams SP, int cand, int t_token, DecAttnArgs AT, int stop) {
-    typedef typename std::conditional<std::is_same<T, __bf16>::value, bf16x8, f16x8>::type x8;
+template <typename T, int KSTEPS>
+__global__ __launch_bounds__(1024) void decode_score_select_kernel(DecodeParams P, SelectParams SP, int cand, int t_token, int stop) {
+    using x8 = typename MfmaT<T>::x8;
     extern __shared__ __attribute__((aligned(16))) float dsm[];
     const int lane = threadIdx.x & 63, wave = uniform((int)(threadIdx.x >> 6)), rho = lane & 15, q = lane >> 4;
     constexpr int NW = 16;
@@ -461,8 +417,7 @@ __global__ __launch_bounds__(1024) void decode_score_select_kernel(DecodeParams 
                 acc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int s = 0; s < KSTEPS; ++s) {
-                    if constexpr (std::is_same<T, __bf16>::value) acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[u][s], qf[s], acc[u], 0, 0, 0);
-                    else acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[u][s], qf[s], acc[u], 0, 0, 0);
+                    acc[u] = MfmaT<T>::mma(a[u][s], qf[s], acc[u]);
                 }
             }
             float m = -INFINITY;
@@ -642,9 +597,6 @@ __global__ __launch_bounds__(1024) void decode_score_select_kernel(DecodeParams 
             out[2 * lane + 1] = re;
         }
     }
-    // ---- phase 4: selection attention of the row over the ranges just chosen (same workgroup: the 16 waves take the 64-key chunks,
-    // partials merged through LDS -- sel_attn_decode.hpp).  The logits / scores in LDS are dead by now: their space holds the V tiles.
-    (void)rs, (void)re, (void)AT;  // (the attention of the row is its own launch behind this kernel: the one-launch step is sel_decode_fused.hip)
 }
 
 static size_t decode_fused_lds(int h, int S_cmp, int S_sel) {
@@ -653,45 +605,35 @@ static size_t decode_fused_lds(int h, int S_cmp, int S_sel) {
 }
 
 // fused route available?  (bf16/f16 MFMA shapes, the row's logits fit in LDS)
-bool decode_score_select_shape_ok(int dtype, int h, int Dk, int S_cmp, int S_sel, int64_t rows) {
+bool decode_score_select_shape_ok(const ScoresCall &c) {
     const int mode = tuning(TUNE_DECODE_UNFUSED);  // A/B switch for measurements and for the equivalence test: -1 auto, 0 fused, 1 unfused
     if (mode > 0) return false;
     // one workgroup per row sweeps the row's whole K_cmp: with few rows and a long context the 3-kernel route (one wave per 64 compressed
     // rows, spread over the chip) is faster (64k, B = 1: 73.6 vs 79.8 us per layer step); with >= 64 rows every CU has a row either way
-    const bool long_ok = mode == 0 || S_cmp <= 2048 || rows >= 64;
-    return (dtype == NSA_DT_BF16 || dtype == NSA_DT_F16) && (Dk == 64 || Dk == 128) && h <= 16 && S_cmp >= 1 && S_sel >= 1 &&
-           S_sel <= 64 * 32 && long_ok && decode_fused_lds(h, S_cmp, S_sel) <= 150 * 1024;
+    const bool long_ok = mode == 0 || c.S_cmp <= 2048 || c.rows() >= 64;
+    return (c.dtype == NSA_DT_BF16 || c.dtype == NSA_DT_F16) && (c.Dk == 64 || c.Dk == 128) && c.h <= 16 && c.S_cmp >= 1 && c.S_sel >= 1 &&
+           c.S_sel <= 64 * 32 && long_ok && decode_fused_lds(c.h, c.S_cmp, c.S_sel) <= 150 * 1024;
 }
 
-bool decode_score_select_supported(int dtype, int h, int Dk, int S_cmp, int S_sel, int64_t csb, int64_t csg, int64_t css, const void *Q,
-                                   const void *Kc, int64_t rows) {
-    return decode_score_select_shape_ok(dtype, h, Dk, S_cmp, S_sel, rows) && css % 8 == 0 && csb % 8 == 0 && csg % 8 == 0 &&
-           ((uintptr_t)Q % 16 == 0) && ((uintptr_t)Kc % 16 == 0);
+bool decode_score_select_supported(const ScoresCall &c) {
+    return decode_score_select_shape_ok(c) && kcmp_aligned(c.Q, c.K_cmp, c.csb, c.csg, c.css);
 }
 
-int launch_decode_score_select(const void *Q, const void *Kc, int B, int G, int h, int Dk, int S_cmp, int64_t csb, int64_t csg, int64_t css,
-                               const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel, int l_sel, int n_top,
-                               int t_token, int dtype, float scale, int32_t *ranges_out, hipStream_t st, const DecAttnArgs *attend,
-                               int stencil) {
-    const int64_t R = (int64_t)B * G;
+// one row per (b, g) at token s.t0 (c.S = 1); c.scale as the caller's entry point got it
+int launch_decode_score_select(const ScoresCall &c, const SelectCall &s, int stencil) {
+    const int64_t R = c.rows();
     NSA_CHECK_ARG(R <= 65535 * 32, "decode scorer: too many rows");
-    DecodeParams P{Q, Kc, nullptr, nullptr, nullptr, csc_ptr, csc_rows, csc_vals, R, 1, G, h, Dk, S_cmp, S_sel, csb, csg, css, scale * LOG2E,
-                   stencil && tuning(TUNE_DECODE_STENCIL) ? 1 : 0};
+    DecodeParams P{c.Q, c.K_cmp, nullptr, nullptr, nullptr, c.csc_ptr, c.csc_rows, c.csc_vals, R, 1, c.G, c.h, c.Dk, c.S_cmp, c.S_sel, c.csb, c.csg, c.css,
+                   default_scale(c.scale, c.Dk) * LOG2E, stencil && tuning(TUNE_DECODE_STENCIL) ? 1 : 0};
     SelectParams SP{};
-    if (int rc = select_params_sequential(&SP, S_sel, l_sel, n_top, 1, 2, n_top)) return rc;
-    SP.out = ranges_out;
-    SP.R = R;
-    SP.S = 1;
-    SP.G = G;
-    SP.t0 = t_token;
-    const int c = (S_sel + 63) / 64;
-    const int cand = c <= 1 ? 1 : c <= 2 ? 2 : c <= 4 ? 4 : c <= 8 ? 8 : c <= 16 ? 16 : 32;
-    size_t lds = decode_fused_lds(h, S_cmp, S_sel);
-    void (*k)(DecodeParams, SelectParams, int, int, DecAttnArgs, int);
-    DecAttnArgs AT{};
-    NSA_CHECK_ARG(attend == nullptr, "decode scorer: the attention is not part of this launch any more (sel_decode_fused.hip)");
-    if (dtype == NSA_DT_BF16) k = Dk == 64 ? decode_score_select_kernel<__bf16, 2, false> : decode_score_select_kernel<__bf16, 4, false>;
-    else k = Dk == 64 ? decode_score_select_kernel<_Float16, 2, false> : decode_score_select_kernel<_Float16, 4, false>;
+    if (int rc = select_params_fill(&SP, nullptr, R, 1, c.G, c.S_sel, c.l_sel, s)) return rc;
+    const int n = (c.S_sel + 63) / 64;
+    const int cand = n <= 1 ? 1 : n <= 2 ? 2 : n <= 4 ? 4 : n <= 8 ? 8 : n <= 16 ? 16 : 32;
+    size_t lds = decode_fused_lds(c.h, c.S_cmp, c.S_sel);
+    void (*k)(DecodeParams, SelectParams, int, int, int) = nullptr;
+    with_elt<false>(c.dtype, [&](auto t) {
+        k = c.Dk == 64 ? decode_score_select_kernel<decltype(t), 2> : decode_score_select_kernel<decltype(t), 4>;
+    });
     if (lds > 64 * 1024) {  // raise the dynamic-LDS limit once per kernel (the runtime call costs about a millisecond)
         static void *raised[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
         bool done = false;
@@ -705,7 +647,7 @@ int launch_decode_score_select(const void *Q, const void *Kc, int B, int G, int 
                 }
         }
     }
-    hipLaunchKernelGGL(k, dim3((unsigned)R), dim3(1024), lds, st, P, SP, cand, t_token, AT, tuning(TUNE_DECODE_STOP));
+    hipLaunchKernelGGL(k, dim3((unsigned)R), dim3(1024), lds, c.st, P, SP, cand, s.t0, tuning(TUNE_DECODE_STOP));
     NSA_LAUNCH_CHECK("decode_score_select");
     return NSA_OK;
 }
@@ -717,37 +659,27 @@ size_t decode_scores_workspace(int64_t R, int h, int S_cmp) {
     return three_kernel > split_step ? three_kernel : split_step;
 }
 
-int launch_decode_scores(const void *Q, const void *Kc, float *p_grp, int B, int S, int G, int h, int Dk, int S_cmp, int64_t csb,
-                         int64_t csg, int64_t css, const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals,
-                         int S_sel, int dtype, float scale, void *ws, size_t ws_bytes, hipStream_t st, int q0, int norm, int l, int d) {
-    const int64_t R = (int64_t)B * S * G;
-    NSA_CHECK_ARG(h <= 64 && Dk >= 1 && (size_t)h * Dk * 4 <= 64 * 1024, "decode scorer: h/Dk too large");
-    NSA_CHECK_ARG(ws && ws_bytes >= decode_scores_workspace(R, h, S_cmp), "decode scorer: workspace too small");
+int launch_decode_scores(const ScoresCall &c) {
+    const int64_t R = c.rows();
+    const int h = c.h, Dk = c.Dk;
+    const ScoresRoute route = scores_route(c, 3);
+    NSA_CHECK_ARG(Dk >= 1 && route.decode_fits, "decode scorer: h/Dk too large");
+    NSA_CHECK_ARG(c.ws && c.ws_bytes >= decode_scores_workspace(R, h, c.S_cmp), "decode scorer: workspace too small");
     NSA_CHECK_ARG(R <= 65535, "decode scorer: too many rows");
-    DecodeParams P{Q, Kc, (float *)ws, (float *)ws + (size_t)R * h * S_cmp, p_grp, csc_ptr, csc_rows, csc_vals, R, S, G, h, Dk, S_cmp,
-                   S_sel, csb, csg, css, scale * LOG2E, 0, q0, norm, l, d};
-    const dim3 grid1((unsigned)dec_nchunk(S_cmp), (unsigned)R);
+    DecodeParams P{c.Q, c.K_cmp, (float *)c.ws, (float *)c.ws + (size_t)R * h * c.S_cmp, c.p_grp, c.csc_ptr, c.csc_rows, c.csc_vals, R, c.S, c.G, h, Dk,
+                   c.S_cmp, c.S_sel, c.csb, c.csg, c.css, c.scale * LOG2E, 0, c.q0, c.norm, c.l, c.d};
+    const dim3 grid1((unsigned)dec_nchunk(c.S_cmp), (unsigned)R);
     const size_t lds = sizeof(float) * (size_t)h * Dk;
-    const bool mfma = (dtype == NSA_DT_BF16 || dtype == NSA_DT_F16) && (Dk == 64 || Dk == 128) && h <= 16 && css % 8 == 0 &&
-                      csb % 8 == 0 && csg % 8 == 0 && ((uintptr_t)Q % 16 == 0) && ((uintptr_t)Kc % 16 == 0);
-    if (mfma) {
-        if (dtype == NSA_DT_BF16) {
-            if (Dk == 64) hipLaunchKernelGGL((decode_logits_mfma_kernel<__bf16, 2>), grid1, dim3(64), 0, st, P);
-            else hipLaunchKernelGGL((decode_logits_mfma_kernel<__bf16, 4>), grid1, dim3(64), 0, st, P);
-        } else {
-            if (Dk == 64) hipLaunchKernelGGL((decode_logits_mfma_kernel<_Float16, 2>), grid1, dim3(64), 0, st, P);
-            else hipLaunchKernelGGL((decode_logits_mfma_kernel<_Float16, 4>), grid1, dim3(64), 0, st, P);
-        }
+    if (route.mfma) {
+        with_elt<false>(c.dtype, [&](auto t) {
+            if (Dk == 64) hipLaunchKernelGGL((decode_logits_mfma_kernel<decltype(t), 2>), grid1, dim3(64), 0, c.st, P);
+            else hipLaunchKernelGGL((decode_logits_mfma_kernel<decltype(t), 4>), grid1, dim3(64), 0, c.st, P);
+        });
     } else {
-        switch (dtype) {
-            case NSA_DT_F32: hipLaunchKernelGGL(decode_logits_kernel<float>, grid1, dim3(64), lds, st, P); break;
-            case NSA_DT_BF16: hipLaunchKernelGGL(decode_logits_kernel<__bf16>, grid1, dim3(64), lds, st, P); break;
-            case NSA_DT_F16: hipLaunchKernelGGL(decode_logits_kernel<_Float16>, grid1, dim3(64), lds, st, P); break;
-            default: NSA_CHECK_ARG(false, "decode scorer: unknown dtype %d", dtype);
-        }
+        with_elt(c.dtype, [&](auto t) { hipLaunchKernelGGL(decode_logits_kernel<decltype(t)>, grid1, dim3(64), lds, c.st, P); });
     }
     NSA_LAUNCH_CHECK("decode_logits");
-    hipLaunchKernelGGL(decode_pgrp_kernel, dim3((unsigned)((S_sel + 63) / 64), (unsigned)R), dim3(64), 0, st, P);
+    hipLaunchKernelGGL(decode_pgrp_kernel, dim3((unsigned)((c.S_sel + 63) / 64), (unsigned)R), dim3(64), 0, c.st, P);
     NSA_LAUNCH_CHECK("decode_pgrp");
     return NSA_OK;
 }
@@ -767,26 +699,21 @@ size_t scores_workspace(int64_t R, int h, int S_cmp) {
     return rows * per_row;
 }
 
-int launch_sel_scores(const void *Q, const void *Kc, float *p_grp, int B, int S, int G, int h, int Dk, int S_cmp,
-                      int64_t csb, int64_t csg, int64_t css, const int32_t *csc_ptr, const int32_t *csc_rows,
-                      const float *csc_vals, int S_sel, int dtype, float scale, void *ws, size_t ws_bytes,
-                      hipStream_t st, int q0, int norm, int l, int d) {
-    const int64_t R = (int64_t)B * S * G;
-    if (R == 0 || S_sel == 0) return NSA_OK;
-    if (S_cmp == 0) {  // selection_scorer.py:97-98 -> zeros
-        NSA_HIP_TRY(hipMemsetAsync(p_grp, 0, sizeof(float) * (size_t)R * S_sel, st));
+int launch_sel_scores(const ScoresCall &c) {
+    const int64_t R = c.rows();
+    if (R == 0 || c.S_sel == 0) return NSA_OK;
+    if (c.S_cmp == 0) {  // selection_scorer.py:97-98 -> zeros
+        NSA_HIP_TRY(hipMemsetAsync(c.p_grp, 0, sizeof(float) * (size_t)R * c.S_sel, c.st));
         return NSA_OK;
     }
-    const size_t per_row = sizeof(float) * (size_t)h * (size_t)S_cmp;
-    NSA_CHECK_ARG(ws != nullptr && ws_bytes >= per_row, "scores: workspace too small (%zu < %zu)", ws_bytes, per_row);
-    const int64_t chunk = (int64_t)(ws_bytes / per_row);
+    const size_t per_row = sizeof(float) * (size_t)c.h * (size_t)c.S_cmp;
+    NSA_CHECK_ARG(c.ws != nullptr && c.ws_bytes >= per_row, "scores: workspace too small (%zu < %zu)", c.ws_bytes, per_row);
+    const int64_t chunk = (int64_t)(c.ws_bytes / per_row);
     for (int64_t r0 = 0; r0 < R; r0 += chunk) {
         const int64_t nr = (R - r0 < chunk) ? R - r0 : chunk;
-        int rc = launch_pcmp(Q, Kc, (float *)ws, r0, nr, S, G, h, Dk, S_cmp, csb, csg, css, dtype, scale, st, q0, norm, l, d);
-        if (rc) return rc;
-        rc = launch_map_pcmp((const float *)ws, nr, h, S_cmp, csc_ptr, csc_rows, csc_vals, S_sel, nullptr,
-                             p_grp + r0 * S_sel, st);
-        if (rc) return rc;
+        if (int rc = launch_pcmp(c, r0, nr)) return rc;
+        if (int rc = launch_map_pcmp((const float *)c.ws, nr, c.h, c.S_cmp, c.csc_ptr, c.csc_rows, c.csc_vals, c.S_sel, nullptr, c.p_grp + r0 * c.S_sel, c.st))
+            return rc;
     }
     return NSA_OK;
 }

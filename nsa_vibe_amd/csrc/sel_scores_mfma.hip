@@ -25,24 +25,13 @@
 // sequence); columns c >= n_cmp(t) are masked per lane (-inf in sweep 1, p = 0 in sweep 2) on the few tiles that reach past the wave's
 // earliest bound, so masked tiles leave a row's statistics bit for bit unchanged and a row's p_grp does not depend on which later rows
 // share its chunk (chunk boundaries at multiples of the workgroup's QW queries).
+#include "attn_mfma_tiles.hpp"
 #include "sel_scores_mfma.hpp"
 #include "sel_select_row.hpp"
+#include "nsa_host.hpp"
 #include "nsa_internal.hpp"
 
 namespace nsa {
-
-template <typename T>
-struct MfmaS;
-template <>
-struct MfmaS<__bf16> {
-    using x8 = bf16x8;
-    __device__ static f32x4 mma(x8 a, x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
-template <>
-struct MfmaS<_Float16> {
-    using x8 = f16x8;
-    __device__ static f32x4 mma(x8 a, x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-};
 
 // HC: heads per group as a compile-time constant (0 = read P.h at run time).  The Eq.10 head sum is h - 1 DPP adds per
 // (16-row sub-tile, column tile); with a run-time h every one of the 15 possible adds is its own two-instruction basic block
@@ -56,7 +45,7 @@ struct MfmaS<_Float16> {
 template <typename T, int D, int NT, int HC, bool NORM>
 __global__ __launch_bounds__(256, 2) void scores_mfma_kernel(ScoresMfmaParams P) {
     constexpr bool FLAT = (HC == 6 && NT == 3);
-    using M = MfmaS<T>;
+    using M = MfmaT<T>;  // attn_mfma_tiles.hpp: the 16x16x32 MFMA of the element type
     using x8 = typename M::x8;
     constexpr int ROWB = D * 2;
     constexpr int PIECES = D / 8;
@@ -381,9 +370,9 @@ __global__ __launch_bounds__(256, 2) void scores_mfma_kernel(ScoresMfmaParams P)
 }
 
 // ---- host -----------------------------------------------------------------------------------
-bool scores_mfma_supported(int dtype, int h, int Dk, int l, int d, int l_sel) {
-    return (dtype == NSA_DT_BF16 || dtype == NSA_DT_F16) && (Dk == 64 || Dk == 128) && h >= 1 && h <= 16 && d > 0 && l == 2 * d &&
-           l_sel == 4 * d;
+bool scores_mfma_supported(const ScoresCall &c) {
+    return (c.dtype == NSA_DT_BF16 || c.dtype == NSA_DT_F16) && (c.Dk == 64 || c.Dk == 128) && c.h >= 1 && c.h <= 16 && c.d > 0 && c.l == 2 * c.d &&
+           c.l_sel == 4 * c.d;
 }
 
 template <typename T, int D, bool NORM>
@@ -408,36 +397,35 @@ static int launch_scores_t(const ScoresMfmaParams &P, hipStream_t st) {
 
 // sel / sel_done: the caller wants the top-n ranges of every row too; *sel_done says whether this launch produced them (the 32x32x16 form
 // selects inside the launch) or the caller has to run the select kernel behind it
-int launch_sel_scores_mfma(const void *Q, const void *Kc, float *p_grp, int B, int S, int G, int h, int Dk, int S_cmp,
-                           int64_t csb, int64_t csg, int64_t css, int S_sel, int d_stride, int dtype, float scale,
-                           int causal_skip, hipStream_t st, const SelectParams *sel, int *sel_done, int q0, int norm, int l) {
+int launch_sel_scores_mfma(const ScoresCall &c, const SelectParams *sel, int *sel_done) {
     if (sel_done) *sel_done = 0;
-    NSA_CHECK_ARG(css % 8 == 0 && csb % 8 == 0 && csg % 8 == 0 && ((uintptr_t)Q % 16 == 0) && ((uintptr_t)Kc % 16 == 0),
+    NSA_CHECK_ARG(kcmp_aligned(c.Q, c.K_cmp, c.csb, c.csg, c.css),
                   "scores_mfma: Q/K_cmp must be 16-byte aligned with strides that are multiples of 8 elements");
-    NSA_CHECK_ARG((int64_t)B * G <= 65535, "scores_mfma: B*G too large for one launch");
-    NSA_CHECK_ARG(S_cmp >= 1, "scores_mfma: S_cmp must be >= 1");
+    NSA_CHECK_ARG((int64_t)c.B * c.G <= 65535, "scores_mfma: B*G too large for one launch");
+    NSA_CHECK_ARG(c.S_cmp >= 1, "scores_mfma: S_cmp must be >= 1");
 
     // blocks the second sweep does not visit (causal skip, or selection blocks without any compressed row) are zero -- unless the caller
     // asked for causal_skip == 2: it then reads only entries with (j+1) l' <= t+1 (what both selectors do), all of which are written
-    if (causal_skip != 2) NSA_HIP_TRY(hipMemsetAsync(p_grp, 0, sizeof(float) * (size_t)B * S * G * S_sel, st));
-    ScoresMfmaParams P{Q, Kc, p_grp, B, S, G, h, S_cmp, S_sel, csb, csg, css, scale, causal_skip, d_stride,
-                       (int64_t)S * G * S_sel < ((int64_t)1 << 31) ? 0 : 1, q0, norm ? 1 : 0, l};
+    if (c.causal_skip != 2) NSA_HIP_TRY(hipMemsetAsync(c.p_grp, 0, sizeof(float) * (size_t)c.rows() * c.S_sel, c.st));
+    ScoresMfmaParams P{c.Q, c.K_cmp, c.p_grp, c.B, c.S, c.G, c.h, c.S_cmp, c.S_sel, c.csb, c.csg, c.css, c.scale, c.causal_skip, c.d,
+                       (int64_t)c.S * c.G * c.S_sel < ((int64_t)1 << 31) ? 0 : 1, c.q0, c.norm ? 1 : 0, c.l};
     const int form = tuning(TUNE_SCORES_FORM);
-    if ((form < 0 || form == 2) && scores_mfma32_supported(P, Dk)) {
+    if ((form < 0 || form == 2) && scores_mfma32_supported(P, c.Dk)) {
         // in the launch only where it pays (same box, tools/bench_scores_select.py: 64k x 4 3,537 -> 3,433 us, 64k x 1 905 -> 890, but 32k x 2
         // 509 -> 521, 16k x 2 161 -> 180, 4k x 8 75 -> 87): a wave's 16 rows are 16 dependent chains of ~2 us behind its sweeps, which only
         // a long sweep (a workgroup's lifetime grows with S_cmp) and many workgroups per CU hide.  TUNE_SCORES_SELECT: -1 this rule, 0 never, 1 always
         const int mode = tuning(TUNE_SCORES_SELECT);
-        const bool fuse = sel && sel_done && mode != 0 && (mode > 0 || S_cmp >= 3072) && scores_mfma32_select_supported(P, Dk, *sel);
+        const bool fuse = sel && sel_done && mode != 0 && (mode > 0 || c.S_cmp >= 3072) && scores_mfma32_select_supported(P, c.Dk, *sel);
         if (fuse) *sel_done = 1;
-        return launch_scores_mfma32(P, dtype, st, fuse ? sel : nullptr);
+        return launch_scores_mfma32(P, c.dtype, c.st, fuse ? sel : nullptr);
     }
-    if (P.norm) {
-        if (dtype == NSA_DT_BF16) return Dk == 64 ? launch_scores_t<__bf16, 64, true>(P, st) : launch_scores_t<__bf16, 128, true>(P, st);
-        return Dk == 64 ? launch_scores_t<_Float16, 64, true>(P, st) : launch_scores_t<_Float16, 128, true>(P, st);
-    }
-    if (dtype == NSA_DT_BF16) return Dk == 64 ? launch_scores_t<__bf16, 64, false>(P, st) : launch_scores_t<__bf16, 128, false>(P, st);
-    return Dk == 64 ? launch_scores_t<_Float16, 64, false>(P, st) : launch_scores_t<_Float16, 128, false>(P, st);
+    int rc = NSA_OK;
+    with_elt<false>(c.dtype, [&](auto t) {
+        using T = decltype(t);
+        if (P.norm) rc = c.Dk == 64 ? launch_scores_t<T, 64, true>(P, c.st) : launch_scores_t<T, 128, true>(P, c.st);
+        else rc = c.Dk == 64 ? launch_scores_t<T, 64, false>(P, c.st) : launch_scores_t<T, 128, false>(P, c.st);
+    });
+    return rc;
 }
 
 }  // namespace nsa

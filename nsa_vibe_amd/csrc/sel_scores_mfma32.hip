@@ -449,26 +449,17 @@ bool scores_mfma32_select_supported(const ScoresMfmaParams &P, int Dk, const Sel
 
 int launch_scores_mfma32(const ScoresMfmaParams &P, int dtype, hipStream_t st, const SelectParams *sel) {
     dim3 grid((unsigned)((P.S + 63) / 64), (unsigned)(P.B * P.G));
-    if (P.norm) {
-        const SelectParams none{};
-        if (dtype == NSA_DT_BF16) {
-            if (sel) hipLaunchKernelGGL((scores_mfma32_kernel<__bf16, true, true>), grid, dim3(256), 0, st, P, *sel);
-            else hipLaunchKernelGGL((scores_mfma32_kernel<__bf16, false, true>), grid, dim3(256), 0, st, P, none);
+    const SelectParams none{};
+    with_elt<false>(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (P.norm) {
+            if (sel) hipLaunchKernelGGL((scores_mfma32_kernel<T, true, true>), grid, dim3(256), 0, st, P, *sel);
+            else hipLaunchKernelGGL((scores_mfma32_kernel<T, false, true>), grid, dim3(256), 0, st, P, none);
         } else {
-            if (sel) hipLaunchKernelGGL((scores_mfma32_kernel<_Float16, true, true>), grid, dim3(256), 0, st, P, *sel);
-            else hipLaunchKernelGGL((scores_mfma32_kernel<_Float16, false, true>), grid, dim3(256), 0, st, P, none);
+            if (sel) hipLaunchKernelGGL((scores_mfma32_kernel<T, true, false>), grid, dim3(256), 0, st, P, *sel);
+            else hipLaunchKernelGGL((scores_mfma32_kernel<T, false, false>), grid, dim3(256), 0, st, P, none);
         }
-        NSA_LAUNCH_CHECK("scores_mfma32");
-        return NSA_OK;
-    }
-    if (sel) {
-        if (dtype == NSA_DT_BF16) hipLaunchKernelGGL((scores_mfma32_kernel<__bf16, true, false>), grid, dim3(256), 0, st, P, *sel);
-        else hipLaunchKernelGGL((scores_mfma32_kernel<_Float16, true, false>), grid, dim3(256), 0, st, P, *sel);
-    } else {
-        const SelectParams none{};
-        if (dtype == NSA_DT_BF16) hipLaunchKernelGGL((scores_mfma32_kernel<__bf16, false, false>), grid, dim3(256), 0, st, P, none);
-        else hipLaunchKernelGGL((scores_mfma32_kernel<_Float16, false, false>), grid, dim3(256), 0, st, P, none);
-    }
+    });
     NSA_LAUNCH_CHECK("scores_mfma32");
     return NSA_OK;
 }

@@ -16,6 +16,7 @@
 #include "nsa_common.hpp"
 
 #include "sel_select_row.hpp"
+#include "nsa_host.hpp"
 #include "nsa_internal.hpp"
 
 namespace nsa {
@@ -107,29 +108,16 @@ int batched_width(int S, int S_sel, int l_sel, int n_top, int force_init, int fo
     return nfc < n_top ? nfc : n_top;
 }
 
-int select_params_sequential(SelectParams *P, int S_sel, int l_sel, int n_top, int force_init, int force_local, int W) {
-    NSA_CHECK_ARG(S_sel >= 1 && S_sel <= 64 * 64 && l_sel >= 1 && n_top >= 0 && force_local >= 0 && force_local <= 30 && W == n_top,
-                  "select (sequential): bad sizes");
-    P->S_sel = S_sel; P->l_sel = l_sel; P->n_top = n_top; P->force_init = force_init ? 1 : 0; P->force_local = force_local;
-    P->mode = NSA_SEL_SEQUENTIAL; P->W = W;
-    P->l_sel_shift = (l_sel & (l_sel - 1)) == 0 ? __builtin_ctz((unsigned)l_sel) : -1;
-    const int nf_all = P->force_init + force_local;
-    const int k_rest = n_top - nf_all > 0 ? n_top - nf_all : 0;
-    P->k_actual = k_rest < S_sel ? k_rest : S_sel;
-    P->n_forced = nf_all;
-    P->keepmask = 0xffffffffu;
-    P->all_valid = 0;
-    P->forced_plain = 1;
-    return NSA_OK;
-}
-
-int select_params_fill(SelectParams *Pp, int S_sel, int l_sel, int n_top, int force_init, int force_local, int mode, int S_total, int W) {
+// the one fill of the selector's block: the rows (row (b, s, g) of R selects at token s.t0 + s, or s.t_rows[row]) and the selection rule
+int select_params_fill(SelectParams *Pp, const float *p_grp, int64_t R, int S, int G, int S_sel, int l_sel, const SelectCall &s) {
     SelectParams &P = *Pp;
+    const int n_top = s.n_top, force_local = s.force_local, W = s.out_width;
     NSA_CHECK_ARG(S_sel >= 1 && S_sel <= 64 * 64 && l_sel >= 1 && n_top >= 0 && force_local >= 0 && force_local <= 30, "select: bad sizes");
-    P.S_sel = S_sel; P.l_sel = l_sel; P.n_top = n_top; P.force_init = force_init ? 1 : 0; P.force_local = force_local; P.mode = mode; P.W = W;
+    P.p_grp = p_grp; P.t_rows = s.t_rows; P.out = s.ranges_out; P.R = R; P.S = S; P.G = G; P.t0 = s.t0;
+    P.S_sel = S_sel; P.l_sel = l_sel; P.n_top = n_top; P.force_init = s.force_init ? 1 : 0; P.force_local = force_local; P.mode = s.mode; P.W = W;
     P.l_sel_shift = (l_sel & (l_sel - 1)) == 0 ? __builtin_ctz((unsigned)l_sel) : -1;
     const int nf_all = P.force_init + force_local;
-    if (mode == NSA_SEL_SEQUENTIAL) {
+    if (s.mode == NSA_SEL_SEQUENTIAL) {
         NSA_CHECK_ARG(W == n_top, "select (sequential): out_width must be n_top");
         const int k_rest = n_top - nf_all > 0 ? n_top - nf_all : 0;
         P.k_actual = k_rest < S_sel ? k_rest : S_sel;
@@ -137,10 +125,10 @@ int select_params_fill(SelectParams *Pp, int S_sel, int l_sel, int n_top, int fo
         P.keepmask = 0xffffffffu;
         P.all_valid = 0;
         P.forced_plain = 1;
-    } else if (mode == NSA_SEL_BATCHED) {
+    } else if (s.mode == NSA_SEL_BATCHED) {
         int nfc;
-        P.keepmask = batched_keepmask(S_total, l_sel, force_init, force_local, &nfc);
-        NSA_CHECK_ARG(W == batched_width(S_total, S_sel, l_sel, n_top, force_init, force_local),
+        P.keepmask = batched_keepmask(s.S_total, l_sel, s.force_init, force_local, &nfc);
+        NSA_CHECK_ARG(W == batched_width(s.S_total, S_sel, l_sel, n_top, s.force_init, force_local),
                       "select (batched): out_width %d != nsa_batched_ranges_width()", W);
         const int k_rest = n_top - nfc > 0 ? n_top - nfc : 0;
         P.k_actual = k_rest < S_sel ? k_rest : S_sel;
@@ -148,25 +136,15 @@ int select_params_fill(SelectParams *Pp, int S_sel, int l_sel, int n_top, int fo
         P.all_valid = n_top >= S_sel ? 1 : 0;
         P.forced_plain = (nfc == nf_all && P.n_forced == nf_all) ? 1 : 0;
     } else {
-        NSA_CHECK_ARG(false, "select: unknown mode %d", mode);
+        NSA_CHECK_ARG(false, "select: unknown mode %d", s.mode);
     }
     return NSA_OK;
 }
 
-int launch_select_topn(const float *p_grp, int64_t R, int S, int G, int t0, const int32_t *t_rows, int S_sel,
-                       int l_sel, int n_top, int force_init, int force_local, int mode, int S_total,
-                       int32_t *out, int W, hipStream_t st) {
-    NSA_CHECK_ARG(R >= 0 && S >= 1 && G >= 1 && S_sel >= 1 && l_sel >= 1 && n_top >= 0, "select: bad sizes");
-    NSA_CHECK_ARG(S_sel <= 64 * 64, "select: S_sel=%d exceeds 4096 selection blocks", S_sel);
-    NSA_CHECK_ARG(force_local >= 0 && force_local <= 30, "select: force_local out of range");
-    SelectParams P{};
-    P.p_grp = p_grp; P.t_rows = t_rows; P.out = out; P.R = R; P.S = S; P.G = G; P.t0 = t0; P.S_sel = S_sel;
-    P.l_sel = l_sel; P.n_top = n_top; P.force_init = force_init ? 1 : 0; P.force_local = force_local; P.mode = mode;
-    P.W = W;
-    if (int rc = select_params_fill(&P, S_sel, l_sel, n_top, force_init, force_local, mode, S_total, W)) return rc;
-    if (R == 0 || W == 0) return NSA_OK;
-    const unsigned grid = (unsigned)((R + 3) / 4);
-    const int cand = (S_sel + 63) / 64;
+int launch_select_topn(const SelectParams &P, hipStream_t st) {
+    if (P.R == 0 || P.W == 0) return NSA_OK;
+    const unsigned grid = (unsigned)((P.R + 3) / 4);
+    const int cand = (P.S_sel + 63) / 64;
 #define NSA_SEL_LAUNCH(C) hipLaunchKernelGGL(select_topn_kernel<C>, dim3(grid), dim3(256), 0, st, P)
     if (cand <= 1) NSA_SEL_LAUNCH(1);
     else if (cand <= 2) NSA_SEL_LAUNCH(2);

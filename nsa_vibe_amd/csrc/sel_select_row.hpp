@@ -3,25 +3,12 @@
 #include <type_traits>
 
 #include "nsa_common.hpp"
+#include "sel_scores_params.hpp"
 
 #ifndef DEC_TS
 #define DEC_TS(i)
 #endif
 namespace nsa {
-
-struct SelectParams {
-    const float *p_grp;     // [R,S_sel]
-    const int32_t *t_rows;  // [R] or null
-    int32_t *out;           // [R,W,2]
-    int64_t R;
-    int S, G, t0, S_sel, l_sel, n_top, force_init, force_local, mode, W;
-    int k_actual;      // picks per row
-    int n_forced;      // forced entries used (sequential: all; batched: kept columns, maybe truncated)
-    unsigned keepmask; // batched: bit i = sorted forced column i is kept
-    int all_valid;     // batched with n_top >= S_sel: select every valid block
-    int l_sel_shift;   // log2(l_sel) when l_sel is a power of two, else -1 (the block of a token without an integer division)
-    int forced_plain;  // batched: every forced column is kept and used (S > 2 l'), the forced set is {0} + (cblk - force_local, cblk]
-};
 
 // runs of a selected-block bitmap (wd[c] = blocks 64 c .. 64 c + 63, wave uniform) -> token ranges, by all lanes at once: a lane that starts /
 // ends a run takes the run's index from the bits below it and drops the token bound into scr[2 index (+1)]; lane i then holds run i in
@@ -395,8 +382,8 @@ __device__ __forceinline__ void select_topn_row_auto(const SelectParams &P, cons
     select_topn_row<CAND>(P, p, t, out, sc, pre);
 }
 
-// host: SelectParams of the sequential selector (decode / per-row prefill), see sel_select.hip
-int select_params_sequential(SelectParams *P, int S_sel, int l_sel, int n_top, int force_init, int force_local, int W);
-int select_params_fill(SelectParams *P, int S_sel, int l_sel, int n_top, int force_init, int force_local, int mode, int S_total, int W);
+// host: the one fill of SelectParams (sel_select.hip)
+struct SelectCall;  // nsa_host.hpp
+int select_params_fill(SelectParams *P, const float *p_grp, int64_t R, int S, int G, int S_sel, int l_sel, const SelectCall &s);
 
 }  // namespace nsa

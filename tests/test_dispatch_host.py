@@ -221,3 +221,90 @@ def test_layer_decode_step_routes(routes):
     assert launches(routes["layer_decode_step/t100"]) == ["qkv_rope_append(fast)", "decode_step", "linear_small_mix"]  # three launches
     assert launches(routes["layer_decode_step/t31_first_compressed_token"])[1] == "cmp_pool(wide)"
     assert launches(routes["layer_decode_step/D128_t100"])[:2] == ["qkv_rope_append(fast)", "decode_step"]
+
+
+# ---- the scorer and selector family: the argument blocks of its launches (csrc/sel_scores_params.hpp), member by member
+
+def blocks(case, key):
+    """the argument blocks named `key` of a case's launches, in launch order"""
+    return [a[key] for a in case["args"] if key in a]
+
+
+def test_generic_scorer_walks_its_rows_in_workspace_sized_chunks(routes):
+    case = routes["sel_scores_rows/v1_10_rows_workspace_of_3"]  # ten rows, room for three
+    assert launches(case) == ["pcmp", "map_pcmp"] * 4
+    assert [(p["row0"], p["nrows"]) for p in blocks(case, "PcmpParams")] == [(0, 3), (3, 3), (6, 3), (9, 1)]
+    maps = blocks(case, "MapParams")
+    assert [m["R"] for m in maps] == [3, 3, 3, 1]
+    assert [m["p_grp"] for m in maps] == [f"p_grp+{4 * r0 * m['S_sel']}" for r0, m in zip((0, 3, 6, 9), maps)]  # fp32 [R, S_sel] rows
+    assert all(p["p_cmp"] == m["p_cmp"] == "ws+0" for p, m in zip(blocks(case, "PcmpParams"), maps))
+
+
+def test_q0_norm_l_d_land_in_the_members_of_those_names(routes):
+    """q0 = 100, norm = 1, l = 32, d = 16: four neighbouring ints that differ pairwise, on every route"""
+    (p,) = blocks(routes["sel_scores_rows/q0_100_v1"], "PcmpParams")
+    assert (p["q0"], p["norm"], p["l"], p["d"]) == (100, 1, 32, 16)
+    for p in blocks(routes["sel_scores_rows/q0_100_v3"], "DecodeParams"):  # both kernels of the decode-shaped pair
+        assert (p["q0"], p["norm"], p["l"], p["d"], p["stencil"]) == (100, 1, 32, 16, 0)
+    (p,) = blocks(routes["sel_scores_rows/q0_100_v0"], "ScoresMfmaParams")
+    assert (p["q0"], p["norm"], p["l"], p["d_stride"]) == (100, 1, 32, 16)
+    (sp,) = blocks(routes["sel_scores_select_rows/mfma32_q0_100"], "SelectParams")[1:]  # the select kernel's: rows select at t0 = q0
+    assert (sp["t0"], sp["S"], sp["G"], sp["R"]) == (100, 64, 2, 128)
+
+
+def test_causal_skip_2_leaves_p_grp_unwritten(routes):
+    """the tiled scorer zero-fills p_grp unless the caller reads only what the second sweep writes (causal_skip = 2)"""
+    assert [routes[f"sel_scores_rows/causal_skip_{s}"]["memsets"] for s in (0, 1, 2)] == [1, 1, 0]
+    for s in (0, 1, 2):
+        case = routes[f"sel_scores_rows/causal_skip_{s}"]
+        assert launches(case) == ["scores_mfma32"] and blocks(case, "ScoresMfmaParams")[0]["causal_skip"] == s
+    empty = routes["sel_scores_rows/S_cmp_0"]  # no compressed token: zero scores, no launch
+    assert (empty["rc"], empty["launches"], empty["memsets"]) == (0, [], 1)
+
+
+def test_selection_inside_the_scorer_launch_gets_the_select_kernels_block(routes):
+    """nsa_sel_scores_select_rows on the 32x32x16 route: the SelectParams handed to the scorer launch (SCORES_SELECT 1) and to the
+    select_topn launch behind it (default) are the same block, member for member -- there is no field the scorer kernel's selection does not
+    take from it (its row function is the select kernel's own)."""
+    for mode in ("sequential", "batched"):
+        inside = routes[f"sel_scores_select_rows/mfma32_{mode}_SCORES_SELECT_1"]
+        behind = routes[f"sel_scores_select_rows/mfma32_{mode}"]
+        assert launches(inside) == ["scores_mfma32"] and launches(behind) == ["scores_mfma32", "select_topn"]
+        (sp_inside,) = blocks(inside, "SelectParams")
+        none, sp_behind = blocks(behind, "SelectParams")
+        assert sp_inside == sp_behind and sp_inside["out"] == "ranges+0" and sp_inside["p_grp"] == "p_grp+0"
+        assert none["out"] == "null" and none["R"] == 0  # the scorer launch without a selection carries an empty block
+        assert blocks(inside, "ScoresMfmaParams") == blocks(behind, "ScoresMfmaParams")
+    for mode, message in (("sequential", "select (sequential): out_width must be n_top"),
+                          ("batched", "select (batched): out_width 2 != nsa_batched_ranges_width()")):
+        wrong = routes[f"sel_scores_select_rows/{mode}_wrong_out_width"]
+        assert (wrong["rc"], wrong["error"], wrong["launches"]) == (INVALID, message, [])
+
+
+def test_unaligned_K_cmp_keeps_the_generic_scorer(routes):
+    """K_cmp 8 bytes off its 16-byte alignment: pcmp + map_pcmp from nsa_sel_scores_select_rows and from the layer calls; nsa_sel_scores_rows
+    itself never leaves the route of a shape (variant 0 refuses, as a forced variant 2 does): its callers ask for variant 1."""
+    assert launches(routes["sel_scores_select_rows/K_cmp_8_bytes_off"]) == ["pcmp", "map_pcmp", "select_topn"]
+    assert blocks(routes["sel_scores_select_rows/K_cmp_8_bytes_off"], "PcmpParams")[0]["Kc"] == "Kc+8"
+    assert launches(routes["sel_scores_rows/K_cmp_8_bytes_off_v1"]) == launches(routes["sel_scores_rows/css_not_8_v1"]) == ["pcmp", "map_pcmp"]
+    refusal = ("sel_scores: MFMA route needs bf16/f16, Dk in {64,128}, h <= 16, l = 2d, l' = 4d and 16-byte aligned rows "
+               "(pass variant 1 for the generic route)")
+    for case in ("K_cmp_8_bytes_off", "css_not_8", "K_cmp_8_bytes_off_forced_v2", "css_not_8_forced_v2"):
+        assert (routes[f"sel_scores_rows/{case}"]["rc"], routes[f"sel_scores_rows/{case}"]["error"]) == (INVALID, refusal), case
+    for case in ("layer_prefill/S512_K_cmp_8_bytes_off", "layer_extend/t0_S512_K_cmp_8_bytes_off", "layer_prefill/S100_K_cmp_8_bytes_off",
+                 "layer_extend/t0_S100_K_cmp_8_bytes_off"):
+        assert launches(routes[case])[2:4] == ["pcmp", "map_pcmp"], case
+
+
+def test_decode_step_separate_launches_and_their_blocks(routes):
+    fused = routes["sel_decode_step/t100_DECODE_STEP_0"]
+    assert launches(fused) == ["decode_score_select", "sel_attn_decode_wg"]
+    (a,) = fused["args"]
+    assert (a["cand"], a["t_token"], a["DecodeParams"]["stencil"], a["SelectParams"]["t0"], a["SelectParams"]["out"]) == (1, 100, 1, 100, "ranges+0")
+    other = routes["sel_decode_step/t100_DECODE_STEP_0_geometry_16_16_32"]["args"][0]  # l != 2d: the CSC arrays, not the stencil
+    assert (other["DecodeParams"]["stencil"], other["SelectParams"]["l_sel"], other["SelectParams"]["l_sel_shift"]) == (0, 32, 5)
+    unfused = routes["sel_decode_step/t100_DECODE_STEP_0_DECODE_UNFUSED_1"]
+    assert launches(unfused) == ["decode_logits", "decode_pgrp", "select_topn", "sel_attn_decode_wg"]
+    logits, pgrp = blocks(unfused, "DecodeParams")
+    (sp,) = blocks(unfused, "SelectParams")
+    assert logits == pgrp and logits["p_grp"] == sp["p_grp"] and sp == dict(a["SelectParams"], p_grp=sp["p_grp"])

@@ -993,3 +993,38 @@ def test_scores_and_select_falls_back_to_two_launches_off_the_mfma32_route(nv, t
         p1, r1 = nv.selection_scores_select(Q, Kc, meta, n)
         torch.cuda.synchronize()
         assert torch.equal(r0, r1), (h, dtype)
+
+
+def test_generic_scorer_row_chunks_give_the_same_scores(nv, orc):
+    """The generic scorer walks its rows in chunks of what the workspace holds (h * S_cmp floats per row): ten rows of 27 logits with the
+    workspace of nsa_sel_scores_rows_workspace (one chunk) and with room for exactly three rows (chunks of 3, 3, 3, 1) give the same p_grp
+    bit for bit, and the oracle's within the generic scorer's bound (test_mfma_scorer_vs_oracle)."""
+    from nsa_vibe_amd import _lib
+    from nsa_vibe_amd.selection_scorer import _DT, _stream
+
+    B, S, G, h, D, geom = 1, 5, 2, 3, 32, (16, 8, 32)
+    m = nv.build_block_meta(80, *geom, 16, 512)
+    mo = orc.build_block_meta(80, *geom, 16, 512)
+    assert (m.S_cmp, m.S_sel) == (9, 3)
+    rng = np.random.default_rng([S, h, D])
+    Q = rng.standard_normal((B, S, G, h, D), dtype=np.float32)
+    Kc = rng.standard_normal((B, G, m.S_cmp, D), dtype=np.float32)
+    Qd, Kd = dev(Q), dev(Kc)
+    cptr, crows, cvals = m.device_csc(Qd.device)
+    L = _lib.lib()
+    dt = _DT[torch.float32]
+    full = L.nsa_sel_scores_rows_workspace(B, S, G, h, D, m.S_cmp, m.S_sel, *geom, dt, 1, 0)
+    three_rows = 3 * h * m.S_cmp * 4
+    assert full >= B * S * G * h * m.S_cmp * 4 > three_rows
+    got = []
+    for nbytes in (full, three_rows):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+        p_grp = torch.full((B, S, G, m.S_sel), float("nan"), dtype=torch.float32, device="cuda")
+        rc = L.nsa_sel_scores_rows(Qd.data_ptr(), Kd.data_ptr(), p_grp.data_ptr(), B, S, G, h, D, m.S_cmp, G * m.S_cmp * D, m.S_cmp * D, D,
+                                   cptr.data_ptr(), crows.data_ptr(), cvals.data_ptr(), m.S_sel, *geom, 0, 1, dt, 0.0, 0, 0, ws.data_ptr(), nbytes,
+                                   _stream(Qd.device))
+        _lib.check(rc, "nsa_sel_scores_rows")
+        got.append(p_grp)
+    assert torch.equal(got[0], got[1])
+    ref = orc.map_pcmp_to_pslc_and_pgrp(orc.compute_pcmp_all(Q, Kc, 1.0 / np.sqrt(D)), mo)[1]
+    assert np.abs(got[0].cpu().numpy() - ref).max() < 2e-6
