@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/nsa_sel_hip.h"
+#include "layer_fused.hpp"
 #include "sel_attn_params.hpp"
 #include "sel_scores_params.hpp"
 
@@ -37,6 +38,7 @@ struct Config {
     hipStream_t stream;
 };
 static std::vector<Config> g_config;
+static std::function<void(int, const void *, void **)> g_on_launch;  // when set: sees every launch (index, host function, arguments)
 
 extern "C" {
 __attribute__((visibility("default"))) hipError_t hipMalloc(void **p, size_t n) {
@@ -82,13 +84,14 @@ __attribute__((visibility("default"))) hipError_t __hipPopCallConfiguration(dim3
     *grid = c.grid; *block = c.block; *shmem = c.shmem; *stream = c.stream;
     return hipSuccess;
 }
-__attribute__((visibility("default"))) hipError_t hipLaunchKernel(const void *, dim3 grid, dim3 block, void **args, size_t shmem, hipStream_t) {
+__attribute__((visibility("default"))) hipError_t hipLaunchKernel(const void *fn, dim3 grid, dim3 block, void **args, size_t shmem, hipStream_t) {
     const int i = g_launches++;
     char s[96];
     snprintf(s, sizeof(s), "%u,%u,%u/%u,%u,%u/%zu", grid.x, grid.y, grid.z, block.x, block.y, block.z, shmem);
     g_geom.push_back(s);
     for (Peek &p : g_peeks)
         if (p.launch == i) memcpy(p.bytes.data(), args[p.arg], p.bytes.size());
+    if (g_on_launch) g_on_launch(i, fn, args);
     if (i == g_refuse_at) return g_last = REFUSED;
     return hipSuccess;
 }
@@ -306,6 +309,68 @@ static void run_args(const std::string &label, const std::function<int()> &call,
             o += ", " + quoted(of[k]->key) + ": " + of[k]->print(g_peeks[k].bytes.data());
         }
         return o + (g_peeks.empty() ? "]" : "}]");
+    });
+}
+
+// ---- the few-row projection family (layer_fused.hip: the launchers linear_small* and qkv_rope_append*).  walks `call` like run(), then calls
+// it once more and prints, for every launch of the family, what tells its route:
+//   "kernel": the ordinal of the launched host function among the family's functions seen so far -- two launches share a template instance
+//             (all-loads-first chunks NC, weight rows per wave, 4 or 8 MFMA waves) exactly when they share an ordinal;
+//   the operand the launch reads and whether norm weights ride along, M, N, K, and the epilogue's or the mix's operands.
+// The VALU kernels take (A policy, W, M, N, K, epilogue policy), the MFMA kernel (RopeAppendParams, X, W, out, M, N, K, epi, res, mix).
+// "linear_small_mix" names a launch of either: the weights are argument 1 of the VALU kernels and argument 2 of the MFMA kernel.
+static std::vector<const void *> g_kernels;
+static void run_proj(const std::string &label, const std::function<int()> &call) {
+    struct RowsArg { const void *A, *norm_w; float eps; };
+    struct MixArg { const void *Oc, *Os, *Ow, *gates; int G; };
+    struct EpiArg { const void *out, *res; int epi, N; };
+    struct MfmaMixArg { const void *Os, *Ow, *gates; int G; };
+    run(label.c_str(), call, [&] {
+        std::string o;
+        g_on_launch = [&](int i, const void *fn, void **a) {
+            auto get = [&](int k, auto v) {
+                memcpy(&v, a[k], sizeof(v));
+                return v;
+            };
+            const std::string name = i < (int)g_names.size() ? g_names[i] : "";
+            const bool qkv = name.rfind("qkv_rope_append", 0) == 0, mix = name == "linear_small_mix launch";
+            if (!qkv && name.rfind("linear_small", 0) != 0) return;
+            size_t ord = 0;
+            while (ord < g_kernels.size() && g_kernels[ord] != fn) ++ord;
+            if (ord == g_kernels.size()) g_kernels.push_back(fn);
+            const bool mfma = name.find("mfma") != std::string::npos || (mix && where(get(1, (const void *)nullptr)).rfind("W_", 0) != 0);
+            Obj e;
+            e.i("launch", i).i("kernel", (long long)ord);
+            const int m0 = mfma ? 4 : 2;  // M, N, K
+            if (mfma) {
+                const MfmaMixArg x = get(9, MfmaMixArg{});
+                e.p("A", get(1, (const void *)nullptr)).p("norm_w", nullptr).p("W", get(2, (const void *)nullptr));
+                if (mix) e.p("Os", x.Os).p("Ow", x.Ow).p("gates", x.gates).i("G", x.G);
+            } else if (mix) {
+                const MixArg x = get(0, MixArg{});
+                e.p("A", x.Oc).p("norm_w", nullptr).p("W", get(1, (const void *)nullptr)).p("Os", x.Os).p("Ow", x.Ow).p("gates", x.gates).i("G", x.G);
+            } else {
+                const RowsArg x = get(0, RowsArg{});
+                e.p("A", x.A).p("norm_w", x.norm_w).p("W", get(1, (const void *)nullptr));
+                if (x.norm_w) e.f("eps", x.eps);
+            }
+            e.i("M", get(m0, 0)).i("N", get(m0 + 1, 0)).i("K", get(m0 + 2, 0));
+            if (qkv) {
+                const nsa::RopeAppendParams P = get(mfma ? 0 : 5, nsa::RopeAppendParams{});
+                e.p("proj", P.proj).p("Q_out", P.Q_out).i("B", P.B).i("S", P.S).i("t0", P.t0);
+            } else if (mfma) {
+                e.p("out", get(3, (const void *)nullptr)).i("epi", get(7, 0)).p("res", get(8, (const void *)nullptr));
+            } else {
+                const EpiArg x = get(5, EpiArg{});
+                e.p("out", x.out).i("epi", x.epi).p("res", x.res);
+            }
+            o += (o.empty() ? "" : ", ") + e.str();
+        };
+        g_refuse_at = -1;
+        g_launches = 0;
+        call();
+        g_on_launch = nullptr;
+        return "\"proj\": [" + o + "]";
     });
 }
 
@@ -662,6 +727,76 @@ int main(int argc, char **argv) {
     set_tuning("DECODE_STEP", 1);
     L.Dk = L.Dv = 128;
     run_step("layer_decode_rows/D128_t100_S4", [&] { return layer_rows(100, 4); });
+
+    // ---- the few-row projection family: the smallest shapes on each side of every branch of its route
+    L.Dk = L.Dv = 64;
+    void *A_lin = dev(MB), *W_lin = dev(MB), *out_lin = dev(MB), *res_lin = dev(MB);
+    nsa_block_desc Bk{};
+    Bk.attn = L;
+    Bk.norm1_w = dev(MB); Bk.norm2_w = dev(MB); Bk.mlp_w1 = dev(8 * MB); Bk.mlp_w2 = dev(8 * MB); Bk.mlp_hidden = 3072; Bk.norm_eps = 1e-5f;
+    int32_t *tokens = (int32_t *)dev(MB), *next_tokens = (int32_t *)dev(MB);
+    void *embed = dev(8 * MB), *norm_f_w = dev(MB), *lm_head = dev(8 * MB), *logits = dev(MB);
+    g_named.insert(g_named.end(), {{"A", A_lin, MB}, {"W_lin", W_lin, MB}, {"out", out_lin, MB}, {"res", res_lin, MB}, {"x", x, MB}, {"y", y, MB},
+                                   {"W_qkv", L.W_qkv, 4 * MB}, {"W_out", L.W_out, 4 * MB}, {"norm1_w", Bk.norm1_w, MB}, {"norm2_w", Bk.norm2_w, MB},
+                                   {"W_fc1", Bk.mlp_w1, 8 * MB}, {"W_fc2", Bk.mlp_w2, 8 * MB}, {"norm_f_w", norm_f_w, MB}, {"W_lm", lm_head, 8 * MB},
+                                   {"logits", logits, MB}});
+    auto lin_fn = NSA_FN(nsa_linear_small);
+    auto lin = [&](int M, int N, int K, int dtype = NSA_DT_BF16, int epi = 0, size_t a_off = 0) {
+        const std::string label = std::string("linear_small/") + (dtype == NSA_DT_F32 ? "f32_" : "") + "M" + std::to_string(M) + "_N" + std::to_string(N) + "_K" +
+                                  std::to_string(K) + (epi ? "_epi" + std::to_string(epi) : "") + (a_off ? "_A_2_bytes_off" : "");
+        run_proj(label, [&] { return lin_fn(off(A_lin, a_off), W_lin, out_lin, M, N, K, dtype, epi, epi == 2 ? res_lin : nullptr, nullptr); });
+    };
+    const int few[][2] = {{40, 8}, {37, 520}, {36, 1032}, {36, 3072}, {36, 4096}, {36, 4104}, {4097, 8}, {4100, 1000}, {4100, 1536}};
+    for (int M : {1, 2})
+        for (const auto &nk : few) lin(M, nk[0], nk[1]);
+    lin(2, 37, 520, dt, 0, 2);
+    lin(2, 4100, 1000, dt, 0, 2);
+    lin(1, 36, 1032, NSA_DT_F32);
+    lin(2, 4100, 1000, NSA_DT_F32);
+    lin(5, 37, 520, NSA_DT_F32);
+    lin(3, 40, 64);
+    lin(3, 40, 40);
+    lin(3, 40, 64, dt, 0, 2);
+    lin(9, 36, 2016);
+    lin(9, 36, 2048);
+    lin(70, 37, 1024);
+    for (int epi : {1, 2}) {  // (epi 0: above) the all-loads-first form, the chunk loop, the MFMA form
+        lin(1, 37, 520, dt, epi);
+        lin(1, 36, 4104, dt, epi);
+        lin(3, 40, 64, dt, epi);
+    }
+    lin(0, 40, 8);
+    lin(1, 0, 8);
+
+    // the block and the model step (m7c block: dim 768, hidden 3072): from three rows on both norms are launches of their own
+    auto block_fn = NSA_FN(nsa_block_decode_step);
+    auto block = [&](const nsa_block_desc &b, int B_, void *x_) {
+        kv.B = B_;
+        return block_fn(&b, &kv, x_, y, 100, csc_ptr, csc_rows, csc_vals, S_sel_max, nullptr, nullptr, ws, 64 * MB, nullptr);
+    };
+    for (int B_ : {1, 2, 3}) run_proj("block_decode_step/B" + std::to_string(B_), [&] { return block(Bk, B_, x); });
+    run_proj("block_decode_step/B1_x_2_bytes_off", [&] { return block(Bk, 1, off(x, 2)); });
+    nsa_block_desc Bk776 = Bk;  // K % 32 != 0: no MFMA form, the chunk loop folds the norms at three rows
+    Bk776.attn.dim = 776;
+    run_proj("block_decode_step/dim776_B3", [&] { return block(Bk776, 3, x); });
+    auto model_fn = NSA_FN(nsa_model_decode_step);
+    const nsa_block_desc two[2] = {Bk, Bk};
+    for (int vocab : {131, 4100})
+        for (int B_ : {1, 3})
+            for (int32_t *next : {(int32_t *)nullptr, next_tokens})
+                run_proj("model_decode_step/vocab" + std::to_string(vocab) + "_B" + std::to_string(B_) + (next ? "_next_tokens" : ""), [&] {
+                    kv.B = B_;
+                    const nsa_kv_desc kvs[2] = {kv, kv};
+                    return model_fn(two, kvs, 2, tokens, embed, norm_f_w, lm_head, vocab, logits, next, 100, csc_ptr, csc_rows, csc_vals, S_sel_max, ws, 64 * MB, nullptr);
+                });
+    // the layer step by batch: the mix rides in the output projection up to 32 rows (DECODE_BAND 3: at any batch)
+    for (int B_ : {2, 3, 32, 33})
+        run_proj("layer_decode_step/B" + std::to_string(B_) + "_t100", [&] { kv.B = B_; return decode(100); });
+    set_tuning("DECODE_BAND", 3);
+    run_proj("layer_decode_step/B33_t100_DECODE_BAND_3", [&] { kv.B = 33; return decode(100); });
+    set_tuning("DECODE_BAND", -1);
+    for (int B_ : {1, 2})
+        run_proj("layer_decode_rows/B" + std::to_string(B_) + "_t100_S2", [&] { kv.B = B_; return layer_rows(100, 2); });
     printf("\n}\n");
     return 0;
 }

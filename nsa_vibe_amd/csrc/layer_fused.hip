@@ -701,151 +701,122 @@ __global__ __launch_bounds__(NWV * 64, 2) void linear_mfma_kernel(RopeAppendPara
     }
 }
 
-// the VALU forms of out = A . W^T (norm_w: RMSNorm(A) folded in)
-static int launch_linear_small_valu(const void *A, const void *W, void *out, int M, int N, int K, int dtype, int epi, const void *res,
-                                    const void *norm_w, float eps, hipStream_t st) {
-    const bool fast = dtype != NSA_DT_F32 && M <= 2 && K >= 8 && K % 8 == 0 && K <= 4096 && (((uintptr_t)A | (uintptr_t)W) % 16 == 0) &&
-                      (!norm_w || (uintptr_t)norm_w % 16 == 0);
-    const int nc = (K + 511) / 512;
-    const bool g4 = fast ? N >= 4096 && nc <= 2 : M <= 2 && N >= 4096;  // four weight rows per wave
-    const dim3 grid(g4 ? (unsigned)((N + 15) / 16) : (unsigned)((N + 3) / 4));
-    with_elt(dtype, [&](auto t) {
-        using T = decltype(t);
-        const RowsA<T> a{(const T *)A, (const T *)norm_w, eps};
-        const LinearEpi<T> e{(T *)out, (const T *)res, epi, N};
-        auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, a, (const T *)W, M, N, K, e); };
-        if constexpr (sizeof(T) == 2) {
-            if (fast) {
-                if (g4) go(proj_fast_kernel<T, 2, 4, RowsA<T>, LinearEpi<T>>);
-                else if (nc <= 2) go(proj_fast_kernel<T, 2, 1, RowsA<T>, LinearEpi<T>>);
-                else if (nc <= 4) go(proj_fast_kernel<T, 4, 1, RowsA<T>, LinearEpi<T>>);
-                else if (nc <= 6) go(proj_fast_kernel<T, 6, 1, RowsA<T>, LinearEpi<T>>);
-                else go(proj_fast_kernel<T, 8, 1, RowsA<T>, LinearEpi<T>>);
-                return;
-            }
+// ---- the family's route: the only place that knows the bounds of its forms.  The launchers below switch on the answer, the callers read
+// fold_norm (the block and the model step) and form (the mix) from it.
+ProjRoute proj_route(const LinearCall &c, ProjKind kind) {
+    const bool plain = kind == PROJ_PLAIN, mix = kind == PROJ_MIX, b16 = c.dtype == NSA_DT_BF16 || c.dtype == NSA_DT_F16;
+    const bool aligned = (((uintptr_t)c.A | (uintptr_t)c.W | (uintptr_t)c.Os | (uintptr_t)c.Ow) % 16 == 0);  // (Os, Ow: null without a mix)
+    ProjRoute r{};
+    // the mix: 16-bit whole k-steps per group; rows 1-2 as VALU dot products of at most 2048 elements, from 3 on the MFMA kernel
+    if (mix && !(b16 && aligned && c.M >= 1 && c.N >= 1 && c.G >= 1 && c.K % (32 * c.G) == 0 && (c.M >= 3 || c.K <= 2048))) return r;
+    if (b16 && aligned && c.M >= 3 && c.K % 32 == 0) {
+        r.form = PROJ_MFMA;
+        r.waves = plain && c.K >= 2048 ? 8 : 4;
+        r.grid = dim3((unsigned)((c.N + 15) / 16), (unsigned)((c.M + 63) / 64));
+        return r;
+    }
+    // all-loads-first: 1-2 rows of 16-byte aligned 16-bit operands with K <= 512 NC, NC <= 8 (with a RoPE epilogue or a mix: 4); the rows
+    // call stays with the chunk loop
+    const int nc = (c.K + 511) / 512;
+    const bool fast = mix || (kind != PROJ_ROPE_ROWS && b16 && aligned && c.M <= 2 && c.K >= 8 && c.K % 8 == 0 && c.K <= (plain ? 4096 : 2048) &&
+                              (uintptr_t)c.norm_w % 16 == 0);
+    const bool g4 = plain && c.N >= 4096 && (fast ? nc <= 2 : c.M <= 2);  // four weight rows per wave
+    r.form = fast ? PROJ_FAST : PROJ_LOOP;
+    r.nc = 2 * ((nc + 1) / 2);  // tiers of 2, 4, 6, 8 chunks
+    r.cw = plain ? (g4 ? 4 : 1) : mix ? 1 : 2;
+    r.grid = dim3((unsigned)((c.N + 4 * r.cw - 1) / (4 * r.cw)));
+    r.fold_norm = !mix;
+    return r;
+}
+
+// one launch of a VALU form as the route says: proj_fast_kernel with r.nc of the tiers NCS the policy pair is built for, else the chunk loop
+template <typename T, int CW, int... NCS, typename AOp, typename Epi>
+static void launch_proj_valu(const ProjRoute &r, const LinearCall &c, const AOp &a, const Epi &e) {
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, r.grid, dim3(256), 0, c.st, a, (const T *)c.W, c.M, c.N, c.K, e); };
+    if constexpr (sizeof(T) == 2) {
+        if (r.form == PROJ_FAST) {
+            ((r.nc == NCS ? go(proj_fast_kernel<T, NCS, CW, AOp, Epi>) : void()), ...);
+            return;
         }
-        if (g4) go(proj_loop_kernel<T, 4, RowsA<T>, LinearEpi<T>>);
-        else go(proj_loop_kernel<T, 1, RowsA<T>, LinearEpi<T>>);
-    });
-    if (fast) NSA_LAUNCH_CHECK("linear_small(fast)");
-    else NSA_LAUNCH_CHECK("linear_small");
-    return NSA_OK;
+    }
+    if constexpr (std::is_same_v<AOp, RowsA<T>>) go(proj_loop_kernel<T, CW, AOp, Epi>);
 }
-
-static bool linear_mfma_ok(int dtype, int M, int N, int K, const void *X, const void *W) {
-    return (dtype == NSA_DT_BF16 || dtype == NSA_DT_F16) && M >= 3 && K % 32 == 0 &&
-           (((uintptr_t)X | (uintptr_t)W) % 16 == 0);
-}
-template <bool ROPE, bool MIX = false, int NWV = 4, bool ROWS = false>
-static void launch_linear_mfma(const RopeAppendParams &P, const void *X, const void *W, void *out, int M, int N, int K, int dtype, int epi,
-                               const void *res, const LinearMixArgs &mx, hipStream_t st) {
-    const dim3 grid((unsigned)((N + 15) / 16), (unsigned)((M + 63) / 64));
-    with_elt<false>(dtype, [&](auto t) {
+template <bool ROPE, bool MIX, int NWV, bool ROWS>
+static void launch_linear_mfma(const RopeAppendParams &P, const ProjRoute &r, const LinearCall &c) {
+    with_elt<false>(c.dtype, [&](auto t) {
         using T = decltype(t);
-        hipLaunchKernelGGL((linear_mfma_kernel<T, ROPE, MIX, NWV, ROWS>), grid, dim3(NWV * 64), 0, st, P, (const T *)X, (const T *)W, (T *)out, M, N, K,
-                           epi, (const T *)res, mx);
+        hipLaunchKernelGGL((linear_mfma_kernel<T, ROPE, MIX, NWV, ROWS>), r.grid, dim3(NWV * 64), 0, c.st, P, (const T *)c.A, (const T *)c.W, (T *)c.out, c.M,
+                           c.N, c.K, c.epi, (const T *)c.res, LinearMixArgs{c.Os, c.Ow, c.gates, c.G});
     });
 }
 
-int launch_linear_small_epi(const void *A, const void *W, void *out, int M, int N, int K, int dtype, int epi, const void *res, hipStream_t st) {
-    if (linear_mfma_ok(dtype, M, N, K, A, W)) {
-        if (K >= 2048) launch_linear_mfma<false, false, 8>({}, A, W, out, M, N, K, dtype, epi, res, {}, st);
-        else launch_linear_mfma<false>({}, A, W, out, M, N, K, dtype, epi, res, {}, st);
+int launch_linear_small_epi(const LinearCall &c) {
+    const ProjRoute r = proj_route(c, PROJ_PLAIN);
+    if (r.form == PROJ_MFMA) {
+        NSA_CHECK_ARG(c.norm_w == nullptr, "linear_small: the MFMA form takes normalised input");  // (launch_linear_normed sees to it)
+        if (r.waves == 8) launch_linear_mfma<false, false, 8, false>({}, r, c);
+        else launch_linear_mfma<false, false, 4, false>({}, r, c);
         NSA_LAUNCH_CHECK("linear_small(mfma)");
         return NSA_OK;
     }
-    return launch_linear_small_valu(A, W, out, M, N, K, dtype, epi, res, nullptr, 0.f, st);
+    with_elt(c.dtype, [&](auto t) {
+        using T = decltype(t);
+        const RowsA<T> a{(const T *)c.A, (const T *)c.norm_w, c.eps};
+        const LinearEpi<T> e{(T *)c.out, (const T *)c.res, c.epi, c.N};
+        if (r.cw == 4) launch_proj_valu<T, 4, 2>(r, c, a, e);
+        else launch_proj_valu<T, 1, 2, 4, 6, 8>(r, c, a, e);
+    });
+    if (r.form == PROJ_FAST) NSA_LAUNCH_CHECK("linear_small(fast)");
+    else NSA_LAUNCH_CHECK("linear_small");
+    return NSA_OK;
 }
-// RMSNorm(x) folded into the projection (rows <= 8: the VALU kernel); returns NSA_ERR_INVALID without side effects when not applicable
-bool linear_small_can_fold_norm(int dtype, int M, int N, int K, const void *A, const void *W) { return !linear_mfma_ok(dtype, M, N, K, A, W); }
-bool linear_small_mix_supported(int dtype, int M, int N, int K, int G, const void *Oc, const void *Os, const void *Ow, const void *W) {
-    return (dtype == NSA_DT_BF16 || dtype == NSA_DT_F16) && M >= 1 && G >= 1 && K % (32 * G) == 0 && N >= 1 && (M >= 3 || K <= 2048) &&
-           (((uintptr_t)Oc | (uintptr_t)Os | (uintptr_t)Ow | (uintptr_t)W) % 16 == 0);
+int launch_linear_normed(const LinearCall &c, void *scratch) {
+    if (proj_route(c, PROJ_PLAIN).fold_norm) return launch_linear_small_epi(c);
+    if (int rc = launch_rmsnorm_rows(c.A, c.norm_w, scratch, c.M, c.K, c.eps, c.dtype, c.st)) return rc;
+    LinearCall p = c;
+    p.A = scratch;
+    p.norm_w = nullptr;
+    return launch_linear_small_epi(p);
 }
 
-// rows 1-2: the VALU dot products (all-loads-first form); from 3 on: the MFMA kernel (what launch_linear_small_epi picks for a ready-made A)
-int launch_linear_small_mix(const void *Oc, const void *Os, const void *Ow, const float *gates, const void *W, void *out, int M, int N, int K, int G,
-                            int dtype, int epi, const void *res, hipStream_t st) {
-    NSA_CHECK_ARG(linear_small_mix_supported(dtype, M, N, K, G, Oc, Os, Ow, W) && gates && out, "linear_small_mix: unsupported shape");
-    if (linear_mfma_ok(dtype, M, N, K, Oc, W)) {
-        launch_linear_mfma<false, true>({}, Oc, W, out, M, N, K, dtype, epi, res, LinearMixArgs{Os, Ow, gates, G}, st);
+int launch_linear_small_mix(const LinearCall &c) {
+    const ProjRoute r = proj_route(c, PROJ_MIX);
+    NSA_CHECK_ARG(r.form != PROJ_NONE && c.gates && c.out, "linear_small_mix: unsupported shape");
+    if (r.form == PROJ_MFMA) {
+        launch_linear_mfma<false, true, 4, false>({}, r, c);
     } else {
-        NSA_CHECK_ARG(M <= 2 && K <= 2048, "linear_small_mix: the VALU form takes 1-2 rows of at most 2048 elements");
-        with_elt<false>(dtype, [&](auto t) {
+        with_elt<false>(c.dtype, [&](auto t) {
             using T = decltype(t);
-            const MixA<T> a{(const T *)Oc, (const T *)Os, (const T *)Ow, gates, G};
-            const LinearEpi<T> e{(T *)out, (const T *)res, epi, N};
-            auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, a, (const T *)W, M, N, K, e); };
-            if (K <= 1024) go(proj_fast_kernel<T, 2, 1, MixA<T>, LinearEpi<T>>);
-            else go(proj_fast_kernel<T, 4, 1, MixA<T>, LinearEpi<T>>);
+            launch_proj_valu<T, 1, 2, 4>(r, c, MixA<T>{(const T *)c.A, (const T *)c.Os, (const T *)c.Ow, c.gates, c.G},
+                                         LinearEpi<T>{(T *)c.out, (const T *)c.res, c.epi, c.N});
         });
     }
     NSA_LAUNCH_CHECK("linear_small_mix");
     return NSA_OK;
 }
 
-int launch_linear_small_norm(const void *A, const void *W, void *out, int M, int N, int K, int dtype, int epi, const void *res, const void *norm_w,
-                             float eps, hipStream_t st) {
-    return launch_linear_small_valu(A, W, out, M, N, K, dtype, epi, res, norm_w, eps, st);
-}
-int launch_linear_small(const void *A, const void *W, void *out, int M, int N, int K, int dtype, hipStream_t st) {
-    return launch_linear_small_epi(A, W, out, M, N, K, dtype, 0, nullptr, st);
-}
-
-// norm_w != nullptr: RMSNorm(X) is folded into the projection (only taken by the VALU form, i.e. when qkv_can_fold_norm())
-bool qkv_can_fold_norm(const RopeAppendParams &P, const void *X, const void *W, int K, int dtype) {
-    const int NT = P.G * P.h * P.Dk + 3 * P.G * P.Dk + 3 * P.G * P.Dv;
-    return !linear_mfma_ok(dtype, P.B, NT, K, X, W);
-}
-// P.S consecutive tokens per sequence (the layer's rows call): X [B S, K], row m = b S + s at position t0 + s.  The MFMA form where the
-// projection of B S rows takes it, else the chunk loop; the all-loads-first form stays with the single step
-static int launch_qkv_rope_append_rows(const RopeAppendParams &P, const void *X, const void *W, int K, int dtype, hipStream_t st,
-                                       const void *norm_w, float norm_eps) {
-    const int NT = P.G * P.h * P.Dk + 3 * P.G * P.Dk + 3 * P.G * P.Dv, M = P.B * P.S;
+// c.N = the columns P maps (qkv_cols); c.norm_w: RMSNorm(c.A) folded in where the caller read fold_norm from this call's route
+int launch_qkv_rope_append(const RopeAppendParams &P, const LinearCall &c, bool rows) {
     NSA_CHECK_ARG(P.S >= 1 && P.S <= RopeRowsEpi<float>::MAX_S, "qkv_rope_append: 1 to 16 tokens per sequence");
-    if (linear_mfma_ok(dtype, M, NT, K, X, W)) {
-        NSA_CHECK_ARG(norm_w == nullptr, "qkv_rope_append: the MFMA form takes normalised input");
-        launch_linear_mfma<true, false, 4, true>(P, X, W, nullptr, M, NT, K, dtype, 0, nullptr, {}, st);
-        NSA_LAUNCH_CHECK("qkv_rope_append(rows, mfma)");
-        return NSA_OK;
-    }
-    with_elt(dtype, [&](auto t) {
-        using T = decltype(t);
-        const RowsA<T> a{(const T *)X, (const T *)norm_w, norm_eps};
-        const RopeRowsEpi<T> e{P};
-        hipLaunchKernelGGL((proj_loop_kernel<T, 2, RowsA<T>, RopeRowsEpi<T>>), dim3((unsigned)((NT / 2 + 3) / 4)), dim3(256), 0, st, a, (const T *)W, M,
-                           NT, K, e);
-    });
-    NSA_LAUNCH_CHECK("qkv_rope_append(rows)");
-    return NSA_OK;
-}
-int launch_qkv_rope_append(const RopeAppendParams &P, const void *X, const void *W, int K, int dtype, hipStream_t st, const void *norm_w,
-                           float norm_eps, bool rows) {
-    if (rows) return launch_qkv_rope_append_rows(P, X, W, K, dtype, st, norm_w, norm_eps);
-    const int NT = P.G * P.h * P.Dk + 3 * P.G * P.Dk + 3 * P.G * P.Dv;
-    if (linear_mfma_ok(dtype, P.B, NT, K, X, W)) {
-        NSA_CHECK_ARG(norm_w == nullptr, "qkv_rope_append: the MFMA form takes normalised input");
-        launch_linear_mfma<true>(P, X, W, nullptr, P.B, NT, K, dtype, 0, nullptr, {}, st);
-        NSA_LAUNCH_CHECK("qkv_rope_append(mfma)");
-        return NSA_OK;
-    }
-    const bool fast = dtype != NSA_DT_F32 && P.B <= 2 && P.S == 1 && K >= 8 && K % 8 == 0 && K <= 2048 &&
-                      (((uintptr_t)X | (uintptr_t)W) % 16 == 0) && (!norm_w || (uintptr_t)norm_w % 16 == 0);
-    with_elt(dtype, [&](auto t) {
-        using T = decltype(t);
-        const RowsA<T> a{(const T *)X, (const T *)norm_w, norm_eps};
-        const RopeEpi<T> e{P};
-        auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)((NT / 2 + 3) / 4)), dim3(256), 0, st, a, (const T *)W, P.B, NT, K, e); };
-        if constexpr (sizeof(T) == 2) {
-            if (fast) {
-                if (K <= 1024) go(proj_fast_kernel<T, 2, 2, RowsA<T>, RopeEpi<T>>);
-                else go(proj_fast_kernel<T, 4, 2, RowsA<T>, RopeEpi<T>>);
-                return;
-            }
+    const ProjRoute r = proj_route(c, rows ? PROJ_ROPE_ROWS : PROJ_ROPE);
+    if (r.form == PROJ_MFMA) {
+        if (rows) {
+            launch_linear_mfma<true, false, 4, true>(P, r, c);
+            NSA_LAUNCH_CHECK("qkv_rope_append(rows, mfma)");
+        } else {
+            launch_linear_mfma<true, false, 4, false>(P, r, c);
+            NSA_LAUNCH_CHECK("qkv_rope_append(mfma)");
         }
-        go(proj_loop_kernel<T, 2, RowsA<T>, RopeEpi<T>>);
+        return NSA_OK;
+    }
+    with_elt(c.dtype, [&](auto t) {
+        using T = decltype(t);
+        const RowsA<T> a{(const T *)c.A, (const T *)c.norm_w, c.eps};
+        if (rows) launch_proj_valu<T, 2>(r, c, a, RopeRowsEpi<T>{P});
+        else launch_proj_valu<T, 2, 2, 4>(r, c, a, RopeEpi<T>{P});
     });
-    if (fast) NSA_LAUNCH_CHECK("qkv_rope_append(fast)");
+    if (rows) NSA_LAUNCH_CHECK("qkv_rope_append(rows)");
+    else if (r.form == PROJ_FAST) NSA_LAUNCH_CHECK("qkv_rope_append(fast)");
     else NSA_LAUNCH_CHECK("qkv_rope_append");
     return NSA_OK;
 }

@@ -39,22 +39,42 @@ struct DecodeFinishParams {
     int h, Dk, Dv, Hd;
     float tau;
 };
-bool qkv_can_fold_norm(const RopeAppendParams &P, const void *X, const void *W, int K, int dtype);
-// rows: P.S (1 to 16) consecutive tokens per sequence, row b P.S + s of X at position P.t0 + s (the layer's rows call; false: P.S = 1, the
-// single step, with its all-loads-first form)
-int launch_qkv_rope_append(const RopeAppendParams &P, const void *X, const void *W, int K, int dtype, hipStream_t st, const void *norm_w = nullptr,
-                           float norm_eps = 0.f, bool rows = false);
-bool linear_small_can_fold_norm(int dtype, int M, int N, int K, const void *A, const void *W);
-int launch_linear_small_norm(const void *A, const void *W, void *out, int M, int N, int K, int dtype, int epi, const void *res, const void *norm_w,
-                             float eps, hipStream_t st);
+// One few-row projection out [M,N] = A [M,K] . W [N,K]^T: what nsa_linear_small and the layer calls hand to every launcher of the family
+// (layer_fused.hip).  Filled once by aggregate initialisation: the fields after `st` are optional groups and stay zero when left out.
+struct LinearCall {
+    const void *A, *W;
+    void *out;
+    int M, N, K, dtype;
+    int epi;  // 0 none, 1 silu, 2 + res[M,N]
+    const void *res;
+    hipStream_t st;
+    const void *norm_w;  // RMSNorm(A) with these weights and eps folded into the projection (a route with fold_norm only)
+    float eps;
+    const void *Os, *Ow;  // the mix (launch_linear_small_mix): A = O_cmp, these O_sel and O_win, the row gates [M G][3]
+    const float *gates;
+    int G;
+};
+// What runs a LinearCall under an epilogue kind -- the family's one route decision (proj_route): the MFMA kernel with 4 or 8 waves, the
+// all-loads-first VALU form with nc chunks in flight, or the chunk loop; cw = weight rows per wave of the VALU forms.
+enum ProjKind { PROJ_PLAIN, PROJ_ROPE, PROJ_ROPE_ROWS, PROJ_MIX };
+enum ProjForm { PROJ_NONE, PROJ_MFMA, PROJ_FAST, PROJ_LOOP };  // PROJ_NONE: a mix the projection does not take
+struct ProjRoute {
+    ProjForm form;
+    int waves, nc, cw;
+    dim3 grid;
+    bool fold_norm;  // the form takes c.norm_w (the MFMA kernel reads normalised rows)
+};
+ProjRoute proj_route(const LinearCall &c, ProjKind kind);
+// epilogue of the fused QKV projection: every column pair rotated and appended at its row's position.  rows: P.S (1 to 16) consecutive
+// tokens per sequence, row b P.S + s of c.A at position P.t0 + s (the layer's rows call; false: P.S = 1, the single step)
+int launch_qkv_rope_append(const RopeAppendParams &P, const LinearCall &c, bool rows);
+int launch_linear_small_epi(const LinearCall &c);
+// c.norm_w set: one launch where the route folds the norm, else RMSNorm(A) into scratch [M,K] and the projection from there
+int launch_linear_normed(const LinearCall &c, void *scratch);
 int launch_decode_finish(const DecodeFinishParams &P, int dtype, hipStream_t st);
-// output projection of a decode step fed by the three branch outputs and the row gates (few rows: M <= 8): out = mix(O_cmp, O_sel, O_win) . W^T
-bool linear_small_mix_supported(int dtype, int M, int N, int K, int G, const void *Oc, const void *Os, const void *Ow, const void *W);
-int launch_linear_small_mix(const void *Oc, const void *Os, const void *Ow, const float *gates, const void *W, void *out, int M, int N, int K, int G,
-                            int dtype, int epi, const void *res, hipStream_t st);
-int launch_linear_small(const void *A, const void *W, void *out, int M, int N, int K, int dtype, hipStream_t st);
-// epi: 0 none, 1 silu, 2 + res[M,N]
-int launch_linear_small_epi(const void *A, const void *W, void *out, int M, int N, int K, int dtype, int epi, const void *res, hipStream_t st);
+// output projection of a decode step fed by the three branch outputs and the row gates: out = mix(O_cmp, O_sel, O_win) . W^T
+inline bool linear_small_mix_supported(const LinearCall &c) { return proj_route(c, PROJ_MIX).form != PROJ_NONE; }
+int launch_linear_small_mix(const LinearCall &c);
 int launch_embed_rows(const int32_t *tokens, const void *embed, void *x, int B, int dim, int vocab, int dtype, hipStream_t st);
 size_t argmax_rows_workspace(int B, int vocab);
 int launch_argmax_rows(const void *logits, int32_t *next, int B, int vocab, int dtype, void *ws, hipStream_t st);

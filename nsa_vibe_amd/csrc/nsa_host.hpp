@@ -141,6 +141,14 @@ inline RopeAppendParams rope_append_params(const nsa_layer_desc *L, const nsa_kv
     return P;
 }
 
+// columns of the fused QKV projection: Q | K_sel | V_sel | K_win | V_win | K_raw | V_raw
+inline int qkv_cols(const nsa_layer_desc *L) { return L->G * L->h * L->Dk + 3 * L->G * L->Dk + 3 * L->G * L->Dv; }
+// that projection of `rows` rows of x as the projection family's block (no out: the launch's RopeAppendParams say where each column goes).
+// The block step reads fold_norm from this call's route and the launcher decides on the same call: the two cannot disagree
+inline LinearCall qkv_call(const nsa_layer_desc *L, const void *x, int rows, const void *norm_w, float eps, void *stream) {
+    return LinearCall{x, L->W_qkv, nullptr, rows, qkv_cols(L), L->dim, L->dtype, 0, nullptr, (hipStream_t)stream, norm_w, eps};
+}
+
 // everything else (split-KV, mapping, fused selector) stays zero: the caller sets what its route needs
 inline SelAttnParams sel_attn_params(const void *Q, const void *K, const void *V, const int32_t *ranges, void *O, float *lse, int64_t R, int S,
                                      int G, int h, int Dk, int Dv, int S_kv, int n, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb,

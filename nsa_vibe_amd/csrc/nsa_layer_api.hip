@@ -29,7 +29,7 @@ int nsa_linear_small(const void *A, const void *W, void *out, int M, int N, int 
     NSA_CHECK_ARG(epilogue >= 0 && epilogue <= 2 && (epilogue != 2 || residual), "linear_small: bad epilogue");
     if (M == 0 || N == 0) return NSA_OK;
     NSA_CHECK_ARG(A && W && out, "linear_small: null pointer");
-    return launch_linear_small_epi(A, W, out, M, N, K, dtype, epilogue, residual, (hipStream_t)stream);
+    return launch_linear_small_epi(LinearCall{A, W, out, M, N, K, dtype, epilogue, residual, (hipStream_t)stream});
 }
 
 int nsa_rmsnorm_rows(const void *x, const void *w, void *y, int M, int dim, float eps, int dtype, void *stream) {
@@ -254,11 +254,10 @@ static DecodeWs decode_ws(const nsa_layer_desc *L, int B1, int S_max, int S = 0)
     const size_t B = (size_t)B1 * (S > 0 ? S : 1);
     const size_t e = esize(L->dtype);
     const size_t NQ = (size_t)L->G * L->h * L->Dk, NO = (size_t)L->G * L->h * L->Dv;
-    const size_t NT = NQ + 3 * (size_t)L->G * L->Dk + 3 * (size_t)L->G * L->Dv;
     const int n_cmp_max = ncmp_of(S_max, L->l, L->d);
     const int S_sel_max = (S_max + L->l_sel - 1) / L->l_sel + 1;
     size_t o = 0;
-    w.proj = o; o += up256(B * NT * e);
+    w.proj = o; o += up256(B * qkv_cols(L) * e);
     w.q = o; o += up256(B * NQ * e);
     w.ocmp = o; o += up256(B * NO * e);
     w.osel = o; o += up256(B * NO * e);
@@ -346,6 +345,12 @@ static SelDecodeCall layer_sel_call(const LayerDecode &D, const CacheStrides &C,
     return c;
 }
 
+// the output projection of the call's rows from the mixed O (+ residual in its epilogue when given)
+static LinearCall out_proj_call(const LayerDecode &D, void *y, const void *residual, void *stream) {
+    const nsa_layer_desc *L = D.L;
+    return LinearCall{D.Omix, L->W_out, y, D.kv->B * D.S, L->dim, L->G * L->h * L->Dv, L->dtype, residual ? 2 : 0, residual, (hipStream_t)stream};
+}
+
 // the finish kernel's block: one pass merges the splits of all three branches, evaluates the gate and mixes (ns / part: set by the branches)
 static DecodeFinishParams decode_finish_params(const LayerDecode &D, float *gates_out) {
     const nsa_layer_desc *L = D.L;
@@ -387,19 +392,19 @@ static int layer_decode_tail(const LayerDecode &D, const CacheStrides &C, Decode
     } else {
         if (int rc = nsa_gate_combine(L, D.Q, D.Ocmp, D.Osel, D.Owin, D.Omix, gates_out, (int64_t)B * S * G, stream)) return rc;
     }
-    return launch_linear_small_epi(D.Omix, L->W_out, y, B * S, L->dim, G * h * Dv, dt, residual ? 2 : 0, residual, st);
+    return launch_linear_small_epi(out_proj_call(D, y, residual, stream));
 }
 
 static int layer_decode_step_impl(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *x, void *y, int t, const int32_t *csc_ptr,
                                   const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out, float *gates_out,
-                                  void *workspace, size_t workspace_bytes, void *stream, const void *residual, const void *norm_w = nullptr,
-                                  float norm_eps = 0.f) {
+                                  void *workspace, size_t workspace_bytes, void *stream, const void *residual, const void *norm_w,
+                                  float norm_eps) {
     LayerDecode D;
     if (int rc = layer_decode_begin("layer_decode_step", L, kv, x, y, t, 1, false, S_sel, workspace, workspace_bytes, &D)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const int dt = L->dtype, B = kv->B, G = L->G, h = L->h, Dk = L->Dk, Dv = L->Dv, NO = G * h * Dv, n_cmp = D.n1;
+    const int dt = L->dtype, B = kv->B, G = L->G, h = L->h, Dk = L->Dk, Dv = L->Dv, n_cmp = D.n1;
     // 1+2. fused QKV projection with RoPE + cache append at position t in its epilogue
-    if (int rc = launch_qkv_rope_append(rope_append_params(L, kv, D.ws + D.W.proj, D.Q, 1, t), x, L->W_qkv, L->dim, dt, st, norm_w, norm_eps)) return rc;
+    if (int rc = launch_qkv_rope_append(rope_append_params(L, kv, D.ws + D.W.proj, D.Q, 1, t), qkv_call(L, x, B, norm_w, norm_eps, stream), false)) return rc;
     // 3. emit a compressed token when a window completes (nsa_attention.py:588-604)
     NSA_CHECK_ARG(n_cmp <= kv->n_cmp_max, "layer_decode_step: compressed cache too small");
     if (n_cmp > D.n0)
@@ -432,19 +437,21 @@ static int layer_decode_step_impl(const nsa_layer_desc *L, const nsa_kv_desc *kv
     F.ns[2] = F.ns[0] = 1;
     // (measured: the mix in the projection wins up to 32 rows -- 43.3 -> 40.5 us at B = 32 -- and loses from 64 on, where every one of the
     // projection's 48 workgroups would redo the mix of all rows: 47.1 -> 50.6 us; DECODE_BAND = 3 takes it at any batch)
-    if (((band_mode < 0 && B <= 32) || band_mode == 3) && F.ns[1] == 1 &&
-        linear_small_mix_supported(dt, B, L->dim, NO, G, D.Ocmp, D.Osel, D.Owin, L->W_out) && Dv == 64)
-        return launch_linear_small_mix(D.Ocmp, D.Osel, D.Owin, gates, L->W_out, y, B, L->dim, NO, G, dt, residual ? 2 : 0, residual, st);
+    const LinearCall out = out_proj_call(D, y, residual, stream);
+    LinearCall mixed = out;
+    mixed.A = D.Ocmp; mixed.Os = D.Osel; mixed.Ow = D.Owin; mixed.gates = gates; mixed.G = G;
+    if (((band_mode < 0 && B <= 32) || band_mode == 3) && F.ns[1] == 1 && Dv == 64 && linear_small_mix_supported(mixed))
+        return launch_linear_small_mix(mixed);
     // 6. split combine + gates + mix, 7. output projection
     if (int rc = launch_decode_finish(F, dt, st)) return rc;
-    return launch_linear_small_epi(D.Omix, L->W_out, y, B, L->dim, NO, dt, residual ? 2 : 0, residual, st);
+    return launch_linear_small_epi(out);
 }
 
 int nsa_layer_decode_step(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *x, void *y, int t, const int32_t *csc_ptr,
                           const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out, float *gates_out,
                           void *workspace, size_t workspace_bytes, void *stream) {
     return layer_decode_step_impl(L, kv, x, y, t, csc_ptr, csc_rows, csc_vals, S_sel, ranges_out, gates_out, workspace, workspace_bytes, stream,
-                                  nullptr);
+                                  nullptr, nullptr, 0.f);
 }
 
 // ------------------------------------------------------------------------------ layer decode step for S consecutive tokens
@@ -483,14 +490,13 @@ static bool layer_decode_rows_measured_ok(int B, int S, int t0) { return S >= 2;
 
 static int layer_decode_rows_impl(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *x, void *y, int t0, int S, const int32_t *csc_ptr,
                                   const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out, float *gates_out,
-                                  void *workspace, size_t workspace_bytes, void *stream, const void *residual, const void *norm_w = nullptr,
-                                  float norm_eps = 0.f) {
+                                  void *workspace, size_t workspace_bytes, void *stream, const void *residual, const void *norm_w,
+                                  float norm_eps) {
     LayerDecode D;
     if (int rc = layer_decode_begin("layer_decode_rows", L, kv, x, y, t0, S, true, S_sel, workspace, workspace_bytes, &D)) return rc;
     NSA_CHECK_ARG(D.n1 <= kv->n_cmp_max, "layer_decode_rows: compressed cache too small");
     // 1. fused QKV projection of the B S rows, each rotated and appended at its own position t0 + s
-    if (int rc = launch_qkv_rope_append(rope_append_params(L, kv, D.ws + D.W.proj, D.Q, S, t0), x, L->W_qkv, L->dim, L->dtype, (hipStream_t)stream, norm_w,
-                                        norm_eps, true))
+    if (int rc = launch_qkv_rope_append(rope_append_params(L, kv, D.ws + D.W.proj, D.Q, S, t0), qkv_call(L, x, kv->B * S, norm_w, norm_eps, stream), true))
         return rc;
     // 2. the compressed tokens whose windows complete inside the call
     if (D.n1 > D.n0)
@@ -518,7 +524,7 @@ int nsa_layer_decode_rows(const nsa_layer_desc *L, const nsa_kv_desc *kv, const 
                           const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out, float *gates_out, void *workspace,
                           size_t workspace_bytes, void *stream) {
     return layer_decode_rows_impl(L, kv, x, y, t0, S, csc_ptr, csc_rows, csc_vals, S_sel, ranges_out, gates_out, workspace, workspace_bytes, stream,
-                                  nullptr);
+                                  nullptr, nullptr, 0.f);
 }
 
 int nsa_layer_decode_rows_plan(const nsa_layer_desc *L, int B, int S, int S_max, int t0, int S_sel, int *launches, int *route) {
@@ -572,22 +578,15 @@ int nsa_block_decode_step(const nsa_block_desc *Bk, const nsa_kv_desc *kv, const
     void *xn = ws + W.xn, *h = ws + W.h, *hn = ws + W.hn, *u = ws + W.u;
     const float eps = Bk->norm_eps > 0.f ? Bk->norm_eps : 1e-6f;
     // small batches: both RMSNorms are folded into the projections that consume them (two launches fewer per block)
-    RopeAppendParams probe{};
-    probe.B = B; probe.G = Bk->attn.G; probe.h = Bk->attn.h; probe.Dk = Bk->attn.Dk; probe.Dv = Bk->attn.Dv;
-    const bool fold1 = qkv_can_fold_norm(probe, x, Bk->attn.W_qkv, dim, dt);
+    const bool fold1 = proj_route(qkv_call(&Bk->attn, x, B, Bk->norm1_w, eps, stream), PROJ_ROPE).fold_norm;
     if (!fold1)
         if (int rc = launch_rmsnorm_rows(x, Bk->norm1_w, xn, B, dim, eps, dt, st)) return rc;
     // h = x + attn(norm1(x)): the residual rides in the output projection's epilogue
     if (int rc = layer_decode_step_impl(&Bk->attn, kv, fold1 ? x : xn, h, t, csc_ptr, csc_rows, csc_vals, S_sel, ranges_out, gates_out,
                                         ws + W.layer, W.layer_bytes, stream, x, fold1 ? Bk->norm1_w : nullptr, eps))
         return rc;
-    if (linear_small_can_fold_norm(dt, B, Bk->mlp_hidden, dim, h, Bk->mlp_w1)) {
-        if (int rc = launch_linear_small_norm(h, Bk->mlp_w1, u, B, Bk->mlp_hidden, dim, dt, 1, nullptr, Bk->norm2_w, eps, st)) return rc;
-    } else {
-        if (int rc = launch_rmsnorm_rows(h, Bk->norm2_w, hn, B, dim, eps, dt, st)) return rc;
-        if (int rc = launch_linear_small_epi(hn, Bk->mlp_w1, u, B, Bk->mlp_hidden, dim, dt, 1, nullptr, st)) return rc;  // silu(fc1)
-    }
-    return launch_linear_small_epi(u, Bk->mlp_w2, y, B, dim, Bk->mlp_hidden, dt, 2, h, st);  // fc2 + h
+    if (int rc = launch_linear_normed(LinearCall{h, Bk->mlp_w1, u, B, Bk->mlp_hidden, dim, dt, 1, nullptr, st, Bk->norm2_w, eps}, hn)) return rc;  // silu(fc1)
+    return launch_linear_small_epi(LinearCall{u, Bk->mlp_w2, y, B, dim, Bk->mlp_hidden, dt, 2, h, st});  // fc2 + h
 }
 
 // model workspace: x ping | x pong | block workspace
@@ -630,12 +629,7 @@ int nsa_model_decode_step(const nsa_block_desc *blocks, const nsa_kv_desc *kvs, 
         xc = tmp;
     }
     const float eps = blocks[0].norm_eps > 0.f ? blocks[0].norm_eps : 1e-6f;
-    if (linear_small_can_fold_norm(dt, B, vocab, dim, xa, lm_head)) {
-        if (int rc = launch_linear_small_norm(xa, lm_head, logits, B, vocab, dim, dt, 0, nullptr, norm_f_w, eps, st)) return rc;
-    } else {
-        if (int rc = launch_rmsnorm_rows(xa, norm_f_w, xc, B, dim, eps, dt, st)) return rc;
-        if (int rc = launch_linear_small_epi(xc, lm_head, logits, B, vocab, dim, dt, 0, nullptr, st)) return rc;
-    }
+    if (int rc = launch_linear_normed(LinearCall{xa, lm_head, logits, B, vocab, dim, dt, 0, nullptr, st, norm_f_w, eps}, xc)) return rc;
     if (next_tokens) {
         NSA_CHECK_ARG(argmax_rows_workspace(B, vocab) <= (size_t)B * 64 * 8, "model_decode_step: vocabulary too large for the in-call argmax");
         return launch_argmax_rows(logits, next_tokens, B, vocab, dt, ws + need - up256((size_t)B * 64 * 8), st);

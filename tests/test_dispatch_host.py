@@ -308,3 +308,102 @@ def test_decode_step_separate_launches_and_their_blocks(routes):
     logits, pgrp = blocks(unfused, "DecodeParams")
     (sp,) = blocks(unfused, "SelectParams")
     assert logits == pgrp and logits["p_grp"] == sp["p_grp"] and sp == dict(a["SelectParams"], p_grp=sp["p_grp"])
+
+
+# ---- the few-row projection family (csrc/layer_fused.hip: proj_route): form, template instance and operands of every launch
+
+def proj(case):
+    """the family's launches of a case: [(launcher, record)], the record as dispatch_check's run_proj prints it"""
+    names = launches(case)
+    return [(names[p["launch"]], p) for p in case["proj"]]
+
+
+def lin(routes, M, N, K, tag=""):
+    ((name, p),) = proj(routes[f"linear_small/{tag}M{M}_N{N}_K{K}"])
+    assert (p["M"], p["N"], p["K"], p["W"], p["out"]) == (M, N, K, "W_lin+0", "out+0")
+    return name, p["kernel"]
+
+
+def test_linear_small_forms_change_where_the_route_says(routes):
+    for M in (1, 2):
+        for N, K in ((40, 8), (37, 520), (36, 1032), (36, 3072), (36, 4096), (4097, 8), (4100, 1000), (4100, 1536)):
+            assert lin(routes, M, N, K)[0] == "linear_small(fast)", (M, N, K)
+        assert lin(routes, M, 36, 4104)[0] == "linear_small"  # past the all-loads-first form's 8 chunks
+    for case in ("M2_N37_K520_A_2_bytes_off", "M2_N4100_K1000_A_2_bytes_off", "f32_M1_N36_K1032", "f32_M2_N4100_K1000", "f32_M5_N37_K520",
+                 "M3_N40_K40", "M3_N40_K64_A_2_bytes_off"):
+        assert launches(routes[f"linear_small/{case}"]) == ["linear_small"], case
+    for M, N, K in ((3, 40, 64), (9, 36, 2016), (9, 36, 2048), (70, 37, 1024)):
+        assert lin(routes, M, N, K)[0] == "linear_small(mfma)"
+    assert routes["linear_small/M70_N37_K1024"]["geometry"] == ["3,2,1/256,1,1/0"]  # ragged column tile, second row tile
+    for case in ("M0_N40_K8", "M1_N0_K8"):
+        assert (routes[f"linear_small/{case}"]["rc"], routes[f"linear_small/{case}"]["launches"]) == (0, [])
+
+
+def test_linear_small_template_instances(routes):
+    """Two launches share a kernel ordinal exactly when they run the same template instance: the chunk tiers (2, 4, 6, 8 x 512 elements),
+    four weight rows per wave from N = 4096 on with at most two chunks, 4 or 8 MFMA waves.  A larger tier would give the same bits."""
+    k = {(N, K): lin(routes, 1, N, K)[1] for N, K in ((40, 8), (37, 520), (36, 1032), (36, 3072), (36, 4096), (36, 4104), (4097, 8), (4100, 1000),
+                                                      (4100, 1536))}
+    assert all(lin(routes, 2, N, K)[1] == v for (N, K), v in k.items())  # one and two rows: the same instances
+    assert k[40, 8] == k[37, 520] and k[4097, 8] == k[4100, 1000] and k[4100, 1536] == k[36, 1032]
+    assert len({k[40, 8], k[36, 1032], k[36, 3072], k[36, 4096], k[36, 4104], k[4097, 8]}) == 6
+    assert routes["linear_small/M1_N4100_K1000"]["geometry"] == ["257,1,1/256,1,1/0"]  # 16 columns per workgroup
+    assert routes["linear_small/M1_N4100_K1536"]["geometry"] == ["1025,1,1/256,1,1/0"]  # three chunks: one weight row per wave
+    assert lin(routes, 2, 4100, 1000, "f32_")[1] != lin(routes, 1, 36, 1032, "f32_")[1] == lin(routes, 5, 37, 520, "f32_")[1]
+    four, eight = lin(routes, 9, 36, 2016)[1], lin(routes, 9, 36, 2048)[1]
+    assert four == lin(routes, 3, 40, 64)[1] == lin(routes, 70, 37, 1024)[1] != eight
+    assert routes["linear_small/M9_N36_K2048"]["geometry"] == ["3,1,1/512,1,1/0"]
+    for epi in (1, 2):  # the epilogue is an argument, not an instance
+        for M, N, K in ((1, 37, 520), (1, 36, 4104), (3, 40, 64)):
+            ((_, p),) = proj(routes[f"linear_small/M{M}_N{N}_K{K}_epi{epi}"])
+            assert (p["kernel"], p["epi"], p["res"]) == (lin(routes, M, N, K)[1], epi, "res+0" if epi == 2 else "null")
+
+
+def test_block_step_folds_both_norms_where_the_route_takes_them(routes):
+    for case, x in (("B1", "x+0"), ("B2", "x+0"), ("B1_x_2_bytes_off", "x+2"), ("dim776_B3", "x+0")):
+        c = routes[f"block_decode_step/{case}"]
+        assert "rmsnorm_rows" not in launches(c), case
+        (_, qkv), (_, out), (_, fc1), (_, fc2) = proj(c)
+        assert (qkv["A"], qkv["norm_w"], fc1["norm_w"], fc1["A"]) == (x, "norm1_w+0", "norm2_w+0", out["out"]), case
+        assert (out["epi"], out["res"], fc1["epi"], fc2["epi"], fc2["res"], fc2["out"]) == (2, x, 1, 2, out["out"], "y+0"), case
+    assert launches(routes["block_decode_step/B1_x_2_bytes_off"])[0] == "qkv_rope_append"  # the chunk loop
+    assert launches(routes["block_decode_step/dim776_B3"]) == ["qkv_rope_append", "decode_step", "linear_small_mix", "linear_small", "linear_small(mfma)"]
+    c = routes["block_decode_step/B3"]  # the MFMA form reads normalised rows: both norms are launches of their own, into the workspace
+    assert launches(c) == ["rmsnorm_rows", "qkv_rope_append(mfma)", "decode_step", "linear_small_mix", "rmsnorm_rows", "linear_small(mfma)", "linear_small(mfma)"]
+    (_, qkv), (_, out), (_, fc1), (_, fc2) = proj(c)
+    assert qkv["A"].startswith("ws+") and fc1["A"].startswith("ws+") and fc1["A"] != out["out"]
+    assert {qkv["norm_w"], fc1["norm_w"], fc2["norm_w"]} == {"null"} and (out["res"], fc2["res"]) == ("x+0", out["out"])
+    assert fc1["kernel"] != fc2["kernel"]  # K = 3072: eight waves
+
+
+def test_model_step_lm_head(routes):
+    for vocab in (131, 4100):
+        for tail in ("", "_next_tokens"):
+            one, three = routes[f"model_decode_step/vocab{vocab}_B1{tail}"], routes[f"model_decode_step/vocab{vocab}_B3{tail}"]
+            name, head = proj(one)[-1]
+            assert (name, head["norm_w"], head["W"], head["out"], head["N"], head["epi"]) == ("linear_small(fast)", "norm_f_w+0", "W_lm+0", "logits+0", vocab, 0)
+            name, head3 = proj(three)[-1]
+            assert (name, head3["norm_w"], head3["out"]) == ("linear_small(mfma)", "null", "logits+0") and head3["A"] != proj(three)[-2][1]["out"]
+            assert launches(three)[-(3 if tail else 1) - 1] == "rmsnorm_rows"
+            assert (launches(one)[-2:] == ["argmax_part", "argmax_final"]) == bool(tail)
+            assert len(proj(one)) == 9 and len(proj(three)) == 9  # two blocks of four, the head
+    # four weight rows per wave at vocab 4100, as nsa_linear_small at the same N with one chunk pair
+    assert proj(routes["model_decode_step/vocab4100_B1"])[-1][1]["kernel"] == lin(routes, 1, 4100, 1000)[1]
+    assert proj(routes["model_decode_step/vocab131_B1"])[-1][1]["kernel"] == lin(routes, 1, 37, 520)[1]
+
+
+def test_layer_step_mix_rides_in_the_projection_up_to_32_rows(routes):
+    for B in (2, 3, 32):
+        c = routes[f"layer_decode_step/B{B}_t100"]
+        assert launches(c) == ["qkv_rope_append(fast)" if B <= 2 else "qkv_rope_append(mfma)", "decode_step", "linear_small_mix"]
+        _, mix = proj(c)[-1]
+        assert (mix["M"], mix["G"], mix["W"], mix["out"], mix["epi"], mix["res"]) == (B, 2, "W_out+0", "y+0", 0, "null")
+        assert len({mix["A"], mix["Os"], mix["Ow"], mix["gates"]}) == 4
+    assert launches(routes["layer_decode_step/B33_t100"]) == ["qkv_rope_append(mfma)", "decode_step", "decode_finish", "linear_small(mfma)"]
+    assert launches(routes["layer_decode_step/B33_t100_DECODE_BAND_3"]) == ["qkv_rope_append(mfma)", "decode_step", "linear_small_mix"]
+    mixes = [proj(routes[f"layer_decode_step/B{B}_t100"])[-1][1]["kernel"] for B in (2, 3, 32)]
+    assert mixes[0] != mixes[1] == mixes[2] == proj(routes["layer_decode_step/B33_t100_DECODE_BAND_3"])[-1][1]["kernel"]
+    one, two = routes["layer_decode_rows/B1_t100_S2"], routes["layer_decode_rows/B2_t100_S2"]  # B S rows: the MFMA form from four rows on
+    assert (launches(one)[0], launches(one)[-1]) == ("qkv_rope_append(rows)", "linear_small(fast)")
+    assert (launches(two)[0], launches(two)[-1]) == ("qkv_rope_append(rows, mfma)", "linear_small(mfma)")
+    assert [(p["M"], p["B"], p["S"], p["t0"]) for p in (proj(one)[0][1], proj(two)[0][1])] == [(2, 1, 2, 100), (4, 2, 2, 100)]
