@@ -66,9 +66,7 @@ int launch_band_attn_fwd_generic(const BandAttnParams &P, int dtype, hipStream_t
     const int64_t nrh = (int64_t)P.B * P.S * P.G * P.h;
     NSA_CHECK_ARG((nrh + 3) / 4 < ((int64_t)1 << 31), "band_attn: too many rows for one launch");
     const dim3 grid((unsigned)((nrh + 3) / 4)), block(256);
-    if (dtype == NSA_DT_F32) hipLaunchKernelGGL(band_attn_fwd_generic_kernel<float>, grid, block, 0, st, P);
-    else if (dtype == NSA_DT_BF16) hipLaunchKernelGGL(band_attn_fwd_generic_kernel<__bf16>, grid, block, 0, st, P);
-    else hipLaunchKernelGGL(band_attn_fwd_generic_kernel<_Float16>, grid, block, 0, st, P);
+    with_elt(dtype, [&](auto t) { hipLaunchKernelGGL(band_attn_fwd_generic_kernel<decltype(t)>, grid, block, 0, st, P); });
     NSA_LAUNCH_CHECK("band_attn_fwd_generic");
     return NSA_OK;
 }

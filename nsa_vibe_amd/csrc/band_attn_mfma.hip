@@ -235,10 +235,6 @@ __global__ __launch_bounds__(256, 2) void band_attn_bwd_dq_kernel(BandAttnParams
 }
 
 // ---- host side ----------------------------------------------------------------------------
-bool band_attn_mfma_supported(int dtype, int h, int Dk, int Dv) {
-    return (dtype == NSA_DT_BF16 || dtype == NSA_DT_F16) && Dk == Dv && (Dk == 64 || Dk == 128) && h >= 1 && h <= 16;
-}
-
 // NT = 3 column tiles per wave (48 / h tokens) once there are enough tokens to fill the chip, NT = 1 (16 / h tokens)
 // below that; with very few token groups (decode) the key interval is also split over several waves.
 // (D = 128: 2 column tiles, the accumulators are twice as wide)
@@ -262,7 +258,7 @@ static void band_plan(int B, int S, int G, int h, int D, int *nt, int *tpw, int 
 
 size_t band_attn_workspace(int B, int S, int G, int h, int Dk, int Dv, int dtype, int *nsplit_out) {
     int nt = 1, tpw = 1, ns = 1;
-    if (band_attn_mfma_supported(dtype, h, Dk, Dv)) band_plan(B, S, G, h, Dk, &nt, &tpw, &ns);
+    if (attn_mfma_shape_ok(dtype, h, Dk, Dv)) band_plan(B, S, G, h, Dk, &nt, &tpw, &ns);
     if (nsplit_out) *nsplit_out = ns;
     return ns > 1 ? (size_t)B * S * G * ns * h * (Dv + PART_PAD) * sizeof(float) : 0;
 }
@@ -299,31 +295,15 @@ static int launch_band_t(const BandAttnParams &P0, hipStream_t st) {
     const unsigned grid = (unsigned)(nbg * W);
     const int stage = tuning(TUNE_BAND_STAGE);  // A/B switch: 0 = register staging, 1 = LDS-DMA  // measured: LDS-DMA 750 vs register staging 650 TFLOP/s (compressed branch, 64k)
     constexpr int NTW = D == 64 ? 3 : 2;
-    bool done = false;
-    if constexpr (D == 64) {
-        if (nt == NTW && stage == 0) {
-            hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, NTW, false, 0>), dim3(grid), dim3(256), lds, st, P);
-            done = true;
-        }
-    }
-    if (done) {
-    } else if (nt == NTW) hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, NTW, false, 1>), dim3(grid), dim3(256), lds, st, P);
-    else hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, 1, false, 1>), dim3(grid), dim3(256), lds, st, P);
+    if (nt != NTW) hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, 1, false, 1>), dim3(grid), dim3(256), lds, st, P);
+    else if (D == 128 || stage != 0) hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, NTW, false, 1>), dim3(grid), dim3(256), lds, st, P);
+    else if constexpr (D == 64) hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, NTW, false, 0>), dim3(grid), dim3(256), lds, st, P);  // (register staging: D = 64 only)
     NSA_LAUNCH_CHECK("band_attn_fwd");
     return NSA_OK;
 }
 
 int launch_band_attn_fwd_mfma(const BandAttnParams &P, int dtype, hipStream_t st) {
-    NSA_CHECK_ARG(band_attn_mfma_supported(dtype, P.h, P.Dk, P.Dv), "band MFMA kernel: unsupported dtype/h/Dk/Dv = %d/%d/%d/%d", dtype, P.h,
-                  P.Dk, P.Dv);
-    NSA_CHECK_ARG(P.kss % 8 == 0 && P.vss % 8 == 0 && P.ksb % 8 == 0 && P.vsb % 8 == 0 && P.ksg % 8 == 0 && P.vsg % 8 == 0,
-                  "band MFMA kernel: K/V strides must be multiples of 8 elements (16 B)");
-    NSA_CHECK_ARG(((uintptr_t)P.Q % 16 == 0) && ((uintptr_t)P.K % 16 == 0) && ((uintptr_t)P.V % 16 == 0) && ((uintptr_t)P.O % 8 == 0),
-                  "band MFMA kernel: Q/K/V must be 16-byte aligned");
-    NSA_CHECK_ARG((int64_t)P.S_kv * P.kss * 2 < ((int64_t)1 << 31) && (int64_t)P.S_kv * P.vss * 2 < ((int64_t)1 << 31),
-                  "band MFMA kernel: one (b,g) K/V slab must be smaller than 2 GiB (buffer addressing)");
-    if (dtype == NSA_DT_BF16) return P.Dk == 64 ? launch_band_t<__bf16, 64>(P, st) : launch_band_t<__bf16, 128>(P, st);
-    return P.Dk == 64 ? launch_band_t<_Float16, 64>(P, st) : launch_band_t<_Float16, 128>(P, st);
+    return with_elt<false>(dtype, [&](auto t) { return P.Dk == 64 ? launch_band_t<decltype(t), 64>(P, st) : launch_band_t<decltype(t), 128>(P, st); });
 }
 
 // Both branches of a decode step in one launch.  Requires both to be in split form with deferred combine (the caller combines).
@@ -335,7 +315,7 @@ bool band_dual_plan(BandAttnParams *P0, BandAttnParams *P1, int dtype, int64_t w
         if (!(nt == 1 && ns > 1 && P[i]->part && P[i]->nsplit == ns && P[i]->defer_combine)) return false;
         waves[i] = (int64_t)P[i]->B * P[i]->G * ((P[i]->S + P[i]->tpw - 1) / P[i]->tpw) * ns;
     }
-    return P0->Dk == P1->Dk && band_attn_mfma_supported(dtype, P0->h, P0->Dk, P0->Dv);
+    return P0->Dk == P1->Dk && attn_mfma_shape_ok(dtype, P0->h, P0->Dk, P0->Dv);
 }
 
 int launch_band_attn_fwd_dual(const BandAttnParams &A0, const BandAttnParams &A1, int dtype, hipStream_t st) {
@@ -346,13 +326,10 @@ int launch_band_attn_fwd_dual(const BandAttnParams &A0, const BandAttnParams &A1
     const bool d64 = P[0].Dk == 64;
     const size_t lds = 4 * (size_t)(2 * (d64 ? Geo<64>::TILE_BYTES : Geo<128>::TILE_BYTES));
     const dim3 g2(grid[0] + grid[1]);
-    if (dtype == NSA_DT_BF16) {
-        if (d64) hipLaunchKernelGGL((band_attn_fwd_dual_kernel<__bf16, 64>), g2, dim3(256), lds, st, P[0], P[1], grid[0]);
-        else hipLaunchKernelGGL((band_attn_fwd_dual_kernel<__bf16, 128>), g2, dim3(256), lds, st, P[0], P[1], grid[0]);
-    } else {
-        if (d64) hipLaunchKernelGGL((band_attn_fwd_dual_kernel<_Float16, 64>), g2, dim3(256), lds, st, P[0], P[1], grid[0]);
-        else hipLaunchKernelGGL((band_attn_fwd_dual_kernel<_Float16, 128>), g2, dim3(256), lds, st, P[0], P[1], grid[0]);
-    }
+    with_elt<false>(dtype, [&](auto t) {
+        if (d64) hipLaunchKernelGGL((band_attn_fwd_dual_kernel<decltype(t), 64>), g2, dim3(256), lds, st, P[0], P[1], grid[0]);
+        else hipLaunchKernelGGL((band_attn_fwd_dual_kernel<decltype(t), 128>), g2, dim3(256), lds, st, P[0], P[1], grid[0]);
+    });
     NSA_LAUNCH_CHECK("band_attn_fwd_dual");
     return NSA_OK;
 }
@@ -380,10 +357,8 @@ static int launch_band_dq_t(BandAttnParams P, const BandBwdExtra &E, hipStream_t
 
 int launch_band_attn_bwd_dq(const BandAttnParams &P, const void *dO, const float *lse, const float *delta, void *dQ, int dtype,
                             hipStream_t st) {
-    NSA_CHECK_ARG(band_attn_mfma_supported(dtype, P.h, P.Dk, P.Dv), "band dQ kernel: unsupported dtype/h/Dk/Dv");
     BandBwdExtra E{dO, lse, delta, dQ};
-    if (dtype == NSA_DT_BF16) return P.Dk == 64 ? launch_band_dq_t<__bf16, 64>(P, E, st) : launch_band_dq_t<__bf16, 128>(P, E, st);
-    return P.Dk == 64 ? launch_band_dq_t<_Float16, 64>(P, E, st) : launch_band_dq_t<_Float16, 128>(P, E, st);
+    return with_elt<false>(dtype, [&](auto t) { return P.Dk == 64 ? launch_band_dq_t<decltype(t), 64>(P, E, st) : launch_band_dq_t<decltype(t), 128>(P, E, st); });
 }
 
 }  // namespace nsa

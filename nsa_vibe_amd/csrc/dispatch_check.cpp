@@ -269,6 +269,38 @@ static std::string show(const nsa::SelectParams &P) {
         .M_I(W).M_I(k_actual).M_I(n_forced).M_I(keepmask).M_I(all_valid).M_I(l_sel_shift).M_I(forced_plain).str();
 }
 static std::string show(const int &v) { return std::to_string(v); }
+// ---- the argument blocks of the attention family (sel_attn_params.hpp), member by member.  `select` points at the launcher's caller's own
+// SelectParams (host memory): "set" or "null"; the copy the kernel takes is argument 1 of the launch
+static std::string show(const nsa::SelAttnParams &P) {
+    return Obj().M_P(Q).M_P(K).M_P(V).M_P(ranges).M_P(O).M_P(lse).M_I(R).M_I(S).M_I(G).M_I(h).M_I(Dk).M_I(Dv).M_I(S_kv).M_I(n).M_I(ksb).M_I(ksg).M_I(kss)
+        .M_I(vsb).M_I(vsg).M_I(vss).f("scale", P.scale).M_P(part).M_I(nsplit).M_I(map_mode).M_I(defer_combine).M_I(fuse_select)
+        .raw("select", P.select ? "\"set\"" : "\"null\"").M_I(tpw).M_I(nw).M_I(wave_lds).M_P(ks_ws).M_I(ks_bytes).M_I(ks_r1).M_I(ks_r2).M_I(ks_w1).M_I(ks_w2)
+        .M_I(ks_wa).M_I(ks_wb).M_I(ks_wc).str();
+}
+static std::string show(const nsa::SelAttnBwdParams &P) {
+    return Obj().M_P(Q).M_P(K).M_P(V).M_P(ranges).M_P(O).M_P(lse).M_P(dO).M_P(dQ).M_P(dK).M_P(dV).M_I(R).M_I(S).M_I(G).M_I(h).M_I(Dk).M_I(Dv).M_I(S_kv).M_I(n)
+        .M_I(ksb).M_I(ksg).M_I(kss).M_I(vsb).M_I(vsg).M_I(vss).f("scale", P.scale).M_I(skip_delta_dq).str();
+}
+static std::string show(const nsa::BandAttnParams &P) {
+    return Obj().M_P(Q).M_P(K).M_P(V).M_P(O).M_P(lse).M_I(B).M_I(S).M_I(G).M_I(h).M_I(Dk).M_I(Dv).M_I(S_kv).M_I(ksb).M_I(ksg).M_I(kss).M_I(vsb).M_I(vsg).M_I(vss)
+        .f("scale", P.scale).M_I(t0).M_I(a).M_I(dd).M_I(c).M_I(w).M_P(part).M_I(nsplit).M_I(map_mode).M_I(tpw).M_I(defer_combine).str();
+}
+static std::string show(const nsa::DecAttnArgs &P) {
+    return Obj().M_P(Q).M_P(K).M_P(V).M_P(O).M_I(G).M_I(h).M_I(S_kv).M_I(n).M_I(ksb).M_I(ksg).M_I(kss).M_I(vsb).M_I(vsg).M_I(vss).f("c2", P.c2).str();
+}
+static std::string show(const nsa::DecBandPair &P) {
+    return Obj().raw("w", show(P.w)).raw("c", show(P.c)).i("mg_on", P.mg.on).p("gates", P.mg.gates).i("n_sel", P.n_sel).i("n_w", P.n_w).str();
+}
+struct BandBwdExtraArg {  // band_attn_mfma.hip: BandBwdExtra, argument 1 of the band dQ kernel
+    const void *dO, *lse, *delta, *dQ;
+};
+static std::string show(const BandBwdExtraArg &P) { return Obj().M_P(dO).M_P(lse).M_P(delta).M_P(dQ).str(); }
+struct PtrArg {  // a pointer passed by value
+    const void *p;
+};
+static std::string show(const PtrArg &v) { return quoted(where(v.p)); }
+static std::string show(const int64_t &v) { return std::to_string(v); }
+static std::string show(const unsigned &v) { return std::to_string(v); }
 #undef M_I
 #undef M_P
 
@@ -797,6 +829,182 @@ int main(int argc, char **argv) {
     set_tuning("DECODE_BAND", -1);
     for (int B_ : {1, 2})
         run_proj("layer_decode_rows/B" + std::to_string(B_) + "_t100_S2", [&] { kv.B = B_; return layer_rows(100, 2); });
+
+    // ---- the attention family: every member of the argument blocks of its launches.  1024 rows (S = 512) are where selection attention
+    // stops splitting the keys of a row over waves: the block, row and key-split forms show from there on
+    kv.B = 1;
+    g_named.insert(g_named.end(), {{"K", K, MB}, {"V", V, MB}, {"lse", lse, MB}, {"dO", dO, MB}, {"dQ", dQ, MB}, {"dK", dK, MB}, {"dV", dV, MB},
+                                   {"K_win", kv.K_win, MB}, {"V_win", kv.V_win, MB}, {"K_raw", kv.K_raw, MB}, {"V_raw", kv.V_raw, MB}, {"V_cmp", kv.V_cmp, MB},
+                                   {"proj", proj, 4 * MB}, {"O_mix", O_mix, MB}});
+    std::vector<Want> attn_blocks;
+    for (const char *k : {"sel_attn_fwd_mfma", "sel_attn_blocks_mfma", "sel_attn_rows_mfma"}) {
+        attn_blocks.push_back(want<nsa::SelAttnParams>(k, "SelAttnParams"));
+        attn_blocks.push_back(want<nsa::SelectParams>(k, "SelectParams", 1));
+        attn_blocks.push_back(want<int>(k, "cand", 2));
+    }
+    for (const char *k : {"sel_attn_combine", "band_attn_combine", "sel_attn_fwd_generic", "sel_head_causal"}) attn_blocks.push_back(want<nsa::SelAttnParams>(k, "SelAttnParams"));
+    {
+        const char *names[] = {"ml", "acc", "O", "lse"}, *ints[] = {"nbg", "S", "G", "h", "r1", "r2"};
+        for (int i = 0; i < 4; ++i) attn_blocks.push_back(want<PtrArg>("sel_attn_ksplit_combine", names[i], i));
+        for (int i = 0; i < 6; ++i) attn_blocks.push_back(want<int>("sel_attn_ksplit_combine", ints[i], 4 + i));
+        const char *fk_p[] = {"V", "ranges", "O"}, *fk_i[] = {"S", "G", "h", "Dv", "n", "S_kv"}, *fk_l[] = {"vsb", "vsg", "vss"};
+        for (int i = 0; i < 3; ++i) attn_blocks.push_back(want<PtrArg>("sel_first_key", fk_p[i], i));
+        attn_blocks.push_back(want<int64_t>("sel_first_key", "R", 3));
+        for (int i = 0; i < 6; ++i) attn_blocks.push_back(want<int>("sel_first_key", fk_i[i], 4 + i));
+        for (int i = 0; i < 3; ++i) attn_blocks.push_back(want<int64_t>("sel_first_key", fk_l[i], 10 + i));
+        const char *br_i[] = {"S", "G", "S_kv", "t0", "a", "dd", "c", "w"};
+        attn_blocks.push_back(want<PtrArg>("band_ranges", "ranges", 0));
+        attn_blocks.push_back(want<int64_t>("band_ranges", "R", 1));
+        for (int i = 0; i < 8; ++i) attn_blocks.push_back(want<int>("band_ranges", br_i[i], 2 + i));
+    }
+    attn_blocks.push_back(want<nsa::DecAttnArgs>("sel_attn_decode_wg", "DecAttnArgs"));
+    attn_blocks.push_back(want<PtrArg>("sel_attn_decode_wg", "ranges", 1));
+    for (const char *k : {"bwd_dq_rows", "bwd_dq", "bwd_dkdv"}) {
+        attn_blocks.push_back(want<nsa::SelAttnBwdParams>(k, "SelAttnBwdParams"));
+        attn_blocks.push_back(want<PtrArg>(k, "delta", 1));
+    }
+    attn_blocks.push_back(want<nsa::SelAttnBwdParams>("sel_attn_bwd_generic", "SelAttnBwdParams"));
+    for (const char *k : {"band_attn_fwd(split)", "band_attn_fwd", "band_attn_fwd_generic", "band_attn_fwd_dual", "band_attn_bwd_dq"})
+        attn_blocks.push_back(want<nsa::BandAttnParams>(k, "BandAttnParams"));
+    attn_blocks.push_back(want<nsa::BandAttnParams>("band_attn_fwd_dual", "BandAttnParams1", 1));
+    attn_blocks.push_back(want<unsigned>("band_attn_fwd_dual", "grid0", 2));
+    attn_blocks.push_back(want<BandBwdExtraArg>("band_attn_bwd_dq", "BandBwdExtra", 1));
+    for (const char *k : {"decode_step", "decode_rows"}) {
+        attn_blocks.push_back(want<nsa::DecAttnArgs>(k, "DecAttnArgs", 3));
+        attn_blocks.push_back(want<nsa::DecBandPair>(k, "DecBandPair", 4));
+    }
+
+    struct AttnCase {
+        int B = 1, S = 128, G = 2, h = 6, D = 64, S_kv = 128, n = 16, dtype = NSA_DT_BF16, variant = 0;
+        int64_t kss = 0;  // 0: D
+        void *O = nullptr, *ws = nullptr;
+        float *lse = nullptr;
+        size_t ws_bytes = (size_t)64 << 20;
+        float scale = 0.f;
+        int t0 = 0, a = 0, dd = 1, c = 0, w = 64;  // the band (sliding by default)
+    };
+    typedef std::function<void(AttnCase &)> AttnTweak;
+    auto attn_case = [&](const AttnTweak &tweak) {
+        AttnCase c;
+        c.O = O;
+        c.ws = ws;
+        tweak(c);
+        if (!c.kss) c.kss = c.D;
+        return c;
+    };
+    auto sel_fwd_case = [&](const char *label, const AttnTweak &tweak) {
+        const AttnCase c = attn_case(tweak);
+        const int64_t ksg = c.S_kv * c.kss, vsg = (int64_t)c.S_kv * c.D;
+        run_args(std::string("sel_attn_fwd/") + label, [&] {
+            return fwd(Q, K, V, ranges, c.O, c.lse, c.B, c.S, c.G, c.h, c.D, c.D, c.S_kv, c.n, c.G * ksg, ksg, c.kss, c.G * vsg, vsg, c.D, c.dtype, c.scale, c.variant,
+                       c.ws, c.ws_bytes, nullptr);
+        }, attn_blocks);
+    };
+    sel_fwd_case("blocks", [](AttnCase &c) { c.S = c.S_kv = 512; });
+    sel_fwd_case("blocks_lse", [&](AttnCase &c) { c.S = c.S_kv = 512; c.lse = lse; });
+    sel_fwd_case("split_base_shape", [](AttnCase &) {});
+    sel_fwd_case("S1_decode_wg", [](AttnCase &c) { c.S = 1; });
+    sel_fwd_case("S1_lse_split", [&](AttnCase &c) { c.S = 1; c.lse = lse; });
+    sel_fwd_case("S1_lse_null_workspace", [&](AttnCase &c) { c.S = 1; c.lse = lse; c.ws = nullptr; c.ws_bytes = 0; });
+    sel_fwd_case("S1_lse_workspace_8_bytes_off", [&](AttnCase &c) { c.S = 1; c.lse = lse; c.ws = off(ws, 8); });
+    sel_fwd_case("S128_Skv32768", [](AttnCase &c) { c.S_kv = 32768; });
+    sel_fwd_case("S512_Skv32768_key_split", [](AttnCase &c) { c.S = 512; c.S_kv = 32768; });
+    sel_fwd_case("S512_Skv32768_null_workspace", [](AttnCase &c) { c.S = 512; c.S_kv = 32768; c.ws = nullptr; c.ws_bytes = 0; });
+    sel_fwd_case("D128_base_shape", [](AttnCase &c) { c.D = 128; });
+    sel_fwd_case("D128_S512_rows", [](AttnCase &c) { c.D = 128; c.S = c.S_kv = 512; });
+    sel_fwd_case("S512_Skv33280_key_split_rows_in_two", [](AttnCase &c) { c.S = 512; c.S_kv = 33280; });
+    sel_fwd_case("S512_kss72_rows", [](AttnCase &c) { c.S = c.S_kv = 512; c.kss = 72; });
+    sel_fwd_case("S512_kss72_h16_one_row_per_wave", [](AttnCase &c) { c.S = c.S_kv = 512; c.kss = 72; c.h = 16; });
+    sel_fwd_case("variant_1", [](AttnCase &c) { c.variant = 1; });
+    sel_fwd_case("f32", [](AttnCase &c) { c.dtype = NSA_DT_F32; });
+    sel_fwd_case("h32", [](AttnCase &c) { c.h = 32; });
+    sel_fwd_case("O_4_bytes_off", [&](AttnCase &c) { c.O = off(O, 4); });
+    sel_fwd_case("S512_O_4_bytes_off", [&](AttnCase &c) { c.S = c.S_kv = 512; c.O = off(O, 4); });
+    sel_fwd_case("slab_2GiB", [](AttnCase &c) { c.S_kv = 1 << 20; c.kss = 1024; });
+    sel_fwd_case("S1_V_slab_2GiB", [](AttnCase &c) { c.S = 1; c.S_kv = 1 << 24; });
+    sel_fwd_case("S1_V_slab_under_2GiB", [](AttnCase &c) { c.S = 1; c.S_kv = (1 << 24) - 1; });
+
+    auto sel_bwd_case = [&](const char *label, const AttnTweak &tweak) {
+        const AttnCase c = attn_case(tweak);
+        const int64_t sg_ = (int64_t)c.S_kv * c.D;
+        run_args(std::string("sel_attn_bwd/") + label, [&] {
+            return bwd(Q, K, V, ranges, O, lse, dO, dQ, dK, dV, c.B, c.S, c.G, c.h, c.D, c.D, c.S_kv, c.n, c.G * sg_, sg_, c.D, c.G * sg_, sg_, c.D, c.dtype, c.scale,
+                       c.variant, c.ws, c.ws_bytes, nullptr);
+        }, attn_blocks);
+    };
+    sel_bwd_case("mfma_members", [](AttnCase &) {});
+    sel_bwd_case("generic_members", [](AttnCase &c) { c.variant = 1; });
+    sel_bwd_case("D128_members", [](AttnCase &c) { c.D = 128; c.scale = 0.5f; });
+
+    run_args("sel_attn_first_key_parity/members", [&] {
+        return NSA_FN(nsa_sel_attn_first_key_parity)(V, ranges, O, B, S, G, h, D, S_kv, n, sb, sg, D, dt, nullptr);
+    }, attn_blocks);
+    run_args("sel_attn_first_key_parity/f32", [&] {
+        return NSA_FN(nsa_sel_attn_first_key_parity)(V, ranges, O, B, S, G, h, D, S_kv, n, sb, sg, D, NSA_DT_F32, nullptr);
+    }, attn_blocks);
+    run_args("sel_attn_head_causal_parity/members", [&] {
+        return NSA_FN(nsa_sel_attn_head_causal_parity)(Q, K, V, ranges, O, B, S, G, h, D, D, S_kv, n, sb, sg, D, sb, sg, D, dt, 0.f, nullptr);
+    }, attn_blocks);
+
+    auto band_fwd_case = [&](const char *label, const AttnTweak &tweak) {
+        const AttnCase c = attn_case(tweak);
+        const int64_t ksg = c.S_kv * c.kss, vsg = (int64_t)c.S_kv * c.D;
+        run_args(std::string("band_attn_fwd/") + label, [&] {
+            return bfwd(Q, K, V, c.O, c.lse, c.B, c.S, c.G, c.h, c.D, c.D, c.S_kv, c.G * ksg, ksg, c.kss, c.G * vsg, vsg, c.D, c.t0, c.a, c.dd, c.c, c.w, c.dtype, c.scale,
+                        c.variant, c.ws, c.ws_bytes, nullptr);
+        }, attn_blocks);
+    };
+    auto compressed = [](AttnCase &c) { c.t0 = 100; c.a = 32; c.dd = 16; c.c = 1; c.w = 1 << 30; };
+    band_fwd_case("sliding_members", [&](AttnCase &c) { c.t0 = 7; c.lse = lse; });
+    band_fwd_case("compressed_members", [&](AttnCase &c) { compressed(c); c.S_kv = 13; });
+    band_fwd_case("S4096_sliding_members", [&](AttnCase &c) { c.S = c.S_kv = 4096; c.lse = lse; });
+    band_fwd_case("S4096_compressed_members", [&](AttnCase &c) { compressed(c); c.t0 = 0; c.S = 4096; c.S_kv = 255; });
+    band_fwd_case("S1_split", [&](AttnCase &c) { c.S = 1; c.t0 = 127; });
+    band_fwd_case("S1_null_workspace", [&](AttnCase &c) { c.S = 1; c.t0 = 127; c.ws = nullptr; c.ws_bytes = 0; });
+    band_fwd_case("slab_2GiB_generic", [](AttnCase &c) { c.S_kv = 1 << 20; c.kss = 1024; });
+    band_fwd_case("generic_members", [&](AttnCase &c) { compressed(c); c.S_kv = 13; c.variant = 1; });
+    band_fwd_case("w_0", [](AttnCase &c) { c.w = 0; });
+
+    auto band_bwd_case = [&](const char *label, const AttnTweak &tweak) {
+        const AttnCase c = attn_case(tweak);
+        const int64_t sg_ = (int64_t)c.S_kv * c.D;
+        run_args(std::string("band_attn_bwd/") + label, [&] {
+            return bbwd(Q, K, V, O, lse, dO, dQ, dK, dV, c.B, c.S, c.G, c.h, c.D, c.D, c.S_kv, c.G * sg_, sg_, c.D, c.G * sg_, sg_, c.D, c.t0, c.a, c.dd, c.c, c.w, c.dtype,
+                        c.scale, c.variant, c.ws, c.ws_bytes, nullptr);
+        }, attn_blocks);
+    };
+    band_bwd_case("mfma_members", [&](AttnCase &c) { compressed(c); c.S_kv = 13; });
+    band_bwd_case("generic_fallback", [&](AttnCase &c) { compressed(c); c.S_kv = 13; c.variant = 1; });
+    band_bwd_case("f32_fallback", [](AttnCase &c) { c.dtype = NSA_DT_F32; });
+
+    for (int S_ : {512, 32768}) {
+        set_tuning("SEL_FUSE", 1);
+        run_args("sel_select_attn_fwd/S" + std::to_string(S_) + "_SEL_FUSE_members", [&] { return select_attn(K, S_); }, attn_blocks);
+        set_tuning("SEL_FUSE", 0);
+    }
+    run_args("sel_select_attn_fwd/S512_two_launches_members", [&] { return select_attn(K, 512); }, attn_blocks);
+
+    // the layer calls: the attention launches of their three branches
+    run_args("layer_prefill/S100_attention", [&] { return prefill(100); }, attn_blocks);
+    set_tuning("SEL_FUSE", 1);
+    run_args("layer_prefill/S512_SEL_FUSE_attention", [&] { return prefill(512); }, attn_blocks);
+    set_tuning("SEL_FUSE", 0);
+    run_args("layer_extend/t100_S28_attention", [&] { return extend(100, 28); }, attn_blocks);
+    run_args("layer_decode_step/t100_attention", [&] { return decode(100); }, attn_blocks);
+    set_tuning("DECODE_STEP", 0);  // the separate launches: the deferred split of the selected branch and the dual band launch
+    run_args("layer_decode_step/t100_DECODE_STEP_0_attention", [&] { return decode(100); }, attn_blocks);
+    set_tuning("DECODE_WG", 0);
+    run_args("layer_decode_step/t100_DECODE_STEP_0_DECODE_WG_0_attention", [&] { return decode(100); }, attn_blocks);
+    run_args("layer_decode_rows/t100_S4_DECODE_STEP_0_DECODE_WG_0_attention", [&] { return layer_rows(100, 4); }, attn_blocks);
+    set_tuning("DECODE_WG", -1);
+    set_tuning("DECODE_STEP", 1);
+    run_args("layer_decode_rows/t100_S4_attention", [&] { return layer_rows(100, 4); }, attn_blocks);
+    set_tuning("DECODE_ROWS", 0);
+    run_args("layer_decode_rows/t100_S4_DECODE_ROWS_0_attention", [&] { return layer_rows(100, 4); }, attn_blocks);
+    set_tuning("DECODE_ROWS", -1);
+    L.Dk = L.Dv = 128;
+    run_args("layer_decode_step/D128_t100_DECODE_STEP_0_attention", [&] { set_tuning("DECODE_STEP", 0); const int rc = decode(100); set_tuning("DECODE_STEP", 1); return rc; }, attn_blocks);
+    L.Dk = L.Dv = 64;
     printf("\n}\n");
     return 0;
 }

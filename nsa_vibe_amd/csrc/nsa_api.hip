@@ -110,10 +110,12 @@ int nsa_hip_device_check(int dev, int *cu_count, size_t *hbm_bytes) {
 
 // ------------------------------------------------------------------------------ attention
 size_t nsa_sel_attn_fwd_workspace_kv(int B, int S, int G, int h, int Dk, int Dv, int S_kv, int n_ranges, int dtype) {
-    if (!sel_attn_mfma_supported(dtype, h, Dk, Dv)) return 0;
-    const size_t split_kv = sel_attn_mfma_workspace((int64_t)B * S * G, h, Dv, nullptr);
+    AttnCall c{};  // the shape alone: no tensors, the route of variant 0
+    c.B = B; c.S = S; c.G = G; c.h = h; c.Dk = Dk; c.Dv = Dv; c.S_kv = S_kv; c.n = n_ranges; c.dtype = dtype;
+    if (!sel_attn_route(c).fast_ok) return 0;
+    const size_t split_kv = sel_attn_mfma_workspace(c.rows(), h, Dv, nullptr);
     // key-split form of the block kernel (long contexts): its zones follow the rows' positions S_kv - S + row
-    const size_t key_split = sel_attn_ksplit_workspace(dtype, h, Dk, Dv, S, S_kv > S ? S_kv : S, n_ranges, (int64_t)B * S * G);
+    const size_t key_split = sel_attn_ksplit_workspace(dtype, h, Dk, Dv, S, S_kv > S ? S_kv : S, n_ranges, c.rows());
     return split_kv > key_split ? split_kv : key_split;
 }
 
@@ -123,51 +125,70 @@ size_t nsa_sel_attn_fwd_workspace(int B, int S, int G, int h, int Dk, int Dv, in
 
 }  // extern "C"
 
-int nsa::sel_attn_fwd_impl(const void *Q, const void *K, const void *V, const int32_t *ranges, void *O, float *lse, int B, int S, int G,
-                           int h, int Dk, int Dv, int S_kv, int n_ranges, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg,
-                           int64_t vss, int dtype, float scale, int variant, void *workspace, size_t workspace_bytes, void *stream,
-                           int defer, int *ns_used) {
-    if (ns_used) *ns_used = 1;
-    NSA_CHECK_ARG(dtype_ok(dtype), "sel_attn_fwd: unknown dtype %d", dtype);
-    NSA_CHECK_ARG(B >= 0 && S >= 0 && G >= 1 && h >= 1 && Dk >= 1 && Dv >= 1 && S_kv >= 0 && n_ranges >= 0,
-                  "sel_attn_fwd: negative size");
-    NSA_CHECK_ARG(n_ranges <= 64, "sel_attn_fwd: at most 64 ranges per row are supported (got %d)", n_ranges);
-    NSA_CHECK_ARG(Dk <= 256 && Dv <= 256, "sel_attn_fwd: Dk/Dv up to 256 supported (got %d/%d)", Dk, Dv);
-    const int64_t R = (int64_t)B * S * G;
-    if (R == 0) return NSA_OK;
-    NSA_CHECK_ARG(Q && O && ranges || n_ranges == 0, "sel_attn_fwd: null pointer");
-    NSA_CHECK_ARG((K && V) || S_kv == 0, "sel_attn_fwd: null K/V");
-    hipStream_t st = (hipStream_t)stream;
-    if (S_kv == 0 || n_ranges == 0) {
-        if (int rc = zero_rows(O, R, h, Dv, dtype, st)) return rc;
-        if (lse) NSA_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)lse, (int)0xff800000, (size_t)R * h, st));  // lse = -inf (its bit pattern)
-        return NSA_OK;
+AttnRoute nsa::sel_attn_route(const AttnCall &c) {
+    AttnRoute r{AttnRoute::GENERIC, AttnRoute::WS_NONE, attn_mfma_shape_ok(c.dtype, c.h, c.Dk, c.Dv) && qkv_aligned(c), 1};
+    const size_t need = r.fast_ok ? sel_attn_mfma_workspace(c.rows(), c.h, c.Dv, &r.nsplit) : 0;
+    if (c.S_kv == 0 || c.n == 0) {
+        r.kind = AttnRoute::ZERO_FILL;
+    } else if (c.variant == 0 && c.S == 1 && !c.lse && sel_attn_decode_wg_supported(c) && (int64_t)c.S_kv * 2 * c.Dv < ((int64_t)1 << 31)) {
+        r.kind = AttnRoute::DECODE_WG;  // decode: one workgroup per row, partials merged through LDS, no combine launch
+    } else if (c.variant == 2 || (c.variant == 0 && r.fast_ok)) {
+        r.kind = AttnRoute::MFMA;
+        if (c.ws && ((uintptr_t)c.ws % 16 == 0) && (r.nsplit == 1 || c.ws_bytes >= need)) r.ws = r.nsplit > 1 ? AttnRoute::WS_SPLIT : AttnRoute::WS_KSPLIT;
     }
-    SelAttnParams P = sel_attn_params(Q, K, V, ranges, O, lse, R, S, G, h, Dk, Dv, S_kv, n_ranges, ksb, ksg, kss, vsb, vsg, vss, scale);
-    P.nsplit = 1;
-    const bool fast_ok = sel_attn_mfma_supported(dtype, h, Dk, Dv) && qkv_aligned(Q, K, V, ksb, ksg, kss, vsb, vsg, vss);
-    if (variant == 2) NSA_CHECK_ARG(fast_ok, "sel_attn_fwd: MFMA variant requested but shape/dtype/alignment unsupported");
-    NSA_CHECK_ARG(variant >= 0 && variant <= 2, "sel_attn_fwd: unknown variant %d", variant);
-    if (variant == 0 && S == 1 && !lse && sel_attn_decode_wg_supported(dtype, h, Dk, Dv, n_ranges, ksb, ksg, kss, vsb, vsg, vss, Q, K, V) &&
-        (int64_t)S_kv * 2 * Dv < ((int64_t)1 << 31))  // decode: one workgroup per row, partials merged through LDS, no combine launch
-        return launch_sel_attn_decode_wg(Q, K, V, ranges, O, R, G, h, S_kv, n_ranges, ksb, ksg, kss, vsb, vsg, vss, dtype, P.scale, st, Dk);
-    if (variant == 2 || (variant == 0 && fast_ok)) {
-        int ns = 1;
-        const size_t need = sel_attn_mfma_workspace(R, h, Dv, &ns);
-        if (ns > 1 && workspace && workspace_bytes >= need && ((uintptr_t)workspace % 16 == 0)) {
-            P.part = (float *)workspace;
-            P.nsplit = ns;
-            P.defer_combine = defer;
-            if (ns_used && defer) *ns_used = ns;
-        } else if (ns == 1 && workspace && ((uintptr_t)workspace % 16 == 0)) {
-            P.ks_ws = workspace;  // the block kernel may split the keys of a pair over two XCD groups (partial records go here)
-            P.ks_bytes = workspace_bytes;
-        }
-        return launch_sel_attn_fwd_mfma(P, dtype, st);
-    }
-    return launch_sel_attn_fwd_generic(P, dtype, st);
+    return r;
 }
 
+// the block of a call on the MFMA route
+static SelAttnParams sel_attn_mfma_params(const AttnCall &c, const AttnRoute &r, int defer) {
+    SelAttnParams P = sel_attn_params(c);
+    P.nsplit = 1;
+    if (r.ws == AttnRoute::WS_SPLIT) {
+        P.part = (float *)c.ws;
+        P.nsplit = r.nsplit;
+        P.defer_combine = defer;
+    } else if (r.ws == AttnRoute::WS_KSPLIT) {
+        P.ks_ws = c.ws;
+        P.ks_bytes = c.ws_bytes;
+    }
+    return P;
+}
+
+int nsa::sel_attn_fwd_impl(const AttnCall &c, int defer, int *ns_used) {
+    if (ns_used) *ns_used = 1;
+    NSA_CHECK_ARG(dtype_ok(c.dtype), "sel_attn_fwd: unknown dtype %d", c.dtype);
+    NSA_CHECK_ARG(c.B >= 0 && c.S >= 0 && c.G >= 1 && c.h >= 1 && c.Dk >= 1 && c.Dv >= 1 && c.S_kv >= 0 && c.n >= 0, "sel_attn_fwd: negative size");
+    NSA_CHECK_ARG(c.n <= 64, "sel_attn_fwd: at most 64 ranges per row are supported (got %d)", c.n);
+    NSA_CHECK_ARG(c.Dk <= 256 && c.Dv <= 256, "sel_attn_fwd: Dk/Dv up to 256 supported (got %d/%d)", c.Dk, c.Dv);
+    const int64_t R = c.rows();
+    if (R == 0) return NSA_OK;
+    NSA_CHECK_ARG(c.Q && c.O && c.ranges || c.n == 0, "sel_attn_fwd: null pointer");
+    NSA_CHECK_ARG((c.K && c.V) || c.S_kv == 0, "sel_attn_fwd: null K/V");
+    const AttnRoute r = sel_attn_route(c);
+    if (r.kind == AttnRoute::ZERO_FILL) {
+        if (int rc = zero_rows(c.O, R, c.h, c.Dv, c.dtype, c.st)) return rc;
+        if (c.lse) NSA_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)c.lse, (int)0xff800000, (size_t)R * c.h, c.st));  // lse = -inf (its bit pattern)
+        return NSA_OK;
+    }
+    if (c.variant == 2) NSA_CHECK_ARG(r.fast_ok, "sel_attn_fwd: MFMA variant requested but shape/dtype/alignment unsupported");
+    NSA_CHECK_ARG(c.variant >= 0 && c.variant <= 2, "sel_attn_fwd: unknown variant %d", c.variant);
+    const SelAttnParams P = sel_attn_mfma_params(c, r, defer);
+    if (ns_used && defer) *ns_used = P.nsplit;
+    if (r.kind == AttnRoute::DECODE_WG) return launch_sel_attn_decode_wg(P, c.dtype, c.st);
+    if (r.kind == AttnRoute::MFMA) return launch_sel_attn_fwd_mfma(P, c.dtype, c.st);
+    return launch_sel_attn_fwd_generic(P, c.dtype, c.st);
+}
+
+// the two parity modes: their checks, the rows that select nothing, their one launch (qk: the mode reads Q and K too)
+static int parity_mode(const char *who, bool qk, int (*launch)(const SelAttnParams &, int, hipStream_t), const AttnCall &c) {
+    NSA_CHECK_ARG(dtype_ok(c.dtype), "%s: unknown dtype %d", who, c.dtype);
+    NSA_CHECK_ARG(c.B >= 0 && c.S >= 0 && c.G >= 1 && c.h >= 1 && c.Dk >= 1 && c.Dv >= 1 && c.S_kv >= 0 && c.n >= 0, "%s: negative size", who);
+    NSA_CHECK_ARG(c.n <= 64, "%s: at most 64 ranges per row are supported (got %d)", who, c.n);
+    if (c.rows() == 0) return NSA_OK;
+    NSA_CHECK_ARG((c.Q || !qk) && c.O && (c.ranges || c.n == 0) && (((c.K || !qk) && c.V) || c.S_kv == 0), "%s: null pointer", who);
+    if (c.S_kv == 0 || c.n == 0) return zero_rows(c.O, c.rows(), c.h, c.Dv, c.dtype, c.st);
+    return launch(sel_attn_params(c), c.dtype, c.st);
+}
 
 extern "C" {
 
@@ -175,76 +196,106 @@ int nsa_sel_attn_fwd(const void *Q, const void *K, const void *V, const int32_t 
                      int S, int G, int h, int Dk, int Dv, int S_kv, int n_ranges, int64_t ksb, int64_t ksg,
                      int64_t kss, int64_t vsb, int64_t vsg, int64_t vss, int dtype, float scale, int variant,
                      void *workspace, size_t workspace_bytes, void *stream) {
-    return sel_attn_fwd_impl(Q, K, V, ranges, O, lse, B, S, G, h, Dk, Dv, S_kv, n_ranges, ksb, ksg, kss, vsb, vsg, vss, dtype, scale, variant,
-                             workspace, workspace_bytes, stream, 0, nullptr);
+    return sel_attn_fwd_impl(AttnCall{Q, K, V, ranges, O, lse, B, S, G, h, Dk, Dv, S_kv, n_ranges, ksb, ksg, kss, vsb, vsg, vss, dtype, scale, variant,
+                                      workspace, workspace_bytes, (hipStream_t)stream},
+                             0, nullptr);
 }
 
 int nsa_sel_attn_first_key_parity(const void *V, const int32_t *ranges, void *O, int B, int S, int G, int h, int Dv, int S_kv, int n_ranges,
                                   int64_t vsb, int64_t vsg, int64_t vss, int dtype, void *stream) {
-    NSA_CHECK_ARG(dtype_ok(dtype), "sel_attn_first_key_parity: unknown dtype %d", dtype);
-    NSA_CHECK_ARG(B >= 0 && S >= 0 && G >= 1 && h >= 1 && Dv >= 1 && S_kv >= 0 && n_ranges >= 0, "sel_attn_first_key_parity: negative size");
-    NSA_CHECK_ARG(n_ranges <= 64, "sel_attn_first_key_parity: at most 64 ranges per row are supported (got %d)", n_ranges);
-    const int64_t R = (int64_t)B * S * G;
-    if (R == 0) return NSA_OK;
-    NSA_CHECK_ARG(O && (ranges || n_ranges == 0) && (V || S_kv == 0), "sel_attn_first_key_parity: null pointer");
-    if (S_kv == 0 || n_ranges == 0) return zero_rows(O, R, h, Dv, dtype, (hipStream_t)stream);
-    return launch_sel_first_key(V, ranges, O, R, S, G, h, Dv, n_ranges, S_kv, vsb, vsg, vss, (int)esize(dtype), (hipStream_t)stream);
+    // (no Q, no K: the mode copies rows of V; Dk and the scale are not read)
+    return parity_mode("sel_attn_first_key_parity", false, launch_sel_first_key,
+                       AttnCall{nullptr, nullptr, V, ranges, O, nullptr, B, S, G, h, Dv, Dv, S_kv, n_ranges, 0, 0, 0, vsb, vsg, vss, dtype, 1.f, 0, nullptr, 0, (hipStream_t)stream});
 }
 
 int nsa_sel_attn_head_causal_parity(const void *Q, const void *K, const void *V, const int32_t *ranges, void *O, int B, int S, int G, int h,
                                     int Dk, int Dv, int S_kv, int n_ranges, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg,
                                     int64_t vss, int dtype, float scale, void *stream) {
-    NSA_CHECK_ARG(dtype_ok(dtype), "sel_attn_head_causal_parity: unknown dtype %d", dtype);
-    NSA_CHECK_ARG(B >= 0 && S >= 0 && G >= 1 && h >= 1 && Dk >= 1 && Dv >= 1 && S_kv >= 0 && n_ranges >= 0,
-                  "sel_attn_head_causal_parity: negative size");
-    NSA_CHECK_ARG(n_ranges <= 64, "sel_attn_head_causal_parity: at most 64 ranges per row are supported (got %d)", n_ranges);
-    const int64_t R = (int64_t)B * S * G;
-    if (R == 0) return NSA_OK;
-    NSA_CHECK_ARG(Q && O && (ranges || n_ranges == 0) && ((K && V) || S_kv == 0), "sel_attn_head_causal_parity: null pointer");
-    if (S_kv == 0 || n_ranges == 0) return zero_rows(O, R, h, Dv, dtype, (hipStream_t)stream);
-    const SelAttnParams P = sel_attn_params(Q, K, V, ranges, O, nullptr, R, S, G, h, Dk, Dv, S_kv, n_ranges, ksb, ksg, kss, vsb, vsg, vss, scale);
-    return launch_sel_head_causal(P, dtype, (hipStream_t)stream);
+    return parity_mode("sel_attn_head_causal_parity", true, launch_sel_head_causal,
+                       AttnCall{Q, K, V, ranges, O, nullptr, B, S, G, h, Dk, Dv, S_kv, n_ranges, ksb, ksg, kss, vsb, vsg, vss, dtype, scale, 0, nullptr, 0, (hipStream_t)stream});
 }
 
 size_t nsa_sel_attn_bwd_workspace(int B, int S, int G, int h, int Dk, int Dv, int S_kv, int dtype, int variant) {
-    if (variant == 1 || !sel_attn_bwd_mfma_supported(dtype, h, Dk, Dv)) return 0;
+    if (variant == 1 || !attn_mfma_shape_ok(dtype, h, Dk, Dv)) return 0;
     return sel_attn_bwd_mfma_workspace((int64_t)B * S * G, h, S, (int64_t)B * G, S_kv, Dk);
 }
+
+}  // extern "C"
+
+// what both MFMA backwards ask beyond the route of their forward: the shape, aligned operands, O and dO read in 16-byte pieces, one launch
+static bool bwd_mfma_ok(const AttnCall &c, const AttnGrads &g) {
+    return attn_mfma_shape_ok(c.dtype, c.h, c.Dk, c.Dv) && qkv_aligned(c) && ((uintptr_t)g.dO % 16 == 0) && ((uintptr_t)c.O % 16 == 0) &&
+           (int64_t)c.B * c.G <= 65535;
+}
+
+int nsa::sel_attn_bwd_impl(const AttnCall &c, const AttnGrads &g) {
+    NSA_CHECK_ARG(dtype_ok(c.dtype), "sel_attn_bwd: unknown dtype %d", c.dtype);
+    NSA_CHECK_ARG(c.B >= 0 && c.S >= 0 && c.G >= 1 && c.h >= 1 && c.Dk >= 1 && c.Dv >= 1 && c.S_kv >= 0 && c.n >= 0, "sel_attn_bwd: negative size");
+    NSA_CHECK_ARG(c.n <= 64, "sel_attn_bwd: at most 64 ranges per row");
+    NSA_CHECK_ARG(c.Dk <= 256 && c.Dv <= 256, "sel_attn_bwd: Dk/Dv up to 256 supported");
+    NSA_CHECK_ARG(c.variant >= 0 && c.variant <= 2, "sel_attn_bwd: unknown variant %d", c.variant);
+    const int64_t R = c.rows(), nbg = (int64_t)c.B * c.G;
+    const bool empty = R == 0 || c.S_kv == 0 || c.n == 0;
+    const bool fast_ok = !empty && bwd_mfma_ok(c, g) && c.ws && c.ws_bytes >= sel_attn_bwd_mfma_workspace(R, c.h, c.S, nbg, c.S_kv, c.Dk) &&
+                         ((uintptr_t)c.ws % 16 == 0);
+    if (c.variant == 2) NSA_CHECK_ARG(fast_ok, "sel_attn_bwd: MFMA variant requested but shape/dtype/alignment/workspace unsupported");
+    const bool fast = fast_ok && c.variant != 1;
+    if (!fast && nbg * c.S_kv > 0) {  // the generic kernel accumulates with atomics; the MFMA route writes every element
+        NSA_HIP_TRY(hipMemsetAsync(g.dK, 0, sizeof(float) * (size_t)nbg * c.S_kv * c.Dk, c.st));
+        NSA_HIP_TRY(hipMemsetAsync(g.dV, 0, sizeof(float) * (size_t)nbg * c.S_kv * c.Dv, c.st));
+    }
+    if (R == 0) return NSA_OK;
+    if (c.S_kv == 0 || c.n == 0) {
+        NSA_HIP_TRY(hipMemsetAsync(g.dQ, 0, (size_t)R * c.h * c.Dk * esize(c.dtype), c.st));
+        return NSA_OK;
+    }
+    NSA_CHECK_ARG(c.Q && c.K && c.V && c.ranges && c.O && c.lse && g.dO && g.dQ && g.dK && g.dV, "sel_attn_bwd: null pointer");
+    const SelAttnBwdParams P = sel_attn_bwd_params(c, g);
+    if (fast) return launch_sel_attn_bwd_mfma(P, c.dtype, (float *)c.ws, c.st);
+    return launch_sel_attn_bwd_generic(P, c.dtype, c.st);
+}
+
+AttnRoute nsa::band_attn_route(const AttnCall &c, const Band &band) {
+    AttnRoute r{AttnRoute::GENERIC, AttnRoute::WS_NONE,
+                c.S_kv > 0 && band.w > 0 && attn_mfma_shape_ok(c.dtype, c.h, c.Dk, c.Dv) && qkv_aligned(c) && out_aligned(c) && slabs_under_2gib(c), 1};
+    const size_t need = band_attn_workspace(c.B, c.S, c.G, c.h, c.Dk, c.Dv, c.dtype, &r.nsplit);
+    if (r.fast_ok && c.variant != 1) r.kind = AttnRoute::MFMA;
+    if (r.kind == AttnRoute::MFMA && r.nsplit > 1 && c.ws && ((uintptr_t)c.ws % 16 == 0) && c.ws_bytes >= need) r.ws = AttnRoute::WS_SPLIT;
+    return r;
+}
+
+int nsa::band_attn_fwd_impl(const AttnCall &c, const Band &band, int defer, int *ns_used) {
+    if (ns_used) *ns_used = 1;
+    NSA_CHECK_ARG(dtype_ok(c.dtype), "band_attn_fwd: unknown dtype %d", c.dtype);
+    NSA_CHECK_ARG(c.B >= 0 && c.S >= 0 && c.G >= 1 && c.h >= 1 && c.Dk >= 1 && c.Dv >= 1 && c.S_kv >= 0, "band_attn_fwd: negative size");
+    NSA_CHECK_ARG(band.t0 >= 0 && band.dd >= 1 && band.w >= 0, "band_attn_fwd: need t0 >= 0, dd >= 1, w >= 0");
+    NSA_CHECK_ARG(c.variant >= 0 && c.variant <= 2, "band_attn_fwd: unknown variant %d", c.variant);
+    if (c.rows() == 0) return NSA_OK;
+    // S_kv == 0 or w == 0: every interval is empty; the generic kernel writes the zeros / -inf rows
+    NSA_CHECK_ARG(c.Q && c.O && ((c.K && c.V) || c.S_kv == 0), "band_attn_fwd: null pointer");
+    BandAttnParams P = band_attn_params(c, band);
+    const AttnRoute r = band_attn_route(c, band);
+    if (c.variant == 2) NSA_CHECK_ARG(r.fast_ok, "band_attn_fwd: MFMA variant requested but shape/dtype/alignment unsupported");
+    if (r.kind != AttnRoute::MFMA) return launch_band_attn_fwd_generic(P, c.dtype, c.st);
+    if (r.ws == AttnRoute::WS_SPLIT) {
+        P.part = (float *)c.ws;
+        P.nsplit = r.nsplit;
+        P.defer_combine = defer;
+        if (ns_used && defer) *ns_used = r.nsplit;
+    }
+    return launch_band_attn_fwd_mfma(P, c.dtype, c.st);
+}
+
+extern "C" {
 
 int nsa_sel_attn_bwd(const void *Q, const void *K, const void *V, const int32_t *ranges, const void *O,
                      const float *lse, const void *dO, void *dQ, float *dK, float *dV, int B, int S, int G, int h,
                      int Dk, int Dv, int S_kv, int n_ranges, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb,
                      int64_t vsg, int64_t vss, int dtype, float scale, int variant, void *workspace, size_t workspace_bytes,
                      void *stream) {
-    NSA_CHECK_ARG(dtype_ok(dtype), "sel_attn_bwd: unknown dtype %d", dtype);
-    NSA_CHECK_ARG(B >= 0 && S >= 0 && G >= 1 && h >= 1 && Dk >= 1 && Dv >= 1 && S_kv >= 0 && n_ranges >= 0,
-                  "sel_attn_bwd: negative size");
-    NSA_CHECK_ARG(n_ranges <= 64, "sel_attn_bwd: at most 64 ranges per row");
-    NSA_CHECK_ARG(Dk <= 256 && Dv <= 256, "sel_attn_bwd: Dk/Dv up to 256 supported");
-    NSA_CHECK_ARG(variant >= 0 && variant <= 2, "sel_attn_bwd: unknown variant %d", variant);
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t R = (int64_t)B * S * G;
-    const bool empty = R == 0 || S_kv == 0 || n_ranges == 0;
-    const bool fast_ok = !empty && sel_attn_bwd_mfma_supported(dtype, h, Dk, Dv) && qkv_aligned(Q, K, V, ksb, ksg, kss, vsb, vsg, vss) &&
-                         ((uintptr_t)dO % 16 == 0) && ((uintptr_t)O % 16 == 0) && (int64_t)B * G <= 65535 &&
-                         workspace && workspace_bytes >= sel_attn_bwd_mfma_workspace(R, h, S, (int64_t)B * G, S_kv, Dk) && ((uintptr_t)workspace % 16 == 0);
-    if (variant == 2) NSA_CHECK_ARG(fast_ok, "sel_attn_bwd: MFMA variant requested but shape/dtype/alignment/workspace unsupported");
-    const bool fast = fast_ok && variant != 1;
-    if (!fast && (int64_t)B * G * S_kv > 0) {  // the generic kernel accumulates with atomics; the MFMA route writes every element
-        NSA_HIP_TRY(hipMemsetAsync(dK, 0, sizeof(float) * (size_t)B * G * S_kv * Dk, st));
-        NSA_HIP_TRY(hipMemsetAsync(dV, 0, sizeof(float) * (size_t)B * G * S_kv * Dv, st));
-    }
-    if (R == 0) return NSA_OK;
-    if (S_kv == 0 || n_ranges == 0) {
-        const size_t esz = esize(dtype);
-        NSA_HIP_TRY(hipMemsetAsync(dQ, 0, (size_t)R * h * Dk * esz, st));
-        return NSA_OK;
-    }
-    NSA_CHECK_ARG(Q && K && V && ranges && O && lse && dO && dQ && dK && dV, "sel_attn_bwd: null pointer");
-    const SelAttnBwdParams P =
-        sel_attn_bwd_params(Q, K, V, ranges, O, lse, dO, dQ, dK, dV, R, S, G, h, Dk, Dv, S_kv, n_ranges, ksb, ksg, kss, vsb, vsg, vss, scale);
-    if (fast) return launch_sel_attn_bwd_mfma(P, dtype, (float *)workspace, st);
-    return launch_sel_attn_bwd_generic(P, dtype, st);
+    return sel_attn_bwd_impl(AttnCall{Q, K, V, ranges, (void *)O, (float *)lse, B, S, G, h, Dk, Dv, S_kv, n_ranges, ksb, ksg, kss, vsb, vsg, vss, dtype, scale,
+                                      variant, workspace, workspace_bytes, (hipStream_t)stream},
+                             AttnGrads{dO, dQ, dK, dV});
 }
 
 // ------------------------------------------------------------------------------ band attention
@@ -252,50 +303,13 @@ size_t nsa_band_attn_fwd_workspace(int B, int S, int G, int h, int Dk, int Dv, i
     return band_attn_workspace(B, S, G, h, Dk, Dv, dtype, nullptr);
 }
 
-}  // extern "C"
-
-int nsa::band_attn_fwd_impl(const void *Q, const void *K, const void *V, void *O, float *lse, int B, int S, int G, int h, int Dk, int Dv,
-                            int S_kv, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg, int64_t vss, int t0, int a, int dd,
-                            int c, int w, int dtype, float scale, int variant, void *workspace, size_t workspace_bytes, void *stream,
-                            int defer, int *ns_used) {
-    if (ns_used) *ns_used = 1;
-    NSA_CHECK_ARG(dtype_ok(dtype), "band_attn_fwd: unknown dtype %d", dtype);
-    NSA_CHECK_ARG(B >= 0 && S >= 0 && G >= 1 && h >= 1 && Dk >= 1 && Dv >= 1 && S_kv >= 0, "band_attn_fwd: negative size");
-    NSA_CHECK_ARG(t0 >= 0 && dd >= 1 && w >= 0, "band_attn_fwd: need t0 >= 0, dd >= 1, w >= 0");
-    NSA_CHECK_ARG(variant >= 0 && variant <= 2, "band_attn_fwd: unknown variant %d", variant);
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t R = (int64_t)B * S * G;
-    if (R == 0) return NSA_OK;
-    // S_kv == 0 or w == 0: every interval is empty; the generic kernel writes the zeros / -inf rows
-    NSA_CHECK_ARG(Q && O && ((K && V) || S_kv == 0), "band_attn_fwd: null pointer");
-    BandAttnParams P = band_attn_params(Q, K, V, O, lse, B, S, G, h, Dk, Dv, S_kv, ksb, ksg, kss, vsb, vsg, vss, t0, a, dd, c, w, scale);
-    const bool fast_ok = S_kv > 0 && w > 0 && band_attn_mfma_supported(dtype, h, Dk, Dv) && qkv_aligned(Q, K, V, ksb, ksg, kss, vsb, vsg, vss) &&
-                         ((uintptr_t)O % 8 == 0) && (int64_t)S_kv * kss * 2 < ((int64_t)1 << 31) &&
-                         (int64_t)S_kv * vss * 2 < ((int64_t)1 << 31);
-    if (variant == 2) NSA_CHECK_ARG(fast_ok, "band_attn_fwd: MFMA variant requested but shape/dtype/alignment unsupported");
-    if (fast_ok && variant != 1) {
-        int ns = 1;
-        const size_t need = band_attn_workspace(B, S, G, h, Dk, Dv, dtype, &ns);
-        if (ns > 1 && workspace && workspace_bytes >= need && ((uintptr_t)workspace % 16 == 0)) {
-            P.part = (float *)workspace;
-            P.nsplit = ns;
-            P.defer_combine = defer;
-            if (ns_used && defer) *ns_used = ns;
-        }
-        return launch_band_attn_fwd_mfma(P, dtype, st);
-    }
-    return launch_band_attn_fwd_generic(P, dtype, st);
-}
-
-
-extern "C" {
-
 int nsa_band_attn_fwd(const void *Q, const void *K, const void *V, void *O, float *lse, int B, int S, int G, int h, int Dk,
                       int Dv, int S_kv, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg, int64_t vss, int t0,
                       int a, int dd, int c, int w, int dtype, float scale, int variant, void *workspace, size_t workspace_bytes,
                       void *stream) {
-    return band_attn_fwd_impl(Q, K, V, O, lse, B, S, G, h, Dk, Dv, S_kv, ksb, ksg, kss, vsb, vsg, vss, t0, a, dd, c, w, dtype, scale, variant,
-                              workspace, workspace_bytes, stream, 0, nullptr);
+    return band_attn_fwd_impl(AttnCall{Q, K, V, nullptr, O, lse, B, S, G, h, Dk, Dv, S_kv, 0, ksb, ksg, kss, vsb, vsg, vss, dtype, scale, variant, workspace,
+                                       workspace_bytes, (hipStream_t)stream},
+                              Band{t0, a, dd, c, w}, 0, nullptr);
 }
 
 // Band attention backward.  dQ: dense 48-slot kernel (MFMA route); dK/dV: the key-block-major selection backward kernels fed
@@ -318,27 +332,28 @@ int nsa_band_attn_bwd(const void *Q, const void *K, const void *V, const void *O
     NSA_CHECK_ARG(variant >= 0 && variant <= 2, "band_attn_bwd: unknown variant %d", variant);
     const int64_t R = (int64_t)B * S * G;
     if (R == 0) return NSA_OK;
-    hipStream_t st = (hipStream_t)stream;
     const size_t roff = band_bwd_ranges_off(B, S, G, h, Dk, Dv, S_kv, dtype, variant);
     if (int rc = check_workspace("band_attn_bwd", workspace, workspace_bytes, roff + sizeof(int32_t) * 2 * (size_t)R)) return rc;
     int32_t *ranges = (int32_t *)((unsigned char *)workspace + roff);
-    if (int rc = launch_band_ranges(ranges, B, S, G, S_kv, t0, a, dd, c, w, st)) return rc;
-    const bool fast_ok = S_kv > 0 && w > 0 && roff > 0 && band_attn_mfma_supported(dtype, h, Dk, Dv) && sel_attn_bwd_mfma_supported(dtype, h, Dk, Dv) &&
-                         qkv_aligned(Q, K, V, ksb, ksg, kss, vsb, vsg, vss) && ((uintptr_t)dO % 16 == 0) && ((uintptr_t)O % 16 == 0) && (int64_t)B * G <= 65535 && (int64_t)S_kv * kss * 2 < ((int64_t)1 << 31) &&
-                         (int64_t)S_kv * vss * 2 < ((int64_t)1 << 31);
+    // the band as one range per row: what the selection backward (either route) reads; its workspace ends where the ranges begin
+    const AttnCall call{Q, K, V, ranges, (void *)O, (float *)lse, B, S, G, h, Dk, Dv, S_kv, 1, ksb, ksg, kss, vsb, vsg, vss, dtype, scale, variant == 2 ? 0 : variant,
+                        workspace, roff, (hipStream_t)stream};
+    const Band band{t0, a, dd, c, w};
+    const AttnGrads grads{dO, dQ, dK, dV};
+    BandAttnParams BP = band_attn_params(call, band);
+    BP.O = nullptr;  // (the dQ kernel takes lse, delta and dO as its own arguments)
+    BP.lse = nullptr;
+    if (int rc = launch_band_ranges(ranges, BP, call.st)) return rc;
+    const bool fast_ok = band_attn_route(call, band).fast_ok && roff > 0 && bwd_mfma_ok(call, grads);
     if (variant == 2) NSA_CHECK_ARG(fast_ok, "band_attn_bwd: MFMA variant requested but shape/dtype/alignment unsupported");
-    if (!fast_ok || variant == 1)
-        return nsa_sel_attn_bwd(Q, K, V, ranges, O, lse, dO, dQ, dK, dV, B, S, G, h, Dk, Dv, S_kv, 1, ksb, ksg, kss, vsb, vsg, vss, dtype, scale,
-                                variant == 2 ? 0 : variant, workspace, roff, stream);
+    if (!fast_ok || variant == 1) return sel_attn_bwd_impl(call, grads);
     NSA_CHECK_ARG(Q && K && V && O && lse && dO && dQ && dK && dV, "band_attn_bwd: null pointer");
     float *delta = (float *)workspace;
-    if (int rc = launch_bwd_delta(O, dO, delta, R * h, Dv, dtype, st)) return rc;
-    const BandAttnParams BP =
-        band_attn_params(Q, K, V, nullptr, nullptr, B, S, G, h, Dk, Dv, S_kv, ksb, ksg, kss, vsb, vsg, vss, t0, a, dd, c, w, scale);
-    if (int rc = launch_band_attn_bwd_dq(BP, dO, lse, delta, dQ, dtype, st)) return rc;
-    SelAttnBwdParams P = sel_attn_bwd_params(Q, K, V, ranges, O, lse, dO, dQ, dK, dV, R, S, G, h, Dk, Dv, S_kv, 1, ksb, ksg, kss, vsb, vsg, vss, scale);
+    if (int rc = launch_bwd_delta(O, dO, delta, R * h, Dv, dtype, call.st)) return rc;
+    if (int rc = launch_band_attn_bwd_dq(BP, dO, lse, delta, dQ, dtype, call.st)) return rc;
+    SelAttnBwdParams P = sel_attn_bwd_params(call, grads);
     P.skip_delta_dq = 1;
-    return launch_sel_attn_bwd_mfma(P, dtype, delta, st);
+    return launch_sel_attn_bwd_mfma(P, dtype, delta, call.st);
 }
 
 // ------------------------------------------------------------------------------ block meta (host)
@@ -507,35 +522,9 @@ int nsa_sel_select_attn_fwd(const float *p_grp, int t0, const int32_t *t_rows, i
                             const void *V, void *O, float *lse, int B, int S, int G, int h, int Dk, int Dv, int S_kv, int64_t ksb,
                             int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg, int64_t vss, int dtype, float scale, void *workspace,
                             size_t workspace_bytes, void *stream) {
-    NSA_CHECK_ARG(dtype_ok(dtype), "sel_select_attn_fwd: unknown dtype %d", dtype);
-    NSA_CHECK_ARG(B >= 0 && S >= 1 && G >= 1 && h >= 1 && Dk >= 1 && Dv >= 1 && S_kv >= 0 && out_width >= 0, "sel_select_attn_fwd: bad sizes");
-    const int64_t R = (int64_t)B * S * G;
-    if (R == 0) return NSA_OK;
-    NSA_CHECK_ARG(p_grp && ranges_out, "sel_select_attn_fwd: null pointer");
-    int ns = 1;
-    const bool fast_ok = sel_attn_mfma_supported(dtype, h, Dk, Dv) && qkv_aligned(Q, K, V, ksb, ksg, kss, vsb, vsg, vss) && S_kv > 0 && out_width >= 1 && out_width <= 64 && S_sel >= 1 && S_sel <= 1024 &&
-                         (sel_attn_mfma_workspace(R, h, Dv, &ns), ns == 1);
-    // One launch (the selector inside the attention kernel) or two.  The fused selector runs 8 rows one after the other in a wave of a
-    // kernel held to 2 waves per SIMD by its 253 VGPRs: its scalar chains run at latency and it adds 36 / 120 / 424 us at 4k x 8 / 16k x 2 /
-    // 64k x 1, where the select kernel on its own (a row per wave, 6+ waves per SIMD) takes 28 / 57 / 243 us (profiles/r02
-    // i_selector_share.txt): two launches are the default.
-    // (never fused where the attention would split the keys over two XCD groups: that form takes its ranges from memory, and both ways of
-    // calling must give the same bits)
-    const bool fuse = tuning(TUNE_SEL_FUSE) > 0 && sel_attn_ksplit_workspace(dtype, h, Dk, Dv, S, S_kv, out_width, R) == 0;
-    const SelectCall sel{t0, t_rows, n_top, force_init, force_local, mode, S_total, ranges_out, out_width};
-    if (!fast_ok || !fuse) {  // two launches
-        if (int rc = select_topn_impl(p_grp, R, S, G, S_sel, l_sel, sel, (hipStream_t)stream)) return rc;
-        return nsa_sel_attn_fwd(Q, K, V, ranges_out, O, lse, B, S, G, h, Dk, Dv, S_kv, out_width, ksb, ksg, kss, vsb, vsg, vss, dtype, scale, 0,
-                                workspace, workspace_bytes, stream);
-    }
-    NSA_CHECK_ARG(Q && K && V && O, "sel_select_attn_fwd: null pointer");
-    SelectParams SP{};
-    if (int rc = select_params_fill(&SP, p_grp, R, S, G, S_sel, l_sel, sel)) return rc;
-    SelAttnParams P = sel_attn_params(Q, K, V, ranges_out, O, lse, R, S, G, h, Dk, Dv, S_kv, out_width, ksb, ksg, kss, vsb, vsg, vss, scale);
-    P.nsplit = 1;
-    P.fuse_select = 1;
-    P.select = &SP;
-    return launch_sel_attn_fwd_mfma(P, dtype, (hipStream_t)stream);
+    return sel_select_attn_impl(p_grp, S_sel, l_sel, SelectCall{t0, t_rows, n_top, force_init, force_local, mode, S_total, ranges_out, out_width},
+                                AttnCall{Q, K, V, ranges_out, O, lse, B, S, G, h, Dk, Dv, S_kv, out_width, ksb, ksg, kss, vsb, vsg, vss, dtype, scale, 0, workspace,
+                                         workspace_bytes, (hipStream_t)stream});
 }
 
 // ------------------------------------------------------------------------------ fused decode step
@@ -613,6 +602,35 @@ int nsa::select_topn_impl(const float *p_grp, int64_t R, int S, int G, int S_sel
     return launch_select_topn(P, st);
 }
 
+int nsa::sel_select_attn_impl(const float *p_grp, int S_sel, int l_sel, const SelectCall &sel, const AttnCall &c) {
+    NSA_CHECK_ARG(dtype_ok(c.dtype), "sel_select_attn_fwd: unknown dtype %d", c.dtype);
+    NSA_CHECK_ARG(c.B >= 0 && c.S >= 1 && c.G >= 1 && c.h >= 1 && c.Dk >= 1 && c.Dv >= 1 && c.S_kv >= 0 && c.n >= 0, "sel_select_attn_fwd: bad sizes");
+    const int64_t R = c.rows();
+    if (R == 0) return NSA_OK;
+    NSA_CHECK_ARG(p_grp && sel.ranges_out, "sel_select_attn_fwd: null pointer");
+    const AttnRoute r = sel_attn_route(c);
+    const bool fast_ok = r.fast_ok && c.S_kv > 0 && c.n >= 1 && c.n <= 64 && S_sel >= 1 && S_sel <= 1024 && r.nsplit == 1;
+    // One launch (the selector inside the attention kernel) or two.  The fused selector runs 8 rows one after the other in a wave of a
+    // kernel held to 2 waves per SIMD by its 253 VGPRs: its scalar chains run at latency and it adds 36 / 120 / 424 us at 4k x 8 / 16k x 2 /
+    // 64k x 1, where the select kernel on its own (a row per wave, 6+ waves per SIMD) takes 28 / 57 / 243 us (profiles/r02
+    // i_selector_share.txt): two launches are the default.
+    // (never fused where the attention launch of the two calls would split the keys over two XCD groups: that form takes its ranges from
+    // memory, and both ways of calling must give the same bits)
+    const bool fuse = fast_ok && tuning(TUNE_SEL_FUSE) > 0 && !sel_attn_mfma_form(sel_attn_mfma_params(c, r, 0), c.dtype).ksplit;
+    if (!fuse) {  // two launches
+        if (int rc = select_topn_impl(p_grp, R, c.S, c.G, S_sel, l_sel, sel, c.st)) return rc;
+        return sel_attn_fwd_impl(c, 0, nullptr);
+    }
+    NSA_CHECK_ARG(c.Q && c.K && c.V && c.O, "sel_select_attn_fwd: null pointer");
+    SelectParams SP{};
+    if (int rc = select_params_fill(&SP, p_grp, R, c.S, c.G, S_sel, l_sel, sel)) return rc;
+    SelAttnParams P = sel_attn_params(c);
+    P.nsplit = 1;
+    P.fuse_select = 1;
+    P.select = &SP;
+    return launch_sel_attn_fwd_mfma(P, c.dtype, c.st);
+}
+
 // scores + top-n ranges of every row (prefill): on the 32x32x16 scorer route the selection of a query tile runs inside the scorer launch,
 // everywhere else the scorer and the select kernel are launched back to back -- the same ranges bit for bit either way
 int nsa::sel_scores_select_impl(ScoresCall c, const SelectCall &s) {
@@ -660,8 +678,7 @@ int nsa::sel_decode_step_impl(const SelDecodeCall &c, void *workspace, size_t wo
         if (int rc = select_topn_impl(p_grp, c.rows(), 1, c.G, c.S_sel, c.l_sel, sel, sc.st)) return rc;
     }
     if (part_used) *part_used = (float *)(w + a + p);
-    return sel_attn_fwd_impl(c.Q, c.K, c.V, c.ranges_out, c.O, nullptr, c.B, 1, c.G, c.h, c.Dk, c.Dv, c.S_kv, c.n_top, c.ksb, c.ksg, c.kss, c.vsb,
-                             c.vsg, c.vss, c.dtype, c.scale, 0, w + a + p, workspace_bytes - a - p, stream, defer, ns_used);
+    return sel_attn_fwd_impl(attn_call(c, w + a + p, workspace_bytes - a - p, stream), defer, ns_used);
 }
 
 int nsa::sel_decode_rows_impl(const SelDecodeCall &c, void *workspace, size_t workspace_bytes, void *stream) {
@@ -680,8 +697,7 @@ int nsa::sel_decode_rows_impl(const SelDecodeCall &c, void *workspace, size_t wo
     if (int rc = sel_scores_select_impl(scores_call(c, (float *)(w + W.a), 2 /* skipped blocks stay unwritten: only the selector reads p_grp */, 1, w, W.a, stream),
                                         decode_select_call(c)))
         return rc;
-    return nsa_sel_attn_fwd(c.Q, c.K, c.V, c.ranges_out, c.O, nullptr, c.B, c.S, c.G, c.h, c.Dk, c.Dv, c.S_kv, c.n_top, c.ksb, c.ksg, c.kss, c.vsb, c.vsg,
-                            c.vss, c.dtype, c.scale, 0, w + W.a + W.p, workspace_bytes - W.a - W.p, stream);
+    return sel_attn_fwd_impl(attn_call(c, w + W.a + W.p, workspace_bytes - W.a - W.p, stream), 0, nullptr);
 }
 
 extern "C" {
@@ -724,7 +740,7 @@ int nsa_sel_decode_step_plan(int B, int G, int h, int Dk, int Dv, int S_cmp, int
         n += 1;
     } else {
         int ns = 1;
-        if (sel_attn_mfma_supported(dtype, h, Dk, Dv)) sel_attn_mfma_workspace(R, h, Dv, &ns);
+        if (attn_mfma_shape_ok(dtype, h, Dk, Dv)) sel_attn_mfma_workspace(R, h, Dv, &ns);
         n += ns > 1 ? 2 : 1;
     }
     *launches = n;

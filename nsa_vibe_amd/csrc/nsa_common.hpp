@@ -132,9 +132,9 @@ struct Elt<_Float16> {
 };
 
 // the element type of a runtime dtype, once (host): f(T{}) with T = float (F32: where the kernel has an fp32 form), __bf16 or _Float16.
-// The entry points refuse an unknown dtype (dtype_ok) before any launcher runs.
+// The entry points refuse an unknown dtype (dtype_ok) before any launcher runs.  Returns what f returns (a launcher's status, or nothing).
 template <bool F32 = true, typename F>
-static inline void with_elt(int dtype, F &&f) {
+static inline auto with_elt(int dtype, F &&f) {
     if constexpr (F32)
         if (dtype == NSA_DT_F32) return f(float{});
     if (dtype == NSA_DT_BF16) return f(__bf16{});

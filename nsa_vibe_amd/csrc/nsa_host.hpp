@@ -24,13 +24,6 @@ inline int check_workspace(const char *who, const void *ws, size_t bytes, size_t
     return NSA_OK;
 }
 
-// what the MFMA attention kernels ask of their operands: every K / V stride a multiple of 8 elements, Q, K and V 16-byte aligned
-inline bool qkv_aligned(const void *Q, const void *K, const void *V, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg,
-                        int64_t vss) {
-    return kss % 8 == 0 && vss % 8 == 0 && ksb % 8 == 0 && vsb % 8 == 0 && ksg % 8 == 0 && vsg % 8 == 0 && ((uintptr_t)Q % 16 == 0) &&
-           ((uintptr_t)K % 16 == 0) && ((uintptr_t)V % 16 == 0);
-}
-
 // what the MFMA scorer kernels ask of their operands: every K_cmp stride a multiple of 8 elements, Q and K_cmp 16-byte aligned
 inline bool kcmp_aligned(const void *Q, const void *Kc, int64_t csb, int64_t csg, int64_t css) {
     return csb % 8 == 0 && csg % 8 == 0 && css % 8 == 0 && ((uintptr_t)Q % 16 == 0) && ((uintptr_t)Kc % 16 == 0);
@@ -149,40 +142,82 @@ inline LinearCall qkv_call(const nsa_layer_desc *L, const void *x, int rows, con
     return LinearCall{x, L->W_qkv, nullptr, rows, qkv_cols(L), L->dim, L->dtype, 0, nullptr, (hipStream_t)stream, norm_w, eps};
 }
 
-// everything else (split-KV, mapping, fused selector) stays zero: the caller sets what its route needs
-inline SelAttnParams sel_attn_params(const void *Q, const void *K, const void *V, const int32_t *ranges, void *O, float *lse, int64_t R, int S,
-                                     int G, int h, int Dk, int Dv, int S_kv, int n, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb,
-                                     int64_t vsg, int64_t vss, float scale) {
-    SelAttnParams P{};
-    P.Q = Q; P.K = K; P.V = V; P.ranges = ranges; P.O = O; P.lse = lse; P.R = R;
-    P.S = S; P.G = G; P.h = h; P.Dk = Dk; P.Dv = Dv; P.S_kv = S_kv; P.n = n;
-    P.ksb = ksb; P.ksg = ksg; P.kss = kss; P.vsb = vsb; P.vsg = vsg; P.vss = vss;
-    P.scale = default_scale(scale, Dk);
-    return P;
+// What the attention family (nsa_sel_attn_* / nsa_band_attn_* / nsa_sel_select_attn_fwd and everything below them) passes around: the
+// arguments of the C ABI, once.  ranges / n: selection attention only; ws: the call's scratch (split-KV or key-split records)
+struct AttnCall {
+    const void *Q, *K, *V;
+    const int32_t *ranges;
+    void *O;
+    float *lse;
+    int B, S, G, h, Dk, Dv, S_kv, n;
+    int64_t ksb, ksg, kss, vsb, vsg, vss;
+    int dtype;
+    float scale;
+    int variant;
+    void *ws;
+    size_t ws_bytes;
+    hipStream_t st;
+    int64_t rows() const { return (int64_t)B * S * G; }
+};
+// the band of a band-attention call (BandAttnParams): the sliding window of w tokens, and the compressed tokens on their emission schedule
+struct Band {
+    int t0, a, dd, c, w;
+};
+inline Band sliding_band(int t0, int w) { return Band{t0, 0, 1, 0, w}; }
+inline Band compressed_band(int t0, int l, int d) { return Band{t0, l, d, 1, 1 << 30}; }
+struct AttnGrads {
+    const void *dO;
+    void *dQ;
+    float *dK, *dV;
+};
+// the branches of a layer call over the S rows of Q (variant 0, no lse; ws: the branch's scratch): selected, sliding, compressed
+inline AttnCall selected_call(const nsa_layer_desc *L, const nsa_kv_desc *kv, const CacheStrides &C, const void *Q, const int32_t *ranges, void *O, int S,
+                              int S_kv, int n, void *ws, size_t ws_bytes, void *stream) {
+    return AttnCall{Q, kv->K_sel, kv->V_sel, ranges, O, nullptr, kv->B, S, L->G, L->h, L->Dk, L->Dv, S_kv, n, C.ksb, C.ksg, L->Dk, C.vsb, C.vsg, L->Dv,
+                    L->dtype, C.scale, 0, ws, ws_bytes, (hipStream_t)stream};
+}
+inline AttnCall sliding_call(const nsa_layer_desc *L, const nsa_kv_desc *kv, const CacheStrides &C, const void *Q, void *O, int S, int S_kv, void *ws,
+                             size_t ws_bytes, void *stream) {
+    return AttnCall{Q, kv->K_win, kv->V_win, nullptr, O, nullptr, kv->B, S, L->G, L->h, L->Dk, L->Dv, S_kv, 0, C.ksb, C.ksg, L->Dk, C.vsb, C.vsg, L->Dv,
+                    L->dtype, C.scale, 0, ws, ws_bytes, (hipStream_t)stream};
+}
+inline AttnCall compressed_call(const nsa_layer_desc *L, const nsa_kv_desc *kv, const CacheStrides &C, const void *Q, void *O, int S, int n_cmp, void *ws,
+                                size_t ws_bytes, void *stream) {
+    return AttnCall{Q, kv->K_cmp, kv->V_cmp, nullptr, O, nullptr, kv->B, S, L->G, L->h, L->Dk, L->Dv, n_cmp, 0, C.kcb, C.kcg, L->Dk, C.vcb, C.vcg, L->Dv,
+                    L->dtype, C.scale, 0, ws, ws_bytes, (hipStream_t)stream};
+}
+// the attention of a decode-family call's rows over the ranges it selected
+inline AttnCall attn_call(const SelDecodeCall &c, void *ws, size_t ws_bytes, void *stream) {
+    return AttnCall{c.Q, c.K, c.V, c.ranges_out, c.O, nullptr, c.B, c.S, c.G, c.h, c.Dk, c.Dv, c.S_kv, c.n_top, c.ksb, c.ksg, c.kss, c.vsb, c.vsg, c.vss,
+                    c.dtype, c.scale, 0, ws, ws_bytes, (hipStream_t)stream};
 }
 
-inline SelAttnBwdParams sel_attn_bwd_params(const void *Q, const void *K, const void *V, const int32_t *ranges, const void *O, const float *lse,
-                                            const void *dO, void *dQ, float *dK, float *dV, int64_t R, int S, int G, int h, int Dk, int Dv,
-                                            int S_kv, int n, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg, int64_t vss,
-                                            float scale) {
-    SelAttnBwdParams P{};
-    P.Q = Q; P.K = K; P.V = V; P.ranges = ranges; P.O = O; P.lse = lse; P.dO = dO; P.dQ = dQ; P.dK = dK; P.dV = dV;
-    P.R = R; P.S = S; P.G = G; P.h = h; P.Dk = Dk; P.Dv = Dv; P.S_kv = S_kv; P.n = n;
-    P.ksb = ksb; P.ksg = ksg; P.kss = kss; P.vsb = vsb; P.vsg = vsg; P.vss = vss;
-    P.scale = default_scale(scale, Dk);
+// ---- the kernel blocks of a call.  What the three share (P: SelAttnParams, SelAttnBwdParams or BandAttnParams); everything a fill does not
+// name (split-KV, mapping, fused selector) stays zero: the caller sets what its route needs
+template <class P>
+inline P attn_operands(const AttnCall &c) {
+    P p{};
+    p.Q = c.Q; p.K = c.K; p.V = c.V; p.O = c.O; p.lse = c.lse;
+    p.S = c.S; p.G = c.G; p.h = c.h; p.Dk = c.Dk; p.Dv = c.Dv; p.S_kv = c.S_kv;
+    p.ksb = c.ksb; p.ksg = c.ksg; p.kss = c.kss; p.vsb = c.vsb; p.vsg = c.vsg; p.vss = c.vss;
+    p.scale = default_scale(c.scale, c.Dk);
+    return p;
+}
+inline SelAttnParams sel_attn_params(const AttnCall &c) {
+    SelAttnParams P = attn_operands<SelAttnParams>(c);
+    P.ranges = c.ranges; P.R = c.rows(); P.n = c.n;
     return P;
 }
-
-// the split-KV fields stay zero (one split, the kernel's own combine)
-inline BandAttnParams band_attn_params(const void *Q, const void *K, const void *V, void *O, float *lse, int B, int S, int G, int h, int Dk,
-                                       int Dv, int S_kv, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg, int64_t vss, int t0,
-                                       int a, int dd, int c, int w, float scale) {
-    BandAttnParams P{};
-    P.Q = Q; P.K = K; P.V = V; P.O = O; P.lse = lse;
-    P.B = B; P.S = S; P.G = G; P.h = h; P.Dk = Dk; P.Dv = Dv; P.S_kv = S_kv;
-    P.ksb = ksb; P.ksg = ksg; P.kss = kss; P.vsb = vsb; P.vsg = vsg; P.vss = vss;
-    P.scale = default_scale(scale, Dk);
-    P.t0 = t0; P.a = a; P.dd = dd; P.c = c; P.w = w;
+inline SelAttnBwdParams sel_attn_bwd_params(const AttnCall &c, const AttnGrads &g) {
+    SelAttnBwdParams P = attn_operands<SelAttnBwdParams>(c);
+    P.ranges = c.ranges; P.R = c.rows(); P.n = c.n;
+    P.dO = g.dO; P.dQ = g.dQ; P.dK = g.dK; P.dV = g.dV;
+    return P;
+}
+inline BandAttnParams band_attn_params(const AttnCall &c, const Band &b) {
+    BandAttnParams P = attn_operands<BandAttnParams>(c);
+    P.B = c.B;
+    P.t0 = b.t0; P.a = b.a; P.dd = b.dd; P.c = b.c; P.w = b.w;
     return P;
 }
 

@@ -1,7 +1,7 @@
-// Internal forms of the C-ABI entry points and the launchers behind them.  The attention forms take the entry point's arguments plus the
-// split-KV hand-over used by the fused decode step (defer != 0: the partial records stay in the workspace, *ns_used tells how many splits
-// were written; 1 = O is final); the decode-step and the scorer / selector families take their argument blocks (nsa_host.hpp:
-// SelDecodeCall, ScoresCall, SelectCall), filled once by the entry point or built from the block the caller already holds.
+// Internal forms of the C-ABI entry points and the launchers behind them.  Every family takes its argument block (nsa_host.hpp: AttnCall with
+// Band / AttnGrads, SelDecodeCall, ScoresCall, SelectCall), filled once by the entry point or built from the block the caller already holds.
+// The attention forwards add the split-KV hand-over used by the fused decode step (defer != 0: the partial records stay in the workspace,
+// *ns_used tells how many splits were written; 1 = O is final).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -10,12 +10,26 @@
 
 namespace nsa {
 
-int sel_attn_fwd_impl(const void *Q, const void *K, const void *V, const int32_t *ranges, void *O, float *lse, int B, int S, int G, int h,
-                      int Dk, int Dv, int S_kv, int n_ranges, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg, int64_t vss,
-                      int dtype, float scale, int variant, void *workspace, size_t workspace_bytes, void *stream, int defer, int *ns_used);
-int band_attn_fwd_impl(const void *Q, const void *K, const void *V, void *O, float *lse, int B, int S, int G, int h, int Dk, int Dv, int S_kv,
-                       int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg, int64_t vss, int t0, int a, int dd, int c, int w,
-                       int dtype, float scale, int variant, void *workspace, size_t workspace_bytes, void *stream, int defer, int *ns_used);
+struct AttnCall;   // nsa_host.hpp: the arguments of the attention family (nsa_sel_attn_* / nsa_band_attn_* / nsa_sel_select_attn_fwd)
+struct Band;       // nsa_host.hpp: the band of a band-attention call
+struct AttnGrads;  // nsa_host.hpp: dO, dQ, dK, dV
+struct SelectCall;  // nsa_host.hpp: the top-n selection of a call's rows
+int sel_attn_fwd_impl(const AttnCall &c, int defer, int *ns_used);
+int band_attn_fwd_impl(const AttnCall &c, const Band &band, int defer, int *ns_used);
+int sel_attn_bwd_impl(const AttnCall &c, const AttnGrads &g);
+// top-n ranges of the call's rows from p_grp [R, S_sel] into s.ranges_out (= c.ranges), then the attention over them: one launch or two
+int sel_select_attn_impl(const float *p_grp, int S_sel, int l_sel, const SelectCall &s, const AttnCall &c);
+// The route of an attention forward (selection or band), decided in one function each.  fast_ok: the MFMA kernels cover the shape and can
+// read the operands (band: with the forward's extras, out_aligned and slabs_under_2gib); nsplit: the splits of a row the shape asks for (few
+// rows); ws: the call's workspace holds the split records, may hold the block form's key-split records (selection), or is not used
+struct AttnRoute {
+    enum Kind { ZERO_FILL, DECODE_WG, MFMA, GENERIC } kind;
+    enum Ws { WS_NONE, WS_SPLIT, WS_KSPLIT } ws;
+    bool fast_ok;
+    int nsplit;
+};
+AttnRoute sel_attn_route(const AttnCall &c);
+AttnRoute band_attn_route(const AttnCall &c, const Band &band);
 struct DecBandPair;    // sel_attn_params.hpp
 struct SelDecodeCall;  // nsa_host.hpp: the arguments of nsa_sel_decode_step / nsa_sel_decode_rows (S tokens per sequence from t0 on; the step: S = 1)
 // band / band_taken: the layer step's sliding + compressed branches (split form, deferred combine); *band_taken = 1 when the selected branch ran
@@ -25,7 +39,6 @@ int sel_decode_step_impl(const SelDecodeCall &c, void *workspace, size_t workspa
 int sel_decode_rows_impl(const SelDecodeCall &c, void *workspace, size_t workspace_bytes, void *stream);
 
 struct ScoresCall;  // nsa_host.hpp: the arguments of the scorer family (nsa_sel_scores* and every launcher below them)
-struct SelectCall;  // nsa_host.hpp: the top-n selection of a call's rows
 struct SelectParams;  // sel_scores_params.hpp
 // scores + top-n of a decode step's rows in one launch (sel_scores.hip): the shape / tuning part, and with the operands' alignment
 bool decode_score_select_shape_ok(const ScoresCall &c);
@@ -78,8 +91,5 @@ int launch_decode_scores(const ScoresCall &c);
 bool scores_mfma_supported(const ScoresCall &c);  // bf16 / f16, Dk 64 or 128, h <= 16, the default block geometry l = 2d, l' = 4d
 // sel / sel_done: the caller wants the top-n ranges of every row too; *sel_done says whether the launch produced them
 int launch_sel_scores_mfma(const ScoresCall &c, const SelectParams *sel, int *sel_done);
-// sel_attn_generic.hip
-int launch_sel_first_key(const void *V, const int32_t *ranges, void *O, int64_t R, int S, int G, int h, int Dv, int n, int S_kv, int64_t vsb,
-                         int64_t vsg, int64_t vss, int esz, hipStream_t st);
 
 }  // namespace nsa

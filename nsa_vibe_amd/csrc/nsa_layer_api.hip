@@ -176,7 +176,7 @@ static int layer_rows(const char *who, const nsa_layer_desc *L, const nsa_kv_des
     NSA_CHECK_ARG(S_sel >= 1 && (int64_t)S_sel * L->l_sel >= (int64_t)t0 + S, "%s: block metadata (S_sel=%d) does not cover %d tokens", who,
                   S_sel, t0 + S);
     NSA_CHECK_ARG(selector == NSA_SEL_BATCHED || selector == NSA_SEL_SEQUENTIAL, "%s: unknown selector %d", who, selector);
-    const int B = kv->B, G = L->G, h = L->h, Dk = L->Dk, Dv = L->Dv, dt = L->dtype;
+    const int B = kv->B, G = L->G, h = L->h, Dk = L->Dk, dt = L->dtype;
     const int S_kv = t0 + S;
     const RowsWs W = rows_ws(L, B, S, t0, S_sel, norm);
     if (int rc = check_workspace(who, workspace, workspace_bytes, W.total)) return rc;
@@ -190,32 +190,25 @@ static int layer_rows(const char *who, const nsa_layer_desc *L, const nsa_kv_des
     if (n1 > n0)
         if (int rc = nsa_cmp_pool_append(L, kv, n0, n1, stream)) return rc;
     const CacheStrides C(L, kv);
-    const float scale = C.scale;
     // selected branch: scores of rows t0 .. t0 + S - 1 (blocks no selector can read at row t are skipped) -> top-n at their tokens -> the
     // attention over K_sel[:t + 1]
     // (causal_skip 2: skipped blocks stay unwritten, only the selector reads p_grp)
-    const ScoresCall sc{Q, kv->K_cmp, p_grp, csc_ptr, csc_rows, csc_vals, B, S, G, h, Dk, n1, S_sel, C.kcb, C.kcg, Dk, L->l, L->d, L->l_sel, 2, dt, scale,
+    const ScoresCall sc{Q, kv->K_cmp, p_grp, csc_ptr, csc_rows, csc_vals, B, S, G, h, Dk, n1, S_sel, C.kcb, C.kcg, Dk, L->l, L->d, L->l_sel, 2, dt, C.scale,
                         t0, norm, ws + W.sc, W.sc_bytes, (hipStream_t)stream};
     const bool aligned = kcmp_aligned(Q, kv->K_cmp, C.kcb, C.kcg, Dk);
+    const SelectCall select{t0, nullptr, L->n_sel, 1, 2, selector, S, ranges_out, out_width};
+    const AttnCall attend = selected_call(L, kv, C, Q, ranges_out, Osel, S, S_kv, out_width, ws + W.att, W.att_bytes, stream);
     if (!prefill || (aligned && n1 >= 1 && tuning(TUNE_SEL_FUSE) <= 0)) {
         // scores + top-n in one call (on the 32x32x16 scorer's route one LAUNCH, the selection in the scorer's epilogue), then the attention
-        if (int rc = sel_scores_select_impl(sc, SelectCall{t0, nullptr, L->n_sel, 1, 2, selector, S, ranges_out, out_width})) return rc;
-        if (int rc = nsa_sel_attn_fwd(Q, kv->K_sel, kv->V_sel, ranges_out, Osel, nullptr, B, S, G, h, Dk, Dv, S_kv, out_width, C.ksb, C.ksg, Dk,
-                                      C.vsb, C.vsg, Dv, dt, scale, 0, ws + W.att, W.att_bytes, stream))
-            return rc;
-    } else {  // prefill only: the selector inside the attention launch (SEL_FUSE), an unaligned K_cmp, or no compressed token yet
+        if (int rc = sel_scores_select_impl(sc, select)) return rc;
+        if (int rc = sel_attn_fwd_impl(attend, 0, nullptr)) return rc;
+    } else {  // prefill only (t0 = 0): the selector inside the attention launch (SEL_FUSE), an unaligned K_cmp, or no compressed token yet
         if (int rc = sel_scores_impl(sc, aligned ? 0 : 1)) return rc;
-        if (int rc = nsa_sel_select_attn_fwd(p_grp, 0, nullptr, S_sel, L->l_sel, L->n_sel, 1, 2, selector, S, ranges_out, out_width, Q, kv->K_sel,
-                                             kv->V_sel, Osel, nullptr, B, S, G, h, Dk, Dv, S, C.ksb, C.ksg, Dk, C.vsb, C.vsg, Dv, dt, scale,
-                                             ws + W.att, W.att_bytes, stream))
-            return rc;
+        if (int rc = sel_select_attn_impl(p_grp, S_sel, L->l_sel, select, attend)) return rc;
     }
     // sliding and compressed branches at the rows' absolute positions
-    if (int rc = nsa_band_attn_fwd(Q, kv->K_win, kv->V_win, Owin, nullptr, B, S, G, h, Dk, Dv, S_kv, C.ksb, C.ksg, Dk, C.vsb, C.vsg, Dv, t0, 0, 1, 0,
-                                   L->w, dt, scale, 0, ws + W.band, W.band_bytes, stream))
-        return rc;
-    if (int rc = nsa_band_attn_fwd(Q, kv->K_cmp, kv->V_cmp, Ocmp, nullptr, B, S, G, h, Dk, Dv, n1, C.kcb, C.kcg, Dk, C.vcb, C.vcg, Dv, t0, L->l,
-                                   L->d, 1, 1 << 30, dt, scale, 0, ws + W.band, W.band_bytes, stream))
+    if (int rc = band_attn_fwd_impl(sliding_call(L, kv, C, Q, Owin, S, S_kv, ws + W.band, W.band_bytes, stream), sliding_band(t0, L->w), 0, nullptr)) return rc;
+    if (int rc = band_attn_fwd_impl(compressed_call(L, kv, C, Q, Ocmp, S, n1, ws + W.band, W.band_bytes, stream), compressed_band(t0, L->l, L->d), 0, nullptr))
         return rc;
     return nsa_gate_combine(L, Q, Ocmp, Osel, Owin, O_mix, gates_out, (int64_t)B * S * G, stream);
 }
@@ -280,29 +273,6 @@ size_t nsa_layer_decode_step_workspace(const nsa_layer_desc *L, int B, int S_max
     return decode_ws(L, B, S_max).total;
 }
 
-// The sliding and the compressed branch of S rows at t0 as ONE launch (launch_band_attn_fwd_dual): both in split form with the combine left to
-// the finish kernel (defer: Dv = 64).  *ns_band = the splits of a branch at (B, S)
-static bool band_pair_dual(const nsa_layer_desc *L, const nsa_kv_desc *kv, const CacheStrides &C, int S, int n_cmp, int defer, int *ns_band) {
-    *ns_band = 1;
-    band_attn_workspace(kv->B, S, L->G, L->h, L->Dk, L->Dv, L->dtype, ns_band);
-    return defer && *ns_band > 1 && n_cmp > 0 && L->w > 0 && band_attn_mfma_supported(L->dtype, L->h, L->Dk, L->Dv) &&
-           ((uintptr_t)kv->K_win % 16 == 0) && ((uintptr_t)kv->V_win % 16 == 0) && ((uintptr_t)kv->K_cmp % 16 == 0) &&
-           ((uintptr_t)kv->V_cmp % 16 == 0) && C.ksb * 2 < ((int64_t)1 << 31) && C.vsb * 2 < ((int64_t)1 << 31);
-}
-// their argument blocks: rows t0 .. t0 + S - 1 over K_win[:t0 + S] (the last w tokens) and over the n_cmp compressed tokens (emission schedule)
-static void band_pair_fill(DecBandPair &BP, const nsa_layer_desc *L, const nsa_kv_desc *kv, const CacheStrides &C, const void *Q, void *Owin,
-                           void *Ocmp, int S, int t0, int n_cmp, int ns_band, float *part_w, float *part_c) {
-    BandAttnParams &PW = BP.w, &PC = BP.c;
-    PW = band_attn_params(Q, kv->K_win, kv->V_win, Owin, nullptr, kv->B, S, L->G, L->h, L->Dk, L->Dv, t0 + S, C.ksb, C.ksg, L->Dk, C.vsb, C.vsg,
-                          L->Dv, t0, 0, 1, 0, L->w, C.scale);
-    PW.part = part_w; PW.nsplit = ns_band; PW.defer_combine = 1;
-    PC = PW;
-    PC.K = kv->K_cmp; PC.V = kv->V_cmp; PC.O = Ocmp; PC.S_kv = n_cmp;
-    PC.ksb = C.kcb; PC.ksg = C.kcg; PC.vsb = C.vcb; PC.vsg = C.vcg;
-    PC.a = L->l; PC.dd = L->d; PC.c = 1; PC.w = 1 << 30;
-    PC.part = part_c;
-}
-
 // One layer decode call over S rows per sequence at t0 .. t0 + S - 1: what its prologue checks, carves from the workspace and derives
 struct LayerDecode {
     const nsa_layer_desc *L;
@@ -334,6 +304,31 @@ static int layer_decode_begin(const char *who, const nsa_layer_desc *L, const ns
     unsigned char *ws = (unsigned char *)workspace;
     *D = LayerDecode{L, kv, W, ws, ws + W.q, ws + W.ocmp, ws + W.osel, ws + W.owin, ws + W.omix, S, t0, ncmp_of(t0, L->l, L->d), ncmp_of(t0 + S, L->l, L->d)};
     return NSA_OK;
+}
+
+// The sliding and the compressed branch of the call's rows: over K_win[:t0 + S] (the last w tokens) and over the n1 compressed tokens
+// (emission schedule), each with its own scratch
+struct BandBranches {
+    AttnCall w, c;
+    Band bw, bc;
+};
+static BandBranches band_branches(const LayerDecode &D, const CacheStrides &C, void *stream) {
+    return BandBranches{sliding_call(D.L, D.kv, C, D.Q, D.Owin, D.S, D.t0 + D.S, D.ws + D.W.band, D.W.band_bytes, stream),
+                        compressed_call(D.L, D.kv, C, D.Q, D.Ocmp, D.S, D.n1, D.ws + D.W.band2, D.W.band_bytes, stream), sliding_band(D.t0, D.L->w),
+                        compressed_band(D.t0, D.L->l, D.L->d)};
+}
+// Both as ONE launch (launch_band_attn_fwd_dual, or riding on the selected branch's): both in split form with the combine left to the finish
+// kernel (defer: Dv = 64); BP gets their blocks.  (The whole-cache bound is this launch's own: stricter than the slab bound of the route.)
+static bool band_pair(const LayerDecode &D, const CacheStrides &C, int defer, DecBandPair &BP) {
+    const BandBranches b = band_branches(D, C, nullptr);
+    const AttnRoute rw = band_attn_route(b.w, b.bw), rc = band_attn_route(b.c, b.bc);
+    if (!(defer && rw.nsplit > 1 && rw.fast_ok && rc.fast_ok && C.ksb * 2 < ((int64_t)1 << 31) && C.vsb * 2 < ((int64_t)1 << 31))) return false;
+    BP.w = band_attn_params(b.w, b.bw);
+    BP.c = band_attn_params(b.c, b.bc);
+    BP.w.part = (float *)b.w.ws; BP.c.part = (float *)b.c.ws;
+    BP.w.nsplit = BP.c.nsplit = rw.nsplit;
+    BP.w.defer_combine = BP.c.defer_combine = 1;
+    return true;
 }
 
 // the selected branch of the call as the decode family's argument block (ranges_out null: the ranges stay in the workspace)
@@ -370,7 +365,7 @@ static int layer_decode_tail(const LayerDecode &D, const CacheStrides &C, Decode
     const nsa_layer_desc *L = D.L;
     const nsa_kv_desc *kv = D.kv;
     hipStream_t st = (hipStream_t)stream;
-    const int B = kv->B, S = D.S, G = L->G, h = L->h, Dk = L->Dk, Dv = L->Dv, dt = L->dtype, t0 = D.t0, defer = Dv == 64 ? 1 : 0;
+    const int B = kv->B, S = D.S, G = L->G, dt = L->dtype, defer = L->Dv == 64 ? 1 : 0;
     if (BP) {
         if (!ridden)
             if (int rc = launch_band_attn_fwd_dual(BP->w, BP->c, dt, st)) return rc;
@@ -378,14 +373,11 @@ static int layer_decode_tail(const LayerDecode &D, const CacheStrides &C, Decode
         F.part[2] = BP->w.part;
         F.part[0] = BP->c.part;
     } else {
-        if (int rc = band_attn_fwd_impl(D.Q, kv->K_win, kv->V_win, D.Owin, nullptr, B, S, G, h, Dk, Dv, t0 + S, C.ksb, C.ksg, Dk, C.vsb, C.vsg, Dv, t0, 0,
-                                        1, 0, L->w, dt, C.scale, 0, D.ws + D.W.band, D.W.band_bytes, stream, defer, &F.ns[2]))
-            return rc;
-        F.part[2] = (const float *)(D.ws + D.W.band);
-        if (int rc = band_attn_fwd_impl(D.Q, kv->K_cmp, kv->V_cmp, D.Ocmp, nullptr, B, S, G, h, Dk, Dv, D.n1, C.kcb, C.kcg, Dk, C.vcb, C.vcg, Dv, t0, L->l,
-                                        L->d, 1, 1 << 30, dt, C.scale, 0, D.ws + D.W.band2, D.W.band_bytes, stream, defer, &F.ns[0]))
-            return rc;
-        F.part[0] = (const float *)(D.ws + D.W.band2);
+        const BandBranches b = band_branches(D, C, stream);
+        if (int rc = band_attn_fwd_impl(b.w, b.bw, defer, &F.ns[2])) return rc;
+        F.part[2] = (const float *)b.w.ws;
+        if (int rc = band_attn_fwd_impl(b.c, b.bc, defer, &F.ns[0])) return rc;
+        F.part[0] = (const float *)b.c.ws;
     }
     if (defer) {
         if (int rc = launch_decode_finish(F, dt, st)) return rc;
@@ -417,10 +409,8 @@ static int layer_decode_step_impl(const nsa_layer_desc *L, const nsa_kv_desc *kv
     // 4 + 5. the three branches.  The sliding and the compressed branch run in split-KV form with the combine left to the finish kernel; when
     // the selected branch runs as the one-launch decode step they ride on ITS launch (workgroups behind the step's own: sel_decode_fused.hip),
     // otherwise they are one launch of their own.
-    int ns_band = 1;
-    const bool dual = band_pair_dual(L, kv, C, 1, n_cmp, defer, &ns_band);
     DecBandPair BP{};
-    if (dual) band_pair_fill(BP, L, kv, C, D.Q, D.Owin, D.Ocmp, 1, t, n_cmp, ns_band, (float *)(D.ws + D.W.band), (float *)(D.ws + D.W.band2));
+    const bool dual = band_pair(D, C, defer, BP);
     const int band_mode = tuning(TUNE_DECODE_BAND);  // 0 own launch, 1 ride, 2 ride + merge in the workgroup, -1 / 3: 2 + the mix in the output projection
     const bool ride = dual && Dk == 64 && band_mode != 0;
     float *gates = gates_out ? gates_out : (float *)(D.ws + D.W.gates);
@@ -476,8 +466,8 @@ static bool layer_decode_rows_route(const nsa_layer_desc *L, int B, int S, int S
         if (nsa_sel_decode_rows_plan(B, S, L->G, L->h, L->Dk, L->Dv, n1, S_sel, t0 + S, L->n_sel, L->dtype, &nl, &form) != NSA_OK || nl < 2) nl = 3;
         n += nl;
     }
-    int ns_band = 1;
-    n += band_pair_dual(L, &kv, C, S, n1, L->Dv == 64 ? 1 : 0, &ns_band) ? 1 : 2;  // (an undeferred split branch adds its combine: not counted)
+    DecBandPair BP{};  // (an undeferred split branch adds its combine: not counted)
+    n += band_pair(LayerDecode{L, &kv, DecodeWs{}, nullptr, kv.K_sel, kv.K_sel, kv.K_sel, kv.K_sel, kv.K_sel, S, t0, n0, n1}, C, L->Dv == 64 ? 1 : 0, BP) ? 1 : 2;
     n += 2;                                                                          // finish (or gate + mix), output projection
     *launches = n;
     *route = one ? 1 : 0;
@@ -508,10 +498,8 @@ static int layer_decode_rows_impl(const nsa_layer_desc *L, const nsa_kv_desc *kv
     // 5. split combine + gates + mix, 6. output projection of the B S rows
     DecodeFinishParams F = decode_finish_params(D, gates_out);
     F.ns[1] = 1;
-    int ns_band = 1;
     DecBandPair BP{};
-    const bool dual = band_pair_dual(L, kv, C, S, D.n1, L->Dv == 64 ? 1 : 0, &ns_band);
-    if (dual) band_pair_fill(BP, L, kv, C, D.Q, D.Owin, D.Ocmp, S, t0, D.n1, ns_band, (float *)(D.ws + D.W.band), (float *)(D.ws + D.W.band2));
+    const bool dual = band_pair(D, C, L->Dv == 64 ? 1 : 0, BP);
     return layer_decode_tail(D, C, F, dual ? &BP : nullptr, false, gates_out, y, residual, stream);
 }
 

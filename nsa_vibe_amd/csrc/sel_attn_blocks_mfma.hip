@@ -560,11 +560,10 @@ __global__ __launch_bounds__(256) void sel_attn_ksplit_combine_kernel(const floa
 // key-split form wanted for this shape?  TUNE_SEL_KSPLIT: -1 = by the K/V footprint of a (b,g) pair against the 4 MiB of L2 per XCD, 0 never,
 // 1 always.  The zones of the form (rows walked whole / in two / in four key classes) follow the rows' positions, so a short context is all
 // zone 0 and costs nothing but the different workgroup order; the rule below is where the measured gain starts (profiles/r04/key_split_zones.txt).
-static bool ksplit_rule(int dtype, int h, int Dk, int Dv, int S, int S_kv, int n, int64_t R) {
+static bool ksplit_rule(int dtype, int Dk, int Dv, int S, int S_kv) {
     const int mode = tuning(TUNE_SEL_KSPLIT);
     if (mode == 0 || S <= 0 || Dv != 64 || Dk != 64 || !(dtype == NSA_DT_BF16 || dtype == NSA_DT_F16)) return false;
     if (mode > 0) return true;
-    (void)n, (void)R;
     return S_kv >= 32768;  // (at 32k no row is split yet: the shared-walk workgroup order alone is 0.96 x the plain order; 0.89 x at 48k, 0.80-0.82 x at 64k)
 }
 // zone boundaries in rows of a (b,g), multiples of the rows of one workgroup: rows whose position (row + S_kv - S: the rows are the last S
@@ -584,7 +583,7 @@ static void ksplit_zones(int h, int S, int S_kv, int *r1, int *r2) {
     *r2 = rows_below(t2 > t1 ? t2 : t1);
 }
 size_t sel_attn_ksplit_workspace(int dtype, int h, int Dk, int Dv, int S, int S_kv, int n, int64_t R) {
-    if (!ksplit_rule(dtype, h, Dk, Dv, S, S_kv, n, R) || h < 1 || h > 16) return 0;
+    if (!ksplit_rule(dtype, Dk, Dv, S, S_kv) || h < 1 || h > 16) return 0;
     int r1, r2;
     ksplit_zones(h, S, S_kv, &r1, &r2);
     const int64_t nbg = R / S;
@@ -594,10 +593,10 @@ size_t sel_attn_ksplit_workspace(int dtype, int h, int Dk, int Dv, int S, int S_
 }
 
 // Column tiles per wave for a shape, 0 = not covered (the query-tile kernel takes it).  TUNE_SEL_BLOCKS: -1 auto, 0 off, N forces NT = N.
-int sel_attn_blocks_nt(int dtype, int h, int Dk, int Dv, int S, int S_kv, int n, int64_t R, int64_t kss, int64_t vss) {
-    if (!(dtype == NSA_DT_BF16 || dtype == NSA_DT_F16) || Dk != 64 || Dv != 64 || h < 1 || h > 16) return 0;
-    if (n < 1 || n > 64 || S_kv < 1 || S_kv > 131072) return 0;
-    if (kss != 64 || vss != 64) return 0;  // the DMA steps through rows 128 B apart (rows of a [.., S, 64] cache are)
+int sel_attn_blocks_nt(const SelAttnParams &P, int dtype) {
+    const int h = P.h, S = P.S;
+    if (!attn_mfma_shape_ok(dtype, h, P.Dk, P.Dv) || P.Dk != 64 || P.n < 1 || P.n > 64 || P.S_kv < 1 || P.S_kv > 131072) return 0;
+    if (P.kss != 64 || P.vss != 64) return 0;  // the DMA steps through rows 128 B apart (rows of a [.., S, 64] cache are)
     const int mode = tuning(TUNE_SEL_BLOCKS);
     if (mode == 0) return 0;
     // automatic choice: the block form wherever it applies.  Same-box A/B (profiles/r02/c_kernel_form_sweep_3.txt): 5-25 % faster than the
@@ -609,7 +608,6 @@ int sel_attn_blocks_nt(int dtype, int h, int Dk, int Dv, int S, int S_kv, int n,
     if (nt * tpt > 32) return 0;
     while (nt > 1 && S < 2 * nt * tpt) nt >>= 1;  // short sequences: do not leave most of a wave's tiles empty
     if (S < tpt) return 0;
-    (void)R;
     return nt;
 }
 
@@ -650,10 +648,7 @@ static int launch_blocks_t(const SelAttnParams &P0, hipStream_t st) {
     int cand = 0;
     if (P.fuse_select) {
         NSA_CHECK_ARG(P.select != nullptr, "fused selection without selector parameters");
-        SP = *(const SelectParams *)P.select;
-        const int c = (SP.S_sel + 63) / 64;
-        NSA_CHECK_ARG(c <= 16 && SP.W <= 64 && SP.W == P.n, "fused selection: S_sel <= 1024 and at most 64 ranges per row");
-        cand = c <= 1 ? 1 : c <= 2 ? 2 : c <= 4 ? 4 : c <= 8 ? 8 : 16;
+        NSA_CHECK_ARG(fused_select_args(P, &SP, &cand) && SP.W <= 64 && SP.W == P.n, "fused selection: S_sel <= 1024 and at most 64 ranges per row");
     }
     void (*k)(SelAttnParams, SelectParams, int) = tuning(TUNE_SEL_ROWSUM) ? sel_attn_blocks_mfma_kernel<T, NT, true, FLAT, KSPLIT>
                                                                           : sel_attn_blocks_mfma_kernel<T, NT, false, FLAT, KSPLIT>;
@@ -673,27 +668,15 @@ static int launch_blocks_t(const SelAttnParams &P0, hipStream_t st) {
     return NSA_OK;
 }
 
-int launch_sel_attn_blocks_mfma(const SelAttnParams &P, int dtype, int nt, hipStream_t st) {
-    // 8 rows per wave with h = 6: three fully used column tiles instead of four with 12 of 16 columns.  It pays while the rows of a wave share
-    // their blocks (every tile of a block is computed anyway: -10 % at 2k, -8 % at 4k); once a block belongs to one row (S_kv >> n l') the
-    // four-tile form computes the one tile of that row and skips three, the flat form needs two tiles for the straddling rows 2 and 5
-    // (+3 % at 16k, +4..10 % at 64k; same-box A/B, profiles/r02/k_flat_columns.txt).  TUNE_SEL_FLAT: -1 this rule, 0 never, 1 always.
-    const int fmode = tuning(TUNE_SEL_FLAT);
-    const bool flat = nt == 4 && P.h == 6 && (fmode > 0 || (fmode < 0 && (int64_t)P.S_kv <= (int64_t)384 * P.n));
-    // key halves on different XCDs (see the kernel): needs the caller's workspace, no fused selector, and the walk of a row group long enough
-    const size_t ks_need = (nt == 4 && !flat && !P.fuse_select) ? sel_attn_ksplit_workspace(dtype, P.h, P.Dk, P.Dv, P.S, P.S_kv, P.n, P.R) : 0;
-    if (ks_need > 0 && P.ks_ws && P.ks_bytes >= ks_need)
-        return dtype == NSA_DT_BF16 ? launch_blocks_t<__bf16, 4, false, true>(P, st) : launch_blocks_t<_Float16, 4, false, true>(P, st);
-    if (dtype == NSA_DT_BF16) {
-        if (flat) return launch_blocks_t<__bf16, 3, true>(P, st);
-        if (nt == 4) return launch_blocks_t<__bf16, 4, false>(P, st);
-        if (nt == 2) return launch_blocks_t<__bf16, 2, false>(P, st);
-        return launch_blocks_t<__bf16, 1, false>(P, st);
-    }
-    if (flat) return launch_blocks_t<_Float16, 3, true>(P, st);
-    if (nt == 4) return launch_blocks_t<_Float16, 4, false>(P, st);
-    if (nt == 2) return launch_blocks_t<_Float16, 2, false>(P, st);
-    return launch_blocks_t<_Float16, 1, false>(P, st);
+int launch_sel_attn_blocks_mfma(const SelAttnParams &P, int dtype, const SelAttnForm &f, hipStream_t st) {
+    return with_elt<false>(dtype, [&](auto t) {
+        using T = decltype(t);
+        return f.ksplit    ? launch_blocks_t<T, 4, false, true>(P, st)
+               : f.flat    ? launch_blocks_t<T, 3, true>(P, st)
+               : f.nt == 4 ? launch_blocks_t<T, 4, false>(P, st)
+               : f.nt == 2 ? launch_blocks_t<T, 2, false>(P, st)
+                           : launch_blocks_t<T, 1, false>(P, st);
+    });
 }
 
 }  // namespace nsa

@@ -965,10 +965,6 @@ static int dkdv_splits(int S) {
     return ns < 1 ? 1 : (ns > 16 ? 16 : ns);
 }
 
-bool sel_attn_bwd_mfma_supported(int dtype, int h, int Dk, int Dv) {
-    return (dtype == NSA_DT_BF16 || dtype == NSA_DT_F16) && Dk == Dv && (Dk == 64 || Dk == 128) && h >= 1 && h <= 16;
-}
-
 // workspace layout: delta [R*h] f32 | hit map [nbg][nkb][ceil(S/64)] u64 | full map (same shape) | flags [ns][nbg][nkb] i32 | ns partial [dK|dV] slabs
 struct BwdWs {
     size_t hitmap, fullmap, flags, part, total, hitmap_bytes;
@@ -1031,8 +1027,7 @@ static int launch_bwd_t(const SelAttnBwdParams &P, float *delta, hipStream_t st)
             NSA_LAUNCH_CHECK("bwd_dq");
         }
     }
-    const int64_t nbg = (int64_t)(P.R / P.S);
-    NSA_CHECK_ARG(nbg <= 65535, "bwd: B*G too large for one launch");
+    const int64_t nbg = (int64_t)(P.R / P.S);  // (at most 65535: both entry points test it)
     const BwdWs W = bwd_ws_layout(P.R, P.h, P.S, nbg, P.S_kv, D);
     const int ns = W.ns;
     const int rows_per_split = ((P.S + ns - 1) / ns + 255) / 256 * 256;
@@ -1066,29 +1061,17 @@ extern "C" __attribute__((visibility("default"))) int nsa_dbg_read(void *host) {
 }
 #endif
 int launch_sel_attn_bwd_mfma(const SelAttnBwdParams &P, int dtype, float *delta_ws, hipStream_t st) {
-    NSA_CHECK_ARG(sel_attn_bwd_mfma_supported(dtype, P.h, P.Dk, P.Dv), "bwd MFMA: unsupported dtype/h/D");
-    NSA_CHECK_ARG(P.kss % 8 == 0 && P.vss % 8 == 0 && P.ksb % 8 == 0 && P.vsb % 8 == 0 && P.ksg % 8 == 0 && P.vsg % 8 == 0,
-                  "bwd MFMA: K/V strides must be multiples of 8 elements");
-    NSA_CHECK_ARG((int64_t)P.S_kv * P.kss * 2 < ((int64_t)1 << 31) && (int64_t)P.S_kv * P.vss * 2 < ((int64_t)1 << 31),
-                  "bwd MFMA: one (b,g) K/V slab must be smaller than 2 GiB");
-    if (dtype == NSA_DT_BF16) return P.Dk == 64 ? launch_bwd_t<__bf16, 64>(P, delta_ws, st) : launch_bwd_t<__bf16, 128>(P, delta_ws, st);
-    return P.Dk == 64 ? launch_bwd_t<_Float16, 64>(P, delta_ws, st) : launch_bwd_t<_Float16, 128>(P, delta_ws, st);
-}
-
-template <typename T>
-static void launch_bwd_delta_t(const void *O, const void *dO, float *delta, int64_t n_rows, int Dv, hipStream_t st) {
-    if (Dv == 64)
-        hipLaunchKernelGGL((bwd_delta_kernel<T, 64>), dim3((unsigned)((n_rows * 8 + 255) / 256)), dim3(256), 0, st, (const T *)O, (const T *)dO,
-                           delta, n_rows, Dv);
-    else
-        hipLaunchKernelGGL((bwd_delta_kernel<T, 128>), dim3((unsigned)((n_rows * 16 + 255) / 256)), dim3(256), 0, st, (const T *)O, (const T *)dO,
-                           delta, n_rows, Dv);
+    NSA_CHECK_ARG(slabs_under_2gib(P), "bwd MFMA: one (b,g) K/V slab must be smaller than 2 GiB");
+    return with_elt<false>(dtype, [&](auto t) { return P.Dk == 64 ? launch_bwd_t<decltype(t), 64>(P, delta_ws, st) : launch_bwd_t<decltype(t), 128>(P, delta_ws, st); });
 }
 
 int launch_bwd_delta(const void *O, const void *dO, float *delta, int64_t n_rows, int Dv, int dtype, hipStream_t st) {
-    NSA_CHECK_ARG((Dv == 64 || Dv == 128) && (dtype == NSA_DT_BF16 || dtype == NSA_DT_F16), "bwd_delta: bf16/f16 with Dv = 64 or 128 only");
-    if (dtype == NSA_DT_BF16) launch_bwd_delta_t<__bf16>(O, dO, delta, n_rows, Dv, st);
-    else launch_bwd_delta_t<_Float16>(O, dO, delta, n_rows, Dv, st);
+    const dim3 grid((unsigned)((n_rows * (Dv / 8) + 255) / 256));
+    with_elt<false>(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (Dv == 64) hipLaunchKernelGGL((bwd_delta_kernel<T, 64>), grid, dim3(256), 0, st, (const T *)O, (const T *)dO, delta, n_rows, Dv);
+        else hipLaunchKernelGGL((bwd_delta_kernel<T, 128>), grid, dim3(256), 0, st, (const T *)O, (const T *)dO, delta, n_rows, Dv);
+    });
     NSA_LAUNCH_CHECK("bwd_delta");
     return NSA_OK;
 }
@@ -1104,10 +1087,10 @@ __global__ __launch_bounds__(256) void band_ranges_kernel(int32_t *__restrict__ 
     ranges[2 * row + 1] = hi;
 }
 
-int launch_band_ranges(int32_t *ranges, int B, int S, int G, int S_kv, int t0, int a, int dd, int c, int w, hipStream_t st) {
-    const int64_t R = (int64_t)B * S * G;
+int launch_band_ranges(int32_t *ranges, const BandAttnParams &P, hipStream_t st) {
+    const int64_t R = (int64_t)P.B * P.S * P.G;
     if (R == 0) return NSA_OK;
-    hipLaunchKernelGGL(band_ranges_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, ranges, R, S, G, S_kv, t0, a, dd, c, w);
+    hipLaunchKernelGGL(band_ranges_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, ranges, R, P.S, P.G, P.S_kv, P.t0, P.a, P.dd, P.c, P.w);
     NSA_LAUNCH_CHECK("band_ranges");
     return NSA_OK;
 }

@@ -2,6 +2,7 @@
 // Used by the decode routes that do not run the fused scorer+selector+attention kernel (contexts beyond its LDS budget, other
 // score geometries, the plain nsa_sel_attn_fwd call with S = 1).
 #include "sel_attn_decode.hpp"
+#include "nsa_host.hpp"
 
 namespace nsa {
 
@@ -30,27 +31,22 @@ int dec_att_waves(int64_t rows, int D) {
 
 bool sel_attn_decode_wg_shape_ok(int dtype, int h, int Dk, int Dv, int n) {
     if (tuning(TUNE_DECODE_WG) == 0) return false;
-    return (dtype == NSA_DT_BF16 || dtype == NSA_DT_F16) && Dk == Dv && (Dk == 64 || Dk == 128) && h >= 1 && h <= 16 && n >= 1 && n <= 64;
+    return attn_mfma_shape_ok(dtype, h, Dk, Dv) && n >= 1 && n <= 64;
 }
 
-bool sel_attn_decode_wg_supported(int dtype, int h, int Dk, int Dv, int n, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg,
-                                  int64_t vss, const void *Q, const void *K, const void *V) {
-    // 16-byte global loads and LDS-DMA pieces at K + b ksb + g ksg (+ row kss): every stride a multiple of 8 elements
-    return sel_attn_decode_wg_shape_ok(dtype, h, Dk, Dv, n) && vss == Dv &&
-           kss % 8 == 0 && ksb % 8 == 0 && ksg % 8 == 0 && vsb % 8 == 0 && vsg % 8 == 0 && ((uintptr_t)Q % 16 == 0) && ((uintptr_t)K % 16 == 0) && ((uintptr_t)V % 16 == 0);
+bool sel_attn_decode_wg_supported(const AttnCall &c) {
+    return sel_attn_decode_wg_shape_ok(c.dtype, c.h, c.Dk, c.Dv, c.n) && c.vss == c.Dv && qkv_aligned(c);
 }
 
-int launch_sel_attn_decode_wg(const void *Q, const void *K, const void *V, const int32_t *ranges, void *O, int64_t R, int G, int h, int S_kv, int n,
-                              int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg, int64_t vss, int dtype, float scale, hipStream_t st, int D) {
-    NSA_CHECK_ARG(D == 64 || D == 128, "sel_attn_decode: head dimension 64 or 128");
-    NSA_CHECK_ARG(R >= 1 && R < ((int64_t)1 << 31), "sel_attn_decode: bad row count");
-    NSA_CHECK_ARG((int64_t)S_kv * 2 * D < ((int64_t)1 << 31), "sel_attn_decode: one (b,g) V slab must be smaller than 2 GiB (buffer addressing)");
-    DecAttnArgs A{Q, K, V, O, G, h, S_kv, n, ksb, ksg, kss, vsb, vsg, vss, scale * LOG2E};
-    const int nw = dec_att_waves(R, D);
-    void (*k)(DecAttnArgs, const int32_t *) =
-        D == 128 ? (dtype == NSA_DT_BF16 ? sel_attn_decode_wg_kernel<__bf16, 8, 128> : sel_attn_decode_wg_kernel<_Float16, 8, 128>)
-        : nw == 16 ? (dtype == NSA_DT_BF16 ? sel_attn_decode_wg_kernel<__bf16, 16> : sel_attn_decode_wg_kernel<_Float16, 16>)
-                 : (dtype == NSA_DT_BF16 ? sel_attn_decode_wg_kernel<__bf16, 8> : sel_attn_decode_wg_kernel<_Float16, 8>);
+int launch_sel_attn_decode_wg(const SelAttnParams &P, int dtype, hipStream_t st) {
+    NSA_CHECK_ARG(P.R >= 1 && P.R < ((int64_t)1 << 31), "sel_attn_decode: bad row count");
+    DecAttnArgs A{P.Q, P.K, P.V, P.O, P.G, P.h, P.S_kv, P.n, P.ksb, P.ksg, P.kss, P.vsb, P.vsg, P.vss, P.scale * LOG2E};
+    const int nw = dec_att_waves(P.R, P.Dk);
+    void (*k)(DecAttnArgs, const int32_t *) = nullptr;
+    with_elt<false>(dtype, [&](auto t) {
+        using T = decltype(t);
+        k = P.Dk == 128 ? sel_attn_decode_wg_kernel<T, 8, 128> : nw == 16 ? sel_attn_decode_wg_kernel<T, 16> : sel_attn_decode_wg_kernel<T, 8>;
+    });
     static void *raised[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // raise the dynamic-LDS limit once per kernel (the runtime call costs about a millisecond)
     bool done = false;
     for (void *r : raised) done |= (r == (void *)k);
@@ -62,7 +58,7 @@ int launch_sel_attn_decode_wg(const void *Q, const void *K, const void *V, const
                 break;
             }
     }
-    hipLaunchKernelGGL(k, dim3((unsigned)R), dim3(nw * 64), dec_att_lds(nw, D), st, A, ranges);
+    hipLaunchKernelGGL(k, dim3((unsigned)P.R), dim3(nw * 64), dec_att_lds(nw, P.Dk), st, A, P.ranges);
     NSA_LAUNCH_CHECK("sel_attn_decode_wg");
     return NSA_OK;
 }

@@ -263,46 +263,35 @@ __global__ __launch_bounds__(256) void sel_attn_bwd_generic_kernel(SelAttnBwdPar
 template <typename T>
 static int launch_fwd_generic_t(const SelAttnParams &P, hipStream_t st) {
     const int dvc = (P.Dv + 63) / 64;
-    const size_t lds = 4 * gen_wave_lds_bytes(P.Dk);
-    NSA_CHECK_ARG(lds <= 160 * 1024, "generic kernel: Dk=%d needs %zu B LDS", P.Dk, lds);
+    const size_t lds = 4 * gen_wave_lds_bytes(P.Dk);  // (43 KiB at the entry point's bound Dk = 256: under the 64 KiB a kernel gets unasked)
     const unsigned grid = (unsigned)((P.R + 3) / 4);
     void (*k)(SelAttnParams) = nullptr;
     switch (dvc) {
         case 1: k = sel_attn_fwd_generic_kernel<T, 1>; break;
         case 2: k = sel_attn_fwd_generic_kernel<T, 2>; break;
         case 3: k = sel_attn_fwd_generic_kernel<T, 3>; break;
-        case 4: k = sel_attn_fwd_generic_kernel<T, 4>; break;
-        default: NSA_CHECK_ARG(false, "generic kernel supports Dv <= 256 (got %d)", P.Dv);
+        default: k = sel_attn_fwd_generic_kernel<T, 4>;  // (Dv <= 256: the entry point's check)
     }
-    if (lds > 64 * 1024) NSA_HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, st, P);
     NSA_LAUNCH_CHECK("sel_attn_fwd_generic");
     return NSA_OK;
 }
 
 int launch_sel_attn_fwd_generic(const SelAttnParams &P, int dtype, hipStream_t st) {
-    switch (dtype) {
-        case NSA_DT_F32: return launch_fwd_generic_t<float>(P, st);
-        case NSA_DT_BF16: return launch_fwd_generic_t<__bf16>(P, st);
-        case NSA_DT_F16: return launch_fwd_generic_t<_Float16>(P, st);
-    }
-    set_error("unknown dtype %d", dtype);
-    return NSA_ERR_INVALID;
+    return with_elt(dtype, [&](auto t) { return launch_fwd_generic_t<decltype(t)>(P, st); });
 }
 
 template <typename T>
 static int launch_bwd_generic_t(const SelAttnBwdParams &P, hipStream_t st) {
     const int dc = (max(P.Dk, P.Dv) + 63) / 64;
-    const size_t lds = 4 * gen_bwd_wave_lds_bytes(P.Dk, P.Dv);
-    NSA_CHECK_ARG(lds <= 160 * 1024, "generic bwd kernel: Dk=%d Dv=%d needs %zu B LDS", P.Dk, P.Dv, lds);
+    const size_t lds = 4 * gen_bwd_wave_lds_bytes(P.Dk, P.Dv);  // (at most 83 KiB: Dk, Dv <= 256 at the entry point)
     const unsigned grid = (unsigned)((P.R + 3) / 4);
     void (*k)(SelAttnBwdParams) = nullptr;
     switch (dc) {
         case 1: k = sel_attn_bwd_generic_kernel<T, 1>; break;
         case 2: k = sel_attn_bwd_generic_kernel<T, 2>; break;
         case 3: k = sel_attn_bwd_generic_kernel<T, 3>; break;
-        case 4: k = sel_attn_bwd_generic_kernel<T, 4>; break;
-        default: NSA_CHECK_ARG(false, "generic bwd kernel supports D <= 256");
+        default: k = sel_attn_bwd_generic_kernel<T, 4>;  // (Dk, Dv <= 256: the entry point's check)
     }
     if (lds > 64 * 1024) NSA_HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, st, P);
@@ -311,13 +300,7 @@ static int launch_bwd_generic_t(const SelAttnBwdParams &P, hipStream_t st) {
 }
 
 int launch_sel_attn_bwd_generic(const SelAttnBwdParams &P, int dtype, hipStream_t st) {
-    switch (dtype) {
-        case NSA_DT_F32: return launch_bwd_generic_t<float>(P, st);
-        case NSA_DT_BF16: return launch_bwd_generic_t<__bf16>(P, st);
-        case NSA_DT_F16: return launch_bwd_generic_t<_Float16>(P, st);
-    }
-    set_error("unknown dtype %d", dtype);
-    return NSA_ERR_INVALID;
+    return with_elt(dtype, [&](auto t) { return launch_bwd_generic_t<decltype(t)>(P, st); });
 }
 
 // ---- parity mode of the reference's packed / gather executors (attention_kernels.py:181-226, 273-388) ----------------------
@@ -350,15 +333,14 @@ __global__ __launch_bounds__(256) void sel_first_key_kernel(const E *__restrict_
     for (int i = lane; i < h * Dv; i += 64) o[i] = v[i % Dv];
 }
 
-int launch_sel_first_key(const void *V, const int32_t *ranges, void *O, int64_t R, int S, int G, int h, int Dv, int n, int S_kv, int64_t vsb,
-                         int64_t vsg, int64_t vss, int esz, hipStream_t st) {
-    const unsigned grid = (unsigned)((R + 3) / 4);
-    if (esz == 4)
-        hipLaunchKernelGGL(sel_first_key_kernel<uint32_t>, dim3(grid), dim3(256), 0, st, (const uint32_t *)V, ranges, (uint32_t *)O, R, S, G, h,
-                           Dv, n, S_kv, vsb, vsg, vss);
+int launch_sel_first_key(const SelAttnParams &P, int dtype, hipStream_t st) {
+    const unsigned grid = (unsigned)((P.R + 3) / 4);
+    if (dtype == NSA_DT_F32)
+        hipLaunchKernelGGL(sel_first_key_kernel<uint32_t>, dim3(grid), dim3(256), 0, st, (const uint32_t *)P.V, P.ranges, (uint32_t *)P.O, P.R, P.S, P.G, P.h,
+                           P.Dv, P.n, P.S_kv, P.vsb, P.vsg, P.vss);
     else
-        hipLaunchKernelGGL(sel_first_key_kernel<uint16_t>, dim3(grid), dim3(256), 0, st, (const uint16_t *)V, ranges, (uint16_t *)O, R, S, G, h,
-                           Dv, n, S_kv, vsb, vsg, vss);
+        hipLaunchKernelGGL(sel_first_key_kernel<uint16_t>, dim3(grid), dim3(256), 0, st, (const uint16_t *)P.V, P.ranges, (uint16_t *)P.O, P.R, P.S, P.G, P.h,
+                           P.Dv, P.n, P.S_kv, P.vsb, P.vsg, P.vss);
     NSA_LAUNCH_CHECK("sel_first_key");
     return NSA_OK;
 }
@@ -430,11 +412,7 @@ __global__ __launch_bounds__(256) void sel_head_causal_kernel(SelAttnParams P) {
 int launch_sel_head_causal(const SelAttnParams &P, int dtype, hipStream_t st) {
     NSA_CHECK_ARG(P.h <= HC_MAX, "sel_attn_head_causal_parity: at most %d heads per group (got %d)", HC_MAX, P.h);
     const unsigned grid = (unsigned)((P.R + 3) / 4);
-    switch (dtype) {
-        case NSA_DT_F32: hipLaunchKernelGGL(sel_head_causal_kernel<float>, dim3(grid), dim3(256), 0, st, P); break;
-        case NSA_DT_BF16: hipLaunchKernelGGL(sel_head_causal_kernel<__bf16>, dim3(grid), dim3(256), 0, st, P); break;
-        default: hipLaunchKernelGGL(sel_head_causal_kernel<_Float16>, dim3(grid), dim3(256), 0, st, P); break;
-    }
+    with_elt(dtype, [&](auto t) { hipLaunchKernelGGL(sel_head_causal_kernel<decltype(t)>, dim3(grid), dim3(256), 0, st, P); });
     NSA_LAUNCH_CHECK("sel_head_causal");
     return NSA_OK;
 }

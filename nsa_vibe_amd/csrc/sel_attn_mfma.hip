@@ -387,10 +387,6 @@ __global__ __launch_bounds__(256, 2) void sel_attn_fwd_mfma_kernel(SelAttnParams
 }
 
 // ---- host side ----------------------------------------------------------------------------
-bool sel_attn_mfma_supported(int dtype, int h, int Dk, int Dv) {
-    return (dtype == NSA_DT_BF16 || dtype == NSA_DT_F16) && Dk == Dv && (Dk == 64 || Dk == 128) && h >= 1 && h <= 16;
-}
-
 // Few rows (decode): split each row's tiles over several waves so the launch fills the chip.
 static int pick_nsplit(int64_t R) {
     const int64_t target = 256 * 8;  // waves wanted in flight
@@ -441,10 +437,7 @@ static int launch_mfma_t(const SelAttnParams &P0, hipStream_t st) {
     int cand = 0;
     if (P.fuse_select) {
         NSA_CHECK_ARG(!split && P.select != nullptr, "fused selection needs the non-split route");
-        SP = *(const SelectParams *)P.select;
-        const int c = (SP.S_sel + 63) / 64;
-        NSA_CHECK_ARG(c <= 16 && SP.W <= 64, "fused selection: S_sel <= 1024 and at most 64 ranges per row");
-        cand = c <= 1 ? 1 : c <= 2 ? 2 : c <= 4 ? 4 : c <= 8 ? 8 : 16;
+        NSA_CHECK_ARG(fused_select_args(P, &SP, &cand) && SP.W <= 64, "fused selection: S_sel <= 1024 and at most 64 ranges per row");
     }
     hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, st, P, SP, cand);
     NSA_LAUNCH_CHECK("sel_attn_fwd_mfma");
@@ -455,25 +448,35 @@ static int launch_mfma_t(const SelAttnParams &P0, hipStream_t st) {
     return NSA_OK;
 }
 
-int launch_sel_attn_fwd_mfma(const SelAttnParams &P, int dtype, hipStream_t st) {
-    NSA_CHECK_ARG(sel_attn_mfma_supported(dtype, P.h, P.Dk, P.Dv), "MFMA kernel: unsupported dtype/h/Dk/Dv = %d/%d/%d/%d", dtype, P.h, P.Dk, P.Dv);
-    NSA_CHECK_ARG(P.kss % 8 == 0 && P.vss % 8 == 0 && P.ksb % 8 == 0 && P.vsb % 8 == 0 && P.ksg % 8 == 0 && P.vsg % 8 == 0,
-                  "MFMA kernel: K/V strides must be multiples of 8 elements (16 B)");
-    NSA_CHECK_ARG(((uintptr_t)P.Q % 16 == 0) && ((uintptr_t)P.K % 16 == 0) && ((uintptr_t)P.V % 16 == 0) && ((uintptr_t)P.O % 8 == 0),
-                  "MFMA kernel: Q/K/V must be 16-byte aligned");
-    NSA_CHECK_ARG((int64_t)P.S_kv * P.kss * 2 < ((int64_t)1 << 31) && (int64_t)P.S_kv * P.vss * 2 < ((int64_t)1 << 31),
-                  "MFMA kernel: one (b,g) K/V slab must be smaller than 2 GiB (buffer addressing)");
-    if (!(P.part != nullptr && P.nsplit > 1)) {  // many rows: rows of a wave share the K/V tiles they both selected
-        if (tuning(TUNE_SEL_ROWS) < 0) {  // block form (64-key blocks, several column tiles per wave) unless a row form is forced
-            const int nb = sel_attn_blocks_nt(dtype, P.h, P.Dk, P.Dv, P.S, P.S_kv, P.n, P.R, P.kss, P.vss);
-            if (nb > 0) return launch_sel_attn_blocks_mfma(P, dtype, nb, st);
-        }
-        int nt = 1;
-        const int tpw = sel_attn_rows_tpw(dtype, P.h, P.Dk, P.Dv, P.S, P.S_kv, P.n, P.R, &nt);
-        if (tpw > 0) return launch_sel_attn_rows_mfma(P, dtype, tpw, nt, st);
+SelAttnForm sel_attn_mfma_form(const SelAttnParams &P, int dtype) {
+    SelAttnForm f{SelAttnForm::ONE_ROW, 1, 0, false, false};
+    if (P.part != nullptr && P.nsplit > 1) {
+        f.kind = SelAttnForm::SPLIT;
+    } else if (tuning(TUNE_SEL_ROWS) < 0 && (f.nt = sel_attn_blocks_nt(P, dtype)) > 0) {
+        f.kind = SelAttnForm::BLOCKS;  // many rows: rows of a wave share the K/V tiles they both selected; the block form unless a row form is forced
+        // 8 rows per wave with h = 6: three fully used column tiles instead of four with 12 of 16 columns.  It pays while the rows of a wave share
+        // their blocks (every tile of a block is computed anyway: -10 % at 2k, -8 % at 4k); once a block belongs to one row (S_kv >> n l') the
+        // four-tile form computes the one tile of that row and skips three, the flat form needs two tiles for the straddling rows 2 and 5
+        // (+3 % at 16k, +4..10 % at 64k; same-box A/B, profiles/r02/k_flat_columns.txt).  TUNE_SEL_FLAT: -1 this rule, 0 never, 1 always.
+        const int fmode = tuning(TUNE_SEL_FLAT);
+        f.flat = f.nt == 4 && P.h == 6 && (fmode > 0 || (fmode < 0 && (int64_t)P.S_kv <= (int64_t)384 * P.n));
+        // key halves on different XCDs (see the kernel): needs the caller's workspace, no fused selector, and the walk of a row group long enough
+        const size_t ks_need = (f.nt == 4 && !f.flat && !P.fuse_select) ? sel_attn_ksplit_workspace(dtype, P.h, P.Dk, P.Dv, P.S, P.S_kv, P.n, P.R) : 0;
+        f.ksplit = ks_need > 0 && P.ks_ws && P.ks_bytes >= ks_need;
+    } else if ((f.tpw = sel_attn_rows_tpw(P, dtype, &f.nt)) > 0) {
+        f.kind = SelAttnForm::ROWS;
     }
-    if (dtype == NSA_DT_BF16) return P.Dk == 64 ? launch_mfma_t<__bf16, 64>(P, st) : launch_mfma_t<__bf16, 128>(P, st);
-    return P.Dk == 64 ? launch_mfma_t<_Float16, 64>(P, st) : launch_mfma_t<_Float16, 128>(P, st);
+    return f;
+}
+
+int launch_sel_attn_fwd_mfma(const SelAttnParams &P, int dtype, hipStream_t st) {
+    // (reached by O alone: the route tested Q, K, V and the strides)
+    NSA_CHECK_ARG(out_aligned(P), "MFMA kernel: Q/K/V must be 16-byte aligned");
+    NSA_CHECK_ARG(slabs_under_2gib(P), "MFMA kernel: one (b,g) K/V slab must be smaller than 2 GiB (buffer addressing)");
+    const SelAttnForm f = sel_attn_mfma_form(P, dtype);
+    if (f.kind == SelAttnForm::BLOCKS) return launch_sel_attn_blocks_mfma(P, dtype, f, st);
+    if (f.kind == SelAttnForm::ROWS) return launch_sel_attn_rows_mfma(P, dtype, f, st);
+    return with_elt<false>(dtype, [&](auto t) { return P.Dk == 64 ? launch_mfma_t<decltype(t), 64>(P, st) : launch_mfma_t<decltype(t), 128>(P, st); });
 }
 
 }  // namespace nsa

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/nsa_sel_hip.h"
+
 namespace nsa {
 
 struct SelAttnParams {
@@ -71,7 +73,6 @@ __host__ __device__ inline int band_hi(int t0, int a, int dd, int c, int S_kv, i
     const int hi = e / dd + c;
     return hi < S_kv ? hi : S_kv;
 }
-bool band_attn_mfma_supported(int dtype, int h, int Dk, int Dv);
 size_t band_attn_workspace(int B, int S, int G, int h, int Dk, int Dv, int dtype, int *nsplit_out);
 int launch_band_attn_fwd_mfma(const BandAttnParams &P, int dtype, hipStream_t st);
 int launch_band_attn_fwd_dual(const BandAttnParams &P0, const BandAttnParams &P1, int dtype, hipStream_t st);
@@ -121,31 +122,57 @@ bool band_dual_plan(BandAttnParams *P0, BandAttnParams *P1, int dtype, int64_t w
 int launch_band_attn_bwd_dq(const BandAttnParams &P, const void *dO, const float *lse, const float *delta, void *dQ, int dtype,
                             hipStream_t st);
 int launch_bwd_delta(const void *O, const void *dO, float *delta, int64_t n_rows, int Dv, int dtype, hipStream_t st);
-int launch_band_ranges(int32_t *ranges, int B, int S, int G, int S_kv, int t0, int a, int dd, int c, int w, hipStream_t st);
+int launch_band_ranges(int32_t *ranges, const BandAttnParams &P, hipStream_t st);  // the band as one [lo, hi) range per row
 int launch_band_attn_fwd_generic(const BandAttnParams &P, int dtype, hipStream_t st);
 
+// ---- what the MFMA attention kernels (selection forward and backward, band) ask, stated once.  The shapes they cover:
+inline bool attn_mfma_shape_ok(int dtype, int h, int Dk, int Dv) {
+    return (dtype == NSA_DT_BF16 || dtype == NSA_DT_F16) && Dk == Dv && (Dk == 64 || Dk == 128) && h >= 1 && h <= 16;
+}
+// Their operands (A: the host's AttnCall or any of the kernel blocks above):
+// 16-byte loads and LDS-DMA pieces at K + b ksb + g ksg + row kss: every K / V stride a multiple of 8 elements, Q, K and V 16-byte aligned
+template <class A>
+inline bool qkv_aligned(const A &a) {
+    return a.kss % 8 == 0 && a.vss % 8 == 0 && a.ksb % 8 == 0 && a.vsb % 8 == 0 && a.ksg % 8 == 0 && a.vsg % 8 == 0 && ((uintptr_t)a.Q % 16 == 0) &&
+           ((uintptr_t)a.K % 16 == 0) && ((uintptr_t)a.V % 16 == 0);
+}
+// the forward kernels' extras: 8-byte stores of O rows, and the K / V slab of one (b,g) under 2 GiB (buffer addressing)
+template <class A>
+inline bool out_aligned(const A &a) {
+    return (uintptr_t)a.O % 8 == 0;
+}
+template <class A>
+inline bool slabs_under_2gib(const A &a) {
+    return (int64_t)a.S_kv * a.kss * 2 < ((int64_t)1 << 31) && (int64_t)a.S_kv * a.vss * 2 < ((int64_t)1 << 31);
+}
+
+struct AttnCall;  // nsa_host.hpp: the arguments of the attention family's entry points
 int launch_sel_attn_fwd_generic(const SelAttnParams &P, int dtype, hipStream_t st);
 int launch_sel_attn_bwd_generic(const SelAttnBwdParams &P, int dtype, hipStream_t st);
+int launch_sel_first_key(const SelAttnParams &P, int dtype, hipStream_t st);    // parity mode of the packed / gather executors (reads V, ranges, O)
+int launch_sel_head_causal(const SelAttnParams &P, int dtype, hipStream_t st);  // parity mode of _sdpa_over_ranges
 // decode form (S = 1): one 1024-thread workgroup per row, partials merged through LDS (sel_attn_decode.hpp)
 bool sel_attn_decode_wg_shape_ok(int dtype, int h, int Dk, int Dv, int n);  // shape / tuning part of the next one
-bool sel_attn_decode_wg_supported(int dtype, int h, int Dk, int Dv, int n, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg,
-                                  int64_t vss, const void *Q, const void *K, const void *V);
-int launch_sel_attn_decode_wg(const void *Q, const void *K, const void *V, const int32_t *ranges, void *O, int64_t R, int G, int h, int S_kv, int n,
-                              int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg, int64_t vss, int dtype, float scale, hipStream_t st, int D = 64);
-int launch_sel_head_causal(const SelAttnParams &P, int dtype, hipStream_t st);  // parity mode of _sdpa_over_ranges
-// returns NSA_ERR_INVALID (without setting an error) when the shape is not covered
-bool sel_attn_mfma_supported(int dtype, int h, int Dk, int Dv);
-int launch_sel_attn_fwd_mfma(const SelAttnParams &P, int dtype, hipStream_t st);
+bool sel_attn_decode_wg_supported(const AttnCall &c);
+int launch_sel_attn_decode_wg(const SelAttnParams &P, int dtype, hipStream_t st);
 size_t sel_attn_mfma_workspace(int64_t R, int h, int Dv, int *nsplit_out);
-// query-tile form: rows per wave for this shape, 0 = not covered (use the one-row-per-wave kernel)
-int sel_attn_rows_tpw(int dtype, int h, int Dk, int Dv, int S, int S_kv, int n, int64_t R, int *nt);
+// The kernel form launch_sel_attn_fwd_mfma runs a filled block in, decided here alone.  SPLIT: few rows, the keys of a row over P.nsplit waves;
+// BLOCKS: 64-key blocks, nt column tiles of 16/h rows per wave (flat: 8 rows over 3 tiles; ksplit: key classes on different XCDs, records in
+// P.ks_ws); ROWS: query tiles of tpw rows per wave, nt column tiles; ONE_ROW: one row per wave
+struct SelAttnForm {
+    enum Kind { SPLIT, BLOCKS, ROWS, ONE_ROW } kind;
+    int nt, tpw;
+    bool flat, ksplit;
+};
+SelAttnForm sel_attn_mfma_form(const SelAttnParams &P, int dtype);
+int launch_sel_attn_fwd_mfma(const SelAttnParams &P, int dtype, hipStream_t st);
 // key-split form of the block kernel: bytes of partial records it needs, 0 = not wanted for this shape (rule / tuning in sel_attn_blocks_mfma.hip)
 size_t sel_attn_ksplit_workspace(int dtype, int h, int Dk, int Dv, int S, int S_kv, int n, int64_t R);
-int launch_sel_attn_rows_mfma(const SelAttnParams &P, int dtype, int tpw, int nt, hipStream_t st);
-// block form (64-key blocks, NT column tiles of 16/h rows per wave): column tiles per wave for this shape, 0 = not covered
-int sel_attn_blocks_nt(int dtype, int h, int Dk, int Dv, int S, int S_kv, int n, int64_t R, int64_t kss, int64_t vss);
-int launch_sel_attn_blocks_mfma(const SelAttnParams &P, int dtype, int nt, hipStream_t st);
-bool sel_attn_bwd_mfma_supported(int dtype, int h, int Dk, int Dv);
+// the forms' own shape rules (0 = not covered) and launchers: for sel_attn_mfma_form / launch_sel_attn_fwd_mfma alone
+int sel_attn_rows_tpw(const SelAttnParams &P, int dtype, int *nt);
+int sel_attn_blocks_nt(const SelAttnParams &P, int dtype);
+int launch_sel_attn_rows_mfma(const SelAttnParams &P, int dtype, const SelAttnForm &f, hipStream_t st);
+int launch_sel_attn_blocks_mfma(const SelAttnParams &P, int dtype, const SelAttnForm &f, hipStream_t st);
 size_t sel_attn_bwd_mfma_workspace(int64_t R, int h, int S, int64_t nbg, int S_kv, int D);  // D = Dk = Dv
 int launch_sel_attn_bwd_mfma(const SelAttnBwdParams &P, int dtype, float *delta_ws, hipStream_t st);
 

@@ -469,14 +469,14 @@ __global__ __launch_bounds__(256, 2) void sel_attn_rows_mfma_kernel(SelAttnParam
 //   NT = 1: 16/h rows share one MFMA column tile (h = 6: a pair of rows, 12 of 16 columns used).  A union tile costs what a tile
 //           of the one-row kernel costs, so the gain is the union/sum ratio of the rows' selections -- never a loss.
 //   NT = 3: 48/h rows; pays off only while (nearly) every row selects (nearly) every tile, i.e. short contexts (S_kv <= ~n*l').
-int sel_attn_rows_tpw(int dtype, int h, int Dk, int Dv, int S, int S_kv, int n, int64_t R, int *nt) {
+int sel_attn_rows_tpw(const SelAttnParams &P, int dtype, int *nt) {
+    const int h = P.h, Dk = P.Dk, S = P.S, S_kv = P.S_kv;
     *nt = 1;
-    if (!(dtype == NSA_DT_BF16 || dtype == NSA_DT_F16) || Dk != Dv || (Dk != 64 && Dk != 128) || h < 1 || h > 16) return 0;
-    if (n < 1 || n > 64 || S_kv < 1 || S_kv > 131072) return 0;
+    if (!attn_mfma_shape_ok(dtype, h, Dk, P.Dv) || P.n < 1 || P.n > 64 || S_kv < 1 || S_kv > 131072) return 0;
     const int mode = tuning(TUNE_SEL_ROWS);  // 0 = off, 1 = pairs (NT 1), 3 = query tiles (NT 3); -1 = automatic
     if (mode == 0) return 0;
     int want_nt = 1;
-    if (Dk == 64 && (mode == 3 || (mode < 0 && S_kv <= 1536 && R >= 16384 && h >= 3))) want_nt = 3;
+    if (Dk == 64 && (mode == 3 || (mode < 0 && S_kv <= 1536 && P.R >= 16384 && h >= 3))) want_nt = 3;
     if (want_nt == 3 && h < 3) want_nt = 1;
     const int tpw = (16 * want_nt) / h;
     if (tpw < 2 || S < 2 * tpw) return 0;
@@ -505,10 +505,7 @@ static int launch_rows_t(const SelAttnParams &P0, int tpw, hipStream_t st) {
     int cand = 0;
     if (P.fuse_select) {
         NSA_CHECK_ARG(P.select != nullptr, "fused selection without selector parameters");
-        SP = *(const SelectParams *)P.select;
-        const int c = (SP.S_sel + 63) / 64;
-        NSA_CHECK_ARG(c <= 16 && SP.W <= 64 && SP.W == P.n, "fused selection: S_sel <= 1024 and at most 64 ranges per row");
-        cand = c <= 1 ? 1 : c <= 2 ? 2 : c <= 4 ? 4 : c <= 8 ? 8 : 16;
+        NSA_CHECK_ARG(fused_select_args(P, &SP, &cand) && SP.W <= 64 && SP.W == P.n, "fused selection: S_sel <= 1024 and at most 64 ranges per row");
     }
     void (*k)(SelAttnParams, SelectParams, int) =
         tuning(TUNE_SEL_ROWSUM) ? sel_attn_rows_mfma_kernel<T, D, NT, true> : sel_attn_rows_mfma_kernel<T, D, NT, false>;
@@ -518,10 +515,11 @@ static int launch_rows_t(const SelAttnParams &P0, int tpw, hipStream_t st) {
     return NSA_OK;
 }
 
-int launch_sel_attn_rows_mfma(const SelAttnParams &P, int dtype, int tpw, int nt, hipStream_t st) {
-    if (P.Dk == 128) return dtype == NSA_DT_BF16 ? launch_rows_t<__bf16, 128, 1>(P, tpw, st) : launch_rows_t<_Float16, 128, 1>(P, tpw, st);
-    if (nt == 3) return dtype == NSA_DT_BF16 ? launch_rows_t<__bf16, 64, 3>(P, tpw, st) : launch_rows_t<_Float16, 64, 3>(P, tpw, st);
-    return dtype == NSA_DT_BF16 ? launch_rows_t<__bf16, 64, 1>(P, tpw, st) : launch_rows_t<_Float16, 64, 1>(P, tpw, st);
+int launch_sel_attn_rows_mfma(const SelAttnParams &P, int dtype, const SelAttnForm &f, hipStream_t st) {
+    return with_elt<false>(dtype, [&](auto t) {
+        using T = decltype(t);
+        return P.Dk == 128 ? launch_rows_t<T, 128, 1>(P, f.tpw, st) : f.nt == 3 ? launch_rows_t<T, 64, 3>(P, f.tpw, st) : launch_rows_t<T, 64, 1>(P, f.tpw, st);
+    });
 }
 
 }  // namespace nsa

@@ -827,7 +827,7 @@ static bool dstep_shape_ok(const SelDecodeCall &c, int nw, int fm) {
 // multiples of 8 elements, and the operands of the row's attention (sel_attn_decode_wg_supported)
 static bool dstep_operands_ok(const SelDecodeCall &c) {
     return c.d == 16 && c.l == 32 && c.l_sel == 64 && c.kcs % 8 == 0 && c.kcb % 8 == 0 && c.kcg % 8 == 0 && ((uintptr_t)c.K_cmp % 16 == 0) &&
-           sel_attn_decode_wg_supported(c.dtype, c.h, c.Dk, c.Dv, c.n_top, c.ksb, c.ksg, c.kss, c.vsb, c.vsg, c.vss, c.Q, c.K, c.V);
+           sel_attn_decode_wg_supported(attn_call(c, nullptr, 0, nullptr));
 }
 
 // the part of decode_step_supported that depends on the shape and the tuning switches alone (default block geometry assumed): the one

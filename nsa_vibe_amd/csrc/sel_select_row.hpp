@@ -385,5 +385,14 @@ __device__ __forceinline__ void select_topn_row_auto(const SelectParams &P, cons
 // host: the one fill of SelectParams (sel_select.hip)
 struct SelectCall;  // nsa_host.hpp
 int select_params_fill(SelectParams *P, const float *p_grp, int64_t R, int S, int G, int S_sel, int l_sel, const SelectCall &s);
+// host: the fused selector's kernel arguments of an attention launch (A: SelAttnParams with fuse_select set): the caller's SelectParams
+// (A.select, host memory) and the candidate slots per lane for its S_sel; false: more than 1024 selection blocks
+template <class A>
+inline bool fused_select_args(const A &P, SelectParams *SP, int *cand) {
+    *SP = *(const SelectParams *)P.select;
+    const int c = (SP->S_sel + 63) / 64;
+    *cand = c <= 1 ? 1 : c <= 2 ? 2 : c <= 4 ? 4 : c <= 8 ? 8 : 16;
+    return c <= 16;
+}
 
 }  // namespace nsa

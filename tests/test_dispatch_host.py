@@ -407,3 +407,213 @@ def test_layer_step_mix_rides_in_the_projection_up_to_32_rows(routes):
     assert (launches(one)[0], launches(one)[-1]) == ("qkv_rope_append(rows)", "linear_small(fast)")
     assert (launches(two)[0], launches(two)[-1]) == ("qkv_rope_append(rows, mfma)", "linear_small(mfma)")
     assert [(p["M"], p["B"], p["S"], p["t0"]) for p in (proj(one)[0][1], proj(two)[0][1])] == [(2, 1, 2, 100), (4, 2, 2, 100)]
+
+
+# ---- the attention family: the argument blocks of its launches (csrc/sel_attn_params.hpp), member by member
+
+def attn(routes, label, key="SelAttnParams"):
+    """(launcher names, the blocks named `key` in launch order) of a case of the attention family"""
+    case = routes[label]
+    assert case["rc"] == 0, (label, case["error"])
+    return launches(case), blocks(case, key)
+
+
+BASE = dict(Q="Q+0", K="K+0", V="V+0", G=2, h=6, Dk=64, Dv=64, scale=0.125)
+
+
+def has(block, **want):
+    return {k: block[k] for k in want} == want
+
+
+def test_selection_attention_forms_and_their_members(routes):
+    """The form of a selection-attention forward and what its block carries: rows of 1024 and more take the block form (row form at D = 128 or
+    with a K row stride other than 64, one row per wave where 16 / h < 2), fewer rows split the keys of a row over waves."""
+    for label, lse in (("sel_attn_fwd/blocks", "null"), ("sel_attn_fwd/blocks_lse", "lse+0")):
+        names, (p,) = attn(routes, label)
+        assert names == ["sel_attn_blocks_mfma"]
+        assert has(p, **BASE, ranges="ranges+0", O="O+0", lse=lse, R=1024, S=512, S_kv=512, n=16, ksb=65536, ksg=32768, kss=64, vsb=65536, vsg=32768, vss=64)
+        assert has(p, part="null", nsplit=1, map_mode=1, defer_combine=0, fuse_select=0, select="null", tpw=2, nw=1, ks_ws="ws+0", ks_r1=0, ks_r2=0)
+        assert routes[label]["args"][0]["cand"] == 0 and routes[label]["args"][0]["SelectParams"]["R"] == 0
+    names, (p,) = attn(routes, "sel_attn_fwd/D128_S512_rows")
+    assert names == ["sel_attn_rows_mfma"] and has(p, Dk=128, Dv=128, tpw=2, nw=1, wave_lds=16720, ksb=131072, kss=128, part="null", nsplit=1)
+    names, (p,) = attn(routes, "sel_attn_fwd/S512_kss72_rows")
+    assert names == ["sel_attn_rows_mfma"] and has(p, kss=72, ksg=36864, ksb=73728, vss=64, vsg=32768, tpw=2)
+    names, (p,) = attn(routes, "sel_attn_fwd/S512_kss72_h16_one_row_per_wave")
+    assert names == ["sel_attn_fwd_mfma"] and has(p, h=16, part="null", nsplit=1, map_mode=1, tpw=0, wave_lds=0)
+    for label in ("sel_attn_fwd/split_base_shape", "sel_attn_fwd/S128_Skv32768", "sel_attn_fwd/D128_base_shape"):  # 256 rows: eight splits
+        names, (p, c) = attn(routes, label)
+        assert names == ["sel_attn_fwd_mfma", "sel_attn_combine"] and p == c, label
+        assert has(p, R=256, part="ws+0", nsplit=8, defer_combine=0, ks_ws="null", ks_bytes=0), label
+
+
+def test_selection_attention_decode_routes(routes):
+    """S = 1: one workgroup per row without lse; with lse the split route and its combine, one split without a usable workspace."""
+    for label, S_kv in (("sel_attn_fwd/S1_decode_wg", 128), ("sel_attn_fwd/S1_V_slab_under_2GiB", (1 << 24) - 1)):
+        names, (a,) = attn(routes, label, "DecAttnArgs")
+        assert names == ["sel_attn_decode_wg"] and routes[label]["geometry"] == ["2,1,1/1024,1,1/131600"]
+        assert a == dict(Q="Q+0", K="K+0", V="V+0", O="O+0", G=2, h=6, S_kv=S_kv, n=16, ksb=2 * S_kv * 64, ksg=S_kv * 64, kss=64, vsb=2 * S_kv * 64, vsg=S_kv * 64,
+                         vss=64, c2=0.180336878)
+        assert routes[label]["args"][0]["ranges"] == "ranges+0"
+    names, (p, c) = attn(routes, "sel_attn_fwd/S1_lse_split")
+    assert names == ["sel_attn_fwd_mfma", "sel_attn_combine"] and p == c
+    assert has(p, lse="lse+0", R=2, S=1, part="ws+0", nsplit=16, defer_combine=0, map_mode=0)
+    for label in ("sel_attn_fwd/S1_lse_null_workspace", "sel_attn_fwd/S1_lse_workspace_8_bytes_off"):
+        names, (p,) = attn(routes, label)
+        assert names == ["sel_attn_fwd_mfma"] and has(p, part="null", nsplit=1, ks_ws="null"), label
+    big = routes["sel_attn_fwd/S1_V_slab_2GiB"]  # past the decode workgroup's bound the MFMA launcher refuses the slab
+    assert (big["rc"], big["error"], big["launches"]) == (INVALID, "MFMA kernel: one (b,g) K/V slab must be smaller than 2 GiB (buffer addressing)", [])
+
+
+def test_key_split_form_and_its_members(routes):
+    names, (p,) = attn(routes, "sel_attn_fwd/S512_Skv32768_key_split")  # every row below 32768: zone 0, no record, no combine
+    assert names == ["sel_attn_blocks_mfma"]
+    assert has(p, part="ws+0", ks_ws="ws+0", ks_bytes=64 << 20, ks_r1=512, ks_r2=512, ks_w1=16, ks_w2=16, ks_wa=2, ks_wb=0, ks_wc=0, nw=16)
+    names, (p,) = attn(routes, "sel_attn_fwd/S512_Skv33280_key_split_rows_in_two")  # every row from 32768 on: two key classes
+    assert names == ["sel_attn_blocks_mfma", "sel_attn_ksplit_combine"]
+    assert has(p, part="ws+0", ks_r1=0, ks_r2=512, ks_w1=0, ks_w2=16, ks_wa=0, ks_wb=2, ks_wc=0, nw=17)
+    merge = routes["sel_attn_fwd/S512_Skv33280_key_split_rows_in_two"]["args"][1]
+    assert merge == dict(launch=1, ml="ws+0", acc="ws+196608", O="O+0", lse="null", nbg=2, S=512, G=2, h=6, r1=0, r2=512)
+    names, (p,) = attn(routes, "sel_attn_fwd/S512_Skv32768_null_workspace")  # no workspace: the plain block form
+    assert names == ["sel_attn_blocks_mfma"] and has(p, part="null", ks_ws="null", ks_bytes=0, ks_w2=0, ks_wa=0)
+
+
+def test_generic_kernel_and_launcher_refusals_of_the_selection_forward(routes):
+    for label in ("sel_attn_fwd/variant_1", "sel_attn_fwd/f32", "sel_attn_fwd/h32"):
+        names, (p,) = attn(routes, label)
+        assert names == ["sel_attn_fwd_generic"] and has(p, part="null", nsplit=1, ks_ws="null", scale=0.125, R=256), label
+    # variant 0 with an operand only the launcher tests: refused there, not routed to the generic kernel (DESIGN.md section 7)
+    for label in ("sel_attn_fwd/O_4_bytes_off", "sel_attn_fwd/S512_O_4_bytes_off"):
+        assert (routes[label]["rc"], routes[label]["error"], routes[label]["launches"]) == (INVALID, "MFMA kernel: Q/K/V must be 16-byte aligned", []), label
+    slab = routes["sel_attn_fwd/slab_2GiB"]
+    assert (slab["rc"], slab["error"], slab["launches"]) == (INVALID, "MFMA kernel: one (b,g) K/V slab must be smaller than 2 GiB (buffer addressing)", [])
+    # the band forward tests both before it chooses: the generic kernel, no refusal
+    names, (p,) = attn(routes, "band_attn_fwd/slab_2GiB_generic", "BandAttnParams")
+    assert names == ["band_attn_fwd_generic"] and has(p, S_kv=1 << 20, kss=1024, ksg=1 << 30, ksb=1 << 31)
+    assert launches(routes["band_attn_fwd/O_4_bytes_off"]) == ["band_attn_fwd_generic"]
+
+
+def test_selection_backward_members_on_both_routes(routes):
+    want = dict(Q="Q+0", K="K+0", V="V+0", ranges="ranges+0", O="O+0", lse="lse+0", dO="dO+0", dQ="dQ+0", dK="dK+0", dV="dV+0", R=256, S=128, G=2, h=6, Dk=64, Dv=64,
+                S_kv=128, n=16, ksb=16384, ksg=8192, kss=64, vsb=16384, vsg=8192, vss=64, scale=0.125, skip_delta_dq=0)
+    names, (dq, dkdv) = attn(routes, "sel_attn_bwd/mfma_members", "SelAttnBwdParams")
+    assert names == ["bwd_delta", "bwd_dq_rows", "bwd_hitmap", "bwd_dkdv"] and dq == dkdv == want
+    assert blocks(routes["sel_attn_bwd/mfma_members"], "delta") == ["ws+0", "ws+0"]
+    names, (p,) = attn(routes, "sel_attn_bwd/generic_members", "SelAttnBwdParams")
+    assert names == ["sel_attn_bwd_generic"] and p == want
+    names, (dq, dkdv) = attn(routes, "sel_attn_bwd/D128_members", "SelAttnBwdParams")
+    assert dq == dkdv == dict(want, Dk=128, Dv=128, ksb=32768, ksg=16384, kss=128, vsb=32768, vsg=16384, vss=128, scale=0.5)
+
+
+def test_parity_modes_members(routes):
+    for label in ("sel_attn_first_key_parity/members", "sel_attn_first_key_parity/f32"):
+        (a,) = routes[label]["args"]
+        assert launches(routes[label]) == ["sel_first_key"]
+        assert a == dict(launch=0, V="V+0", ranges="ranges+0", O="O+0", R=256, S=128, G=2, h=6, Dv=64, n=16, S_kv=128, vsb=16384, vsg=8192, vss=64), label
+    names, (p,) = attn(routes, "sel_attn_head_causal_parity/members")
+    assert names == ["sel_head_causal"] and has(p, **BASE, ranges="ranges+0", O="O+0", lse="null", R=256, S=128, S_kv=128, n=16, ksb=16384, vsg=8192, nsplit=0)
+
+
+SLIDING = dict(a=0, dd=1, c=0)
+COMPRESSED = dict(a=32, dd=16, c=1, w=1 << 30)
+
+
+def test_band_forward_members(routes):
+    names = launches(routes["band_attn_fwd/sliding_members"])
+    (p,) = blocks(routes["band_attn_fwd/sliding_members"], "BandAttnParams")
+    (c,) = blocks(routes["band_attn_fwd/sliding_members"], "SelAttnParams")  # the combine launch takes the selection family's block
+    assert names == ["band_attn_fwd(split)", "band_attn_combine"]
+    assert has(p, **BASE, **SLIDING, O="O+0", lse="lse+0", B=1, S=128, S_kv=128, t0=7, w=64, ksb=16384, ksg=8192, kss=64, vsb=16384, vsg=8192, vss=64)
+    assert has(p, part="ws+0", nsplit=16, defer_combine=0, tpw=2, map_mode=0)
+    assert has(c, O="O+0", lse="lse+0", R=256, h=6, part="ws+0", nsplit=16, Q="null", S_kv=0)
+    (p,) = blocks(routes["band_attn_fwd/compressed_members"], "BandAttnParams")
+    assert has(p, **BASE, **COMPRESSED, lse="null", S_kv=13, t0=100, ksb=1664, ksg=832, part="ws+0", nsplit=16)
+    for label, geometry, S_kv in (("S4096_sliding_members", dict(SLIDING, t0=0, w=64), 4096), ("S4096_compressed_members", dict(COMPRESSED, t0=0), 255)):
+        names, (p,) = attn(routes, f"band_attn_fwd/{label}", "BandAttnParams")  # 4096 token groups: no split
+        assert names == ["band_attn_fwd"] and has(p, **geometry, S=4096, S_kv=S_kv, part="null", nsplit=1, tpw=2, map_mode=1), label
+    names, (p,) = (launches(routes["band_attn_fwd/S1_split"]), blocks(routes["band_attn_fwd/S1_split"], "BandAttnParams"))
+    assert names == ["band_attn_fwd(split)", "band_attn_combine"] and has(p, S=1, t0=127, part="ws+0", nsplit=16, defer_combine=0)
+    names, (p,) = attn(routes, "band_attn_fwd/S1_null_workspace", "BandAttnParams")
+    assert names == ["band_attn_fwd"] and has(p, part="null", nsplit=1)
+    for label in ("band_attn_fwd/generic_members", "band_attn_fwd/w_0"):
+        names, (p,) = attn(routes, label, "BandAttnParams")
+        assert names == ["band_attn_fwd_generic"] and has(p, part="null", nsplit=0, scale=0.125), label
+
+
+def test_band_backward_members_and_its_generic_fallback(routes):
+    case = routes["band_attn_bwd/mfma_members"]
+    assert launches(case) == ["band_ranges", "bwd_delta", "band_attn_bwd_dq", "bwd_hitmap", "bwd_dkdv"]
+    roff = case["args"][0]["ranges"]  # the ranges sit behind the selection backward's workspace
+    assert has(case["args"][0], R=256, S=128, G=2, S_kv=13, t0=100, **COMPRESSED)
+    (bp,) = blocks(case, "BandAttnParams")
+    assert has(bp, **BASE, **COMPRESSED, O="null", lse="null", B=1, S=128, S_kv=13, t0=100, part="null", nsplit=0)
+    assert blocks(case, "BandBwdExtra") == [dict(dO="dO+0", lse="lse+0", delta="ws+0", dQ="dQ+0")]
+    (p,) = blocks(case, "SelAttnBwdParams")
+    assert has(p, ranges=roff, O="O+0", lse="lse+0", dO="dO+0", dQ="dQ+0", dK="dK+0", dV="dV+0", R=256, n=1, S_kv=13, skip_delta_dq=1, scale=0.125)
+    for label in ("band_attn_bwd/generic_fallback", "band_attn_bwd/f32_fallback"):
+        names, (p,) = attn(routes, label, "SelAttnBwdParams")  # one range per row, the ranges in the workspace, dK / dV zeroed by the host
+        assert names == ["band_ranges", "sel_attn_bwd_generic"] and routes[label]["memsets"] == 2, label
+        assert has(p, ranges=routes[label]["args"][0]["ranges"], n=1, skip_delta_dq=0, dK="dK+0", dV="dV+0") and p["ranges"].startswith("ws+"), label
+    assert routes["band_attn_bwd/f32_fallback"]["args"][0]["ranges"] == "ws+0"  # no MFMA workspace in front of the ranges
+
+
+def test_select_and_attend_fuses_only_without_key_split(routes):
+    fused = routes["sel_select_attn_fwd/S512_SEL_FUSE_members"]
+    assert launches(fused) == ["sel_attn_blocks_mfma"]
+    (a,) = fused["args"]
+    assert has(a["SelAttnParams"], fuse_select=1, select="set", ranges="ranges+0", n=16, R=1024, ks_ws="null", part="null") and a["cand"] == 1
+    assert has(a["SelectParams"], p_grp="p_grp+0", out="ranges+0", R=1024, S=512, G=2, t0=0, S_sel=8, l_sel=64, n_top=16, force_init=1, force_local=2, W=16)
+    two = routes["sel_select_attn_fwd/S512_two_launches_members"]
+    assert launches(two) == ["select_topn", "sel_attn_blocks_mfma"]
+    (sp,), (p,) = blocks(two, "SelectParams"), blocks(two, "SelAttnParams")  # the attention launch of the two carries an empty selector block
+    assert sp["R"] == 0 and sp["out"] == "null" and two["args"][0]["cand"] == 0 and has(p, fuse_select=0, select="null", ks_ws="ws+0")
+    assert {k: v for k, v in p.items() if k not in ("fuse_select", "select", "ks_ws", "ks_bytes")} == \
+           {k: v for k, v in a["SelAttnParams"].items() if k not in ("fuse_select", "select", "ks_ws", "ks_bytes")}
+    split = routes["sel_select_attn_fwd/S32768_SEL_FUSE_members"]  # the attention would split the keys over XCD groups: two launches
+    assert launches(split) == ["select_topn", "sel_attn_blocks_mfma"]  # (S_kv = S: every row below 32768, no record to merge)
+    assert has(blocks(split, "SelAttnParams")[0], fuse_select=0, part="ws+0", ks_ws="ws+0", ks_r1=32768)
+
+
+def test_layer_calls_build_their_three_branches(routes):
+    """nsa_layer_prefill / _extend / _decode_step / _decode_rows: K / V and strides of each branch, the band geometry, the scratch of each."""
+    cache = dict(ksb=131072, ksg=65536, kss=64, vsb=131072, vsg=65536, vss=64)
+    cmp_cache = dict(ksb=8064, ksg=4032, kss=64, vsb=8064, vsg=4032, vss=64)
+    for label, S, t0, n_cmp in (("layer_prefill/S100_attention", 100, 0, 5), ("layer_extend/t100_S28_attention", 28, 100, 7)):
+        case = routes[label]
+        sel = blocks(case, "SelAttnParams")[0]
+        assert has(sel, K="K_sel+0", V="V_sel+0", ranges="ranges+0", lse="null", S=S, S_kv=t0 + S, n=16, R=2 * S, **cache) and sel["part"].startswith("ws+"), label
+        win, cmp_ = blocks(case, "BandAttnParams")
+        assert has(win, K="K_win+0", V="V_win+0", Q=sel["Q"], S=S, S_kv=t0 + S, t0=t0, w=512, **SLIDING, **cache), label
+        assert has(cmp_, K="K_cmp+0", V="V_cmp+0", Q=sel["Q"], S=S, S_kv=n_cmp, t0=t0, **COMPRESSED, **cmp_cache), label
+        assert win["part"] == cmp_["part"] and len({sel["O"], win["O"], cmp_["O"]}) == 3, label  # one band scratch, used in turn
+    fused = routes["layer_prefill/S512_SEL_FUSE_attention"]["args"][0]
+    assert has(fused["SelAttnParams"], fuse_select=1, select="set", K="K_sel+0", S=512, S_kv=512, n=16) and fused["SelectParams"]["out"] == "ranges+0"
+    # the single step: the band pair rides on the decode step's launch, merged in the workgroup
+    (a,) = routes["layer_decode_step/t100_attention"]["args"]
+    pair = a["DecBandPair"]
+    assert has(a["DecAttnArgs"], K="K_sel+0", V="V_sel+0", S_kv=101, n=16, **cache) and (pair["mg_on"], pair["n_sel"], pair["n_w"]) == (1, 2, 2)
+    assert has(pair["w"], K="K_win+0", V="V_win+0", S=1, S_kv=101, t0=100, w=512, nsplit=16, defer_combine=1, **SLIDING, **cache)
+    assert has(pair["c"], K="K_cmp+0", V="V_cmp+0", S=1, S_kv=5, t0=100, nsplit=16, defer_combine=1, **COMPRESSED, **cmp_cache)
+    assert pair["w"]["part"] != pair["c"]["part"] and pair["w"]["O"] != pair["c"]["O"] and pair["w"]["Q"] == pair["c"]["Q"] == a["DecAttnArgs"]["Q"]
+    # its separate launches: the decode workgroup (or the deferred split) and the dual band launch with the same two blocks
+    wg = routes["layer_decode_step/t100_DECODE_STEP_0_attention"]
+    assert launches(wg) == ["qkv_rope_append(fast)", "decode_score_select", "sel_attn_decode_wg", "band_attn_fwd_dual", "decode_finish", "linear_small(fast)"]
+    dual = [x for x in wg["args"] if "BandAttnParams1" in x][0]
+    assert dual["BandAttnParams"] == pair["w"] and dual["BandAttnParams1"] == pair["c"] and dual["grid0"] == 8
+    split = routes["layer_decode_step/t100_DECODE_STEP_0_DECODE_WG_0_attention"]
+    (p,) = blocks(split, "SelAttnParams")
+    assert launches(split)[2:4] == ["sel_attn_fwd_mfma", "band_attn_fwd_dual"]  # no combine launch: the finish kernel merges
+    assert has(p, K="K_sel+0", S=1, S_kv=101, nsplit=16, defer_combine=1) and p["part"].startswith("ws+")
+    d128 = routes["layer_decode_step/D128_t100_DECODE_STEP_0_attention"]  # Dv = 128: no deferred combine, one band launch each
+    assert launches(d128)[3:7] == ["band_attn_fwd(split)", "band_attn_combine", "band_attn_fwd(split)", "band_attn_combine"]
+    win, cmp_ = blocks(d128, "BandAttnParams")
+    assert has(win, K="K_win+0", Dk=128, defer_combine=0, **SLIDING) and has(cmp_, K="K_cmp+0", defer_combine=0, **COMPRESSED) and win["part"] != cmp_["part"]
+    # S rows per sequence: the rows form's attention block, and the same band pair at S = 4
+    rows = routes["layer_decode_rows/t100_S4_attention"]
+    assert launches(rows) == ["qkv_rope_append(rows, mfma)", "decode_rows", "band_attn_fwd_dual", "decode_finish", "linear_small(mfma)"]
+    assert has(rows["args"][0]["DecAttnArgs"], K="K_sel+0", V="V_sel+0", S_kv=104, n=16, **cache) and rows["args"][0]["DecBandPair"]["n_sel"] == 0xFFFFFFFF
+    dual = rows["args"][1]
+    assert has(dual["BandAttnParams"], K="K_win+0", S=4, S_kv=104, t0=100, w=512, defer_combine=1, **SLIDING)
+    assert has(dual["BandAttnParams1"], K="K_cmp+0", S=4, S_kv=5, t0=100, defer_combine=1, **COMPRESSED)
+    for label in ("layer_decode_rows/t100_S4_DECODE_ROWS_0_attention", "layer_decode_rows/t100_S4_DECODE_STEP_0_DECODE_WG_0_attention"):
+        (p, c) = blocks(routes[label], "SelAttnParams")  # the separate launches of the rows call: the attention with its own combine
+        assert p == c and has(p, K="K_sel+0", S=4, S_kv=104, R=8, n=16, defer_combine=0) and p["nsplit"] > 1, label
