@@ -37,14 +37,7 @@ __device__ __forceinline__ void band_attn_body(const BandAttnParams &P, const un
     } else {
         const int W = (ngrp + 3) >> 2;  // workgroups per (b,g)
         int tc;
-        if (P.map_mode == 2) {  // whole (b,g) pairs per XCD (workgroups go round-robin over the 8 XCDs)
-            const int xcd = bid & 7, idx = bid >> 3;
-            bg = (idx / W) * 8 + xcd;
-            tc = idx % W;
-        } else {
-            bg = bid / W;
-            tc = bid % W;
-        }
+        wg_pair(bid, P.map_mode, W, bg, tc);
         grp = 4 * tc + wave;
         if (grp >= ngrp || bg >= nbg) return;
     }
@@ -78,81 +71,29 @@ __device__ __forceinline__ void band_attn_body(const BandAttnParams &P, const un
         }
     }
 
-    const unsigned char *Kb = (const unsigned char *)((const T *)P.K + (int64_t)b * P.ksb + (int64_t)g * P.ksg);
-    const unsigned char *Vb = (const unsigned char *)((const T *)P.V + (int64_t)b * P.vsb + (int64_t)g * P.vsg);
-    const int64_t krowb = P.kss * 2, vrowb = P.vss * 2;
-    auto make_rsrc = [&](const unsigned char *base, int64_t bytes) {
-        const uint64_t a = (uint64_t)base;
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), (short)0,
-                                                 __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
-    };
-    [[maybe_unused]] const auto krs = make_rsrc(Kb, (int64_t)(P.S_kv - 1) * krowb + G_::ROWB);
-    [[maybe_unused]] const auto vrs = make_rsrc(Vb, (int64_t)(P.S_kv - 1) * vrowb + G_::ROWB);
-    [[maybe_unused]] const int krowb32 = uniform((int)krowb), vrowb32 = uniform((int)vrowb);
-    [[maybe_unused]] const int kstep = uniform(G_::RPI * (int)krowb), vstep = uniform(G_::RPI * (int)vrowb);
-    const int ld_row = lane / G_::PIECES, ld_piece = lane % G_::PIECES;
-    uint32_t kdma[G_::NLD], vdma[G_::NLD];
-#pragma unroll
-    for (int i = 0; i < G_::NLD; ++i) {
-        const int r = i * G_::RPI + ld_row;
-        kdma[i] = (uint32_t)(ld_row * krowb + ((ld_piece ^ G_::swz_k(r)) << 4));
-        vdma[i] = (uint32_t)(ld_row * vrowb + (((((ld_piece >> 1) ^ G_::swz_v(r)) << 1) | (ld_piece & 1)) << 4));
-    }
+    const KvSrc<D> kv = kv_src<T, D>(P, b, g, lane);
     uint32_t krd0[KS], vrd0[MT];
-#pragma unroll
-    for (int s = 0; s < KS; ++s) krd0[s] = rho * G_::ROWB + (((4 * s + q) ^ G_::swz_k(rho)) << 4);
-    {
-        const int qq = rho >> 2, pp = rho & 3, r = 4 * q + qq;
-#pragma unroll
-        for (int m = 0; m < MT; ++m) vrd0[m] = r * G_::ROWB + ((m ^ G_::swz_v(r)) << 5) + 8 * pp;
-    }
-    // a tile of 32 keys starting at tok0 -> wave-private LDS (swizzle applied on the source side); rows past the end of
-    // K/V re-read the last row (they are masked: only boundary tiles reach past hi)
-    auto issue_dma = [&](int tok0) {
-#if defined(__HIP_DEVICE_COMPILE__)
-        typedef __attribute__((address_space(3))) void lds_void;
-        const int ks = uniform(tok0 * krowb32), vs = uniform(tok0 * vrowb32);
-        if (tok0 + 32 <= P.S_kv) {
-#pragma unroll
-            for (int i = 0; i < G_::NLD; ++i) {
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(krs, (lds_void *)(kl + i * 1024), 16, kdma[i], ks + i * kstep, 0, 0);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(vrs, (lds_void *)(vl + i * 1024), 16, vdma[i], vs + i * vstep, 0, 0);
-            }
-        } else {
-            const int last = P.S_kv - 1 - tok0;
-#pragma unroll
-            for (int i = 0; i < G_::NLD; ++i) {
-                const int r = i * G_::RPI + ld_row;
-                const int rc = min(r, last);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(krs, (lds_void *)(kl + i * 1024), 16,
-                                                         rc * krowb32 + ((ld_piece ^ G_::swz_k(r)) << 4), ks, 0, 0);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(vrs, (lds_void *)(vl + i * 1024), 16,
-                                                         rc * vrowb32 + (((((ld_piece >> 1) ^ G_::swz_v(r)) << 1) | (ld_piece & 1)) << 4), vs, 0, 0);
-            }
-        }
-#else
-        (void)tok0;
-#endif
-    };
+    frag_read_offsets<D>(rho, q, krd0, vrd0);
+    // rows past the end of K/V re-read the last row (they are masked: only boundary tiles reach past hi)
+    auto issue_dma = [&](int tok0) { tile_dma(kv, kl, vl, tok0, tok0 + 32 <= P.S_kv, P.S_kv - 1 - tok0); };
 
     typedef __attribute__((ext_vector_type(4))) unsigned int bu32x4;
     u32x4 kreg[G_::NLD], vreg[G_::NLD];
     uint32_t kwr[G_::NLD], vwr[G_::NLD];
 #pragma unroll
     for (int i = 0; i < G_::NLD; ++i) {
-        const int r = i * G_::RPI + ld_row;
-        kwr[i] = r * G_::ROWB + ((ld_piece ^ G_::swz_k(r)) << 4);
-        vwr[i] = r * G_::ROWB + ((((ld_piece >> 1) ^ G_::swz_v(r)) << 5) | ((ld_piece & 1) << 4));
+        const int r = i * G_::RPI + kv.ld_row;
+        kwr[i] = G_::row_img(r, kv.ld_piece);
+        vwr[i] = G_::tr_img(r, kv.ld_piece);
     }
     auto issue_loads = [&](int tok0) {
-        const int ks = uniform(tok0 * krowb32), vs = uniform(tok0 * vrowb32);
+        const int ks = uniform(tok0 * kv.krowb), vs = uniform(tok0 * kv.vrowb);
         const int last = P.S_kv - 1 - tok0;
 #pragma unroll
         for (int i = 0; i < G_::NLD; ++i) {
-            const int rc = min(i * G_::RPI + ld_row, last);
-            kreg[i] = __builtin_bit_cast(u32x4, (bu32x4)__builtin_amdgcn_raw_buffer_load_b128(krs, rc * krowb32 + ld_piece * 16, ks, 0));
-            vreg[i] = __builtin_bit_cast(u32x4, (bu32x4)__builtin_amdgcn_raw_buffer_load_b128(vrs, rc * vrowb32 + ld_piece * 16, vs, 0));
+            const int rc = min(i * G_::RPI + kv.ld_row, last);
+            kreg[i] = __builtin_bit_cast(u32x4, (bu32x4)__builtin_amdgcn_raw_buffer_load_b128(kv.krs, rc * kv.krowb + kv.ld_piece * 16, ks, 0));
+            vreg[i] = __builtin_bit_cast(u32x4, (bu32x4)__builtin_amdgcn_raw_buffer_load_b128(kv.vrs, rc * kv.vrowb + kv.ld_piece * 16, vs, 0));
         }
     };
 
@@ -194,19 +135,8 @@ __device__ __forceinline__ void band_attn_body(const BandAttnParams &P, const un
             }
             wave_lds_fence();
         }
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int s = 0; s < KS; ++s) kfr[u][s] = *(const x8 *)(kl + krd0[s] + u * 16 * G_::ROWB);
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-            const x4 lo = M::tr(vl + vrd0[m]), hi = M::tr(vl + vrd0[m] + 16 * G_::ROWB);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                va[m][j] = lo[j];
-                va[m][4 + j] = hi[j];
-            }
-        }
+        read_row_frags<D>(kl, krd0, kfr);
+        read_tr_frags<T, D>(vl, vrd0, va);
         if (STAGE == 1) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // fragments are in registers: the buffers may be refilled
             __builtin_amdgcn_sched_barrier(0);

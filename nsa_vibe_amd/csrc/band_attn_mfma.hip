@@ -67,14 +67,7 @@ __global__ __launch_bounds__(256, 2) void band_attn_bwd_dq_kernel(BandAttnParams
     const int nbg = P.B * P.G;
     const int W = (ngrp + 3) >> 2;
     int bg, tc;
-    if (P.map_mode == 2) {
-        const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        bg = (idx / W) * 8 + xcd;
-        tc = idx % W;
-    } else {
-        bg = blockIdx.x / W;
-        tc = blockIdx.x % W;
-    }
+    wg_pair(blockIdx.x, P.map_mode, W, bg, tc);
     const int grp = 4 * tc + wave;
     if (grp >= ngrp || bg >= nbg) return;
     const int b = bg / P.G, g = bg - b * P.G;
@@ -101,58 +94,30 @@ __global__ __launch_bounds__(256, 2) void band_attn_bwd_dq_kernel(BandAttnParams
         const float l = used ? E.lse[orow[n]] : -INFINITY;
         lse2[n] = l > -INFINITY ? l * LOG2E : INFINITY;  // empty / unused slot: exp2(s - inf) = 0
         dlt[n] = used ? E.delta[orow[n]] : 0.f;
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            u32x4 rq = {0u, 0u, 0u, 0u}, rd = {0u, 0u, 0u, 0u};
-            if (used) {
-                rq = *(const u32x4 *)((const T *)P.Q + orow[n] * D + 32 * s + 8 * q);
-                rd = *(const u32x4 *)((const T *)E.dO + orow[n] * D + 32 * s + 8 * q);
-            }
-            qf[n][s] = __builtin_bit_cast(x8, rq);
-            dof[n][s] = __builtin_bit_cast(x8, rd);
-        }
+        load_col_frags<D>((const T *)P.Q + orow[n] * D, used, q, qf[n]);
+        load_col_frags<D>((const T *)E.dO + orow[n] * D, used, q, dof[n]);
     }
 
-    const unsigned char *Kb = (const unsigned char *)((const T *)P.K + (int64_t)b * P.ksb + (int64_t)g * P.ksg);
-    const unsigned char *Vb = (const unsigned char *)((const T *)P.V + (int64_t)b * P.vsb + (int64_t)g * P.vsg);
-    const int64_t krowb = P.kss * 2, vrowb = P.vss * 2;
-    auto make_rsrc = [&](const unsigned char *base, int64_t bytes) {
-        const uint64_t a = (uint64_t)base;
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), (short)0,
-                                                 __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
-    };
-    [[maybe_unused]] const auto krs = make_rsrc(Kb, (int64_t)(P.S_kv - 1) * krowb + G_::ROWB);
-    [[maybe_unused]] const auto vrs = make_rsrc(Vb, (int64_t)(P.S_kv - 1) * vrowb + G_::ROWB);
-    [[maybe_unused]] const int krowb32 = uniform((int)krowb), vrowb32 = uniform((int)vrowb);
-    [[maybe_unused]] const int ld_row = lane / G_::PIECES, ld_piece = lane % G_::PIECES;
+    [[maybe_unused]] const KvSrc<D> kv = kv_src<T, D>(P, b, g, lane);  // (the host pass sees no use: the DMA builtin is device only)
+    // V is read as row fragments (A operand of dP^T), K as transposed ones and as row fragments: from its own row image, or (ONE_K) from the transposable one
     uint32_t krd0[KS], vrd0[KS], trd0[MT];
+    frag_read_offsets<D>(rho, q, vrd0, trd0);
 #pragma unroll
-    for (int s = 0; s < KS; ++s) {
-        const int pc = 4 * s + q;
-        vrd0[s] = rho * G_::ROWB + ((pc ^ G_::swz_k(rho)) << 4);
-        krd0[s] = ONE_K ? rho * G_::ROWB + ((((pc >> 1) ^ G_::swz_v(rho)) << 5) | ((pc & 1) << 4)) : vrd0[s];
-    }
-    {
-        const int qq = rho >> 2, pp = rho & 3, r = 4 * q + qq;
-#pragma unroll
-        for (int m = 0; m < MT; ++m) trd0[m] = r * G_::ROWB + ((m ^ G_::swz_v(r)) << 5) + 8 * pp;
-    }
+    for (int s = 0; s < KS; ++s) krd0[s] = ONE_K ? rho * G_::ROWB + G_::tr_piece(rho, 4 * s + q) : vrd0[s];
     // one 32-key tile -> three wave-private images (rows past the end of K/V re-read the last row; they are masked)
     auto issue_dma = [&](int tok0) {
 #if defined(__HIP_DEVICE_COMPILE__)
         typedef __attribute__((address_space(3))) void lds_void;
-        const int ks = uniform(tok0 * krowb32), vs = uniform(tok0 * vrowb32);
+        const int ks = uniform(tok0 * kv.krowb), vs = uniform(tok0 * kv.vrowb);
         const int last = P.S_kv - 1 - tok0;
 #pragma unroll
         for (int i = 0; i < G_::NLD; ++i) {
-            const int r = i * G_::RPI + ld_row;
+            const int r = i * G_::RPI + kv.ld_row;
             const int rc = min(r, last);
-            const uint32_t pk = (uint32_t)((ld_piece ^ G_::swz_k(r)) << 4);
-            const uint32_t pt = (uint32_t)(((((ld_piece >> 1) ^ G_::swz_v(r)) << 1) | (ld_piece & 1)) << 4);
-            if constexpr (!ONE_K) __builtin_amdgcn_raw_ptr_buffer_load_lds(krs, (lds_void *)(kl + i * 1024), 16, rc * krowb32 + pk, ks, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(krs, (lds_void *)(ktl + i * 1024), 16, rc * krowb32 + pt, ks, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(vrs, (lds_void *)(vl + i * 1024), 16, rc * vrowb32 + pk, vs, 0, 0);
+            const uint32_t pk = G_::row_piece(r, kv.ld_piece), pt = G_::tr_piece(r, kv.ld_piece);
+            if constexpr (!ONE_K) __builtin_amdgcn_raw_ptr_buffer_load_lds(kv.krs, (lds_void *)(kl + i * 1024), 16, rc * kv.krowb + pk, ks, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(kv.krs, (lds_void *)(ktl + i * 1024), 16, rc * kv.krowb + pt, ks, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(kv.vrs, (lds_void *)(vl + i * 1024), 16, rc * kv.vrowb + pk, vs, 0, 0);
         }
 #else
         (void)tok0;
@@ -174,19 +139,11 @@ __global__ __launch_bounds__(256, 2) void band_attn_bwd_dq_kernel(BandAttnParams
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
-            for (int s = 0; s < KS; ++s) {
+            for (int s = 0; s < KS; ++s) {  // (K and V interleaved: the order the loop's schedule was measured with)
                 kfr[u][s] = *(const x8 *)(kl + krd0[s] + u * 16 * G_::ROWB);
                 vfr[u][s] = *(const x8 *)(vl + vrd0[s] + u * 16 * G_::ROWB);
             }
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-            const x4 lo = M::tr(ktl + trd0[m]), hi = M::tr(ktl + trd0[m] + 16 * G_::ROWB);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                ka[m][j] = lo[j];
-                ka[m][4 + j] = hi[j];
-            }
-        }
+        read_tr_frags<T, D>(ktl, trd0, ka);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         if (tile + 1 < ntile) issue_dma(tok0 + 32);

@@ -220,56 +220,34 @@ __global__ __launch_bounds__(256, 2) void sel_attn_blocks_mfma_kernel(SelAttnPar
     }
     unsigned long long nz0 = __ballot(u0 != 0u);
 
-    const unsigned char *Kb = (const unsigned char *)((const T *)P.K + (int64_t)b * P.ksb + (int64_t)g * P.ksg);
-    const unsigned char *Vb = (const unsigned char *)((const T *)P.V + (int64_t)b * P.vsb + (int64_t)g * P.vsg);
-    const int64_t krowb = P.kss * 2, vrowb = P.vss * 2;
-    auto make_rsrc = [&](const unsigned char *base, int64_t bytes) {
-        const uint64_t a = (uint64_t)base;
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), (short)0,
-                                                 __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
-    };
-    [[maybe_unused]] const auto krs = make_rsrc(Kb, (int64_t)(P.S_kv - 1) * krowb + ROWB);
-    [[maybe_unused]] const auto vrs = make_rsrc(Vb, (int64_t)(P.S_kv - 1) * vrowb + ROWB);
-    [[maybe_unused]] const int krowb32 = uniform((int)krowb), vrowb32 = uniform((int)vrowb);
-    // one wave-wide 16-B load covers 8 rows x 128 B; the XOR swizzle sits on the SOURCE side (the DMA destination is lane-linear),
-    // and for 8-row pieces it depends on the lane only: swz_k(8 i + r) = r & 7, swz_v(8 i + r) = (r >> 1) & 3
-    const int ld_row = lane >> 3, ld_piece = lane & 7;
-    [[maybe_unused]] const uint32_t kdma = (uint32_t)(ld_row * krowb + ((ld_piece ^ (ld_row & 7)) << 4));
-    [[maybe_unused]] const uint32_t vdma = (uint32_t)(ld_row * vrowb + (((((ld_piece >> 1) ^ ((ld_row >> 1) & 3)) << 1) | (ld_piece & 1)) << 4));
+    // one wave-wide 16-B load covers 8 rows x 128 B, and for 8-row steps the swizzles depend on the lane only (swz_k(8 i + r) = swz_k(r), the
+    // same for swz_v): every load of a block takes the per-lane source offsets of the first
+    [[maybe_unused]] const KvSrc<D> kv = kv_src<T, D>(P, b, g, lane);  // (the host pass sees no use: the DMA builtin is device only)
     uint32_t krd0[KS], vrd0[MT];
-#pragma unroll
-    for (int s = 0; s < KS; ++s) krd0[s] = rho * ROWB + (((4 * s + q) ^ (rho & 7)) << 4);
-    {
-        const int qq = rho >> 2, pp = rho & 3, r = 4 * q + qq;
-#pragma unroll
-        for (int m = 0; m < MT; ++m) vrd0[m] = r * ROWB + ((m ^ ((r >> 1) & 3)) << 5) + 8 * pp;
-    }
+    frag_read_offsets<D>(rho, q, krd0, vrd0);
     // a block of 64 keys starting at tok0 -> wave-private LDS; rows past the end of K/V re-read the last row (they are masked:
     // a block reaching past S_kv is never `full`)
     auto issue_dma = [&](int tok0) {
 #if defined(__HIP_DEVICE_COMPILE__)
         typedef __attribute__((address_space(3))) void lds_void;
-        const int ks = uniform(tok0 * krowb32), vs = uniform(tok0 * vrowb32);
+        const int ks = uniform(tok0 * kv.krowb), vs = uniform(tok0 * kv.vrowb);
         if (tok0 + BLK <= P.S_kv) {
             // K/V rows are contiguous (128 B apart: checked by the host), so 8 rows = 1 KiB on both sides: the instruction's immediate
             // offset (added to the memory address AND to the LDS address) steps through four pieces per M0 / soffset setting
 #define NSA_BLK_DMA(RS, LP, VO, SO, I) \
     __builtin_amdgcn_raw_ptr_buffer_load_lds(RS, (lds_void *)((LP) + ((I) >> 2) * 4096), 16, VO, (SO) + ((I) >> 2) * 4096, ((I)&3) * 1024, 0)
-            NSA_BLK_DMA(krs, kl, kdma, ks, 0); NSA_BLK_DMA(krs, kl, kdma, ks, 1); NSA_BLK_DMA(krs, kl, kdma, ks, 2); NSA_BLK_DMA(krs, kl, kdma, ks, 3);
-            NSA_BLK_DMA(krs, kl, kdma, ks, 4); NSA_BLK_DMA(krs, kl, kdma, ks, 5); NSA_BLK_DMA(krs, kl, kdma, ks, 6); NSA_BLK_DMA(krs, kl, kdma, ks, 7);
-            NSA_BLK_DMA(vrs, vl, vdma, vs, 0); NSA_BLK_DMA(vrs, vl, vdma, vs, 1); NSA_BLK_DMA(vrs, vl, vdma, vs, 2); NSA_BLK_DMA(vrs, vl, vdma, vs, 3);
-            NSA_BLK_DMA(vrs, vl, vdma, vs, 4); NSA_BLK_DMA(vrs, vl, vdma, vs, 5); NSA_BLK_DMA(vrs, vl, vdma, vs, 6); NSA_BLK_DMA(vrs, vl, vdma, vs, 7);
+            NSA_BLK_DMA(kv.krs, kl, kv.kdma[0], ks, 0); NSA_BLK_DMA(kv.krs, kl, kv.kdma[0], ks, 1); NSA_BLK_DMA(kv.krs, kl, kv.kdma[0], ks, 2); NSA_BLK_DMA(kv.krs, kl, kv.kdma[0], ks, 3);
+            NSA_BLK_DMA(kv.krs, kl, kv.kdma[0], ks, 4); NSA_BLK_DMA(kv.krs, kl, kv.kdma[0], ks, 5); NSA_BLK_DMA(kv.krs, kl, kv.kdma[0], ks, 6); NSA_BLK_DMA(kv.krs, kl, kv.kdma[0], ks, 7);
+            NSA_BLK_DMA(kv.vrs, vl, kv.vdma[0], vs, 0); NSA_BLK_DMA(kv.vrs, vl, kv.vdma[0], vs, 1); NSA_BLK_DMA(kv.vrs, vl, kv.vdma[0], vs, 2); NSA_BLK_DMA(kv.vrs, vl, kv.vdma[0], vs, 3);
+            NSA_BLK_DMA(kv.vrs, vl, kv.vdma[0], vs, 4); NSA_BLK_DMA(kv.vrs, vl, kv.vdma[0], vs, 5); NSA_BLK_DMA(kv.vrs, vl, kv.vdma[0], vs, 6); NSA_BLK_DMA(kv.vrs, vl, kv.vdma[0], vs, 7);
 #undef NSA_BLK_DMA
         } else {
             const int last = P.S_kv - 1 - tok0;
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const int rc = min(8 * i + ld_row, last);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(krs, (lds_void *)(kl + i * 1024), 16,
-                                                         rc * krowb32 + ((ld_piece ^ (ld_row & 7)) << 4), ks, 0, 0);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(vrs, (lds_void *)(vl + i * 1024), 16,
-                                                         rc * vrowb32 + (((((ld_piece >> 1) ^ ((ld_row >> 1) & 3)) << 1) | (ld_piece & 1)) << 4), vs, 0, 0);
+                const int rc = min(8 * i + kv.ld_row, last);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(kv.krs, (lds_void *)(kl + i * 1024), 16, rc * kv.krowb + Geo<D>::row_piece(kv.ld_row, kv.ld_piece), ks, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(kv.vrs, (lds_void *)(vl + i * 1024), 16, rc * kv.vrowb + Geo<D>::tr_piece(kv.ld_row, kv.ld_piece), vs, 0, 0);
             }
         }
 #else
@@ -315,23 +293,11 @@ __global__ __launch_bounds__(256, 2) void sel_attn_blocks_mfma_kernel(SelAttnPar
         const int nxt = next_blk();
         const int tok0 = BLK * cur;
         x8 kfr[4][KS];
-        x8 va[MT][2];
+        x8 va[2][MT];  // per 32-key half of the block
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // LDS-DMA completion is a vmcnt event
+        read_row_frags<D>(kl, krd0, kfr);
 #pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int s = 0; s < KS; ++s) kfr[u][s] = *(const x8 *)(kl + krd0[s] + u * 16 * ROWB);
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int hf = 0; hf < 2; ++hf) {
-                const x4 lo = M::tr(vl + vrd0[m] + hf * 32 * ROWB), hi = M::tr(vl + vrd0[m] + (hf * 32 + 16) * ROWB);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    va[m][hf][j] = lo[j];
-                    va[m][hf][4 + j] = hi[j];
-                }
-            }
+        for (int hf = 0; hf < 2; ++hf) read_tr_frags<T, D>(vl + hf * 32 * ROWB, vrd0, va[hf]);
         // ownership of this block: bit r of fullm / touchm = row r covers it completely / selected at least one of its keys
         if ((cur >> 5) != cw) {  // lane r < ntok caches row r's bitmap words of the current 32-block group
             cw = cur >> 5;
@@ -439,8 +405,8 @@ __global__ __launch_bounds__(256, 2) void sel_attn_blocks_mfma_kernel(SelAttnPar
             lrun[nn] += psum;
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
-                o[nn][m] = M::mma(va[m][0], pf[0], o[nn][m]);
-                o[nn][m] = M::mma(va[m][1], pf[1], o[nn][m]);
+                o[nn][m] = M::mma(va[0][m], pf[0], o[nn][m]);
+                o[nn][m] = M::mma(va[1][m], pf[1], o[nn][m]);
             }
         }
         cur = nxt;

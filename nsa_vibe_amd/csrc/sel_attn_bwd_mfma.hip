@@ -16,8 +16,7 @@
 //      S = Q.K^T, dP = dO.V^T (16x16x32), then dV += P^T.dO and
 //      dK += dS^T.Q as 16x16x16 MFMAs whose A operand is taken straight from the S/dP accumulators (their row index,
 //      the (query,head) slot, is the contraction index) and whose B operand is read transposed from LDS.
-#include "nsa_common.hpp"
-#include "sel_attn_params.hpp"
+#include "attn_mfma_tiles.hpp"
 
 namespace nsa {
 
@@ -48,6 +47,7 @@ __device__ __forceinline__ X4 tr_read(const unsigned char *p) {
     return __builtin_bit_cast(X4, r);
 }
 
+// Tile geometry: the forward's Geo<D> (attn_mfma_tiles.hpp), a row image and a transposable image.
 // Head dimension D = Dk = Dv in {64, 128}: rows of D bf16/f16 elements = D / 8 pieces of 16 B = D / 16 chunks of 32 B.
 //   D = 64:  128-B rows, piece XOR r & 7,  chunk XOR (r >> 1) & 3.
 //   D = 128: 256-B rows, piece XOR r & 15, chunk XOR r & 7 (the forward's Geo<128> swizzles).
@@ -55,19 +55,6 @@ __device__ __forceinline__ X4 tr_read(const unsigned char *p) {
 // ds_read_b64_tr_b16 in two 32-lane groups), done exhaustively over every lane group, fragment index and 16-row half, for both D:
 // the row reads of the row image (row rho, piece 4s + q), the row reads of the transposable image (same pieces) and the transposing
 // reads (row 4q + rho / 4, chunk m, 8 B at 8 (rho & 3)) each touch every bank once per group -- no conflicts.
-template <int D>
-struct BGeo {
-    static constexpr int ROWB = D * 2;          // bytes per row
-    static constexpr int PIECES = D / 8;        // 16-B pieces per row
-    static constexpr int RPI = 64 / PIECES;     // rows of one wave-wide 16-B load (1 KiB)
-    static constexpr int NLD = 32 / RPI;        // such loads per 32-row tile
-    static constexpr int KS = D / 32;           // 16x16x32 k-steps over d
-    static constexpr int MT = D / 16;           // 16-column d tiles
-    __device__ static int swz_row(int r) { return r & (PIECES - 1); }            // 16-B piece XOR for b128 row reads
-    __device__ static int swz_tr(int r) { return D == 64 ? ((r >> 1) & 3) : (r & 7); }  // 32-B chunk XOR for transposed reads
-    __device__ static uint32_t off_row_img(int r, int piece) { return r * ROWB + ((piece ^ swz_row(r)) << 4); }
-    __device__ static uint32_t off_tr_img(int r, int piece) { return r * ROWB + ((((piece >> 1) ^ swz_tr(r)) << 5) | ((piece & 1) << 4)); }
-};
 
 // ------------------------------------------------------------------------------------------ 1. delta
 // Dv / 8 lanes per (row, head), 16 bytes per lane -- a wave reads 512 / Dv whole rows of O and of dO per instruction (one thread
@@ -93,16 +80,16 @@ __global__ __launch_bounds__(256) void bwd_delta_kernel(const T *__restrict__ O,
 // ------------------------------------------------------------------------------------------ 2. dQ (query-major)
 template <int D>
 constexpr int bwd_dq_wave_lds() {
-    return 3 * 32 * BGeo<D>::ROWB + ((SEG_INTS * 4 + 15) / 16) * 16;
+    return 3 * 32 * Geo<D>::ROWB + ((SEG_INTS * 4 + 15) / 16) * 16;
 }
 
 template <typename T, int D>
 __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(SelAttnBwdParams P, const float *__restrict__ delta, int map_mode) {
     using M = BwdT<T>;
-    using Gm = BGeo<D>;
+    using Gm = Geo<D>;
     using x8 = typename M::x8;
     using x4 = typename M::x4;
-    constexpr int BROWB = Gm::ROWB, KS = Gm::KS, MT = Gm::MT, NLD = Gm::NLD, RPI = Gm::RPI;
+    constexpr int BROWB = Gm::ROWB, KS = Gm::KSTEPS, MT = Gm::MT, NLD = Gm::NLD, RPI = Gm::RPI;
     constexpr int TILE = 32 * BROWB;  // 4 KiB (D = 64), 8 KiB (D = 128)
     constexpr int WAVE_LDS = bwd_dq_wave_lds<D>();
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -112,14 +99,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(SelAttnBwdParams P, cons
     if (map_mode != 0) {  // same (b,g)-major / XCD-aware order as the forward kernel
         const int W = (P.S + 3) >> 2;
         int bg, tc;
-        if (map_mode == 2) {
-            const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-            bg = (idx / W) * 8 + xcd;
-            tc = idx % W;
-        } else {
-            bg = blockIdx.x / W;
-            tc = blockIdx.x % W;
-        }
+        wg_pair(blockIdx.x, map_mode, W, bg, tc);
         const int t = 4 * tc + wave;
         if (t >= P.S) return;
         row = ((int64_t)(bg / P.G) * P.S + t) * P.G + (bg % P.G);
@@ -133,56 +113,29 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(SelAttnBwdParams P, cons
     const int h = P.h;
     const int g = (int)(row % P.G);
     const int b = (int)(row / ((int64_t)P.G * P.S));
-    const unsigned char *Kb = (const unsigned char *)((const T *)P.K + (int64_t)b * P.ksb + (int64_t)g * P.ksg);
-    const unsigned char *Vb = (const unsigned char *)((const T *)P.V + (int64_t)b * P.vsb + (int64_t)g * P.vsg);
-    const int64_t krowb = P.kss * 2, vrowb = P.vss * 2;
     int nseg;
     const int L = normalise_ranges(P.ranges + row * (int64_t)P.n * 2, P.n, P.S_kv, seg, &nseg);
     const int rho = lane & 15, q = lane >> 4;
 
     // B operands held for the whole row: Q^T and dO^T fragments (head = column), per-head lse (log2 domain) and delta
     x8 qf[KS], dof[KS];
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-        u32x4 a = {0u, 0u, 0u, 0u}, c = {0u, 0u, 0u, 0u};
-        if (rho < h) {
-            a = *(const u32x4 *)((const T *)P.Q + (row * h + rho) * (int64_t)D + 32 * s + 8 * q);
-            c = *(const u32x4 *)((const T *)P.dO + (row * h + rho) * (int64_t)D + 32 * s + 8 * q);
-        }
-        qf[s] = __builtin_bit_cast(x8, a);
-        dof[s] = __builtin_bit_cast(x8, c);
-    }
+    load_col_frags<D>((const T *)P.Q + (row * h + rho) * (int64_t)D, rho < h, q, qf);
+    load_col_frags<D>((const T *)P.dO + (row * h + rho) * (int64_t)D, rho < h, q, dof);
     const float lse2 = (rho < h && L > 0) ? P.lse[row * h + rho] * LOG2E : 0.f;
     const float dlt = (rho < h) ? delta[row * h + rho] : 0.f;
     const float c2 = P.scale * LOG2E;
 
-    const int ld_row = lane / Gm::PIECES, ld_piece = lane % Gm::PIECES;  // RPI rows x PIECES pieces per wave-wide 16-B load
-    uint32_t kd_row[NLD], kd_tr[NLD], vd_row[NLD];
+    // K goes into a row image and a transposable one, V into a row image: per-lane source offsets of the LDS-DMA loads of a full tile
+    const KvSrc<D> kv = kv_src<T, D>(P, b, g, lane);
+    uint32_t kd_tr[NLD], vd_row[NLD];
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
-        const int r = RPI * i + ld_row;
-        kd_row[i] = (uint32_t)(ld_row * krowb + ((ld_piece ^ Gm::swz_row(r)) << 4));
-        kd_tr[i] = (uint32_t)(ld_row * krowb + (((((ld_piece >> 1) ^ Gm::swz_tr(r)) << 1) | (ld_piece & 1)) << 4));
-        vd_row[i] = (uint32_t)(ld_row * vrowb + ((ld_piece ^ Gm::swz_row(r)) << 4));
+        const int r = RPI * i + kv.ld_row;
+        kd_tr[i] = kv.ld_row * kv.krowb + Gm::tr_piece(r, kv.ld_piece);
+        vd_row[i] = kv.ld_row * kv.vrowb + Gm::row_piece(r, kv.ld_piece);
     }
     uint32_t rd_row[KS], rd_tr[MT];
-#pragma unroll
-    for (int s = 0; s < KS; ++s) rd_row[s] = Gm::off_row_img(rho, 4 * s + q);
-    {
-        const int qq = rho >> 2, pp = rho & 3, r = 4 * q + qq;
-#pragma unroll
-        for (int m = 0; m < MT; ++m) rd_tr[m] = r * BROWB + ((m ^ Gm::swz_tr(r)) << 5) + 8 * pp;
-    }
-    auto make_rsrc = [&](const unsigned char *base, int64_t bytes) {
-        const uint64_t a = (uint64_t)base;
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), (short)0,
-                                                 __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
-    };
-    [[maybe_unused]] const auto krs = make_rsrc(Kb, (int64_t)(P.S_kv - 1) * krowb + BROWB);
-    [[maybe_unused]] const auto vrs = make_rsrc(Vb, (int64_t)(P.S_kv - 1) * vrowb + BROWB);
-    [[maybe_unused]] const int krowb32 = uniform((int)krowb), vrowb32 = uniform((int)vrowb);
-    [[maybe_unused]] const int kstep = uniform(RPI * (int)krowb), vstep = uniform(RPI * (int)vrowb);
+    frag_read_offsets<D>(rho, q, rd_row, rd_tr);
 
     int it_seg = -1, it_start = 0, it_len = 0, it_pos = 0;
     auto next_tile = [&](int &tok0, int &nvalid) -> bool {
@@ -202,16 +155,16 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(SelAttnBwdParams P, cons
     auto issue_dma = [&](int tok0, int nvalid) {
 #if defined(__HIP_DEVICE_COMPILE__)
         typedef __attribute__((address_space(3))) void lds_void;
-        const int ks = uniform(tok0 * krowb32), vs = uniform(tok0 * vrowb32);
+        const int ks = uniform(tok0 * kv.krowb), vs = uniform(tok0 * kv.vrowb);
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
             // tail tiles: rows past the segment re-read its last row (their dS is masked to zero below)
-            const int rowshift = (nvalid == 32) ? 0 : (min(RPI * i + ld_row, nvalid - 1) - ld_row);
-            const int kso = (nvalid == 32) ? ks + i * kstep : ks, vso = (nvalid == 32) ? vs + i * vstep : vs;
-            const uint32_t kadd = (nvalid == 32) ? 0u : (uint32_t)(rowshift * krowb32), vadd = (nvalid == 32) ? 0u : (uint32_t)(rowshift * vrowb32);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(krs, (lds_void *)(k_row + i * 1024), 16, kd_row[i] + kadd, kso, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(krs, (lds_void *)(k_tr + i * 1024), 16, kd_tr[i] + kadd, kso, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(vrs, (lds_void *)(v_row + i * 1024), 16, vd_row[i] + vadd, vso, 0, 0);
+            const int rowshift = (nvalid == 32) ? 0 : (min(RPI * i + kv.ld_row, nvalid - 1) - kv.ld_row);
+            const int kso = (nvalid == 32) ? ks + i * kv.kstep : ks, vso = (nvalid == 32) ? vs + i * kv.vstep : vs;
+            const uint32_t kadd = (nvalid == 32) ? 0u : (uint32_t)(rowshift * kv.krowb), vadd = (nvalid == 32) ? 0u : (uint32_t)(rowshift * kv.vrowb);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(kv.krs, (lds_void *)(k_row + i * 1024), 16, kv.kdma[i] + kadd, kso, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(kv.krs, (lds_void *)(k_tr + i * 1024), 16, kd_tr[i] + kadd, kso, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(kv.vrs, (lds_void *)(v_row + i * 1024), 16, vd_row[i] + vadd, vso, 0, 0);
         }
 #else
         (void)tok0;
@@ -230,13 +183,8 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(SelAttnBwdParams P, cons
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         x8 kfr[2][KS], vfr[2][KS];
         x4 ktr[2][MT];
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int s = 0; s < KS; ++s) {
-                kfr[u][s] = *(const x8 *)(k_row + rd_row[s] + u * 16 * BROWB);
-                vfr[u][s] = *(const x8 *)(v_row + rd_row[s] + u * 16 * BROWB);
-            }
+        read_row_frags<D>(k_row, rd_row, kfr);
+        read_row_frags<D>(v_row, rd_row, vfr);
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -307,10 +255,10 @@ template <typename T, int D>
 __global__ __launch_bounds__(256, 2) void bwd_dq_rows_kernel(SelAttnBwdParams P, const float *__restrict__ delta, int map_mode, int tpw, int NW,
                                                           int wave_lds) {
     using M = BwdT<T>;
-    using Gm = BGeo<D>;
+    using Gm = Geo<D>;
     using x8 = typename M::x8;
     using x4 = typename M::x4;
-    constexpr int BROWB = Gm::ROWB, KS = Gm::KS, MT = Gm::MT, NLD = Gm::NLD, RPI = Gm::RPI;
+    constexpr int BROWB = Gm::ROWB, KS = Gm::KSTEPS, MT = Gm::MT, NLD = Gm::NLD, RPI = Gm::RPI;
     constexpr int TILE = 32 * BROWB;  // 4 KiB (D = 64), 8 KiB (D = 128)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = lane_id();
@@ -320,14 +268,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_rows_kernel(SelAttnBwdParams P,
     const int nbg = (int)(P.R / P.S);
     const int W4 = (ngrp + 3) >> 2;
     int bg, tc;
-    if (map_mode == 2) {
-        const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        bg = (idx / W4) * 8 + xcd;
-        tc = idx % W4;
-    } else {
-        bg = blockIdx.x / W4;
-        tc = blockIdx.x % W4;
-    }
+    wg_pair(blockIdx.x, map_mode, W4, bg, tc);
     const int grp = 4 * tc + wave;
     if (grp >= ngrp || bg >= nbg) return;
     const int b = bg / P.G, g = bg - b * P.G;
@@ -382,16 +323,8 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_rows_kernel(SelAttnBwdParams P,
     const int64_t orow = used ? ((((int64_t)b * P.S + tw0 + tok) * P.G + g) * h + head) : -1;  // row * h + head
 
     x8 qf[KS], dof[KS];
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-        u32x4 a = {0u, 0u, 0u, 0u}, c = {0u, 0u, 0u, 0u};
-        if (used) {
-            a = *(const u32x4 *)((const T *)P.Q + orow * D + 32 * s + 8 * q);
-            c = *(const u32x4 *)((const T *)P.dO + orow * D + 32 * s + 8 * q);
-        }
-        qf[s] = __builtin_bit_cast(x8, a);
-        dof[s] = __builtin_bit_cast(x8, c);
-    }
+    load_col_frags<D>((const T *)P.Q + orow * D, used, q, qf);
+    load_col_frags<D>((const T *)P.dO + orow * D, used, q, dof);
     float lse2 = 0.f, dlt = 0.f;
     bool live = false;  // rows without any selected key have lse = -inf: every p is 0
     if (used) {
@@ -402,54 +335,34 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_rows_kernel(SelAttnBwdParams P,
     }
     const float c2 = P.scale * LOG2E;
 
-    const unsigned char *Kb = (const unsigned char *)((const T *)P.K + (int64_t)b * P.ksb + (int64_t)g * P.ksg);
-    const unsigned char *Vb = (const unsigned char *)((const T *)P.V + (int64_t)b * P.vsb + (int64_t)g * P.vsg);
-    const int64_t krowb = P.kss * 2, vrowb = P.vss * 2;
-    const int ld_row = lane / Gm::PIECES, ld_piece = lane % Gm::PIECES;
-    uint32_t kd_tr[NLD], vd_row[NLD];
+    const KvSrc<D> kv = kv_src<T, D>(P, b, g, lane);
+    uint32_t kd_tr[NLD], vd_row[NLD];  // K into the transposable image, V into a row image
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
-        const int r = RPI * i + ld_row;
-        kd_tr[i] = (uint32_t)(ld_row * krowb + (((((ld_piece >> 1) ^ Gm::swz_tr(r)) << 1) | (ld_piece & 1)) << 4));
-        vd_row[i] = (uint32_t)(ld_row * vrowb + ((ld_piece ^ Gm::swz_row(r)) << 4));
+        const int r = RPI * i + kv.ld_row;
+        kd_tr[i] = kv.ld_row * kv.krowb + Gm::tr_piece(r, kv.ld_piece);
+        vd_row[i] = kv.ld_row * kv.vrowb + Gm::row_piece(r, kv.ld_piece);
     }
     uint32_t rd_row[KS], rd_krow[KS], rd_tr[MT];
+    frag_read_offsets<D>(rho, q, rd_row, rd_tr);
 #pragma unroll
-    for (int s = 0; s < KS; ++s) {
-        rd_row[s] = Gm::off_row_img(rho, 4 * s + q);
-        rd_krow[s] = Gm::off_tr_img(rho, 4 * s + q);
-    }
-    {
-        const int qq = rho >> 2, pp = rho & 3, r = 4 * q + qq;
-#pragma unroll
-        for (int m = 0; m < MT; ++m) rd_tr[m] = r * BROWB + ((m ^ Gm::swz_tr(r)) << 5) + 8 * pp;
-    }
-    auto make_rsrc = [&](const unsigned char *base, int64_t bytes) {
-        const uint64_t a = (uint64_t)base;
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), (short)0,
-                                                 __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
-    };
-    [[maybe_unused]] const auto krs = make_rsrc(Kb, (int64_t)(P.S_kv - 1) * krowb + BROWB);
-    [[maybe_unused]] const auto vrs = make_rsrc(Vb, (int64_t)(P.S_kv - 1) * vrowb + BROWB);
-    [[maybe_unused]] const int krowb32 = uniform((int)krowb), vrowb32 = uniform((int)vrowb);
-    [[maybe_unused]] const int kstep = uniform(RPI * (int)krowb), vstep = uniform(RPI * (int)vrowb);
+    for (int s = 0; s < KS; ++s) rd_krow[s] = Gm::tr_img(rho, 4 * s + q);
     auto issue_dma = [&](int tok0) {
 #ifdef DQ_NODMA  // ablation (timing only, results meaningless): no K / V tile fetches
         return;
 #endif
 #if defined(__HIP_DEVICE_COMPILE__)
         typedef __attribute__((address_space(3))) void lds_void;
-        const int ks = uniform(tok0 * krowb32), vs = uniform(tok0 * vrowb32);
+        const int ks = uniform(tok0 * kv.krowb), vs = uniform(tok0 * kv.vrowb);
         const bool whole = tok0 + 32 <= P.S_kv;
         const int last = P.S_kv - 1 - tok0;  // rows past the end of K/V re-read the last row (masked: such a tile is never `full`)
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
-            const int rowshift = whole ? 0 : (min(RPI * i + ld_row, last) - ld_row);
-            const int kso = whole ? ks + i * kstep : ks, vso = whole ? vs + i * vstep : vs;
-            const uint32_t kadd = whole ? 0u : (uint32_t)(rowshift * krowb32), vadd = whole ? 0u : (uint32_t)(rowshift * vrowb32);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(krs, (lds_void *)(k_tr + i * 1024), 16, kd_tr[i] + kadd, kso, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(vrs, (lds_void *)(v_row + i * 1024), 16, vd_row[i] + vadd, vso, 0, 0);
+            const int rowshift = whole ? 0 : (min(RPI * i + kv.ld_row, last) - kv.ld_row);
+            const int kso = whole ? ks + i * kv.kstep : ks, vso = whole ? vs + i * kv.vstep : vs;
+            const uint32_t kadd = whole ? 0u : (uint32_t)(rowshift * kv.krowb), vadd = whole ? 0u : (uint32_t)(rowshift * kv.vrowb);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(kv.krs, (lds_void *)(k_tr + i * 1024), 16, kd_tr[i] + kadd, kso, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(kv.vrs, (lds_void *)(v_row + i * 1024), 16, vd_row[i] + vadd, vso, 0, 0);
         }
 #else
         (void)tok0;
@@ -492,13 +405,8 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_rows_kernel(SelAttnBwdParams P,
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         x8 kfr[2][KS], vfr[2][KS];
         x4 ktr[2][MT];
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int s = 0; s < KS; ++s) {
-                kfr[u][s] = *(const x8 *)(k_tr + rd_krow[s] + u * 16 * BROWB);
-                vfr[u][s] = *(const x8 *)(v_row + rd_row[s] + u * 16 * BROWB);
-            }
+        read_row_frags<D>(k_tr, rd_krow, kfr);
+        read_row_frags<D>(v_row, rd_row, vfr);
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -599,10 +507,10 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(SelAttnBwdParams P, co
                                                         const unsigned long long *__restrict__ hitmap, const unsigned long long *__restrict__ fullmap,
                                                         int *__restrict__ flags, int rows_per_split, int nkb, int nbg, int nsplit) {
     using M = BwdT<T>;
-    using Gm = BGeo<D>;
+    using Gm = Geo<D>;
     using x8 = typename M::x8;
     using x4 = typename M::x4;
-    constexpr int BROWB = Gm::ROWB, PIECES = Gm::PIECES, KS = Gm::KS, MT = Gm::MT;
+    constexpr int BROWB = Gm::ROWB, PIECES = Gm::PIECES, KS = Gm::KSTEPS, MT = Gm::MT;
     // Workgroup -> (key block j, bg, row split z).  Workgroups go round-robin over the 8 XCDs by linear id; all key blocks
     // of one (bg, z) pair are put on ONE XCD (its 512 Q/dO rows stay in that L2), and the pairs are dealt evenly over the
     // XCDs (every pair carries about the same number of hits, while key block 0 alone is hit by every row: a j-major
@@ -655,8 +563,8 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(SelAttnBwdParams P, co
     for (int i = 0; i < 64 * PIECES / 256; ++i) {
         const int p = tid + 256 * i, r = p / PIECES, pc = p % PIECES;
         const int64_t kr = min(key0 + r, P.S_kv - 1);
-        *(u32x4 *)(k_img + Gm::off_row_img(r, pc)) = *(const u32x4 *)(Kb + kr * P.kss + pc * 8);
-        *(u32x4 *)(v_img + Gm::off_row_img(r, pc)) = *(const u32x4 *)(Vb + kr * P.vss + pc * 8);
+        *(u32x4 *)(k_img + Gm::row_img(r, pc)) = *(const u32x4 *)(Kb + kr * P.kss + pc * 8);
+        *(u32x4 *)(v_img + Gm::row_img(r, pc)) = *(const u32x4 *)(Vb + kr * P.vss + pc * 8);
     }
     __syncthreads();
     // B operands of S = Q.K^T and dP = dO.V^T for this wave's 16 keys: loop invariant
@@ -664,7 +572,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(SelAttnBwdParams P, co
     uint32_t kvrd[KS];
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
-        kvrd[s] = Gm::off_row_img(16 * wave + rho, 4 * s + q);
+        kvrd[s] = Gm::row_img(16 * wave + rho, 4 * s + q);
         if constexpr (!KV_LDS) {
             kB[s] = *(const x8 *)(k_img + kvrd[s]);
             vB[s] = *(const x8 *)(v_img + kvrd[s]);
@@ -679,11 +587,11 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(SelAttnBwdParams P, co
     }
     uint32_t rd_row[KS], rd_tr[MT];
 #pragma unroll
-    for (int s = 0; s < KS; ++s) rd_row[s] = Gm::off_tr_img(rho, 4 * s + q);
+    for (int s = 0; s < KS; ++s) rd_row[s] = Gm::tr_img(rho, 4 * s + q);
     {
         const int qq = rho >> 2, pp = rho & 3, r = 4 * q + qq;
 #pragma unroll
-        for (int n = 0; n < MT; ++n) rd_tr[n] = r * BROWB + ((n ^ Gm::swz_tr(r)) << 5) + 8 * pp;
+        for (int n = 0; n < MT; ++n) rd_tr[n] = r * BROWB + ((n ^ Gm::swz_v(r)) << 5) + 8 * pp;
     }
 
     // query rows are split over gridDim.z workgroups per key block (block 0 and the local blocks are selected by every
@@ -785,8 +693,8 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(SelAttnBwdParams P, co
 #pragma unroll
             for (int i = 0; i < NLD; ++i) {
                 const int p = tid + 256 * i, slot = p / PIECES, pc = p % PIECES;
-                *(u32x4 *)(q_img + Gm::off_tr_img(slot, pc)) = qa[i];
-                *(u32x4 *)(do_img + Gm::off_tr_img(slot, pc)) = da[i];
+                *(u32x4 *)(q_img + Gm::tr_img(slot, pc)) = qa[i];
+                *(u32x4 *)(do_img + Gm::tr_img(slot, pc)) = da[i];
             }
             if (tid < SLOTS) {
                 s_lse2[tid] = l2n;
@@ -1012,7 +920,7 @@ static int launch_bwd_t(const SelAttnBwdParams &P, float *delta, hipStream_t st)
         const int nw = ((P.S_kv + 31) / 32 + 31) / 32;
         if (tpw >= 2 && P.S >= 2 * tpw && P.n >= 1 && P.n <= 64 && nw <= 128) {
             const int rg_ints = (2 * tpw * P.n + 3) & ~3, bm_ints = (2 * tpw * nw + 16 + 3) & ~3;
-            const int wave_lds = 2 * 32 * BGeo<D>::ROWB + 4 * (rg_ints + bm_ints);
+            const int wave_lds = 2 * 32 * Geo<D>::ROWB + 4 * (rg_ints + bm_ints);
             const int64_t nbg2 = P.R / P.S, ngrp = (P.S + tpw - 1) / tpw, W4 = (ngrp + 3) / 4;
             NSA_CHECK_ARG(nbg2 * W4 < ((int64_t)1 << 31) && 4 * (size_t)wave_lds <= 160 * 1024, "bwd_dq_rows: launch too large");
             if (4 * (size_t)wave_lds > 64 * 1024)

@@ -175,18 +175,11 @@ __global__ __launch_bounds__(256, 2) void sel_attn_fwd_mfma_kernel(SelAttnParams
         }
     };
 
-    // K/V of this (b,g) as buffer resources: loads are `buffer_load_dwordx4 v, voffset(VGPR), srsrc, soffset(SGPR)` --
-    // the per-tile part of the address is scalar, the per-lane part a loop-invariant VGPR: no VALU address math.
-    // The descriptor is built from wave-uniform values only (readfirstlane'd halves), so no waterfall loop is emitted.
+    // K/V of this (b,g) as buffer resources (kv_rsrc).  The tile source, DMA and staging below are this kernel's own copy of kv_src / tile_dma
+    // (attn_mfma_tiles.hpp): with the shared ones its launches measured 0.6 % slower; a swizzle or tail-clamp fix goes to both.
     typedef __attribute__((ext_vector_type(4))) unsigned int bu32x4;
-    auto make_rsrc = [&](const unsigned char *base, int64_t bytes) {
-        const uint64_t a = (uint64_t)base;
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), (short)0,
-                                                 __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
-    };
-    const auto krs = make_rsrc(Kb, (int64_t)(P.S_kv - 1) * krowb + G_::ROWB);
-    const auto vrs = make_rsrc(Vb, (int64_t)(P.S_kv - 1) * vrowb + G_::ROWB);
+    const auto krs = kv_rsrc(Kb, (int64_t)(P.S_kv - 1) * krowb + G_::ROWB);
+    const auto vrs = kv_rsrc(Vb, (int64_t)(P.S_kv - 1) * vrowb + G_::ROWB);
     // readfirstlane pins these in SGPRs (a soffset the compiler keeps in a VGPR costs a waterfall loop per load)
     const int krowb32 = uniform((int)krowb), vrowb32 = uniform((int)vrowb);
     const int kstep = uniform(G_::RPI * (int)krowb), vstep = uniform(G_::RPI * (int)vrowb);

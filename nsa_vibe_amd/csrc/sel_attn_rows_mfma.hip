@@ -162,14 +162,8 @@ __global__ __launch_bounds__(256, 2) void sel_attn_rows_mfma_kernel(SelAttnParam
     const unsigned char *Kb = (const unsigned char *)((const T *)P.K + (int64_t)b * P.ksb + (int64_t)g * P.ksg);
     const unsigned char *Vb = (const unsigned char *)((const T *)P.V + (int64_t)b * P.vsb + (int64_t)g * P.vsg);
     const int64_t krowb = P.kss * 2, vrowb = P.vss * 2;
-    auto make_rsrc = [&](const unsigned char *base, int64_t bytes) {
-        const uint64_t a = (uint64_t)base;
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), (short)0,
-                                                 __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
-    };
-    [[maybe_unused]] const auto krs = make_rsrc(Kb, (int64_t)(P.S_kv - 1) * krowb + G_::ROWB);
-    [[maybe_unused]] const auto vrs = make_rsrc(Vb, (int64_t)(P.S_kv - 1) * vrowb + G_::ROWB);
+    [[maybe_unused]] const auto krs = kv_rsrc(Kb, (int64_t)(P.S_kv - 1) * krowb + G_::ROWB);
+    [[maybe_unused]] const auto vrs = kv_rsrc(Vb, (int64_t)(P.S_kv - 1) * vrowb + G_::ROWB);
     [[maybe_unused]] const int krowb32 = uniform((int)krowb), vrowb32 = uniform((int)vrowb);
     [[maybe_unused]] const int kstep = uniform(G_::RPI * (int)krowb), vstep = uniform(G_::RPI * (int)vrowb);
     const int ld_row = lane / G_::PIECES, ld_piece = lane % G_::PIECES;
@@ -177,17 +171,13 @@ __global__ __launch_bounds__(256, 2) void sel_attn_rows_mfma_kernel(SelAttnParam
 #pragma unroll
     for (int i = 0; i < G_::NLD; ++i) {
         const int r = i * G_::RPI + ld_row;
-        kdma[i] = (uint32_t)(ld_row * krowb + ((ld_piece ^ G_::swz_k(r)) << 4));
-        vdma[i] = (uint32_t)(ld_row * vrowb + (((((ld_piece >> 1) ^ G_::swz_v(r)) << 1) | (ld_piece & 1)) << 4));
+        kdma[i] = (uint32_t)(ld_row * krowb + G_::row_piece(r, ld_piece));
+        vdma[i] = (uint32_t)(ld_row * vrowb + G_::tr_piece(r, ld_piece));
     }
     uint32_t krd0[KS], vrd0[MT];
-#pragma unroll
-    for (int s = 0; s < KS; ++s) krd0[s] = rho * G_::ROWB + (((4 * s + q) ^ G_::swz_k(rho)) << 4);
-    {
-        const int qq = rho >> 2, pp = rho & 3, r = 4 * q + qq;
-#pragma unroll
-        for (int m = 0; m < MT; ++m) vrd0[m] = r * G_::ROWB + ((m ^ G_::swz_v(r)) << 5) + 8 * pp;
-    }
+    frag_read_offsets<D>(rho, q, krd0, vrd0);
+    // (the tile source above and this DMA are the kernel's own copy of kv_src / tile_dma, attn_mfma_tiles.hpp: with the shared ones the D = 128
+    // instances lose a hazard s_nop in the partial-mask loop.  A swizzle or tail-clamp fix goes to both.)
     // a tile of 32 keys starting at tok0 -> wave-private LDS (swizzle applied on the source side); rows past the end of K/V
     // re-read the last row (they are masked: a tile reaching past S_kv is never `full`)
     auto issue_dma = [&](int tok0) {
@@ -207,9 +197,9 @@ __global__ __launch_bounds__(256, 2) void sel_attn_rows_mfma_kernel(SelAttnParam
                 const int r = i * G_::RPI + ld_row;
                 const int rc = min(r, last);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(krs, (lds_void *)(kl + i * 1024), 16,
-                                                         rc * krowb32 + ((ld_piece ^ G_::swz_k(r)) << 4), ks, 0, 0);
+                                                         rc * krowb32 + G_::row_piece(r, ld_piece), ks, 0, 0);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(vrs, (lds_void *)(vl + i * 1024), 16,
-                                                         rc * vrowb32 + (((((ld_piece >> 1) ^ G_::swz_v(r)) << 1) | (ld_piece & 1)) << 4), vs, 0, 0);
+                                                         rc * vrowb32 + G_::tr_piece(r, ld_piece), vs, 0, 0);
             }
         }
 #else
@@ -265,19 +255,8 @@ __global__ __launch_bounds__(256, 2) void sel_attn_rows_mfma_kernel(SelAttnParam
         x8 kfr[2][KS];
         x8 va[MT];
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // LDS-DMA completion is a vmcnt event
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int s = 0; s < KS; ++s) kfr[u][s] = *(const x8 *)(kl + krd0[s] + u * 16 * G_::ROWB);
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-            const x4 lo = M::tr(vl + vrd0[m]), hi = M::tr(vl + vrd0[m] + 16 * G_::ROWB);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                va[m][j] = lo[j];
-                va[m][4 + j] = hi[j];
-            }
-        }
+        read_row_frags<D>(kl, krd0, kfr);
+        read_tr_frags<T, D>(vl, vrd0, va);
         // ownership of this tile: bit r of fullm / touchm = row r covers it completely / selected at least one of its keys
         if ((cur >> 5) != cw) {  // lane r < ntok caches row r's bitmap words of the current 32-tile group (refreshed once per word)
             cw = cur >> 5;

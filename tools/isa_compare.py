@@ -2,8 +2,11 @@
 """Per-kernel comparison of two device-assembly listings of one translation unit (a refactor's before / after):
     hipcc <the Makefile's FLAGS> --cuda-device-only -S x.hip -o x.s -Rpass-analysis=kernel-resource-usage 2> x.remarks
     tools/isa_compare.py old.s old.remarks new.s new.remarks [old-name-regex=new-name-template ...]
-Prints instruction count, VGPRs, scratch and waves per SIMD of every kernel in both builds and whether the instruction streams are
-identical (labels renumbered, symbol names ignored).  Renamed kernels are paired by the regex arguments (on demangled names)."""
+Prints instruction count, VGPRs, scratch, LDS and waves per SIMD of every kernel in both builds and whether the instruction streams are
+identical (labels renumbered, symbol names ignored).  A kernel that differs also gets the verdict on its loops: "loops same" when every
+loop block (tools/isa_loop.py's blocks, in order) keeps its VALU / SALU / DS / VMEM / MFMA counts, so that the difference lies outside the
+loops or in the order inside a block.  Flags: SCRATCH+, OCC-, VGPR+, LDS!=, LOOPS!=.  Renamed kernels are paired by the regex arguments
+(on demangled names)."""
 import re, subprocess, sys
 
 
@@ -15,13 +18,18 @@ def demangle(names):
     return [re.sub(r"^void ", "", re.sub(r"\(.*", "", o)).replace("nsa::", "") for o in out]
 
 
+def kind(op):
+    return 4 if op.startswith("v_mfma") else 0 if op.startswith("v_") else 1 if op.startswith("s_") else 2 if op.startswith("ds_") else \
+        3 if op.startswith(("global_", "buffer_", "flat_", "scratch_")) else 5
+
+
 def kernels(asm, remarks):
-    body, cur = {}, None
+    body, loops, cur = {}, {}, None
     for line in open(asm):
         m = re.match(r"\s*\.type\s+(\S+),@function", line)
         if m:
             cur = m.group(1)
-            body[cur] = []
+            body[cur], loops[cur], mix = [], [], None
             continue
         if cur is None:
             continue
@@ -32,6 +40,12 @@ def kernels(asm, remarks):
         if not t or t.startswith(".") and not t.endswith(":") or t == cur + ":":
             continue
         body[cur].append(re.sub(r"\.LBB\d+_", ".LBB_", t))
+        if t.endswith(":"):  # a block label: the blocks of a loop say so in the label's comment
+            mix = [0] * 6 if ("Loop" in line or "Depth" in line) else None
+            if mix is not None:
+                loops[cur].append(mix)
+        elif mix is not None:
+            mix[kind(t.split()[0])] += 1
     res, cur = {}, None
     for line in open(remarks):
         m = re.search(r"remark:\s+(.*?)\s*\[-Rpass", line)
@@ -48,7 +62,8 @@ def kernels(asm, remarks):
     for n, d in zip(names, demangle(names)):
         ins = [t for t in body[n] if not t.endswith(":")]
         r = res[n]
-        out[d] = dict(n=len(ins), text=body[n], vgpr=r.get("VGPRs"), scratch=r.get("ScratchSize [bytes/lane]"), occ=r.get("Occupancy [waves/SIMD]"))
+        out[d] = dict(n=len(ins), text=body[n], loops=[m[:5] for m in loops[n]], vgpr=r.get("VGPRs"), scratch=r.get("ScratchSize [bytes/lane]"),
+                      occ=r.get("Occupancy [waves/SIMD]"), lds=r.get("LDS Size [bytes/block]"))
     return out
 
 
@@ -68,9 +83,12 @@ def main():
         ident = o["text"] == b["text"]
         if ident:
             same.append(name if to == name else f"{name} -> {to}")
-        flags = "".join([" SCRATCH+" if int(b["scratch"]) > int(o["scratch"]) else "", " OCC-" if int(b["occ"]) < int(o["occ"]) else ""])
+        flags = "".join([" SCRATCH+" if int(b["scratch"]) > int(o["scratch"]) else "", " OCC-" if int(b["occ"]) < int(o["occ"]) else "",
+                         " VGPR+" if int(b["vgpr"]) > int(o["vgpr"]) else "", " LDS!=" if b["lds"] != o["lds"] else ""])
+        if not ident:
+            flags = ("  loops same" if o["loops"] == b["loops"] else " LOOPS!=") + flags
         rows.append(f"{name}" + (f"\n    -> {to}" if to != name else "") +
-                    f"\n    instr {o['n']} -> {b['n']}  vgpr {o['vgpr']} -> {b['vgpr']}  scratch {o['scratch']} -> {b['scratch']}  waves/SIMD {o['occ']} -> {b['occ']}"
+                    f"\n    instr {o['n']} -> {b['n']}  vgpr {o['vgpr']} -> {b['vgpr']}  scratch {o['scratch']} -> {b['scratch']}  lds {o['lds']} -> {b['lds']}  waves/SIMD {o['occ']} -> {b['occ']}"
                     f"  {'identical' if ident else 'differs'}{flags}")
     print("\n".join(rows))
     print(f"\nidentical instruction streams ({len(same)} of {len(old)} kernels):")
