@@ -469,7 +469,8 @@ NSA_API int nsa_sel_decode_step_plan(int B, int G, int h, int Dk, int Dv, int S_
  *   forced initial and local blocks, and attends K/V[b,g,:t+1].
  *   Q [B,S,G,h,Dk], O [B,S,G,h,Dv], ranges_out [B,S,G,n_top,2] int32; K_cmp / K / V and their strides as in nsa_sel_decode_step.
  *   S_cmp, S_sel, S_kv describe the cache AFTER the S tokens were appended (the block meta of t0 + S tokens); S_kv >= t0 + S.
- * This is not a ragged-batch step: there is no array of positions, every row's bounds follow from its index, S and t0.
+ * Every sequence of this call sits at the same t0: every row's bounds follow from its index, S and t0.  A batch whose sequences sit at
+ * different positions is nsa_sel_decode_ragged (below), the same kernel form with a device array of positions.
  * Kernel form: ONE launch -- the decode step's kernel with one workgroup per row, each deriving its own token, compressed rows and chunks
  * from the row index -- on the unsplit exact forms only: logits in registers (two chunks of 64 compressed rows per wave, 8 or 16 waves by
  * B*S*G) at Dk = Dv in {64, 128}, four chunks per wave at 64 where the LARGEST row (t0 + S - 1) exceeds that, whatever DECODE_WIDE says;
@@ -494,6 +495,54 @@ NSA_API int nsa_sel_decode_rows(const void *Q, const void *K_cmp, const void *K,
                         int64_t v_stride_s, int dtype, float scale, void *workspace, size_t workspace_bytes, void *stream);
 NSA_API int nsa_sel_decode_rows_plan(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int n_top, int dtype,
                              int *launches /* host */, int *form /* host */);
+
+/* ---------------------------------------------------------------------------------------
+ * Ragged-batch decode step of the selected branch: nsa_sel_decode_rows with the position of every sequence read from a DEVICE array.
+ * Shapes as there (Q [B,S,G,h,Dk], O [B,S,G,h,Dv], ranges_out [B,S,G,n_top,2], 1 <= S <= 16); row (b,s,g) sits at token
+ * t = t_pos[b] + s and computes what nsa_sel_decode_step computes at t on sequence b's cache truncated to t + 1 tokens: its own n_cmp(t)
+ * compressed rows, normalised over those alone, sequential selection at t, attention over K/V[b,g,:t+1].
+ *   t_pos  device int32 [B].  The host never reads it: no copy, no synchronisation, and the call's arguments need not change from token
+ *          to token (a captured graph can advance the array on the device).
+ *   t_max  host upper bound of t_pos[b] + S - 1 over the batch.  Form and waves per row are planned from t_max and B*S*G exactly as the
+ *          rows form plans from t0 + S - 1: logits in registers (form 0) or, at D = 64, four chunks per wave (form 1); 8 or 16 waves.
+ *   S_cmp, S_sel, S_kv describe the caches' CAPACITY bound: the block metadata of at least min(t_max, S_kv - 1) + 1 tokens, and the rows
+ *          the buffers may be read up to.
+ * Inactive sequences: t_pos[b] < 0, or t_pos[b] + S - 1 > min(t_max, S_kv - 1).  Such a sequence reads nothing from the caches and gets
+ * zeros in all of its O and ranges_out rows -- the padding slot of a serving batch, and the guard that keeps a wrong position inside the
+ * buffers.  Nothing is clamped silently.
+ * A row without a compressed token (t < l - 1) is handled inside the kernel: no compressed row is read, its group scores are zero, the
+ * selector and the attention run as for any row -- the ranges of nsa_sel_decode_step at that token.
+ * ONE launch or none.  Declined with NSA_ERR_INVALID and a message naming the limit: anything but bf16 / f16, Dk = Dv in {64, 128},
+ * h <= 16, the default block geometry (l = 32, d = 16, l' = 64), 16-byte aligned operands, S <= 16, or a t_max beyond the unsplit forms
+ * (more than 64 / 32 / 16 chunks of 64 compressed tokens at 16 waves / 8 waves / D = 128) -- the separate launches take a scalar
+ * position only and cannot stand in.  DECODE_STEP = 0 and DECODE_UNFUSED = 1 decline as well; DECODE_ROWS does not apply.
+ * nsa_sel_decode_ragged_plan: *launches = 1 and *form = 0 / 1, or *launches = 0 and *form = -1 for a declined shape (status NSA_OK).
+ * workspace: nsa_sel_decode_ragged_workspace() bytes (0 today: the launch keeps everything on chip); may be null.
+ * Bits: with t_pos[b] = t0 for every b, ranges and O are those of nsa_sel_decode_rows(t0); the existing entry points are unchanged.
+ * ------------------------------------------------------------------------------------- */
+NSA_API size_t nsa_sel_decode_ragged_workspace(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int n_top, int dtype);
+NSA_API int nsa_sel_decode_ragged(const void *Q, const void *K_cmp, const void *K, const void *V, const int32_t *csc_ptr,
+                          const int32_t *csc_rows, const float *csc_vals, int32_t *ranges_out, void *O,
+                          const int32_t *t_pos /* device, [B] */, int t_max /* host */, int B, int S, int G, int h, int Dk, int Dv,
+                          int S_cmp, int S_sel, int S_kv, int l, int d, int l_sel, int n_top, int64_t kc_stride_b, int64_t kc_stride_g,
+                          int64_t kc_stride_s, int64_t k_stride_b, int64_t k_stride_g, int64_t k_stride_s, int64_t v_stride_b,
+                          int64_t v_stride_g, int64_t v_stride_s, int dtype, float scale, void *workspace, size_t workspace_bytes,
+                          void *stream);
+NSA_API int nsa_sel_decode_ragged_plan(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int n_top, int dtype,
+                               int t_max, int *launches /* host */, int *form /* host */);
+
+/* Band attention forward with per-sequence positions (the sliding and the compressed branch of a ragged decode step): nsa_band_attn_fwd
+ * with t0 replaced by a device array.  Query row (b, t) sits at absolute position t_pos[b] + t; hi and lo follow from it by the formula
+ * above.  t_max: host upper bound of t_pos[b] + S - 1 (the host never reads t_pos).  Route, split count and workspace are those of the
+ * scalar call (they depend on B, S, G, h, D alone).  Inactive sequences -- t_pos[b] < 0, t_pos[b] + S - 1 > t_max, or a last row whose
+ * unclamped hi exceeds S_kv (sliding: t_pos[b] + S - 1 > S_kv - 1) -- give zero rows and lse = -inf.  Both kernels take the array: MFMA
+ * (bf16 / f16) and generic (fp32 and everything else it covers).  Forward only. */
+NSA_API size_t nsa_band_attn_fwd_ragged_workspace(int B, int S, int G, int h, int Dk, int Dv, int dtype);
+NSA_API int nsa_band_attn_fwd_ragged(const void *Q, const void *K, const void *V, void *O, float *lse,
+                             const int32_t *t_pos /* device, [B] */, int t_max /* host */, int B, int S, int G, int h, int Dk, int Dv,
+                             int S_kv, int64_t k_stride_b, int64_t k_stride_g, int64_t k_stride_s, int64_t v_stride_b,
+                             int64_t v_stride_g, int64_t v_stride_s, int a, int dd, int c, int w, int dtype, float scale, int variant,
+                             void *workspace, size_t workspace_bytes, void *stream);
 
 /* indices [R,K] int32 ascending with -1 padding -> ranges [R,K,2]; clamp end to t+1. */
 NSA_API int nsa_indices_to_ranges_v2(const int32_t *indices, int64_t R, int S, int G, int t0, int K, int S_sel,

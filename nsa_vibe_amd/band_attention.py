@@ -19,7 +19,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .selection_attention import _bwd_variant
+from .selection_attention import _bwd_variant, _positions_to, _ragged_positions
 from .selection_scorer import _DT, _need_gpu, _scale_arg, _stream, _ws_args, workspace, workspace_at
 
 _W_INF = 2 ** 30
@@ -33,7 +33,18 @@ def band_ranges(S: int, S_kv: int, t0: int, a: int, dd: int, c: int, w: int, dev
     return torch.stack((lo, hi), dim=-1).to(torch.int32)
 
 
-def _fwd(Q, K, V, band, scale, variant, want_lse):
+def _fwd(Q, K, V, band, scale, variant, want_lse, t_pos=None, t_max=None):
+    who = "band attention"
+    if t_pos is not None:  # ragged form: the positions are checked before anything native is touched
+        if Q.dim() != 5:
+            raise RuntimeError("band attention: expected Q[B,S,G,h,Dk] K[B,G,S_kv,Dk] V[B,G,S_kv,Dv]")
+        if band[0] != 0:
+            raise RuntimeError(f"{who}: t_pos and a non-zero t0 are mutually exclusive")
+        if Q.requires_grad or K.requires_grad or V.requires_grad:
+            raise RuntimeError(f"{who}: per-sequence positions (t_pos) are forward only: no input may require grad")
+        t_pos, t_max, host = _ragged_positions(who, t_pos, t_max, Q.shape[0], Q.shape[1])
+    elif t_max is not None:
+        raise RuntimeError(f"{who}: t_max is the bound of t_pos and needs it")
     dev = _need_gpu(Q, K, V)
     if not (Q.dtype == K.dtype == V.dtype) or Q.dtype not in _DT:
         raise RuntimeError(f"band attention: Q/K/V must share a dtype in fp32/bf16/fp16 (got {Q.dtype},{K.dtype},{V.dtype})")
@@ -54,6 +65,17 @@ def _fwd(Q, K, V, band, scale, variant, want_lse):
     L = _lib.lib()
     dt = _DT[Q.dtype]
     ws = workspace(dev, L.nsa_band_attn_fwd_workspace(B, S, G, h, Dk, Dv, dt), "band")
+    if t_pos is not None:
+        if host is None and t_pos.device != dev:
+            raise RuntimeError("all tensors must be on the same device")
+        pos = _positions_to(dev, t_pos, host)
+        rc = L.nsa_band_attn_fwd_ragged(Qc.data_ptr(), Kc.data_ptr() if S_kv else None, Vc.data_ptr() if S_kv else None, O.data_ptr(),
+                                        lse.data_ptr() if lse is not None else None, pos.data_ptr(), t_max, B, S, G, h, Dk, Dv, S_kv,
+                                        Kc.stride(0), Kc.stride(1), Kc.stride(2), Vc.stride(0), Vc.stride(1), Vc.stride(2),
+                                        int(a), int(dd), int(c), int(min(w, _W_INF)), dt, _scale_arg(scale), int(variant),
+                                        *_ws_args(ws), _stream(dev))
+        _lib.check(rc, "nsa_band_attn_fwd_ragged")
+        return O, lse, (Qc, Kc, Vc)
     rc = L.nsa_band_attn_fwd(Qc.data_ptr(), Kc.data_ptr() if S_kv else None, Vc.data_ptr() if S_kv else None, O.data_ptr(),
                              lse.data_ptr() if lse is not None else None, B, S, G, h, Dk, Dv, S_kv,
                              Kc.stride(0), Kc.stride(1), Kc.stride(2), Vc.stride(0), Vc.stride(1), Vc.stride(2),
@@ -97,11 +119,18 @@ class _BandAttnFn(torch.autograd.Function):
 
 def band_attention_hip(Q, K, V, *, t0: int = 0, a: int = 0, dd: int = 1, c: int = 0, w: int = _W_INF,
                        scale: Optional[float] = None, variant: int = 0, return_lse: bool = False,
-                       bwd_variant: Optional[int] = None):
+                       bwd_variant: Optional[int] = None, t_pos=None, t_max: Optional[int] = None):
     """Row t attends keys [max(0, hi - w), hi), hi = (t0+t+1 >= a) ? min(S_kv, (t0+t+1-a)//dd + c) : 0.
 
-    variant: 0 auto, 1 generic, 2 MFMA (forward); bwd_variant: the same for the backward, None = 0 unless variant is 1."""
+    variant: 0 auto, 1 generic, 2 MFMA (forward); bwd_variant: the same for the backward, None = 0 unless variant is 1.
+    t_pos / t_max (ragged batch, nsa_band_attn_fwd_ragged; forward only, exclusive with a non-zero t0): sequence b's row t sits at
+    t_pos[b] + t.  t_pos is a device int32 tensor [B] (t_max, a host bound of t_pos[b] + S - 1, is then required: nothing is read back) or
+    host integers (t_max defaults to max + S - 1).  A sequence with a negative position, one beyond t_max, or one whose last row would need
+    keys past S_kv gives zero rows and lse = -inf."""
     band = (int(t0), int(a), int(dd), int(c), int(w))
+    if t_pos is not None or t_max is not None:
+        O, lse, _ = _fwd(Q, K, V, band, scale, variant, return_lse, t_pos, t_max)
+        return (O, lse) if return_lse else O
     if torch.is_grad_enabled() and (Q.requires_grad or K.requires_grad or V.requires_grad):
         if return_lse:
             raise RuntimeError("return_lse is not available on the autograd path")
@@ -112,15 +141,19 @@ def band_attention_hip(Q, K, V, *, t0: int = 0, a: int = 0, dd: int = 1, c: int 
     return (O, lse) if return_lse else O
 
 
-def sliding_window_attention(Q, K, V, w: int, *, t0: int = 0, scale: Optional[float] = None, variant: int = 0):
-    """Keys [t-w+1 .. t] of row t (reference attention_kernels.py:146-178; w <= 0 or no keys -> zeros, :153-154)."""
-    return band_attention_hip(Q, K, V, t0=t0, a=0, dd=1, c=0, w=max(int(w), 0), scale=scale, variant=variant)
+def sliding_window_attention(Q, K, V, w: int, *, t0: int = 0, scale: Optional[float] = None, variant: int = 0, t_pos=None,
+                             t_max: Optional[int] = None):
+    """Keys [t-w+1 .. t] of row t (reference attention_kernels.py:146-178; w <= 0 or no keys -> zeros, :153-154).
+    t_pos / t_max: per-sequence positions of a ragged batch (band_attention_hip)."""
+    return band_attention_hip(Q, K, V, t0=t0, a=0, dd=1, c=0, w=max(int(w), 0), scale=scale, variant=variant, t_pos=t_pos, t_max=t_max)
 
 
 def batched_causal_attention_compressed(Q, K_cmp, V_cmp, l: int, d: int, *, t0: int = 0, scale: Optional[float] = None,
-                                        variant: int = 0):
-    """Keys [0, num_cmp(t)), num_cmp(t) = 0 if t+1 < l else (t+1-l)//d + 1, clamped to S_cmp (attention_kernels.py:118-121)."""
-    return band_attention_hip(Q, K_cmp, V_cmp, t0=t0, a=int(l), dd=int(d), c=1, w=_W_INF, scale=scale, variant=variant)
+                                        variant: int = 0, t_pos=None, t_max: Optional[int] = None):
+    """Keys [0, num_cmp(t)), num_cmp(t) = 0 if t+1 < l else (t+1-l)//d + 1, clamped to S_cmp (attention_kernels.py:118-121).
+    t_pos / t_max: per-sequence positions of a ragged batch (band_attention_hip)."""
+    return band_attention_hip(Q, K_cmp, V_cmp, t0=t0, a=int(l), dd=int(d), c=1, w=_W_INF, scale=scale, variant=variant, t_pos=t_pos,
+                              t_max=t_max)
 
 
 def batched_causal_attention_compressed_first_key_parity(Q, K_cmp, V_cmp, l: int, d: int, *, t0: int = 0):

@@ -9,7 +9,9 @@ namespace nsa {
 
 // STAGE 1: tiles come by LDS-DMA; STAGE 0: register staging (global loads issued behind the fragment reads, ds_write at the top of the
 // next iteration): the compute-bound NT = 3 form spends ~19 % of a tile issuing its 8 DMA instructions, plain loads issue faster.
-template <typename T, int D, int NT, bool SPLIT, int STAGE>
+// RAGGED (nsa_band_attn_fwd_ragged): the position of sequence b comes from P.t_pos[b] (band_pos, sel_attn_params.hpp).  A template flag, not a
+// test of the pointer: this body is inlined into every decode-step kernel, and those -- like the scalar band kernels -- keep their code.
+template <typename T, int D, int NT, bool SPLIT, int STAGE, bool RAGGED = false>
 // WPB: waves of a workgroup that take band work (SPLIT form: every wave is its own unit; the plain kernels run 4)
 // mg (SPLIT, S = 1 only): BandMergeArgs of sel_attn_params.hpp -- merge the unit's splits here; eval_gates: this launch's branch also
 // evaluates the gate probabilities of its rows
@@ -48,8 +50,14 @@ __device__ __forceinline__ void band_attn_body(const BandAttnParams &P, const un
     unsigned char *vl = kl + G_::TILE_BYTES;
 
     // ---- key interval of the wave and of every slot (hi and lo are non-decreasing in t)
-    const int hi_min = band_hi(P.t0, P.a, P.dd, P.c, P.S_kv, tw0);
-    const int hi_max = band_hi(P.t0, P.a, P.dd, P.c, P.S_kv, tw0 + ntok - 1);
+    [[maybe_unused]] BandPos bp{0, true};
+    if constexpr (RAGGED) bp = band_pos(P, b);  // the sequence's own position, one scalar load (b is wave uniform)
+    auto row_hi = [&](int t) {
+        if constexpr (RAGGED) return band_row_hi(P, bp, t);
+        else return band_hi(P.t0, P.a, P.dd, P.c, P.S_kv, t);
+    };
+    const int hi_min = row_hi(tw0);
+    const int hi_max = row_hi(tw0 + ntok - 1);
     const int klo = max(0, hi_min - P.w), lo_max = max(0, hi_max - P.w);
     const int rho = lane & 15, q = lane >> 4;
     int hi_s[NT], lo_s[NT];
@@ -60,7 +68,7 @@ __device__ __forceinline__ void band_attn_body(const BandAttnParams &P, const un
         const int slot = 16 * n + rho, tok = slot / h, head = slot - tok * h;
         const bool used = tok < ntok;
         const int t = tw0 + tok;
-        hi_s[n] = used ? band_hi(P.t0, P.a, P.dd, P.c, P.S_kv, t) : 0;
+        hi_s[n] = used ? row_hi(t) : 0;
         lo_s[n] = max(0, hi_s[n] - P.w);
         orow[n] = used ? ((((int64_t)b * P.S + t) * P.G + g) * h + head) : -1;
 #pragma unroll

@@ -5,7 +5,8 @@
 
 namespace nsa {
 
-template <typename T>
+// RAGGED: row (b, t) sits at P.t_pos[b] + t (nsa_band_attn_fwd_ragged); a template flag, so the scalar kernel keeps its code
+template <typename T, bool RAGGED = false>
 __global__ __launch_bounds__(256) void band_attn_fwd_generic_kernel(BandAttnParams P) {
     __shared__ float sq[4][256];
     const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
@@ -16,7 +17,10 @@ __global__ __launch_bounds__(256) void band_attn_fwd_generic_kernel(BandAttnPara
     const int g = (int)(row % P.G);
     const int64_t bt = row / P.G;
     const int t = (int)(bt % P.S), b = (int)(bt / P.S);
-    const int hi = band_hi(P.t0, P.a, P.dd, P.c, P.S_kv, t), lo = max(0, hi - P.w);
+    int hi;
+    if constexpr (RAGGED) hi = band_row_hi(P, band_pos(P, b), t);
+    else hi = band_hi(P.t0, P.a, P.dd, P.c, P.S_kv, t);
+    const int lo = max(0, hi - P.w);
     const T *Qr = (const T *)P.Q + wid * P.Dk;
     const T *Kb = (const T *)P.K + (int64_t)b * P.ksb + (int64_t)g * P.ksg;
     const T *Vb = (const T *)P.V + (int64_t)b * P.vsb + (int64_t)g * P.vsg;
@@ -66,7 +70,10 @@ int launch_band_attn_fwd_generic(const BandAttnParams &P, int dtype, hipStream_t
     const int64_t nrh = (int64_t)P.B * P.S * P.G * P.h;
     NSA_CHECK_ARG((nrh + 3) / 4 < ((int64_t)1 << 31), "band_attn: too many rows for one launch");
     const dim3 grid((unsigned)((nrh + 3) / 4)), block(256);
-    with_elt(dtype, [&](auto t) { hipLaunchKernelGGL(band_attn_fwd_generic_kernel<decltype(t)>, grid, block, 0, st, P); });
+    with_elt(dtype, [&](auto t) {
+        if (P.t_pos) hipLaunchKernelGGL((band_attn_fwd_generic_kernel<decltype(t), true>), grid, block, 0, st, P);
+        else hipLaunchKernelGGL(band_attn_fwd_generic_kernel<decltype(t)>, grid, block, 0, st, P);
+    });
     NSA_LAUNCH_CHECK("band_attn_fwd_generic");
     return NSA_OK;
 }

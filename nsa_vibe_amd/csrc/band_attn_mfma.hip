@@ -18,9 +18,9 @@
 
 namespace nsa {
 
-template <typename T, int D, int NT, bool SPLIT, int STAGE>
+template <typename T, int D, int NT, bool SPLIT, int STAGE, bool RAGGED = false>
 __global__ __launch_bounds__(256, 2) void band_attn_fwd_kernel(BandAttnParams P) {
-    band_attn_body<T, D, NT, SPLIT, STAGE>(P, blockIdx.x);
+    band_attn_body<T, D, NT, SPLIT, STAGE, RAGGED>(P, blockIdx.x);
 }
 
 // decode: the sliding and the compressed branch of one step in ONE launch (two argument blocks, split-KV form)
@@ -230,9 +230,11 @@ static int launch_band_t(const BandAttnParams &P0, hipStream_t st) {
     const int64_t nbg = (int64_t)P.B * P.G;
     const int ngrp = (P.S + P.tpw - 1) / P.tpw;
     const size_t lds = 4 * (size_t)(2 * Geo<D>::TILE_BYTES);
+    const bool ragged = P.t_pos != nullptr;  // per-sequence positions: the RAGGED instantiations (LDS-DMA staging only)
     if (split) {
         const int64_t waves = nbg * ngrp * P.nsplit;
-        hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, 1, true, 1>), dim3((unsigned)((waves + 3) / 4)), dim3(256), lds, st, P);
+        if (ragged) hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, 1, true, 1, true>), dim3((unsigned)((waves + 3) / 4)), dim3(256), lds, st, P);
+        else hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, 1, true, 1>), dim3((unsigned)((waves + 3) / 4)), dim3(256), lds, st, P);
         NSA_LAUNCH_CHECK("band_attn_fwd(split)");
         if (P.defer_combine) return NSA_OK;
         SelAttnParams C{};
@@ -252,7 +254,9 @@ static int launch_band_t(const BandAttnParams &P0, hipStream_t st) {
     const unsigned grid = (unsigned)(nbg * W);
     const int stage = tuning(TUNE_BAND_STAGE);  // A/B switch: 0 = register staging, 1 = LDS-DMA  // measured: LDS-DMA 750 vs register staging 650 TFLOP/s (compressed branch, 64k)
     constexpr int NTW = D == 64 ? 3 : 2;
-    if (nt != NTW) hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, 1, false, 1>), dim3(grid), dim3(256), lds, st, P);
+    if (ragged && nt != NTW) hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, 1, false, 1, true>), dim3(grid), dim3(256), lds, st, P);
+    else if (ragged) hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, NTW, false, 1, true>), dim3(grid), dim3(256), lds, st, P);
+    else if (nt != NTW) hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, 1, false, 1>), dim3(grid), dim3(256), lds, st, P);
     else if (D == 128 || stage != 0) hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, NTW, false, 1>), dim3(grid), dim3(256), lds, st, P);
     else if constexpr (D == 64) hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, NTW, false, 0>), dim3(grid), dim3(256), lds, st, P);  // (register staging: D = 64 only)
     NSA_LAUNCH_CHECK("band_attn_fwd");

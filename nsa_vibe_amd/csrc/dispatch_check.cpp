@@ -406,15 +406,117 @@ static void run_proj(const std::string &label, const std::function<int()> &call)
     });
 }
 
+// ---- dispatch_check <library> ragged: the entry points with per-sequence positions (nsa_sel_decode_ragged, nsa_band_attn_fwd_ragged), cases
+// of their own so that the default output keeps its cases and members.  The position array is a device pointer the host must never read: it
+// is handed over as an address inside a named buffer and shows up again in the argument block of the launch.
+static void ragged_cases() {
+    const int dt = NSA_DT_BF16, G = 2, h = 6, n = 16;
+    const size_t MB = 1 << 20;
+    void *Q = dev(MB), *K = dev(MB), *V = dev(MB), *Kc = dev(MB), *O = dev(MB), *ws = dev(16 * MB);
+    float *lse = (float *)dev(MB), *csc_vals = (float *)dev(MB);
+    int32_t *ranges = (int32_t *)dev(MB), *t_pos = (int32_t *)dev(MB, 0x7f), *csc_ptr = (int32_t *)dev(MB), *csc_rows = (int32_t *)dev(MB);
+    g_named = {{"Q", Q, MB}, {"K", K, MB}, {"V", V, MB}, {"K_cmp", Kc, MB}, {"O", O, MB}, {"ranges", ranges, MB}, {"t_pos", t_pos, MB}, {"ws", ws, 16 * MB},
+               {"lse", lse, MB}};
+    auto ncmp = [](int t) { return t + 1 < 32 ? 0 : (t + 1 - 32) / 16 + 1; };
+    auto ragged_fn = NSA_FN(nsa_sel_decode_ragged);
+    auto plan_fn = NSA_FN(nsa_sel_decode_ragged_plan);
+    struct Case {
+        int B = 3, S = 1, D = 64, t_max = 100, dtype = NSA_DT_BF16;
+        void *K = nullptr;
+        const int32_t *t_pos = nullptr;
+    };
+    auto ragged_case = [&](const char *label, const std::function<void(Case &)> &tweak) {
+        Case c;
+        c.K = K;
+        c.t_pos = t_pos + 5;
+        tweak(c);
+        const int S_kv = c.t_max + 1, S_cmp = ncmp(c.t_max), S_sel = (S_kv + 63) / 64;
+        const int64_t ccg = (int64_t)S_cmp * c.D, ksg = (int64_t)S_kv * c.D;
+        auto call = [&] {
+            return ragged_fn(Q, Kc, c.K, V, csc_ptr, csc_rows, csc_vals, ranges, O, c.t_pos, c.t_max, c.B, c.S, G, h, c.D, c.D, S_cmp, S_sel, S_kv, 32, 16, 64, n, G * ccg,
+                             ccg, c.D, G * ksg, ksg, c.D, G * ksg, ksg, c.D, c.dtype, 0.f, nullptr, 0, nullptr);
+        };
+        run((std::string("sel_decode_ragged/") + label).c_str(), call, [&] {
+            int launches = -1, form = -2;
+            const int prc = plan_fn(c.B, c.S, G, h, c.D, c.D, S_cmp, S_sel, S_kv, n, c.dtype, c.t_max, &launches, &form);
+            std::string o = Obj().i("rc", prc).i("launches", launches).i("form", form).str();
+            o = "\"plan\": " + o;
+            int at = -1;
+            for (size_t i = 0; i < g_names.size(); ++i)
+                if (g_names[i] == "decode_step launch" || g_names[i] == "decode_rows launch") at = (int)i;
+            if (at < 0) return o + ", \"step\": null";
+            peek<nsa::DecStepParams>(at);
+            g_refuse_at = -1;
+            g_launches = 0;
+            call();
+            const nsa::DecStepParams P = peeked<nsa::DecStepParams>(0);
+            return o + ", \"step\": " +
+                   Obj().p("Q", P.Q).p("Kc", P.Kc).i("R", P.R).i("G", P.G).i("h", P.h).i("S_cmp", P.S_cmp).i("S_sel", P.S_sel).i("NS", P.NS).i("nchunk", P.nchunk)
+                       .i("S", P.S).p("t_pos", P.t_pos).i("t_max", P.t_max).str();
+        });
+    };
+    ragged_case("t_max100", [](Case &) {});
+    ragged_case("t_max100_S4", [](Case &c) { c.S = 4; });
+    ragged_case("t_max20_no_compressed_token", [](Case &c) { c.t_max = 20; });
+    ragged_case("t_max40000_form1", [](Case &c) { c.B = 1; c.t_max = 40000; });
+    ragged_case("D128_t_max20000_declined", [](Case &c) { c.D = 128; c.t_max = 20000; });
+    ragged_case("t_max70000_declined", [](Case &c) { c.B = 1; c.t_max = 70000; });
+    ragged_case("B200_t_max40000_declined", [](Case &c) { c.B = 200; c.t_max = 40000; });
+    ragged_case("f32_declined", [](Case &c) { c.dtype = NSA_DT_F32; });
+    ragged_case("S17_declined", [](Case &c) { c.S = 17; });
+    ragged_case("K_2_bytes_off", [&](Case &c) { c.K = off(K, 2); });
+    ragged_case("null_t_pos", [](Case &c) { c.t_pos = nullptr; });
+    NSA_FN(nsa_hip_set_tuning)("DECODE_STEP", 0);
+    ragged_case("DECODE_STEP_0_declined", [](Case &) {});
+    NSA_FN(nsa_hip_set_tuning)("DECODE_STEP", 1);
+    NSA_FN(nsa_hip_set_tuning)("DECODE_ROWS", 0);  // the rows form's own switch does not apply
+    ragged_case("DECODE_ROWS_0_still_one_launch", [](Case &) {});
+    NSA_FN(nsa_hip_set_tuning)("DECODE_ROWS", -1);
+
+    // the band call: launches and split count are the scalar call's (planned from the row count), the positions ride in the argument block
+    auto band_fn = NSA_FN(nsa_band_attn_fwd_ragged);
+    auto band_ws = NSA_FN(nsa_band_attn_fwd_ragged_workspace);
+    const std::vector<Want> blocks = {want<nsa::BandAttnParams>("band_attn_fwd(split)", "BandAttnParams"), want<nsa::BandAttnParams>("band_attn_fwd", "BandAttnParams"),
+                                      want<nsa::BandAttnParams>("band_attn_fwd_generic", "BandAttnParams")};
+    auto band_case = [&](const char *label, int B, int S, int dtype, int t_max, bool compressed, bool with_ws) {
+        const int D = 64, S_kv = compressed ? ncmp(t_max) : t_max + 1;
+        const int64_t sg = (int64_t)S_kv * D;
+        run_args(std::string("band_attn_fwd_ragged/") + label, [&] {
+            return band_fn(Q, K, V, O, lse, t_pos + 5, t_max, B, S, G, h, D, D, S_kv, G * sg, sg, D, G * sg, sg, D, compressed ? 32 : 0, compressed ? 16 : 1,
+                           compressed ? 1 : 0, compressed ? 1 << 30 : 512, dtype, 0.f, 0, with_ws ? ws : nullptr, with_ws ? 16 * MB : 0, nullptr);
+        }, blocks);
+        // (what show(BandAttnParams) leaves out: the ragged members, from the first launch)
+        peek<nsa::BandAttnParams>(0);
+        run((std::string("band_attn_fwd_ragged/") + label + "_positions").c_str(), [&] {
+            return band_fn(Q, K, V, O, lse, t_pos + 5, t_max, B, S, G, h, D, D, S_kv, G * sg, sg, D, G * sg, sg, D, compressed ? 32 : 0, compressed ? 16 : 1,
+                           compressed ? 1 : 0, compressed ? 1 << 30 : 512, dtype, 0.f, 0, with_ws ? ws : nullptr, with_ws ? 16 * MB : 0, nullptr);
+        }, [&] {
+            const nsa::BandAttnParams P = peeked<nsa::BandAttnParams>();
+            return Obj().p("t_pos", P.t_pos).i("t_max", P.t_max).i("t0", P.t0).i("nsplit", P.nsplit).i("workspace", (long long)band_ws(B, S, G, h, D, D, dtype)).s;
+        });
+    };
+    band_case("sliding_B5_S1_split", 5, 1, dt, 4100, false, true);
+    band_case("sliding_B5_S1_no_workspace", 5, 1, dt, 4100, false, false);
+    band_case("compressed_B5_S3_split", 5, 3, dt, 5002, true, true);
+    band_case("sliding_B600_S3_unsplit", 600, 3, dt, 1000, false, true);
+    band_case("sliding_f32_generic", 5, 1, NSA_DT_F32, 1000, false, true);
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: dispatch_check <libnsa_sel_hip.so>\n");
+        fprintf(stderr, "usage: dispatch_check <libnsa_sel_hip.so> [ragged]\n");
         return 2;
     }
     g_lib = dlopen(argv[1], RTLD_NOW | RTLD_GLOBAL);
     if (!g_lib) {
         fprintf(stderr, "%s\n", dlerror());
         return 2;
+    }
+    if (argc >= 3 && !strcmp(argv[2], "ragged")) {  // the cases of the ragged entry points alone (tests/test_dispatch_ragged_host.py)
+        printf("{");
+        ragged_cases();
+        printf("\n}\n");
+        return 0;
     }
     auto set_tuning = NSA_FN(nsa_hip_set_tuning);
     const int dt = NSA_DT_BF16;

@@ -700,7 +700,91 @@ int nsa::sel_decode_rows_impl(const SelDecodeCall &c, void *workspace, size_t wo
     return sel_attn_fwd_impl(attn_call(c, w + W.a + W.p, workspace_bytes - W.a - W.p, stream), 0, nullptr);
 }
 
+// compressed tokens / selection blocks that the metadata of t + 1 tokens holds (default geometry)
+static int ragged_ncmp(int t) { return t + 1 < 32 ? 0 : (t + 1 - 32) / 16 + 1; }
+
+int nsa::sel_decode_ragged_impl(const SelDecodeCall &c, const int32_t *t_pos, int t_max, void *stream) {
+    NSA_CHECK_ARG(dtype_ok(c.dtype), "decode_ragged: unknown dtype %d", c.dtype);
+    NSA_CHECK_ARG(c.B >= 0 && c.S >= 0 && c.G >= 1 && c.h >= 1 && c.Dk >= 1 && c.Dv >= 1 && c.S_cmp >= 0 && c.S_sel >= 1 && c.S_kv >= 1, "decode_ragged: bad sizes");
+    NSA_CHECK_ARG(c.n_top >= 1 && c.n_top <= 64, "decode_ragged: n_top must be in [1,64]");
+    NSA_CHECK_ARG(t_max >= 0, "decode_ragged: t_max (the host bound of t_pos[b] + S - 1) must not be negative");
+    // the caches' capacity bound: no live row sits beyond te, and the metadata must cover te + 1 tokens
+    const int te = std::min(t_max, c.S_kv - 1);
+    NSA_CHECK_ARG(c.S_cmp >= ragged_ncmp(te) && (int64_t)c.S_sel * 64 >= (int64_t)te + 1,
+                  "decode_ragged: S_cmp / S_sel must describe at least min(t_max, S_kv - 1) + 1 = %d tokens (got S_cmp = %d, S_sel = %d)", te + 1, c.S_cmp, c.S_sel);
+    if (c.rows() == 0) return NSA_OK;
+    NSA_CHECK_ARG(c.Q && c.K && c.V && c.O && c.ranges_out && t_pos && (c.K_cmp || c.S_cmp == 0), "decode_ragged: null pointer");
+    NSA_CHECK_ARG((uintptr_t)t_pos % 4 == 0, "decode_ragged: t_pos must be 4-byte aligned");
+    const char *why = nullptr;
+    NSA_CHECK_ARG(decode_ragged_shape_plan(c, t_max, nullptr, nullptr, &why), "decode_ragged: %s (B = %d, S = %d, D = %d, t_max = %d)", why, c.B, c.S, c.Dk, t_max);
+    NSA_CHECK_ARG(c.d == 16 && c.l == 32 && c.l_sel == 64, "decode_ragged: the default block geometry only (l = 32, d = 16, l' = 64)");
+    NSA_CHECK_ARG(decode_ragged_operands_ok(c), "decode_ragged: Q, K_cmp, K and V must be 16-byte aligned with strides in multiples of 8 elements, "
+                                                "V rows contiguous and O 8-byte aligned");
+    return launch_decode_rows(c, (hipStream_t)stream, t_pos, t_max);
+}
+
+int nsa::band_attn_fwd_ragged_impl(const AttnCall &c, const Band &band, const int32_t *t_pos, int t_max) {
+    NSA_CHECK_ARG(dtype_ok(c.dtype), "band_attn_fwd_ragged: unknown dtype %d", c.dtype);
+    NSA_CHECK_ARG(c.B >= 0 && c.S >= 0 && c.G >= 1 && c.h >= 1 && c.Dk >= 1 && c.Dv >= 1 && c.S_kv >= 0, "band_attn_fwd_ragged: negative size");
+    NSA_CHECK_ARG(band.dd >= 1 && band.w >= 0 && t_max >= 0, "band_attn_fwd_ragged: need dd >= 1, w >= 0, t_max >= 0");
+    NSA_CHECK_ARG(c.variant >= 0 && c.variant <= 2, "band_attn_fwd_ragged: unknown variant %d", c.variant);
+    if (c.rows() == 0) return NSA_OK;
+    NSA_CHECK_ARG(c.Q && c.O && t_pos && ((c.K && c.V) || c.S_kv == 0), "band_attn_fwd_ragged: null pointer");
+    NSA_CHECK_ARG((uintptr_t)t_pos % 4 == 0, "band_attn_fwd_ragged: t_pos must be 4-byte aligned");
+    // the route, the split count and the workspace do not depend on the positions: they are the scalar call's (planned from B, S, G, h, D)
+    BandAttnParams P = band_attn_params(c, Band{0, band.a, band.dd, band.c, band.w});
+    P.t_pos = t_pos;
+    P.t_max = t_max;
+    const AttnRoute r = band_attn_route(c, band);
+    if (c.variant == 2) NSA_CHECK_ARG(r.fast_ok, "band_attn_fwd_ragged: MFMA variant requested but shape/dtype/alignment unsupported");
+    if (r.kind != AttnRoute::MFMA) return launch_band_attn_fwd_generic(P, c.dtype, c.st);
+    if (r.ws == AttnRoute::WS_SPLIT) {
+        P.part = (float *)c.ws;
+        P.nsplit = r.nsplit;
+    }
+    return launch_band_attn_fwd_mfma(P, c.dtype, c.st);
+}
+
 extern "C" {
+
+int nsa_sel_decode_ragged(const void *Q, const void *K_cmp, const void *K, const void *V, const int32_t *csc_ptr, const int32_t *csc_rows,
+                          const float *csc_vals, int32_t *ranges_out, void *O, const int32_t *t_pos, int t_max, int B, int S, int G, int h, int Dk,
+                          int Dv, int S_cmp, int S_sel, int S_kv, int l, int d, int l_sel, int n_top, int64_t kcb, int64_t kcg, int64_t kcs,
+                          int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg, int64_t vss, int dtype, float scale, void *workspace,
+                          size_t workspace_bytes, void *stream) {
+    (void)workspace, (void)workspace_bytes;  // (the one launch needs no scratch)
+    const SelDecodeCall c{Q, K_cmp, K, V, csc_ptr, csc_rows, csc_vals, ranges_out, O, B, S, G, h, Dk, Dv, S_cmp, S_sel, S_kv, l, d, l_sel, n_top, 0,
+                          kcb, kcg, kcs, ksb, ksg, kss, vsb, vsg, vss, dtype, scale};
+    return sel_decode_ragged_impl(c, t_pos, t_max, stream);
+}
+
+size_t nsa_sel_decode_ragged_workspace(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int n_top, int dtype) {
+    (void)B, (void)S, (void)G, (void)h, (void)Dk, (void)Dv, (void)S_cmp, (void)S_sel, (void)n_top, (void)dtype;
+    return 0;  // one launch, everything on chip: the query exists so that a later form may ask for scratch without a change of the callers
+}
+
+int nsa_sel_decode_ragged_plan(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int n_top, int dtype, int t_max,
+                               int *launches, int *form) {
+    NSA_CHECK_ARG(launches && form, "decode_ragged_plan: null pointer");
+    NSA_CHECK_ARG(dtype_ok(dtype), "decode_ragged_plan: unknown dtype %d", dtype);
+    NSA_CHECK_ARG(B >= 1 && S >= 1 && G >= 1 && h >= 1 && Dk >= 1 && Dv >= 1 && S_cmp >= 0 && S_sel >= 1 && S_kv >= 1 && n_top >= 1 && n_top <= 64 && t_max >= 0,
+                  "decode_ragged_plan: bad sizes");
+    // one launch or none: the separate launches take a scalar position only, so a declined shape has no route (launches 0, form -1)
+    *launches = decode_ragged_shape_plan(sel_decode_plan_call(B, S, G, h, Dk, Dv, S_cmp, S_sel, S_kv, n_top, dtype), t_max, form, nullptr, nullptr) ? 1 : 0;
+    return NSA_OK;
+}
+
+int nsa_band_attn_fwd_ragged(const void *Q, const void *K, const void *V, void *O, float *lse, const int32_t *t_pos, int t_max, int B, int S, int G,
+                             int h, int Dk, int Dv, int S_kv, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg, int64_t vss, int a, int dd,
+                             int c, int w, int dtype, float scale, int variant, void *workspace, size_t workspace_bytes, void *stream) {
+    return band_attn_fwd_ragged_impl(AttnCall{Q, K, V, nullptr, O, lse, B, S, G, h, Dk, Dv, S_kv, 0, ksb, ksg, kss, vsb, vsg, vss, dtype, scale, variant,
+                                              workspace, workspace_bytes, (hipStream_t)stream},
+                                     Band{0, a, dd, c, w}, t_pos, t_max);
+}
+
+size_t nsa_band_attn_fwd_ragged_workspace(int B, int S, int G, int h, int Dk, int Dv, int dtype) {
+    return band_attn_workspace(B, S, G, h, Dk, Dv, dtype, nullptr);  // the split count is planned from the row count alone: the scalar call's
+}
 
 int nsa_sel_decode_step(const void *Q, const void *K_cmp, const void *K, const void *V, const int32_t *csc_ptr,
                         const int32_t *csc_rows, const float *csc_vals, int32_t *ranges_out, void *O, int B, int G, int h, int Dk,

@@ -53,7 +53,15 @@ bool decode_step_shape_plan(const SelDecodeCall &c, int *form, int *nsplit);
 // rows form of the one-launch step (nsa_sel_decode_rows): S consecutive tokens per sequence at t0 .. t0 + S - 1, one workgroup per row
 bool decode_rows_shape_plan(const SelDecodeCall &c, int *form, int *nw_out);
 bool decode_rows_supported(const SelDecodeCall &c);
-int launch_decode_rows(const SelDecodeCall &c, hipStream_t st);
+// t_pos (device, [B]) / t_max: the ragged form (nsa_sel_decode_ragged) -- row (b, s, g) at t_pos[b] + s, planned from t_max
+int launch_decode_rows(const SelDecodeCall &c, hipStream_t st, const int32_t *t_pos = nullptr, int t_max = 0);
+// shape / tuning part of the ragged form's predicate, from the host bound t_max alone (the position array is never read on the host);
+// *why (optional): the limit a declined shape ran into
+bool decode_ragged_shape_plan(const SelDecodeCall &c, int t_max, int *form, int *nw_out, const char **why);
+bool decode_ragged_operands_ok(const SelDecodeCall &c);
+int sel_decode_ragged_impl(const SelDecodeCall &c, const int32_t *t_pos, int t_max, void *stream);
+// the band forward with per-sequence positions (nsa_band_attn_fwd_ragged): band.t0 is ignored
+int band_attn_fwd_ragged_impl(const AttnCall &c, const Band &band, const int32_t *t_pos, int t_max);
 
 // ---- the scorer and selector family behind the C ABI (nsa_api.hip): what nsa_sel_scores[_rows], nsa_sel_scores_select[_rows] and
 // nsa_select_topn_ranges run once their arguments are in the blocks

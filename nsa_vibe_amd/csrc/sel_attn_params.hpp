@@ -66,12 +66,33 @@ struct BandAttnParams {
     int map_mode;  // 0 linear, 1 workgroup = 4 token groups of one (b,g), 2 = 1 + XCD-aware order
     int tpw;       // tokens per wave
     int defer_combine;  // split-KV: leave the partial records for the caller's own combine pass
+    // ragged form (nsa_band_attn_fwd_ragged): device [B] positions or null; with it query row (b, t) sits at t_pos[b] + t instead of t0 + t,
+    // and a sequence outside [0, t_max - S + 1] or whose last row's interval would end past S_kv has every interval empty (band_pos)
+    const int32_t *t_pos;
+    int t_max;
 };
 __host__ __device__ inline int band_hi(int t0, int a, int dd, int c, int S_kv, int t) {
     const int e = t0 + t + 1 - a;
     if (e < 0) return 0;
     const int hi = e / dd + c;
     return hi < S_kv ? hi : S_kv;
+}
+// the position of sequence b's first query row and whether the sequence is live: the launch's t0, or with a position array t_pos[b] -- one
+// scalar load per wave (b is wave uniform).  Not live: a padding slot (negative position), a position past the caller's bound t_max, or
+// one whose last row would need keys the buffers do not hold; band_row_hi then gives 0 for every row, the existing empty-interval case
+// (zero output rows, lse = -inf).  No silent clamp.
+struct BandPos {
+    int t0;
+    bool live;
+};
+__device__ __forceinline__ BandPos band_pos(const BandAttnParams &P, int b) {
+    if (!P.t_pos) return BandPos{P.t0, true};
+    const int t0 = P.t_pos[b], last = t0 + P.S - 1;
+    const int e = last + 1 - P.a;
+    return BandPos{t0, t0 >= 0 && last <= P.t_max && (e < 0 || e / P.dd + P.c <= P.S_kv)};
+}
+__device__ __forceinline__ int band_row_hi(const BandAttnParams &P, const BandPos &bp, int t) {
+    return bp.live ? band_hi(bp.t0, P.a, P.dd, P.c, P.S_kv, t) : 0;
 }
 size_t band_attn_workspace(int B, int S, int G, int h, int Dk, int Dv, int dtype, int *nsplit_out);
 int launch_band_attn_fwd_mfma(const BandAttnParams &P, int dtype, hipStream_t st);
@@ -116,6 +137,10 @@ struct DecStepParams {
     int64_t csb, csg, css;
     float c2;
     int S;           // rows form: query rows per sequence, row (b, s, g) at token t_token + s (in the struct's tail padding: the layout of the rest is unchanged)
+    // ragged form of the rows form (nsa_sel_decode_ragged): device [B] positions or null; with it row (b, s, g) sits at t_pos[b] + s, and a
+    // sequence with t_pos[b] < 0 or t_pos[b] + S - 1 > min(t_max, S_kv - 1) reads nothing and gets zero O and ranges rows
+    const int32_t *t_pos;
+    int t_max;
 };
 // fills tpw of both argument blocks and returns the (row, split) units = waves of each; false: not both in split form with deferred combine
 bool band_dual_plan(BandAttnParams *P0, BandAttnParams *P1, int dtype, int64_t waves[2]);

@@ -24,7 +24,8 @@
 // that already holds them ("k draft tokens to verify", speculative-verify rows, the tail of a chunked prefill -- cases that otherwise take
 // the extend route's three or more launches).  One workgroup is one row (b, s, g); only the row's bounds and position were launch-wide
 // scalars (S_cmp, nchunk, t_token, and S_kv through t_end), so the workgroup derives its own from the row index, S, G and t0 and uses them
-// everywhere -- no device array of positions, not a ragged-batch step.  Unsplit exact forms only (form 0 at D = 64 / 128, form 1 at D = 64
+// everywhere.  With a device array of positions (P.t_pos, nsa_sel_decode_ragged) the same form is the ragged-batch step: t0 becomes
+// t_pos[b], a slot without a sequence writes zeros, a row without a compressed token skips the score phases.  Unsplit exact forms only (form 0 at D = 64 / 128, form 1 at D = 64
 // where the largest row exceeds form 0): no team of workgroups, no tickets, no wait of one workgroup on another, no band workgroups; shapes
 // beyond them take the separate launches.  Ranges and O are those of S single steps (tests/test_hip_decode_rows.py).  Measured against S
 // single steps and the separate launches: not slower in every cell but S = 1 on rows of >= 32 chunks, which default to the
@@ -128,8 +129,26 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
     // ROWS: the workgroup's row is (b, s, g) of S consecutive tokens per sequence on ONE cache that already holds them; its token, the
     // compressed rows it sees (n_cmp(t) of the default geometry l = 32, d = 16; the host launches only where n_cmp(t0) >= 1) and its
     // chunks follow from the row index alone.  Otherwise they are the launch's.
-    const int t_tok = ROWS ? P.t_token + (row / P.G) % P.S : P.t_token;
-    const int S_cmp = ROWS ? min(P.S_cmp, (t_tok + 1 - 32) / 16 + 1) : P.S_cmp;
+    // Ragged form (P.t_pos, nsa_sel_decode_ragged): the sequence's position comes from the device array -- one scalar load, b is uniform --
+    // instead of the launch.  A sequence that holds nothing (negative position) or whose rows would pass the caller's bound or the buffers
+    // reads nothing and gets zero O and ranges rows: the whole workgroup leaves here, before any barrier.  A row too short to have a
+    // compressed token (t < 31) has S_cmp = nchunk = 0: no chunk is loaded (load_chunk would clamp with S_cmp - 1) or scored, the group
+    // scores keep their zeros, and the selector and the gather run as for any row -- the single step's route for such a token.
+    int t_base = P.t_token;
+    if constexpr (ROWS) {
+        if (P.t_pos) {
+            t_base = P.t_pos[b];
+            if (t_base < 0 || t_base + P.S - 1 > min(P.t_max, AT.S_kv - 1)) {
+                T *Or = (T *)AT.O + (int64_t)row * h * D;
+                for (int i = threadIdx.x; i < h * D; i += NW * 64) Or[i] = Elt<T>::from_f(0.f);
+                int32_t *out = SP.out + (int64_t)row * SP.W * 2;
+                for (int i = threadIdx.x; i < 2 * SP.W; i += NW * 64) out[i] = 0;
+                return;
+            }
+        }
+    }
+    const int t_tok = ROWS ? t_base + (row / P.G) % P.S : P.t_token;
+    const int S_cmp = ROWS ? (t_tok < 31 ? 0 : min(P.S_cmp, (t_tok + 1 - 32) / 16 + 1)) : P.S_cmp;
     const int nchunk = ROWS ? (S_cmp + 63) >> 6 : P.nchunk;
     [[maybe_unused]] const int64_t kvrow = ROWS ? b * P.G + g : (int64_t)row;  // the row's K/V plane
     const int hc = min(rho, h - 1);  // head of this lane's column (columns >= h repeat the last head: their results are never used)
@@ -986,14 +1005,50 @@ bool decode_rows_shape_plan(const SelDecodeCall &c, int *form, int *nw_out) {
 
 bool decode_rows_supported(const SelDecodeCall &c) { return decode_rows_shape_plan(c, nullptr, nullptr) && dstep_operands_ok(c); }
 
-int launch_decode_rows(const SelDecodeCall &c, hipStream_t st) {
+// ---- ragged form (nsa_sel_decode_ragged): the rows form with the position of sequence b read from a device array.  The host never reads
+// the array: form and waves are planned from the caller's bound t_max (the largest token any live row can sit at) and the row count exactly
+// as decode_rows_shape_plan plans from t0 + S - 1.  What the rows form may decline on the host -- a row without a compressed token -- the
+// kernel handles, so t_max < 31 is fine here; DECODE_ROWS does not apply (its measured rule weighs alternatives this call does not have: the
+// separate launches cannot take per-sequence positions).  *why: the limit a declined call names.
+bool decode_ragged_shape_plan(const SelDecodeCall &c, int t_max, int *form, int *nw_out, const char **why) {
+    static const char *unused;
+    if (!why) why = &unused;
+    if (form) *form = -1;
+    *why = "the one-launch decode step is switched off (DECODE_STEP = 0 or DECODE_UNFUSED = 1) and there is no other route with per-sequence positions";
+    if (tuning(TUNE_DECODE_STEP) == 0 || tuning(TUNE_DECODE_UNFUSED) > 0) return false;
+    *why = "needs bf16 / f16, Dk = Dv in {64, 128}, h <= 16, 1 <= S <= 16, 3 <= n_top <= 64 and at most 2048 selection blocks";
+    if (c.B < 1 || c.S < 1 || c.S > 16 || c.G < 1 || c.h < 1 || c.h > 16 || c.Dk != c.Dv || (c.Dk != 64 && c.Dk != 128) || c.S_cmp < 0 || c.S_sel < 1 ||
+        c.S_kv < 1 || t_max < 0 || t_max > (1 << 30) || c.rows() > (1 << 24))
+        return false;
+    const int nw = dec_att_waves(c.rows(), c.Dk);
+    const int n_max = std::min(c.S_cmp, dstep_ncmp(t_max)), nchunk = (n_max + 63) / 64;
+    int fm;
+    if (nchunk <= 2 * nw) fm = 0;
+    else if (c.Dk == 64 && nchunk <= 4 * nw) fm = 1;
+    else {
+        *why = c.Dk == 128 ? "t_max is beyond the unsplit form at D = 128: more than 16 chunks of 64 compressed tokens per row"
+               : nw == 16  ? "t_max is beyond the unsplit forms at 16 waves per row: more than 64 chunks of 64 compressed tokens per row"
+                           : "t_max is beyond the unsplit forms at 8 waves per row (more than 256 rows): more than 32 chunks of 64 compressed tokens per row";
+        return false;
+    }
+    if (!dstep_shape_ok(c, nw, fm)) return false;
+    if (form) *form = fm;
+    if (nw_out) *nw_out = nw;
+    return true;
+}
+
+bool decode_ragged_operands_ok(const SelDecodeCall &c) { return dstep_operands_ok(c); }
+
+int launch_decode_rows(const SelDecodeCall &c, hipStream_t st, const int32_t *t_pos, int t_max) {
     int nw = 16, form = 0;
-    NSA_CHECK_ARG(decode_rows_shape_plan(c, &form, &nw), "decode rows: shape not covered (decode_rows_supported)");
+    if (t_pos) NSA_CHECK_ARG(decode_ragged_shape_plan(c, t_max, &form, &nw, nullptr), "decode ragged: shape not covered (decode_ragged_shape_plan)");
+    else NSA_CHECK_ARG(decode_rows_shape_plan(c, &form, &nw), "decode rows: shape not covered (decode_rows_supported)");
     const int64_t R = c.rows();
     const int D = c.Dk, h = c.h, cpw = form == 1 ? 4 : 2;
-    const int nchunk = (std::min(c.S_cmp, dstep_ncmp(c.t0 + c.S - 1)) + 63) / 64;  // of the largest row: every row derives its own
+    const int nchunk = (std::min(c.S_cmp, dstep_ncmp(t_pos ? t_max : c.t0 + c.S - 1)) + 63) / 64;  // of the largest row: every row derives its own
     const float c2 = default_scale(c.scale, D) * LOG2E;
-    DecStepParams P{c.Q, c.K_cmp, nullptr, nullptr, nullptr, nullptr, (int)R, c.G, h, c.S_cmp, c.S_sel, 1, nchunk, nchunk, c.t0, 0, c.kcb, c.kcg, c.kcs, c2, c.S};
+    DecStepParams P{c.Q, c.K_cmp, nullptr, nullptr, nullptr, nullptr, (int)R, c.G, h, c.S_cmp, c.S_sel, 1, nchunk, nchunk, c.t0, 0, c.kcb, c.kcg, c.kcs, c2, c.S,
+                    t_pos, t_max};
     DecStepBlocks A{};
     if (int rc = dstep_blocks(c, c2, &A)) return rc;
     void (*k)(DecStepParams, SelectParams, int, DecAttnArgs, DecBandPair);

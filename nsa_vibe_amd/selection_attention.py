@@ -260,6 +260,121 @@ def selection_decode_rows_plan(B: int, S: int, G: int, h: int, Dk: int, Dv: int,
     return {"launches": n.value, "form": f.value}
 
 
+def _ragged_positions(who: str, t_pos, t_max, B: int, S: int):
+    """the per-sequence positions of a ragged call, checked before any native call -> (positions, t_max, host): a device int32 tensor [B]
+    as given (host = None; t_max is then required: nothing is read back), or host integers (a sequence or a CPU tensor) as a list with
+    t_max defaulting to max + S - 1; the caller copies the list to the device without blocking (_positions_to)"""
+    if isinstance(t_pos, torch.Tensor) and t_pos.device.type != "cpu":
+        if t_pos.dtype != torch.int32 or t_pos.dim() != 1 or t_pos.numel() != B or not t_pos.is_contiguous():
+            raise RuntimeError(f"{who}: t_pos on the device must be a contiguous int32 tensor [B = {B}] (got {t_pos.dtype}, {tuple(t_pos.shape)})")
+        if t_max is None:
+            raise RuntimeError(f"{who}: t_max (a host upper bound of t_pos[b] + S - 1) is required with device positions: they are never read back")
+        host = None
+    else:
+        if isinstance(t_pos, torch.Tensor):
+            if t_pos.is_floating_point() or t_pos.is_complex() or t_pos.dtype == torch.bool or t_pos.dim() != 1:
+                raise RuntimeError(f"{who}: t_pos must hold integers, one per sequence (got {t_pos.dtype}, {tuple(t_pos.shape)})")
+            host = [int(v) for v in t_pos.tolist()]
+        else:
+            try:
+                host = list(t_pos)
+            except TypeError:
+                raise RuntimeError(f"{who}: t_pos must be a device int32 tensor [B] or a sequence of B integers") from None
+            if any(isinstance(v, bool) or not isinstance(v, int) for v in host):
+                raise RuntimeError(f"{who}: t_pos must hold integers")
+        if len(host) != B:
+            raise RuntimeError(f"{who}: t_pos has {len(host)} entries for B = {B} sequences")
+        if any(v >= 2 ** 30 or v < -2 ** 31 for v in host):
+            raise RuntimeError(f"{who}: t_pos out of range")
+        if t_max is None:
+            t_max = max([v for v in host if v >= 0], default=0) + S - 1
+    t_max = int(t_max)
+    if t_max < 0 or t_max >= 2 ** 30:
+        raise RuntimeError(f"{who}: t_max must be in [0, 2^30)")
+    return t_pos, t_max, host
+
+
+def _positions_to(dev, t_pos, host):
+    """device int32 [B] of the positions: the caller's device tensor, or the host integers through pinned memory (a non-blocking copy)"""
+    if host is None:
+        return t_pos
+    return torch.tensor(host, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+
+
+def selection_decode_ragged_plan(B: int, S: int, G: int, h: int, Dk: int, Dv: int, S_cmp: int, S_sel: int, S_kv: int, n_top: int, t_max: int,
+                                 dtype: torch.dtype = torch.bfloat16) -> dict:
+    """What selection_decode_ragged does with a shape whose largest live row sits at t_max (nsa_sel_decode_ragged_plan; default block
+    geometry, aligned inputs): {"launches": 1, "form": 0 logits in registers / 1 four chunks per wave}, or {"launches": 0, "form": -1}
+    where the call declines -- there is no other native route with per-sequence positions."""
+    import ctypes
+
+    n, f = ctypes.c_int(0), ctypes.c_int(0)
+    rc = _lib.lib().nsa_sel_decode_ragged_plan(int(B), int(S), int(G), int(h), int(Dk), int(Dv), int(S_cmp), int(S_sel), int(S_kv), int(n_top),
+                                               _DT[dtype], int(t_max), ctypes.byref(n), ctypes.byref(f))
+    _lib.check(rc, "nsa_sel_decode_ragged_plan")
+    return {"launches": n.value, "form": f.value}
+
+
+def selection_decode_ragged(Q: torch.Tensor, K_cmp: torch.Tensor, K: torch.Tensor, V: torch.Tensor, meta, n_top: int, t_pos, *,
+                            t_max: Optional[int] = None, scale: Optional[float] = None, out: Optional[torch.Tensor] = None,
+                            ranges_out: Optional[torch.Tensor] = None):
+    """The decode step of the selected branch for a batch whose sequences sit at DIFFERENT positions, in one native call
+    (nsa_sel_decode_ragged: the rows form of the one-launch step with a device array of positions).
+
+    Q [B,S,G,h,Dk] (1 <= S <= 16): row (b, s) is token t_pos[b] + s of sequence b and computes what selection_decode_step computes at that
+    token on sequence b's cache truncated to it.  K_cmp [B,G,S_cmp,Dk], K/V [B,G,S_kv,D] and meta give the caches' capacity: the block
+    metadata of at least t_max + 1 tokens, and the rows the buffers may be read up to.
+    t_pos: a device int32 tensor [B] -- then t_max, a host upper bound of t_pos[b] + S - 1, is required and nothing is synchronised -- or
+    host integers (a sequence or a CPU tensor), copied to the device without blocking, with t_max defaulting to max + S - 1.
+    A sequence with t_pos[b] < 0 or t_pos[b] + S - 1 > min(t_max, S_kv - 1) is inactive: it reads nothing and its O and ranges rows are
+    zeros (the padding slot of a serving batch).
+    Where the native call declines (selection_decode_ragged_plan: launches 0) host positions run one selection_decode_rows call per active
+    sequence on that sequence's views (same ranges, O from that route); device positions raise RuntimeError with the library's message.
+    Returns (O [B,S,G,h,Dv], ranges [B,S,G,n_top,2] int32).  Inference only."""
+    who = "selection_decode_ragged"
+    if Q.dim() != 5:
+        raise RuntimeError(f"{who}: expected Q[B,S,G,h,Dk]")
+    B, S, G, h, Dk = Q.shape
+    t_pos, t_max, host = _ragged_positions(who, t_pos, t_max, B, S)
+    dev = _need_gpu(Q, K_cmp, K, V)
+    if host is None and t_pos.device != dev:
+        raise RuntimeError("all tensors must be on the same device")
+    S_kv, Dv = K.shape[2], V.shape[3]
+    S_cmp, S_sel = K_cmp.shape[2], meta.S_sel
+    O = out if out is not None else torch.empty((B, S, G, h, Dv), dtype=V.dtype, device=dev)
+    rg = ranges_out if ranges_out is not None else torch.empty((B, S, G, n_top, 2), dtype=torch.int32, device=dev)
+    if O.numel() == 0:
+        return O, rg
+    dt = _DT[Q.dtype]
+    if host is not None and selection_decode_ragged_plan(B, S, G, h, Dk, Dv, S_cmp, S_sel, S_kv, n_top, t_max, Q.dtype)["launches"] == 0:
+        # declined (a t_max beyond the unsplit forms, fp32, ...): the positions are known here, so each active sequence takes the rows call
+        from .block_index import build_block_meta
+
+        O.zero_()
+        rg.zero_()
+        for b, t0 in enumerate(host):
+            if t0 < 0 or t0 + S - 1 > min(t_max, S_kv - 1):
+                continue
+            n_tok = t0 + S
+            n_c = 0 if n_tok < meta.l else (n_tok - meta.l) // meta.d + 1
+            selection_decode_rows(Q[b:b + 1], K_cmp[b:b + 1, :, :min(n_c, S_cmp)], K[b:b + 1, :, :n_tok], V[b:b + 1, :, :n_tok],
+                                  build_block_meta(n_tok, meta.l, meta.d, meta.l_sel, meta.n_sel, meta.w), n_top, t0, scale=scale,
+                                  out=O[b:b + 1], ranges_out=rg[b:b + 1])
+        return O, rg
+    L = _lib.lib()
+    Qc, Kc, Kk, Vv = Q.contiguous(), _prep_kv(K_cmp), _prep_kv(K), _prep_kv(V)
+    pos = _positions_to(dev, t_pos, host)
+    cptr, crows, cvals = meta.device_csc(dev)
+    ws = workspace(dev, L.nsa_sel_decode_ragged_workspace(B, S, G, h, Dk, Dv, S_cmp, S_sel, n_top, dt), "decode_ragged")
+    rc = L.nsa_sel_decode_ragged(Qc.data_ptr(), Kc.data_ptr() if S_cmp else None, Kk.data_ptr(), Vv.data_ptr(), cptr.data_ptr(), crows.data_ptr(),
+                                 cvals.data_ptr(), rg.data_ptr(), O.data_ptr(), pos.data_ptr(), t_max, B, S, G, h, Dk, Dv, S_cmp, S_sel, S_kv,
+                                 int(meta.l), int(meta.d), int(meta.l_sel), int(n_top), Kc.stride(0), Kc.stride(1), Kc.stride(2), Kk.stride(0),
+                                 Kk.stride(1), Kk.stride(2), Vv.stride(0), Vv.stride(1), Vv.stride(2), dt, _scale_arg(scale), *_ws_args(ws),
+                                 _stream(dev))
+    _lib.check(rc, "nsa_sel_decode_ragged")
+    return O, rg
+
+
 def select_and_attend(p_grp: torch.Tensor, Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, meta, n_top: int, *,
                       mode: str = "batched", t0: int = 0, force_init: bool = True, force_local: int = 2,
                       scale: Optional[float] = None, return_lse: bool = False):
