@@ -20,7 +20,7 @@ import torch
 
 from . import _lib
 from .selection_attention import _bwd_variant, _positions_to, _ragged_positions
-from .selection_scorer import _DT, _need_gpu, _scale_arg, _stream, _ws_args, workspace, workspace_at
+from ._native import _DT, _need_gpu, _needs_grad, _scale_arg, _stream, _unit_rows, _ws_args, workspace, workspace_at
 
 _W_INF = 2 ** 30
 
@@ -55,9 +55,7 @@ def _fwd(Q, K, V, band, scale, variant, want_lse, t_pos=None, t_max=None):
     if K.shape[:2] != (B, G) or V.shape[:3] != (B, G, S_kv) or K.shape[3] != Dk:
         raise RuntimeError("band attention: inconsistent shapes")
     t0, a, dd, c, w = band
-    Qc = Q.contiguous()
-    Kc = K if K.stride(-1) == 1 else K.contiguous()
-    Vc = V if V.stride(-1) == 1 else V.contiguous()
+    Qc, (Kc, *ks), (Vc, *vs) = Q.contiguous(), _unit_rows(K), _unit_rows(V)
     O = torch.empty((B, S, G, h, Dv), dtype=V.dtype, device=dev)
     lse = torch.empty((B, S, G, h), dtype=torch.float32, device=dev) if want_lse else None
     if O.numel() == 0:
@@ -65,23 +63,16 @@ def _fwd(Q, K, V, band, scale, variant, want_lse, t_pos=None, t_max=None):
     L = _lib.lib()
     dt = _DT[Q.dtype]
     ws = workspace(dev, L.nsa_band_attn_fwd_workspace(B, S, G, h, Dk, Dv, dt), "band")
-    if t_pos is not None:
+    name, at, row0 = "nsa_band_attn_fwd", (), (int(t0),)  # row s at token t0 + s ...
+    if t_pos is not None:  # ... or, in the ragged form, at t_pos[b] + s: the positions stand behind lse, and there is no t0
         if host is None and t_pos.device != dev:
             raise RuntimeError("all tensors must be on the same device")
         pos = _positions_to(dev, t_pos, host)
-        rc = L.nsa_band_attn_fwd_ragged(Qc.data_ptr(), Kc.data_ptr() if S_kv else None, Vc.data_ptr() if S_kv else None, O.data_ptr(),
-                                        lse.data_ptr() if lse is not None else None, pos.data_ptr(), t_max, B, S, G, h, Dk, Dv, S_kv,
-                                        Kc.stride(0), Kc.stride(1), Kc.stride(2), Vc.stride(0), Vc.stride(1), Vc.stride(2),
-                                        int(a), int(dd), int(c), int(min(w, _W_INF)), dt, _scale_arg(scale), int(variant),
-                                        *_ws_args(ws), _stream(dev))
-        _lib.check(rc, "nsa_band_attn_fwd_ragged")
-        return O, lse, (Qc, Kc, Vc)
-    rc = L.nsa_band_attn_fwd(Qc.data_ptr(), Kc.data_ptr() if S_kv else None, Vc.data_ptr() if S_kv else None, O.data_ptr(),
-                             lse.data_ptr() if lse is not None else None, B, S, G, h, Dk, Dv, S_kv,
-                             Kc.stride(0), Kc.stride(1), Kc.stride(2), Vc.stride(0), Vc.stride(1), Vc.stride(2),
-                             int(t0), int(a), int(dd), int(c), int(min(w, _W_INF)), dt, _scale_arg(scale), int(variant),
-                             *_ws_args(ws), _stream(dev))
-    _lib.check(rc, "nsa_band_attn_fwd")
+        name, at, row0 = "nsa_band_attn_fwd_ragged", (pos.data_ptr(), t_max), ()
+    rc = getattr(L, name)(Qc.data_ptr(), Kc.data_ptr() if S_kv else None, Vc.data_ptr() if S_kv else None, O.data_ptr(),
+              lse.data_ptr() if lse is not None else None, *at, B, S, G, h, Dk, Dv, S_kv, *ks, *vs, *row0, int(a), int(dd), int(c),
+              int(min(w, _W_INF)), dt, _scale_arg(scale), int(variant), *_ws_args(ws), _stream(dev))
+    _lib.check(rc, name)
     return O, lse, (Qc, Kc, Vc)
 
 
@@ -109,8 +100,7 @@ class _BandAttnFn(torch.autograd.Function):
         dt = _DT[Qc.dtype]
         wptr, wsize, _ = workspace_at(dev, L.nsa_band_attn_bwd_workspace(B, S, G, h, Dk, Dv, S_kv, dt, ctx.bwd_variant), "band_bwd", 256)
         rc = L.nsa_band_attn_bwd(Qc.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), O.data_ptr(), lse.data_ptr(), dO.data_ptr(), dQ.data_ptr(),
-                                 dK.data_ptr(), dV.data_ptr(), B, S, G, h, Dk, Dv, S_kv,
-                                 Kc.stride(0), Kc.stride(1), Kc.stride(2), Vc.stride(0), Vc.stride(1), Vc.stride(2),
+                                 dK.data_ptr(), dV.data_ptr(), B, S, G, h, Dk, Dv, S_kv, *_unit_rows(Kc)[1:], *_unit_rows(Vc)[1:],
                                  int(t0), int(a), int(dd), int(c), int(min(w, _W_INF)), dt, _scale_arg(ctx.scale),
                                  int(ctx.bwd_variant), wptr, wsize, _stream(dev))
         _lib.check(rc, "nsa_band_attn_bwd")
@@ -131,7 +121,7 @@ def band_attention_hip(Q, K, V, *, t0: int = 0, a: int = 0, dd: int = 1, c: int 
     if t_pos is not None or t_max is not None:
         O, lse, _ = _fwd(Q, K, V, band, scale, variant, return_lse, t_pos, t_max)
         return (O, lse) if return_lse else O
-    if torch.is_grad_enabled() and (Q.requires_grad or K.requires_grad or V.requires_grad):
+    if _needs_grad(Q, K, V):
         if return_lse:
             raise RuntimeError("return_lse is not available on the autograd path")
         if K.shape[2] == 0:

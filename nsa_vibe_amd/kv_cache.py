@@ -12,10 +12,16 @@ from typing import List, Optional
 
 import torch
 
+from . import _lib
 from .block_index import BlockMeta, build_block_meta
 
 
 _META_CACHE: dict = {}
+
+
+def n_cmp_at(n_tokens: int, l: int, d: int) -> int:
+    """compressed tokens emitted once n_tokens are cached (the emission schedule of the reference, nsa_attention.py:588-604)"""
+    return 0 if n_tokens < l else (n_tokens - l) // d + 1
 
 
 class NSA_KV:
@@ -24,7 +30,7 @@ class NSA_KV:
         self.B, self.G, self.d_k, self.d_v, self.S_max = B, G, d_k, d_v, S_max
         self.auto_grow = auto_grow
         self.l, self.d, self.l_sel, self.n_sel, self.w = l, d, l_sel, n_sel, w
-        n_cmp_max = 0 if S_max < l else (S_max - l) // d + 1
+        n_cmp_max = n_cmp_at(S_max, l, d)
         mk = lambda n, dim: torch.empty((B, G, max(n, 1), dim), device=device, dtype=dtype)  # noqa: E731
         self._K_sel, self._V_sel = mk(S_max, d_k), mk(S_max, d_v)
         self._K_win, self._V_win = mk(S_max, d_k), mk(S_max, d_v)
@@ -40,6 +46,17 @@ class NSA_KV:
         self.reads_act_sel: List[int] = []
         self.reads_act_cmp: List[int] = []
         self.reads_act_win: List[int] = []
+        # what the native routes keep per cache: "desc" (native_desc) and the context of each single-step route under its workspace tag;
+        # all of it names the buffers, so reserve() empties it
+        self._native: dict = {}
+
+    def __copy__(self):
+        """a shallow copy shares the buffers until its holder replaces them (a test's clone does): it must not share _native, whose
+        descriptor and step contexts carry the addresses of the original's buffers"""
+        c = object.__new__(type(self))
+        c.__dict__.update(self.__dict__)
+        c._native = {}
+        return c
 
     # ---- reference field names as views -------------------------------------------------
     @property
@@ -80,7 +97,7 @@ class NSA_KV:
         kv_cache.py:28-30, paid here once per doubling).  Cached native descriptors of the old buffers are dropped."""
         if S_max <= self._K_sel.shape[2]:
             return
-        n_cmp_max = 0 if S_max < self.l else (S_max - self.l) // self.d + 1
+        n_cmp_max = self.n_cmp_at(S_max)
 
         def grow(buf, n, used):
             new = torch.empty((self.B, self.G, max(n, 1), buf.shape[3]), device=buf.device, dtype=buf.dtype)
@@ -92,8 +109,7 @@ class NSA_KV:
             setattr(self, name, grow(getattr(self, name), S_max, self.t))
         self._K_cmp, self._V_cmp = grow(self._K_cmp, n_cmp_max, self.n_cmp), grow(self._V_cmp, n_cmp_max, self.n_cmp)
         self.S_max = S_max
-        for attr in ("_desc", "_dec_ctx", "_blk_ctx"):
-            self.__dict__.pop(attr, None)
+        self._native.clear()
 
     def ensure_capacity(self, n_tokens: int) -> None:
         """room for n_tokens in total: grows geometrically (auto_grow) or raises"""
@@ -145,7 +161,7 @@ class NSA_KV:
             raise ValueError(f"NSA_KV.truncate: t = {t} outside [0, {self.t}]")
         drop = self.t - t
         self.t = t
-        self.n_cmp = 0 if t < self.l else (t - self.l) // self.d + 1
+        self.n_cmp = self.n_cmp_at(t)
         for lst in (self.reads_pred, self.reads_act_total, self.reads_act_sel, self.reads_act_cmp, self.reads_act_win):
             del lst[max(0, len(lst) - drop):]
 
@@ -157,3 +173,47 @@ class NSA_KV:
         self.reads_act_sel.append(sel)
         self.reads_act_cmp.append(num_cmp)
         self.reads_act_win.append(win)
+
+    # ---- bookkeeping of the rows a native call appends ------------------------------------------------------------------------------------
+    def n_cmp_at(self, n_tokens: int) -> int:
+        return n_cmp_at(n_tokens, self.l, self.d)
+
+    def refresh_meta(self, upto: int) -> None:
+        """block metadata refresh policy of the reference (:606-632): rebuilt only when the first `upto` tokens leave the covered blocks"""
+        if self.meta.S_sel == 0:
+            self.ensure_meta(max(upto, self.l_sel))
+        elif upto > self.meta.S_sel * self.l_sel:
+            self.ensure_meta(upto)
+
+    def begin_rows(self, S: int):
+        """before S tokens are appended at t: capacity, and the block metadata by the decode step's policy -> (t, meta)"""
+        t0 = self.t
+        self.ensure_capacity(t0 + S)
+        self.refresh_meta(t0 + S)
+        return t0, self.meta
+
+    def end_rows(self, t0: int, S: int) -> None:
+        """after the S tokens t0 .. t0 + S - 1 were appended: token count, compressed count and read counters as S decode steps leave them"""
+        for n in range(t0 + 1, t0 + S + 1):
+            self.append_reads(self.n_cmp_at(n), n)
+        self.t, self.n_cmp = t0 + S, self.n_cmp_at(t0 + S)
+
+    def snapshot(self):
+        """what restore() needs to forget the rows appended after this point"""
+        return self.t, self.n_cmp, len(self.reads_pred)
+
+    def restore(self, saved) -> None:
+        """back to a snapshot(): the rows a failed call appended are written again by the next executor"""
+        self.t, self.n_cmp = saved[0], saved[1]
+        for lst in (self.reads_pred, self.reads_act_total, self.reads_act_sel, self.reads_act_cmp, self.reads_act_win):
+            del lst[saved[2]:]
+
+    def native_desc(self):
+        """struct nsa_kv_desc of the buffers (include/nsa_sel_hip.h), built once per set of buffers"""
+        d = self._native.get("desc")
+        if d is None:
+            d = self._native["desc"] = _lib.NsaKvDesc()
+            d.K_sel, d.V_sel, d.K_win, d.V_win = self._K_sel.data_ptr(), self._V_sel.data_ptr(), self._K_win.data_ptr(), self._V_win.data_ptr()
+            d.K_raw, d.V_raw, d.K_cmp, d.V_cmp = self._K_raw.data_ptr(), self._V_raw.data_ptr(), self._K_cmp.data_ptr(), self._V_cmp.data_ptr()
+            d.B, d.S_max, d.n_cmp_max = self.B, self._K_sel.shape[2], self._K_cmp.shape[2]
+        return d

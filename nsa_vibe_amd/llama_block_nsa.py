@@ -18,15 +18,13 @@ import torch.nn.functional as F
 import ctypes
 
 from . import _lib
+from ._native import _DT, _stream, workspace_at
 from .kv_cache import NSA_KV
-from .nsa_attention import NSAAttention
-from .selection_scorer import _stream, workspace_at
+from .nsa_attention import NSAAttention, _one_call
 
 
 def _rmsnorm_native_ok(x: torch.Tensor, w: torch.Tensor) -> bool:
     """GPU tensors of a kernel dtype, rows the vectorised kernels take (dim % 8 == 0, <= 4096); NSA_HIP_EAGER_TRAIN=1 keeps the eager chain"""
-    from .selection_scorer import _DT
-
     return (x.is_cuda and x.dtype in _DT and w.dtype == x.dtype and x.shape[-1] % 8 == 0 and x.shape[-1] <= 4096 and x.numel() > 0
             and os.getenv("NSA_HIP_EAGER_TRAIN", "0") != "1")
 
@@ -37,8 +35,6 @@ class _RMSNormFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, eps):
-        from .selection_scorer import _DT
-
         xc = x.contiguous()
         wc = w.contiguous()
         y = torch.empty_like(xc)
@@ -51,8 +47,6 @@ class _RMSNormFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        from .selection_scorer import _DT
-
         xc, wc = ctx.saved_tensors
         dyc = dy.contiguous()
         M, dim = xc.numel() // xc.shape[-1], xc.shape[-1]
@@ -122,8 +116,6 @@ class LlamaBlockNSA(nn.Module):
 
     # ---- inference prefill: native RMSNorm + native layer core, residuals folded into the GEMMs (addmm) -----------------
     def _rmsnorm_native(self, x2d: torch.Tensor, norm: RMSNorm) -> torch.Tensor:
-        from .selection_scorer import _DT
-
         y = torch.empty_like(x2d)
         rc = _lib.lib().nsa_rmsnorm_rows(x2d.data_ptr(), norm.weight.data_ptr(), y.data_ptr(), x2d.shape[0], x2d.shape[1], float(norm.eps),
                                          _DT[x2d.dtype], _stream(x2d.device))
@@ -158,35 +150,16 @@ class LlamaBlockNSA(nn.Module):
 
     def _decode_native(self, x: torch.Tensor, kv: NSA_KV) -> torch.Tensor:
         a = self.attn
-        t, B, dev = kv.t, x.shape[0], x.device
-        kv.ensure_capacity(t + 1)
-        if kv.meta.S_sel == 0:
-            kv.ensure_meta(max(t + 1, a.l_sel))
-        elif t + 1 > kv.meta.S_sel * a.l_sel:
-            kv.ensure_meta(t + 1)
-        L = _lib.lib()
-        desc = self._block_desc()
-        ctx = getattr(kv, "_blk_ctx", None)
-        if ctx is None or ctx[0] is not desc:
-            kd = a._kv_desc(kv)
-            wptr, wsize, ws = workspace_at(dev, L.nsa_block_decode_step_workspace(ctypes.byref(desc), B, kd.S_max), "block_decode", 256)
-            ranges = torch.empty((B, a.n_kv_groups, a.n_sel, 2), dtype=torch.int32, device=dev)
-            gates = torch.empty((B, 1, a.n_kv_groups, 3), dtype=torch.float32, device=dev)
-            ctx = kv._blk_ctx = (desc, ctypes.byref(desc), ctypes.byref(kd), kd, ws, wptr, wsize, ranges, gates)
-        _, desc_ref, kd_ref, _, _, wptr, wsize, ranges, gates = ctx
-        cptr, crows, cvals = kv.meta.device_csc(dev)
+        t, meta = kv.begin_rows(1)
+        B, dev, G = x.shape[0], x.device, a.n_kv_groups
         xc = x.reshape(B, a.dim)
         if not xc.is_contiguous():
             xc = xc.contiguous()
         y = torch.empty((B, 1, a.dim), dtype=x.dtype, device=dev)
-        rc = L.nsa_block_decode_step(desc_ref, kd_ref, xc.data_ptr(), y.data_ptr(), t, cptr.data_ptr(), crows.data_ptr(), cvals.data_ptr(),
-                                     int(kv.meta.S_sel), ranges.data_ptr(), gates.data_ptr(), wptr, wsize, _stream(dev))
-        _lib.check(rc, "nsa_block_decode_step")
-        S_raw = t + 1
-        num_cmp = 0 if S_raw < a.l else (S_raw - a.l) // a.d + 1
-        kv.t, kv.n_cmp = S_raw, num_cmp
-        kv.append_reads(num_cmp, S_raw)
-        a._last_ranges, a._last_gates = ranges, gates
+        ranges, gates = _one_call("nsa_block_decode_step", "block_decode", self._block_desc(), kv, meta, dev,
+                                  (B, kv._K_sel.shape[2]), (xc.data_ptr(), y.data_ptr(), t), (), (B, G, a.n_sel, 2), (B, 1, G, 3), keep=True)
+        kv.end_rows(t, 1)
+        a._monitors(ranges, gates)
         return y
 
 
@@ -240,20 +213,13 @@ class TinyLM(nn.Module):
             len({kv.t for kv in caches}) == 1 and len({kv._K_sel.shape[2] for kv in caches}) == 1
 
     def _decode_native(self, tokens: torch.Tensor, caches: List[NSA_KV], return_next: bool):
-        from .selection_scorer import _DT  # noqa: F401
-
-        a0, kv0 = self.blocks[0].attn, caches[0]
-        t, B, dev = kv0.t, tokens.shape[0], tokens.device
+        kv0 = caches[0]
+        B, dev = tokens.shape[0], tokens.device
         probe = torch.empty((B, 1, 0), dtype=self.embed.weight.dtype, device=dev)
         for blk, kv in zip(self.blocks, caches):
             blk.attn._check_kv(probe, kv)
-            kv.ensure_capacity(t + 1)
-        if kv0.meta.S_sel == 0:
-            meta = kv0.ensure_meta(max(t + 1, a0.l_sel))
-        elif t + 1 > kv0.meta.S_sel * a0.l_sel:
-            meta = kv0.ensure_meta(t + 1)
-        else:
-            meta = kv0.meta
+            kv.ensure_capacity(kv0.t + 1)
+        t, meta = kv0.begin_rows(1)  # one block map for the stack: every layer has the geometry of the first
         L = _lib.lib()
         n = len(self.blocks)
         descs = [blk._block_desc() for blk in self.blocks]
@@ -262,7 +228,7 @@ class TinyLM(nn.Module):
         ctx = getattr(self, "_dec_ctx", None)
         if ctx is None or ctx[0] != key:
             barr = (_lib.NsaBlockDesc * n)(*descs)
-            karr = (_lib.NsaKvDesc * n)(*[blk.attn._kv_desc(kv) for blk, kv in zip(self.blocks, caches)])
+            karr = (_lib.NsaKvDesc * n)(*[kv.native_desc() for kv in caches])
             wptr, wsize, ws = workspace_at(dev, L.nsa_model_decode_step_workspace(barr, n, B, karr[0].S_max), "model_decode", 256)
             nxt = torch.empty((B, 1), dtype=torch.int32, device=dev)
             ctx = self._dec_ctx = (key, barr, karr, ws, wptr, wsize, nxt)
@@ -275,11 +241,7 @@ class TinyLM(nn.Module):
                                      nxt.data_ptr() if return_next else None, t, cptr.data_ptr(), crows.data_ptr(), cvals.data_ptr(),
                                      int(meta.S_sel), wptr, wsize, _stream(dev))
         _lib.check(rc, "nsa_model_decode_step")
-        S_raw = t + 1
-        for blk, kv in zip(self.blocks, caches):
-            a = blk.attn
-            num_cmp = 0 if S_raw < a.l else (S_raw - a.l) // a.d + 1
-            kv.t, kv.n_cmp, kv.meta = S_raw, num_cmp, meta
-            kv.meta_seq_len = kv0.meta_seq_len
-            kv.append_reads(num_cmp, S_raw)
+        for kv in caches:
+            kv.meta, kv.meta_seq_len = meta, kv0.meta_seq_len
+            kv.end_rows(t, 1)
         return (logits, nxt.to(torch.int64)) if return_next else logits

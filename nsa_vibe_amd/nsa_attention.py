@@ -42,8 +42,8 @@ from .selection_attention import (
     selection_attention_hip,
     selection_decode_step,
 )
-from .selection_scorer import (_DT, _stream, _ws_args, select_topn_ranges_batched, select_topn_ranges_rows, selection_scores,
-                               selection_scores_select, workspace, workspace_at)
+from ._native import _DT, _plan_ints, _sel_mode, _stream, workspace_at
+from .selection_scorer import select_topn_ranges_batched, select_topn_ranges_rows, selection_scores, selection_scores_select
 
 _ORIG_SELECTORS = (select_topn_ranges_batched, select_topn_ranges_rows, selection_scores)
 
@@ -57,16 +57,29 @@ def _env_prefill_tile() -> int:
     return pt if pt > 0 else 0
 
 
-def _n_cmp(S_raw: int, l: int, d: int) -> int:
-    """compressed tokens emitted once S_raw tokens are cached"""
-    return 0 if S_raw < l else (S_raw - l) // d + 1
-
-
-def _restore(kv: NSA_KV, saved) -> None:
-    """back to saved = (kv.t, kv.n_cmp, len(kv.reads_pred)): the rows a failed call appended are written again by the next executor"""
-    kv.t, kv.n_cmp = saved[0], saved[1]
-    for lst in (kv.reads_pred, kv.reads_act_total, kv.reads_act_sel, kv.reads_act_cmp, kv.reads_act_win):
-        del lst[saved[2]:]
+def _one_call(name: str, tag: str, desc, kv: NSA_KV, meta, dev, qargs, head, mid, ranges_shape, gates_shape, keep: bool = False):
+    """ONE native call of a layer route (prefill, extend, decode rows, the layer's and the block's decode step) -> (ranges, gates), which it
+    allocates.  The entry point `name` takes, in the family's common order: the layer (or block) and cache descriptors, `head` (inputs and positions), the
+    block map, S_sel, ranges, `mid` (what stands between ranges and gates), gates, the workspace, the stream.  The workspace is
+    <name>_workspace(desc, *qargs) bytes of the pool's `tag` from a 256-byte boundary on.
+    keep: a single-step route -- what does not change from step to step (the references, the workspace pointer, ranges and gates, which
+    every step overwrites) is built once per cache and descriptor and kept with the cache under `tag`."""
+    L = _lib.lib()
+    ctx = kv._native.get(tag) if keep else None
+    if ctx is None or ctx[0] is not desc:
+        dref = ctypes.byref(desc)
+        ranges = torch.empty(ranges_shape, dtype=torch.int32, device=dev)
+        gates = torch.empty(gates_shape, dtype=torch.float32, device=dev)
+        wptr, wsize, ws = workspace_at(dev, getattr(L, name + "_workspace")(dref, *qargs), tag, 256)
+        ctx = (desc, dref, ctypes.byref(kv.native_desc()), ws, wptr, wsize, ranges, gates)
+        if keep:
+            kv._native[tag] = ctx
+    _, dref, kref, _, wptr, wsize, ranges, gates = ctx
+    cptr, crows, cvals = meta.device_csc(dev)
+    rc = getattr(L, name)(dref, kref, *head, cptr.data_ptr(), crows.data_ptr(), cvals.data_ptr(), int(meta.S_sel), ranges.data_ptr(), *mid,
+                          gates.data_ptr(), wptr, wsize, _stream(dev))
+    _lib.check(rc, name)
+    return ranges, gates
 
 
 def _scores_and_ranges(Q, K_cmp, meta, n_sel, selector, S, scale):
@@ -184,7 +197,7 @@ class _RopeAppendFn(torch.autograd.Function):
     def forward(ctx, proj, module, kv, S):
         L, dev = _lib.lib(), proj.device
         desc, _ = module._layer_desc()
-        kd = module._kv_desc(kv)
+        kd = kv.native_desc()
         B = proj.shape[0]
         proj = proj.contiguous()
         Q = torch.empty((B, S, module.n_kv_groups, module.h_per_group, module.d_k), dtype=proj.dtype, device=dev)
@@ -217,8 +230,8 @@ class _CmpPoolFn(torch.autograd.Function):
     def forward(ctx, K_raw, V_raw, module, kv, S):
         L, dev = _lib.lib(), K_raw.device
         desc, _ = module._layer_desc()
-        kd = module._kv_desc(kv)
-        n_cmp = _n_cmp(S, module.l, module.d)
+        kd = kv.native_desc()
+        n_cmp = kv.n_cmp_at(S)
         _lib.check(L.nsa_cmp_pool_append(ctypes.byref(desc), ctypes.byref(kd), 0, n_cmp, _stream(dev)), "nsa_cmp_pool_append")
         kv.n_cmp = n_cmp
         ctx.module, ctx.S, ctx.n_cmp, ctx.B = module, S, n_cmp, K_raw.shape[0]
@@ -363,11 +376,20 @@ class NSAAttention(nn.Module):
     # ---- native layer path (inference): descriptors for the C ABI ------------------------------
     _QKV = ("W_Q", "W_K_sel", "W_V_sel", "W_K_win", "W_V_win", "W_K_cmp", "W_V_cmp")
 
+    def _grad_needed(self, x: torch.Tensor) -> bool:
+        """whether autograd has to see a call on x: recording is on, and x or a parameter asks for a gradient"""
+        return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+
+    def _monitors(self, ranges, gates) -> None:
+        """what get_selection_stats / get_gate_stats read"""
+        _set_plain(self, "_last_ranges", ranges)
+        _set_plain(self, "_last_gates", gates)
+
     def _native_ok(self, x: torch.Tensor) -> bool:
         """the fused kernels cover inference (no autograd graph) on the GPU; training keeps the differentiable eager ops"""
         if self._force_parity:
             return False  # the one-call layer fuses the masked-semantics executor; parity mode composes the layer from its stages
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+        if self._grad_needed(x):
             return False
         return x.is_cuda and x.dtype in _DT and self.W_Q.weight.dtype == x.dtype and self.gate.fc1.out_features <= 64
 
@@ -400,17 +422,6 @@ class NSAAttention(nn.Module):
             _set_plain(self, "_desc", d)
             _set_plain(self, "_desc_keep", keep)
         return self._desc, self._desc_keep[0]
-
-    @staticmethod
-    def _kv_desc(kv: NSA_KV):
-        d = getattr(kv, "_desc", None)
-        if d is None:
-            d = _lib.NsaKvDesc()
-            d.K_sel, d.V_sel, d.K_win, d.V_win = kv._K_sel.data_ptr(), kv._V_sel.data_ptr(), kv._K_win.data_ptr(), kv._V_win.data_ptr()
-            d.K_raw, d.V_raw, d.K_cmp, d.V_cmp = kv._K_raw.data_ptr(), kv._V_raw.data_ptr(), kv._K_cmp.data_ptr(), kv._V_cmp.data_ptr()
-            d.B, d.S_max, d.n_cmp_max = kv.B, kv._K_sel.shape[2], kv._K_cmp.shape[2]
-            kv._desc = d
-        return d
 
     # ---- helpers ---------------------------------------------------------------------------
     def _project(self, x: torch.Tensor, pos: torch.Tensor):
@@ -456,7 +467,7 @@ class NSAAttention(nn.Module):
             x = x.contiguous()
         extend = prefill and self._extend_wanted(x, kv)
         one_call = self._native_ok(x)
-        saved = (kv.t, kv.n_cmp, len(kv.reads_pred)) if extend else None
+        saved = kv.snapshot() if extend else None
         try:
             if extend:
                 return self._extend(x, kv)
@@ -464,7 +475,7 @@ class NSAAttention(nn.Module):
         except RuntimeError as e:
             def stages():  # the next executor: the layer composed from the separate native calls
                 if extend:
-                    _restore(kv, saved)  # the chunks the one-call route appended are written again
+                    kv.restore(saved)  # the chunks the one-call route appended are written again
                     return self._extend(x, kv, one_call=False)
                 return self._prefill(x, kv, one_call=False) if prefill else self._decode(x, kv, one_call=False)
             # (not one_call: the per-stage composition is the last executor there is, no CPU / eager-SDPA route exists by design)
@@ -491,8 +502,7 @@ class NSAAttention(nn.Module):
         """whether this prefill runs the extend route (kv.t > 0 or prefill_tile > 0); raises where it cannot run"""
         if kv.t == 0 and self.prefill_tile <= 0:
             return False
-        grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
-        if grad:
+        if self._grad_needed(x):
             if kv.t > 0:
                 raise RuntimeError(f"NSAAttention: prefill onto a filled cache (kv.t = {kv.t}) runs the extend route, which is inference only "
                                    "(no backward); run it under torch.no_grad() or start training from an empty cache")
@@ -524,91 +534,50 @@ class NSAAttention(nn.Module):
             rs.append(ranges)
             gs.append(gates)
         O = mixes[0] if len(mixes) == 1 else torch.cat(mixes, dim=1)
-        _set_plain(self, "_last_ranges", rs[0] if len(rs) == 1 else torch.cat(rs, dim=1))
-        _set_plain(self, "_last_gates", gs[0] if len(gs) == 1 else torch.cat(gs, dim=1))
+        self._monitors(rs[0] if len(rs) == 1 else torch.cat(rs, dim=1), gs[0] if len(gs) == 1 else torch.cat(gs, dim=1))
         return self.out(O), kv
-
-    def _extend_begin(self, kv: NSA_KV, S: int):
-        """capacity and block metadata for the chunk (metadata refreshed by the decode step's policy, reference :606-632)"""
-        t0 = kv.t
-        kv.ensure_capacity(t0 + S)
-        self._refresh_meta(kv, t0 + S)
-        return t0, kv.meta
-
-    def _refresh_meta(self, kv: NSA_KV, upto: int) -> None:
-        """block metadata refresh policy of the reference (:606-632): rebuilt only when the first `upto` tokens leave the covered blocks"""
-        if kv.meta.S_sel == 0:
-            kv.ensure_meta(max(upto, self.l_sel))
-        elif upto > kv.meta.S_sel * self.l_sel:
-            kv.ensure_meta(upto)
-
-    def _extend_end(self, kv: NSA_KV, t0: int, S: int) -> None:
-        """cache state and read counters as S decode steps leave them"""
-        for t in range(t0, t0 + S):
-            kv.append_reads(_n_cmp(t + 1, self.l, self.d), t + 1)
-        kv.t, kv.n_cmp = t0 + S, _n_cmp(t0 + S, self.l, self.d)
 
     def _extend_native(self, x: torch.Tensor, kv: NSA_KV):
         """one chunk: fused projection GEMM -> ONE native call (nsa_layer_extend) -> O_mix, ranges, gates"""
         B, S, _ = x.shape
-        t0, meta = self._extend_begin(kv, S)
-        L, dev = _lib.lib(), x.device
+        t0, meta = kv.begin_rows(S)
+        G = self.n_kv_groups
         desc, W_qkv = self._layer_desc()
-        kd = self._kv_desc(kv)
         proj = F.linear(x, W_qkv)
-        ranges = torch.empty((B, S, self.n_kv_groups, self.n_sel, 2), dtype=torch.int32, device=dev)
-        gates = torch.empty((B, S, self.n_kv_groups, 3), dtype=torch.float32, device=dev)
-        O = torch.empty((B, S, self.n_heads * self.d_v), dtype=x.dtype, device=dev)
-        wptr, wsize, _ = workspace_at(dev, L.nsa_layer_extend_workspace(ctypes.byref(desc), B, S, t0, int(meta.S_sel)), "layer_extend", 256)
-        cptr, crows, cvals = meta.device_csc(dev)
-        rc = L.nsa_layer_extend(ctypes.byref(desc), ctypes.byref(kd), proj.data_ptr(), t0, S, cptr.data_ptr(), crows.data_ptr(),
-                                cvals.data_ptr(), int(meta.S_sel), ranges.data_ptr(), O.data_ptr(), gates.data_ptr(), wptr, wsize, _stream(dev))
-        _lib.check(rc, "nsa_layer_extend")
-        self._extend_end(kv, t0, S)
+        O = torch.empty((B, S, self.n_heads * self.d_v), dtype=x.dtype, device=x.device)
+        ranges, gates = _one_call("nsa_layer_extend", "layer_extend", desc, kv, meta, x.device,
+                                  (B, S, t0, int(meta.S_sel)), (proj.data_ptr(), t0, S), (O.data_ptr(),), (B, S, G, self.n_sel, 2), (B, S, G, 3))
+        kv.end_rows(t0, S)
         return O, ranges, gates
 
     def _extend_stages(self, x: torch.Tensor, kv: NSA_KV):
-        """one chunk composed from the separate native entry points (the next executor of the one-call route): the same kernels with the
-        same arguments and workspaces, so the same bits"""
+        """one chunk composed from the separate native entry points (the next executor of the one-call route): the operators of the three
+        branches on views of the cache, so the same kernels with the same arguments, and the same bits"""
         B, S, _ = x.shape
         if not (x.is_cuda and x.dtype in _DT):
             raise RuntimeError("nsa_vibe_amd: the extend route needs a HIP device tensor of a supported dtype (no CPU fallback exists)")
-        t0, meta = self._extend_begin(kv, S)
+        t0, meta = kv.begin_rows(S)
         L, dev, st = _lib.lib(), x.device, _stream(x.device)
         desc, W_qkv = self._layer_desc()
-        dref, kd = ctypes.byref(desc), self._kv_desc(kv)
-        G, h, Dk, Dv, dt = self.n_kv_groups, self.h_per_group, self.d_k, self.d_v, _DT[x.dtype]
-        S_kv, n0, n1 = t0 + S, _n_cmp(t0, self.l, self.d), _n_cmp(t0 + S, self.l, self.d)
-        scale = 1.0 / math.sqrt(Dk)
+        dref, kref = ctypes.byref(desc), ctypes.byref(kv.native_desc())
+        G, h = self.n_kv_groups, self.h_per_group
+        S_kv, n0, n1 = t0 + S, kv.n_cmp_at(t0), kv.n_cmp_at(t0 + S)
+        scale = 1.0 / math.sqrt(self.d_k)
         proj = F.linear(x, W_qkv)
-        Q = torch.empty((B, S, G, h, Dk), dtype=x.dtype, device=dev)
-        _lib.check(L.nsa_rope_cache_append(dref, ctypes.byref(kd), proj.data_ptr(), Q.data_ptr(), S, t0, st), "nsa_rope_cache_append")
+        Q = torch.empty((B, S, G, h, self.d_k), dtype=x.dtype, device=dev)
+        _lib.check(L.nsa_rope_cache_append(dref, kref, proj.data_ptr(), Q.data_ptr(), S, t0, st), "nsa_rope_cache_append")
         if n1 > n0:
-            _lib.check(L.nsa_cmp_pool_append(dref, ctypes.byref(kd), n0, n1, st), "nsa_cmp_pool_append")
+            _lib.check(L.nsa_cmp_pool_append(dref, kref, n0, n1, st), "nsa_cmp_pool_append")
         _, ranges = selection_scores_select(Q, kv._K_cmp[:, :, :n1], meta, self.n_sel, mode="sequential", t0=t0, scale=scale,
                                             q0=t0, normalize="causal")
-        Ks, Vs, Kw, Vw = kv._K_sel, kv._V_sel, kv._K_win, kv._V_win
-        O_sel, O_win, O_cmp = (torch.empty((B, S, G, h, Dv), dtype=x.dtype, device=dev) for _ in range(3))
-        nb = L.nsa_sel_attn_fwd_workspace_kv(B, S, G, h, Dk, Dv, S_kv, self.n_sel, dt)
-        ws = workspace(dev, nb, "extend_attn")
-        _lib.check(L.nsa_sel_attn_fwd(Q.data_ptr(), Ks.data_ptr(), Vs.data_ptr(), ranges.data_ptr(), O_sel.data_ptr(), None, B, S, G, h, Dk, Dv,
-                                      S_kv, self.n_sel, Ks.stride(0), Ks.stride(1), Ks.stride(2), Vs.stride(0), Vs.stride(1), Vs.stride(2), dt,
-                                      scale, 0, _ws_args(ws)[0], nb, st), "nsa_sel_attn_fwd")
-        nb = L.nsa_band_attn_fwd_workspace(B, S, G, h, Dk, Dv, dt)
-        ws = workspace(dev, nb, "extend_band")
-        wp = _ws_args(ws)[0]
-        _lib.check(L.nsa_band_attn_fwd(Q.data_ptr(), Kw.data_ptr(), Vw.data_ptr(), O_win.data_ptr(), None, B, S, G, h, Dk, Dv, S_kv,
-                                       Kw.stride(0), Kw.stride(1), Kw.stride(2), Vw.stride(0), Vw.stride(1), Vw.stride(2), t0, 0, 1, 0, self.w,
-                                       dt, scale, 0, wp, nb, st), "nsa_band_attn_fwd")
-        Kc, Vc = kv._K_cmp, kv._V_cmp
-        _lib.check(L.nsa_band_attn_fwd(Q.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), O_cmp.data_ptr(), None, B, S, G, h, Dk, Dv, n1,
-                                       Kc.stride(0), Kc.stride(1), Kc.stride(2), Vc.stride(0), Vc.stride(1), Vc.stride(2), t0, self.l, self.d,
-                                       1, 1 << 30, dt, scale, 0, wp, nb, st), "nsa_band_attn_fwd")
-        O = torch.empty((B, S, self.n_heads * Dv), dtype=x.dtype, device=dev)
+        O_sel = selection_attention_hip(Q, kv._K_sel[:, :, :S_kv], kv._V_sel[:, :, :S_kv], ranges, scale=scale)
+        O_win = sliding_window_attention(Q, kv._K_win[:, :, :S_kv], kv._V_win[:, :, :S_kv], self.w, t0=t0, scale=scale)
+        O_cmp = batched_causal_attention_compressed(Q, kv._K_cmp[:, :, :n1], kv._V_cmp[:, :, :n1], self.l, self.d, t0=t0, scale=scale)
+        O = torch.empty((B, S, self.n_heads * self.d_v), dtype=x.dtype, device=dev)
         gates = torch.empty((B, S, G, 3), dtype=torch.float32, device=dev)
         _lib.check(L.nsa_gate_combine(dref, Q.data_ptr(), O_cmp.data_ptr(), O_sel.data_ptr(), O_win.data_ptr(), O.data_ptr(),
                                       gates.data_ptr(), B * S * G, st), "nsa_gate_combine")
-        self._extend_end(kv, t0, S)
+        kv.end_rows(t0, S)
         return O, ranges, gates
 
     def _prefill(self, x: torch.Tensor, kv: NSA_KV, one_call: bool = True):
@@ -645,32 +614,18 @@ class NSAAttention(nn.Module):
         """inference prefill: fused projection GEMM -> ONE native call for everything up to the output projection
         (nsa_layer_prefill: RoPE + cache append, pooling, scores, top-n + selection attention, sliding / compressed branches,
         gates + combine) -> output GEMM"""
-        from .selection_scorer import batched_ranges_width
-
         B, S, _ = x.shape
         kv.ensure_capacity(S)
-        L, dev = _lib.lib(), x.device
+        G = self.n_kv_groups
         desc, W_qkv = self._layer_desc()
-        kd = self._kv_desc(kv)
         meta = kv.ensure_meta(S)
         proj = F.linear(x, W_qkv)
-        G = self.n_kv_groups
-        if self.selector == "batched":
-            mode, W = _lib.NSA_SEL_BATCHED, batched_ranges_width(meta.S_sel, self.l_sel, self.n_sel, S, True, 2)
-        else:
-            mode, W = _lib.NSA_SEL_SEQUENTIAL, self.n_sel
-        ranges = torch.empty((B, S, G, W, 2), dtype=torch.int32, device=dev)
-        gates = torch.empty((B, S, G, 3), dtype=torch.float32, device=dev)
-        O = torch.empty((B, S, self.n_heads * self.d_v), dtype=x.dtype, device=dev)
-        wptr, wsize, _ = workspace_at(dev, L.nsa_layer_prefill_workspace(ctypes.byref(desc), B, S, int(meta.S_sel)), "layer_prefill", 256)
-        cptr, crows, cvals = meta.device_csc(dev)
-        rc = L.nsa_layer_prefill(ctypes.byref(desc), ctypes.byref(kd), proj.data_ptr(), S, mode, cptr.data_ptr(), crows.data_ptr(),
-                                 cvals.data_ptr(), int(meta.S_sel), ranges.data_ptr(), W, O.data_ptr(), gates.data_ptr(), wptr, wsize, _stream(dev))
-        _lib.check(rc, "nsa_layer_prefill")
-        kv.t = S
-        kv.n_cmp = _n_cmp(S, self.l, self.d)
-        _set_plain(self, "_last_ranges", ranges)
-        _set_plain(self, "_last_gates", gates)
+        mode, W = _sel_mode(self.selector, meta.S_sel, self.l_sel, self.n_sel, S)
+        O = torch.empty((B, S, self.n_heads * self.d_v), dtype=x.dtype, device=x.device)
+        ranges, gates = _one_call("nsa_layer_prefill", "layer_prefill", desc, kv, meta, x.device,
+                                  (B, S, int(meta.S_sel)), (proj.data_ptr(), S, mode), (W, O.data_ptr()), (B, S, G, W, 2), (B, S, G, 3))
+        kv.t, kv.n_cmp = S, kv.n_cmp_at(S)
+        self._monitors(ranges, gates)
         return O if mix_only else self.out(O), kv
 
     def _prefill_train_native(self, x: torch.Tensor, kv: NSA_KV):
@@ -697,36 +652,17 @@ class NSAAttention(nn.Module):
 
     def _decode_native(self, x: torch.Tensor, kv: NSA_KV):
         """the whole decode step in one native call (nsa_layer_decode_step): ~15 kernel launches, no host sync"""
-        t, B, dev = kv.t, x.shape[0], x.device
-        kv.ensure_capacity(t + 1)
-        if kv.meta.S_sel == 0:  # _refresh_meta and _n_cmp, inline: a call each is measurable in this step's host time
-            kv.ensure_meta(max(t + 1, self.l_sel))
-        elif t + 1 > kv.meta.S_sel * self.l_sel:
-            kv.ensure_meta(t + 1)
-        S_raw = t + 1
-        num_cmp = 0 if S_raw < self.l else (S_raw - self.l) // self.d + 1
-        L = _lib.lib()
+        t, meta = kv.begin_rows(1)
+        B, dev, G = x.shape[0], x.device, self.n_kv_groups
         desc, _ = self._layer_desc()
-        ctx = getattr(kv, "_dec_ctx", None)  # per-cache constants of the native call (descriptors, workspace, monitors)
-        if ctx is None or ctx[0] is not desc:
-            kd = self._kv_desc(kv)
-            wptr, wsize, ws = workspace_at(dev, L.nsa_layer_decode_step_workspace(ctypes.byref(desc), B, kd.S_max), "layer_decode", 256)
-            ranges = torch.empty((B, self.n_kv_groups, self.n_sel, 2), dtype=torch.int32, device=dev)
-            gates = torch.empty((B, 1, self.n_kv_groups, 3), dtype=torch.float32, device=dev)
-            ctx = kv._dec_ctx = (desc, ctypes.byref(desc), ctypes.byref(kd), kd, ws, wptr, wsize, ranges, gates)
-        _, desc_ref, kd_ref, _, _, wptr, wsize, ranges, gates = ctx
-        cptr, crows, cvals = kv.meta.device_csc(dev)
         xc = x.reshape(B, self.dim)
         if not xc.is_contiguous():
             xc = xc.contiguous()
         y = torch.empty((B, 1, self.dim), dtype=x.dtype, device=dev)
-        rc = L.nsa_layer_decode_step(desc_ref, kd_ref, xc.data_ptr(), y.data_ptr(), t, cptr.data_ptr(), crows.data_ptr(), cvals.data_ptr(),
-                                     int(kv.meta.S_sel), ranges.data_ptr(), gates.data_ptr(), wptr, wsize, _stream(dev))
-        _lib.check(rc, "nsa_layer_decode_step")
-        kv.t, kv.n_cmp = S_raw, num_cmp
-        kv.append_reads(num_cmp, S_raw)
-        _set_plain(self, "_last_ranges", ranges)
-        _set_plain(self, "_last_gates", gates)
+        ranges, gates = _one_call("nsa_layer_decode_step", "layer_decode", desc, kv, meta, dev,
+                                  (B, kv._K_sel.shape[2]), (xc.data_ptr(), y.data_ptr(), t), (), (B, G, self.n_sel, 2), (B, 1, G, 3), keep=True)
+        kv.end_rows(t, 1)
+        self._monitors(ranges, gates)
         return y, kv
 
     # ---- decode step for S consecutive tokens (k draft tokens to verify, the tail of a chunked prefill) ------------------------------
@@ -734,11 +670,8 @@ class NSAAttention(nn.Module):
         """what nsa_layer_decode_rows does with a shape under the current tuning switches (nsa_layer_decode_rows_plan, no device call):
         {"launches", "route": 1 the selected branch in its one-launch rows form / 0 its separate launches / -1 declined (S single steps)}"""
         desc, _ = self._layer_desc()
-        n, r = ctypes.c_int(0), ctypes.c_int(0)
-        rc = _lib.lib().nsa_layer_decode_rows_plan(ctypes.byref(desc), int(B), int(S), int(S_max), int(t0), int(S_sel), ctypes.byref(n),
-                                                   ctypes.byref(r))
-        _lib.check(rc, "nsa_layer_decode_rows_plan")
-        return {"launches": n.value, "route": r.value}
+        n, r = _plan_ints("nsa_layer_decode_rows_plan", 2, ctypes.byref(desc), int(B), int(S), int(S_max), int(t0), int(S_sel))
+        return {"launches": n, "route": r}
 
     def decode_rows(self, x: torch.Tensor, kv: NSA_KV):
         """x [B,S,dim], 1 <= S <= 16: the S tokens of positions kv.t .. kv.t + S - 1 in ONE native call (nsa_layer_decode_rows) -> (y [B,S,dim],
@@ -750,21 +683,21 @@ class NSAAttention(nn.Module):
         if not 1 <= S <= 16:
             raise ValueError(f"NSAAttention.decode_rows takes 1 to 16 tokens per sequence, got S={S}")
         self._check_kv(x, kv)
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+        if self._grad_needed(x):
             raise RuntimeError("NSAAttention.decode_rows is inference only (no backward); run it under torch.no_grad()")
         if not x.is_contiguous():
             x = x.contiguous()
         if not self._native_ok(x):
             return self._decode_rows_steps(x, kv)
-        t0, meta = self._extend_begin(kv, S)
-        if self.decode_rows_plan(B, S, self._kv_desc(kv).S_max, t0, int(meta.S_sel))["route"] < 0:
+        t0, meta = kv.begin_rows(S)
+        if self.decode_rows_plan(B, S, kv._K_sel.shape[2], t0, int(meta.S_sel))["route"] < 0:
             return self._decode_rows_steps(x, kv)
-        saved = (kv.t, kv.n_cmp, len(kv.reads_pred))
+        saved = kv.snapshot()
         try:
             return self._decode_rows_native(x, kv)
         except RuntimeError as e:
             def steps():  # the next executor: the S single steps from the saved state
-                _restore(kv, saved)
+                kv.restore(saved)
                 return self._decode_rows_steps(x, kv)
             return self._route_failure(e, False, f"nsa_vibe_amd: the one-call decode step for {S} tokens failed ({e}); falling back to {S} "
                                        "single steps", steps)
@@ -777,27 +710,19 @@ class NSAAttention(nn.Module):
             ys.append(y)
             rs.append(self._last_ranges.unsqueeze(1).clone())  # (the native step writes every step's ranges and gates into the same tensors)
             gs.append(self._last_gates.reshape(x.shape[0], 1, self.n_kv_groups, 3).clone())
-        _set_plain(self, "_last_ranges", torch.cat(rs, dim=1))
-        _set_plain(self, "_last_gates", torch.cat(gs, dim=1))
+        self._monitors(torch.cat(rs, dim=1), torch.cat(gs, dim=1))
         return torch.cat(ys, dim=1), kv
 
     def _decode_rows_native(self, x: torch.Tensor, kv: NSA_KV):
         B, S, _ = x.shape
-        t0, meta = self._extend_begin(kv, S)
-        L, dev = _lib.lib(), x.device
+        t0, meta = kv.begin_rows(S)
+        G = self.n_kv_groups
         desc, _ = self._layer_desc()
-        kd = self._kv_desc(kv)
-        ranges = torch.empty((B, S, self.n_kv_groups, self.n_sel, 2), dtype=torch.int32, device=dev)
-        gates = torch.empty((B, S, self.n_kv_groups, 3), dtype=torch.float32, device=dev)
-        y = torch.empty((B, S, self.dim), dtype=x.dtype, device=dev)
-        wptr, wsize, _ = workspace_at(dev, L.nsa_layer_decode_rows_workspace(ctypes.byref(desc), B, S, kd.S_max), "layer_decode_rows", 256)
-        cptr, crows, cvals = meta.device_csc(dev)
-        rc = L.nsa_layer_decode_rows(ctypes.byref(desc), ctypes.byref(kd), x.data_ptr(), y.data_ptr(), t0, S, cptr.data_ptr(), crows.data_ptr(),
-                                     cvals.data_ptr(), int(meta.S_sel), ranges.data_ptr(), gates.data_ptr(), wptr, wsize, _stream(dev))
-        _lib.check(rc, "nsa_layer_decode_rows")
-        self._extend_end(kv, t0, S)
-        _set_plain(self, "_last_ranges", ranges)
-        _set_plain(self, "_last_gates", gates)
+        y = torch.empty((B, S, self.dim), dtype=x.dtype, device=x.device)
+        ranges, gates = _one_call("nsa_layer_decode_rows", "layer_decode_rows", desc, kv, meta, x.device,
+                                  (B, S, kv._K_sel.shape[2]), (x.data_ptr(), y.data_ptr(), t0, S), (), (B, S, G, self.n_sel, 2), (B, S, G, 3))
+        kv.end_rows(t0, S)
+        self._monitors(ranges, gates)
         return y, kv
 
     def _decode(self, x: torch.Tensor, kv: NSA_KV, one_call: bool = True):
@@ -813,9 +738,8 @@ class NSAAttention(nn.Module):
             K_new = apply_rope(kv._K_raw[:, :, S_raw - self.l: S_raw], p_last).mean(dim=2, keepdim=True)
             V_new = kv._V_raw[:, :, S_raw - self.l: S_raw].mean(dim=2, keepdim=True)
             kv.write_compressed(K_new.to(kv._K_cmp.dtype), V_new.to(kv._V_cmp.dtype))
-        self._refresh_meta(kv, t + 1)
-        num_cmp = _n_cmp(S_raw, self.l, self.d)
-        kv.append_reads(num_cmp, S_raw)
+        kv.refresh_meta(t + 1)
+        kv.append_reads(kv.n_cmp_at(S_raw), S_raw)
         scale = 1.0 / math.sqrt(self.d_k)
         Qc = Q.contiguous()
         O_sel, ranges = selection_decode_step(Qc, kv.K_cmp, kv.K_sel, kv.V_sel, kv.meta, self.n_sel, t, scale=scale)

@@ -20,11 +20,9 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .selection_scorer import _DT, _need_gpu, _scale_arg, _stream, _ws_args, workspace
-
-
-def _prep_kv(X: torch.Tensor) -> torch.Tensor:
-    return X if X.stride(-1) == 1 else X.contiguous()
+from .block_index import build_block_meta
+from .kv_cache import n_cmp_at
+from ._native import _DT, _need_gpu, _needs_grad, _plan_ints, _scale_arg, _sel_mode, _stream, _unit_rows, _ws_args, workspace
 
 
 def _prep_ranges(ranges: torch.Tensor) -> torch.Tensor:
@@ -55,7 +53,7 @@ def _fwd(Q, K, V, ranges, scale, variant, want_lse):
     n = ranges.shape[3]
     if K.shape[:2] != (B, G) or V.shape[:3] != (B, G, S_kv) or K.shape[3] != Dk or ranges.shape[:3] != (B, S, G):
         raise RuntimeError("selection_attention_hip: inconsistent shapes")
-    Qc, Kc, Vc, rg = Q.contiguous(), _prep_kv(K), _prep_kv(V), _prep_ranges(ranges)
+    Qc, (Kc, *ks), (Vc, *vs), rg = Q.contiguous(), _unit_rows(K), _unit_rows(V), _prep_ranges(ranges)
     O = torch.empty((B, S, G, h, Dv), dtype=V.dtype, device=dev)
     lse = torch.empty((B, S, G, h), dtype=torch.float32, device=dev) if want_lse else None
     if O.numel() == 0:
@@ -64,10 +62,8 @@ def _fwd(Q, K, V, ranges, scale, variant, want_lse):
     dt = _DT[Q.dtype]
     ws = workspace(dev, L.nsa_sel_attn_fwd_workspace_kv(B, S, G, h, Dk, Dv, S_kv, n, dt), "attn")
     rc = L.nsa_sel_attn_fwd(Qc.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), rg.data_ptr(), O.data_ptr(),
-                            lse.data_ptr() if lse is not None else None, B, S, G, h, Dk, Dv, S_kv, n,
-                            Kc.stride(0), Kc.stride(1), Kc.stride(2), Vc.stride(0), Vc.stride(1), Vc.stride(2),
-                            dt, _scale_arg(scale), int(variant),
-                            *_ws_args(ws), _stream(dev))
+                            lse.data_ptr() if lse is not None else None, B, S, G, h, Dk, Dv, S_kv, n, *ks, *vs,
+                            dt, _scale_arg(scale), int(variant), *_ws_args(ws), _stream(dev))
     _lib.check(rc, "nsa_sel_attn_fwd")
     return O, lse, (Qc, Kc, Vc, rg)
 
@@ -98,8 +94,7 @@ class _SelAttnFn(torch.autograd.Function):
         ws = workspace(dev, L.nsa_sel_attn_bwd_workspace(B, S, G, h, Dk, Dv, S_kv, _DT[Qc.dtype], ctx.bwd_variant), "attn_bwd")
         rc = L.nsa_sel_attn_bwd(Qc.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), rg.data_ptr(), O.data_ptr(),
                                 lse.data_ptr(), dO.data_ptr(), dQ.data_ptr(), dK.data_ptr(), dV.data_ptr(),
-                                B, S, G, h, Dk, Dv, S_kv, rg.shape[3],
-                                Kc.stride(0), Kc.stride(1), Kc.stride(2), Vc.stride(0), Vc.stride(1), Vc.stride(2),
+                                B, S, G, h, Dk, Dv, S_kv, rg.shape[3], *_unit_rows(Kc)[1:], *_unit_rows(Vc)[1:],
                                 _DT[Qc.dtype], _scale_arg(ctx.scale), int(ctx.bwd_variant),
                                 *_ws_args(ws), _stream(dev))
         _lib.check(rc, "nsa_sel_attn_bwd")
@@ -124,7 +119,7 @@ def selection_attention_hip(Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, r
     variant: 0 auto (MFMA kernel when dtype/shape allow, else the generic kernel), 1 generic, 2 MFMA.
     bwd_variant: the same choice for the backward; None = 0 (auto) unless variant is 1.  2 raises where the MFMA backward does not
     cover the shape (bf16/f16, Dk = Dv = 64 or 128, h <= 16, 16-byte aligned K/V strides)."""
-    if torch.is_grad_enabled() and (Q.requires_grad or K.requires_grad or V.requires_grad):
+    if _needs_grad(Q, K, V):
         if return_lse:
             raise RuntimeError("return_lse is not available on the autograd path")
         return _SelAttnFn.apply(Q, K, V, ranges, scale, variant, bwd_variant)
@@ -138,14 +133,14 @@ def selection_attention_first_key_parity(Q: torch.Tensor, K: torch.Tensor, V: to
     the first gathered key is visible and O[b,t,g,h,:] = V[b,g,start of the first non-empty range] for every head (zeros when the row
     has none).  Same executor signature as selection_attention_hip; Q and K do not influence the result.  Inference only."""
     dev = _need_gpu(Q, K, V)
-    if torch.is_grad_enabled() and V.requires_grad:
+    if _needs_grad(V):
         raise RuntimeError("selection_attention_first_key_parity is an inference-only parity mode")
     B, S, G, h, _ = Q.shape
     S_kv, Dv = V.shape[2], V.shape[3]
-    Vv, rg = _prep_kv(V), _prep_ranges(ranges)
+    (Vv, *vs), rg = _unit_rows(V), _prep_ranges(ranges)
     O = torch.empty((B, S, G, h, Dv), dtype=V.dtype, device=dev)
-    rc = _lib.lib().nsa_sel_attn_first_key_parity(Vv.data_ptr(), rg.data_ptr(), O.data_ptr(), B, S, G, h, Dv, S_kv, rg.shape[3],
-                                                  Vv.stride(0), Vv.stride(1), Vv.stride(2), _DT[V.dtype], _stream(dev))
+    rc = _lib.lib().nsa_sel_attn_first_key_parity(Vv.data_ptr(), rg.data_ptr(), O.data_ptr(), B, S, G, h, Dv, S_kv, rg.shape[3], *vs,
+                                                  _DT[V.dtype], _stream(dev))
     _lib.check(rc, "nsa_sel_attn_first_key_parity")
     return O
 
@@ -157,19 +152,18 @@ def selection_attention_head_causal_parity(Q: torch.Tensor, K: torch.Tensor, V: 
     group as the query LENGTH with is_causal=True, so head i attends the first i+1 tokens of the gathered union (ascending token
     order); rows without a token give zeros.  Executor signature ([B,S,G,...] tensors); inference only."""
     dev = _need_gpu(Q, K, V)
-    if torch.is_grad_enabled() and (Q.requires_grad or K.requires_grad or V.requires_grad):
+    if _needs_grad(Q, K, V):
         raise RuntimeError("selection_attention_head_causal_parity is an inference-only parity mode")
     if not (Q.dtype == K.dtype == V.dtype) or Q.dtype not in _DT:
         raise RuntimeError("selection_attention_head_causal_parity: Q/K/V must share a dtype in fp32/bf16/fp16")
     B, S, G, h, Dk = Q.shape
     S_kv, Dv = V.shape[2], V.shape[3]
-    Qc, Kk, Vv, rg = Q.contiguous(), _prep_kv(K), _prep_kv(V), _prep_ranges(ranges)
+    Qc, (Kk, *ks), (Vv, *vs), rg = Q.contiguous(), _unit_rows(K), _unit_rows(V), _prep_ranges(ranges)
     if rg.shape[:3] != (B, S, G) or Kk.shape[:3] != (B, G, S_kv):
         raise RuntimeError("selection_attention_head_causal_parity: inconsistent shapes")
     O = torch.empty((B, S, G, h, Dv), dtype=V.dtype, device=dev)
     rc = _lib.lib().nsa_sel_attn_head_causal_parity(Qc.data_ptr(), Kk.data_ptr(), Vv.data_ptr(), rg.data_ptr(), O.data_ptr(), B, S, G, h, Dk,
-                                                    Dv, S_kv, rg.shape[3], Kk.stride(0), Kk.stride(1), Kk.stride(2), Vv.stride(0),
-                                                    Vv.stride(1), Vv.stride(2), _DT[Q.dtype], _scale_arg(scale), _stream(dev))
+                                                    Dv, S_kv, rg.shape[3], *ks, *vs, _DT[Q.dtype], _scale_arg(scale), _stream(dev))
     _lib.check(rc, "nsa_sel_attn_head_causal_parity")
     return O
 
@@ -199,7 +193,7 @@ def _selection_decode(call, size, tag: str, rows: bool, Q, K_cmp, K, V, meta, n_
         raise RuntimeError("selection_decode_step: decode requires S == 1")
     if rows and S_kv < t0 + S:
         raise RuntimeError("selection_decode_rows: the cache must hold the S tokens t0 .. t0 + S - 1")
-    Qc, Kc, Kk, Vv = Q.contiguous(), _prep_kv(K_cmp), _prep_kv(K), _prep_kv(V)
+    Qc, (Kc, *cs), (Kk, *ks), (Vv, *vs) = Q.contiguous(), _unit_rows(K_cmp), _unit_rows(K), _unit_rows(V)
     O = out if out is not None else torch.empty((B, S, G, h, Dv), dtype=V.dtype, device=dev)
     rg = ranges_out if ranges_out is not None else torch.empty((B, S, G, n_top, 2) if rows else (B, G, n_top, 2), dtype=torch.int32, device=dev)
     if rows and O.numel() == 0:
@@ -210,8 +204,7 @@ def _selection_decode(call, size, tag: str, rows: bool, Q, K_cmp, K, V, meta, n_
     wptr = (ws.data_ptr() + 15) & ~15
     cptr, crows, cvals = meta.device_csc(dev)
     rc = call(Qc.data_ptr(), Kc.data_ptr(), Kk.data_ptr(), Vv.data_ptr(), cptr.data_ptr(), crows.data_ptr(), cvals.data_ptr(), rg.data_ptr(),
-              O.data_ptr(), B, *s, G, h, Dk, Dv, S_cmp, S_sel, S_kv, int(meta.l), int(meta.d), int(meta.l_sel), int(n_top), int(t0),
-              Kc.stride(0), Kc.stride(1), Kc.stride(2), Kk.stride(0), Kk.stride(1), Kk.stride(2), Vv.stride(0), Vv.stride(1), Vv.stride(2), dt,
+              O.data_ptr(), B, *s, G, h, Dk, Dv, S_cmp, S_sel, S_kv, int(meta.l), int(meta.d), int(meta.l_sel), int(n_top), int(t0), *cs, *ks, *vs, dt,
               float(scale) if scale else 0.0, wptr, ws.numel() - (wptr - ws.data_ptr()), _stream(dev))
     _lib.check(rc, call.__name__)
     return O, rg
@@ -223,13 +216,8 @@ def selection_decode_step_plan(B: int, G: int, h: int, Dk: int, Dv: int, S_cmp: 
     aligned contiguous-row inputs): {"launches": 1 exactly when the call is the one-launch step, otherwise an estimate > 1 of the separate route's launches, "form": 0 logits in registers /
     1 four chunks per wave / 2 one-pass / -1 step declined, "nsplit": workgroups per row (0 when declined)}.  Launches no kernel, but asks the HIP runtime for the current device's CU count (which initialises the runtime): the
     answer is for the device that is current when it is called."""
-    import ctypes
-
-    n, f, s = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
-    rc = _lib.lib().nsa_sel_decode_step_plan(int(B), int(G), int(h), int(Dk), int(Dv), int(S_cmp), int(S_sel), int(S_kv), int(n_top),
-                                             _DT[dtype], ctypes.byref(n), ctypes.byref(f), ctypes.byref(s))
-    _lib.check(rc, "nsa_sel_decode_step_plan")
-    return {"launches": n.value, "form": f.value, "nsplit": s.value}
+    ints = _plan_ints("nsa_sel_decode_step_plan", 3, int(B), int(G), int(h), int(Dk), int(Dv), int(S_cmp), int(S_sel), int(S_kv), int(n_top), _DT[dtype])
+    return dict(zip(("launches", "form", "nsplit"), ints))
 
 
 def selection_decode_rows(Q: torch.Tensor, K_cmp: torch.Tensor, K: torch.Tensor, V: torch.Tensor, meta, n_top: int, t0: int,
@@ -251,13 +239,9 @@ def selection_decode_rows_plan(B: int, S: int, G: int, h: int, Dk: int, Dv: int,
     """What selection_decode_rows does with a shape under the current tuning switches (nsa_sel_decode_rows_plan; default block geometry,
     aligned contiguous-row inputs, a cache of exactly S_kv = t0 + S tokens): {"launches": 1 exactly when the call is the one-launch rows
     form, otherwise an estimate > 1 of the separate launches, "form": 0 logits in registers / 1 four chunks per wave / -1 declined}."""
-    import ctypes
-
-    n, f = ctypes.c_int(0), ctypes.c_int(0)
-    rc = _lib.lib().nsa_sel_decode_rows_plan(int(B), int(S), int(G), int(h), int(Dk), int(Dv), int(S_cmp), int(S_sel), int(S_kv), int(n_top),
-                                             _DT[dtype], ctypes.byref(n), ctypes.byref(f))
-    _lib.check(rc, "nsa_sel_decode_rows_plan")
-    return {"launches": n.value, "form": f.value}
+    ints = _plan_ints("nsa_sel_decode_rows_plan", 2, int(B), int(S), int(G), int(h), int(Dk), int(Dv), int(S_cmp), int(S_sel), int(S_kv), int(n_top),
+                      _DT[dtype])
+    return dict(zip(("launches", "form"), ints))
 
 
 def _ragged_positions(who: str, t_pos, t_max, B: int, S: int):
@@ -306,13 +290,9 @@ def selection_decode_ragged_plan(B: int, S: int, G: int, h: int, Dk: int, Dv: in
     """What selection_decode_ragged does with a shape whose largest live row sits at t_max (nsa_sel_decode_ragged_plan; default block
     geometry, aligned inputs): {"launches": 1, "form": 0 logits in registers / 1 four chunks per wave}, or {"launches": 0, "form": -1}
     where the call declines -- there is no other native route with per-sequence positions."""
-    import ctypes
-
-    n, f = ctypes.c_int(0), ctypes.c_int(0)
-    rc = _lib.lib().nsa_sel_decode_ragged_plan(int(B), int(S), int(G), int(h), int(Dk), int(Dv), int(S_cmp), int(S_sel), int(S_kv), int(n_top),
-                                               _DT[dtype], int(t_max), ctypes.byref(n), ctypes.byref(f))
-    _lib.check(rc, "nsa_sel_decode_ragged_plan")
-    return {"launches": n.value, "form": f.value}
+    ints = _plan_ints("nsa_sel_decode_ragged_plan", 2, int(B), int(S), int(G), int(h), int(Dk), int(Dv), int(S_cmp), int(S_sel), int(S_kv), int(n_top),
+                      _DT[dtype], int(t_max))
+    return dict(zip(("launches", "form"), ints))
 
 
 def selection_decode_ragged(Q: torch.Tensor, K_cmp: torch.Tensor, K: torch.Tensor, V: torch.Tensor, meta, n_top: int, t_pos, *,
@@ -348,29 +328,25 @@ def selection_decode_ragged(Q: torch.Tensor, K_cmp: torch.Tensor, K: torch.Tenso
     dt = _DT[Q.dtype]
     if host is not None and selection_decode_ragged_plan(B, S, G, h, Dk, Dv, S_cmp, S_sel, S_kv, n_top, t_max, Q.dtype)["launches"] == 0:
         # declined (a t_max beyond the unsplit forms, fp32, ...): the positions are known here, so each active sequence takes the rows call
-        from .block_index import build_block_meta
-
         O.zero_()
         rg.zero_()
         for b, t0 in enumerate(host):
             if t0 < 0 or t0 + S - 1 > min(t_max, S_kv - 1):
                 continue
             n_tok = t0 + S
-            n_c = 0 if n_tok < meta.l else (n_tok - meta.l) // meta.d + 1
+            n_c = n_cmp_at(n_tok, meta.l, meta.d)
             selection_decode_rows(Q[b:b + 1], K_cmp[b:b + 1, :, :min(n_c, S_cmp)], K[b:b + 1, :, :n_tok], V[b:b + 1, :, :n_tok],
                                   build_block_meta(n_tok, meta.l, meta.d, meta.l_sel, meta.n_sel, meta.w), n_top, t0, scale=scale,
                                   out=O[b:b + 1], ranges_out=rg[b:b + 1])
         return O, rg
     L = _lib.lib()
-    Qc, Kc, Kk, Vv = Q.contiguous(), _prep_kv(K_cmp), _prep_kv(K), _prep_kv(V)
+    Qc, (Kc, *cs), (Kk, *ks), (Vv, *vs) = Q.contiguous(), _unit_rows(K_cmp), _unit_rows(K), _unit_rows(V)
     pos = _positions_to(dev, t_pos, host)
     cptr, crows, cvals = meta.device_csc(dev)
     ws = workspace(dev, L.nsa_sel_decode_ragged_workspace(B, S, G, h, Dk, Dv, S_cmp, S_sel, n_top, dt), "decode_ragged")
     rc = L.nsa_sel_decode_ragged(Qc.data_ptr(), Kc.data_ptr() if S_cmp else None, Kk.data_ptr(), Vv.data_ptr(), cptr.data_ptr(), crows.data_ptr(),
                                  cvals.data_ptr(), rg.data_ptr(), O.data_ptr(), pos.data_ptr(), t_max, B, S, G, h, Dk, Dv, S_cmp, S_sel, S_kv,
-                                 int(meta.l), int(meta.d), int(meta.l_sel), int(n_top), Kc.stride(0), Kc.stride(1), Kc.stride(2), Kk.stride(0),
-                                 Kk.stride(1), Kk.stride(2), Vv.stride(0), Vv.stride(1), Vv.stride(2), dt, _scale_arg(scale), *_ws_args(ws),
-                                 _stream(dev))
+                                 int(meta.l), int(meta.d), int(meta.l_sel), int(n_top), *cs, *ks, *vs, dt, _scale_arg(scale), *_ws_args(ws), _stream(dev))
     _lib.check(rc, "nsa_sel_decode_ragged")
     return O, rg
 
@@ -384,22 +360,15 @@ def select_and_attend(p_grp: torch.Tensor, Q: torch.Tensor, K: torch.Tensor, V: 
     mode "batched" = select_topn_ranges_batched semantics (selection_scorer.py:255-362), "sequential" = select_topn_ranges per
     row at token t0 + s (:124-249).  Returns (ranges [B,S,G,W,2] int32, O [B,S,G,h,Dv]) -- bit-identical to
     select_topn_ranges_batched / select_topn_ranges_rows followed by selection_attention_hip."""
-    from .selection_scorer import batched_ranges_width
-
     dev = _need_gpu(p_grp, Q, K, V)
-    if torch.is_grad_enabled() and (Q.requires_grad or K.requires_grad or V.requires_grad):
+    if _needs_grad(Q, K, V):
         raise RuntimeError("select_and_attend is the inference form; with autograd use select_topn_ranges_* + selection_attention_hip")
     B, S, G, h, Dk = Q.shape
     S_kv, Dv, S_sel = K.shape[2], V.shape[3], p_grp.shape[-1]
     if p_grp.shape[:3] != (B, S, G) or p_grp.dtype != torch.float32:
         raise RuntimeError("select_and_attend: p_grp must be fp32 [B,S,G,S_sel]")
-    if mode == "batched":
-        md, W = _lib.NSA_SEL_BATCHED, batched_ranges_width(S_sel, meta.l_sel, n_top, S, force_init, force_local)
-    elif mode == "sequential":
-        md, W = _lib.NSA_SEL_SEQUENTIAL, n_top
-    else:
-        raise ValueError("mode must be 'batched' or 'sequential'")
-    Qc, Kc, Vc, pg = Q.contiguous(), _prep_kv(K), _prep_kv(V), p_grp.contiguous()
+    md, W = _sel_mode(mode, S_sel, meta.l_sel, n_top, S, force_init, force_local)
+    Qc, (Kc, *ks), (Vc, *vs), pg = Q.contiguous(), _unit_rows(K), _unit_rows(V), p_grp.contiguous()
     ranges = torch.empty((B, S, G, W, 2), dtype=torch.int32, device=dev)
     O = torch.empty((B, S, G, h, Dv), dtype=V.dtype, device=dev)
     lse = torch.empty((B, S, G, h), dtype=torch.float32, device=dev) if return_lse else None
@@ -411,8 +380,7 @@ def select_and_attend(p_grp: torch.Tensor, Q: torch.Tensor, K: torch.Tensor, V: 
     ws = workspace(dev, L.nsa_sel_attn_fwd_workspace_kv(B, S, G, h, Dk, Dv, S_kv, W, dt), "attn")
     rc = L.nsa_sel_select_attn_fwd(pg.data_ptr(), int(t0), None, S_sel, int(meta.l_sel), int(n_top), int(bool(force_init)), int(force_local),
                                    md, S, ranges.data_ptr(), W, Qc.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), O.data_ptr(),
-                                   lse.data_ptr() if lse is not None else None, B, S, G, h, Dk, Dv, S_kv,
-                                   Kc.stride(0), Kc.stride(1), Kc.stride(2), Vc.stride(0), Vc.stride(1), Vc.stride(2),
+                                   lse.data_ptr() if lse is not None else None, B, S, G, h, Dk, Dv, S_kv, *ks, *vs,
                                    dt, _scale_arg(scale), *_ws_args(ws), _stream(dev))
     _lib.check(rc, "nsa_sel_select_attn_fwd")
     return (ranges, O, lse) if return_lse else (ranges, O)

@@ -6,76 +6,13 @@ the C ABI (include/nsa_sel_hip.h).  Tensors must live on a HIP device -- there i
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Optional
 
 import torch
 
 from . import _lib
+from ._native import _DT, _need_gpu, _scale_arg, _sel_mode, _stream, _unit_rows, _ws_args, workspace, workspace_at  # noqa: F401  (re-exported: tests and tools import them from here)
 from .block_index import BlockMeta
-
-_DT = {torch.float32: _lib.NSA_DT_F32, torch.bfloat16: _lib.NSA_DT_BF16, torch.float16: _lib.NSA_DT_F16}
-_WS: Dict[tuple, torch.Tensor] = {}
-
-
-def _need_gpu(*ts: torch.Tensor) -> torch.device:
-    dev = ts[0].device
-    for t in ts:
-        if not t.is_cuda:
-            raise RuntimeError("nsa_vibe_amd kernels need HIP device tensors (no CPU fallback exists)")
-        if t.device != dev:
-            raise RuntimeError("all tensors must be on the same device")
-    return dev
-
-
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-
-def _stream(dev: torch.device) -> int:
-    """raw handle of torch's current stream on dev (a decode step makes this call once per layer: the Stream object of
-    torch.cuda.current_stream costs tens of microseconds of host time, the raw getter about one)"""
-    if _raw_stream is not None:
-        idx = dev.index if isinstance(dev, torch.device) else None
-        return _raw_stream(torch.cuda.current_device() if idx is None else idx)
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def workspace(dev: torch.device, nbytes: int, tag: str = "ws") -> Optional[torch.Tensor]:
-    """Grow-on-demand scratch per (device, stream) (the reference keeps process-global workspaces too,
-    nsa/core/attention_kernels.py:25-26,64-103; keyed by stream here so concurrent streams cannot race on it)."""
-    if nbytes <= 0:
-        return None
-    key = (tag, dev.index, _stream(dev))  # per stream: two streams never share scratch
-    buf = _WS.get(key)
-    # grown on demand; given back when a much smaller shape follows a big one (the key-split records of a 64k prefill are gigabytes)
-    if buf is None or buf.numel() < nbytes or buf.numel() > max(4 * nbytes, 256 << 20):
-        _WS.pop(key, None)
-        buf = None
-        buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=dev)
-        _WS[key] = buf
-    return buf
-
-
-def workspace_at(dev: torch.device, nbytes: int, tag: str, align: int):
-    """workspace() of nbytes from an `align`-byte boundary on -> (pointer, bytes behind it, the buffer)"""
-    ws = workspace(dev, nbytes + align, tag)
-    ptr = (ws.data_ptr() + align - 1) & ~(align - 1)
-    return ptr, ws.numel() - (ptr - ws.data_ptr()), ws
-
-
-def _ws_args(ws: Optional[torch.Tensor]):
-    """(pointer, bytes) of an optional workspace as the C ABI takes them"""
-    return (ws.data_ptr(), ws.numel()) if ws is not None else (None, 0)
-
-
-def _scale_arg(scale: Optional[float]) -> float:
-    """the C ABI's scale: 0 asks for 1/sqrt(Dk)"""
-    return float(scale) if scale else 0.0
-
-
-def _kc_strides(K_cmp: torch.Tensor):
-    if K_cmp.stride(-1) != 1:
-        K_cmp = K_cmp.contiguous()
-    return K_cmp, K_cmp.stride(0), K_cmp.stride(1), K_cmp.stride(2)
 
 
 def compute_pcmp_all(Q_all: torch.Tensor, K_cmp: torch.Tensor, scale: float, out_dtype=None) -> torch.Tensor:
@@ -86,7 +23,7 @@ def compute_pcmp_all(Q_all: torch.Tensor, K_cmp: torch.Tensor, scale: float, out
     B, S, G, h, Dk = Q_all.shape
     S_cmp = K_cmp.shape[2]
     Q_all = Q_all.contiguous()
-    K_cmp, sb, sg, ss = _kc_strides(K_cmp)
+    K_cmp, sb, sg, ss = _unit_rows(K_cmp)
     p = torch.empty((B, S, G, h, S_cmp), dtype=torch.float32, device=dev)
     if p.numel():
         rc = _lib.lib().nsa_pcmp_all(Q_all.data_ptr(), K_cmp.data_ptr(), p.data_ptr(), B, S, G, h, Dk, S_cmp, sb, sg, ss,
@@ -149,6 +86,16 @@ def _norm_code(normalize: str) -> int:
     return _NORM[normalize]
 
 
+def _scorer(name: str, q0: int, norm: int):
+    """the scorer entry point `name`, or its _rows twin once row 0 is not token 0 or the softmax is the causal one (at q0 = 0, norm = 0 the
+    twin runs the same kernels to the same bits) -> (its name, the entry point, its workspace query, the arguments the twin takes behind the common
+    ones: (q0, norm) in the call, (norm,) in the query)"""
+    L = _lib.lib()
+    if q0 == 0 and norm == 0:
+        return name, getattr(L, name), L.nsa_sel_scores_workspace, ()
+    return name + "_rows", getattr(L, name + "_rows"), L.nsa_sel_scores_rows_workspace, (int(q0), norm)
+
+
 def selection_scores(Q_all: torch.Tensor, K_cmp: torch.Tensor, meta: BlockMeta, scale: Optional[float] = None,
                      causal_skip: bool = False, variant: int = 0, leave_skipped: bool = False, q0: int = 0,
                      normalize: str = "all") -> torch.Tensor:
@@ -169,29 +116,20 @@ def selection_scores(Q_all: torch.Tensor, K_cmp: torch.Tensor, meta: BlockMeta, 
     B, S, G, h, Dk = Q_all.shape
     S_cmp, S_sel = K_cmp.shape[2], meta.S_sel
     Q_all = Q_all.contiguous()
-    K_cmp, sb, sg, ss = _kc_strides(K_cmp)
+    K_cmp, sb, sg, ss = _unit_rows(K_cmp)
     p_grp = torch.empty((B, S, G, S_sel), dtype=torch.float32, device=dev)
     if p_grp.numel() == 0:
         return p_grp
-    L = _lib.lib()
     if variant == 0 and B * S * G > 1024 and not (sb % 8 == 0 and sg % 8 == 0 and ss % 8 == 0 and K_cmp.data_ptr() % 16 == 0):
         variant = 1  # rows not 16-byte aligned: the MFMA route would refuse them
-    if q0 == 0 and norm == 0:  # the original entry point (same kernels and bits as nsa_sel_scores_rows with q0 = 0, norm = 0)
-        nbytes = L.nsa_sel_scores_workspace(B, S, G, h, Dk, S_cmp, S_sel, int(meta.l), int(meta.d), int(meta.l_sel), _DT[Q_all.dtype],
-                                            int(variant))
-    else:
-        nbytes = L.nsa_sel_scores_rows_workspace(B, S, G, h, Dk, S_cmp, S_sel, int(meta.l), int(meta.d), int(meta.l_sel),
-                                                 _DT[Q_all.dtype], int(variant), norm)
-    ws = workspace(dev, nbytes, "scores")
+    name, call, size, rows = _scorer("nsa_sel_scores", q0, norm)
+    geo, dt = (int(meta.l), int(meta.d), int(meta.l_sel)), _DT[Q_all.dtype]
+    ws = workspace(dev, size(B, S, G, h, Dk, S_cmp, S_sel, *geo, dt, int(variant), *rows[1:]), "scores")
     cptr, crows, cvals = meta.device_csc(dev)
-    args = (Q_all.data_ptr(), K_cmp.data_ptr(), p_grp.data_ptr(), B, S, G, h, Dk, S_cmp, sb, sg, ss, cptr.data_ptr(), crows.data_ptr(),
-            cvals.data_ptr(), S_sel, int(meta.l), int(meta.d), int(meta.l_sel), (2 if leave_skipped else 1) if causal_skip else 0, int(variant),
-            _DT[Q_all.dtype], _scale_arg(scale))
-    tail = (*_ws_args(ws), _stream(dev))
-    if q0 == 0 and norm == 0:
-        _lib.check(L.nsa_sel_scores(*args, *tail), "nsa_sel_scores")
-    else:
-        _lib.check(L.nsa_sel_scores_rows(*args, int(q0), norm, *tail), "nsa_sel_scores_rows")
+    rc = call(Q_all.data_ptr(), K_cmp.data_ptr(), p_grp.data_ptr(), B, S, G, h, Dk, S_cmp, sb, sg, ss, cptr.data_ptr(), crows.data_ptr(),
+              cvals.data_ptr(), S_sel, *geo, (2 if leave_skipped else 1) if causal_skip else 0, int(variant), dt, _scale_arg(scale), *rows,
+              *_ws_args(ws), _stream(dev))
+    _lib.check(rc, name)
     return p_grp
 
 
@@ -210,36 +148,21 @@ def selection_scores_select(Q_all: torch.Tensor, K_cmp: torch.Tensor, meta: Bloc
     dev = _need_gpu(Q_all, K_cmp)
     B, S, G, h, Dk = Q_all.shape
     S_cmp, S_sel = K_cmp.shape[2], meta.S_sel
-    if mode == "batched":
-        md, W = _lib.NSA_SEL_BATCHED, batched_ranges_width(S_sel, meta.l_sel, n_top, S, force_init, force_local)
-    elif mode == "sequential":
-        md, W = _lib.NSA_SEL_SEQUENTIAL, n_top
-    else:
-        raise ValueError("mode must be 'batched' or 'sequential'")
+    md, W = _sel_mode(mode, S_sel, meta.l_sel, n_top, S, force_init, force_local)
     Q_all = Q_all.contiguous()
-    K_cmp, sb, sg, ss = _kc_strides(K_cmp)
+    K_cmp, sb, sg, ss = _unit_rows(K_cmp)
     p_grp = torch.empty((B, S, G, S_sel), dtype=torch.float32, device=dev)
     ranges = torch.empty((B, S, G, W, 2), dtype=torch.int32, device=dev)
     if p_grp.numel() == 0 or W == 0:
         return p_grp, ranges
-    L = _lib.lib()
-    dt = _DT[Q_all.dtype]
-    geo = (int(meta.l), int(meta.d), int(meta.l_sel))
-    if q0 == 0 and norm == 0:
-        nbytes = max(L.nsa_sel_scores_workspace(B, S, G, h, Dk, S_cmp, S_sel, *geo, dt, 0), L.nsa_sel_scores_workspace(B, S, G, h, Dk, S_cmp, S_sel, *geo, dt, 1))
-    else:
-        nbytes = max(L.nsa_sel_scores_rows_workspace(B, S, G, h, Dk, S_cmp, S_sel, *geo, dt, 0, norm),
-                     L.nsa_sel_scores_rows_workspace(B, S, G, h, Dk, S_cmp, S_sel, *geo, dt, 1, norm))
-    ws = workspace(dev, nbytes, "scores")
+    name, call, size, rows = _scorer("nsa_sel_scores_select", q0, norm)
+    geo, dt = (int(meta.l), int(meta.d), int(meta.l_sel)), _DT[Q_all.dtype]
+    ws = workspace(dev, max(size(B, S, G, h, Dk, S_cmp, S_sel, *geo, dt, variant, *rows[1:]) for variant in (0, 1)), "scores")
     cptr, crows, cvals = meta.device_csc(dev)
-    args = (Q_all.data_ptr(), K_cmp.data_ptr(), p_grp.data_ptr(), B, S, G, h, Dk, S_cmp, sb, sg, ss, cptr.data_ptr(), crows.data_ptr(),
-            cvals.data_ptr(), S_sel, *geo, 2 if leave_skipped else 1, dt, _scale_arg(scale), int(t0), int(n_top),
-            int(bool(force_init)), int(force_local), md, S, ranges.data_ptr(), W)
-    tail = (*_ws_args(ws), _stream(dev))
-    if q0 == 0 and norm == 0:
-        _lib.check(L.nsa_sel_scores_select(*args, *tail), "nsa_sel_scores_select")
-    else:
-        _lib.check(L.nsa_sel_scores_select_rows(*args, q0, norm, *tail), "nsa_sel_scores_select_rows")
+    rc = call(Q_all.data_ptr(), K_cmp.data_ptr(), p_grp.data_ptr(), B, S, G, h, Dk, S_cmp, sb, sg, ss, cptr.data_ptr(), crows.data_ptr(),
+              cvals.data_ptr(), S_sel, *geo, 2 if leave_skipped else 1, dt, _scale_arg(scale), int(t0), int(n_top), int(bool(force_init)),
+              int(force_local), md, S, ranges.data_ptr(), W, *rows, *_ws_args(ws), _stream(dev))
+    _lib.check(rc, name)
     return p_grp, ranges
 
 
@@ -283,7 +206,7 @@ def select_topn_ranges_rows(p_grp_all: torch.Tensor, meta: BlockMeta, n_top: int
 
 def batched_ranges_width(meta_or_S_sel, l_sel: int, n_top: int, S: int, force_init: bool = True, force_local: int = 2) -> int:
     S_sel = meta_or_S_sel.S_sel if isinstance(meta_or_S_sel, BlockMeta) else int(meta_or_S_sel)
-    return int(_lib.lib().nsa_batched_ranges_width(int(S), S_sel, int(l_sel), int(n_top), int(bool(force_init)), int(force_local)))
+    return _sel_mode("batched", S_sel, l_sel, n_top, S, force_init, force_local)[1]
 
 
 def select_topn_ranges_batched(p_grp_all: torch.Tensor, meta: BlockMeta, n_top: int, S: int, force_init: bool = True,

@@ -209,11 +209,11 @@ def test_kv_cache_grows_in_place_of_the_reference_cat(nv):
     first = tok(20)
     kv.write_tokens(*first)
     kv.write_compressed(torch.ones(2, 2, 9, 8), torch.ones(2, 2, 9, 8), at=0)
-    kv._desc = kv._dec_ctx = object()
+    kv._native["desc"] = kv._native["layer_decode"] = object()
     more = tok(5)
     kv.write_tokens(*more)  # 25 > 20: doubles
     assert kv.S_max == 40 and kv._K_sel.shape[2] == 40 and kv._K_cmp.shape[2] == (40 - 4) // 2 + 1
-    assert not hasattr(kv, "_desc") and not hasattr(kv, "_dec_ctx")
+    assert not kv._native
     assert torch.equal(kv.K_sel, torch.cat([first[0], more[0]], dim=2)) and torch.equal(kv.V_cmp_raw_seq[:, :, :20], first[5])
     assert kv.K_cmp.shape[2] == 9 and bool((kv.K_cmp == 1).all())
     assert kv.K_win.shape[2] == 16

@@ -52,10 +52,10 @@ def rows_cabi(m, x, kv):
     from nsa_vibe_amd.selection_scorer import _stream
 
     B, S, _ = x.shape
-    t0, meta = m._extend_begin(kv, S)
+    t0, meta = kv.begin_rows(S)
     L, dev = _lib.lib(), x.device
     desc, _ = m._layer_desc()
-    kd = m._kv_desc(kv)
+    kd = kv.native_desc()
     plan = m.decode_rows_plan(B, S, kd.S_max, t0, int(meta.S_sel))
     ranges = torch.full((B, S, m.n_kv_groups, m.n_sel, 2), -7, dtype=torch.int32, device=dev)
     gates = torch.full((B, S, m.n_kv_groups, 3), float("nan"), dtype=torch.float32, device=dev)
@@ -68,7 +68,7 @@ def rows_cabi(m, x, kv):
     rc = L.nsa_layer_decode_rows(ctypes.byref(desc), ctypes.byref(kd), xc.data_ptr(), y.data_ptr(), t0, S, cptr.data_ptr(), crows.data_ptr(),
                                  cvals.data_ptr(), int(meta.S_sel), ranges.data_ptr(), gates.data_ptr(), wptr, nb, _stream(dev))
     _lib.check(rc, "nsa_layer_decode_rows")
-    m._extend_end(kv, t0, S)
+    kv.end_rows(t0, S)
     torch.cuda.synchronize()
     return y, ranges, gates, plan
 

@@ -59,7 +59,7 @@ def main():
             kv = m.new_kv(B, ctx, dev, dt)
             for name in ("_K_sel", "_V_sel", "_K_win", "_V_win", "_K_raw", "_V_raw", "_K_cmp", "_V_cmp"):
                 getattr(kv, name).normal_()
-            kd = m._kv_desc(kv)
+            kd = kv.native_desc()
             kref = ctypes.byref(kd)
             for S in (1, 2, 4, 8, 16):  # (S = 1: the cell behind the default rule's one decline)
                 t0 = ctx - S
