@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/nsa_sel_hip.h"
 
 namespace nsa {
@@ -139,6 +141,11 @@ static inline auto with_elt(int dtype, F &&f) {
         if (dtype == NSA_DT_F32) return f(float{});
     if (dtype == NSA_DT_BF16) return f(__bf16{});
     return f(_Float16{});
+}
+// a run-time flag as a compile-time constant, once (host): f(std::true_type{}) or f(std::false_type{}) -- decltype(flag)::value in a template argument
+template <typename F>
+static inline auto with_flag(bool on, F &&f) {
+    return on ? f(std::true_type{}) : f(std::false_type{});
 }
 
 // ---- wave helpers ----------------------------------------------------------------------

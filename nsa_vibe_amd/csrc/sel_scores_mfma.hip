@@ -25,6 +25,8 @@
 // sequence); columns c >= n_cmp(t) are masked per lane (-inf in sweep 1, p = 0 in sweep 2) on the few tiles that reach past the wave's
 // earliest bound, so masked tiles leave a row's statistics bit for bit unchanged and a row's p_grp does not depend on which later rows
 // share its chunk (chunk boundaries at multiples of the workgroup's QW queries).
+// Shared with the 32x32x16 form (sel_scores_mfma.hpp): the K_cmp tile source, the sweep bounds and the exact sweep-1 update; the Q^T column
+// fragments and the K row reads stay spelled out here (through load_col_frags / read_row_frags the tile loops change their instruction mix).
 #include "attn_mfma_tiles.hpp"
 #include "sel_scores_mfma.hpp"
 #include "sel_select_row.hpp"
@@ -65,9 +67,7 @@ __global__ __launch_bounds__(256, 2) void scores_mfma_kernel(ScoresMfmaParams P)
     const int QW = 4 * QPW;                          // queries per workgroup
     const int bg = blockIdx.y;
     const int b = bg / P.G, g = bg % P.G;
-    // late query tiles first: with causal_skip the second sweep of a tile grows with its position (a tile at the end of a 64k sequence does
-    // 1.5x the work of the first one), and the dispatcher hands out workgroups in index order -- longest first keeps the tail short
-    const int t0 = (P.causal_skip ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x) * QW;
+    const int t0 = wg_first_query(P, QW);
     const T *Kc = (const T *)P.Kc + (int64_t)b * P.csb + (int64_t)g * P.csg;
     const float c2 = P.scale * LOG2E;
 
@@ -91,52 +91,19 @@ __global__ __launch_bounds__(256, 2) void scores_mfma_kernel(ScoresMfmaParams P)
         }
     }
 
-    const int ntiles = (P.S_cmp + TILE_ROWS - 1) / TILE_ROWS;
-    // NORM: visible columns per lane column (n_cmp of its query; columns of absent queries take the last row's), the wave's smallest
-    // bound (its first query) and the workgroup's largest (its last query)
-    int ncl[NT];
-    int nc_wmin = P.S_cmp, nc_wgmax = P.S_cmp;
+    int ncl[NT];  // NORM: visible columns per lane column (n_cmp of its query; columns of absent queries take the last row's)
     if constexpr (NORM) {
 #pragma unroll
         for (int n = 0; n < NT; ++n) ncl[n] = ncmp_at(P.q0 + (tq[n] >= 0 ? tq[n] : P.S - 1), P.l, P.d_stride, P.S_cmp);
-        nc_wmin = ncmp_at(P.q0 + min(t0 + wave * QPW, P.S - 1), P.l, P.d_stride, P.S_cmp);
-        nc_wgmax = ncmp_at(P.q0 + min(t0 + QW, P.S) - 1, P.l, P.d_stride, P.S_cmp);
     }
-    const int ntiles1 = NORM ? (nc_wgmax + TILE_ROWS - 1) / TILE_ROWS : ntiles;  // tiles of the first sweep
-    // staging: thread -> (row, piece) pairs
+    const SweepBounds sb = sweep_bounds<NORM>(P, t0, QW, t0 + wave * QPW);
+    const int ntiles = sb.ntiles, ntiles1 = sb.ntiles1, nc_wmin = sb.nc_wmin;
     u32x4 stg[LD_PER_THREAD];
-    // full tiles: one scalar base per tile + a lane-constant 32-bit offset (the per-lane 64-bit row arithmetic with its clamp was 16 VALU
-    // instructions per tile and wave in a kernel bound by instruction issue); only the last, padded tile clamps its rows
     unsigned toff[LD_PER_THREAD];
-#pragma unroll
-    for (int i = 0; i < LD_PER_THREAD; ++i) {
-        const int p = tid + 256 * i;
-        toff[i] = (unsigned)((p / PIECES) * (int)P.css + (p % PIECES) * 8) * (unsigned)sizeof(T);
-    }
-    const bool small_stride = P.css * (int64_t)TILE_ROWS * (int64_t)sizeof(T) < ((int64_t)1 << 31);
-    auto load_tile = [&](int tile) {
-        if (small_stride && (tile + 1) * TILE_ROWS <= P.S_cmp) {
-            const unsigned char *base = (const unsigned char *)(Kc + (int64_t)tile * TILE_ROWS * P.css);  // wave uniform
-#pragma unroll
-            for (int i = 0; i < LD_PER_THREAD; ++i) stg[i] = *(const u32x4 *)(base + toff[i]);
-            return;
-        }
-#pragma unroll
-        for (int i = 0; i < LD_PER_THREAD; ++i) {
-            const int p = tid + 256 * i;
-            const int r = p / PIECES, pc = p % PIECES;
-            const int row = min(tile * TILE_ROWS + r, P.S_cmp - 1);
-            stg[i] = *(const u32x4 *)(Kc + (int64_t)row * P.css + pc * 8);
-        }
-    };
-    auto store_tile = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < LD_PER_THREAD; ++i) {
-            const int p = tid + 256 * i;
-            const int r = p / PIECES, pc = p % PIECES;
-            *(u32x4 *)(lds + buf * TILE_BYTES + r * ROWB + ((pc ^ (r & (PIECES - 1))) << 4)) = stg[i];
-        }
-    };
+    bool small_stride;
+    kcmp_tile_offsets<T, D>(P, tid, toff, small_stride);
+    auto load_tile = [&](int tile) { kcmp_tile_load<T, D>(P, Kc, tid, toff, small_stride, tile, stg); };
+    auto store_tile = [&](int buf) { kcmp_tile_store<D, 0, PIECES - 1>(tid, stg, lds + buf * TILE_BYTES); };
     // S^T accumulators of one 64-row tile for all NT column tiles
     auto compute_tile = [&](int buf, f32x4 (&acc)[4][NT]) {
         const unsigned char *base = lds + buf * TILE_BYTES;
@@ -193,37 +160,10 @@ __global__ __launch_bounds__(256, 2) void scores_mfma_kernel(ScoresMfmaParams P)
                 }
             float sum = sum2[0] + sum2[1];
             if (__any(!(sum <= 4096.f)) || rows_valid < TILE_ROWS || masked) {
-                asm volatile("; sweep-1 slow path" ::: "memory");
-                int rv = rows_valid;  // (same reason as for the logits below: the 16 row masks belong to this block)
-                if constexpr (NORM) {
-                    rv = min(rv, ncl[n] - tile * TILE_ROWS);  // per lane column
-                    asm volatile("" : "+v"(rv));
-                } else {
-                    asm volatile("" : "+s"(rv));
-                }
-                float v[16];
-                float mx = -INFINITY;
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int r = 16 * u + 4 * q + j;
-                        // the logit enters this block through an (empty) asm: without it the compiler evaluates the masks, products and maxima
-                        // of this rare path ahead of the branch, on every tile (90 of 255 VALU instructions of the common path)
-                        float a = acc[u][n][j];
-                        asm volatile("" : "+v"(a));
-                        const float x = (r < rv) ? a * c2 : -INFINITY;
-                        v[4 * u + j] = x;
-                        mx = fmaxf(mx, x);
-                    }
-                const float mnew = fmaxf(mrun[n], mx);
-                sum = 0.f;
-                if (mnew > -INFINITY) {  // a lane group may see only padding rows in the last tile
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) sum += __builtin_amdgcn_exp2f(v[i] - mnew);
-                    lrun[n] = lrun[n] * __builtin_amdgcn_exp2f(mrun[n] - mnew);
-                    mrun[n] = mnew;
-                }
+                int rv = rows_valid;
+                if constexpr (NORM) rv = min(rv, ncl[n] - tile * TILE_ROWS);
+                sum = sweep1_exact<NORM>([&](int i) { return acc[i >> 2][n][i & 3]; }, [&](int i) { return 16 * (i >> 2) + 4 * q + (i & 3); }, rv, c2,
+                                         mrun[n], lrun[n]);
             }
             lrun[n] += sum;
         }
@@ -243,13 +183,7 @@ __global__ __launch_bounds__(256, 2) void scores_mfma_kernel(ScoresMfmaParams P)
     }
 
     // ================= sweep 2: normalise, Eq.9 stencil, Eq.10 head sum, store =================
-    const int l_sel = 4 * P.d_stride;
-    int jlast = P.S_sel - 1;  // last selection block this workgroup has to produce
-    if (P.causal_skip) {
-        const int t_last = P.q0 + min(t0 + QW, P.S) - 1;  // absolute position of the workgroup's last query
-        jlast = min(jlast, (t_last + 1) / l_sel - 1);
-    }
-    if constexpr (NORM) jlast = min(jlast, nc_wgmax / 4);  // later blocks have no visible tap (block j's first tap is column 4j - 1)
+    const int jlast = sweep2_last_block<NORM>(P, t0, QW, sb.nc_wgmax);
     const int tiles2 = (jlast < 0) ? 0 : min(ntiles, (4 * jlast + 3) / TILE_ROWS + 1);
     float rot_prev[NT];
 #pragma unroll
@@ -419,13 +353,11 @@ int launch_sel_scores_mfma(const ScoresCall &c, const SelectParams *sel, int *se
         if (fuse) *sel_done = 1;
         return launch_scores_mfma32(P, c.dtype, c.st, fuse ? sel : nullptr);
     }
-    int rc = NSA_OK;
-    with_elt<false>(c.dtype, [&](auto t) {
-        using T = decltype(t);
-        if (P.norm) rc = c.Dk == 64 ? launch_scores_t<T, 64, true>(P, c.st) : launch_scores_t<T, 128, true>(P, c.st);
-        else rc = c.Dk == 64 ? launch_scores_t<T, 64, false>(P, c.st) : launch_scores_t<T, 128, false>(P, c.st);
+    return with_elt<false>(c.dtype, [&](auto t) {
+        return with_flag(c.Dk == 128, [&](auto wide) {
+            return with_flag(P.norm, [&](auto norm) { return launch_scores_t<decltype(t), decltype(wide)::value ? 128 : 64, decltype(norm)::value>(P, c.st); });
+        });
     });
-    return rc;
 }
 
 }  // namespace nsa

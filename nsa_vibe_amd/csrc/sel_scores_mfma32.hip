@@ -2,7 +2,8 @@
 //
 // Same reference chain and the same two sweeps as sel_scores_mfma.hip (compute_pcmp_all, selection_scorer.py:42-61 ->
 // map_pcmp_to_pslc_batched, :89-116 -> .sum(dim=3), nsa_attention.py:1091; Eq.9 as the 5-tap stencil of l = 2d, l' = 4d).  What changes is
-// the tile shape and, in the second sweep, which operand supplies the MFMA rows.
+// the tile shape and, in the second sweep, which operand supplies the MFMA rows; the sweep bounds and the exact sweep-1 update are the shared
+// ones of sel_scores_mfma.hpp.
 //
 // Cost model (tools/ubench/issue_rates.hip, profiles/r03/issue_rates.txt and scorer_notes.txt; cycles of one SIMD at the nominal clock, two or
 // more waves to pick from): v_fma / v_add / v_mul 2.6, v_pk_fma_f32 4.9-5.8 (two plain ops cost the same), DPP add 4.2, v_exp_f32 8.2,
@@ -87,8 +88,7 @@ __global__ __launch_bounds__(256, 3) void scores_mfma32_kernel(ScoresMfmaParams 
     const int r = lane & 31, half = lane >> 5;
     const int bg = blockIdx.y;
     const int b = bg / P.G, g = bg % P.G;
-    // late query tiles first (longest second sweep first), as in the 16x16 form
-    const int t0 = (P.causal_skip ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x) * QW;
+    const int t0 = wg_first_query(P, QW);
     const int tw = t0 + wave * QPW;
     const T *Kc = (const T *)P.Kc + (int64_t)b * P.csb + (int64_t)g * P.csg;
     const float c2 = P.scale * LOG2E;
@@ -114,11 +114,7 @@ __global__ __launch_bounds__(256, 3) void scores_mfma32_kernel(ScoresMfmaParams 
         }
     }
 
-    const int ntiles = (P.S_cmp + TILE_ROWS - 1) / TILE_ROWS;
-    // NORM: visible columns of the lane's sweep-1 column per tile n (its query's n_cmp; absent queries take the last row's), the wave's
-    // smallest bound (query tw) and the workgroup's largest (its last query)
-    int ncl[3];
-    int nc_wmin = P.S_cmp, nc_wgmax = P.S_cmp;
+    int ncl[3];  // NORM: visible columns of the lane's sweep-1 column per tile n (its query's n_cmp; absent queries take the last row's)
     if constexpr (NORM) {
 #pragma unroll
         for (int n = 0; n < 3; ++n) {
@@ -127,42 +123,17 @@ __global__ __launch_bounds__(256, 3) void scores_mfma32_kernel(ScoresMfmaParams 
             const int t = tw + 8 * ((R >> 2) & 1) + ridx / HC;
             ncl[n] = ncmp_at(P.q0 + min(t, P.S - 1), P.l, P.d_stride, P.S_cmp);
         }
-        nc_wmin = ncmp_at(P.q0 + min(tw, P.S - 1), P.l, P.d_stride, P.S_cmp);
-        nc_wgmax = ncmp_at(P.q0 + min(t0 + QW, P.S) - 1, P.l, P.d_stride, P.S_cmp);
     }
-    const int ntiles1 = NORM ? (nc_wgmax + TILE_ROWS - 1) / TILE_ROWS : ntiles;  // tiles of the first sweep
+    const SweepBounds sb = sweep_bounds<NORM>(P, t0, QW, tw);
+    const int ntiles = sb.ntiles, ntiles1 = sb.ntiles1, nc_wmin = sb.nc_wmin;
     // staging of one 64-row K_cmp tile: thread -> 2 (row, 16-B piece) pairs.  LDS piece swizzle (row >> 1) & 7: the 16 rows x one piece a
     // quarter-wave reads, and the 2 rows x 8 pieces it writes, both cover the 64 banks exactly once.
     u32x4 stg[NLD];
     unsigned toff[NLD];
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-        const int p = tid + 256 * i;
-        toff[i] = (unsigned)((p >> 3) * (int)P.css + (p & 7) * 8) * (unsigned)sizeof(T);
-    }
-    const bool small_stride = P.css * (int64_t)TILE_ROWS * (int64_t)sizeof(T) < ((int64_t)1 << 31);
-    auto load_tile = [&](int tile) {
-        if (small_stride && (tile + 1) * TILE_ROWS <= P.S_cmp) {
-            const unsigned char *base = (const unsigned char *)(Kc + (int64_t)tile * TILE_ROWS * P.css);  // wave uniform
-#pragma unroll
-            for (int i = 0; i < NLD; ++i) stg[i] = *(const u32x4 *)(base + toff[i]);
-            return;
-        }
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-            const int p = tid + 256 * i;
-            const int row = min(tile * TILE_ROWS + (p >> 3), P.S_cmp - 1);
-            stg[i] = *(const u32x4 *)(Kc + (int64_t)row * P.css + (p & 7) * 8);
-        }
-    };
-    auto store_tile = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-            const int p = tid + 256 * i;
-            const int row = p >> 3, pc = p & 7;
-            *(u32x4 *)(lds + buf * TILE_BYTES + row * ROWB + ((pc ^ ((row >> 1) & 7)) << 4)) = stg[i];
-        }
-    };
+    bool small_stride;
+    kcmp_tile_offsets<T, D>(P, tid, toff, small_stride);
+    auto load_tile = [&](int tile) { kcmp_tile_load<T, D>(P, Kc, tid, toff, small_stride, tile, stg); };
+    auto store_tile = [&](int buf) { kcmp_tile_store<D, 1, 7>(tid, stg, lds + buf * TILE_BYTES); };
     // K fragment of the 32-row half hf of a tile: row 32 hf + r, dims 16 s + 8 half .. (piece 2 s + half)
     unsigned koff[4];
 #pragma unroll
@@ -222,33 +193,10 @@ __global__ __launch_bounds__(256, 3) void scores_mfma32_kernel(ScoresMfmaParams 
                 }
                 float sum = s0 + s1;
                 if (__any(!(sum <= 4096.f)) || rows_valid < 32 || masked) {
-                    asm volatile("; sweep-1 slow path" ::: "memory");
-                    int rv = rows_valid;  // the row masks belong to this block
-                    if constexpr (NORM) {
-                        rv = min(rv, ncl[n] - tile * TILE_ROWS - 32 * hf);  // per lane column
-                        asm volatile("" : "+v"(rv));
-                    } else {
-                        asm volatile("" : "+s"(rv));
-                    }
-                    float v[16];
-                    float mx = -INFINITY;
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const int row = 8 * (i >> 2) + 4 * half + (i & 3);
-                        float a = acc[n][i];  // through an (empty) asm: keeps the masks, products and maxima of this rare path behind the branch
-                        asm volatile("" : "+v"(a));
-                        const float x = (row < rv) ? a * c2 : -INFINITY;
-                        v[i] = x;
-                        mx = fmaxf(mx, x);
-                    }
-                    const float mnew = fmaxf(mrun[n], mx);
-                    sum = 0.f;
-                    if (mnew > -INFINITY) {  // a lane may see only padding rows
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) sum += __builtin_amdgcn_exp2f(v[i] - mnew);
-                        lrun[n] = lrun[n] * __builtin_amdgcn_exp2f(mrun[n] - mnew);
-                        mrun[n] = mnew;
-                    }
+                    int rv = rows_valid;
+                    if constexpr (NORM) rv = min(rv, ncl[n] - tile * TILE_ROWS - 32 * hf);
+                    sum = sweep1_exact<NORM>([&](int i) { return acc[n][i]; }, [&](int i) { return 8 * (i >> 2) + 4 * half + (i & 3); }, rv, c2, mrun[n],
+                                             lrun[n]);
                 }
                 lrun[n] += sum;
             }
@@ -271,13 +219,7 @@ __global__ __launch_bounds__(256, 3) void scores_mfma32_kernel(ScoresMfmaParams 
     // difference between 3 and 2 waves per SIMD (broadcast reads, 12 ds_read_b128 per half tile)
 
     // ================= sweep 2: normalise, Eq.10 head sum (in lane), Eq.9 stencil (along the lanes), store =================
-    const int l_sel = 4 * P.d_stride;
-    int jlast = P.S_sel - 1;  // last selection block this workgroup has to produce
-    if (P.causal_skip) {
-        const int t_last = P.q0 + min(t0 + QW, P.S) - 1;  // absolute position of the workgroup's last query
-        jlast = min(jlast, (t_last + 1) / l_sel - 1);
-    }
-    if constexpr (NORM) jlast = min(jlast, nc_wgmax / 4);  // later blocks have no visible tap (block j's first tap is column 4j - 1)
+    const int jlast = sweep2_last_block<NORM>(P, t0, QW, sb.nc_wgmax);
     const int nhalf2 = (jlast < 0) ? 0 : min(NH * ntiles, (4 * jlast + 3) / 32 + 1);  // 32-row halves (8 selection blocks each) to visit
 #ifdef SC32_SWEEP1  // ablation: first sweep only
     const int tiles2 = 0;
@@ -451,14 +393,12 @@ int launch_scores_mfma32(const ScoresMfmaParams &P, int dtype, hipStream_t st, c
     dim3 grid((unsigned)((P.S + 63) / 64), (unsigned)(P.B * P.G));
     const SelectParams none{};
     with_elt<false>(dtype, [&](auto t) {
-        using T = decltype(t);
-        if (P.norm) {
-            if (sel) hipLaunchKernelGGL((scores_mfma32_kernel<T, true, true>), grid, dim3(256), 0, st, P, *sel);
-            else hipLaunchKernelGGL((scores_mfma32_kernel<T, false, true>), grid, dim3(256), 0, st, P, none);
-        } else {
-            if (sel) hipLaunchKernelGGL((scores_mfma32_kernel<T, true, false>), grid, dim3(256), 0, st, P, *sel);
-            else hipLaunchKernelGGL((scores_mfma32_kernel<T, false, false>), grid, dim3(256), 0, st, P, none);
-        }
+        with_flag(sel != nullptr, [&](auto fused) {
+            with_flag(P.norm, [&](auto norm) {
+                hipLaunchKernelGGL((scores_mfma32_kernel<decltype(t), decltype(fused)::value, decltype(norm)::value>), grid, dim3(256), 0, st, P,
+                                   sel ? *sel : none);
+            });
+        });
     });
     NSA_LAUNCH_CHECK("scores_mfma32");
     return NSA_OK;

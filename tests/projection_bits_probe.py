@@ -93,15 +93,16 @@ def rope_inputs(B, S, ci):
 
 
 class Out(dict):
-    def put(self, key, t):
-        """t: a device / host tensor of a kernel dtype -> its bit pattern"""
+    def put(self, key, t, big=None):
+        """t: a device / host tensor of a kernel dtype -> its bit pattern (big: the size from which only the ends + SHA-256 are kept; default BIG)"""
+        big = BIG if big is None else big
         import torch
 
         a = t.detach().contiguous().cpu()
         bits = a.view(torch.int16 if a.element_size() == 2 else torch.int32).numpy().view(np.uint16 if a.element_size() == 2 else np.uint32).reshape(-1)
-        if bits.size > BIG:
+        if bits.size > big:
             self[key + ".sha"] = np.frombuffer(hashlib.sha256(bits.tobytes()).digest(), np.uint32).copy()
-            bits = np.concatenate([bits[:BIG // 2], bits[-BIG // 2:]])
+            bits = np.concatenate([bits[:big // 2], bits[-big // 2:]])
         self[key] = bits.copy()
 
 

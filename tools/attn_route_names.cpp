@@ -2,6 +2,7 @@
 // the HIP calls of its host code itself (no kernel runs) and notes the device name that every kernel was registered under, so that each
 // launch can be printed by its template instance.  Reads one case per line from stdin, as `tests/attention_bits_probe.py --routes` prints them:
 //   case=NAME entry=sel|fuse|band|selbwd|bandbwd dt= B= S= G= h= D= S_kv= pad= [n= lse= S_sel= mode= t0= a= dd= c= w=] sw=SWITCH:VALUE,...
+// and, for `tests/scorer_bits_probe.py --routes`, entry=scores|scoresel (S_kv = S_cmp, skip = causal_skip, t0 = q0, norm; l / d / l' = 32 / 16 / 64)
 // and prints per case: NAME <tab> kernel [map_mode=..] [cand=..] | kernel ...
 //   hipcc -x c++ -std=c++17 -O1 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include tools/attn_route_names.cpp -o ab/attn_route_names -rdynamic -ldl
 //   python tests/attention_bits_probe.py --routes | ab/attn_route_names nsa_vibe_amd/libnsa_sel_hip.so > routes.txt
@@ -12,6 +13,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <iostream>
 #include <map>
 #include <sstream>
@@ -143,6 +145,16 @@ int main(int argc, char **argv) {
             ws = mem(need);
             rc = FN(nsa_band_attn_bwd)(Q, K, V, O, (const float *)lse, dO, dQ, (float *)dK, (float *)dV, B, S, G, h, D, D, S_kv, sb, sg, ss, sb, sg, ss, I("t0"), I("a"),
                                        I("dd"), I("c"), I("w"), dt, 0.f, 2, ws, need, nullptr);
+        } else if (e == "scores") {  // the scorer alone, variant 2 (no workspace)
+            rc = FN(nsa_sel_scores_rows)(Q, K, (float *)pg, B, S, G, h, D, S_kv, sb, sg, ss, (const int32_t *)rg, (const int32_t *)rg, (const float *)lse, I("S_sel"), 32, 16,
+                                         64, I("skip"), 2, dt, 0.f, I("t0"), I("norm"), nullptr, 0, nullptr);
+        } else if (e == "scoresel") {  // scorer + top-16 selection in one call
+            const int md = I("mode"), W = md == NSA_SEL_BATCHED ? FN(nsa_batched_ranges_width)(S, I("S_sel"), 64, 16, 1, 2) : 16;
+            for (int v : {0, 1}) need = std::max(need, FN(nsa_sel_scores_rows_workspace)(B, S, G, h, D, S_kv, I("S_sel"), 32, 16, 64, dt, v, I("norm")));
+            ws = mem(need);
+            rc = FN(nsa_sel_scores_select_rows)(Q, K, (float *)pg, B, S, G, h, D, S_kv, sb, sg, ss, (const int32_t *)rg, (const int32_t *)rg, (const float *)lse, I("S_sel"),
+                                                32, 16, 64, I("skip"), dt, 0.f, I("t0"), 16, 1, 2, md, S, (int32_t *)O, W, I("t0"), I("norm"), need ? ws : nullptr, need,
+                                                nullptr);
         }
         printf("%s\t", kv["case"].c_str());
         if (rc) printf("rc=%d %s", rc, FN(nsa_hip_last_error)());
