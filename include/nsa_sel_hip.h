@@ -308,6 +308,34 @@ NSA_API int nsa_layer_decode_rows(const nsa_layer_desc *L, const nsa_kv_desc *kv
                           int32_t *ranges_out, float *gates_out, void *workspace, size_t workspace_bytes, void *stream);
 NSA_API int nsa_layer_decode_rows_plan(const nsa_layer_desc *L, int B, int S, int S_max, int t0, int S_sel, int *launches /* host */,
                                int *route /* host */);
+/* The same for a RAGGED batch: every sequence at its own position, read on the device.  x / y [B,S,dim], 1 <= S <= 16; row (b, s) is the token
+ * at position t_pos[b] + s of sequence b, whose slab of the caches already holds t_pos[b] tokens.  For every live sequence the call does
+ * what nsa_layer_decode_rows(t0 = t_pos[b]) does to that sequence: the same appended cache rows, pooled tokens, ranges, gates and y rows.
+ * t_pos: DEVICE int32 [B], 4-byte aligned.  t_max: the caller's HOST bound of t_pos[b] + S - 1.  With te = min(t_max, kv->S_max - 1) the host
+ * checks that S_sel and kv->n_cmp_max cover te + 1 tokens and plans every launch from te, B and S alone; it never reads t_pos (no copy, no
+ * synchronisation), so the arguments of the call do not change from token to token: advance t_pos on the device and call again.
+ * A sequence with t_pos[b] < 0 or t_pos[b] + S - 1 > te is INACTIVE -- the padding slot of a batch, and the guard that keeps a wrong
+ * position inside the buffers (nothing is clamped silently): NOTHING is written to any of its eight cache tensors, its y and ranges_out
+ * rows are zero, its gates_out rows are UNSPECIFIED (the gate is evaluated from whatever Q the projection left in the workspace; x rows
+ * of an inactive sequence must still be finite for its y rows to be zero).  Rows of a slab beyond its own sequence are never read:
+ * every kernel bounds its loads by the sequence's own last token, so what an allocator left there (NaN patterns included) is harmless.
+ * Six launches at Dk = Dv = 64, always: 1. the fused QKV projection with RoPE + append at t_pos[b] + s, 2. pooling (launched every call,
+ * since the host cannot know whether a window completes: ceil(S / d) blocks per (b, g), which exit where none does), 3. the selected
+ * branch as the rows form of nsa_sel_decode_ragged, 4. the sliding and the compressed branch in one launch, 5. split combine + gates +
+ * mix, 6. the output projection.  At Dk = Dv = 128 the band branches are one ragged launch each and the gate kernel stands in for 5.
+ * There is no scalar route to stand in, so the call DECLINES with NSA_ERR_INVALID and a message naming the limit wherever
+ * nsa_sel_decode_ragged does: a dtype other than bf16 / f16, anything but Dk = Dv in {64, 128} and the default block geometry, te beyond the
+ * unsplit forms, DECODE_STEP = 0 or DECODE_UNFUSED = 1, a null or misaligned operand, S outside [1,16].
+ * nsa_layer_decode_ragged_plan makes no HIP call: NSA_OK with *launches = n and *route = 1, or *launches = 0 and *route = -1 for a declined
+ * shape; an error status for bad arguments.  workspace: nsa_layer_decode_ragged_workspace() bytes, 256-byte aligned -- not less than
+ * nsa_layer_decode_rows_workspace(L, B, S, S_max), and 0 for the arguments that call answers 0 for. */
+NSA_API size_t nsa_layer_decode_ragged_workspace(const nsa_layer_desc *L, int B, int S, int S_max);
+NSA_API int nsa_layer_decode_ragged(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *x, void *y,
+                            const int32_t *t_pos /* device [B] */, int t_max /* host */, int S, const int32_t *csc_ptr,
+                            const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out, float *gates_out,
+                            void *workspace, size_t workspace_bytes, void *stream);
+NSA_API int nsa_layer_decode_ragged_plan(const nsa_layer_desc *L, int B, int S, int S_max, int t_max, int S_sel, int *launches /* host */,
+                                 int *route /* host */);
 
 /* ---------------------------------------------------------------------------------------
  * Eq.9 map in gather (CSC) form.  For selection block j the entries csc_ptr[j]..csc_ptr[j+1]

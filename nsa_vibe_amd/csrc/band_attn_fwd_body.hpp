@@ -83,7 +83,13 @@ __device__ __forceinline__ void band_attn_body(const BandAttnParams &P, const un
     uint32_t krd0[KS], vrd0[MT];
     frag_read_offsets<D>(rho, q, krd0, vrd0);
     // rows past the end of K/V re-read the last row (they are masked: only boundary tiles reach past hi)
-    auto issue_dma = [&](int tok0) { tile_dma(kv, kl, vl, tok0, tok0 + 32 <= P.S_kv, P.S_kv - 1 - tok0); };
+    // RAGGED: one S_kv serves every sequence of the launch, and the rows between a shorter sequence's last key and S_kv were never
+    // written -- allocator garbage, NaN bit patterns included.  They would be masked to p = 0, but 0 * NaN poisons the P V product, so
+    // the end of K/V is the wave's own last key here: no row beyond hi_max is read (rows below it belong to the sequence: its S tokens
+    // and its compressed tokens are in the cache when the branch runs).  The scalar forms keep P.S_kv, which their caller bounds.
+    int kend = P.S_kv;
+    if constexpr (RAGGED) kend = min(P.S_kv, hi_max);
+    auto issue_dma = [&](int tok0) { tile_dma(kv, kl, vl, tok0, tok0 + 32 <= kend, kend - 1 - tok0); };
 
     typedef __attribute__((ext_vector_type(4))) unsigned int bu32x4;
     u32x4 kreg[G_::NLD], vreg[G_::NLD];
@@ -96,7 +102,7 @@ __device__ __forceinline__ void band_attn_body(const BandAttnParams &P, const un
     }
     auto issue_loads = [&](int tok0) {
         const int ks = uniform(tok0 * kv.krowb), vs = uniform(tok0 * kv.vrowb);
-        const int last = P.S_kv - 1 - tok0;
+        const int last = kend - 1 - tok0;
 #pragma unroll
         for (int i = 0; i < G_::NLD; ++i) {
             const int rc = min(i * G_::RPI + kv.ld_row, last);

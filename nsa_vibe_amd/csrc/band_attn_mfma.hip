@@ -24,10 +24,12 @@ __global__ __launch_bounds__(256, 2) void band_attn_fwd_kernel(BandAttnParams P)
 }
 
 // decode: the sliding and the compressed branch of one step in ONE launch (two argument blocks, split-KV form)
-template <typename T, int D>
+// RAGGED: both blocks carry the same position array (the layer's ragged call); a sequence that is not live leaves the empty-interval
+// records (m = -inf, l = 0, o = 0) the finish kernel turns into zero rows, as a row too short for a compressed token does today
+template <typename T, int D, bool RAGGED = false>
 __global__ __launch_bounds__(256, 2) void band_attn_fwd_dual_kernel(BandAttnParams P0, BandAttnParams P1, unsigned grid0) {
-    if (blockIdx.x < grid0) band_attn_body<T, D, 1, true, 1>(P0, blockIdx.x);
-    else band_attn_body<T, D, 1, true, 1>(P1, blockIdx.x - grid0);
+    if (blockIdx.x < grid0) band_attn_body<T, D, 1, true, 1, RAGGED>(P0, blockIdx.x);
+    else band_attn_body<T, D, 1, true, 1, RAGGED>(P1, blockIdx.x - grid0);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -287,8 +289,12 @@ int launch_band_attn_fwd_dual(const BandAttnParams &A0, const BandAttnParams &A1
     const bool d64 = P[0].Dk == 64;
     const size_t lds = 4 * (size_t)(2 * (d64 ? Geo<64>::TILE_BYTES : Geo<128>::TILE_BYTES));
     const dim3 g2(grid[0] + grid[1]);
+    const bool ragged = P[0].t_pos != nullptr;  // per-sequence positions: the RAGGED instantiation
+    NSA_CHECK_ARG(P[0].t_pos == P[1].t_pos && (!ragged || P[0].t_max == P[1].t_max), "band dual launch: one position array for both branches");
     with_elt<false>(dtype, [&](auto t) {
-        if (d64) hipLaunchKernelGGL((band_attn_fwd_dual_kernel<decltype(t), 64>), g2, dim3(256), lds, st, P[0], P[1], grid[0]);
+        if (ragged && d64) hipLaunchKernelGGL((band_attn_fwd_dual_kernel<decltype(t), 64, true>), g2, dim3(256), lds, st, P[0], P[1], grid[0]);
+        else if (ragged) hipLaunchKernelGGL((band_attn_fwd_dual_kernel<decltype(t), 128, true>), g2, dim3(256), lds, st, P[0], P[1], grid[0]);
+        else if (d64) hipLaunchKernelGGL((band_attn_fwd_dual_kernel<decltype(t), 64>), g2, dim3(256), lds, st, P[0], P[1], grid[0]);
         else hipLaunchKernelGGL((band_attn_fwd_dual_kernel<decltype(t), 128>), g2, dim3(256), lds, st, P[0], P[1], grid[0]);
     });
     NSA_LAUNCH_CHECK("band_attn_fwd_dual");

@@ -4,6 +4,7 @@
 // entry point again and again with the refusal moved one launch further walks its whole route: every case prints the launchers in order,
 // each launch's grid / block / LDS bytes, the host memsets, and the status and nsa_hip_last_error() of the complete call.
 //   dispatch_check <path of libnsa_sel_hip.so>      prints one JSON object, a member per case
+//   dispatch_check <library> ragged | layer_ragged  the cases of the entry points with per-sequence positions instead
 #include <dlfcn.h>
 #include <math.h>
 #include <stdio.h>
@@ -502,9 +503,106 @@ static void ragged_cases() {
     band_case("sliding_f32_generic", 5, 1, NSA_DT_F32, 1000, false, true);
 }
 
+// ---- dispatch_check <library> layer_ragged: the layer's ragged call (nsa_layer_decode_ragged), cases of their own like `ragged`.  Every
+// case prints the launchers in order with their geometry, the plan's answer for the same shape, and "positions": the position pointer and the
+// bound te as they arrive in the argument blocks of the four launches that depend on the position (projection, pooling, the selected branch,
+// the band pair: both of its blocks).
+static void layer_ragged_cases() {
+    const size_t MB = 1 << 20;
+    void *x = dev(MB), *y = dev(MB), *W_qkv = dev(MB), *W_out = dev(MB), *gw = dev(MB), *ws = dev(64 * MB);
+    void *cache[8];
+    static const char *cname[8] = {"K_sel", "V_sel", "K_win", "V_win", "K_raw", "V_raw", "K_cmp", "V_cmp"};
+    int32_t *t_pos = (int32_t *)dev(MB, 0x7f), *ranges = (int32_t *)dev(MB);
+    float *gates = (float *)dev(MB);
+    g_named = {{"x", x, MB}, {"y", y, MB}, {"W_qkv", W_qkv, MB}, {"W_out", W_out, MB}, {"t_pos", t_pos, MB}, {"ranges", ranges, MB}, {"gates", gates, MB},
+               {"ws", ws, 64 * MB}};
+    for (int i = 0; i < 8; ++i) {
+        cache[i] = dev(MB);
+        g_named.push_back({cname[i], cache[i], MB});
+    }
+    auto fn = NSA_FN(nsa_layer_decode_ragged);
+    auto plan_fn = NSA_FN(nsa_layer_decode_ragged_plan);
+    auto ws_fn = NSA_FN(nsa_layer_decode_ragged_workspace);
+    struct Case {
+        int B = 3, S = 8, D = 64, dim = 768, S_max = 1072, t_max = 1059, dtype = NSA_DT_BF16;
+        const int32_t *t_pos = nullptr;
+        bool with_ws = true;
+    };
+    auto positions = [](const char *launcher, int arg, size_t bytes, const char *key, std::function<std::string(const void *)> print) {
+        return Want{std::string(launcher) + " launch", arg, bytes, key, std::move(print)};
+    };
+    auto rope = [](const void *b) {
+        nsa::RopeAppendParams P;
+        memcpy(&P, b, sizeof(P));
+        return Obj().p("t_pos", P.t_pos).i("t_max", P.t_max).i("t0", P.t0).i("B", P.B).i("S", P.S).i("S_max", P.S_max).p("Q_out", P.Q_out).str();
+    };
+    auto pool = [](const void *b) {
+        nsa::CmpPoolParams P;
+        memcpy(&P, b, sizeof(P));
+        return Obj().p("t_pos", P.t_pos).i("t_max", P.t_max).i("S", P.S).i("G", P.G).i("nbg", P.nbg).i("S_max", P.S_max).i("n_cmp_max", P.n_cmp_max).str();
+    };
+    auto step = [](const void *b) {
+        nsa::DecStepParams P;
+        memcpy(&P, b, sizeof(P));
+        return Obj().p("t_pos", P.t_pos).i("t_max", P.t_max).i("S", P.S).i("R", P.R).i("S_cmp", P.S_cmp).i("nchunk", P.nchunk).str();
+    };
+    auto band = [](const void *b) {
+        nsa::BandAttnParams P;
+        memcpy(&P, b, sizeof(P));
+        return Obj().p("t_pos", P.t_pos).i("t_max", P.t_max).i("t0", P.t0).i("S_kv", P.S_kv).i("nsplit", P.nsplit).i("defer_combine", P.defer_combine).p("K", P.K).str();
+    };
+    const std::vector<Want> wants = {
+        positions("qkv_rope_append(rows, mfma)", 0, sizeof(nsa::RopeAppendParams), "rope", rope),
+        positions("qkv_rope_append(rows)", 5, sizeof(nsa::RopeAppendParams), "rope", rope),
+        positions("cmp_pool(ragged)", 0, sizeof(nsa::CmpPoolParams), "pool", pool),
+        positions("decode_rows", 0, sizeof(nsa::DecStepParams), "step", step),
+        positions("band_attn_fwd_dual", 0, sizeof(nsa::BandAttnParams), "band_w", band),
+        positions("band_attn_fwd_dual", 1, sizeof(nsa::BandAttnParams), "band_c", band),
+        positions("band_attn_fwd(split)", 0, sizeof(nsa::BandAttnParams), "band", band),
+    };
+    auto layer_case = [&](const char *label, const std::function<void(Case &)> &tweak) {
+        Case c;
+        c.t_pos = t_pos + 5;
+        tweak(c);
+        nsa_layer_desc L{};
+        L.dim = c.dim; L.G = 2; L.h = 6; L.Dk = L.Dv = c.D; L.l = 32; L.d = 16; L.l_sel = 64; L.n_sel = 16; L.w = 512; L.gate_hidden = 32; L.dtype = c.dtype;
+        L.rope_base = 10000.f; L.rope_scale = 1.f; L.gate_tau = 1.f;
+        L.W_qkv = W_qkv; L.W_out = W_out; L.gate_w1 = L.gate_b1 = L.gate_w2 = L.gate_b2 = gw;
+        nsa_kv_desc kv{};
+        kv.K_sel = cache[0]; kv.V_sel = cache[1]; kv.K_win = cache[2]; kv.V_win = cache[3]; kv.K_raw = cache[4]; kv.V_raw = cache[5]; kv.K_cmp = cache[6];
+        kv.V_cmp = cache[7];
+        kv.B = c.B; kv.S_max = c.S_max; kv.n_cmp_max = (c.S_max - 32) / 16 + 1;
+        const int te = c.t_max < c.S_max - 1 ? c.t_max : c.S_max - 1, S_sel = (te + 64) / 64;
+        run_args(std::string("layer_decode_ragged/") + label, [&] {
+            return fn(&L, &kv, x, y, c.t_pos, c.t_max, c.S, nullptr, nullptr, nullptr, S_sel, ranges, gates, c.with_ws ? ws : nullptr, c.with_ws ? 64 * MB : 0, nullptr);
+        }, wants);
+        int launches = -7, route = -7;
+        const int prc = plan_fn(&L, c.B, c.S, c.S_max, c.t_max, S_sel, &launches, &route);
+        printf(",\n%s: %s", quoted(std::string("layer_decode_ragged/") + label + "_plan").c_str(),
+               Obj().i("rc", prc).i("launches", launches).i("route", route).i("workspace", (long long)ws_fn(&L, c.B, c.S, c.S_max)).str().c_str());
+    };
+    layer_case("m7c_B3_S8", [](Case &) {});
+    layer_case("m7c_B3_S8_no_token_due", [](Case &c) { c.t_max = 1063; });
+    layer_case("m7c_B16_S1", [](Case &c) { c.B = 16; c.S = 1; });
+    layer_case("m7c_B1_S2_chunk_loop", [](Case &c) { c.B = 1; c.S = 2; });
+    layer_case("D128_B3_S4", [](Case &c) { c.D = 128; c.dim = 1536; c.S = 4; });
+    layer_case("t_max_beyond_capacity", [](Case &c) { c.t_max = 5000; });
+    layer_case("t_max_below_S", [](Case &c) { c.t_max = 3; });  // nobody can be live: planned from position 0, never a negative one
+    layer_case("f32_declined", [](Case &c) { c.dtype = NSA_DT_F32; });
+    layer_case("t_max70000_declined", [](Case &c) { c.S_max = 131072; c.t_max = 70000; });
+    layer_case("D128_t_max20000_declined", [](Case &c) { c.D = 128; c.dim = 1536; c.S_max = 32768; c.t_max = 20000; });
+    layer_case("S17_refused", [](Case &c) { c.S = 17; });
+    layer_case("null_t_pos", [](Case &c) { c.t_pos = nullptr; });
+    layer_case("t_pos_2_bytes_off", [&](Case &c) { c.t_pos = (const int32_t *)off(t_pos, 2); });
+    layer_case("no_workspace", [](Case &c) { c.with_ws = false; });
+    NSA_FN(nsa_hip_set_tuning)("DECODE_UNFUSED", 1);
+    layer_case("DECODE_UNFUSED_1_declined", [](Case &) {});
+    NSA_FN(nsa_hip_set_tuning)("DECODE_UNFUSED", -1);
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: dispatch_check <libnsa_sel_hip.so> [ragged]\n");
+        fprintf(stderr, "usage: dispatch_check <libnsa_sel_hip.so> [ragged | layer_ragged]\n");
         return 2;
     }
     g_lib = dlopen(argv[1], RTLD_NOW | RTLD_GLOBAL);
@@ -515,6 +613,12 @@ int main(int argc, char **argv) {
     if (argc >= 3 && !strcmp(argv[2], "ragged")) {  // the cases of the ragged entry points alone (tests/test_dispatch_ragged_host.py)
         printf("{");
         ragged_cases();
+        printf("\n}\n");
+        return 0;
+    }
+    if (argc >= 3 && !strcmp(argv[2], "layer_ragged")) {  // the layer's ragged call alone (tests/test_layer_decode_ragged_host.py)
+        printf("{");
+        layer_ragged_cases();
         printf("\n}\n");
         return 0;
     }

@@ -227,6 +227,17 @@ struct RopeDest {
     }
 };
 
+// ragged rows form (P.t_pos): the position of sequence b's first row and whether the sequence is live.  Not live: a padding slot (negative
+// position) or rows past the caller's bound / the cache capacity; such a sequence appends nothing.  No silent clamp.
+struct RopeSeq {
+    int t0;
+    bool live;
+};
+__device__ __forceinline__ RopeSeq rope_seq(const RopeAppendParams &P, int b) {
+    const int t0 = P.t_pos[b];
+    return RopeSeq{t0, t0 >= 0 && t0 <= min(P.t_max, P.S_max - 1) - (P.S - 1)};
+}
+
 // rows form (S consecutive tokens per sequence: row m = b S + s of the projection sits at position t0 + s): the destination of a column pair.
 // The rotation of (pair, s) is the single step's rope_sincos call at (float)(t0 + s), evaluated by whoever owns that pair of values.
 template <typename T>
@@ -252,6 +263,21 @@ struct RopeRowsDest {
     __device__ __forceinline__ void store(int b, int s, float sn, float cs, float x0, float x1) const {
         if (rot) rope_rotate<T>(x0, x1, sn, cs, x0, x1);
         T *d = dst + b * sb + s * ss;
+        d[0] = Elt<T>::from_f(x0);
+        d[1] = Elt<T>::from_f(x1);
+    }
+    // ---- ragged form (P.t_pos; P.t0 = 0, so dst is row 0 of the tensor): the sequence's own position
+    __device__ __forceinline__ void sincos_at(const RopeAppendParams &P, int pos, float &sn, float &cs) const {
+        sn = 0.f;
+        cs = 1.f;
+        if (rot) rope_sincos<T>(ri, rD, (float)pos, P.rope_base, P.inv_scale, sn, cs);
+    }
+    // q: the pair belongs to Q_out [B,S,NQ] (row s, written for every row); else to a cache tensor: row sq.t0 + s, and only of a live
+    // sequence -- the one guard between a wrong position and the neighbouring slab
+    __device__ __forceinline__ void store_at(bool q, int b, int s, const RopeSeq &sq, float sn, float cs, float x0, float x1) const {
+        if (!q && !sq.live) return;
+        if (rot) rope_rotate<T>(x0, x1, sn, cs, x0, x1);
+        T *d = dst + b * sb + (int64_t)(q ? s : sq.t0 + s) * ss;
         d[0] = Elt<T>::from_f(x0);
         d[1] = Elt<T>::from_f(x1);
     }
@@ -435,6 +461,47 @@ struct RopeRowsEpi {
     }
 };
 
+// RopeRaggedEpi (CW = 2, chunk loop): RopeRowsEpi with per-sequence positions (P.t_pos), row m = b S + s appended at t_pos[b] + s where the
+// sequence is live.  The wave's pair has one rotation per (b, s) now: lane m evaluates that of row m for the first 64 rows (the route
+// hands the chunk loop the calls of one or two rows), lane 0 evaluates a later row's when it stores it.  The scalar form keeps its table.
+template <typename T>
+struct RopeRaggedEpi {
+    static constexpr int MIN_BLOCKS = 2, GROUP = 2;
+    static constexpr int TABLE = 64;
+    RopeAppendParams P;
+    struct Wave {
+        RopeRowsDest<T> rd;
+        bool q;
+        const float *sc;  // [min(B S, 64)][2]: (sin, cos) of row m's position
+    };
+    __device__ __forceinline__ Wave init(int n0) const {
+        __shared__ float sc[4][TABLE][2];
+        Wave w;
+        w.rd.init(P, n0);
+        w.q = n0 < P.G * P.h * P.Dk;
+        const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
+        if (lane < P.B * P.S) {
+            const int b = lane / P.S;
+            w.rd.sincos_at(P, P.t_pos[b] + (lane - b * P.S), sc[wave][lane][0], sc[wave][lane][1]);
+        }
+        wave_lds_fence();
+        w.sc = &sc[wave][0][0];
+        return w;
+    }
+    __device__ __forceinline__ void store(const Wave &w, int m, int, const float (&s)[2]) const {
+        const int b = m / P.S, si = m - b * P.S;
+        const RopeSeq sq = rope_seq(P, b);
+        float sn, cs;
+        if (m < TABLE) {
+            sn = w.sc[2 * m];
+            cs = w.sc[2 * m + 1];
+        } else {
+            w.rd.sincos_at(P, sq.t0 + si, sn, cs);
+        }
+        w.rd.store_at(w.q, b, si, sq, sn, cs, rnd<T>(s[0]), rnd<T>(s[1]));
+    }
+};
+
 // chunk-loop form (any dtype, K and alignment): k in 512-element chunks, rows of A in passes of 8 (CW = 4: at most 2 rows, one pass).  The
 // loads of one k chunk are waited for before the next goes out.
 template <typename T, int CW, typename AOp, typename Epi>
@@ -551,12 +618,15 @@ struct LinearMixArgs {
 // NWV = waves of a workgroup that split the K axis: 4, or 8 for long rows (K >= 2048: fc2 of the MLP) -- a wave's k-steps go out in
 // rounds of 6, each round a memory round trip, so K = 3072 on 4 waves was four of them in a row (15.5 us at 32 rows, 8.5 for fc1)
 // ROWS (with ROPE): P.S <= 16 consecutive tokens per sequence, row m = b P.S + s appended at position P.t0 + s (RopeRowsDest)
-template <typename T, bool ROPE, bool MIX = false, int NWV = 4, bool ROWS = false>
+// RAGGED (with ROWS): at position P.t_pos[b] + s, the cache rows of a live sequence only (rope_seq).  A template flag: the scalar
+// instantiations keep their code
+template <typename T, bool ROPE, bool MIX = false, int NWV = 4, bool ROWS = false, bool RAGGED = false>
 __global__ __launch_bounds__(NWV * 64, 2) void linear_mfma_kernel(RopeAppendParams P, const T *__restrict__ X, const T *__restrict__ W,
                                                                T *__restrict__ out, int M, int N, int K, int epi, const T *__restrict__ res,
                                                                LinearMixArgs mx) {
     static_assert(NWV == 4 || (NWV == 8 && !ROPE && !MIX), "eight waves: the plain projection only");
     static_assert(!ROWS || ROPE, "rows form: the RoPE + append epilogue only");
+    static_assert(!RAGGED || ROWS, "ragged form: the rows epilogue only");
     using MT_ = MfmaT<T>;
     using x8 = typename MT_::x8;
     __shared__ float part[NWV][16][65];
@@ -582,8 +652,20 @@ __global__ __launch_bounds__(NWV * 64, 2) void linear_mfma_kernel(RopeAppendPara
     // sincosf) while the loads are in flight and pass it through LDS; every thread then needs only the destinations of its two pairs
     // ROWS: one rotation per (pair, s), 8 P.S <= 128 values: thread 8 s + pair evaluates one, entry [8 s + pair]
     [[maybe_unused]] std::conditional_t<ROWS, RopeRowsDest<T>, RopeDest<T>> rd[2];
-    __shared__ float rsc[ROWS ? 128 : 8][2];
-    if constexpr (ROWS) {
+    __shared__ float rsc[ROWS && !RAGGED ? 128 : 8][2];
+    // RAGGED: a rotation per (pair, b, s) -- up to 64 sequences under one workgroup, too many for a table: the thread that stores row
+    // m = m0 + t % 64 evaluates the rotations of its own two pairs at t_pos[b] + s here, before the loads go out (one position load each)
+    [[maybe_unused]] RopeSeq sq{0, false};
+    [[maybe_unused]] float rsn[2], rcs[2];
+    if constexpr (RAGGED) {
+        const int mr = min(m0 + (int)(threadIdx.x & 63), M - 1), b = mr / P.S;
+        sq = rope_seq(P, b);
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            rd[p].init(P, min(n0 + 4 * (int)(threadIdx.x >> 6) + 2 * p, N - 2));
+            rd[p].sincos_at(P, sq.t0 + (mr - b * P.S), rsn[p], rcs[p]);
+        }
+    } else if constexpr (ROWS) {
         if ((int)threadIdx.x < 8 * P.S) {
             RopeRowsDest<T> one;
             one.init(P, min(n0 + 2 * (int)(threadIdx.x & 7), N - 2));
@@ -682,7 +764,10 @@ __global__ __launch_bounds__(NWV * 64, 2) void linear_mfma_kernel(RopeAppendPara
 #pragma unroll
         for (int p = 0; p < 2; ++p)
             if (n0 + 4 * nq + 2 * p < N) {
-                if constexpr (ROWS) {
+                if constexpr (RAGGED) {
+                    const int b = m / P.S;
+                    rd[p].store_at(n0 + 4 * nq + 2 * p < P.G * P.h * P.Dk, b, m - b * P.S, sq, rsn[p], rcs[p], rnd<T>(v[2 * p]), rnd<T>(v[2 * p + 1]));
+                } else if constexpr (ROWS) {
                     const int b = m / P.S, s = m - b * P.S, e = 8 * s + 2 * nq + p;  // (the entry of this row's position)
                     rd[p].store(b, s, rsc[e][0], rsc[e][1], rnd<T>(v[2 * p]), rnd<T>(v[2 * p + 1]));
                 } else {
@@ -741,11 +826,11 @@ static void launch_proj_valu(const ProjRoute &r, const LinearCall &c, const AOp 
     }
     if constexpr (std::is_same_v<AOp, RowsA<T>>) go(proj_loop_kernel<T, CW, AOp, Epi>);
 }
-template <bool ROPE, bool MIX, int NWV, bool ROWS>
+template <bool ROPE, bool MIX, int NWV, bool ROWS, bool RAGGED = false>
 static void launch_linear_mfma(const RopeAppendParams &P, const ProjRoute &r, const LinearCall &c) {
     with_elt<false>(c.dtype, [&](auto t) {
         using T = decltype(t);
-        hipLaunchKernelGGL((linear_mfma_kernel<T, ROPE, MIX, NWV, ROWS>), r.grid, dim3(NWV * 64), 0, c.st, P, (const T *)c.A, (const T *)c.W, (T *)c.out, c.M,
+        hipLaunchKernelGGL((linear_mfma_kernel<T, ROPE, MIX, NWV, ROWS, RAGGED>), r.grid, dim3(NWV * 64), 0, c.st, P, (const T *)c.A, (const T *)c.W, (T *)c.out, c.M,
                            c.N, c.K, c.epi, (const T *)c.res, LinearMixArgs{c.Os, c.Ow, c.gates, c.G});
     });
 }
@@ -798,10 +883,13 @@ int launch_linear_small_mix(const LinearCall &c) {
 // c.N = the columns P maps (qkv_cols); c.norm_w: RMSNorm(c.A) folded in where the caller read fold_norm from this call's route
 int launch_qkv_rope_append(const RopeAppendParams &P, const LinearCall &c, bool rows) {
     NSA_CHECK_ARG(P.S >= 1 && P.S <= RopeRowsEpi<float>::MAX_S, "qkv_rope_append: 1 to 16 tokens per sequence");
+    const bool ragged = P.t_pos != nullptr;  // per-sequence positions: the RAGGED instantiations of the rows forms
+    NSA_CHECK_ARG(!ragged || (rows && P.t0 == 0), "qkv_rope_append: a position array goes with the rows form and t0 = 0");
     const ProjRoute r = proj_route(c, rows ? PROJ_ROPE_ROWS : PROJ_ROPE);
     if (r.form == PROJ_MFMA) {
         if (rows) {
-            launch_linear_mfma<true, false, 4, true>(P, r, c);
+            if (ragged) launch_linear_mfma<true, false, 4, true, true>(P, r, c);
+            else launch_linear_mfma<true, false, 4, true>(P, r, c);
             NSA_LAUNCH_CHECK("qkv_rope_append(rows, mfma)");
         } else {
             launch_linear_mfma<true, false, 4, false>(P, r, c);
@@ -812,7 +900,8 @@ int launch_qkv_rope_append(const RopeAppendParams &P, const LinearCall &c, bool 
     with_elt(c.dtype, [&](auto t) {
         using T = decltype(t);
         const RowsA<T> a{(const T *)c.A, (const T *)c.norm_w, c.eps};
-        if (rows) launch_proj_valu<T, 2>(r, c, a, RopeRowsEpi<T>{P});
+        if (ragged) launch_proj_valu<T, 2>(r, c, a, RopeRaggedEpi<T>{P});
+        else if (rows) launch_proj_valu<T, 2>(r, c, a, RopeRowsEpi<T>{P});
         else launch_proj_valu<T, 2, 2, 4>(r, c, a, RopeEpi<T>{P});
     });
     if (rows) NSA_LAUNCH_CHECK("qkv_rope_append(rows)");
@@ -878,14 +967,27 @@ __global__ __launch_bounds__(64) void cmp_pool_kernel(CmpPoolParams P) {
 // l x (powf + sincosf) in a row, 24 us for the ONE token a decode step emits): rotated keys and raw values go to LDS, then one thread per
 // column sums them in the original order i = 0 .. l-1 -- the same fp32 additions, the same bits.  (Sharing a rotation between the (b, g)
 // pairs of a block -- it depends on position and pair only -- was tried: fewer, serial blocks, 30 -> 45 us at 4k x 8.)
-template <typename T>
+// RAGGED (launch_cmp_pool_ragged): ceil(S / d) blocks per (b, g); block k takes token n_cmp(t_pos[b]) + k and leaves -- the whole block, before
+// the barrier -- unless the sequence is live and emits that token inside its S rows.  A template flag: the scalar kernel keeps its code.
+template <typename T, bool RAGGED = false>
 __global__ __launch_bounds__(256) void cmp_pool_wide_kernel(CmpPoolParams P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *rk = (float *)smem;    // [l][Dk] rotated raw keys
     float *rv = rk + P.l * P.Dk;  // [l][Dv] raw values
-    const int nj = P.j1 - P.j0;
-    const int j = P.j0 + (int)(blockIdx.x % nj);
-    const int bg = (int)(blockIdx.x / nj);
+    int j, bg;
+    if constexpr (RAGGED) {
+        const int per = (P.S + P.d - 1) / P.d;
+        bg = (int)(blockIdx.x / per);
+        const int t0 = P.t_pos[bg / P.G];  // tokens the sequence holds before the call (one scalar load: bg is uniform)
+        if (t0 < 0 || t0 > min(P.t_max, P.S_max - 1) - (P.S - 1)) return;
+        auto ncmp = [&](int n) { return n < P.l ? 0 : (n - P.l) / P.d + 1; };  // compressed tokens of n cached ones (ncmp_of)
+        j = ncmp(t0) + (int)(blockIdx.x - bg * per);
+        if (j >= ncmp(t0 + P.S) || j >= P.n_cmp_max) return;
+    } else {
+        const int nj = P.j1 - P.j0;
+        j = P.j0 + (int)(blockIdx.x % nj);
+        bg = (int)(blockIdx.x / nj);
+    }
     const T *Kr = (const T *)P.K_raw + (int64_t)bg * P.S_max * P.Dk;
     const T *Vr = (const T *)P.V_raw + (int64_t)bg * P.S_max * P.Dv;
     T *Kc = (T *)P.K_cmp + ((int64_t)bg * P.n_cmp_max + j) * P.Dk;
@@ -929,6 +1031,19 @@ int launch_cmp_pool(const CmpPoolParams &P, int dtype, hipStream_t st) {
     }
     with_elt(dtype, [&](auto t) { hipLaunchKernelGGL(cmp_pool_kernel<decltype(t)>, dim3((unsigned)nblk), dim3(64), 0, st, P); });
     NSA_LAUNCH_CHECK("cmp_pool");
+    return NSA_OK;
+}
+
+// the wide form only (the few tokens of a decode call): declined where its LDS bound fails
+int launch_cmp_pool_ragged(const CmpPoolParams &P, int dtype, hipStream_t st) {
+    NSA_CHECK_ARG(P.t_pos && P.S >= 1 && P.G >= 1 && P.d >= 1 && P.nbg % P.G == 0, "cmp_pool(ragged): positions, S >= 1 and whole sequences");
+    const int64_t nblk = (int64_t)P.nbg * ((P.S + P.d - 1) / P.d);
+    if (nblk <= 0) return NSA_OK;
+    const size_t lds = sizeof(float) * (size_t)P.l * (size_t)(P.Dk + P.Dv);
+    NSA_CHECK_ARG(lds <= 48 * 1024 && P.Dk % 2 == 0 && nblk < ((int64_t)1 << 31),
+                  "cmp_pool(ragged): the wide form holds l (Dk + Dv) floats in 48 KiB of LDS (l = %d, Dk = %d, Dv = %d)", P.l, P.Dk, P.Dv);
+    with_elt(dtype, [&](auto t) { hipLaunchKernelGGL((cmp_pool_wide_kernel<decltype(t), true>), dim3((unsigned)nblk), dim3(256), lds, st, P); });
+    NSA_LAUNCH_CHECK("cmp_pool(ragged)");
     return NSA_OK;
 }
 

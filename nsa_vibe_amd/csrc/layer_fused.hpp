@@ -11,12 +11,21 @@ struct RopeAppendParams {
     void *cache[6];    // K_sel, V_sel, K_win, V_win, K_raw, V_raw: [B,G,S_max,D] contiguous
     int B, S, G, h, Dk, Dv, S_max, t0;
     float rope_base, inv_scale;
+    // ragged form of the rows epilogue (nsa_layer_decode_ragged): device [B] positions or null; with it row (b, s) is rotated at and
+    // appended to position t_pos[b] + s (t0 = 0), and a sequence with t_pos[b] < 0 or t_pos[b] + S - 1 > min(t_max, S_max - 1) writes
+    // NO cache row (rope_seq); Q_out is written for every row
+    const int32_t *t_pos;
+    int t_max;
 };
 struct CmpPoolParams {
     const void *K_raw, *V_raw;  // [nbg, S_max, D]
     void *K_cmp, *V_cmp;        // [nbg, n_cmp_max, D]
     int nbg, S_max, n_cmp_max, Dk, Dv, l, d, j0, j1;
     float rope_base, inv_scale;
+    // ragged form (launch_cmp_pool_ragged): device [nbg / G] positions; sequence b emits the tokens whose windows complete inside its S
+    // rows t_pos[b] .. t_pos[b] + S - 1 (j0 / j1 unused), a sequence that is not live (as above) none
+    const int32_t *t_pos;
+    int t_max, S, G;
 };
 struct GateCombineParams {
     const void *Q, *O_cmp, *O_sel, *O_win;
@@ -66,7 +75,8 @@ struct ProjRoute {
 };
 ProjRoute proj_route(const LinearCall &c, ProjKind kind);
 // epilogue of the fused QKV projection: every column pair rotated and appended at its row's position.  rows: P.S (1 to 16) consecutive
-// tokens per sequence, row b P.S + s of c.A at position P.t0 + s (the layer's rows call; false: P.S = 1, the single step)
+// tokens per sequence, row b P.S + s of c.A at position P.t0 + s (the layer's rows call; false: P.S = 1, the single step); with P.t_pos the
+// rows form's ragged instantiations (position P.t_pos[b] + s, cache stores predicated on the sequence being live)
 int launch_qkv_rope_append(const RopeAppendParams &P, const LinearCall &c, bool rows);
 int launch_linear_small_epi(const LinearCall &c);
 // c.norm_w set: one launch where the route folds the norm, else RMSNorm(A) into scratch [M,K] and the projection from there
@@ -84,6 +94,9 @@ int launch_rmsnorm_rows_bwd(const void *x, const void *w, const void *dy, void *
                             void *workspace, size_t workspace_bytes, hipStream_t st);
 int launch_rope_cache_append(const RopeAppendParams &P, int dtype, hipStream_t st);
 int launch_cmp_pool(const CmpPoolParams &P, int dtype, hipStream_t st);
+// per-sequence positions (P.t_pos): nbg ceil(S / d) blocks of the wide form, launched whether or not a window completes (the host never
+// reads the positions); block (bg, k) takes token n_cmp(t_pos[b]) + k and leaves where its sequence does not emit it
+int launch_cmp_pool_ragged(const CmpPoolParams &P, int dtype, hipStream_t st);
 int launch_rope_cache_append_bwd(const RopeAppendParams &P, int dtype, hipStream_t st);
 int launch_cmp_pool_bwd(const CmpPoolParams &P, const void *dKc, const void *dVc, void *dKr, void *dVr, int S, int n_cmp, int dtype,
                         hipStream_t st);

@@ -281,6 +281,13 @@ struct LayerDecode {
     unsigned char *ws;
     void *Q, *Ocmp, *Osel, *Owin, *Omix;
     int S, t0, n0, n1;  // n0 / n1: compressed tokens emitted before the rows (n_cmp(t0 - 1)) and after them (n_cmp(t0 + S - 1))
+    // ragged call (nsa_layer_decode_ragged): the device positions and te = min(t_max, S_max - 1), the last token a live row can sit at.
+    // Then the launches are planned for the LARGEST sequence there can be: te + 1 tokens after the call (tokens()), n1 = n_cmp(te)
+    // compressed ones, t0 = max(0, te + 1 - S) (never negative: with te < S - 1 no sequence is live and every row is a zero row); every
+    // kernel takes its rows' positions from t_pos
+    const int32_t *t_pos;
+    int te;
+    int tokens() const { return t_pos ? te + 1 : t0 + S; }  // tokens the caches hold after the call (of the largest sequence)
 };
 constexpr int LAYER_ROWS_MAX_S = 16;
 
@@ -313,7 +320,7 @@ struct BandBranches {
     Band bw, bc;
 };
 static BandBranches band_branches(const LayerDecode &D, const CacheStrides &C, void *stream) {
-    return BandBranches{sliding_call(D.L, D.kv, C, D.Q, D.Owin, D.S, D.t0 + D.S, D.ws + D.W.band, D.W.band_bytes, stream),
+    return BandBranches{sliding_call(D.L, D.kv, C, D.Q, D.Owin, D.S, D.tokens(), D.ws + D.W.band, D.W.band_bytes, stream),
                         compressed_call(D.L, D.kv, C, D.Q, D.Ocmp, D.S, D.n1, D.ws + D.W.band2, D.W.band_bytes, stream), sliding_band(D.t0, D.L->w),
                         compressed_band(D.t0, D.L->l, D.L->d)};
 }
@@ -328,6 +335,11 @@ static bool band_pair(const LayerDecode &D, const CacheStrides &C, int defer, De
     BP.w.part = (float *)b.w.ws; BP.c.part = (float *)b.c.ws;
     BP.w.nsplit = BP.c.nsplit = rw.nsplit;
     BP.w.defer_combine = BP.c.defer_combine = 1;
+    if (D.t_pos) {  // the ragged call: every sequence at its own position (the launch's t0 is not read)
+        BP.w.t_pos = BP.c.t_pos = D.t_pos;
+        BP.w.t_max = BP.c.t_max = D.te;
+        BP.w.t0 = BP.c.t0 = 0;
+    }
     return true;
 }
 
@@ -372,6 +384,11 @@ static int layer_decode_tail(const LayerDecode &D, const CacheStrides &C, Decode
         F.ns[2] = F.ns[0] = BP->w.nsplit;
         F.part[2] = BP->w.part;
         F.part[0] = BP->c.part;
+    } else if (D.t_pos) {  // the ragged call: one ragged launch each, combined by the branch itself (O final)
+        const BandBranches b = band_branches(D, C, stream);
+        if (int rc = band_attn_fwd_ragged_impl(b.w, b.bw, D.t_pos, D.te)) return rc;
+        if (int rc = band_attn_fwd_ragged_impl(b.c, b.bc, D.t_pos, D.te)) return rc;
+        F.ns[2] = F.ns[0] = 1;
     } else {
         const BandBranches b = band_branches(D, C, stream);
         if (int rc = band_attn_fwd_impl(b.w, b.bw, defer, &F.ns[2])) return rc;
@@ -526,6 +543,117 @@ int nsa_layer_decode_rows_plan(const nsa_layer_desc *L, int B, int S, int S_max,
     *launches = n;
     *route = r;
     return NSA_OK;
+}
+
+// ------------------------------------------------------------------------------ ragged-batch layer decode: per-sequence positions
+// What the call and its plan share, from the shape, the host bound and the switches alone (aligned caches of capacity S_max assumed; the
+// position array is never read on the host).  NSA_OK with *launches = n: the call runs; *launches = 0 and *why = the limit: DECLINED --
+// there is no scalar route to stand in (every other launch of the layer takes one position per call); an error status: bad arguments.
+static int layer_decode_ragged_route(const char *who, const nsa_layer_desc *L, int B, int S, int S_max, int t_max, int S_sel, int n_cmp_max,
+                                     int *launches, const char **why) {
+    *launches = 0;
+    *why = nullptr;
+    if (int rc = check_layer(L, who)) return rc;
+    NSA_CHECK_ARG(S >= 1 && S <= LAYER_ROWS_MAX_S, "%s: 1 to %d tokens per sequence (got %d)", who, LAYER_ROWS_MAX_S, S);
+    NSA_CHECK_ARG(B >= 1 && S_max >= 1, "%s: bad cache sizes", who);
+    NSA_CHECK_ARG(t_max >= 0, "%s: t_max (the host bound of t_pos[b] + S - 1) must not be negative", who);
+    const int te = std::min(t_max, S_max - 1);  // no live row sits beyond te
+    NSA_CHECK_ARG(S_sel >= 1 && (int64_t)S_sel * L->l_sel >= (int64_t)te + 1, "%s: block metadata (S_sel=%d) does not cover %d tokens", who, S_sel, te + 1);
+    NSA_CHECK_ARG(n_cmp_max < 0 || n_cmp_max >= ncmp_of(te + 1, L->l, L->d), "%s: compressed cache too small (n_cmp_max=%d) for %d tokens", who, n_cmp_max,
+                  te + 1);
+    if (!(L->dtype == NSA_DT_BF16 || L->dtype == NSA_DT_F16)) {
+        *why = "bf16 / f16 only (the launches that take per-sequence positions have no fp32 form)";
+        return NSA_OK;
+    }
+    if (!(L->Dk == L->Dv && (L->Dk == 64 || L->Dk == 128) && L->l == 32 && L->d == 16 && L->l_sel == 64)) {
+        *why = "Dk = Dv in {64, 128} and the default block geometry only (l = 32, d = 16, l' = 64)";
+        return NSA_OK;
+    }
+    nsa_kv_desc kv{};  // stands in for aligned caches: the predicates below read the sizes and the pointers' alignment only
+    kv.K_sel = kv.V_sel = kv.K_win = kv.V_win = kv.K_raw = kv.V_raw = kv.K_cmp = kv.V_cmp = (void *)(uintptr_t)256;
+    kv.B = B; kv.S_max = S_max; kv.n_cmp_max = std::max(1, ncmp_of(S_max, L->l, L->d));
+    const CacheStrides C(L, &kv);
+    const int t0 = std::max(0, te + 1 - S), n1 = ncmp_of(te + 1, L->l, L->d);
+    SelDecodeCall sc = sel_decode_call(L, &kv, C, S, t0, n1, S_sel);
+    sc.S_kv = te + 1;
+    if (!decode_ragged_shape_plan(sc, te, nullptr, nullptr, why)) return NSA_OK;
+    *why = nullptr;
+    DecBandPair BP{};  // (an undeferred split branch adds its combine: not counted)
+    const bool dual = band_pair(LayerDecode{L, &kv, DecodeWs{}, nullptr, kv.K_sel, kv.K_sel, kv.K_sel, kv.K_sel, kv.K_sel, S, t0, 0, n1, (const int32_t *)kv.K_sel, te}, C,
+                                L->Dv == 64 ? 1 : 0, BP);
+    // projection + RoPE + append, pooling (always: the host cannot know whether a window completes), the selected branch's one launch,
+    // the band pair (or one launch each), finish (or gate + mix), output projection
+    *launches = 3 + (dual ? 1 : 2) + 2;
+    return NSA_OK;
+}
+
+size_t nsa_layer_decode_ragged_workspace(const nsa_layer_desc *L, int B, int S, int S_max) { return nsa_layer_decode_rows_workspace(L, B, S, S_max); }
+
+int nsa_layer_decode_ragged_plan(const nsa_layer_desc *L, int B, int S, int S_max, int t_max, int S_sel, int *launches, int *route) {
+    NSA_CHECK_ARG(launches && route, "layer_decode_ragged_plan: null pointer");
+    *launches = 0;
+    *route = -1;
+    int n = 0;
+    const char *why = nullptr;
+    if (int rc = layer_decode_ragged_route("layer_decode_ragged_plan", L, B, S, S_max, t_max, S_sel, -1, &n, &why)) return rc;
+    if (why) return NSA_OK;  // declined
+    *launches = n;
+    *route = 1;
+    return NSA_OK;
+}
+
+int nsa_layer_decode_ragged(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *x, void *y, const int32_t *t_pos, int t_max, int S,
+                            const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out, float *gates_out,
+                            void *workspace, size_t workspace_bytes, void *stream) {
+    const char *who = "layer_decode_ragged";
+    if (int rc = check_layer(L, who)) return rc;
+    if (int rc = check_kv(kv, who)) return rc;
+    NSA_CHECK_ARG(x && y && L->W_qkv && L->W_out, "%s: null pointer", who);
+    NSA_CHECK_ARG(t_pos, "%s: null position array t_pos", who);
+    NSA_CHECK_ARG((uintptr_t)t_pos % 4 == 0, "%s: t_pos must be 4-byte aligned", who);
+    int n = 0;
+    const char *why = nullptr;
+    if (int rc = layer_decode_ragged_route(who, L, kv->B, S, kv->S_max, t_max, S_sel, kv->n_cmp_max, &n, &why)) return rc;
+    const int te = std::min(t_max, kv->S_max - 1);
+    NSA_CHECK_ARG(!why, "%s: %s (B = %d, S = %d, D = %d, t_max = %d)", who, why, kv->B, S, L->Dk, t_max);
+    // the largest sequence the launches are planned for: te + 1 tokens after the call, n1 compressed ones (LayerDecode)
+    const int t0 = std::max(0, te + 1 - S), n1 = ncmp_of(te + 1, L->l, L->d);
+    const CacheStrides C(L, kv);
+    SelDecodeCall probe = sel_decode_call(L, kv, C, S, 0, n1, S_sel);
+    probe.S_kv = te + 1;
+    probe.Q = probe.O = kv->K_cmp;  // (Q and O come from the 256-byte aligned workspace)
+    NSA_CHECK_ARG(decode_ragged_operands_ok(probe) && (uintptr_t)kv->K_cmp % 16 == 0,
+                  "%s: K_cmp, K_sel and V_sel must be 16-byte aligned with strides in multiples of 8 elements", who);
+    const DecodeWs W = decode_ws(L, kv->B, kv->S_max, S);
+    if (int rc = check_workspace(who, workspace, workspace_bytes, W.total)) return rc;
+    unsigned char *ws = (unsigned char *)workspace;
+    const LayerDecode D{L, kv, W, ws, ws + W.q, ws + W.ocmp, ws + W.osel, ws + W.owin, ws + W.omix, S, t0, 0, n1, t_pos, te};
+    SelDecodeCall c = layer_sel_call(D, C, csc_ptr, csc_rows, csc_vals, S_sel, ranges_out);
+    c.t0 = 0;  // as nsa_sel_decode_ragged hands it over: every row's token comes from t_pos
+    c.S_kv = te + 1;
+    hipStream_t st = (hipStream_t)stream;
+    // 1. fused QKV projection of the B S rows, row (b, s) rotated at t_pos[b] + s and appended there where sequence b is live
+    RopeAppendParams R = rope_append_params(L, kv, ws + W.proj, D.Q, S, 0);
+    R.t_pos = t_pos;
+    R.t_max = te;
+    if (int rc = launch_qkv_rope_append(R, qkv_call(L, x, kv->B * S, nullptr, 0.f, stream), true)) return rc;
+    // 2. every live sequence's compressed tokens whose windows complete inside its rows (launched every call: its blocks exit where none does)
+    CmpPoolParams P{};
+    P.K_raw = kv->K_raw; P.V_raw = kv->V_raw; P.K_cmp = kv->K_cmp; P.V_cmp = kv->V_cmp;
+    P.nbg = kv->B * L->G; P.S_max = kv->S_max; P.n_cmp_max = kv->n_cmp_max; P.Dk = L->Dk; P.Dv = L->Dv; P.l = L->l; P.d = L->d;
+    P.rope_base = L->rope_base > 0.f ? L->rope_base : 10000.0f;
+    P.inv_scale = 1.0f;  // as nsa_cmp_pool_append: no position scaling inside the pooled keys
+    P.t_pos = t_pos; P.t_max = te; P.S = S; P.G = L->G;
+    if (int rc = launch_cmp_pool_ragged(P, L->dtype, st)) return rc;
+    // 3. selected branch: the rows form with the position array (one launch; zero O and ranges rows for a sequence that is not live)
+    if (int rc = launch_decode_rows(c, st, t_pos, te)) return rc;
+    // 4. both band branches in one dual launch (split form, deferred combine; Dv = 128: one ragged launch each), 5. finish (or the gate
+    // kernel), 6. output projection -- the rows call's tail with the position array in D
+    DecodeFinishParams F = decode_finish_params(D, gates_out);
+    F.ns[1] = 1;
+    DecBandPair BP{};
+    const bool dual = band_pair(D, C, L->Dv == 64 ? 1 : 0, BP);
+    return layer_decode_tail(D, C, F, dual ? &BP : nullptr, false, gates_out, y, nullptr, stream);
 }
 
 // block workspace: xn | h | hn | u [B, mlp_hidden] | layer decode workspace

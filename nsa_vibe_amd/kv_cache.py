@@ -58,6 +58,28 @@ class NSA_KV:
         c._native = {}
         return c
 
+    def sequence_view(self, b: int, t: int = 0) -> "NSA_KV":
+        """slab b of these buffers as a cache of its own: a B = 1 NSA_KV that SHARES the storage (a write through the view lands in the
+        pool) and holds t tokens, n_cmp_at(t) compressed ones and empty read counters.  It has its own native descriptor and does not
+        grow (auto_grow = False: growing would detach it from the pool).  What NSAAttention.decode_ragged's pool of slabs is filled
+        through -- m(x_b, kv.sequence_view(b), prefill=True) -- and what its per-sequence route runs on."""
+        b, t = int(b), int(t)
+        if not 0 <= b < self.B:
+            raise IndexError(f"NSA_KV.sequence_view: sequence {b} outside [0, {self.B})")
+        cap = self._K_sel.shape[2]
+        if not 0 <= t <= cap:
+            raise ValueError(f"NSA_KV.sequence_view: t = {t} outside [0, {cap}]")
+        v = object.__new__(type(self))
+        v.__dict__.update(self.__dict__)
+        v.B, v.auto_grow, v.S_max = 1, False, cap
+        for name in ("_K_sel", "_V_sel", "_K_win", "_V_win", "_K_raw", "_V_raw", "_K_cmp", "_V_cmp"):
+            setattr(v, name, getattr(self, name)[b:b + 1])  # (a leading-axis slice: contiguous, the same memory)
+        v.t, v.n_cmp = t, self.n_cmp_at(t)
+        v.meta, v.meta_seq_len = build_block_meta(0, self.l, self.d, self.l_sel, self.n_sel, self.w), 0
+        v.reads_pred, v.reads_act_total, v.reads_act_sel, v.reads_act_cmp, v.reads_act_win = [], [], [], [], []
+        v._native = {}
+        return v
+
     # ---- reference field names as views -------------------------------------------------
     @property
     def K_sel(self):

@@ -725,6 +725,93 @@ class NSAAttention(nn.Module):
         self._monitors(ranges, gates)
         return y, kv
 
+    # ---- ragged batch: every sequence of the batch at its own position (a serving batch) --------------------------------------------------
+    def decode_ragged_plan(self, B: int, S: int, S_max: int, t_max: int, S_sel: int) -> dict:
+        """what nsa_layer_decode_ragged does with a shape under the current tuning switches (nsa_layer_decode_ragged_plan, no device call):
+        {"launches", "route": 1 the one native call / -1 declined (no native route with per-sequence positions)}"""
+        desc, _ = self._layer_desc()
+        n, r = _plan_ints("nsa_layer_decode_ragged_plan", 2, ctypes.byref(desc), int(B), int(S), int(S_max), int(t_max), int(S_sel))
+        return {"launches": n, "route": r}
+
+    def decode_ragged(self, x: torch.Tensor, kv: NSA_KV, t_pos, *, t_max: Optional[int] = None):
+        """x [B,S,dim], 1 <= S <= 16: row (b, s) is the token at position t_pos[b] + s of sequence b, whose slab of `kv` holds t_pos[b] tokens
+        -> (y [B,S,dim], kv), in ONE native call (nsa_layer_decode_ragged) whose arguments do not change from token to token.
+        kv is a POOL of slabs here: its t, n_cmp and read counters are not touched -- the lengths belong to the caller (fill slot b with
+        m(x_b, kv.sequence_view(b), prefill=True); rows of a slab beyond its sequence are never read).  Capacity is not grown: build the pool
+        with the capacity it will need (kv.reserve keeps only the first kv.t rows of every slab, so it is for a pool that is not filled yet).
+        t_pos: a device int32 tensor [B], advanced by the caller on the device; the host never reads it, so t_max -- the host bound of
+        t_pos[b] + S - 1 -- is required.  Or a sequence of B host integers: copied without blocking, t_max derived from them.
+        A slot with t_pos[b] < 0 or t_pos[b] + S - 1 > t_max is padding: nothing is written to its slab, its y and ranges rows are zero.
+        Monitors: _last_ranges [B,S,G,n,2], _last_gates [B,S,G,3] (gates of a padding slot: unspecified).  Inference only.
+        Where the native call declines (nsa_layer_decode_ragged_plan) or the module is in parity mode: with host positions one decode_rows
+        per live sequence on kv.sequence_view(b, t_b); with device positions the native message is raised."""
+        assert x.dim() == 3, "x must be [B,S,dim]"
+        B, S, _ = x.shape
+        if not 1 <= S <= 16:
+            raise ValueError(f"NSAAttention.decode_ragged takes 1 to 16 tokens per sequence, got S={S}")
+        host = None
+        if isinstance(t_pos, torch.Tensor):
+            if t_pos.dtype != torch.int32 or tuple(t_pos.shape) != (B,):
+                raise ValueError(f"NSAAttention.decode_ragged: t_pos must be an int32 tensor [{B}], got {t_pos.dtype} {tuple(t_pos.shape)}")
+            if t_max is None:
+                raise ValueError("NSAAttention.decode_ragged: t_max (the host bound of t_pos[b] + S - 1) is required with a tensor of positions: "
+                                 "the host never reads them")
+        else:
+            host = [int(p) for p in t_pos]
+            if len(host) != B:
+                raise ValueError(f"NSAAttention.decode_ragged: {len(host)} positions for a batch of {B}")
+            if t_max is None:
+                t_max = max([p + S - 1 for p in host if p >= 0], default=0)
+        t_max = int(t_max)
+        cap = kv._K_sel.shape[2]
+        if t_max < 0:
+            raise ValueError(f"NSAAttention.decode_ragged: t_max = {t_max} is negative")
+        if t_max + 1 > cap:
+            raise RuntimeError(f"NSAAttention.decode_ragged: {t_max + 1} tokens exceed the capacity {cap} of the pool, which is not grown here (it has "
+                               f"no single length to copy by): build the pool with that capacity, or kv.reserve({t_max + 1}) BEFORE it is filled (reserve keeps only "
+                               f"the first kv.t = {kv.t} rows of every slab)")
+        if not x.is_cuda or (host is None and t_pos.device != x.device):
+            raise RuntimeError("NSAAttention.decode_ragged needs HIP device tensors on one device (no CPU fallback exists)")
+        self._check_kv(x, kv)
+        if self._grad_needed(x):
+            raise RuntimeError("NSAAttention.decode_ragged is inference only (no backward); run it under torch.no_grad()")
+        if not x.is_contiguous():
+            x = x.contiguous()
+        kv.refresh_meta(t_max + 1)
+        if host is not None and (self._force_parity or not self._native_ok(x)
+                                 or self.decode_ragged_plan(B, S, cap, t_max, int(kv.meta.S_sel))["route"] < 0):
+            return self._decode_ragged_sequences(x, kv, host, t_max)
+        if not self._native_ok(x):
+            raise RuntimeError("NSAAttention.decode_ragged: the native call does not take this module or input (parity mode, dtype, gate "
+                               "width), and the per-sequence route needs host positions")
+        if host is not None:
+            t_pos = torch.tensor(host, dtype=torch.int32).pin_memory().to(x.device, non_blocking=True)
+        elif not t_pos.is_contiguous():
+            t_pos = t_pos.contiguous()
+        G = self.n_kv_groups
+        desc, _ = self._layer_desc()
+        y = torch.empty((B, S, self.dim), dtype=x.dtype, device=x.device)
+        # (a declined shape comes back from the call itself, before its first launch, with the limit named)
+        ranges, gates = _one_call("nsa_layer_decode_ragged", "layer_decode_ragged", desc, kv, kv.meta, x.device, (B, S, cap),
+                                  (x.data_ptr(), y.data_ptr(), t_pos.data_ptr(), t_max, S), (), (B, S, G, self.n_sel, 2), (B, S, G, 3))
+        self._monitors(ranges, gates)
+        return y, kv
+
+    def _decode_ragged_sequences(self, x: torch.Tensor, kv: NSA_KV, host, t_max: int):
+        """the per-sequence route of decode_ragged: one decode_rows per live sequence on its slab, zeros for the padding slots"""
+        B, S, _ = x.shape
+        G = self.n_kv_groups
+        y = torch.zeros((B, S, self.dim), dtype=x.dtype, device=x.device)
+        ranges = torch.zeros((B, S, G, self.n_sel, 2), dtype=torch.int32, device=x.device)
+        gates = torch.zeros((B, S, G, 3), dtype=torch.float32, device=x.device)
+        for b, p in enumerate(host):
+            if p < 0 or p + S - 1 > t_max:
+                continue
+            yb, _ = self.decode_rows(x[b:b + 1], kv.sequence_view(b, p))
+            y[b], ranges[b], gates[b] = yb[0], self._last_ranges[0], self._last_gates.reshape(1, S, G, 3)[0]
+        self._monitors(ranges, gates)
+        return y, kv
+
     def _decode(self, x: torch.Tensor, kv: NSA_KV, one_call: bool = True):
         if one_call and self._native_ok(x):
             return self._decode_native(x, kv)
