@@ -480,3 +480,180 @@ def cmp_pool_bwd_bound(dK_cmp, dV_cmp, S: int, l: int, d: int, pos=None, dtype="
     nk, w = _pair_norm(ak), -(-l // d)
     bk = rope_bound(ak, p, dtype, c=ROPE_C[dtype] + w + 1.0, base=base) + 2.0 ** -22 * nk
     return bk, (w + 1.0) * ulp(av, dtype) + 2.0 ** -22 * av
+
+
+# ---- float64 backward of the selection / band attention with per-element error bounds (numpy only) ---------------------------------------
+_U = {"fp32": 2.0 ** -24, "bf16": 2.0 ** -8, "fp16": 2.0 ** -11}  # unit roundoff u_T (half an ulp of 1)
+_TINY = {k: 2.0 ** (_EMIN[k] - _MANT[k] - 1) for k in _MANT}     # half the subnormal spacing: the rounding error below the normal range
+_U32 = 2.0 ** -24
+
+
+def round_to(a, dtype="fp32") -> np.ndarray:
+    """a rounded to the nearest value of dtype (ties to even), returned as float64"""
+    a = np.asarray(a, np.float64)
+    if dtype == "fp16":
+        return a.astype(np.float16).astype(np.float64)
+    f = np.ascontiguousarray(a.astype(np.float32))
+    if dtype == "fp32":
+        return f.astype(np.float64)
+    u = f.view(np.uint32).astype(np.uint64)
+    u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
+    return u.astype(np.uint32).view(np.float32).reshape(a.shape).astype(np.float64)
+
+
+def _rd(x, dtype):
+    """bound on |round_T(y) - y| for |y| <= x: u_T x, or half the subnormal spacing"""
+    return np.maximum(_U[dtype] * x, _TINY[dtype])
+
+
+def _rows_keys(a, Kc):
+    """[R,h,D] x [C,D] -> [R,h,C]"""
+    return np.matmul(a, Kc.T)
+
+
+def _keys_sum(p, a):
+    """[R,h,C] x [R,h,D] -> [C,D]: the sum over (row, head)"""
+    return np.matmul(p.reshape(-1, p.shape[-1]).T, a.reshape(-1, a.shape[-1]))
+
+
+def sel_attention_bwd_terms(Q, K, V, ranges, dO, dtype, scale=None, extend=False, probe_only=False, chunk=64):
+    """Generator behind sel_attention_bwd_bound: the float64 terms of the backward, one dict per (b, g, chunk of query rows):
+      b, g, rows [R], cols [C] (ascending keys: every key some row of the chunk selects; extend=True adds the rest of their 64-key blocks
+      and the key on either side of every range, for mutants that switch a key on), cnt [R,C] (ranges of the row covering the key),
+      lse [R,h], O [R,h,Dv], active [R] (rows with a non-zero dO) and, on the active rows `ar` (indices into rows), for EVERY column
+      (covered or not: p = exp(s - lse) is what a kernel with a wrong mask evaluates there) p, dS, e_p, e_dS [A,h,C]; see
+      sel_attention_bwd_bound for the two error terms.  probe_only: the rows with a zero dO are left out altogether."""
+    Q, K, V, dO = (np.asarray(x, np.float64) for x in (Q, K, V, dO))
+    rg = np.asarray(ranges, np.int64)
+    B, S, G, h, Dk = Q.shape
+    S_kv, Dv, n = K.shape[2], V.shape[3], rg.shape[3]
+    sc = float(np.float32(1.0 / np.sqrt(Dk) if not scale else scale))  # the fp32 scale a kernel is handed
+    s0 = np.clip(rg[..., 0], 0, S_kv)
+    e0 = np.clip(rg[..., 1], s0, S_kv)
+    for b in range(B):
+        for g in range(G):
+            todo = np.nonzero(dO[b, :, g].reshape(S, -1).any(axis=1))[0] if probe_only else np.arange(S)
+            step = max(chunk // 4, 1) if probe_only else chunk  # probe rows lie apart: fewer of them share the keys of a chunk
+            for r0 in range(0, todo.size, step):
+                rows = todo[r0: r0 + step]
+                R = rows.size
+                st, en = s0[b, rows, g], e0[b, rows, g]  # [R,n]
+                diff = np.zeros((R, S_kv + 2), np.int32)
+                ri = np.repeat(np.arange(R), n)
+                np.add.at(diff, (ri, st.reshape(-1)), 1)
+                np.add.at(diff, (ri, en.reshape(-1)), -1)
+                cnt_full = np.cumsum(diff, axis=1)[:, :S_kv]
+                keep = cnt_full.any(axis=0)
+                if extend and keep.any():
+                    blk = np.zeros((S_kv + 63) // 64, bool)
+                    blk[np.nonzero(keep)[0] // 64] = True
+                    keep = np.repeat(blk, 64)[:S_kv]
+                    ne = en > st
+                    for k in (st[ne] - 1, en[ne]):
+                        keep[k[(k >= 0) & (k < S_kv)]] = True
+                cols = np.nonzero(keep)[0]
+                cnt = cnt_full[:, cols]
+                mask = cnt > 0
+                Kc, Vc = K[b, g, cols], V[b, g, cols]
+                q, do = Q[b, rows, g], dO[b, rows, g]
+                s = _rows_keys(q, Kc) * sc
+                sm = np.where(mask[:, None, :], s, -np.inf)
+                live = mask.any(axis=1)
+                m = np.where(live[:, None], sm.max(axis=2, initial=-np.inf), 0.0)
+                with np.errstate(divide="ignore"):
+                    lse = np.where(live[:, None], m + np.log(np.exp(sm - m[:, :, None]).sum(axis=2)), -np.inf)
+                p_all = np.where(live[:, None, None], np.exp(s - np.where(live[:, None], lse, 0.0)[:, :, None]), 0.0)
+                p = p_all * mask[:, None, :]
+                O = np.matmul(p, Vc)
+                active = do.reshape(R, -1).any(axis=1)
+                out = dict(b=b, g=g, rows=rows, cols=cols, cnt=cnt, lse=lse, O=O, active=active, scale=sc)
+                ar = np.nonzero(active)[0]
+                if ar.size and cols.size:
+                    qa, da, pa, Oa = q[ar], do[ar], p_all[ar], O[ar]
+                    dP = _rows_keys(da, Vc)
+                    delta = (da * Oa).sum(axis=2)
+                    x = pa * (dP - delta[:, :, None])
+                    dS = x * sc
+                    # p: the fp32 logit (Dk products summed in fp32), scale log2(e) and lse log2(e) formed and rounded in fp32, the fused
+                    # multiply-add, the hardware exp2 (1 ulp) -- the generic kernel's __expf(s scale - lse) has the same count
+                    eta = 2.0 ** -22 * (np.abs(s[ar]) + np.abs(np.where(live[ar, None], lse[ar], 0.0))[:, :, None] + 1.0) \
+                        + Dk * _U32 * sc * _rows_keys(np.abs(qa), np.abs(Kc))
+                    e_p = _rd(pa * (1.0 + eta), dtype) + eta * pa
+                    e_dP = Dv * _U32 * _rows_keys(np.abs(da), np.abs(Vc))
+                    e_delta = (np.abs(da) * _rd(np.abs(Oa), dtype)).sum(axis=2) + Dv * _U32 * (np.abs(da) * np.abs(Oa)).sum(axis=2)
+                    ex = eta * np.abs(x) + pa * (1.0 + eta) * (e_dP + e_delta[:, :, None])
+                    pert = np.abs(dS) + sc * ex
+                    e_dS = sc * ex + np.maximum(_U[dtype] * pert, _TINY[dtype] * max(sc, 1.0)) + 2.0 ** -22 * pert
+                    out.update(ar=ar, p=pa, dS=dS, e_p=e_p, e_dS=e_dS, q=qa, dO=da, Kc=Kc, Vc=Vc)
+                yield out
+
+
+def sel_attention_bwd_bound(Q, K, V, ranges, dO, dtype, scale=None, probe_only=False):
+    """Float64 backward of sel_attention_masked with a per-element bound on what a kernel of activation type T = dtype may differ by.
+    Inputs must already be representable in T.  -> (dQ, dK, dV), (bQ, bK, bV), (O, lse): gradients and bounds shaped like Q, K, V, the
+    forward output O [B,S,G,h,Dv] and lse [B,S,G,h] (-inf on rows without a key), all float64.  Rows whose dO is zero add no term;
+    probe_only=True skips them altogether (a probe phase, dO on every s-th row, then costs its probe rows only) and leaves their O at 0
+    and their lse at -inf.
+
+    Per (row, head, selected key), with s = scale q.k, p = exp(s - lse), dP = dO.v, delta = sum_dv dO O, dS = p (dP - delta) scale:
+        dV[key] += p dO      dK[key] += dS q      dQ[row, head] += dS k.
+    A kernel is given the T-rounded O and the fp32 lse of THIS forward (no forward error enters) and rounds where its header says
+    (sel_attn_bwd_mfma.hip, band_attn_mfma.hip, sel_attn_generic.hip); rd_T(y) = max(u_T |y|, half the subnormal spacing of T) is one
+    rounding to T, u_T = 2^-8 / 2^-11 / 2^-24 for bf16 / fp16 / fp32.  Each term of the bound is one of those points:
+      eta     relative error of the fp32 p: the logit's Dk-term fp32 sum (Dk 2^-24 scale sum|q||k|), the fp32 constants scale log2(e)
+              and lse log2(e), the fused multiply-add and the exp2 instruction: 2^-22 (|s| + |lse| + 1) in all
+      e_p     = rd_T(p (1 + eta)) + eta p            P is rounded to T as the MFMA operand of dV  (c = 1: one rounding)
+      e_delta = sum_dv |dO| rd_T(O) + Dv 2^-24 sum_dv |dO||O|      O enters as the rounded forward output; the fp32 row sum
+      e_dP    = Dv 2^-24 sum_dv |dO||v|              the fp32 sum of dP
+      e_dS    = scale (eta |x| + p (e_dP + e_delta)) + rd_T(dS') + 2^-22 |dS'|,  x = p (dP - delta), dS' = |dS| + the first term:
+              dS is rounded to T as the MFMA operand of dK and dQ (c = 1; before the scale in the dK kernel, after it in the dQ
+              kernels: the same relative rounding), the fp32 products around it
+      bV = sum e_p |dO| + (N + 2) 2^-24 sum (p + e_p)|dO|                    N terms summed in fp32, in any order (splits, atomics)
+      bK = sum e_dS |q| + (N + 2) 2^-24 sum (|dS| + e_dS)|q|                 the same, and the final multiplication by scale
+      bQ = sum e_dS |k| + N 2^-24 sum (|dS| + e_dS)|k| + rd_T(|dQ| + those)  dQ is stored in T
+    The sums run over the selected (row, head, key) terms only: where none lands, gradient and bound are 0 and a kernel must write an
+    exact zero.  The bound does not depend on the summation order, so it holds for the atomics of the generic kernel as well."""
+    Q = np.asarray(Q, np.float64)
+    B, S, G, h, Dk = Q.shape
+    S_kv, Dv = np.asarray(K).shape[2], np.asarray(V).shape[3]
+    dQ, bQ = np.zeros((B, S, G, h, Dk)), np.zeros((B, S, G, h, Dk))
+    dK, bK, aK = (np.zeros((B, G, S_kv, Dk)) for _ in range(3))
+    dV, bV, aV = (np.zeros((B, G, S_kv, Dv)) for _ in range(3))
+    nKV = np.zeros((B, G, S_kv))
+    O, lse = np.zeros((B, S, G, h, Dv)), np.full((B, S, G, h), -np.inf)
+    for c in sel_attention_bwd_terms(Q, K, V, ranges, dO, dtype, scale, probe_only=probe_only):
+        b, g, rows, cols = c["b"], c["g"], c["rows"], c["cols"]
+        O[b, rows, g], lse[b, rows, g] = c["O"], c["lse"]
+        if "ar" not in c:
+            continue
+        ar = c["ar"]
+        mk = (c["cnt"][ar] > 0)[:, None, :]
+        p, dS, e_p, e_dS = (c[k] * mk for k in ("p", "dS", "e_p", "e_dS"))
+        aq, ado, aKc = np.abs(c["q"]), np.abs(c["dO"]), np.abs(c["Kc"])
+        dV[b, g, cols] += _keys_sum(p, c["dO"])
+        dK[b, g, cols] += _keys_sum(dS, c["q"])
+        bV[b, g, cols] += _keys_sum(e_p, ado)
+        aV[b, g, cols] += _keys_sum(p + e_p, ado)
+        bK[b, g, cols] += _keys_sum(e_dS, aq)
+        aK[b, g, cols] += _keys_sum(np.abs(dS) + e_dS, aq)
+        nKV[b, g, cols] += h * mk[:, 0, :].sum(axis=0)
+        dq = np.matmul(dS, c["Kc"])
+        eq = np.matmul(e_dS, aKc)
+        eq += mk.sum(axis=2)[:, :, None] * _U32 * np.matmul(np.abs(dS) + e_dS, aKc)
+        dQ[b, rows[ar], g] = dq
+        bQ[b, rows[ar], g] = np.where(mk.any(axis=2)[:, :, None], eq + _rd(np.abs(dq) + eq, dtype), 0.0)
+    bV += (nKV[..., None] + 2.0) * _U32 * aV
+    bK += (nKV[..., None] + 2.0) * _U32 * aK
+    return (dQ, dK, dV), (bQ, bK, bV), (O, lse)
+
+
+def band_ranges_rows(B: int, S: int, G: int, S_kv: int, **band) -> np.ndarray:
+    """band_ranges as the one-range-per-row ranges tensor [B,S,G,1,2] of the selection functions"""
+    return np.ascontiguousarray(np.broadcast_to(band_ranges(S, S_kv, **band).reshape(1, S, 1, 1, 2), (B, S, G, 1, 2)))
+
+
+def band_attention_bwd_bound(Q, K, V, dO, dtype, *, t0: int = 0, a: int = 0, dd: int = 1, c: int = 0, w: int = 2 ** 30, scale=None):
+    """sel_attention_bwd_bound of the sliding / compressed band (band_ranges: one key interval per row)"""
+    B, S, G = np.asarray(Q).shape[:3]
+    rg = band_ranges_rows(B, S, G, np.asarray(K).shape[2], t0=t0, a=a, dd=dd, c=c, w=w)
+    return sel_attention_bwd_bound(Q, K, V, rg, dO, dtype, scale)
