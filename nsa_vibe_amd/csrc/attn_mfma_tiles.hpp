@@ -1,5 +1,6 @@
 // Pieces shared by the MFMA attention kernels (selection attention forward and backward, band attention) -- everything between a K/V
-// pointer and the MFMA operands; schedule, softmax, masks, epilogue and the LDS carve-up stay with each kernel:
+// pointer and the MFMA operands; schedule, softmax, masks, epilogue and the LDS carve-up stay with each kernel (the query-tile schedule of
+// the two rows-per-wave kernels is attn_rows_schedule.hpp):
 //   MfmaT<T>            MFMA / transposing-read wrappers per element type
 //   Geo<D>              LDS tile geometry: row image and transposable image with their XOR swizzles (row_piece / tr_piece)
 //   frag_read_offsets   a lane's fragment read offsets into the two images

@@ -6,9 +6,9 @@
 //
 // Three kernels, no atomics, bitwise reproducible:
 //   1. delta[row,h] = sum_dv dO*O.
-//   2. dQ, query-major (one wave per query row, the forward's mapping): per 32-key tile
+//   2. dQ, query-major (one wave per query row, or per 16/h consecutive rows that share their tiles: the forward's mappings): per 32-key tile
 //        S^T = K.Q^T, dP^T = V.dO^T, dS^T = exp2(S^T c - lse) * (dP^T - delta) * scale, dQ^T += K^T.dS^T
-//      (K is staged twice in LDS: a row image for the S^T A-operand and a transposable image for the dQ^T A-operand.)
+//      (K is staged once in LDS, as a transposable image: transposing reads give the dQ^T A-operand, row reads the S^T A-operand.)
 //   3. dK, dV, KEY-BLOCK-major: one workgroup owns 64 keys of one (b,g) and keeps their dK/dV (64xD fp32 each) in MFMA
 //      accumulators while it sweeps every query row that selected the block.  The rows are found by scanning the range
 //      lists (lane = row) and compacted in ascending t, so the summation order is fixed.  Rows are processed two at a
@@ -17,35 +17,9 @@
 //      dK += dS^T.Q as 16x16x16 MFMAs whose A operand is taken straight from the S/dP accumulators (their row index,
 //      the (query,head) slot, is the contraction index) and whose B operand is read transposed from LDS.
 #include "attn_mfma_tiles.hpp"
+#include "attn_rows_schedule.hpp"
 
 namespace nsa {
-
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-
-template <typename T>
-struct BwdT;
-template <>
-struct BwdT<__bf16> {
-    using x8 = bf16x8;
-    using x4 = bf16x4;
-    __device__ static f32x4 mma32(x8 a, x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-    __device__ static f32x4 mma16(x4 a, x4 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4, a), __builtin_bit_cast(s16x4, b), c, 0, 0, 0);
-    }
-};
-template <>
-struct BwdT<_Float16> {
-    using x8 = f16x8;
-    using x4 = f16x4;
-    __device__ static f32x4 mma32(x8 a, x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-    __device__ static f32x4 mma16(x4 a, x4 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0); }
-};
-
-template <typename X4>
-__device__ __forceinline__ X4 tr_read(const unsigned char *p) {
-    const s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)p);
-    return __builtin_bit_cast(X4, r);
-}
 
 // Tile geometry: the forward's Geo<D> (attn_mfma_tiles.hpp), a row image and a transposable image.
 // Head dimension D = Dk = Dv in {64, 128}: rows of D bf16/f16 elements = D / 8 pieces of 16 B = D / 16 chunks of 32 B.
@@ -78,20 +52,131 @@ __global__ __launch_bounds__(256) void bwd_delta_kernel(const T *__restrict__ O,
 }
 
 // ------------------------------------------------------------------------------------------ 2. dQ (query-major)
-template <int D>
-constexpr int bwd_dq_wave_lds() {
-    return 3 * 32 * Geo<D>::ROWB + ((SEG_INTS * 4 + 15) / 16) * 16;
-}
-
+// What a wave of either dQ kernel holds for its 16 MFMA columns (one (query row, head) slot each) and what it does per 32-key tile.
+// Wave-private LDS: K in a transposable image, V in a row image.  ONE K image (round 4): the chunk-swizzled image of the transposing reads
+// also serves the b128 row-fragment reads without bank conflicts (see bwd_dkdv_kernel), so K is fetched once per tile: 8 LDS-DMA
+// instructions per 32 keys at D = 64.
 template <typename T, int D>
-__global__ __launch_bounds__(256, 2) void bwd_dq_kernel(SelAttnBwdParams P, const float *__restrict__ delta, int map_mode) {
-    using M = BwdT<T>;
+struct DqWave {
+    using M = MfmaT<T>;
     using Gm = Geo<D>;
     using x8 = typename M::x8;
     using x4 = typename M::x4;
-    constexpr int BROWB = Gm::ROWB, KS = Gm::KSTEPS, MT = Gm::MT, NLD = Gm::NLD, RPI = Gm::RPI;
-    constexpr int TILE = 32 * BROWB;  // 4 KiB (D = 64), 8 KiB (D = 128)
-    constexpr int WAVE_LDS = bwd_dq_wave_lds<D>();
+    static constexpr int BROWB = Gm::ROWB, KS = Gm::KSTEPS, MT = Gm::MT, NLD = Gm::NLD, RPI = Gm::RPI;
+    unsigned char *k_tr, *v_row;        // K, transposable image (row fragments are read from it too); V, row image
+    KvSrc<D> kv;
+    uint32_t kd_tr[NLD], vd_row[NLD];   // per-lane source offsets of the LDS-DMA loads of a full tile
+    uint32_t rd_krow[KS], rd_row[KS], rd_tr[MT];
+    x8 qf[KS], dof[KS];                 // B operands held for every tile: Q^T and dO^T fragments (slot = column)
+    float lse2 = 0.f, dlt = 0.f;        // the slot's lse (log2 domain) and delta: set by the kernel
+    float c2, scale;
+    f32x4 dq[MT];
+    x8 kfr[2][KS], vfr[2][KS];          // fragments of the current tile
+    x4 ktr[2][MT];
+
+    // orow = row * h + head of the lane's slot (used: the slot holds one)
+    __device__ __forceinline__ DqWave(const SelAttnBwdParams &P, unsigned char *lds, int b, int g, int lane, int64_t orow, bool used)
+        : k_tr(lds), v_row(lds + Gm::TILE_BYTES) {
+        const int rho = lane & 15, q = lane >> 4;
+        load_col_frags<D>((const T *)P.Q + orow * D, used, q, qf);
+        load_col_frags<D>((const T *)P.dO + orow * D, used, q, dof);
+        c2 = P.scale * LOG2E;
+        scale = P.scale;
+        kv = kv_src<T, D>(P, b, g, lane);
+#pragma unroll
+        for (int i = 0; i < NLD; ++i) {
+            const int r = RPI * i + kv.ld_row;
+            kd_tr[i] = kv.ld_row * kv.krowb + Gm::tr_piece(r, kv.ld_piece);
+            vd_row[i] = kv.ld_row * kv.vrowb + Gm::row_piece(r, kv.ld_piece);
+        }
+        frag_read_offsets<D>(rho, q, rd_row, rd_tr);
+#pragma unroll
+        for (int s = 0; s < KS; ++s) rd_krow[s] = Gm::tr_img(rho, 4 * s + q);
+#pragma unroll
+        for (int m = 0; m < MT; ++m) dq[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    // the 32 keys from tok0 -> LDS by LDS-DMA.  !whole: the rows past `last` re-read row `last` (the caller masks their dS to zero)
+    __device__ __forceinline__ void fetch(int tok0, bool whole, int last) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        typedef __attribute__((address_space(3))) void lds_void;
+        const int ks = uniform(tok0 * kv.krowb), vs = uniform(tok0 * kv.vrowb);
+#pragma unroll
+        for (int i = 0; i < NLD; ++i) {
+            const int rowshift = whole ? 0 : (min(RPI * i + kv.ld_row, last) - kv.ld_row);
+            const int kso = whole ? ks + i * kv.kstep : ks, vso = whole ? vs + i * kv.vstep : vs;
+            const uint32_t kadd = whole ? 0u : (uint32_t)(rowshift * kv.krowb), vadd = whole ? 0u : (uint32_t)(rowshift * kv.vrowb);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(kv.krs, (lds_void *)(k_tr + i * 1024), 16, kd_tr[i] + kadd, kso, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(kv.vrs, (lds_void *)(v_row + i * 1024), 16, vd_row[i] + vadd, vso, 0, 0);
+        }
+#else
+        (void)tok0, (void)whole, (void)last;
+#endif
+    }
+    // A tile step in three parts; the kernel's own LDS reads and tile bookkeeping go between them.  (1) the tile has landed: its fragments
+    __device__ __forceinline__ void read_frags() {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        read_row_frags<D>(k_tr, rd_krow, kfr);
+        read_row_frags<D>(v_row, rd_row, vfr);
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int m = 0; m < MT; ++m) ktr[u][m] = M::tr(k_tr + rd_tr[m] + u * 16 * BROWB);
+    }
+    // (2) the fragments are in registers: the images are refilled with the next tile (more: there is one) under the products of this one
+    __device__ __forceinline__ void refill(bool more, int tok0, bool whole, int last) {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        if (more) fetch(tok0, whole, last);
+    }
+    // (3) the products.  The slot takes key 16u + 4q + j of the tile if bit 16u + j of km is set; !mixed (wave uniform): no slot of the wave
+    // is covered in part, every slot is all-on or all-off -- one predicate per lane
+    __device__ __forceinline__ void accumulate(bool mixed, bool on, unsigned km) {
+        f32x4 sacc[2], pacc[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            sacc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            pacc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s = 0; s < KS; ++s) {
+                sacc[u] = M::mma(kfr[u][s], qf[s], sacc[u]);
+                pacc[u] = M::mma(vfr[u][s], dof[s], pacc[u]);
+            }
+        }
+        x8 dsf;
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float p = __builtin_amdgcn_exp2f(fmaf(sacc[u][j], c2, -lse2));
+                if (!mixed) p = on ? p : 0.f;
+                else if (!((km >> (16 * u + j)) & 1u)) p = 0.f;
+                dsf[4 * u + j] = Elt<T>::from_f(p * (pacc[u][j] - dlt) * scale);
+            }
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            x8 a;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                a[j] = ktr[0][m][j];
+                a[4 + j] = ktr[1][m][j];
+            }
+            dq[m] = M::mma(a, dsf, dq[m]);
+        }
+    }
+    __device__ __forceinline__ void store(T *dQr, int q) const {
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            x4 ov;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) ov[j] = Elt<T>::from_f(dq[m][j]);
+            *(x4 *)(dQr + 16 * m + 4 * q) = ov;
+        }
+    }
+};
+
+// One query row per wave: the row's ranges as sorted disjoint segments, each walked in 32-key tiles
+template <typename T, int D>
+__global__ __launch_bounds__(256, 2) void bwd_dq_kernel(SelAttnBwdParams P, const float *__restrict__ delta, int map_mode) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = lane_id();
     const int wave = uniform((int)(threadIdx.x >> 6));
@@ -105,37 +190,19 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(SelAttnBwdParams P, cons
         row = ((int64_t)(bg / P.G) * P.S + t) * P.G + (bg % P.G);
     }
     if (row >= P.R) return;
-    unsigned char *k_row = smem + (size_t)wave * WAVE_LDS;  // K, row image
-    unsigned char *k_tr = k_row + TILE;                     // K, transposable image
-    unsigned char *v_row = k_tr + TILE;                     // V, row image
-    int *seg = (int *)(v_row + TILE);
+    unsigned char *lds = smem + (size_t)wave * Geo<D>::WAVE_LDS;
+    int *seg = (int *)(lds + 2 * Geo<D>::TILE_BYTES);
 
     const int h = P.h;
     const int g = (int)(row % P.G);
     const int b = (int)(row / ((int64_t)P.G * P.S));
     int nseg;
     const int L = normalise_ranges(P.ranges + row * (int64_t)P.n * 2, P.n, P.S_kv, seg, &nseg);
-    const int rho = lane & 15, q = lane >> 4;
+    const int rho = lane & 15, q = lane >> 4;  // head = column
 
-    // B operands held for the whole row: Q^T and dO^T fragments (head = column), per-head lse (log2 domain) and delta
-    x8 qf[KS], dof[KS];
-    load_col_frags<D>((const T *)P.Q + (row * h + rho) * (int64_t)D, rho < h, q, qf);
-    load_col_frags<D>((const T *)P.dO + (row * h + rho) * (int64_t)D, rho < h, q, dof);
-    const float lse2 = (rho < h && L > 0) ? P.lse[row * h + rho] * LOG2E : 0.f;
-    const float dlt = (rho < h) ? delta[row * h + rho] : 0.f;
-    const float c2 = P.scale * LOG2E;
-
-    // K goes into a row image and a transposable one, V into a row image: per-lane source offsets of the LDS-DMA loads of a full tile
-    const KvSrc<D> kv = kv_src<T, D>(P, b, g, lane);
-    uint32_t kd_tr[NLD], vd_row[NLD];
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-        const int r = RPI * i + kv.ld_row;
-        kd_tr[i] = kv.ld_row * kv.krowb + Gm::tr_piece(r, kv.ld_piece);
-        vd_row[i] = kv.ld_row * kv.vrowb + Gm::row_piece(r, kv.ld_piece);
-    }
-    uint32_t rd_row[KS], rd_tr[MT];
-    frag_read_offsets<D>(rho, q, rd_row, rd_tr);
+    DqWave<T, D> w(P, lds, b, g, lane, row * h + rho, rho < h);
+    w.lse2 = (rho < h && L > 0) ? P.lse[row * h + rho] * LOG2E : 0.f;
+    w.dlt = (rho < h) ? delta[row * h + rho] : 0.f;
 
     int it_seg = -1, it_start = 0, it_len = 0, it_pos = 0;
     auto next_tile = [&](int &tok0, int &nvalid) -> bool {
@@ -152,114 +219,27 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(SelAttnBwdParams P, cons
             it_pos = 0;
         }
     };
-    auto issue_dma = [&](int tok0, int nvalid) {
-#if defined(__HIP_DEVICE_COMPILE__)
-        typedef __attribute__((address_space(3))) void lds_void;
-        const int ks = uniform(tok0 * kv.krowb), vs = uniform(tok0 * kv.vrowb);
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-            // tail tiles: rows past the segment re-read its last row (their dS is masked to zero below)
-            const int rowshift = (nvalid == 32) ? 0 : (min(RPI * i + kv.ld_row, nvalid - 1) - kv.ld_row);
-            const int kso = (nvalid == 32) ? ks + i * kv.kstep : ks, vso = (nvalid == 32) ? vs + i * kv.vstep : vs;
-            const uint32_t kadd = (nvalid == 32) ? 0u : (uint32_t)(rowshift * kv.krowb), vadd = (nvalid == 32) ? 0u : (uint32_t)(rowshift * kv.vrowb);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(kv.krs, (lds_void *)(k_row + i * 1024), 16, kv.kdma[i] + kadd, kso, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(kv.krs, (lds_void *)(k_tr + i * 1024), 16, kd_tr[i] + kadd, kso, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(kv.vrs, (lds_void *)(v_row + i * 1024), 16, vd_row[i] + vadd, vso, 0, 0);
-        }
-#else
-        (void)tok0;
-        (void)nvalid;
-#endif
-    };
-
-    f32x4 dq[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m) dq[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    // tail tiles: rows past the segment re-read its last row, their keys are masked
     int tok0 = 0, nvalid = 0;
     bool have = next_tile(tok0, nvalid);
-    if (have) issue_dma(tok0, nvalid);
+    if (have) w.fetch(tok0, nvalid == 32, nvalid - 1);
     while (have) {
         const int cur_nvalid = nvalid;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        x8 kfr[2][KS], vfr[2][KS];
-        x4 ktr[2][MT];
-        read_row_frags<D>(k_row, rd_row, kfr);
-        read_row_frags<D>(v_row, rd_row, vfr);
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int m = 0; m < MT; ++m) ktr[u][m] = tr_read<x4>(k_tr + rd_tr[m] + u * 16 * BROWB);
+        w.read_frags();
         have = next_tile(tok0, nvalid);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        if (have) issue_dma(tok0, nvalid);
-
-        f32x4 sacc[2], pacc[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            sacc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            pacc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int s = 0; s < KS; ++s) {
-                sacc[u] = M::mma32(kfr[u][s], qf[s], sacc[u]);
-                pacc[u] = M::mma32(vfr[u][s], dof[s], pacc[u]);
-            }
-        }
-        x8 dsf;
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float p = __builtin_amdgcn_exp2f(fmaf(sacc[u][j], c2, -lse2));
-                if (16 * u + 4 * q + j >= cur_nvalid) p = 0.f;
-                dsf[4 * u + j] = Elt<T>::from_f(p * (pacc[u][j] - dlt) * P.scale);
-            }
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-            x8 a;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                a[j] = ktr[0][m][j];
-                a[4 + j] = ktr[1][m][j];
-            }
-            dq[m] = M::mma32(a, dsf, dq[m]);
-        }
+        w.refill(have, tok0, nvalid == 32, nvalid - 1);
+        w.accumulate(cur_nvalid != 32, true, bit_span(0, cur_nvalid - 1) >> (4 * q));
     }
-    if (rho < h) {
-        T *dQr = (T *)P.dQ + (row * (int64_t)h + rho) * D;
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-            x4 ov;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) ov[j] = Elt<T>::from_f(dq[m][j]);
-            *(x4 *)(dQr + 16 * m + 4 * q) = ov;
-        }
-    }
+    if (rho < h) w.store((T *)P.dQ + (row * (int64_t)h + rho) * D, q);
 }
 
-// ------------------------------------------------------------------------------------------ 2b. dQ, several rows per wave
-// Query-tile form of the dQ kernel (see sel_attn_rows_mfma.hip): one wave owns TPW = 16/h consecutive rows of one (b,g) (h = 6: two
-// rows = 12 of the 16 MFMA columns) and walks the UNION of their selected 32-key tiles, so the three LDS images of a tile (K rows,
-// K transposable, V rows: 12 KB written and read back) are built once for the rows that share it.  Tile schedule and ownership
-// come from per-row tile bitmaps (`touch` / `full`, LDS atomics); a slot whose row did not select a key gets p = 0.
-__device__ __forceinline__ unsigned bwd_bit_span(int lo, int hi) {  // bits lo..hi inclusive
-    const unsigned up = hi >= 31 ? 0xffffffffu : ((1u << (hi + 1)) - 1u);
-    return up & ~((1u << lo) - 1u);
-}
-__device__ __forceinline__ void bwd_lds_or(unsigned *p, unsigned v) {
-    typedef __attribute__((address_space(3))) unsigned lds_u32;
-    __hip_atomic_fetch_or((lds_u32 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-}
-
+// Several rows per wave, the query-tile form (see sel_attn_rows_mfma.hip): one wave owns TPW = 16/h consecutive rows of one (b,g) (h = 6:
+// two rows = 12 of the 16 MFMA columns) and walks the UNION of their selected 32-key tiles, so the two LDS images of a tile are built once
+// for the rows that share it.  Tile schedule and ownership are those of attn_rows_schedule.hpp; a slot whose row did not select a key
+// gets p = 0.
 template <typename T, int D>
 __global__ __launch_bounds__(256, 2) void bwd_dq_rows_kernel(SelAttnBwdParams P, const float *__restrict__ delta, int map_mode, int tpw, int NW,
                                                           int wave_lds) {
-    using M = BwdT<T>;
-    using Gm = Geo<D>;
-    using x8 = typename M::x8;
-    using x4 = typename M::x4;
-    constexpr int BROWB = Gm::ROWB, KS = Gm::KSTEPS, MT = Gm::MT, NLD = Gm::NLD, RPI = Gm::RPI;
-    constexpr int TILE = 32 * BROWB;  // 4 KiB (D = 64), 8 KiB (D = 128)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = lane_id();
     const int wave = uniform((int)(threadIdx.x >> 6));
@@ -274,220 +254,59 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_rows_kernel(SelAttnBwdParams P,
     const int b = bg / P.G, g = bg - b * P.G;
     const int tw0 = grp * tpw, ntok = min(tpw, P.S - tw0);
 
-    // ONE K image (round 4): the chunk-swizzled image of the transposing reads also serves the b128 row-fragment reads without bank
-    // conflicts (see bwd_dkdv_kernel), so K is fetched once per tile, not twice: 8 instead of 12 LDS-DMA instructions per 32 keys
-    unsigned char *k_tr = smem + (size_t)wave * wave_lds;   // K, transposable image (row fragments are read from it too)
-    unsigned char *v_row = k_tr + TILE;                     // V, row image
-    int *rg = (int *)(v_row + TILE);                        // [tpw][n][2]
-    unsigned *fullw = (unsigned *)(rg + ((2 * tpw * n + 3) & ~3));
-    unsigned *touchw = fullw + tpw * NW;
-    unsigned *kmask = touchw + tpw * NW;  // [16]
-
-    for (int i = lane; i < 2 * tpw * NW + 16; i += 64) fullw[i] = 0u;
+    unsigned char *lds = smem + (size_t)wave * wave_lds;
+    RowsSched sch(lds + 2 * Geo<D>::TILE_BYTES, tpw, n, NW, ntok);
+    for (int i = lane; i < 2 * tpw * NW + 16; i += 64) sch.fullw[i] = 0u;
     for (int r = 0; r < ntok; ++r) {
         const int64_t row = ((int64_t)b * P.S + tw0 + r) * P.G + g;
         if (lane < n) {
             const int32_t *in = P.ranges + (row * n + lane) * 2;
             const int s = min(max(in[0], 0), P.S_kv);
             const int e = min(max(in[1], s), P.S_kv);
-            rg[2 * (r * n + lane)] = s;
-            rg[2 * (r * n + lane) + 1] = e;
+            sch.rg[2 * (r * n + lane)] = s;
+            sch.rg[2 * (r * n + lane) + 1] = e;
         }
     }
-    wave_lds_fence();
-    for (int p = lane; p < ntok * n; p += 64) {
-        const int r = p / n;
-        const int s = rg[2 * p], e = rg[2 * p + 1];
-        if (e > s) {
-            const int ta = s >> 5, tb = (e - 1) >> 5;
-            const int fa = (s + 31) >> 5, fb = (e >> 5) - 1;
-            for (int w = ta >> 5; w <= (tb >> 5); ++w) {
-                const int base = 32 * w;
-                bwd_lds_or(&touchw[r * NW + w], bwd_bit_span(max(ta, base) - base, min(tb, base + 31) - base));
-                const int flo = max(fa, base), fhi = min(fb, base + 31);
-                if (flo <= fhi) bwd_lds_or(&fullw[r * NW + w], bwd_bit_span(flo - base, fhi - base));
-            }
-        }
-    }
-    wave_lds_fence();
-    unsigned u0 = 0u, u1 = 0u;
-    for (int r = 0; r < ntok; ++r) {
-        if (lane < NW) u0 |= touchw[r * NW + lane];
-        if (lane + 64 < NW) u1 |= touchw[r * NW + 64 + lane];
-    }
-    unsigned long long nz0 = __ballot(u0 != 0u), nz1 = __ballot(u1 != 0u);
+    sch.build(lane);
 
     const int rho = lane & 15, q = lane >> 4;
     const int tok = rho / h, head = rho - tok * h;
     const bool used = tok < ntok;
     const int64_t orow = used ? ((((int64_t)b * P.S + tw0 + tok) * P.G + g) * h + head) : -1;  // row * h + head
 
-    x8 qf[KS], dof[KS];
-    load_col_frags<D>((const T *)P.Q + orow * D, used, q, qf);
-    load_col_frags<D>((const T *)P.dO + orow * D, used, q, dof);
-    float lse2 = 0.f, dlt = 0.f;
+    DqWave<T, D> w(P, lds, b, g, lane, orow, used);
     bool live = false;  // rows without any selected key have lse = -inf: every p is 0
     if (used) {
         const float l = P.lse[orow];
         live = l > -INFINITY;
-        lse2 = live ? l * LOG2E : 0.f;
-        dlt = delta[orow];
+        w.lse2 = live ? l * LOG2E : 0.f;
+        w.dlt = delta[orow];
     }
-    const float c2 = P.scale * LOG2E;
 
-    const KvSrc<D> kv = kv_src<T, D>(P, b, g, lane);
-    uint32_t kd_tr[NLD], vd_row[NLD];  // K into the transposable image, V into a row image
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-        const int r = RPI * i + kv.ld_row;
-        kd_tr[i] = kv.ld_row * kv.krowb + Gm::tr_piece(r, kv.ld_piece);
-        vd_row[i] = kv.ld_row * kv.vrowb + Gm::row_piece(r, kv.ld_piece);
-    }
-    uint32_t rd_row[KS], rd_krow[KS], rd_tr[MT];
-    frag_read_offsets<D>(rho, q, rd_row, rd_tr);
-#pragma unroll
-    for (int s = 0; s < KS; ++s) rd_krow[s] = Gm::tr_img(rho, 4 * s + q);
-    auto issue_dma = [&](int tok0) {
-#ifdef DQ_NODMA  // ablation (timing only, results meaningless): no K / V tile fetches
-        return;
-#endif
-#if defined(__HIP_DEVICE_COMPILE__)
-        typedef __attribute__((address_space(3))) void lds_void;
-        const int ks = uniform(tok0 * kv.krowb), vs = uniform(tok0 * kv.vrowb);
-        const bool whole = tok0 + 32 <= P.S_kv;
-        const int last = P.S_kv - 1 - tok0;  // rows past the end of K/V re-read the last row (masked: such a tile is never `full`)
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-            const int rowshift = whole ? 0 : (min(RPI * i + kv.ld_row, last) - kv.ld_row);
-            const int kso = whole ? ks + i * kv.kstep : ks, vso = whole ? vs + i * kv.vstep : vs;
-            const uint32_t kadd = whole ? 0u : (uint32_t)(rowshift * kv.krowb), vadd = whole ? 0u : (uint32_t)(rowshift * kv.vrowb);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(kv.krs, (lds_void *)(k_tr + i * 1024), 16, kd_tr[i] + kadd, kso, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(kv.vrs, (lds_void *)(v_row + i * 1024), 16, vd_row[i] + vadd, vso, 0, 0);
-        }
-#else
-        (void)tok0;
-#endif
-    };
-
-    int iw = 0;
-    unsigned ibits = 0u;
-    auto next_tile = [&]() -> int {
-        if (ibits == 0u) {
-            if (nz0) {
-                iw = __builtin_ctzll(nz0);
-                nz0 &= nz0 - 1ull;
-                ibits = (unsigned)__builtin_amdgcn_readlane((int)u0, iw);
-            } else if (nz1) {
-                const int w = __builtin_ctzll(nz1);
-                nz1 &= nz1 - 1ull;
-                ibits = (unsigned)__builtin_amdgcn_readlane((int)u1, w);
-                iw = 64 + w;
-            } else {
-                return -1;
-            }
-        }
-        const int bit = __builtin_ctz(ibits);
-        ibits &= ibits - 1u;
-        return 32 * iw + bit;
-    };
-
-    f32x4 dq[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m) dq[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    int cur = next_tile();
-    if (cur >= 0) issue_dma(32 * cur);
-    int cw = -1;
-    unsigned fw = 0u, tw = 0u;
+    // a tile reaching past the end of K/V is never `full`: its clamped rows are masked
+    int cur = sch.next_tile();
+    if (cur >= 0) w.fetch(32 * cur, 32 * cur + 32 <= P.S_kv, P.S_kv - 1 - 32 * cur);
     const unsigned rowbit = live ? (1u << tok) : 0u;
     while (cur >= 0) {
-        const int nxt = next_tile();
+        const int nxt = sch.next_tile();
         const int tok0 = 32 * cur;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        x8 kfr[2][KS], vfr[2][KS];
-        x4 ktr[2][MT];
-        read_row_frags<D>(k_tr, rd_krow, kfr);
-        read_row_frags<D>(v_row, rd_row, vfr);
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int m = 0; m < MT; ++m) ktr[u][m] = tr_read<x4>(k_tr + rd_tr[m] + u * 16 * BROWB);
-        if ((cur >> 5) != cw) {  // lane r < ntok caches row r's bitmap words of the current 32-tile group
-            cw = cur >> 5;
-            if (lane < ntok) {
-                fw = fullw[lane * NW + cw];
-                tw = touchw[lane * NW + cw];
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        if (nxt >= 0) issue_dma(32 * nxt);
-        const unsigned fullm = (unsigned)__ballot((fw >> (cur & 31)) & 1u);
-        const unsigned touchm = (unsigned)__ballot((tw >> (cur & 31)) & 1u);
+        w.read_frags();
+        sch.refresh(cur, lane);
+        w.refill(nxt >= 0, 32 * nxt, 32 * nxt + 32 <= P.S_kv, P.S_kv - 1 - 32 * nxt);
+        unsigned fullm, touchm;
+        sch.owners(cur, fullm, touchm);
         const unsigned partm = touchm & ~fullm;
-        if (partm) {  // partially covered by some row: that row's 32-key mask from its ranges
-            if (lane < 16) kmask[lane] = 0u;
-            wave_lds_fence();
-            for (int p = lane; p < ntok * n; p += 64) {
-                const int r = p / n;
-                const int lo = max(rg[2 * p], tok0) - tok0, hi = min(rg[2 * p + 1], tok0 + 32) - tok0;
-                if (((partm >> r) & 1u) && hi > lo) bwd_lds_or(&kmask[r], bwd_bit_span(lo, hi - 1));
-            }
-            wave_lds_fence();
-        }
+        if (partm) sch.rebuild_kmask(partm, tok0, lane);  // partially covered by some row: that row's 32-key mask from its ranges
         const bool on = (fullm & rowbit) != 0u;
         unsigned km = on ? 0xffffffffu : 0u;
         if (partm) {
-            if (partm & rowbit) km = kmask[tok];
+            if (partm & rowbit) km = sch.kmask[tok];
             km >>= 4 * q;  // bit 16u + j = key 16u + 4q + j of the tile
         }
-
-#ifdef DQ_NOCOMPUTE  // ablation (timing only): tile walk and fetches without the products
-        cur = nxt;
-        continue;
-#endif
-        f32x4 sacc[2], pacc[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            sacc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            pacc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int s = 0; s < KS; ++s) {
-                sacc[u] = M::mma32(kfr[u][s], qf[s], sacc[u]);
-                pacc[u] = M::mma32(vfr[u][s], dof[s], pacc[u]);
-            }
-        }
-        x8 dsf;
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float p = __builtin_amdgcn_exp2f(fmaf(sacc[u][j], c2, -lse2));
-                if (partm == 0u) p = on ? p : 0.f;  // every slot all-on or all-off: one predicate per lane (wave-uniform branch)
-                else if (!((km >> (16 * u + j)) & 1u)) p = 0.f;
-                dsf[4 * u + j] = Elt<T>::from_f(p * (pacc[u][j] - dlt) * P.scale);
-            }
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-            x8 a;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                a[j] = ktr[0][m][j];
-                a[4 + j] = ktr[1][m][j];
-            }
-            dq[m] = M::mma32(a, dsf, dq[m]);
-        }
+        w.accumulate(partm != 0u, on, km);
         cur = nxt;
     }
-    if (used) {
-        T *dQr = (T *)P.dQ + orow * D;
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-            x4 ov;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) ov[j] = Elt<T>::from_f(dq[m][j]);
-            *(x4 *)(dQr + 16 * m + 4 * q) = ov;
-        }
-    }
+    if (used) w.store((T *)P.dQ + orow * D, q);
 }
 
 // ------------------------------------------------------------------------------------------ 3. dK / dV (key-block-major)
@@ -506,7 +325,7 @@ template <typename T, int D>
 __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(SelAttnBwdParams P, const float *__restrict__ delta, float *__restrict__ part,
                                                         const unsigned long long *__restrict__ hitmap, const unsigned long long *__restrict__ fullmap,
                                                         int *__restrict__ flags, int rows_per_split, int nkb, int nbg, int nsplit) {
-    using M = BwdT<T>;
+    using M = MfmaT<T>;
     using Gm = Geo<D>;
     using x8 = typename M::x8;
     using x4 = typename M::x4;
@@ -656,9 +475,6 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(SelAttnBwdParams P, co
         float l2n = 0.f, dln = 0.f;
         unsigned long long mkn = 0ull;
         auto fetch_round = [&](int r0) {
-#ifdef DKDV_NOFETCH  // ablation (timing only): no global loads of Q / dO rows
-            return;
-#endif
 #pragma unroll
             for (int i = 0; i < NLD; ++i) {
                 const int p = tid + 256 * i, slot = p / PIECES, pc = p % PIECES;
@@ -713,11 +529,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(SelAttnBwdParams P, co
             // tools/ubench/issue_rates.hip: 19-20 reported cycles either way; the MFMA's k index is only a label, so k = 8q + r is slot
             // 4q + r of the first tile and k = 8q + 4 + r the same slot of the second, on both operands).  A second tile past the last
             // hit row is all zero rows (p = 1 times zero dO, dS = 0): it adds nothing.
-#ifdef DKDV_NOCOMPUTE  // ablation (timing only, results meaningless): staging and bookkeeping without the tile loop
-            const int ntile = 0;
-#else
             const int ntile = min(KB_NCT, (min(nhit - r0, rows_per_round) * h + 15) >> 4);
-#endif
             for (int ct = 0; ct < ntile; ct += 2) {
                 x8 pa8, dsa8;
 #pragma unroll
@@ -728,8 +540,8 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(SelAttnBwdParams P, co
                     for (int s = 0; s < KS; ++s) {
                         const x8 kb = KV_LDS ? *(const x8 *)(k_img + kvrd[s]) : kB[KV_LDS ? 0 : s];
                         const x8 vb = KV_LDS ? *(const x8 *)(v_img + kvrd[s]) : vB[KV_LDS ? 0 : s];
-                        S = M::mma32(*(const x8 *)(q_img + rd_row[s] + sbase * BROWB), kb, S);
-                        dP = M::mma32(*(const x8 *)(do_img + rd_row[s] + sbase * BROWB), vb, dP);
+                        S = M::mma(*(const x8 *)(q_img + rd_row[s] + sbase * BROWB), kb, S);
+                        dP = M::mma(*(const x8 *)(do_img + rd_row[s] + sbase * BROWB), vb, dP);
                     }
                     // accumulator rows = slots sbase + 4q + r, column = key 16 wave + rho
                     const f32x4 l2 = *(const f32x4 *)(s_lse2 + sbase + 4 * q);
@@ -757,8 +569,8 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(SelAttnBwdParams P, co
                 }
 #pragma unroll
                 for (int n = 0; n < MT; ++n) {
-                    const x4 d0 = tr_read<x4>(do_img + rd_tr[n] + 16 * ct * BROWB), d1 = tr_read<x4>(do_img + rd_tr[n] + 16 * (ct + 1) * BROWB);
-                    const x4 q0 = tr_read<x4>(q_img + rd_tr[n] + 16 * ct * BROWB), q1 = tr_read<x4>(q_img + rd_tr[n] + 16 * (ct + 1) * BROWB);
+                    const x4 d0 = M::tr(do_img + rd_tr[n] + 16 * ct * BROWB), d1 = M::tr(do_img + rd_tr[n] + 16 * (ct + 1) * BROWB);
+                    const x4 q0 = M::tr(q_img + rd_tr[n] + 16 * ct * BROWB), q1 = M::tr(q_img + rd_tr[n] + 16 * (ct + 1) * BROWB);
                     x8 db, qb;
 #pragma unroll
                     for (int jj = 0; jj < 4; ++jj) {
@@ -767,8 +579,8 @@ __global__ __launch_bounds__(256, 2) void bwd_dkdv_kernel(SelAttnBwdParams P, co
                         qb[jj] = q0[jj];
                         qb[4 + jj] = q1[jj];
                     }
-                    dV[n] = M::mma32(pa8, db, dV[n]);
-                    dK[n] = M::mma32(dsa8, qb, dK[n]);
+                    dV[n] = M::mma(pa8, db, dV[n]);
+                    dK[n] = M::mma(dsa8, qb, dK[n]);
                 }
             }
             __syncthreads();
@@ -895,45 +707,41 @@ size_t sel_attn_bwd_mfma_workspace(int64_t R, int h, int S, int64_t nbg, int S_k
     return bwd_ws_layout(R, h, S, nbg, S_kv, D).total;
 }
 
+// The dQ launch.  The rows of one wave share the K/V tile images when 16/h >= 2 rows fit the MFMA columns (NSA_HIP_SEL_ROWS=0: one row
+// per wave).  Workgroups of 4 waves go (b,g)-major (map_mode 1; 2 = whole pairs per XCD, see wg_pair); short sequences (S < 16) would leave
+// most waves of such a workgroup idle, so the one-row kernel then takes the rows as they come (map_mode 0).
 template <typename T, int D>
-static int launch_bwd_t(const SelAttnBwdParams &P, float *delta, hipStream_t st) {
-    const int64_t nrh = P.R * P.h;
-    if (!P.skip_delta_dq) {
-        hipLaunchKernelGGL((bwd_delta_kernel<T, D>), dim3((unsigned)((nrh * (D / 8) + 255) / 256)), dim3(256), 0, st, (const T *)P.O,
-                           (const T *)P.dO, delta, nrh, P.Dv);
-        NSA_LAUNCH_CHECK("bwd_delta");
+static int launch_bwd_dq(const SelAttnBwdParams &P, const float *delta, hipStream_t st) {
+    const int tpw = tuning(TUNE_SEL_ROWS) == 0 ? 1 : 16 / P.h;
+    const int nw = rows_sched_words(P.S_kv);
+    const bool rows = tpw >= 2 && P.S >= 2 * tpw && P.n >= 1 && P.n <= 64 && nw <= 128;
+    const int rpw = rows ? tpw : 1;                                         // rows per wave
+    const int64_t nbg = P.R / P.S, W = ((P.S + rpw - 1) / rpw + 3) / 4;     // workgroups per (b,g)
+    const bool fits = nbg * W < ((int64_t)1 << 31);
+    // 34 KiB (D = 64), 66 KiB (D = 128) of tiles and segment list per workgroup of the one-row kernel
+    const int wave_lds = rows ? 2 * Geo<D>::TILE_BYTES + rows_sched_bytes(tpw, P.n, nw) : Geo<D>::WAVE_LDS;
+    const size_t lds = 4 * (size_t)wave_lds;
+    NSA_CHECK_ARG(!rows || (fits && lds <= 160 * 1024), "bwd_dq_rows: launch too large");
+    const bool pairs = rows || (P.S >= 16 && fits);
+    const int map_mode = !pairs ? 0 : (nbg % 8 == 0) ? 2 : 1;
+    const dim3 grid((unsigned)(pairs ? nbg * W : (P.R + 3) / 4));
+    const void *k = rows ? (const void *)bwd_dq_rows_kernel<T, D> : (const void *)bwd_dq_kernel<T, D>;
+    if (lds > 64 * 1024) NSA_HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (rows) {
+        hipLaunchKernelGGL((bwd_dq_rows_kernel<T, D>), grid, dim3(256), lds, st, P, delta, map_mode, tpw, nw, wave_lds);
+        NSA_LAUNCH_CHECK("bwd_dq_rows");
+    } else {
+        hipLaunchKernelGGL((bwd_dq_kernel<T, D>), grid, dim3(256), lds, st, P, delta, map_mode);
+        NSA_LAUNCH_CHECK("bwd_dq");
     }
-    int map_mode = 0;
-    unsigned grid = (unsigned)((P.R + 3) / 4);
-    if (P.S >= 16) {
-        const int64_t nbg = P.R / P.S, W = (P.S + 3) / 4;
-        if (nbg * W < ((int64_t)1 << 31)) {
-            map_mode = (nbg % 8 == 0) ? 2 : 1;
-            grid = (unsigned)(nbg * W);
-        }
-    }
-    constexpr size_t lds = 4 * (size_t)bwd_dq_wave_lds<D>();  // 50 KiB (D = 64), 98 KiB (D = 128: one workgroup per CU)
+    return NSA_OK;
+}
+
+template <typename T, int D>
+static int launch_bwd_t(const SelAttnBwdParams &P, int dtype, float *delta, hipStream_t st) {
     if (!P.skip_delta_dq) {
-        // rows of one wave share the K/V tile images when 16/h >= 2 rows fit the MFMA columns (NSA_HIP_SEL_ROWS=0: one row per wave)
-        int tpw = 16 / P.h;
-        if (tuning(TUNE_SEL_ROWS) == 0) tpw = 1;
-        const int nw = ((P.S_kv + 31) / 32 + 31) / 32;
-        if (tpw >= 2 && P.S >= 2 * tpw && P.n >= 1 && P.n <= 64 && nw <= 128) {
-            const int rg_ints = (2 * tpw * P.n + 3) & ~3, bm_ints = (2 * tpw * nw + 16 + 3) & ~3;
-            const int wave_lds = 2 * 32 * Geo<D>::ROWB + 4 * (rg_ints + bm_ints);
-            const int64_t nbg2 = P.R / P.S, ngrp = (P.S + tpw - 1) / tpw, W4 = (ngrp + 3) / 4;
-            NSA_CHECK_ARG(nbg2 * W4 < ((int64_t)1 << 31) && 4 * (size_t)wave_lds <= 160 * 1024, "bwd_dq_rows: launch too large");
-            if (4 * (size_t)wave_lds > 64 * 1024)
-                NSA_HIP_TRY(hipFuncSetAttribute((const void *)bwd_dq_rows_kernel<T, D>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * wave_lds));
-            hipLaunchKernelGGL((bwd_dq_rows_kernel<T, D>), dim3((unsigned)(nbg2 * W4)), dim3(256), 4 * (size_t)wave_lds, st, P, (const float *)delta,
-                               (nbg2 % 8 == 0) ? 2 : 1, tpw, nw, wave_lds);
-            NSA_LAUNCH_CHECK("bwd_dq_rows");
-        } else {
-            if (lds > 64 * 1024)
-                NSA_HIP_TRY(hipFuncSetAttribute((const void *)bwd_dq_kernel<T, D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((bwd_dq_kernel<T, D>), dim3(grid), dim3(256), lds, st, P, (const float *)delta, map_mode);
-            NSA_LAUNCH_CHECK("bwd_dq");
-        }
+        if (const int rc = launch_bwd_delta(P.O, P.dO, delta, P.R * P.h, P.Dv, dtype, st)) return rc;
+        if (const int rc = launch_bwd_dq<T, D>(P, delta, st)) return rc;
     }
     const int64_t nbg = (int64_t)(P.R / P.S);  // (at most 65535: both entry points test it)
     const BwdWs W = bwd_ws_layout(P.R, P.h, P.S, nbg, P.S_kv, D);
@@ -970,7 +778,7 @@ extern "C" __attribute__((visibility("default"))) int nsa_dbg_read(void *host) {
 #endif
 int launch_sel_attn_bwd_mfma(const SelAttnBwdParams &P, int dtype, float *delta_ws, hipStream_t st) {
     NSA_CHECK_ARG(slabs_under_2gib(P), "bwd MFMA: one (b,g) K/V slab must be smaller than 2 GiB");
-    return with_elt<false>(dtype, [&](auto t) { return P.Dk == 64 ? launch_bwd_t<decltype(t), 64>(P, delta_ws, st) : launch_bwd_t<decltype(t), 128>(P, delta_ws, st); });
+    return with_elt<false>(dtype, [&](auto t) { return P.Dk == 64 ? launch_bwd_t<decltype(t), 64>(P, dtype, delta_ws, st) : launch_bwd_t<decltype(t), 128>(P, dtype, delta_ws, st); });
 }
 
 int launch_bwd_delta(const void *O, const void *dO, float *delta, int64_t n_rows, int Dv, int dtype, hipStream_t st) {

@@ -7,37 +7,26 @@
 // is brought into LDS once for all TPW rows and each row masks the keys it did not select.  At S = 4096 the union of 8
 // rows is ~0.4x the sum of their selections, which is the factor the L2 gather shrinks by.
 //
-// Per wave: (1) the rows' ranges go to LDS (from the fused selector, sel_select_row.hpp, or from the ranges tensor);
-// (2) two bitmaps per row over 32-key tiles -- `touch` (some key of the tile selected) and `full` (a single range covers
-// the whole tile) -- are built with LDS atomics, one (row, range) pair per lane; their OR over the rows is the tile
-// schedule; (3) tiles are walked in ascending order with one tile of LDS-DMA prefetch.  A tile that every row covers in
-// full takes the mask-free path of the band kernel; otherwise each slot applies a 32-bit key mask (all ones, zero, or
-// -- for the few partially covered tiles, e.g. the causal clamp at t+1 -- a mask rebuilt from the row's ranges), and
-// column tiles none of whose rows touch the key tile are skipped.  Union semantics of overlapping ranges
-// (attention_kernels.py:721-732) fall out of the bitmaps: no sorting / merging of ranges is needed.
+// Per wave: the rows' ranges (from the fused selector, sel_select_row.hpp, or from the ranges tensor) feed the tile
+// schedule of attn_rows_schedule.hpp (per-row `touch` / `full` bitmaps over 32-key tiles, their union walked in ascending
+// order), here with one tile of LDS-DMA prefetch.  A tile that every row covers in full takes the mask-free path of the
+// band kernel; otherwise each slot applies a 32-bit key mask (all ones, zero, or -- for the few partially covered tiles,
+// e.g. the causal clamp at t+1 -- a mask rebuilt from the row's ranges), and column tiles none of whose rows touch the
+// key tile are skipped.
 // Softmax (deferred max), S^T / O^T formulation, tile geometry and the epilogue are those of band_attn_mfma.hip.
 #include <stdlib.h>
 
 #include "attn_mfma_tiles.hpp"
+#include "attn_rows_schedule.hpp"
 #include "sel_select_row.hpp"
 
 namespace nsa {
-
-__device__ __forceinline__ unsigned bit_span(int lo, int hi) {  // bits lo..hi inclusive, 0 <= lo <= hi <= 31
-    const unsigned up = hi >= 31 ? 0xffffffffu : ((1u << (hi + 1)) - 1u);
-    return up & ~((1u << lo) - 1u);
-}
 
 // one v_max3_f32 (fmaxf makes hipcc canonicalise every MFMA-derived operand with a v_max x,x first)
 __device__ __forceinline__ float max3f(float a, float b, float c) {
     float r;
     asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
-}
-
-__device__ __forceinline__ void lds_or(unsigned *p, unsigned v) {  // ds_or_b32: stays in the wave's in-order DS queue
-    typedef __attribute__((address_space(3))) unsigned lds_u32;
-    __hip_atomic_fetch_or((lds_u32 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
 }
 
 // RS: row sums of P on the matrix pipe (l += ones . P^T, one MFMA per tile instead of 8 v_add; see sel_attn_blocks_mfma.hip)
@@ -71,10 +60,7 @@ __global__ __launch_bounds__(256, 2) void sel_attn_rows_mfma_kernel(SelAttnParam
 
     unsigned char *kl = smem + (size_t)wave * P.wave_lds;
     unsigned char *vl = kl + G_::TILE_BYTES;
-    int *rg = (int *)(vl + G_::TILE_BYTES);                   // [tpw][n][2] clamped ranges
-    unsigned *fullw = (unsigned *)(rg + ((2 * tpw * n + 3) & ~3));  // [tpw][NW]
-    unsigned *touchw = fullw + tpw * NW;                      // [tpw][NW]
-    unsigned *kmask = touchw + tpw * NW;                      // [16]
+    RowsSched sch(vl + G_::TILE_BYTES, tpw, n, NW, ntok);
 
     // ---- per-slot constants; the Q loads are issued first so that their latency runs under the range / bitmap work below
     const int rho = lane & 15, q = lane >> 4;
@@ -102,7 +88,7 @@ __global__ __launch_bounds__(256, 2) void sel_attn_rows_mfma_kernel(SelAttnParam
     const unsigned usedmask = bit_span(0, ntok - 1);
 
     // ---- (1) bitmaps cleared, ranges of the rows -> LDS
-    for (int i = lane; i < 2 * tpw * NW + 16; i += 64) fullw[i] = 0u;
+    for (int i = lane; i < 2 * tpw * NW + 16; i += 64) sch.fullw[i] = 0u;
     for (int r = 0; r < ntok; ++r) {
         const int64_t row = ((int64_t)b * P.S + tw0 + r) * P.G + g;
         int s = 0, e = 0;
@@ -126,38 +112,15 @@ __global__ __launch_bounds__(256, 2) void sel_attn_rows_mfma_kernel(SelAttnParam
             s = in[0];
             e = in[1];
         }
-        if (lane < n) {
+        if (lane < n) {  // clamped to the keys that exist
             s = min(max(s, 0), P.S_kv);
             e = min(max(e, s), P.S_kv);
-            rg[2 * (r * n + lane)] = s;
-            rg[2 * (r * n + lane) + 1] = e;
+            sch.rg[2 * (r * n + lane)] = s;
+            sch.rg[2 * (r * n + lane) + 1] = e;
         }
     }
-    wave_lds_fence();
-
-    // ---- (2) tile bitmaps: one (row, range) pair per lane
-    for (int p = lane; p < ntok * n; p += 64) {
-        const int r = p / n;
-        const int s = rg[2 * p], e = rg[2 * p + 1];
-        if (e > s) {
-            const int ta = s >> 5, tb = (e - 1) >> 5;      // tiles touched
-            const int fa = (s + 31) >> 5, fb = (e >> 5) - 1;  // tiles covered completely: fa..fb
-            for (int w = ta >> 5; w <= (tb >> 5); ++w) {
-                const int base = 32 * w;
-                lds_or(&touchw[r * NW + w], bit_span(max(ta, base) - base, min(tb, base + 31) - base));
-                const int flo = max(fa, base), fhi = min(fb, base + 31);
-                if (flo <= fhi) lds_or(&fullw[r * NW + w], bit_span(flo - base, fhi - base));
-            }
-        }
-    }
-    wave_lds_fence();
-    // union over the rows = the tile schedule; kept in registers (lane w holds word w, NW <= 128): walking it costs no LDS round trips
-    unsigned u0 = 0u, u1 = 0u;
-    for (int r = 0; r < ntok; ++r) {
-        if (lane < NW) u0 |= touchw[r * NW + lane];
-        if (lane + 64 < NW) u1 |= touchw[r * NW + 64 + lane];
-    }
-    unsigned long long nz0 = __ballot(u0 != 0u), nz1 = __ballot(u1 != 0u);
+    // ---- (2) tile bitmaps and their union = the tile schedule
+    sch.build(lane);
 
     const unsigned char *Kb = (const unsigned char *)((const T *)P.K + (int64_t)b * P.ksb + (int64_t)g * P.ksg);
     const unsigned char *Vb = (const unsigned char *)((const T *)P.V + (int64_t)b * P.vsb + (int64_t)g * P.vsg);
@@ -222,54 +185,24 @@ __global__ __launch_bounds__(256, 2) void sel_attn_rows_mfma_kernel(SelAttnParam
 #pragma unroll
     for (int j = 0; j < 8; ++j) ones[j] = Elt<T>::from_f(1.f);
 
-    // ---- (3) tile schedule = set bits of the union bitmap, ascending (wave-uniform scalars)
-    int iw = 0;
-    unsigned ibits = 0u;
-    auto next_tile = [&]() -> int {
-        if (ibits == 0u) {
-            if (nz0) {
-                iw = __builtin_ctzll(nz0);
-                nz0 &= nz0 - 1ull;
-                ibits = (unsigned)__builtin_amdgcn_readlane((int)u0, iw);
-            } else if (nz1) {
-                const int w = __builtin_ctzll(nz1);
-                nz1 &= nz1 - 1ull;
-                ibits = (unsigned)__builtin_amdgcn_readlane((int)u1, w);
-                iw = 64 + w;
-            } else {
-                return -1;
-            }
-        }
-        const int bit = __builtin_ctz(ibits);
-        ibits &= ibits - 1u;
-        return 32 * iw + bit;
-    };
-    int cur = next_tile();
+    // ---- (3) the tiles of the schedule in ascending order
+    int cur = sch.next_tile();
     if (cur >= 0) issue_dma(32 * cur);
-    int cw = -1;
-    unsigned fw = 0u, tw = 0u;
 
     while (cur >= 0) {
-        const int nxt = next_tile();
+        const int nxt = sch.next_tile();
         const int tok0 = 32 * cur;
         x8 kfr[2][KS];
         x8 va[MT];
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // LDS-DMA completion is a vmcnt event
         read_row_frags<D>(kl, krd0, kfr);
         read_tr_frags<T, D>(vl, vrd0, va);
-        // ownership of this tile: bit r of fullm / touchm = row r covers it completely / selected at least one of its keys
-        if ((cur >> 5) != cw) {  // lane r < ntok caches row r's bitmap words of the current 32-tile group (refreshed once per word)
-            cw = cur >> 5;
-            if (lane < ntok) {
-                fw = fullw[lane * NW + cw];
-                tw = touchw[lane * NW + cw];
-            }
-        }
+        sch.refresh(cur, lane);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // fragments are in registers: the buffers may be refilled
         __builtin_amdgcn_sched_barrier(0);
         if (nxt >= 0) issue_dma(32 * nxt);
-        const unsigned fullm = (unsigned)__ballot((fw >> (cur & 31)) & 1u);
-        const unsigned touchm = (unsigned)__ballot((tw >> (cur & 31)) & 1u);
+        unsigned fullm, touchm;  // bit r: row r covers this tile completely / selected at least one of its keys
+        sch.owners(cur, fullm, touchm);
         const unsigned partm = touchm & ~fullm;
 
         if (NT > 1 && fullm == usedmask) {  // (NT = 1 keeps ONE path: the predicate costs 8 v_cndmask, a second path costs registers)
@@ -336,16 +269,7 @@ __global__ __launch_bounds__(256, 2) void sel_attn_rows_mfma_kernel(SelAttnParam
             }
         } else {
             // ---- mixed ownership: per-slot key masks; column tiles none of whose rows touch the tile are skipped
-            if (partm) {  // partially covered by some row: rebuild that row's 32-key mask from its ranges
-                if (lane < 16) kmask[lane] = 0u;
-                wave_lds_fence();
-                for (int p = lane; p < ntok * n; p += 64) {
-                    const int r = p / n;
-                    const int lo = max(rg[2 * p], tok0) - tok0, hi = min(rg[2 * p + 1], tok0 + 32) - tok0;
-                    if (((partm >> r) & 1u) && hi > lo) lds_or(&kmask[r], bit_span(lo, hi - 1));
-                }
-                wave_lds_fence();
-            }
+            if (partm) sch.rebuild_kmask(partm, tok0, lane);  // partially covered by some row
             // one column tile at a time (short live ranges: the mixed path must not cost the kernel its second wave per SIMD)
 #pragma unroll
             for (int nn = 0; nn < NT; ++nn) {
@@ -353,7 +277,7 @@ __global__ __launch_bounds__(256, 2) void sel_attn_rows_mfma_kernel(SelAttnParam
                 const bool on = (fullm & rowbit[nn]) != 0u;
                 unsigned km = on ? 0xffffffffu : 0u;
                 if (partm) {
-                    if (partm & rowbit[nn]) km = kmask[tokn[nn]];
+                    if (partm & rowbit[nn]) km = sch.kmask[tokn[nn]];
                     km >>= 4 * q;  // bit 16u + j of km = key 16u + 4q + j of the tile
                 }
                 f32x4 sacc[2];
@@ -467,12 +391,10 @@ template <typename T, int D, int NT>
 static int launch_rows_t(const SelAttnParams &P0, int tpw, hipStream_t st) {
     SelAttnParams P = P0;
     P.tpw = tpw;
-    P.nw = ((P.S_kv + 31) / 32 + 31) / 32;
+    P.nw = rows_sched_words(P.S_kv);
     P.nsplit = 1;
     P.part = nullptr;
-    const int rg_ints = (2 * tpw * P.n + 3) & ~3;
-    const int bm_ints = (2 * tpw * P.nw + 16 + 3) & ~3;
-    P.wave_lds = 2 * Geo<D>::TILE_BYTES + 4 * (rg_ints + bm_ints);
+    P.wave_lds = 2 * Geo<D>::TILE_BYTES + rows_sched_bytes(tpw, P.n, P.nw);
     const size_t lds = 4 * (size_t)P.wave_lds;
     NSA_CHECK_ARG(lds <= 160 * 1024, "sel_attn_rows: %zu B of LDS needed", lds);
     const int64_t nbg = P.R / P.S;

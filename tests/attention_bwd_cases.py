@@ -65,7 +65,12 @@ BAND_CASES = {c.name: c for c in [
     Case("long_w33", 2, 2050, 4, 6, 2050, stride=16, residues=(1, 14, 15), band=dict(a=0, dd=1, c=0, w=33)),
     Case("long_cmp", 2, 2050, 4, 6, 127, stride=16, residues=(1, 14, 15), band=_CMP),
 ]}
-CASES = {**SEL_CASES, **BAND_CASES}
+# ---- selection cases added later: they go behind the bands, because inputs() seeds from a case's position in CASES ------------------------
+LATE_CASES = {c.name: c for c in [
+    # S < 2 * (16 / h): the one-row dQ kernel on its row-linear grid (12 rows, 3 workgroups of 4 waves, no (b,g)-major map)
+    Case("S3", B=2, S=3, G=2, h=6, S_kv=100, n=3, stride=3),
+]}
+CASES = {**SEL_CASES, **BAND_CASES, **LATE_CASES}
 
 
 def _rng(*key):
