@@ -559,6 +559,51 @@ NSA_API int nsa_sel_decode_ragged(const void *Q, const void *K_cmp, const void *
 NSA_API int nsa_sel_decode_ragged_plan(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int n_top, int dtype,
                                int t_max, int *launches /* host */, int *form /* host */);
 
+/* ---------------------------------------------------------------------------------------
+ * The ragged-batch decode step of the selected branch over PAGED caches: nsa_sel_decode_ragged in every respect except where row (b,s,g)
+ * finds its cache rows.  The caches are pools of fixed-size pages that a serving layer hands out as sequences grow and takes back when
+ * they finish; a block table says which pool page holds which 1024 tokens of which sequence.
+ *   page_tokens   tokens per page.  Only 1024 is built -- one scorer chunk (64 compressed rows at d = 16) and 16 selection blocks of
+ *                 l' = 64, so a chunk of K_cmp, a gathered K/V block and a forced block each lie inside exactly one page and the table
+ *                 costs one wave-uniform lookup per chunk.  Every other value is declined with a message that names it.
+ *   K_pool, V_pool [n_pages, G, 1024, D]; Kc_pool [n_pages, G, 64, D].  Each with a page stride (k_stride_p ...), a group stride and a row
+ *                 stride in elements.  Rules as for the ragged call's caches: strides in multiples of 8 elements, 16-byte aligned bases, V
+ *                 rows contiguous (v_stride_s = Dv), K rows contiguous (k_stride_s = Dk) for the forced-block prefetch, else no prefetch.
+ *                 A pool may be of any size (beyond 2 GiB too): page bases are formed in 64 bits, and the only 32-bit byte offsets are
+ *                 those of a row inside one (page, group) plane -- 1024 rows of K / V, 64 of K_cmp -- which must stay under 2 GiB
+ *                 (1024 * stride_s * 2 bytes; declined otherwise).
+ *   block_table   device int32 [B, max_pages], table_stride elements between its rows (>= max_pages).  Entry j of sequence b is the pool
+ *                 page that holds tokens [1024 j, 1024 j + 1024) of its K and V and compressed rows [64 j, 64 j + 64) of its K_cmp: one
+ *                 page id indexes all three pools.  The host never reads the table, as it never reads t_pos.
+ *   t_pos, t_max, S   as in nsa_sel_decode_ragged.  The capacity that call takes from S_kv is max_pages * 1024 here; S_cmp and S_sel are
+ *                 the metadata bounds of min(t_max, capacity - 1) + 1 tokens.  max_pages <= 2^20.
+ * Inactive sequences: the ragged call's rule -- t_pos[b] < 0, or t_pos[b] + S - 1 > min(t_max, capacity - 1) -- plus one case: any table
+ * entry the sequence NEEDS lies outside [0, n_pages).  The entries it needs are j = 0 .. (t_pos[b] + S - 1) >> 10; entries behind them are
+ * never read.  An inactive sequence gets zeros in all of its O and ranges_out rows and reads nothing from the pools: its workgroups check
+ * the needed entries once, before their first cache read, and leave.  Nothing is clamped silently, and no table value can send an access
+ * outside the pools: only entries inside [0, n_pages) are ever turned into an address.
+ * ONE launch or none: the form and the waves per row are planned from t_max and B*S*G exactly as nsa_sel_decode_ragged plans them, with
+ * the same declines and messages (dtype, Dk = Dv in {64, 128}, h <= 16, the default block geometry, S <= 16, a t_max beyond the unsplit
+ * forms, DECODE_STEP = 0, DECODE_UNFUSED = 1), and in addition NSA_ERR_INVALID for page_tokens != 1024, a null table, max_pages < 1,
+ * n_pages < 1, a table stride below max_pages, misaligned pools or strides, and row strides that leave the 32-bit in-plane offsets.
+ * nsa_sel_decode_paged_plan: *launches = 1 and *form = 0 / 1, or *launches = 0 and *form = -1 for a declined shape or page size (status
+ * NSA_OK).  workspace: nsa_sel_decode_paged_workspace() bytes (0 today); may be null.
+ * Bits: for a table that scatters contiguous caches into pages, in any order, ranges and O are those of nsa_sel_decode_ragged on the
+ * contiguous caches bit for bit -- the same form and waves, the same arithmetic on the same values in the same order.  The existing entry
+ * points are unchanged: the paged form is a kernel instantiation of its own.
+ * ------------------------------------------------------------------------------------- */
+NSA_API size_t nsa_sel_decode_paged_workspace(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int n_top, int dtype);
+NSA_API int nsa_sel_decode_paged(const void *Q, const void *Kc_pool, const void *K_pool, const void *V_pool,
+                         const int32_t *block_table /* device, [B,max_pages] */, int64_t table_stride, int n_pages, int max_pages,
+                         int page_tokens, const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int32_t *ranges_out,
+                         void *O, const int32_t *t_pos /* device, [B] */, int t_max /* host */, int B, int S, int G, int h, int Dk, int Dv,
+                         int S_cmp, int S_sel, int l, int d, int l_sel, int n_top, int64_t kc_stride_p, int64_t kc_stride_g,
+                         int64_t kc_stride_s, int64_t k_stride_p, int64_t k_stride_g, int64_t k_stride_s, int64_t v_stride_p,
+                         int64_t v_stride_g, int64_t v_stride_s, int dtype, float scale, void *workspace, size_t workspace_bytes,
+                         void *stream);
+NSA_API int nsa_sel_decode_paged_plan(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int max_pages, int page_tokens,
+                              int n_top, int dtype, int t_max, int *launches /* host */, int *form /* host */);
+
 /* Band attention forward with per-sequence positions (the sliding and the compressed branch of a ragged decode step): nsa_band_attn_fwd
  * with t0 replaced by a device array.  Query row (b, t) sits at absolute position t_pos[b] + t; hi and lo follow from it by the formula
  * above.  t_max: host upper bound of t_pos[b] + S - 1 (the host never reads t_pos).  Route, split count and workspace are those of the

@@ -25,6 +25,8 @@ from .selection_attention import (  # noqa: F401
     selection_attention_first_key_parity,
     selection_attention_head_causal_parity,
     selection_attention_hip,
+    selection_decode_paged,
+    selection_decode_paged_plan,
     selection_decode_ragged,
     selection_decode_ragged_plan,
     selection_decode_rows,

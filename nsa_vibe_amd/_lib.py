@@ -104,6 +104,9 @@ SIGNATURES = {
     "nsa_sel_decode_ragged_workspace": (_sz, [_i] * 10),
     "nsa_sel_decode_ragged": (_i, [_vp] * 10 + [_i] * 14 + [_i64] * 9 + [_i, _f, _vp, _sz, _vp]),
     "nsa_sel_decode_ragged_plan": (_i, [_i] * 12 + [C.POINTER(_i)] * 2),
+    "nsa_sel_decode_paged_workspace": (_sz, [_i] * 10),
+    "nsa_sel_decode_paged": (_i, [_vp] * 5 + [_i64] + [_i] * 3 + [_vp] * 6 + [_i] * 13 + [_i64] * 9 + [_i, _f, _vp, _sz, _vp]),
+    "nsa_sel_decode_paged_plan": (_i, [_i] * 13 + [C.POINTER(_i)] * 2),
     "nsa_band_attn_fwd_ragged_workspace": (_sz, [_i] * 7),
     "nsa_band_attn_fwd_ragged": (_i, [_vp] * 6 + [_i] * 8 + [_i64] * 6 + [_i] * 4 + [_i, _f, _i, _vp, _sz, _vp]),
     "nsa_batched_ranges_width": (_i, [_i] * 6),

@@ -5,6 +5,7 @@
 // each launch's grid / block / LDS bytes, the host memsets, and the status and nsa_hip_last_error() of the complete call.
 //   dispatch_check <path of libnsa_sel_hip.so>      prints one JSON object, a member per case
 //   dispatch_check <library> ragged | layer_ragged  the cases of the entry points with per-sequence positions instead
+//   dispatch_check <library> paged                  the cases of the ragged decode step over paged caches (nsa_sel_decode_paged)
 #include <dlfcn.h>
 #include <math.h>
 #include <stdio.h>
@@ -503,6 +504,98 @@ static void ragged_cases() {
     band_case("sliding_f32_generic", 5, 1, NSA_DT_F32, 1000, false, true);
 }
 
+// ---- dispatch_check <library> paged: the ragged decode step over paged caches (nsa_sel_decode_paged), cases of their own like `ragged`.  The
+// block table, like the position array, is a device pointer the host must never read: it is handed over as an address inside a named buffer
+// filled with 0x7f bytes (no valid page id) and shows up again in the argument block of the launch, with its stride, n_pages and the
+// three page strides.
+static void paged_cases() {
+    const int G = 2, h = 6, n = 16;
+    const size_t MB = 1 << 20;
+    void *Q = dev(MB), *K = dev(MB), *V = dev(MB), *Kc = dev(MB), *O = dev(MB);
+    float *csc_vals = (float *)dev(MB);
+    int32_t *ranges = (int32_t *)dev(MB), *t_pos = (int32_t *)dev(MB, 0x7f), *table = (int32_t *)dev(MB, 0x7f), *csc_ptr = (int32_t *)dev(MB),
+            *csc_rows = (int32_t *)dev(MB);
+    g_named = {{"Q", Q, MB}, {"K_pool", K, MB}, {"V_pool", V, MB}, {"Kc_pool", Kc, MB}, {"O", O, MB}, {"ranges", ranges, MB}, {"t_pos", t_pos, MB},
+               {"table", table, MB}};
+    auto ncmp = [](int t) { return t + 1 < 32 ? 0 : (t + 1 - 32) / 16 + 1; };
+    auto paged_fn = NSA_FN(nsa_sel_decode_paged);
+    auto plan_fn = NSA_FN(nsa_sel_decode_paged_plan);
+    struct Case {
+        int B = 3, S = 1, D = 64, t_max = 100, dtype = NSA_DT_BF16, page_tokens = 1024, n_pages = 40, max_pages = 0 /* 0: what t_max needs */;
+        int64_t table_stride = 0 /* 0: max_pages + 3 */, k_page_stride = 0 /* 0: G * 1024 * D */;
+        void *K = nullptr;
+        const int32_t *table = nullptr, *t_pos = nullptr;
+    };
+    auto paged_case = [&](const char *label, const std::function<void(Case &)> &tweak) {
+        Case c;
+        c.K = K;
+        c.table = table + 7;
+        c.t_pos = t_pos + 5;
+        tweak(c);
+        const int max_pages = c.max_pages ? c.max_pages : c.t_max / 1024 + 1;
+        const int cap = max_pages * 1024, te = c.t_max < cap - 1 ? c.t_max : cap - 1;
+        const int S_cmp = ncmp(te), S_sel = (te + 1 + 63) / 64;
+        const int64_t tstride = c.table_stride ? c.table_stride : max_pages + 3;
+        const int64_t kg = (int64_t)1024 * c.D, cg = (int64_t)64 * c.D, kp = c.k_page_stride ? c.k_page_stride : G * kg;
+        auto call = [&] {
+            return paged_fn(Q, Kc, c.K, V, c.table, tstride, c.n_pages, max_pages, c.page_tokens, csc_ptr, csc_rows, csc_vals, ranges, O, c.t_pos, c.t_max, c.B, c.S, G,
+                            h, c.D, c.D, S_cmp, S_sel, 32, 16, 64, n, G * cg, cg, c.D, kp, kg, c.D, G * kg, kg, c.D, c.dtype, 0.f, nullptr, 0, nullptr);
+        };
+        run((std::string("sel_decode_paged/") + label).c_str(), call, [&] {
+            int launches = -1, form = -2;
+            const int prc = plan_fn(c.B, c.S, G, h, c.D, c.D, S_cmp, S_sel, max_pages, c.page_tokens, n, c.dtype, c.t_max, &launches, &form);
+            std::string o = "\"plan\": " + Obj().i("rc", prc).i("launches", launches).i("form", form).str();
+            int at = -1;
+            for (size_t i = 0; i < g_names.size(); ++i)
+                if (g_names[i] == "decode_paged launch") at = (int)i;
+            if (at < 0) return o + ", \"step\": null";
+            peek<nsa::DecStepParams>(at);
+            peek<nsa::DecAttnArgs>(at, 3);
+            g_refuse_at = -1;
+            g_launches = 0;
+            call();
+            const nsa::DecStepParams P = peeked<nsa::DecStepParams>(0);
+            const nsa::DecAttnArgs A = peeked<nsa::DecAttnArgs>(1);
+            return o + ", \"step\": " +
+                   Obj().p("Q", P.Q).p("Kc", P.Kc).i("R", P.R).i("G", P.G).i("h", P.h).i("S_cmp", P.S_cmp).i("S_sel", P.S_sel).i("NS", P.NS).i("nchunk", P.nchunk)
+                       .i("S", P.S).p("t_pos", P.t_pos).i("t_max", P.t_max).p("block_table", P.block_table).i("bt_stride", P.bt_stride).i("n_pages", P.n_pages)
+                       .i("kc_page_stride", P.csb).p("K", A.K).p("V", A.V).i("k_page_stride", A.ksb).i("v_page_stride", A.vsb).i("capacity", A.S_kv).str();
+        });
+    };
+    paged_case("t_max100", [](Case &) {});
+    paged_case("t_max100_S4", [](Case &c) { c.S = 4; });
+    paged_case("t_max20_no_compressed_token", [](Case &c) { c.t_max = 20; });
+    paged_case("t_max5000_max_pages9", [](Case &c) { c.t_max = 5000; c.max_pages = 9; });
+    paged_case("t_max40000_form1", [](Case &c) { c.B = 1; c.t_max = 40000; });
+    paged_case("k_page_stride_3GiB", [](Case &c) { c.k_page_stride = (int64_t)3 << 29; });  // elements of 2 bytes: 3 GiB between pages
+    paged_case("page_tokens64_declined", [](Case &c) { c.page_tokens = 64; });
+    paged_case("null_table", [](Case &c) { c.table = nullptr; });
+    paged_case("max_pages_minus1", [](Case &c) { c.max_pages = -1; });
+    paged_case("n_pages0", [](Case &c) { c.n_pages = 0; });
+    paged_case("table_stride_below_max_pages", [](Case &c) { c.t_max = 5000; c.table_stride = 4; });
+    paged_case("D128_t_max20000_declined", [](Case &c) { c.D = 128; c.t_max = 20000; });
+    paged_case("t_max70000_declined", [](Case &c) { c.B = 1; c.t_max = 70000; });
+    paged_case("B200_t_max40000_declined", [](Case &c) { c.B = 200; c.t_max = 40000; });
+    paged_case("f32_declined", [](Case &c) { c.dtype = NSA_DT_F32; });
+    paged_case("S17_declined", [](Case &c) { c.S = 17; });
+    paged_case("K_pool_2_bytes_off", [&](Case &c) { c.K = off(K, 2); });
+    paged_case("k_page_stride_not_8", [](Case &c) { c.k_page_stride = (int64_t)2 * 1024 * 64 + 4; });
+    paged_case("null_t_pos", [](Case &c) { c.t_pos = nullptr; });
+    NSA_FN(nsa_hip_set_tuning)("DECODE_STEP", 0);
+    paged_case("DECODE_STEP_0_declined", [](Case &) {});
+    NSA_FN(nsa_hip_set_tuning)("DECODE_STEP", 1);
+
+    // a row stride that puts a page's 1024 rows outside the 32-bit in-plane offsets (V rows must be contiguous, so it is K's): 2^20 elements
+    // = 2 MiB a row, 2 GiB a plane
+    {
+        const int64_t kss = (int64_t)1 << 20, kg = 1024 * kss, cg = 64 * 64;
+        run("sel_decode_paged/k_row_stride_2MiB", [&] {
+            return paged_fn(Q, Kc, K, V, table + 7, 4, 40, 1, 1024, csc_ptr, csc_rows, csc_vals, ranges, O, t_pos + 5, 100, 3, 1, G, h, 64, 64, ncmp(100), 2, 32, 16, 64, n,
+                            G * cg, cg, 64, G * kg, kg, kss, (int64_t)G * 1024 * 64, 1024 * 64, 64, NSA_DT_BF16, 0.f, nullptr, 0, nullptr);
+        });
+    }
+}
+
 // ---- dispatch_check <library> layer_ragged: the layer's ragged call (nsa_layer_decode_ragged), cases of their own like `ragged`.  Every
 // case prints the launchers in order with their geometry, the plan's answer for the same shape, and "positions": the position pointer and the
 // bound te as they arrive in the argument blocks of the four launches that depend on the position (projection, pooling, the selected branch,
@@ -602,7 +695,7 @@ static void layer_ragged_cases() {
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: dispatch_check <libnsa_sel_hip.so> [ragged | layer_ragged]\n");
+        fprintf(stderr, "usage: dispatch_check <libnsa_sel_hip.so> [ragged | layer_ragged | paged]\n");
         return 2;
     }
     g_lib = dlopen(argv[1], RTLD_NOW | RTLD_GLOBAL);
@@ -613,6 +706,12 @@ int main(int argc, char **argv) {
     if (argc >= 3 && !strcmp(argv[2], "ragged")) {  // the cases of the ragged entry points alone (tests/test_dispatch_ragged_host.py)
         printf("{");
         ragged_cases();
+        printf("\n}\n");
+        return 0;
+    }
+    if (argc >= 3 && !strcmp(argv[2], "paged")) {  // the paged decode step alone (tests/test_dispatch_paged_host.py)
+        printf("{");
+        paged_cases();
         printf("\n}\n");
         return 0;
     }

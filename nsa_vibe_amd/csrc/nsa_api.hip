@@ -723,6 +723,42 @@ int nsa::sel_decode_ragged_impl(const SelDecodeCall &c, const int32_t *t_pos, in
     return launch_decode_rows(c, (hipStream_t)stream, t_pos, t_max);
 }
 
+// The ragged step over paged caches.  c: K_cmp / K / V are the pools, kcb / ksb / vsb their PAGE strides, S_kv is filled here with the
+// capacity max_pages * 1024; S_cmp / S_sel are the metadata bounds of min(t_max, capacity - 1) + 1 tokens as in the ragged call.
+int nsa::sel_decode_paged_impl(const SelDecodeCall &c0, const DecPageTable &pt, int max_pages, int page_tokens, const int32_t *t_pos, int t_max, void *stream) {
+    NSA_CHECK_ARG(page_tokens == DEC_PAGE_TOKENS, "decode_paged: page_tokens = %d is not built: pages of 1024 tokens only (one scorer chunk of 64 compressed rows, "
+                                                  "16 selection blocks)", page_tokens);
+    NSA_CHECK_ARG(dtype_ok(c0.dtype), "decode_paged: unknown dtype %d", c0.dtype);
+    NSA_CHECK_ARG(max_pages >= 1 && max_pages <= (1 << 20), "decode_paged: max_pages = %d, must be in [1, 2^20]", max_pages);
+    NSA_CHECK_ARG(pt.n_pages >= 1, "decode_paged: n_pages = %d, the pools must hold at least one page", pt.n_pages);
+    SelDecodeCall c = c0;
+    c.S_kv = max_pages * DEC_PAGE_TOKENS;
+    NSA_CHECK_ARG(c.B >= 0 && c.S >= 0 && c.G >= 1 && c.h >= 1 && c.Dk >= 1 && c.Dv >= 1 && c.S_cmp >= 0 && c.S_sel >= 1, "decode_paged: bad sizes");
+    NSA_CHECK_ARG(c.n_top >= 1 && c.n_top <= 64, "decode_paged: n_top must be in [1,64]");
+    NSA_CHECK_ARG(t_max >= 0, "decode_paged: t_max (the host bound of t_pos[b] + S - 1) must not be negative");
+    const int te = std::min(t_max, c.S_kv - 1);
+    NSA_CHECK_ARG(c.S_cmp >= ragged_ncmp(te) && (int64_t)c.S_sel * 64 >= (int64_t)te + 1,
+                  "decode_paged: S_cmp / S_sel must describe at least min(t_max, max_pages * 1024 - 1) + 1 = %d tokens (got S_cmp = %d, S_sel = %d)", te + 1, c.S_cmp,
+                  c.S_sel);
+    if (c.rows() == 0) return NSA_OK;
+    NSA_CHECK_ARG(pt.table != nullptr, "decode_paged: null block table");
+    NSA_CHECK_ARG((uintptr_t)pt.table % 4 == 0 && pt.stride >= max_pages, "decode_paged: the block table must be 4-byte aligned with a row stride of at least max_pages = %d "
+                                                                          "(got %lld)", max_pages, (long long)pt.stride);
+    NSA_CHECK_ARG(c.Q && c.K && c.V && c.O && c.ranges_out && t_pos && (c.K_cmp || c.S_cmp == 0), "decode_paged: null pointer");
+    NSA_CHECK_ARG((uintptr_t)t_pos % 4 == 0, "decode_paged: t_pos must be 4-byte aligned");
+    const char *why = nullptr;
+    NSA_CHECK_ARG(decode_paged_shape_plan(c, t_max, nullptr, nullptr, &why), "decode_paged: %s (B = %d, S = %d, D = %d, t_max = %d)", why, c.B, c.S, c.Dk, t_max);
+    NSA_CHECK_ARG(c.d == 16 && c.l == 32 && c.l_sel == 64, "decode_paged: the default block geometry only (l = 32, d = 16, l' = 64)");
+    NSA_CHECK_ARG(decode_ragged_operands_ok(c), "decode_paged: Q and the three pools must be 16-byte aligned with page, group and row strides in multiples of 8 elements, "
+                                                "V rows contiguous and O 8-byte aligned");
+    // the kernel's only 32-bit byte offsets are those of a row inside one (page, group) plane: 1024 K / V rows, 64 compressed rows
+    const int64_t lim = (int64_t)1 << 31;
+    NSA_CHECK_ARG(c.kss >= 1 && c.vss >= 1 && c.kcs >= 1 && (int64_t)DEC_PAGE_TOKENS * c.kss * 2 < lim && (int64_t)DEC_PAGE_TOKENS * c.vss * 2 < lim &&
+                      (int64_t)(DEC_PAGE_TOKENS / 16) * c.kcs * 2 < lim,
+                  "decode_paged: the row strides put a page's rows outside the 32-bit offsets of one (page, group) plane (1024 rows of K / V, 64 of K_cmp: under 2 GiB each)");
+    return launch_decode_rows(c, (hipStream_t)stream, t_pos, t_max, &pt);
+}
+
 int nsa::band_attn_fwd_ragged_impl(const AttnCall &c, const Band &band, const int32_t *t_pos, int t_max) {
     NSA_CHECK_ARG(dtype_ok(c.dtype), "band_attn_fwd_ragged: unknown dtype %d", c.dtype);
     NSA_CHECK_ARG(c.B >= 0 && c.S >= 0 && c.G >= 1 && c.h >= 1 && c.Dk >= 1 && c.Dv >= 1 && c.S_kv >= 0, "band_attn_fwd_ragged: negative size");
@@ -756,6 +792,37 @@ int nsa_sel_decode_ragged(const void *Q, const void *K_cmp, const void *K, const
     const SelDecodeCall c{Q, K_cmp, K, V, csc_ptr, csc_rows, csc_vals, ranges_out, O, B, S, G, h, Dk, Dv, S_cmp, S_sel, S_kv, l, d, l_sel, n_top, 0,
                           kcb, kcg, kcs, ksb, ksg, kss, vsb, vsg, vss, dtype, scale};
     return sel_decode_ragged_impl(c, t_pos, t_max, stream);
+}
+
+int nsa_sel_decode_paged(const void *Q, const void *Kc_pool, const void *K_pool, const void *V_pool, const int32_t *block_table, int64_t table_stride,
+                         int n_pages, int max_pages, int page_tokens, const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals,
+                         int32_t *ranges_out, void *O, const int32_t *t_pos, int t_max, int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int l,
+                         int d, int l_sel, int n_top, int64_t kcp, int64_t kcg, int64_t kcs, int64_t ksp, int64_t ksg, int64_t kss, int64_t vsp, int64_t vsg,
+                         int64_t vss, int dtype, float scale, void *workspace, size_t workspace_bytes, void *stream) {
+    (void)workspace, (void)workspace_bytes;  // (the one launch needs no scratch)
+    const SelDecodeCall c{Q, Kc_pool, K_pool, V_pool, csc_ptr, csc_rows, csc_vals, ranges_out, O, B, S, G, h, Dk, Dv, S_cmp, S_sel, 0, l, d, l_sel, n_top, 0,
+                          kcp, kcg, kcs, ksp, ksg, kss, vsp, vsg, vss, dtype, scale};
+    return sel_decode_paged_impl(c, DecPageTable{block_table, table_stride, n_pages}, max_pages, page_tokens, t_pos, t_max, stream);
+}
+
+size_t nsa_sel_decode_paged_workspace(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int n_top, int dtype) {
+    (void)B, (void)S, (void)G, (void)h, (void)Dk, (void)Dv, (void)S_cmp, (void)S_sel, (void)n_top, (void)dtype;
+    return 0;  // one launch, everything on chip (the ragged call's answer)
+}
+
+int nsa_sel_decode_paged_plan(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int max_pages, int page_tokens, int n_top, int dtype,
+                              int t_max, int *launches, int *form) {
+    NSA_CHECK_ARG(launches && form, "decode_paged_plan: null pointer");
+    NSA_CHECK_ARG(dtype_ok(dtype), "decode_paged_plan: unknown dtype %d", dtype);
+    NSA_CHECK_ARG(B >= 1 && S >= 1 && G >= 1 && h >= 1 && Dk >= 1 && Dv >= 1 && S_cmp >= 0 && S_sel >= 1 && max_pages >= 1 && max_pages <= (1 << 20) &&
+                      page_tokens >= 1 && n_top >= 1 && n_top <= 64 && t_max >= 0,
+                  "decode_paged_plan: bad sizes");
+    *launches = 0;
+    *form = -1;
+    if (page_tokens == DEC_PAGE_TOKENS &&
+        decode_paged_shape_plan(sel_decode_plan_call(B, S, G, h, Dk, Dv, S_cmp, S_sel, max_pages * DEC_PAGE_TOKENS, n_top, dtype), t_max, form, nullptr, nullptr))
+        *launches = 1;
+    return NSA_OK;
 }
 
 size_t nsa_sel_decode_ragged_workspace(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int n_top, int dtype) {

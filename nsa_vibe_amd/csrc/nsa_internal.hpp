@@ -54,12 +54,21 @@ bool decode_step_shape_plan(const SelDecodeCall &c, int *form, int *nsplit);
 bool decode_rows_shape_plan(const SelDecodeCall &c, int *form, int *nw_out);
 bool decode_rows_supported(const SelDecodeCall &c);
 // t_pos (device, [B]) / t_max: the ragged form (nsa_sel_decode_ragged) -- row (b, s, g) at t_pos[b] + s, planned from t_max
-int launch_decode_rows(const SelDecodeCall &c, hipStream_t st, const int32_t *t_pos = nullptr, int t_max = 0);
+// pt: the paged form (nsa_sel_decode_paged) -- the caches are pools of pages found through a device table, c.S_kv the capacity max_pages * 1024
+struct DecPageTable {
+    const int32_t *table;  // device [B, max_pages] int32
+    int64_t stride;        // elements between its rows
+    int n_pages;           // pages of the pools: entries outside [0, n_pages) make a sequence inactive
+};
+int launch_decode_rows(const SelDecodeCall &c, hipStream_t st, const int32_t *t_pos = nullptr, int t_max = 0, const DecPageTable *pt = nullptr);
 // shape / tuning part of the ragged form's predicate, from the host bound t_max alone (the position array is never read on the host);
 // *why (optional): the limit a declined shape ran into
 bool decode_ragged_shape_plan(const SelDecodeCall &c, int t_max, int *form, int *nw_out, const char **why);
 bool decode_ragged_operands_ok(const SelDecodeCall &c);
 int sel_decode_ragged_impl(const SelDecodeCall &c, const int32_t *t_pos, int t_max, void *stream);
+// the paged form's plan: the ragged form's with one (page, group) plane of 1024 rows as the extent of the 32-bit offsets
+bool decode_paged_shape_plan(const SelDecodeCall &c, int t_max, int *form, int *nw_out, const char **why);
+int sel_decode_paged_impl(const SelDecodeCall &c, const DecPageTable &pt, int max_pages, int page_tokens, const int32_t *t_pos, int t_max, void *stream);
 // the band forward with per-sequence positions (nsa_band_attn_fwd_ragged): band.t0 is ignored
 int band_attn_fwd_ragged_impl(const AttnCall &c, const Band &band, const int32_t *t_pos, int t_max);
 

@@ -42,6 +42,7 @@ int dec_att_waves(int64_t rows, int D = 64);
 // ---- chunk providers: chunk e (ascending token order) -> first key and number of keys (1..64)
 // blocks picked by the selector, in LDS (sorted, disjoint, 64 keys each; the last one is cut at t_end = min(t + 1, S_kv))
 struct ListChunks {
+    static constexpr bool PAGED = false;
     const int *list;
     int t_end;
     __device__ __forceinline__ void get(int e, int &tok0, int &len) const {
@@ -49,8 +50,24 @@ struct ListChunks {
         len = min(64, t_end - tok0);
     }
 };
+// the selector's blocks over PAGED caches (nsa_sel_decode_paged): chunk e is the logical block list[e] as above -- the same tok0 and len, so
+// the same arithmetic on the same keys -- and lies inside ONE page of 1024 tokens (a block is 64 tokens, 64-aligned): page(tok0) is the
+// pool page that holds it, from the workgroup's checked copy of the sequence's table entries in LDS (one wave-uniform read per chunk), and
+// its first row inside that page's (page, group) plane is tok0 & 1023
+struct PagedListChunks {
+    static constexpr bool PAGED = true;
+    const int *list;
+    int t_end;
+    const int *pages;  // LDS: the sequence's needed table entries, every one inside [0, n_pages)
+    __device__ __forceinline__ void get(int e, int &tok0, int &len) const {
+        tok0 = uniform(list[e]) << 6;
+        len = min(64, t_end - tok0);
+    }
+    __device__ __forceinline__ int page(int tok0) const { return uniform(pages[tok0 >> 10]); }
+};
 // sorted disjoint segments in registers: lane i holds segment i (start, length), cb = chunks before it
 struct SegChunks {
+    static constexpr bool PAGED = false;
     int nseg, sstart, slen, cb, nck;
     __device__ __forceinline__ void get(int c, int &tok0, int &len) const {
         const int lane = lane_id();
@@ -92,8 +109,12 @@ struct DecPrefetch {
     int tok0;                    // first key of the chunk the wave fetched, -1 = none
     const unsigned char *ktile;  // its K image in LDS
 };
+// `row` names the plane as (b, g) = (row / G, row % G) and tok0 is a row of it; rows = the plane's extent (S_kv).  Paged caches
+// (nsa_sel_decode_paged): b is the pool PAGE (ksb / vsb are the page strides), tok0 the first row inside the page's plane and rows = 1024 --
+// the base is 64-bit, the only 32-bit offsets are those inside one plane
 template <typename T>
-__device__ __forceinline__ void decode_prefetch_chunk(const DecAttnArgs &A, int64_t row, int tok0, int len, unsigned char *vtile, unsigned char *ktile) {
+__device__ __forceinline__ void decode_prefetch_chunk(const DecAttnArgs &A, int64_t row, int tok0, int len, unsigned char *vtile, unsigned char *ktile,
+                                                      int rows = -1) {
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef __attribute__((address_space(3))) void lds_void;
     const int lane = lane_id();
@@ -102,7 +123,7 @@ __device__ __forceinline__ void decode_prefetch_chunk(const DecAttnArgs &A, int6
     const uint64_t ka = (uint64_t)((const T *)A.K + b * A.ksb + (int64_t)g * A.ksg), va = (uint64_t)((const T *)A.V + b * A.vsb + (int64_t)g * A.vsg);
     const uint32_t ka_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ka), ka_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ka >> 32));
     const uint32_t va_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)va), va_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(va >> 32));
-    const int bytes = __builtin_amdgcn_readfirstlane((int)((int64_t)A.S_kv * 128));
+    const int bytes = __builtin_amdgcn_readfirstlane((int)((int64_t)(rows < 0 ? A.S_kv : rows) * 128));
     const auto krs = __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)ka_hi << 32) | (uint64_t)ka_lo), (short)0, bytes, 0x00020000);
     const auto vrs = __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)va_hi << 32) | (uint64_t)va_lo), (short)0, bytes, 0x00020000);
     const int ld_row = lane >> 3, ld_piece = lane & 7;
@@ -120,7 +141,7 @@ __device__ __forceinline__ void decode_prefetch_chunk(const DecAttnArgs &A, int6
         __builtin_amdgcn_raw_ptr_buffer_load_lds(vrs, (lds_void *)(vtile + i * 1024), 16, rc * 128 + vsw, so, 0, 0);
     }
 #else
-    (void)A, (void)row, (void)tok0, (void)len, (void)vtile, (void)ktile;
+    (void)A, (void)row, (void)tok0, (void)len, (void)vtile, (void)ktile, (void)rows;
 #endif
 }
 
@@ -180,27 +201,43 @@ __device__ __forceinline__ void decode_attend_chunks(const DecAttnArgs &A, int64
     const uint32_t va_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)va), va_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(va >> 32));
     [[maybe_unused]] const auto vrs = __builtin_amdgcn_make_buffer_rsrc(
         (void *)(((uint64_t)va_hi << 32) | (uint64_t)va_lo), (short)0, __builtin_amdgcn_readfirstlane((int)((int64_t)(A.S_kv - 1) * ROWB + ROWB)), 0x00020000);
+    // Paged caches (CH::PAGED): Kb / Vb above are the planes of pool page 0 (b = 0: the caller passes kv_row = g), ksb / vsb the page
+    // strides.  A chunk's K rows and its V descriptor sit on the plane of ITS page -- a 64-bit base, formed per chunk from the wave-uniform
+    // page id; the descriptor covers that plane's 1024 rows, so every 32-bit offset stays inside one plane however large the pool is.
+    constexpr bool PG = CH::PAGED;
 
     // every load of a chunk goes out at once: V by LDS-DMA, K straight to registers (rows past the chunk re-read its last row)
-    auto issue_v = [&](int tok0, int len) {
+    auto issue_v = [&](int tok0, int len, [[maybe_unused]] int page) {
 #if defined(__HIP_DEVICE_COMPILE__)
         typedef __attribute__((address_space(3))) void lds_void;
-        const int vs = uniform(tok0 * ROWB);
+        auto rs = vrs;
+        int vs = uniform(tok0 * ROWB);
+        if constexpr (PG) {
+            const uint64_t pa = va + (uint64_t)page * (uint64_t)A.vsb * 2;
+            const uint32_t pa_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)pa), pa_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(pa >> 32));
+            rs = __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)pa_hi << 32) | (uint64_t)pa_lo), (short)0, 1024 * ROWB, 0x00020000);
+            vs = uniform((tok0 & 1023) * ROWB);
+        }
 #pragma unroll
         for (int i = 0; i < VLD; ++i) {
             const int rc = min(VRPI * i + ld_row, len - 1);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(vrs, (lds_void *)(vl + i * 1024), 16, rc * ROWB + vsw[i % NSW], vs, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void *)(vl + i * 1024), 16, rc * ROWB + vsw[i % NSW], vs, 0, 0);
         }
 #else
         (void)tok0, (void)len;
 #endif
     };
-    auto load_k = [&](int tok0, int len, x8 (&k)[4][KS]) {
+    auto load_k = [&](int tok0, int len, x8 (&k)[4][KS], [[maybe_unused]] int page) {
+        const unsigned char *kp = Kb;
+        if constexpr (PG) {
+            kp = Kb + (int64_t)page * A.ksb * 2;
+            tok0 &= 1023;
+        }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int kr = tok0 + min(16 * u + rho, len - 1);
 #pragma unroll
-            for (int s = 0; s < KS; ++s) k[u][s] = __builtin_bit_cast(x8, *(const u32x4 *)(Kb + (int64_t)kr * krowb + 64 * s + 16 * q));
+            for (int s = 0; s < KS; ++s) k[u][s] = __builtin_bit_cast(x8, *(const u32x4 *)(kp + (int64_t)kr * krowb + 64 * s + 16 * q));
         }
     };
 
@@ -210,9 +247,11 @@ __device__ __forceinline__ void decode_attend_chunks(const DecAttnArgs &A, int64
     float mrun = -INFINITY, lrun = 0.f;
 
     int cur = dec_first_chunk<NW>(wave, NC), tok0 = 0, len = 0;
+    [[maybe_unused]] int pg = 0, npg = 0;  // PG: the pool page of the current / the next chunk
     x8 kfr[4][KS];
     if (cur < NC) {
         ch.get(cur, tok0, len);
+        if constexpr (PG) pg = ch.page(tok0);
         if (D == 64 && pre.tok0 == tok0 && pre.tok0 >= 0) {
             // this chunk went out at kernel start (K and V by LDS-DMA): both have long landed; the K fragments come from the LDS image
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -221,8 +260,8 @@ __device__ __forceinline__ void decode_attend_chunks(const DecAttnArgs &A, int64
 #pragma unroll
                 for (int s = 0; s < KS; ++s) kfr[u][s] = *(const x8 *)(pre.ktile + (16 * u + rho) * ROWB + (((4 * s + q) ^ (rho & 7)) << 4));
         } else {
-            load_k(tok0, len, kfr);  // K first: loads complete in order, and the scores need K before the P V product needs V
-            issue_v(tok0, len);
+            load_k(tok0, len, kfr, pg);  // K first: loads complete in order, and the scores need K before the P V product needs V
+            issue_v(tok0, len, pg);
         }
     }
     while (cur < NC) {
@@ -232,7 +271,8 @@ __device__ __forceinline__ void decode_attend_chunks(const DecAttnArgs &A, int64
         [[maybe_unused]] x8 kn[4][KS];
         if (hn) {
             ch.get(nxt, ntok0, nlen);
-            if constexpr (PF) load_k(ntok0, nlen, kn);
+            if constexpr (PG) npg = ch.page(ntok0);
+            if constexpr (PF) load_k(ntok0, nlen, kn, npg);
         }
         f32x4 sacc[4];
 #pragma unroll
@@ -294,9 +334,9 @@ __device__ __forceinline__ void decode_attend_chunks(const DecAttnArgs &A, int64
 #pragma unroll
                     for (int s = 0; s < KS; ++s) kfr[u][s] = kn[u][s];
             } else {
-                load_k(ntok0, nlen, kfr);
+                load_k(ntok0, nlen, kfr, npg);
             }
-            issue_v(ntok0, nlen);
+            issue_v(ntok0, nlen, npg);
         }
         cur = nxt;
         tok0 = ntok0;

@@ -141,7 +141,15 @@ struct DecStepParams {
     // sequence with t_pos[b] < 0 or t_pos[b] + S - 1 > min(t_max, S_kv - 1) reads nothing and gets zero O and ranges rows
     const int32_t *t_pos;
     int t_max;
+    // paged form of the ragged form (nsa_sel_decode_paged; the kernel's PAGED instantiations alone read these): the caches are pools of
+    // pages of DEC_PAGE_TOKENS tokens (K / V) and DEC_PAGE_TOKENS / 16 compressed rows (K_cmp); entry j of row b of the table is the pool
+    // page of the sequence's tokens [1024 j, 1024 j + 1024).  csb (here) and ksb / vsb (DecAttnArgs) are then the PAGE strides, S_kv the
+    // capacity max_pages * 1024; a sequence with a needed entry outside [0, n_pages) is inactive like one with a position out of bounds
+    int n_pages;
+    const int32_t *block_table;  // device [B, max_pages] int32, row stride bt_stride
+    int64_t bt_stride;
 };
+constexpr int DEC_PAGE_TOKENS = 1024;  // one scorer chunk (64 compressed rows at d = 16) = 16 selection blocks of 64
 // fills tpw of both argument blocks and returns the (row, split) units = waves of each; false: not both in split form with deferred combine
 bool band_dual_plan(BandAttnParams *P0, BandAttnParams *P1, int dtype, int64_t waves[2]);
 int launch_band_attn_bwd_dq(const BandAttnParams &P, const void *dO, const float *lse, const float *delta, void *dQ, int dtype,

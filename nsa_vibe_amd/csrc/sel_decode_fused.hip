@@ -30,6 +30,10 @@
 // beyond them take the separate launches.  Ranges and O are those of S single steps (tests/test_hip_decode_rows.py).  Measured against S
 // single steps and the separate launches: not slower in every cell but S = 1 on rows of >= 32 chunks, which default to the
 // separate launches.
+// Paged form (template flag PAGED on the ragged rows form; nsa_sel_decode_paged): the caches are pools of pages of 1024 tokens found
+// through a device block table -- one scorer chunk and 16 selection blocks per page, so every K_cmp chunk, gathered block and forced block
+// lies in ONE page and the table costs one wave-uniform lookup per chunk.  Same form, waves, values and order as the ragged form: ranges
+// and O are its bits (tests/test_hip_decode_paged.py).  An instantiation of its own: no other one holds any of its code.
 #include <algorithm>
 #include <mutex>
 #include <unordered_map>
@@ -55,6 +59,7 @@ constexpr int DSTEP_CH = 128;                  // chunks of 64 compressed rows p
 constexpr int DSTEP_PART = 16 * DSTEP_CH * 2;  // floats: [head][chunk][2]
 constexpr int DSTEP_HALO = DSTEP_CH * 16;      // floats: [chunk][head] scaled logit of the chunk's last row
 constexpr int DSTEP_TAIL = 1024 + 4 * (128 + 68 + 4);  // bytes behind the V tiles: mlw [16][16] f32 | scr | list | misc
+constexpr int DSTEP_PAGES = 128;               // paged form: table entries of a sequence kept in LDS behind everything else (the forms end below 66 pages)
 // D = 128 (eight waves): 8 x 16 KiB of V tiles + the tail = 132,896 bytes -- one workgroup per CU; the score phases (part 16 KiB | halo 8 KiB |
 // pg <= 8 KiB) fit the 128 KiB of tiles with room to spare
 static size_t dstep_lds(int nw, int D = 64) { return (size_t)nw * dec_att_tile(D) + DSTEP_TAIL + (nw == 16 ? 3 * dec_att_tile(D) : 0); }
@@ -84,9 +89,10 @@ __device__ __forceinline__ bool decode_band_workgroup(const DecBandPair &BP) {
 // registers, those of the later three wait in LDS ([slot][u][head][q] f32x4, 256 h bytes per chunk: each lane reads back exactly what it
 // wrote, so no barrier guards them) until the row's log-sum-exp is known.  Two chunks (16 KiB per wave) are in flight throughout.  Same
 // arithmetic on the same values: p_grp, ranges and O have the bits of every other form.
-template <typename T, int NW, bool SPLIT, int HC, int CPW = 2, int D = 64, bool ROWS = false>
+template <typename T, int NW, bool SPLIT, int HC, int CPW = 2, int D = 64, bool ROWS = false, bool PAGED = false>
 __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(DecStepParams P, SelectParams SP, int cand, DecAttnArgs AT, DecBandPair BP) {
     static_assert(CPW == 2 || (CPW == 4 && !SPLIT), "four chunks per wave: unsplit form only");
+    static_assert(!PAGED || ROWS, "paged caches: the ragged rows form only");
     static_assert(D == 64 || (D == 128 && NW == 8 && CPW == 2), "D = 128: eight waves per row, logits in the accumulators");
     constexpr int KS = D / 32;              // MFMA k-steps of a logit
     constexpr int TILE = dec_att_tile(D);   // V tile of a wave (the score phases live in the same LDS)
@@ -109,6 +115,7 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
     int *list = scr + 128;                            // [68] picked blocks, ascending
     int *misc = list + 68;                            // [0] number of picked blocks, [1] ticket, [2] team assembled
     [[maybe_unused]] unsigned char *ktiles = lds + NW * TILE + DSTEP_TAIL;  // PREF: [3] K images of the prefetched blocks
+    [[maybe_unused]] int *pages = (int *)(lds + NW * TILE + DSTEP_TAIL + (NW == 16 ? 3 * TILE : 0));  // PAGED: [DSTEP_PAGES] the sequence's table entries
 
     const int lane = lane_id(), wave = uniform((int)(threadIdx.x >> 6)), rho = lane & 15, q = lane >> 4;
     const int h = P.h;
@@ -134,11 +141,35 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
     // reads nothing and gets zero O and ranges rows: the whole workgroup leaves here, before any barrier.  A row too short to have a
     // compressed token (t < 31) has S_cmp = nchunk = 0: no chunk is loaded (load_chunk would clamp with S_cmp - 1) or scored, the group
     // scores keep their zeros, and the selector and the gather run as for any row -- the single step's route for such a token.
+    // Paged form (PAGED, nsa_sel_decode_paged): the caches are pools of pages of 1024 tokens -- one scorer chunk of 64 compressed rows, 16
+    // selection blocks -- and entry j of row b of P.block_table is the pool page of the sequence's tokens [1024 j, 1024 j + 1024) in all
+    // three pools; AT.S_kv is the capacity max_pages * 1024.  A sequence whose position passes the bounds is inactive as above; one that
+    // passes them needs the entries j = 0 .. (t_base + S - 1) >> 10 (< max_pages by the capacity bound), and is inactive too if any of
+    // them lies outside [0, n_pages).  Every wave checks the needed entries for itself, lane L loading entries L and L + 64 (the forms
+    // end at 64 chunks = 65,567 tokens: at most 65), so the verdict needs no barrier and is the same in every wave; entries behind the
+    // needed ones are never read.  The checked entries go to LDS -- every wave stores the same values and reads only behind its own
+    // stores -- for the wave-uniform lookups of the sweep, the forced-block prefetch and the gather (kept in the two registers for
+    // v_readlane instead, the 16-wave form 1 spilled 17 - 24 VGPRs against 9 this way: DESIGN.md 4.1h).  No table value reaches an
+    // address: only entries inside [0, n_pages) do.
     int t_base = P.t_token;
     if constexpr (ROWS) {
         if (P.t_pos) {
             t_base = P.t_pos[b];
-            if (t_base < 0 || t_base + P.S - 1 > min(P.t_max, AT.S_kv - 1)) {
+            bool live = !(t_base < 0 || t_base + P.S - 1 > min(P.t_max, AT.S_kv - 1));
+            if constexpr (PAGED) {
+                if (live) {
+                    const int need = ((t_base + P.S - 1) >> 10) + 1;
+                    const int32_t *te = P.block_table + b * P.bt_stride;
+                    const int pe0 = lane < need ? te[lane] : 0, pe1 = lane + 64 < need ? te[lane + 64] : 0;
+                    live = __ballot((unsigned)pe0 >= (unsigned)P.n_pages || (unsigned)pe1 >= (unsigned)P.n_pages) == 0;
+                    if (live) {
+                        pages[lane] = pe0;
+                        pages[lane + 64] = pe1;
+                        wave_lds_fence();
+                    }
+                }
+            }
+            if (!live) {
                 T *Or = (T *)AT.O + (int64_t)row * h * D;
                 for (int i = threadIdx.x; i < h * D; i += NW * 64) Or[i] = Elt<T>::from_f(0.f);
                 int32_t *out = SP.out + (int64_t)row * SP.W * 2;
@@ -147,6 +178,8 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
             }
         }
     }
+    // PAGED: the pool page of the sequence's page j (j wave uniform)
+    [[maybe_unused]] auto page_of = [&](int j) -> int { return uniform(pages[j]); };
     const int t_tok = ROWS ? t_base + (row / P.G) % P.S : P.t_token;
     const int S_cmp = ROWS ? (t_tok < 31 ? 0 : min(P.S_cmp, (t_tok + 1 - 32) / 16 + 1)) : P.S_cmp;
     const int nchunk = ROWS ? (S_cmp + 63) >> 6 : P.nchunk;
@@ -163,11 +196,18 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
     x8 a[2][4][KS];
     f32x4 acc[REGC][4];
     auto load_chunk = [&](int c, x8 (&dst)[4][KS]) {
+        // PAGED: chunk c = the 64 compressed rows of the sequence's page c (P.csb: the page stride); the clamp stays inside the chunk
+        // (c < nchunk), so inside its page
+        [[maybe_unused]] const T *kp = nullptr;
+        if constexpr (PAGED) kp = (const T *)P.Kc + (int64_t)page_of(c) * P.csb + (int64_t)g * P.csg;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int r = min(c * 64 + 16 * u + rho, S_cmp - 1);
 #pragma unroll
-            for (int s = 0; s < KS; ++s) dst[u][s] = *(const x8 *)(kb + (int64_t)r * P.css + 32 * s + 8 * q);
+            for (int s = 0; s < KS; ++s) {
+                if constexpr (PAGED) dst[u][s] = *(const x8 *)(kp + (int64_t)(r & 63) * P.css + 32 * s + 8 * q);
+                else dst[u][s] = *(const x8 *)(kb + (int64_t)r * P.css + 32 * s + 8 * q);
+            }
         }
     };
 #pragma unroll
@@ -184,7 +224,10 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
             const int blk = wave == 0 ? 0 : cb - (15 - wave);
             pre.tok0 = 64 * blk;
             pre.ktile = ktiles + slot * TILE;
-            decode_prefetch_chunk<T>(AT, kvrow, pre.tok0, min(64, t_end - pre.tok0), lds + wave * TILE, ktiles + slot * TILE);
+            if constexpr (PAGED)  // block blk lies in the sequence's page blk >> 4, from row (blk & 15) * 64 of that page's plane
+                decode_prefetch_chunk<T>(AT, (int64_t)page_of(blk >> 4) * P.G + g, (blk & 15) * 64, min(64, t_end - pre.tok0), lds + wave * TILE,
+                                         ktiles + slot * TILE, DEC_PAGE_TOKENS);
+            else decode_prefetch_chunk<T>(AT, kvrow, pre.tok0, min(64, t_end - pre.tok0), lds + wave * TILE, ktiles + slot * TILE);
         }
     }
 
@@ -507,7 +550,10 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
     // ---- phase 4: selection attention over the picked blocks (wave e mod NW gathers block e; partials merged through LDS)
     const ListChunks ch{list, min(t_tok + 1, AT.S_kv)};
     DS_TS(9);
-    if constexpr (ROWS) decode_attend_chunks<T, NW, ListChunks, D>(AT, row, ch, NC, lds, qf, pre, kvrow);
+    if constexpr (PAGED) {  // the same blocks, each on the plane of its page (kv_row = g: the planes of pool page 0)
+        const PagedListChunks pch{list, ch.t_end, pages};
+        decode_attend_chunks<T, NW, PagedListChunks, D>(AT, row, pch, NC, lds, qf, pre, g);
+    } else if constexpr (ROWS) decode_attend_chunks<T, NW, ListChunks, D>(AT, row, ch, NC, lds, qf, pre, kvrow);
     else decode_attend_chunks<T, NW, ListChunks, D>(AT, row, ch, NC, lds, qf, pre);
     DS_TS(10);
 }
@@ -872,7 +918,7 @@ bool decode_step_supported(const SelDecodeCall &c) {
 // raise the dynamic-LDS limit once per kernel (the runtime call costs about a millisecond)
 static int dstep_raise_lds(void *k) {
     static std::mutex mu;
-    static void *raised[80] = {};
+    static void *raised[112] = {};
     std::lock_guard<std::mutex> lk(mu);
     for (void *r : raised)
         if (r == k) return NSA_OK;
@@ -1039,9 +1085,20 @@ bool decode_ragged_shape_plan(const SelDecodeCall &c, int t_max, int *form, int 
 
 bool decode_ragged_operands_ok(const SelDecodeCall &c) { return dstep_operands_ok(c); }
 
-int launch_decode_rows(const SelDecodeCall &c, hipStream_t st, const int32_t *t_pos, int t_max) {
+// ---- paged form (nsa_sel_decode_paged): the ragged form over pools of pages.  c.K_cmp / c.K / c.V are the pools, kcb / ksb / vsb their PAGE
+// strides and c.S_kv the capacity max_pages * 1024.  Form and waves are the ragged form's, from t_max and the row count alone -- same
+// declines, same messages -- except that the byte offsets the kernel forms in 32 bits are those inside one (page, group) plane of 1024 rows
+// (the bases are 64-bit: a pool has no size limit), so the plane stands where dstep_shape_ok asks for S_kv 2 Dv < 2^31.
+bool decode_paged_shape_plan(const SelDecodeCall &c, int t_max, int *form, int *nw_out, const char **why) {
+    SelDecodeCall plane = c;
+    plane.S_kv = DEC_PAGE_TOKENS;
+    return decode_ragged_shape_plan(plane, t_max, form, nw_out, why);
+}
+
+int launch_decode_rows(const SelDecodeCall &c, hipStream_t st, const int32_t *t_pos, int t_max, const DecPageTable *pt) {
     int nw = 16, form = 0;
-    if (t_pos) NSA_CHECK_ARG(decode_ragged_shape_plan(c, t_max, &form, &nw, nullptr), "decode ragged: shape not covered (decode_ragged_shape_plan)");
+    if (pt) NSA_CHECK_ARG(t_pos && decode_paged_shape_plan(c, t_max, &form, &nw, nullptr), "decode paged: shape not covered (decode_paged_shape_plan)");
+    else if (t_pos) NSA_CHECK_ARG(decode_ragged_shape_plan(c, t_max, &form, &nw, nullptr), "decode ragged: shape not covered (decode_ragged_shape_plan)");
     else NSA_CHECK_ARG(decode_rows_shape_plan(c, &form, &nw), "decode rows: shape not covered (decode_rows_supported)");
     const int64_t R = c.rows();
     const int D = c.Dk, h = c.h, cpw = form == 1 ? 4 : 2;
@@ -1049,22 +1106,34 @@ int launch_decode_rows(const SelDecodeCall &c, hipStream_t st, const int32_t *t_
     const float c2 = default_scale(c.scale, D) * LOG2E;
     DecStepParams P{c.Q, c.K_cmp, nullptr, nullptr, nullptr, nullptr, (int)R, c.G, h, c.S_cmp, c.S_sel, 1, nchunk, nchunk, c.t0, 0, c.kcb, c.kcg, c.kcs, c2, c.S,
                     t_pos, t_max};
+    if (pt) {
+        // (every table entry the kernel follows is < n_pages, every needed index < max_pages: c.S_kv = max_pages * 1024 bounds the positions)
+        NSA_CHECK_ARG(pt->table && pt->n_pages >= 1 && pt->stride >= (int64_t)c.S_kv / DEC_PAGE_TOKENS, "decode paged: bad block table");
+        P.n_pages = pt->n_pages;
+        P.block_table = pt->table;
+        P.bt_stride = pt->stride;
+    }
     DecStepBlocks A{};
     if (int rc = dstep_blocks(c, c2, &A)) return rc;
     void (*k)(DecStepParams, SelectParams, int, DecAttnArgs, DecBandPair);
     const bool bf = c.dtype == NSA_DT_BF16;
-#define NSA_DSR(NW_, HC_, CPW_, D_) (bf ? decode_step_kernel<__bf16, NW_, false, HC_, CPW_, D_, true> : decode_step_kernel<_Float16, NW_, false, HC_, CPW_, D_, true>)
+    // (the paged form is an instantiation of its own: the rows / ragged instantiations hold none of its code)
+#define NSA_DSR1(NW_, HC_, CPW_, D_, PG_) \
+    (bf ? decode_step_kernel<__bf16, NW_, false, HC_, CPW_, D_, true, PG_> : decode_step_kernel<_Float16, NW_, false, HC_, CPW_, D_, true, PG_>)
+#define NSA_DSR(NW_, HC_, CPW_, D_) (pt ? NSA_DSR1(NW_, HC_, CPW_, D_, true) : NSA_DSR1(NW_, HC_, CPW_, D_, false))
     if (D == 128) {
         NSA_CHECK_ARG(form == 0 && nw == 8, "decode rows: D = 128 runs form 0 on eight waves");
         k = h == 6 ? NSA_DSR(8, 6, 2, 128) : NSA_DSR(8, 0, 2, 128);
     } else if (cpw == 4) k = h == 6 ? (nw == 16 ? NSA_DSR(16, 6, 4, 64) : NSA_DSR(8, 6, 4, 64)) : (nw == 16 ? NSA_DSR(16, 0, 4, 64) : NSA_DSR(8, 0, 4, 64));
     else k = h == 6 ? (nw == 16 ? NSA_DSR(16, 6, 2, 64) : NSA_DSR(8, 6, 2, 64)) : (nw == 16 ? NSA_DSR(16, 0, 2, 64) : NSA_DSR(8, 0, 2, 64));
 #undef NSA_DSR
+#undef NSA_DSR1
     if (int rc = dstep_raise_lds((void *)k)) return rc;
     DecBandPair BP{};
     BP.n_sel = 0xffffffffu;  // (no band workgroups on this form)
-    hipLaunchKernelGGL(k, dim3((unsigned)R), dim3(nw * 64), dstep_lds(nw, D), st, P, A.SP, A.cand, A.AT, BP);
-    NSA_LAUNCH_CHECK("decode_rows");
+    hipLaunchKernelGGL(k, dim3((unsigned)R), dim3(nw * 64), dstep_lds(nw, D) + (pt ? sizeof(int) * DSTEP_PAGES : 0), st, P, A.SP, A.cand, A.AT, BP);
+    if (pt) NSA_LAUNCH_CHECK("decode_paged");
+    else NSA_LAUNCH_CHECK("decode_rows");
     return NSA_OK;
 }
 

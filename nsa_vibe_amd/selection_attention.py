@@ -351,6 +351,83 @@ def selection_decode_ragged(Q: torch.Tensor, K_cmp: torch.Tensor, K: torch.Tenso
     return O, rg
 
 
+PAGE_TOKENS = 1024  # tokens per cache page of the paged decode step: one scorer chunk (64 compressed rows), 16 selection blocks
+
+
+def selection_decode_paged_plan(B: int, S: int, G: int, h: int, Dk: int, Dv: int, S_cmp: int, S_sel: int, max_pages: int, n_top: int, t_max: int,
+                                dtype: torch.dtype = torch.bfloat16, page_tokens: int = PAGE_TOKENS) -> dict:
+    """What selection_decode_paged does with a shape whose largest live row sits at t_max (nsa_sel_decode_paged_plan): the plan of
+    selection_decode_ragged_plan for a capacity of max_pages * 1024 tokens -- {"launches": 1, "form": 0 / 1}, or {"launches": 0,
+    "form": -1} where the call declines (a shape the ragged call declines, or a page size other than 1024)."""
+    ints = _plan_ints("nsa_sel_decode_paged_plan", 2, int(B), int(S), int(G), int(h), int(Dk), int(Dv), int(S_cmp), int(S_sel), int(max_pages),
+                      int(page_tokens), int(n_top), _DT[dtype], int(t_max))
+    return dict(zip(("launches", "form"), ints))
+
+
+def _unit_rows_pool(who: str, name: str, X: torch.Tensor, rows: int):
+    """a pool [n_pages, G, rows, D] as the C ABI takes it -> (X, its page, group and row strides); a pool is never copied"""
+    if X.dim() != 4 or X.shape[2] != rows:
+        raise RuntimeError(f"{who}: {name} must be [n_pages, G, {rows}, D] (got {tuple(X.shape)})")
+    if X.stride(-1) != 1:
+        raise RuntimeError(f"{who}: {name} must have a contiguous last dimension (a pool is used in place, never copied)")
+    return X, X.stride(0), X.stride(1), X.stride(2)
+
+
+def selection_decode_paged(Q: torch.Tensor, Kc_pool: torch.Tensor, K_pool: torch.Tensor, V_pool: torch.Tensor, block_table: torch.Tensor, meta,
+                           n_top: int, t_pos, t_max: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                           ranges_out: Optional[torch.Tensor] = None, *, scale: Optional[float] = None):
+    """selection_decode_ragged over PAGED caches, in one native call (nsa_sel_decode_paged).
+
+    K_pool / V_pool [n_pages, G, 1024, D] and Kc_pool [n_pages, G, 64, D] are pools of pages (views with page, group and row strides are
+    fine; the last dimension must be contiguous); block_table is a device int32 tensor [B, max_pages] whose entry [b, j] is the pool page
+    that holds tokens [1024 j, 1024 j + 1024) of sequence b's K and V and compressed rows [64 j, 64 j + 64) of its K_cmp.  Its last
+    dimension must be contiguous; it is never read back.  Q, meta, n_top, t_pos and t_max are those of selection_decode_ragged, with
+    max_pages * 1024 as the caches' capacity: meta covers at least min(t_max, capacity - 1) + 1 tokens.
+    A sequence is inactive -- zero O and ranges rows, nothing read -- under the ragged rule (t_pos[b] < 0, or t_pos[b] + S - 1 >
+    min(t_max, capacity - 1)) or when one of the table entries it needs, j = 0 .. (t_pos[b] + S - 1) >> 10, lies outside [0, n_pages).
+    For a table that scatters contiguous caches into pages the result is selection_decode_ragged's on those caches bit for bit.
+    There is no per-sequence fallback: the contiguous operators cannot read a pool, so a declined shape (selection_decode_paged_plan:
+    launches 0) raises RuntimeError with the library's message.  Returns (O [B,S,G,h,Dv], ranges [B,S,G,n_top,2] int32).  Inference only."""
+    who = "selection_decode_paged"
+    if Q.dim() != 5:
+        raise RuntimeError(f"{who}: expected Q[B,S,G,h,Dk]")
+    B, S, G, h, Dk = Q.shape
+    bt = block_table
+    if not isinstance(bt, torch.Tensor) or bt.device.type == "cpu" or bt.dtype != torch.int32 or bt.dim() != 2:
+        raise RuntimeError(f"{who}: block_table must be a device int32 tensor [B, max_pages] (it is never read back); got "
+                           f"{getattr(bt, 'dtype', type(bt))} {tuple(getattr(bt, 'shape', ()))} on {getattr(bt, 'device', 'the host')}")
+    if bt.shape[0] != B or bt.shape[1] < 1:
+        raise RuntimeError(f"{who}: block_table has shape {tuple(bt.shape)} for B = {B} sequences: expected [B, max_pages >= 1]")
+    if bt.stride(1) != 1:
+        raise RuntimeError(f"{who}: block_table must have a contiguous last dimension (stride {bt.stride(1)})")
+    t_pos, t_max, host = _ragged_positions(who, t_pos, t_max, B, S)
+    dev = _need_gpu(Q, Kc_pool, K_pool, V_pool, bt)
+    if host is None and t_pos.device != dev:
+        raise RuntimeError("all tensors must be on the same device")
+    (Kc, *cs), (Kk, *ks), (Vv, *vs) = (_unit_rows_pool(who, "Kc_pool", Kc_pool, PAGE_TOKENS // 16), _unit_rows_pool(who, "K_pool", K_pool, PAGE_TOKENS),
+                                      _unit_rows_pool(who, "V_pool", V_pool, PAGE_TOKENS))
+    n_pages, max_pages, Dv = Kk.shape[0], bt.shape[1], Vv.shape[3]
+    if Kc.shape[0] != n_pages or Vv.shape[0] != n_pages or not (Kc.shape[1] == Kk.shape[1] == Vv.shape[1] == G) or Kk.shape[3] != Dk or Kc.shape[3] != Dk:
+        raise RuntimeError(f"{who}: the three pools must share n_pages and G = {G}, with Dk = {Dk} columns in Kc_pool and K_pool")
+    S_cmp, S_sel = min(int(meta.S_cmp), max_pages * (PAGE_TOKENS // 16)), meta.S_sel
+    O = out if out is not None else torch.empty((B, S, G, h, Dv), dtype=V_pool.dtype, device=dev)
+    rg = ranges_out if ranges_out is not None else torch.empty((B, S, G, n_top, 2), dtype=torch.int32, device=dev)
+    if O.numel() == 0:
+        return O, rg
+    L = _lib.lib()
+    dt = _DT[Q.dtype]
+    Qc = Q.contiguous()
+    pos = _positions_to(dev, t_pos, host)
+    cptr, crows, cvals = meta.device_csc(dev)
+    ws = workspace(dev, L.nsa_sel_decode_paged_workspace(B, S, G, h, Dk, Dv, S_cmp, S_sel, n_top, dt), "decode_paged")
+    rc = L.nsa_sel_decode_paged(Qc.data_ptr(), Kc.data_ptr(), Kk.data_ptr(), Vv.data_ptr(), bt.data_ptr(), bt.stride(0), n_pages, max_pages, PAGE_TOKENS,
+                                cptr.data_ptr(), crows.data_ptr(), cvals.data_ptr(), rg.data_ptr(), O.data_ptr(), pos.data_ptr(), t_max, B, S, G, h, Dk, Dv,
+                                S_cmp, S_sel, int(meta.l), int(meta.d), int(meta.l_sel), int(n_top), *cs, *ks, *vs, dt, _scale_arg(scale), *_ws_args(ws),
+                                _stream(dev))
+    _lib.check(rc, "nsa_sel_decode_paged")
+    return O, rg
+
+
 def select_and_attend(p_grp: torch.Tensor, Q: torch.Tensor, K: torch.Tensor, V: torch.Tensor, meta, n_top: int, *,
                       mode: str = "batched", t0: int = 0, force_init: bool = True, force_local: int = 2,
                       scale: Optional[float] = None, return_lse: bool = False):
