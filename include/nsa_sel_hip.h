@@ -617,6 +617,38 @@ NSA_API int nsa_band_attn_fwd_ragged(const void *Q, const void *K, const void *V
                              int64_t v_stride_g, int64_t v_stride_s, int a, int dd, int c, int w, int dtype, float scale, int variant,
                              void *workspace, size_t workspace_bytes, void *stream);
 
+/* nsa_band_attn_fwd_ragged over PAGED caches (the sliding and the compressed branch of a ragged decode step whose K_win / V_win or K_cmp /
+ * V_cmp live in pools of pages): that call in every respect except where a key row is found.
+ *   K_pool, V_pool  [n_pages, G, page_rows, D], each with a page, a group and a row stride in elements.  Page bases are formed in 64 bits,
+ *                   so a pool may exceed 2 GiB; the only 32-bit byte offsets are inside one (page, group) plane: page_rows * stride_s * 2
+ *                   bytes must stay under 2 GiB (declined otherwise).
+ *   block_table     device int32 [B, max_pages], table_stride elements between its rows (>= max_pages).  Key row r of sequence b is row
+ *                   r & (page_rows - 1) of pool page block_table[b, r >> log2(page_rows)].  The host never reads it.
+ *   page_rows       a power of two in [32, 65536] (32 = the key tile: a tile touches at most two pages).  1024 for the sliding branch and
+ *                   64 for the compressed one (d = 16) are the sizes at which one table -- nsa_sel_decode_paged's -- serves all five pools.
+ *   Q, O, lse, t_pos, t_max, B, S, G, h, Dk, Dv, a, dd, c, w, dtype, scale   as in nsa_band_attn_fwd_ragged.  The capacity that call takes
+ *                   from S_kv is max_pages * page_rows here.  max_pages <= 2^20.  There is no variant: one route.
+ * Inactive sequences: the ragged call's rule with the capacity in the place of S_kv, plus one case: a table entry the sequence NEEDS lies
+ * outside [0, n_pages).  The needed entries are those that cover key rows [lo_b, hi_b): hi_b the unclamped hi of the sequence's last query
+ * row, lo_b = max(0, hi(first row) - w).  Entries below the sliding window and entries behind hi_b are never read and may hold anything.
+ * The set is the sequence's, not a wave's: every wave of a sequence and every split of a row reaches the same verdict.  An inactive
+ * sequence gives zero rows and lse = -inf and reads nothing from the pools.  Only entries that passed the test are turned into addresses;
+ * nothing is clamped silently.
+ * Route, split count and workspace are those of the scalar and the ragged call, planned from (B, S, G, h, D) alone; a missing or too small
+ * workspace runs the unsplit form.  NSA_ERR_INVALID, with a message that names the limit and no fallback, for: anything outside the MFMA
+ * kernels (fp32, Dk != Dv, D not 64 or 128, h > 16), w < 1, a null table or t_pos, max_pages outside [1, 2^20], n_pages < 1, a table stride
+ * below max_pages, a page_rows that is not built, misaligned pools or strides (16-byte pools and Q, strides in multiples of 8 elements, O
+ * 8-byte aligned), and row strides that leave the 32-bit in-plane offsets.
+ * Bits: for a table that scatters contiguous caches into pages, in any order, O and lse are those of nsa_band_attn_fwd_ragged on the
+ * contiguous caches bit for bit -- the same tiles of 32 keys, masks, split shares and epilogue.  Forward only. */
+NSA_API size_t nsa_band_attn_fwd_paged_workspace(int B, int S, int G, int h, int Dk, int Dv, int dtype);
+NSA_API int nsa_band_attn_fwd_paged(const void *Q, const void *K_pool, const void *V_pool,
+                            const int32_t *block_table /* device, [B,max_pages] */, int64_t table_stride, int n_pages, int max_pages,
+                            int page_rows, void *O, float *lse, const int32_t *t_pos /* device, [B] */, int t_max /* host */, int B, int S,
+                            int G, int h, int Dk, int Dv, int64_t k_stride_p, int64_t k_stride_g, int64_t k_stride_s, int64_t v_stride_p,
+                            int64_t v_stride_g, int64_t v_stride_s, int a, int dd, int c, int w, int dtype, float scale, void *workspace,
+                            size_t workspace_bytes, void *stream);
+
 /* indices [R,K] int32 ascending with -1 padding -> ranges [R,K,2]; clamp end to t+1. */
 NSA_API int nsa_indices_to_ranges_v2(const int32_t *indices, int64_t R, int S, int G, int t0, int K, int S_sel,
                              int l_sel, int32_t *ranges_out, void *stream);

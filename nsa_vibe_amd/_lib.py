@@ -109,6 +109,8 @@ SIGNATURES = {
     "nsa_sel_decode_paged_plan": (_i, [_i] * 13 + [C.POINTER(_i)] * 2),
     "nsa_band_attn_fwd_ragged_workspace": (_sz, [_i] * 7),
     "nsa_band_attn_fwd_ragged": (_i, [_vp] * 6 + [_i] * 8 + [_i64] * 6 + [_i] * 4 + [_i, _f, _i, _vp, _sz, _vp]),
+    "nsa_band_attn_fwd_paged_workspace": (_sz, [_i] * 7),
+    "nsa_band_attn_fwd_paged": (_i, [_vp] * 4 + [_i64] + [_i] * 3 + [_vp] * 3 + [_i] * 7 + [_i64] * 6 + [_i] * 4 + [_i, _f, _vp, _sz, _vp]),
     "nsa_batched_ranges_width": (_i, [_i] * 6),
     "nsa_select_topn_ranges": (_i, [_vp, _i64, _i, _i, _i, _vp] + [_i] * 7 + [_vp, _i, _vp]),
     "nsa_sel_select_attn_fwd": (_i, [_vp, _i, _vp] + [_i] * 7 + [_vp, _i] + [_vp] * 5 + [_i] * 7 + [_i64] * 6 + [_i, _f, _vp, _sz, _vp]),

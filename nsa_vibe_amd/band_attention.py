@@ -19,7 +19,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .selection_attention import _bwd_variant, _positions_to, _ragged_positions
+from .selection_attention import _bwd_variant, _positions_to, _ragged_positions, _unit_rows_pool
 from ._native import _DT, _need_gpu, _needs_grad, _scale_arg, _stream, _unit_rows, _ws_args, workspace, workspace_at
 
 _W_INF = 2 ** 30
@@ -76,6 +76,56 @@ def _fwd(Q, K, V, band, scale, variant, want_lse, t_pos=None, t_max=None):
     return O, lse, (Qc, Kc, Vc)
 
 
+def _fwd_paged(Q, K_pool, V_pool, block_table, band, scale, want_lse, t_pos, t_max):
+    """the ragged forward over pools of pages (nsa_band_attn_fwd_paged); everything is checked before anything native is touched"""
+    who = "band attention (paged)"
+    if Q.dim() != 5:
+        raise RuntimeError(f"{who}: expected Q[B,S,G,h,Dk] K_pool[n_pages,G,page_rows,Dk] V_pool[n_pages,G,page_rows,Dv]")
+    B, S, G, h, Dk = Q.shape
+    bt = block_table
+    if not isinstance(bt, torch.Tensor) or bt.device.type == "cpu" or bt.dtype != torch.int32 or bt.dim() != 2:
+        raise RuntimeError(f"{who}: block_table must be a device int32 tensor [B, max_pages] (it is never read back); got "
+                           f"{getattr(bt, 'dtype', type(bt))} {tuple(getattr(bt, 'shape', ()))} on {getattr(bt, 'device', 'the host')}")
+    if bt.shape[0] != B or bt.shape[1] < 1:
+        raise RuntimeError(f"{who}: block_table has shape {tuple(bt.shape)} for B = {B} sequences: expected [B, max_pages >= 1]")
+    if bt.stride(1) != 1:
+        raise RuntimeError(f"{who}: block_table must have a contiguous last dimension (stride {bt.stride(1)})")
+    if band[0] != 0:
+        raise RuntimeError(f"{who}: t_pos and a non-zero t0 are mutually exclusive")
+    if t_pos is None:
+        raise RuntimeError(f"{who}: block_table needs the per-sequence positions t_pos")
+    if Q.requires_grad or K_pool.requires_grad or V_pool.requires_grad:
+        raise RuntimeError(f"{who}: paged caches (block_table) are forward only: no input may require grad")
+    t_pos, t_max, host = _ragged_positions(who, t_pos, t_max, B, S)
+    dev = _need_gpu(Q, K_pool, V_pool, bt)
+    if host is None and t_pos.device != dev:
+        raise RuntimeError("all tensors must be on the same device")
+    if not (Q.dtype == K_pool.dtype == V_pool.dtype) or Q.dtype not in _DT:
+        raise RuntimeError(f"{who}: Q and the pools must share a dtype (got {Q.dtype},{K_pool.dtype},{V_pool.dtype})")
+    if K_pool.dim() != 4 or V_pool.dim() != 4:
+        raise RuntimeError(f"{who}: expected Q[B,S,G,h,Dk] K_pool[n_pages,G,page_rows,Dk] V_pool[n_pages,G,page_rows,Dv]")
+    page_rows = K_pool.shape[2]
+    (Kk, *ks), (Vv, *vs) = _unit_rows_pool(who, "K_pool", K_pool, page_rows), _unit_rows_pool(who, "V_pool", V_pool, page_rows)
+    n_pages, max_pages, Dv = Kk.shape[0], bt.shape[1], Vv.shape[3]
+    if Vv.shape[0] != n_pages or not (Kk.shape[1] == Vv.shape[1] == G) or Kk.shape[3] != Dk:
+        raise RuntimeError(f"{who}: the two pools must share n_pages and G = {G}, with Dk = {Dk} columns in K_pool")
+    t0, a, dd, c, w = band
+    O = torch.empty((B, S, G, h, Dv), dtype=V_pool.dtype, device=dev)
+    lse = torch.empty((B, S, G, h), dtype=torch.float32, device=dev) if want_lse else None
+    if O.numel() == 0:
+        return O, lse
+    L = _lib.lib()
+    dt = _DT[Q.dtype]
+    Qc = Q.contiguous()
+    pos = _positions_to(dev, t_pos, host)
+    ws = workspace(dev, L.nsa_band_attn_fwd_paged_workspace(B, S, G, h, Dk, Dv, dt), "band")
+    rc = L.nsa_band_attn_fwd_paged(Qc.data_ptr(), Kk.data_ptr(), Vv.data_ptr(), bt.data_ptr(), bt.stride(0), n_pages, max_pages, page_rows, O.data_ptr(),
+                                   lse.data_ptr() if lse is not None else None, pos.data_ptr(), t_max, B, S, G, h, Dk, Dv, *ks, *vs, int(a), int(dd), int(c),
+                                   int(min(w, _W_INF)), dt, _scale_arg(scale), *_ws_args(ws), _stream(dev))
+    _lib.check(rc, "nsa_band_attn_fwd_paged")
+    return O, lse
+
+
 class _BandAttnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, Q, K, V, band, scale, variant, bwd_variant):
@@ -109,15 +159,26 @@ class _BandAttnFn(torch.autograd.Function):
 
 def band_attention_hip(Q, K, V, *, t0: int = 0, a: int = 0, dd: int = 1, c: int = 0, w: int = _W_INF,
                        scale: Optional[float] = None, variant: int = 0, return_lse: bool = False,
-                       bwd_variant: Optional[int] = None, t_pos=None, t_max: Optional[int] = None):
+                       bwd_variant: Optional[int] = None, t_pos=None, t_max: Optional[int] = None, block_table=None):
     """Row t attends keys [max(0, hi - w), hi), hi = (t0+t+1 >= a) ? min(S_kv, (t0+t+1-a)//dd + c) : 0.
 
     variant: 0 auto, 1 generic, 2 MFMA (forward); bwd_variant: the same for the backward, None = 0 unless variant is 1.
     t_pos / t_max (ragged batch, nsa_band_attn_fwd_ragged; forward only, exclusive with a non-zero t0): sequence b's row t sits at
     t_pos[b] + t.  t_pos is a device int32 tensor [B] (t_max, a host bound of t_pos[b] + S - 1, is then required: nothing is read back) or
     host integers (t_max defaults to max + S - 1).  A sequence with a negative position, one beyond t_max, or one whose last row would need
-    keys past S_kv gives zero rows and lse = -inf."""
+    keys past S_kv gives zero rows and lse = -inf.
+    block_table (paged caches, nsa_band_attn_fwd_paged; forward only, needs t_pos): K / V are POOLS [n_pages, G, page_rows, D] -- views with
+    page, group and row strides are used in place, the last dimension must be contiguous; page_rows, read from their shape, is a power of two
+    in [32, 65536] -- and block_table is a device int32 tensor [B, max_pages] with a contiguous last dimension, never read on the host: key
+    row r of sequence b is row r % page_rows of pool page block_table[b, r // page_rows].  The capacity is max_pages * page_rows.  A
+    sequence is inactive (zero rows, lse = -inf, nothing read) under the ragged rule, or when a table entry it needs -- those covering its
+    key rows from the window start of its first row to the end of its last -- lies outside [0, n_pages); entries outside that set are never
+    read.  O and lse are those of the ragged call on the contiguous caches bit for bit.  bf16 / f16 at D = 64 or 128 only: anything else
+    raises the library's message, there is no fallback.  variant is not used."""
     band = (int(t0), int(a), int(dd), int(c), int(w))
+    if block_table is not None:
+        O, lse = _fwd_paged(Q, K, V, block_table, band, scale, return_lse, t_pos, t_max)
+        return (O, lse) if return_lse else O
     if t_pos is not None or t_max is not None:
         O, lse, _ = _fwd(Q, K, V, band, scale, variant, return_lse, t_pos, t_max)
         return (O, lse) if return_lse else O
@@ -132,18 +193,21 @@ def band_attention_hip(Q, K, V, *, t0: int = 0, a: int = 0, dd: int = 1, c: int 
 
 
 def sliding_window_attention(Q, K, V, w: int, *, t0: int = 0, scale: Optional[float] = None, variant: int = 0, t_pos=None,
-                             t_max: Optional[int] = None):
+                             t_max: Optional[int] = None, block_table=None):
     """Keys [t-w+1 .. t] of row t (reference attention_kernels.py:146-178; w <= 0 or no keys -> zeros, :153-154).
-    t_pos / t_max: per-sequence positions of a ragged batch (band_attention_hip)."""
-    return band_attention_hip(Q, K, V, t0=t0, a=0, dd=1, c=0, w=max(int(w), 0), scale=scale, variant=variant, t_pos=t_pos, t_max=t_max)
+    t_pos / t_max: per-sequence positions of a ragged batch; block_table: K / V are pools of pages (band_attention_hip; pages of 1024
+    rows share their page ids with selection_decode_paged)."""
+    return band_attention_hip(Q, K, V, t0=t0, a=0, dd=1, c=0, w=max(int(w), 0), scale=scale, variant=variant, t_pos=t_pos, t_max=t_max,
+                              block_table=block_table)
 
 
 def batched_causal_attention_compressed(Q, K_cmp, V_cmp, l: int, d: int, *, t0: int = 0, scale: Optional[float] = None,
-                                        variant: int = 0, t_pos=None, t_max: Optional[int] = None):
+                                        variant: int = 0, t_pos=None, t_max: Optional[int] = None, block_table=None):
     """Keys [0, num_cmp(t)), num_cmp(t) = 0 if t+1 < l else (t+1-l)//d + 1, clamped to S_cmp (attention_kernels.py:118-121).
-    t_pos / t_max: per-sequence positions of a ragged batch (band_attention_hip)."""
+    t_pos / t_max: per-sequence positions of a ragged batch; block_table: K_cmp / V_cmp are pools of pages (band_attention_hip; pages of
+    64 rows at d = 16 share their page ids with selection_decode_paged)."""
     return band_attention_hip(Q, K_cmp, V_cmp, t0=t0, a=int(l), dd=int(d), c=1, w=_W_INF, scale=scale, variant=variant, t_pos=t_pos,
-                              t_max=t_max)
+                              t_max=t_max, block_table=block_table)
 
 
 def batched_causal_attention_compressed_first_key_parity(Q, K_cmp, V_cmp, l: int, d: int, *, t0: int = 0):

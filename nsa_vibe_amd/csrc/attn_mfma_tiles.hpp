@@ -9,6 +9,8 @@
 //   kv_rsrc, KvSrc<D>, kv_src       K/V of one (b,g) as buffer resources + the per-lane and scalar offsets of its 32-key tiles
 //   tile_dma            a tile -> LDS by LDS-DMA (full-tile arm with scalar steps, tail arm with the clamped row): the band forward's; the one-row
 //                       and the rows kernel of the selection keep a copy each (they say why)
+//   kv_plane, kv_page, paged_tile_dma2   paged K/V (the band forward's PAGED form): the 64-bit base of a (page, group) plane, the descriptors
+//                       of a KvSrc on it, and a tile whose rows lie in two pages by LDS-DMA with per-lane global addresses
 //   wg_pair             workgroup index -> ((b,g) pair, workgroup of the pair) under map_mode 0 / 1 / 2
 //   PART_PAD, RESCALE_THR, sel_attn_combine_kernel   split-KV partial record and its combine kernel
 #pragma once
@@ -173,6 +175,48 @@ __device__ __forceinline__ void tile_dma(const KvSrc<D> &t, unsigned char *kl, u
             __builtin_amdgcn_raw_ptr_buffer_load_lds(t.krs, (lds_void *)(kl + i * 1024), 16, rc * t.krowb + G_::row_piece(r, t.ld_piece), ks, 0, 0);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(t.vrs, (lds_void *)(vl + i * 1024), 16, rc * t.vrowb + G_::tr_piece(r, t.ld_piece), vs, 0, 0);
         }
+    }
+#endif
+}
+
+// Paged K/V (the band forward's PAGED form): the pools are [n_pages, G, rows, D] with P.ksb / P.vsb as PAGE strides.  The base of a
+// (page, group) plane is formed in 64 bits -- a pool may exceed 2 GiB --; the 32-bit offsets stay inside one plane of `rows` rows (the host
+// bounds rows * row stride).  `page` is a checked table entry, wave uniform.
+template <typename T>
+__device__ __forceinline__ const unsigned char *kv_plane(const void *pool, int64_t page_stride, int64_t group_stride, int page, int g) {
+    const uint64_t a = (uint64_t)((const T *)pool + (int64_t)page * page_stride + (int64_t)g * group_stride);
+    // (wave uniform by construction: pinned in SGPRs, so a lane's choice between two planes is one select per half, not a 64-bit multiply)
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
+    return (const unsigned char *)(((uint64_t)hi << 32) | lo);
+}
+// the descriptors of t on the plane of `page`: tile_dma then takes the row INSIDE the page as tok0
+template <typename T, int D, class A>
+__device__ __forceinline__ void kv_page(KvSrc<D> &t, const A &P, int page, int g, int rows) {
+    t.krs = kv_rsrc(kv_plane<T>(P.K, P.ksb, P.ksg, page, g), (int64_t)(rows - 1) * t.krowb + Geo<D>::ROWB);
+    t.vrs = kv_rsrc(kv_plane<T>(P.V, P.vsb, P.vsg, page, g), (int64_t)(rows - 1) * t.vrowb + Geo<D>::ROWB);
+}
+// A 32-key tile whose rows lie in TWO pages (p0: rows row0 .. rows - 1 of it, p1: the rest from its row 0): a buffer descriptor is wave
+// uniform, so this arm gives every lane its own 64-bit source address -- one of the two wave-uniform plane bases by the lane's row, the row
+// offset and the swizzled piece offset of tile_dma's tail arm -- through global_load_lds_dwordx4.  The destination is lane-linear like the
+// buffer form's, so the LDS image is byte-identical, and completion is a vmcnt event like the buffer form's.  Rows past `last` re-read row
+// `last` (clamped first, then the page of the clamped row: nothing beyond the wave's last key is read).
+template <typename T, int D, class A>
+__device__ __forceinline__ void paged_tile_dma2(const KvSrc<D> &t, const A &P, int p0, int p1, int g, unsigned char *kl, unsigned char *vl, int row0,
+                                                int rows, int last) {
+#if defined(__HIP_DEVICE_COMPILE__)  // (device-only builtin, like tile_dma's)
+    using G_ = Geo<D>;
+    typedef __attribute__((address_space(3))) void lds_void;
+    typedef const __attribute__((address_space(1))) void gbl_void;
+    const unsigned char *k0 = kv_plane<T>(P.K, P.ksb, P.ksg, p0, g), *k1 = kv_plane<T>(P.K, P.ksb, P.ksg, p1, g);
+    const unsigned char *v0 = kv_plane<T>(P.V, P.vsb, P.vsg, p0, g), *v1 = kv_plane<T>(P.V, P.vsb, P.vsg, p1, g);
+#pragma unroll
+    for (int i = 0; i < G_::NLD; ++i) {
+        const int r = i * G_::RPI + t.ld_row;
+        const int pr = row0 + min(r, last);  // row counted from the start of page p0
+        const bool second = pr >= rows;
+        const int in = second ? pr - rows : pr;
+        __builtin_amdgcn_global_load_lds((gbl_void *)((second ? k1 : k0) + (uint32_t)(in * t.krowb + G_::row_piece(r, t.ld_piece))), (lds_void *)(kl + i * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gbl_void *)((second ? v1 : v0) + (uint32_t)(in * t.vrowb + G_::tr_piece(r, t.ld_piece))), (lds_void *)(vl + i * 1024), 16, 0, 0);
     }
 #endif
 }

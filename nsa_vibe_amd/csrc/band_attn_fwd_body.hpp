@@ -11,12 +11,16 @@ namespace nsa {
 // next iteration): the compute-bound NT = 3 form spends ~19 % of a tile issuing its 8 DMA instructions, plain loads issue faster.
 // RAGGED (nsa_band_attn_fwd_ragged): the position of sequence b comes from P.t_pos[b] (band_pos, sel_attn_params.hpp).  A template flag, not a
 // test of the pointer: this body is inlined into every decode-step kernel, and those -- like the scalar band kernels -- keep their code.
-template <typename T, int D, int NT, bool SPLIT, int STAGE, bool RAGGED = false>
+// PAGED (nsa_band_attn_fwd_paged; implies RAGGED, STAGE 1, the stand-alone launch only): K / V are pools of pages found through *pt
+// (BandPageTable, sel_attn_params.hpp); P.ksb / P.vsb are the page strides and P.S_kv the capacity.  The tile partition, masks, split shares
+// and epilogue are the ragged form's, so the result is bit-equal; only the source of a tile's rows differs (issue_dma below).
+template <typename T, int D, int NT, bool SPLIT, int STAGE, bool RAGGED = false, bool PAGED = false>
 // WPB: waves of a workgroup that take band work (SPLIT form: every wave is its own unit; the plain kernels run 4)
 // mg (SPLIT, S = 1 only): BandMergeArgs of sel_attn_params.hpp -- merge the unit's splits here; eval_gates: this launch's branch also
 // evaluates the gate probabilities of its rows
 __device__ __forceinline__ void band_attn_body(const BandAttnParams &P, const unsigned bid, const int wpb = 4, const BandMergeArgs *mg = nullptr,
-                                               const bool eval_gates = false) {
+                                               const bool eval_gates = false, [[maybe_unused]] const BandPageTable *pt = nullptr) {
+    static_assert(!PAGED || (RAGGED && STAGE == 1), "the paged form is a ragged form with LDS-DMA staging");
     using M = MfmaT<T>;
     using G_ = Geo<D>;
     using x8 = typename M::x8;
@@ -52,6 +56,30 @@ __device__ __forceinline__ void band_attn_body(const BandAttnParams &P, const un
     // ---- key interval of the wave and of every slot (hi and lo are non-decreasing in t)
     [[maybe_unused]] BandPos bp{0, true};
     if constexpr (RAGGED) bp = band_pos(P, b);  // the sequence's own position, one scalar load (b is wave uniform)
+    // PAGED: the table entries the SEQUENCE needs -- those of key rows [lo_b, hi_b), from the window start of its first query row to the
+    // unclamped hi of its last -- are loaded and checked once per wave, before the first pool read: lane L takes entry j + L, one ballot per
+    // 64 entries.  The set is the sequence's, not the wave's, so every wave and every split of a row reaches the same verdict; an entry
+    // outside [0, n_pages) makes the sequence inactive (every interval empty, nothing read).  Entries below lo_b or behind hi_b are never
+    // loaded.  The first 64 checked entries stay in `ent` (one per lane) as the walk's window: pg_j0 is the entry index of lane 0.
+    [[maybe_unused]] int ent = 0, pg_j0 = 0, pg_jhi = -1;
+    if constexpr (PAGED) {
+        if (bp.live) {
+            const int e = bp.t0 + P.S - P.a;  // the last row's t + 1 - a
+            const int hi_b = e < 0 ? 0 : e / P.dd + P.c;  // (<= P.S_kv: the sequence is live)
+            const int lo_b = max(0, band_hi(bp.t0, P.a, P.dd, P.c, P.S_kv, 0) - P.w);
+            if (hi_b > lo_b) {
+                pg_j0 = uniform(lo_b >> pt->shift), pg_jhi = uniform((hi_b - 1) >> pt->shift);
+                const int32_t *row = pt->table + (int64_t)b * pt->stride;
+                bool bad = false;
+                for (int j = pg_j0; j <= pg_jhi; j += 64) {
+                    const int v = j + lane <= pg_jhi ? row[j + lane] : 0;
+                    bad |= __any((unsigned)v >= (unsigned)pt->n_pages) != 0;
+                    if (j == pg_j0) ent = v;
+                }
+                if (bad) bp.live = false;
+            }
+        }
+    }
     auto row_hi = [&](int t) {
         if constexpr (RAGGED) return band_row_hi(P, bp, t);
         else return band_hi(P.t0, P.a, P.dd, P.c, P.S_kv, t);
@@ -79,7 +107,7 @@ __device__ __forceinline__ void band_attn_body(const BandAttnParams &P, const un
         }
     }
 
-    const KvSrc<D> kv = kv_src<T, D>(P, b, g, lane);
+    KvSrc<D> kv = kv_src<T, D>(P, PAGED ? 0 : b, g, lane);  // (PAGED: the lane offsets; the descriptors are set per page)
     uint32_t krd0[KS], vrd0[MT];
     frag_read_offsets<D>(rho, q, krd0, vrd0);
     // rows past the end of K/V re-read the last row (they are masked: only boundary tiles reach past hi)
@@ -89,7 +117,36 @@ __device__ __forceinline__ void band_attn_body(const BandAttnParams &P, const un
     // and its compressed tokens are in the cache when the branch runs).  The scalar forms keep P.S_kv, which their caller bounds.
     int kend = P.S_kv;
     if constexpr (RAGGED) kend = min(P.S_kv, hi_max);
-    auto issue_dma = [&](int tok0) { tile_dma(kv, kl, vl, tok0, tok0 + 32 <= kend, kend - 1 - tok0); };
+    // PAGED: a tile lies in one page -- the existing arms on a descriptor of that page's (page, group) plane, rebuilt only when the walk
+    // enters a new page -- or straddles two (paged_tile_dma2).  The page of the clamped last row is looked up, so no row beyond kend - 1
+    // is read and every page used is one of the checked entries.  The window of 64 entries is reloaded when the walk leaves it.
+    [[maybe_unused]] int pg_cur = -1;  // table index of the page the descriptors describe
+    [[maybe_unused]] auto page_of = [&](int j) {
+        if (j - pg_j0 >= 64) {
+            pg_j0 = j;
+            ent = j + lane <= pg_jhi ? pt->table[(int64_t)b * pt->stride + j + lane] : 0;
+        }
+        return __builtin_amdgcn_readlane(ent, uniform(j - pg_j0));
+    };
+    auto issue_dma = [&](int tok0) {
+        if constexpr (PAGED) {
+            const int mask = (1 << pt->shift) - 1;
+            const int last = kend - 1 - tok0;
+            const int j0 = uniform(tok0 >> pt->shift), j1 = uniform((tok0 + min(31, last)) >> pt->shift);
+            if (j0 == j1) {
+                if (j0 != pg_cur) {
+                    kv_page<T, D>(kv, P, page_of(j0), g, mask + 1);
+                    pg_cur = j0;
+                }
+                tile_dma(kv, kl, vl, tok0 & mask, last >= 31, last);
+            } else {
+                const int p0 = page_of(j0), p1 = page_of(j1);
+                paged_tile_dma2<T, D>(kv, P, p0, p1, g, kl, vl, tok0 & mask, mask + 1, last);
+            }
+        } else {
+            tile_dma(kv, kl, vl, tok0, tok0 + 32 <= kend, kend - 1 - tok0);
+        }
+    };
 
     typedef __attribute__((ext_vector_type(4))) unsigned int bu32x4;
     u32x4 kreg[G_::NLD], vreg[G_::NLD];

@@ -223,7 +223,8 @@ size_t band_attn_workspace(int B, int S, int G, int h, int Dk, int Dv, int dtype
 }
 
 template <typename T, int D>
-static int launch_band_t(const BandAttnParams &P0, hipStream_t st) {
+static int launch_band_t(const BandAttnParams &P0, hipStream_t st, const BandPageTable *pt) {
+    constexpr int dtype = std::is_same<T, __bf16>::value ? NSA_DT_BF16 : NSA_DT_F16;
     BandAttnParams P = P0;
     int nt = 1, ns = 1;
     band_plan(P.B, P.S, P.G, P.h, D, &nt, &P.tpw, &ns);
@@ -235,7 +236,9 @@ static int launch_band_t(const BandAttnParams &P0, hipStream_t st) {
     const bool ragged = P.t_pos != nullptr;  // per-sequence positions: the RAGGED instantiations (LDS-DMA staging only)
     if (split) {
         const int64_t waves = nbg * ngrp * P.nsplit;
-        if (ragged) hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, 1, true, 1, true>), dim3((unsigned)((waves + 3) / 4)), dim3(256), lds, st, P);
+        // pt: the paged form -- the same plan and geometry, the PAGED kernels of band_attn_paged.hip (a translation unit of their own)
+        if (pt) launch_band_attn_paged_kernel(P, *pt, dtype, 1, true, (unsigned)((waves + 3) / 4), lds, st);
+        else if (ragged) hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, 1, true, 1, true>), dim3((unsigned)((waves + 3) / 4)), dim3(256), lds, st, P);
         else hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, 1, true, 1>), dim3((unsigned)((waves + 3) / 4)), dim3(256), lds, st, P);
         NSA_LAUNCH_CHECK("band_attn_fwd(split)");
         if (P.defer_combine) return NSA_OK;
@@ -256,7 +259,8 @@ static int launch_band_t(const BandAttnParams &P0, hipStream_t st) {
     const unsigned grid = (unsigned)(nbg * W);
     const int stage = tuning(TUNE_BAND_STAGE);  // A/B switch: 0 = register staging, 1 = LDS-DMA  // measured: LDS-DMA 750 vs register staging 650 TFLOP/s (compressed branch, 64k)
     constexpr int NTW = D == 64 ? 3 : 2;
-    if (ragged && nt != NTW) hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, 1, false, 1, true>), dim3(grid), dim3(256), lds, st, P);
+    if (pt) launch_band_attn_paged_kernel(P, *pt, dtype, nt, false, grid, lds, st);
+    else if (ragged && nt != NTW) hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, 1, false, 1, true>), dim3(grid), dim3(256), lds, st, P);
     else if (ragged) hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, NTW, false, 1, true>), dim3(grid), dim3(256), lds, st, P);
     else if (nt != NTW) hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, 1, false, 1>), dim3(grid), dim3(256), lds, st, P);
     else if (D == 128 || stage != 0) hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, NTW, false, 1>), dim3(grid), dim3(256), lds, st, P);
@@ -265,8 +269,9 @@ static int launch_band_t(const BandAttnParams &P0, hipStream_t st) {
     return NSA_OK;
 }
 
-int launch_band_attn_fwd_mfma(const BandAttnParams &P, int dtype, hipStream_t st) {
-    return with_elt<false>(dtype, [&](auto t) { return P.Dk == 64 ? launch_band_t<decltype(t), 64>(P, st) : launch_band_t<decltype(t), 128>(P, st); });
+int launch_band_attn_fwd_mfma(const BandAttnParams &P, int dtype, hipStream_t st, const BandPageTable *pt) {
+    NSA_CHECK_ARG(!pt || P.t_pos, "band_attn: the paged form takes per-sequence positions");
+    return with_elt<false>(dtype, [&](auto t) { return P.Dk == 64 ? launch_band_t<decltype(t), 64>(P, st, pt) : launch_band_t<decltype(t), 128>(P, st, pt); });
 }
 
 // Both branches of a decode step in one launch.  Requires both to be in split form with deferred combine (the caller combines).

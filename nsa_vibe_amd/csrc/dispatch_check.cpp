@@ -6,6 +6,7 @@
 //   dispatch_check <path of libnsa_sel_hip.so>      prints one JSON object, a member per case
 //   dispatch_check <library> ragged | layer_ragged  the cases of the entry points with per-sequence positions instead
 //   dispatch_check <library> paged                  the cases of the ragged decode step over paged caches (nsa_sel_decode_paged)
+//   dispatch_check <library> band_paged             the cases of the ragged band forward over paged caches (nsa_band_attn_fwd_paged)
 #include <dlfcn.h>
 #include <math.h>
 #include <stdio.h>
@@ -293,6 +294,8 @@ static std::string show(const nsa::DecAttnArgs &P) {
 static std::string show(const nsa::DecBandPair &P) {
     return Obj().raw("w", show(P.w)).raw("c", show(P.c)).i("mg_on", P.mg.on).p("gates", P.mg.gates).i("n_sel", P.n_sel).i("n_w", P.n_w).str();
 }
+// nsa_band_attn_fwd_paged: the table block, argument 1 of the paged band kernels
+static std::string show(const nsa::BandPageTable &P) { return Obj().p("table", P.table).i("stride", P.stride).i("n_pages", P.n_pages).i("shift", P.shift).str(); }
 struct BandBwdExtraArg {  // band_attn_mfma.hip: BandBwdExtra, argument 1 of the band dQ kernel
     const void *dO, *lse, *delta, *dQ;
 };
@@ -596,6 +599,91 @@ static void paged_cases() {
     }
 }
 
+// ---- dispatch_check <library> band_paged: the ragged band forward over paged caches (nsa_band_attn_fwd_paged), cases of their own like
+// `ragged` and `paged`.  Every case prints the launches and their geometry, the two argument blocks of the band launch -- BandAttnParams
+// (ksb / vsb: the page strides, S_kv: the capacity) and BandPageTable (the table pointer, its stride, n_pages, the page shift) -- as they
+// arrive, the split count and the workspace query, or the decline with its message.  The table and the positions are device pointers the
+// host must never read: addresses inside buffers of 0x7f bytes.
+static void band_paged_cases() {
+    const int G = 2, h = 6;
+    const size_t MB = 1 << 20;
+    void *Q = dev(MB), *K = dev(MB), *V = dev(MB), *O = dev(MB), *ws = dev(16 * MB);
+    float *lse = (float *)dev(MB);
+    int32_t *t_pos = (int32_t *)dev(MB, 0x7f), *table = (int32_t *)dev(MB, 0x7f);
+    g_named = {{"Q", Q, MB}, {"K_pool", K, MB}, {"V_pool", V, MB}, {"O", O, MB}, {"lse", lse, MB}, {"t_pos", t_pos, MB}, {"table", table, MB}, {"ws", ws, 16 * MB}};
+    auto fn = NSA_FN(nsa_band_attn_fwd_paged);
+    auto ws_fn = NSA_FN(nsa_band_attn_fwd_paged_workspace);
+    auto scalar_ws_fn = NSA_FN(nsa_band_attn_fwd_workspace);
+    const std::vector<Want> blocks = {want<nsa::BandAttnParams>("band_attn_fwd(split)", "BandAttnParams"), want<nsa::BandPageTable>("band_attn_fwd(split)", "BandPageTable", 1),
+                                      want<nsa::BandAttnParams>("band_attn_fwd", "BandAttnParams"), want<nsa::BandPageTable>("band_attn_fwd", "BandPageTable", 1)};
+    struct Case {
+        int B = 5, S = 1, D = 64, Dv = 0 /* 0: D */, hh = 6, t_max = 4100, dtype = NSA_DT_BF16, page_rows = 0 /* 0: 1024 sliding, 64 compressed */, n_pages = 40,
+            max_pages = 0 /* 0: what t_max needs */, w = 0 /* 0: 512 sliding, 2^30 compressed */;
+        bool compressed = false, with_ws = true;
+        int64_t table_stride = 0 /* 0: max_pages + 3 */, k_page_stride = 0 /* 0: G * page_rows * D */, k_row_stride = 0 /* 0: D */;
+        void *K = nullptr, *O = nullptr;
+        const int32_t *table = nullptr, *t_pos = nullptr;
+    };
+    auto band_case = [&](const char *label, const std::function<void(Case &)> &tweak) {
+        Case c;
+        c.K = K, c.O = O, c.table = table + 7, c.t_pos = t_pos + 5;
+        tweak(c);
+        const int rows = c.page_rows ? c.page_rows : (c.compressed ? 64 : 1024);
+        const int keys = c.compressed ? (c.t_max + 1 < 32 ? 0 : (c.t_max + 1 - 32) / 16 + 1) : c.t_max + 1;
+        const int max_pages = c.max_pages ? c.max_pages : (keys + rows - 1) / rows + (keys == 0);
+        const int64_t tstride = c.table_stride ? c.table_stride : max_pages + 3;
+        const int64_t kss = c.k_row_stride ? c.k_row_stride : c.D, kg = (int64_t)rows * kss, kp = c.k_page_stride ? c.k_page_stride : G * kg;
+        const int Dv = c.Dv ? c.Dv : c.D;
+        const int64_t vg = (int64_t)rows * Dv;
+        const int w = c.w ? c.w : (c.compressed ? 1 << 30 : 512);
+        run_args(std::string("band_attn_fwd_paged/") + label, [&] {
+            return fn(Q, c.K, V, c.table, tstride, c.n_pages, max_pages, rows, c.O, lse, c.t_pos, c.t_max, c.B, c.S, G, c.hh, c.D, Dv, kp, kg, kss, G * vg, vg, Dv,
+                      c.compressed ? 32 : 0, c.compressed ? 16 : 1, c.compressed ? 1 : 0, w, c.dtype, 0.f, c.with_ws ? ws : nullptr, c.with_ws ? 16 * MB : 0, nullptr);
+        }, blocks);
+        // (what show(BandAttnParams) leaves out: the ragged members; and the workspace query beside the scalar call's)
+        peek<nsa::BandAttnParams>(0);
+        run((std::string("band_attn_fwd_paged/") + label + "_positions").c_str(), [&] {
+            return fn(Q, c.K, V, c.table, tstride, c.n_pages, max_pages, rows, c.O, lse, c.t_pos, c.t_max, c.B, c.S, G, c.hh, c.D, Dv, kp, kg, kss, G * vg, vg, Dv,
+                      c.compressed ? 32 : 0, c.compressed ? 16 : 1, c.compressed ? 1 : 0, w, c.dtype, 0.f, c.with_ws ? ws : nullptr, c.with_ws ? 16 * MB : 0, nullptr);
+        }, [&] {
+            const nsa::BandAttnParams P = peeked<nsa::BandAttnParams>();
+            return Obj().p("t_pos", P.t_pos).i("t_max", P.t_max).i("t0", P.t0).i("nsplit", P.nsplit).i("workspace", (long long)ws_fn(c.B, c.S, G, c.hh, c.D, Dv, c.dtype))
+                .i("scalar_workspace", (long long)scalar_ws_fn(c.B, c.S, G, c.hh, c.D, Dv, c.dtype)).s;
+        });
+    };
+    (void)h;
+    // the cases of the `ragged` mode's band calls at the same (B, S, G, h, D): launches and geometry must be theirs
+    band_case("sliding_B5_S1_split", [](Case &) {});
+    band_case("sliding_B5_S1_no_workspace", [](Case &c) { c.with_ws = false; });
+    band_case("compressed_B5_S3_split", [](Case &c) { c.S = 3; c.t_max = 5002; c.compressed = true; });
+    band_case("sliding_B600_S3_unsplit", [](Case &c) { c.B = 600; c.S = 3; c.t_max = 1000; });
+    band_case("sliding_B600_S256_nt3", [](Case &c) { c.B = 600; c.S = 256; c.t_max = 1500; });
+    band_case("sliding_D128_B5_S1_split", [](Case &c) { c.D = 128; });
+    band_case("sliding_page_rows32", [](Case &c) { c.page_rows = 32; });
+    band_case("sliding_page_rows65536", [](Case &c) { c.page_rows = 65536; });
+    band_case("k_page_stride_3GiB", [](Case &c) { c.k_page_stride = (int64_t)3 << 29; });  // elements of 2 bytes: 3 GiB between pages
+    band_case("max_pages_2pow20", [](Case &c) { c.max_pages = 1 << 20; c.table_stride = 1 << 20; });
+    // the declines
+    band_case("f32_declined", [](Case &c) { c.dtype = NSA_DT_F32; });
+    band_case("Dk_ne_Dv_declined", [](Case &c) { c.Dv = 128; });
+    band_case("D96_declined", [](Case &c) { c.D = 96; });
+    band_case("h17_declined", [](Case &c) { c.hh = 17; });
+    band_case("w_below_1_declined", [](Case &c) { c.w = -1; });
+    band_case("null_table", [](Case &c) { c.table = nullptr; });
+    band_case("null_t_pos", [](Case &c) { c.t_pos = nullptr; });
+    band_case("max_pages_minus1", [](Case &c) { c.max_pages = -1; });
+    band_case("max_pages_above_2pow20", [](Case &c) { c.max_pages = (1 << 20) + 1; c.table_stride = 1 << 21; });
+    band_case("n_pages0", [](Case &c) { c.n_pages = 0; });
+    band_case("table_stride_below_max_pages", [](Case &c) { c.table_stride = 4; });
+    band_case("page_rows16_declined", [](Case &c) { c.page_rows = 16; });
+    band_case("page_rows96_declined", [](Case &c) { c.page_rows = 96; });
+    band_case("page_rows131072_declined", [](Case &c) { c.page_rows = 131072; });
+    band_case("K_pool_2_bytes_off", [&](Case &c) { c.K = off(K, 2); });
+    band_case("O_4_bytes_off", [&](Case &c) { c.O = off(O, 4); });
+    band_case("k_page_stride_not_8", [](Case &c) { c.k_page_stride = (int64_t)2 * 1024 * 64 + 4; });
+    band_case("k_row_stride_2MiB_plane_limit", [](Case &c) { c.k_row_stride = (int64_t)1 << 20; });  // 1024 rows of 2 MiB: a plane of 2 GiB
+}
+
 // ---- dispatch_check <library> layer_ragged: the layer's ragged call (nsa_layer_decode_ragged), cases of their own like `ragged`.  Every
 // case prints the launchers in order with their geometry, the plan's answer for the same shape, and "positions": the position pointer and the
 // bound te as they arrive in the argument blocks of the four launches that depend on the position (projection, pooling, the selected branch,
@@ -695,7 +783,7 @@ static void layer_ragged_cases() {
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: dispatch_check <libnsa_sel_hip.so> [ragged | layer_ragged | paged]\n");
+        fprintf(stderr, "usage: dispatch_check <libnsa_sel_hip.so> [ragged | layer_ragged | paged | band_paged]\n");
         return 2;
     }
     g_lib = dlopen(argv[1], RTLD_NOW | RTLD_GLOBAL);
@@ -712,6 +800,12 @@ int main(int argc, char **argv) {
     if (argc >= 3 && !strcmp(argv[2], "paged")) {  // the paged decode step alone (tests/test_dispatch_paged_host.py)
         printf("{");
         paged_cases();
+        printf("\n}\n");
+        return 0;
+    }
+    if (argc >= 3 && !strcmp(argv[2], "band_paged")) {  // the paged band forward alone (tests/test_dispatch_band_paged_host.py)
+        printf("{");
+        band_paged_cases();
         printf("\n}\n");
         return 0;
     }

@@ -781,7 +781,66 @@ int nsa::band_attn_fwd_ragged_impl(const AttnCall &c, const Band &band, const in
     return launch_band_attn_fwd_mfma(P, c.dtype, c.st);
 }
 
+// The ragged band forward over paged caches.  c: K / V are the pools, ksb / vsb their PAGE strides; S_kv is filled here with the capacity
+// max_pages * page_rows.  One route -- the MFMA kernels' PAGED form -- with the plan (form, split count, workspace) of the scalar and the
+// ragged call; everything else is declined, there is no generic kernel over pools.
+int nsa::band_attn_fwd_paged_impl(const AttnCall &c0, const Band &band, const BandPageTable &pt0, int max_pages, int page_rows, const int32_t *t_pos, int t_max) {
+    NSA_CHECK_ARG(dtype_ok(c0.dtype), "band_attn_fwd_paged: unknown dtype %d", c0.dtype);
+    NSA_CHECK_ARG(c0.B >= 0 && c0.S >= 0 && c0.G >= 1 && c0.h >= 1 && c0.Dk >= 1 && c0.Dv >= 1, "band_attn_fwd_paged: negative size");
+    NSA_CHECK_ARG(band.dd >= 1 && t_max >= 0, "band_attn_fwd_paged: need dd >= 1, t_max >= 0");
+    NSA_CHECK_ARG(attn_mfma_shape_ok(c0.dtype, c0.h, c0.Dk, c0.Dv),
+                  "band_attn_fwd_paged: the MFMA kernels only -- bf16 / f16, Dk = Dv in {64, 128}, h <= 16 (got dtype %d, Dk = %d, Dv = %d, h = %d); no kernel reads "
+                  "pools of pages for other shapes", c0.dtype, c0.Dk, c0.Dv, c0.h);
+    NSA_CHECK_ARG(band.w >= 1, "band_attn_fwd_paged: w = %d, the window must hold at least one key (w >= 1)", band.w);
+    NSA_CHECK_ARG(page_rows >= 32 && page_rows <= 65536 && (page_rows & (page_rows - 1)) == 0,
+                  "band_attn_fwd_paged: page_rows = %d is not built: a power of two in [32, 65536] (a 32-key tile then touches at most two pages)", page_rows);
+    NSA_CHECK_ARG(max_pages >= 1 && max_pages <= (1 << 20), "band_attn_fwd_paged: max_pages = %d, must be in [1, 2^20]", max_pages);
+    NSA_CHECK_ARG(pt0.n_pages >= 1, "band_attn_fwd_paged: n_pages = %d, the pools must hold at least one page", pt0.n_pages);
+    AttnCall c = c0;
+    // (positions are 32-bit: a capacity beyond INT32_MAX rows bounds nothing a position can reach)
+    c.S_kv = (int)std::min<int64_t>((int64_t)max_pages * page_rows, INT32_MAX);
+    if (c.rows() == 0) return NSA_OK;
+    NSA_CHECK_ARG(pt0.table != nullptr, "band_attn_fwd_paged: null block table");
+    NSA_CHECK_ARG((uintptr_t)pt0.table % 4 == 0 && pt0.stride >= max_pages, "band_attn_fwd_paged: the block table must be 4-byte aligned with a row stride of at least "
+                                                                           "max_pages = %d (got %lld)", max_pages, (long long)pt0.stride);
+    NSA_CHECK_ARG(c.Q && c.K && c.V && c.O && t_pos, "band_attn_fwd_paged: null pointer");
+    NSA_CHECK_ARG((uintptr_t)t_pos % 4 == 0, "band_attn_fwd_paged: t_pos must be 4-byte aligned");
+    NSA_CHECK_ARG(qkv_aligned(c) && out_aligned(c), "band_attn_fwd_paged: Q and the two pools must be 16-byte aligned with page, group and row strides in multiples of "
+                                                    "8 elements, and O 8-byte aligned");
+    // the kernel's only 32-bit byte offsets are those of a row inside one (page, group) plane of page_rows rows
+    const int64_t lim = (int64_t)1 << 31;
+    NSA_CHECK_ARG(c.kss >= 1 && c.vss >= 1 && (int64_t)page_rows * c.kss * 2 < lim && (int64_t)page_rows * c.vss * 2 < lim,
+                  "band_attn_fwd_paged: the row strides put a page's rows outside the 32-bit offsets of one (page, group) plane (page_rows = %d rows: under 2 GiB)",
+                  page_rows);
+    BandAttnParams P = band_attn_params(c, Band{0, band.a, band.dd, band.c, band.w});
+    P.t_pos = t_pos;
+    P.t_max = t_max;
+    // the split count and the workspace do not depend on the positions or the pages: the scalar call's; without the workspace, the unsplit form
+    int ns = 1;
+    const size_t need = band_attn_workspace(c.B, c.S, c.G, c.h, c.Dk, c.Dv, c.dtype, &ns);
+    if (ns > 1 && c.ws && ((uintptr_t)c.ws % 16 == 0) && c.ws_bytes >= need) {
+        P.part = (float *)c.ws;
+        P.nsplit = ns;
+    }
+    BandPageTable pt = pt0;
+    pt.shift = __builtin_ctz((unsigned)page_rows);
+    return launch_band_attn_fwd_mfma(P, c.dtype, c.st, &pt);
+}
+
 extern "C" {
+
+size_t nsa_band_attn_fwd_paged_workspace(int B, int S, int G, int h, int Dk, int Dv, int dtype) {
+    return band_attn_workspace(B, S, G, h, Dk, Dv, dtype, nullptr);  // planned from (B, S, G, h, D) alone: the scalar and the ragged call's
+}
+
+int nsa_band_attn_fwd_paged(const void *Q, const void *K_pool, const void *V_pool, const int32_t *block_table, int64_t table_stride, int n_pages, int max_pages,
+                            int page_rows, void *O, float *lse, const int32_t *t_pos, int t_max, int B, int S, int G, int h, int Dk, int Dv, int64_t ksp, int64_t ksg,
+                            int64_t kss, int64_t vsp, int64_t vsg, int64_t vss, int a, int dd, int c, int w, int dtype, float scale, void *workspace,
+                            size_t workspace_bytes, void *stream) {
+    return band_attn_fwd_paged_impl(AttnCall{Q, K_pool, V_pool, nullptr, O, lse, B, S, G, h, Dk, Dv, 0, 0, ksp, ksg, kss, vsp, vsg, vss, dtype, scale, 0, workspace,
+                                             workspace_bytes, (hipStream_t)stream},
+                                    Band{0, a, dd, c, w}, BandPageTable{block_table, table_stride, n_pages, 0}, max_pages, page_rows, t_pos, t_max);
+}
 
 int nsa_sel_decode_ragged(const void *Q, const void *K_cmp, const void *K, const void *V, const int32_t *csc_ptr, const int32_t *csc_rows,
                           const float *csc_vals, int32_t *ranges_out, void *O, const int32_t *t_pos, int t_max, int B, int S, int G, int h, int Dk,

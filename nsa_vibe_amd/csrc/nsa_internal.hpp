@@ -71,6 +71,10 @@ bool decode_paged_shape_plan(const SelDecodeCall &c, int t_max, int *form, int *
 int sel_decode_paged_impl(const SelDecodeCall &c, const DecPageTable &pt, int max_pages, int page_tokens, const int32_t *t_pos, int t_max, void *stream);
 // the band forward with per-sequence positions (nsa_band_attn_fwd_ragged): band.t0 is ignored
 int band_attn_fwd_ragged_impl(const AttnCall &c, const Band &band, const int32_t *t_pos, int t_max);
+// the ragged band forward over paged caches (nsa_band_attn_fwd_paged): c.K / c.V are the pools, c.ksb / c.vsb their page strides, c.S_kv is
+// ignored (the capacity is max_pages * page_rows); pt.shift is filled from page_rows
+struct BandPageTable;  // sel_attn_params.hpp
+int band_attn_fwd_paged_impl(const AttnCall &c, const Band &band, const BandPageTable &pt, int max_pages, int page_rows, const int32_t *t_pos, int t_max);
 
 // ---- the scorer and selector family behind the C ABI (nsa_api.hip): what nsa_sel_scores[_rows], nsa_sel_scores_select[_rows] and
 // nsa_select_topn_ranges run once their arguments are in the blocks

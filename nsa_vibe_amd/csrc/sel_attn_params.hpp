@@ -94,8 +94,23 @@ __device__ __forceinline__ BandPos band_pos(const BandAttnParams &P, int b) {
 __device__ __forceinline__ int band_row_hi(const BandAttnParams &P, const BandPos &bp, int t) {
     return bp.live ? band_hi(bp.t0, P.a, P.dd, P.c, P.S_kv, t) : 0;
 }
+// paged form (nsa_band_attn_fwd_paged): K / V are pools [n_pages, G, page_rows, D], key row r of sequence b is row r & (page_rows - 1) of
+// pool page table[b * stride + (r >> shift)].  An argument block of its own behind BandAttnParams (which sits twice inside DecBandPair: a
+// member there would move the kernarg offsets of every decode-step kernel).  In that launch P.ksb / P.vsb are the PAGE strides and P.S_kv
+// the capacity max_pages * page_rows.
+struct BandPageTable {
+    const int32_t *table;  // device [B, max_pages] int32
+    int64_t stride;        // elements between its rows
+    int n_pages;           // pages of the pools: a needed entry outside [0, n_pages) makes the sequence inactive
+    int shift;             // log2(page_rows), 5 .. 16
+};
 size_t band_attn_workspace(int B, int S, int G, int h, int Dk, int Dv, int dtype, int *nsplit_out);
-int launch_band_attn_fwd_mfma(const BandAttnParams &P, int dtype, hipStream_t st);
+// pt: the paged form -- the PAGED instantiations (LDS-DMA staging, the ragged call's three forms); needs P.t_pos
+int launch_band_attn_fwd_mfma(const BandAttnParams &P, int dtype, hipStream_t st, const BandPageTable *pt = nullptr);
+// band_attn_paged.hip: the PAGED kernels live in a translation unit of their own -- new instantiations inside band_attn_mfma.hip's module
+// change the inlining order, and with it the registers and code, of that module's existing D = 128 kernels.  One launch of the form the
+// caller planned (nt column tiles, split or not); the caller checks the launch.
+void launch_band_attn_paged_kernel(const BandAttnParams &P, const BandPageTable &pt, int dtype, int nt, bool split, unsigned grid, size_t lds, hipStream_t st);
 int launch_band_attn_fwd_dual(const BandAttnParams &P0, const BandAttnParams &P1, int dtype, hipStream_t st);
 // the sliding (w) and compressed (c) branch of a decode step as extra workgroups of ANOTHER launch (the one-launch decode step of the
 // selected branch): workgroups [n_sel, n_sel + n_w) take w, those behind them c; every wave of such a workgroup is one (row, split) unit
