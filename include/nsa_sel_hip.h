@@ -337,6 +337,57 @@ NSA_API int nsa_layer_decode_ragged(const nsa_layer_desc *L, const nsa_kv_desc *
 NSA_API int nsa_layer_decode_ragged_plan(const nsa_layer_desc *L, int B, int S, int S_max, int t_max, int S_sel, int *launches /* host */,
                                  int *route /* host */);
 
+/* The ragged layer decode over PAGED caches: nsa_layer_decode_ragged with all eight cache tensors held in pools of fixed-size pages and
+ * found through a device block table -- the layer around nsa_sel_decode_paged and nsa_band_attn_fwd_paged, and the one place that WRITES
+ * a token into a page.
+ *   nsa_paged_kv_desc   K_sel, V_sel, K_win, V_win, K_raw, V_raw  [n_pages, G, 1024, D] and K_cmp, V_cmp [n_pages, G, 64, D], each contiguous
+ *                 (as nsa_kv_desc requires of its slabs) and 16-byte aligned.  block_table: device int32 [B, max_pages], table_stride
+ *                 elements between its rows (>= max_pages).  ONE page id serves all eight pools: entry [b, j] holds tokens
+ *                 [1024 j, 1024 j + 1024) and compressed rows [64 j, 64 j + 64) of sequence b.  The capacity that stands for S_max is
+ *                 max_pages * 1024 (max_pages <= 2^20).  Page bases are formed in 64 bits, so a pool may exceed 2 GiB.
+ *                 OWNERSHIP: the page a live sequence appends to -- the page(s) of positions t_pos[b] .. t_pos[b] + S - 1 and of the
+ *                 compressed rows emitted there -- must belong to that sequence ALONE; pages that are only read may be shared between
+ *                 sequences (a common prefix).  Nothing checks this: two sequences appending to one page overwrite each other.
+ *   x, y, t_pos, t_max, S, csc_*, S_sel, ranges_out, gates_out   as in nsa_layer_decode_ragged; te = min(t_max, max_pages * 1024 - 1).  The
+ *                 host reads neither t_pos nor the table, and the arguments do not change from token to token.
+ * One verdict per sequence: the call's first launch, one wave per sequence, writes t_live[b] into the workspace -- t_pos[b] where the
+ * sequence is live under the ragged rule (0 <= t_pos[b], t_pos[b] + S - 1 <= te) AND every table entry j = 0 .. (t_pos[b] + S - 1) >> 10
+ * lies in [0, n_pages); -1 otherwise.  Every later launch takes t_live as its position array, so writers and readers agree: an inactive
+ * sequence appends NOTHING to any pool and gets zero y and ranges_out rows (gates_out rows unspecified, as in the ragged call).  Beyond the
+ * verdict every kernel forms an address only from a table entry it has itself tested against [0, n_pages): the two writers re-test the
+ * one or two entries they use, the readers test as nsa_sel_decode_paged / nsa_band_attn_fwd_paged do.  No table value can send a load or
+ * a store outside the pools; nothing is clamped silently.
+ * Launches: 0. the verdicts, 1. the fused QKV projection with RoPE + append (row (b, s) at pos = t_live[b] + s goes to row pos & 1023 of
+ * page table[b][pos >> 10] of the six token pools; the S rows of a sequence may lie in two pages), 2. pooling (compressed row j =
+ * n_cmp(t_live[b]) + k from raw rows [16 j, 16 j + 32), every one found through its own page -- j = 63 reads rows 1008 .. 1039 -- into row
+ * j & 63 of page table[b][j >> 6]), 3. nsa_sel_decode_paged's launch, 4. the sliding and the compressed branch as one
+ * nsa_band_attn_fwd_paged launch each (page_rows 1024 / 64; in split form each is followed by its combine), 5. gates + mix (the finish
+ * kernel at Dv = 64, the gate kernel at 128), 6. the output projection.  Ten launches at the m7c shape.
+ * Bits: for a table that scatters contiguous slabs into pages, in any order, the appended rows, the pooled rows and the ranges are those of
+ * nsa_layer_decode_ragged on the slabs bit for bit; at Dv = 128 y and the gates too.  At Dv = 64 the ragged call merges the band splits in
+ * its finish kernel while this call combines per branch: y is within the rounding of that.
+ * DECLINES with NSA_ERR_INVALID and a message naming the limit, no fallback, wherever nsa_layer_decode_ragged and the two paged operators
+ * do: a dtype other than bf16 / f16, anything but Dk = Dv in {64, 128} and the default block geometry, h > 16, w < 1, te beyond the unsplit
+ * forms, DECODE_STEP = 0 or DECODE_UNFUSED = 1, S outside [1,16], a null or misaligned operand, max_pages outside [1, 2^20], n_pages < 1, a
+ * table stride below max_pages.
+ * nsa_layer_decode_paged_plan makes no HIP call: NSA_OK with *launches = n and *route = 1, or *launches = 0 and *route = -1 for a declined
+ * shape; an error status for bad arguments.  workspace: nsa_layer_decode_paged_workspace() bytes, 256-byte aligned (0 for a null descriptor,
+ * B < 1, S outside [1,16] or max_pages outside [1, 2^20]); it does not grow with max_pages beyond the contexts the unsplit forms reach. */
+typedef struct nsa_paged_kv_desc {
+    void *K_sel, *V_sel, *K_win, *V_win, *K_raw, *V_raw; /* [n_pages, G, 1024, D] */
+    void *K_cmp, *V_cmp;                                 /* [n_pages, G, 64, D] */
+    const int32_t *block_table;                          /* device, [B, max_pages] */
+    int64_t table_stride;
+    int n_pages, B, max_pages;
+} nsa_paged_kv_desc;
+NSA_API size_t nsa_layer_decode_paged_workspace(const nsa_layer_desc *L, int B, int S, int max_pages);
+NSA_API int nsa_layer_decode_paged(const nsa_layer_desc *L, const nsa_paged_kv_desc *pkv, const void *x, void *y,
+                           const int32_t *t_pos /* device [B] */, int t_max /* host */, int S, const int32_t *csc_ptr,
+                           const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out, float *gates_out,
+                           void *workspace, size_t workspace_bytes, void *stream);
+NSA_API int nsa_layer_decode_paged_plan(const nsa_layer_desc *L, int B, int S, int max_pages, int t_max, int S_sel, int *launches /* host */,
+                                int *route /* host */);
+
 /* ---------------------------------------------------------------------------------------
  * Eq.9 map in gather (CSC) form.  For selection block j the entries csc_ptr[j]..csc_ptr[j+1]
  * list (cmp row, weight) in ASCENDING cmp row -- the order the reference's CPU scatter_add

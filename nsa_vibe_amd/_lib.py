@@ -39,7 +39,13 @@ class NsaBlockDesc(C.Structure):
                 ("norm_eps", _f)]
 
 
-_pl, _pk, _pb = C.POINTER(NsaLayerDesc), C.POINTER(NsaKvDesc), C.POINTER(NsaBlockDesc)
+class NsaPagedKvDesc(C.Structure):
+    """struct nsa_paged_kv_desc (include/nsa_sel_hip.h)"""
+    _fields_ = [(n, _vp) for n in ("K_sel", "V_sel", "K_win", "V_win", "K_raw", "V_raw", "K_cmp", "V_cmp", "block_table")] + \
+               [("table_stride", _i64)] + [(n, _i) for n in ("n_pages", "B", "max_pages")]
+
+
+_pl, _pk, _pb, _pp = C.POINTER(NsaLayerDesc), C.POINTER(NsaKvDesc), C.POINTER(NsaBlockDesc), C.POINTER(NsaPagedKvDesc)
 
 # name -> (restype, argtypes); mirrors include/nsa_sel_hip.h one to one
 SIGNATURES = {
@@ -81,6 +87,9 @@ SIGNATURES = {
     "nsa_layer_decode_ragged_workspace": (_sz, [_pl, _i, _i, _i]),
     "nsa_layer_decode_ragged": (_i, [_pl, _pk, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "nsa_layer_decode_ragged_plan": (_i, [_pl, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "nsa_layer_decode_paged_workspace": (_sz, [_pl, _i, _i, _i]),
+    "nsa_layer_decode_paged": (_i, [_pl, _pp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "nsa_layer_decode_paged_plan": (_i, [_pl, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "nsa_band_attn_bwd_workspace": (_sz, [_i] * 9),
     "nsa_band_attn_bwd": (_i, [_vp] * 9 + [_i] * 7 + [_i64] * 6 + [_i] * 5 + [_i, _f, _i, _vp, _sz, _vp]),
     "nsa_block_counts": (_i, [_i] * 4 + [C.POINTER(_i)] * 3),

@@ -7,6 +7,7 @@
 //   dispatch_check <library> ragged | layer_ragged  the cases of the entry points with per-sequence positions instead
 //   dispatch_check <library> paged                  the cases of the ragged decode step over paged caches (nsa_sel_decode_paged)
 //   dispatch_check <library> band_paged             the cases of the ragged band forward over paged caches (nsa_band_attn_fwd_paged)
+//   dispatch_check <library> layer_paged            the cases of the layer's paged call (nsa_layer_decode_paged)
 #include <dlfcn.h>
 #include <math.h>
 #include <stdio.h>
@@ -781,9 +782,145 @@ static void layer_ragged_cases() {
     NSA_FN(nsa_hip_set_tuning)("DECODE_UNFUSED", -1);
 }
 
+// ---- dispatch_check <library> layer_paged: the layer's paged call (nsa_layer_decode_paged), cases of their own like `layer_ragged`.  Every
+// case prints the launchers in order with their geometry, the plan's answer for the same shape, the verdict launch's block, BOTH writers'
+// argument blocks in full (RopePagedParams, CmpPoolPagedParams: the pools, the capacities, the table block) and the position array and the
+// table as they arrive at the readers.  The positions, the table and the pools are device memory the host must never read: addresses inside
+// buffers of 0x7f bytes.  Every launch behind the pre-pass must name ws + <the offset of t_live> as its position array, never t_pos.
+static void layer_paged_cases() {
+    const size_t MB = 1 << 20;
+    void *x = dev(MB), *y = dev(MB), *W_qkv = dev(MB), *W_out = dev(MB), *gw = dev(MB), *ws = dev(128 * MB);
+    void *pool[8];
+    static const char *pname[8] = {"K_sel", "V_sel", "K_win", "V_win", "K_raw", "V_raw", "K_cmp", "V_cmp"};
+    int32_t *t_pos = (int32_t *)dev(MB, 0x7f), *table = (int32_t *)dev(MB, 0x7f), *ranges = (int32_t *)dev(MB);
+    float *gates = (float *)dev(MB);
+    g_named = {{"x", x, MB}, {"y", y, MB}, {"W_qkv", W_qkv, MB}, {"W_out", W_out, MB}, {"t_pos", t_pos, MB}, {"table", table, MB}, {"ranges", ranges, MB},
+               {"gates", gates, MB}, {"ws", ws, 128 * MB}};
+    for (int i = 0; i < 8; ++i) {
+        pool[i] = dev(MB, 0x7f);
+        g_named.push_back({pname[i], pool[i], MB});
+    }
+    auto fn = NSA_FN(nsa_layer_decode_paged);
+    auto plan_fn = NSA_FN(nsa_layer_decode_paged_plan);
+    auto ws_fn = NSA_FN(nsa_layer_decode_paged_workspace);
+    struct Case {
+        int B = 3, S = 8, D = 64, dim = 768, h = 6, w = 512, max_pages = 2, n_pages = 7, t_max = 1059, dtype = NSA_DT_BF16;
+        int64_t table_stride = 0 /* 0: max_pages + 3 */;
+        const int32_t *t_pos = nullptr, *table = nullptr;
+        void *K_win = nullptr;
+        bool with_ws = true;
+    };
+    auto block = [](const char *launcher, int arg, size_t bytes, const char *key, std::function<std::string(const void *)> print) {
+        return Want{std::string(launcher) + " launch", arg, bytes, key, std::move(print)};
+    };
+    auto pgt = [](const nsa::LayerPageTable &T) { return Obj().p("table", T.table).i("stride", T.stride).i("n_pages", T.n_pages).i("max_pages", T.max_pages).str(); };
+    auto live = [pgt](const void *b) {
+        nsa::PagedLiveParams P;
+        memcpy(&P, b, sizeof(P));
+        return Obj().p("t_pos", P.t_pos).p("t_live", P.t_live).raw("pg", pgt(P.pg)).i("B", P.B).i("S", P.S).i("te", P.te).str();
+    };
+    auto rope = [pgt](const void *b) {
+        nsa::RopePagedParams P;
+        memcpy(&P, b, sizeof(P));
+        Obj o;
+        o.p("proj", P.proj).p("Q_out", P.Q_out);
+        for (int i = 0; i < 6; ++i) o.p(pname[i], P.cache[i]);
+        return o.i("B", P.B).i("S", P.S).i("G", P.G).i("h", P.h).i("Dk", P.Dk).i("Dv", P.Dv).i("S_max", P.S_max).i("t0", P.t0).f("rope_base", P.rope_base)
+            .f("inv_scale", P.inv_scale).p("t_pos", P.t_pos).i("t_max", P.t_max).raw("pg", pgt(P.pg)).str();
+    };
+    auto pool_block = [pgt](const void *b) {
+        nsa::CmpPoolPagedParams P;
+        memcpy(&P, b, sizeof(P));
+        return Obj().p("K_raw", P.K_raw).p("V_raw", P.V_raw).p("K_cmp", P.K_cmp).p("V_cmp", P.V_cmp).i("nbg", P.nbg).i("S_max", P.S_max).i("n_cmp_max", P.n_cmp_max)
+            .i("Dk", P.Dk).i("Dv", P.Dv).i("l", P.l).i("d", P.d).f("rope_base", P.rope_base).f("inv_scale", P.inv_scale).p("t_pos", P.t_pos).i("t_max", P.t_max)
+            .i("S", P.S).i("G", P.G).raw("pg", pgt(P.pg)).str();
+    };
+    auto step = [](const void *b) {
+        nsa::DecStepParams P;
+        memcpy(&P, b, sizeof(P));
+        return Obj().p("t_pos", P.t_pos).i("t_max", P.t_max).i("S", P.S).i("R", P.R).i("S_cmp", P.S_cmp).i("nchunk", P.nchunk).p("Kc", P.Kc).i("csb", P.csb)
+            .p("table", P.block_table).i("table_stride", P.bt_stride).i("n_pages", P.n_pages).str();
+    };
+    auto band = [](const void *b) {
+        nsa::BandAttnParams P;
+        memcpy(&P, b, sizeof(P));
+        return Obj().p("t_pos", P.t_pos).i("t_max", P.t_max).i("t0", P.t0).i("S_kv", P.S_kv).i("nsplit", P.nsplit).i("defer_combine", P.defer_combine).p("K", P.K)
+            .p("V", P.V).i("ksb", P.ksb).i("ksg", P.ksg).i("a", P.a).i("dd", P.dd).i("w", P.w).str();
+    };
+    auto band_table = [](const void *b) {
+        nsa::BandPageTable P;
+        memcpy(&P, b, sizeof(P));
+        return show(P);
+    };
+    const std::vector<Want> wants = {
+        block("paged_live", 0, sizeof(nsa::PagedLiveParams), "live", live),
+        block("qkv_rope_append(paged, mfma)", 0, sizeof(nsa::RopePagedParams), "rope", rope),
+        block("qkv_rope_append(paged)", 5, sizeof(nsa::RopePagedParams), "rope", rope),
+        block("cmp_pool(paged)", 0, sizeof(nsa::CmpPoolPagedParams), "pool", pool_block),
+        block("decode_paged", 0, sizeof(nsa::DecStepParams), "step", step),
+        block("band_attn_fwd(split)", 0, sizeof(nsa::BandAttnParams), "band", band),
+        block("band_attn_fwd(split)", 1, sizeof(nsa::BandPageTable), "band_table", band_table),
+        block("band_attn_fwd", 0, sizeof(nsa::BandAttnParams), "band", band),
+        block("band_attn_fwd", 1, sizeof(nsa::BandPageTable), "band_table", band_table),
+    };
+    auto layer_case = [&](const char *label, const std::function<void(Case &)> &tweak) {
+        Case c;
+        c.t_pos = t_pos + 5, c.table = table + 7, c.K_win = pool[2];
+        tweak(c);
+        nsa_layer_desc L{};
+        L.dim = c.dim; L.G = 2; L.h = c.h; L.Dk = L.Dv = c.D; L.l = 32; L.d = 16; L.l_sel = 64; L.n_sel = 16; L.w = c.w; L.gate_hidden = 32; L.dtype = c.dtype;
+        L.rope_base = 10000.f; L.rope_scale = 1.f; L.gate_tau = 1.f;
+        L.W_qkv = W_qkv; L.W_out = W_out; L.gate_w1 = L.gate_b1 = L.gate_w2 = L.gate_b2 = gw;
+        nsa_paged_kv_desc kv{};
+        kv.K_sel = pool[0]; kv.V_sel = pool[1]; kv.K_win = c.K_win; kv.V_win = pool[3]; kv.K_raw = pool[4]; kv.V_raw = pool[5]; kv.K_cmp = pool[6]; kv.V_cmp = pool[7];
+        kv.block_table = c.table;
+        kv.table_stride = c.table_stride ? c.table_stride : c.max_pages + 3;
+        kv.n_pages = c.n_pages; kv.B = c.B; kv.max_pages = c.max_pages;
+        const long long cap = (long long)c.max_pages * 1024;
+        const int te = c.t_max < cap - 1 ? c.t_max : (int)(cap - 1 > 0 ? cap - 1 : 0), S_sel = (te + 64) / 64;
+        run_args(std::string("layer_decode_paged/") + label, [&] {
+            return fn(&L, &kv, x, y, c.t_pos, c.t_max, c.S, nullptr, nullptr, nullptr, S_sel, ranges, gates, c.with_ws ? ws : nullptr, c.with_ws ? 128 * MB : 0, nullptr);
+        }, wants);
+        int launches = -7, route = -7;
+        const int prc = plan_fn(&L, c.B, c.S, c.max_pages, c.t_max, S_sel, &launches, &route);
+        printf(",\n%s: %s", quoted(std::string("layer_decode_paged/") + label + "_plan").c_str(),
+               Obj().i("rc", prc).i("launches", launches).i("route", route).i("workspace", (long long)ws_fn(&L, c.B, c.S, c.max_pages)).str().c_str());
+    };
+    layer_case("m7c_B3_S8", [](Case &) {});
+    layer_case("m7c_B16_S1", [](Case &c) { c.B = 16; c.S = 1; });
+    layer_case("m7c_B1_S2_chunk_loop", [](Case &c) { c.B = 1; c.S = 2; });
+    layer_case("m7c_B600_S3_unsplit_bands", [](Case &c) { c.B = 600; c.S = 3; });
+    layer_case("D128_B3_S4", [](Case &c) { c.D = 128; c.dim = 1536; c.S = 4; });
+    layer_case("t_max_beyond_capacity", [](Case &c) { c.t_max = 5000; });
+    layer_case("t_max_below_S", [](Case &c) { c.t_max = 3; });
+    layer_case("max_pages_2pow20", [](Case &c) { c.max_pages = 1 << 20; c.table_stride = 1 << 20; });
+    // the declines: each with its message and no launch
+    layer_case("f32_declined", [](Case &c) { c.dtype = NSA_DT_F32; });
+    layer_case("D96_declined", [](Case &c) { c.D = 96; });
+    layer_case("h17_declined", [](Case &c) { c.h = 17; });
+    layer_case("w0_declined", [](Case &c) { c.w = 0; });
+    layer_case("t_max70000_declined", [](Case &c) { c.max_pages = 128; c.t_max = 70000; });
+    layer_case("D128_t_max20000_declined", [](Case &c) { c.D = 128; c.dim = 1536; c.max_pages = 32; c.t_max = 20000; });
+    layer_case("S17_refused", [](Case &c) { c.S = 17; });
+    layer_case("null_t_pos", [](Case &c) { c.t_pos = nullptr; });
+    layer_case("t_pos_2_bytes_off", [&](Case &c) { c.t_pos = (const int32_t *)off(t_pos, 2); });
+    layer_case("null_table", [](Case &c) { c.table = nullptr; });
+    layer_case("table_2_bytes_off", [&](Case &c) { c.table = (const int32_t *)off(table, 2); });
+    layer_case("table_stride_below_max_pages", [](Case &c) { c.table_stride = 1; });
+    layer_case("max_pages0", [](Case &c) { c.max_pages = 0; c.table_stride = 4; });
+    layer_case("max_pages_above_2pow20", [](Case &c) { c.max_pages = (1 << 20) + 1; c.table_stride = 1 << 21; });
+    layer_case("n_pages0", [](Case &c) { c.n_pages = 0; });
+    layer_case("null_pool", [](Case &c) { c.K_win = nullptr; });
+    layer_case("K_win_2_bytes_off", [&](Case &c) { c.K_win = off(pool[2], 2); });
+    layer_case("no_workspace", [](Case &c) { c.with_ws = false; });
+    NSA_FN(nsa_hip_set_tuning)("DECODE_UNFUSED", 1);
+    layer_case("DECODE_UNFUSED_1_declined", [](Case &) {});
+    NSA_FN(nsa_hip_set_tuning)("DECODE_UNFUSED", -1);
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: dispatch_check <libnsa_sel_hip.so> [ragged | layer_ragged | paged | band_paged]\n");
+        fprintf(stderr, "usage: dispatch_check <libnsa_sel_hip.so> [ragged | layer_ragged | layer_paged | paged | band_paged]\n");
         return 2;
     }
     g_lib = dlopen(argv[1], RTLD_NOW | RTLD_GLOBAL);
@@ -812,6 +949,12 @@ int main(int argc, char **argv) {
     if (argc >= 3 && !strcmp(argv[2], "layer_ragged")) {  // the layer's ragged call alone (tests/test_layer_decode_ragged_host.py)
         printf("{");
         layer_ragged_cases();
+        printf("\n}\n");
+        return 0;
+    }
+    if (argc >= 3 && !strcmp(argv[2], "layer_paged")) {  // the layer's paged call alone (tests/test_layer_decode_paged_host.py)
+        printf("{");
+        layer_paged_cases();
         printf("\n}\n");
         return 0;
     }

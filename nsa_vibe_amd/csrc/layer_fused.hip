@@ -281,7 +281,32 @@ struct RopeRowsDest {
         d[0] = Elt<T>::from_f(x0);
         d[1] = Elt<T>::from_f(x1);
     }
+    // ---- paged form (RopePagedParams): dst is row 0 of the group's plane in pool page 0, sb the page stride
+    __device__ __forceinline__ void init_paged(const RopeAppendParams &P, int col) {
+        const QkvCol<T> c(P, col, LAYER_PAGE_TOKENS, 0);
+        rot = c.ri >= 0;
+        ri = c.ri;
+        rD = c.rD;
+        dst = c.p;
+        sb = c.sb;
+        ss = c.ss;
+    }
+    // page: the pool page of the row's position pos = sq.t0 + s, already tested against [0, n_pages) by the caller (rope_page); -1 = no store
+    __device__ __forceinline__ void store_paged(bool q, int b, int s, const RopeSeq &sq, int page, float sn, float cs, float x0, float x1) const {
+        if (!q && (!sq.live || page < 0)) return;
+        if (rot) rope_rotate<T>(x0, x1, sn, cs, x0, x1);
+        T *d = q ? dst + b * sb + (int64_t)s * ss : dst + (int64_t)page * sb + (int64_t)((sq.t0 + s) & (LAYER_PAGE_TOKENS - 1)) * ss;
+        d[0] = Elt<T>::from_f(x0);
+        d[1] = Elt<T>::from_f(x1);
+    }
 };
+// the pool page that holds position pos of live sequence b, or -1: the entry is read only for a live sequence (then pos < capacity, so the
+// index is inside the table's row) and returned only after its test against [0, n_pages)
+__device__ __forceinline__ int rope_page(const LayerPageTable &pg, int b, const RopeSeq &sq, int pos) {
+    if (!sq.live) return -1;
+    const int e = pg.table[(int64_t)b * pg.stride + (pos >> 10)];
+    return e >= 0 && e < pg.n_pages ? e : -1;
+}
 
 // ------------------------------------------------------------------------------------------ few-row projections on the VALU
 // out[m, n] = A[m, :] . W[n, :] for a few rows m: a wave owns CW weight rows (1; 2 = a rotation pair; 4 = the LM head, where four rows in
@@ -464,11 +489,12 @@ struct RopeRowsEpi {
 // RopeRaggedEpi (CW = 2, chunk loop): RopeRowsEpi with per-sequence positions (P.t_pos), row m = b S + s appended at t_pos[b] + s where the
 // sequence is live.  The wave's pair has one rotation per (b, s) now: lane m evaluates that of row m for the first 64 rows (the route
 // hands the chunk loop the calls of one or two rows), lane 0 evaluates a later row's when it stores it.  The scalar form keeps its table.
-template <typename T>
+// PAGED (nsa_layer_decode_paged): the argument block with the table at its end; a cache row goes to the page of its own position
+template <typename T, bool PAGED = false>
 struct RopeRaggedEpi {
     static constexpr int MIN_BLOCKS = 2, GROUP = 2;
     static constexpr int TABLE = 64;
-    RopeAppendParams P;
+    std::conditional_t<PAGED, RopePagedParams, RopeAppendParams> P;
     struct Wave {
         RopeRowsDest<T> rd;
         bool q;
@@ -477,7 +503,8 @@ struct RopeRaggedEpi {
     __device__ __forceinline__ Wave init(int n0) const {
         __shared__ float sc[4][TABLE][2];
         Wave w;
-        w.rd.init(P, n0);
+        if constexpr (PAGED) w.rd.init_paged(P, n0);
+        else w.rd.init(P, n0);
         w.q = n0 < P.G * P.h * P.Dk;
         const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
         if (lane < P.B * P.S) {
@@ -498,7 +525,8 @@ struct RopeRaggedEpi {
         } else {
             w.rd.sincos_at(P, sq.t0 + si, sn, cs);
         }
-        w.rd.store_at(w.q, b, si, sq, sn, cs, rnd<T>(s[0]), rnd<T>(s[1]));
+        if constexpr (PAGED) w.rd.store_paged(w.q, b, si, sq, w.q ? -1 : rope_page(P.pg, b, sq, sq.t0 + si), sn, cs, rnd<T>(s[0]), rnd<T>(s[1]));
+        else w.rd.store_at(w.q, b, si, sq, sn, cs, rnd<T>(s[0]), rnd<T>(s[1]));
     }
 };
 
@@ -620,13 +648,17 @@ struct LinearMixArgs {
 // ROWS (with ROPE): P.S <= 16 consecutive tokens per sequence, row m = b P.S + s appended at position P.t0 + s (RopeRowsDest)
 // RAGGED (with ROWS): at position P.t_pos[b] + s, the cache rows of a live sequence only (rope_seq).  A template flag: the scalar
 // instantiations keep their code
-template <typename T, bool ROPE, bool MIX = false, int NWV = 4, bool ROWS = false, bool RAGGED = false>
-__global__ __launch_bounds__(NWV * 64, 2) void linear_mfma_kernel(RopeAppendParams P, const T *__restrict__ X, const T *__restrict__ W,
+// PAGED (with RAGGED; nsa_layer_decode_paged): the argument block is RopePagedParams, the six caches are pools of pages; the thread looks up
+// the page of its row's position beside the position itself and tests it before any address is formed (rope_page)
+template <typename T, bool ROPE, bool MIX = false, int NWV = 4, bool ROWS = false, bool RAGGED = false, bool PAGED = false>
+__global__ __launch_bounds__(NWV * 64, 2) void linear_mfma_kernel(std::conditional_t<PAGED, RopePagedParams, RopeAppendParams> P, const T *__restrict__ X,
+                                                               const T *__restrict__ W,
                                                                T *__restrict__ out, int M, int N, int K, int epi, const T *__restrict__ res,
                                                                LinearMixArgs mx) {
     static_assert(NWV == 4 || (NWV == 8 && !ROPE && !MIX), "eight waves: the plain projection only");
     static_assert(!ROWS || ROPE, "rows form: the RoPE + append epilogue only");
     static_assert(!RAGGED || ROWS, "ragged form: the rows epilogue only");
+    static_assert(!PAGED || RAGGED, "paged form: the ragged rows epilogue only");
     using MT_ = MfmaT<T>;
     using x8 = typename MT_::x8;
     __shared__ float part[NWV][16][65];
@@ -657,12 +689,15 @@ __global__ __launch_bounds__(NWV * 64, 2) void linear_mfma_kernel(RopeAppendPara
     // m = m0 + t % 64 evaluates the rotations of its own two pairs at t_pos[b] + s here, before the loads go out (one position load each)
     [[maybe_unused]] RopeSeq sq{0, false};
     [[maybe_unused]] float rsn[2], rcs[2];
+    [[maybe_unused]] int page = -1;  // PAGED: the pool page of this thread's row (one lookup beside the position's), -1 = no cache store
     if constexpr (RAGGED) {
         const int mr = min(m0 + (int)(threadIdx.x & 63), M - 1), b = mr / P.S;
         sq = rope_seq(P, b);
+        if constexpr (PAGED) page = rope_page(P.pg, b, sq, sq.t0 + (mr - b * P.S));
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
-            rd[p].init(P, min(n0 + 4 * (int)(threadIdx.x >> 6) + 2 * p, N - 2));
+            if constexpr (PAGED) rd[p].init_paged(P, min(n0 + 4 * (int)(threadIdx.x >> 6) + 2 * p, N - 2));
+            else rd[p].init(P, min(n0 + 4 * (int)(threadIdx.x >> 6) + 2 * p, N - 2));
             rd[p].sincos_at(P, sq.t0 + (mr - b * P.S), rsn[p], rcs[p]);
         }
     } else if constexpr (ROWS) {
@@ -764,7 +799,10 @@ __global__ __launch_bounds__(NWV * 64, 2) void linear_mfma_kernel(RopeAppendPara
 #pragma unroll
         for (int p = 0; p < 2; ++p)
             if (n0 + 4 * nq + 2 * p < N) {
-                if constexpr (RAGGED) {
+                if constexpr (PAGED) {
+                    const int b = m / P.S;
+                    rd[p].store_paged(n0 + 4 * nq + 2 * p < P.G * P.h * P.Dk, b, m - b * P.S, sq, page, rsn[p], rcs[p], rnd<T>(v[2 * p]), rnd<T>(v[2 * p + 1]));
+                } else if constexpr (RAGGED) {
                     const int b = m / P.S;
                     rd[p].store_at(n0 + 4 * nq + 2 * p < P.G * P.h * P.Dk, b, m - b * P.S, sq, rsn[p], rcs[p], rnd<T>(v[2 * p]), rnd<T>(v[2 * p + 1]));
                 } else if constexpr (ROWS) {
@@ -826,11 +864,11 @@ static void launch_proj_valu(const ProjRoute &r, const LinearCall &c, const AOp 
     }
     if constexpr (std::is_same_v<AOp, RowsA<T>>) go(proj_loop_kernel<T, CW, AOp, Epi>);
 }
-template <bool ROPE, bool MIX, int NWV, bool ROWS, bool RAGGED = false>
-static void launch_linear_mfma(const RopeAppendParams &P, const ProjRoute &r, const LinearCall &c) {
+template <bool ROPE, bool MIX, int NWV, bool ROWS, bool RAGGED = false, bool PAGED = false>
+static void launch_linear_mfma(const std::conditional_t<PAGED, RopePagedParams, RopeAppendParams> &P, const ProjRoute &r, const LinearCall &c) {
     with_elt<false>(c.dtype, [&](auto t) {
         using T = decltype(t);
-        hipLaunchKernelGGL((linear_mfma_kernel<T, ROPE, MIX, NWV, ROWS, RAGGED>), r.grid, dim3(NWV * 64), 0, c.st, P, (const T *)c.A, (const T *)c.W, (T *)c.out, c.M,
+        hipLaunchKernelGGL((linear_mfma_kernel<T, ROPE, MIX, NWV, ROWS, RAGGED, PAGED>), r.grid, dim3(NWV * 64), 0, c.st, P, (const T *)c.A, (const T *)c.W, (T *)c.out, c.M,
                            c.N, c.K, c.epi, (const T *)c.res, LinearMixArgs{c.Os, c.Ow, c.gates, c.G});
     });
 }
@@ -910,6 +948,52 @@ int launch_qkv_rope_append(const RopeAppendParams &P, const LinearCall &c, bool 
     return NSA_OK;
 }
 
+// the paged call's projection: the rows route (MFMA from three rows on, else the chunk loop), its PAGED instantiations
+int launch_qkv_rope_append_paged(const RopePagedParams &P, const LinearCall &c) {
+    NSA_CHECK_ARG(P.S >= 1 && P.S <= RopeRowsEpi<float>::MAX_S, "qkv_rope_append(paged): 1 to 16 tokens per sequence");
+    NSA_CHECK_ARG(P.t_pos && P.t0 == 0 && P.pg.table && P.pg.n_pages >= 1 && P.pg.stride >= P.pg.max_pages && P.S_max == P.pg.max_pages * LAYER_PAGE_TOKENS,
+                  "qkv_rope_append(paged): positions, a block table and the capacity max_pages * 1024");
+    NSA_CHECK_ARG(c.dtype == NSA_DT_BF16 || c.dtype == NSA_DT_F16, "qkv_rope_append(paged): bf16 / f16 only");
+    const ProjRoute r = proj_route(c, PROJ_ROPE_ROWS);
+    if (r.form == PROJ_MFMA) {
+        launch_linear_mfma<true, false, 4, true, true, true>(P, r, c);
+        NSA_LAUNCH_CHECK("qkv_rope_append(paged, mfma)");
+        return NSA_OK;
+    }
+    with_elt<false>(c.dtype, [&](auto t) {
+        using T = decltype(t);
+        launch_proj_valu<T, 2>(r, c, RowsA<T>{(const T *)c.A, (const T *)c.norm_w, c.eps}, RopeRaggedEpi<T, true>{P});
+    });
+    NSA_LAUNCH_CHECK("qkv_rope_append(paged)");
+    return NSA_OK;
+}
+
+// the paged call's verdicts: wave b tests sequence b once for every later launch (they take t_live as their position array)
+__global__ __launch_bounds__(256) void paged_live_kernel(PagedLiveParams P) {
+    const int b = (int)(blockIdx.x * 4 + (threadIdx.x >> 6)), lane = lane_id();
+    if (b >= P.B) return;
+    const int t0 = P.t_pos[b];
+    bool ok = t0 >= 0 && t0 <= P.te - (P.S - 1);  // (te <= max_pages * 1024 - 1: the entries read below lie inside the table's row)
+    if (ok) {
+        const int last = (t0 + P.S - 1) >> 10;
+        int bad = 0;
+        for (int j = lane; j <= last; j += 64) {
+            const int e = P.pg.table[(int64_t)b * P.pg.stride + j];
+            bad |= (e < 0 || e >= P.pg.n_pages) ? 1 : 0;
+        }
+        ok = wave_sum_i(bad) == 0;
+    }
+    if (lane == 0) P.t_live[b] = ok ? t0 : -1;
+}
+int launch_paged_live(const PagedLiveParams &P, hipStream_t st) {
+    NSA_CHECK_ARG(P.t_pos && P.t_live && P.pg.table && P.B >= 1 && P.S >= 1 && P.pg.n_pages >= 1 && P.pg.max_pages >= 1 && P.pg.stride >= P.pg.max_pages &&
+                      P.te >= 0 && (int64_t)P.te <= (int64_t)P.pg.max_pages * LAYER_PAGE_TOKENS - 1,
+                  "paged_live: positions, a block table and te inside the capacity max_pages * 1024");
+    hipLaunchKernelGGL(paged_live_kernel, dim3((unsigned)((P.B + 3) / 4)), dim3(256), 0, st, P);
+    NSA_LAUNCH_CHECK("paged_live");
+    return NSA_OK;
+}
+
 // ------------------------------------------------------------------------------------------ compressed-token emission
 // one 64-thread block per (b, g, j): K_cmp[j] = mean_i rope(K_raw[j d + i], pos = j d + i), V_cmp[j] = mean_i V_raw[j d + i]
 template <typename T>
@@ -969,8 +1053,13 @@ __global__ __launch_bounds__(64) void cmp_pool_kernel(CmpPoolParams P) {
 // pairs of a block -- it depends on position and pair only -- was tried: fewer, serial blocks, 30 -> 45 us at 4k x 8.)
 // RAGGED (launch_cmp_pool_ragged): ceil(S / d) blocks per (b, g); block k takes token n_cmp(t_pos[b]) + k and leaves -- the whole block, before
 // the barrier -- unless the sequence is live and emits that token inside its S rows.  A template flag: the scalar kernel keeps its code.
-template <typename T, bool RAGGED = false>
-__global__ __launch_bounds__(256) void cmp_pool_wide_kernel(CmpPoolParams P) {
+// PAGED (with RAGGED; launch_cmp_pool_paged, l = 32, d = 16): the four tensors are pools of pages.  The window of token j -- raw rows
+// [16 j, 16 j + 32) -- can straddle a page boundary (j = 63: rows 1008 .. 1039), so every window row is found through its own page: entry
+// r >> 10 of the sequence's table row, one of the two entries the block tests before it forms any address (the first is also the page
+// of compressed row j: j >> 6 = 16 j >> 10).  The additions and their order are the ragged kernel's: the same bits.
+template <typename T, bool RAGGED = false, bool PAGED = false>
+__global__ __launch_bounds__(256) void cmp_pool_wide_kernel(std::conditional_t<PAGED, CmpPoolPagedParams, CmpPoolParams> P) {
+    static_assert(!PAGED || RAGGED, "paged form: the ragged form only");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *rk = (float *)smem;    // [l][Dk] rotated raw keys
     float *rv = rk + P.l * P.Dk;  // [l][Dv] raw values
@@ -988,14 +1077,36 @@ __global__ __launch_bounds__(256) void cmp_pool_wide_kernel(CmpPoolParams P) {
         j = P.j0 + (int)(blockIdx.x % nj);
         bg = (int)(blockIdx.x / nj);
     }
-    const T *Kr = (const T *)P.K_raw + (int64_t)bg * P.S_max * P.Dk;
-    const T *Vr = (const T *)P.V_raw + (int64_t)bg * P.S_max * P.Dv;
-    T *Kc = (T *)P.K_cmp + ((int64_t)bg * P.n_cmp_max + j) * P.Dk;
-    T *Vc = (T *)P.V_cmp + ((int64_t)bg * P.n_cmp_max + j) * P.Dv;
     const int r0 = j * P.d, hp = P.Dk / 2;
+    const T *Kr, *Vr;
+    T *Kc, *Vc;
+    [[maybe_unused]] int64_t pl0 = 0, pl1 = 0;  // PAGED: the (page, group) planes of the window's first and last row
+    if constexpr (PAGED) {
+        // (the sequence is live and emits j inside its rows: rows r0 .. r0 + l - 1 lie below t0 + S <= the capacity, their entries in the row)
+        const int g = bg % P.G;
+        const int32_t *row = P.pg.table + (int64_t)(bg / P.G) * P.pg.stride;
+        const int e0 = row[r0 >> 10], e1 = row[(r0 + P.l - 1) >> 10];
+        if (e0 < 0 || e0 >= P.pg.n_pages || e1 < 0 || e1 >= P.pg.n_pages) return;  // (the whole block, before the barrier)
+        pl0 = (int64_t)e0 * P.G + g;  // (formed in 64 bits: a pool may exceed 2 GiB)
+        pl1 = (int64_t)e1 * P.G + g;
+        Kr = (const T *)P.K_raw;  // the pools: a window row's plane and row inside it are added per row (prow)
+        Vr = (const T *)P.V_raw;
+        Kc = (T *)P.K_cmp + (pl0 * LAYER_PAGE_CMP + (j & (LAYER_PAGE_CMP - 1))) * P.Dk;
+        Vc = (T *)P.V_cmp + (pl0 * LAYER_PAGE_CMP + (j & (LAYER_PAGE_CMP - 1))) * P.Dv;
+    } else {
+        Kr = (const T *)P.K_raw + (int64_t)bg * P.S_max * P.Dk;
+        Vr = (const T *)P.V_raw + (int64_t)bg * P.S_max * P.Dv;
+        Kc = (T *)P.K_cmp + ((int64_t)bg * P.n_cmp_max + j) * P.Dk;
+        Vc = (T *)P.V_cmp + ((int64_t)bg * P.n_cmp_max + j) * P.Dv;
+    }
+    // where raw row r of the sequence lies: PAGED -- in the first page's plane up to that page's last row, behind it in the second's
+    auto prow = [&](int r) {
+        if constexpr (PAGED) return ((r >> 10) == (r0 >> 10) ? pl0 : pl1) * LAYER_PAGE_TOKENS + (r & (LAYER_PAGE_TOKENS - 1));
+        else return (int64_t)r;
+    };
     for (int it = threadIdx.x; it < P.l * hp; it += 256) {
         const int i = it / hp, pp = it - i * hp;
-        const T *src = Kr + (int64_t)(r0 + i) * P.Dk + 2 * pp;
+        const T *src = Kr + prow(r0 + i) * P.Dk + 2 * pp;
         float x0, x1;
         rope_pair<T>(Elt<T>::to_f(src[0]), Elt<T>::to_f(src[1]), pp, P.Dk, (float)(r0 + i), P.rope_base, P.inv_scale, x0, x1);
         rk[i * P.Dk + 2 * pp] = x0;
@@ -1003,7 +1114,7 @@ __global__ __launch_bounds__(256) void cmp_pool_wide_kernel(CmpPoolParams P) {
     }
     for (int it = threadIdx.x; it < P.l * P.Dv; it += 256) {
         const int i = it / P.Dv, c = it - i * P.Dv;
-        rv[it] = Elt<T>::to_f(Vr[(int64_t)(r0 + i) * P.Dv + c]);
+        rv[it] = Elt<T>::to_f(Vr[prow(r0 + i) * P.Dv + c]);
     }
     __syncthreads();
     for (int c = threadIdx.x; c < P.Dk + P.Dv; c += 256) {
@@ -1044,6 +1155,23 @@ int launch_cmp_pool_ragged(const CmpPoolParams &P, int dtype, hipStream_t st) {
                   "cmp_pool(ragged): the wide form holds l (Dk + Dv) floats in 48 KiB of LDS (l = %d, Dk = %d, Dv = %d)", P.l, P.Dk, P.Dv);
     with_elt(dtype, [&](auto t) { hipLaunchKernelGGL((cmp_pool_wide_kernel<decltype(t), true>), dim3((unsigned)nblk), dim3(256), lds, st, P); });
     NSA_LAUNCH_CHECK("cmp_pool(ragged)");
+    return NSA_OK;
+}
+
+// the same grid over pools of pages: the default block geometry only (a window then touches at most two pages, and compressed page j >> 6
+// is the page of the window's first row)
+int launch_cmp_pool_paged(const CmpPoolPagedParams &P, int dtype, hipStream_t st) {
+    NSA_CHECK_ARG(P.t_pos && P.S >= 1 && P.G >= 1 && P.nbg >= 1 && P.nbg % P.G == 0, "cmp_pool(paged): positions, S >= 1 and whole sequences");
+    NSA_CHECK_ARG(P.l == 32 && P.d == 16 && (dtype == NSA_DT_BF16 || dtype == NSA_DT_F16), "cmp_pool(paged): bf16 / f16 and the default block geometry only");
+    NSA_CHECK_ARG(P.pg.table && P.pg.n_pages >= 1 && P.pg.max_pages >= 1 && P.pg.stride >= P.pg.max_pages && P.S_max == P.pg.max_pages * LAYER_PAGE_TOKENS &&
+                      P.n_cmp_max == P.pg.max_pages * LAYER_PAGE_CMP,
+                  "cmp_pool(paged): a block table and the capacities max_pages * 1024 / max_pages * 64");
+    const int64_t nblk = (int64_t)P.nbg * ((P.S + P.d - 1) / P.d);
+    const size_t lds = sizeof(float) * (size_t)P.l * (size_t)(P.Dk + P.Dv);
+    NSA_CHECK_ARG(lds <= 48 * 1024 && P.Dk % 2 == 0 && nblk < ((int64_t)1 << 31),
+                  "cmp_pool(paged): the wide form holds l (Dk + Dv) floats in 48 KiB of LDS (l = %d, Dk = %d, Dv = %d)", P.l, P.Dk, P.Dv);
+    with_elt<false>(dtype, [&](auto t) { hipLaunchKernelGGL((cmp_pool_wide_kernel<decltype(t), true, true>), dim3((unsigned)nblk), dim3(256), lds, st, P); });
+    NSA_LAUNCH_CHECK("cmp_pool(paged)");
     return NSA_OK;
 }
 

@@ -27,6 +27,32 @@ struct CmpPoolParams {
     const int32_t *t_pos;
     int t_max, S, G;
 };
+// ---- paged caches (nsa_layer_decode_paged): the eight cache tensors are pools [n_pages, G, 1024 | 64, D] found through a device block table.
+// One table block, and the two writers' argument blocks with it at their end -- the PAGED instantiations alone take these; RopeAppendParams,
+// CmpPoolParams and every other instantiation keep their layout.  Entry [b, j] of the table is the pool page of tokens [1024 j, 1024 j + 1024)
+// and compressed rows [64 j, 64 j + 64) of sequence b.  A kernel forms an address only from an entry it has itself tested against [0, n_pages).
+constexpr int LAYER_PAGE_TOKENS = 1024, LAYER_PAGE_CMP = 64;
+struct LayerPageTable {
+    const int32_t *table;  // device [B, max_pages] int32
+    int64_t stride;        // elements between its rows
+    int n_pages, max_pages;
+};
+// cache[]: the six token pools; S_max: the capacity max_pages * 1024; t_pos: the verdicts t_live of the pre-pass; t0 = 0
+struct RopePagedParams : RopeAppendParams {
+    LayerPageTable pg;
+};
+// K_raw / V_raw / K_cmp / V_cmp: the pools; S_max: the capacity; n_cmp_max = max_pages * 64; t_pos: t_live
+struct CmpPoolPagedParams : CmpPoolParams {
+    LayerPageTable pg;
+};
+// the pre-pass: one wave per sequence writes its verdict t_live[b] = t_pos[b] where the sequence is live -- 0 <= t_pos[b],
+// t_pos[b] + S - 1 <= te, every table entry j = 0 .. (t_pos[b] + S - 1) >> 10 inside [0, n_pages) -- and -1 otherwise
+struct PagedLiveParams {
+    const int32_t *t_pos;
+    int32_t *t_live;
+    LayerPageTable pg;
+    int B, S, te;
+};
 struct GateCombineParams {
     const void *Q, *O_cmp, *O_sel, *O_win;
     void *O_out;
@@ -97,6 +123,12 @@ int launch_cmp_pool(const CmpPoolParams &P, int dtype, hipStream_t st);
 // per-sequence positions (P.t_pos): nbg ceil(S / d) blocks of the wide form, launched whether or not a window completes (the host never
 // reads the positions); block (bg, k) takes token n_cmp(t_pos[b]) + k and leaves where its sequence does not emit it
 int launch_cmp_pool_ragged(const CmpPoolParams &P, int dtype, hipStream_t st);
+// the paged call's three launches of this file: the verdicts, the rows epilogue's PAGED instantiations (row (b, s) at pos = t_live[b] + s
+// goes to row pos & 1023 of page table[b][pos >> 10] of each token pool) and the wide pooling kernel's (window rows and the compressed
+// row each found through their own page)
+int launch_paged_live(const PagedLiveParams &P, hipStream_t st);
+int launch_qkv_rope_append_paged(const RopePagedParams &P, const LinearCall &c);
+int launch_cmp_pool_paged(const CmpPoolPagedParams &P, int dtype, hipStream_t st);
 int launch_rope_cache_append_bwd(const RopeAppendParams &P, int dtype, hipStream_t st);
 int launch_cmp_pool_bwd(const CmpPoolParams &P, const void *dKc, const void *dVc, void *dKr, void *dVr, int S, int n_cmp, int dtype,
                         hipStream_t st);

@@ -287,6 +287,9 @@ struct LayerDecode {
     // kernel takes its rows' positions from t_pos
     const int32_t *t_pos;
     int te;
+    // paged call (nsa_layer_decode_paged): the block table; kv then names the POOLS with one page as its extent (S_max = 1024, n_cmp_max = 64,
+    // so that CacheStrides gives the page strides), t_pos is the pre-pass's t_live and te = min(t_max, max_pages 1024 - 1)
+    const LayerPageTable *pg;
     int tokens() const { return t_pos ? te + 1 : t0 + S; }  // tokens the caches hold after the call (of the largest sequence)
 };
 constexpr int LAYER_ROWS_MAX_S = 16;
@@ -384,6 +387,12 @@ static int layer_decode_tail(const LayerDecode &D, const CacheStrides &C, Decode
         F.ns[2] = F.ns[0] = BP->w.nsplit;
         F.part[2] = BP->w.part;
         F.part[0] = BP->c.part;
+    } else if (D.pg) {  // the paged call: one paged launch each -- 1024-row pages of K_win / V_win, 64-row pages of K_cmp / V_cmp -- combined by the branch itself
+        const BandBranches b = band_branches(D, C, stream);
+        const BandPageTable pt{D.pg->table, D.pg->stride, D.pg->n_pages, 0};
+        if (int rc = band_attn_fwd_paged_impl(b.w, b.bw, pt, D.pg->max_pages, LAYER_PAGE_TOKENS, D.t_pos, D.te)) return rc;
+        if (int rc = band_attn_fwd_paged_impl(b.c, b.bc, pt, D.pg->max_pages, LAYER_PAGE_CMP, D.t_pos, D.te)) return rc;
+        F.ns[2] = F.ns[0] = 1;
     } else if (D.t_pos) {  // the ragged call: one ragged launch each, combined by the branch itself (O final)
         const BandBranches b = band_branches(D, C, stream);
         if (int rc = band_attn_fwd_ragged_impl(b.w, b.bw, D.t_pos, D.te)) return rc;
@@ -654,6 +663,147 @@ int nsa_layer_decode_ragged(const nsa_layer_desc *L, const nsa_kv_desc *kv, cons
     DecBandPair BP{};
     const bool dual = band_pair(D, C, L->Dv == 64 ? 1 : 0, BP);
     return layer_decode_tail(D, C, F, dual ? &BP : nullptr, false, gates_out, y, nullptr, stream);
+}
+
+// ------------------------------------------------------------------------------ paged layer decode: append, pool and attend through a block table
+// The pools under a nsa_kv_desc whose extent is ONE page (S_max = 1024, n_cmp_max = 64): CacheStrides then gives the page and group strides
+// of the pools, and every block that is filled from a nsa_kv_desc (the branches' calls, the selected branch's block) names the pools.
+static nsa_kv_desc page_extent_kv(const nsa_paged_kv_desc *p) {
+    nsa_kv_desc kv{};
+    kv.K_sel = p->K_sel; kv.V_sel = p->V_sel; kv.K_win = p->K_win; kv.V_win = p->V_win; kv.K_raw = p->K_raw; kv.V_raw = p->V_raw;
+    kv.K_cmp = p->K_cmp; kv.V_cmp = p->V_cmp;
+    kv.B = p->B; kv.S_max = LAYER_PAGE_TOKENS; kv.n_cmp_max = LAYER_PAGE_CMP;
+    return kv;
+}
+constexpr int LAYER_PAGED_MAX_PAGES = 1 << 20;  // (the paged operators' bound: the capacity max_pages * 1024 stays a positive int)
+// the workspace is the ragged call's for the longest context a live row can sit in -- the unsplit forms end at 64 chunks of 64 compressed
+// tokens, under 2^17 tokens -- plus the verdicts t_live [B]; it does not grow with max_pages
+static int paged_ws_tokens(int max_pages) { return (int)std::min<int64_t>((int64_t)max_pages * LAYER_PAGE_TOKENS, 1 << 17); }
+
+// What the call and its plan share, from the shape, the host bound and the switches alone (aligned pools assumed; neither the positions nor
+// the table are read on the host).  As layer_decode_ragged_route: NSA_OK with *launches = n, or *launches = 0 and *why = the limit (DECLINED:
+// there is no fallback), or an error status for bad arguments.
+static int layer_decode_paged_route(const char *who, const nsa_layer_desc *L, int B, int S, int max_pages, int t_max, int S_sel, int *launches,
+                                    const char **why) {
+    *launches = 0;
+    *why = nullptr;
+    if (int rc = check_layer(L, who)) return rc;
+    NSA_CHECK_ARG(S >= 1 && S <= LAYER_ROWS_MAX_S, "%s: 1 to %d tokens per sequence (got %d)", who, LAYER_ROWS_MAX_S, S);
+    NSA_CHECK_ARG(B >= 1, "%s: bad batch size %d", who, B);
+    NSA_CHECK_ARG(max_pages >= 1 && max_pages <= LAYER_PAGED_MAX_PAGES, "%s: max_pages = %d, must be in [1, 2^20]", who, max_pages);
+    NSA_CHECK_ARG(t_max >= 0, "%s: t_max (the host bound of t_pos[b] + S - 1) must not be negative", who);
+    const int cap = max_pages * LAYER_PAGE_TOKENS;
+    const int te = std::min(t_max, cap - 1);  // no live row sits beyond te
+    NSA_CHECK_ARG(S_sel >= 1 && (int64_t)S_sel * L->l_sel >= (int64_t)te + 1, "%s: block metadata (S_sel=%d) does not cover %d tokens", who, S_sel, te + 1);
+    if (!(L->dtype == NSA_DT_BF16 || L->dtype == NSA_DT_F16)) {
+        *why = "bf16 / f16 only (no kernel reads or writes pools of pages in fp32)";
+        return NSA_OK;
+    }
+    if (!(L->Dk == L->Dv && (L->Dk == 64 || L->Dk == 128) && L->l == 32 && L->d == 16 && L->l_sel == 64)) {
+        *why = "Dk = Dv in {64, 128} and the default block geometry only (l = 32, d = 16, l' = 64: pages of 1024 tokens and 64 compressed rows)";
+        return NSA_OK;
+    }
+    if (L->w < 1) {
+        *why = "the sliding window must hold at least one key (w >= 1)";
+        return NSA_OK;
+    }
+    nsa_paged_kv_desc pools{};  // stands in for aligned pools: the predicates below read the sizes and the pointers' alignment only
+    pools.K_sel = pools.V_sel = pools.K_win = pools.V_win = pools.K_raw = pools.V_raw = pools.K_cmp = pools.V_cmp = (void *)(uintptr_t)256;
+    pools.B = B;
+    const nsa_kv_desc kv = page_extent_kv(&pools);
+    const CacheStrides C(L, &kv);
+    SelDecodeCall sc = sel_decode_call(L, &kv, C, S, 0, ncmp_of(te + 1, L->l, L->d), S_sel);
+    sc.S_kv = cap;
+    if (!decode_paged_shape_plan(sc, te, nullptr, nullptr, why)) return NSA_OK;
+    *why = nullptr;
+    int ns = 1;
+    band_attn_workspace(B, S, L->G, L->h, L->Dk, L->Dv, L->dtype, &ns);
+    // the verdicts, projection + RoPE + append, pooling (always), the selected branch's one launch, the sliding and the compressed branch (each
+    // one paged launch, with its combine behind it in split form), finish (or gate + mix), output projection
+    *launches = 4 + 2 * (ns > 1 ? 2 : 1) + 2;
+    return NSA_OK;
+}
+
+size_t nsa_layer_decode_paged_workspace(const nsa_layer_desc *L, int B, int S, int max_pages) {
+    if (!L || !dtype_ok(L->dtype) || B < 1 || S < 1 || S > LAYER_ROWS_MAX_S || max_pages < 1 || max_pages > LAYER_PAGED_MAX_PAGES) return 0;
+    return decode_ws(L, B, paged_ws_tokens(max_pages), S).total + up256(sizeof(int32_t) * (size_t)B);
+}
+
+int nsa_layer_decode_paged_plan(const nsa_layer_desc *L, int B, int S, int max_pages, int t_max, int S_sel, int *launches, int *route) {
+    NSA_CHECK_ARG(launches && route, "layer_decode_paged_plan: null pointer");
+    *launches = 0;
+    *route = -1;
+    int n = 0;
+    const char *why = nullptr;
+    if (int rc = layer_decode_paged_route("layer_decode_paged_plan", L, B, S, max_pages, t_max, S_sel, &n, &why)) return rc;
+    if (why) return NSA_OK;  // declined
+    *launches = n;
+    *route = 1;
+    return NSA_OK;
+}
+
+int nsa_layer_decode_paged(const nsa_layer_desc *L, const nsa_paged_kv_desc *pkv, const void *x, void *y, const int32_t *t_pos, int t_max, int S,
+                           const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out, float *gates_out,
+                           void *workspace, size_t workspace_bytes, void *stream) {
+    const char *who = "layer_decode_paged";
+    if (int rc = check_layer(L, who)) return rc;
+    NSA_CHECK_ARG(pkv && pkv->K_sel && pkv->V_sel && pkv->K_win && pkv->V_win && pkv->K_raw && pkv->V_raw && pkv->K_cmp && pkv->V_cmp, "%s: null pool pointer", who);
+    NSA_CHECK_ARG(pkv->B >= 1 && pkv->n_pages >= 1, "%s: bad pool sizes (B = %d, n_pages = %d)", who, pkv->B, pkv->n_pages);
+    NSA_CHECK_ARG(x && y && L->W_qkv && L->W_out, "%s: null pointer", who);
+    NSA_CHECK_ARG(t_pos, "%s: null position array t_pos", who);
+    NSA_CHECK_ARG((uintptr_t)t_pos % 4 == 0, "%s: t_pos must be 4-byte aligned", who);
+    NSA_CHECK_ARG(pkv->block_table, "%s: null block table", who);
+    int n = 0;
+    const char *why = nullptr;
+    if (int rc = layer_decode_paged_route(who, L, pkv->B, S, pkv->max_pages, t_max, S_sel, &n, &why)) return rc;
+    NSA_CHECK_ARG((uintptr_t)pkv->block_table % 4 == 0 && pkv->table_stride >= pkv->max_pages,
+                  "%s: the block table must be 4-byte aligned with a row stride of at least max_pages = %d (got %lld)", who, pkv->max_pages,
+                  (long long)pkv->table_stride);
+    NSA_CHECK_ARG(!why, "%s: %s (B = %d, S = %d, D = %d, t_max = %d)", who, why, pkv->B, S, L->Dk, t_max);
+    NSA_CHECK_ARG(((uintptr_t)pkv->K_sel | (uintptr_t)pkv->V_sel | (uintptr_t)pkv->K_win | (uintptr_t)pkv->V_win | (uintptr_t)pkv->K_raw | (uintptr_t)pkv->V_raw |
+                   (uintptr_t)pkv->K_cmp | (uintptr_t)pkv->V_cmp) % 16 == 0,
+                  "%s: the eight pools must be 16-byte aligned", who);
+    const int B = pkv->B, cap = pkv->max_pages * LAYER_PAGE_TOKENS, te = std::min(t_max, cap - 1);
+    // the largest sequence the launches are planned for: te + 1 tokens after the call, n1 compressed ones (LayerDecode)
+    const int t0 = std::max(0, te + 1 - S), n1 = ncmp_of(te + 1, L->l, L->d);
+    const nsa_kv_desc kv = page_extent_kv(pkv);
+    const CacheStrides C(L, &kv);
+    const DecodeWs W = decode_ws(L, B, paged_ws_tokens(pkv->max_pages), S);
+    if (int rc = check_workspace(who, workspace, workspace_bytes, W.total + up256(sizeof(int32_t) * (size_t)B))) return rc;
+    unsigned char *ws = (unsigned char *)workspace;
+    int32_t *t_live = (int32_t *)(ws + W.total);
+    const LayerPageTable pg{pkv->block_table, pkv->table_stride, pkv->n_pages, pkv->max_pages};
+    // every launch behind the pre-pass takes t_live as its position array: one verdict per sequence for the writers and the readers
+    const LayerDecode D{L, &kv, W, ws, ws + W.q, ws + W.ocmp, ws + W.osel, ws + W.owin, ws + W.omix, S, t0, 0, n1, t_live, te, &pg};
+    hipStream_t st = (hipStream_t)stream;
+    // 0. the verdicts: t_live[b] = t_pos[b] where sequence b is live (positions, and every table entry it needs inside [0, n_pages)), else -1
+    if (int rc = launch_paged_live(PagedLiveParams{t_pos, t_live, pg, B, S, te}, st)) return rc;
+    // 1. fused QKV projection of the B S rows, row (b, s) rotated at pos = t_live[b] + s and appended to row pos & 1023 of page
+    // table[b][pos >> 10] of the six token pools where sequence b is live
+    RopePagedParams R{};
+    static_cast<RopeAppendParams &>(R) = rope_append_params(L, &kv, ws + W.proj, D.Q, S, 0);
+    R.S_max = cap;
+    R.t_pos = t_live;
+    R.t_max = te;
+    R.pg = pg;
+    if (int rc = launch_qkv_rope_append_paged(R, qkv_call(L, x, B * S, nullptr, 0.f, stream))) return rc;
+    // 2. every live sequence's compressed tokens whose windows complete inside its rows, each window row and the compressed row through its page
+    CmpPoolPagedParams P{};
+    P.K_raw = pkv->K_raw; P.V_raw = pkv->V_raw; P.K_cmp = pkv->K_cmp; P.V_cmp = pkv->V_cmp;
+    P.nbg = B * L->G; P.S_max = cap; P.n_cmp_max = pkv->max_pages * LAYER_PAGE_CMP; P.Dk = L->Dk; P.Dv = L->Dv; P.l = L->l; P.d = L->d;
+    P.rope_base = L->rope_base > 0.f ? L->rope_base : 10000.0f;
+    P.inv_scale = 1.0f;  // as nsa_cmp_pool_append: no position scaling inside the pooled keys
+    P.t_pos = t_live; P.t_max = te; P.S = S; P.G = L->G;
+    P.pg = pg;
+    if (int rc = launch_cmp_pool_paged(P, L->dtype, st)) return rc;
+    // 3. selected branch: the paged rows form (one launch; zero O and ranges rows for a sequence that is not live)
+    SelDecodeCall c = layer_sel_call(D, C, csc_ptr, csc_rows, csc_vals, S_sel, ranges_out);
+    c.t0 = 0;  // as nsa_sel_decode_paged hands it over: every row's token comes from the position array
+    if (int rc = sel_decode_paged_impl(c, DecPageTable{pg.table, pg.stride, pg.n_pages}, pg.max_pages, LAYER_PAGE_TOKENS, t_live, te, stream)) return rc;
+    // 4. the sliding and the compressed branch, one paged launch each with its own combine, 5. finish (or the gate kernel), 6. output projection
+    DecodeFinishParams F = decode_finish_params(D, gates_out);
+    F.ns[1] = 1;
+    return layer_decode_tail(D, C, F, nullptr, false, gates_out, y, nullptr, stream);
 }
 
 // block workspace: xn | h | hn | u [B, mlp_hidden] | layer decode workspace

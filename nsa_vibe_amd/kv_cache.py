@@ -239,3 +239,127 @@ class NSA_KV:
             d.K_raw, d.V_raw, d.K_cmp, d.V_cmp = self._K_raw.data_ptr(), self._V_raw.data_ptr(), self._K_cmp.data_ptr(), self._V_cmp.data_ptr()
             d.B, d.S_max, d.n_cmp_max = self.B, self._K_sel.shape[2], self._K_cmp.shape[2]
         return d
+
+
+PAGE_TOKENS, PAGE_CMP = 1024, 64  # a page: 1024 tokens of the six token caches, 64 rows of K_cmp / V_cmp (d = 16)
+_POOLS = ("_K_sel", "_V_sel", "_K_win", "_V_win", "_K_raw", "_V_raw", "_K_cmp", "_V_cmp")
+
+
+class NSA_PagedKV:
+    """The eight caches of NSA_KV as POOLS of pages behind a block table (include/nsa_sel_hip.h: nsa_paged_kv_desc): six token pools
+    [n_pages, G, 1024, D], K_cmp / V_cmp [n_pages, G, 64, D], a device int32 block_table [B, max_pages] (-1 = no page) and a host free
+    list.  One page id serves all eight pools: entry [b, j] holds tokens [1024 j, 1024 j + 1024) and compressed rows [64 j, 64 j + 64) of
+    the sequence in slot b.  What NSAAttention.decode_paged (nsa_layer_decode_paged) appends to and reads; the lengths of the sequences
+    belong to the caller.  The page a sequence appends to must be its own (ensure() hands out a page once); nothing here shares pages.
+    The default block geometry only (l = 32, d = 16, l_sel = 64): the page sizes follow from it."""
+
+    def __init__(self, n_pages: int, B: int, max_pages: int, G: int, d_k: int, d_v: int, l: int, d: int, l_sel: int, n_sel: int, w: int,
+                 device, dtype):
+        if (l, d, l_sel) != (32, 16, 64):
+            raise ValueError(f"NSA_PagedKV: pages of {PAGE_TOKENS} tokens / {PAGE_CMP} compressed rows need the default block geometry "
+                             f"(l = 32, d = 16, l_sel = 64), got ({l}, {d}, {l_sel})")
+        if n_pages < 1 or B < 1 or max_pages < 1:
+            raise ValueError(f"NSA_PagedKV: n_pages = {n_pages}, B = {B}, max_pages = {max_pages} must all be positive")
+        self.n_pages, self.B, self.max_pages, self.G, self.d_k, self.d_v = n_pages, B, max_pages, G, d_k, d_v
+        self.l, self.d, self.l_sel, self.n_sel, self.w = l, d, l_sel, n_sel, w
+        mk = lambda rows, dim: torch.empty((n_pages, G, rows, dim), device=device, dtype=dtype)  # noqa: E731
+        self._K_sel, self._V_sel = mk(PAGE_TOKENS, d_k), mk(PAGE_TOKENS, d_v)
+        self._K_win, self._V_win = mk(PAGE_TOKENS, d_k), mk(PAGE_TOKENS, d_v)
+        self._K_raw, self._V_raw = mk(PAGE_TOKENS, d_k), mk(PAGE_TOKENS, d_v)
+        self._K_cmp, self._V_cmp = mk(PAGE_CMP, d_k), mk(PAGE_CMP, d_v)
+        self.block_table = torch.full((B, max_pages), -1, dtype=torch.int32, device=device)
+        self.pages: List[List[int]] = [[] for _ in range(B)]  # host mirror of the table rows
+        self._free: List[int] = list(range(n_pages - 1, -1, -1))  # (a stack: page 0 goes out first)
+        self.meta: BlockMeta = build_block_meta(0, l, d, l_sel, n_sel, w)
+        self.meta_seq_len = 0
+        self._native: dict = {}
+
+    # the block metadata is NSA_KV's (immutable, shared through the process-wide cache)
+    ensure_meta = NSA_KV.ensure_meta
+    refresh_meta = NSA_KV.refresh_meta
+
+    @property
+    def capacity(self) -> int:
+        """tokens a sequence can hold: what stands for S_max"""
+        return self.max_pages * PAGE_TOKENS
+
+    @property
+    def free_pages(self) -> int:
+        return len(self._free)
+
+    def _slot(self, b: int) -> int:
+        b = int(b)
+        if not 0 <= b < self.B:
+            raise IndexError(f"NSA_PagedKV: slot {b} outside [0, {self.B})")
+        return b
+
+    def ensure(self, b: int, n_tokens: int) -> None:
+        """pages for slot b until they cover n_tokens (idempotent: pages it holds stay where they are); raises when n_tokens exceed the
+        capacity or the pool is exhausted -- then nothing is assigned"""
+        b, n_tokens = self._slot(b), int(n_tokens)
+        need = (n_tokens + PAGE_TOKENS - 1) // PAGE_TOKENS
+        if n_tokens < 0 or need > self.max_pages:
+            raise RuntimeError(f"NSA_PagedKV.ensure: {n_tokens} tokens outside the capacity {self.capacity} of a slot (max_pages = {self.max_pages})")
+        have = len(self.pages[b])
+        if need <= have:
+            return
+        if need - have > len(self._free):
+            raise RuntimeError(f"NSA_PagedKV.ensure: pool exhausted -- slot {b} needs {need - have} more pages, {len(self._free)} of {self.n_pages} are free")
+        new = [self._free.pop() for _ in range(need - have)]
+        self.pages[b].extend(new)
+        self.block_table[b, have:need] = torch.tensor(new, dtype=torch.int32).to(self.block_table.device)
+
+    def free(self, b: int) -> None:
+        """slot b's pages back to the free list, its table entries back to -1"""
+        b = self._slot(b)
+        self._free.extend(reversed(self.pages[b]))
+        self.pages[b] = []
+        self.block_table[b].fill_(-1)
+
+    def load_sequence(self, b: int, kv1: "NSA_KV", t: int) -> None:
+        """the first t tokens and n_cmp(t) compressed rows of a B = 1 NSA_KV into slot b's pages (assigned here as needed): how a
+        prefilled sequence enters the pool.  Torch indexing, not a hot path."""
+        b, t = self._slot(b), int(t)
+        if kv1.B != 1 or (kv1.G, kv1.d_k, kv1.d_v) != (self.G, self.d_k, self.d_v) or kv1._K_sel.dtype != self._K_sel.dtype:
+            raise RuntimeError("NSA_PagedKV.load_sequence: a B = 1 NSA_KV of the pool's geometry and dtype is needed")
+        if not 0 <= t <= kv1._K_sel.shape[2]:
+            raise ValueError(f"NSA_PagedKV.load_sequence: t = {t} outside [0, {kv1._K_sel.shape[2]}]")
+        self.ensure(b, t)
+        n_cmp = n_cmp_at(t, self.l, self.d)
+        for name in _POOLS:
+            rows, n = (PAGE_CMP, n_cmp) if name in ("_K_cmp", "_V_cmp") else (PAGE_TOKENS, t)
+            pool, src = getattr(self, name), getattr(kv1, name)
+            for j in range((n + rows - 1) // rows):
+                k = min(rows, n - j * rows)
+                pool[self.pages[b][j], :, :k] = src[0, :, j * rows:j * rows + k]
+
+    def gather_sequence(self, b: int, t: int) -> "NSA_KV":
+        """the reverse: a B = 1 NSA_KV (capacity: the slot's assigned pages, at least one) holding the first t tokens and n_cmp(t)
+        compressed rows of slot b.  Rows beyond them are zero."""
+        b, t = self._slot(b), int(t)
+        if not 0 <= t <= len(self.pages[b]) * PAGE_TOKENS:
+            raise ValueError(f"NSA_PagedKV.gather_sequence: t = {t} outside the {len(self.pages[b])} pages of slot {b}")
+        cap = max(1, len(self.pages[b])) * PAGE_TOKENS
+        kv1 = NSA_KV(1, self.G, self.d_k, self.d_v, cap, self.l, self.d, self.l_sel, self.n_sel, self.w, self._K_sel.device, self._K_sel.dtype,
+                     auto_grow=False)
+        n_cmp = n_cmp_at(t, self.l, self.d)
+        for name in _POOLS:
+            rows, n = (PAGE_CMP, n_cmp) if name in ("_K_cmp", "_V_cmp") else (PAGE_TOKENS, t)
+            pool, dst = getattr(self, name), getattr(kv1, name)
+            dst.zero_()
+            for j in range((n + rows - 1) // rows):
+                k = min(rows, n - j * rows)
+                dst[0, :, j * rows:j * rows + k] = pool[self.pages[b][j], :, :k]
+        kv1.t, kv1.n_cmp = t, n_cmp
+        return kv1
+
+    def native_desc(self):
+        """struct nsa_paged_kv_desc of the pools and the table (include/nsa_sel_hip.h), built once"""
+        d = self._native.get("desc")
+        if d is None:
+            d = self._native["desc"] = _lib.NsaPagedKvDesc()
+            for name in _POOLS:
+                setattr(d, name[1:], getattr(self, name).data_ptr())
+            d.block_table, d.table_stride = self.block_table.data_ptr(), self.block_table.stride(0)
+            d.n_pages, d.B, d.max_pages = self.n_pages, self.B, self.max_pages
+        return d

@@ -34,7 +34,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from .band_attention import batched_causal_attention_compressed, sliding_window_attention
-from .kv_cache import NSA_KV
+from .kv_cache import NSA_KV, NSA_PagedKV
 from .selection_attention import (
     select_and_attend,
     selection_attention_first_key_parity,
@@ -796,6 +796,63 @@ class NSAAttention(nn.Module):
                                   (x.data_ptr(), y.data_ptr(), t_pos.data_ptr(), t_max, S), (), (B, S, G, self.n_sel, 2), (B, S, G, 3))
         self._monitors(ranges, gates)
         return y, kv
+
+    # ---- ragged batch over PAGED caches: the eight caches in pools of pages behind a device block table ------------------------------------
+    def new_paged_kv(self, n_pages: int, B: int, max_pages: int, device, dtype) -> NSA_PagedKV:
+        """pools of n_pages pages for B slots of up to max_pages pages (max_pages * 1024 tokens) each"""
+        return NSA_PagedKV(n_pages, B, max_pages, self.n_kv_groups, self.d_k, self.d_v, self.l, self.d, self.l_sel, self.n_sel, self.w, device, dtype)
+
+    def decode_paged_plan(self, B: int, S: int, max_pages: int, t_max: int, S_sel: int) -> dict:
+        """what nsa_layer_decode_paged does with a shape under the current tuning switches (nsa_layer_decode_paged_plan, no device call):
+        {"launches", "route": 1 the one native call / -1 declined (there is no other route over pages)}"""
+        desc, _ = self._layer_desc()
+        n, r = _plan_ints("nsa_layer_decode_paged_plan", 2, ctypes.byref(desc), int(B), int(S), int(max_pages), int(t_max), int(S_sel))
+        return {"launches": n, "route": r}
+
+    def decode_paged(self, x: torch.Tensor, pkv: NSA_PagedKV, t_pos, *, t_max: int):
+        """decode_ragged over a paged cache: x [B,S,dim], 1 <= S <= 16, row (b, s) the token at position t_pos[b] + s of the sequence in slot
+        b of `pkv`, whose pages already hold t_pos[b] tokens -> (y [B,S,dim], pkv), in ONE native call (nsa_layer_decode_paged) whose
+        arguments do not change from token to token.  The call appends the S tokens to the slot's pages, pools the compressed tokens that
+        complete, and attends through the block table; the pages that positions t_pos[b] .. t_pos[b] + S - 1 fall into must be assigned
+        beforehand (pkv.ensure) and belong to the slot alone.
+        t_pos: a device int32 tensor [B]; the host never reads it or the table, so t_max -- the host bound of t_pos[b] + S - 1 -- is required.
+        Lengths belong to the caller.  A slot with t_pos[b] < 0, t_pos[b] + S - 1 > min(t_max, capacity - 1) or a needed table entry
+        outside [0, n_pages) is inactive: nothing is written to any page, its y and ranges rows are zero.
+        Monitors: _last_ranges [B,S,G,n,2], _last_gates [B,S,G,3] (gates of an inactive slot: unspecified).  Inference only.  There is no
+        other route over pages: parity mode, or a module, input or shape the native call declines, raises -- the latter with the library's message."""
+        assert x.dim() == 3, "x must be [B,S,dim]"
+        B, S, _ = x.shape
+        if not 1 <= S <= 16:
+            raise ValueError(f"NSAAttention.decode_paged takes 1 to 16 tokens per sequence, got S={S}")
+        if not isinstance(t_pos, torch.Tensor) or t_pos.dtype != torch.int32 or tuple(t_pos.shape) != (B,):
+            raise ValueError(f"NSAAttention.decode_paged: t_pos must be a device int32 tensor [{B}]")
+        t_max = int(t_max)
+        if t_max < 0:
+            raise ValueError(f"NSAAttention.decode_paged: t_max = {t_max} is negative")
+        if not x.is_cuda or t_pos.device != x.device or pkv.block_table.device != x.device:
+            raise RuntimeError("NSAAttention.decode_paged needs HIP device tensors on one device (no CPU fallback exists)")
+        buf = pkv._K_sel
+        if B != pkv.B or buf.dtype != x.dtype or buf.device != x.device or (pkv.G, pkv.d_k, pkv.d_v) != (self.n_kv_groups, self.d_k, self.d_v):
+            raise RuntimeError(f"NSA_PagedKV does not match the input or the module: pools B={pkv.B} {buf.dtype} on {buf.device} (G={pkv.G}, d_k={pkv.d_k}, "
+                               f"d_v={pkv.d_v}), x B={B} {x.dtype} on {x.device}")
+        if self._grad_needed(x):
+            raise RuntimeError("NSAAttention.decode_paged is inference only (no backward); run it under torch.no_grad()")
+        if not self._native_ok(x):
+            raise RuntimeError("NSAAttention.decode_paged: the native call does not take this module or input (parity mode, dtype, gate width), and "
+                               "there is no other route over pages")
+        if not x.is_contiguous():
+            x = x.contiguous()
+        if not t_pos.is_contiguous():
+            t_pos = t_pos.contiguous()
+        pkv.refresh_meta(min(t_max, pkv.capacity - 1) + 1)
+        G = self.n_kv_groups
+        desc, _ = self._layer_desc()
+        y = torch.empty((B, S, self.dim), dtype=x.dtype, device=x.device)
+        # (a declined shape comes back from the call itself, before its first launch, with the limit named)
+        ranges, gates = _one_call("nsa_layer_decode_paged", "layer_decode_paged", desc, pkv, pkv.meta, x.device, (B, S, pkv.max_pages),
+                                  (x.data_ptr(), y.data_ptr(), t_pos.data_ptr(), t_max, S), (), (B, S, G, self.n_sel, 2), (B, S, G, 3))
+        self._monitors(ranges, gates)
+        return y, pkv
 
     def _decode_ragged_sequences(self, x: torch.Tensor, kv: NSA_KV, host, t_max: int):
         """the per-sequence route of decode_ragged: one decode_rows per live sequence on its slab, zeros for the padding slots"""
