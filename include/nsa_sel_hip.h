@@ -346,8 +346,13 @@ NSA_API int nsa_layer_decode_ragged_plan(const nsa_layer_desc *L, int B, int S, 
  *                 [1024 j, 1024 j + 1024) and compressed rows [64 j, 64 j + 64) of sequence b.  The capacity that stands for S_max is
  *                 max_pages * 1024 (max_pages <= 2^20).  Page bases are formed in 64 bits, so a pool may exceed 2 GiB.
  *                 OWNERSHIP: the page a live sequence appends to -- the page(s) of positions t_pos[b] .. t_pos[b] + S - 1 and of the
- *                 compressed rows emitted there -- must belong to that sequence ALONE; pages that are only read may be shared between
- *                 sequences (a common prefix).  Nothing checks this: two sequences appending to one page overwrite each other.
+ *                 compressed rows emitted there -- must belong to that sequence ALONE.  A page may be shared between sequences (a common
+ *                 prefix) only once it is CLOSED: page j of a sequence of t tokens is closed when t >= 1024 (j + 1) + 16, equivalently
+ *                 n_cmp(t) >= 64 (j + 1).  Until then its last compressed row, 64 j + 63 -- pooled from raw rows 1024 j + 1008 ..
+ *                 1024 j + 1039 -- is still to be written, so two sequences that share the page and diverge at a position in
+ *                 [1024 (j + 1), 1024 (j + 1) + 16) would both write it.  The kernels check none of this: two sequences appending to one
+ *                 page overwrite each other.  The allocator does: NSA_PagedKV.fork / own_tail / truncate (nsa_vibe_amd/kv_cache.py) share
+ *                 closed pages only, by reference count, and give a sequence private copies of the others (nsa_paged_kv_copy_pages).
  *   x, y, t_pos, t_max, S, csc_*, S_sel, ranges_out, gates_out   as in nsa_layer_decode_ragged; te = min(t_max, max_pages * 1024 - 1).  The
  *                 host reads neither t_pos nor the table, and the arguments do not change from token to token.
  * One verdict per sequence: the call's first launch, one wave per sequence, writes t_live[b] into the workspace -- t_pos[b] where the
@@ -387,6 +392,33 @@ NSA_API int nsa_layer_decode_paged(const nsa_layer_desc *L, const nsa_paged_kv_d
                            void *workspace, size_t workspace_bytes, void *stream);
 NSA_API int nsa_layer_decode_paged_plan(const nsa_layer_desc *L, int B, int S, int max_pages, int t_max, int S_sel, int *launches /* host */,
                                 int *route /* host */);
+
+/* Copies between a contiguous cache and the pages of a paged one, and between pages: how a prefilled sequence ENTERS the pools (admission),
+ * leaves them, and how a sequence gets a private copy of a page it shares.  Plain streaming copies, ONE launch per call, 16-byte loads and
+ * stores.  G, Dk, Dv, dtype: the geometry of the pools and the cache (the descriptors hold pointers and extents only); bf16 / f16,
+ * Dk and Dv in {64, 128}.  Every address is formed in 64 bits: pools and caches may exceed 2 GiB.
+ *   nsa_paged_kv_store   token rows [t0, t1) of the six token tensors of slab b_src of `kv` ([B, G, S_max, D], contiguous) go to the pages of table
+ *                  row `slot`: row r to row r & 1023 of page table[slot][r >> 10].  The same launch copies compressed rows
+ *                  [n_cmp(t0), n_cmp(t1)) of K_cmp / V_cmp ([B, G, n_cmp_max, D]): row c to row c & 63 of page table[slot][c >> 6]
+ *                  (n_cmp(t) = 0 below t = 32, else (t - 32) / 16 + 1: the default block geometry).
+ *   nsa_paged_kv_load    the same arguments, the other way: pages -> slab.
+ *   nsa_paged_kv_copy_pages   jobs: DEVICE int32 [n_jobs, 4] of (src_page, dst_page, n_tokens, n_cmp_rows).  For every job, token rows
+ *                  [0, n_tokens) of the six token pools and compressed rows [0, n_cmp_rows) of the two compressed pools go from page src
+ *                  to page dst.  The jobs of one launch must not write a page that another of them reads or writes.
+ * The host reads neither the table nor the jobs.  A kernel forms an address only from a page id it has itself tested against [0, n_pages):
+ * the rows of a table entry outside that range are SKIPPED (nothing is read or written for them), and so is a whole job with a page id
+ * outside it, n_tokens outside [0, 1024] or n_cmp_rows outside [0, 64].  Nothing is clamped silently; no table or job value can send a load
+ * or a store outside the pools or the slab; rows outside the ranges, and every other page, are left untouched.
+ * NSA_ERR_INVALID with a message naming the limit, and no launch, for: a null pointer; a pool, cache or table that is misaligned (16 / 16 /
+ * 4 bytes; the job array 4); a table stride below max_pages; t0 < 0, t1 < t0; t1 beyond kv->S_max or max_pages * 1024; n_cmp(t1) beyond
+ * kv->n_cmp_max; a dtype other than bf16 / f16; Dk or Dv outside {64, 128}; slot outside [0, pkv->B); b_src outside [0, kv->B); G < 1;
+ * n_pages < 1; max_pages outside [1, 2^20]; n_jobs < 0.  t0 == t1 and n_jobs == 0: NSA_OK, no launch. */
+NSA_API int nsa_paged_kv_store(const nsa_paged_kv_desc *pkv, const nsa_kv_desc *kv, int b_src, int slot, int t0, int t1, int G, int Dk, int Dv,
+                       int dtype, void *stream);
+NSA_API int nsa_paged_kv_load(const nsa_paged_kv_desc *pkv, const nsa_kv_desc *kv, int b_src, int slot, int t0, int t1, int G, int Dk, int Dv,
+                      int dtype, void *stream);
+NSA_API int nsa_paged_kv_copy_pages(const nsa_paged_kv_desc *pkv, const int32_t *jobs /* device [n_jobs, 4] */, int n_jobs, int G, int Dk, int Dv,
+                            int dtype, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * Eq.9 map in gather (CSC) form.  For selection block j the entries csc_ptr[j]..csc_ptr[j+1]

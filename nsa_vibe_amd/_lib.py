@@ -90,6 +90,9 @@ SIGNATURES = {
     "nsa_layer_decode_paged_workspace": (_sz, [_pl, _i, _i, _i]),
     "nsa_layer_decode_paged": (_i, [_pl, _pp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "nsa_layer_decode_paged_plan": (_i, [_pl, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "nsa_paged_kv_store": (_i, [_pp, _pk] + [_i] * 8 + [_vp]),
+    "nsa_paged_kv_load": (_i, [_pp, _pk] + [_i] * 8 + [_vp]),
+    "nsa_paged_kv_copy_pages": (_i, [_pp, _vp] + [_i] * 5 + [_vp]),
     "nsa_band_attn_bwd_workspace": (_sz, [_i] * 9),
     "nsa_band_attn_bwd": (_i, [_vp] * 9 + [_i] * 7 + [_i64] * 6 + [_i] * 5 + [_i, _f, _i, _vp, _sz, _vp]),
     "nsa_block_counts": (_i, [_i] * 4 + [C.POINTER(_i)] * 3),

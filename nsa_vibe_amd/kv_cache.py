@@ -8,6 +8,7 @@ of these views through the C ABI, so nothing is ever re-packed.
 """
 from __future__ import annotations
 
+import ctypes
 from typing import List, Optional
 
 import torch
@@ -242,15 +243,22 @@ class NSA_KV:
 
 
 PAGE_TOKENS, PAGE_CMP = 1024, 64  # a page: 1024 tokens of the six token caches, 64 rows of K_cmp / V_cmp (d = 16)
+CLOSE_LAG = 16  # d: compressed row 64 j + 63, the last of page j, is pooled from raw rows up to 1024 (j + 1) + 15
 _POOLS = ("_K_sel", "_V_sel", "_K_win", "_V_win", "_K_raw", "_V_raw", "_K_cmp", "_V_cmp")
 
 
 class NSA_PagedKV:
     """The eight caches of NSA_KV as POOLS of pages behind a block table (include/nsa_sel_hip.h: nsa_paged_kv_desc): six token pools
-    [n_pages, G, 1024, D], K_cmp / V_cmp [n_pages, G, 64, D], a device int32 block_table [B, max_pages] (-1 = no page) and a host free
-    list.  One page id serves all eight pools: entry [b, j] holds tokens [1024 j, 1024 j + 1024) and compressed rows [64 j, 64 j + 64) of
-    the sequence in slot b.  What NSAAttention.decode_paged (nsa_layer_decode_paged) appends to and reads; the lengths of the sequences
-    belong to the caller.  The page a sequence appends to must be its own (ensure() hands out a page once); nothing here shares pages.
+    [n_pages, G, 1024, D], K_cmp / V_cmp [n_pages, G, 64, D], a device int32 block_table [B, max_pages] (-1 = no page), a host free
+    list and one reference count per page.  One page id serves all eight pools: entry [b, j] holds tokens [1024 j, 1024 j + 1024) and
+    compressed rows [64 j, 64 j + 64) of the sequence in slot b.  What NSAAttention.decode_paged (nsa_layer_decode_paged) appends to and
+    reads; the lengths of the sequences belong to the caller.
+    Sharing.  ensure() hands a page to one slot (count 1).  fork() lets a second slot name the pages of a common prefix, but only the
+    CLOSED ones: page j of a sequence of t tokens is closed once t >= 1024 (j + 1) + 16, i.e. n_cmp(t) >= 64 (j + 1) -- until then its
+    compressed row 64 j + 63 (pooled from raw rows 1024 j + 1008 .. 1024 j + 1039) is still to be written, and two sequences that diverge
+    inside [1024 (j + 1), 1024 (j + 1) + 16) would both write it.  Every page an append can still write is private to its slot:
+    own_tail() replaces a shared one by a copy (one nsa_paged_kv_copy_pages launch; torch indexing on CPU tensors), fork(), truncate() and
+    load_sequence() call it.  free() returns a page to the free list when its count reaches zero.
     The default block geometry only (l = 32, d = 16, l_sel = 64): the page sizes follow from it."""
 
     def __init__(self, n_pages: int, B: int, max_pages: int, G: int, d_k: int, d_v: int, l: int, d: int, l_sel: int, n_sel: int, w: int,
@@ -270,6 +278,7 @@ class NSA_PagedKV:
         self.block_table = torch.full((B, max_pages), -1, dtype=torch.int32, device=device)
         self.pages: List[List[int]] = [[] for _ in range(B)]  # host mirror of the table rows
         self._free: List[int] = list(range(n_pages - 1, -1, -1))  # (a stack: page 0 goes out first)
+        self._refs: List[int] = [0] * n_pages  # table entries that name the page; 0: on the free list
         self.meta: BlockMeta = build_block_meta(0, l, d, l_sel, n_sel, w)
         self.meta_seq_len = 0
         self._native: dict = {}
@@ -293,6 +302,24 @@ class NSA_PagedKV:
             raise IndexError(f"NSA_PagedKV: slot {b} outside [0, {self.B})")
         return b
 
+    def page_refs(self, b: int) -> List[int]:
+        """the reference counts of slot b's pages, in table order (1: the slot's own)"""
+        return [self._refs[p] for p in self.pages[self._slot(b)]]
+
+    def shared_pages(self, b: int) -> List[int]:
+        """the pages of slot b that another table entry names too (count > 1): read-only for every holder"""
+        return [p for p in self.pages[self._slot(b)] if self._refs[p] > 1]
+
+    def _set_entries(self, b: int, j0: int, ids: List[int]) -> None:
+        self.block_table[b, j0:j0 + len(ids)] = torch.tensor(ids, dtype=torch.int32).to(self.block_table.device)
+
+    def _release(self, ids) -> None:
+        """one reference less on each page, in this order; a page whose count reaches zero goes back to the free list"""
+        for p in ids:
+            self._refs[p] -= 1
+            if self._refs[p] == 0:
+                self._free.append(p)
+
     def ensure(self, b: int, n_tokens: int) -> None:
         """pages for slot b until they cover n_tokens (idempotent: pages it holds stay where they are); raises when n_tokens exceed the
         capacity or the pool is exhausted -- then nothing is assigned"""
@@ -306,51 +333,192 @@ class NSA_PagedKV:
         if need - have > len(self._free):
             raise RuntimeError(f"NSA_PagedKV.ensure: pool exhausted -- slot {b} needs {need - have} more pages, {len(self._free)} of {self.n_pages} are free")
         new = [self._free.pop() for _ in range(need - have)]
+        for p in new:
+            self._refs[p] = 1
         self.pages[b].extend(new)
-        self.block_table[b, have:need] = torch.tensor(new, dtype=torch.int32).to(self.block_table.device)
+        self._set_entries(b, have, new)
 
     def free(self, b: int) -> None:
-        """slot b's pages back to the free list, its table entries back to -1"""
+        """slot b gives up its pages (each back to the free list once no other slot names it), its table entries go back to -1"""
         b = self._slot(b)
-        self._free.extend(reversed(self.pages[b]))
+        self._release(reversed(self.pages[b]))
         self.pages[b] = []
         self.block_table[b].fill_(-1)
 
-    def load_sequence(self, b: int, kv1: "NSA_KV", t: int) -> None:
-        """the first t tokens and n_cmp(t) compressed rows of a B = 1 NSA_KV into slot b's pages (assigned here as needed): how a
-        prefilled sequence enters the pool.  Torch indexing, not a hot path."""
-        b, t = self._slot(b), int(t)
-        if kv1.B != 1 or (kv1.G, kv1.d_k, kv1.d_v) != (self.G, self.d_k, self.d_v) or kv1._K_sel.dtype != self._K_sel.dtype:
-            raise RuntimeError("NSA_PagedKV.load_sequence: a B = 1 NSA_KV of the pool's geometry and dtype is needed")
-        if not 0 <= t <= kv1._K_sel.shape[2]:
-            raise ValueError(f"NSA_PagedKV.load_sequence: t = {t} outside [0, {kv1._K_sel.shape[2]}]")
-        self.ensure(b, t)
-        n_cmp = n_cmp_at(t, self.l, self.d)
-        for name in _POOLS:
-            rows, n = (PAGE_CMP, n_cmp) if name in ("_K_cmp", "_V_cmp") else (PAGE_TOKENS, t)
-            pool, src = getattr(self, name), getattr(kv1, name)
-            for j in range((n + rows - 1) // rows):
-                k = min(rows, n - j * rows)
-                pool[self.pages[b][j], :, :k] = src[0, :, j * rows:j * rows + k]
+    # ---- sharing: closed pages by reference, every other page private ----------------------------------------------------------------------
+    @staticmethod
+    def page_closed(j: int, t: int) -> bool:
+        """whether page j of a sequence of t tokens is closed: no append at a position >= t writes it (its 64 compressed rows are emitted)"""
+        return t >= PAGE_TOKENS * (j + 1) + CLOSE_LAG
 
-    def gather_sequence(self, b: int, t: int) -> "NSA_KV":
-        """the reverse: a B = 1 NSA_KV (capacity: the slot's assigned pages, at least one) holding the first t tokens and n_cmp(t)
-        compressed rows of slot b.  Rows beyond them are zero."""
+    def _open_pages(self, b: int, t: int) -> List[int]:
+        """the table positions j <= t >> 10 of slot b's pages that are not closed at t: the last one, and the one before it while
+        t & 1023 < 16 (t >= 1024)"""
+        return [j for j in range(max(0, (t >> 10) - 1), min(len(self.pages[b]), (t >> 10) + 1)) if not self.page_closed(j, t)]
+
+    def _copy_pages(self, jobs: List[tuple]) -> None:
+        """jobs of (src page, dst page, token rows, compressed rows), all in one nsa_paged_kv_copy_pages launch (torch indexing on CPU)"""
+        jobs = [jb for jb in jobs if jb[2] > 0 or jb[3] > 0]
+        if not jobs:
+            return
+        dev = self._K_sel.device
+        if dev.type == "cuda":
+            from ._native import _stream
+
+            with torch.cuda.device(dev):
+                dj = torch.tensor(jobs, dtype=torch.int32).to(dev)
+                _lib.check(_lib.lib().nsa_paged_kv_copy_pages(ctypes.byref(self.native_desc()), dj.data_ptr(), len(jobs), self.G, self.d_k, self.d_v,
+                                                              self._dtype_code(), _stream(dev)), "nsa_paged_kv_copy_pages")
+            return
+        for src, dst, n_tok, n_cmp in jobs:
+            for name in _POOLS:
+                k = n_cmp if name in ("_K_cmp", "_V_cmp") else n_tok
+                if k:
+                    pool = getattr(self, name)
+                    pool[dst, :, :k] = pool[src, :, :k]
+
+    def _dtype_code(self) -> int:
+        from ._native import _DT
+
+        code = _DT.get(self._K_sel.dtype)
+        if code is None:
+            raise RuntimeError(f"NSA_PagedKV: the native page copies take bf16 / f16 pools, not {self._K_sel.dtype}")
+        return code
+
+    def own_tail(self, b: int, t: int) -> None:
+        """every page of slot b that an append at a position >= t can write becomes the slot's own: a page j <= t >> 10 that is not closed
+        at t and has count > 1 is replaced by a fresh page holding its token rows [0, min(1024, t - 1024 j)) and compressed rows
+        [0, min(64, n_cmp(t) - 64 j)) (at most two pages, one copy launch); the old page loses a reference.  Raises when the pool cannot
+        supply the pages -- then nothing changes."""
+        b, t = self._slot(b), int(t)
+        if t < 0:
+            raise ValueError(f"NSA_PagedKV.own_tail: t = {t} is negative")
+        todo = [j for j in self._open_pages(b, t) if self._refs[self.pages[b][j]] > 1]
+        if not todo:
+            return
+        if len(todo) > len(self._free):
+            raise RuntimeError(f"NSA_PagedKV.own_tail: pool exhausted -- slot {b} needs {len(todo)} private pages, {len(self._free)} of {self.n_pages} are free")
+        n_cmp, jobs = n_cmp_at(t, self.l, self.d), []
+        for j in todo:
+            old, new = self.pages[b][j], self._free.pop()
+            self._refs[new] = 1
+            self._refs[old] -= 1  # (stays >= 1: another entry names it)
+            self.pages[b][j] = new
+            self._set_entries(b, j, [new])
+            jobs.append((old, new, max(0, min(PAGE_TOKENS, t - PAGE_TOKENS * j)), max(0, min(PAGE_CMP, n_cmp - PAGE_CMP * j))))
+        self._copy_pages(jobs)
+
+    def fork(self, src: int, dst: int, t: int) -> None:
+        """slot dst (empty) becomes a sequence of the first t tokens of slot src, 0 <= t <= the tokens src's pages cover: the pages closed
+        at t are SHARED (the same table entry, one more reference), the others that hold one of the t tokens -- the last, and the one
+        before it while t & 1023 < 16 -- are private copies (own_tail).  src is not modified and may go on decoding on the pages it owns
+        alone (own_tail(src, .) first where its open pages are shared from an earlier fork).  Raises when the pool cannot supply the
+        private pages -- then nothing is assigned and no count changes."""
+        src, dst, t = self._slot(src), self._slot(dst), int(t)
+        if src == dst:
+            raise RuntimeError(f"NSA_PagedKV.fork: src and dst are both slot {src}")
+        if self.pages[dst]:
+            raise RuntimeError(f"NSA_PagedKV.fork: slot {dst} is not empty (free it first)")
+        if not 0 <= t <= len(self.pages[src]) * PAGE_TOKENS:
+            raise ValueError(f"NSA_PagedKV.fork: t = {t} outside the {len(self.pages[src])} pages of slot {src}")
+        need = (t + PAGE_TOKENS - 1) // PAGE_TOKENS
+        private = sum(1 for j in range(need) if not self.page_closed(j, t))
+        if private > len(self._free):
+            raise RuntimeError(f"NSA_PagedKV.fork: pool exhausted -- slot {dst} needs {private} private pages, {len(self._free)} of {self.n_pages} are free")
+        ids = self.pages[src][:need]
+        for p in ids:
+            self._refs[p] += 1
+        self.pages[dst] = list(ids)
+        if ids:
+            self._set_entries(dst, 0, ids)
+        self.own_tail(dst, t)
+
+    def truncate(self, b: int, t: int) -> None:
+        """the page bookkeeping of a rollback of slot b to t tokens (the length itself is the caller's): the pages above the one that holds
+        token t - 1 are released and their table entries set to -1, then own_tail(b, t) makes the next append's pages private.  t = 0 is
+        free(b).  Raises when own_tail cannot be supplied -- then nothing changes."""
         b, t = self._slot(b), int(t)
         if not 0 <= t <= len(self.pages[b]) * PAGE_TOKENS:
+            raise ValueError(f"NSA_PagedKV.truncate: t = {t} outside the {len(self.pages[b])} pages of slot {b}")
+        if t == 0:
+            return self.free(b)
+        keep = (t + PAGE_TOKENS - 1) // PAGE_TOKENS
+        gone = self.pages[b][keep:]
+        private = sum(1 for j in self._open_pages(b, t) if j < keep and self._refs[self.pages[b][j]] > 1)
+        if private > len(self._free) + sum(1 for p in gone if self._refs[p] == 1):
+            raise RuntimeError(f"NSA_PagedKV.truncate: pool exhausted -- slot {b} needs {private} private pages")
+        if gone:
+            self._release(reversed(gone))
+            del self.pages[b][keep:]
+            self.block_table[b, keep:].fill_(-1)
+        self.own_tail(b, t)
+
+    # ---- copies between a contiguous B = 1 cache and a slot's pages ------------------------------------------------------------------------
+    def _copy_rows(self, b: int, kv1: "NSA_KV", t0: int, t: int, to_pages: bool) -> None:
+        """token rows [t0, t) and compressed rows [n_cmp(t0), n_cmp(t)) between kv1 and slot b's pages: one nsa_paged_kv_store / _load
+        launch on HIP device tensors, torch indexing on CPU tensors"""
+        if t0 == t:
+            return
+        dev = self._K_sel.device
+        if dev.type == "cuda":
+            from ._native import _stream
+
+            fn = _lib.lib().nsa_paged_kv_store if to_pages else _lib.lib().nsa_paged_kv_load
+            with torch.cuda.device(dev):
+                _lib.check(fn(ctypes.byref(self.native_desc()), ctypes.byref(kv1.native_desc()), 0, b, t0, t, self.G, self.d_k, self.d_v, self._dtype_code(),
+                              _stream(dev)), "nsa_paged_kv_store" if to_pages else "nsa_paged_kv_load")
+            return
+        for name in _POOLS:
+            rows, lo, hi = (PAGE_CMP, n_cmp_at(t0, self.l, self.d), n_cmp_at(t, self.l, self.d)) if name in ("_K_cmp", "_V_cmp") else (PAGE_TOKENS, t0, t)
+            pool, slab = getattr(self, name), getattr(kv1, name)
+            for j in range(lo // rows, (hi + rows - 1) // rows):
+                r0, r1 = max(lo, j * rows), min(hi, (j + 1) * rows)
+                if r1 <= r0:
+                    continue
+                if to_pages:
+                    pool[self.pages[b][j], :, r0 - j * rows:r1 - j * rows] = slab[0, :, r0:r1]
+                else:
+                    slab[0, :, r0:r1] = pool[self.pages[b][j], :, r0 - j * rows:r1 - j * rows]
+
+    def _check_kv1(self, who: str, kv1: "NSA_KV") -> None:
+        if kv1.B != 1 or (kv1.G, kv1.d_k, kv1.d_v) != (self.G, self.d_k, self.d_v) or kv1._K_sel.dtype != self._K_sel.dtype:
+            raise RuntimeError(f"NSA_PagedKV.{who}: a B = 1 NSA_KV of the pool's geometry and dtype is needed")
+        if kv1._K_sel.device != self._K_sel.device:
+            raise RuntimeError(f"NSA_PagedKV.{who}: the NSA_KV is on {kv1._K_sel.device}, the pools on {self._K_sel.device}")
+
+    def load_sequence(self, b: int, kv1: "NSA_KV", t: int, t0: int = 0) -> None:
+        """token rows [t0, t) and compressed rows [n_cmp(t0), n_cmp(t)) of a B = 1 NSA_KV into slot b's pages (assigned here as needed; the
+        pages these rows fall into are made private first, own_tail(b, t0)): how a prefilled sequence, or the suffix a forked slot was
+        extended by, enters the pool.  One nsa_paged_kv_store launch on HIP device tensors, torch indexing on CPU tensors."""
+        b, t, t0 = self._slot(b), int(t), int(t0)
+        self._check_kv1("load_sequence", kv1)
+        if not 0 <= t <= kv1._K_sel.shape[2]:
+            raise ValueError(f"NSA_PagedKV.load_sequence: t = {t} outside [0, {kv1._K_sel.shape[2]}]")
+        if not 0 <= t0 <= t:
+            raise ValueError(f"NSA_PagedKV.load_sequence: t0 = {t0} outside [0, t = {t}]")
+        for j in range((t0 >> 10) + 1, len(self.pages[b])):  # (own_tail looks after the pages up to t0 >> 10)
+            if self._refs[self.pages[b][j]] > 1:
+                raise RuntimeError(f"NSA_PagedKV.load_sequence: page {j} of slot {b}, above row t0 = {t0}, is shared: truncate(b, t0) first")
+        self.own_tail(b, t0)
+        self.ensure(b, t)
+        self._copy_rows(b, kv1, t0, t, True)
+
+    def gather_sequence(self, b: int, t: int, t0: int = 0) -> "NSA_KV":
+        """the reverse: a B = 1 NSA_KV (capacity: the slot's assigned pages, at least one) of t tokens and n_cmp(t) compressed rows holding
+        token rows [t0, t) and compressed rows [n_cmp(t0), n_cmp(t)) of slot b.  Every other row is zero.  One nsa_paged_kv_load launch on
+        HIP device tensors, torch indexing on CPU tensors."""
+        b, t, t0 = self._slot(b), int(t), int(t0)
+        if not 0 <= t <= len(self.pages[b]) * PAGE_TOKENS:
             raise ValueError(f"NSA_PagedKV.gather_sequence: t = {t} outside the {len(self.pages[b])} pages of slot {b}")
+        if not 0 <= t0 <= t:
+            raise ValueError(f"NSA_PagedKV.gather_sequence: t0 = {t0} outside [0, t = {t}]")
         cap = max(1, len(self.pages[b])) * PAGE_TOKENS
         kv1 = NSA_KV(1, self.G, self.d_k, self.d_v, cap, self.l, self.d, self.l_sel, self.n_sel, self.w, self._K_sel.device, self._K_sel.dtype,
                      auto_grow=False)
-        n_cmp = n_cmp_at(t, self.l, self.d)
         for name in _POOLS:
-            rows, n = (PAGE_CMP, n_cmp) if name in ("_K_cmp", "_V_cmp") else (PAGE_TOKENS, t)
-            pool, dst = getattr(self, name), getattr(kv1, name)
-            dst.zero_()
-            for j in range((n + rows - 1) // rows):
-                k = min(rows, n - j * rows)
-                dst[0, :, j * rows:j * rows + k] = pool[self.pages[b][j], :, :k]
-        kv1.t, kv1.n_cmp = t, n_cmp
+            getattr(kv1, name).zero_()
+        self._copy_rows(b, kv1, t0, t, False)
+        kv1.t, kv1.n_cmp = t, n_cmp_at(t, self.l, self.d)
         return kv1
 
     def native_desc(self):

@@ -34,7 +34,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from .band_attention import batched_causal_attention_compressed, sliding_window_attention
-from .kv_cache import NSA_KV, NSA_PagedKV
+from .kv_cache import NSA_KV, NSA_PagedKV, PAGE_TOKENS
 from .selection_attention import (
     select_and_attend,
     selection_attention_first_key_parity,
@@ -853,6 +853,44 @@ class NSAAttention(nn.Module):
                                   (x.data_ptr(), y.data_ptr(), t_pos.data_ptr(), t_max, S), (), (B, S, G, self.n_sel, 2), (B, S, G, 3))
         self._monitors(ranges, gates)
         return y, pkv
+
+    def prefill_paged(self, x: torch.Tensor, pkv: NSA_PagedKV, b: int, t0: int = 0):
+        """x [1,S,dim], the tokens of positions t0 .. t0 + S - 1 of the sequence in slot b of `pkv` -> y [1,S,dim]; afterwards the slot's pages
+        hold t0 + S tokens (pages are assigned as needed; lengths belong to the caller).
+        t0 = 0: the one-shot prefill onto a scratch B = 1 NSA_KV, then one store launch (nsa_paged_kv_store) into the slot's pages.
+        t0 > 0: the slot already holds t0 tokens -- from a pkv.fork of a common prefix, say.  own_tail(b, t0) and ensure(b, t0 + S), one load
+        launch into a scratch cache, the extend route on it (forward(x, scratch, prefill=True) with scratch.t = t0: decode-step semantics, as
+        documented there), one store launch of rows [t0, t0 + S) and of the compressed rows that completed.
+        Monitors: as forward leaves them.  Inference only; CPU tensors and parity mode are refused as in decode_paged."""
+        assert x.dim() == 3, "x must be [B,S,dim]"
+        if x.shape[0] != 1 or x.shape[1] < 1:
+            raise ValueError(f"NSAAttention.prefill_paged takes one sequence x [1,S,dim] with S >= 1, got {tuple(x.shape)}")
+        S, b, t0 = x.shape[1], pkv._slot(b), int(t0)
+        if not x.is_cuda or pkv.block_table.device != x.device:
+            raise RuntimeError("NSAAttention.prefill_paged needs HIP device tensors on one device (no CPU fallback exists)")
+        buf = pkv._K_sel
+        if buf.dtype != x.dtype or buf.device != x.device or (pkv.G, pkv.d_k, pkv.d_v) != (self.n_kv_groups, self.d_k, self.d_v):
+            raise RuntimeError(f"NSA_PagedKV does not match the input or the module: pools {buf.dtype} on {buf.device} (G={pkv.G}, d_k={pkv.d_k}, "
+                               f"d_v={pkv.d_v}), x {x.dtype} on {x.device}")
+        if self._grad_needed(x):
+            raise RuntimeError("NSAAttention.prefill_paged is inference only (no backward); run it under torch.no_grad()")
+        if not self._native_ok(x):
+            raise RuntimeError("NSAAttention.prefill_paged: the native calls do not take this module or input (parity mode, dtype, gate width), and "
+                               "there is no other route over pages")
+        if not 0 <= t0 <= len(pkv.pages[b]) * PAGE_TOKENS:
+            raise ValueError(f"NSAAttention.prefill_paged: t0 = {t0} outside the {len(pkv.pages[b])} pages of slot {b}")
+        if t0 + S > pkv.capacity:
+            raise RuntimeError(f"NSAAttention.prefill_paged: {t0 + S} tokens outside the capacity {pkv.capacity} of a slot")
+        if t0 == 0:
+            cap = (S + PAGE_TOKENS - 1) // PAGE_TOKENS * PAGE_TOKENS
+            kv1 = NSA_KV(1, pkv.G, pkv.d_k, pkv.d_v, cap, self.l, self.d, self.l_sel, self.n_sel, self.w, x.device, x.dtype, auto_grow=False)
+        else:
+            pkv.own_tail(b, t0)
+            pkv.ensure(b, t0 + S)
+            kv1 = pkv.gather_sequence(b, t0)  # (capacity: the slot's pages, which now cover t0 + S)
+        y, _ = self.forward(x, kv1, prefill=True)
+        pkv.load_sequence(b, kv1, t0 + S, t0=t0)
+        return y
 
     def _decode_ragged_sequences(self, x: torch.Tensor, kv: NSA_KV, host, t_max: int):
         """the per-sequence route of decode_ragged: one decode_rows per live sequence on its slab, zeros for the padding slots"""
