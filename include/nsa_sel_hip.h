@@ -70,7 +70,7 @@ NSA_API const char *nsa_hip_last_error(void);
 /* Measurement / A-B switches (kernel form, staging, mapping).  Each switch is seeded once per process from the environment
  * variable NSA_HIP_<NAME> and can be changed afterwards only through this call (nothing reads the environment on the launch
  * path).  name: "SEL_ROWS", "ATTN_MAP", "ATTN_STAGE", "BAND_STAGE", "DECODE_UNFUSED", "SEL_BLOCKS", "DECODE_WG", "SEL_ROWSUM", "DECODE_STENCIL", "SEL_FUSE", "SCORES_FORM", "SEL_FLAT", "SEL_KSPLIT", "DECODE_STOP" (TIMELINE builds
- * only), "DECODE_WAVES", "DECODE_SPLIT", "DECODE_STEP", "DECODE_TEAM_SPIN", "DECODE_WIDE", "SEL_KSPLIT_T1", "SEL_KSPLIT_T2", "SCORES_SELECT", "DECODE_BAND" (with or without the NSA_HIP_ prefix); value -1 = automatic where the switch has an automatic setting.  Results never depend on a switch beyond the
+ * only), "DECODE_WAVES", "DECODE_SPLIT", "DECODE_STEP", "DECODE_TEAM_SPIN", "DECODE_WIDE", "SEL_KSPLIT_T1", "SEL_KSPLIT_T2", "SCORES_SELECT", "DECODE_BAND", "DECODE_LONG" (with or without the NSA_HIP_ prefix); value -1 = automatic where the switch has an automatic setting.  Results never depend on a switch beyond the
  * tolerances stated for the entry point. */
 NSA_API int nsa_hip_set_tuning(const char *name, int value);
 NSA_API int nsa_hip_get_tuning(const char *name, int *value);
@@ -325,7 +325,8 @@ NSA_API int nsa_layer_decode_rows_plan(const nsa_layer_desc *L, int B, int S, in
  * mix, 6. the output projection.  At Dk = Dv = 128 the band branches are one ragged launch each and the gate kernel stands in for 5.
  * There is no scalar route to stand in, so the call DECLINES with NSA_ERR_INVALID and a message naming the limit wherever
  * nsa_sel_decode_ragged does: a dtype other than bf16 / f16, anything but Dk = Dv in {64, 128} and the default block geometry, te beyond the
- * unsplit forms, DECODE_STEP = 0 or DECODE_UNFUSED = 1, a null or misaligned operand, S outside [1,16].
+ * unsplit forms (with the tuning switch DECODE_LONG = 1: te beyond 131,071, the limit of the long-row form the selected branch then runs --
+ * same launch count, same workspace), DECODE_STEP = 0 or DECODE_UNFUSED = 1, a null or misaligned operand, S outside [1,16].
  * nsa_layer_decode_ragged_plan makes no HIP call: NSA_OK with *launches = n and *route = 1, or *launches = 0 and *route = -1 for a declined
  * shape; an error status for bad arguments.  workspace: nsa_layer_decode_ragged_workspace() bytes, 256-byte aligned -- not less than
  * nsa_layer_decode_rows_workspace(L, B, S, S_max), and 0 for the arguments that call answers 0 for. */
@@ -373,11 +374,12 @@ NSA_API int nsa_layer_decode_ragged_plan(const nsa_layer_desc *L, int B, int S, 
  * its finish kernel while this call combines per branch: y is within the rounding of that.
  * DECLINES with NSA_ERR_INVALID and a message naming the limit, no fallback, wherever nsa_layer_decode_ragged and the two paged operators
  * do: a dtype other than bf16 / f16, anything but Dk = Dv in {64, 128} and the default block geometry, h > 16, w < 1, te beyond the unsplit
- * forms, DECODE_STEP = 0 or DECODE_UNFUSED = 1, S outside [1,16], a null or misaligned operand, max_pages outside [1, 2^20], n_pages < 1, a
- * table stride below max_pages.
+ * forms (with the tuning switch DECODE_LONG = 1: te beyond 131,071, the limit of the long-row form the selected branch then runs -- same
+ * launch count, same workspace), DECODE_STEP = 0 or DECODE_UNFUSED = 1, S outside [1,16], a null or misaligned operand, max_pages outside
+ * [1, 2^20], n_pages < 1, a table stride below max_pages.
  * nsa_layer_decode_paged_plan makes no HIP call: NSA_OK with *launches = n and *route = 1, or *launches = 0 and *route = -1 for a declined
  * shape; an error status for bad arguments.  workspace: nsa_layer_decode_paged_workspace() bytes, 256-byte aligned (0 for a null descriptor,
- * B < 1, S outside [1,16] or max_pages outside [1, 2^20]); it does not grow with max_pages beyond the contexts the unsplit forms reach. */
+ * B < 1, S outside [1,16] or max_pages outside [1, 2^20]); it does not grow with max_pages beyond 2^17 tokens, the contexts the forms reach. */
 typedef struct nsa_paged_kv_desc {
     void *K_sel, *V_sel, *K_win, *V_win, *K_raw, *V_raw; /* [n_pages, G, 1024, D] */
     void *K_cmp, *V_cmp;                                 /* [n_pages, G, 64, D] */
@@ -627,7 +629,14 @@ NSA_API int nsa_sel_decode_rows_plan(int B, int S, int G, int h, int Dk, int Dv,
  * h <= 16, the default block geometry (l = 32, d = 16, l' = 64), 16-byte aligned operands, S <= 16, or a t_max beyond the unsplit forms
  * (more than 64 / 32 / 16 chunks of 64 compressed tokens at 16 waves / 8 waves / D = 128) -- the separate launches take a scalar
  * position only and cannot stand in.  DECODE_STEP = 0 and DECODE_UNFUSED = 1 decline as well; DECODE_ROWS does not apply.
- * nsa_sel_decode_ragged_plan: *launches = 1 and *form = 0 / 1, or *launches = 0 and *form = -1 for a declined shape (status NSA_OK).
+ * Tuning switch "DECODE_LONG" (default 0): with 1 a t_max beyond the unsplit forms is not declined but runs the LONG-ROW form (form 3):
+ * still one workgroup per row and one launch, no workspace; a wave keeps the logits of its first two chunks in registers and sweeps every
+ * further chunk twice (records first, then -- with the row's log-sum-exp -- the same MFMAs on the same operands again), so ranges and O
+ * are the bits of the other exact forms.  It holds rows of up to 128 chunks of 64 compressed tokens and 2048 selection blocks:
+ * t_max <= 131,071.  Beyond that the call declines with a message naming that limit.  A shape inside the unsplit forms keeps form 0 / 1
+ * whatever the switch says.
+ * nsa_sel_decode_ragged_plan: *launches = 1 and *form = 0 / 1 (/ 3 with DECODE_LONG = 1), or *launches = 0 and *form = -1 for a declined
+ * shape (status NSA_OK).
  * workspace: nsa_sel_decode_ragged_workspace() bytes (0 today: the launch keeps everything on chip); may be null.
  * Bits: with t_pos[b] = t0 for every b, ranges and O are those of nsa_sel_decode_rows(t0); the existing entry points are unchanged.
  * ------------------------------------------------------------------------------------- */
@@ -669,7 +678,9 @@ NSA_API int nsa_sel_decode_ragged_plan(int B, int S, int G, int h, int Dk, int D
  * the same declines and messages (dtype, Dk = Dv in {64, 128}, h <= 16, the default block geometry, S <= 16, a t_max beyond the unsplit
  * forms, DECODE_STEP = 0, DECODE_UNFUSED = 1), and in addition NSA_ERR_INVALID for page_tokens != 1024, a null table, max_pages < 1,
  * n_pages < 1, a table stride below max_pages, misaligned pools or strides, and row strides that leave the 32-bit in-plane offsets.
- * nsa_sel_decode_paged_plan: *launches = 1 and *form = 0 / 1, or *launches = 0 and *form = -1 for a declined shape or page size (status
+ * With the tuning switch DECODE_LONG = 1 a t_max beyond the unsplit forms runs the long-row form (form 3) as in nsa_sel_decode_ragged: rows
+ * of up to 128 chunks (t_max <= 131,071: table entries 0 .. 127), the same bits as that call on contiguous caches.
+ * nsa_sel_decode_paged_plan: *launches = 1 and *form = 0 / 1 (/ 3 with DECODE_LONG = 1), or *launches = 0 and *form = -1 for a declined shape or page size (status
  * NSA_OK).  workspace: nsa_sel_decode_paged_workspace() bytes (0 today); may be null.
  * Bits: for a table that scatters contiguous caches into pages, in any order, ranges and O are those of nsa_sel_decode_ragged on the
  * contiguous caches bit for bit -- the same form and waves, the same arithmetic on the same values in the same order.  The existing entry

@@ -8,6 +8,7 @@
 //   dispatch_check <library> paged                  the cases of the ragged decode step over paged caches (nsa_sel_decode_paged)
 //   dispatch_check <library> band_paged             the cases of the ragged band forward over paged caches (nsa_band_attn_fwd_paged)
 //   dispatch_check <library> layer_paged            the cases of the layer's paged call (nsa_layer_decode_paged)
+//   dispatch_check <library> decode_long            the four ragged / paged entry points beyond the unsplit forms (switch DECODE_LONG)
 #include <dlfcn.h>
 #include <math.h>
 #include <stdio.h>
@@ -415,7 +416,9 @@ static void run_proj(const std::string &label, const std::function<int()> &call)
 // ---- dispatch_check <library> ragged: the entry points with per-sequence positions (nsa_sel_decode_ragged, nsa_band_attn_fwd_ragged), cases
 // of their own so that the default output keeps its cases and members.  The position array is a device pointer the host must never read: it
 // is handed over as an address inside a named buffer and shows up again in the argument block of the launch.
-static void ragged_cases() {
+// long_mode (dispatch_check <library> decode_long): not the cases below but the shapes beyond the unsplit forms, with the switch DECODE_LONG at 1
+// (one launch in form 3), at the limit, past it, and with the switch back at 0 (the declines as they were)
+static void ragged_cases(bool long_mode = false) {
     const int dt = NSA_DT_BF16, G = 2, h = 6, n = 16;
     const size_t MB = 1 << 20;
     void *Q = dev(MB), *K = dev(MB), *V = dev(MB), *Kc = dev(MB), *O = dev(MB), *ws = dev(16 * MB);
@@ -461,6 +464,25 @@ static void ragged_cases() {
                        .i("S", P.S).p("t_pos", P.t_pos).i("t_max", P.t_max).str();
         });
     };
+    if (long_mode) {
+        NSA_FN(nsa_hip_set_tuning)("DECODE_LONG", 1);
+        ragged_case("long_D128_t_max20000", [](Case &c) { c.D = 128; c.t_max = 20000; });
+        ragged_case("long_t_max70000", [](Case &c) { c.B = 1; c.t_max = 70000; });
+        ragged_case("long_B200_t_max40000", [](Case &c) { c.B = 200; c.t_max = 40000; });
+        ragged_case("long_t_max131071", [](Case &c) { c.B = 1; c.t_max = 131071; });
+        ragged_case("long_D128_S4_t_max131071", [](Case &c) { c.D = 128; c.S = 4; c.t_max = 131071; });
+        ragged_case("long_t_max131072_declined", [](Case &c) { c.B = 1; c.t_max = 131072; });
+        ragged_case("long_t_max100_form0", [](Case &) {});
+        ragged_case("long_t_max40000_form1", [](Case &c) { c.B = 1; c.t_max = 40000; });
+        NSA_FN(nsa_hip_set_tuning)("DECODE_STEP", 0);
+        ragged_case("long_DECODE_STEP_0_declined", [](Case &c) { c.B = 1; c.t_max = 70000; });
+        NSA_FN(nsa_hip_set_tuning)("DECODE_STEP", 1);
+        NSA_FN(nsa_hip_set_tuning)("DECODE_LONG", 0);
+        ragged_case("off_D128_t_max20000_declined", [](Case &c) { c.D = 128; c.t_max = 20000; });
+        ragged_case("off_t_max70000_declined", [](Case &c) { c.B = 1; c.t_max = 70000; });
+        ragged_case("off_B200_t_max40000_declined", [](Case &c) { c.B = 200; c.t_max = 40000; });
+        return;
+    }
     ragged_case("t_max100", [](Case &) {});
     ragged_case("t_max100_S4", [](Case &c) { c.S = 4; });
     ragged_case("t_max20_no_compressed_token", [](Case &c) { c.t_max = 20; });
@@ -512,7 +534,7 @@ static void ragged_cases() {
 // block table, like the position array, is a device pointer the host must never read: it is handed over as an address inside a named buffer
 // filled with 0x7f bytes (no valid page id) and shows up again in the argument block of the launch, with its stride, n_pages and the
 // three page strides.
-static void paged_cases() {
+static void paged_cases(bool long_mode = false) {  // long_mode: as ragged_cases
     const int G = 2, h = 6, n = 16;
     const size_t MB = 1 << 20;
     void *Q = dev(MB), *K = dev(MB), *V = dev(MB), *Kc = dev(MB), *O = dev(MB);
@@ -566,6 +588,21 @@ static void paged_cases() {
                        .i("kc_page_stride", P.csb).p("K", A.K).p("V", A.V).i("k_page_stride", A.ksb).i("v_page_stride", A.vsb).i("capacity", A.S_kv).str();
         });
     };
+    if (long_mode) {
+        NSA_FN(nsa_hip_set_tuning)("DECODE_LONG", 1);
+        paged_case("long_D128_t_max20000", [](Case &c) { c.D = 128; c.t_max = 20000; });
+        paged_case("long_t_max70000", [](Case &c) { c.B = 1; c.t_max = 70000; });
+        paged_case("long_B200_t_max40000", [](Case &c) { c.B = 200; c.t_max = 40000; });
+        paged_case("long_t_max131071", [](Case &c) { c.B = 1; c.t_max = 131071; });
+        paged_case("long_t_max131071_max_pages4096", [](Case &c) { c.B = 1; c.t_max = 131071; c.max_pages = 4096; });
+        paged_case("long_t_max131072_declined", [](Case &c) { c.B = 1; c.t_max = 131072; });
+        paged_case("long_t_max100_form0", [](Case &) {});
+        NSA_FN(nsa_hip_set_tuning)("DECODE_LONG", 0);
+        paged_case("off_D128_t_max20000_declined", [](Case &c) { c.D = 128; c.t_max = 20000; });
+        paged_case("off_t_max70000_declined", [](Case &c) { c.B = 1; c.t_max = 70000; });
+        paged_case("off_B200_t_max40000_declined", [](Case &c) { c.B = 200; c.t_max = 40000; });
+        return;
+    }
     paged_case("t_max100", [](Case &) {});
     paged_case("t_max100_S4", [](Case &c) { c.S = 4; });
     paged_case("t_max20_no_compressed_token", [](Case &c) { c.t_max = 20; });
@@ -689,7 +726,7 @@ static void band_paged_cases() {
 // case prints the launchers in order with their geometry, the plan's answer for the same shape, and "positions": the position pointer and the
 // bound te as they arrive in the argument blocks of the four launches that depend on the position (projection, pooling, the selected branch,
 // the band pair: both of its blocks).
-static void layer_ragged_cases() {
+static void layer_ragged_cases(bool long_mode = false) {  // long_mode: the layer twins of ragged_cases' long shapes, beside an in-range plan
     const size_t MB = 1 << 20;
     void *x = dev(MB), *y = dev(MB), *W_qkv = dev(MB), *W_out = dev(MB), *gw = dev(MB), *ws = dev(64 * MB);
     void *cache[8];
@@ -763,6 +800,18 @@ static void layer_ragged_cases() {
         printf(",\n%s: %s", quoted(std::string("layer_decode_ragged/") + label + "_plan").c_str(),
                Obj().i("rc", prc).i("launches", launches).i("route", route).i("workspace", (long long)ws_fn(&L, c.B, c.S, c.S_max)).str().c_str());
     };
+    if (long_mode) {
+        NSA_FN(nsa_hip_set_tuning)("DECODE_LONG", 1);
+        layer_case("in_range_m7c_B3_S8", [](Case &) {});
+        layer_case("in_range_D128_B3_S4", [](Case &c) { c.D = 128; c.dim = 1536; c.S = 4; });
+        layer_case("long_t_max70000", [](Case &c) { c.S_max = 131072; c.t_max = 70000; });
+        layer_case("long_t_max131071", [](Case &c) { c.S_max = 131072; c.t_max = 131071; });
+        layer_case("long_D128_t_max20000", [](Case &c) { c.D = 128; c.dim = 1536; c.S = 4; c.S_max = 32768; c.t_max = 20000; });
+        layer_case("long_t_max131072_declined", [](Case &c) { c.S_max = 140000; c.t_max = 131072; });
+        NSA_FN(nsa_hip_set_tuning)("DECODE_LONG", 0);
+        layer_case("off_t_max70000_declined", [](Case &c) { c.S_max = 131072; c.t_max = 70000; });
+        return;
+    }
     layer_case("m7c_B3_S8", [](Case &) {});
     layer_case("m7c_B3_S8_no_token_due", [](Case &c) { c.t_max = 1063; });
     layer_case("m7c_B16_S1", [](Case &c) { c.B = 16; c.S = 1; });
@@ -787,7 +836,7 @@ static void layer_ragged_cases() {
 // argument blocks in full (RopePagedParams, CmpPoolPagedParams: the pools, the capacities, the table block) and the position array and the
 // table as they arrive at the readers.  The positions, the table and the pools are device memory the host must never read: addresses inside
 // buffers of 0x7f bytes.  Every launch behind the pre-pass must name ws + <the offset of t_live> as its position array, never t_pos.
-static void layer_paged_cases() {
+static void layer_paged_cases(bool long_mode = false) {  // long_mode: as layer_ragged_cases
     const size_t MB = 1 << 20;
     void *x = dev(MB), *y = dev(MB), *W_qkv = dev(MB), *W_out = dev(MB), *gw = dev(MB), *ws = dev(128 * MB);
     void *pool[8];
@@ -886,6 +935,18 @@ static void layer_paged_cases() {
         printf(",\n%s: %s", quoted(std::string("layer_decode_paged/") + label + "_plan").c_str(),
                Obj().i("rc", prc).i("launches", launches).i("route", route).i("workspace", (long long)ws_fn(&L, c.B, c.S, c.max_pages)).str().c_str());
     };
+    if (long_mode) {
+        NSA_FN(nsa_hip_set_tuning)("DECODE_LONG", 1);
+        layer_case("in_range_m7c_B3_S8", [](Case &) {});
+        layer_case("in_range_D128_B3_S4", [](Case &c) { c.D = 128; c.dim = 1536; c.S = 4; });
+        layer_case("long_t_max70000", [](Case &c) { c.max_pages = 128; c.t_max = 70000; });
+        layer_case("long_t_max131071", [](Case &c) { c.max_pages = 128; c.t_max = 131071; });
+        layer_case("long_D128_t_max20000", [](Case &c) { c.D = 128; c.dim = 1536; c.S = 4; c.max_pages = 32; c.t_max = 20000; });
+        layer_case("long_t_max131072_declined", [](Case &c) { c.max_pages = 200; c.t_max = 131072; });
+        NSA_FN(nsa_hip_set_tuning)("DECODE_LONG", 0);
+        layer_case("off_t_max70000_declined", [](Case &c) { c.max_pages = 128; c.t_max = 70000; });
+        return;
+    }
     layer_case("m7c_B3_S8", [](Case &) {});
     layer_case("m7c_B16_S1", [](Case &c) { c.B = 16; c.S = 1; });
     layer_case("m7c_B1_S2_chunk_loop", [](Case &c) { c.B = 1; c.S = 2; });
@@ -920,7 +981,7 @@ static void layer_paged_cases() {
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: dispatch_check <libnsa_sel_hip.so> [ragged | layer_ragged | layer_paged | paged | band_paged]\n");
+        fprintf(stderr, "usage: dispatch_check <libnsa_sel_hip.so> [ragged | layer_ragged | layer_paged | paged | band_paged | decode_long]\n");
         return 2;
     }
     g_lib = dlopen(argv[1], RTLD_NOW | RTLD_GLOBAL);
@@ -955,6 +1016,15 @@ int main(int argc, char **argv) {
     if (argc >= 3 && !strcmp(argv[2], "layer_paged")) {  // the layer's paged call alone (tests/test_layer_decode_paged_host.py)
         printf("{");
         layer_paged_cases();
+        printf("\n}\n");
+        return 0;
+    }
+    if (argc >= 3 && !strcmp(argv[2], "decode_long")) {  // the long-row form of the ragged / paged step (tests/test_dispatch_decode_long_host.py)
+        printf("{");
+        ragged_cases(true);
+        paged_cases(true);
+        layer_ragged_cases(true);
+        layer_paged_cases(true);
         printf("\n}\n");
         return 0;
     }

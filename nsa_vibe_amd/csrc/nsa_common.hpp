@@ -62,6 +62,7 @@ enum Tune {
     TUNE_DECODE_BAND,       // NSA_HIP_DECODE_BAND: layer decode step, the sliding + compressed branches: 0 = their own launch; 1 = on the launch of the selected branch's one-launch decode step, splits merged by the finish kernel; 2 = the same with the splits merged by the workgroup that holds them (branch outputs and gates final); 3 / -1 (default) = 2 + with <= 8 rows the gate mix is the A operand of the output projection (three launches per step)
     TUNE_DECODE_ROWS,       // NSA_HIP_DECODE_ROWS: nsa_sel_decode_rows, 1 = the one-launch rows form wherever its unsplit forms hold the shape, 0 = always the separate launches, -1 = the one-launch form in the (S, context) cells where it was measured not slower
     TUNE_LAYER_DECODE_ROWS, // NSA_HIP_LAYER_DECODE_ROWS: nsa_layer_decode_rows_plan, 1 = the rows call for every shape it takes, 0 = always declined (S single layer steps), -1 = taken in the (B, S, context) cells where it was measured not slower than S single steps
+    TUNE_DECODE_LONG,       // NSA_HIP_DECODE_LONG: ragged / paged decode (nsa_sel_decode_ragged / _paged, nsa_layer_decode_ragged / _paged), 1 = a row beyond the unsplit forms runs the long-row form (form 3: up to 128 chunks, t_max <= 131,071, later chunks swept twice, no workspace), 0 (default) = such a call is declined
     TUNE_COUNT
 };
 // the switches' names (environment: NSA_HIP_<name>) and defaults, one entry per Tune in the enum's order
@@ -78,7 +79,7 @@ constexpr TuneEntry TUNE_TABLE[] = {
     NSA_TUNE(SEL_KSPLIT, -1),     NSA_TUNE(DECODE_STOP, 0),    NSA_TUNE(DECODE_WAVES, -1),  NSA_TUNE(DECODE_SPLIT, -1),
     NSA_TUNE(DECODE_STEP, 1),     NSA_TUNE(DECODE_TEAM_SPIN, -1), NSA_TUNE(DECODE_WIDE, -1), NSA_TUNE(SEL_KSPLIT_T1, -1),
     NSA_TUNE(SEL_KSPLIT_T2, -1),  NSA_TUNE(SCORES_SELECT, -1), NSA_TUNE(DECODE_BAND, -1),    NSA_TUNE(DECODE_ROWS, -1),
-    NSA_TUNE(LAYER_DECODE_ROWS, -1),
+    NSA_TUNE(LAYER_DECODE_ROWS, -1), NSA_TUNE(DECODE_LONG, 0),
 };
 #undef NSA_TUNE
 constexpr bool tune_table_in_order() {

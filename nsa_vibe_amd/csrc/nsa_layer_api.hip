@@ -676,8 +676,8 @@ static nsa_kv_desc page_extent_kv(const nsa_paged_kv_desc *p) {
     return kv;
 }
 constexpr int LAYER_PAGED_MAX_PAGES = 1 << 20;  // (the paged operators' bound: the capacity max_pages * 1024 stays a positive int)
-// the workspace is the ragged call's for the longest context a live row can sit in -- the unsplit forms end at 64 chunks of 64 compressed
-// tokens, under 2^17 tokens -- plus the verdicts t_live [B]; it does not grow with max_pages
+// the workspace is the ragged call's for the longest context a live row can sit in -- the long-row form of the selected branch ends at 128 chunks of 64
+// compressed tokens, te = 2^17 - 1 -- plus the verdicts t_live [B]; it does not grow with max_pages
 static int paged_ws_tokens(int max_pages) { return (int)std::min<int64_t>((int64_t)max_pages * LAYER_PAGE_TOKENS, 1 << 17); }
 
 // What the call and its plan share, from the shape, the host bound and the switches alone (aligned pools assumed; neither the positions nor

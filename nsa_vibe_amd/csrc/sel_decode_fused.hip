@@ -34,8 +34,14 @@
 // through a device block table -- one scorer chunk and 16 selection blocks per page, so every K_cmp chunk, gathered block and forced block
 // lies in ONE page and the table costs one wave-uniform lookup per chunk.  Same form, waves, values and order as the ragged form: ranges
 // and O are its bits (tests/test_hip_decode_paged.py).  An instantiation of its own: no other one holds any of its code.
+// Long-row form (template flag LONG on the ragged rows form and its paged form; plan form 3, switch DECODE_LONG): a row of up to DSTEP_CH =
+// 128 chunks (t <= 131,071) in ONE workgroup, no workspace.  A wave owns chunks wave + NW k; the logits of its first two stay in the
+// accumulators as in form 0, every further chunk is swept TWICE: the first sweep leaves only its (max, sum) record and edge logit, the
+// second -- once the row's log-sum-exp is known -- loads it again and recomputes the logits with the same MFMAs on the same operands in the
+// same order, so the scores, ranges and O are the bits of every other exact form (tests/test_hip_decode_long.py).
 #include <algorithm>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 
 #define DEC_TS(i)  // (the shared device functions' own stamps belong to the round-2 kernel's timeline: this kernel stamps with DS_TS)
@@ -59,7 +65,7 @@ constexpr int DSTEP_CH = 128;                  // chunks of 64 compressed rows p
 constexpr int DSTEP_PART = 16 * DSTEP_CH * 2;  // floats: [head][chunk][2]
 constexpr int DSTEP_HALO = DSTEP_CH * 16;      // floats: [chunk][head] scaled logit of the chunk's last row
 constexpr int DSTEP_TAIL = 1024 + 4 * (128 + 68 + 4);  // bytes behind the V tiles: mlw [16][16] f32 | scr | list | misc
-constexpr int DSTEP_PAGES = 128;               // paged form: table entries of a sequence kept in LDS behind everything else (the forms end below 66 pages)
+constexpr int DSTEP_PAGES = 128;               // paged form: table entries of a sequence kept in LDS behind everything else (the long-row form ends at 128 chunks = 131,072 tokens: pages 0 .. 127)
 // D = 128 (eight waves): 8 x 16 KiB of V tiles + the tail = 132,896 bytes -- one workgroup per CU; the score phases (part 16 KiB | halo 8 KiB |
 // pg <= 8 KiB) fit the 128 KiB of tiles with room to spare
 static size_t dstep_lds(int nw, int D = 64) { return (size_t)nw * dec_att_tile(D) + DSTEP_TAIL + (nw == 16 ? 3 * dec_att_tile(D) : 0); }
@@ -89,7 +95,7 @@ __device__ __forceinline__ bool decode_band_workgroup(const DecBandPair &BP) {
 // registers, those of the later three wait in LDS ([slot][u][head][q] f32x4, 256 h bytes per chunk: each lane reads back exactly what it
 // wrote, so no barrier guards them) until the row's log-sum-exp is known.  Two chunks (16 KiB per wave) are in flight throughout.  Same
 // arithmetic on the same values: p_grp, ranges and O have the bits of every other form.
-template <typename T, int NW, bool SPLIT, int HC, int CPW = 2, int D = 64, bool ROWS = false, bool PAGED = false>
+template <typename T, int NW, bool SPLIT, int HC, int CPW = 2, int D = 64, bool ROWS = false, bool PAGED = false, bool LONG = false>
 __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(DecStepParams P, SelectParams SP, int cand, DecAttnArgs AT, DecBandPair BP) {
     static_assert(CPW == 2 || (CPW == 4 && !SPLIT), "four chunks per wave: unsplit form only");
     static_assert(!PAGED || ROWS, "paged caches: the ragged rows form only");
@@ -97,6 +103,7 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
     constexpr int KS = D / 32;              // MFMA k-steps of a logit
     constexpr int TILE = dec_att_tile(D);   // V tile of a wave (the score phases live in the same LDS)
     static_assert(!ROWS || !SPLIT, "rows form: one workgroup per row, no meeting of workgroups");
+    static_assert(!LONG || (ROWS && CPW == 2), "long-row form: the rows form, the first two chunks of a wave in the accumulators");
     if constexpr (!ROWS) {
         if (decode_band_workgroup<T, NW>(BP)) return;
     }
@@ -145,8 +152,8 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
     // selection blocks -- and entry j of row b of P.block_table is the pool page of the sequence's tokens [1024 j, 1024 j + 1024) in all
     // three pools; AT.S_kv is the capacity max_pages * 1024.  A sequence whose position passes the bounds is inactive as above; one that
     // passes them needs the entries j = 0 .. (t_base + S - 1) >> 10 (< max_pages by the capacity bound), and is inactive too if any of
-    // them lies outside [0, n_pages).  Every wave checks the needed entries for itself, lane L loading entries L and L + 64 (the forms
-    // end at 64 chunks = 65,567 tokens: at most 65), so the verdict needs no barrier and is the same in every wave; entries behind the
+    // them lies outside [0, n_pages).  Every wave checks the needed entries for itself, lane L loading entries L and L + 64 (the long-row
+    // form ends at 128 chunks, t <= 131,071: at most DSTEP_PAGES = 128 entries), so the verdict needs no barrier and is the same in every wave; entries behind the
     // needed ones are never read.  The checked entries go to LDS -- every wave stores the same values and reads only behind its own
     // stores -- for the wave-uniform lookups of the sweep, the forced-block prefetch and the gather (kept in the two registers for
     // v_readlane instead, the 16-wave form 1 spilled 17 - 24 VGPRs against 9 this way: DESIGN.md 4.1h).  No table value reaches an
@@ -243,7 +250,8 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
             z[u] = zz;
         }
     };
-    auto chunk_stats = [&](int c, f32x4 (&z)[4]) {
+    // (to_ws: the records go to the team's workspace; otherwise to this workgroup's LDS)
+    auto chunk_stats_as = [&](int c, f32x4 (&z)[4], auto to_ws) {
         float m = -INFINITY;
 #pragma unroll
         for (int u = 0; u < 4; ++u)
@@ -261,7 +269,7 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
             for (int j = 0; j < 4; ++j)
                 if (c * 64 + 16 * u + 4 * q + j < S_cmp) l += __builtin_amdgcn_exp2f(z[u][j] - m);
         l = xor32_add(xor16_add(l));
-        if constexpr (SPLIT) {
+        if constexpr (decltype(to_ws)::value) {
             if (rho < h) {  // write-through (sc1) stores: no release fence needed (cdna guide, Guideline 16 R1)
                 if (q == 0)
                     __hip_atomic_store((unsigned long long *)(P.part_g + (((int64_t)row * h + rho) * DSTEP_CH + c) * 2),
@@ -277,7 +285,36 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
             }
         }
     };
-    if constexpr (CPW == 2) {
+    auto chunk_stats = [&](int c, f32x4 (&z)[4]) { chunk_stats_as(c, z, std::bool_constant<SPLIT>{}); };
+    // LONG: the chunk whose loads follow chunk c into the same registers -- the chunk after next of the sweep, and behind the first sweep's
+    // last chunks the first ones of the second sweep (wave + 2 NW, wave + 3 NW: same register parity), so two chunks stay in flight across
+    // the barrier and the log-sum-exp.  (At D = 64 the 32 accumulator registers of the first two chunks beside two chunks in flight exceed
+    // the 128 registers of a lane: 14 - 20 are spilled, with or without these early loads -- profiles/decode_long/resources.txt.)
+    [[maybe_unused]] auto long_next = [&](int c, int k) -> int { return c + 2 * NW < c_hi ? c + 2 * NW : wave + NW * (2 + k); };
+    if constexpr (LONG) {
+        // chunks 0, 1 of the wave -> registers (form 0); every later one leaves its record and edge logit only (first sweep)
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int c = wave + NW * k;
+            if (c < c_hi) {
+                chunk_logits(c, a[k], acc[k]);
+                if (c + 2 * NW < c_hi) load_chunk(c + 2 * NW, a[k]);
+                chunk_stats(c, acc[k]);
+            }
+        }
+        for (int c0 = wave + 2 * NW; c0 < c_hi; c0 += 2 * NW) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int c = c0 + NW * k;
+                if (c < c_hi) {
+                    f32x4 z[4];
+                    chunk_logits(c, a[k], z);
+                    if (long_next(c, k) < c_hi) load_chunk(long_next(c, k), a[k]);
+                    chunk_stats(c, z);
+                }
+            }
+        }
+    } else if constexpr (CPW == 2) {
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             const int c = c_lo + wave + NW * k;
@@ -357,38 +394,10 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
             // the same instructions on the same data, so the same bits as its team mates publish -- and carries on.  Slower, never stuck.
             for (int c = wave; c < nchunk; c += NW) {
                 x8 b2[4][KS];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int r = min(c * 64 + 16 * u + rho, S_cmp - 1);
-#pragma unroll
-                    for (int s2 = 0; s2 < KS; ++s2) b2[u][s2] = *(const x8 *)(kb + (int64_t)r * P.css + 32 * s2 + 8 * q);
-                }
+                load_chunk(c, b2);
                 f32x4 z[4];
-                float m = -INFINITY;
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    z[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int s2 = 0; s2 < KS; ++s2) z[u] = M::mma(b2[u][s2], qf[s2], z[u]);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float v = z[u][j] * P.c2;
-                        z[u][j] = v;
-                        if (c * 64 + 16 * u + 4 * q + j < S_cmp) m = fmaxf(m, v);
-                    }
-                }
-                m = xor32_max(xor16_max(m));
-                float l = 0.f;
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (c * 64 + 16 * u + 4 * q + j < S_cmp) l += __builtin_amdgcn_exp2f(z[u][j] - m);
-                l = xor32_add(xor16_add(l));
-                if (rho < h) {
-                    if (q == 0) *(f32x2 *)(part + (rho * DSTEP_CH + c) * 2) = (f32x2){m, l};
-                    if (q == 3) halo[c * 16 + rho] = z[3][3];
-                }
+                chunk_logits(c, b2, z);
+                chunk_stats_as(c, z, std::false_type{});
             }
         }
         __syncthreads();
@@ -495,6 +504,26 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
 #pragma unroll
                 for (int u = 0; u < 4; ++u) z[u] = *(const f32x4 *)(slot + ((u * h + hc) * 4 + q) * 4);
                 blocks_of_chunk(c, z, halo[(c - 1) * 16 + hc]);
+            }
+        }
+    }
+    if constexpr (LONG) {
+        // second sweep: the later chunks again -- the same MFMAs on the same operands in the same order, the same scaling: the bits the
+        // first sweep reduced to the chunk's record
+        for (int c0 = wave + 2 * NW; c0 < c_hi; c0 += 2 * NW) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int c = c0 + NW * k;
+                if (c < c_hi) {
+                    f32x4 z[4];
+                    chunk_logits(c, a[k], z);
+                    if (c + 2 * NW < c_hi) load_chunk(c + 2 * NW, a[k]);
+#pragma unroll
+                    for (int u = 0; u < 4; ++u)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) z[u][j] = z[u][j] * P.c2;
+                    blocks_of_chunk(c, z, halo[(c - 1) * 16 + hc]);
+                }
             }
         }
     }
@@ -1053,7 +1082,8 @@ bool decode_rows_supported(const SelDecodeCall &c) { return decode_rows_shape_pl
 
 // ---- ragged form (nsa_sel_decode_ragged): the rows form with the position of sequence b read from a device array.  The host never reads
 // the array: form and waves are planned from the caller's bound t_max (the largest token any live row can sit at) and the row count exactly
-// as decode_rows_shape_plan plans from t0 + S - 1.  What the rows form may decline on the host -- a row without a compressed token -- the
+// as decode_rows_shape_plan plans from t0 + S - 1; with DECODE_LONG = 1 a row beyond the unsplit forms gets form 3 (the long-row form, up to
+// 128 chunks: t_max <= 131,071) instead of a decline -- a shape inside the unsplit forms keeps form 0 / 1 whatever the switch says.  What the rows form may decline on the host -- a row without a compressed token -- the
 // kernel handles, so t_max < 31 is fine here; DECODE_ROWS does not apply (its measured rule weighs alternatives this call does not have: the
 // separate launches cannot take per-sequence positions).  *why: the limit a declined call names.
 bool decode_ragged_shape_plan(const SelDecodeCall &c, int t_max, int *form, int *nw_out, const char **why) {
@@ -1071,7 +1101,16 @@ bool decode_ragged_shape_plan(const SelDecodeCall &c, int t_max, int *form, int 
     int fm;
     if (nchunk <= 2 * nw) fm = 0;
     else if (c.Dk == 64 && nchunk <= 4 * nw) fm = 1;
-    else {
+    else if (tuning(TUNE_DECODE_LONG) > 0) {
+        // the long-row form (form 3): any row of up to DSTEP_CH chunks, its later chunks swept twice.  t_max itself bounds the selection
+        // blocks a live row needs (block t >> 6 must be one of 2048), whatever the buffers hold beyond it
+        if (nchunk > DSTEP_CH || t_max >= 64 * 2048) {
+            *why = "t_max is beyond the long-row form: at most 131,072 tokens per sequence (t_max <= 131,071), 128 chunks of 64 compressed tokens and 2048 "
+                   "selection blocks per row";
+            return false;
+        }
+        fm = 3;
+    } else {
         *why = c.Dk == 128 ? "t_max is beyond the unsplit form at D = 128: more than 16 chunks of 64 compressed tokens per row"
                : nw == 16  ? "t_max is beyond the unsplit forms at 16 waves per row: more than 64 chunks of 64 compressed tokens per row"
                            : "t_max is beyond the unsplit forms at 8 waves per row (more than 256 rows): more than 32 chunks of 64 compressed tokens per row";
@@ -1121,11 +1160,20 @@ int launch_decode_rows(const SelDecodeCall &c, hipStream_t st, const int32_t *t_
 #define NSA_DSR1(NW_, HC_, CPW_, D_, PG_) \
     (bf ? decode_step_kernel<__bf16, NW_, false, HC_, CPW_, D_, true, PG_> : decode_step_kernel<_Float16, NW_, false, HC_, CPW_, D_, true, PG_>)
 #define NSA_DSR(NW_, HC_, CPW_, D_) (pt ? NSA_DSR1(NW_, HC_, CPW_, D_, true) : NSA_DSR1(NW_, HC_, CPW_, D_, false))
-    if (D == 128) {
+#define NSA_DSL1(NW_, HC_, D_, PG_) \
+    (bf ? decode_step_kernel<__bf16, NW_, false, HC_, 2, D_, true, PG_, true> : decode_step_kernel<_Float16, NW_, false, HC_, 2, D_, true, PG_, true>)
+#define NSA_DSL(NW_, HC_, D_) (pt ? NSA_DSL1(NW_, HC_, D_, true) : NSA_DSL1(NW_, HC_, D_, false))
+    if (form == 3) {  // the long-row form: D = 64 on 16 / 8 waves, D = 128 on 8
+        NSA_CHECK_ARG(D == 64 || nw == 8, "decode rows: D = 128 runs on eight waves");
+        if (D == 128) k = h == 6 ? NSA_DSL(8, 6, 128) : NSA_DSL(8, 0, 128);
+        else k = h == 6 ? (nw == 16 ? NSA_DSL(16, 6, 64) : NSA_DSL(8, 6, 64)) : (nw == 16 ? NSA_DSL(16, 0, 64) : NSA_DSL(8, 0, 64));
+    } else if (D == 128) {
         NSA_CHECK_ARG(form == 0 && nw == 8, "decode rows: D = 128 runs form 0 on eight waves");
         k = h == 6 ? NSA_DSR(8, 6, 2, 128) : NSA_DSR(8, 0, 2, 128);
     } else if (cpw == 4) k = h == 6 ? (nw == 16 ? NSA_DSR(16, 6, 4, 64) : NSA_DSR(8, 6, 4, 64)) : (nw == 16 ? NSA_DSR(16, 0, 4, 64) : NSA_DSR(8, 0, 4, 64));
     else k = h == 6 ? (nw == 16 ? NSA_DSR(16, 6, 2, 64) : NSA_DSR(8, 6, 2, 64)) : (nw == 16 ? NSA_DSR(16, 0, 2, 64) : NSA_DSR(8, 0, 2, 64));
+#undef NSA_DSL
+#undef NSA_DSL1
 #undef NSA_DSR
 #undef NSA_DSR1
     if (int rc = dstep_raise_lds((void *)k)) return rc;

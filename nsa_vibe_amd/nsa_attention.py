@@ -728,7 +728,9 @@ class NSAAttention(nn.Module):
     # ---- ragged batch: every sequence of the batch at its own position (a serving batch) --------------------------------------------------
     def decode_ragged_plan(self, B: int, S: int, S_max: int, t_max: int, S_sel: int) -> dict:
         """what nsa_layer_decode_ragged does with a shape under the current tuning switches (nsa_layer_decode_ragged_plan, no device call):
-        {"launches", "route": 1 the one native call / -1 declined (no native route with per-sequence positions)}"""
+        {"launches", "route": 1 the one native call / -1 declined (no native route with per-sequence positions)}.  A t_max beyond the unsplit
+        forms of the selected branch is declined unless the tuning switch DECODE_LONG = 1 (the long-row form: up to t_max = 131,071, the same
+        launch count)"""
         desc, _ = self._layer_desc()
         n, r = _plan_ints("nsa_layer_decode_ragged_plan", 2, ctypes.byref(desc), int(B), int(S), int(S_max), int(t_max), int(S_sel))
         return {"launches": n, "route": r}
@@ -804,7 +806,9 @@ class NSAAttention(nn.Module):
 
     def decode_paged_plan(self, B: int, S: int, max_pages: int, t_max: int, S_sel: int) -> dict:
         """what nsa_layer_decode_paged does with a shape under the current tuning switches (nsa_layer_decode_paged_plan, no device call):
-        {"launches", "route": 1 the one native call / -1 declined (there is no other route over pages)}"""
+        {"launches", "route": 1 the one native call / -1 declined (there is no other route over pages)}.  A t_max beyond the unsplit forms
+        of the selected branch is declined unless the tuning switch DECODE_LONG = 1 (the long-row form: up to t_max = 131,071, the same
+        launch count and workspace)"""
         desc, _ = self._layer_desc()
         n, r = _plan_ints("nsa_layer_decode_paged_plan", 2, ctypes.byref(desc), int(B), int(S), int(max_pages), int(t_max), int(S_sel))
         return {"launches": n, "route": r}

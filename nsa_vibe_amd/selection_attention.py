@@ -288,8 +288,9 @@ def _positions_to(dev, t_pos, host):
 def selection_decode_ragged_plan(B: int, S: int, G: int, h: int, Dk: int, Dv: int, S_cmp: int, S_sel: int, S_kv: int, n_top: int, t_max: int,
                                  dtype: torch.dtype = torch.bfloat16) -> dict:
     """What selection_decode_ragged does with a shape whose largest live row sits at t_max (nsa_sel_decode_ragged_plan; default block
-    geometry, aligned inputs): {"launches": 1, "form": 0 logits in registers / 1 four chunks per wave}, or {"launches": 0, "form": -1}
-    where the call declines -- there is no other native route with per-sequence positions."""
+    geometry, aligned inputs): {"launches": 1, "form": 0 logits in registers / 1 four chunks per wave / 3 the long-row form (tuning switch
+    DECODE_LONG = 1 only: a t_max beyond the unsplit forms, up to 131,071)}, or {"launches": 0, "form": -1} where the call declines --
+    there is no other native route with per-sequence positions."""
     ints = _plan_ints("nsa_sel_decode_ragged_plan", 2, int(B), int(S), int(G), int(h), int(Dk), int(Dv), int(S_cmp), int(S_sel), int(S_kv), int(n_top),
                       _DT[dtype], int(t_max))
     return dict(zip(("launches", "form"), ints))
@@ -308,7 +309,8 @@ def selection_decode_ragged(Q: torch.Tensor, K_cmp: torch.Tensor, K: torch.Tenso
     host integers (a sequence or a CPU tensor), copied to the device without blocking, with t_max defaulting to max + S - 1.
     A sequence with t_pos[b] < 0 or t_pos[b] + S - 1 > min(t_max, S_kv - 1) is inactive: it reads nothing and its O and ranges rows are
     zeros (the padding slot of a serving batch).
-    Where the native call declines (selection_decode_ragged_plan: launches 0) host positions run one selection_decode_rows call per active
+    Where the native call declines (selection_decode_ragged_plan: launches 0 -- a t_max beyond the unsplit forms unless the tuning switch
+    DECODE_LONG = 1 lets the long-row form take it, up to t_max = 131,071) host positions run one selection_decode_rows call per active
     sequence on that sequence's views (same ranges, O from that route); device positions raise RuntimeError with the library's message.
     Returns (O [B,S,G,h,Dv], ranges [B,S,G,n_top,2] int32).  Inference only."""
     who = "selection_decode_ragged"
@@ -357,7 +359,7 @@ PAGE_TOKENS = 1024  # tokens per cache page of the paged decode step: one scorer
 def selection_decode_paged_plan(B: int, S: int, G: int, h: int, Dk: int, Dv: int, S_cmp: int, S_sel: int, max_pages: int, n_top: int, t_max: int,
                                 dtype: torch.dtype = torch.bfloat16, page_tokens: int = PAGE_TOKENS) -> dict:
     """What selection_decode_paged does with a shape whose largest live row sits at t_max (nsa_sel_decode_paged_plan): the plan of
-    selection_decode_ragged_plan for a capacity of max_pages * 1024 tokens -- {"launches": 1, "form": 0 / 1}, or {"launches": 0,
+    selection_decode_ragged_plan for a capacity of max_pages * 1024 tokens -- {"launches": 1, "form": 0 / 1 / 3}, or {"launches": 0,
     "form": -1} where the call declines (a shape the ragged call declines, or a page size other than 1024)."""
     ints = _plan_ints("nsa_sel_decode_paged_plan", 2, int(B), int(S), int(G), int(h), int(Dk), int(Dv), int(S_cmp), int(S_sel), int(max_pages),
                       int(page_tokens), int(n_top), _DT[dtype], int(t_max))
@@ -387,7 +389,7 @@ def selection_decode_paged(Q: torch.Tensor, Kc_pool: torch.Tensor, K_pool: torch
     min(t_max, capacity - 1)) or when one of the table entries it needs, j = 0 .. (t_pos[b] + S - 1) >> 10, lies outside [0, n_pages).
     For a table that scatters contiguous caches into pages the result is selection_decode_ragged's on those caches bit for bit.
     There is no per-sequence fallback: the contiguous operators cannot read a pool, so a declined shape (selection_decode_paged_plan:
-    launches 0) raises RuntimeError with the library's message.  Returns (O [B,S,G,h,Dv], ranges [B,S,G,n_top,2] int32).  Inference only."""
+    launches 0; a t_max beyond the unsplit forms is one unless the tuning switch DECODE_LONG = 1, which reaches t_max = 131,071) raises RuntimeError with the library's message.  Returns (O [B,S,G,h,Dv], ranges [B,S,G,n_top,2] int32).  Inference only."""
     who = "selection_decode_paged"
     if Q.dim() != 5:
         raise RuntimeError(f"{who}: expected Q[B,S,G,h,Dk]")
