@@ -413,6 +413,63 @@ static void run_proj(const std::string &label, const std::function<int()> &call)
     });
 }
 
+// ---- the tail of a layer decode call (step, rows, ragged, paged): calls `call` once more, every launch let through, and returns the members
+// "finish" (DecodeFinishParams of the decode_finish launch), "gate" (GateCombineParams of the gate_combine launch) and "out" (the output
+// projection: the last launch of the linear_small family, read as run_proj reads it), each null without its launch.  The launchers' names
+// are those of the walk before it (g_names), so it goes behind a run() of the same call or into its `after`.
+static std::string tail_fields(const std::function<int()> &call) {
+    struct RowsArg { const void *A, *norm_w; float eps; };
+    struct MixArg { const void *Oc, *Os, *Ow, *gates; int G; };
+    struct EpiArg { const void *out, *res; int epi, N; };
+    struct MfmaMixArg { const void *Os, *Ow, *gates; int G; };
+    std::string fin = "null", gate = "null", out = "null";
+    g_on_launch = [&](int i, const void *, void **a) {
+        auto get = [&](int k, auto v) {
+            memcpy(&v, a[k], sizeof(v));
+            return v;
+        };
+        const std::string name = i < (int)g_names.size() ? g_names[i] : "";
+        if (name == "decode_finish launch") {
+            const nsa::DecodeFinishParams P = get(0, nsa::DecodeFinishParams{});
+            Obj o;
+            o.raw("ns", "[" + std::to_string(P.ns[0]) + ", " + std::to_string(P.ns[1]) + ", " + std::to_string(P.ns[2]) + "]");
+            o.raw("part", list({where(P.part[0]), where(P.part[1]), where(P.part[2])})).raw("O", list({where(P.O[0]), where(P.O[1]), where(P.O[2])}));
+            fin = o.i("R", P.R).p("Q", P.Q).p("O_out", P.O_out).p("gates_out", P.gates_out).p("w1", P.w1).p("b1", P.b1).p("w2", P.w2).p("b2", P.b2)
+                      .i("h", P.h).i("Dk", P.Dk).i("Dv", P.Dv).i("Hd", P.Hd).f("tau", P.tau).str();
+        } else if (name == "gate_combine launch") {
+            const nsa::GateCombineParams P = get(0, nsa::GateCombineParams{});
+            gate = Obj().raw("O", list({where(P.O_cmp), where(P.O_sel), where(P.O_win)})).i("R", P.R).p("Q", P.Q).p("O_out", P.O_out).p("gates_out", P.gates_out)
+                       .p("w1", P.w1).p("b1", P.b1).p("w2", P.w2).p("b2", P.b2).i("h", P.h).i("Dk", P.Dk).i("Dv", P.Dv).i("Hd", P.Hd).f("tau", P.tau).str();
+        } else if (name.rfind("linear_small", 0) == 0) {
+            const bool mix = name == "linear_small_mix launch";
+            const bool mfma = name.find("mfma") != std::string::npos || (mix && where(get(1, (const void *)nullptr)).rfind("W_", 0) != 0);
+            Obj e;
+            e.i("launch", i);
+            const int m0 = mfma ? 4 : 2;  // M, N, K
+            if (mfma) {
+                const MfmaMixArg x = get(9, MfmaMixArg{});
+                e.p("A", get(1, (const void *)nullptr)).p("W", get(2, (const void *)nullptr));
+                if (mix) e.p("Os", x.Os).p("Ow", x.Ow).p("gates", x.gates).i("G", x.G);
+                e.p("out", get(3, (const void *)nullptr)).i("epi", get(7, 0)).p("res", get(8, (const void *)nullptr));
+            } else if (mix) {
+                const MixArg x = get(0, MixArg{});
+                const EpiArg y = get(5, EpiArg{});
+                e.p("A", x.Oc).p("W", get(1, (const void *)nullptr)).p("Os", x.Os).p("Ow", x.Ow).p("gates", x.gates).i("G", x.G).p("out", y.out).i("epi", y.epi).p("res", y.res);
+            } else {
+                const RowsArg x = get(0, RowsArg{});
+                const EpiArg y = get(5, EpiArg{});
+                e.p("A", x.A).p("norm_w", x.norm_w).p("W", get(1, (const void *)nullptr)).p("out", y.out).i("epi", y.epi).p("res", y.res);
+            }
+            out = e.i("M", get(m0, 0)).i("N", get(m0 + 1, 0)).i("K", get(m0 + 2, 0)).str();
+        }
+    };
+    g_refuse_at = -1;
+    g_launches = 0;
+    const int rc = call();
+    g_on_launch = nullptr;
+    return "\"tail_rc\": " + std::to_string(rc) + ", \"finish\": " + fin + ", \"gate\": " + gate + ", \"out\": " + out;
+}
+
 // ---- dispatch_check <library> ragged: the entry points with per-sequence positions (nsa_sel_decode_ragged, nsa_band_attn_fwd_ragged), cases
 // of their own so that the default output keeps its cases and members.  The position array is a device pointer the host must never read: it
 // is handed over as an address inside a named buffer and shows up again in the argument block of the launch.
@@ -739,6 +796,7 @@ static void layer_ragged_cases(bool long_mode = false) {  // long_mode: the laye
         cache[i] = dev(MB);
         g_named.push_back({cname[i], cache[i], MB});
     }
+    g_named.push_back({"gate_w", gw, MB});
     auto fn = NSA_FN(nsa_layer_decode_ragged);
     auto plan_fn = NSA_FN(nsa_layer_decode_ragged_plan);
     auto ws_fn = NSA_FN(nsa_layer_decode_ragged_workspace);
@@ -746,6 +804,7 @@ static void layer_ragged_cases(bool long_mode = false) {  // long_mode: the laye
         int B = 3, S = 8, D = 64, dim = 768, S_max = 1072, t_max = 1059, dtype = NSA_DT_BF16;
         const int32_t *t_pos = nullptr;
         bool with_ws = true;
+        int K_cmp_off = 0, K_sel_off = 0, n_cmp_short = 0 /* 1: n_cmp_max one short of n_cmp(te + 1) */, S_sel_short = 0;
     };
     auto positions = [](const char *launcher, int arg, size_t bytes, const char *key, std::function<std::string(const void *)> print) {
         return Want{std::string(launcher) + " launch", arg, bytes, key, std::move(print)};
@@ -791,10 +850,16 @@ static void layer_ragged_cases(bool long_mode = false) {  // long_mode: the laye
         kv.K_sel = cache[0]; kv.V_sel = cache[1]; kv.K_win = cache[2]; kv.V_win = cache[3]; kv.K_raw = cache[4]; kv.V_raw = cache[5]; kv.K_cmp = cache[6];
         kv.V_cmp = cache[7];
         kv.B = c.B; kv.S_max = c.S_max; kv.n_cmp_max = (c.S_max - 32) / 16 + 1;
-        const int te = c.t_max < c.S_max - 1 ? c.t_max : c.S_max - 1, S_sel = (te + 64) / 64;
-        run_args(std::string("layer_decode_ragged/") + label, [&] {
+        const int te = c.t_max < c.S_max - 1 ? c.t_max : c.S_max - 1, S_sel = (te + 64) / 64 - c.S_sel_short;
+        kv.K_cmp = off(kv.K_cmp, c.K_cmp_off); kv.K_sel = off(kv.K_sel, c.K_sel_off);
+        if (c.n_cmp_short) kv.n_cmp_max = (te + 1 - 32) / 16 + 1 - 1;
+        const std::function<int()> call = [&] {
             return fn(&L, &kv, x, y, c.t_pos, c.t_max, c.S, nullptr, nullptr, nullptr, S_sel, ranges, gates, c.with_ws ? ws : nullptr, c.with_ws ? 64 * MB : 0, nullptr);
-        }, wants);
+        };
+        run_args(std::string("layer_decode_ragged/") + label, call, wants);
+        g_refuse_at = -1;
+        if (call() == NSA_OK)  // the tail of a call that runs: a member of its own, behind the members the case had before
+            printf(",\n%s: {%s}", quoted(std::string("layer_decode_ragged/") + label + "_tail").c_str(), tail_fields(call).c_str());
         int launches = -7, route = -7;
         const int prc = plan_fn(&L, c.B, c.S, c.S_max, c.t_max, S_sel, &launches, &route);
         printf(",\n%s: %s", quoted(std::string("layer_decode_ragged/") + label + "_plan").c_str(),
@@ -829,6 +894,19 @@ static void layer_ragged_cases(bool long_mode = false) {  // long_mode: the laye
     NSA_FN(nsa_hip_set_tuning)("DECODE_UNFUSED", 1);
     layer_case("DECODE_UNFUSED_1_declined", [](Case &) {});
     NSA_FN(nsa_hip_set_tuning)("DECODE_UNFUSED", -1);
+    // the declines nothing above walks
+    layer_case("K_cmp_2_bytes_off", [](Case &c) { c.K_cmp_off = 2; });
+    layer_case("K_sel_2_bytes_off", [](Case &c) { c.K_sel_off = 2; });
+    layer_case("n_cmp_max_one_short", [](Case &c) { c.n_cmp_short = 1; });
+    layer_case("S_sel_one_short", [](Case &c) { c.S_sel_short = 1; });
+    layer_case("D96_declined", [](Case &c) { c.D = 96; });
+    layer_case("B0", [](Case &c) { c.B = 0; });
+    layer_case("t_max_minus_1", [](Case &c) { c.t_max = -1; });
+    // two defects at once: which message wins (the order of the checks is behaviour)
+    layer_case("S17_and_null_t_pos", [](Case &c) { c.S = 17; c.t_pos = nullptr; });
+    layer_case("f32_and_S_sel_one_short", [](Case &c) { c.dtype = NSA_DT_F32; c.S_sel_short = 1; });
+    layer_case("t_max70000_declined_and_no_workspace", [](Case &c) { c.S_max = 131072; c.t_max = 70000; c.with_ws = false; });
+    layer_case("K_cmp_2_bytes_off_and_no_workspace", [](Case &c) { c.K_cmp_off = 2; c.with_ws = false; });
 }
 
 // ---- dispatch_check <library> layer_paged: the layer's paged call (nsa_layer_decode_paged), cases of their own like `layer_ragged`.  Every
@@ -849,6 +927,7 @@ static void layer_paged_cases(bool long_mode = false) {  // long_mode: as layer_
         pool[i] = dev(MB, 0x7f);
         g_named.push_back({pname[i], pool[i], MB});
     }
+    g_named.push_back({"gate_w", gw, MB});
     auto fn = NSA_FN(nsa_layer_decode_paged);
     auto plan_fn = NSA_FN(nsa_layer_decode_paged_plan);
     auto ws_fn = NSA_FN(nsa_layer_decode_paged_workspace);
@@ -858,6 +937,7 @@ static void layer_paged_cases(bool long_mode = false) {  // long_mode: as layer_
         const int32_t *t_pos = nullptr, *table = nullptr;
         void *K_win = nullptr;
         bool with_ws = true;
+        int S_sel_short = 0;
     };
     auto block = [](const char *launcher, int arg, size_t bytes, const char *key, std::function<std::string(const void *)> print) {
         return Want{std::string(launcher) + " launch", arg, bytes, key, std::move(print)};
@@ -926,10 +1006,14 @@ static void layer_paged_cases(bool long_mode = false) {  // long_mode: as layer_
         kv.table_stride = c.table_stride ? c.table_stride : c.max_pages + 3;
         kv.n_pages = c.n_pages; kv.B = c.B; kv.max_pages = c.max_pages;
         const long long cap = (long long)c.max_pages * 1024;
-        const int te = c.t_max < cap - 1 ? c.t_max : (int)(cap - 1 > 0 ? cap - 1 : 0), S_sel = (te + 64) / 64;
-        run_args(std::string("layer_decode_paged/") + label, [&] {
+        const int te = c.t_max < cap - 1 ? c.t_max : (int)(cap - 1 > 0 ? cap - 1 : 0), S_sel = (te + 64) / 64 - c.S_sel_short;
+        const std::function<int()> call = [&] {
             return fn(&L, &kv, x, y, c.t_pos, c.t_max, c.S, nullptr, nullptr, nullptr, S_sel, ranges, gates, c.with_ws ? ws : nullptr, c.with_ws ? 128 * MB : 0, nullptr);
-        }, wants);
+        };
+        run_args(std::string("layer_decode_paged/") + label, call, wants);
+        g_refuse_at = -1;
+        if (call() == NSA_OK)  // the tail of a call that runs: a member of its own, behind the members the case had before
+            printf(",\n%s: {%s}", quoted(std::string("layer_decode_paged/") + label + "_tail").c_str(), tail_fields(call).c_str());
         int launches = -7, route = -7;
         const int prc = plan_fn(&L, c.B, c.S, c.max_pages, c.t_max, S_sel, &launches, &route);
         printf(",\n%s: %s", quoted(std::string("layer_decode_paged/") + label + "_plan").c_str(),
@@ -977,6 +1061,16 @@ static void layer_paged_cases(bool long_mode = false) {  // long_mode: as layer_
     NSA_FN(nsa_hip_set_tuning)("DECODE_UNFUSED", 1);
     layer_case("DECODE_UNFUSED_1_declined", [](Case &) {});
     NSA_FN(nsa_hip_set_tuning)("DECODE_UNFUSED", -1);
+    // the declines nothing above walks
+    layer_case("S_sel_one_short", [](Case &c) { c.S_sel_short = 1; });
+    layer_case("B0", [](Case &c) { c.B = 0; });
+    layer_case("t_max_minus_1", [](Case &c) { c.t_max = -1; });
+    // two defects at once: which message wins (the order of the checks is behaviour)
+    layer_case("table_stride_below_max_pages_and_f32", [](Case &c) { c.table_stride = 1; c.dtype = NSA_DT_F32; });
+    layer_case("table_stride_below_max_pages_and_max_pages0", [](Case &c) { c.table_stride = -1; c.max_pages = 0; });
+    layer_case("K_win_2_bytes_off_and_t_max70000_declined", [&](Case &c) { c.K_win = off(pool[2], 2); c.max_pages = 128; c.t_max = 70000; });
+    layer_case("K_win_2_bytes_off_and_no_workspace", [&](Case &c) { c.K_win = off(pool[2], 2); c.with_ws = false; });
+    layer_case("null_table_and_S17", [](Case &c) { c.table = nullptr; c.S = 17; });
 }
 
 int main(int argc, char **argv) {
@@ -1617,6 +1711,42 @@ int main(int argc, char **argv) {
     L.Dk = L.Dv = 128;
     run_args("layer_decode_step/D128_t100_DECODE_STEP_0_attention", [&] { set_tuning("DECODE_STEP", 0); const int rc = decode(100); set_tuning("DECODE_STEP", 1); return rc; }, attn_blocks);
     L.Dk = L.Dv = 64;
+
+    // ---- the step and the rows call: a compressed cache one token short (the step refuses it behind its first launch, the rows call before
+    // any), and the tail blocks of every form of the two that runs (tail_fields)
+    kv.n_cmp_max = ncmp(101) - 1;
+    run("layer_decode_step/t100_n_cmp_max_one_short", [&] { return decode(100); });
+    run("layer_decode_rows/t100_S4_n_cmp_max_one_short", [&] { return layer_rows(100, 4); });
+    kv.n_cmp_max = 63;
+    g_named.insert(g_named.end(), {{"gate_w1", L.gate_w1, MB}, {"gate_b1", L.gate_b1, MB}, {"gate_w2", L.gate_w2, MB}, {"gate_b2", L.gate_b2, MB}});
+    auto tail = [&](const std::string &label, const std::function<int()> &call) {
+        run((label + "_tail").c_str(), call, [&] { return tail_fields(call); });
+    };
+    for (int D_ : {64, 128}) {
+        L.Dk = L.Dv = D_;
+        const std::string at = D_ == 128 ? "D128_" : "";
+        tail("layer_decode_step/" + at + "t100", [&] { return decode(100); });
+        tail("layer_decode_rows/" + at + "t100_S4", [&] { return layer_rows(100, 4); });
+    }
+    L.Dk = L.Dv = 64;
+    tail("layer_decode_step/t31_first_compressed_token", [&] { return decode(31); });
+    tail("layer_decode_step/t5_no_compressed_token", [&] { return decode(5); });
+    tail("layer_decode_rows/t100_S1", [&] { return layer_rows(100, 1); });
+    tail("layer_decode_rows/t30_S4_pooling", [&] { return layer_rows(30, 4); });
+    for (int band : {0, 1}) {
+        set_tuning("DECODE_BAND", band);
+        tail("layer_decode_step/t100_DECODE_BAND_" + std::to_string(band), [&] { return decode(100); });
+    }
+    set_tuning("DECODE_BAND", -1);
+    set_tuning("DECODE_STEP", 0);
+    tail("layer_decode_step/t100_DECODE_STEP_0", [&] { return decode(100); });
+    set_tuning("DECODE_STEP", 1);
+    set_tuning("DECODE_ROWS", 0);
+    tail("layer_decode_rows/t100_S4_DECODE_ROWS_0", [&] { return layer_rows(100, 4); });
+    set_tuning("DECODE_ROWS", -1);
+    for (int B_ : {2, 32, 33}) tail("layer_decode_step/B" + std::to_string(B_) + "_t100", [&] { kv.B = B_; return decode(100); });
+    tail("layer_decode_rows/B2_t100_S2", [&] { kv.B = 2; return layer_rows(100, 2); });
+    kv.B = 1;
     printf("\n}\n");
     return 0;
 }

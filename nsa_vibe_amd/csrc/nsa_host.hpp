@@ -134,6 +134,17 @@ inline RopeAppendParams rope_append_params(const nsa_layer_desc *L, const nsa_kv
     return P;
 }
 
+// pooling of the compressed tokens of B sequences: raw caches [B G, S_max, D] -> compressed caches [B G, n_cmp_max, D] (the backward passes
+// no caches: its gradients go beside the block).  The caller adds the tokens: j0 / j1, or the position array of the ragged forms
+inline CmpPoolParams cmp_pool_params(const nsa_layer_desc *L, int B, const void *K_raw, const void *V_raw, void *K_cmp, void *V_cmp, int S_max, int n_cmp_max) {
+    CmpPoolParams P{};
+    P.K_raw = K_raw; P.V_raw = V_raw; P.K_cmp = K_cmp; P.V_cmp = V_cmp;
+    P.nbg = B * L->G; P.S_max = S_max; P.n_cmp_max = n_cmp_max; P.Dk = L->Dk; P.Dv = L->Dv; P.l = L->l; P.d = L->d;
+    P.rope_base = L->rope_base > 0.f ? L->rope_base : 10000.0f;
+    P.inv_scale = 1.0f;  // the reference pools apply_rope(K_raw, pos) WITHOUT the NSA_ROPE_SCALE position scaling (compress_pool.py:20)
+    return P;
+}
+
 // columns of the fused QKV projection: Q | K_sel | V_sel | K_win | V_win | K_raw | V_raw
 inline int qkv_cols(const nsa_layer_desc *L) { return L->G * L->h * L->Dk + 3 * L->G * L->Dk + 3 * L->G * L->Dv; }
 // that projection of `rows` rows of x as the projection family's block (no out: the launch's RopeAppendParams say where each column goes).

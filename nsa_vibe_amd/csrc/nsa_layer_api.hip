@@ -66,12 +66,8 @@ int nsa_cmp_pool_append(const nsa_layer_desc *L, const nsa_kv_desc *kv, int j0, 
     if (int rc = check_kv(kv, "cmp_pool_append")) return rc;
     NSA_CHECK_ARG(j0 >= 0 && j1 >= j0 && j1 <= kv->n_cmp_max, "cmp_pool_append: tokens [%d,%d) exceed n_cmp_max %d", j0, j1, kv->n_cmp_max);
     NSA_CHECK_ARG(j1 == j0 || (int64_t)(j1 - 1) * L->d + L->l <= kv->S_max, "cmp_pool_append: window past the cache capacity");
-    CmpPoolParams P{};
-    P.K_raw = kv->K_raw; P.V_raw = kv->V_raw; P.K_cmp = kv->K_cmp; P.V_cmp = kv->V_cmp;
-    P.nbg = kv->B * L->G; P.S_max = kv->S_max; P.n_cmp_max = kv->n_cmp_max; P.Dk = L->Dk; P.Dv = L->Dv; P.l = L->l; P.d = L->d;
+    CmpPoolParams P = cmp_pool_params(L, kv->B, kv->K_raw, kv->V_raw, kv->K_cmp, kv->V_cmp, kv->S_max, kv->n_cmp_max);
     P.j0 = j0; P.j1 = j1;
-    P.rope_base = L->rope_base > 0.f ? L->rope_base : 10000.0f;
-    P.inv_scale = 1.0f;  // the reference pools apply_rope(K_raw, pos) WITHOUT the NSA_ROPE_SCALE position scaling (compress_pool.py:20)
     return launch_cmp_pool(P, L->dtype, (hipStream_t)stream);
 }
 
@@ -109,10 +105,7 @@ int nsa_cmp_pool_bwd(const nsa_layer_desc *L, int B, int S, int n_cmp, const voi
     if (B == 0 || S == 0) return NSA_OK;
     NSA_CHECK_ARG(dK_raw && dV_raw && ((dK_cmp && dV_cmp) || n_cmp == 0), "cmp_pool_bwd: null pointer");
     NSA_CHECK_ARG(n_cmp == 0 || (int64_t)(n_cmp - 1) * L->d + L->l <= S, "cmp_pool_bwd: windows reach past S");
-    CmpPoolParams P{};
-    P.nbg = B * L->G; P.Dk = L->Dk; P.Dv = L->Dv; P.l = L->l; P.d = L->d;
-    P.rope_base = L->rope_base > 0.f ? L->rope_base : 10000.0f;
-    P.inv_scale = 1.0f;  // as the forward: no position scaling inside the pooled keys (compress_pool.py:20)
+    const CmpPoolParams P = cmp_pool_params(L, B, nullptr, nullptr, nullptr, nullptr, 0, 0);  // (the geometry and the rotation alone)
     return launch_cmp_pool_bwd(P, dK_cmp, dV_cmp, dK_raw, dV_raw, S, n_cmp, L->dtype, (hipStream_t)stream);
 }
 
@@ -294,25 +287,91 @@ struct LayerDecode {
 };
 constexpr int LAYER_ROWS_MAX_S = 16;
 
+// the call at a scalar position: rows t0 .. t0 + S - 1 of every sequence, its pieces carved from the (checked) workspace
+static LayerDecode layer_decode_at(const nsa_layer_desc *L, const nsa_kv_desc *kv, const DecodeWs &W, void *workspace, int S, int t0) {
+    LayerDecode D{};
+    D.L = L; D.kv = kv; D.W = W; D.ws = (unsigned char *)workspace;
+    D.Q = D.ws + W.q; D.Ocmp = D.ws + W.ocmp; D.Osel = D.ws + W.osel; D.Owin = D.ws + W.owin; D.Omix = D.ws + W.omix;
+    D.S = S; D.t0 = t0; D.n0 = ncmp_of(t0, L->l, L->d); D.n1 = ncmp_of(t0 + S, L->l, L->d);
+    return D;
+}
+
+// What a call with a position array plans its launches from, and what its route answers: the largest sequence there can be (LayerDecode;
+// check_bound derives it) and the launches -- 0 and why where the shape is declined
+struct PositionsPlan {
+    int te, t0, n1, launches;
+    const char *why;
+};
+// the call at the positions t_pos (pg: through a block table), planned as p says
+static LayerDecode layer_decode_positions(const nsa_layer_desc *L, const nsa_kv_desc *kv, const DecodeWs &W, void *workspace, int S,
+                                          const PositionsPlan &p, const int32_t *t_pos, const LayerPageTable *pg = nullptr) {
+    LayerDecode D = layer_decode_at(L, kv, W, workspace, S, p.t0);
+    D.n0 = 0; D.n1 = p.n1; D.t_pos = t_pos; D.te = p.te; D.pg = pg;
+    return D;
+}
+
+// ---- what the calls of the family check alike.  x, y and the projections' weights; with a device position array (never read on the host)
+static int check_io(const char *who, const nsa_layer_desc *L, const void *x, const void *y) {
+    NSA_CHECK_ARG(x && y && L->W_qkv && L->W_out, "%s: null pointer", who);
+    return NSA_OK;
+}
+static int check_io(const char *who, const nsa_layer_desc *L, const void *x, const void *y, const int32_t *t_pos) {
+    if (int rc = check_io(who, L, x, y)) return rc;
+    NSA_CHECK_ARG(t_pos, "%s: null position array t_pos", who);
+    NSA_CHECK_ARG((uintptr_t)t_pos % 4 == 0, "%s: t_pos must be 4-byte aligned", who);
+    return NSA_OK;
+}
+static int check_rows_count(const char *who, int S) {
+    NSA_CHECK_ARG(S >= 1 && S <= LAYER_ROWS_MAX_S, "%s: 1 to %d tokens per sequence (got %d)", who, LAYER_ROWS_MAX_S, S);
+    return NSA_OK;
+}
+// the host bound of a position array over caches of `cap` tokens and the block metadata: *p = the planned sequence
+static int check_bound(const char *who, const nsa_layer_desc *L, int S, int cap, int t_max, int S_sel, PositionsPlan *p) {
+    NSA_CHECK_ARG(t_max >= 0, "%s: t_max (the host bound of t_pos[b] + S - 1) must not be negative", who);
+    p->te = std::min(t_max, cap - 1);  // no live row sits beyond te
+    p->t0 = std::max(0, p->te + 1 - S);
+    p->n1 = ncmp_of(p->te + 1, L->l, L->d);
+    NSA_CHECK_ARG(S_sel >= 1 && (int64_t)S_sel * L->l_sel >= (int64_t)p->te + 1, "%s: block metadata (S_sel=%d) does not cover %d tokens", who, S_sel,
+                  p->te + 1);
+    return NSA_OK;
+}
+// what every launch with per-sequence positions asks of the layer (each route names the limit in its own words)
+static bool dtype_16bit(int dt) { return dt == NSA_DT_BF16 || dt == NSA_DT_F16; }
+static bool default_decode_geometry(const nsa_layer_desc *L) {
+    return L->Dk == L->Dv && (L->Dk == 64 || L->Dk == 128) && L->l == 32 && L->d == 16 && L->l_sel == 64;
+}
+// stands in for aligned caches in a route: its predicates read the sizes and the pointers' alignment only
+static nsa_kv_desc stand_in_kv(int B, int S_max, int n_cmp_max) {
+    nsa_kv_desc kv{};
+    kv.K_sel = kv.V_sel = kv.K_win = kv.V_win = kv.K_raw = kv.V_raw = kv.K_cmp = kv.V_cmp = (void *)(uintptr_t)256;
+    kv.B = B; kv.S_max = S_max; kv.n_cmp_max = n_cmp_max;
+    return kv;
+}
+// a plan query's answer from its route's: (0, -1) for bad arguments (with the status) and for a declined shape, else (launches, 1)
+static int plan_answer(int rc, const PositionsPlan &p, int *launches, int *route) {
+    *launches = p.launches;  // (set behind the route's last check alone)
+    *route = p.launches ? 1 : -1;
+    return rc;
+}
+
 // rows = false: the single step at token t0 (S = 1, its own wording of the position checks, the workspace of one row per sequence)
 static int layer_decode_begin(const char *who, const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *x, void *y, int t0, int S, bool rows,
                               int S_sel, void *workspace, size_t workspace_bytes, LayerDecode *D) {
     if (int rc = check_layer(L, who)) return rc;
     if (int rc = check_kv(kv, who)) return rc;
-    NSA_CHECK_ARG(x && y && L->W_qkv && L->W_out, "%s: null pointer", who);
+    if (int rc = check_io(who, L, x, y)) return rc;
     if (!rows) {
         NSA_CHECK_ARG(t0 >= 0 && t0 < kv->S_max, "%s: position %d outside the cache capacity %d", who, t0, kv->S_max);
         NSA_CHECK_ARG(S_sel >= 1 && (int64_t)S_sel * L->l_sel >= t0 + 1, "%s: block metadata (S_sel=%d) does not cover token %d", who, S_sel, t0);
     } else {
-        NSA_CHECK_ARG(S >= 1 && S <= LAYER_ROWS_MAX_S, "%s: 1 to %d tokens per sequence (got %d)", who, LAYER_ROWS_MAX_S, S);
+        if (int rc = check_rows_count(who, S)) return rc;
         NSA_CHECK_ARG(t0 >= 0 && (int64_t)t0 + S <= kv->S_max, "%s: tokens [%d,%d) exceed the cache capacity %d", who, t0, t0 + S, kv->S_max);
         NSA_CHECK_ARG(S_sel >= 1 && (int64_t)S_sel * L->l_sel >= (int64_t)t0 + S, "%s: block metadata (S_sel=%d) does not cover %d tokens", who, S_sel,
                       t0 + S);
     }
     const DecodeWs W = decode_ws(L, kv->B, kv->S_max, rows ? S : 0);
     if (int rc = check_workspace(who, workspace, workspace_bytes, W.total)) return rc;
-    unsigned char *ws = (unsigned char *)workspace;
-    *D = LayerDecode{L, kv, W, ws, ws + W.q, ws + W.ocmp, ws + W.osel, ws + W.owin, ws + W.omix, S, t0, ncmp_of(t0, L->l, L->d), ncmp_of(t0 + S, L->l, L->d)};
+    *D = layer_decode_at(L, kv, W, workspace, S, t0);
     return NSA_OK;
 }
 
@@ -327,16 +386,28 @@ static BandBranches band_branches(const LayerDecode &D, const CacheStrides &C, v
                         compressed_call(D.L, D.kv, C, D.Q, D.Ocmp, D.S, D.n1, D.ws + D.W.band2, D.W.band_bytes, stream), sliding_band(D.t0, D.L->w),
                         compressed_band(D.t0, D.L->l, D.L->d)};
 }
-// Both as ONE launch (launch_band_attn_fwd_dual, or riding on the selected branch's): both in split form with the combine left to the finish
-// kernel (defer: Dv = 64); BP gets their blocks.  (The whole-cache bound is this launch's own: stricter than the slab bound of the route.)
-static bool band_pair(const LayerDecode &D, const CacheStrides &C, int defer, DecBandPair &BP) {
+// When the finish kernel can take split-KV partial records (Dv = 64) the branches skip their own combine kernels: one kernel then merges the
+// splits of all branches, evaluates the gate and mixes
+static int finish_defers(const nsa_layer_desc *L) { return L->Dv == 64 ? 1 : 0; }
+// Whether both run as ONE launch (launch_band_attn_fwd_dual, or riding on the selected branch's), both in split form with the combine left to
+// the finish kernel: their common split count, 0 for a launch each.  The shape, the strides and the caches' alignment decide -- Q and the
+// outputs lie in the 256-byte aligned workspace.  (The whole-cache bound is this launch's own: stricter than the slab bound of the route.)
+static int band_pair_splits(const nsa_layer_desc *L, const nsa_kv_desc *kv, const CacheStrides &C, int S, int t0, int tokens, int n1) {
+    void *const in_ws = (void *)(uintptr_t)256;
+    const AttnRoute rw = band_attn_route(sliding_call(L, kv, C, in_ws, in_ws, S, tokens, nullptr, 0, nullptr), sliding_band(t0, L->w));
+    const AttnRoute rc = band_attn_route(compressed_call(L, kv, C, in_ws, in_ws, S, n1, nullptr, 0, nullptr), compressed_band(t0, L->l, L->d));
+    const bool one = finish_defers(L) && rw.nsplit > 1 && rw.fast_ok && rc.fast_ok && C.ksb * 2 < ((int64_t)1 << 31) && C.vsb * 2 < ((int64_t)1 << 31);
+    return one ? rw.nsplit : 0;
+}
+// the pair of a call that runs: BP gets the blocks of both branches
+static bool band_pair(const LayerDecode &D, const CacheStrides &C, DecBandPair &BP) {
+    const int nsplit = band_pair_splits(D.L, D.kv, C, D.S, D.t0, D.tokens(), D.n1);
+    if (!nsplit) return false;
     const BandBranches b = band_branches(D, C, nullptr);
-    const AttnRoute rw = band_attn_route(b.w, b.bw), rc = band_attn_route(b.c, b.bc);
-    if (!(defer && rw.nsplit > 1 && rw.fast_ok && rc.fast_ok && C.ksb * 2 < ((int64_t)1 << 31) && C.vsb * 2 < ((int64_t)1 << 31))) return false;
     BP.w = band_attn_params(b.w, b.bw);
     BP.c = band_attn_params(b.c, b.bc);
     BP.w.part = (float *)b.w.ws; BP.c.part = (float *)b.c.ws;
-    BP.w.nsplit = BP.c.nsplit = rw.nsplit;
+    BP.w.nsplit = BP.c.nsplit = nsplit;
     BP.w.defer_combine = BP.c.defer_combine = 1;
     if (D.t_pos) {  // the ragged call: every sequence at its own position (the launch's t0 is not read)
         BP.w.t_pos = BP.c.t_pos = D.t_pos;
@@ -350,6 +421,7 @@ static bool band_pair(const LayerDecode &D, const CacheStrides &C, int defer, De
 static SelDecodeCall layer_sel_call(const LayerDecode &D, const CacheStrides &C, const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals,
                                     int S_sel, int32_t *ranges_out) {
     SelDecodeCall c = sel_decode_call(D.L, D.kv, C, D.S, D.t0, D.n1, S_sel);
+    if (D.t_pos) c.t0 = 0;  // as nsa_sel_decode_ragged / _paged hand it over: every row's token comes from the position array
     c.Q = D.Q; c.csc_ptr = csc_ptr; c.csc_rows = csc_rows; c.csc_vals = csc_vals; c.O = D.Osel;
     c.ranges_out = ranges_out ? ranges_out : (int32_t *)(D.ws + D.W.ranges);
     return c;
@@ -369,6 +441,7 @@ static DecodeFinishParams decode_finish_params(const LayerDecode &D, float *gate
     F.w1 = L->gate_w1; F.b1 = L->gate_b1; F.w2 = L->gate_w2; F.b2 = L->gate_b2;
     F.R = (int64_t)D.kv->B * D.S * L->G; F.h = L->h; F.Dk = L->Dk; F.Dv = L->Dv; F.Hd = L->gate_hidden; F.tau = L->gate_tau;
     F.O[0] = D.Ocmp; F.O[1] = D.Osel; F.O[2] = D.Owin;
+    F.ns[0] = F.ns[1] = F.ns[2] = 1;  // every O final, until a branch leaves its split records instead
     return F;
 }
 
@@ -380,7 +453,7 @@ static int layer_decode_tail(const LayerDecode &D, const CacheStrides &C, Decode
     const nsa_layer_desc *L = D.L;
     const nsa_kv_desc *kv = D.kv;
     hipStream_t st = (hipStream_t)stream;
-    const int B = kv->B, S = D.S, G = L->G, dt = L->dtype, defer = L->Dv == 64 ? 1 : 0;
+    const int B = kv->B, S = D.S, G = L->G, dt = L->dtype, defer = finish_defers(L);
     if (BP) {
         if (!ridden)
             if (int rc = launch_band_attn_fwd_dual(BP->w, BP->c, dt, st)) return rc;
@@ -392,12 +465,10 @@ static int layer_decode_tail(const LayerDecode &D, const CacheStrides &C, Decode
         const BandPageTable pt{D.pg->table, D.pg->stride, D.pg->n_pages, 0};
         if (int rc = band_attn_fwd_paged_impl(b.w, b.bw, pt, D.pg->max_pages, LAYER_PAGE_TOKENS, D.t_pos, D.te)) return rc;
         if (int rc = band_attn_fwd_paged_impl(b.c, b.bc, pt, D.pg->max_pages, LAYER_PAGE_CMP, D.t_pos, D.te)) return rc;
-        F.ns[2] = F.ns[0] = 1;
     } else if (D.t_pos) {  // the ragged call: one ragged launch each, combined by the branch itself (O final)
         const BandBranches b = band_branches(D, C, stream);
         if (int rc = band_attn_fwd_ragged_impl(b.w, b.bw, D.t_pos, D.te)) return rc;
         if (int rc = band_attn_fwd_ragged_impl(b.c, b.bc, D.t_pos, D.te)) return rc;
-        F.ns[2] = F.ns[0] = 1;
     } else {
         const BandBranches b = band_branches(D, C, stream);
         if (int rc = band_attn_fwd_impl(b.w, b.bw, defer, &F.ns[2])) return rc;
@@ -411,6 +482,14 @@ static int layer_decode_tail(const LayerDecode &D, const CacheStrides &C, Decode
         if (int rc = nsa_gate_combine(L, D.Q, D.Ocmp, D.Osel, D.Owin, D.Omix, gates_out, (int64_t)B * S * G, stream)) return rc;
     }
     return launch_linear_small_epi(out_proj_call(D, y, residual, stream));
+}
+// The tail of the rows, ragged and paged calls (O_sel is final; no residual and no folded norm: the block step alone has them): the
+// pair-or-not decision is taken here, on the call's own operands.  (The paged branches have no dual launch: one paged launch each.)
+static int layer_decode_rows_tail(const LayerDecode &D, const CacheStrides &C, float *gates_out, void *y, void *stream) {
+    DecodeFinishParams F = decode_finish_params(D, gates_out);
+    DecBandPair BP{};
+    const bool dual = !D.pg && band_pair(D, C, BP);
+    return layer_decode_tail(D, C, F, dual ? &BP : nullptr, false, gates_out, y, nullptr, stream);
 }
 
 static int layer_decode_step_impl(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *x, void *y, int t, const int32_t *csc_ptr,
@@ -428,15 +507,13 @@ static int layer_decode_step_impl(const nsa_layer_desc *L, const nsa_kv_desc *kv
     if (n_cmp > D.n0)
         if (int rc = nsa_cmp_pool_append(L, kv, D.n0, n_cmp, stream)) return rc;
     const CacheStrides C(L, kv);
-    // When the final pass can take split-KV partial records (Dv = 64) the three branches skip their own combine kernels:
-    // one kernel then merges the splits of all branches, evaluates the gate and mixes.
-    const int defer = Dv == 64 ? 1 : 0;
+    const int defer = finish_defers(L);
     DecodeFinishParams F = decode_finish_params(D, gates_out);
     // 4 + 5. the three branches.  The sliding and the compressed branch run in split-KV form with the combine left to the finish kernel; when
     // the selected branch runs as the one-launch decode step they ride on ITS launch (workgroups behind the step's own: sel_decode_fused.hip),
     // otherwise they are one launch of their own.
     DecBandPair BP{};
-    const bool dual = band_pair(D, C, defer, BP);
+    const bool dual = band_pair(D, C, BP);
     const int band_mode = tuning(TUNE_DECODE_BAND);  // 0 own launch, 1 ride, 2 ride + merge in the workgroup, -1 / 3: 2 + the mix in the output projection
     const bool ride = dual && Dk == 64 && band_mode != 0;
     float *gates = gates_out ? gates_out : (float *)(D.ws + D.W.gates);
@@ -449,8 +526,7 @@ static int layer_decode_step_impl(const nsa_layer_desc *L, const nsa_kv_desc *kv
     F.part[1] = sel_part;
     if (!(dual && band_taken && BP.mg.on)) return layer_decode_tail(D, C, F, dual ? &BP : nullptr, band_taken != 0, gates_out, y, residual, stream);
     // O_win, O_cmp (merged by the workgroups that held their splits), O_sel and the row gates are final: with few rows the mix is the
-    // A operand of the output projection -- three launches per step
-    F.ns[2] = F.ns[0] = 1;
+    // A operand of the output projection -- three launches per step (F.ns stays 1 for all three)
     // (measured: the mix in the projection wins up to 32 rows -- 43.3 -> 40.5 us at B = 32 -- and loses from 64 on, where every one of the
     // projection's 48 workgroups would redo the mix of all rows: 47.1 -> 50.6 us; DECODE_BAND = 3 takes it at any batch)
     const LinearCall out = out_proj_call(D, y, residual, stream);
@@ -476,9 +552,7 @@ int nsa_layer_decode_step(const nsa_layer_desc *L, const nsa_kv_desc *kv, const 
 static bool layer_decode_rows_route(const nsa_layer_desc *L, int B, int S, int S_max, int t0, int S_sel, int *launches, int *route) {
     if (check_layer(L, "layer_decode_rows_plan")) return false;
     if (B < 1 || S < 1 || S > LAYER_ROWS_MAX_S || t0 < 0 || (int64_t)t0 + S > S_max || S_sel < 1 || (int64_t)S_sel * L->l_sel < (int64_t)t0 + S) return false;
-    nsa_kv_desc kv{};  // stands in for aligned caches: the predicates below read the sizes and the pointers' alignment only
-    kv.K_sel = kv.V_sel = kv.K_win = kv.V_win = kv.K_raw = kv.V_raw = kv.K_cmp = kv.V_cmp = (void *)(uintptr_t)256;
-    kv.B = B; kv.S_max = S_max; kv.n_cmp_max = std::max(1, ncmp_of(S_max, L->l, L->d));
+    const nsa_kv_desc kv = stand_in_kv(B, S_max, std::max(1, ncmp_of(S_max, L->l, L->d)));
     const CacheStrides C(L, &kv);
     const int n0 = ncmp_of(t0, L->l, L->d), n1 = ncmp_of(t0 + S, L->l, L->d);
     int n = 1 + (n1 > n0 ? 1 : 0);  // projection + RoPE + append, pooling
@@ -492,9 +566,8 @@ static bool layer_decode_rows_route(const nsa_layer_desc *L, int B, int S, int S
         if (nsa_sel_decode_rows_plan(B, S, L->G, L->h, L->Dk, L->Dv, n1, S_sel, t0 + S, L->n_sel, L->dtype, &nl, &form) != NSA_OK || nl < 2) nl = 3;
         n += nl;
     }
-    DecBandPair BP{};  // (an undeferred split branch adds its combine: not counted)
-    n += band_pair(LayerDecode{L, &kv, DecodeWs{}, nullptr, kv.K_sel, kv.K_sel, kv.K_sel, kv.K_sel, kv.K_sel, S, t0, n0, n1}, C, L->Dv == 64 ? 1 : 0, BP) ? 1 : 2;
-    n += 2;                                                                          // finish (or gate + mix), output projection
+    n += band_pair_splits(L, &kv, C, S, t0, t0 + S, n1) ? 1 : 2;  // (an undeferred split branch adds its combine: not counted)
+    n += 2;  // finish (or gate + mix), output projection
     *launches = n;
     *route = one ? 1 : 0;
     return true;
@@ -504,31 +577,6 @@ static bool layer_decode_rows_route(const nsa_layer_desc *L, int B, int S, int S
 // band branches ride on the selected branch's launch (three launches against five here)
 static bool layer_decode_rows_measured_ok(int B, int S, int t0) { return S >= 2; }
 
-static int layer_decode_rows_impl(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *x, void *y, int t0, int S, const int32_t *csc_ptr,
-                                  const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out, float *gates_out,
-                                  void *workspace, size_t workspace_bytes, void *stream, const void *residual, const void *norm_w,
-                                  float norm_eps) {
-    LayerDecode D;
-    if (int rc = layer_decode_begin("layer_decode_rows", L, kv, x, y, t0, S, true, S_sel, workspace, workspace_bytes, &D)) return rc;
-    NSA_CHECK_ARG(D.n1 <= kv->n_cmp_max, "layer_decode_rows: compressed cache too small");
-    // 1. fused QKV projection of the B S rows, each rotated and appended at its own position t0 + s
-    if (int rc = launch_qkv_rope_append(rope_append_params(L, kv, D.ws + D.W.proj, D.Q, S, t0), qkv_call(L, x, kv->B * S, norm_w, norm_eps, stream), true))
-        return rc;
-    // 2. the compressed tokens whose windows complete inside the call
-    if (D.n1 > D.n0)
-        if (int rc = nsa_cmp_pool_append(L, kv, D.n0, D.n1, stream)) return rc;
-    const CacheStrides C(L, kv);
-    // 3. selected branch: every row's scores -> top-n at its token -> attention over K_sel[:t + 1] (one launch, or the separate launches)
-    if (int rc = sel_decode_rows_impl(layer_sel_call(D, C, csc_ptr, csc_rows, csc_vals, S_sel, ranges_out), D.ws + D.W.sel, D.W.sel_bytes, stream)) return rc;
-    // 4. sliding and compressed branches of the S rows: one launch in split form with the combine left to the finish kernel, else one each;
-    // 5. split combine + gates + mix, 6. output projection of the B S rows
-    DecodeFinishParams F = decode_finish_params(D, gates_out);
-    F.ns[1] = 1;
-    DecBandPair BP{};
-    const bool dual = band_pair(D, C, L->Dv == 64 ? 1 : 0, BP);
-    return layer_decode_tail(D, C, F, dual ? &BP : nullptr, false, gates_out, y, residual, stream);
-}
-
 size_t nsa_layer_decode_rows_workspace(const nsa_layer_desc *L, int B, int S, int S_max) {
     if (!L || !dtype_ok(L->dtype) || B < 1 || S < 1 || S > LAYER_ROWS_MAX_S || S_max < 1) return 0;
     return decode_ws(L, B, S_max, S).total;
@@ -537,8 +585,21 @@ size_t nsa_layer_decode_rows_workspace(const nsa_layer_desc *L, int B, int S, in
 int nsa_layer_decode_rows(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *x, void *y, int t0, int S, const int32_t *csc_ptr,
                           const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out, float *gates_out, void *workspace,
                           size_t workspace_bytes, void *stream) {
-    return layer_decode_rows_impl(L, kv, x, y, t0, S, csc_ptr, csc_rows, csc_vals, S_sel, ranges_out, gates_out, workspace, workspace_bytes, stream,
-                                  nullptr, nullptr, 0.f);
+    LayerDecode D;
+    if (int rc = layer_decode_begin("layer_decode_rows", L, kv, x, y, t0, S, true, S_sel, workspace, workspace_bytes, &D)) return rc;
+    NSA_CHECK_ARG(D.n1 <= kv->n_cmp_max, "layer_decode_rows: compressed cache too small");
+    // 1. fused QKV projection of the B S rows, each rotated and appended at its own position t0 + s
+    if (int rc = launch_qkv_rope_append(rope_append_params(L, kv, D.ws + D.W.proj, D.Q, S, t0), qkv_call(L, x, kv->B * S, nullptr, 0.f, stream), true))
+        return rc;
+    // 2. the compressed tokens whose windows complete inside the call
+    if (D.n1 > D.n0)
+        if (int rc = nsa_cmp_pool_append(L, kv, D.n0, D.n1, stream)) return rc;
+    const CacheStrides C(L, kv);
+    // 3. selected branch: every row's scores -> top-n at its token -> attention over K_sel[:t + 1] (one launch, or the separate launches)
+    if (int rc = sel_decode_rows_impl(layer_sel_call(D, C, csc_ptr, csc_rows, csc_vals, S_sel, ranges_out), D.ws + D.W.sel, D.W.sel_bytes, stream)) return rc;
+    // 4. sliding and compressed branches of the S rows: one launch in split form with the combine left to the finish kernel, else one each;
+    // 5. split combine + gates + mix, 6. output projection of the B S rows (no residual, no folded norm: the block step alone has them)
+    return layer_decode_rows_tail(D, C, gates_out, y, stream);
 }
 
 int nsa_layer_decode_rows_plan(const nsa_layer_desc *L, int B, int S, int S_max, int t0, int S_sel, int *launches, int *route) {
@@ -556,43 +617,28 @@ int nsa_layer_decode_rows_plan(const nsa_layer_desc *L, int B, int S, int S_max,
 
 // ------------------------------------------------------------------------------ ragged-batch layer decode: per-sequence positions
 // What the call and its plan share, from the shape, the host bound and the switches alone (aligned caches of capacity S_max assumed; the
-// position array is never read on the host).  NSA_OK with *launches = n: the call runs; *launches = 0 and *why = the limit: DECLINED --
+// position array is never read on the host).  NSA_OK with p->launches = n: the call runs; p->launches = 0 and p->why = the limit: DECLINED --
 // there is no scalar route to stand in (every other launch of the layer takes one position per call); an error status: bad arguments.
 static int layer_decode_ragged_route(const char *who, const nsa_layer_desc *L, int B, int S, int S_max, int t_max, int S_sel, int n_cmp_max,
-                                     int *launches, const char **why) {
-    *launches = 0;
-    *why = nullptr;
+                                     PositionsPlan *p) {
+    *p = PositionsPlan{};
     if (int rc = check_layer(L, who)) return rc;
-    NSA_CHECK_ARG(S >= 1 && S <= LAYER_ROWS_MAX_S, "%s: 1 to %d tokens per sequence (got %d)", who, LAYER_ROWS_MAX_S, S);
+    if (int rc = check_rows_count(who, S)) return rc;
     NSA_CHECK_ARG(B >= 1 && S_max >= 1, "%s: bad cache sizes", who);
-    NSA_CHECK_ARG(t_max >= 0, "%s: t_max (the host bound of t_pos[b] + S - 1) must not be negative", who);
-    const int te = std::min(t_max, S_max - 1);  // no live row sits beyond te
-    NSA_CHECK_ARG(S_sel >= 1 && (int64_t)S_sel * L->l_sel >= (int64_t)te + 1, "%s: block metadata (S_sel=%d) does not cover %d tokens", who, S_sel, te + 1);
-    NSA_CHECK_ARG(n_cmp_max < 0 || n_cmp_max >= ncmp_of(te + 1, L->l, L->d), "%s: compressed cache too small (n_cmp_max=%d) for %d tokens", who, n_cmp_max,
-                  te + 1);
-    if (!(L->dtype == NSA_DT_BF16 || L->dtype == NSA_DT_F16)) {
-        *why = "bf16 / f16 only (the launches that take per-sequence positions have no fp32 form)";
-        return NSA_OK;
-    }
-    if (!(L->Dk == L->Dv && (L->Dk == 64 || L->Dk == 128) && L->l == 32 && L->d == 16 && L->l_sel == 64)) {
-        *why = "Dk = Dv in {64, 128} and the default block geometry only (l = 32, d = 16, l' = 64)";
-        return NSA_OK;
-    }
-    nsa_kv_desc kv{};  // stands in for aligned caches: the predicates below read the sizes and the pointers' alignment only
-    kv.K_sel = kv.V_sel = kv.K_win = kv.V_win = kv.K_raw = kv.V_raw = kv.K_cmp = kv.V_cmp = (void *)(uintptr_t)256;
-    kv.B = B; kv.S_max = S_max; kv.n_cmp_max = std::max(1, ncmp_of(S_max, L->l, L->d));
+    if (int rc = check_bound(who, L, S, S_max, t_max, S_sel, p)) return rc;
+    NSA_CHECK_ARG(n_cmp_max < 0 || n_cmp_max >= p->n1, "%s: compressed cache too small (n_cmp_max=%d) for %d tokens", who, n_cmp_max, p->te + 1);
+    p->why = !dtype_16bit(L->dtype)          ? "bf16 / f16 only (the launches that take per-sequence positions have no fp32 form)"
+             : !default_decode_geometry(L) ? "Dk = Dv in {64, 128} and the default block geometry only (l = 32, d = 16, l' = 64)" : nullptr;
+    if (p->why) return NSA_OK;
+    const nsa_kv_desc kv = stand_in_kv(B, S_max, std::max(1, ncmp_of(S_max, L->l, L->d)));
     const CacheStrides C(L, &kv);
-    const int t0 = std::max(0, te + 1 - S), n1 = ncmp_of(te + 1, L->l, L->d);
-    SelDecodeCall sc = sel_decode_call(L, &kv, C, S, t0, n1, S_sel);
-    sc.S_kv = te + 1;
-    if (!decode_ragged_shape_plan(sc, te, nullptr, nullptr, why)) return NSA_OK;
-    *why = nullptr;
-    DecBandPair BP{};  // (an undeferred split branch adds its combine: not counted)
-    const bool dual = band_pair(LayerDecode{L, &kv, DecodeWs{}, nullptr, kv.K_sel, kv.K_sel, kv.K_sel, kv.K_sel, kv.K_sel, S, t0, 0, n1, (const int32_t *)kv.K_sel, te}, C,
-                                L->Dv == 64 ? 1 : 0, BP);
+    SelDecodeCall sc = sel_decode_call(L, &kv, C, S, p->t0, p->n1, S_sel);
+    sc.S_kv = p->te + 1;
+    if (!decode_ragged_shape_plan(sc, p->te, nullptr, nullptr, &p->why)) return NSA_OK;
+    p->why = nullptr;
     // projection + RoPE + append, pooling (always: the host cannot know whether a window completes), the selected branch's one launch,
-    // the band pair (or one launch each), finish (or gate + mix), output projection
-    *launches = 3 + (dual ? 1 : 2) + 2;
+    // the band pair (or one launch each; an undeferred split branch adds its combine: not counted), finish (or gate + mix), output projection
+    p->launches = 3 + (band_pair_splits(L, &kv, C, S, p->t0, p->te + 1, p->n1) ? 1 : 2) + 2;
     return NSA_OK;
 }
 
@@ -600,15 +646,8 @@ size_t nsa_layer_decode_ragged_workspace(const nsa_layer_desc *L, int B, int S, 
 
 int nsa_layer_decode_ragged_plan(const nsa_layer_desc *L, int B, int S, int S_max, int t_max, int S_sel, int *launches, int *route) {
     NSA_CHECK_ARG(launches && route, "layer_decode_ragged_plan: null pointer");
-    *launches = 0;
-    *route = -1;
-    int n = 0;
-    const char *why = nullptr;
-    if (int rc = layer_decode_ragged_route("layer_decode_ragged_plan", L, B, S, S_max, t_max, S_sel, -1, &n, &why)) return rc;
-    if (why) return NSA_OK;  // declined
-    *launches = n;
-    *route = 1;
-    return NSA_OK;
+    PositionsPlan p;
+    return plan_answer(layer_decode_ragged_route("layer_decode_ragged_plan", L, B, S, S_max, t_max, S_sel, -1, &p), p, launches, route);
 }
 
 int nsa_layer_decode_ragged(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *x, void *y, const int32_t *t_pos, int t_max, int S,
@@ -617,52 +656,36 @@ int nsa_layer_decode_ragged(const nsa_layer_desc *L, const nsa_kv_desc *kv, cons
     const char *who = "layer_decode_ragged";
     if (int rc = check_layer(L, who)) return rc;
     if (int rc = check_kv(kv, who)) return rc;
-    NSA_CHECK_ARG(x && y && L->W_qkv && L->W_out, "%s: null pointer", who);
-    NSA_CHECK_ARG(t_pos, "%s: null position array t_pos", who);
-    NSA_CHECK_ARG((uintptr_t)t_pos % 4 == 0, "%s: t_pos must be 4-byte aligned", who);
-    int n = 0;
-    const char *why = nullptr;
-    if (int rc = layer_decode_ragged_route(who, L, kv->B, S, kv->S_max, t_max, S_sel, kv->n_cmp_max, &n, &why)) return rc;
-    const int te = std::min(t_max, kv->S_max - 1);
-    NSA_CHECK_ARG(!why, "%s: %s (B = %d, S = %d, D = %d, t_max = %d)", who, why, kv->B, S, L->Dk, t_max);
-    // the largest sequence the launches are planned for: te + 1 tokens after the call, n1 compressed ones (LayerDecode)
-    const int t0 = std::max(0, te + 1 - S), n1 = ncmp_of(te + 1, L->l, L->d);
+    if (int rc = check_io(who, L, x, y, t_pos)) return rc;
+    PositionsPlan p;  // the largest sequence the launches are planned for: te + 1 tokens after the call, n1 compressed ones (LayerDecode)
+    if (int rc = layer_decode_ragged_route(who, L, kv->B, S, kv->S_max, t_max, S_sel, kv->n_cmp_max, &p)) return rc;
+    NSA_CHECK_ARG(!p.why, "%s: %s (B = %d, S = %d, D = %d, t_max = %d)", who, p.why, kv->B, S, L->Dk, t_max);
     const CacheStrides C(L, kv);
-    SelDecodeCall probe = sel_decode_call(L, kv, C, S, 0, n1, S_sel);
-    probe.S_kv = te + 1;
+    SelDecodeCall probe = sel_decode_call(L, kv, C, S, 0, p.n1, S_sel);
+    probe.S_kv = p.te + 1;
     probe.Q = probe.O = kv->K_cmp;  // (Q and O come from the 256-byte aligned workspace)
     NSA_CHECK_ARG(decode_ragged_operands_ok(probe) && (uintptr_t)kv->K_cmp % 16 == 0,
                   "%s: K_cmp, K_sel and V_sel must be 16-byte aligned with strides in multiples of 8 elements", who);
     const DecodeWs W = decode_ws(L, kv->B, kv->S_max, S);
     if (int rc = check_workspace(who, workspace, workspace_bytes, W.total)) return rc;
-    unsigned char *ws = (unsigned char *)workspace;
-    const LayerDecode D{L, kv, W, ws, ws + W.q, ws + W.ocmp, ws + W.osel, ws + W.owin, ws + W.omix, S, t0, 0, n1, t_pos, te};
-    SelDecodeCall c = layer_sel_call(D, C, csc_ptr, csc_rows, csc_vals, S_sel, ranges_out);
-    c.t0 = 0;  // as nsa_sel_decode_ragged hands it over: every row's token comes from t_pos
-    c.S_kv = te + 1;
+    const LayerDecode D = layer_decode_positions(L, kv, W, workspace, S, p, t_pos);
     hipStream_t st = (hipStream_t)stream;
     // 1. fused QKV projection of the B S rows, row (b, s) rotated at t_pos[b] + s and appended there where sequence b is live
-    RopeAppendParams R = rope_append_params(L, kv, ws + W.proj, D.Q, S, 0);
+    RopeAppendParams R = rope_append_params(L, kv, D.ws + W.proj, D.Q, S, 0);
     R.t_pos = t_pos;
-    R.t_max = te;
+    R.t_max = p.te;
     if (int rc = launch_qkv_rope_append(R, qkv_call(L, x, kv->B * S, nullptr, 0.f, stream), true)) return rc;
     // 2. every live sequence's compressed tokens whose windows complete inside its rows (launched every call: its blocks exit where none does)
-    CmpPoolParams P{};
-    P.K_raw = kv->K_raw; P.V_raw = kv->V_raw; P.K_cmp = kv->K_cmp; P.V_cmp = kv->V_cmp;
-    P.nbg = kv->B * L->G; P.S_max = kv->S_max; P.n_cmp_max = kv->n_cmp_max; P.Dk = L->Dk; P.Dv = L->Dv; P.l = L->l; P.d = L->d;
-    P.rope_base = L->rope_base > 0.f ? L->rope_base : 10000.0f;
-    P.inv_scale = 1.0f;  // as nsa_cmp_pool_append: no position scaling inside the pooled keys
-    P.t_pos = t_pos; P.t_max = te; P.S = S; P.G = L->G;
+    CmpPoolParams P = cmp_pool_params(L, kv->B, kv->K_raw, kv->V_raw, kv->K_cmp, kv->V_cmp, kv->S_max, kv->n_cmp_max);
+    P.t_pos = t_pos; P.t_max = p.te; P.S = S; P.G = L->G;
     if (int rc = launch_cmp_pool_ragged(P, L->dtype, st)) return rc;
     // 3. selected branch: the rows form with the position array (one launch; zero O and ranges rows for a sequence that is not live)
-    if (int rc = launch_decode_rows(c, st, t_pos, te)) return rc;
+    SelDecodeCall c = layer_sel_call(D, C, csc_ptr, csc_rows, csc_vals, S_sel, ranges_out);
+    c.S_kv = p.te + 1;  // (the paged call leaves t0 + S)
+    if (int rc = launch_decode_rows(c, st, t_pos, p.te)) return rc;
     // 4. both band branches in one dual launch (split form, deferred combine; Dv = 128: one ragged launch each), 5. finish (or the gate
     // kernel), 6. output projection -- the rows call's tail with the position array in D
-    DecodeFinishParams F = decode_finish_params(D, gates_out);
-    F.ns[1] = 1;
-    DecBandPair BP{};
-    const bool dual = band_pair(D, C, L->Dv == 64 ? 1 : 0, BP);
-    return layer_decode_tail(D, C, F, dual ? &BP : nullptr, false, gates_out, y, nullptr, stream);
+    return layer_decode_rows_tail(D, C, gates_out, y, stream);
 }
 
 // ------------------------------------------------------------------------------ paged layer decode: append, pool and attend through a block table
@@ -681,46 +704,31 @@ constexpr int LAYER_PAGED_MAX_PAGES = 1 << 20;  // (the paged operators' bound: 
 static int paged_ws_tokens(int max_pages) { return (int)std::min<int64_t>((int64_t)max_pages * LAYER_PAGE_TOKENS, 1 << 17); }
 
 // What the call and its plan share, from the shape, the host bound and the switches alone (aligned pools assumed; neither the positions nor
-// the table are read on the host).  As layer_decode_ragged_route: NSA_OK with *launches = n, or *launches = 0 and *why = the limit (DECLINED:
-// there is no fallback), or an error status for bad arguments.
-static int layer_decode_paged_route(const char *who, const nsa_layer_desc *L, int B, int S, int max_pages, int t_max, int S_sel, int *launches,
-                                    const char **why) {
-    *launches = 0;
-    *why = nullptr;
+// the table are read on the host).  Answers as layer_decode_ragged_route does (declined: there is no fallback).
+static int layer_decode_paged_route(const char *who, const nsa_layer_desc *L, int B, int S, int max_pages, int t_max, int S_sel, PositionsPlan *p) {
+    *p = PositionsPlan{};
     if (int rc = check_layer(L, who)) return rc;
-    NSA_CHECK_ARG(S >= 1 && S <= LAYER_ROWS_MAX_S, "%s: 1 to %d tokens per sequence (got %d)", who, LAYER_ROWS_MAX_S, S);
+    if (int rc = check_rows_count(who, S)) return rc;
     NSA_CHECK_ARG(B >= 1, "%s: bad batch size %d", who, B);
     NSA_CHECK_ARG(max_pages >= 1 && max_pages <= LAYER_PAGED_MAX_PAGES, "%s: max_pages = %d, must be in [1, 2^20]", who, max_pages);
-    NSA_CHECK_ARG(t_max >= 0, "%s: t_max (the host bound of t_pos[b] + S - 1) must not be negative", who);
     const int cap = max_pages * LAYER_PAGE_TOKENS;
-    const int te = std::min(t_max, cap - 1);  // no live row sits beyond te
-    NSA_CHECK_ARG(S_sel >= 1 && (int64_t)S_sel * L->l_sel >= (int64_t)te + 1, "%s: block metadata (S_sel=%d) does not cover %d tokens", who, S_sel, te + 1);
-    if (!(L->dtype == NSA_DT_BF16 || L->dtype == NSA_DT_F16)) {
-        *why = "bf16 / f16 only (no kernel reads or writes pools of pages in fp32)";
-        return NSA_OK;
-    }
-    if (!(L->Dk == L->Dv && (L->Dk == 64 || L->Dk == 128) && L->l == 32 && L->d == 16 && L->l_sel == 64)) {
-        *why = "Dk = Dv in {64, 128} and the default block geometry only (l = 32, d = 16, l' = 64: pages of 1024 tokens and 64 compressed rows)";
-        return NSA_OK;
-    }
-    if (L->w < 1) {
-        *why = "the sliding window must hold at least one key (w >= 1)";
-        return NSA_OK;
-    }
-    nsa_paged_kv_desc pools{};  // stands in for aligned pools: the predicates below read the sizes and the pointers' alignment only
-    pools.K_sel = pools.V_sel = pools.K_win = pools.V_win = pools.K_raw = pools.V_raw = pools.K_cmp = pools.V_cmp = (void *)(uintptr_t)256;
-    pools.B = B;
-    const nsa_kv_desc kv = page_extent_kv(&pools);
+    if (int rc = check_bound(who, L, S, cap, t_max, S_sel, p)) return rc;
+    p->why = !dtype_16bit(L->dtype) ? "bf16 / f16 only (no kernel reads or writes pools of pages in fp32)"
+             : !default_decode_geometry(L)
+                 ? "Dk = Dv in {64, 128} and the default block geometry only (l = 32, d = 16, l' = 64: pages of 1024 tokens and 64 compressed rows)"
+                 : L->w < 1 ? "the sliding window must hold at least one key (w >= 1)" : nullptr;
+    if (p->why) return NSA_OK;
+    const nsa_kv_desc kv = stand_in_kv(B, LAYER_PAGE_TOKENS, LAYER_PAGE_CMP);  // (aligned pools under their page extent: page_extent_kv)
     const CacheStrides C(L, &kv);
-    SelDecodeCall sc = sel_decode_call(L, &kv, C, S, 0, ncmp_of(te + 1, L->l, L->d), S_sel);
+    SelDecodeCall sc = sel_decode_call(L, &kv, C, S, 0, p->n1, S_sel);
     sc.S_kv = cap;
-    if (!decode_paged_shape_plan(sc, te, nullptr, nullptr, why)) return NSA_OK;
-    *why = nullptr;
+    if (!decode_paged_shape_plan(sc, p->te, nullptr, nullptr, &p->why)) return NSA_OK;
+    p->why = nullptr;
     int ns = 1;
     band_attn_workspace(B, S, L->G, L->h, L->Dk, L->Dv, L->dtype, &ns);
     // the verdicts, projection + RoPE + append, pooling (always), the selected branch's one launch, the sliding and the compressed branch (each
     // one paged launch, with its combine behind it in split form), finish (or gate + mix), output projection
-    *launches = 4 + 2 * (ns > 1 ? 2 : 1) + 2;
+    p->launches = 4 + 2 * (ns > 1 ? 2 : 1) + 2;
     return NSA_OK;
 }
 
@@ -731,15 +739,8 @@ size_t nsa_layer_decode_paged_workspace(const nsa_layer_desc *L, int B, int S, i
 
 int nsa_layer_decode_paged_plan(const nsa_layer_desc *L, int B, int S, int max_pages, int t_max, int S_sel, int *launches, int *route) {
     NSA_CHECK_ARG(launches && route, "layer_decode_paged_plan: null pointer");
-    *launches = 0;
-    *route = -1;
-    int n = 0;
-    const char *why = nullptr;
-    if (int rc = layer_decode_paged_route("layer_decode_paged_plan", L, B, S, max_pages, t_max, S_sel, &n, &why)) return rc;
-    if (why) return NSA_OK;  // declined
-    *launches = n;
-    *route = 1;
-    return NSA_OK;
+    PositionsPlan p;
+    return plan_answer(layer_decode_paged_route("layer_decode_paged_plan", L, B, S, max_pages, t_max, S_sel, &p), p, launches, route);
 }
 
 int nsa_layer_decode_paged(const nsa_layer_desc *L, const nsa_paged_kv_desc *pkv, const void *x, void *y, const int32_t *t_pos, int t_max, int S,
@@ -749,61 +750,49 @@ int nsa_layer_decode_paged(const nsa_layer_desc *L, const nsa_paged_kv_desc *pkv
     if (int rc = check_layer(L, who)) return rc;
     NSA_CHECK_ARG(pkv && pkv->K_sel && pkv->V_sel && pkv->K_win && pkv->V_win && pkv->K_raw && pkv->V_raw && pkv->K_cmp && pkv->V_cmp, "%s: null pool pointer", who);
     NSA_CHECK_ARG(pkv->B >= 1 && pkv->n_pages >= 1, "%s: bad pool sizes (B = %d, n_pages = %d)", who, pkv->B, pkv->n_pages);
-    NSA_CHECK_ARG(x && y && L->W_qkv && L->W_out, "%s: null pointer", who);
-    NSA_CHECK_ARG(t_pos, "%s: null position array t_pos", who);
-    NSA_CHECK_ARG((uintptr_t)t_pos % 4 == 0, "%s: t_pos must be 4-byte aligned", who);
+    if (int rc = check_io(who, L, x, y, t_pos)) return rc;
     NSA_CHECK_ARG(pkv->block_table, "%s: null block table", who);
-    int n = 0;
-    const char *why = nullptr;
-    if (int rc = layer_decode_paged_route(who, L, pkv->B, S, pkv->max_pages, t_max, S_sel, &n, &why)) return rc;
+    PositionsPlan p;  // the largest sequence the launches are planned for: te + 1 tokens after the call, n1 compressed ones (LayerDecode)
+    if (int rc = layer_decode_paged_route(who, L, pkv->B, S, pkv->max_pages, t_max, S_sel, &p)) return rc;
     NSA_CHECK_ARG((uintptr_t)pkv->block_table % 4 == 0 && pkv->table_stride >= pkv->max_pages,
                   "%s: the block table must be 4-byte aligned with a row stride of at least max_pages = %d (got %lld)", who, pkv->max_pages,
                   (long long)pkv->table_stride);
-    NSA_CHECK_ARG(!why, "%s: %s (B = %d, S = %d, D = %d, t_max = %d)", who, why, pkv->B, S, L->Dk, t_max);
+    NSA_CHECK_ARG(!p.why, "%s: %s (B = %d, S = %d, D = %d, t_max = %d)", who, p.why, pkv->B, S, L->Dk, t_max);
     NSA_CHECK_ARG(((uintptr_t)pkv->K_sel | (uintptr_t)pkv->V_sel | (uintptr_t)pkv->K_win | (uintptr_t)pkv->V_win | (uintptr_t)pkv->K_raw | (uintptr_t)pkv->V_raw |
                    (uintptr_t)pkv->K_cmp | (uintptr_t)pkv->V_cmp) % 16 == 0,
                   "%s: the eight pools must be 16-byte aligned", who);
-    const int B = pkv->B, cap = pkv->max_pages * LAYER_PAGE_TOKENS, te = std::min(t_max, cap - 1);
-    // the largest sequence the launches are planned for: te + 1 tokens after the call, n1 compressed ones (LayerDecode)
-    const int t0 = std::max(0, te + 1 - S), n1 = ncmp_of(te + 1, L->l, L->d);
+    const int B = pkv->B, cap = pkv->max_pages * LAYER_PAGE_TOKENS;
     const nsa_kv_desc kv = page_extent_kv(pkv);
     const CacheStrides C(L, &kv);
     const DecodeWs W = decode_ws(L, B, paged_ws_tokens(pkv->max_pages), S);
     if (int rc = check_workspace(who, workspace, workspace_bytes, W.total + up256(sizeof(int32_t) * (size_t)B))) return rc;
-    unsigned char *ws = (unsigned char *)workspace;
-    int32_t *t_live = (int32_t *)(ws + W.total);
+    int32_t *t_live = (int32_t *)((unsigned char *)workspace + W.total);
     const LayerPageTable pg{pkv->block_table, pkv->table_stride, pkv->n_pages, pkv->max_pages};
     // every launch behind the pre-pass takes t_live as its position array: one verdict per sequence for the writers and the readers
-    const LayerDecode D{L, &kv, W, ws, ws + W.q, ws + W.ocmp, ws + W.osel, ws + W.owin, ws + W.omix, S, t0, 0, n1, t_live, te, &pg};
+    const LayerDecode D = layer_decode_positions(L, &kv, W, workspace, S, p, t_live, &pg);
     hipStream_t st = (hipStream_t)stream;
     // 0. the verdicts: t_live[b] = t_pos[b] where sequence b is live (positions, and every table entry it needs inside [0, n_pages)), else -1
-    if (int rc = launch_paged_live(PagedLiveParams{t_pos, t_live, pg, B, S, te}, st)) return rc;
+    if (int rc = launch_paged_live(PagedLiveParams{t_pos, t_live, pg, B, S, p.te}, st)) return rc;
     // 1. fused QKV projection of the B S rows, row (b, s) rotated at pos = t_live[b] + s and appended to row pos & 1023 of page
     // table[b][pos >> 10] of the six token pools where sequence b is live
     RopePagedParams R{};
-    static_cast<RopeAppendParams &>(R) = rope_append_params(L, &kv, ws + W.proj, D.Q, S, 0);
+    static_cast<RopeAppendParams &>(R) = rope_append_params(L, &kv, D.ws + W.proj, D.Q, S, 0);
     R.S_max = cap;
     R.t_pos = t_live;
-    R.t_max = te;
+    R.t_max = p.te;
     R.pg = pg;
     if (int rc = launch_qkv_rope_append_paged(R, qkv_call(L, x, B * S, nullptr, 0.f, stream))) return rc;
     // 2. every live sequence's compressed tokens whose windows complete inside its rows, each window row and the compressed row through its page
     CmpPoolPagedParams P{};
-    P.K_raw = pkv->K_raw; P.V_raw = pkv->V_raw; P.K_cmp = pkv->K_cmp; P.V_cmp = pkv->V_cmp;
-    P.nbg = B * L->G; P.S_max = cap; P.n_cmp_max = pkv->max_pages * LAYER_PAGE_CMP; P.Dk = L->Dk; P.Dv = L->Dv; P.l = L->l; P.d = L->d;
-    P.rope_base = L->rope_base > 0.f ? L->rope_base : 10000.0f;
-    P.inv_scale = 1.0f;  // as nsa_cmp_pool_append: no position scaling inside the pooled keys
-    P.t_pos = t_live; P.t_max = te; P.S = S; P.G = L->G;
+    static_cast<CmpPoolParams &>(P) = cmp_pool_params(L, B, pkv->K_raw, pkv->V_raw, pkv->K_cmp, pkv->V_cmp, cap, pkv->max_pages * LAYER_PAGE_CMP);
+    P.t_pos = t_live; P.t_max = p.te; P.S = S; P.G = L->G;
     P.pg = pg;
     if (int rc = launch_cmp_pool_paged(P, L->dtype, st)) return rc;
-    // 3. selected branch: the paged rows form (one launch; zero O and ranges rows for a sequence that is not live)
-    SelDecodeCall c = layer_sel_call(D, C, csc_ptr, csc_rows, csc_vals, S_sel, ranges_out);
-    c.t0 = 0;  // as nsa_sel_decode_paged hands it over: every row's token comes from the position array
-    if (int rc = sel_decode_paged_impl(c, DecPageTable{pg.table, pg.stride, pg.n_pages}, pg.max_pages, LAYER_PAGE_TOKENS, t_live, te, stream)) return rc;
+    // 3. selected branch: the paged rows form (one launch; zero O and ranges rows for a sequence that is not live; S_kv stays t0 + S)
+    const SelDecodeCall c = layer_sel_call(D, C, csc_ptr, csc_rows, csc_vals, S_sel, ranges_out);
+    if (int rc = sel_decode_paged_impl(c, DecPageTable{pg.table, pg.stride, pg.n_pages}, pg.max_pages, LAYER_PAGE_TOKENS, t_live, p.te, stream)) return rc;
     // 4. the sliding and the compressed branch, one paged launch each with its own combine, 5. finish (or the gate kernel), 6. output projection
-    DecodeFinishParams F = decode_finish_params(D, gates_out);
-    F.ns[1] = 1;
-    return layer_decode_tail(D, C, F, nullptr, false, gates_out, y, nullptr, stream);
+    return layer_decode_rows_tail(D, C, gates_out, y, stream);
 }
 
 // block workspace: xn | h | hn | u [B, mlp_hidden] | layer decode workspace

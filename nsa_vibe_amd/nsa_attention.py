@@ -666,6 +666,33 @@ class NSAAttention(nn.Module):
         return y, kv
 
     # ---- decode step for S consecutive tokens (k draft tokens to verify, the tail of a chunked prefill) ------------------------------
+    # what decode_rows, decode_ragged and decode_paged share (`who`: the method, for the messages); each keeps its own checks between the two
+    def _rows_shape(self, who: str, x: torch.Tensor):
+        """x [B,S,dim] with 1 <= S <= 16 -> (B, S)"""
+        assert x.dim() == 3, "x must be [B,S,dim]"
+        B, S, _ = x.shape
+        if not 1 <= S <= 16:
+            raise ValueError(f"NSAAttention.{who} takes 1 to 16 tokens per sequence, got S={S}")
+        return B, S
+
+    def _rows_input(self, who: str, x: torch.Tensor) -> torch.Tensor:
+        """inference only -> x, contiguous"""
+        if self._grad_needed(x):
+            raise RuntimeError(f"NSAAttention.{who} is inference only (no backward); run it under torch.no_grad()")
+        return x if x.is_contiguous() else x.contiguous()
+
+    def _rows_call(self, who: str, x: torch.Tensor, kv, meta, extent: int, head) -> torch.Tensor:
+        """the closing native call nsa_layer_<who> of x [B,S,dim] (`extent`: the last argument of its workspace query, `head`: what it
+        takes between y and the block map) -> y [B,S,dim]; ranges [B,S,G,n,2] and gates [B,S,G,3] go to the monitors"""
+        B, S, _ = x.shape
+        G = self.n_kv_groups
+        desc, _ = self._layer_desc()
+        y = torch.empty((B, S, self.dim), dtype=x.dtype, device=x.device)
+        ranges, gates = _one_call("nsa_layer_" + who, "layer_" + who, desc, kv, meta, x.device, (B, S, extent),
+                                  (x.data_ptr(), y.data_ptr(), *head), (), (B, S, G, self.n_sel, 2), (B, S, G, 3))
+        self._monitors(ranges, gates)
+        return y
+
     def decode_rows_plan(self, B: int, S: int, S_max: int, t0: int, S_sel: int) -> dict:
         """what nsa_layer_decode_rows does with a shape under the current tuning switches (nsa_layer_decode_rows_plan, no device call):
         {"launches", "route": 1 the selected branch in its one-launch rows form / 0 its separate launches / -1 declined (S single steps)}"""
@@ -678,15 +705,9 @@ class NSAAttention(nn.Module):
         kv) with the caches, read counters, ranges (_last_ranges [B,S,G,n,2]) and gates (_last_gates [B,S,G,3]) of S decode steps.  Inference
         only.  Where the native route does not apply (parity mode, a dtype or device the kernels do not take, a declining plan) it IS S
         decode steps, concatenated; a failed native call is counted and, unless NSA_HIP_STRICT, falls back to them as well."""
-        assert x.dim() == 3, "x must be [B,S,dim]"
-        B, S, _ = x.shape
-        if not 1 <= S <= 16:
-            raise ValueError(f"NSAAttention.decode_rows takes 1 to 16 tokens per sequence, got S={S}")
+        B, S = self._rows_shape("decode_rows", x)
         self._check_kv(x, kv)
-        if self._grad_needed(x):
-            raise RuntimeError("NSAAttention.decode_rows is inference only (no backward); run it under torch.no_grad()")
-        if not x.is_contiguous():
-            x = x.contiguous()
+        x = self._rows_input("decode_rows", x)
         if not self._native_ok(x):
             return self._decode_rows_steps(x, kv)
         t0, meta = kv.begin_rows(S)
@@ -714,15 +735,10 @@ class NSAAttention(nn.Module):
         return torch.cat(ys, dim=1), kv
 
     def _decode_rows_native(self, x: torch.Tensor, kv: NSA_KV):
-        B, S, _ = x.shape
+        S = x.shape[1]
         t0, meta = kv.begin_rows(S)
-        G = self.n_kv_groups
-        desc, _ = self._layer_desc()
-        y = torch.empty((B, S, self.dim), dtype=x.dtype, device=x.device)
-        ranges, gates = _one_call("nsa_layer_decode_rows", "layer_decode_rows", desc, kv, meta, x.device,
-                                  (B, S, kv._K_sel.shape[2]), (x.data_ptr(), y.data_ptr(), t0, S), (), (B, S, G, self.n_sel, 2), (B, S, G, 3))
+        y = self._rows_call("decode_rows", x, kv, meta, kv._K_sel.shape[2], (t0, S))
         kv.end_rows(t0, S)
-        self._monitors(ranges, gates)
         return y, kv
 
     # ---- ragged batch: every sequence of the batch at its own position (a serving batch) --------------------------------------------------
@@ -747,10 +763,7 @@ class NSAAttention(nn.Module):
         Monitors: _last_ranges [B,S,G,n,2], _last_gates [B,S,G,3] (gates of a padding slot: unspecified).  Inference only.
         Where the native call declines (nsa_layer_decode_ragged_plan) or the module is in parity mode: with host positions one decode_rows
         per live sequence on kv.sequence_view(b, t_b); with device positions the native message is raised."""
-        assert x.dim() == 3, "x must be [B,S,dim]"
-        B, S, _ = x.shape
-        if not 1 <= S <= 16:
-            raise ValueError(f"NSAAttention.decode_ragged takes 1 to 16 tokens per sequence, got S={S}")
+        B, S = self._rows_shape("decode_ragged", x)
         host = None
         if isinstance(t_pos, torch.Tensor):
             if t_pos.dtype != torch.int32 or tuple(t_pos.shape) != (B,):
@@ -775,10 +788,7 @@ class NSAAttention(nn.Module):
         if not x.is_cuda or (host is None and t_pos.device != x.device):
             raise RuntimeError("NSAAttention.decode_ragged needs HIP device tensors on one device (no CPU fallback exists)")
         self._check_kv(x, kv)
-        if self._grad_needed(x):
-            raise RuntimeError("NSAAttention.decode_ragged is inference only (no backward); run it under torch.no_grad()")
-        if not x.is_contiguous():
-            x = x.contiguous()
+        x = self._rows_input("decode_ragged", x)
         kv.refresh_meta(t_max + 1)
         if host is not None and (self._force_parity or not self._native_ok(x)
                                  or self.decode_ragged_plan(B, S, cap, t_max, int(kv.meta.S_sel))["route"] < 0):
@@ -790,14 +800,8 @@ class NSAAttention(nn.Module):
             t_pos = torch.tensor(host, dtype=torch.int32).pin_memory().to(x.device, non_blocking=True)
         elif not t_pos.is_contiguous():
             t_pos = t_pos.contiguous()
-        G = self.n_kv_groups
-        desc, _ = self._layer_desc()
-        y = torch.empty((B, S, self.dim), dtype=x.dtype, device=x.device)
         # (a declined shape comes back from the call itself, before its first launch, with the limit named)
-        ranges, gates = _one_call("nsa_layer_decode_ragged", "layer_decode_ragged", desc, kv, kv.meta, x.device, (B, S, cap),
-                                  (x.data_ptr(), y.data_ptr(), t_pos.data_ptr(), t_max, S), (), (B, S, G, self.n_sel, 2), (B, S, G, 3))
-        self._monitors(ranges, gates)
-        return y, kv
+        return self._rows_call("decode_ragged", x, kv, kv.meta, cap, (t_pos.data_ptr(), t_max, S)), kv
 
     # ---- ragged batch over PAGED caches: the eight caches in pools of pages behind a device block table ------------------------------------
     def new_paged_kv(self, n_pages: int, B: int, max_pages: int, device, dtype) -> NSA_PagedKV:
@@ -824,10 +828,7 @@ class NSAAttention(nn.Module):
         outside [0, n_pages) is inactive: nothing is written to any page, its y and ranges rows are zero.
         Monitors: _last_ranges [B,S,G,n,2], _last_gates [B,S,G,3] (gates of an inactive slot: unspecified).  Inference only.  There is no
         other route over pages: parity mode, or a module, input or shape the native call declines, raises -- the latter with the library's message."""
-        assert x.dim() == 3, "x must be [B,S,dim]"
-        B, S, _ = x.shape
-        if not 1 <= S <= 16:
-            raise ValueError(f"NSAAttention.decode_paged takes 1 to 16 tokens per sequence, got S={S}")
+        B, S = self._rows_shape("decode_paged", x)
         if not isinstance(t_pos, torch.Tensor) or t_pos.dtype != torch.int32 or tuple(t_pos.shape) != (B,):
             raise ValueError(f"NSAAttention.decode_paged: t_pos must be a device int32 tensor [{B}]")
         t_max = int(t_max)
@@ -839,24 +840,15 @@ class NSAAttention(nn.Module):
         if B != pkv.B or buf.dtype != x.dtype or buf.device != x.device or (pkv.G, pkv.d_k, pkv.d_v) != (self.n_kv_groups, self.d_k, self.d_v):
             raise RuntimeError(f"NSA_PagedKV does not match the input or the module: pools B={pkv.B} {buf.dtype} on {buf.device} (G={pkv.G}, d_k={pkv.d_k}, "
                                f"d_v={pkv.d_v}), x B={B} {x.dtype} on {x.device}")
-        if self._grad_needed(x):
-            raise RuntimeError("NSAAttention.decode_paged is inference only (no backward); run it under torch.no_grad()")
+        x = self._rows_input("decode_paged", x)  # (the copy of a strided x raises nothing: the order of the checks is as it was)
         if not self._native_ok(x):
             raise RuntimeError("NSAAttention.decode_paged: the native call does not take this module or input (parity mode, dtype, gate width), and "
                                "there is no other route over pages")
-        if not x.is_contiguous():
-            x = x.contiguous()
         if not t_pos.is_contiguous():
             t_pos = t_pos.contiguous()
         pkv.refresh_meta(min(t_max, pkv.capacity - 1) + 1)
-        G = self.n_kv_groups
-        desc, _ = self._layer_desc()
-        y = torch.empty((B, S, self.dim), dtype=x.dtype, device=x.device)
         # (a declined shape comes back from the call itself, before its first launch, with the limit named)
-        ranges, gates = _one_call("nsa_layer_decode_paged", "layer_decode_paged", desc, pkv, pkv.meta, x.device, (B, S, pkv.max_pages),
-                                  (x.data_ptr(), y.data_ptr(), t_pos.data_ptr(), t_max, S), (), (B, S, G, self.n_sel, 2), (B, S, G, 3))
-        self._monitors(ranges, gates)
-        return y, pkv
+        return self._rows_call("decode_paged", x, pkv, pkv.meta, pkv.max_pages, (t_pos.data_ptr(), t_max, S)), pkv
 
     def prefill_paged(self, x: torch.Tensor, pkv: NSA_PagedKV, b: int, t0: int = 0):
         """x [1,S,dim], the tokens of positions t0 .. t0 + S - 1 of the sequence in slot b of `pkv` -> y [1,S,dim]; afterwards the slot's pages
