@@ -700,9 +700,6 @@ int nsa::sel_decode_rows_impl(const SelDecodeCall &c, void *workspace, size_t wo
     return sel_attn_fwd_impl(attn_call(c, w + W.a + W.p, workspace_bytes - W.a - W.p, stream), 0, nullptr);
 }
 
-// compressed tokens / selection blocks that the metadata of t + 1 tokens holds (default geometry)
-static int ragged_ncmp(int t) { return t + 1 < 32 ? 0 : (t + 1 - 32) / 16 + 1; }
-
 int nsa::sel_decode_ragged_impl(const SelDecodeCall &c, const int32_t *t_pos, int t_max, void *stream) {
     NSA_CHECK_ARG(dtype_ok(c.dtype), "decode_ragged: unknown dtype %d", c.dtype);
     NSA_CHECK_ARG(c.B >= 0 && c.S >= 0 && c.G >= 1 && c.h >= 1 && c.Dk >= 1 && c.Dv >= 1 && c.S_cmp >= 0 && c.S_sel >= 1 && c.S_kv >= 1, "decode_ragged: bad sizes");
@@ -710,7 +707,7 @@ int nsa::sel_decode_ragged_impl(const SelDecodeCall &c, const int32_t *t_pos, in
     NSA_CHECK_ARG(t_max >= 0, "decode_ragged: t_max (the host bound of t_pos[b] + S - 1) must not be negative");
     // the caches' capacity bound: no live row sits beyond te, and the metadata must cover te + 1 tokens
     const int te = std::min(t_max, c.S_kv - 1);
-    NSA_CHECK_ARG(c.S_cmp >= ragged_ncmp(te) && (int64_t)c.S_sel * 64 >= (int64_t)te + 1,
+    NSA_CHECK_ARG(c.S_cmp >= decode_ncmp(te) && (int64_t)c.S_sel * 64 >= (int64_t)te + 1,
                   "decode_ragged: S_cmp / S_sel must describe at least min(t_max, S_kv - 1) + 1 = %d tokens (got S_cmp = %d, S_sel = %d)", te + 1, c.S_cmp, c.S_sel);
     if (c.rows() == 0) return NSA_OK;
     NSA_CHECK_ARG(c.Q && c.K && c.V && c.O && c.ranges_out && t_pos && (c.K_cmp || c.S_cmp == 0), "decode_ragged: null pointer");
@@ -718,7 +715,7 @@ int nsa::sel_decode_ragged_impl(const SelDecodeCall &c, const int32_t *t_pos, in
     const char *why = nullptr;
     NSA_CHECK_ARG(decode_ragged_shape_plan(c, t_max, nullptr, nullptr, &why), "decode_ragged: %s (B = %d, S = %d, D = %d, t_max = %d)", why, c.B, c.S, c.Dk, t_max);
     NSA_CHECK_ARG(c.d == 16 && c.l == 32 && c.l_sel == 64, "decode_ragged: the default block geometry only (l = 32, d = 16, l' = 64)");
-    NSA_CHECK_ARG(decode_ragged_operands_ok(c), "decode_ragged: Q, K_cmp, K and V must be 16-byte aligned with strides in multiples of 8 elements, "
+    NSA_CHECK_ARG(decode_step_operands_ok(c), "decode_ragged: Q, K_cmp, K and V must be 16-byte aligned with strides in multiples of 8 elements, "
                                                 "V rows contiguous and O 8-byte aligned");
     return launch_decode_rows(c, (hipStream_t)stream, t_pos, t_max);
 }
@@ -737,7 +734,7 @@ int nsa::sel_decode_paged_impl(const SelDecodeCall &c0, const DecPageTable &pt, 
     NSA_CHECK_ARG(c.n_top >= 1 && c.n_top <= 64, "decode_paged: n_top must be in [1,64]");
     NSA_CHECK_ARG(t_max >= 0, "decode_paged: t_max (the host bound of t_pos[b] + S - 1) must not be negative");
     const int te = std::min(t_max, c.S_kv - 1);
-    NSA_CHECK_ARG(c.S_cmp >= ragged_ncmp(te) && (int64_t)c.S_sel * 64 >= (int64_t)te + 1,
+    NSA_CHECK_ARG(c.S_cmp >= decode_ncmp(te) && (int64_t)c.S_sel * 64 >= (int64_t)te + 1,
                   "decode_paged: S_cmp / S_sel must describe at least min(t_max, max_pages * 1024 - 1) + 1 = %d tokens (got S_cmp = %d, S_sel = %d)", te + 1, c.S_cmp,
                   c.S_sel);
     if (c.rows() == 0) return NSA_OK;
@@ -749,7 +746,7 @@ int nsa::sel_decode_paged_impl(const SelDecodeCall &c0, const DecPageTable &pt, 
     const char *why = nullptr;
     NSA_CHECK_ARG(decode_paged_shape_plan(c, t_max, nullptr, nullptr, &why), "decode_paged: %s (B = %d, S = %d, D = %d, t_max = %d)", why, c.B, c.S, c.Dk, t_max);
     NSA_CHECK_ARG(c.d == 16 && c.l == 32 && c.l_sel == 64, "decode_paged: the default block geometry only (l = 32, d = 16, l' = 64)");
-    NSA_CHECK_ARG(decode_ragged_operands_ok(c), "decode_paged: Q and the three pools must be 16-byte aligned with page, group and row strides in multiples of 8 elements, "
+    NSA_CHECK_ARG(decode_step_operands_ok(c), "decode_paged: Q and the three pools must be 16-byte aligned with page, group and row strides in multiples of 8 elements, "
                                                 "V rows contiguous and O 8-byte aligned");
     // the kernel's only 32-bit byte offsets are those of a row inside one (page, group) plane: 1024 K / V rows, 64 compressed rows
     const int64_t lim = (int64_t)1 << 31;

@@ -53,6 +53,10 @@ bool decode_step_shape_plan(const SelDecodeCall &c, int *form, int *nsplit);
 // rows form of the one-launch step (nsa_sel_decode_rows): S consecutive tokens per sequence at t0 .. t0 + S - 1, one workgroup per row
 bool decode_rows_shape_plan(const SelDecodeCall &c, int *form, int *nw_out);
 bool decode_rows_supported(const SelDecodeCall &c);
+// what every form asks of the call beyond its shape: default block geometry, an aligned K_cmp, the operands of the row's attention
+bool decode_step_operands_ok(const SelDecodeCall &c);
+// compressed rows a decode step at token t sees, default geometry (l = 32, d = 16)
+__host__ __device__ inline int decode_ncmp(int t) { return t + 1 < 32 ? 0 : (t + 1 - 32) / 16 + 1; }
 // t_pos (device, [B]) / t_max: the ragged form (nsa_sel_decode_ragged) -- row (b, s, g) at t_pos[b] + s, planned from t_max
 // pt: the paged form (nsa_sel_decode_paged) -- the caches are pools of pages found through a device table, c.S_kv the capacity max_pages * 1024
 struct DecPageTable {
@@ -64,7 +68,6 @@ int launch_decode_rows(const SelDecodeCall &c, hipStream_t st, const int32_t *t_
 // shape / tuning part of the ragged form's predicate, from the host bound t_max alone (the position array is never read on the host);
 // *why (optional): the limit a declined shape ran into
 bool decode_ragged_shape_plan(const SelDecodeCall &c, int t_max, int *form, int *nw_out, const char **why);
-bool decode_ragged_operands_ok(const SelDecodeCall &c);
 int sel_decode_ragged_impl(const SelDecodeCall &c, const int32_t *t_pos, int t_max, void *stream);
 // the paged form's plan: the ragged form's with one (page, group) plane of 1024 rows as the extent of the 32-bit offsets
 bool decode_paged_shape_plan(const SelDecodeCall &c, int t_max, int *form, int *nw_out, const char **why);

@@ -664,7 +664,7 @@ int nsa_layer_decode_ragged(const nsa_layer_desc *L, const nsa_kv_desc *kv, cons
     SelDecodeCall probe = sel_decode_call(L, kv, C, S, 0, p.n1, S_sel);
     probe.S_kv = p.te + 1;
     probe.Q = probe.O = kv->K_cmp;  // (Q and O come from the 256-byte aligned workspace)
-    NSA_CHECK_ARG(decode_ragged_operands_ok(probe) && (uintptr_t)kv->K_cmp % 16 == 0,
+    NSA_CHECK_ARG(decode_step_operands_ok(probe) && (uintptr_t)kv->K_cmp % 16 == 0,
                   "%s: K_cmp, K_sel and V_sel must be 16-byte aligned with strides in multiples of 8 elements", who);
     const DecodeWs W = decode_ws(L, kv->B, kv->S_max, S);
     if (int rc = check_workspace(who, workspace, workspace_bytes, W.total)) return rc;

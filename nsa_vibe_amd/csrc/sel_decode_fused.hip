@@ -43,6 +43,7 @@
 #include <mutex>
 #include <type_traits>
 #include <unordered_map>
+#include <utility>
 
 #define DEC_TS(i)  // (the shared device functions' own stamps belong to the round-2 kernel's timeline: this kernel stamps with DS_TS)
 #include "nsa_host.hpp"
@@ -66,9 +67,31 @@ constexpr int DSTEP_PART = 16 * DSTEP_CH * 2;  // floats: [head][chunk][2]
 constexpr int DSTEP_HALO = DSTEP_CH * 16;      // floats: [chunk][head] scaled logit of the chunk's last row
 constexpr int DSTEP_TAIL = 1024 + 4 * (128 + 68 + 4);  // bytes behind the V tiles: mlw [16][16] f32 | scr | list | misc
 constexpr int DSTEP_PAGES = 128;               // paged form: table entries of a sequence kept in LDS behind everything else (the long-row form ends at 128 chunks = 131,072 tokens: pages 0 .. 127)
+// The LDS map of a row workgroup, byte offsets for both kernel templates.  The score phases live where the V tiles of the gather will be:
+// part | halo | pg.  PREF (16 waves, unsplit): waves 0, 14 and 15 fetch the row's forced blocks (0, t//64 - 1, t//64: known from t alone,
+// selection_scorer.py:159-170) at kernel start, V into their own tiles, K into three tiles behind the tail -- so the score data starts at
+// tile 1.  (Offsets, not a struct of pointers: with the pointers read back from a struct every kernel of the unit compiled to about 3000
+// instructions fewer or more and some to more scratch, profiles/decode_step_fold/isa.txt.)
+template <int NW, int D, bool PREF>
+struct DecStepLds {
+    static constexpr int TILE = dec_att_tile(D);  // V tile of a wave
+    static constexpr int PART = PREF ? TILE : 0;  // f32 [head][chunk][2] (max, sum exp2)
+    static constexpr int HALO = PART + 4 * DSTEP_PART, PG = HALO + 4 * DSTEP_HALO;  // f32 [chunk][head] edge logits | f32 [S_sel] group scores
+    static constexpr int MLW = NW * TILE;  // f32 [NW][16] per-wave copy of the per-head log-sum-exp
+    // int [128] run extraction of the selector | int [68] picked blocks, ascending | int [0] number of picked blocks, [1] ticket, [2] team assembled
+    static constexpr int SCR = MLW + 4 * NW * 16, LIST = SCR + 4 * 128, MISC = LIST + 4 * 68;
+    static constexpr int KTILES = NW * TILE + DSTEP_TAIL;  // PREF: [3] K images of the prefetched blocks
+    static constexpr int PAGES = KTILES + (NW == 16 ? 3 * TILE : 0);  // PAGED: int [DSTEP_PAGES] the sequence's table entries
+    static_assert(MISC + 4 * 4 <= KTILES, "mlw | scr | list | misc fit the tail behind the V tiles");
+};
+// The host's view of that map: bytes of a launch, bytes of score data the unsplit kernel keeps in the V-tile area, and what that area holds.
 // D = 128 (eight waves): 8 x 16 KiB of V tiles + the tail = 132,896 bytes -- one workgroup per CU; the score phases (part 16 KiB | halo 8 KiB |
 // pg <= 8 KiB) fit the 128 KiB of tiles with room to spare
 static size_t dstep_lds(int nw, int D = 64) { return (size_t)nw * dec_att_tile(D) + DSTEP_TAIL + (nw == 16 ? 3 * dec_att_tile(D) : 0); }
+static size_t dstep_score_bytes(int nw, int h, int S_sel, int cpw) {
+    return sizeof(float) * (DSTEP_PART + DSTEP_HALO + (size_t)((S_sel + 3) & ~3)) + (cpw == 4 ? (size_t)3 * nw * 256 * h : 0);
+}
+static size_t dstep_score_room(int nw, int D = 64) { return (size_t)(nw == 16 ? 13 : nw) * dec_att_tile(D); }
 
 // workgroup barrier for data exchanged through LDS only: waits for this wave's LDS operations, NOT for its vector memory operations
 // (__syncthreads() drains vmcnt too, which would stall the three prefetching waves -- and with them the whole workgroup -- until their
@@ -87,6 +110,39 @@ __device__ __forceinline__ bool decode_band_workgroup(const DecBandPair &BP) {
     if (bb < BP.n_w) band_attn_body<T, 64, 1, true, 1>(BP.w, bb, NW, &BP.mg, true);
     else band_attn_body<T, 64, 1, true, 1>(BP.c, bb - BP.n_w, NW, &BP.mg, false);
     return true;
+}
+
+// logits of one chunk before scaling (MFMA rows = 64 compressed rows, columns = heads): the MFMAs of decode_logits_mfma_kernel.  Every
+// chunk loop of both kernels but the two-chunk arm of phase 1, which keeps its written-out copy: called from there, the D = 64 and D = 128
+// forms 0 compile to other code (profiles/decode_step_fold/isa.txt)
+template <class M, int KS>
+__device__ __forceinline__ void chunk_logits(const typename M::x8 (&src)[4][KS], const typename M::x8 (&qf)[KS], f32x4 (&z)[4]) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        f32x4 zz = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < KS; ++s) zz = M::mma(src[u][s], qf[s], zz);
+        z[u] = zz;
+    }
+}
+
+// Eq.10 head sum: heads of the group = columns 0 .. h-1 of this 16-lane row, lane 0 collects them in ascending order by DPP row shifts.  HC =
+// the group size at compile time (straight-line code); HC = 0: any h <= 16 -- columns >= h enter as zeros (p >= 0: adding +0 is exact), so
+// the 15 shifted adds run unconditionally (a scalar branch per possible head cost 2 us per step at 64k)
+template <int K>
+__device__ __forceinline__ float dstep_shift_add(float grp, float src) {
+    return grp + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, src), 0x100 | K, 0xf, 0xf, true));
+}
+template <int HC, int... K>
+__device__ __forceinline__ float dstep_head_sum(float slc, int rho, int h, std::integer_sequence<int, K...>) {
+    const float src = HC == 6 ? slc : rho < h ? slc : 0.f;
+    float grp = src;
+    ((grp = dstep_shift_add<K + 1>(grp, src)), ...);
+    return grp;
+}
+template <int HC>
+__device__ __forceinline__ float dstep_head_sum(float slc, int rho, int h) {
+    return dstep_head_sum<HC>(slc, rho, h, std::make_integer_sequence<int, HC == 6 ? 5 : 15>{});
 }
 
 // CPW = chunks of 64 compressed rows per wave.  2: the logits of both stay in the MFMA accumulators (contexts to 32 NW chunks).  4 (round 4,
@@ -110,19 +166,12 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
     using M = MfmaT<T>;
     using x8 = typename M::x8;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    // the score phases live where the V tiles of the gather will be: part | halo | pg.  PREF (16 waves, unsplit): waves 0, 14 and 15 fetch
-    // the row's forced blocks (0, t//64 - 1, t//64: known from t alone, selection_scorer.py:159-170) at kernel start, V into their own
-    // tiles, K into three tiles behind the tail -- so the score data starts at tile 1
     constexpr bool PREF = NW == 16 && !SPLIT;
-    float *part = (float *)(lds + (PREF ? TILE : 0));
-    float *halo = part + DSTEP_PART;
-    float *pg = halo + DSTEP_HALO;  // [S_sel]
-    float *mlw = (float *)(lds + NW * TILE);  // [NW][16] per-wave copy of the per-head log-sum-exp
-    int *scr = (int *)(mlw + NW * 16);                // [128] run extraction of the selector
-    int *list = scr + 128;                            // [68] picked blocks, ascending
-    int *misc = list + 68;                            // [0] number of picked blocks, [1] ticket, [2] team assembled
-    [[maybe_unused]] unsigned char *ktiles = lds + NW * TILE + DSTEP_TAIL;  // PREF: [3] K images of the prefetched blocks
-    [[maybe_unused]] int *pages = (int *)(lds + NW * TILE + DSTEP_TAIL + (NW == 16 ? 3 * TILE : 0));  // PAGED: [DSTEP_PAGES] the sequence's table entries
+    using L = DecStepLds<NW, D, PREF>;
+    float *part = (float *)(lds + L::PART), *halo = (float *)(lds + L::HALO), *pg = (float *)(lds + L::PG), *mlw = (float *)(lds + L::MLW);
+    int *scr = (int *)(lds + L::SCR), *list = (int *)(lds + L::LIST), *misc = (int *)(lds + L::MISC);
+    [[maybe_unused]] unsigned char *ktiles = lds + L::KTILES;
+    [[maybe_unused]] int *pages = (int *)(lds + L::PAGES);
 
     const int lane = lane_id(), wave = uniform((int)(threadIdx.x >> 6)), rho = lane & 15, q = lane >> 4;
     const int h = P.h;
@@ -188,7 +237,7 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
     // PAGED: the pool page of the sequence's page j (j wave uniform)
     [[maybe_unused]] auto page_of = [&](int j) -> int { return uniform(pages[j]); };
     const int t_tok = ROWS ? t_base + (row / P.G) % P.S : P.t_token;
-    const int S_cmp = ROWS ? (t_tok < 31 ? 0 : min(P.S_cmp, (t_tok + 1 - 32) / 16 + 1)) : P.S_cmp;
+    const int S_cmp = ROWS ? (t_tok < 31 ? 0 : min(P.S_cmp, decode_ncmp(t_tok))) : P.S_cmp;  // (t < 31: zero whatever P.S_cmp holds)
     const int nchunk = ROWS ? (S_cmp + 63) >> 6 : P.nchunk;
     [[maybe_unused]] const int64_t kvrow = ROWS ? b * P.G + g : (int64_t)row;  // the row's K/V plane
     const int hc = min(rho, h - 1);  // head of this lane's column (columns >= h repeat the last head: their results are never used)
@@ -241,15 +290,6 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
     for (int i = threadIdx.x; i < P.S_sel; i += NW * 64) pg[i] = 0.f;  // blocks without a compressed row keep a zero score
     // scaled logits of chunk c (MFMA rows = 64 compressed rows, columns = heads) and the chunk's (max, sum exp2) per head: the arithmetic of
     // decode_logits_mfma_kernel
-    auto chunk_logits = [&](int c, const x8 (&src)[4][KS], f32x4 (&z)[4]) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            f32x4 zz = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int s = 0; s < KS; ++s) zz = M::mma(src[u][s], qf[s], zz);
-            z[u] = zz;
-        }
-    };
     // (to_ws: the records go to the team's workspace; otherwise to this workgroup's LDS)
     auto chunk_stats_as = [&](int c, f32x4 (&z)[4], auto to_ws) {
         float m = -INFINITY;
@@ -297,7 +337,7 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
         for (int k = 0; k < 2; ++k) {
             const int c = wave + NW * k;
             if (c < c_hi) {
-                chunk_logits(c, a[k], acc[k]);
+                chunk_logits<M, KS>(a[k], qf, acc[k]);
                 if (c + 2 * NW < c_hi) load_chunk(c + 2 * NW, a[k]);
                 chunk_stats(c, acc[k]);
             }
@@ -308,7 +348,7 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
                 const int c = c0 + NW * k;
                 if (c < c_hi) {
                     f32x4 z[4];
-                    chunk_logits(c, a[k], z);
+                    chunk_logits<M, KS>(a[k], qf, z);
                     if (long_next(c, k) < c_hi) load_chunk(long_next(c, k), a[k]);
                     chunk_stats(c, z);
                 }
@@ -336,7 +376,7 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
             const int c = wave + NW * k;
             if (c < c_hi) {
                 f32x4 z[4];
-                chunk_logits(c, a[k & 1], z);
+                chunk_logits<M, KS>(a[k & 1], qf, z);
                 if (k + 2 < CPW && c + 2 * NW < c_hi) load_chunk(c + 2 * NW, a[k & 1]);
                 chunk_stats(c, z);
                 if (k == 0) {
@@ -396,7 +436,7 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
                 x8 b2[4][KS];
                 load_chunk(c, b2);
                 f32x4 z[4];
-                chunk_logits(c, b2, z);
+                chunk_logits<M, KS>(b2, qf, z);
                 chunk_stats_as(c, z, std::false_type{});
             }
         }
@@ -472,19 +512,7 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
             // heads of the group = columns 0 .. h-1 of this 16-lane row: lane 0 collects them in ascending order by DPP row shifts.  HC = the
             // group size at compile time (straight-line code); HC = 0: any h <= 16 -- columns >= h enter as zeros (p >= 0: adding +0 is exact),
             // so the 15 shifted adds run unconditionally (a scalar branch per possible head cost 2 us per step at 64k)
-            float grp;
-#define NSA_DS_HS(K) grp += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, src), 0x100 | K, 0xf, 0xf, true));
-            if constexpr (HC == 6) {
-                const float src = slc;
-                grp = slc;
-                NSA_DS_HS(1) NSA_DS_HS(2) NSA_DS_HS(3) NSA_DS_HS(4) NSA_DS_HS(5)
-            } else {
-                const float src = rho < h ? slc : 0.f;
-                grp = src;
-                NSA_DS_HS(1) NSA_DS_HS(2) NSA_DS_HS(3) NSA_DS_HS(4) NSA_DS_HS(5) NSA_DS_HS(6) NSA_DS_HS(7) NSA_DS_HS(8)
-                NSA_DS_HS(9) NSA_DS_HS(10) NSA_DS_HS(11) NSA_DS_HS(12) NSA_DS_HS(13) NSA_DS_HS(14) NSA_DS_HS(15)
-            }
-#undef NSA_DS_HS
+            const float grp = dstep_head_sum<HC>(slc, rho, h);
             const int j = 16 * c + 4 * u + q;
             if (rho == 0 && j < P.S_sel) {
                 if constexpr (SPLIT) __hip_atomic_store((unsigned *)(P.pg_g + (int64_t)row * 2048 + j), __float_as_uint(grp), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -516,7 +544,7 @@ __global__ __launch_bounds__(NW * 64, D == 64 ? 4 : 2) void decode_step_kernel(D
                 const int c = c0 + NW * k;
                 if (c < c_hi) {
                     f32x4 z[4];
-                    chunk_logits(c, a[k], z);
+                    chunk_logits<M, KS>(a[k], qf, z);
                     if (c + 2 * NW < c_hi) load_chunk(c + 2 * NW, a[k]);
 #pragma unroll
                     for (int u = 0; u < 4; ++u)
@@ -608,14 +636,11 @@ __global__ __launch_bounds__(NW * 64, 4) void decode_step_onepass_kernel(DecStep
     constexpr int CPW = 8;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr bool PREF = NW == 16;
-    float *part = (float *)(lds + (PREF ? DEC_ATT_TILE : 0));
-    float *halo = part + DSTEP_PART;
-    float *pg = halo + DSTEP_HALO;  // [S_sel]
-    float *mlw = (float *)(lds + NW * DEC_ATT_TILE);
-    int *scr = (int *)(mlw + NW * 16);
-    int *list = scr + 128;
-    int *misc = list + 68;
-    [[maybe_unused]] unsigned char *ktiles = lds + NW * DEC_ATT_TILE + DSTEP_TAIL;
+    using L = DecStepLds<NW, 64, PREF>;
+    float *part = (float *)(lds + L::PART), *halo = (float *)(lds + L::HALO), *pg = (float *)(lds + L::PG), *mlw = (float *)(lds + L::MLW);
+    int *scr = (int *)(lds + L::SCR), *list = (int *)(lds + L::LIST), *misc = (int *)(lds + L::MISC);
+    [[maybe_unused]] unsigned char *ktiles = lds + L::KTILES;
+    [[maybe_unused]] int *pages = (int *)(lds + L::PAGES);
 
     const int lane = lane_id(), wave = uniform((int)(threadIdx.x >> 6)), rho = lane & 15, q = lane >> 4;
     const int h = P.h;
@@ -664,13 +689,7 @@ __global__ __launch_bounds__(NW * 64, 4) void decode_step_onepass_kernel(DecStep
         for (int u = 0; u < 4; ++u) E[k][u] = 0.f;
         if (c < nchunk) {
             f32x4 z[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                f32x4 zz = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int s = 0; s < 2; ++s) zz = M::mma(a[k & 1][u][s], qf[s], zz);
-                z[u] = zz;
-            }
+            chunk_logits<M, 2>(a[k & 1], qf, z);
             if (k + 2 < CPW && c + 2 * NW < nchunk) load_chunk(c + 2 * NW, a[k & 1]);  // two chunks (16 KiB per wave) in flight throughout
             float m = -INFINITY;
 #pragma unroll
@@ -717,7 +736,7 @@ __global__ __launch_bounds__(NW * 64, 4) void decode_step_onepass_kernel(DecStep
 #endif
     lds_barrier();
     DS_TS(4);
-    // ---- phase 2a: per-head log-sum-exp from the chunk records (the arithmetic of decode_step_kernel: same bits)
+    // ---- phase 2a: per-head log-sum-exp from the chunk records (decode_step_kernel's, statement for statement: same bits)
     const int nr = (nchunk + 15) >> 4;
     for (int h0 = 0; h0 < h; h0 += 4) {
         const int hh = h0 + q;
@@ -765,19 +784,7 @@ __global__ __launch_bounds__(NW * 64, 4) void decode_step_onepass_kernel(DecStep
             for (int u = 0; u < 4; ++u) {
                 float slc = E[k][u] * f;
                 if (u == 0 && q == 0) slc += hp;
-                float grp;
-#define NSA_DS_HS(K) grp += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, src), 0x100 | K, 0xf, 0xf, true));
-                if constexpr (HC == 6) {
-                    const float src = slc;
-                    grp = slc;
-                    NSA_DS_HS(1) NSA_DS_HS(2) NSA_DS_HS(3) NSA_DS_HS(4) NSA_DS_HS(5)
-                } else {
-                    const float src = rho < h ? slc : 0.f;
-                    grp = src;
-                    NSA_DS_HS(1) NSA_DS_HS(2) NSA_DS_HS(3) NSA_DS_HS(4) NSA_DS_HS(5) NSA_DS_HS(6) NSA_DS_HS(7) NSA_DS_HS(8)
-                    NSA_DS_HS(9) NSA_DS_HS(10) NSA_DS_HS(11) NSA_DS_HS(12) NSA_DS_HS(13) NSA_DS_HS(14) NSA_DS_HS(15)
-                }
-#undef NSA_DS_HS
+                const float grp = dstep_head_sum<HC>(slc, rho, h);
                 const int j = 16 * c + 4 * u + q;
                 if (rho == 0 && j < P.S_sel) pg[j] = grp;
             }
@@ -858,12 +865,6 @@ static int device_cu_count() {
     return cus[dev];
 }
 
-// bytes of score data the unsplit kernel keeps in the V-tile area, and what that area holds
-static size_t dstep_score_bytes(int nw, int h, int S_sel, int cpw) {
-    return sizeof(float) * (DSTEP_PART + DSTEP_HALO + (size_t)((S_sel + 3) & ~3)) + (cpw == 4 ? (size_t)3 * nw * 256 * h : 0);
-}
-static size_t dstep_score_room(int nw, int D = 64) { return (size_t)(nw == 16 ? 13 : nw) * dec_att_tile(D); }
-
 // waves per row workgroup, workgroups per row (1 = an unsplit kernel) and the kernel form; false = this shape is not for the one-launch step.
 // form 0: logits in the accumulators (two chunks per wave; a long row as a team of NS workgroups that meet inside the launch: R * NS of them
 // must be resident together); 1: one 16- or 8-wave workgroup per row with four chunks per wave, the later chunks' logits in LDS (exact: the
@@ -919,7 +920,7 @@ static bool dstep_shape_ok(const SelDecodeCall &c, int nw, int fm) {
 }
 // what both forms ask of the call beyond its shape: the default block geometry (l = 2d, l' = 4d = 64), an aligned K_cmp with strides in
 // multiples of 8 elements, and the operands of the row's attention (sel_attn_decode_wg_supported)
-static bool dstep_operands_ok(const SelDecodeCall &c) {
+bool decode_step_operands_ok(const SelDecodeCall &c) {
     return c.d == 16 && c.l == 32 && c.l_sel == 64 && c.kcs % 8 == 0 && c.kcb % 8 == 0 && c.kcg % 8 == 0 && ((uintptr_t)c.K_cmp % 16 == 0) &&
            sel_attn_decode_wg_supported(attn_call(c, nullptr, 0, nullptr));
 }
@@ -941,7 +942,7 @@ bool decode_step_shape_plan(const SelDecodeCall &c, int *form, int *nsplit) {
 }
 
 bool decode_step_supported(const SelDecodeCall &c) {
-    return decode_step_shape_plan(c, nullptr, nullptr) && c.t0 >= 0 && c.S_kv >= c.t0 + 1 && dstep_operands_ok(c);
+    return decode_step_shape_plan(c, nullptr, nullptr) && c.t0 >= 0 && c.S_kv >= c.t0 + 1 && decode_step_operands_ok(c);
 }
 
 // raise the dynamic-LDS limit once per kernel (the runtime call costs about a millisecond)
@@ -974,6 +975,64 @@ static int dstep_blocks(const SelDecodeCall &c, float c2, DecStepBlocks *b) {
     return NSA_OK;
 }
 
+// ---- the kernel table: one function answers the instantiation of a launch -------------------------------------------------------
+using DecStepKernel = void (*)(DecStepParams, SelectParams, int, DecAttnArgs, DecBandPair);
+// run-time choices to compile-time constants, one pair of alternatives at a time: dstep_consts(f, Alt<A, B>{first}, ...) = f(A or B, ...)
+template <auto A, auto B>
+struct Alt {
+    bool first;
+};
+template <class F>
+static DecStepKernel dstep_consts(F f) {
+    return f();
+}
+template <class F, auto A, auto B, class... R>
+static DecStepKernel dstep_consts(F f, Alt<A, B> x, R... r) {
+    return x.first ? dstep_consts([&](auto... c) { return f(std::integral_constant<decltype(A), A>{}, c...); }, r...)
+                   : dstep_consts([&](auto... c) { return f(std::integral_constant<decltype(B), B>{}, c...); }, r...);
+}
+// hc: 6 = the group size at compile time, 0 = any h <= 16; cpw: chunks per wave (4: form 1); lng: the long-row form; onepass: form 2.  Null
+// for a combination no route launches: those are not instantiated either (the kernels' static_asserts forbid most of them)
+static DecStepKernel dstep_kernel(int dtype, int nw, bool split, int hc, int cpw, int D, bool rows, bool paged, bool lng, bool onepass) {
+    return dstep_consts(
+        [](auto BF, auto NW, auto SPLIT, auto HC, auto CPW, auto D_, auto ROWS, auto PAGED, auto LONG, auto ONE) -> DecStepKernel {
+            using T = std::conditional_t<BF, __bf16, _Float16>;
+            [[maybe_unused]] constexpr bool geom = D_ == 64 || (NW == 8 && CPW == 2);  // D = 128: eight waves, two chunks per wave
+            if constexpr (ONE) {
+                if constexpr (D_ == 64 && CPW == 2 && !SPLIT && !ROWS && !PAGED && !LONG) return decode_step_onepass_kernel<T, NW, HC>;
+            } else if constexpr (geom && (CPW == 2 || !(SPLIT || LONG)) && (ROWS ? !SPLIT : !(PAGED || LONG)))  // four chunks: unsplit, not long; rows: no team; paged, long: rows only
+                return decode_step_kernel<T, NW, SPLIT, HC, CPW, D_, ROWS, PAGED, LONG>;
+            return nullptr;
+        },
+        Alt<true, false>{dtype == NSA_DT_BF16}, Alt<16, 8>{nw == 16}, Alt<true, false>{split}, Alt<6, 0>{hc == 6}, Alt<2, 4>{cpw == 2}, Alt<64, 128>{D == 64},
+        Alt<true, false>{rows}, Alt<true, false>{paged}, Alt<true, false>{lng}, Alt<true, false>{onepass});
+}
+
+// What both launchers end with, for nw waves per row workgroup, ns workgroups per row and the plan's form.  own: the caller's fields of the
+// argument block (the team's workspace, tickets and poll budget; or S, the positions and the block table), the rest is filled here (c2 =
+// scale log2 e).  BP: the band pair of a layer step, its n_sel / n_w set for `grid`; null: the launch carries no band work.  lds_extra:
+// bytes behind the map (the paged form's table entries).  what: the launch's name in a HIP error
+static int dstep_launch(const SelDecodeCall &c, const DecStepParams &own, int nw, int ns, int form, int nchunk, bool rows, int64_t grid, size_t lds_extra,
+                        const DecBandPair *band, hipStream_t st, const char *what) {
+    const int D = c.Dk, h = c.h, cpw = form == 1 ? 4 : 2;
+    const float c2 = default_scale(c.scale, D) * LOG2E;
+    const DecStepParams P{c.Q, c.K_cmp, own.part_g, own.halo_g, own.pg_g, own.cnt, (int)c.rows(), c.G, h, c.S_cmp, c.S_sel, ns, nchunk, (nchunk + ns - 1) / ns, c.t0,
+                          own.spin, c.kcb, c.kcg, c.kcs, c2, own.S, own.t_pos, own.t_max, own.n_pages, own.block_table, own.bt_stride};
+    DecStepBlocks A{};
+    if (int rc = dstep_blocks(c, c2, &A)) return rc;
+    const DecStepKernel k = dstep_kernel(c.dtype, nw, ns > 1, h == 6 ? 6 : 0, cpw, D, rows, own.block_table != nullptr, form == 3, form == 2);
+    NSA_CHECK_ARG(k != nullptr, "decode step: no kernel for form %d at D = %d on %d waves", form, D, nw);
+    // the score data sits in V tiles 1 .. (the prefetching waves of the 16-wave form own tiles 0, 14, 15)
+    NSA_CHECK_ARG(dstep_score_bytes(nw, h, c.S_sel, cpw) <= dstep_score_room(nw, D), "decode step: S_sel too large");
+    if (int rc = dstep_raise_lds((void *)k)) return rc;
+    DecBandPair BP{};
+    BP.n_sel = 0xffffffffu;
+    if (band) BP = *band;
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(nw * 64), dstep_lds(nw, D) + lds_extra, st, P, A.SP, A.cand, A.AT, BP);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, what);
+    return NSA_OK;
+}
+
 int launch_decode_step(const SelDecodeCall &c, void *ws, size_t ws_bytes, hipStream_t st, const DecBandPair *band) {
     const int64_t R = c.rows();
     const int D = c.Dk, h = c.h;
@@ -982,44 +1041,19 @@ int launch_decode_step(const SelDecodeCall &c, void *ws, size_t ws_bytes, hipStr
     const int nchunk = ((c.S_cmp + 63) / 64);
     int nw = 16, ns = 1, form = 0;
     NSA_CHECK_ARG(decode_step_plan(R, nchunk, h, c.S_sel, D, &nw, &ns, &form), "decode step: shape not covered (decode_step_supported)");
-    const int cpw = form == 1 ? 4 : 2;
-    const float c2 = default_scale(c.scale, D) * LOG2E;
-    DecStepParams P{c.Q, c.K_cmp, nullptr, nullptr, nullptr, nullptr, (int)R, c.G, h, c.S_cmp, c.S_sel, ns, nchunk, (nchunk + ns - 1) / ns, c.t0, 0, c.kcb, c.kcg, c.kcs, c2};
-    P.spin = tuning(TUNE_DECODE_TEAM_SPIN) >= 0 ? tuning(TUNE_DECODE_TEAM_SPIN) : 512;  // polls of ~0.5-1 us each before a workgroup goes on alone
+    DecStepParams own{};
+    own.spin = tuning(TUNE_DECODE_TEAM_SPIN) >= 0 ? tuning(TUNE_DECODE_TEAM_SPIN) : 512;  // polls of ~0.5-1 us each before a workgroup goes on alone
     if (ns > 1) {
         NSA_CHECK_ARG(ws && ws_bytes >= decode_step_workspace(R, h, c.S_cmp) && ((uintptr_t)ws % 16 == 0), "decode step: workspace too small");
-        P.part_g = (float *)ws;
-        P.halo_g = P.part_g + (size_t)R * h * DSTEP_CH * 2;
-        P.pg_g = P.halo_g + (size_t)R * DSTEP_CH * 16;
-        P.cnt = decode_tickets(st, 2 * R);
-        NSA_CHECK_ARG(P.cnt != nullptr, "decode step: could not allocate the arrival tickets");
+        own.part_g = (float *)ws;
+        own.halo_g = own.part_g + (size_t)R * h * DSTEP_CH * 2;
+        own.pg_g = own.halo_g + (size_t)R * DSTEP_CH * 16;
+        own.cnt = decode_tickets(st, 2 * R);
+        NSA_CHECK_ARG(own.cnt != nullptr, "decode step: could not allocate the arrival tickets");
     }
-    DecStepBlocks A{};
-    if (int rc = dstep_blocks(c, c2, &A)) return rc;
-    void (*k)(DecStepParams, SelectParams, int, DecAttnArgs, DecBandPair);
-    const bool bf = c.dtype == NSA_DT_BF16, split = ns > 1;
-#define NSA_DSK(NW_, SP_, HC_) (bf ? decode_step_kernel<__bf16, NW_, SP_, HC_> : decode_step_kernel<_Float16, NW_, SP_, HC_>)
-#define NSA_DSK4(NW_, HC_) (bf ? decode_step_kernel<__bf16, NW_, false, HC_, 4> : decode_step_kernel<_Float16, NW_, false, HC_, 4>)
-#define NSA_DSK1(NW_, HC_) (bf ? decode_step_onepass_kernel<__bf16, NW_, HC_> : decode_step_onepass_kernel<_Float16, NW_, HC_>)
-#define NSA_DSK128(SP_, HC_) (bf ? decode_step_kernel<__bf16, 8, SP_, HC_, 2, 128> : decode_step_kernel<_Float16, 8, SP_, HC_, 2, 128>)
-    if (D == 128) {
-        NSA_CHECK_ARG(form == 0 && nw == 8, "decode step: D = 128 runs form 0 on eight waves");
-        k = h == 6 ? (split ? NSA_DSK128(true, 6) : NSA_DSK128(false, 6)) : (split ? NSA_DSK128(true, 0) : NSA_DSK128(false, 0));
-    } else if (form == 2) k = h == 6 ? (nw == 16 ? NSA_DSK1(16, 6) : NSA_DSK1(8, 6)) : (nw == 16 ? NSA_DSK1(16, 0) : NSA_DSK1(8, 0));
-    else if (cpw == 4) k = h == 6 ? (nw == 16 ? NSA_DSK4(16, 6) : NSA_DSK4(8, 6)) : (nw == 16 ? NSA_DSK4(16, 0) : NSA_DSK4(8, 0));
-    else if (h == 6) k = nw == 16 ? (split ? NSA_DSK(16, true, 6) : NSA_DSK(16, false, 6)) : (split ? NSA_DSK(8, true, 6) : NSA_DSK(8, false, 6));
-    else k = nw == 16 ? (split ? NSA_DSK(16, true, 0) : NSA_DSK(16, false, 0)) : (split ? NSA_DSK(8, true, 0) : NSA_DSK(8, false, 0));
-#undef NSA_DSK128
-#undef NSA_DSK1
-#undef NSA_DSK4
-#undef NSA_DSK
-    const size_t lds = dstep_lds(nw, D);
-    // the score data sits in V tiles 1 .. (the prefetching waves of the 16-wave form own tiles 0, 14, 15)
-    NSA_CHECK_ARG(dstep_score_bytes(nw, h, c.S_sel, cpw) <= dstep_score_room(nw, D), "decode step: S_sel too large");
-    if (int rc = dstep_raise_lds((void *)k)) return rc;
+    NSA_CHECK_ARG(D == 64 || (form == 0 && nw == 8), "decode step: D = 128 runs form 0 on eight waves");
     int64_t grid = ns > 1 ? ((R + 7) / 8) * 8 * ns : R;
     DecBandPair BP{};
-    BP.n_sel = 0xffffffffu;
     if (band) {  // the layer step's sliding + compressed branches on workgroups behind the step's own (decode_band_workgroup)
         BP = *band;
         int64_t waves[2];
@@ -1038,11 +1072,8 @@ int launch_decode_step(const SelDecodeCall &c, void *ws, size_t ws_bytes, hipStr
         grid += gw + gc;
     }
     static_assert(2 * Geo<64>::TILE_BYTES <= DEC_ATT_TILE, "a band wave keeps its K and V tile in the wave's V tile of the step");
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(nw * 64), lds, st, P, A.SP, A.cand, A.AT, BP);
-    NSA_LAUNCH_CHECK("decode_step");
-    return NSA_OK;
+    return dstep_launch(c, own, nw, ns, form, nchunk, false, grid, 0, band ? &BP : nullptr, st, "decode_step launch");
 }
-
 
 // The measured rule behind DECODE_ROWS = -1 (tools/bench_sel_decode_rows.py, table in DESIGN.md 4.1f; S in {1, 2, 4, 8} x 4k / 16k / 32k x
 // B in {1, 16}): one rows launch beat both S single decode steps and the separate launches in every cell except S = 1 at 32k, where the
@@ -1051,8 +1082,8 @@ int launch_decode_step(const SelDecodeCall &c, void *ws, size_t ws_bytes, hipStr
 static bool decode_rows_measured_ok(int S, int nchunk_max) { return !(S == 1 && nchunk_max >= 32); }
 
 // ---- rows form: S consecutive tokens per sequence in one launch (nsa_sel_decode_rows) -----------------------------------------------
-// compressed rows a decode step at token t sees, default geometry (l = 32, d = 16)
-static int dstep_ncmp(int t) { return t + 1 < 32 ? 0 : (t + 1 - 32) / 16 + 1; }
+// the unsplit exact form that holds a row of nchunk chunks on nw waves: 0 (two chunks per wave), at D = 64 1 (four), -1 = neither
+static int dstep_unsplit_form(int nw, int D, int nchunk) { return nchunk <= 2 * nw ? 0 : D == 64 && nchunk <= 4 * nw ? 1 : -1; }
 
 // Shape / tuning part of the rows form's predicate (default block geometry assumed).  One workgroup per row (b, s, g), the form and the
 // waves chosen for the launch from its LARGEST row (t0 + S - 1) and its row count B S G: form 0 (two chunks per wave) or, at D = 64, form 1
@@ -1063,22 +1094,19 @@ bool decode_rows_shape_plan(const SelDecodeCall &c, int *form, int *nw_out) {
     const int sw = tuning(TUNE_DECODE_ROWS), S = c.S, t0 = c.t0;
     if (tuning(TUNE_DECODE_STEP) == 0 || tuning(TUNE_DECODE_UNFUSED) > 0 || sw == 0) return false;
     if (c.B < 1 || S < 1 || S > 16 || c.G < 1 || c.h < 1 || c.h > 16 || c.Dk != c.Dv || (c.Dk != 64 && c.Dk != 128) || c.S_cmp < 1 || c.S_sel < 1) return false;
-    if (t0 < 0 || t0 > (1 << 30) || dstep_ncmp(t0) < 1 || c.S_kv < t0 + S) return false;  // every row has a compressed row and its own token in the cache
+    if (t0 < 0 || t0 > (1 << 30) || decode_ncmp(t0) < 1 || c.S_kv < t0 + S) return false;  // every row has a compressed row and its own token in the cache
     if (c.rows() > (1 << 24)) return false;
     const int nw = dec_att_waves(c.rows(), c.Dk);
-    const int n_max = std::min(c.S_cmp, dstep_ncmp(t0 + S - 1)), nchunk = (n_max + 63) / 64;
-    int fm;
-    if (nchunk <= 2 * nw) fm = 0;
-    else if (c.Dk == 64 && nchunk <= 4 * nw) fm = 1;
-    else return false;
-    if (!dstep_shape_ok(c, nw, fm)) return false;
+    const int n_max = std::min(c.S_cmp, decode_ncmp(t0 + S - 1)), nchunk = (n_max + 63) / 64;
+    const int fm = dstep_unsplit_form(nw, c.Dk, nchunk);
+    if (fm < 0 || !dstep_shape_ok(c, nw, fm)) return false;
     if (sw < 0 && !decode_rows_measured_ok(S, nchunk)) return false;
     if (form) *form = fm;
     if (nw_out) *nw_out = nw;
     return true;
 }
 
-bool decode_rows_supported(const SelDecodeCall &c) { return decode_rows_shape_plan(c, nullptr, nullptr) && dstep_operands_ok(c); }
+bool decode_rows_supported(const SelDecodeCall &c) { return decode_rows_shape_plan(c, nullptr, nullptr) && decode_step_operands_ok(c); }
 
 // ---- ragged form (nsa_sel_decode_ragged): the rows form with the position of sequence b read from a device array.  The host never reads
 // the array: form and waves are planned from the caller's bound t_max (the largest token any live row can sit at) and the row count exactly
@@ -1097,11 +1125,9 @@ bool decode_ragged_shape_plan(const SelDecodeCall &c, int t_max, int *form, int 
         c.S_kv < 1 || t_max < 0 || t_max > (1 << 30) || c.rows() > (1 << 24))
         return false;
     const int nw = dec_att_waves(c.rows(), c.Dk);
-    const int n_max = std::min(c.S_cmp, dstep_ncmp(t_max)), nchunk = (n_max + 63) / 64;
-    int fm;
-    if (nchunk <= 2 * nw) fm = 0;
-    else if (c.Dk == 64 && nchunk <= 4 * nw) fm = 1;
-    else if (tuning(TUNE_DECODE_LONG) > 0) {
+    const int n_max = std::min(c.S_cmp, decode_ncmp(t_max)), nchunk = (n_max + 63) / 64;
+    int fm = dstep_unsplit_form(nw, c.Dk, nchunk);
+    if (fm < 0 && tuning(TUNE_DECODE_LONG) > 0) {
         // the long-row form (form 3): any row of up to DSTEP_CH chunks, its later chunks swept twice.  t_max itself bounds the selection
         // blocks a live row needs (block t >> 6 must be one of 2048), whatever the buffers hold beyond it
         if (nchunk > DSTEP_CH || t_max >= 64 * 2048) {
@@ -1110,7 +1136,7 @@ bool decode_ragged_shape_plan(const SelDecodeCall &c, int t_max, int *form, int 
             return false;
         }
         fm = 3;
-    } else {
+    } else if (fm < 0) {
         *why = c.Dk == 128 ? "t_max is beyond the unsplit form at D = 128: more than 16 chunks of 64 compressed tokens per row"
                : nw == 16  ? "t_max is beyond the unsplit forms at 16 waves per row: more than 64 chunks of 64 compressed tokens per row"
                            : "t_max is beyond the unsplit forms at 8 waves per row (more than 256 rows): more than 32 chunks of 64 compressed tokens per row";
@@ -1121,8 +1147,6 @@ bool decode_ragged_shape_plan(const SelDecodeCall &c, int t_max, int *form, int 
     if (nw_out) *nw_out = nw;
     return true;
 }
-
-bool decode_ragged_operands_ok(const SelDecodeCall &c) { return dstep_operands_ok(c); }
 
 // ---- paged form (nsa_sel_decode_paged): the ragged form over pools of pages.  c.K_cmp / c.K / c.V are the pools, kcb / ksb / vsb their PAGE
 // strides and c.S_kv the capacity max_pages * 1024.  Form and waves are the ragged form's, from t_max and the row count alone -- same
@@ -1139,50 +1163,22 @@ int launch_decode_rows(const SelDecodeCall &c, hipStream_t st, const int32_t *t_
     if (pt) NSA_CHECK_ARG(t_pos && decode_paged_shape_plan(c, t_max, &form, &nw, nullptr), "decode paged: shape not covered (decode_paged_shape_plan)");
     else if (t_pos) NSA_CHECK_ARG(decode_ragged_shape_plan(c, t_max, &form, &nw, nullptr), "decode ragged: shape not covered (decode_ragged_shape_plan)");
     else NSA_CHECK_ARG(decode_rows_shape_plan(c, &form, &nw), "decode rows: shape not covered (decode_rows_supported)");
-    const int64_t R = c.rows();
-    const int D = c.Dk, h = c.h, cpw = form == 1 ? 4 : 2;
-    const int nchunk = (std::min(c.S_cmp, dstep_ncmp(t_pos ? t_max : c.t0 + c.S - 1)) + 63) / 64;  // of the largest row: every row derives its own
-    const float c2 = default_scale(c.scale, D) * LOG2E;
-    DecStepParams P{c.Q, c.K_cmp, nullptr, nullptr, nullptr, nullptr, (int)R, c.G, h, c.S_cmp, c.S_sel, 1, nchunk, nchunk, c.t0, 0, c.kcb, c.kcg, c.kcs, c2, c.S,
-                    t_pos, t_max};
+    const int nchunk = (std::min(c.S_cmp, decode_ncmp(t_pos ? t_max : c.t0 + c.S - 1)) + 63) / 64;  // of the largest row: every row derives its own
+    DecStepParams own{};
+    own.S = c.S;
+    own.t_pos = t_pos;
+    own.t_max = t_max;
     if (pt) {
         // (every table entry the kernel follows is < n_pages, every needed index < max_pages: c.S_kv = max_pages * 1024 bounds the positions)
         NSA_CHECK_ARG(pt->table && pt->n_pages >= 1 && pt->stride >= (int64_t)c.S_kv / DEC_PAGE_TOKENS, "decode paged: bad block table");
-        P.n_pages = pt->n_pages;
-        P.block_table = pt->table;
-        P.bt_stride = pt->stride;
+        own.n_pages = pt->n_pages;
+        own.block_table = pt->table;
+        own.bt_stride = pt->stride;
     }
-    DecStepBlocks A{};
-    if (int rc = dstep_blocks(c, c2, &A)) return rc;
-    void (*k)(DecStepParams, SelectParams, int, DecAttnArgs, DecBandPair);
-    const bool bf = c.dtype == NSA_DT_BF16;
     // (the paged form is an instantiation of its own: the rows / ragged instantiations hold none of its code)
-#define NSA_DSR1(NW_, HC_, CPW_, D_, PG_) \
-    (bf ? decode_step_kernel<__bf16, NW_, false, HC_, CPW_, D_, true, PG_> : decode_step_kernel<_Float16, NW_, false, HC_, CPW_, D_, true, PG_>)
-#define NSA_DSR(NW_, HC_, CPW_, D_) (pt ? NSA_DSR1(NW_, HC_, CPW_, D_, true) : NSA_DSR1(NW_, HC_, CPW_, D_, false))
-#define NSA_DSL1(NW_, HC_, D_, PG_) \
-    (bf ? decode_step_kernel<__bf16, NW_, false, HC_, 2, D_, true, PG_, true> : decode_step_kernel<_Float16, NW_, false, HC_, 2, D_, true, PG_, true>)
-#define NSA_DSL(NW_, HC_, D_) (pt ? NSA_DSL1(NW_, HC_, D_, true) : NSA_DSL1(NW_, HC_, D_, false))
-    if (form == 3) {  // the long-row form: D = 64 on 16 / 8 waves, D = 128 on 8
-        NSA_CHECK_ARG(D == 64 || nw == 8, "decode rows: D = 128 runs on eight waves");
-        if (D == 128) k = h == 6 ? NSA_DSL(8, 6, 128) : NSA_DSL(8, 0, 128);
-        else k = h == 6 ? (nw == 16 ? NSA_DSL(16, 6, 64) : NSA_DSL(8, 6, 64)) : (nw == 16 ? NSA_DSL(16, 0, 64) : NSA_DSL(8, 0, 64));
-    } else if (D == 128) {
-        NSA_CHECK_ARG(form == 0 && nw == 8, "decode rows: D = 128 runs form 0 on eight waves");
-        k = h == 6 ? NSA_DSR(8, 6, 2, 128) : NSA_DSR(8, 0, 2, 128);
-    } else if (cpw == 4) k = h == 6 ? (nw == 16 ? NSA_DSR(16, 6, 4, 64) : NSA_DSR(8, 6, 4, 64)) : (nw == 16 ? NSA_DSR(16, 0, 4, 64) : NSA_DSR(8, 0, 4, 64));
-    else k = h == 6 ? (nw == 16 ? NSA_DSR(16, 6, 2, 64) : NSA_DSR(8, 6, 2, 64)) : (nw == 16 ? NSA_DSR(16, 0, 2, 64) : NSA_DSR(8, 0, 2, 64));
-#undef NSA_DSL
-#undef NSA_DSL1
-#undef NSA_DSR
-#undef NSA_DSR1
-    if (int rc = dstep_raise_lds((void *)k)) return rc;
-    DecBandPair BP{};
-    BP.n_sel = 0xffffffffu;  // (no band workgroups on this form)
-    hipLaunchKernelGGL(k, dim3((unsigned)R), dim3(nw * 64), dstep_lds(nw, D) + (pt ? sizeof(int) * DSTEP_PAGES : 0), st, P, A.SP, A.cand, A.AT, BP);
-    if (pt) NSA_LAUNCH_CHECK("decode_paged");
-    else NSA_LAUNCH_CHECK("decode_rows");
-    return NSA_OK;
+    if (form == 3) NSA_CHECK_ARG(c.Dk == 64 || nw == 8, "decode rows: D = 128 runs on eight waves");  // the long-row form: D = 64 on 16 / 8 waves, D = 128 on 8
+    else NSA_CHECK_ARG(c.Dk == 64 || (form == 0 && nw == 8), "decode rows: D = 128 runs form 0 on eight waves");
+    return dstep_launch(c, own, nw, 1, form, nchunk, true, c.rows(), pt ? sizeof(int) * DSTEP_PAGES : 0, nullptr, st, pt ? "decode_paged launch" : "decode_rows launch");
 }
 
 }  // namespace nsa
