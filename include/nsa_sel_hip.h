@@ -53,6 +53,7 @@ extern "C" {
 #define NSA_DT_F32 0
 #define NSA_DT_BF16 1
 #define NSA_DT_F16 2
+#define NSA_DT_FP8_E4M3 3 /* OCP e4m3 (torch.float8_e4m3fn, max 448): K / V caches of the nsa_sel_decode_*_fp8 calls only */
 
 /* selector semantics */
 #define NSA_SEL_SEQUENTIAL 0 /* select_topn_ranges        (decode, sequential prefill) */
@@ -697,6 +698,65 @@ NSA_API int nsa_sel_decode_paged(const void *Q, const void *Kc_pool, const void 
                          void *stream);
 NSA_API int nsa_sel_decode_paged_plan(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int max_pages, int page_tokens,
                               int n_top, int dtype, int t_max, int *launches /* host */, int *form /* host */);
+
+/* ---------------------------------------------------------------------------------------
+ * FP8 K/V caches for the ragged and the paged decode step of the selected branch: nsa_sel_decode_ragged / nsa_sel_decode_paged with the
+ * gathered K and V held as OCP e4m3 bytes (NSA_DT_FP8_E4M3) and ONE fp32 scale per (sequence or page, group, token row):
+ *     K^[r, :] = float(K8[r, :]) * k_scale[r],   V^[r, :] = float(V8[r, :]) * v_scale[r].
+ * Half the bytes of the gather, twice the tokens per pool.  Q, K_cmp, the taps, scoring, top-n and the output dtype are those of the bf16
+ * call: the selection does not read K / V, so ranges_out is that call's bit for bit.  The attention stays on the bf16 MFMAs (e4m3 converts
+ * to bf16 exactly; Q and P keep bf16 precision): the K scale multiplies the fp32 logit, x = (q . K8[key]) scale log2e k_scale[key]; the V
+ * scale multiplies the probability before it is rounded to the MFMA operand, P[key] = bf16(p v_scale[key]); the row sum takes the unscaled
+ * p.  Waves, chunk order, contraction order and merge order are the bf16 call's: with every scale 1.0f, O is bit for bit the bf16 call's O
+ * on the dequantised caches.
+ *   K / V (pools)   e4m3 bytes, rows contiguous: k_stride_s = Dk, v_stride_s = Dv (strides count elements = bytes); 16-byte aligned, batch
+ *                   (page) and group strides multiples of 16
+ *   k_scale, v_scale   fp32 [B, G, S_kv] (paged: pools [n_pages, G, 1024]), unit row stride, 4-byte aligned; *_stride_b / _p and *_stride_g in
+ *                   elements.  Paged: a scale is addressed through the same checked page id as its row -- plane of page p, row t & 1023 -- so
+ *                   no table value can send a scale load outside the scale pools.  Scales of rows behind a sequence's tokens are never read.
+ * Everything else as in the bf16 calls (inactive sequences, bounds, the table).  Served: dtype (of Q / O / K_cmp) bf16; Dk = Dv in {64, 128};
+ * h <= 16; the unsplit forms 0 and 1 (D = 128: form 0).  DECLINED with NSA_ERR_INVALID and a message naming the limit: f16 or fp32
+ * queries; a t_max beyond forms 0 / 1 whatever DECODE_LONG says (the long-row form, form 3, is not built for FP8); DECODE_STEP = 0 or
+ * DECODE_UNFUSED = 1; K / V row strides other than D; a null scale.  The _plan queries answer as the bf16 ones for served shapes and
+ * launches 0, form -1 for declined ones; the _workspace queries answer 0.
+ *
+ * nsa_kv_quantize_fp8: rows [t0, t1) of a bf16 tensor X [B, G, S, D] (element strides; rows of D in {64, 128} contiguous elements, 16-byte
+ * aligned, strides multiples of 8) -> X8 (e4m3, byte strides multiples of 8, 8-byte aligned) and scale [B, G, S] fp32 (unit row stride):
+ *     scale = amax(|x|) / 448.0f (IEEE fp32 division; 1.0f for an all-zero row),  X8 = e4m3_rne(clamp(x / scale, -448, 448)).
+ * Rows outside [t0, t1) are untouched.  One launch: what keeps an FP8 mirror of the selected branch's K / V current, per appended chunk.
+ * nsa_paged_kv_quantize_fp8: the same for tokens [t0, t1) of ONE slot of paged pools -- X_pool bf16 [n_pages, G, 1024, D] -> X8_pool and
+ * scale_pool [n_pages, G, 1024], token r at row r & 1023 of page table_row[r >> 10] (table_row: device int32 [max_pages], the slot's row of
+ * the block table).  The host does not read the table; the kernel forms an address only from an entry it has tested against [0, n_pages):
+ * the rows of any other entry are skipped, as nsa_paged_kv_store does.
+ * ------------------------------------------------------------------------------------- */
+NSA_API size_t nsa_sel_decode_ragged_fp8_workspace(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int n_top, int dtype);
+NSA_API int nsa_sel_decode_ragged_fp8(const void *Q, const void *K_cmp, const void *K8, const void *V8, const float *k_scale, const float *v_scale,
+                              const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int32_t *ranges_out, void *O,
+                              const int32_t *t_pos /* device, [B] */, int t_max /* host */, int B, int S, int G, int h, int Dk, int Dv, int S_cmp,
+                              int S_sel, int S_kv, int l, int d, int l_sel, int n_top, int64_t kc_stride_b, int64_t kc_stride_g,
+                              int64_t kc_stride_s, int64_t k_stride_b, int64_t k_stride_g, int64_t k_stride_s, int64_t v_stride_b,
+                              int64_t v_stride_g, int64_t v_stride_s, int64_t ks_stride_b, int64_t ks_stride_g, int64_t vs_stride_b,
+                              int64_t vs_stride_g, int dtype, float scale, void *workspace, size_t workspace_bytes, void *stream);
+NSA_API int nsa_sel_decode_ragged_fp8_plan(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int n_top, int dtype, int t_max,
+                                   int *launches /* host */, int *form /* host */);
+NSA_API size_t nsa_sel_decode_paged_fp8_workspace(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int n_top, int dtype);
+NSA_API int nsa_sel_decode_paged_fp8(const void *Q, const void *Kc_pool, const void *K8_pool, const void *V8_pool, const float *k_scale_pool,
+                             const float *v_scale_pool, const int32_t *block_table /* device, [B,max_pages] */, int64_t table_stride, int n_pages,
+                             int max_pages, int page_tokens, const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals,
+                             int32_t *ranges_out, void *O, const int32_t *t_pos /* device, [B] */, int t_max /* host */, int B, int S, int G, int h,
+                             int Dk, int Dv, int S_cmp, int S_sel, int l, int d, int l_sel, int n_top, int64_t kc_stride_p, int64_t kc_stride_g,
+                             int64_t kc_stride_s, int64_t k_stride_p, int64_t k_stride_g, int64_t k_stride_s, int64_t v_stride_p,
+                             int64_t v_stride_g, int64_t v_stride_s, int64_t ks_stride_p, int64_t ks_stride_g, int64_t vs_stride_p,
+                             int64_t vs_stride_g, int dtype, float scale, void *workspace, size_t workspace_bytes, void *stream);
+NSA_API int nsa_sel_decode_paged_fp8_plan(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int max_pages, int page_tokens, int n_top,
+                                  int dtype, int t_max, int *launches /* host */, int *form /* host */);
+NSA_API int nsa_kv_quantize_fp8(const void *X, void *X8, float *scale, int B, int G, int S, int D, int t0, int t1, int64_t x_stride_b,
+                        int64_t x_stride_g, int64_t x_stride_s, int64_t q_stride_b, int64_t q_stride_g, int64_t q_stride_s, int64_t s_stride_b,
+                        int64_t s_stride_g, void *stream);
+NSA_API int nsa_paged_kv_quantize_fp8(const void *X_pool, void *X8_pool, float *scale_pool, const int32_t *table_row /* device, [max_pages] */,
+                              int n_pages, int max_pages, int G, int D, int t0, int t1, int64_t x_stride_p, int64_t x_stride_g,
+                              int64_t x_stride_s, int64_t q_stride_p, int64_t q_stride_g, int64_t q_stride_s, int64_t s_stride_p,
+                              int64_t s_stride_g, void *stream);
 
 /* Band attention forward with per-sequence positions (the sliding and the compressed branch of a ragged decode step): nsa_band_attn_fwd
  * with t0 replaced by a device array.  Query row (b, t) sits at absolute position t_pos[b] + t; hi and lo follow from it by the formula

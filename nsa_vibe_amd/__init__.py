@@ -21,13 +21,17 @@ from .selection_attention import (  # noqa: F401
     selection_attention_varlen_all,
     selection_attention_varlen_all_v2,
     hip_sel_available,
+    quantize_kv_fp8,
+    quantize_kv_fp8_paged,
     select_and_attend,
     selection_attention_first_key_parity,
     selection_attention_head_causal_parity,
     selection_attention_hip,
     selection_decode_paged,
+    selection_decode_paged_fp8_plan,
     selection_decode_paged_plan,
     selection_decode_ragged,
+    selection_decode_ragged_fp8_plan,
     selection_decode_ragged_plan,
     selection_decode_rows,
     selection_decode_rows_plan,

@@ -119,6 +119,14 @@ SIGNATURES = {
     "nsa_sel_decode_paged_workspace": (_sz, [_i] * 10),
     "nsa_sel_decode_paged": (_i, [_vp] * 5 + [_i64] + [_i] * 3 + [_vp] * 6 + [_i] * 13 + [_i64] * 9 + [_i, _f, _vp, _sz, _vp]),
     "nsa_sel_decode_paged_plan": (_i, [_i] * 13 + [C.POINTER(_i)] * 2),
+    "nsa_sel_decode_ragged_fp8_workspace": (_sz, [_i] * 10),
+    "nsa_sel_decode_ragged_fp8": (_i, [_vp] * 12 + [_i] * 14 + [_i64] * 13 + [_i, _f, _vp, _sz, _vp]),
+    "nsa_sel_decode_ragged_fp8_plan": (_i, [_i] * 12 + [C.POINTER(_i)] * 2),
+    "nsa_sel_decode_paged_fp8_workspace": (_sz, [_i] * 10),
+    "nsa_sel_decode_paged_fp8": (_i, [_vp] * 7 + [_i64] + [_i] * 3 + [_vp] * 6 + [_i] * 13 + [_i64] * 13 + [_i, _f, _vp, _sz, _vp]),
+    "nsa_sel_decode_paged_fp8_plan": (_i, [_i] * 13 + [C.POINTER(_i)] * 2),
+    "nsa_kv_quantize_fp8": (_i, [_vp] * 3 + [_i] * 6 + [_i64] * 8 + [_vp]),
+    "nsa_paged_kv_quantize_fp8": (_i, [_vp] * 4 + [_i] * 6 + [_i64] * 8 + [_vp]),
     "nsa_band_attn_fwd_ragged_workspace": (_sz, [_i] * 7),
     "nsa_band_attn_fwd_ragged": (_i, [_vp] * 6 + [_i] * 8 + [_i64] * 6 + [_i] * 4 + [_i, _f, _i, _vp, _sz, _vp]),
     "nsa_band_attn_fwd_paged_workspace": (_sz, [_i] * 7),

@@ -700,6 +700,19 @@ int nsa::sel_decode_rows_impl(const SelDecodeCall &c, void *workspace, size_t wo
     return sel_attn_fwd_impl(attn_call(c, w + W.a + W.p, workspace_bytes - W.a - W.p, stream), 0, nullptr);
 }
 
+// what the FP8 K/V forms ask of their caches beyond the bf16 checks (kv_dtype = NSA_DT_FP8_E4M3; nothing otherwise)
+static int decode_fp8_operands(const char *who, const SelDecodeCall &c) {
+    if (c.kv_dtype != NSA_DT_FP8_E4M3) return NSA_OK;
+    NSA_CHECK_ARG(c.k_scale && c.v_scale, "%s: FP8 K/V caches need both k_scale and v_scale", who);
+    NSA_CHECK_ARG(c.kss == c.Dk && c.vss == c.Dv, "%s: FP8 K/V rows must be contiguous: a row stride of D = %d bytes (got %lld for K, %lld for V)", who, c.Dk,
+                  (long long)c.kss, (long long)c.vss);
+    NSA_CHECK_ARG(c.ksb % 16 == 0 && c.ksg % 16 == 0 && c.vsb % 16 == 0 && c.vsg % 16 == 0,
+                  "%s: FP8 K/V batch (page) and group strides must be multiples of 16 bytes", who);
+    NSA_CHECK_ARG((uintptr_t)c.k_scale % 4 == 0 && (uintptr_t)c.v_scale % 4 == 0 && c.kzb >= 0 && c.kzg >= 0 && c.vzb >= 0 && c.vzg >= 0,
+                  "%s: the scales must be 4-byte aligned fp32 with non-negative strides", who);
+    return NSA_OK;
+}
+
 int nsa::sel_decode_ragged_impl(const SelDecodeCall &c, const int32_t *t_pos, int t_max, void *stream) {
     NSA_CHECK_ARG(dtype_ok(c.dtype), "decode_ragged: unknown dtype %d", c.dtype);
     NSA_CHECK_ARG(c.B >= 0 && c.S >= 0 && c.G >= 1 && c.h >= 1 && c.Dk >= 1 && c.Dv >= 1 && c.S_cmp >= 0 && c.S_sel >= 1 && c.S_kv >= 1, "decode_ragged: bad sizes");
@@ -717,6 +730,7 @@ int nsa::sel_decode_ragged_impl(const SelDecodeCall &c, const int32_t *t_pos, in
     NSA_CHECK_ARG(c.d == 16 && c.l == 32 && c.l_sel == 64, "decode_ragged: the default block geometry only (l = 32, d = 16, l' = 64)");
     NSA_CHECK_ARG(decode_step_operands_ok(c), "decode_ragged: Q, K_cmp, K and V must be 16-byte aligned with strides in multiples of 8 elements, "
                                                 "V rows contiguous and O 8-byte aligned");
+    if (int rc = decode_fp8_operands("decode_ragged", c)) return rc;
     return launch_decode_rows(c, (hipStream_t)stream, t_pos, t_max);
 }
 
@@ -753,6 +767,7 @@ int nsa::sel_decode_paged_impl(const SelDecodeCall &c0, const DecPageTable &pt, 
     NSA_CHECK_ARG(c.kss >= 1 && c.vss >= 1 && c.kcs >= 1 && (int64_t)DEC_PAGE_TOKENS * c.kss * 2 < lim && (int64_t)DEC_PAGE_TOKENS * c.vss * 2 < lim &&
                       (int64_t)(DEC_PAGE_TOKENS / 16) * c.kcs * 2 < lim,
                   "decode_paged: the row strides put a page's rows outside the 32-bit offsets of one (page, group) plane (1024 rows of K / V, 64 of K_cmp: under 2 GiB each)");
+    if (int rc = decode_fp8_operands("decode_paged", c)) return rc;
     return launch_decode_rows(c, (hipStream_t)stream, t_pos, t_max, &pt);
 }
 
@@ -878,6 +893,71 @@ int nsa_sel_decode_paged_plan(int B, int S, int G, int h, int Dk, int Dv, int S_
     if (page_tokens == DEC_PAGE_TOKENS &&
         decode_paged_shape_plan(sel_decode_plan_call(B, S, G, h, Dk, Dv, S_cmp, S_sel, max_pages * DEC_PAGE_TOKENS, n_top, dtype), t_max, form, nullptr, nullptr))
         *launches = 1;
+    return NSA_OK;
+}
+
+// ---- FP8 K/V forms of the two calls above: the same blocks with kv_dtype and the scales set, the same impl, plan and launch tail
+static SelDecodeCall with_fp8(SelDecodeCall c, const float *k_scale, const float *v_scale, int64_t kzb, int64_t kzg, int64_t vzb, int64_t vzg) {
+    c.kv_dtype = NSA_DT_FP8_E4M3;
+    c.k_scale = k_scale; c.v_scale = v_scale; c.kzb = kzb; c.kzg = kzg; c.vzb = vzb; c.vzg = vzg;
+    return c;
+}
+
+int nsa_sel_decode_ragged_fp8(const void *Q, const void *K_cmp, const void *K8, const void *V8, const float *k_scale, const float *v_scale, const int32_t *csc_ptr,
+                              const int32_t *csc_rows, const float *csc_vals, int32_t *ranges_out, void *O, const int32_t *t_pos, int t_max, int B, int S, int G,
+                              int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int l, int d, int l_sel, int n_top, int64_t kcb, int64_t kcg, int64_t kcs,
+                              int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg, int64_t vss, int64_t kzb, int64_t kzg, int64_t vzb, int64_t vzg,
+                              int dtype, float scale, void *workspace, size_t workspace_bytes, void *stream) {
+    (void)workspace, (void)workspace_bytes;
+    const SelDecodeCall c{Q, K_cmp, K8, V8, csc_ptr, csc_rows, csc_vals, ranges_out, O, B, S, G, h, Dk, Dv, S_cmp, S_sel, S_kv, l, d, l_sel, n_top, 0,
+                          kcb, kcg, kcs, ksb, ksg, kss, vsb, vsg, vss, dtype, scale};
+    return sel_decode_ragged_impl(with_fp8(c, k_scale, v_scale, kzb, kzg, vzb, vzg), t_pos, t_max, stream);
+}
+
+int nsa_sel_decode_paged_fp8(const void *Q, const void *Kc_pool, const void *K8_pool, const void *V8_pool, const float *k_scale_pool, const float *v_scale_pool,
+                             const int32_t *block_table, int64_t table_stride, int n_pages, int max_pages, int page_tokens, const int32_t *csc_ptr,
+                             const int32_t *csc_rows, const float *csc_vals, int32_t *ranges_out, void *O, const int32_t *t_pos, int t_max, int B, int S, int G,
+                             int h, int Dk, int Dv, int S_cmp, int S_sel, int l, int d, int l_sel, int n_top, int64_t kcp, int64_t kcg, int64_t kcs, int64_t ksp,
+                             int64_t ksg, int64_t kss, int64_t vsp, int64_t vsg, int64_t vss, int64_t kzp, int64_t kzg, int64_t vzp, int64_t vzg, int dtype,
+                             float scale, void *workspace, size_t workspace_bytes, void *stream) {
+    (void)workspace, (void)workspace_bytes;
+    const SelDecodeCall c{Q, Kc_pool, K8_pool, V8_pool, csc_ptr, csc_rows, csc_vals, ranges_out, O, B, S, G, h, Dk, Dv, S_cmp, S_sel, 0, l, d, l_sel, n_top, 0,
+                          kcp, kcg, kcs, ksp, ksg, kss, vsp, vsg, vss, dtype, scale};
+    return sel_decode_paged_impl(with_fp8(c, k_scale_pool, v_scale_pool, kzp, kzg, vzp, vzg), DecPageTable{block_table, table_stride, n_pages}, max_pages,
+                                 page_tokens, t_pos, t_max, stream);
+}
+
+size_t nsa_sel_decode_ragged_fp8_workspace(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int n_top, int dtype) {
+    return nsa_sel_decode_ragged_workspace(B, S, G, h, Dk, Dv, S_cmp, S_sel, n_top, dtype);
+}
+size_t nsa_sel_decode_paged_fp8_workspace(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int n_top, int dtype) {
+    return nsa_sel_decode_paged_workspace(B, S, G, h, Dk, Dv, S_cmp, S_sel, n_top, dtype);
+}
+
+int nsa_sel_decode_ragged_fp8_plan(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int S_kv, int n_top, int dtype, int t_max, int *launches,
+                                   int *form) {
+    NSA_CHECK_ARG(launches && form, "decode_ragged_fp8_plan: null pointer");
+    NSA_CHECK_ARG(dtype_ok(dtype), "decode_ragged_fp8_plan: unknown dtype %d", dtype);
+    NSA_CHECK_ARG(B >= 1 && S >= 1 && G >= 1 && h >= 1 && Dk >= 1 && Dv >= 1 && S_cmp >= 0 && S_sel >= 1 && S_kv >= 1 && n_top >= 1 && n_top <= 64 && t_max >= 0,
+                  "decode_ragged_fp8_plan: bad sizes");
+    SelDecodeCall c = sel_decode_plan_call(B, S, G, h, Dk, Dv, S_cmp, S_sel, S_kv, n_top, dtype);
+    c.kv_dtype = NSA_DT_FP8_E4M3;
+    *launches = decode_ragged_shape_plan(c, t_max, form, nullptr, nullptr) ? 1 : 0;
+    return NSA_OK;
+}
+
+int nsa_sel_decode_paged_fp8_plan(int B, int S, int G, int h, int Dk, int Dv, int S_cmp, int S_sel, int max_pages, int page_tokens, int n_top, int dtype, int t_max,
+                                  int *launches, int *form) {
+    NSA_CHECK_ARG(launches && form, "decode_paged_fp8_plan: null pointer");
+    NSA_CHECK_ARG(dtype_ok(dtype), "decode_paged_fp8_plan: unknown dtype %d", dtype);
+    NSA_CHECK_ARG(B >= 1 && S >= 1 && G >= 1 && h >= 1 && Dk >= 1 && Dv >= 1 && S_cmp >= 0 && S_sel >= 1 && max_pages >= 1 && max_pages <= (1 << 20) &&
+                      page_tokens >= 1 && n_top >= 1 && n_top <= 64 && t_max >= 0,
+                  "decode_paged_fp8_plan: bad sizes");
+    *launches = 0;
+    *form = -1;
+    SelDecodeCall c = sel_decode_plan_call(B, S, G, h, Dk, Dv, S_cmp, S_sel, max_pages * DEC_PAGE_TOKENS, n_top, dtype);
+    c.kv_dtype = NSA_DT_FP8_E4M3;
+    if (page_tokens == DEC_PAGE_TOKENS && decode_paged_shape_plan(c, t_max, form, nullptr, nullptr)) *launches = 1;
     return NSA_OK;
 }
 

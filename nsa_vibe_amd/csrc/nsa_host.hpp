@@ -60,6 +60,11 @@ struct SelDecodeCall {
     int64_t kcb, kcg, kcs, ksb, ksg, kss, vsb, vsg, vss;
     int dtype;
     float scale;
+    // FP8 K/V (nsa_sel_decode_ragged_fp8 / _paged_fp8): kv_dtype = NSA_DT_FP8_E4M3 -- K / V are e4m3 bytes (their strides count bytes) with one fp32
+    // scale per row, batch (page) and group strides in elements; 0: K / V have the call's dtype
+    int kv_dtype;
+    const float *k_scale, *v_scale;
+    int64_t kzb, kzg, vzb, vzg;
     int64_t rows() const { return (int64_t)B * S * G; }
 };
 // the layer calls' block: rows t0 .. t0 + S - 1 over the caches kv, which then hold t0 + S tokens and n_cmp compressed ones; the caller adds

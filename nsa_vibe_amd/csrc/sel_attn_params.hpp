@@ -140,6 +140,10 @@ struct DecAttnArgs {
     int G, h, S_kv, n;
     int64_t ksb, ksg, kss, vsb, vsg, vss;
     float c2;  // scale * log2(e)
+    // FP8 K/V (nsa_sel_decode_ragged_fp8 / _paged_fp8; the kernel's FP8 instantiations alone read these): K / V are OCP e4m3 bytes and row r of
+    // plane (b, g) -- paged: (page, g) -- is K8[r, :] * k_scale[b kzb + g kzg + r]; element strides, the rows of a plane contiguous
+    const float *k_scale, *v_scale;
+    int64_t kzb, kzg, vzb, vzg;
 };
 struct DecStepParams {
     const void *Q;   // [R,h,D]

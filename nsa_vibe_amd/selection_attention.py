@@ -298,7 +298,8 @@ def selection_decode_ragged_plan(B: int, S: int, G: int, h: int, Dk: int, Dv: in
 
 def selection_decode_ragged(Q: torch.Tensor, K_cmp: torch.Tensor, K: torch.Tensor, V: torch.Tensor, meta, n_top: int, t_pos, *,
                             t_max: Optional[int] = None, scale: Optional[float] = None, out: Optional[torch.Tensor] = None,
-                            ranges_out: Optional[torch.Tensor] = None):
+                            ranges_out: Optional[torch.Tensor] = None, k_scale: Optional[torch.Tensor] = None,
+                            v_scale: Optional[torch.Tensor] = None):
     """The decode step of the selected branch for a batch whose sequences sit at DIFFERENT positions, in one native call
     (nsa_sel_decode_ragged: the rows form of the one-launch step with a device array of positions).
 
@@ -312,6 +313,9 @@ def selection_decode_ragged(Q: torch.Tensor, K_cmp: torch.Tensor, K: torch.Tenso
     Where the native call declines (selection_decode_ragged_plan: launches 0 -- a t_max beyond the unsplit forms unless the tuning switch
     DECODE_LONG = 1 lets the long-row form take it, up to t_max = 131,071) host positions run one selection_decode_rows call per active
     sequence on that sequence's views (same ranges, O from that route); device positions raise RuntimeError with the library's message.
+    FP8 caches: K and V as torch.float8_e4m3fn with k_scale / v_scale fp32 [B,G,S_kv] (one scale per row, K^[r] = K8[r] * k_scale[r];
+    quantize_kv_fp8 makes them) run nsa_sel_decode_ragged_fp8 -- half the gather traffic, bf16 Q only, forms 0 / 1, the same ranges.  FP8 K / V
+    require both scales, bf16 / f16 K / V forbid them; a declined FP8 shape has no fallback and raises the library's message.
     Returns (O [B,S,G,h,Dv], ranges [B,S,G,n_top,2] int32).  Inference only."""
     who = "selection_decode_ragged"
     if Q.dim() != 5:
@@ -323,12 +327,13 @@ def selection_decode_ragged(Q: torch.Tensor, K_cmp: torch.Tensor, K: torch.Tenso
         raise RuntimeError("all tensors must be on the same device")
     S_kv, Dv = K.shape[2], V.shape[3]
     S_cmp, S_sel = K_cmp.shape[2], meta.S_sel
-    O = out if out is not None else torch.empty((B, S, G, h, Dv), dtype=V.dtype, device=dev)
+    zs = _fp8_scales(who, K, V, k_scale, v_scale, (B, G, S_kv))
+    O = out if out is not None else torch.empty((B, S, G, h, Dv), dtype=Q.dtype if zs else V.dtype, device=dev)
     rg = ranges_out if ranges_out is not None else torch.empty((B, S, G, n_top, 2), dtype=torch.int32, device=dev)
     if O.numel() == 0:
         return O, rg
     dt = _DT[Q.dtype]
-    if host is not None and selection_decode_ragged_plan(B, S, G, h, Dk, Dv, S_cmp, S_sel, S_kv, n_top, t_max, Q.dtype)["launches"] == 0:
+    if host is not None and not zs and selection_decode_ragged_plan(B, S, G, h, Dk, Dv, S_cmp, S_sel, S_kv, n_top, t_max, Q.dtype)["launches"] == 0:
         # declined (a t_max beyond the unsplit forms, fp32, ...): the positions are known here, so each active sequence takes the rows call
         O.zero_()
         rg.zero_()
@@ -346,11 +351,105 @@ def selection_decode_ragged(Q: torch.Tensor, K_cmp: torch.Tensor, K: torch.Tenso
     pos = _positions_to(dev, t_pos, host)
     cptr, crows, cvals = meta.device_csc(dev)
     ws = workspace(dev, L.nsa_sel_decode_ragged_workspace(B, S, G, h, Dk, Dv, S_cmp, S_sel, n_top, dt), "decode_ragged")
+    if zs:
+        (kz, *kzs), (vz, *vzs) = zs
+        rc = L.nsa_sel_decode_ragged_fp8(Qc.data_ptr(), Kc.data_ptr() if S_cmp else None, Kk.data_ptr(), Vv.data_ptr(), kz.data_ptr(), vz.data_ptr(),
+                                         cptr.data_ptr(), crows.data_ptr(), cvals.data_ptr(), rg.data_ptr(), O.data_ptr(), pos.data_ptr(), t_max, B, S, G, h,
+                                         Dk, Dv, S_cmp, S_sel, S_kv, int(meta.l), int(meta.d), int(meta.l_sel), int(n_top), *cs, *ks, *vs, *kzs, *vzs, dt,
+                                         _scale_arg(scale), *_ws_args(ws), _stream(dev))
+        _lib.check(rc, "nsa_sel_decode_ragged_fp8")
+        return O, rg
     rc = L.nsa_sel_decode_ragged(Qc.data_ptr(), Kc.data_ptr() if S_cmp else None, Kk.data_ptr(), Vv.data_ptr(), cptr.data_ptr(), crows.data_ptr(),
                                  cvals.data_ptr(), rg.data_ptr(), O.data_ptr(), pos.data_ptr(), t_max, B, S, G, h, Dk, Dv, S_cmp, S_sel, S_kv,
                                  int(meta.l), int(meta.d), int(meta.l_sel), int(n_top), *cs, *ks, *vs, dt, _scale_arg(scale), *_ws_args(ws), _stream(dev))
     _lib.check(rc, "nsa_sel_decode_ragged")
     return O, rg
+
+
+FP8 = torch.float8_e4m3fn  # the FP8 K / V cache format: OCP e4m3, max 448 (gfx950's native fp8)
+
+
+def _fp8_scales(who: str, K: torch.Tensor, V: torch.Tensor, k_scale, v_scale, lead, suffix: str = ""):
+    """the scales of FP8 K / V as the C ABI takes them -> ((k_scale, batch stride, group stride), (v_scale, ...)), or None for bf16 / f16
+    K / V.  FP8 K / V require both scales (fp32, shape `lead`, unit row stride: they are used in place), anything else forbids them."""
+    names = f"k_scale{suffix} / v_scale{suffix}"
+    if K.dtype != FP8 and V.dtype != FP8:
+        if k_scale is not None or v_scale is not None:
+            raise RuntimeError(f"{who}: {names} belong to FP8 K / V (torch.float8_e4m3fn); K / V are {K.dtype} / {V.dtype}")
+        return None
+    if K.dtype != FP8 or V.dtype != FP8:
+        raise RuntimeError(f"{who}: K and V must both be torch.float8_e4m3fn (got {K.dtype} / {V.dtype})")
+    if k_scale is None or v_scale is None:
+        raise RuntimeError(f"{who}: FP8 K / V need both {names} (one fp32 scale per row)")
+    out = []
+    for name, z in (("k_scale" + suffix, k_scale), ("v_scale" + suffix, v_scale)):
+        if z.dtype != torch.float32 or tuple(z.shape) != tuple(lead) or z.stride(-1) != 1 or z.device != K.device:
+            raise RuntimeError(f"{who}: {name} must be fp32 {list(lead)} with unit row stride on the caches' device (got {z.dtype} {list(z.shape)}, row stride "
+                               f"{z.stride(-1) if z.dim() else 0})")
+        out.append((z, z.stride(0), z.stride(1)))
+    return out
+
+
+def selection_decode_ragged_fp8_plan(B: int, S: int, G: int, h: int, Dk: int, Dv: int, S_cmp: int, S_sel: int, S_kv: int, n_top: int, t_max: int,
+                                     dtype: torch.dtype = torch.bfloat16) -> dict:
+    """selection_decode_ragged_plan for FP8 K / V (nsa_sel_decode_ragged_fp8_plan): the bf16 call's answer for served shapes (bf16 queries, forms
+    0 / 1), {"launches": 0, "form": -1} for declined ones (f16 / fp32 queries, a t_max beyond form 1 whatever DECODE_LONG says, DECODE_UNFUSED = 1)."""
+    ints = _plan_ints("nsa_sel_decode_ragged_fp8_plan", 2, int(B), int(S), int(G), int(h), int(Dk), int(Dv), int(S_cmp), int(S_sel), int(S_kv), int(n_top),
+                      _DT[dtype], int(t_max))
+    return dict(zip(("launches", "form"), ints))
+
+
+def selection_decode_paged_fp8_plan(B: int, S: int, G: int, h: int, Dk: int, Dv: int, S_cmp: int, S_sel: int, max_pages: int, n_top: int, t_max: int,
+                                    dtype: torch.dtype = torch.bfloat16, page_tokens: int = 1024) -> dict:
+    """selection_decode_paged_plan for FP8 pools (nsa_sel_decode_paged_fp8_plan)."""
+    ints = _plan_ints("nsa_sel_decode_paged_fp8_plan", 2, int(B), int(S), int(G), int(h), int(Dk), int(Dv), int(S_cmp), int(S_sel), int(max_pages),
+                      int(page_tokens), int(n_top), _DT[dtype], int(t_max))
+    return dict(zip(("launches", "form"), ints))
+
+
+def quantize_kv_fp8(X: torch.Tensor, t0: int = 0, t1: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                    scale_out: Optional[torch.Tensor] = None):
+    """Rows [t0, t1) of a bf16 K or V cache X [B,G,S,D] (any batch / group / row strides, D in {64, 128} contiguous) -> (X8 torch.float8_e4m3fn
+    [B,G,S,D], scale fp32 [B,G,S]) in one launch (nsa_kv_quantize_fp8): scale = amax / 448 in fp32 (1 for an all-zero row), X8 =
+    e4m3(clamp(x / scale, -448, 448)) rounded to nearest even.  out / scale_out: the mirror to update in place -- rows outside [t0, t1) are
+    untouched (fresh tensors are zero-filled there, with scale 1)."""
+    who = "quantize_kv_fp8"
+    dev = _need_gpu(X)
+    if X.dim() != 4 or X.dtype != torch.bfloat16 or X.stride(-1) != 1:
+        raise RuntimeError(f"{who}: X must be bf16 [B,G,S,D] with a contiguous last dimension (got {X.dtype} {tuple(X.shape)})")
+    B, G, S, D = X.shape
+    t1 = S if t1 is None else int(t1)
+    X8 = out if out is not None else torch.zeros((B, G, S, D), dtype=FP8, device=dev)
+    sc = scale_out if scale_out is not None else torch.ones((B, G, S), dtype=torch.float32, device=dev)
+    if X8.dtype != FP8 or tuple(X8.shape) != (B, G, S, D) or X8.stride(-1) != 1 or sc.dtype != torch.float32 or tuple(sc.shape) != (B, G, S) or sc.stride(-1) != 1:
+        raise RuntimeError(f"{who}: out must be float8_e4m3fn {[B, G, S, D]} and scale_out fp32 {[B, G, S]}, both with a contiguous last dimension")
+    rc = _lib.lib().nsa_kv_quantize_fp8(X.data_ptr(), X8.data_ptr(), sc.data_ptr(), B, G, S, D, int(t0), t1, X.stride(0), X.stride(1), X.stride(2),
+                                        X8.stride(0), X8.stride(1), X8.stride(2), sc.stride(0), sc.stride(1), _stream(dev))
+    _lib.check(rc, "nsa_kv_quantize_fp8")
+    return X8, sc
+
+
+def quantize_kv_fp8_paged(X_pool: torch.Tensor, table_row: torch.Tensor, t0: int, t1: int, out: torch.Tensor, scale_out: torch.Tensor):
+    """quantize_kv_fp8 for tokens [t0, t1) of ONE slot of paged pools (nsa_paged_kv_quantize_fp8): X_pool bf16 [n_pages, G, 1024, D] -> out
+    float8_e4m3fn [n_pages, G, 1024, D] and scale_out fp32 [n_pages, G, 1024] in place, token r at row r & 1023 of page table_row[r >> 10].
+    table_row: the slot's row of the block table, a device int32 tensor [max_pages] (never read back; rows of an entry outside [0, n_pages)
+    are skipped).  Returns (out, scale_out)."""
+    who = "quantize_kv_fp8_paged"
+    dev = _need_gpu(X_pool, out, scale_out, table_row)
+    _unit_rows_pool(who, "X_pool", X_pool, PAGE_TOKENS)
+    _unit_rows_pool(who, "out", out, PAGE_TOKENS)
+    n_pages, G, _, D = X_pool.shape
+    if X_pool.dtype != torch.bfloat16 or out.dtype != FP8 or tuple(out.shape) != tuple(X_pool.shape):
+        raise RuntimeError(f"{who}: X_pool must be bf16 and out float8_e4m3fn of the same shape")
+    if scale_out.dtype != torch.float32 or tuple(scale_out.shape) != (n_pages, G, PAGE_TOKENS) or scale_out.stride(-1) != 1:
+        raise RuntimeError(f"{who}: scale_out must be fp32 {[n_pages, G, PAGE_TOKENS]} with unit row stride")
+    if table_row.dtype != torch.int32 or table_row.dim() != 1 or table_row.stride(0) != 1:
+        raise RuntimeError(f"{who}: table_row must be a contiguous device int32 tensor [max_pages]")
+    rc = _lib.lib().nsa_paged_kv_quantize_fp8(X_pool.data_ptr(), out.data_ptr(), scale_out.data_ptr(), table_row.data_ptr(), n_pages, table_row.shape[0], G, D,
+                                              int(t0), int(t1), X_pool.stride(0), X_pool.stride(1), X_pool.stride(2), out.stride(0), out.stride(1),
+                                              out.stride(2), scale_out.stride(0), scale_out.stride(1), _stream(dev))
+    _lib.check(rc, "nsa_paged_kv_quantize_fp8")
+    return out, scale_out
 
 
 PAGE_TOKENS = 1024  # tokens per cache page of the paged decode step: one scorer chunk (64 compressed rows), 16 selection blocks
@@ -377,7 +476,8 @@ def _unit_rows_pool(who: str, name: str, X: torch.Tensor, rows: int):
 
 def selection_decode_paged(Q: torch.Tensor, Kc_pool: torch.Tensor, K_pool: torch.Tensor, V_pool: torch.Tensor, block_table: torch.Tensor, meta,
                            n_top: int, t_pos, t_max: Optional[int] = None, out: Optional[torch.Tensor] = None,
-                           ranges_out: Optional[torch.Tensor] = None, *, scale: Optional[float] = None):
+                           ranges_out: Optional[torch.Tensor] = None, *, scale: Optional[float] = None, k_scale_pool: Optional[torch.Tensor] = None,
+                           v_scale_pool: Optional[torch.Tensor] = None):
     """selection_decode_ragged over PAGED caches, in one native call (nsa_sel_decode_paged).
 
     K_pool / V_pool [n_pages, G, 1024, D] and Kc_pool [n_pages, G, 64, D] are pools of pages (views with page, group and row strides are
@@ -389,7 +489,9 @@ def selection_decode_paged(Q: torch.Tensor, Kc_pool: torch.Tensor, K_pool: torch
     min(t_max, capacity - 1)) or when one of the table entries it needs, j = 0 .. (t_pos[b] + S - 1) >> 10, lies outside [0, n_pages).
     For a table that scatters contiguous caches into pages the result is selection_decode_ragged's on those caches bit for bit.
     There is no per-sequence fallback: the contiguous operators cannot read a pool, so a declined shape (selection_decode_paged_plan:
-    launches 0; a t_max beyond the unsplit forms is one unless the tuning switch DECODE_LONG = 1, which reaches t_max = 131,071) raises RuntimeError with the library's message.  Returns (O [B,S,G,h,Dv], ranges [B,S,G,n_top,2] int32).  Inference only."""
+    launches 0; a t_max beyond the unsplit forms is one unless the tuning switch DECODE_LONG = 1, which reaches t_max = 131,071) raises RuntimeError with the library's message.
+    FP8 pools: K_pool / V_pool as torch.float8_e4m3fn with k_scale_pool / v_scale_pool fp32 [n_pages, G, 1024] run nsa_sel_decode_paged_fp8 (as
+    selection_decode_ragged's FP8 form; a scale is found through the same checked page id as its row).  Returns (O [B,S,G,h,Dv], ranges [B,S,G,n_top,2] int32).  Inference only."""
     who = "selection_decode_paged"
     if Q.dim() != 5:
         raise RuntimeError(f"{who}: expected Q[B,S,G,h,Dk]")
@@ -412,7 +514,8 @@ def selection_decode_paged(Q: torch.Tensor, Kc_pool: torch.Tensor, K_pool: torch
     if Kc.shape[0] != n_pages or Vv.shape[0] != n_pages or not (Kc.shape[1] == Kk.shape[1] == Vv.shape[1] == G) or Kk.shape[3] != Dk or Kc.shape[3] != Dk:
         raise RuntimeError(f"{who}: the three pools must share n_pages and G = {G}, with Dk = {Dk} columns in Kc_pool and K_pool")
     S_cmp, S_sel = min(int(meta.S_cmp), max_pages * (PAGE_TOKENS // 16)), meta.S_sel
-    O = out if out is not None else torch.empty((B, S, G, h, Dv), dtype=V_pool.dtype, device=dev)
+    zs = _fp8_scales(who, K_pool, V_pool, k_scale_pool, v_scale_pool, (n_pages, G, PAGE_TOKENS), "_pool")
+    O = out if out is not None else torch.empty((B, S, G, h, Dv), dtype=Q.dtype if zs else V_pool.dtype, device=dev)
     rg = ranges_out if ranges_out is not None else torch.empty((B, S, G, n_top, 2), dtype=torch.int32, device=dev)
     if O.numel() == 0:
         return O, rg
@@ -422,6 +525,14 @@ def selection_decode_paged(Q: torch.Tensor, Kc_pool: torch.Tensor, K_pool: torch
     pos = _positions_to(dev, t_pos, host)
     cptr, crows, cvals = meta.device_csc(dev)
     ws = workspace(dev, L.nsa_sel_decode_paged_workspace(B, S, G, h, Dk, Dv, S_cmp, S_sel, n_top, dt), "decode_paged")
+    if zs:
+        (kz, *kzs), (vz, *vzs) = zs
+        rc = L.nsa_sel_decode_paged_fp8(Qc.data_ptr(), Kc.data_ptr(), Kk.data_ptr(), Vv.data_ptr(), kz.data_ptr(), vz.data_ptr(), bt.data_ptr(), bt.stride(0),
+                                        n_pages, max_pages, PAGE_TOKENS, cptr.data_ptr(), crows.data_ptr(), cvals.data_ptr(), rg.data_ptr(), O.data_ptr(),
+                                        pos.data_ptr(), t_max, B, S, G, h, Dk, Dv, S_cmp, S_sel, int(meta.l), int(meta.d), int(meta.l_sel), int(n_top), *cs,
+                                        *ks, *vs, *kzs, *vzs, dt, _scale_arg(scale), *_ws_args(ws), _stream(dev))
+        _lib.check(rc, "nsa_sel_decode_paged_fp8")
+        return O, rg
     rc = L.nsa_sel_decode_paged(Qc.data_ptr(), Kc.data_ptr(), Kk.data_ptr(), Vv.data_ptr(), bt.data_ptr(), bt.stride(0), n_pages, max_pages, PAGE_TOKENS,
                                 cptr.data_ptr(), crows.data_ptr(), cvals.data_ptr(), rg.data_ptr(), O.data_ptr(), pos.data_ptr(), t_max, B, S, G, h, Dk, Dv,
                                 S_cmp, S_sel, int(meta.l), int(meta.d), int(meta.l_sel), int(n_top), *cs, *ks, *vs, dt, _scale_arg(scale), *_ws_args(ws),
