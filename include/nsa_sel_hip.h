@@ -803,6 +803,44 @@ NSA_API int nsa_band_attn_fwd_paged(const void *Q, const void *K_pool, const voi
                             int64_t v_stride_g, int64_t v_stride_s, int a, int dd, int c, int w, int dtype, float scale, void *workspace,
                             size_t workspace_bytes, void *stream);
 
+/* FP8 (OCP e4m3) K/V for nsa_band_attn_fwd_ragged and nsa_band_attn_fwd_paged: the sliding and the compressed branch of a ragged decode
+ * step read caches of half the bytes.  Semantics as nsa_sel_decode_*_fp8: K^[r] = float(K8[r]) * k_scale[r], V^ likewise; Q, O and lse stay
+ * bf16 / fp32 and the arithmetic stays on the bf16 MFMAs (e4m3 -> bf16 is exact).  k_scale enters the fp32 logit behind the QK MFMA, v_scale
+ * the probability before it is rounded to the PV operand; the row sum stays unscaled.  With all scales 1.0f, O and lse are those of the bf16
+ * call on the dequantised caches bit for bit: the plan, the 32-key tiles, the split shares, the masks and the combine pass are that call's.
+ *   K8, V8 (pools)  e4m3 bytes, [B, G, S_kv, D] (pools: [n_pages, G, page_rows, D]); batch (page) and group strides in bytes, multiples of
+ *                   16, bases 16-byte aligned; rows contiguous: the row stride must be D.
+ *   k_scale, v_scale  fp32 [B, G, S_kv] (pools: [n_pages, G, page_rows]) with batch (page) and group strides in elements and unit row
+ *                   stride.  Paged: a scale is found through the same checked page id as its row.  Scales and rows behind a wave's last key
+ *                   are never read, and a key outside a row's interval contributes exactly zero whatever its scale holds.
+ * Everything else as in the bf16 calls (positions, inactive sequences, the table and its verdict, page sizes).  Workspace and split count are
+ * the bf16 calls'.  Served: dtype (of Q / O) bf16, Dk = Dv in {64, 128}, h <= 16.  DECLINED with NSA_ERR_INVALID and a message naming the
+ * limit: f16 or fp32 queries; a null scale; a K / V row stride other than D; S_kv < 1 or w < 1; a missing, misaligned or too small workspace
+ * where the plan splits (the bf16 calls then run unsplit; this one keeps one form per shape); everything nsa_band_attn_fwd_paged declines.
+ * There is no generic-kernel route and no fallback.  Forward only.
+ * nsa_paged_kv_quantize_fp8_rows: nsa_paged_kv_quantize_fp8 with the page size as an argument, a power of two in [32, 65536] -- pools
+ * [n_pages, G, page_rows, D] and [n_pages, G, page_rows], token r at row r & (page_rows - 1) of page table_row[r / page_rows]: the FP8 mirror
+ * of the 64-row K_cmp / V_cmp pools.  nsa_paged_kv_quantize_fp8 is this call at 1024. */
+NSA_API size_t nsa_band_attn_fwd_ragged_fp8_workspace(int B, int S, int G, int h, int Dk, int Dv, int dtype);
+NSA_API int nsa_band_attn_fwd_ragged_fp8(const void *Q, const void *K8, const void *V8, const float *k_scale, const float *v_scale, void *O,
+                                 float *lse, const int32_t *t_pos /* device, [B] */, int t_max /* host */, int B, int S, int G, int h, int Dk,
+                                 int Dv, int S_kv, int64_t k_stride_b, int64_t k_stride_g, int64_t k_stride_s, int64_t v_stride_b,
+                                 int64_t v_stride_g, int64_t v_stride_s, int64_t ks_stride_b, int64_t ks_stride_g, int64_t vs_stride_b,
+                                 int64_t vs_stride_g, int a, int dd, int c, int w, int dtype, float scale, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+NSA_API size_t nsa_band_attn_fwd_paged_fp8_workspace(int B, int S, int G, int h, int Dk, int Dv, int dtype);
+NSA_API int nsa_band_attn_fwd_paged_fp8(const void *Q, const void *K8_pool, const void *V8_pool, const float *k_scale_pool,
+                                const float *v_scale_pool, const int32_t *block_table /* device, [B,max_pages] */, int64_t table_stride,
+                                int n_pages, int max_pages, int page_rows, void *O, float *lse, const int32_t *t_pos /* device, [B] */,
+                                int t_max /* host */, int B, int S, int G, int h, int Dk, int Dv, int64_t k_stride_p, int64_t k_stride_g,
+                                int64_t k_stride_s, int64_t v_stride_p, int64_t v_stride_g, int64_t v_stride_s, int64_t ks_stride_p,
+                                int64_t ks_stride_g, int64_t vs_stride_p, int64_t vs_stride_g, int a, int dd, int c, int w, int dtype,
+                                float scale, void *workspace, size_t workspace_bytes, void *stream);
+NSA_API int nsa_paged_kv_quantize_fp8_rows(const void *X_pool, void *X8_pool, float *scale_pool, const int32_t *table_row /* device, [max_pages] */,
+                                   int n_pages, int max_pages, int page_rows, int G, int D, int t0, int t1, int64_t x_stride_p,
+                                   int64_t x_stride_g, int64_t x_stride_s, int64_t q_stride_p, int64_t q_stride_g, int64_t q_stride_s,
+                                   int64_t s_stride_p, int64_t s_stride_g, void *stream);
+
 /* indices [R,K] int32 ascending with -1 padding -> ranges [R,K,2]; clamp end to t+1. */
 NSA_API int nsa_indices_to_ranges_v2(const int32_t *indices, int64_t R, int S, int G, int t0, int K, int S_sel,
                              int l_sel, int32_t *ranges_out, void *stream);

@@ -131,6 +131,11 @@ SIGNATURES = {
     "nsa_band_attn_fwd_ragged": (_i, [_vp] * 6 + [_i] * 8 + [_i64] * 6 + [_i] * 4 + [_i, _f, _i, _vp, _sz, _vp]),
     "nsa_band_attn_fwd_paged_workspace": (_sz, [_i] * 7),
     "nsa_band_attn_fwd_paged": (_i, [_vp] * 4 + [_i64] + [_i] * 3 + [_vp] * 3 + [_i] * 7 + [_i64] * 6 + [_i] * 4 + [_i, _f, _vp, _sz, _vp]),
+    "nsa_band_attn_fwd_ragged_fp8_workspace": (_sz, [_i] * 7),
+    "nsa_band_attn_fwd_ragged_fp8": (_i, [_vp] * 8 + [_i] * 8 + [_i64] * 10 + [_i] * 4 + [_i, _f, _vp, _sz, _vp]),
+    "nsa_band_attn_fwd_paged_fp8_workspace": (_sz, [_i] * 7),
+    "nsa_band_attn_fwd_paged_fp8": (_i, [_vp] * 6 + [_i64] + [_i] * 3 + [_vp] * 3 + [_i] * 7 + [_i64] * 10 + [_i] * 4 + [_i, _f, _vp, _sz, _vp]),
+    "nsa_paged_kv_quantize_fp8_rows": (_i, [_vp] * 4 + [_i] * 7 + [_i64] * 8 + [_vp]),
     "nsa_batched_ranges_width": (_i, [_i] * 6),
     "nsa_select_topn_ranges": (_i, [_vp, _i64, _i, _i, _i, _vp] + [_i] * 7 + [_vp, _i, _vp]),
     "nsa_sel_select_attn_fwd": (_i, [_vp, _i, _vp] + [_i] * 7 + [_vp, _i] + [_vp] * 5 + [_i] * 7 + [_i64] * 6 + [_i, _f, _vp, _sz, _vp]),

@@ -19,7 +19,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .selection_attention import _bwd_variant, _positions_to, _ragged_positions, _unit_rows_pool
+from .selection_attention import FP8, _bwd_variant, _fp8_scales, _positions_to, _ragged_positions, _unit_rows_pool
 from ._native import _DT, _need_gpu, _needs_grad, _scale_arg, _stream, _unit_rows, _ws_args, workspace, workspace_at
 
 _W_INF = 2 ** 30
@@ -126,6 +126,61 @@ def _fwd_paged(Q, K_pool, V_pool, block_table, band, scale, want_lse, t_pos, t_m
     return O, lse
 
 
+def _fwd_fp8(Q, K8, V8, zs, block_table, band, scale, want_lse, t_pos, t_max):
+    """the ragged and the paged forward over FP8 K / V (nsa_band_attn_fwd_ragged_fp8 / _paged_fp8): e4m3 rows with one fp32 scale per row,
+    [B,G,S_kv] or, with a block table, pools [n_pages,G,page_rows] (zs: _fp8_scales' answer); O in Q's dtype.  Checked before anything
+    native is touched"""
+    paged = block_table is not None
+    who = "band attention (FP8 K/V, paged)" if paged else "band attention (FP8 K/V)"
+    if Q.dim() != 5 or K8.dim() != 4 or V8.dim() != 4:
+        raise RuntimeError(f"{who}: expected Q[B,S,G,h,D] and K / V [B,G,S_kv,D] or pools [n_pages,G,page_rows,D]")
+    B, S, G, h, Dk = Q.shape
+    if t_pos is None:
+        raise RuntimeError(f"{who}: FP8 K / V need the per-sequence positions t_pos (the scalar-t0 call has no FP8 kernel)")
+    if band[0] != 0:
+        raise RuntimeError(f"{who}: t_pos and a non-zero t0 are mutually exclusive")
+    if Q.requires_grad or K8.requires_grad or V8.requires_grad:
+        raise RuntimeError(f"{who}: FP8 K / V are forward only (there is no backward over quantised caches): no input may require grad")
+    if Q.dtype != torch.bfloat16:
+        raise RuntimeError(f"{who}: FP8 K / V take bf16 queries only (got {Q.dtype})")
+    lead, Dv = tuple(K8.shape[:3]), V8.shape[3]
+    if tuple(V8.shape[:3]) != lead or K8.shape[3] != Dk or lead[1] != G or (not paged and lead[0] != B):
+        raise RuntimeError(f"{who}: inconsistent shapes")
+    if K8.stride(3) != 1 or V8.stride(3) != 1 or K8.stride(2) != Dk or V8.stride(2) != Dv:
+        raise RuntimeError(f"{who}: FP8 K / V rows must be contiguous (row stride = D bytes); they are used in place")
+    t_pos, t_max, host = _ragged_positions(who, t_pos, t_max, B, S)
+    bt = block_table
+    if paged and (not isinstance(bt, torch.Tensor) or bt.dtype != torch.int32 or bt.dim() != 2 or bt.shape[0] != B or bt.shape[1] < 1 or bt.stride(1) != 1):
+        raise RuntimeError(f"{who}: block_table must be a device int32 tensor [B, max_pages >= 1] with a contiguous last dimension")
+    dev = _need_gpu(Q, K8, V8, *((bt,) if paged else ()))
+    if host is None and t_pos.device != dev:
+        raise RuntimeError("all tensors must be on the same device")
+    t0, a, dd, c, w = band
+    O = torch.empty((B, S, G, h, Dv), dtype=Q.dtype, device=dev)
+    lse = torch.empty((B, S, G, h), dtype=torch.float32, device=dev) if want_lse else None
+    if O.numel() == 0:
+        return O, lse
+    L = _lib.lib()
+    dt = _DT[Q.dtype]
+    Qc, pos = Q.contiguous(), _positions_to(dev, t_pos, host)
+    (kz, *kzs), (vz, *vzs) = zs
+    kv = (K8.data_ptr(), V8.data_ptr(), kz.data_ptr(), vz.data_ptr())
+    out = (O.data_ptr(), lse.data_ptr() if lse is not None else None, pos.data_ptr(), t_max, B, S, G, h, Dk, Dv)
+    strides = (K8.stride(0), K8.stride(1), K8.stride(2), V8.stride(0), V8.stride(1), V8.stride(2), *kzs, *vzs)
+    tail = (int(a), int(dd), int(c), int(min(w, _W_INF)), dt, _scale_arg(scale))
+    if paged:
+        ws = workspace(dev, L.nsa_band_attn_fwd_paged_fp8_workspace(B, S, G, h, Dk, Dv, dt), "band")
+        name = "nsa_band_attn_fwd_paged_fp8"
+        rc = L.nsa_band_attn_fwd_paged_fp8(Qc.data_ptr(), *kv, bt.data_ptr(), bt.stride(0), lead[0], bt.shape[1], lead[2], *out, *strides, *tail,
+                                           *_ws_args(ws), _stream(dev))
+    else:
+        ws = workspace(dev, L.nsa_band_attn_fwd_ragged_fp8_workspace(B, S, G, h, Dk, Dv, dt), "band")
+        name = "nsa_band_attn_fwd_ragged_fp8"
+        rc = L.nsa_band_attn_fwd_ragged_fp8(Qc.data_ptr(), *kv, *out, lead[2], *strides, *tail, *_ws_args(ws), _stream(dev))
+    _lib.check(rc, name)
+    return O, lse
+
+
 class _BandAttnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, Q, K, V, band, scale, variant, bwd_variant):
@@ -159,7 +214,8 @@ class _BandAttnFn(torch.autograd.Function):
 
 def band_attention_hip(Q, K, V, *, t0: int = 0, a: int = 0, dd: int = 1, c: int = 0, w: int = _W_INF,
                        scale: Optional[float] = None, variant: int = 0, return_lse: bool = False,
-                       bwd_variant: Optional[int] = None, t_pos=None, t_max: Optional[int] = None, block_table=None):
+                       bwd_variant: Optional[int] = None, t_pos=None, t_max: Optional[int] = None, block_table=None,
+                       k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None):
     """Row t attends keys [max(0, hi - w), hi), hi = (t0+t+1 >= a) ? min(S_kv, (t0+t+1-a)//dd + c) : 0.
 
     variant: 0 auto, 1 generic, 2 MFMA (forward); bwd_variant: the same for the backward, None = 0 unless variant is 1.
@@ -174,8 +230,18 @@ def band_attention_hip(Q, K, V, *, t0: int = 0, a: int = 0, dd: int = 1, c: int 
     sequence is inactive (zero rows, lse = -inf, nothing read) under the ragged rule, or when a table entry it needs -- those covering its
     key rows from the window start of its first row to the end of its last -- lies outside [0, n_pages); entries outside that set are never
     read.  O and lse are those of the ragged call on the contiguous caches bit for bit.  bf16 / f16 at D = 64 or 128 only: anything else
-    raises the library's message, there is no fallback.  variant is not used."""
+    raises the library's message, there is no fallback.  variant is not used.
+    k_scale / v_scale (FP8 caches, nsa_band_attn_fwd_ragged_fp8 / _paged_fp8; forward only, needs t_pos): K and V as torch.float8_e4m3fn with
+    contiguous rows and one fp32 scale per key row, K^[r] = K8[r] * k_scale[r] -- tensors [B,G,S_kv], or with block_table scale pools
+    [n_pages,G,page_rows] addressed like the pools (quantize_kv_fp8 / quantize_kv_fp8_paged make them).  Half the K/V bytes; bf16 queries at
+    D = 64 or 128 only, O in Q's dtype; with all scales 1 the bits of the bf16 call on the dequantised caches.  FP8 K / V require both
+    scales, bf16 / f16 K / V forbid them; the scalar-t0 and the autograd path have no FP8 form and say so."""
     band = (int(t0), int(a), int(dd), int(c), int(w))
+    if K.dtype == FP8 or V.dtype == FP8 or k_scale is not None or v_scale is not None:
+        zs = _fp8_scales("band attention", K, V, k_scale, v_scale, K.shape[:3])  # (scales beside bf16 / f16 K / V raise here)
+        if zs is not None:
+            O, lse = _fwd_fp8(Q, K, V, zs, block_table, band, scale, return_lse, t_pos, t_max)
+            return (O, lse) if return_lse else O
     if block_table is not None:
         O, lse = _fwd_paged(Q, K, V, block_table, band, scale, return_lse, t_pos, t_max)
         return (O, lse) if return_lse else O
@@ -193,21 +259,23 @@ def band_attention_hip(Q, K, V, *, t0: int = 0, a: int = 0, dd: int = 1, c: int 
 
 
 def sliding_window_attention(Q, K, V, w: int, *, t0: int = 0, scale: Optional[float] = None, variant: int = 0, t_pos=None,
-                             t_max: Optional[int] = None, block_table=None):
+                             t_max: Optional[int] = None, block_table=None, k_scale=None, v_scale=None):
     """Keys [t-w+1 .. t] of row t (reference attention_kernels.py:146-178; w <= 0 or no keys -> zeros, :153-154).
     t_pos / t_max: per-sequence positions of a ragged batch; block_table: K / V are pools of pages (band_attention_hip; pages of 1024
-    rows share their page ids with selection_decode_paged)."""
+    rows share their page ids with selection_decode_paged); k_scale / v_scale: K / V are FP8 (e4m3) with one fp32 scale per row."""
     return band_attention_hip(Q, K, V, t0=t0, a=0, dd=1, c=0, w=max(int(w), 0), scale=scale, variant=variant, t_pos=t_pos, t_max=t_max,
-                              block_table=block_table)
+                              block_table=block_table, k_scale=k_scale, v_scale=v_scale)
 
 
 def batched_causal_attention_compressed(Q, K_cmp, V_cmp, l: int, d: int, *, t0: int = 0, scale: Optional[float] = None,
-                                        variant: int = 0, t_pos=None, t_max: Optional[int] = None, block_table=None):
+                                        variant: int = 0, t_pos=None, t_max: Optional[int] = None, block_table=None, k_scale=None,
+                                        v_scale=None):
     """Keys [0, num_cmp(t)), num_cmp(t) = 0 if t+1 < l else (t+1-l)//d + 1, clamped to S_cmp (attention_kernels.py:118-121).
     t_pos / t_max: per-sequence positions of a ragged batch; block_table: K_cmp / V_cmp are pools of pages (band_attention_hip; pages of
-    64 rows at d = 16 share their page ids with selection_decode_paged)."""
+    64 rows at d = 16 share their page ids with selection_decode_paged); k_scale / v_scale: K_cmp / V_cmp are FP8 (e4m3) with one fp32
+    scale per row (the scorer's K_cmp stays bf16: the selection does not change)."""
     return band_attention_hip(Q, K_cmp, V_cmp, t0=t0, a=int(l), dd=int(d), c=1, w=_W_INF, scale=scale, variant=variant, t_pos=t_pos,
-                              t_max=t_max, block_table=block_table)
+                              t_max=t_max, block_table=block_table, k_scale=k_scale, v_scale=v_scale)
 
 
 def batched_causal_attention_compressed_first_key_parity(Q, K_cmp, V_cmp, l: int, d: int, *, t0: int = 0):

@@ -197,7 +197,7 @@ __global__ __launch_bounds__(256, 2) void band_attn_bwd_dq_kernel(BandAttnParams
 // NT = 3 column tiles per wave (48 / h tokens) once there are enough tokens to fill the chip, NT = 1 (16 / h tokens)
 // below that; with very few token groups (decode) the key interval is also split over several waves.
 // (D = 128: 2 column tiles, the accumulators are twice as wide)
-static void band_plan(int B, int S, int G, int h, int D, int *nt, int *tpw, int *nsplit) {
+void band_plan(int B, int S, int G, int h, int D, int *nt, int *tpw, int *nsplit) {
     const int ntw = D == 64 ? 3 : 2;
     const int tpw3 = 16 * ntw / h, tpw1 = 16 / h;
     const int64_t grp3 = (int64_t)B * G * ((S + tpw3 - 1) / tpw3);

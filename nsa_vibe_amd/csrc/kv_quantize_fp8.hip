@@ -4,9 +4,10 @@
 // A row is D / 8 lanes of 16 bytes (8 lanes at D = 64, 16 at D = 128), so a wave takes 8 / 4 rows at once: one 16-byte load per lane, the
 // row's absmax by xor-shuffles inside the row's lanes, eight divisions, four v_cvt_pk_fp8_f32 (the instruction does not saturate: 465 and
 // beyond would become NaN, hence the clamp), one 8-byte store per lane and one scale store per row.  Rows outside [t0, t1) are not touched.
-// Paged form: source and destination are pools [n_pages, G, 1024, D] / [n_pages, G, 1024] under ONE table row; token r lives in row r & 1023
-// of page table[r >> 10].  The page id is tested against [0, n_pages) before any address is formed from it and a row whose entry fails is
-// skipped, as the paged copy kernels do (paged_kv_copy.hip).
+// Paged form: source and destination are pools [n_pages, G, page_rows, D] / [n_pages, G, page_rows] under ONE table row; token r lives in row
+// r & (page_rows - 1) of page table[r / page_rows] (nsa_paged_kv_quantize_fp8: page_rows = 1024, the selected branch's pages;
+// nsa_paged_kv_quantize_fp8_rows: any power of two in [32, 65536], the band branches' -- 64 for K_cmp / V_cmp).  The page id is tested against
+// [0, n_pages) before any address is formed from it and a row whose entry fails is skipped, as the paged copy kernels do (paged_kv_copy.hip).
 #include "nsa_common.hpp"
 #include "nsa_internal.hpp"
 #include "sel_attn_params.hpp"
@@ -22,6 +23,7 @@ struct KvQuantParams {
     int64_t planes;               // B G (paged: G)
     const int32_t *table_row;     // paged: device [max_pages]; null: contiguous tensors
     int n_pages, max_pages;
+    int page_shift;               // paged: log2(page_rows)
 };
 
 template <int D>
@@ -36,12 +38,12 @@ __global__ __launch_bounds__(256) void kv_quantize_fp8_kernel(KvQuantParams P) {
     int64_t b = plane / P.G;
     const int g = (int)(plane % P.G);
     if (P.table_row) {
-        const int64_t j = r >> 10;
+        const int64_t j = r >> P.page_shift;
         if (j >= P.max_pages) return;
         const int page = P.table_row[j];
         if (page < 0 || page >= P.n_pages) return;  // no page, or a bad id: the row is skipped
         b = page;
-        r &= DEC_PAGE_TOKENS - 1;
+        r &= ((int64_t)1 << P.page_shift) - 1;
     }
     const u32x4 raw = *(const u32x4 *)(P.X + b * P.xsb + g * P.xsg + r * P.xss + 8 * sub);
     float x[8];
@@ -99,20 +101,29 @@ extern "C" {
 int nsa_kv_quantize_fp8(const void *X, void *X8, float *scale, int B, int G, int S, int D, int t0, int t1, int64_t xsb, int64_t xsg, int64_t xss, int64_t qsb,
                         int64_t qsg, int64_t qss, int64_t zsb, int64_t zsg, void *stream) {
     NSA_CHECK_ARG(B >= 0 && S >= 0 && t1 <= S, "kv_quantize_fp8: rows [t0, t1) = [%d, %d) must lie inside the S = %d rows of the tensors", t0, t1, S);
-    const KvQuantParams P{(const __bf16 *)X, (unsigned char *)X8, scale, xsb, xsg, xss, qsb, qsg, qss, zsb, zsg, G, t0, t1, (int64_t)B * G, nullptr, 0, 0};
+    const KvQuantParams P{(const __bf16 *)X, (unsigned char *)X8, scale, xsb, xsg, xss, qsb, qsg, qss, zsb, zsg, G, t0, t1, (int64_t)B * G, nullptr, 0, 0, 0};
     return kv_quantize_launch("kv_quantize_fp8", P, D, stream);
+}
+
+int nsa_paged_kv_quantize_fp8_rows(const void *X_pool, void *X8_pool, float *scale_pool, const int32_t *table_row, int n_pages, int max_pages, int page_rows, int G,
+                                   int D, int t0, int t1, int64_t xsp, int64_t xsg, int64_t xss, int64_t qsp, int64_t qsg, int64_t qss, int64_t zsp, int64_t zsg,
+                                   void *stream) {
+    NSA_CHECK_ARG(page_rows >= 32 && page_rows <= 65536 && (page_rows & (page_rows - 1)) == 0,
+                  "paged_kv_quantize_fp8: page_rows = %d, must be a power of two in [32, 65536]", page_rows);
+    NSA_CHECK_ARG(n_pages >= 1 && max_pages >= 1 && max_pages <= (1 << 20), "paged_kv_quantize_fp8: n_pages >= 1 and max_pages in [1, 2^20] (got %d, %d)", n_pages,
+                  max_pages);
+    NSA_CHECK_ARG((int64_t)t1 <= (int64_t)max_pages * page_rows, "paged_kv_quantize_fp8: t1 = %d is beyond the table's max_pages * %d = %lld tokens", t1, page_rows,
+                  (long long)max_pages * page_rows);
+    NSA_CHECK_ARG(table_row && (uintptr_t)table_row % 4 == 0, "paged_kv_quantize_fp8: the table row must be a 4-byte aligned device pointer");
+    const KvQuantParams P{(const __bf16 *)X_pool, (unsigned char *)X8_pool, scale_pool, xsp, xsg, xss, qsp, qsg, qss, zsp, zsg, G, t0, t1, (int64_t)G, table_row,
+                          n_pages, max_pages, __builtin_ctz((unsigned)page_rows)};
+    return kv_quantize_launch("paged_kv_quantize_fp8", P, D, stream);
 }
 
 int nsa_paged_kv_quantize_fp8(const void *X_pool, void *X8_pool, float *scale_pool, const int32_t *table_row, int n_pages, int max_pages, int G, int D, int t0,
                               int t1, int64_t xsp, int64_t xsg, int64_t xss, int64_t qsp, int64_t qsg, int64_t qss, int64_t zsp, int64_t zsg, void *stream) {
-    NSA_CHECK_ARG(n_pages >= 1 && max_pages >= 1 && max_pages <= (1 << 20), "paged_kv_quantize_fp8: n_pages >= 1 and max_pages in [1, 2^20] (got %d, %d)", n_pages,
-                  max_pages);
-    NSA_CHECK_ARG((int64_t)t1 <= (int64_t)max_pages * DEC_PAGE_TOKENS, "paged_kv_quantize_fp8: t1 = %d is beyond the table's max_pages * 1024 = %lld tokens", t1,
-                  (long long)max_pages * DEC_PAGE_TOKENS);
-    NSA_CHECK_ARG(table_row && (uintptr_t)table_row % 4 == 0, "paged_kv_quantize_fp8: the table row must be a 4-byte aligned device pointer");
-    const KvQuantParams P{(const __bf16 *)X_pool, (unsigned char *)X8_pool, scale_pool, xsp, xsg, xss, qsp, qsg, qss, zsp, zsg, G, t0, t1, (int64_t)G, table_row,
-                          n_pages, max_pages};
-    return kv_quantize_launch("paged_kv_quantize_fp8", P, D, stream);
+    return nsa_paged_kv_quantize_fp8_rows(X_pool, X8_pool, scale_pool, table_row, n_pages, max_pages, DEC_PAGE_TOKENS, G, D, t0, t1, xsp, xsg, xss, qsp, qsg, qss, zsp,
+                                          zsg, stream);
 }
 
 }  // extern "C"

@@ -839,7 +839,90 @@ int nsa::band_attn_fwd_paged_impl(const AttnCall &c0, const Band &band, const Ba
     return launch_band_attn_fwd_mfma(P, c.dtype, c.st, &pt);
 }
 
+// The FP8 K/V form of the two calls above (nsa_band_attn_fwd_ragged_fp8; with pt0: nsa_band_attn_fwd_paged_fp8).  c: K / V are e4m3 bytes and
+// their strides count bytes.  One route -- the FP8 kernels of band_attn_fp8.hip in the form band_plan gives the shape -- and no fallback: a
+// plan that splits asks for its workspace instead of running unsplit, so that a shape has one form and one set of bits.
+static int band_attn_fwd_fp8_impl(const char *who, const AttnCall &c0, const Band &band, const BandFp8Scales &Z, const BandPageTable *pt0, int max_pages, int page_rows,
+                                  const int32_t *t_pos, int t_max) {
+    NSA_CHECK_ARG(dtype_ok(c0.dtype), "%s: unknown dtype %d", who, c0.dtype);
+    NSA_CHECK_ARG(c0.B >= 0 && c0.S >= 0 && c0.G >= 1 && c0.h >= 1 && c0.Dk >= 1 && c0.Dv >= 1 && c0.S_kv >= 0, "%s: negative size", who);
+    NSA_CHECK_ARG(band.dd >= 1 && t_max >= 0, "%s: need dd >= 1, t_max >= 0", who);
+    NSA_CHECK_ARG(c0.dtype == NSA_DT_BF16, "%s: FP8 K / V take bf16 queries only (got dtype %d); f16 and fp32 queries have no FP8 kernel", who, c0.dtype);
+    NSA_CHECK_ARG(attn_mfma_shape_ok(c0.dtype, c0.h, c0.Dk, c0.Dv), "%s: the MFMA kernels only -- Dk = Dv in {64, 128}, h <= 16 (got Dk = %d, Dv = %d, h = %d)", who,
+                  c0.Dk, c0.Dv, c0.h);
+    NSA_CHECK_ARG(band.w >= 1, "%s: w = %d, the window must hold at least one key (w >= 1)", who, band.w);
+    AttnCall c = c0;
+    if (pt0) {
+        NSA_CHECK_ARG(page_rows >= 32 && page_rows <= 65536 && (page_rows & (page_rows - 1)) == 0,
+                      "%s: page_rows = %d is not built: a power of two in [32, 65536] (a 32-key tile then touches at most two pages)", who, page_rows);
+        NSA_CHECK_ARG(max_pages >= 1 && max_pages <= (1 << 20), "%s: max_pages = %d, must be in [1, 2^20]", who, max_pages);
+        NSA_CHECK_ARG(pt0->n_pages >= 1, "%s: n_pages = %d, the pools must hold at least one page", who, pt0->n_pages);
+        c.S_kv = (int)std::min<int64_t>((int64_t)max_pages * page_rows, INT32_MAX);
+    }
+    NSA_CHECK_ARG(c.S_kv >= 1, "%s: S_kv = %d, the caches must hold at least one row (there is no kernel for empty FP8 caches)", who, c.S_kv);
+    if (c.rows() == 0) return NSA_OK;
+    if (pt0) {
+        NSA_CHECK_ARG(pt0->table != nullptr, "%s: null block table", who);
+        NSA_CHECK_ARG((uintptr_t)pt0->table % 4 == 0 && pt0->stride >= max_pages, "%s: the block table must be 4-byte aligned with a row stride of at least max_pages = %d "
+                                                                                  "(got %lld)", who, max_pages, (long long)pt0->stride);
+    }
+    NSA_CHECK_ARG(c.Q && c.K && c.V && c.O && t_pos, "%s: null pointer", who);
+    NSA_CHECK_ARG(Z.k_scale && Z.v_scale, "%s: null scale: FP8 K / V need k_scale and v_scale (one fp32 per key row)", who);
+    NSA_CHECK_ARG((uintptr_t)t_pos % 4 == 0 && (uintptr_t)Z.k_scale % 4 == 0 && (uintptr_t)Z.v_scale % 4 == 0, "%s: t_pos and the scales must be 4-byte aligned", who);
+    NSA_CHECK_ARG(c.kss == c.Dk && c.vss == c.Dv, "%s: FP8 K / V rows must be contiguous: row stride %lld / %lld bytes, must be D = %d", who, (long long)c.kss,
+                  (long long)c.vss, c.Dk);
+    NSA_CHECK_ARG((uintptr_t)c.Q % 16 == 0 && (uintptr_t)c.K % 16 == 0 && (uintptr_t)c.V % 16 == 0 && c.ksb % 16 == 0 && c.ksg % 16 == 0 && c.vsb % 16 == 0 &&
+                      c.vsg % 16 == 0 && out_aligned(c),
+                  "%s: Q, K8 and V8 must be 16-byte aligned with batch (page) and group strides in multiples of 16 bytes, and O 8-byte aligned", who);
+    // the kernel's 32-bit byte offsets are those of a row inside one plane: S_kv rows (pools: page_rows <= 65536 rows) of D bytes
+    NSA_CHECK_ARG(pt0 || (int64_t)c.S_kv * c.Dk < ((int64_t)1 << 31), "%s: S_kv = %d rows of %d bytes leave the 32-bit offsets of one (b, g) plane", who, c.S_kv, c.Dk);
+    BandAttnParams P = band_attn_params(c, Band{0, band.a, band.dd, band.c, band.w});
+    P.t_pos = t_pos;
+    P.t_max = t_max;
+    int ns = 1;
+    const size_t need = band_attn_workspace(c.B, c.S, c.G, c.h, c.Dk, c.Dv, c.dtype, &ns);
+    if (ns > 1) {
+        NSA_CHECK_ARG(c.ws && ((uintptr_t)c.ws % 16 == 0) && c.ws_bytes >= need,
+                      "%s: workspace missing, misaligned or too small: the plan splits a row over %d waves and needs %zu bytes (16-byte aligned)", who, ns, need);
+        P.part = (float *)c.ws;
+        P.nsplit = ns;
+    }
+    if (!pt0) return launch_band_attn_fwd_fp8(P, Z, c.st);
+    BandPageTable pt = *pt0;
+    pt.shift = __builtin_ctz((unsigned)page_rows);
+    return launch_band_attn_fwd_fp8(P, Z, c.st, &pt);
+}
+
 extern "C" {
+
+size_t nsa_band_attn_fwd_ragged_fp8_workspace(int B, int S, int G, int h, int Dk, int Dv, int dtype) {
+    return band_attn_workspace(B, S, G, h, Dk, Dv, dtype, nullptr);  // the bf16 call's: the plan does not depend on the K/V format
+}
+size_t nsa_band_attn_fwd_paged_fp8_workspace(int B, int S, int G, int h, int Dk, int Dv, int dtype) {
+    return band_attn_workspace(B, S, G, h, Dk, Dv, dtype, nullptr);
+}
+
+int nsa_band_attn_fwd_ragged_fp8(const void *Q, const void *K8, const void *V8, const float *k_scale, const float *v_scale, void *O, float *lse, const int32_t *t_pos,
+                                 int t_max, int B, int S, int G, int h, int Dk, int Dv, int S_kv, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg,
+                                 int64_t vss, int64_t kzb, int64_t kzg, int64_t vzb, int64_t vzg, int a, int dd, int c, int w, int dtype, float scale, void *workspace,
+                                 size_t workspace_bytes, void *stream) {
+    return band_attn_fwd_fp8_impl("band_attn_fwd_ragged_fp8",
+                                  AttnCall{Q, K8, V8, nullptr, O, lse, B, S, G, h, Dk, Dv, S_kv, 0, ksb, ksg, kss, vsb, vsg, vss, dtype, scale, 0, workspace,
+                                           workspace_bytes, (hipStream_t)stream},
+                                  Band{0, a, dd, c, w}, BandFp8Scales{k_scale, v_scale, kzb, kzg, vzb, vzg}, nullptr, 0, 0, t_pos, t_max);
+}
+
+int nsa_band_attn_fwd_paged_fp8(const void *Q, const void *K8_pool, const void *V8_pool, const float *k_scale_pool, const float *v_scale_pool,
+                                const int32_t *block_table, int64_t table_stride, int n_pages, int max_pages, int page_rows, void *O, float *lse, const int32_t *t_pos,
+                                int t_max, int B, int S, int G, int h, int Dk, int Dv, int64_t ksp, int64_t ksg, int64_t kss, int64_t vsp, int64_t vsg, int64_t vss,
+                                int64_t kzp, int64_t kzg, int64_t vzp, int64_t vzg, int a, int dd, int c, int w, int dtype, float scale, void *workspace,
+                                size_t workspace_bytes, void *stream) {
+    const BandPageTable pt{block_table, table_stride, n_pages, 0};
+    return band_attn_fwd_fp8_impl("band_attn_fwd_paged_fp8",
+                                  AttnCall{Q, K8_pool, V8_pool, nullptr, O, lse, B, S, G, h, Dk, Dv, 0, 0, ksp, ksg, kss, vsp, vsg, vss, dtype, scale, 0, workspace,
+                                           workspace_bytes, (hipStream_t)stream},
+                                  Band{0, a, dd, c, w}, BandFp8Scales{k_scale_pool, v_scale_pool, kzp, kzg, vzp, vzg}, &pt, max_pages, page_rows, t_pos, t_max);
+}
 
 size_t nsa_band_attn_fwd_paged_workspace(int B, int S, int G, int h, int Dk, int Dv, int dtype) {
     return band_attn_workspace(B, S, G, h, Dk, Dv, dtype, nullptr);  // planned from (B, S, G, h, D) alone: the scalar and the ragged call's

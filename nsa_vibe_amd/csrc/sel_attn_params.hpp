@@ -105,6 +105,17 @@ struct BandPageTable {
     int shift;             // log2(page_rows), 5 .. 16
 };
 size_t band_attn_workspace(int B, int S, int G, int h, int Dk, int Dv, int dtype, int *nsplit_out);
+// the form of a band forward of a supported shape (band_attn_mfma.hip): column tiles and tokens per wave, waves a row's keys are split over
+void band_plan(int B, int S, int G, int h, int D, int *nt, int *tpw, int *nsplit);
+// FP8 K/V of the ragged and the paged band forward (nsa_band_attn_fwd_ragged_fp8 / _paged_fp8; band_attn_fwd_fp8.hpp): P.K / P.V are OCP e4m3
+// bytes with rows of D contiguous bytes (their strides count bytes), and key row r of plane (b, g) -- paged: (page, g) -- is
+// K8[r, :] * k_scale[b kzb + g kzg + r].  An argument block of its own behind BandAttnParams, like BandPageTable
+struct BandFp8Scales {
+    const float *k_scale, *v_scale;
+    int64_t kzb, kzg, vzb, vzg;  // element strides: batch (page), group; the rows of a plane are contiguous
+};
+// the FP8 kernels (band_attn_fp8.hip): bf16 queries, the ragged call's plan and three forms, a plan that splits needs P.part / P.nsplit
+int launch_band_attn_fwd_fp8(const BandAttnParams &P, const BandFp8Scales &Z, hipStream_t st, const struct BandPageTable *pt = nullptr);
 // pt: the paged form -- the PAGED instantiations (LDS-DMA staging, the ragged call's three forms); needs P.t_pos
 int launch_band_attn_fwd_mfma(const BandAttnParams &P, int dtype, hipStream_t st, const BandPageTable *pt = nullptr);
 // band_attn_paged.hip: the PAGED kernels live in a translation unit of their own -- new instantiations inside band_attn_mfma.hip's module

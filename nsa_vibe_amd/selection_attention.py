@@ -430,25 +430,31 @@ def quantize_kv_fp8(X: torch.Tensor, t0: int = 0, t1: Optional[int] = None, out:
 
 
 def quantize_kv_fp8_paged(X_pool: torch.Tensor, table_row: torch.Tensor, t0: int, t1: int, out: torch.Tensor, scale_out: torch.Tensor):
-    """quantize_kv_fp8 for tokens [t0, t1) of ONE slot of paged pools (nsa_paged_kv_quantize_fp8): X_pool bf16 [n_pages, G, 1024, D] -> out
-    float8_e4m3fn [n_pages, G, 1024, D] and scale_out fp32 [n_pages, G, 1024] in place, token r at row r & 1023 of page table_row[r >> 10].
+    """quantize_kv_fp8 for tokens [t0, t1) of ONE slot of paged pools: X_pool bf16 [n_pages, G, page_rows, D] -> out float8_e4m3fn of the
+    same shape and scale_out fp32 [n_pages, G, page_rows] in place, token r at row r % page_rows of page table_row[r // page_rows].
+    page_rows is read from the pool's shape, a power of two in [32, 65536]: 1024 (the K / V pools of the selected and the sliding branch)
+    runs nsa_paged_kv_quantize_fp8, any other size -- 64 for the K_cmp / V_cmp pools -- nsa_paged_kv_quantize_fp8_rows.
     table_row: the slot's row of the block table, a device int32 tensor [max_pages] (never read back; rows of an entry outside [0, n_pages)
     are skipped).  Returns (out, scale_out)."""
     who = "quantize_kv_fp8_paged"
     dev = _need_gpu(X_pool, out, scale_out, table_row)
-    _unit_rows_pool(who, "X_pool", X_pool, PAGE_TOKENS)
-    _unit_rows_pool(who, "out", out, PAGE_TOKENS)
-    n_pages, G, _, D = X_pool.shape
+    if X_pool.dim() != 4:
+        raise RuntimeError(f"{who}: X_pool must be [n_pages, G, page_rows, D] (got {tuple(X_pool.shape)})")
+    n_pages, G, rows, D = X_pool.shape
+    _unit_rows_pool(who, "X_pool", X_pool, rows)
+    _unit_rows_pool(who, "out", out, rows)
     if X_pool.dtype != torch.bfloat16 or out.dtype != FP8 or tuple(out.shape) != tuple(X_pool.shape):
         raise RuntimeError(f"{who}: X_pool must be bf16 and out float8_e4m3fn of the same shape")
-    if scale_out.dtype != torch.float32 or tuple(scale_out.shape) != (n_pages, G, PAGE_TOKENS) or scale_out.stride(-1) != 1:
-        raise RuntimeError(f"{who}: scale_out must be fp32 {[n_pages, G, PAGE_TOKENS]} with unit row stride")
+    if scale_out.dtype != torch.float32 or tuple(scale_out.shape) != (n_pages, G, rows) or scale_out.stride(-1) != 1:
+        raise RuntimeError(f"{who}: scale_out must be fp32 {[n_pages, G, rows]} with unit row stride")
     if table_row.dtype != torch.int32 or table_row.dim() != 1 or table_row.stride(0) != 1:
         raise RuntimeError(f"{who}: table_row must be a contiguous device int32 tensor [max_pages]")
-    rc = _lib.lib().nsa_paged_kv_quantize_fp8(X_pool.data_ptr(), out.data_ptr(), scale_out.data_ptr(), table_row.data_ptr(), n_pages, table_row.shape[0], G, D,
-                                              int(t0), int(t1), X_pool.stride(0), X_pool.stride(1), X_pool.stride(2), out.stride(0), out.stride(1),
-                                              out.stride(2), scale_out.stride(0), scale_out.stride(1), _stream(dev))
-    _lib.check(rc, "nsa_paged_kv_quantize_fp8")
+    L = _lib.lib()
+    name, page = ("nsa_paged_kv_quantize_fp8", ()) if rows == PAGE_TOKENS else ("nsa_paged_kv_quantize_fp8_rows", (rows,))
+    rc = getattr(L, name)(X_pool.data_ptr(), out.data_ptr(), scale_out.data_ptr(), table_row.data_ptr(), n_pages, table_row.shape[0], *page, G, D, int(t0),
+                          int(t1), X_pool.stride(0), X_pool.stride(1), X_pool.stride(2), out.stride(0), out.stride(1), out.stride(2), scale_out.stride(0),
+                          scale_out.stride(1), _stream(dev))
+    _lib.check(rc, name)
     return out, scale_out
 
 
