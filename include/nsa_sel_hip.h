@@ -723,6 +723,8 @@ NSA_API int nsa_sel_decode_paged_plan(int B, int S, int G, int h, int Dk, int Dv
  * nsa_kv_quantize_fp8: rows [t0, t1) of a bf16 tensor X [B, G, S, D] (element strides; rows of D in {64, 128} contiguous elements, 16-byte
  * aligned, strides multiples of 8) -> X8 (e4m3, byte strides multiples of 8, 8-byte aligned) and scale [B, G, S] fp32 (unit row stride):
  *     scale = amax(|x|) / 448.0f (IEEE fp32 division; 1.0f for an all-zero row),  X8 = e4m3_rne(clamp(x / scale, -448, 448)).
+ * A row that holds a NaN or an infinity gets scale = NaN and an e4m3 NaN code (0x7F or 0xFF) in every byte: the FP8 calls then do with the
+ * row what the bf16 calls do with it in the bf16 cache (a V row: NaN in the output rows that read it).
  * Rows outside [t0, t1) are untouched.  One launch: what keeps an FP8 mirror of the selected branch's K / V current, per appended chunk.
  * nsa_paged_kv_quantize_fp8: the same for tokens [t0, t1) of ONE slot of paged pools -- X_pool bf16 [n_pages, G, 1024, D] -> X8_pool and
  * scale_pool [n_pages, G, 1024], token r at row r & 1023 of page table_row[r >> 10] (table_row: device int32 [max_pages], the slot's row of

@@ -411,8 +411,9 @@ def quantize_kv_fp8(X: torch.Tensor, t0: int = 0, t1: Optional[int] = None, out:
                     scale_out: Optional[torch.Tensor] = None):
     """Rows [t0, t1) of a bf16 K or V cache X [B,G,S,D] (any batch / group / row strides, D in {64, 128} contiguous) -> (X8 torch.float8_e4m3fn
     [B,G,S,D], scale fp32 [B,G,S]) in one launch (nsa_kv_quantize_fp8): scale = amax / 448 in fp32 (1 for an all-zero row), X8 =
-    e4m3(clamp(x / scale, -448, 448)) rounded to nearest even.  out / scale_out: the mirror to update in place -- rows outside [t0, t1) are
-    untouched (fresh tensors are zero-filled there, with scale 1)."""
+    e4m3(clamp(x / scale, -448, 448)) rounded to nearest even.  A row that holds a NaN or an infinity gets scale NaN and an e4m3 NaN code
+    (0x7F or 0xFF) in every byte, so the FP8 calls do with the row what the bf16 calls on X would (a V row: NaN in the output rows that read
+    it).  out / scale_out: the mirror to update in place -- rows outside [t0, t1) are untouched (fresh tensors are zero-filled there, with scale 1)."""
     who = "quantize_kv_fp8"
     dev = _need_gpu(X)
     if X.dim() != 4 or X.dtype != torch.bfloat16 or X.stride(-1) != 1:

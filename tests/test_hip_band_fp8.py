@@ -157,6 +157,33 @@ def test_general_scales_against_float64(nv, name, D, branch):
 
 
 @pytest.mark.parametrize("branch", BRANCHES)
+def test_nan_scale_of_a_live_key_reaches_the_rows_that_read_it(nv, branch):
+    """what the quantiser stores for a row that holds a NaN or an infinity is a NaN scale.  On a V row (sequence 0's last key row, group 1) it
+    makes that (sequence, group)'s output rows NaN and changes no bit of lse, of the other group or of the other sequences.  On a K row the
+    FP8 call does what the bf16 call does with a NaN in that K row (unit scales, the dequantised caches): the same elements of O and lse
+    are NaN and every other bit is equal -- the epilogues the band kernels share write a zero row when the row sum is not > 0, NaN included."""
+    c, Q = get_case("set", "S1_mixed", 64)
+    f = fp8_case(c, branch)
+    r = own_rows(c, branch, 0) - 1
+    O, lse = call(nv, c, Q, f["K8"], f["V8"], branch, k_scale=f["ks"], v_scale=f["vs"])
+    z = f["vs"].clone()
+    z[0, 1, r] = float("nan")
+    O2, lse2 = call(nv, c, Q, f["K8"], f["V8"], branch, k_scale=f["ks"], v_scale=z)
+    assert torch.isnan(O2[0, :, 1].float()).all()
+    assert torch.equal(O2[0, :, 0], O[0, :, 0]) and torch.equal(O2[1:], O[1:]) and torch.equal(lse2, lse)
+    z = f["one"].clone()
+    z[0, 1, r] = float("nan")
+    O3, lse3 = call(nv, c, Q, f["K8"], f["V8"], branch, k_scale=z, v_scale=f["one"])
+    Kn = f["Kd"].clone()
+    Kn[0, 1, r] = float("nan")
+    Ob, lseb = call(nv, c, Q, Kn, f["Vd"], branch)
+    for got, ref in ((O3, Ob), (lse3, lseb)):
+        assert torch.equal(torch.isnan(got), torch.isnan(ref)) and torch.equal(got.nan_to_num(0.0), ref.nan_to_num(0.0))
+    O1, lse1 = call(nv, c, Q, f["K8"], f["V8"], branch, k_scale=f["one"], v_scale=f["one"])
+    assert not torch.equal(O3[0, :, 1], O1[0, :, 1]) and torch.equal(O3[0, :, 0], O1[0, :, 0]) and torch.equal(O3[1:], O1[1:])
+
+
+@pytest.mark.parametrize("branch", BRANCHES)
 def test_table_entry_outside_the_pool_makes_the_sequence_inactive(nv, branch):
     c, Q = get_case("set", "S1_mixed", 64)
     f = fp8_case(c, branch)

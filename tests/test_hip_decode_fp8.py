@@ -126,6 +126,30 @@ def test_general_scales_against_float64(nv, case):
     assert torch.equal(ragged8(nv, c, f, ki, vi)[0], O)
 
 
+def test_nan_scale_of_a_live_row_reaches_the_rows_that_read_it(nv):
+    """what the quantiser stores for a row that holds a NaN or an infinity is a NaN scale.  On a V row (sequence 0's own token, group 0; every
+    row reads its own token) it makes that (sequence, group)'s output rows NaN and changes no bit of the other group or sequences.  On a K
+    row the FP8 call does what the bf16 call does with a NaN in that K row (unit scales, the dequantised caches): the same rows are NaN
+    and every other bit is equal -- the epilogue all decode kernels share writes a zero row when the row sum is not > 0, NaN included."""
+    c, f = fp8_case(nv, FP8_CASES[0])
+    t0 = c["t_pos"][0]
+    O, rg = ragged8(nv, c, f, f["ks"], f["vs"])
+    z = f["vs"].clone()
+    z[0, 0, t0] = float("nan")
+    O2, r2 = ragged8(nv, c, f, f["ks"], z)
+    assert torch.isnan(O2[0, :, 0].float()).all()
+    assert torch.equal(r2, rg) and torch.equal(O2[0, :, 1], O[0, :, 1]) and torch.equal(O2[1:], O[1:])
+    z = f["one"].clone()
+    z[0, 0, t0] = float("nan")
+    O3, r3 = ragged8(nv, c, f, z, f["one"])
+    Kn = f["deq"]["K"].clone()
+    Kn[0, 0, t0] = float("nan")
+    Ob, rb = ragged(nv, dict(f["deq"], K=Kn))
+    assert torch.equal(r3, rb) and torch.equal(torch.isnan(O3), torch.isnan(Ob)) and torch.equal(O3.nan_to_num(0.0), Ob.nan_to_num(0.0))
+    O1 = ragged8(nv, c, f, f["one"], f["one"])[0]
+    assert not torch.equal(O3[0, :, 0], O1[0, :, 0]) and torch.equal(O3[0, :, 1], O1[0, :, 1]) and torch.equal(O3[1:], O1[1:])
+
+
 def test_table_entry_outside_the_pool_makes_the_sequence_inactive(nv):
     c, f = fp8_case(nv, FP8_CASES[0])
     pl, zk, zv = fp8_pools(c, f, f["ks"], f["vs"])
