@@ -33,152 +33,89 @@ def band_ranges(S: int, S_kv: int, t0: int, a: int, dd: int, c: int, w: int, dev
     return torch.stack((lo, hi), dim=-1).to(torch.int32)
 
 
-def _fwd(Q, K, V, band, scale, variant, want_lse, t_pos=None, t_max=None):
-    who = "band attention"
-    if t_pos is not None:  # ragged form: the positions are checked before anything native is touched
-        if Q.dim() != 5:
-            raise RuntimeError("band attention: expected Q[B,S,G,h,Dk] K[B,G,S_kv,Dk] V[B,G,S_kv,Dv]")
+def _fwd(Q, K, V, band, scale, variant, want_lse, t_pos=None, t_max=None, block_table=None, zs=None):
+    """The forward in every form, told from what the call carries -> (O, lse, (Qc, Kc, Vc)).  t_pos: per-sequence positions
+    (nsa_band_attn_fwd_ragged); block_table: K / V are pools of pages (_paged); zs, _fp8_scales' answer: K / V are e4m3 rows with one fp32 scale
+    per row, [B,G,S_kv] or scale pools (_ragged_fp8 / _paged_fp8), O in Q's dtype.  Everything is checked before anything native is touched."""
+    bt, ragged, paged, fp8 = block_table, t_pos is not None, block_table is not None, zs is not None
+    who = "band attention" + ((" (FP8 K/V, paged)" if paged else " (FP8 K/V)") if fp8 else " (paged)" if paged else "")
+    if Q.dim() != 5 or K.dim() != 4 or V.dim() != 4:
+        raise RuntimeError(f"{who}: expected Q[B,S,G,h,D] and K / V [B,G,S_kv,D] or pools [n_pages,G,page_rows,D]" if fp8 else
+                           f"{who}: expected Q[B,S,G,h,Dk] K_pool[n_pages,G,page_rows,Dk] V_pool[n_pages,G,page_rows,Dv]" if paged else
+                           "band attention: expected Q[B,S,G,h,Dk] K[B,G,S_kv,Dk] V[B,G,S_kv,Dv]")
+    B, S, G, h, Dk = Q.shape
+    if paged:
+        if not isinstance(bt, torch.Tensor) or bt.device.type == "cpu" or bt.dtype != torch.int32 or bt.dim() != 2:
+            raise RuntimeError(f"{who}: block_table must be a device int32 tensor [B, max_pages] (it is never read back); got "
+                               f"{getattr(bt, 'dtype', type(bt))} {tuple(getattr(bt, 'shape', ()))} on {getattr(bt, 'device', 'the host')}")
+        if bt.shape[0] != B or bt.shape[1] < 1:
+            raise RuntimeError(f"{who}: block_table has shape {tuple(bt.shape)} for B = {B} sequences: expected [B, max_pages >= 1]")
+        if bt.stride(1) != 1:
+            raise RuntimeError(f"{who}: block_table must have a contiguous last dimension (stride {bt.stride(1)})")
+    # the forms beyond the scalar call are ragged and forward only
+    if not ragged:
+        if fp8:
+            raise RuntimeError(f"{who}: FP8 K / V need the per-sequence positions t_pos (the scalar-t0 call has no FP8 kernel)")
+        if paged:
+            raise RuntimeError(f"{who}: block_table needs the per-sequence positions t_pos")
+        if t_max is not None:
+            raise RuntimeError(f"{who}: t_max is the bound of t_pos and needs it")
+    else:
         if band[0] != 0:
             raise RuntimeError(f"{who}: t_pos and a non-zero t0 are mutually exclusive")
         if Q.requires_grad or K.requires_grad or V.requires_grad:
-            raise RuntimeError(f"{who}: per-sequence positions (t_pos) are forward only: no input may require grad")
-        t_pos, t_max, host = _ragged_positions(who, t_pos, t_max, Q.shape[0], Q.shape[1])
-    elif t_max is not None:
-        raise RuntimeError(f"{who}: t_max is the bound of t_pos and needs it")
-    dev = _need_gpu(Q, K, V)
-    if not (Q.dtype == K.dtype == V.dtype) or Q.dtype not in _DT:
-        raise RuntimeError(f"band attention: Q/K/V must share a dtype in fp32/bf16/fp16 (got {Q.dtype},{K.dtype},{V.dtype})")
-    if Q.dim() != 5 or K.dim() != 4 or V.dim() != 4:
-        raise RuntimeError("band attention: expected Q[B,S,G,h,Dk] K[B,G,S_kv,Dk] V[B,G,S_kv,Dv]")
-    B, S, G, h, Dk = Q.shape
-    S_kv, Dv = K.shape[2], V.shape[3]
-    if K.shape[:2] != (B, G) or V.shape[:3] != (B, G, S_kv) or K.shape[3] != Dk:
-        raise RuntimeError("band attention: inconsistent shapes")
+            what = ("FP8 K / V are forward only (there is no backward over quantised caches)" if fp8 else
+                    "paged caches (block_table) are forward only" if paged else "per-sequence positions (t_pos) are forward only")
+            raise RuntimeError(f"{who}: {what}: no input may require grad")
+        t_pos, t_max, host = _ragged_positions(who, t_pos, t_max, B, S)
+    dev = _need_gpu(Q, K, V, *((bt,) if paged else ()))
+    if ragged and host is None and t_pos.device != dev:
+        raise RuntimeError("all tensors must be on the same device")
+    if fp8:
+        if Q.dtype != torch.bfloat16:
+            raise RuntimeError(f"{who}: FP8 K / V take bf16 queries only (got {Q.dtype})")
+    elif not (Q.dtype == K.dtype == V.dtype) or Q.dtype not in _DT:
+        raise RuntimeError(f"{who}: Q and the pools must share a dtype (got {Q.dtype},{K.dtype},{V.dtype})" if paged else
+                           f"band attention: Q/K/V must share a dtype in fp32/bf16/fp16 (got {Q.dtype},{K.dtype},{V.dtype})")
+    # contiguous caches: S_kv rows of sequence b; pools: page_rows rows of a page, found through the table
+    lead, rows, Dv = tuple(K.shape[:3]), K.shape[2], V.shape[3]
+    if fp8:  # used in place: the rows are D contiguous bytes
+        if tuple(V.shape[:3]) != lead or K.shape[3] != Dk or lead[1] != G or (not paged and lead[0] != B):
+            raise RuntimeError(f"{who}: inconsistent shapes")
+        if K.stride(3) != 1 or V.stride(3) != 1 or K.stride(2) != Dk or V.stride(2) != Dv:
+            raise RuntimeError(f"{who}: FP8 K / V rows must be contiguous (row stride = D bytes); they are used in place")
+        (Kc, *ks), (Vc, *vs) = (K, *K.stride()[:3]), (V, *V.stride()[:3])
+    elif paged:  # used in place: page, group and row strides
+        (Kc, *ks), (Vc, *vs) = _unit_rows_pool(who, "K_pool", K, rows), _unit_rows_pool(who, "V_pool", V, rows)
+        if V.shape[0] != lead[0] or not (lead[1] == V.shape[1] == G) or K.shape[3] != Dk:
+            raise RuntimeError(f"{who}: the two pools must share n_pages and G = {G}, with Dk = {Dk} columns in K_pool")
+    else:
+        if lead[:2] != (B, G) or tuple(V.shape[:3]) != lead or K.shape[3] != Dk:
+            raise RuntimeError("band attention: inconsistent shapes")
+        (Kc, *ks), (Vc, *vs) = _unit_rows(K), _unit_rows(V)
     t0, a, dd, c, w = band
-    Qc, (Kc, *ks), (Vc, *vs) = Q.contiguous(), _unit_rows(K), _unit_rows(V)
-    O = torch.empty((B, S, G, h, Dv), dtype=V.dtype, device=dev)
+    Qc = Q.contiguous()
+    O = torch.empty((B, S, G, h, Dv), dtype=Q.dtype, device=dev)
     lse = torch.empty((B, S, G, h), dtype=torch.float32, device=dev) if want_lse else None
     if O.numel() == 0:
         return O, lse, (Qc, Kc, Vc)
     L = _lib.lib()
     dt = _DT[Q.dtype]
-    ws = workspace(dev, L.nsa_band_attn_fwd_workspace(B, S, G, h, Dk, Dv, dt), "band")
-    name, at, row0 = "nsa_band_attn_fwd", (), (int(t0),)  # row s at token t0 + s ...
-    if t_pos is not None:  # ... or, in the ragged form, at t_pos[b] + s: the positions stand behind lse, and there is no t0
-        if host is None and t_pos.device != dev:
-            raise RuntimeError("all tensors must be on the same device")
-        pos = _positions_to(dev, t_pos, host)
-        name, at, row0 = "nsa_band_attn_fwd_ragged", (pos.data_ptr(), t_max), ()
-    rc = getattr(L, name)(Qc.data_ptr(), Kc.data_ptr() if S_kv else None, Vc.data_ptr() if S_kv else None, O.data_ptr(),
-              lse.data_ptr() if lse is not None else None, *at, B, S, G, h, Dk, Dv, S_kv, *ks, *vs, *row0, int(a), int(dd), int(c),
-              int(min(w, _W_INF)), dt, _scale_arg(scale), int(variant), *_ws_args(ws), _stream(dev))
+    name = "nsa_band_attn_fwd" + ("_paged" if paged else "_ragged" if ragged else "") + ("_fp8" if fp8 else "")
+    ws = workspace(dev, L.nsa_band_attn_fwd_workspace(B, S, G, h, Dk, Dv, dt), "band")  # (one plan from (B, S, G, h, D): every form's query answers it)
+    # the native argument list, piece by piece in the order every entry point shares; a form adds its pieces and leaves out what it has no use for
+    kv = (Qc.data_ptr(), Kc.data_ptr() if rows else None, Vc.data_ptr() if rows else None)
+    scales, scale_strides = ((zs[0][0].data_ptr(), zs[1][0].data_ptr()), (*zs[0][1:], *zs[1][1:])) if fp8 else ((), ())
+    table = (bt.data_ptr(), bt.stride(0), lead[0], bt.shape[1], rows) if paged else ()
+    out = (O.data_ptr(), lse.data_ptr() if lse is not None else None)
+    pos = _positions_to(dev, t_pos, host) if ragged else None  # (bound here: the device copy of host positions lives until the call has returned)
+    at = (pos.data_ptr(), t_max) if ragged else ()  # row s at t_pos[b] + s ...
+    row0 = () if ragged else (int(t0),)                                          # ... or at t0 + s
+    dims = (B, S, G, h, Dk, Dv) + (() if paged else (rows,))
+    tail = (int(a), int(dd), int(c), int(min(w, _W_INF)), dt, _scale_arg(scale)) + (() if paged or fp8 else (int(variant),))
+    rc = getattr(L, name)(*kv, *scales, *table, *out, *at, *dims, *ks, *vs, *scale_strides, *row0, *tail, *_ws_args(ws), _stream(dev))
     _lib.check(rc, name)
     return O, lse, (Qc, Kc, Vc)
-
-
-def _fwd_paged(Q, K_pool, V_pool, block_table, band, scale, want_lse, t_pos, t_max):
-    """the ragged forward over pools of pages (nsa_band_attn_fwd_paged); everything is checked before anything native is touched"""
-    who = "band attention (paged)"
-    if Q.dim() != 5:
-        raise RuntimeError(f"{who}: expected Q[B,S,G,h,Dk] K_pool[n_pages,G,page_rows,Dk] V_pool[n_pages,G,page_rows,Dv]")
-    B, S, G, h, Dk = Q.shape
-    bt = block_table
-    if not isinstance(bt, torch.Tensor) or bt.device.type == "cpu" or bt.dtype != torch.int32 or bt.dim() != 2:
-        raise RuntimeError(f"{who}: block_table must be a device int32 tensor [B, max_pages] (it is never read back); got "
-                           f"{getattr(bt, 'dtype', type(bt))} {tuple(getattr(bt, 'shape', ()))} on {getattr(bt, 'device', 'the host')}")
-    if bt.shape[0] != B or bt.shape[1] < 1:
-        raise RuntimeError(f"{who}: block_table has shape {tuple(bt.shape)} for B = {B} sequences: expected [B, max_pages >= 1]")
-    if bt.stride(1) != 1:
-        raise RuntimeError(f"{who}: block_table must have a contiguous last dimension (stride {bt.stride(1)})")
-    if band[0] != 0:
-        raise RuntimeError(f"{who}: t_pos and a non-zero t0 are mutually exclusive")
-    if t_pos is None:
-        raise RuntimeError(f"{who}: block_table needs the per-sequence positions t_pos")
-    if Q.requires_grad or K_pool.requires_grad or V_pool.requires_grad:
-        raise RuntimeError(f"{who}: paged caches (block_table) are forward only: no input may require grad")
-    t_pos, t_max, host = _ragged_positions(who, t_pos, t_max, B, S)
-    dev = _need_gpu(Q, K_pool, V_pool, bt)
-    if host is None and t_pos.device != dev:
-        raise RuntimeError("all tensors must be on the same device")
-    if not (Q.dtype == K_pool.dtype == V_pool.dtype) or Q.dtype not in _DT:
-        raise RuntimeError(f"{who}: Q and the pools must share a dtype (got {Q.dtype},{K_pool.dtype},{V_pool.dtype})")
-    if K_pool.dim() != 4 or V_pool.dim() != 4:
-        raise RuntimeError(f"{who}: expected Q[B,S,G,h,Dk] K_pool[n_pages,G,page_rows,Dk] V_pool[n_pages,G,page_rows,Dv]")
-    page_rows = K_pool.shape[2]
-    (Kk, *ks), (Vv, *vs) = _unit_rows_pool(who, "K_pool", K_pool, page_rows), _unit_rows_pool(who, "V_pool", V_pool, page_rows)
-    n_pages, max_pages, Dv = Kk.shape[0], bt.shape[1], Vv.shape[3]
-    if Vv.shape[0] != n_pages or not (Kk.shape[1] == Vv.shape[1] == G) or Kk.shape[3] != Dk:
-        raise RuntimeError(f"{who}: the two pools must share n_pages and G = {G}, with Dk = {Dk} columns in K_pool")
-    t0, a, dd, c, w = band
-    O = torch.empty((B, S, G, h, Dv), dtype=V_pool.dtype, device=dev)
-    lse = torch.empty((B, S, G, h), dtype=torch.float32, device=dev) if want_lse else None
-    if O.numel() == 0:
-        return O, lse
-    L = _lib.lib()
-    dt = _DT[Q.dtype]
-    Qc = Q.contiguous()
-    pos = _positions_to(dev, t_pos, host)
-    ws = workspace(dev, L.nsa_band_attn_fwd_paged_workspace(B, S, G, h, Dk, Dv, dt), "band")
-    rc = L.nsa_band_attn_fwd_paged(Qc.data_ptr(), Kk.data_ptr(), Vv.data_ptr(), bt.data_ptr(), bt.stride(0), n_pages, max_pages, page_rows, O.data_ptr(),
-                                   lse.data_ptr() if lse is not None else None, pos.data_ptr(), t_max, B, S, G, h, Dk, Dv, *ks, *vs, int(a), int(dd), int(c),
-                                   int(min(w, _W_INF)), dt, _scale_arg(scale), *_ws_args(ws), _stream(dev))
-    _lib.check(rc, "nsa_band_attn_fwd_paged")
-    return O, lse
-
-
-def _fwd_fp8(Q, K8, V8, zs, block_table, band, scale, want_lse, t_pos, t_max):
-    """the ragged and the paged forward over FP8 K / V (nsa_band_attn_fwd_ragged_fp8 / _paged_fp8): e4m3 rows with one fp32 scale per row,
-    [B,G,S_kv] or, with a block table, pools [n_pages,G,page_rows] (zs: _fp8_scales' answer); O in Q's dtype.  Checked before anything
-    native is touched"""
-    paged = block_table is not None
-    who = "band attention (FP8 K/V, paged)" if paged else "band attention (FP8 K/V)"
-    if Q.dim() != 5 or K8.dim() != 4 or V8.dim() != 4:
-        raise RuntimeError(f"{who}: expected Q[B,S,G,h,D] and K / V [B,G,S_kv,D] or pools [n_pages,G,page_rows,D]")
-    B, S, G, h, Dk = Q.shape
-    if t_pos is None:
-        raise RuntimeError(f"{who}: FP8 K / V need the per-sequence positions t_pos (the scalar-t0 call has no FP8 kernel)")
-    if band[0] != 0:
-        raise RuntimeError(f"{who}: t_pos and a non-zero t0 are mutually exclusive")
-    if Q.requires_grad or K8.requires_grad or V8.requires_grad:
-        raise RuntimeError(f"{who}: FP8 K / V are forward only (there is no backward over quantised caches): no input may require grad")
-    if Q.dtype != torch.bfloat16:
-        raise RuntimeError(f"{who}: FP8 K / V take bf16 queries only (got {Q.dtype})")
-    lead, Dv = tuple(K8.shape[:3]), V8.shape[3]
-    if tuple(V8.shape[:3]) != lead or K8.shape[3] != Dk or lead[1] != G or (not paged and lead[0] != B):
-        raise RuntimeError(f"{who}: inconsistent shapes")
-    if K8.stride(3) != 1 or V8.stride(3) != 1 or K8.stride(2) != Dk or V8.stride(2) != Dv:
-        raise RuntimeError(f"{who}: FP8 K / V rows must be contiguous (row stride = D bytes); they are used in place")
-    t_pos, t_max, host = _ragged_positions(who, t_pos, t_max, B, S)
-    bt = block_table
-    if paged and (not isinstance(bt, torch.Tensor) or bt.dtype != torch.int32 or bt.dim() != 2 or bt.shape[0] != B or bt.shape[1] < 1 or bt.stride(1) != 1):
-        raise RuntimeError(f"{who}: block_table must be a device int32 tensor [B, max_pages >= 1] with a contiguous last dimension")
-    dev = _need_gpu(Q, K8, V8, *((bt,) if paged else ()))
-    if host is None and t_pos.device != dev:
-        raise RuntimeError("all tensors must be on the same device")
-    t0, a, dd, c, w = band
-    O = torch.empty((B, S, G, h, Dv), dtype=Q.dtype, device=dev)
-    lse = torch.empty((B, S, G, h), dtype=torch.float32, device=dev) if want_lse else None
-    if O.numel() == 0:
-        return O, lse
-    L = _lib.lib()
-    dt = _DT[Q.dtype]
-    Qc, pos = Q.contiguous(), _positions_to(dev, t_pos, host)
-    (kz, *kzs), (vz, *vzs) = zs
-    kv = (K8.data_ptr(), V8.data_ptr(), kz.data_ptr(), vz.data_ptr())
-    out = (O.data_ptr(), lse.data_ptr() if lse is not None else None, pos.data_ptr(), t_max, B, S, G, h, Dk, Dv)
-    strides = (K8.stride(0), K8.stride(1), K8.stride(2), V8.stride(0), V8.stride(1), V8.stride(2), *kzs, *vzs)
-    tail = (int(a), int(dd), int(c), int(min(w, _W_INF)), dt, _scale_arg(scale))
-    if paged:
-        ws = workspace(dev, L.nsa_band_attn_fwd_paged_fp8_workspace(B, S, G, h, Dk, Dv, dt), "band")
-        name = "nsa_band_attn_fwd_paged_fp8"
-        rc = L.nsa_band_attn_fwd_paged_fp8(Qc.data_ptr(), *kv, bt.data_ptr(), bt.stride(0), lead[0], bt.shape[1], lead[2], *out, *strides, *tail,
-                                           *_ws_args(ws), _stream(dev))
-    else:
-        ws = workspace(dev, L.nsa_band_attn_fwd_ragged_fp8_workspace(B, S, G, h, Dk, Dv, dt), "band")
-        name = "nsa_band_attn_fwd_ragged_fp8"
-        rc = L.nsa_band_attn_fwd_ragged_fp8(Qc.data_ptr(), *kv, *out, lead[2], *strides, *tail, *_ws_args(ws), _stream(dev))
-    _lib.check(rc, name)
-    return O, lse
 
 
 class _BandAttnFn(torch.autograd.Function):
@@ -237,24 +174,17 @@ def band_attention_hip(Q, K, V, *, t0: int = 0, a: int = 0, dd: int = 1, c: int 
     D = 64 or 128 only, O in Q's dtype; with all scales 1 the bits of the bf16 call on the dequantised caches.  FP8 K / V require both
     scales, bf16 / f16 K / V forbid them; the scalar-t0 and the autograd path have no FP8 form and say so."""
     band = (int(t0), int(a), int(dd), int(c), int(w))
+    zs = None
     if K.dtype == FP8 or V.dtype == FP8 or k_scale is not None or v_scale is not None:
         zs = _fp8_scales("band attention", K, V, k_scale, v_scale, K.shape[:3])  # (scales beside bf16 / f16 K / V raise here)
-        if zs is not None:
-            O, lse = _fwd_fp8(Q, K, V, zs, block_table, band, scale, return_lse, t_pos, t_max)
-            return (O, lse) if return_lse else O
-    if block_table is not None:
-        O, lse = _fwd_paged(Q, K, V, block_table, band, scale, return_lse, t_pos, t_max)
-        return (O, lse) if return_lse else O
-    if t_pos is not None or t_max is not None:
-        O, lse, _ = _fwd(Q, K, V, band, scale, variant, return_lse, t_pos, t_max)
-        return (O, lse) if return_lse else O
-    if _needs_grad(Q, K, V):
+    forward_only = zs is not None or block_table is not None or t_pos is not None or t_max is not None
+    if not forward_only and _needs_grad(Q, K, V):
         if return_lse:
             raise RuntimeError("return_lse is not available on the autograd path")
         if K.shape[2] == 0:
             return Q.new_zeros(Q.shape[:-1] + (V.shape[-1],)) + 0.0 * Q.sum()
         return _BandAttnFn.apply(Q, K, V, band, scale, variant, bwd_variant)
-    O, lse, _ = _fwd(Q, K, V, band, scale, variant, return_lse)
+    O, lse, _ = _fwd(Q, K, V, band, scale, variant, return_lse, t_pos, t_max, block_table, zs)
     return (O, lse) if return_lse else O
 
 

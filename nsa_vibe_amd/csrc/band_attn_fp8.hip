@@ -16,38 +16,21 @@ template <int D, bool PAGED>
 static int launch_band_fp8_t(const BandAttnParams &P0, const BandFp8Scales &Z, const BandPageTable &pt, hipStream_t st) {
     constexpr int NTW = D == 64 ? 3 : 2;
     BandAttnParams P = P0;
-    int nt = 1, ns = 1;
-    band_plan(P.B, P.S, P.G, P.h, D, &nt, &P.tpw, &ns);
-    const bool split = ns > 1;
+    BandLaunch L;
     // (the caller has checked the workspace: a plan that splits has its records, there is no second form to fall to)
-    NSA_CHECK_ARG(!split || (P.part != nullptr && P.nsplit == ns), "band_attn_fp8: the plan splits a row over %d waves and needs its workspace", ns);
-    if (!split) P.nsplit = 1;
-    const int64_t nbg = (int64_t)P.B * P.G;
-    const int ngrp = (P.S + P.tpw - 1) / P.tpw;
+    if (int rc = band_launch_plan(P, true, "band_attn_fp8", &L)) return rc;
     // two stages of (V tile + scales) per wave: 18 / 34 KiB a workgroup where the bf16 kernels ask 32 / 64 KiB
     const size_t lds = 4 * (size_t)band_fp8_wave_lds(D);
-    if (split) {
-        const int64_t waves = nbg * ngrp * P.nsplit;
-        NSA_CHECK_ARG((waves + 3) / 4 < ((int64_t)1 << 31), "band_attn_fp8: too many workgroups for one launch");
-        hipLaunchKernelGGL((band_attn_fwd_fp8_kernel<D, 1, true, PAGED>), dim3((unsigned)((waves + 3) / 4)), dim3(256), lds, st, P, Z, pt);
+    if (L.split) {
+        hipLaunchKernelGGL((band_attn_fwd_fp8_kernel<D, 1, true, PAGED>), dim3(L.grid), dim3(256), lds, st, P, Z, pt);
         NSA_LAUNCH_CHECK("band_attn_fwd_fp8(split)");
-        SelAttnParams C{};
-        C.O = P.O;
-        C.lse = P.lse;
-        C.R = nbg * P.S;
-        C.h = P.h;
-        C.part = P.part;
-        C.nsplit = P.nsplit;
+        const SelAttnParams C = band_combine_params(P);
         hipLaunchKernelGGL((sel_attn_combine_kernel<__bf16, D>), dim3((unsigned)((C.R * C.h + 3) / 4)), dim3(256), 0, st, C);
         NSA_LAUNCH_CHECK("band_attn_combine");
         return NSA_OK;
     }
-    const int64_t W = (ngrp + 3) / 4;
-    P.map_mode = (nbg % 8 == 0) ? 2 : 1;
-    NSA_CHECK_ARG(nbg * W < ((int64_t)1 << 31), "band_attn_fp8: too many workgroups for one launch");
-    const unsigned grid = (unsigned)(nbg * W);
-    if (nt != NTW) hipLaunchKernelGGL((band_attn_fwd_fp8_kernel<D, 1, false, PAGED>), dim3(grid), dim3(256), lds, st, P, Z, pt);
-    else hipLaunchKernelGGL((band_attn_fwd_fp8_kernel<D, NTW, false, PAGED>), dim3(grid), dim3(256), lds, st, P, Z, pt);
+    if (L.nt != NTW) hipLaunchKernelGGL((band_attn_fwd_fp8_kernel<D, 1, false, PAGED>), dim3(L.grid), dim3(256), lds, st, P, Z, pt);
+    else hipLaunchKernelGGL((band_attn_fwd_fp8_kernel<D, NTW, false, PAGED>), dim3(L.grid), dim3(256), lds, st, P, Z, pt);
     NSA_LAUNCH_CHECK("band_attn_fwd_fp8");
     return NSA_OK;
 }

@@ -222,41 +222,50 @@ size_t band_attn_workspace(int B, int S, int G, int h, int Dk, int Dv, int dtype
     return ns > 1 ? (size_t)B * S * G * ns * h * (Dv + PART_PAD) * sizeof(float) : 0;
 }
 
+// The launch of a filled block, planned once for the bf16 / f16 launcher below, the FP8 launcher (band_attn_fp8.hip) and the dual launch.  The
+// split form is taken when the plan splits and the block carries its records (P.part, P.nsplit = the plan's count); otherwise the call runs
+// unsplit, unless need_ws: the caller has no second form to fall to.  Fills P.tpw, P.nsplit (1 unless split) and, unsplit, P.map_mode
+int band_launch_plan(BandAttnParams &P, bool need_ws, const char *who, BandLaunch *L) {
+    int ns = 1;
+    band_plan(P.B, P.S, P.G, P.h, P.Dk, &L->nt, &P.tpw, &ns);
+    L->split = ns > 1 && P.part != nullptr && P.nsplit == ns;
+    NSA_CHECK_ARG(L->split || ns == 1 || !need_ws, "%s: the plan splits a row over %d waves and needs its workspace", who, ns);
+    if (!L->split) P.nsplit = 1;
+    const int64_t nbg = (int64_t)P.B * P.G;
+    const int ngrp = (P.S + P.tpw - 1) / P.tpw;
+    L->waves = nbg * ngrp * P.nsplit;
+    int64_t wgs = (L->waves + 3) / 4;  // split: four (token group, split) units per workgroup
+    if (!L->split) {                   // unsplit: four consecutive token groups of one (b, g)
+        wgs = nbg * ((ngrp + 3) / 4);
+        P.map_mode = (nbg % 8 == 0) ? 2 : 1;
+    }
+    NSA_CHECK_ARG(wgs < ((int64_t)1 << 31), "%s: too many workgroups for one launch", who);
+    L->grid = (unsigned)wgs;
+    return NSA_OK;
+}
+
 template <typename T, int D>
 static int launch_band_t(const BandAttnParams &P0, hipStream_t st, const BandPageTable *pt) {
     constexpr int dtype = std::is_same<T, __bf16>::value ? NSA_DT_BF16 : NSA_DT_F16;
     BandAttnParams P = P0;
-    int nt = 1, ns = 1;
-    band_plan(P.B, P.S, P.G, P.h, D, &nt, &P.tpw, &ns);
-    const bool split = ns > 1 && P.part != nullptr && P.nsplit == ns;
-    if (!split) P.nsplit = 1;
-    const int64_t nbg = (int64_t)P.B * P.G;
-    const int ngrp = (P.S + P.tpw - 1) / P.tpw;
+    BandLaunch L;
+    if (int rc = band_launch_plan(P, false, "band_attn", &L)) return rc;
+    const int nt = L.nt;
+    const unsigned grid = L.grid;
     const size_t lds = 4 * (size_t)(2 * Geo<D>::TILE_BYTES);
     const bool ragged = P.t_pos != nullptr;  // per-sequence positions: the RAGGED instantiations (LDS-DMA staging only)
-    if (split) {
-        const int64_t waves = nbg * ngrp * P.nsplit;
+    if (L.split) {
         // pt: the paged form -- the same plan and geometry, the PAGED kernels of band_attn_paged.hip (a translation unit of their own)
-        if (pt) launch_band_attn_paged_kernel(P, *pt, dtype, 1, true, (unsigned)((waves + 3) / 4), lds, st);
-        else if (ragged) hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, 1, true, 1, true>), dim3((unsigned)((waves + 3) / 4)), dim3(256), lds, st, P);
-        else hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, 1, true, 1>), dim3((unsigned)((waves + 3) / 4)), dim3(256), lds, st, P);
+        if (pt) launch_band_attn_paged_kernel(P, *pt, dtype, 1, true, grid, lds, st);
+        else if (ragged) hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, 1, true, 1, true>), dim3(grid), dim3(256), lds, st, P);
+        else hipLaunchKernelGGL((band_attn_fwd_kernel<T, D, 1, true, 1>), dim3(grid), dim3(256), lds, st, P);
         NSA_LAUNCH_CHECK("band_attn_fwd(split)");
         if (P.defer_combine) return NSA_OK;
-        SelAttnParams C{};
-        C.O = P.O;
-        C.lse = P.lse;
-        C.R = nbg * P.S;
-        C.h = P.h;
-        C.part = P.part;
-        C.nsplit = P.nsplit;
+        const SelAttnParams C = band_combine_params(P);
         hipLaunchKernelGGL((sel_attn_combine_kernel<T, D>), dim3((unsigned)((C.R * C.h + 3) / 4)), dim3(256), 0, st, C);
         NSA_LAUNCH_CHECK("band_attn_combine");
         return NSA_OK;
     }
-    const int64_t W = (ngrp + 3) / 4;
-    P.map_mode = (nbg % 8 == 0) ? 2 : 1;
-    NSA_CHECK_ARG(nbg * W < ((int64_t)1 << 31), "band_attn: too many workgroups for one launch");
-    const unsigned grid = (unsigned)(nbg * W);
     const int stage = tuning(TUNE_BAND_STAGE);  // A/B switch: 0 = register staging, 1 = LDS-DMA  // measured: LDS-DMA 750 vs register staging 650 TFLOP/s (compressed branch, 64k)
     constexpr int NTW = D == 64 ? 3 : 2;
     if (pt) launch_band_attn_paged_kernel(P, *pt, dtype, nt, false, grid, lds, st);
@@ -275,13 +284,14 @@ int launch_band_attn_fwd_mfma(const BandAttnParams &P, int dtype, hipStream_t st
 }
 
 // Both branches of a decode step in one launch.  Requires both to be in split form with deferred combine (the caller combines).
+// (on a false return *P0 / *P1 may be modified -- nsplit = 1, map_mode -- and the error slot may hold the plan's message: both callers return
+// an error of their own then.  The plan's 2^31 grid bound holds for the split launches too; a split plan has under 1024 x 16 waves)
 bool band_dual_plan(BandAttnParams *P0, BandAttnParams *P1, int dtype, int64_t waves[2]) {
     BandAttnParams *P[2] = {P0, P1};
     for (int i = 0; i < 2; ++i) {
-        int nt = 1, ns = 1;
-        band_plan(P[i]->B, P[i]->S, P[i]->G, P[i]->h, P[i]->Dk, &nt, &P[i]->tpw, &ns);
-        if (!(nt == 1 && ns > 1 && P[i]->part && P[i]->nsplit == ns && P[i]->defer_combine)) return false;
-        waves[i] = (int64_t)P[i]->B * P[i]->G * ((P[i]->S + P[i]->tpw - 1) / P[i]->tpw) * ns;
+        BandLaunch L;
+        if (band_launch_plan(*P[i], false, "band dual launch", &L) != NSA_OK || !(L.nt == 1 && L.split && P[i]->defer_combine)) return false;
+        waves[i] = L.waves;
     }
     return P0->Dk == P1->Dk && attn_mfma_shape_ok(dtype, P0->h, P0->Dk, P0->Dv);
 }

@@ -7,6 +7,7 @@
 //   dispatch_check <library> ragged | layer_ragged  the cases of the entry points with per-sequence positions instead
 //   dispatch_check <library> paged                  the cases of the ragged decode step over paged caches (nsa_sel_decode_paged)
 //   dispatch_check <library> band_paged             the cases of the ragged band forward over paged caches (nsa_band_attn_fwd_paged)
+//   dispatch_check <library> band_fp8               the cases of the FP8 K/V band forwards (nsa_band_attn_fwd_ragged_fp8 / _paged_fp8)
 //   dispatch_check <library> layer_paged            the cases of the layer's paged call (nsa_layer_decode_paged)
 //   dispatch_check <library> decode_long            the four ragged / paged entry points beyond the unsplit forms (switch DECODE_LONG)
 #include <dlfcn.h>
@@ -298,6 +299,16 @@ static std::string show(const nsa::DecBandPair &P) {
 }
 // nsa_band_attn_fwd_paged: the table block, argument 1 of the paged band kernels
 static std::string show(const nsa::BandPageTable &P) { return Obj().p("table", P.table).i("stride", P.stride).i("n_pages", P.n_pages).i("shift", P.shift).str(); }
+// nsa_band_attn_fwd_ragged_fp8 / _paged_fp8: BandAttnParams with the two members show(BandAttnParams) leaves out, and the scales, argument 1
+struct BandAttnParamsRagged {
+    nsa::BandAttnParams P;
+};
+static std::string show(const BandAttnParamsRagged &B) {
+    std::string s = show(B.P);
+    s.pop_back();
+    return s + ", " + Obj().p("t_pos", B.P.t_pos).i("t_max", B.P.t_max).s + "}";
+}
+static std::string show(const nsa::BandFp8Scales &P) { return Obj().M_P(k_scale).M_P(v_scale).M_I(kzb).M_I(kzg).M_I(vzb).M_I(vzg).str(); }
 struct BandBwdExtraArg {  // band_attn_mfma.hip: BandBwdExtra, argument 1 of the band dQ kernel
     const void *dO, *lse, *delta, *dQ;
 };
@@ -779,6 +790,132 @@ static void band_paged_cases() {
     band_case("k_row_stride_2MiB_plane_limit", [](Case &c) { c.k_row_stride = (int64_t)1 << 20; });  // 1024 rows of 2 MiB: a plane of 2 GiB
 }
 
+// ---- dispatch_check <library> band_fp8: the FP8 K/V forms of the ragged and the paged band forward (nsa_band_attn_fwd_ragged_fp8 / _paged_fp8),
+// cases of their own in the style of `band_paged` and at its shapes.  Every case prints the launches and their geometry and the argument
+// blocks as they arrive, member by member: BandAttnParams with its position members, BandFp8Scales and BandPageTable (all zero in the ragged
+// form) of the band launch, SelAttnParams of the combine pass; or the decline with its message.  K / V, the scales, the table and the
+// positions are device pointers the host must never read.
+static void band_fp8_cases() {
+    const int G = 2;
+    const size_t MB = 1 << 20;
+    void *Q = dev(MB), *K = dev(MB), *V = dev(MB), *O = dev(MB), *ws = dev(16 * MB);
+    float *lse = (float *)dev(MB), *kz = (float *)dev(MB), *vz = (float *)dev(MB);
+    int32_t *t_pos = (int32_t *)dev(MB, 0x7f), *table = (int32_t *)dev(MB, 0x7f);
+    g_named = {{"Q", Q, MB}, {"K8", K, MB}, {"V8", V, MB}, {"O", O, MB}, {"lse", lse, MB}, {"k_scale", kz, MB}, {"v_scale", vz, MB}, {"t_pos", t_pos, MB},
+               {"table", table, MB}, {"ws", ws, 16 * MB}};
+    auto ragged_fn = NSA_FN(nsa_band_attn_fwd_ragged_fp8);
+    auto paged_fn = NSA_FN(nsa_band_attn_fwd_paged_fp8);
+    auto ragged_ws = NSA_FN(nsa_band_attn_fwd_ragged_fp8_workspace);
+    auto paged_ws = NSA_FN(nsa_band_attn_fwd_paged_fp8_workspace);
+    std::vector<Want> blocks;
+    for (const char *l : {"band_attn_fwd_fp8(split)", "band_attn_fwd_fp8"}) {
+        blocks.push_back(want<BandAttnParamsRagged>(l, "BandAttnParams"));
+        blocks.push_back(want<nsa::BandFp8Scales>(l, "BandFp8Scales", 1));
+        blocks.push_back(want<nsa::BandPageTable>(l, "BandPageTable", 2));
+    }
+    blocks.push_back(want<nsa::SelAttnParams>("band_attn_combine", "SelAttnParams"));
+    struct Case {
+        int B = 5, S = 1, D = 64, Dv = 0 /* 0: D */, hh = 6, t_max = 4100, dtype = NSA_DT_BF16, S_kv = -1 /* -1: what t_max needs */, dd = 0 /* 0: the branch's */,
+            page_rows = 0 /* 0: 1024 sliding, 64 compressed */, n_pages = 40, max_pages = 0 /* 0: what t_max needs */, w = -1 /* -1: 512 sliding, 2^30 compressed */;
+        bool compressed = false;
+        int64_t table_stride = 0 /* 0: max_pages + 3 */, k_page_stride = 0 /* 0: G * rows * D bytes */, k_row_stride = 0 /* 0: D */;
+        void *Q = nullptr, *K = nullptr, *O = nullptr, *ws = nullptr;
+        size_t ws_bytes = 0;
+        const float *kz = nullptr, *vz = nullptr;
+        const int32_t *table = nullptr, *t_pos = nullptr;
+    };
+    auto band_case = [&](bool paged, const char *label, const std::function<void(Case &)> &tweak) {
+        Case c;
+        c.Q = Q, c.K = K, c.O = O, c.ws = ws, c.ws_bytes = 16 * MB, c.kz = kz + 3, c.vz = vz + 9, c.table = table + 7, c.t_pos = t_pos + 5;
+        tweak(c);
+        const int keys = c.S_kv >= 0 ? c.S_kv : c.compressed ? (c.t_max + 1 < 32 ? 0 : (c.t_max + 1 - 32) / 16 + 1) : c.t_max + 1;
+        const int rows = !paged ? keys : c.page_rows ? c.page_rows : (c.compressed ? 64 : 1024);  // rows of one (b, g) or (page, g) plane
+        const int max_pages = c.max_pages ? c.max_pages : (keys + rows - 1) / (rows ? rows : 1) + (keys == 0);
+        const int64_t tstride = c.table_stride ? c.table_stride : max_pages + 3;
+        const int Dv = c.Dv ? c.Dv : c.D;
+        const int64_t kss = c.k_row_stride ? c.k_row_stride : c.D, kg = (int64_t)rows * kss, kp = c.k_page_stride ? c.k_page_stride : G * kg, vg = (int64_t)rows * Dv;
+        const int w = c.w >= 0 ? c.w : (c.compressed ? 1 << 30 : 512), a = c.compressed ? 32 : 0, dd = c.dd ? c.dd : (c.compressed ? 16 : 1), cc = c.compressed ? 1 : 0;
+        const std::string name = std::string(paged ? "band_attn_fwd_paged_fp8/" : "band_attn_fwd_ragged_fp8/") + label;
+        run_args(name, [&] {
+            if (paged)
+                return paged_fn(c.Q, c.K, V, c.kz, c.vz, c.table, tstride, c.n_pages, max_pages, rows, c.O, lse, c.t_pos, c.t_max, c.B, c.S, G, c.hh, c.D, Dv, kp, kg, kss,
+                                G * vg, vg, Dv, (int64_t)G * rows, rows, (int64_t)G * rows, rows, a, dd, cc, w, c.dtype, 0.f, c.ws, c.ws_bytes, nullptr);
+            return ragged_fn(c.Q, c.K, V, c.kz, c.vz, c.O, lse, c.t_pos, c.t_max, c.B, c.S, G, c.hh, c.D, Dv, keys, kp, kg, kss, G * vg, vg, Dv, (int64_t)G * rows, rows,
+                             (int64_t)G * rows, rows, a, dd, cc, w, c.dtype, 0.f, c.ws, c.ws_bytes, nullptr);
+        }, blocks);
+        if (c.B > 0) printf(",\n%s: %lld", quoted(name + "_workspace").c_str(), (long long)(paged ? paged_ws : ragged_ws)(c.B, c.S, G, c.hh, c.D, Dv, c.dtype));
+    };
+    for (int paged = 0; paged < 2; ++paged) {
+        auto both = [&](const char *label, const std::function<void(Case &)> &tweak) { band_case(paged, label, tweak); };
+        // the shapes of the `band_paged` mode's cases: the three forms of the plan, both branches, both head dimensions
+        both("sliding_B5_S1_split", [](Case &) {});
+        both("compressed_B5_S3_split", [](Case &c) { c.S = 3; c.t_max = 5002; c.compressed = true; });
+        both("sliding_B600_S3_unsplit", [](Case &c) { c.B = 600; c.S = 3; c.t_max = 1000; });
+        both("sliding_B600_S256_nt3", [](Case &c) { c.B = 600; c.S = 256; c.t_max = 1500; });
+        both("sliding_D128_B5_S1_split", [](Case &c) { c.D = 128; });
+        both("sliding_D128_B600_S256_nt2", [](Case &c) { c.D = 128; c.B = 600; c.S = 256; c.t_max = 1500; });
+        both("unsplit_needs_no_workspace", [](Case &c) { c.B = 600; c.S = 3; c.t_max = 1000; c.ws = nullptr; c.ws_bytes = 0; });
+        both("B0_no_launch", [](Case &c) { c.B = 0; c.Q = nullptr; c.kz = nullptr; });
+        // the declines, in the order the call checks them
+        both("dtype7_declined", [](Case &c) { c.dtype = 7; });
+        both("B_minus1", [](Case &c) { c.B = -1; });
+        both("dd_below_1", [](Case &c) { c.dd = -1; });
+        both("t_max_minus1", [](Case &c) { c.t_max = -1; c.S_kv = 64; });
+        both("f16_declined", [](Case &c) { c.dtype = NSA_DT_F16; });
+        both("f32_declined", [](Case &c) { c.dtype = NSA_DT_F32; });
+        both("Dk_ne_Dv_declined", [](Case &c) { c.Dv = 128; });
+        both("D96_declined", [](Case &c) { c.D = 96; });
+        both("h17_declined", [](Case &c) { c.hh = 17; });
+        both("w0_declined", [](Case &c) { c.w = 0; });
+        both("null_Q", [](Case &c) { c.Q = nullptr; });
+        both("null_t_pos", [](Case &c) { c.t_pos = nullptr; });
+        both("null_k_scale", [](Case &c) { c.kz = nullptr; });
+        both("null_v_scale", [](Case &c) { c.vz = nullptr; });
+        both("k_scale_2_bytes_off", [&](Case &c) { c.kz = (const float *)off(kz, 2); });
+        both("t_pos_2_bytes_off", [&](Case &c) { c.t_pos = (const int32_t *)off(t_pos, 2); });
+        both("k_row_stride_not_D", [](Case &c) { c.k_row_stride = 128; });
+        both("K8_8_bytes_off", [&](Case &c) { c.K = off(K, 8); });
+        both("O_4_bytes_off", [&](Case &c) { c.O = off(O, 4); });
+        both("k_plane_stride_not_16", [](Case &c) { c.k_page_stride = (int64_t)2 * 1024 * 64 + 8; });
+        both("no_workspace", [](Case &c) { c.ws = nullptr; c.ws_bytes = 0; });
+        both("workspace_64_bytes", [](Case &c) { c.ws_bytes = 64; });
+        both("workspace_8_bytes_off", [&](Case &c) { c.ws = off(ws, 8); });
+        // two limits in one call: the message is the first check's
+        both("f16_and_w0", [](Case &c) { c.dtype = NSA_DT_F16; c.w = 0; });
+        both("D96_and_f32", [](Case &c) { c.D = 96; c.dtype = NSA_DT_F32; });
+        both("null_k_scale_and_k_row_stride_not_D", [](Case &c) { c.kz = nullptr; c.k_row_stride = 128; });
+        both("null_t_pos_and_null_v_scale", [](Case &c) { c.t_pos = nullptr; c.vz = nullptr; });
+        both("K8_8_bytes_off_and_no_workspace", [&](Case &c) { c.K = off(K, 8); c.ws = nullptr; c.ws_bytes = 0; });
+        both("B0_and_w0", [](Case &c) { c.B = 0; c.w = 0; });
+        if (!paged) {
+            both("S_kv0_declined", [](Case &c) { c.S_kv = 0; });
+            both("S_kv0_and_null_t_pos", [](Case &c) { c.S_kv = 0; c.t_pos = nullptr; });
+            both("S_kv_2pow25_plane_limit", [](Case &c) { c.S_kv = 1 << 25; });              // 2^25 rows of 64 bytes: a plane of 2 GiB
+            both("S_kv_2pow25_minus1", [](Case &c) { c.S_kv = (1 << 25) - 1; });
+            both("S_kv_2pow25_and_no_workspace", [](Case &c) { c.S_kv = 1 << 25; c.ws = nullptr; c.ws_bytes = 0; });
+            continue;
+        }
+        both("sliding_page_rows32", [](Case &c) { c.page_rows = 32; });
+        both("sliding_page_rows65536", [](Case &c) { c.page_rows = 65536; });
+        both("k_page_stride_3GiB", [](Case &c) { c.k_page_stride = (int64_t)3 << 30; });  // bytes
+        both("max_pages_2pow20", [](Case &c) { c.max_pages = 1 << 20; c.table_stride = 1 << 20; });
+        both("page_rows16_declined", [](Case &c) { c.page_rows = 16; });
+        both("page_rows96_declined", [](Case &c) { c.page_rows = 96; });
+        both("page_rows131072_declined", [](Case &c) { c.page_rows = 131072; });
+        both("max_pages_minus1", [](Case &c) { c.max_pages = -1; });
+        both("max_pages_above_2pow20", [](Case &c) { c.max_pages = (1 << 20) + 1; c.table_stride = 1 << 21; });
+        both("n_pages0", [](Case &c) { c.n_pages = 0; });
+        both("null_table", [](Case &c) { c.table = nullptr; });
+        both("table_2_bytes_off", [&](Case &c) { c.table = (const int32_t *)off(table, 2); });
+        both("table_stride_below_max_pages", [](Case &c) { c.table_stride = 4; });
+        both("page_rows16_and_n_pages0", [](Case &c) { c.page_rows = 16; c.n_pages = 0; });
+        both("w0_and_page_rows96", [](Case &c) { c.w = 0; c.page_rows = 96; });
+        both("null_table_and_null_Q", [](Case &c) { c.table = nullptr; c.Q = nullptr; });
+        both("B0_and_n_pages0", [](Case &c) { c.B = 0; c.n_pages = 0; });
+        both("B0_and_null_table", [](Case &c) { c.B = 0; c.table = nullptr; });
+    }
+}
+
 // ---- dispatch_check <library> layer_ragged: the layer's ragged call (nsa_layer_decode_ragged), cases of their own like `ragged`.  Every
 // case prints the launchers in order with their geometry, the plan's answer for the same shape, and "positions": the position pointer and the
 // bound te as they arrive in the argument blocks of the four launches that depend on the position (projection, pooling, the selected branch,
@@ -1075,7 +1212,7 @@ static void layer_paged_cases(bool long_mode = false) {  // long_mode: as layer_
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: dispatch_check <libnsa_sel_hip.so> [ragged | layer_ragged | layer_paged | paged | band_paged | decode_long]\n");
+        fprintf(stderr, "usage: dispatch_check <libnsa_sel_hip.so> [ragged | layer_ragged | layer_paged | paged | band_paged | band_fp8 | decode_long]\n");
         return 2;
     }
     g_lib = dlopen(argv[1], RTLD_NOW | RTLD_GLOBAL);
@@ -1098,6 +1235,12 @@ int main(int argc, char **argv) {
     if (argc >= 3 && !strcmp(argv[2], "band_paged")) {  // the paged band forward alone (tests/test_dispatch_band_paged_host.py)
         printf("{");
         band_paged_cases();
+        printf("\n}\n");
+        return 0;
+    }
+    if (argc >= 3 && !strcmp(argv[2], "band_fp8")) {  // the FP8 band forwards alone (tests/test_dispatch_band_fp8_host.py)
+        printf("{");
+        band_fp8_cases();
         printf("\n}\n");
         return 0;
     }

@@ -255,35 +255,118 @@ int nsa::sel_attn_bwd_impl(const AttnCall &c, const AttnGrads &g) {
     return launch_sel_attn_bwd_generic(P, c.dtype, c.st);
 }
 
-AttnRoute nsa::band_attn_route(const AttnCall &c, const Band &band) {
-    AttnRoute r{AttnRoute::GENERIC, AttnRoute::WS_NONE,
-                c.S_kv > 0 && band.w > 0 && attn_mfma_shape_ok(c.dtype, c.h, c.Dk, c.Dv) && qkv_aligned(c) && out_aligned(c) && slabs_under_2gib(c), 1};
+// the route of a band forward whose operands the MFMA kernels can (fast_ok) or cannot read: the split is taken only if the workspace serves it
+static AttnRoute band_route(const AttnCall &c, bool fast_ok) {
+    AttnRoute r{AttnRoute::GENERIC, AttnRoute::WS_NONE, fast_ok, 1};
     const size_t need = band_attn_workspace(c.B, c.S, c.G, c.h, c.Dk, c.Dv, c.dtype, &r.nsplit);
     if (r.fast_ok && c.variant != 1) r.kind = AttnRoute::MFMA;
     if (r.kind == AttnRoute::MFMA && r.nsplit > 1 && c.ws && ((uintptr_t)c.ws % 16 == 0) && c.ws_bytes >= need) r.ws = AttnRoute::WS_SPLIT;
     return r;
 }
+AttnRoute nsa::band_attn_route(const AttnCall &c, const Band &band) {
+    return band_route(c, c.S_kv > 0 && band.w > 0 && attn_mfma_shape_ok(c.dtype, c.h, c.Dk, c.Dv) && qkv_aligned(c) && out_aligned(c) && slabs_under_2gib(c));
+}
 
-int nsa::band_attn_fwd_impl(const AttnCall &c, const Band &band, int defer, int *ns_used) {
-    if (ns_used) *ns_used = 1;
-    NSA_CHECK_ARG(dtype_ok(c.dtype), "band_attn_fwd: unknown dtype %d", c.dtype);
-    NSA_CHECK_ARG(c.B >= 0 && c.S >= 0 && c.G >= 1 && c.h >= 1 && c.Dk >= 1 && c.Dv >= 1 && c.S_kv >= 0, "band_attn_fwd: negative size");
-    NSA_CHECK_ARG(band.t0 >= 0 && band.dd >= 1 && band.w >= 0, "band_attn_fwd: need t0 >= 0, dd >= 1, w >= 0");
-    NSA_CHECK_ARG(c.variant >= 0 && c.variant <= 2, "band_attn_fwd: unknown variant %d", c.variant);
+// The band forward in every form (BandFwdCall, nsa_host.hpp): each check once, under the condition it applies; the policies that differ between
+// the forms are the named decisions below.  The route, the split count and the workspace are planned from (B, S, G, h, D) alone: they do not
+// depend on the positions, the pages or the K/V format.
+int nsa::band_attn_fwd_impl(const BandFwdCall &f) {
+    const char *who = f.who;
+    const bool ragged = f.pos != nullptr, paged = f.pages != nullptr, fp8 = f.fp8 != nullptr;
+    // generic fallback and `variant`: the scalar and the ragged form have them.  Pools of pages and FP8 K/V run the MFMA kernels only, need a
+    // window of at least one key, and decline everything else: no other kernel reads them
+    const bool mfma_only = paged || fp8;
+    AttnCall c = f.c;
+    Band band = f.band;
+    if (ragged) band.t0 = 0;
+    if (mfma_only) c.variant = 0;
+    const int32_t *t_pos = ragged ? f.pos->t_pos : nullptr;
+    const int t_max = ragged ? f.pos->t_max : 0;
+    if (f.ns_used) *f.ns_used = 1;
+    NSA_CHECK_ARG(dtype_ok(c.dtype), "%s: unknown dtype %d", who, c.dtype);
+    NSA_CHECK_ARG(c.B >= 0 && c.S >= 0 && c.G >= 1 && c.h >= 1 && c.Dk >= 1 && c.Dv >= 1 && c.S_kv >= 0, "%s: negative size", who);
+    const char *bounds = !ragged ? "need t0 >= 0, dd >= 1, w >= 0" : mfma_only ? "need dd >= 1, t_max >= 0" : "need dd >= 1, w >= 0, t_max >= 0";
+    NSA_CHECK_ARG(band.t0 >= 0 && band.dd >= 1 && (mfma_only || band.w >= 0) && t_max >= 0, "%s: %s", who, bounds);
+    NSA_CHECK_ARG(c.variant >= 0 && c.variant <= 2, "%s: unknown variant %d", who, c.variant);
+    if (mfma_only) {
+        if (fp8) NSA_CHECK_ARG(c.dtype == NSA_DT_BF16, "%s: FP8 K / V take bf16 queries only (got dtype %d); f16 and fp32 queries have no FP8 kernel", who, c.dtype);
+        const bool shape_ok = attn_mfma_shape_ok(c.dtype, c.h, c.Dk, c.Dv);
+        if (fp8) NSA_CHECK_ARG(shape_ok, "%s: the MFMA kernels only -- Dk = Dv in {64, 128}, h <= 16 (got Dk = %d, Dv = %d, h = %d)", who, c.Dk, c.Dv, c.h);
+        else NSA_CHECK_ARG(shape_ok, "%s: the MFMA kernels only -- bf16 / f16, Dk = Dv in {64, 128}, h <= 16 (got dtype %d, Dk = %d, Dv = %d, h = %d); no kernel reads "
+                                     "pools of pages for other shapes", who, c.dtype, c.Dk, c.Dv, c.h);
+        NSA_CHECK_ARG(band.w >= 1, "%s: w = %d, the window must hold at least one key (w >= 1)", who, band.w);
+    }
+    if (paged) {
+        const int page_rows = f.pages->page_rows, max_pages = f.pages->max_pages;
+        NSA_CHECK_ARG(page_rows >= 32 && page_rows <= 65536 && (page_rows & (page_rows - 1)) == 0,
+                      "%s: page_rows = %d is not built: a power of two in [32, 65536] (a 32-key tile then touches at most two pages)", who, page_rows);
+        NSA_CHECK_ARG(max_pages >= 1 && max_pages <= (1 << 20), "%s: max_pages = %d, must be in [1, 2^20]", who, max_pages);
+        NSA_CHECK_ARG(f.pages->table.n_pages >= 1, "%s: n_pages = %d, the pools must hold at least one page", who, f.pages->table.n_pages);
+        // (positions are 32-bit: a capacity beyond INT32_MAX rows bounds nothing a position can reach)
+        c.S_kv = (int)std::min<int64_t>((int64_t)max_pages * page_rows, INT32_MAX);
+    }
+    // empty caches: S_kv = 0 is a call of the scalar and the ragged form (every interval empty: the generic kernel writes the zeros / -inf rows);
+    // pools have a capacity of at least one page; FP8 K/V decline them
+    if (fp8) NSA_CHECK_ARG(c.S_kv >= 1, "%s: S_kv = %d, the caches must hold at least one row (there is no kernel for empty FP8 caches)", who, c.S_kv);
     if (c.rows() == 0) return NSA_OK;
-    // S_kv == 0 or w == 0: every interval is empty; the generic kernel writes the zeros / -inf rows
-    NSA_CHECK_ARG(c.Q && c.O && ((c.K && c.V) || c.S_kv == 0), "band_attn_fwd: null pointer");
+    if (paged) {
+        const BandPageTable &pt = f.pages->table;
+        NSA_CHECK_ARG(pt.table != nullptr, "%s: null block table", who);
+        NSA_CHECK_ARG((uintptr_t)pt.table % 4 == 0 && pt.stride >= f.pages->max_pages, "%s: the block table must be 4-byte aligned with a row stride of at least "
+                                                                                      "max_pages = %d (got %lld)", who, f.pages->max_pages, (long long)pt.stride);
+    }
+    NSA_CHECK_ARG(c.Q && c.O && (t_pos || !(ragged || mfma_only)) && ((c.K && c.V) || c.S_kv == 0), "%s: null pointer", who);
+    if (fp8) {
+        NSA_CHECK_ARG(f.fp8->k_scale && f.fp8->v_scale, "%s: null scale: FP8 K / V need k_scale and v_scale (one fp32 per key row)", who);
+        NSA_CHECK_ARG((uintptr_t)t_pos % 4 == 0 && (uintptr_t)f.fp8->k_scale % 4 == 0 && (uintptr_t)f.fp8->v_scale % 4 == 0,
+                      "%s: t_pos and the scales must be 4-byte aligned", who);
+    }
+    NSA_CHECK_ARG((uintptr_t)t_pos % 4 == 0, "%s: t_pos must be 4-byte aligned", who);
+    // alignment unit: 16-byte pieces, which are 8 elements of bf16 / f16 K / V and 16 bytes of FP8 rows that must be contiguous.  The scalar and
+    // the ragged form take operands that miss it on the generic route (band_attn_route), the MFMA-only forms decline them
+    if (fp8) {
+        NSA_CHECK_ARG(c.kss == c.Dk && c.vss == c.Dv, "%s: FP8 K / V rows must be contiguous: row stride %lld / %lld bytes, must be D = %d", who, (long long)c.kss,
+                      (long long)c.vss, c.Dk);
+        NSA_CHECK_ARG((uintptr_t)c.Q % 16 == 0 && (uintptr_t)c.K % 16 == 0 && (uintptr_t)c.V % 16 == 0 && c.ksb % 16 == 0 && c.ksg % 16 == 0 && c.vsb % 16 == 0 &&
+                          c.vsg % 16 == 0 && out_aligned(c),
+                      "%s: Q, K8 and V8 must be 16-byte aligned with batch (page) and group strides in multiples of 16 bytes, and O 8-byte aligned", who);
+    } else if (paged) {
+        NSA_CHECK_ARG(qkv_aligned(c) && out_aligned(c), "%s: Q and the two pools must be 16-byte aligned with page, group and row strides in multiples of "
+                                                        "8 elements, and O 8-byte aligned", who);
+    }
+    // 32-bit plane bound: the kernels' only 32-bit byte offsets are those of a row inside one plane -- the K / V slab of a (b, g)
+    // (slabs_under_2gib, part of band_attn_route), page_rows rows of a bf16 / f16 (page, g), S_kv rows of D bytes of ragged FP8 caches (FP8
+    // pools: at most 65536 rows of 128 bytes)
+    const int64_t lim = (int64_t)1 << 31;
+    if (paged && !fp8)
+        NSA_CHECK_ARG(c.kss >= 1 && c.vss >= 1 && (int64_t)f.pages->page_rows * c.kss * 2 < lim && (int64_t)f.pages->page_rows * c.vss * 2 < lim,
+                      "%s: the row strides put a page's rows outside the 32-bit offsets of one (page, group) plane (page_rows = %d rows: under 2 GiB)", who,
+                      f.pages->page_rows);
+    if (fp8 && !paged) NSA_CHECK_ARG((int64_t)c.S_kv * c.Dk < lim, "%s: S_kv = %d rows of %d bytes leave the 32-bit offsets of one (b, g) plane", who, c.S_kv, c.Dk);
     BandAttnParams P = band_attn_params(c, band);
-    const AttnRoute r = band_attn_route(c, band);
-    if (c.variant == 2) NSA_CHECK_ARG(r.fast_ok, "band_attn_fwd: MFMA variant requested but shape/dtype/alignment unsupported");
+    P.t_pos = t_pos;
+    P.t_max = t_max;
+    const AttnRoute r = mfma_only ? band_route(c, true) : band_attn_route(c, band);
+    if (c.variant == 2) NSA_CHECK_ARG(r.fast_ok, "%s: MFMA variant requested but shape/dtype/alignment unsupported", who);
     if (r.kind != AttnRoute::MFMA) return launch_band_attn_fwd_generic(P, c.dtype, c.st);
+    // workspace: a plan that splits runs unsplit when no workspace serves it -- but not over FP8 K/V, which decline, so that a shape has one form
+    // and one set of bits
+    if (fp8 && r.nsplit > 1)
+        NSA_CHECK_ARG(r.ws == AttnRoute::WS_SPLIT, "%s: workspace missing, misaligned or too small: the plan splits a row over %d waves and needs %zu bytes (16-byte aligned)",
+                      who, r.nsplit, band_attn_workspace(c.B, c.S, c.G, c.h, c.Dk, c.Dv, c.dtype, nullptr));
     if (r.ws == AttnRoute::WS_SPLIT) {
         P.part = (float *)c.ws;
         P.nsplit = r.nsplit;
-        P.defer_combine = defer;
-        if (ns_used && defer) *ns_used = r.nsplit;
+        P.defer_combine = f.defer;
+        if (f.ns_used && f.defer) *f.ns_used = r.nsplit;
     }
-    return launch_band_attn_fwd_mfma(P, c.dtype, c.st);
+    BandPageTable pt{};
+    if (paged) {
+        pt = f.pages->table;
+        pt.shift = __builtin_ctz((unsigned)f.pages->page_rows);
+    }
+    if (fp8) return launch_band_attn_fwd_fp8(P, *f.fp8, c.st, paged ? &pt : nullptr);
+    return launch_band_attn_fwd_mfma(P, c.dtype, c.st, paged ? &pt : nullptr);
 }
 
 extern "C" {
@@ -299,17 +382,68 @@ int nsa_sel_attn_bwd(const void *Q, const void *K, const void *V, const int32_t 
 }
 
 // ------------------------------------------------------------------------------ band attention
-size_t nsa_band_attn_fwd_workspace(int B, int S, int G, int h, int Dk, int Dv, int dtype) {
-    return band_attn_workspace(B, S, G, h, Dk, Dv, dtype, nullptr);
-}
+// the five workspace queries: one plan, made from (B, S, G, h, D) alone -- it depends on neither the positions, the pages nor the K/V format
+#define NSA_BAND_FWD_WORKSPACE(name) \
+    size_t name(int B, int S, int G, int h, int Dk, int Dv, int dtype) { return band_attn_workspace(B, S, G, h, Dk, Dv, dtype, nullptr); }
+NSA_BAND_FWD_WORKSPACE(nsa_band_attn_fwd_workspace)
+NSA_BAND_FWD_WORKSPACE(nsa_band_attn_fwd_ragged_workspace)
+NSA_BAND_FWD_WORKSPACE(nsa_band_attn_fwd_paged_workspace)
+NSA_BAND_FWD_WORKSPACE(nsa_band_attn_fwd_ragged_fp8_workspace)
+NSA_BAND_FWD_WORKSPACE(nsa_band_attn_fwd_paged_fp8_workspace)
+#undef NSA_BAND_FWD_WORKSPACE
 
+// the forward's entry points fill the family's block (BandFwdCall) with what they carry: positions, a page table, scales
 int nsa_band_attn_fwd(const void *Q, const void *K, const void *V, void *O, float *lse, int B, int S, int G, int h, int Dk,
                       int Dv, int S_kv, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg, int64_t vss, int t0,
                       int a, int dd, int c, int w, int dtype, float scale, int variant, void *workspace, size_t workspace_bytes,
                       void *stream) {
-    return band_attn_fwd_impl(AttnCall{Q, K, V, nullptr, O, lse, B, S, G, h, Dk, Dv, S_kv, 0, ksb, ksg, kss, vsb, vsg, vss, dtype, scale, variant, workspace,
-                                       workspace_bytes, (hipStream_t)stream},
-                              Band{t0, a, dd, c, w}, 0, nullptr);
+    return band_attn_fwd_impl(BandFwdCall{"band_attn_fwd", AttnCall{Q, K, V, nullptr, O, lse, B, S, G, h, Dk, Dv, S_kv, 0, ksb, ksg, kss, vsb, vsg, vss, dtype, scale, variant,
+                                                                    workspace, workspace_bytes, (hipStream_t)stream},
+                                          Band{t0, a, dd, c, w}});
+}
+
+int nsa_band_attn_fwd_ragged(const void *Q, const void *K, const void *V, void *O, float *lse, const int32_t *t_pos, int t_max, int B, int S, int G,
+                             int h, int Dk, int Dv, int S_kv, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg, int64_t vss, int a, int dd,
+                             int c, int w, int dtype, float scale, int variant, void *workspace, size_t workspace_bytes, void *stream) {
+    const BandPositions pos{t_pos, t_max};
+    return band_attn_fwd_impl(BandFwdCall{"band_attn_fwd_ragged", AttnCall{Q, K, V, nullptr, O, lse, B, S, G, h, Dk, Dv, S_kv, 0, ksb, ksg, kss, vsb, vsg, vss, dtype, scale,
+                                                                           variant, workspace, workspace_bytes, (hipStream_t)stream},
+                                          Band{0, a, dd, c, w}, &pos});
+}
+
+int nsa_band_attn_fwd_paged(const void *Q, const void *K_pool, const void *V_pool, const int32_t *block_table, int64_t table_stride, int n_pages, int max_pages,
+                            int page_rows, void *O, float *lse, const int32_t *t_pos, int t_max, int B, int S, int G, int h, int Dk, int Dv, int64_t ksp, int64_t ksg,
+                            int64_t kss, int64_t vsp, int64_t vsg, int64_t vss, int a, int dd, int c, int w, int dtype, float scale, void *workspace,
+                            size_t workspace_bytes, void *stream) {
+    const BandPositions pos{t_pos, t_max};
+    const BandPages pages{BandPageTable{block_table, table_stride, n_pages, 0}, max_pages, page_rows};
+    return band_attn_fwd_impl(BandFwdCall{"band_attn_fwd_paged", AttnCall{Q, K_pool, V_pool, nullptr, O, lse, B, S, G, h, Dk, Dv, 0, 0, ksp, ksg, kss, vsp, vsg, vss, dtype,
+                                                                          scale, 0, workspace, workspace_bytes, (hipStream_t)stream},
+                                          Band{0, a, dd, c, w}, &pos, &pages});
+}
+
+int nsa_band_attn_fwd_ragged_fp8(const void *Q, const void *K8, const void *V8, const float *k_scale, const float *v_scale, void *O, float *lse, const int32_t *t_pos,
+                                 int t_max, int B, int S, int G, int h, int Dk, int Dv, int S_kv, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg,
+                                 int64_t vss, int64_t kzb, int64_t kzg, int64_t vzb, int64_t vzg, int a, int dd, int c, int w, int dtype, float scale, void *workspace,
+                                 size_t workspace_bytes, void *stream) {
+    const BandPositions pos{t_pos, t_max};
+    const BandFp8Scales Z{k_scale, v_scale, kzb, kzg, vzb, vzg};
+    return band_attn_fwd_impl(BandFwdCall{"band_attn_fwd_ragged_fp8", AttnCall{Q, K8, V8, nullptr, O, lse, B, S, G, h, Dk, Dv, S_kv, 0, ksb, ksg, kss, vsb, vsg, vss, dtype,
+                                                                               scale, 0, workspace, workspace_bytes, (hipStream_t)stream},
+                                          Band{0, a, dd, c, w}, &pos, nullptr, &Z});
+}
+
+int nsa_band_attn_fwd_paged_fp8(const void *Q, const void *K8_pool, const void *V8_pool, const float *k_scale_pool, const float *v_scale_pool,
+                                const int32_t *block_table, int64_t table_stride, int n_pages, int max_pages, int page_rows, void *O, float *lse, const int32_t *t_pos,
+                                int t_max, int B, int S, int G, int h, int Dk, int Dv, int64_t ksp, int64_t ksg, int64_t kss, int64_t vsp, int64_t vsg, int64_t vss,
+                                int64_t kzp, int64_t kzg, int64_t vzp, int64_t vzg, int a, int dd, int c, int w, int dtype, float scale, void *workspace,
+                                size_t workspace_bytes, void *stream) {
+    const BandPositions pos{t_pos, t_max};
+    const BandPages pages{BandPageTable{block_table, table_stride, n_pages, 0}, max_pages, page_rows};
+    const BandFp8Scales Z{k_scale_pool, v_scale_pool, kzp, kzg, vzp, vzg};
+    return band_attn_fwd_impl(BandFwdCall{"band_attn_fwd_paged_fp8", AttnCall{Q, K8_pool, V8_pool, nullptr, O, lse, B, S, G, h, Dk, Dv, 0, 0, ksp, ksg, kss, vsp, vsg, vss,
+                                                                              dtype, scale, 0, workspace, workspace_bytes, (hipStream_t)stream},
+                                          Band{0, a, dd, c, w}, &pos, &pages, &Z});
 }
 
 // Band attention backward.  dQ: dense 48-slot kernel (MFMA route); dK/dV: the key-block-major selection backward kernels fed
@@ -771,171 +905,7 @@ int nsa::sel_decode_paged_impl(const SelDecodeCall &c0, const DecPageTable &pt, 
     return launch_decode_rows(c, (hipStream_t)stream, t_pos, t_max, &pt);
 }
 
-int nsa::band_attn_fwd_ragged_impl(const AttnCall &c, const Band &band, const int32_t *t_pos, int t_max) {
-    NSA_CHECK_ARG(dtype_ok(c.dtype), "band_attn_fwd_ragged: unknown dtype %d", c.dtype);
-    NSA_CHECK_ARG(c.B >= 0 && c.S >= 0 && c.G >= 1 && c.h >= 1 && c.Dk >= 1 && c.Dv >= 1 && c.S_kv >= 0, "band_attn_fwd_ragged: negative size");
-    NSA_CHECK_ARG(band.dd >= 1 && band.w >= 0 && t_max >= 0, "band_attn_fwd_ragged: need dd >= 1, w >= 0, t_max >= 0");
-    NSA_CHECK_ARG(c.variant >= 0 && c.variant <= 2, "band_attn_fwd_ragged: unknown variant %d", c.variant);
-    if (c.rows() == 0) return NSA_OK;
-    NSA_CHECK_ARG(c.Q && c.O && t_pos && ((c.K && c.V) || c.S_kv == 0), "band_attn_fwd_ragged: null pointer");
-    NSA_CHECK_ARG((uintptr_t)t_pos % 4 == 0, "band_attn_fwd_ragged: t_pos must be 4-byte aligned");
-    // the route, the split count and the workspace do not depend on the positions: they are the scalar call's (planned from B, S, G, h, D)
-    BandAttnParams P = band_attn_params(c, Band{0, band.a, band.dd, band.c, band.w});
-    P.t_pos = t_pos;
-    P.t_max = t_max;
-    const AttnRoute r = band_attn_route(c, band);
-    if (c.variant == 2) NSA_CHECK_ARG(r.fast_ok, "band_attn_fwd_ragged: MFMA variant requested but shape/dtype/alignment unsupported");
-    if (r.kind != AttnRoute::MFMA) return launch_band_attn_fwd_generic(P, c.dtype, c.st);
-    if (r.ws == AttnRoute::WS_SPLIT) {
-        P.part = (float *)c.ws;
-        P.nsplit = r.nsplit;
-    }
-    return launch_band_attn_fwd_mfma(P, c.dtype, c.st);
-}
-
-// The ragged band forward over paged caches.  c: K / V are the pools, ksb / vsb their PAGE strides; S_kv is filled here with the capacity
-// max_pages * page_rows.  One route -- the MFMA kernels' PAGED form -- with the plan (form, split count, workspace) of the scalar and the
-// ragged call; everything else is declined, there is no generic kernel over pools.
-int nsa::band_attn_fwd_paged_impl(const AttnCall &c0, const Band &band, const BandPageTable &pt0, int max_pages, int page_rows, const int32_t *t_pos, int t_max) {
-    NSA_CHECK_ARG(dtype_ok(c0.dtype), "band_attn_fwd_paged: unknown dtype %d", c0.dtype);
-    NSA_CHECK_ARG(c0.B >= 0 && c0.S >= 0 && c0.G >= 1 && c0.h >= 1 && c0.Dk >= 1 && c0.Dv >= 1, "band_attn_fwd_paged: negative size");
-    NSA_CHECK_ARG(band.dd >= 1 && t_max >= 0, "band_attn_fwd_paged: need dd >= 1, t_max >= 0");
-    NSA_CHECK_ARG(attn_mfma_shape_ok(c0.dtype, c0.h, c0.Dk, c0.Dv),
-                  "band_attn_fwd_paged: the MFMA kernels only -- bf16 / f16, Dk = Dv in {64, 128}, h <= 16 (got dtype %d, Dk = %d, Dv = %d, h = %d); no kernel reads "
-                  "pools of pages for other shapes", c0.dtype, c0.Dk, c0.Dv, c0.h);
-    NSA_CHECK_ARG(band.w >= 1, "band_attn_fwd_paged: w = %d, the window must hold at least one key (w >= 1)", band.w);
-    NSA_CHECK_ARG(page_rows >= 32 && page_rows <= 65536 && (page_rows & (page_rows - 1)) == 0,
-                  "band_attn_fwd_paged: page_rows = %d is not built: a power of two in [32, 65536] (a 32-key tile then touches at most two pages)", page_rows);
-    NSA_CHECK_ARG(max_pages >= 1 && max_pages <= (1 << 20), "band_attn_fwd_paged: max_pages = %d, must be in [1, 2^20]", max_pages);
-    NSA_CHECK_ARG(pt0.n_pages >= 1, "band_attn_fwd_paged: n_pages = %d, the pools must hold at least one page", pt0.n_pages);
-    AttnCall c = c0;
-    // (positions are 32-bit: a capacity beyond INT32_MAX rows bounds nothing a position can reach)
-    c.S_kv = (int)std::min<int64_t>((int64_t)max_pages * page_rows, INT32_MAX);
-    if (c.rows() == 0) return NSA_OK;
-    NSA_CHECK_ARG(pt0.table != nullptr, "band_attn_fwd_paged: null block table");
-    NSA_CHECK_ARG((uintptr_t)pt0.table % 4 == 0 && pt0.stride >= max_pages, "band_attn_fwd_paged: the block table must be 4-byte aligned with a row stride of at least "
-                                                                           "max_pages = %d (got %lld)", max_pages, (long long)pt0.stride);
-    NSA_CHECK_ARG(c.Q && c.K && c.V && c.O && t_pos, "band_attn_fwd_paged: null pointer");
-    NSA_CHECK_ARG((uintptr_t)t_pos % 4 == 0, "band_attn_fwd_paged: t_pos must be 4-byte aligned");
-    NSA_CHECK_ARG(qkv_aligned(c) && out_aligned(c), "band_attn_fwd_paged: Q and the two pools must be 16-byte aligned with page, group and row strides in multiples of "
-                                                    "8 elements, and O 8-byte aligned");
-    // the kernel's only 32-bit byte offsets are those of a row inside one (page, group) plane of page_rows rows
-    const int64_t lim = (int64_t)1 << 31;
-    NSA_CHECK_ARG(c.kss >= 1 && c.vss >= 1 && (int64_t)page_rows * c.kss * 2 < lim && (int64_t)page_rows * c.vss * 2 < lim,
-                  "band_attn_fwd_paged: the row strides put a page's rows outside the 32-bit offsets of one (page, group) plane (page_rows = %d rows: under 2 GiB)",
-                  page_rows);
-    BandAttnParams P = band_attn_params(c, Band{0, band.a, band.dd, band.c, band.w});
-    P.t_pos = t_pos;
-    P.t_max = t_max;
-    // the split count and the workspace do not depend on the positions or the pages: the scalar call's; without the workspace, the unsplit form
-    int ns = 1;
-    const size_t need = band_attn_workspace(c.B, c.S, c.G, c.h, c.Dk, c.Dv, c.dtype, &ns);
-    if (ns > 1 && c.ws && ((uintptr_t)c.ws % 16 == 0) && c.ws_bytes >= need) {
-        P.part = (float *)c.ws;
-        P.nsplit = ns;
-    }
-    BandPageTable pt = pt0;
-    pt.shift = __builtin_ctz((unsigned)page_rows);
-    return launch_band_attn_fwd_mfma(P, c.dtype, c.st, &pt);
-}
-
-// The FP8 K/V form of the two calls above (nsa_band_attn_fwd_ragged_fp8; with pt0: nsa_band_attn_fwd_paged_fp8).  c: K / V are e4m3 bytes and
-// their strides count bytes.  One route -- the FP8 kernels of band_attn_fp8.hip in the form band_plan gives the shape -- and no fallback: a
-// plan that splits asks for its workspace instead of running unsplit, so that a shape has one form and one set of bits.
-static int band_attn_fwd_fp8_impl(const char *who, const AttnCall &c0, const Band &band, const BandFp8Scales &Z, const BandPageTable *pt0, int max_pages, int page_rows,
-                                  const int32_t *t_pos, int t_max) {
-    NSA_CHECK_ARG(dtype_ok(c0.dtype), "%s: unknown dtype %d", who, c0.dtype);
-    NSA_CHECK_ARG(c0.B >= 0 && c0.S >= 0 && c0.G >= 1 && c0.h >= 1 && c0.Dk >= 1 && c0.Dv >= 1 && c0.S_kv >= 0, "%s: negative size", who);
-    NSA_CHECK_ARG(band.dd >= 1 && t_max >= 0, "%s: need dd >= 1, t_max >= 0", who);
-    NSA_CHECK_ARG(c0.dtype == NSA_DT_BF16, "%s: FP8 K / V take bf16 queries only (got dtype %d); f16 and fp32 queries have no FP8 kernel", who, c0.dtype);
-    NSA_CHECK_ARG(attn_mfma_shape_ok(c0.dtype, c0.h, c0.Dk, c0.Dv), "%s: the MFMA kernels only -- Dk = Dv in {64, 128}, h <= 16 (got Dk = %d, Dv = %d, h = %d)", who,
-                  c0.Dk, c0.Dv, c0.h);
-    NSA_CHECK_ARG(band.w >= 1, "%s: w = %d, the window must hold at least one key (w >= 1)", who, band.w);
-    AttnCall c = c0;
-    if (pt0) {
-        NSA_CHECK_ARG(page_rows >= 32 && page_rows <= 65536 && (page_rows & (page_rows - 1)) == 0,
-                      "%s: page_rows = %d is not built: a power of two in [32, 65536] (a 32-key tile then touches at most two pages)", who, page_rows);
-        NSA_CHECK_ARG(max_pages >= 1 && max_pages <= (1 << 20), "%s: max_pages = %d, must be in [1, 2^20]", who, max_pages);
-        NSA_CHECK_ARG(pt0->n_pages >= 1, "%s: n_pages = %d, the pools must hold at least one page", who, pt0->n_pages);
-        c.S_kv = (int)std::min<int64_t>((int64_t)max_pages * page_rows, INT32_MAX);
-    }
-    NSA_CHECK_ARG(c.S_kv >= 1, "%s: S_kv = %d, the caches must hold at least one row (there is no kernel for empty FP8 caches)", who, c.S_kv);
-    if (c.rows() == 0) return NSA_OK;
-    if (pt0) {
-        NSA_CHECK_ARG(pt0->table != nullptr, "%s: null block table", who);
-        NSA_CHECK_ARG((uintptr_t)pt0->table % 4 == 0 && pt0->stride >= max_pages, "%s: the block table must be 4-byte aligned with a row stride of at least max_pages = %d "
-                                                                                  "(got %lld)", who, max_pages, (long long)pt0->stride);
-    }
-    NSA_CHECK_ARG(c.Q && c.K && c.V && c.O && t_pos, "%s: null pointer", who);
-    NSA_CHECK_ARG(Z.k_scale && Z.v_scale, "%s: null scale: FP8 K / V need k_scale and v_scale (one fp32 per key row)", who);
-    NSA_CHECK_ARG((uintptr_t)t_pos % 4 == 0 && (uintptr_t)Z.k_scale % 4 == 0 && (uintptr_t)Z.v_scale % 4 == 0, "%s: t_pos and the scales must be 4-byte aligned", who);
-    NSA_CHECK_ARG(c.kss == c.Dk && c.vss == c.Dv, "%s: FP8 K / V rows must be contiguous: row stride %lld / %lld bytes, must be D = %d", who, (long long)c.kss,
-                  (long long)c.vss, c.Dk);
-    NSA_CHECK_ARG((uintptr_t)c.Q % 16 == 0 && (uintptr_t)c.K % 16 == 0 && (uintptr_t)c.V % 16 == 0 && c.ksb % 16 == 0 && c.ksg % 16 == 0 && c.vsb % 16 == 0 &&
-                      c.vsg % 16 == 0 && out_aligned(c),
-                  "%s: Q, K8 and V8 must be 16-byte aligned with batch (page) and group strides in multiples of 16 bytes, and O 8-byte aligned", who);
-    // the kernel's 32-bit byte offsets are those of a row inside one plane: S_kv rows (pools: page_rows <= 65536 rows) of D bytes
-    NSA_CHECK_ARG(pt0 || (int64_t)c.S_kv * c.Dk < ((int64_t)1 << 31), "%s: S_kv = %d rows of %d bytes leave the 32-bit offsets of one (b, g) plane", who, c.S_kv, c.Dk);
-    BandAttnParams P = band_attn_params(c, Band{0, band.a, band.dd, band.c, band.w});
-    P.t_pos = t_pos;
-    P.t_max = t_max;
-    int ns = 1;
-    const size_t need = band_attn_workspace(c.B, c.S, c.G, c.h, c.Dk, c.Dv, c.dtype, &ns);
-    if (ns > 1) {
-        NSA_CHECK_ARG(c.ws && ((uintptr_t)c.ws % 16 == 0) && c.ws_bytes >= need,
-                      "%s: workspace missing, misaligned or too small: the plan splits a row over %d waves and needs %zu bytes (16-byte aligned)", who, ns, need);
-        P.part = (float *)c.ws;
-        P.nsplit = ns;
-    }
-    if (!pt0) return launch_band_attn_fwd_fp8(P, Z, c.st);
-    BandPageTable pt = *pt0;
-    pt.shift = __builtin_ctz((unsigned)page_rows);
-    return launch_band_attn_fwd_fp8(P, Z, c.st, &pt);
-}
-
 extern "C" {
-
-size_t nsa_band_attn_fwd_ragged_fp8_workspace(int B, int S, int G, int h, int Dk, int Dv, int dtype) {
-    return band_attn_workspace(B, S, G, h, Dk, Dv, dtype, nullptr);  // the bf16 call's: the plan does not depend on the K/V format
-}
-size_t nsa_band_attn_fwd_paged_fp8_workspace(int B, int S, int G, int h, int Dk, int Dv, int dtype) {
-    return band_attn_workspace(B, S, G, h, Dk, Dv, dtype, nullptr);
-}
-
-int nsa_band_attn_fwd_ragged_fp8(const void *Q, const void *K8, const void *V8, const float *k_scale, const float *v_scale, void *O, float *lse, const int32_t *t_pos,
-                                 int t_max, int B, int S, int G, int h, int Dk, int Dv, int S_kv, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg,
-                                 int64_t vss, int64_t kzb, int64_t kzg, int64_t vzb, int64_t vzg, int a, int dd, int c, int w, int dtype, float scale, void *workspace,
-                                 size_t workspace_bytes, void *stream) {
-    return band_attn_fwd_fp8_impl("band_attn_fwd_ragged_fp8",
-                                  AttnCall{Q, K8, V8, nullptr, O, lse, B, S, G, h, Dk, Dv, S_kv, 0, ksb, ksg, kss, vsb, vsg, vss, dtype, scale, 0, workspace,
-                                           workspace_bytes, (hipStream_t)stream},
-                                  Band{0, a, dd, c, w}, BandFp8Scales{k_scale, v_scale, kzb, kzg, vzb, vzg}, nullptr, 0, 0, t_pos, t_max);
-}
-
-int nsa_band_attn_fwd_paged_fp8(const void *Q, const void *K8_pool, const void *V8_pool, const float *k_scale_pool, const float *v_scale_pool,
-                                const int32_t *block_table, int64_t table_stride, int n_pages, int max_pages, int page_rows, void *O, float *lse, const int32_t *t_pos,
-                                int t_max, int B, int S, int G, int h, int Dk, int Dv, int64_t ksp, int64_t ksg, int64_t kss, int64_t vsp, int64_t vsg, int64_t vss,
-                                int64_t kzp, int64_t kzg, int64_t vzp, int64_t vzg, int a, int dd, int c, int w, int dtype, float scale, void *workspace,
-                                size_t workspace_bytes, void *stream) {
-    const BandPageTable pt{block_table, table_stride, n_pages, 0};
-    return band_attn_fwd_fp8_impl("band_attn_fwd_paged_fp8",
-                                  AttnCall{Q, K8_pool, V8_pool, nullptr, O, lse, B, S, G, h, Dk, Dv, 0, 0, ksp, ksg, kss, vsp, vsg, vss, dtype, scale, 0, workspace,
-                                           workspace_bytes, (hipStream_t)stream},
-                                  Band{0, a, dd, c, w}, BandFp8Scales{k_scale_pool, v_scale_pool, kzp, kzg, vzp, vzg}, &pt, max_pages, page_rows, t_pos, t_max);
-}
-
-size_t nsa_band_attn_fwd_paged_workspace(int B, int S, int G, int h, int Dk, int Dv, int dtype) {
-    return band_attn_workspace(B, S, G, h, Dk, Dv, dtype, nullptr);  // planned from (B, S, G, h, D) alone: the scalar and the ragged call's
-}
-
-int nsa_band_attn_fwd_paged(const void *Q, const void *K_pool, const void *V_pool, const int32_t *block_table, int64_t table_stride, int n_pages, int max_pages,
-                            int page_rows, void *O, float *lse, const int32_t *t_pos, int t_max, int B, int S, int G, int h, int Dk, int Dv, int64_t ksp, int64_t ksg,
-                            int64_t kss, int64_t vsp, int64_t vsg, int64_t vss, int a, int dd, int c, int w, int dtype, float scale, void *workspace,
-                            size_t workspace_bytes, void *stream) {
-    return band_attn_fwd_paged_impl(AttnCall{Q, K_pool, V_pool, nullptr, O, lse, B, S, G, h, Dk, Dv, 0, 0, ksp, ksg, kss, vsp, vsg, vss, dtype, scale, 0, workspace,
-                                             workspace_bytes, (hipStream_t)stream},
-                                    Band{0, a, dd, c, w}, BandPageTable{block_table, table_stride, n_pages, 0}, max_pages, page_rows, t_pos, t_max);
-}
 
 int nsa_sel_decode_ragged(const void *Q, const void *K_cmp, const void *K, const void *V, const int32_t *csc_ptr, const int32_t *csc_rows,
                           const float *csc_vals, int32_t *ranges_out, void *O, const int32_t *t_pos, int t_max, int B, int S, int G, int h, int Dk,
@@ -1058,18 +1028,6 @@ int nsa_sel_decode_ragged_plan(int B, int S, int G, int h, int Dk, int Dv, int S
     // one launch or none: the separate launches take a scalar position only, so a declined shape has no route (launches 0, form -1)
     *launches = decode_ragged_shape_plan(sel_decode_plan_call(B, S, G, h, Dk, Dv, S_cmp, S_sel, S_kv, n_top, dtype), t_max, form, nullptr, nullptr) ? 1 : 0;
     return NSA_OK;
-}
-
-int nsa_band_attn_fwd_ragged(const void *Q, const void *K, const void *V, void *O, float *lse, const int32_t *t_pos, int t_max, int B, int S, int G,
-                             int h, int Dk, int Dv, int S_kv, int64_t ksb, int64_t ksg, int64_t kss, int64_t vsb, int64_t vsg, int64_t vss, int a, int dd,
-                             int c, int w, int dtype, float scale, int variant, void *workspace, size_t workspace_bytes, void *stream) {
-    return band_attn_fwd_ragged_impl(AttnCall{Q, K, V, nullptr, O, lse, B, S, G, h, Dk, Dv, S_kv, 0, ksb, ksg, kss, vsb, vsg, vss, dtype, scale, variant,
-                                              workspace, workspace_bytes, (hipStream_t)stream},
-                                     Band{0, a, dd, c, w}, t_pos, t_max);
-}
-
-size_t nsa_band_attn_fwd_ragged_workspace(int B, int S, int G, int h, int Dk, int Dv, int dtype) {
-    return band_attn_workspace(B, S, G, h, Dk, Dv, dtype, nullptr);  // the split count is planned from the row count alone: the scalar call's
 }
 
 int nsa_sel_decode_step(const void *Q, const void *K_cmp, const void *K, const void *V, const int32_t *csc_ptr,

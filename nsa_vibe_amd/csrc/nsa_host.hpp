@@ -186,6 +186,30 @@ struct AttnGrads {
     void *dQ;
     float *dK, *dV;
 };
+// What the band forward family (nsa_band_attn_fwd, its _ragged, _paged, _ragged_fp8 and _paged_fp8 forms, and the branches of the layer calls)
+// passes around.  The form of a call is read from what the block holds, never from the entry point that filled it:
+//   pos:   per-sequence positions -- row (b, s) at t_pos[b] + s, band.t0 is not read; null: every sequence at band.t0
+//   pages: c.K / c.V are pools of pages (c.ksb / c.vsb their page strides, c.S_kv not read: the capacity is max_pages * page_rows)
+//   fp8:   c.K / c.V are e4m3 bytes (their strides count bytes) with one fp32 scale per row
+// who: the entry point's name in messages.  defer / ns_used: the split-KV hand-over of the layer's decode step (nsa_internal.hpp)
+struct BandPositions {
+    const int32_t *t_pos;  // device [B]
+    int t_max;             // host bound of t_pos[b] + S - 1
+};
+struct BandPages {
+    BandPageTable table;  // (shift is filled from page_rows)
+    int max_pages, page_rows;
+};
+struct BandFwdCall {
+    const char *who;
+    AttnCall c;
+    Band band;
+    const BandPositions *pos;
+    const BandPages *pages;
+    const BandFp8Scales *fp8;
+    int defer;
+    int *ns_used;
+};
 // the branches of a layer call over the S rows of Q (variant 0, no lse; ws: the branch's scratch): selected, sliding, compressed
 inline AttnCall selected_call(const nsa_layer_desc *L, const nsa_kv_desc *kv, const CacheStrides &C, const void *Q, const int32_t *ranges, void *O, int S,
                               int S_kv, int n, void *ws, size_t ws_bytes, void *stream) {

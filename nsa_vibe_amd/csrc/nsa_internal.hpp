@@ -14,8 +14,9 @@ struct AttnCall;   // nsa_host.hpp: the arguments of the attention family (nsa_s
 struct Band;       // nsa_host.hpp: the band of a band-attention call
 struct AttnGrads;  // nsa_host.hpp: dO, dQ, dK, dV
 struct SelectCall;  // nsa_host.hpp: the top-n selection of a call's rows
+struct BandFwdCall;  // nsa_host.hpp: a band forward in any of its forms (scalar t0, per-sequence positions, pools of pages, FP8 K/V)
 int sel_attn_fwd_impl(const AttnCall &c, int defer, int *ns_used);
-int band_attn_fwd_impl(const AttnCall &c, const Band &band, int defer, int *ns_used);
+int band_attn_fwd_impl(const BandFwdCall &f);
 int sel_attn_bwd_impl(const AttnCall &c, const AttnGrads &g);
 // top-n ranges of the call's rows from p_grp [R, S_sel] into s.ranges_out (= c.ranges), then the attention over them: one launch or two
 int sel_select_attn_impl(const float *p_grp, int S_sel, int l_sel, const SelectCall &s, const AttnCall &c);
@@ -72,12 +73,6 @@ int sel_decode_ragged_impl(const SelDecodeCall &c, const int32_t *t_pos, int t_m
 // the paged form's plan: the ragged form's with one (page, group) plane of 1024 rows as the extent of the 32-bit offsets
 bool decode_paged_shape_plan(const SelDecodeCall &c, int t_max, int *form, int *nw_out, const char **why);
 int sel_decode_paged_impl(const SelDecodeCall &c, const DecPageTable &pt, int max_pages, int page_tokens, const int32_t *t_pos, int t_max, void *stream);
-// the band forward with per-sequence positions (nsa_band_attn_fwd_ragged): band.t0 is ignored
-int band_attn_fwd_ragged_impl(const AttnCall &c, const Band &band, const int32_t *t_pos, int t_max);
-// the ragged band forward over paged caches (nsa_band_attn_fwd_paged): c.K / c.V are the pools, c.ksb / c.vsb their page strides, c.S_kv is
-// ignored (the capacity is max_pages * page_rows); pt.shift is filled from page_rows
-struct BandPageTable;  // sel_attn_params.hpp
-int band_attn_fwd_paged_impl(const AttnCall &c, const Band &band, const BandPageTable &pt, int max_pages, int page_rows, const int32_t *t_pos, int t_max);
 
 // ---- the scorer and selector family behind the C ABI (nsa_api.hip): what nsa_sel_scores[_rows], nsa_sel_scores_select[_rows] and
 // nsa_select_topn_ranges run once their arguments are in the blocks

@@ -200,8 +200,10 @@ static int layer_rows(const char *who, const nsa_layer_desc *L, const nsa_kv_des
         if (int rc = sel_select_attn_impl(p_grp, S_sel, L->l_sel, select, attend)) return rc;
     }
     // sliding and compressed branches at the rows' absolute positions
-    if (int rc = band_attn_fwd_impl(sliding_call(L, kv, C, Q, Owin, S, S_kv, ws + W.band, W.band_bytes, stream), sliding_band(t0, L->w), 0, nullptr)) return rc;
-    if (int rc = band_attn_fwd_impl(compressed_call(L, kv, C, Q, Ocmp, S, n1, ws + W.band, W.band_bytes, stream), compressed_band(t0, L->l, L->d), 0, nullptr))
+    if (int rc = band_attn_fwd_impl(BandFwdCall{"band_attn_fwd", sliding_call(L, kv, C, Q, Owin, S, S_kv, ws + W.band, W.band_bytes, stream), sliding_band(t0, L->w)}))
+        return rc;
+    if (int rc = band_attn_fwd_impl(BandFwdCall{"band_attn_fwd", compressed_call(L, kv, C, Q, Ocmp, S, n1, ws + W.band, W.band_bytes, stream),
+                                                compressed_band(t0, L->l, L->d)}))
         return rc;
     return nsa_gate_combine(L, Q, Ocmp, Osel, Owin, O_mix, gates_out, (int64_t)B * S * G, stream);
 }
@@ -460,21 +462,27 @@ static int layer_decode_tail(const LayerDecode &D, const CacheStrides &C, Decode
         F.ns[2] = F.ns[0] = BP->w.nsplit;
         F.part[2] = BP->w.part;
         F.part[0] = BP->c.part;
-    } else if (D.pg) {  // the paged call: one paged launch each -- 1024-row pages of K_win / V_win, 64-row pages of K_cmp / V_cmp -- combined by the branch itself
-        const BandBranches b = band_branches(D, C, stream);
-        const BandPageTable pt{D.pg->table, D.pg->stride, D.pg->n_pages, 0};
-        if (int rc = band_attn_fwd_paged_impl(b.w, b.bw, pt, D.pg->max_pages, LAYER_PAGE_TOKENS, D.t_pos, D.te)) return rc;
-        if (int rc = band_attn_fwd_paged_impl(b.c, b.bc, pt, D.pg->max_pages, LAYER_PAGE_CMP, D.t_pos, D.te)) return rc;
-    } else if (D.t_pos) {  // the ragged call: one ragged launch each, combined by the branch itself (O final)
-        const BandBranches b = band_branches(D, C, stream);
-        if (int rc = band_attn_fwd_ragged_impl(b.w, b.bw, D.t_pos, D.te)) return rc;
-        if (int rc = band_attn_fwd_ragged_impl(b.c, b.bc, D.t_pos, D.te)) return rc;
     } else {
+        // a launch each, in the form the call carries.  Paged: 1024-row pages of K_win / V_win, 64-row pages of K_cmp / V_cmp; it and the ragged call
+        // combine inside the branch (O final); the scalar call leaves its split records to the finish kernel when that defers
         const BandBranches b = band_branches(D, C, stream);
-        if (int rc = band_attn_fwd_impl(b.w, b.bw, defer, &F.ns[2])) return rc;
-        F.part[2] = (const float *)b.w.ws;
-        if (int rc = band_attn_fwd_impl(b.c, b.bc, defer, &F.ns[0])) return rc;
-        F.part[0] = (const float *)b.c.ws;
+        const BandPositions pos{D.t_pos, D.te};
+        BandPages pw{}, pc{};
+        if (D.pg) {
+            pw = BandPages{BandPageTable{D.pg->table, D.pg->stride, D.pg->n_pages, 0}, D.pg->max_pages, LAYER_PAGE_TOKENS};
+            pc = BandPages{pw.table, D.pg->max_pages, LAYER_PAGE_CMP};
+        }
+        const char *who = D.pg ? "band_attn_fwd_paged" : D.t_pos ? "band_attn_fwd_ragged" : "band_attn_fwd";
+        BandFwdCall w{who, b.w, b.bw}, c{who, b.c, b.bc};
+        if (D.t_pos) w.pos = c.pos = &pos;
+        if (D.pg) w.pages = &pw, c.pages = &pc;
+        if (!D.t_pos) {
+            w.defer = c.defer = defer;
+            w.ns_used = &F.ns[2], c.ns_used = &F.ns[0];
+            F.part[2] = (const float *)b.w.ws, F.part[0] = (const float *)b.c.ws;
+        }
+        if (int rc = band_attn_fwd_impl(w)) return rc;
+        if (int rc = band_attn_fwd_impl(c)) return rc;
     }
     if (defer) {
         if (int rc = launch_decode_finish(F, dt, st)) return rc;

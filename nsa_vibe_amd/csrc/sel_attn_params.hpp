@@ -107,6 +107,26 @@ struct BandPageTable {
 size_t band_attn_workspace(int B, int S, int G, int h, int Dk, int Dv, int dtype, int *nsplit_out);
 // the form of a band forward of a supported shape (band_attn_mfma.hip): column tiles and tokens per wave, waves a row's keys are split over
 void band_plan(int B, int S, int G, int h, int D, int *nt, int *tpw, int *nsplit);
+// the launch of a filled block of a supported shape (band_attn_mfma.hip; host only): what band_plan gives and what the block carries, once for
+// every launcher of the family.  Each launcher keeps what is its own: LDS bytes, the kernel pick, the launch lines
+struct BandLaunch {
+    int nt;         // column tiles per wave
+    bool split;     // the keys of a row over P.nsplit waves, their records in P.part
+    int64_t waves;  // (token group, split) units
+    unsigned grid;  // workgroups of four waves, under 2^31
+};
+int band_launch_plan(BandAttnParams &P, bool need_ws, const char *who, BandLaunch *L);
+// the combine pass behind a split launch (sel_attn_combine_kernel, instantiated by each launcher's translation unit): the records of P into O / lse
+inline SelAttnParams band_combine_params(const BandAttnParams &P) {
+    SelAttnParams C{};
+    C.O = P.O;
+    C.lse = P.lse;
+    C.R = (int64_t)P.B * P.G * P.S;
+    C.h = P.h;
+    C.part = P.part;
+    C.nsplit = P.nsplit;
+    return C;
+}
 // FP8 K/V of the ragged and the paged band forward (nsa_band_attn_fwd_ragged_fp8 / _paged_fp8; band_attn_fwd_fp8.hpp): P.K / P.V are OCP e4m3
 // bytes with rows of D contiguous bytes (their strides count bytes), and key row r of plane (b, g) -- paged: (page, g) -- is
 // K8[r, :] * k_scale[b kzb + g kzg + r].  An argument block of its own behind BandAttnParams, like BandPageTable
