@@ -396,6 +396,38 @@ NSA_API int nsa_layer_decode_paged(const nsa_layer_desc *L, const nsa_paged_kv_d
 NSA_API int nsa_layer_decode_paged_plan(const nsa_layer_desc *L, int B, int S, int max_pages, int t_max, int S_sel, int *launches /* host */,
                                 int *route /* host */);
 
+/* nsa_layer_decode_paged with FP8 (OCP e4m3) mirrors of the six ATTENDED pools: the call appends and pools in bf16 exactly as
+ * nsa_layer_decode_paged does (the eight bf16 pools, the ranges and the gates' inputs are those of that call bit for bit), then ONE more
+ * launch -- layer_kv_mirror_fp8_paged_kernel, behind the pooling -- quantises the rows this call wrote into the mirrors, and the three
+ * attention branches read the mirrors: nsa_sel_decode_paged_fp8's kernel for the selected branch, nsa_band_attn_fwd_paged_fp8's for the
+ * sliding (pages of 1024 rows) and the compressed one (pages of 64).  The scorer keeps reading bf16 K_cmp: the selection is unchanged.
+ *   nsa_paged_kv_fp8_desc   K_sel8, V_sel8, K_win8, V_win8 e4m3 [n_pages, G, 1024, D] and K_cmp8, V_cmp8 [n_pages, G, 64, D], contiguous and
+ *                 16-byte aligned, each with its scale pool fp32 [n_pages, G, 1024 | 64], contiguous and 4-byte aligned.  Addressed by the
+ *                 page ids of pkv->block_table like the bf16 pools.  K_raw / V_raw have no mirror.
+ * The mirror writer.  For every live sequence (t_live[b] >= 0) token rows t_live[b] .. t_live[b] + S - 1 of the four token mirrors and
+ * compressed rows [n_cmp(t_live[b]), n_cmp(t_live[b] + S)) of the two compressed ones are written, byte for byte what
+ * nsa_paged_kv_quantize_fp8[_rows] gives for the same bf16 row (scale = amax / 448, 1 for a zero row, NaN scale and NaN bytes for a row
+ * with a NaN or an infinity); no other row of a mirror is touched.  Every OTHER writer of the bf16 pools must keep the mirrors a pure
+ * function of them (NSA_PagedKV does: nsa_vibe_amd/kv_cache.py).  It forms addresses only from table entries it has tested itself.
+ * Launches: those of nsa_layer_decode_paged + 1.  workspace: nsa_layer_decode_paged's.  The bf16 attended pools REMAIN (the fused QKV
+ * epilogue writes them): the mirrors halve the bytes the branches READ, not the pool capacity.
+ * DECLINES with NSA_ERR_INVALID and a message naming the limit, no fallback: wherever nsa_layer_decode_paged does; a layer dtype other
+ * than bf16 (the FP8 readers take bf16 queries only); te beyond unsplit forms 0 / 1 whatever DECODE_LONG says (the long-row form is not
+ * built for FP8); a null descriptor, mirror or scale pointer; a mirror not 16-byte or a scale pool not 4-byte aligned. */
+typedef struct nsa_paged_kv_fp8_desc {
+    void *K_sel8, *V_sel8, *K_win8, *V_win8;                     /* e4m3 [n_pages, G, 1024, D] */
+    void *K_cmp8, *V_cmp8;                                       /* e4m3 [n_pages, G, 64, D] */
+    float *K_sel_scale, *V_sel_scale, *K_win_scale, *V_win_scale; /* [n_pages, G, 1024] */
+    float *K_cmp_scale, *V_cmp_scale;                             /* [n_pages, G, 64] */
+} nsa_paged_kv_fp8_desc;
+NSA_API size_t nsa_layer_decode_paged_fp8_workspace(const nsa_layer_desc *L, int B, int S, int max_pages);
+NSA_API int nsa_layer_decode_paged_fp8(const nsa_layer_desc *L, const nsa_paged_kv_desc *pkv, const nsa_paged_kv_fp8_desc *fp8, const void *x,
+                               void *y, const int32_t *t_pos /* device [B] */, int t_max /* host */, int S, const int32_t *csc_ptr,
+                               const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out, float *gates_out,
+                               void *workspace, size_t workspace_bytes, void *stream);
+NSA_API int nsa_layer_decode_paged_fp8_plan(const nsa_layer_desc *L, int B, int S, int max_pages, int t_max, int S_sel,
+                                    int *launches /* host */, int *route /* host */);
+
 /* Copies between a contiguous cache and the pages of a paged one, and between pages: how a prefilled sequence ENTERS the pools (admission),
  * leaves them, and how a sequence gets a private copy of a page it shares.  Plain streaming copies, ONE launch per call, 16-byte loads and
  * stores.  G, Dk, Dv, dtype: the geometry of the pools and the cache (the descriptors hold pointers and extents only); bf16 / f16,

@@ -45,7 +45,14 @@ class NsaPagedKvDesc(C.Structure):
                [("table_stride", _i64)] + [(n, _i) for n in ("n_pages", "B", "max_pages")]
 
 
+class NsaPagedKvFp8Desc(C.Structure):
+    """struct nsa_paged_kv_fp8_desc (include/nsa_sel_hip.h): the six e4m3 mirrors, then their six fp32 scale pools"""
+    _fields_ = [(n, _vp) for n in ("K_sel8", "V_sel8", "K_win8", "V_win8", "K_cmp8", "V_cmp8", "K_sel_scale", "V_sel_scale", "K_win_scale", "V_win_scale",
+                                   "K_cmp_scale", "V_cmp_scale")]
+
+
 _pl, _pk, _pb, _pp = C.POINTER(NsaLayerDesc), C.POINTER(NsaKvDesc), C.POINTER(NsaBlockDesc), C.POINTER(NsaPagedKvDesc)
+_pp8 = C.POINTER(NsaPagedKvFp8Desc)
 
 # name -> (restype, argtypes); mirrors include/nsa_sel_hip.h one to one
 SIGNATURES = {
@@ -90,6 +97,9 @@ SIGNATURES = {
     "nsa_layer_decode_paged_workspace": (_sz, [_pl, _i, _i, _i]),
     "nsa_layer_decode_paged": (_i, [_pl, _pp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "nsa_layer_decode_paged_plan": (_i, [_pl, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "nsa_layer_decode_paged_fp8_workspace": (_sz, [_pl, _i, _i, _i]),
+    "nsa_layer_decode_paged_fp8": (_i, [_pl, _pp, _pp8, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "nsa_layer_decode_paged_fp8_plan": (_i, [_pl, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "nsa_paged_kv_store": (_i, [_pp, _pk] + [_i] * 8 + [_vp]),
     "nsa_paged_kv_load": (_i, [_pp, _pk] + [_i] * 8 + [_vp]),
     "nsa_paged_kv_copy_pages": (_i, [_pp, _vp] + [_i] * 5 + [_vp]),

@@ -4,14 +4,13 @@
 // A row that holds a NaN, a +inf or a -inf gets a NaN scale and an e4m3 NaN code (0x7F or 0xFF) in every byte, so the corruption reaches the
 // FP8 attention calls as it reaches the bf16 calls through a bf16 cache: NaN output rows from a V row; from a K row what those kernels make of
 // a NaN row sum (the clamp alone would turn the element into -448 under a finite scale taken from the row's other elements).
-// A row is D / 8 lanes of 16 bytes (8 lanes at D = 64, 16 at D = 128), so a wave takes 8 / 4 rows at once: one 16-byte load per lane, the
-// row's absmax by xor-shuffles inside the row's lanes (an unsigned maximum over the |x| bit patterns: inf and NaN order above every finite
-// value), eight divisions, four v_cvt_pk_fp8_f32 (the instruction does not saturate: 465 and beyond would become NaN, hence the clamp), one
-// 8-byte store per lane and one scale store per row.  Rows outside [t0, t1) are not touched.
+// A row is D / 8 lanes of 16 bytes (8 lanes at D = 64, 16 at D = 128), so a wave takes 8 / 4 rows at once; what the row's lanes do is
+// kv_quantize_fp8_row (kv_quantize_fp8_row.hpp, shared with the paged layer call's mirror writer).  Rows outside [t0, t1) are not touched.
 // Paged form: source and destination are pools [n_pages, G, page_rows, D] / [n_pages, G, page_rows] under ONE table row; token r lives in row
 // r & (page_rows - 1) of page table[r / page_rows] (nsa_paged_kv_quantize_fp8: page_rows = 1024, the selected branch's pages;
 // nsa_paged_kv_quantize_fp8_rows: any power of two in [32, 65536], the band branches' -- 64 for K_cmp / V_cmp).  The page id is tested against
 // [0, n_pages) before any address is formed from it and a row whose entry fails is skipped, as the paged copy kernels do (paged_kv_copy.hip).
+#include "kv_quantize_fp8_row.hpp"
 #include "nsa_common.hpp"
 #include "nsa_internal.hpp"
 #include "sel_attn_params.hpp"
@@ -49,37 +48,7 @@ __global__ __launch_bounds__(256) void kv_quantize_fp8_kernel(KvQuantParams P) {
         b = page;
         r &= ((int64_t)1 << P.page_shift) - 1;
     }
-    const u32x4 raw = *(const u32x4 *)(P.X + b * P.xsb + g * P.xsg + r * P.xss + 8 * sub);
-    float x[8];
-    // the row's absmax as the largest |x| bit pattern: the unsigned order of the patterns is the order of the values, with +inf (0x7f800000) and
-    // every NaN above all finite ones, so a non-finite element survives the reduction whatever fmaxf does with a NaN
-    uint32_t amax_bits = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const uint32_t lo = raw[i] << 16, hi = raw[i] & 0xffff0000u;
-        x[2 * i] = __uint_as_float(lo);
-        x[2 * i + 1] = __uint_as_float(hi);
-        amax_bits = max(amax_bits, max(lo & 0x7fffffffu, hi & 0x7fffffffu));
-    }
-#pragma unroll
-    for (int o = 1; o < LPR; o <<= 1) amax_bits = max(amax_bits, (uint32_t)__shfl_xor((int)amax_bits, o, 64));
-    // the row holds an inf or a NaN: NaN scale, NaN bytes.  Branch-free -- such a row runs the divisions like any other (its scale is inf or NaN
-    // here) and gets the seven NaN bits ORed into every byte: 0x7F or 0xFF, both NaN in e4m3
-    const uint32_t nan_bytes = amax_bits >= 0x7f800000u ? 0x7f7f7f7fu : 0u;
-    const float amax = __uint_as_float(amax_bits);
-    const float scale = amax_bits == 0 ? 1.0f : amax / 448.0f;
-    u32x2 out;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        float y[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) y[k] = fminf(fmaxf(x[4 * i + k] / scale, -448.0f), 448.0f);
-        int w = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0, false);
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], w, true);
-        out[i] = (uint32_t)w | nan_bytes;
-    }
-    *(u32x2 *)(P.Q8 + b * P.qsb + g * P.qsg + r * P.qss + 8 * sub) = out;
-    if (sub == 0) P.scale[b * P.zsb + g * P.zsg + r] = nan_bytes ? __uint_as_float(0x7fc00000u) : scale;
+    kv_quantize_fp8_row<D>(P.X + b * P.xsb + g * P.xsg + r * P.xss, P.Q8 + b * P.qsb + g * P.qsg + r * P.qss, P.scale + b * P.zsb + g * P.zsg + r, sub);
 }
 
 static int kv_quantize_launch(const char *who, const KvQuantParams &P, int D, void *stream) {

@@ -45,6 +45,19 @@ struct RopePagedParams : RopeAppendParams {
 struct CmpPoolPagedParams : CmpPoolParams {
     LayerPageTable pg;
 };
+// the FP8 mirror writer of the paged call (layer_kv_mirror_fp8.hip, nsa_layer_decode_paged_fp8): behind the append and the pooling it
+// quantises what they wrote for every live sequence -- token rows t_live[b] .. t_live[b] + S - 1 of the four attended token pools and the
+// compressed rows [n_cmp(t_live[b]), n_cmp(t_live[b] + S)) -- into e4m3 pools of the same shape with one fp32 scale per row.
+// Pairs: 0 = K_sel / V_sel, 1 = K_win / V_win (pages of 1024 rows), 2 = K_cmp / V_cmp (pages of 64); every pool contiguous, D = Dk = Dv.
+struct KvMirrorFp8PagedParams {
+    const void *src[3][2];    // bf16 [n_pages, G, 1024 | 64, D]
+    unsigned char *q8[3][2];  // e4m3, the same shape
+    float *scale[3][2];       // fp32 [n_pages, G, 1024 | 64]
+    const int32_t *t_pos;     // t_live
+    LayerPageTable pg;
+    int B, S, G, te;
+};
+int launch_kv_mirror_fp8_paged(const KvMirrorFp8PagedParams &P, int D, hipStream_t st);
 // the pre-pass: one wave per sequence writes its verdict t_live[b] = t_pos[b] where the sequence is live -- 0 <= t_pos[b],
 // t_pos[b] + S - 1 <= te, every table entry j = 0 .. (t_pos[b] + S - 1) >> 10 inside [0, n_pages) -- and -1 otherwise
 struct PagedLiveParams {

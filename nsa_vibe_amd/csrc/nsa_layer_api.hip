@@ -285,6 +285,8 @@ struct LayerDecode {
     // paged call (nsa_layer_decode_paged): the block table; kv then names the POOLS with one page as its extent (S_max = 1024, n_cmp_max = 64,
     // so that CacheStrides gives the page strides), t_pos is the pre-pass's t_live and te = min(t_max, max_pages 1024 - 1)
     const LayerPageTable *pg;
+    // paged call with FP8 mirrors (nsa_layer_decode_paged_fp8): the branches read these instead of the attended bf16 pools; null: bf16
+    const nsa_paged_kv_fp8_desc *m8;
     int tokens() const { return t_pos ? te + 1 : t0 + S; }  // tokens the caches hold after the call (of the largest sequence)
 };
 constexpr int LAYER_ROWS_MAX_S = 16;
@@ -472,10 +474,20 @@ static int layer_decode_tail(const LayerDecode &D, const CacheStrides &C, Decode
             pw = BandPages{BandPageTable{D.pg->table, D.pg->stride, D.pg->n_pages, 0}, D.pg->max_pages, LAYER_PAGE_TOKENS};
             pc = BandPages{pw.table, D.pg->max_pages, LAYER_PAGE_CMP};
         }
-        const char *who = D.pg ? "band_attn_fwd_paged" : D.t_pos ? "band_attn_fwd_ragged" : "band_attn_fwd";
+        const char *who = D.m8 ? "band_attn_fwd_paged_fp8" : D.pg ? "band_attn_fwd_paged" : D.t_pos ? "band_attn_fwd_ragged" : "band_attn_fwd";
         BandFwdCall w{who, b.w, b.bw}, c{who, b.c, b.bc};
         if (D.t_pos) w.pos = c.pos = &pos;
         if (D.pg) w.pages = &pw, c.pages = &pc;
+        // FP8 mirrors: the e4m3 pools have the bf16 pools' shape, so their strides in BYTES are the element strides C holds; the scale pools are
+        // [n_pages, G, page rows]
+        BandFp8Scales zw{}, zc{};
+        if (D.m8) {
+            const int64_t G = L->G;
+            zw = BandFp8Scales{D.m8->K_win_scale, D.m8->V_win_scale, G * LAYER_PAGE_TOKENS, LAYER_PAGE_TOKENS, G * LAYER_PAGE_TOKENS, LAYER_PAGE_TOKENS};
+            zc = BandFp8Scales{D.m8->K_cmp_scale, D.m8->V_cmp_scale, G * LAYER_PAGE_CMP, LAYER_PAGE_CMP, G * LAYER_PAGE_CMP, LAYER_PAGE_CMP};
+            w.c.K = D.m8->K_win8, w.c.V = D.m8->V_win8, w.fp8 = &zw;
+            c.c.K = D.m8->K_cmp8, c.c.V = D.m8->V_cmp8, c.fp8 = &zc;
+        }
         if (!D.t_pos) {
             w.defer = c.defer = defer;
             w.ns_used = &F.ns[2], c.ns_used = &F.ns[0];
@@ -713,7 +725,10 @@ static int paged_ws_tokens(int max_pages) { return (int)std::min<int64_t>((int64
 
 // What the call and its plan share, from the shape, the host bound and the switches alone (aligned pools assumed; neither the positions nor
 // the table are read on the host).  Answers as layer_decode_ragged_route does (declined: there is no fallback).
-static int layer_decode_paged_route(const char *who, const nsa_layer_desc *L, int B, int S, int max_pages, int t_max, int S_sel, PositionsPlan *p) {
+// fp8: the call with FP8 mirrors (nsa_layer_decode_paged_fp8) -- bf16 only, the selected branch planned on its FP8 axis (forms 0 / 1 whatever
+// DECODE_LONG says), and one more launch: the mirror writer behind the pooling.
+static int layer_decode_paged_route(const char *who, const nsa_layer_desc *L, int B, int S, int max_pages, int t_max, int S_sel, PositionsPlan *p,
+                                    bool fp8 = false) {
     *p = PositionsPlan{};
     if (int rc = check_layer(L, who)) return rc;
     if (int rc = check_rows_count(who, S)) return rc;
@@ -722,6 +737,7 @@ static int layer_decode_paged_route(const char *who, const nsa_layer_desc *L, in
     const int cap = max_pages * LAYER_PAGE_TOKENS;
     if (int rc = check_bound(who, L, S, cap, t_max, S_sel, p)) return rc;
     p->why = !dtype_16bit(L->dtype) ? "bf16 / f16 only (no kernel reads or writes pools of pages in fp32)"
+             : fp8 && L->dtype != NSA_DT_BF16 ? "FP8 K/V mirrors take a bf16 layer only (the FP8 readers are built for bf16 queries; f16 is declined)"
              : !default_decode_geometry(L)
                  ? "Dk = Dv in {64, 128} and the default block geometry only (l = 32, d = 16, l' = 64: pages of 1024 tokens and 64 compressed rows)"
                  : L->w < 1 ? "the sliding window must hold at least one key (w >= 1)" : nullptr;
@@ -730,13 +746,14 @@ static int layer_decode_paged_route(const char *who, const nsa_layer_desc *L, in
     const CacheStrides C(L, &kv);
     SelDecodeCall sc = sel_decode_call(L, &kv, C, S, 0, p->n1, S_sel);
     sc.S_kv = cap;
+    if (fp8) sc.kv_dtype = NSA_DT_FP8_E4M3;
     if (!decode_paged_shape_plan(sc, p->te, nullptr, nullptr, &p->why)) return NSA_OK;
     p->why = nullptr;
     int ns = 1;
     band_attn_workspace(B, S, L->G, L->h, L->Dk, L->Dv, L->dtype, &ns);
     // the verdicts, projection + RoPE + append, pooling (always), the selected branch's one launch, the sliding and the compressed branch (each
     // one paged launch, with its combine behind it in split form), finish (or gate + mix), output projection
-    p->launches = 4 + 2 * (ns > 1 ? 2 : 1) + 2;
+    p->launches = 4 + 2 * (ns > 1 ? 2 : 1) + 2 + (fp8 ? 1 : 0);
     return NSA_OK;
 }
 
@@ -751,17 +768,18 @@ int nsa_layer_decode_paged_plan(const nsa_layer_desc *L, int B, int S, int max_p
     return plan_answer(layer_decode_paged_route("layer_decode_paged_plan", L, B, S, max_pages, t_max, S_sel, &p), p, launches, route);
 }
 
-int nsa_layer_decode_paged(const nsa_layer_desc *L, const nsa_paged_kv_desc *pkv, const void *x, void *y, const int32_t *t_pos, int t_max, int S,
-                           const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out, float *gates_out,
-                           void *workspace, size_t workspace_bytes, void *stream) {
-    const char *who = "layer_decode_paged";
+// The paged call and its FP8 form (m8: the mirrors, null for the bf16 call -- whose checks, launches and messages are those below without the
+// lines that name m8).
+static int layer_decode_paged_impl(const char *who, const nsa_layer_desc *L, const nsa_paged_kv_desc *pkv, const nsa_paged_kv_fp8_desc *m8, const void *x, void *y,
+                                   const int32_t *t_pos, int t_max, int S, const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel,
+                                   int32_t *ranges_out, float *gates_out, void *workspace, size_t workspace_bytes, void *stream) {
     if (int rc = check_layer(L, who)) return rc;
     NSA_CHECK_ARG(pkv && pkv->K_sel && pkv->V_sel && pkv->K_win && pkv->V_win && pkv->K_raw && pkv->V_raw && pkv->K_cmp && pkv->V_cmp, "%s: null pool pointer", who);
     NSA_CHECK_ARG(pkv->B >= 1 && pkv->n_pages >= 1, "%s: bad pool sizes (B = %d, n_pages = %d)", who, pkv->B, pkv->n_pages);
     if (int rc = check_io(who, L, x, y, t_pos)) return rc;
     NSA_CHECK_ARG(pkv->block_table, "%s: null block table", who);
     PositionsPlan p;  // the largest sequence the launches are planned for: te + 1 tokens after the call, n1 compressed ones (LayerDecode)
-    if (int rc = layer_decode_paged_route(who, L, pkv->B, S, pkv->max_pages, t_max, S_sel, &p)) return rc;
+    if (int rc = layer_decode_paged_route(who, L, pkv->B, S, pkv->max_pages, t_max, S_sel, &p, m8 != nullptr)) return rc;
     NSA_CHECK_ARG((uintptr_t)pkv->block_table % 4 == 0 && pkv->table_stride >= pkv->max_pages,
                   "%s: the block table must be 4-byte aligned with a row stride of at least max_pages = %d (got %lld)", who, pkv->max_pages,
                   (long long)pkv->table_stride);
@@ -769,6 +787,15 @@ int nsa_layer_decode_paged(const nsa_layer_desc *L, const nsa_paged_kv_desc *pkv
     NSA_CHECK_ARG(((uintptr_t)pkv->K_sel | (uintptr_t)pkv->V_sel | (uintptr_t)pkv->K_win | (uintptr_t)pkv->V_win | (uintptr_t)pkv->K_raw | (uintptr_t)pkv->V_raw |
                    (uintptr_t)pkv->K_cmp | (uintptr_t)pkv->V_cmp) % 16 == 0,
                   "%s: the eight pools must be 16-byte aligned", who);
+    if (m8) {
+        NSA_CHECK_ARG(m8->K_sel8 && m8->V_sel8 && m8->K_win8 && m8->V_win8 && m8->K_cmp8 && m8->V_cmp8, "%s: null FP8 mirror pool pointer", who);
+        NSA_CHECK_ARG(m8->K_sel_scale && m8->V_sel_scale && m8->K_win_scale && m8->V_win_scale && m8->K_cmp_scale && m8->V_cmp_scale,
+                      "%s: null scale pool pointer (every FP8 mirror needs its fp32 scale pool)", who);
+        NSA_CHECK_ARG(((uintptr_t)m8->K_sel8 | (uintptr_t)m8->V_sel8 | (uintptr_t)m8->K_win8 | (uintptr_t)m8->V_win8 | (uintptr_t)m8->K_cmp8 | (uintptr_t)m8->V_cmp8) % 16 == 0 &&
+                          ((uintptr_t)m8->K_sel_scale | (uintptr_t)m8->V_sel_scale | (uintptr_t)m8->K_win_scale | (uintptr_t)m8->V_win_scale |
+                           (uintptr_t)m8->K_cmp_scale | (uintptr_t)m8->V_cmp_scale) % 4 == 0,
+                      "%s: the six FP8 mirror pools must be 16-byte aligned and their scale pools 4-byte aligned", who);
+    }
     const int B = pkv->B, cap = pkv->max_pages * LAYER_PAGE_TOKENS;
     const nsa_kv_desc kv = page_extent_kv(pkv);
     const CacheStrides C(L, &kv);
@@ -777,7 +804,8 @@ int nsa_layer_decode_paged(const nsa_layer_desc *L, const nsa_paged_kv_desc *pkv
     int32_t *t_live = (int32_t *)((unsigned char *)workspace + W.total);
     const LayerPageTable pg{pkv->block_table, pkv->table_stride, pkv->n_pages, pkv->max_pages};
     // every launch behind the pre-pass takes t_live as its position array: one verdict per sequence for the writers and the readers
-    const LayerDecode D = layer_decode_positions(L, &kv, W, workspace, S, p, t_live, &pg);
+    LayerDecode D = layer_decode_positions(L, &kv, W, workspace, S, p, t_live, &pg);
+    D.m8 = m8;
     hipStream_t st = (hipStream_t)stream;
     // 0. the verdicts: t_live[b] = t_pos[b] where sequence b is live (positions, and every table entry it needs inside [0, n_pages)), else -1
     if (int rc = launch_paged_live(PagedLiveParams{t_pos, t_live, pg, B, S, p.te}, st)) return rc;
@@ -796,11 +824,52 @@ int nsa_layer_decode_paged(const nsa_layer_desc *L, const nsa_paged_kv_desc *pkv
     P.t_pos = t_live; P.t_max = p.te; P.S = S; P.G = L->G;
     P.pg = pg;
     if (int rc = launch_cmp_pool_paged(P, L->dtype, st)) return rc;
-    // 3. selected branch: the paged rows form (one launch; zero O and ranges rows for a sequence that is not live; S_kv stays t0 + S)
-    const SelDecodeCall c = layer_sel_call(D, C, csc_ptr, csc_rows, csc_vals, S_sel, ranges_out);
+    // 2b. FP8 mirrors: the rows launches 1 and 2 wrote, quantised into the six mirrors (one launch, behind them on the stream)
+    if (m8) {
+        const KvMirrorFp8PagedParams M{{{pkv->K_sel, pkv->V_sel}, {pkv->K_win, pkv->V_win}, {pkv->K_cmp, pkv->V_cmp}},
+                                       {{(unsigned char *)m8->K_sel8, (unsigned char *)m8->V_sel8},
+                                        {(unsigned char *)m8->K_win8, (unsigned char *)m8->V_win8},
+                                        {(unsigned char *)m8->K_cmp8, (unsigned char *)m8->V_cmp8}},
+                                       {{m8->K_sel_scale, m8->V_sel_scale}, {m8->K_win_scale, m8->V_win_scale}, {m8->K_cmp_scale, m8->V_cmp_scale}},
+                                       t_live, pg, B, S, L->G, p.te};
+        if (int rc = launch_kv_mirror_fp8_paged(M, L->Dk, st)) return rc;
+    }
+    // 3. selected branch: the paged rows form (one launch; zero O and ranges rows for a sequence that is not live; S_kv stays t0 + S); with
+    // mirrors its FP8 axis -- the scorer still reads bf16 K_cmp, K / V are the e4m3 pools (strides in bytes: the element strides' numbers)
+    SelDecodeCall c = layer_sel_call(D, C, csc_ptr, csc_rows, csc_vals, S_sel, ranges_out);
+    if (m8) {
+        c.kv_dtype = NSA_DT_FP8_E4M3;
+        c.K = m8->K_sel8; c.V = m8->V_sel8; c.k_scale = m8->K_sel_scale; c.v_scale = m8->V_sel_scale;
+        c.kzb = c.vzb = (int64_t)L->G * LAYER_PAGE_TOKENS; c.kzg = c.vzg = LAYER_PAGE_TOKENS;
+    }
     if (int rc = sel_decode_paged_impl(c, DecPageTable{pg.table, pg.stride, pg.n_pages}, pg.max_pages, LAYER_PAGE_TOKENS, t_live, p.te, stream)) return rc;
     // 4. the sliding and the compressed branch, one paged launch each with its own combine, 5. finish (or the gate kernel), 6. output projection
     return layer_decode_rows_tail(D, C, gates_out, y, stream);
+}
+
+int nsa_layer_decode_paged(const nsa_layer_desc *L, const nsa_paged_kv_desc *pkv, const void *x, void *y, const int32_t *t_pos, int t_max, int S,
+                           const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out, float *gates_out,
+                           void *workspace, size_t workspace_bytes, void *stream) {
+    return layer_decode_paged_impl("layer_decode_paged", L, pkv, nullptr, x, y, t_pos, t_max, S, csc_ptr, csc_rows, csc_vals, S_sel, ranges_out, gates_out, workspace,
+                                   workspace_bytes, stream);
+}
+
+// ---- the paged call with FP8 mirrors of the attended pools: the same body, the mirror writer behind the pooling, the branches on their FP8 kernels
+size_t nsa_layer_decode_paged_fp8_workspace(const nsa_layer_desc *L, int B, int S, int max_pages) { return nsa_layer_decode_paged_workspace(L, B, S, max_pages); }
+
+int nsa_layer_decode_paged_fp8_plan(const nsa_layer_desc *L, int B, int S, int max_pages, int t_max, int S_sel, int *launches, int *route) {
+    NSA_CHECK_ARG(launches && route, "layer_decode_paged_fp8_plan: null pointer");
+    PositionsPlan p;
+    return plan_answer(layer_decode_paged_route("layer_decode_paged_fp8_plan", L, B, S, max_pages, t_max, S_sel, &p, true), p, launches, route);
+}
+
+int nsa_layer_decode_paged_fp8(const nsa_layer_desc *L, const nsa_paged_kv_desc *pkv, const nsa_paged_kv_fp8_desc *fp8, const void *x, void *y,
+                               const int32_t *t_pos, int t_max, int S, const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel,
+                               int32_t *ranges_out, float *gates_out, void *workspace, size_t workspace_bytes, void *stream) {
+    const char *who = "layer_decode_paged_fp8";
+    NSA_CHECK_ARG(fp8, "%s: null FP8 mirror descriptor", who);
+    return layer_decode_paged_impl(who, L, pkv, fp8, x, y, t_pos, t_max, S, csc_ptr, csc_rows, csc_vals, S_sel, ranges_out, gates_out, workspace, workspace_bytes,
+                                   stream);
 }
 
 // block workspace: xn | h | hn | u [B, mlp_hidden] | layer decode workspace

@@ -245,6 +245,8 @@ class NSA_KV:
 PAGE_TOKENS, PAGE_CMP = 1024, 64  # a page: 1024 tokens of the six token caches, 64 rows of K_cmp / V_cmp (d = 16)
 CLOSE_LAG = 16  # d: compressed row 64 j + 63, the last of page j, is pooled from raw rows up to 1024 (j + 1) + 15
 _POOLS = ("_K_sel", "_V_sel", "_K_win", "_V_win", "_K_raw", "_V_raw", "_K_cmp", "_V_cmp")
+_MIRRORED = ("_K_sel", "_V_sel", "_K_win", "_V_win", "_K_cmp", "_V_cmp")  # the attended pools: what kv_dtype = float8_e4m3fn mirrors
+FP8 = torch.float8_e4m3fn
 
 
 class NSA_PagedKV:
@@ -259,10 +261,15 @@ class NSA_PagedKV:
     inside [1024 (j + 1), 1024 (j + 1) + 16) would both write it.  Every page an append can still write is private to its slot:
     own_tail() replaces a shared one by a copy (one nsa_paged_kv_copy_pages launch; torch indexing on CPU tensors), fork(), truncate() and
     load_sequence() call it.  free() returns a page to the free list when its count reaches zero.
-    The default block geometry only (l = 32, d = 16, l_sel = 64): the page sizes follow from it."""
+    The default block geometry only (l = 32, d = 16, l_sel = 64): the page sizes follow from it.
+    FP8 mirrors.  kv_dtype = torch.float8_e4m3fn (bf16 pools on a HIP device) adds, for each of the six ATTENDED pools (not K_raw / V_raw), an
+    e4m3 pool of the same shape (<name>8) and an fp32 scale pool [n_pages, G, rows] (<name>_scale): what NSAAttention.decode_paged then reads
+    (nsa_layer_decode_paged_fp8, which also writes the rows it appends).  The bf16 pools remain -- the append writes them -- so the mirrors
+    halve the bytes the branches read, not the capacity.  A mirror row is a pure function of its bf16 row: every writer here that stores bf16
+    rows (load_sequence, the page copies of fork / own_tail / truncate) requantises them with the public quantiser behind its launch."""
 
     def __init__(self, n_pages: int, B: int, max_pages: int, G: int, d_k: int, d_v: int, l: int, d: int, l_sel: int, n_sel: int, w: int,
-                 device, dtype):
+                 device, dtype, kv_dtype=None):
         if (l, d, l_sel) != (32, 16, 64):
             raise ValueError(f"NSA_PagedKV: pages of {PAGE_TOKENS} tokens / {PAGE_CMP} compressed rows need the default block geometry "
                              f"(l = 32, d = 16, l_sel = 64), got ({l}, {d}, {l_sel})")
@@ -275,6 +282,15 @@ class NSA_PagedKV:
         self._K_win, self._V_win = mk(PAGE_TOKENS, d_k), mk(PAGE_TOKENS, d_v)
         self._K_raw, self._V_raw = mk(PAGE_TOKENS, d_k), mk(PAGE_TOKENS, d_v)
         self._K_cmp, self._V_cmp = mk(PAGE_CMP, d_k), mk(PAGE_CMP, d_v)
+        self.kv_dtype = kv_dtype
+        if kv_dtype is not None:
+            if kv_dtype != FP8 or dtype != torch.bfloat16 or self._K_sel.device.type != "cuda":
+                raise ValueError(f"NSA_PagedKV: kv_dtype = {kv_dtype} with {dtype} pools on {self._K_sel.device} -- the only mirror format is "
+                                 "torch.float8_e4m3fn, over bf16 pools on a HIP device")
+            for name in _MIRRORED:
+                pool = getattr(self, name)
+                setattr(self, name + "8", torch.zeros(pool.shape, device=device, dtype=FP8))
+                setattr(self, name + "_scale", torch.ones(pool.shape[:3], device=device, dtype=torch.float32))
         self.block_table = torch.full((B, max_pages), -1, dtype=torch.int32, device=device)
         self.pages: List[List[int]] = [[] for _ in range(B)]  # host mirror of the table rows
         self._free: List[int] = list(range(n_pages - 1, -1, -1))  # (a stack: page 0 goes out first)
@@ -356,8 +372,19 @@ class NSA_PagedKV:
         t & 1023 < 16 (t >= 1024)"""
         return [j for j in range(max(0, (t >> 10) - 1), min(len(self.pages[b]), (t >> 10) + 1)) if not self.page_closed(j, t)]
 
+    def _requantize(self, table_row: torch.Tensor, t0: int, t: int, n0: int, n: int) -> None:
+        """FP8 mirrors: token rows [t0, t) and compressed rows [n0, n) under the table row `table_row` (device int32), requantised from the
+        bf16 pools by the public quantiser (six launches, behind the copy that wrote the bf16 rows on the same stream)"""
+        from .selection_attention import quantize_kv_fp8_paged
+
+        for name in _MIRRORED:
+            lo, hi = (n0, n) if name in ("_K_cmp", "_V_cmp") else (t0, t)
+            if hi > lo:
+                quantize_kv_fp8_paged(getattr(self, name), table_row, lo, hi, getattr(self, name + "8"), getattr(self, name + "_scale"))
+
     def _copy_pages(self, jobs: List[tuple]) -> None:
-        """jobs of (src page, dst page, token rows, compressed rows), all in one nsa_paged_kv_copy_pages launch (torch indexing on CPU)"""
+        """jobs of (src page, dst page, token rows, compressed rows), all in one nsa_paged_kv_copy_pages launch (torch indexing on CPU);
+        with FP8 mirrors the copied rows of every dst page are requantised (a page id is a table row of one entry)"""
         jobs = [jb for jb in jobs if jb[2] > 0 or jb[3] > 0]
         if not jobs:
             return
@@ -369,6 +396,10 @@ class NSA_PagedKV:
                 dj = torch.tensor(jobs, dtype=torch.int32).to(dev)
                 _lib.check(_lib.lib().nsa_paged_kv_copy_pages(ctypes.byref(self.native_desc()), dj.data_ptr(), len(jobs), self.G, self.d_k, self.d_v,
                                                               self._dtype_code(), _stream(dev)), "nsa_paged_kv_copy_pages")
+                if self.kv_dtype is not None:
+                    dst = torch.tensor([jb[1] for jb in jobs], dtype=torch.int32).to(dev)
+                    for i, (_, _, n_tok, n_cmp) in enumerate(jobs):
+                        self._requantize(dst[i:i + 1], 0, n_tok, 0, n_cmp)
             return
         for src, dst, n_tok, n_cmp in jobs:
             for name in _POOLS:
@@ -467,6 +498,8 @@ class NSA_PagedKV:
             with torch.cuda.device(dev):
                 _lib.check(fn(ctypes.byref(self.native_desc()), ctypes.byref(kv1.native_desc()), 0, b, t0, t, self.G, self.d_k, self.d_v, self._dtype_code(),
                               _stream(dev)), "nsa_paged_kv_store" if to_pages else "nsa_paged_kv_load")
+                if to_pages and self.kv_dtype is not None:
+                    self._requantize(self.block_table[b], t0, t, n_cmp_at(t0, self.l, self.d), n_cmp_at(t, self.l, self.d))
             return
         for name in _POOLS:
             rows, lo, hi = (PAGE_CMP, n_cmp_at(t0, self.l, self.d), n_cmp_at(t, self.l, self.d)) if name in ("_K_cmp", "_V_cmp") else (PAGE_TOKENS, t0, t)
@@ -530,4 +563,14 @@ class NSA_PagedKV:
                 setattr(d, name[1:], getattr(self, name).data_ptr())
             d.block_table, d.table_stride = self.block_table.data_ptr(), self.block_table.stride(0)
             d.n_pages, d.B, d.max_pages = self.n_pages, self.B, self.max_pages
+        return d
+
+    def native_fp8_desc(self):
+        """struct nsa_paged_kv_fp8_desc of the mirrors and their scale pools (kv_dtype = float8_e4m3fn), built once"""
+        d = self._native.get("fp8_desc")
+        if d is None:
+            d = self._native["fp8_desc"] = _lib.NsaPagedKvFp8Desc()
+            for name in _MIRRORED:
+                setattr(d, name[1:] + "8", getattr(self, name + "8").data_ptr())
+                setattr(d, name[1:] + "_scale", getattr(self, name + "_scale").data_ptr())
         return d

@@ -681,15 +681,16 @@ class NSAAttention(nn.Module):
             raise RuntimeError(f"NSAAttention.{who} is inference only (no backward); run it under torch.no_grad()")
         return x if x.is_contiguous() else x.contiguous()
 
-    def _rows_call(self, who: str, x: torch.Tensor, kv, meta, extent: int, head) -> torch.Tensor:
+    def _rows_call(self, who: str, x: torch.Tensor, kv, meta, extent: int, head, pre=()) -> torch.Tensor:
         """the closing native call nsa_layer_<who> of x [B,S,dim] (`extent`: the last argument of its workspace query, `head`: what it
-        takes between y and the block map) -> y [B,S,dim]; ranges [B,S,G,n,2] and gates [B,S,G,3] go to the monitors"""
+        takes between y and the block map, `pre`: between the cache descriptor and x) -> y [B,S,dim]; ranges [B,S,G,n,2] and gates
+        [B,S,G,3] go to the monitors"""
         B, S, _ = x.shape
         G = self.n_kv_groups
         desc, _ = self._layer_desc()
         y = torch.empty((B, S, self.dim), dtype=x.dtype, device=x.device)
         ranges, gates = _one_call("nsa_layer_" + who, "layer_" + who, desc, kv, meta, x.device, (B, S, extent),
-                                  (x.data_ptr(), y.data_ptr(), *head), (), (B, S, G, self.n_sel, 2), (B, S, G, 3))
+                                  (*pre, x.data_ptr(), y.data_ptr(), *head), (), (B, S, G, self.n_sel, 2), (B, S, G, 3))
         self._monitors(ranges, gates)
         return y
 
@@ -804,17 +805,21 @@ class NSAAttention(nn.Module):
         return self._rows_call("decode_ragged", x, kv, kv.meta, cap, (t_pos.data_ptr(), t_max, S)), kv
 
     # ---- ragged batch over PAGED caches: the eight caches in pools of pages behind a device block table ------------------------------------
-    def new_paged_kv(self, n_pages: int, B: int, max_pages: int, device, dtype) -> NSA_PagedKV:
-        """pools of n_pages pages for B slots of up to max_pages pages (max_pages * 1024 tokens) each"""
-        return NSA_PagedKV(n_pages, B, max_pages, self.n_kv_groups, self.d_k, self.d_v, self.l, self.d, self.l_sel, self.n_sel, self.w, device, dtype)
+    def new_paged_kv(self, n_pages: int, B: int, max_pages: int, device, dtype, kv_dtype=None) -> NSA_PagedKV:
+        """pools of n_pages pages for B slots of up to max_pages pages (max_pages * 1024 tokens) each.  kv_dtype = torch.float8_e4m3fn: the
+        pools also own FP8 mirrors of the six attended pools with their scale pools (NSA_PagedKV), which decode_paged then reads"""
+        return NSA_PagedKV(n_pages, B, max_pages, self.n_kv_groups, self.d_k, self.d_v, self.l, self.d, self.l_sel, self.n_sel, self.w, device, dtype,
+                           kv_dtype=kv_dtype)
 
-    def decode_paged_plan(self, B: int, S: int, max_pages: int, t_max: int, S_sel: int) -> dict:
+    def decode_paged_plan(self, B: int, S: int, max_pages: int, t_max: int, S_sel: int, fp8: bool = False) -> dict:
         """what nsa_layer_decode_paged does with a shape under the current tuning switches (nsa_layer_decode_paged_plan, no device call):
         {"launches", "route": 1 the one native call / -1 declined (there is no other route over pages)}.  A t_max beyond the unsplit forms
         of the selected branch is declined unless the tuning switch DECODE_LONG = 1 (the long-row form: up to t_max = 131,071, the same
-        launch count and workspace)"""
+        launch count and workspace).  fp8: the call over pools with FP8 mirrors (nsa_layer_decode_paged_fp8_plan: one launch more, bf16
+        only, forms 0 / 1 whatever DECODE_LONG says)"""
         desc, _ = self._layer_desc()
-        n, r = _plan_ints("nsa_layer_decode_paged_plan", 2, ctypes.byref(desc), int(B), int(S), int(max_pages), int(t_max), int(S_sel))
+        name = "nsa_layer_decode_paged_fp8_plan" if fp8 else "nsa_layer_decode_paged_plan"
+        n, r = _plan_ints(name, 2, ctypes.byref(desc), int(B), int(S), int(max_pages), int(t_max), int(S_sel))
         return {"launches": n, "route": r}
 
     def decode_paged(self, x: torch.Tensor, pkv: NSA_PagedKV, t_pos, *, t_max: int):
@@ -827,7 +832,9 @@ class NSAAttention(nn.Module):
         Lengths belong to the caller.  A slot with t_pos[b] < 0, t_pos[b] + S - 1 > min(t_max, capacity - 1) or a needed table entry
         outside [0, n_pages) is inactive: nothing is written to any page, its y and ranges rows are zero.
         Monitors: _last_ranges [B,S,G,n,2], _last_gates [B,S,G,3] (gates of an inactive slot: unspecified).  Inference only.  There is no
-        other route over pages: parity mode, or a module, input or shape the native call declines, raises -- the latter with the library's message."""
+        other route over pages: parity mode, or a module, input or shape the native call declines, raises -- the latter with the library's message.
+        A pkv with FP8 mirrors (new_paged_kv(..., kv_dtype=torch.float8_e4m3fn)) takes nsa_layer_decode_paged_fp8: the same appends and
+        ranges, one launch more that mirrors the appended rows in e4m3, and the three branches read the mirrors."""
         B, S = self._rows_shape("decode_paged", x)
         if not isinstance(t_pos, torch.Tensor) or t_pos.dtype != torch.int32 or tuple(t_pos.shape) != (B,):
             raise ValueError(f"NSAAttention.decode_paged: t_pos must be a device int32 tensor [{B}]")
@@ -848,6 +855,9 @@ class NSAAttention(nn.Module):
             t_pos = t_pos.contiguous()
         pkv.refresh_meta(min(t_max, pkv.capacity - 1) + 1)
         # (a declined shape comes back from the call itself, before its first launch, with the limit named)
+        if pkv.kv_dtype is not None:
+            return self._rows_call("decode_paged_fp8", x, pkv, pkv.meta, pkv.max_pages, (t_pos.data_ptr(), t_max, S),
+                                   pre=(ctypes.byref(pkv.native_fp8_desc()),)), pkv
         return self._rows_call("decode_paged", x, pkv, pkv.meta, pkv.max_pages, (t_pos.data_ptr(), t_max, S)), pkv
 
     def prefill_paged(self, x: torch.Tensor, pkv: NSA_PagedKV, b: int, t0: int = 0):
