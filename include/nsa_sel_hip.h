@@ -339,6 +339,38 @@ NSA_API int nsa_layer_decode_ragged(const nsa_layer_desc *L, const nsa_kv_desc *
 NSA_API int nsa_layer_decode_ragged_plan(const nsa_layer_desc *L, int B, int S, int S_max, int t_max, int S_sel, int *launches /* host */,
                                  int *route /* host */);
 
+/* nsa_layer_decode_ragged with FP8 (OCP e4m3) mirrors of the six ATTENDED slabs: the call appends and pools in bf16 exactly as
+ * nsa_layer_decode_ragged does (the eight bf16 caches and the ranges are that call's bit for bit), then ONE more launch --
+ * layer_kv_mirror_fp8_ragged_kernel, behind the pooling -- quantises the rows this call wrote into the mirrors, and the three branches read
+ * the mirrors: nsa_sel_decode_ragged_fp8's kernel for the selected branch; the sliding and the compressed branch as ONE dual launch over
+ * e4m3 K/V (band_attn_fwd_dual_fp8_kernel: split form, the records merged by the finish kernel as in the bf16 call) wherever the bf16
+ * call takes its dual launch (Dv = 64), else one nsa_band_attn_fwd_ragged_fp8 launch each.  The scorer keeps reading bf16 K_cmp.
+ *   nsa_kv_fp8_desc   K_sel8, V_sel8, K_win8, V_win8 e4m3 [B, G, S_max, D] and K_cmp8, V_cmp8 [B, G, n_cmp_max, D], contiguous and 16-byte
+ *                 aligned (the shapes of the bf16 slabs of kv), each with its scale slab fp32 [B, G, S_max | n_cmp_max], contiguous and
+ *                 4-byte aligned.  K_raw / V_raw have no mirror.
+ * The mirror writer.  For every live sequence (0 <= t_pos[b], t_pos[b] + S - 1 <= te = min(t_max, S_max - 1)) token rows t_pos[b] ..
+ * t_pos[b] + S - 1 of the four token mirrors and compressed rows [n_cmp(t_pos[b]), n_cmp(t_pos[b] + S)) of the two compressed ones are
+ * written, byte for byte what nsa_kv_quantize_fp8 gives for the same bf16 row; no other row of a mirror is touched.  Every OTHER writer of
+ * the bf16 slabs must keep the mirrors a pure function of them (NSA_KV with kv_dtype does: nsa_vibe_amd/kv_cache.py, NSAAttention.forward).
+ * Launches: those of nsa_layer_decode_ragged + 1, the same route.  workspace: nsa_layer_decode_ragged's.  The bf16 attended slabs REMAIN
+ * (the fused QKV epilogue writes them): the mirrors halve the bytes the branches READ, not the pool capacity.
+ * DECLINES with NSA_ERR_INVALID and a message naming the limit, no fallback: wherever nsa_layer_decode_ragged does; a layer dtype other
+ * than bf16; te beyond unsplit forms 0 / 1 whatever DECODE_LONG says (the long-row form is not built for FP8; the plan then answers
+ * launches 0, route -1); a null descriptor, mirror or scale pointer; a mirror not 16-byte or a scale slab not 4-byte aligned. */
+typedef struct nsa_kv_fp8_desc {
+    void *K_sel8, *V_sel8, *K_win8, *V_win8;                      /* e4m3 [B, G, S_max, D] */
+    void *K_cmp8, *V_cmp8;                                        /* e4m3 [B, G, n_cmp_max, D] */
+    float *K_sel_scale, *V_sel_scale, *K_win_scale, *V_win_scale; /* [B, G, S_max] */
+    float *K_cmp_scale, *V_cmp_scale;                             /* [B, G, n_cmp_max] */
+} nsa_kv_fp8_desc;
+NSA_API size_t nsa_layer_decode_ragged_fp8_workspace(const nsa_layer_desc *L, int B, int S, int S_max);
+NSA_API int nsa_layer_decode_ragged_fp8(const nsa_layer_desc *L, const nsa_kv_desc *kv, const nsa_kv_fp8_desc *fp8, const void *x, void *y,
+                                const int32_t *t_pos /* device [B] */, int t_max /* host */, int S, const int32_t *csc_ptr,
+                                const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out, float *gates_out,
+                                void *workspace, size_t workspace_bytes, void *stream);
+NSA_API int nsa_layer_decode_ragged_fp8_plan(const nsa_layer_desc *L, int B, int S, int S_max, int t_max, int S_sel, int *launches /* host */,
+                                     int *route /* host */);
+
 /* The ragged layer decode over PAGED caches: nsa_layer_decode_ragged with all eight cache tensors held in pools of fixed-size pages and
  * found through a device block table -- the layer around nsa_sel_decode_paged and nsa_band_attn_fwd_paged, and the one place that WRITES
  * a token into a page.

@@ -54,6 +54,14 @@ class NsaPagedKvFp8Desc(C.Structure):
 _pl, _pk, _pb, _pp = C.POINTER(NsaLayerDesc), C.POINTER(NsaKvDesc), C.POINTER(NsaBlockDesc), C.POINTER(NsaPagedKvDesc)
 _pp8 = C.POINTER(NsaPagedKvFp8Desc)
 
+
+class NsaKvFp8Desc(C.Structure):
+    """struct nsa_kv_fp8_desc (include/nsa_sel_hip.h): the six e4m3 mirror slabs of an NSA_KV, then their six fp32 scale slabs"""
+    _fields_ = NsaPagedKvFp8Desc._fields_
+
+
+_pk8 = C.POINTER(NsaKvFp8Desc)
+
 # name -> (restype, argtypes); mirrors include/nsa_sel_hip.h one to one
 SIGNATURES = {
     "nsa_hip_abi_version": (_i, []),
@@ -94,6 +102,9 @@ SIGNATURES = {
     "nsa_layer_decode_ragged_workspace": (_sz, [_pl, _i, _i, _i]),
     "nsa_layer_decode_ragged": (_i, [_pl, _pk, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "nsa_layer_decode_ragged_plan": (_i, [_pl, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "nsa_layer_decode_ragged_fp8_workspace": (_sz, [_pl, _i, _i, _i]),
+    "nsa_layer_decode_ragged_fp8": (_i, [_pl, _pk, _pk8, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "nsa_layer_decode_ragged_fp8_plan": (_i, [_pl, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "nsa_layer_decode_paged_workspace": (_sz, [_pl, _i, _i, _i]),
     "nsa_layer_decode_paged": (_i, [_pl, _pp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "nsa_layer_decode_paged_plan": (_i, [_pl, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),

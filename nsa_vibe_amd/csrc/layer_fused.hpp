@@ -58,6 +58,17 @@ struct KvMirrorFp8PagedParams {
     int B, S, G, te;
 };
 int launch_kv_mirror_fp8_paged(const KvMirrorFp8PagedParams &P, int D, hipStream_t st);
+// the mirror writer of the ragged call (nsa_layer_decode_ragged_fp8): the same rows, of contiguous SLABS.  Slabs 0 .. 3 = K_sel, V_sel, K_win,
+// V_win [B, G, S_max, D], 4 / 5 = K_cmp, V_cmp [B, G, n_cmp_max, D]; the scale slabs [B, G, S_max | n_cmp_max]; D = Dk = Dv.  A sequence is
+// live under the ragged rule: 0 <= t_pos[b] and t_pos[b] + S - 1 <= te, te = min(t_max, S_max - 1)
+struct KvMirrorFp8RaggedParams {
+    const void *src[6];
+    unsigned char *q8[6];
+    float *scale[6];
+    const int32_t *t_pos;
+    int B, S, G, te, S_max, n_cmp_max;
+};
+int launch_kv_mirror_fp8_ragged(const KvMirrorFp8RaggedParams &P, int D, hipStream_t st);
 // the pre-pass: one wave per sequence writes its verdict t_live[b] = t_pos[b] where the sequence is live -- 0 <= t_pos[b],
 // t_pos[b] + S - 1 <= te, every table entry j = 0 .. (t_pos[b] + S - 1) >> 10 inside [0, n_pages) -- and -1 otherwise
 struct PagedLiveParams {

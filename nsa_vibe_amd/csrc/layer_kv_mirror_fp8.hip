@@ -80,4 +80,69 @@ int launch_kv_mirror_fp8_paged(const KvMirrorFp8PagedParams &P, int D, hipStream
     return NSA_OK;
 }
 
+// layer_kv_mirror_fp8_ragged_kernel: the mirror writer of nsa_layer_decode_ragged_fp8 -- the same rows of contiguous slabs, row r of plane
+// (b, g) at (b G + g) rows + r.  No table, so nothing is shared between the rows of a sequence: no LDS, no barrier, and the work is dealt
+// out by ROW instead of by (sequence, pair).  A sequence has at most I = G (4 S + 2 CM) rows to quantise -- S token rows of four slabs and
+// CM = ceil(S / 16) compressed rows of two (n_cmp advances by at most that over S tokens) -- in that fixed order (slab, g, row), so the rows a
+// wave takes together are consecutive rows of one plane wherever S allows: contiguous loads and stores.  A wave takes 64 / (D / 8) of them,
+// a sequence ceil(I / rows per wave) waves, and the waves of all sequences are packed four to a workgroup: B = 256, S = 1, G = 4, D = 64 is
+// 192 full workgroups where a workgroup per (sequence, pair) would launch 768 mostly idle ones.  A wave belongs to ONE sequence, so the
+// position is one scalar load and the liveness test is wave uniform; the slab pointers are indexed per lane from the argument block.
+template <int D>
+__global__ __launch_bounds__(256) void layer_kv_mirror_fp8_ragged_kernel(KvMirrorFp8RaggedParams P, int wps) {
+    constexpr int LPR = D / 8, RPW = 64 / LPR;  // lanes per row, rows per wave
+    const int wid = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6))), lane = threadIdx.x & 63;
+    const int b = wid / wps;
+    if (b >= P.B) return;
+    const int t0 = P.t_pos[b];
+    if (t0 < 0 || t0 > P.te - (P.S - 1)) return;  // not live: the whole wave
+    auto ncmp = [](int n) { return n < 32 ? 0 : (n - 32) / 16 + 1; };  // compressed tokens of n cached ones (l = 32, d = 16: ncmp_of)
+    const int n0 = ncmp(t0), nc = ncmp(t0 + P.S) - n0;
+    const int CM = (P.S + 15) / 16, per_tok = P.G * P.S, per_cmp = P.G * CM;
+    const int idx = (wid - b * wps) * RPW + lane / LPR;  // the D / 8 lanes of a row stay together
+    int slab, g, row, rows;
+    if (idx < 4 * per_tok) {
+        slab = idx / per_tok;
+        const int rem = idx - slab * per_tok;
+        g = rem / P.S;
+        row = t0 + rem - g * P.S;  // <= te < S_max
+        rows = P.S_max;
+    } else {
+        const int j = idx - 4 * per_tok;
+        if (j >= 2 * per_cmp) return;  // behind the sequence's last row
+        const int pair = j / per_cmp, rem = j - pair * per_cmp;
+        slab = 4 + pair;
+        g = rem / CM;
+        const int r = rem - g * CM;
+        if (r >= nc) return;  // no window completes for this slot
+        row = n0 + r;  // < n_cmp(te + 1) <= n_cmp_max
+        rows = P.n_cmp_max;
+    }
+    const int64_t at = ((int64_t)b * P.G + g) * rows + row;  // (formed in 64 bits: a slab may exceed 2 GiB)
+    kv_quantize_fp8_row<D>((const __bf16 *)P.src[slab] + at * D, P.q8[slab] + at * D, P.scale[slab] + at, lane % LPR);
+}
+
+int launch_kv_mirror_fp8_ragged(const KvMirrorFp8RaggedParams &P, int D, hipStream_t st) {
+    const char *who = "kv_mirror_fp8(ragged)";
+    NSA_CHECK_ARG(D == 64 || D == 128, "%s: D = %d, the head dimension must be 64 or 128", who, D);
+    NSA_CHECK_ARG(P.B >= 1 && P.S >= 1 && P.S <= 16 && P.G >= 1 && P.S_max >= 1 && P.n_cmp_max >= 1 && P.te >= 0 && P.te < P.S_max, "%s: bad sizes", who);
+    // (the kernel's row bounds: a live row sits at most at te < S_max, and every compressed row it may emit is held)
+    NSA_CHECK_ARG(P.n_cmp_max >= (P.te + 1 < 32 ? 0 : (P.te + 1 - 32) / 16 + 1), "%s: compressed slabs too small for %d tokens", who, P.te + 1);
+    NSA_CHECK_ARG(P.t_pos, "%s: null position array", who);
+    for (int i = 0; i < 6; ++i) {
+        NSA_CHECK_ARG(P.src[i] && P.q8[i] && P.scale[i], "%s: null slab pointer", who);
+        NSA_CHECK_ARG((uintptr_t)P.src[i] % 16 == 0 && (uintptr_t)P.q8[i] % 16 == 0 && (uintptr_t)P.scale[i] % 4 == 0,
+                      "%s: the bf16 and the e4m3 slabs must be 16-byte aligned, the scale slabs 4-byte aligned", who);
+    }
+    const int rpw = 64 / (D / 8), items = P.G * (4 * P.S + 2 * ((P.S + 15) / 16));
+    const int wps = (items + rpw - 1) / rpw;
+    const int64_t waves = (int64_t)P.B * wps;
+    NSA_CHECK_ARG(waves < ((int64_t)1 << 31), "%s: too many sequences", who);
+    const dim3 grid((unsigned)((waves + 3) / 4));
+    if (D == 64) hipLaunchKernelGGL(layer_kv_mirror_fp8_ragged_kernel<64>, grid, dim3(256), 0, st, P, wps);
+    else hipLaunchKernelGGL(layer_kv_mirror_fp8_ragged_kernel<128>, grid, dim3(256), 0, st, P, wps);
+    NSA_LAUNCH_CHECK("layer_kv_mirror_fp8_ragged_kernel");
+    return NSA_OK;
+}
+
 }  // namespace nsa

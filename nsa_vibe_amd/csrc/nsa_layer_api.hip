@@ -285,7 +285,8 @@ struct LayerDecode {
     // paged call (nsa_layer_decode_paged): the block table; kv then names the POOLS with one page as its extent (S_max = 1024, n_cmp_max = 64,
     // so that CacheStrides gives the page strides), t_pos is the pre-pass's t_live and te = min(t_max, max_pages 1024 - 1)
     const LayerPageTable *pg;
-    // paged call with FP8 mirrors (nsa_layer_decode_paged_fp8): the branches read these instead of the attended bf16 pools; null: bf16
+    // call with FP8 mirrors (nsa_layer_decode_paged_fp8: pools; nsa_layer_decode_ragged_fp8: slabs of kv's shape, handed over in the same
+    // struct): the branches read these instead of the attended bf16 caches; null: bf16
     const nsa_paged_kv_fp8_desc *m8;
     int tokens() const { return t_pos ? te + 1 : t0 + S; }  // tokens the caches hold after the call (of the largest sequence)
 };
@@ -458,9 +459,18 @@ static int layer_decode_tail(const LayerDecode &D, const CacheStrides &C, Decode
     const nsa_kv_desc *kv = D.kv;
     hipStream_t st = (hipStream_t)stream;
     const int B = kv->B, S = D.S, G = L->G, dt = L->dtype, defer = finish_defers(L);
+    // FP8 mirrors: the e4m3 caches have the bf16 caches' shape, so their strides in BYTES are the element strides C holds; the scale caches are
+    // [n_pages | B, G, rows] with the rows of kv's extent (a page of the pools, a slab of the ragged call)
+    BandFp8Scales zw{}, zc{};
+    if (D.m8) {
+        zw = BandFp8Scales{D.m8->K_win_scale, D.m8->V_win_scale, (int64_t)G * kv->S_max, kv->S_max, (int64_t)G * kv->S_max, kv->S_max};
+        zc = BandFp8Scales{D.m8->K_cmp_scale, D.m8->V_cmp_scale, (int64_t)G * kv->n_cmp_max, kv->n_cmp_max, (int64_t)G * kv->n_cmp_max, kv->n_cmp_max};
+    }
     if (BP) {
-        if (!ridden)
-            if (int rc = launch_band_attn_fwd_dual(BP->w, BP->c, dt, st)) return rc;
+        if (!ridden) {
+            // (with mirrors: the ragged FP8 call, whose pair names the e4m3 slabs -- layer_decode_rows_tail)
+            if (int rc = D.m8 ? launch_band_attn_fwd_dual_fp8(BP->w, zw, BP->c, zc, st) : launch_band_attn_fwd_dual(BP->w, BP->c, dt, st)) return rc;
+        }
         F.ns[2] = F.ns[0] = BP->w.nsplit;
         F.part[2] = BP->w.part;
         F.part[0] = BP->c.part;
@@ -474,17 +484,11 @@ static int layer_decode_tail(const LayerDecode &D, const CacheStrides &C, Decode
             pw = BandPages{BandPageTable{D.pg->table, D.pg->stride, D.pg->n_pages, 0}, D.pg->max_pages, LAYER_PAGE_TOKENS};
             pc = BandPages{pw.table, D.pg->max_pages, LAYER_PAGE_CMP};
         }
-        const char *who = D.m8 ? "band_attn_fwd_paged_fp8" : D.pg ? "band_attn_fwd_paged" : D.t_pos ? "band_attn_fwd_ragged" : "band_attn_fwd";
+        const char *who = D.m8 ? (D.pg ? "band_attn_fwd_paged_fp8" : "band_attn_fwd_ragged_fp8") : D.pg ? "band_attn_fwd_paged" : D.t_pos ? "band_attn_fwd_ragged" : "band_attn_fwd";
         BandFwdCall w{who, b.w, b.bw}, c{who, b.c, b.bc};
         if (D.t_pos) w.pos = c.pos = &pos;
         if (D.pg) w.pages = &pw, c.pages = &pc;
-        // FP8 mirrors: the e4m3 pools have the bf16 pools' shape, so their strides in BYTES are the element strides C holds; the scale pools are
-        // [n_pages, G, page rows]
-        BandFp8Scales zw{}, zc{};
         if (D.m8) {
-            const int64_t G = L->G;
-            zw = BandFp8Scales{D.m8->K_win_scale, D.m8->V_win_scale, G * LAYER_PAGE_TOKENS, LAYER_PAGE_TOKENS, G * LAYER_PAGE_TOKENS, LAYER_PAGE_TOKENS};
-            zc = BandFp8Scales{D.m8->K_cmp_scale, D.m8->V_cmp_scale, G * LAYER_PAGE_CMP, LAYER_PAGE_CMP, G * LAYER_PAGE_CMP, LAYER_PAGE_CMP};
             w.c.K = D.m8->K_win8, w.c.V = D.m8->V_win8, w.fp8 = &zw;
             c.c.K = D.m8->K_cmp8, c.c.V = D.m8->V_cmp8, c.fp8 = &zc;
         }
@@ -508,7 +512,8 @@ static int layer_decode_tail(const LayerDecode &D, const CacheStrides &C, Decode
 static int layer_decode_rows_tail(const LayerDecode &D, const CacheStrides &C, float *gates_out, void *y, void *stream) {
     DecodeFinishParams F = decode_finish_params(D, gates_out);
     DecBandPair BP{};
-    const bool dual = !D.pg && band_pair(D, C, BP);
+    const bool dual = !D.pg && band_pair(D, C, BP);  // (the bf16 decision, on the bf16 caches, with or without mirrors)
+    if (dual && D.m8) BP.w.K = D.m8->K_win8, BP.w.V = D.m8->V_win8, BP.c.K = D.m8->K_cmp8, BP.c.V = D.m8->V_cmp8;
     return layer_decode_tail(D, C, F, dual ? &BP : nullptr, false, gates_out, y, nullptr, stream);
 }
 
@@ -639,8 +644,10 @@ int nsa_layer_decode_rows_plan(const nsa_layer_desc *L, int B, int S, int S_max,
 // What the call and its plan share, from the shape, the host bound and the switches alone (aligned caches of capacity S_max assumed; the
 // position array is never read on the host).  NSA_OK with p->launches = n: the call runs; p->launches = 0 and p->why = the limit: DECLINED --
 // there is no scalar route to stand in (every other launch of the layer takes one position per call); an error status: bad arguments.
+// fp8: the call with FP8 mirrors (nsa_layer_decode_ragged_fp8) -- bf16 only, the selected branch planned on its FP8 axis (forms 0 / 1 whatever
+// DECODE_LONG says), and one more launch: the mirror writer behind the pooling.
 static int layer_decode_ragged_route(const char *who, const nsa_layer_desc *L, int B, int S, int S_max, int t_max, int S_sel, int n_cmp_max,
-                                     PositionsPlan *p) {
+                                     PositionsPlan *p, bool fp8 = false) {
     *p = PositionsPlan{};
     if (int rc = check_layer(L, who)) return rc;
     if (int rc = check_rows_count(who, S)) return rc;
@@ -648,17 +655,19 @@ static int layer_decode_ragged_route(const char *who, const nsa_layer_desc *L, i
     if (int rc = check_bound(who, L, S, S_max, t_max, S_sel, p)) return rc;
     NSA_CHECK_ARG(n_cmp_max < 0 || n_cmp_max >= p->n1, "%s: compressed cache too small (n_cmp_max=%d) for %d tokens", who, n_cmp_max, p->te + 1);
     p->why = !dtype_16bit(L->dtype)          ? "bf16 / f16 only (the launches that take per-sequence positions have no fp32 form)"
+             : fp8 && L->dtype != NSA_DT_BF16 ? "FP8 K/V mirrors take a bf16 layer only (the FP8 readers are built for bf16 queries; f16 is declined)"
              : !default_decode_geometry(L) ? "Dk = Dv in {64, 128} and the default block geometry only (l = 32, d = 16, l' = 64)" : nullptr;
     if (p->why) return NSA_OK;
     const nsa_kv_desc kv = stand_in_kv(B, S_max, std::max(1, ncmp_of(S_max, L->l, L->d)));
     const CacheStrides C(L, &kv);
     SelDecodeCall sc = sel_decode_call(L, &kv, C, S, p->t0, p->n1, S_sel);
     sc.S_kv = p->te + 1;
+    if (fp8) sc.kv_dtype = NSA_DT_FP8_E4M3;
     if (!decode_ragged_shape_plan(sc, p->te, nullptr, nullptr, &p->why)) return NSA_OK;
     p->why = nullptr;
     // projection + RoPE + append, pooling (always: the host cannot know whether a window completes), the selected branch's one launch,
     // the band pair (or one launch each; an undeferred split branch adds its combine: not counted), finish (or gate + mix), output projection
-    p->launches = 3 + (band_pair_splits(L, &kv, C, S, p->t0, p->te + 1, p->n1) ? 1 : 2) + 2;
+    p->launches = 3 + (band_pair_splits(L, &kv, C, S, p->t0, p->te + 1, p->n1) ? 1 : 2) + 2 + (fp8 ? 1 : 0);
     return NSA_OK;
 }
 
@@ -670,15 +679,16 @@ int nsa_layer_decode_ragged_plan(const nsa_layer_desc *L, int B, int S, int S_ma
     return plan_answer(layer_decode_ragged_route("layer_decode_ragged_plan", L, B, S, S_max, t_max, S_sel, -1, &p), p, launches, route);
 }
 
-int nsa_layer_decode_ragged(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *x, void *y, const int32_t *t_pos, int t_max, int S,
-                            const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out, float *gates_out,
-                            void *workspace, size_t workspace_bytes, void *stream) {
-    const char *who = "layer_decode_ragged";
+// The ragged call and its FP8 form (m8: the mirrors, slabs of kv's shape; null for the bf16 call -- whose checks, launches and messages are
+// those below without the lines that name m8).
+static int layer_decode_ragged_impl(const char *who, const nsa_layer_desc *L, const nsa_kv_desc *kv, const nsa_paged_kv_fp8_desc *m8, const void *x, void *y,
+                                    const int32_t *t_pos, int t_max, int S, const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel,
+                                    int32_t *ranges_out, float *gates_out, void *workspace, size_t workspace_bytes, void *stream) {
     if (int rc = check_layer(L, who)) return rc;
     if (int rc = check_kv(kv, who)) return rc;
     if (int rc = check_io(who, L, x, y, t_pos)) return rc;
     PositionsPlan p;  // the largest sequence the launches are planned for: te + 1 tokens after the call, n1 compressed ones (LayerDecode)
-    if (int rc = layer_decode_ragged_route(who, L, kv->B, S, kv->S_max, t_max, S_sel, kv->n_cmp_max, &p)) return rc;
+    if (int rc = layer_decode_ragged_route(who, L, kv->B, S, kv->S_max, t_max, S_sel, kv->n_cmp_max, &p, m8 != nullptr)) return rc;
     NSA_CHECK_ARG(!p.why, "%s: %s (B = %d, S = %d, D = %d, t_max = %d)", who, p.why, kv->B, S, L->Dk, t_max);
     const CacheStrides C(L, kv);
     SelDecodeCall probe = sel_decode_call(L, kv, C, S, 0, p.n1, S_sel);
@@ -686,9 +696,21 @@ int nsa_layer_decode_ragged(const nsa_layer_desc *L, const nsa_kv_desc *kv, cons
     probe.Q = probe.O = kv->K_cmp;  // (Q and O come from the 256-byte aligned workspace)
     NSA_CHECK_ARG(decode_step_operands_ok(probe) && (uintptr_t)kv->K_cmp % 16 == 0,
                   "%s: K_cmp, K_sel and V_sel must be 16-byte aligned with strides in multiples of 8 elements", who);
+    if (m8) {
+        NSA_CHECK_ARG(m8->K_sel8 && m8->V_sel8 && m8->K_win8 && m8->V_win8 && m8->K_cmp8 && m8->V_cmp8, "%s: null FP8 mirror slab pointer", who);
+        NSA_CHECK_ARG(m8->K_sel_scale && m8->V_sel_scale && m8->K_win_scale && m8->V_win_scale && m8->K_cmp_scale && m8->V_cmp_scale,
+                      "%s: null scale slab pointer (every FP8 mirror needs its fp32 scale slab)", who);
+        NSA_CHECK_ARG(((uintptr_t)m8->K_sel8 | (uintptr_t)m8->V_sel8 | (uintptr_t)m8->K_win8 | (uintptr_t)m8->V_win8 | (uintptr_t)m8->K_cmp8 | (uintptr_t)m8->V_cmp8) % 16 == 0 &&
+                          ((uintptr_t)m8->K_sel_scale | (uintptr_t)m8->V_sel_scale | (uintptr_t)m8->K_win_scale | (uintptr_t)m8->V_win_scale |
+                           (uintptr_t)m8->K_cmp_scale | (uintptr_t)m8->V_cmp_scale) % 4 == 0,
+                      "%s: the six FP8 mirror slabs must be 16-byte aligned and their scale slabs 4-byte aligned", who);
+        // (the mirror writer and the FP8 band kernels read the four band and the V_sel slabs in 16-byte pieces too)
+        NSA_CHECK_ARG(((uintptr_t)kv->V_sel | (uintptr_t)kv->K_win | (uintptr_t)kv->V_win | (uintptr_t)kv->V_cmp) % 16 == 0, "%s: the six attended bf16 slabs must be 16-byte aligned", who);
+    }
     const DecodeWs W = decode_ws(L, kv->B, kv->S_max, S);
     if (int rc = check_workspace(who, workspace, workspace_bytes, W.total)) return rc;
-    const LayerDecode D = layer_decode_positions(L, kv, W, workspace, S, p, t_pos);
+    LayerDecode D = layer_decode_positions(L, kv, W, workspace, S, p, t_pos);
+    D.m8 = m8;
     hipStream_t st = (hipStream_t)stream;
     // 1. fused QKV projection of the B S rows, row (b, s) rotated at t_pos[b] + s and appended there where sequence b is live
     RopeAppendParams R = rope_append_params(L, kv, D.ws + W.proj, D.Q, S, 0);
@@ -699,13 +721,56 @@ int nsa_layer_decode_ragged(const nsa_layer_desc *L, const nsa_kv_desc *kv, cons
     CmpPoolParams P = cmp_pool_params(L, kv->B, kv->K_raw, kv->V_raw, kv->K_cmp, kv->V_cmp, kv->S_max, kv->n_cmp_max);
     P.t_pos = t_pos; P.t_max = p.te; P.S = S; P.G = L->G;
     if (int rc = launch_cmp_pool_ragged(P, L->dtype, st)) return rc;
-    // 3. selected branch: the rows form with the position array (one launch; zero O and ranges rows for a sequence that is not live)
+    // 2b. FP8 mirrors: the rows launches 1 and 2 wrote, quantised into the six mirrors (one launch, behind them on the stream)
+    if (m8) {
+        const KvMirrorFp8RaggedParams M{{kv->K_sel, kv->V_sel, kv->K_win, kv->V_win, kv->K_cmp, kv->V_cmp},
+                                        {(unsigned char *)m8->K_sel8, (unsigned char *)m8->V_sel8, (unsigned char *)m8->K_win8, (unsigned char *)m8->V_win8,
+                                         (unsigned char *)m8->K_cmp8, (unsigned char *)m8->V_cmp8},
+                                        {m8->K_sel_scale, m8->V_sel_scale, m8->K_win_scale, m8->V_win_scale, m8->K_cmp_scale, m8->V_cmp_scale},
+                                        t_pos, kv->B, S, L->G, p.te, kv->S_max, kv->n_cmp_max};
+        if (int rc = launch_kv_mirror_fp8_ragged(M, L->Dk, st)) return rc;
+    }
+    // 3. selected branch: the rows form with the position array (one launch; zero O and ranges rows for a sequence that is not live); with
+    // mirrors its FP8 axis -- the scorer still reads bf16 K_cmp, K / V are the e4m3 slabs (strides in bytes: the element strides' numbers)
     SelDecodeCall c = layer_sel_call(D, C, csc_ptr, csc_rows, csc_vals, S_sel, ranges_out);
     c.S_kv = p.te + 1;  // (the paged call leaves t0 + S)
+    if (m8) {
+        c.kv_dtype = NSA_DT_FP8_E4M3;
+        c.K = m8->K_sel8; c.V = m8->V_sel8; c.k_scale = m8->K_sel_scale; c.v_scale = m8->V_sel_scale;
+        c.kzb = c.vzb = (int64_t)L->G * kv->S_max; c.kzg = c.vzg = kv->S_max;
+    }
     if (int rc = launch_decode_rows(c, st, t_pos, p.te)) return rc;
     // 4. both band branches in one dual launch (split form, deferred combine; Dv = 128: one ragged launch each), 5. finish (or the gate
     // kernel), 6. output projection -- the rows call's tail with the position array in D
     return layer_decode_rows_tail(D, C, gates_out, y, stream);
+}
+
+int nsa_layer_decode_ragged(const nsa_layer_desc *L, const nsa_kv_desc *kv, const void *x, void *y, const int32_t *t_pos, int t_max, int S,
+                            const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out, float *gates_out,
+                            void *workspace, size_t workspace_bytes, void *stream) {
+    return layer_decode_ragged_impl("layer_decode_ragged", L, kv, nullptr, x, y, t_pos, t_max, S, csc_ptr, csc_rows, csc_vals, S_sel, ranges_out, gates_out,
+                                    workspace, workspace_bytes, stream);
+}
+
+// ---- the ragged call with FP8 mirrors of the attended slabs: the same body, the mirror writer behind the pooling, the branches on their FP8 kernels
+size_t nsa_layer_decode_ragged_fp8_workspace(const nsa_layer_desc *L, int B, int S, int S_max) { return nsa_layer_decode_ragged_workspace(L, B, S, S_max); }
+
+int nsa_layer_decode_ragged_fp8_plan(const nsa_layer_desc *L, int B, int S, int S_max, int t_max, int S_sel, int *launches, int *route) {
+    NSA_CHECK_ARG(launches && route, "layer_decode_ragged_fp8_plan: null pointer");
+    PositionsPlan p;
+    return plan_answer(layer_decode_ragged_route("layer_decode_ragged_fp8_plan", L, B, S, S_max, t_max, S_sel, -1, &p, true), p, launches, route);
+}
+
+int nsa_layer_decode_ragged_fp8(const nsa_layer_desc *L, const nsa_kv_desc *kv, const nsa_kv_fp8_desc *fp8, const void *x, void *y, const int32_t *t_pos,
+                                int t_max, int S, const int32_t *csc_ptr, const int32_t *csc_rows, const float *csc_vals, int S_sel, int32_t *ranges_out,
+                                float *gates_out, void *workspace, size_t workspace_bytes, void *stream) {
+    const char *who = "layer_decode_ragged_fp8";
+    NSA_CHECK_ARG(fp8, "%s: null FP8 mirror descriptor", who);
+    // (the body's mirror block: the same twelve members, here slabs of kv's shape)
+    const nsa_paged_kv_fp8_desc m8{fp8->K_sel8, fp8->V_sel8, fp8->K_win8, fp8->V_win8, fp8->K_cmp8, fp8->V_cmp8,
+                                   fp8->K_sel_scale, fp8->V_sel_scale, fp8->K_win_scale, fp8->V_win_scale, fp8->K_cmp_scale, fp8->V_cmp_scale};
+    return layer_decode_ragged_impl(who, L, kv, &m8, x, y, t_pos, t_max, S, csc_ptr, csc_rows, csc_vals, S_sel, ranges_out, gates_out, workspace, workspace_bytes,
+                                    stream);
 }
 
 // ------------------------------------------------------------------------------ paged layer decode: append, pool and attend through a block table

@@ -143,6 +143,8 @@ int launch_band_attn_fwd_mfma(const BandAttnParams &P, int dtype, hipStream_t st
 // caller planned (nt column tiles, split or not); the caller checks the launch.
 void launch_band_attn_paged_kernel(const BandAttnParams &P, const BandPageTable &pt, int dtype, int nt, bool split, unsigned grid, size_t lds, hipStream_t st);
 int launch_band_attn_fwd_dual(const BandAttnParams &P0, const BandAttnParams &P1, int dtype, hipStream_t st);
+// its FP8 form (band_attn_fp8.hip): P0 / Z0 the sliding, P1 / Z1 the compressed branch over e4m3 K/V, one position array, Dk = Dv = 64
+int launch_band_attn_fwd_dual_fp8(const BandAttnParams &P0, const BandFp8Scales &Z0, const BandAttnParams &P1, const BandFp8Scales &Z1, hipStream_t st);
 // the sliding (w) and compressed (c) branch of a decode step as extra workgroups of ANOTHER launch (the one-launch decode step of the
 // selected branch): workgroups [n_sel, n_sel + n_w) take w, those behind them c; every wave of such a workgroup is one (row, split) unit
 // mg.on: the splits of a (row, branch) unit are the consecutive waves of ONE workgroup (nsplit divides the workgroup's waves) and are merged

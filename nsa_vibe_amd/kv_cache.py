@@ -25,9 +25,18 @@ def n_cmp_at(n_tokens: int, l: int, d: int) -> int:
     return 0 if n_tokens < l else (n_tokens - l) // d + 1
 
 
+_MIRRORED = ("_K_sel", "_V_sel", "_K_win", "_V_win", "_K_cmp", "_V_cmp")  # the attended caches: what kv_dtype = float8_e4m3fn mirrors
+FP8 = torch.float8_e4m3fn
+
+
 class NSA_KV:
     def __init__(self, B: int, G: int, d_k: int, d_v: int, S_max: int, l: int, d: int, l_sel: int, n_sel: int, w: int,
-                 device, dtype, auto_grow: bool = True):
+                 device, dtype, auto_grow: bool = True, kv_dtype=None):
+        """kv_dtype = torch.float8_e4m3fn (bf16 caches on a HIP device): the cache also owns, for each of the six ATTENDED caches (not
+        K_raw / V_raw), an e4m3 mirror of the same shape (<name>8) and an fp32 scale slab [B, G, rows] (<name>_scale) -- what
+        NSAAttention.decode_ragged then reads (nsa_layer_decode_ragged_fp8, which also mirrors the rows it appends).  The bf16 caches remain:
+        the mirrors halve the bytes the branches read, not the capacity.  A mirror row is always the quantisation of its bf16 row: a prefill
+        requantises what it wrote (requantize).  None: no mirrors, the object of before."""
         self.B, self.G, self.d_k, self.d_v, self.S_max = B, G, d_k, d_v, S_max
         self.auto_grow = auto_grow
         self.l, self.d, self.l_sel, self.n_sel, self.w = l, d, l_sel, n_sel, w
@@ -37,6 +46,13 @@ class NSA_KV:
         self._K_win, self._V_win = mk(S_max, d_k), mk(S_max, d_v)
         self._K_raw, self._V_raw = mk(S_max, d_k), mk(S_max, d_v)
         self._K_cmp, self._V_cmp = mk(n_cmp_max, d_k), mk(n_cmp_max, d_v)
+        self.kv_dtype = kv_dtype
+        if kv_dtype is not None:
+            if kv_dtype != FP8 or dtype != torch.bfloat16 or self._K_sel.device.type != "cuda":
+                raise ValueError(f"NSA_KV: kv_dtype = {kv_dtype} with {dtype} caches on {self._K_sel.device} -- the only mirror format is "
+                                 "torch.float8_e4m3fn, over bf16 caches on a HIP device")
+            for name in _MIRRORED:
+                self._new_mirror(name)
         self.t = 0  # tokens stored
         self.n_cmp = 0  # compressed tokens emitted
         self.meta: BlockMeta = build_block_meta(0, l, d, l_sel, n_sel, w)
@@ -73,7 +89,10 @@ class NSA_KV:
         v = object.__new__(type(self))
         v.__dict__.update(self.__dict__)
         v.B, v.auto_grow, v.S_max = 1, False, cap
-        for name in ("_K_sel", "_V_sel", "_K_win", "_V_win", "_K_raw", "_V_raw", "_K_cmp", "_V_cmp"):
+        shared = ["_K_sel", "_V_sel", "_K_win", "_V_win", "_K_raw", "_V_raw", "_K_cmp", "_V_cmp"]
+        if self.kv_dtype is not None:  # the view shares the FP8 mirrors too: a prefill through it requantises the pool's rows
+            shared += [name + tail for name in _MIRRORED for tail in ("8", "_scale")]
+        for name in shared:
             setattr(v, name, getattr(self, name)[b:b + 1])  # (a leading-axis slice: contiguous, the same memory)
         v.t, v.n_cmp = t, self.n_cmp_at(t)
         v.meta, v.meta_seq_len = build_block_meta(0, self.l, self.d, self.l_sel, self.n_sel, self.w), 0
@@ -133,6 +152,36 @@ class NSA_KV:
         self._K_cmp, self._V_cmp = grow(self._K_cmp, n_cmp_max, self.n_cmp), grow(self._V_cmp, n_cmp_max, self.n_cmp)
         self.S_max = S_max
         self._native.clear()
+        if self.kv_dtype is not None:  # the mirrors grow with the slabs: fresh ones, the kept rows quantised again
+            for name in _MIRRORED:
+                self._new_mirror(name)
+            self.requantize(0, self.t, 0, self.n_cmp)
+
+    # ---- FP8 mirrors (kv_dtype = float8_e4m3fn) ------------------------------------------------------------------------------------------
+    def _new_mirror(self, name: str) -> None:
+        buf = getattr(self, name)
+        setattr(self, name + "8", torch.zeros(buf.shape, device=buf.device, dtype=FP8))
+        setattr(self, name + "_scale", torch.ones(buf.shape[:3], device=buf.device, dtype=torch.float32))
+
+    def requantize(self, t0: int, t: int, n0: int, n: int) -> None:
+        """token rows [t0, t) and compressed rows [n0, n) of the six mirrors from the bf16 caches, by the public quantiser (one launch per
+        mirror, behind the writer of the bf16 rows on its stream): what every writer other than the ragged FP8 call does after it stored"""
+        from .selection_attention import quantize_kv_fp8
+
+        for name in _MIRRORED:
+            lo, hi = (n0, n) if name in ("_K_cmp", "_V_cmp") else (t0, t)
+            if hi > lo:
+                quantize_kv_fp8(getattr(self, name), lo, hi, out=getattr(self, name + "8"), scale_out=getattr(self, name + "_scale"))
+
+    def native_fp8_desc(self):
+        """struct nsa_kv_fp8_desc of the mirrors and their scale slabs, built once per set of buffers"""
+        d = self._native.get("fp8_desc")
+        if d is None:
+            d = self._native["fp8_desc"] = _lib.NsaKvFp8Desc()
+            for name in _MIRRORED:
+                setattr(d, name[1:] + "8", getattr(self, name + "8").data_ptr())
+                setattr(d, name[1:] + "_scale", getattr(self, name + "_scale").data_ptr())
+        return d
 
     def ensure_capacity(self, n_tokens: int) -> None:
         """room for n_tokens in total: grows geometrically (auto_grow) or raises"""
@@ -245,8 +294,6 @@ class NSA_KV:
 PAGE_TOKENS, PAGE_CMP = 1024, 64  # a page: 1024 tokens of the six token caches, 64 rows of K_cmp / V_cmp (d = 16)
 CLOSE_LAG = 16  # d: compressed row 64 j + 63, the last of page j, is pooled from raw rows up to 1024 (j + 1) + 15
 _POOLS = ("_K_sel", "_V_sel", "_K_win", "_V_win", "_K_raw", "_V_raw", "_K_cmp", "_V_cmp")
-_MIRRORED = ("_K_sel", "_V_sel", "_K_win", "_V_win", "_K_cmp", "_V_cmp")  # the attended pools: what kv_dtype = float8_e4m3fn mirrors
-FP8 = torch.float8_e4m3fn
 
 
 class NSA_PagedKV:

@@ -342,8 +342,10 @@ class NSAAttention(nn.Module):
                                                   "sliding_fa2_fails", "total_fallbacks")}
 
     # ---- cache -------------------------------------------------------------------------------
-    def new_kv(self, B: int, S_max: int, device, dtype) -> NSA_KV:
-        return NSA_KV(B, self.n_kv_groups, self.d_k, self.d_v, S_max, self.l, self.d, self.l_sel, self.n_sel, self.w, device, dtype)
+    def new_kv(self, B: int, S_max: int, device, dtype, kv_dtype=None) -> NSA_KV:
+        """kv_dtype = torch.float8_e4m3fn: the cache also owns FP8 mirrors of the six attended caches with their scale slabs (NSA_KV), which
+        decode_ragged then reads; a prefill keeps them current, the other decode routes decline such a cache"""
+        return NSA_KV(B, self.n_kv_groups, self.d_k, self.d_v, S_max, self.l, self.d, self.l_sel, self.n_sel, self.w, device, dtype, kv_dtype=kv_dtype)
 
     # ---- monitors (reference :407-445); computed on demand so the forward pass never syncs -----
     def get_gate_stats(self) -> Optional[dict]:
@@ -460,6 +462,19 @@ class NSAAttention(nn.Module):
         else:
             assert x.shape[1] == 1, f"Decode mode requires S=1 (single token), got S={x.shape[1]}."
         self._check_kv(x, kv)
+        if kv.kv_dtype is not None:
+            if not prefill:
+                raise RuntimeError("NSAAttention.forward(prefill=False): this cache carries FP8 mirrors, which only decode_ragged reads and keeps "
+                                   "current; decode it with decode_ragged")
+            # FP8 mirrors: whatever route the prefill takes, the rows it wrote are requantised behind it (a mirror row is always the
+            # quantisation of its bf16 row)
+            t0, n0 = kv.t, kv.n_cmp
+            out = self._forward(x, kv, prefill)
+            kv.requantize(t0, kv.t, n0, kv.n_cmp)
+            return out
+        return self._forward(x, kv, prefill)
+
+    def _forward(self, x: torch.Tensor, kv: NSA_KV, prefill: bool):
         # a strided [B,S,dim] view (e.g. x[:, :S] of a longer buffer) is copied first: the projection would otherwise run as a strided-batched
         # GEMM, and PyTorch 2.10 + rocm7.0 returns wrong values from that route at some shapes (3 x 2100 x 768 -> 1536, bf16: errors of
         # several units, a memory fault when the result is consumed; tools/dbg_gemm.py) -- the contiguous 2-D GEMM is correct
@@ -708,6 +723,9 @@ class NSAAttention(nn.Module):
         decode steps, concatenated; a failed native call is counted and, unless NSA_HIP_STRICT, falls back to them as well."""
         B, S = self._rows_shape("decode_rows", x)
         self._check_kv(x, kv)
+        if kv.kv_dtype is not None:
+            raise RuntimeError("NSAAttention.decode_rows: this cache carries FP8 mirrors, which only decode_ragged reads and keeps current; "
+                               "decode it with decode_ragged")
         x = self._rows_input("decode_rows", x)
         if not self._native_ok(x):
             return self._decode_rows_steps(x, kv)
@@ -743,13 +761,15 @@ class NSAAttention(nn.Module):
         return y, kv
 
     # ---- ragged batch: every sequence of the batch at its own position (a serving batch) --------------------------------------------------
-    def decode_ragged_plan(self, B: int, S: int, S_max: int, t_max: int, S_sel: int) -> dict:
+    def decode_ragged_plan(self, B: int, S: int, S_max: int, t_max: int, S_sel: int, fp8: bool = False) -> dict:
         """what nsa_layer_decode_ragged does with a shape under the current tuning switches (nsa_layer_decode_ragged_plan, no device call):
         {"launches", "route": 1 the one native call / -1 declined (no native route with per-sequence positions)}.  A t_max beyond the unsplit
         forms of the selected branch is declined unless the tuning switch DECODE_LONG = 1 (the long-row form: up to t_max = 131,071, the same
-        launch count)"""
+        launch count).  fp8: the call over a pool with FP8 mirrors (nsa_layer_decode_ragged_fp8_plan: one launch more, bf16 only, forms 0 / 1
+        whatever DECODE_LONG says)"""
         desc, _ = self._layer_desc()
-        n, r = _plan_ints("nsa_layer_decode_ragged_plan", 2, ctypes.byref(desc), int(B), int(S), int(S_max), int(t_max), int(S_sel))
+        name = "nsa_layer_decode_ragged_fp8_plan" if fp8 else "nsa_layer_decode_ragged_plan"
+        n, r = _plan_ints(name, 2, ctypes.byref(desc), int(B), int(S), int(S_max), int(t_max), int(S_sel))
         return {"launches": n, "route": r}
 
     def decode_ragged(self, x: torch.Tensor, kv: NSA_KV, t_pos, *, t_max: Optional[int] = None):
@@ -763,7 +783,10 @@ class NSAAttention(nn.Module):
         A slot with t_pos[b] < 0 or t_pos[b] + S - 1 > t_max is padding: nothing is written to its slab, its y and ranges rows are zero.
         Monitors: _last_ranges [B,S,G,n,2], _last_gates [B,S,G,3] (gates of a padding slot: unspecified).  Inference only.
         Where the native call declines (nsa_layer_decode_ragged_plan) or the module is in parity mode: with host positions one decode_rows
-        per live sequence on kv.sequence_view(b, t_b); with device positions the native message is raised."""
+        per live sequence on kv.sequence_view(b, t_b); with device positions the native message is raised.
+        A kv with FP8 mirrors (new_kv(..., kv_dtype=torch.float8_e4m3fn)) takes nsa_layer_decode_ragged_fp8: the same appends and ranges, one
+        launch more that mirrors the appended rows in e4m3, and the three branches read the mirrors.  It has no per-sequence route: parity
+        mode raises, a declined shape raises the native message."""
         B, S = self._rows_shape("decode_ragged", x)
         host = None
         if isinstance(t_pos, torch.Tensor):
@@ -791,6 +814,15 @@ class NSAAttention(nn.Module):
         self._check_kv(x, kv)
         x = self._rows_input("decode_ragged", x)
         kv.refresh_meta(t_max + 1)
+        if kv.kv_dtype is not None:
+            if not self._native_ok(x):
+                raise RuntimeError("NSAAttention.decode_ragged: a pool with FP8 mirrors runs the native call only, which does not take this "
+                                   "module or input (parity mode, dtype, gate width)")
+            if host is not None:
+                t_pos = torch.tensor(host, dtype=torch.int32).pin_memory().to(x.device, non_blocking=True)
+            elif not t_pos.is_contiguous():
+                t_pos = t_pos.contiguous()
+            return self._rows_call("decode_ragged_fp8", x, kv, kv.meta, cap, (t_pos.data_ptr(), t_max, S), pre=(ctypes.byref(kv.native_fp8_desc()),)), kv
         if host is not None and (self._force_parity or not self._native_ok(x)
                                  or self.decode_ragged_plan(B, S, cap, t_max, int(kv.meta.S_sel))["route"] < 0):
             return self._decode_ragged_sequences(x, kv, host, t_max)
